@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- SpMM GFLOPS (2*nnz*k/t) of the MI355X-native engine, one process per GPU.
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload amazon] [--k 128]
+    python bench.py [--gpus N --steps K --warmup W] [--workload amazon] [--k 128] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one flex_spmm() over the whole (sharded) matrix with A's plan and B resident
@@ -75,7 +75,16 @@ def parse():
                     help="no GPU, nothing measured: every rank runs the host side of the N-GPU path (same graph, same re-ordering, "
                          "flex_shard_rows, the B broadcast over gloo) and rank 0 prints the JSON line with zeros for the times -- "
                          "what the world_size-8 CPU test drives")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="N=1: after the timed steps, write the C the last step computed as DIR/C.npy (float32) and the indices of its rows "
+                         "as DIR/C_rows.npy (float64) -- every row when they fit in 60 MB, else a fixed seeded sample -- so that two builds "
+                         "can be compared output for output (the inputs depend on the arguments only)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.gpus != 1 or args.dry_run):
+        ap.error("--dump-outputs needs --gpus 1 and a measured run")
+    return args
 
 
 def _under_a_profiler():
@@ -291,6 +300,9 @@ def main():
     ev1.record()
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
+    # what the last timed step computed, taken now: the counter passes launch the plan again and the hipSPARSE side-by-side
+    # below writes its own result into the same C
+    dumped = dump_outputs(args.dump_outputs, C) if args.dump_outputs else None
     if world > 1:
         dist.barrier()
     dev_ms = ev0.elapsed_time(ev1)  # HIP events on the launch stream (torch's current stream)
@@ -507,6 +519,8 @@ def main():
                 out["roofline"]["hbm_copy_GBps_measured"] = round(pr["copy_GBps"], 1)
         if ok is not None:
             out["check"] = ok
+        if dumped is not None:
+            out["outputs"] = dumped
         if world == 1 and not args.no_vendor:
             out["hipsparse"] = side("hipsparse", lambda: vendor_baseline(a, k, B, C))
         if world == 1 and not args.no_cpu_baseline:  # a reported baseline, timed at N=1 only
@@ -515,6 +529,24 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 60_000_000  # --dump-outputs writes at most this much (under 64 MB in all, with the .npy headers)
+
+
+def dump_outputs(d, C):
+    """--dump-outputs: C [m, k] as the caller of the timed path receives it, in DIR/C.npy (float32), and which of its rows those
+    are in DIR/C_rows.npy (float64).  All m rows when they fit DUMP_BYTES; else a sample drawn with a fixed seed from m alone,
+    so that two runs with the same arguments dump the same rows."""
+    import torch
+    m, k = C.shape
+    cap = max(1, DUMP_BYTES // (4 * k + 8))
+    rows = np.arange(m, dtype=np.int64) if m <= cap else np.sort(np.random.default_rng(0).choice(m, size=cap, replace=False))
+    c = C.index_select(0, torch.from_numpy(rows).to(C.device)).cpu().numpy()
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "C.npy"), c)
+    np.save(os.path.join(d, "C_rows.npy"), rows.astype(np.float64))
+    return {"dir": d, "C": list(c.shape), "rows": "all" if m <= cap else f"seeded sample of {len(rows)} of {m}"}
 
 
 def rmat_graph(scale, edge_factor=16, seed=1):
@@ -576,7 +608,9 @@ def dry_run_tail(args, a, k, rank, world, shard, t_gen, t_plan, timings, host_th
         if not ok:
             raise SystemExit("bench --dry-run: the ranks disagree about the shards or about B")
     if world > 1:
-        dist.barrier()
+        # a collective on a host tensor instead of dist.barrier(): barrier() probes for an accelerator, which starts the GPU
+        # runtime in every rank of a run that is meant to leave the GPU alone
+        dist.all_reduce(torch.zeros(1))
         dist.destroy_process_group()
 
 
