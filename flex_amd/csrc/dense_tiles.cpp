@@ -8,6 +8,7 @@
 // (`in_tile[e - e_base] = 1`) and stored as dense fp32 blocks in the A-operand order of v_mfma_f32_32x32x2_f32.
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <new>
 
 #include "host_parallel.h"
@@ -69,6 +70,9 @@ int detect_dense_tiles(const flex_csr *A, int32_t r0, int32_t m, const std::vect
                             const uint32_t c = A->col[e];
                             const int j = static_cast<int>((colpos.empty() ? c : colpos[c]) & 31);
                             if (taken[i][j]) continue;  // a duplicate (row, col) entry stays with the vector kernel
+                            // so does a non-finite value: the tile kernel feeds non-finite B values to the MFMA as 0 and adds their
+                            // share by a masked pass, so an inf of A against an inf of B would meet the 0 first (inf x 0 = NaN)
+                            if (!std::isfinite(A->vals[e])) continue;
                             taken[i][j] = 1;
                             f.mask[i] |= 1u << j;
                             const int kk = j >> 1, lane = i + 32 * (j & 1);

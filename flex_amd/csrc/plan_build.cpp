@@ -22,6 +22,7 @@
 #include <atomic>
 #include <chrono>
 #include <cstdio>
+#include <cmath>
 #include <cstring>
 #include <new>
 #include <numeric>
@@ -795,13 +796,21 @@ class PlanBuilder {
             std::memcpy(&bits, &rval[e], 4);
             return make_uint2(p->off32 ? c * row_bytes32 : c, bits);
         };
-        // Padding behind the last real record `last` of a row: n_pad more records, `stride` apart.  B row = the last real one (always a
-        // valid address).  The padding does not carry value 0 -- 0 x inf would turn a row's +-inf into NaN (the oracle and the reference
-        // have no padding) -- but SHARES the last real record's value: v = v/2 + v/4 + ... + v/2^p + v/2^p, every part exact
-        // (power-of-two scaling), so a non-finite B value contributes what v itself would and a finite one the same product up to the
-        // last rounding.  Values too small to be halved p times without leaving the normal range keep the plain zero padding.
-        auto pad_row = [](uint2 *last, uint32_t n_pad, uint32_t stride) {
+        // Padding behind the `len` real records of a row (or piece, or bundle slot) at `first`, `stride` apart: n_pad more records.
+        // The padding never carries value 0 at a live B row where that could change the row's class -- 0 x inf would turn a row's
+        // +-inf into NaN (the oracle and the reference have no padding) -- but SHARES the value of one real record (c, v), so a
+        // non-finite B row contributes what v itself would and a finite one the same product up to the extra roundings:
+        //   * the last record, v normal and at least 2^(n_pad+1) above the subnormal range: v = v/2 + v/4 + ... + v/2^p + v/2^p, every
+        //     part exact (power-of-two scaling) -- the form of every plan of values of ordinary size;
+        //   * otherwise the last record that allows one of: v = +-inf / NaN / +-0: n_pad copies of (c, v) (the row holds v x B[c]
+        //     already, and adding it again keeps the class: inf + inf, NaN, +-0); v finite with an integer significand of at least
+        //     n_pad + 1 units (every normal value, a subnormal of at least n_pad + 1 units of 2^-149): n_pad + 1 same-sign parts of that
+        //     significand at v's scale, each exact, one of them replacing v;
+        //   * none does (every value a nonzero subnormal of at most n_pad units of 2^-149): (c_last, 0) -- the one residual,
+        //     include/flex_spmm.h.
+        auto pad_row = [](uint2 *first, uint32_t len, uint32_t n_pad, uint32_t stride) {
             if (n_pad == 0) return;
+            uint2 *const last = first + static_cast<size_t>(len - 1) * stride;
             const uint32_t ex = (last->y >> 23) & 0xFFu;  // biased exponent of v
             if (ex > n_pad + 1 && ex < 0xFFu) {
                 float part;
@@ -814,9 +823,32 @@ class PlanBuilder {
                     q->y = bits;
                     q[stride] = make_uint2(q->x, bits);
                 }
-            } else {
-                for (uint32_t i = 1; i <= n_pad; ++i) last[static_cast<size_t>(i) * stride] = make_uint2(last->x, 0u);
+                return;
             }
+            uint2 *const pad = last + stride;
+            for (uint32_t j = len; j-- > 0;) {
+                uint2 *const d = first + static_cast<size_t>(j) * stride;
+                const uint32_t dex = (d->y >> 23) & 0xFFu, man = d->y & 0x7FFFFFu;
+                if (dex == 0xFFu || (dex == 0 && man == 0)) {  // +-inf, NaN, +-0: copies
+                    for (uint32_t i = 0; i < n_pad; ++i) pad[static_cast<size_t>(i) * stride] = *d;
+                    return;
+                }
+                const uint32_t sig = dex ? (man | 0x800000u) : man, parts = n_pad + 1;
+                if (sig >= parts) {  // sig = parts * q + r: r parts of q + 1 units, the rest of q, all at v's scale (exact: < 2^24 units)
+                    const uint32_t q = sig / parts, r = sig % parts, sign = d->y & 0x80000000u;
+                    const int scale = static_cast<int>(dex ? dex : 1u) - 150;
+                    auto part = [&](uint32_t i) {
+                        const float f = std::ldexp(static_cast<float>(q + (i < r ? 1u : 0u)), scale);
+                        uint32_t bits;
+                        std::memcpy(&bits, &f, 4);
+                        return bits | sign;
+                    };
+                    d->y = part(0);
+                    for (uint32_t i = 0; i < n_pad; ++i) pad[static_cast<size_t>(i) * stride] = make_uint2(d->x, part(i + 1));
+                    return;
+                }
+            }
+            for (uint32_t i = 0; i < n_pad; ++i) pad[static_cast<size_t>(i) * stride] = make_uint2(last->x, 0u);
         };
         parallel_chunks((static_cast<int64_t>(n_tasks) + kTaskBlk - 1) / kTaskBlk, [&](int64_t b) {
             for (int64_t t = b * kTaskBlk; t < std::min<int64_t>(n_tasks, (b + 1) * kTaskBlk); ++t) {
@@ -833,7 +865,7 @@ class PlanBuilder {
                             len = pc.end - pc.beg;
                             for (uint32_t j = 0; j < len; ++j) base[static_cast<size_t>(j) * S + s] = record_of(pc.beg + j);
                         }
-                        if (len > 0) pad_row(base + static_cast<size_t>(len - 1) * S + s, ts.steps - len, S);
+                        if (len > 0) pad_row(base + s, len, ts.steps - len, S);
                         else
                             for (uint32_t j = 0; j < ts.steps; ++j) base[static_cast<size_t>(j) * S + s] = make_uint2(base[static_cast<size_t>(j) * S].x, 0u);
                     }
@@ -872,7 +904,7 @@ class PlanBuilder {
                 }
                 // pad to a whole number of steps
                 uint2 *const end = rec.data() + t_beg[t + 1];
-                if (o > base) pad_row(o - 1, static_cast<uint32_t>(end - o), 1u);
+                if (o > base) pad_row(base, static_cast<uint32_t>(o - base), static_cast<uint32_t>(end - o), 1u);
             }
         });
         pcol = std::vector<uint32_t>();

@@ -205,7 +205,13 @@ int flex_set_host_threads(int n);
  * stream changes: no cost for a plan that stays on its stream; conservative -- unrelated work queued behind the plan's
  * launch on the old stream counts as pending too).  Launches captured into a graph are not checked (nor are replays):
  * ordering those is the caller's.  Plans without split rows (flex_plan_info.n_partials == 0) hold no workspace and may
- * overlap freely. */
+ * overlap freely.
+ * Accuracy (tests/f64ref.py): with C64 = the float64 product of the fp32 inputs, S = |A| |B|, u = 2^-24 and
+ * n_r = nnz(row r) + 32, every entry whose C64 is finite is finite and within gamma(n_r) S + n_r 2^-149 of it (gamma(n) = n u / (1 - n u));
+ * every entry whose C64 is not finite is NaN / +inf / -inf exactly as C64 is.  Both hold while no fp32 sum can overflow (S over the
+ * finite terms < 2^120), with one residual: a row -- or a piece of a split row, or a row in a bundle -- whose stored values are ALL
+ * nonzero subnormals of at most p units of 2^-149 each, p = the padding records its task needs (< 64 / lanes_per_nz, or < bundle_len
+ * in a bundle), may give NaN where C64 is +-inf (its padding carries value 0).  Subnormal inputs and results are kept, not flushed. */
 int flex_spmm(flex_plan *plan, const float *dB, float *dC, flex_stream_t stream);
 
 /* ≙ alpha_freeMatGPU (mat.cuh:184-193). */

@@ -1,0 +1,385 @@
+"""A float64 reference of C = A B with an error bound per element, and seeded value scenarios that span the fp32 range.
+
+resCheck (util.assert_matches_oracle) compares against an fp32 CSR-order oracle with a tolerance made for values near 1; it cannot
+judge results that cancel, scaled inputs or subnormals.  This module can:
+
+    C64[r, j] = sum_e a_e b_{c_e, j}      in float64 (every product of two fp32 values is exact there, none overflows)
+    S[r, j]   = sum_e |a_e| |b_{c_e, j}|
+    |C - C64| <= gamma(n_r) S + n_r 2^-149,    gamma(n) = n u / (1 - n u),  u = 2^-24,  n_r = nnz(row r) + P
+
+for every entry whose reference is finite (and C must be finite there), and EXACTLY the reference's class where it is not: NaN where
+C64 is NaN, +inf / -inf with the same sign.  Without fp32 overflow that class does not depend on the order of the sum, so every
+scenario keeps S < 2^120 over its finite terms (asserted).  The second term is the underflow floor: a rounding in the subnormal range
+costs up to half of 2^-149, whatever the magnitudes.
+
+P, the planner's extra roundings.  The engine sums a row as a tree: every record slot of a task runs an fma chain over its records
+(one per step, padding records included), the slots meet in a tree of log2(S) levels (S = 64 / lanes_per_nz <= 16 records per step),
+the partial sums of a split row's pieces (1-D pieces or 2-D column panels) are added in a last pass, and a dense tile's MFMA sum
+meets the vector kernel's in one more addition.  The padding that fills a task's last step splits ONE product into up to
+steps - len + 1 exact parts (plan_build.cpp, pad_row), so sum |terms| is still S[r, j]; what it costs is depth.  A term's error is at
+most gamma(d) |term| with d the roundings on its path to the result, and for a row of n records in q pieces:
+    chain     <= ceil(len_piece / S) <= len_piece   (padding included: a piece's last step holds at most S - 1 of it)
+    tree      <= log2(16) = 4
+    pieces    <= q, and the q pieces hold n records, so len_piece + q <= n + 1
+    product   <= 1 (a product rounded before it is added: the oracle, an MFMA)
+    merges    <= 1 (the tile route's sum and the vector kernel's)
+so d <= n + 7 on a task.  A row bundle has no tree and no pieces: d <= steps + 1 <= bundle_len + 1 <= 17 (bundle_len <= 16 on every
+tile, tests use the rule).  P = 32 covers both with room; the float32 emulation of tests/test_f64_bound.py runs the planner's order
+with it."""
+import numpy as np
+
+from flex_amd import HostCsr
+
+U = 2.0 ** -24
+TINY = 2.0 ** -149     # the smallest fp32 subnormal
+P = 32                 # the planner's extra roundings (derivation above)
+S_LIMIT = 2.0 ** 120   # finite terms of every scenario stay below this: no fp32 overflow anywhere
+
+
+def gamma(n):
+    n = np.asarray(n, dtype=np.float64)
+    return n * U / (1.0 - n * U)
+
+
+def _row_sum(a, terms):
+    """Per-row sums of a (nnz, k) float64 array of terms (rows contiguous as in CSR), IEEE semantics (inf - inf = NaN)."""
+    rp = a.rowPtr.astype(np.int64)
+    out = np.zeros((a.m, terms.shape[1]), dtype=np.float64)
+    nonempty = np.nonzero(np.diff(rp) > 0)[0]
+    if len(nonempty):
+        with np.errstate(invalid="ignore", over="ignore"):
+            out[nonempty] = np.add.reduceat(terms, rp[nonempty], axis=0)
+    return out
+
+
+def spmm_f64(a, B):
+    """C = A B in float64 from the fp32 inputs; stored zeros are multiplied like any value (0 x inf = NaN)."""
+    B64 = np.asarray(B, dtype=np.float32).astype(np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        terms = a.vals.astype(np.float64)[:, None] * B64[a.col.astype(np.int64)]
+    return _row_sum(a, terms)
+
+
+def abs_sum_f64(a, B, finite_only=False):
+    """S = |A| |B| in float64; finite_only: non-finite values of A and B count as 0 (the finite terms' magnitude)."""
+    av = np.abs(a.vals.astype(np.float64))
+    B64 = np.abs(np.asarray(B, dtype=np.float32).astype(np.float64))
+    if finite_only:
+        av = np.where(np.isfinite(av), av, 0.0)
+        B64 = np.where(np.isfinite(B64), B64, 0.0)
+    with np.errstate(invalid="ignore", over="ignore"):
+        terms = av[:, None] * B64[a.col.astype(np.int64)]
+    return _row_sum(a, terms)
+
+
+def f64_bound(a, B, extra=P):
+    nr = np.diff(a.rowPtr.astype(np.int64)) + extra
+    S = abs_sum_f64(a, B)
+    return gamma(nr)[:, None] * S + (nr * TINY)[:, None]
+
+
+def check_f64_bound(a, B, C, route="", extra=P):
+    """None if C passes, else a message naming the worst entry: err / bound, row, column, nnz(row), route."""
+    C = np.asarray(C, dtype=np.float32)
+    assert C.shape == (a.m, B.shape[1]), (C.shape, a.m, B.shape)
+    s_fin = abs_sum_f64(a, B, finite_only=True)
+    assert np.all(s_fin < S_LIMIT), f"scenario leaves the checked range: max S over finite terms {s_fin.max():g} >= 2^120"
+    ref = spmm_f64(a, B)
+    deg = np.diff(a.rowPtr.astype(np.int64))
+    fin = np.isfinite(ref)
+    C64 = C.astype(np.float64)
+    # non-finite reference: exactly the same class
+    nan_ref, pinf_ref, ninf_ref = np.isnan(ref), ref == np.inf, ref == -np.inf
+    bad_class = (nan_ref & ~np.isnan(C64)) | (pinf_ref & (C64 != np.inf)) | (ninf_ref & (C64 != -np.inf))
+    bad_class |= fin & ~np.isfinite(C64)
+    if bad_class.any():
+        r, j = np.argwhere(bad_class)[0]
+        return (f"[{route}] {int(bad_class.sum())} entries of the wrong class; first at row {r} col {j} (nnz(row) {deg[r]}): "
+                f"got {C[r, j]!r}, reference {ref[r, j]!r}")
+    bound = f64_bound(a, B, extra)
+    with np.errstate(invalid="ignore"):
+        ratio = np.where(fin, np.abs(C64 - ref) / bound, 0.0)
+    if ratio.size and ratio.max() > 1.0:
+        r, j = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
+        return (f"[{route}] {int((ratio > 1).sum())} entries beyond the float64 bound; worst err/bound {ratio[r, j]:.3g} at row {r} "
+                f"col {j} (nnz(row) {deg[r]}): got {C[r, j]!r}, reference {ref[r, j]!r}, bound {bound[r, j]:.3g}")
+    return None
+
+
+def assert_within_f64_bound(a, B, C, route="", extra=P):
+    msg = check_f64_bound(a, B, C, route, extra)
+    assert msg is None, msg
+
+
+# ---- scenarios --------------------------------------------------------------------------------------------------------------
+
+def _logu(rng, lo, hi, size):
+    """Random signs, magnitudes 2^U(lo, hi)."""
+    return (rng.choice([-1.0, 1.0], size=size) * np.exp2(rng.uniform(lo, hi, size=size))).astype(np.float32)
+
+
+def _subnormal(rng, size, min_sig=1 << 10):
+    """Random-sign subnormals: integer significand in [min_sig, 2^23) times 2^-149."""
+    return (rng.choice([-1.0, 1.0], size=size) * rng.integers(min_sig, 1 << 23, size=size) * TINY).astype(np.float32)
+
+
+def _pattern(kind, m, rng):
+    """(rowPtr int64, col int64, n).  random: ~9 per row, 10 % empty rows, three long rows (split when the tuning cuts rows),
+    columns unsorted.  block: 32-row diagonal blocks at fill 0.8 plus two random columns per row (dense tiles for the MFMA
+    route, columns with reuse inside a block of rows for the hot-block route)."""
+    n = m
+    if kind == "random":
+        deg = rng.poisson(9, size=m)
+        deg[rng.random(m) < 0.1] = 0
+        deg[3], deg[m // 5], deg[m - 1] = min(400, n), min(200, n), min(97, n)
+        cols = [rng.permutation(n)[:d] for d in deg]
+    elif kind == "block":
+        cols = []
+        for r in range(m):
+            b0 = r // 32 * 32
+            blk = b0 + np.nonzero(rng.random(min(32, n - b0)) < 0.8)[0]
+            noise = rng.integers(0, n, size=2)
+            c = np.unique(np.concatenate([blk, noise]))
+            cols.append(rng.permutation(c))
+    else:
+        raise ValueError(kind)
+    deg = np.array([len(c) for c in cols], dtype=np.int64)
+    rp = np.zeros(m + 1, dtype=np.int64)
+    np.cumsum(deg, out=rp[1:])
+    col = np.concatenate(cols).astype(np.int64) if rp[-1] else np.zeros(0, np.int64)
+    return rp, col, n
+
+
+def _last_of_rows(rp):
+    d = np.diff(rp)
+    return rp[1:][d > 0] - 1
+
+
+def _sc_wide(rng, rp, col, n, k):
+    return _logu(rng, -60, 60, rp[-1]), _logu(rng, -30, 30, (n, k))
+
+
+def _sc_subnormal_A_large_B(rng, rp, col, n, k):
+    return _subnormal(rng, rp[-1]), _logu(rng, 90, 110, (n, k))
+
+
+def _sc_large_A_subnormal_B(rng, rp, col, n, k):
+    return _logu(rng, 90, 110, rp[-1]), _subnormal(rng, (n, k))
+
+
+def _sc_products_underflow(rng, rp, col, n, k):
+    return _logu(rng, -80, -60, rp[-1]), _logu(rng, -90, -68, (n, k))
+
+
+def _sc_huge(rng, rp, col, n, k):
+    vals = (rng.choice([-1.0, 1.0], rp[-1]) * rng.uniform(0.5, 1.0, rp[-1]) * 2.0 ** 60).astype(np.float32)
+    B = (rng.choice([-1.0, 1.0], (n, k)) * rng.uniform(0.5, 1.0, (n, k))).astype(np.float32)
+    a = HostCsr(rp.astype(np.uint32), col.astype(np.uint32), vals, n=n)
+    smax = abs_sum_f64(a, B).max()
+    if smax > 0:  # scale B by a power of two so that the largest S lands in [2^119, 2^120)
+        B = (B.astype(np.float64) * 2.0 ** (119 - int(np.floor(np.log2(smax))))).astype(np.float32)
+    return vals, B
+
+
+def _sc_zeros(rng, rp, col, n, k):
+    vals = rng.uniform(-1, 1, rp[-1]).astype(np.float32)
+    z = rng.random(rp[-1]) < 0.3
+    vals[z] = np.where(rng.random(z.sum()) < 0.5, 0.0, -0.0).astype(np.float32)
+    deg = np.diff(rp)
+    rows = np.nonzero(deg > 0)[0]
+    zero_rows = rows[rng.random(len(rows)) < 0.25]
+    for r in zero_rows:  # every stored value zero, some against a non-finite B row
+        vals[rp[r]:rp[r + 1]] = np.where(rng.random(deg[r]) < 0.5, 0.0, -0.0)
+    B = rng.uniform(-1, 1, (n, k)).astype(np.float32)
+    for r in zero_rows[::3]:
+        B[col[rp[r + 1] - 1], rng.integers(0, k)] = np.inf
+    return vals, B
+
+
+def _sc_nonfinite_A(rng, rp, col, n, k):
+    vals = rng.uniform(-1, 1, rp[-1]).astype(np.float32)
+    pick = rng.random(rp[-1]) < 0.04
+    last = _last_of_rows(rp)
+    pick[last[rng.random(len(last)) < 0.3]] = True  # the record a task's padding is made from
+    vals[pick] = rng.choice(np.array([np.inf, -np.inf, np.nan], np.float32), pick.sum())
+    return vals, rng.uniform(-1, 1, (n, k)).astype(np.float32)
+
+
+def _sc_tiny_vs_inf_B(rng, rp, col, n, k):
+    vals = rng.uniform(-1, 1, rp[-1]).astype(np.float32)
+    B = rng.uniform(-1, 1, (n, k)).astype(np.float32)
+    deg = np.diff(rp)
+    rows = np.nonzero(deg % 2 == 1)[0]  # odd lengths: never a whole number of steps, so every such task is padded
+    rows = rows[rng.random(len(rows)) < 0.3]
+    for i, r in enumerate(rows):
+        e0, e1 = rp[r], rp[r + 1]
+        if i % 2:
+            vals[e0:e1] = _subnormal(rng, e1 - e0)
+        else:
+            vals[e0:e1] = _logu(rng, -122, -118, e1 - e0)
+        c = col[e1 - 1]  # the B row of the record the padding is made from
+        if i % 3 == 0:
+            B[c, :] = np.inf if i % 2 else -np.inf
+        else:
+            B[c, rng.integers(0, k, size=max(1, k // 4))] = np.inf
+    return vals, B
+
+
+def _sc_inf_A_vs_inf_B(rng, rp, col, n, k):
+    vals = rng.uniform(-1, 1, rp[-1]).astype(np.float32)
+    B = rng.uniform(-1, 1, (n, k)).astype(np.float32)
+    pick = np.zeros(rp[-1], bool)
+    last = _last_of_rows(rp)
+    pick[last[rng.random(len(last)) < 0.3]] = True
+    pick |= rng.random(rp[-1]) < 0.02
+    e = np.nonzero(pick)[0]
+    vals[e] = rng.choice(np.array([np.inf, -np.inf], np.float32), len(e))
+    for i, c in enumerate(col[e][::2]):  # half of them meet an inf in B: whole rows and single entries
+        if i % 2:
+            B[c, :] = np.inf
+        else:
+            B[c, rng.integers(0, k)] = -np.inf
+    return vals, B
+
+
+def _sc_nonfinite_B_wide_A(rng, rp, col, n, k):
+    vals = _logu(rng, -60, 60, rp[-1])
+    B = _logu(rng, -30, 30, (n, k))
+    rows = rng.choice(n, size=max(3, n // 20), replace=False)
+    for i, c in enumerate(rows):
+        if i % 3 == 0:
+            B[c, :] = np.inf
+        elif i % 3 == 1:
+            B[c, rng.integers(0, k)] = np.nan
+        else:
+            B[c, rng.integers(0, k, size=max(1, k // 3))] = -np.inf
+    return vals, B
+
+
+def _cancel(rng, m, k):
+    """Rows of (c, v) + (c + h, -v) pairs over B rows c and c + h that hold the same values, and (c, w) + (c, -w) pairs on one
+    column (duplicate columns inside a row); one small leftover term per row, columns unsorted.  Three long rows."""
+    n = m - m % 2
+    h = n // 2
+    deg = rng.poisson(12, size=m)
+    deg[rng.random(m) < 0.1] = 0
+    deg[3], deg[m // 5], deg[m - 1] = 401, 201, 97
+    cols, vals = [], []
+    for d in deg:
+        c, v = [], []
+        for _ in range(d // 2):
+            x = float(rng.uniform(-1, 1) * 2.0 ** rng.integers(-10, 11))
+            i = int(rng.integers(0, h))
+            if rng.random() < 0.25:
+                c += [i, i]
+            else:
+                c += [i, i + h] if rng.random() < 0.5 else [i + h, i]
+            v += [x, -x]
+        if d % 2:
+            c.append(int(rng.integers(0, n)))
+            v.append(float(rng.uniform(-1, 1) * 2.0 ** -20))
+        perm = rng.permutation(len(c))
+        cols.append(np.array(c, np.int64)[perm])
+        vals.append(np.array(v, np.float32)[perm])
+    B = rng.uniform(-1, 1, (n, k)).astype(np.float32)
+    B[h:] = B[:h]
+    rp = np.zeros(m + 1, dtype=np.int64)
+    np.cumsum([len(c) for c in cols], out=rp[1:])
+    return HostCsr(rp.astype(np.uint32), np.concatenate(cols).astype(np.uint32), np.concatenate(vals), n=n), B
+
+
+def _cancel_block(rng, m, k):
+    """"cancel" on the block pattern (dense tiles): B row c + 16 equals B row c in every 32-row block, and a row's entries on two such
+    columns get v and -v; the rest small values."""
+    rp, col, n = _pattern("block", m - m % 32, rng)
+    B = rng.uniform(-1, 1, (n, k)).astype(np.float32)
+    for b0 in range(0, n, 32):
+        B[b0 + 16:b0 + 32] = B[b0:b0 + 16]
+    vals = (rng.uniform(-1, 1, rp[-1]) * 2.0 ** -20).astype(np.float32)
+    for r in range(len(rp) - 1):
+        pos = {int(c): e for e, c in enumerate(col[rp[r]:rp[r + 1]], start=int(rp[r]))}
+        for c, e in pos.items():
+            if c % 32 < 16 and c + 16 in pos:
+                x = np.float32(rng.uniform(-1, 1) * 2.0 ** rng.integers(-10, 11))
+                vals[e], vals[pos[c + 16]] = x, -x
+    return HostCsr(rp.astype(np.uint32), col.astype(np.uint32), vals, n=n), B
+
+
+_VALUES = {
+    "wide": _sc_wide,
+    "subnormal_A_large_B": _sc_subnormal_A_large_B,
+    "large_A_subnormal_B": _sc_large_A_subnormal_B,
+    "products_underflow": _sc_products_underflow,
+    "huge": _sc_huge,
+    "zeros": _sc_zeros,
+    "nonfinite_A": _sc_nonfinite_A,
+    "tiny_vs_inf_B": _sc_tiny_vs_inf_B,
+    "inf_A_vs_inf_B": _sc_inf_A_vs_inf_B,
+    "nonfinite_B_wide_A": _sc_nonfinite_B_wide_A,
+}
+SCENARIOS = ["wide", "subnormal_A_large_B", "large_A_subnormal_B", "products_underflow", "huge", "cancel", "zeros", "nonfinite_A",
+             "tiny_vs_inf_B", "inf_A_vs_inf_B", "nonfinite_B_wide_A"]
+
+
+def scenario(name, k=32, m=512, seed=0, pattern="random"):
+    """(HostCsr, B) of the named scenario, seeded; pattern "random" or "block" (ignored by "cancel", which has its own)."""
+    rng = np.random.default_rng([seed, SCENARIOS.index(name), k, m])
+    if name == "cancel":
+        return _cancel(rng, m, k) if pattern == "random" else _cancel_block(rng, m, k)
+    rp, col, n = _pattern(pattern, m, rng)
+    vals, B = _VALUES[name](rng, rp, col, n, k)
+    return HostCsr(rp.astype(np.uint32), col.astype(np.uint32), np.asarray(vals, np.float32), n=n), np.ascontiguousarray(B, np.float32)
+
+
+def with_uniform_values(a, seed=0):
+    """The same sparsity pattern with uniform(-1, 1) values."""
+    vals = np.random.default_rng(seed).uniform(-1, 1, a.nnz).astype(np.float32)
+    return HostCsr(a.rowPtr, a.col, vals, n=a.n)
+
+
+# ---- routes -----------------------------------------------------------------------------------------------------------------
+# Every way the engine can sum a row, forced by flex_plan_tuning knobs (k picks the column tile; "pattern" the input a route needs:
+# dense 32 x 32 tiles for the MFMA route, columns reused inside a block of rows for the hot-block route).  "ld": strided B / C;
+# "unaligned": B and C one float off 16-byte alignment (the generic kernels); "mapped": a CSR permuted by RCM planned with its map;
+# "shards": three row shards concatenated.
+SPLIT = {"long_row": 24, "piece_records": 16}
+ROUTES = {
+    "flat_g4": {"k": 16, "tuning": {"lanes_per_nz": 4, "bundle": 2}},
+    "flat_g8": {"k": 32, "tuning": {"lanes_per_nz": 8, "bundle": 2}},
+    "flat_g16": {"k": 64, "tuning": {"lanes_per_nz": 16, "bundle": 2}},
+    "flat_g32": {"k": 128, "tuning": {"lanes_per_nz": 32}},
+    "flat_g64": {"k": 256, "tuning": {"lanes_per_nz": 64}},
+    "generic_odd_k": {"k": 7, "tuning": {}},
+    "generic_unaligned": {"k": 32, "tuning": {}, "unaligned": True},
+    "bundles_g4": {"k": 16, "tuning": {"lanes_per_nz": 4, "bundle": 1}},
+    "bundles_g8": {"k": 32, "tuning": {"lanes_per_nz": 8, "bundle": 1}},
+    "bundles_g16": {"k": 64, "tuning": {"lanes_per_nz": 16, "bundle": 1}},
+    "split_rows1": {"k": 32, "tuning": dict(SPLIT, split_rows=1, bundle=2)},
+    "split_rows2": {"k": 32, "tuning": dict(SPLIT, split_rows=2, bundle=1)},
+    "split_g4": {"k": 12, "tuning": dict(SPLIT, split_rows=2, lanes_per_nz=4)},
+    "two_d": {"k": 32, "tuning": {"two_d": 1, "panel_kb": 1}},
+    "far_first": {"k": 32, "tuning": {"far_first": 8}},
+    "order_cluster": {"k": 32, "tuning": {}, "order": 2},
+    "order_rcm": {"k": 64, "tuning": dict(SPLIT), "order": 1},
+    "mapped": {"k": 32, "tuning": {}, "mapped": True},
+    "shards": {"k": 32, "tuning": dict(SPLIT), "shards": 3},
+    "strided": {"k": 20, "tuning": {}, "ld": (28, 24)},
+    "mfma": {"k": 32, "tuning": {"mfma": 1, "mfma_fill_pct": 50}, "pattern": "block"},
+    "mfma_k100": {"k": 100, "tuning": {"mfma": 1, "mfma_fill_pct": 50}, "pattern": "block"},
+    "blocks": {"k": 64, "tuning": {"blocks": 1}, "pattern": "block"},
+}
+
+
+def plan_for_route(route, a):
+    """The plan(s) of `route` for `a`: a list (one plan, or one per row shard)."""
+    import flex_amd
+    spec = ROUTES[route]
+    k, tn = spec["k"], spec["tuning"]
+    if spec.get("mapped"):
+        vo, ap = flex_amd.perm_csr(a, flex_amd.order_rcm(a))
+        return [flex_amd.Plan(ap, k, vo_mp=vo, tuning=tn)]
+    if spec.get("shards"):
+        b = flex_amd.shard_rows(a, k, spec["shards"])
+        return [flex_amd.Plan(a, k, rows=(int(b[i]), int(b[i + 1])), tuning=tn) for i in range(spec["shards"])]
+    ldb, ldc = spec.get("ld", (None, None))
+    return [flex_amd.Plan(a, k, order=spec.get("order", 0), ldb=ldb, ldc=ldc, tuning=tn)]
