@@ -8,6 +8,7 @@ import os
 from . import binding
 
 FLEX_AXW_AUTO, FLEX_AXW_A_XW, FLEX_AXW_AX_W = 0, 1, 2
+FLEX_AXW_USE_BLAS = 0x10000  # flex_axw_create flag: rocBLAS for the dense half
 _lib = None
 
 
@@ -24,8 +25,16 @@ def lib():
         L.flex_axw_run.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.flex_axw_destroy.argtypes = [vp]
         L.flex_axw_ld.argtypes = [C.c_int]
+        L.flex_axw_gemm_launch.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+        L.flex_axw_gemm_launch.restype = C.c_int
         _lib = L
     return _lib
+
+
+def _gemm_launch(L_ptr: int, Wp_ptr: int, Out_ptr: int, n: int, dim: int, c: int, cp: int, n_cus: int, stream: int = 0) -> int:
+    """The MFMA GEMM of the dense half on its own (flex_axw_gemm_launch, exported by libflex_axw.so but not part of
+    flex_axw.h): Out[n x cp] = L[n x dim] @ Wp[dim x cp], columns >= c written as +0.  Returns the hipError_t; for tests."""
+    return lib().flex_axw_gemm_launch(L_ptr, Wp_ptr, Out_ptr, n, dim, c, cp, n_cus, stream)
 
 
 class Axw:

@@ -4,17 +4,20 @@
 #include <hip/hip_runtime.h>
 #include <rocblas/rocblas.h>
 
+#include <cmath>
+#include <cstdint>
 #include <new>
 
 #include "../../include/flex_axw.h"
 
-extern "C" hipError_t flex_axw_gemm_launch(const float *L, const float *Wp, float *Out, int n, int dim, int cp, int n_cus,
+extern "C" hipError_t flex_axw_gemm_launch(const float *L, const float *Wp, float *Out, int n, int dim, int c, int cp, int n_cus,
                                            hipStream_t s);  // axw_kernels.hip
 
 struct flex_axw {
     int32_t n = 0;
     int n_cus = 0;
     bool use_blas = false;  // FLEX_AXW_USE_BLAS in `flags`, or a shape the MFMA kernel does not take (dim % 4 != 0, dim > 256, n < 32)
+    bool a_nonfinite = false;  // A holds an inf or NaN: in order A_XW its SpMM turns the zero padding of X*W into NaN
     int dim = 0, c = 0, cp = 0, device = 0;
     flex_plan *plan_c = nullptr, *plan_dim = nullptr;
     float *d_xw = nullptr;  // n x cp
@@ -30,17 +33,27 @@ namespace {
 
 int hip_fail(hipError_t e) { return e == hipSuccess ? FLEX_OK : (e == hipErrorOutOfMemory ? FLEX_ERR_NOMEM : FLEX_ERR_HIP); }
 
-// C_rm[n x cp] = L_rm[n x dim] * Wp_rm[dim x cp]   <=>   column-major  C^T = Wp^T * L^T
+// Columns c .. cp-1 of an n x cp row-major array := +0.0f
+int zero_padding(flex_axw *h, float *Cout, hipStream_t s) {
+    if (h->c == h->cp) return FLEX_OK;
+    return hip_fail(hipMemset2DAsync(Cout + h->c, static_cast<size_t>(h->cp) * sizeof(float), 0, static_cast<size_t>(h->cp - h->c) * sizeof(float),
+                                     static_cast<size_t>(h->n), s));
+}
+
+// C_rm[n x cp] = L_rm[n x dim] * Wp_rm[dim x cp], columns >= c of C_rm +0.0f   <=>   column-major  C^T = Wp^T * L^T.
+// The MFMA kernel reads L with 16-byte loads: an L that is not 16-byte aligned goes to rocBLAS.  rocBLAS multiplies the c real
+// columns only (0 x inf in Wp's zero columns would be NaN); the padding of the internal X*W was zeroed at create and is never written.
 int gemm_rm(flex_axw *h, const float *L, float *Cout, hipStream_t s) {
-    if (!h->use_blas) return hip_fail(flex_axw_gemm_launch(L, h->d_wp, Cout, h->n, h->dim, h->cp, h->n_cus, s));
+    if (!h->use_blas && (reinterpret_cast<uintptr_t>(L) & 15) == 0)
+        return hip_fail(flex_axw_gemm_launch(L, h->d_wp, Cout, h->n, h->dim, h->c, h->cp, h->n_cus, s));
     const float one = 1.0f, zero = 0.0f;
-    const rocblas_status st = rocblas_sgemm(h->blas, rocblas_operation_none, rocblas_operation_none, h->cp, h->n, h->dim, &one,
+    const rocblas_status st = rocblas_sgemm(h->blas, rocblas_operation_none, rocblas_operation_none, h->c, h->n, h->dim, &one,
                                             h->d_wp, h->cp, L, h->dim, &zero, Cout, h->cp);
     if (st != rocblas_status_success) {
         g_blas_status = static_cast<int>(st);
         return FLEX_ERR_UNSUPPORTED;
     }
-    return FLEX_OK;
+    return Cout == h->d_xw ? FLEX_OK : zero_padding(h, Cout, s);
 }
 
 }  // namespace
@@ -93,6 +106,8 @@ int flex_axw_create(flex_axw **out, const flex_csr *A, int dim, int c, int devic
     if (!rc) rc = hip_fail(hipMalloc(reinterpret_cast<void **>(&h->d_ax), n1 * dim * sizeof(float)));
     if (!rc) rc = hip_fail(hipMalloc(reinterpret_cast<void **>(&h->d_wp), static_cast<size_t>(dim) * h->cp * sizeof(float)));
     if (!rc) rc = hip_fail(hipMemset(h->d_wp, 0, static_cast<size_t>(dim) * h->cp * sizeof(float)));
+    if (!rc) rc = hip_fail(hipMemset(h->d_xw, 0, n1 * h->cp * sizeof(float)));  // its padding columns stay +0 for good
+    for (int64_t e = 0; e < A->nnz && !h->a_nonfinite; ++e) h->a_nonfinite = !std::isfinite(A->vals[e]);
     for (int i = 0; i < 3 && !rc; ++i) rc = hip_fail(hipEventCreate(&h->ev[i]));
     if (!rc && rocblas_create_handle(&h->blas) != rocblas_status_success) rc = FLEX_ERR_UNSUPPORTED;
     if (!rc) {
@@ -131,6 +146,7 @@ int flex_axw_run(flex_axw *h, int order, const float *dX, const float *dW, float
         if (!rc) rc = gemm_rm(h, dX, h->d_xw, s);
         if (!rc) rc = mark(1);
         if (!rc) rc = flex_spmm(h->plan_c, h->d_xw, dOut, stream);
+        if (!rc && h->a_nonfinite) rc = zero_padding(h, dOut, s);  // inf x 0 = NaN in the padding columns; finite A leaves them +0
         if (!rc) rc = mark(2);
     } else {  // run2: cusp.cu:121-178
         if (!rc) rc = flex_spmm(h->plan_dim, dX, h->d_ax, stream);

@@ -8,7 +8,12 @@
 //     4-byte MFMA operands out), so there is no barrier after the first;
 //   * A operand: lane l holds L[row l&31][k = 2kk + (l>>5)], B operand: Wp[k = 2kk + (l>>5)][col l&31]
 //     (cdna guide, 'FP32-input MFMA'); C/D: col = l&31, row = (reg&3) + 8*(reg>>2) + 4*(l>>5);
-//   * the result is bit-for-bit a k-ordered fmaf chain per output element.
+//   * each output element is one fp32 fmaf chain from +0.0f (one rounding per product, subnormals kept), and its k order
+//     is fixed by the operand layout below: k-quad by k-quad, k = 4q, 4q+2, 4q+1, 4q+3 (an MFMA step sums its lane half 0
+//     term, then its lane half 1 term); oracle_axw_gemm_chain restates it and tests/test_gpu_axw.py holds the kernel to it
+//     bit for bit;
+//   * columns c .. cp-1 of Out are stored as +0.0f whatever the inputs (Wp's zero columns times an inf or NaN of L would
+//     otherwise give NaN there).
 // Replaces rocBLAS SGEMM for dim <= 256 (n x 128 x 128: flickr shape 37-42 us against rocBLAS 37-65, reddit shape
 // 79-85 us against 186-207).  On the flickr shape the matrix pipe is 63 % busy (SQ_VALU_MFMA_BUSY_CYCLES): the clock
 // is ~2.0 GHz under this load, the busiest SIMDs carry 3 panels against 2.7 on average, and ~8 us of launch, W staging,
@@ -41,7 +46,7 @@ constexpr int kWaves = 8;
 
 template <int NT>  // 32-column output tiles per wave and pass (1..4)
 __global__ __launch_bounds__(64 * kWaves) void axw_gemm_kernel(const float *__restrict__ L, const float *__restrict__ Wp,
-                                                               float *__restrict__ Out, int n, int dim, int cp, int col0) {
+                                                               float *__restrict__ Out, int n, int dim, int c, int cp, int col0) {
     extern __shared__ float smem[];
     constexpr int WC = 32 * NT;          // columns of this pass
     constexpr int xs = kSlab + kPad;     // floats per staged row
@@ -149,6 +154,15 @@ __global__ __launch_bounds__(64 * kWaves) void axw_gemm_kernel(const float *__re
             }
         }
         // C/D layout: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
+        // padding columns are +0, not 0 x inf: cleared in place, and only in a tile that holds some (a wave-uniform test), so that the
+        // stores of a full tile are the plain ones (a select into a temporary ahead of each store serialised them: reddit shape +12 %)
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+            if (col0 + t * 32 + 32 > c) {
+                const bool pad = col0 + t * 32 + (lane & 31) >= c;
+#pragma unroll
+                for (int reg = 0; reg < 16; ++reg) acc[t][reg] = pad ? 0.0f : acc[t][reg];
+            }
         float *dst = Out + static_cast<size_t>(r0 + 4 * (lane >> 5)) * cp + col0 + (lane & 31);
 #pragma unroll
         for (int t = 0; t < NT; ++t)
@@ -160,11 +174,17 @@ __global__ __launch_bounds__(64 * kWaves) void axw_gemm_kernel(const float *__re
 
 }  // namespace flex_axw_detail
 
-// Out[n x cp] = L[n x dim] * Wp[dim x cp].  Requires n >= 32, dim % 4 == 0, dim <= 256, cp % 32 == 0.  Returns hipSuccess or
-// the launch error.  The pass width is what keeps Wp's slice within 64 KiB of LDS: 128 columns up to dim = 128, 64 beyond.
-extern "C" hipError_t flex_axw_gemm_launch(const float *L, const float *Wp, float *Out, int n, int dim, int cp, int n_cus, hipStream_t s) {
+// Out[n x cp] = L[n x dim] * Wp[dim x cp], columns c .. cp-1 of Out written as +0.0f.  Takes n >= 32, dim % 4 == 0, 0 < dim <= 256,
+// cp % 32 == 0, 0 < c <= cp, n_cus > 0 and 16-byte aligned L and Wp (the loads are 16 bytes wide and the last panel starts at row
+// n - 32); anything else returns hipErrorInvalidValue before a launch.  Returns hipSuccess or the launch error.  The pass width is
+// what keeps Wp's slice within 64 KiB of LDS: 128 columns up to dim = 128, 64 beyond.
+extern "C" hipError_t flex_axw_gemm_launch(const float *L, const float *Wp, float *Out, int n, int dim, int c, int cp, int n_cus,
+                                           hipStream_t s) {
     using namespace flex_axw_detail;
-    if (n <= 0) return hipSuccess;
+    const auto misaligned = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
+    if (!L || !Wp || !Out || n < kRowsPerWave || dim <= 0 || dim % 4 != 0 || dim > 256 || cp <= 0 || cp % 32 != 0 || c <= 0 || c > cp ||
+        n_cus <= 0 || misaligned(L) || misaligned(Wp))
+        return hipErrorInvalidValue;
     const int max_cols = dim <= 128 ? 128 : 64;
     for (int col0 = 0; col0 < cp; col0 += max_cols) {
         const int nt = std::min(max_cols, cp - col0) / 32;
@@ -174,7 +194,7 @@ extern "C" hipError_t flex_axw_gemm_launch(const float *L, const float *Wp, floa
         auto go = [&](auto kernel) {  // more than 64 KiB of dynamic LDS has to be asked for
             e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
             if (e != hipSuccess) return;
-            hipLaunchKernelGGL(kernel, grid, block, lds, s, L, Wp, Out, n, dim, cp, col0);
+            hipLaunchKernelGGL(kernel, grid, block, lds, s, L, Wp, Out, n, dim, c, cp, col0);
             e = hipGetLastError();
         };
         switch (nt) {

@@ -5,8 +5,8 @@
  * ≙ run1 / run2 of cusp.cu (3-104, 106-208), the AXW block of main.cu:22-77 (compiled out in the
  * reference: `//#define AXW 1`):  run1 = A*(X*W): SGEMM then SpMM at k = c;  run2 = (A*X)*W: SpMM at
  * k = dim then SGEMM.  Here the SpMM is the engine's (flex_spmm, a plan per width) instead of
- * cusparseSpMM, the dense product is a hand-written fp32 MFMA kernel for dim <= 128 (axw_kernels.hip;
- * rocBLAS SGEMM for other widths), and all dense operands are ROW-major (the reference's are
+ * cusparseSpMM, the dense product is a hand-written fp32 MFMA kernel for dim <= 256, dim % 4 == 0 and n >= 32
+ * (axw_kernels.hip; rocBLAS SGEMM for other shapes), and all dense operands are ROW-major (the reference's are
  * column-major, cusp.cu:31-32, 55-60) so that they chain with flex_spmm without a transpose.
  * Kept in its own library: the engine (libflex_spmm.so) never depends on rocBLAS.
  */
@@ -27,7 +27,7 @@ typedef struct flex_axw flex_axw;
 /* Leading dimension of Out and of the X*W intermediate: c rounded up to a multiple of 32 floats, so
  * that every row is a whole number of 128-byte cache lines (a row that starts mid-line costs each
  * gather one extra line: k=100 runs 50 % slower than k=128 on the reddit shape); the extra columns
- * come out as zeros. */
+ * come out as +0.0f, whatever the inputs hold (inf and NaN included). */
 int flex_axw_ld(int c);
 
 /* Plans A once per SpMM width (k = flex_axw_ld(c) and k = dim) and allocates the intermediates
@@ -37,7 +37,21 @@ int flex_axw_create(flex_axw **out, const flex_csr *hostA, int dim, int c, int d
 
 /* Out[n x flex_axw_ld(c)] = A * dX[n x dim] * dW[dim x c], all device, row-major, fp32, on `stream`.
  * order: FLEX_AXW_*.  gemm_ms / spmm_ms (or NULL): device time of the two stages of THIS call; asking
- * for them makes the call synchronise.  ≙ Metrics.gemm_t / spmm_t (common.h:14-36). */
+ * for them makes the call synchronise.  ≙ Metrics.gemm_t / spmm_t (common.h:14-36).
+ * dX may have any 4-byte alignment: in order FLEX_AXW_A_XW an X that is not 16-byte aligned is multiplied
+ * by rocBLAS (the MFMA kernel loads 16 bytes at a time), correct and slower.
+ * Accuracy (tests/f64ref.py): let u = 2^-24, gamma(m) = m u / (1 - m u), n_r = nnz(row r) + 32 (flex_spmm's
+ * bound) and S = |A| (|X| |W|).  Every entry whose float64 reference (the product of the fp32 inputs in the
+ * association order of the call: A (X W) for FLEX_AXW_A_XW, (A X) W for FLEX_AXW_AX_W) is finite is finite and
+ *     |Out - ref| <= gamma(n_r + dim) S + 2^-149 (n_r + dim) (1 + sum_s |A_rs| + sum_k |W_kj|);
+ * the SpMM's gamma(n_r) and the dense product's gamma(dim) compose as gamma(a) + gamma(b) + gamma(a) gamma(b)
+ * <= gamma(a + b).  Every other entry is NaN / +inf / -inf exactly as that reference is (the two orders can
+ * differ: X[s,k] = 0 against W[k,j] = inf is NaN in A (X W) and may be inf in (A X) W).  Both hold while no
+ * stage's fp32 sum can overflow (its sum of finite |terms| < 2^120) and no finite intermediate that fp32 may
+ * round to zero or to the other sign meets an inf or NaN in the next stage.  The MFMA GEMM is one fp32 fmaf
+ * chain per entry in a fixed k order (axw_kernels.hip), bit for bit, signed zeros included; Out's padding
+ * columns are +0.0f in every case.  Subnormal inputs and results are kept on both GEMM paths (rocBLAS included,
+ * at the shapes tests/test_gpu_axw.py runs).  No residual is known. */
 int flex_axw_run(flex_axw *h, int order, const float *dX, const float *dW, float *dOut, flex_stream_t stream,
                  float *gemm_ms, float *spmm_ms);
 int flex_axw_destroy(flex_axw *h);

@@ -52,6 +52,8 @@ def lib():
         L.oracle_gen_B.argtypes = [C.c_int64, C.c_int, f32p, C.c_int]
         L.oracle_spmm.argtypes = [C.c_int64, u32p, u32p, f32p, f32p, f32p, C.c_int]
         L.oracle_spmm_mt.argtypes = [C.c_int64, u32p, u32p, f32p, f32p, f32p, C.c_int, C.c_int]
+        L.oracle_axw_gemm_chain.argtypes = [f32p, f32p, f32p, C.c_int64, C.c_int, C.c_int, C.c_int]
+        L.oracle_axw_gemm_chain.restype = C.c_int
         L.oracle_rescheck.argtypes = [f32p, f32p, u32p, C.c_int64, C.c_int,
                                       C.POINTER(C.c_double), i32p, C.POINTER(C.c_int64)]
         L.oracle_rescheck.restype = C.c_int64
@@ -128,6 +130,20 @@ def spmm(rowPtr, col, vals, B, nthreads: int = 1) -> np.ndarray:
         lib().oracle_spmm(m, _p(rowPtr, C.c_uint32), _p(col, C.c_uint32), _p(vals, C.c_float),
                           _p(B, C.c_float), _p(Cm, C.c_float), k)
     return Cm
+
+
+def axw_gemm_chain(L, Wp, nthreads: int = 1) -> np.ndarray:
+    """L [n, dim] @ Wp [dim, cp] as the A*X*W MFMA kernel sums it: one fp32 fmaf chain per entry from +0.0f,
+    k = 4q, 4q+2, 4q+1, 4q+3 quad by quad (flex_oracle.h).  dim must be a multiple of 4."""
+    L, Wp = _f32(L), _f32(Wp)
+    n, dim = L.shape
+    assert Wp.shape[0] == dim, (L.shape, Wp.shape)
+    cp = Wp.shape[1]
+    out = np.empty((n, cp), dtype=np.float32)
+    rc = lib().oracle_axw_gemm_chain(_p(L, C.c_float), _p(Wp, C.c_float), _p(out, C.c_float), n, dim, cp, nthreads)
+    if rc:
+        raise ValueError(f"oracle_axw_gemm_chain(n={n}, dim={dim}, cp={cp}) failed: {rc}")
+    return out
 
 
 def rescheck(gold, res, orig_rowPtr):

@@ -247,6 +247,51 @@ void oracle_spmm_mt(int64_t m, const uint32_t *rowPtr, const uint32_t *col, cons
     free(th); free(args);
 }
 
+/* ------------------------------------------------- A*X*W: the MFMA GEMM's chain */
+
+typedef struct {
+    int64_t r0, r1;
+    const float *L, *Wp;
+    float *Out;
+    int dim, cp;
+} gemm_arg;
+
+static void *gemm_run(void *p) {
+    const gemm_arg *a = (const gemm_arg *)p;
+    for (int64_t r = a->r0; r < a->r1; ++r) {
+        const float *l = a->L + r * a->dim;
+        for (int j = 0; j < a->cp; ++j) {
+            const float *w = a->Wp + j;
+            float acc = 0.0f;
+            for (int q = 0; q < a->dim; q += 4) { /* k = 4q', 4q'+2, 4q'+1, 4q'+3 */
+                acc = fmaf(l[q], w[(int64_t)q * a->cp], acc);
+                acc = fmaf(l[q + 2], w[(int64_t)(q + 2) * a->cp], acc);
+                acc = fmaf(l[q + 1], w[(int64_t)(q + 1) * a->cp], acc);
+                acc = fmaf(l[q + 3], w[(int64_t)(q + 3) * a->cp], acc);
+            }
+            a->Out[r * a->cp + j] = acc;
+        }
+    }
+    return NULL;
+}
+
+int oracle_axw_gemm_chain(const float *L, const float *Wp, float *Out, int64_t n, int dim, int cp, int nthreads) {
+    if (n < 0 || dim <= 0 || dim % 4 != 0 || cp <= 0) return -EINVAL;
+    if (nthreads < 1 || n < nthreads) nthreads = 1;
+    pthread_t *th = (pthread_t *)malloc(sizeof(pthread_t) * (size_t)nthreads);
+    gemm_arg *args = (gemm_arg *)malloc(sizeof(gemm_arg) * (size_t)nthreads);
+    if (!th || !args) { free(th); free(args); return -ENOMEM; }
+    for (int t = 0; t < nthreads; ++t) { /* equal contiguous row chunks: every row costs the same */
+        args[t] = (gemm_arg){n * t / nthreads, n * (t + 1) / nthreads, L, Wp, Out, dim, cp};
+        if (nthreads == 1) gemm_run(&args[t]);
+        else pthread_create(&th[t], NULL, gemm_run, &args[t]);
+    }
+    if (nthreads > 1)
+        for (int t = 0; t < nthreads; ++t) pthread_join(th[t], NULL);
+    free(th); free(args);
+    return 0;
+}
+
 /* ---------------------------------------------------------------- resCheck */
 
 int64_t oracle_rescheck(const float *gold, const float *res, const uint32_t *orig_rowPtr,

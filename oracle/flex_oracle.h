@@ -65,6 +65,13 @@ void oracle_spmm(int64_t m, const uint32_t *rowPtr, const uint32_t *col,
 void oracle_spmm_mt(int64_t m, const uint32_t *rowPtr, const uint32_t *col,
                     const float *vals, const float *B, float *C, int k, int nthreads);
 
+/* The dense half of A*X*W as flex_amd/csrc/axw_kernels.hip computes it (no reference counterpart: the
+ * reference calls cuBLAS).  Out[n x cp] = L[n x dim] * Wp[dim x cp], row-major, each entry ONE fp32 fmaf
+ * chain from +0.0f in the kernel's k order: k-quad by k-quad, k = 4q, 4q+2, 4q+1, 4q+3.  Every column of
+ * Wp is summed (the kernel's +0 store of padding columns is not restated).  Rows are cut into nthreads
+ * contiguous chunks as in oracle_spmm_mt.  Returns 0, or -EINVAL unless dim % 4 == 0, dim > 0, cp > 0. */
+int oracle_axw_gemm_chain(const float *L, const float *Wp, float *Out, int64_t n, int dim, int cp, int nthreads);
+
 /* resCheck, flex.cu:4154-4213.  row_nnz comes from the ORIGINAL ordering's rowPtr.
  * Returns the mismatch count; writes max error, nnz of the max-error row, and the
  * number of exactly-zero gold elements. */

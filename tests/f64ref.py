@@ -367,6 +367,20 @@ ROUTES = {
     "mfma": {"k": 32, "tuning": {"mfma": 1, "mfma_fill_pct": 50}, "pattern": "block"},
     "mfma_k100": {"k": 100, "tuning": {"mfma": 1, "mfma_fill_pct": 50}, "pattern": "block"},
     "blocks": {"k": 64, "tuning": {"blocks": 1}, "pattern": "block"},
+    # launch and grid-decode variants: the grouped 1-D grid (tile_group) with its short last group, the unroll-8 narrow tiles, the
+    # dealt XCD stretches, non-temporal record loads with an occupancy throttle; "stamped": through flex_plan_measure_imbalance (the
+    # stamped twin of the vector kernel, then the split-row fix-up and the MFMA tiles), which must leave the ordinary result in C.
+    # "m": rows of the scenario where 512 does not reach the route: the XCD slices of the grouped grid end in a short group of 3 at
+    # these sizes, and stretches are dealt only from 256 chunks on.
+    "tile_group_g16": {"k": 128, "tuning": {"lanes_per_nz": 16, "tile_group": 3}},
+    "tile_group_rcm": {"k": 128, "tuning": {"lanes_per_nz": 16, "tile_group": 3}, "order": 1, "m": 448},
+    "tile_group_split": {"k": 128, "tuning": dict(SPLIT, lanes_per_nz=16, tile_group=3, split_rows=1), "m": 640},
+    "unroll8_g8": {"k": 32, "tuning": {"unroll": 8}},
+    "unroll8_g16": {"k": 64, "tuning": {"unroll": 8}},
+    "xcd_dealt": {"k": 32, "tuning": {"xcd_slices": 3, "xcd_stretch": 1}, "m": 2048},
+    "rec_nt_lds": {"k": 64, "tuning": {"rec_nt": 1, "lds_extra": 16384}},
+    "stamped": {"k": 128, "tuning": dict(SPLIT, split_rows=1), "stamped": True},
+    "stamped_g4": {"k": 16, "tuning": dict(SPLIT, lanes_per_nz=4, split_rows=2), "stamped": True},
 }
 
 
@@ -383,3 +397,288 @@ def plan_for_route(route, a):
         return [flex_amd.Plan(a, k, rows=(int(b[i]), int(b[i + 1])), tuning=tn) for i in range(spec["shards"])]
     ldb, ldc = spec.get("ld", (None, None))
     return [flex_amd.Plan(a, k, order=spec.get("order", 0), ldb=ldb, ldc=ldc, tuning=tn)]
+
+
+# ---- A*X*W (libflex_axw.so) -----------------------------------------------------------------------------------------------------
+# Out = A X W in either association order (include/flex_axw.h).  The float64 reference follows the order of the call, since non-finite
+# classes can differ between the orders: X[s,k] = 0 against W[k,j] = inf gives NaN in A (X W), and +-inf in (A X) W when another neighbour
+# of the row carries a nonzero in column k.  The bound composes flex_spmm's with that of a length-dim dot product:
+#
+#   GEMM   Y = fl(L W):    |Y - L W| <= gamma(dim) |L||W| + dim 2^-149    (an fp32 dot product of dim terms, fma or mul + add, in any
+#                                                                          order; each rounding in the subnormal range costs < 2^-149)
+#   SpMM   C = fl(A B):    |C - A B| <= gamma(n_r) |A||B| + n_r 2^-149,   n_r = nnz(row r) + P   (above)
+#
+# A (X W): |Out - A X W| <= |A| |Y - X W| + |fl(A Y) - A Y|
+#                         <= gamma(dim) S + dim 2^-149 sum_s |A_rs| + gamma(n_r) |A| |Y| + n_r 2^-149,
+#          and |A||Y| <= (1 + gamma(dim)) S + dim 2^-149 sum_s |A_rs|, with S = |A| (|X| |W|), so
+#          |Out - ref| <= (gamma(n_r) + gamma(dim) + gamma(n_r) gamma(dim)) S + 2^-149 (n_r + dim (1 + gamma(n_r)) sum_s |A_rs|).
+# (A X) W: the same with the stages swapped: (gamma(n_r) + gamma(dim) + gamma(n_r) gamma(dim)) S + 2^-149 (dim + n_r (1 + gamma(dim)) sum_k |W_kj|).
+# gamma(a) + gamma(b) + gamma(a) gamma(b) <= gamma(a + b), and (1 + gamma) <= 2 while every n u < 1/2, so both are covered by
+#
+#   |Out - ref| <= gamma(n_r + dim) S + 2^-149 (n_r + dim) (1 + sum_s |A_rs| + sum_k |W_kj|)
+#
+# for every entry whose reference is finite; every other entry must be of exactly the reference's class.  Two range guards keep that
+# class argument sound, and the checker asserts both, as S_LIMIT above: every stage's sum of finite |terms| stays below 2^120 (no fp32
+# overflow), and no finite intermediate of the first stage that fp32 may round to zero or to the other sign -- nonzero terms and
+# |Y64| <= its stage bound, or |Y64| < 2^-126 -- meets an inf or NaN operand of the second stage (fp32 would give inf x 0 = NaN or an inf
+# of the other sign there without being wrong).  The padding columns c .. cp-1 of Out must be +0.0 bit for bit.
+
+NORMAL_MIN = 2.0 ** -126
+
+
+def gemm_f64(L, W):
+    """L @ W in float64 by an explicit multiply-add over k, so 0 x inf = NaN is kept (a BLAS dgemm may skip zero operands).  fp32 inputs
+    give exact products."""
+    L, W = np.asarray(L, np.float64), np.asarray(W, np.float64)
+    out = np.zeros((L.shape[0], W.shape[1]), dtype=np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for k in range(L.shape[1]):
+            out += L[:, k, None] * W[None, k, :]
+    return out
+
+
+def spmm64(a, B, absolute=False):
+    """A B in float64 with B kept in float64 (an intermediate of the other stage is not rounded to fp32); absolute: |A| |B|.  Rows in
+    chunks of about 2^24 terms, so that n = 60 000 at k = 260 fits in memory."""
+    B = np.asarray(B, np.float64)
+    vals = a.vals.astype(np.float64)
+    if absolute:
+        vals, B = np.abs(vals), np.abs(B)
+    rp = a.rowPtr.astype(np.int64)
+    col = a.col.astype(np.int64)
+    out = np.zeros((a.m, B.shape[1]), dtype=np.float64)
+    step = max(1, (1 << 24) // max(1, B.shape[1]))
+    r0 = 0
+    while r0 < a.m:
+        r1 = int(np.searchsorted(rp, rp[r0] + step, side="right")) - 1
+        r1 = min(a.m, max(r1, r0 + 1))
+        e0, e1 = rp[r0], rp[r1]
+        if e1 > e0:
+            with np.errstate(invalid="ignore", over="ignore"):
+                terms = vals[e0:e1, None] * B[col[e0:e1]]
+            d = np.diff(rp[r0:r1 + 1])
+            nonempty = np.nonzero(d > 0)[0]
+            with np.errstate(invalid="ignore", over="ignore"):
+                out[r0 + nonempty] = np.add.reduceat(terms, (rp[r0:r1] - e0)[nonempty], axis=0)
+        r0 = r1
+    return out
+
+
+A_XW, AX_W = 1, 2  # FLEX_AXW_A_XW, FLEX_AXW_AX_W
+
+
+def axw_f64(a, X, W, order):
+    """float64 A (X W) (order A_XW) or (A X) W (order AX_W) of the fp32 inputs: n x c."""
+    return spmm64(a, gemm_f64(X, W)) if order == A_XW else gemm_f64(spmm64(a, X), W)
+
+
+def gemm_bound(L, W):
+    """gamma(dim) |L||W| + dim 2^-149: the bound of one fp32 dot product of length dim, per entry."""
+    dim = L.shape[1]
+    with np.errstate(invalid="ignore", over="ignore"):
+        return gamma(dim) * gemm_f64(np.abs(L), np.abs(W)) + dim * TINY
+
+
+def axw_bound(a, X, W, extra=P):
+    dim = X.shape[1]
+    nr = np.diff(a.rowPtr.astype(np.int64)) + extra
+    with np.errstate(invalid="ignore", over="ignore"):
+        S = spmm64(a, gemm_f64(np.abs(X), np.abs(W)), absolute=True)
+        a_sum = spmm64(a, np.ones((a.n, 1)), absolute=True)[:, 0]
+        w_sum = np.abs(np.asarray(W, np.float64)).sum(axis=0)
+    m = (nr + dim).astype(np.float64)
+    return gamma(m)[:, None] * S + TINY * m[:, None] * (1.0 + a_sum[:, None] + w_sum[None, :])
+
+
+def _finite(x):
+    x = np.asarray(x, np.float64)
+    return np.where(np.isfinite(x), np.abs(x), 0.0)
+
+
+def axw_range_guard(a, X, W, order, extra=P):
+    """None if (a, X, W) lies in the range where the composed bound and exact classes hold for `order`, else why not."""
+    Xf, Wf = _finite(X), _finite(W)
+    af = HostCsr(a.rowPtr, a.col, np.where(np.isfinite(a.vals), np.abs(a.vals), 0).astype(np.float32), n=a.n)
+    s_xw = gemm_f64(Xf, Wf)
+    for what, s in (("|X||W|", s_xw), ("|A||X|", spmm64(af, Xf)), ("|A||X||W|", spmm64(af, s_xw))):
+        if s.size and s.max() >= S_LIMIT:
+            return f"stage sum {what} reaches {s.max():g} >= 2^120: fp32 may overflow"
+    dim = X.shape[1]
+    with np.errstate(invalid="ignore", over="ignore"):
+        if order == A_XW:
+            inter, s1 = gemm_f64(X, W), gemm_f64(np.abs(X), np.abs(W))
+            b1 = gamma(dim) * s1 + dim * TINY
+        else:
+            inter, s1 = spmm64(a, X), spmm64(a, X, absolute=True)
+            nr = (np.diff(a.rowPtr.astype(np.int64)) + extra)[:, None]
+            b1 = gamma(nr) * s1 + nr * TINY
+        ai = np.abs(inter)
+        unsafe = np.isfinite(inter) & (s1 > 0) & ~((ai > b1) & (ai >= NORMAL_MIN))
+    if order == A_XW:  # Y[s, :] meets A[r, s]
+        bad_s = np.unique(a.col[~np.isfinite(a.vals)].astype(np.int64))
+        hit = unsafe[bad_s].any(axis=1) if len(bad_s) else np.zeros(0, bool)
+        if hit.any():
+            return f"X W row {bad_s[np.argmax(hit)]} holds a value fp32 may flush or flip, and meets an inf / NaN of A"
+    else:  # Z[r, k] meets W[k, :]
+        bad_k = ~np.isfinite(np.asarray(W, np.float32)).all(axis=1)
+        hit = unsafe[:, bad_k]
+        if hit.any():
+            return f"A X holds {int(hit.sum())} values fp32 may flush or flip that meet an inf / NaN row of W"
+    return None
+
+
+def _class_mismatch(ref, got):
+    nan_ref, pinf_ref, ninf_ref = np.isnan(ref), ref == np.inf, ref == -np.inf
+    bad = (nan_ref & ~np.isnan(got)) | (pinf_ref & (got != np.inf)) | (ninf_ref & (got != -np.inf))
+    return bad | (np.isfinite(ref) & ~np.isfinite(got))
+
+
+def axw_reference(a, X, W, order, route="", extra=P):
+    """(float64 reference, composed bound) of `order`, after asserting the range guards; reusable across runs of one input."""
+    guard = axw_range_guard(a, X, W, order, extra)
+    assert guard is None, f"[{route}] scenario leaves the checked range: {guard}"
+    return axw_f64(a, X, W, order), axw_bound(a, X, W, extra)
+
+
+def check_axw(a, X, W, Out, order, route="", extra=P, ref=None):
+    """None if Out (n x c, or n x cp with the padding columns) passes for `order`, else a message naming the first failure.
+    ref: axw_reference(a, X, W, order) if already computed."""
+    Out = np.asarray(Out, np.float32)
+    c = W.shape[1]
+    assert Out.shape[0] == a.m and Out.shape[1] >= c, (Out.shape, a.m, c)
+    ref, bound = ref if ref is not None else axw_reference(a, X, W, order, route, extra)
+    if Out.shape[1] > c:
+        pad = np.ascontiguousarray(Out[:, c:]).view(np.uint32)
+        if pad.any():
+            r, j = np.argwhere(pad != 0)[0]
+            return (f"[{route}] {int((pad != 0).sum())} padding entries are not +0.0; first at row {r} col {c + j}: "
+                    f"{Out[r, c + j]!r}")
+    got = Out[:, :c].astype(np.float64)
+    deg = np.diff(a.rowPtr.astype(np.int64))
+    bad = _class_mismatch(ref, got)
+    if bad.any():
+        r, j = np.argwhere(bad)[0]
+        return (f"[{route}] {int(bad.sum())} entries of the wrong class; first at row {r} col {j} (nnz(row) {deg[r]}): "
+                f"got {got[r, j]!r}, reference {ref[r, j]!r}")
+    fin = np.isfinite(ref)
+    with np.errstate(invalid="ignore"):
+        ratio = np.where(fin, np.abs(got - ref) / bound, 0.0)
+    if ratio.size and ratio.max() > 1.0:
+        r, j = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
+        return (f"[{route}] {int((ratio > 1).sum())} entries beyond the composed float64 bound; worst err/bound {ratio[r, j]:.3g} at row "
+                f"{r} col {j} (nnz(row) {deg[r]}): got {got[r, j]!r}, reference {ref[r, j]!r}, bound {bound[r, j]:.3g}")
+    return None
+
+
+def assert_axw_within_bound(a, X, W, Out, order, route="", extra=P, ref=None):
+    msg = check_axw(a, X, W, Out, order, route, extra, ref)
+    assert msg is None, msg
+
+
+def check_gemm_bound(L, W, Out):
+    """None if Out (= L W in fp32, n x c) is within gamma(dim) |L||W| + dim 2^-149 of the float64 product, classes exact; else a message."""
+    ref = gemm_f64(L, W)
+    got = np.asarray(Out, np.float32).astype(np.float64)
+    bad = _class_mismatch(ref, got)
+    if bad.any():
+        r, j = np.argwhere(bad)[0]
+        return f"{int(bad.sum())} entries of the wrong class; first at ({r}, {j}): got {got[r, j]!r}, reference {ref[r, j]!r}"
+    with np.errstate(invalid="ignore"):
+        ratio = np.where(np.isfinite(ref), np.abs(got - ref) / gemm_bound(L, W), 0.0)
+    if ratio.size and ratio.max() > 1.0:
+        r, j = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
+        return f"entry ({r}, {j}) beyond the GEMM bound: err/bound {ratio[r, j]:.3g}, got {got[r, j]!r}, reference {ref[r, j]!r}"
+    return None
+
+
+# ---- A*X*W value scenarios: (A, X, W), seeded -----------------------------------------------------------------------------------
+
+def _axw_pattern(rng, n):
+    """rowPtr, col of an n x n graph: Poisson(6) per row, 10 % empty rows, two long rows; columns unsorted, repeats allowed."""
+    deg = rng.poisson(6, size=n)
+    deg[rng.random(n) < 0.1] = 0
+    deg[n // 3] = min(300, 4 * n)
+    deg[n - 1] = min(97, 3 * n)
+    rp = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(deg, out=rp[1:])
+    return rp, rng.integers(0, n, size=rp[-1]).astype(np.int64)
+
+
+def _u(rng, lo, hi, size):
+    return rng.uniform(lo, hi, size).astype(np.float32)
+
+
+def _sprinkle(rng, x, frac, values=(np.inf, -np.inf, np.nan)):
+    x = x.copy()
+    flat = x.reshape(-1)
+    pick = rng.random(flat.size) < frac
+    if flat.size:
+        pick[rng.integers(0, flat.size)] = True  # at least one
+    flat[pick] = rng.choice(np.array(values, np.float32), pick.sum())
+    return x
+
+
+def _axw_values(name, rng, nnz, n, dim, c):
+    if name == "uniform":
+        return _u(rng, -1, 1, nnz), _u(rng, -1, 1, (n, dim)), _u(rng, -1, 1, (dim, c))
+    if name == "wide":
+        return _logu(rng, -20, 20, nnz), _logu(rng, -30, 30, (n, dim)), _logu(rng, -30, 30, (dim, c))
+    if name == "subnormal_X_large_W":  # the products X W are normal: a kernel that flushed X would return 0
+        return _u(rng, -1, 1, nnz), _subnormal(rng, (n, dim)), _logu(rng, 90, 110, (dim, c))
+    if name == "large_X_subnormal_W":
+        return _u(rng, -1, 1, nnz), _logu(rng, 90, 110, (n, dim)), _subnormal(rng, (dim, c))
+    if name == "products_underflow":
+        return _u(rng, -1, 1, nnz), _logu(rng, -80, -60, (n, dim)), _logu(rng, -90, -68, (dim, c))
+    if name == "huge":
+        return (_u(rng, 0.5, 1, nnz) * rng.choice([-1, 1], nnz)).astype(np.float32), _u(rng, 0.5, 1, (n, dim)), \
+            (_u(rng, 0.5, 1, (dim, c)) * rng.choice([-1, 1], (dim, c))).astype(np.float32)
+    if name == "cancel":  # X's columns h.. are its columns ..h, W's rows h.. the negated rows ..h: every k pair cancels exactly
+        h = dim // 2
+        X = _u(rng, -1, 1, (n, dim))
+        X[:, h:2 * h] = X[:, :h]
+        W = (_u(rng, -1, 1, (dim, c)) * np.exp2(rng.integers(-10, 11, (dim, c)))).astype(np.float32)
+        W[h:2 * h] = -W[:h]
+        if dim % 2:
+            W[-1] *= np.float32(2.0 ** -20)
+        return _u(rng, -1, 1, nnz), X, W
+    if name == "zeros":  # stored +-0 in A, zeros in X and W, infs of W against zeros of X; A, X >= 0 so A X never cancels
+        vals = _u(rng, 0.5, 1, nnz)
+        z = rng.random(nnz) < 0.3
+        vals[z] = np.where(rng.random(z.sum()) < 0.5, 0.0, -0.0)
+        X = _u(rng, 0, 1, (n, dim))
+        X[rng.random((n, dim)) < 0.3] = 0.0
+        W = _u(rng, -1, 1, (dim, c))
+        W[rng.random((dim, c)) < 0.3] = 0.0
+        W = _sprinkle(rng, W, 0.02, (np.inf, -np.inf))
+        return vals, X, W
+    if name == "nonfinite_X":
+        return _u(rng, -1, 1, nnz), _sprinkle(rng, _u(rng, -1, 1, (n, dim)), 0.01), _u(rng, -1, 1, (dim, c))
+    if name == "nonfinite_W":  # A >= 0 and X > 0: A X is a sum of positive terms (or exactly 0) where it meets W's infs
+        return _u(rng, 0, 1, nnz), _u(rng, 0.5, 1, (n, dim)), _sprinkle(rng, _u(rng, -1, 1, (dim, c)), 0.03)
+    if name == "nonfinite_A":  # X, W > 0: X W is positive where it meets A's infs
+        return _sprinkle(rng, _u(rng, -1, 1, nnz), 0.04), _u(rng, 0.5, 1, (n, dim)), _u(rng, 0.5, 1, (dim, c))
+    raise ValueError(name)
+
+
+AXW_SCENARIOS = ["uniform", "wide", "subnormal_X_large_W", "large_X_subnormal_W", "products_underflow", "huge", "cancel", "zeros",
+                 "nonfinite_X", "nonfinite_W", "nonfinite_A"]
+
+
+def axw_scenario(name, n, dim, c, seed=0):
+    """(HostCsr A [n x n], X [n x dim], W [dim x c]) of the named scenario, seeded."""
+    rng = np.random.default_rng([seed, AXW_SCENARIOS.index(name), n, dim, c])
+    rp, col = _axw_pattern(rng, n)
+    vals, X, W = _axw_values(name, rng, int(rp[-1]), n, dim, c)
+    a = HostCsr(rp.astype(np.uint32), col.astype(np.uint32), np.asarray(vals, np.float32), n=n)
+    if name == "huge":  # W scaled by a power of two so that the largest stage sum lands in [2^119, 2^120)
+        af = HostCsr(a.rowPtr, a.col, np.abs(a.vals), n=n)
+        s_xw = gemm_f64(np.abs(X), np.abs(W))
+        smax = max(s_xw.max(initial=0), spmm64(af, s_xw).max(initial=0))
+        sx = spmm64(af, np.abs(X)).max(initial=0)
+        if sx >= 2.0 ** 119:  # |A||X| alone must stay below the limit too
+            X = (X * np.float32(2.0 ** (100 - int(np.floor(np.log2(sx)))))).astype(np.float32)
+            s_xw = gemm_f64(np.abs(X), np.abs(W))
+            smax = max(s_xw.max(initial=0), spmm64(af, s_xw).max(initial=0))
+        if smax > 0:
+            W = (W.astype(np.float64) * 2.0 ** (119 - int(np.floor(np.log2(smax))))).astype(np.float32)
+    return a, np.ascontiguousarray(X, np.float32), np.ascontiguousarray(W, np.float32)

@@ -266,7 +266,7 @@ def test_plans_of_every_scenario_are_valid_and_add_no_records(sim, route):
     kernel: the same tiles, each holding only the finite cells."""
     spec = ROUTES[route]
     for name in SCENARIOS:
-        a, B = scenario(name, k=spec["k"], pattern=spec.get("pattern", "random"))
+        a, B = scenario(name, k=spec["k"], m=spec.get("m", 512), pattern=spec.get("pattern", "random"))
         plans = plan_for_route(route, a)
         uniform = plan_for_route(route, with_uniform_values(a))
         for p, q in zip(plans, uniform):

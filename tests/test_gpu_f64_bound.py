@@ -28,6 +28,12 @@ def run_route(route, a, B):
         torch.cuda.synchronize()
         return torch.cat(outs).cpu().numpy()
     p = plans[0]
+    if spec.get("stamped"):
+        Bd = torch.from_numpy(B).cuda()
+        Cd = torch.full((a.m, k), -7.0, device="cuda")  # every row must be written
+        p.measure_imbalance(Bd.data_ptr(), Cd.data_ptr(), stream)
+        torch.cuda.synchronize()
+        return Cd.cpu().numpy()
     if spec.get("unaligned"):
         bb = torch.zeros(a.n * k + 1, device="cuda")
         bb[1:] = torch.from_numpy(B).cuda().ravel()
@@ -50,6 +56,37 @@ def run_route(route, a, B):
     return C.cpu().numpy()
 
 
+def _knobs_took_effect(route, plan):
+    """The tuning knobs of `route` as the plan resolved them (flex_plan_get_tuning), and what they imply for the launch."""
+    spec, tn, info = ROUTES[route], plan.tuning(), plan.info()
+    for knob in ("lanes_per_nz", "tile_group", "unroll", "xcd_slices", "xcd_stretch", "rec_nt", "lds_extra", "split_rows"):
+        if knob in spec["tuning"]:
+            assert tn[knob] == spec["tuning"][knob], (route, knob, tn[knob])
+    if "order" in spec:
+        assert info["order"] == spec["order"], info
+    if route.startswith("tile_group"):
+        assert (info["k"] + 4 * tn["lanes_per_nz"] - 1) // (4 * tn["lanes_per_nz"]) >= 2, info  # a multi-tile launch
+        if route == "tile_group_rcm":
+            assert tn["xcd_slices"] == 2, tn  # RCM: no XCD remap
+    if route == "tile_group_split" or spec.get("stamped"):
+        assert info["n_split_rows"] > 0, info
+
+
+def _group_slice(plan):
+    """Workgroups of one pass in an XCD's slice of the grouped grid (the whole pass without the XCD remap): 4 chunks per workgroup."""
+    nwg = plan.info()["n_slots"] // 4
+    return nwg // 8 if plan.tuning()["xcd_slices"] == 1 else nwg
+
+
+@pytest.mark.parametrize("route", [r for r in ROUTES if r.startswith("tile_group")])
+def test_the_grouped_routes_end_slices_in_a_short_group(route):
+    """spmm_kernels.hip decodes the last group of a slice as short when the slice is not a multiple of tile_group: most scenarios of
+    every grouped route meet that decode."""
+    spec = ROUTES[route]
+    slices = [_group_slice(plan_for_route(route, scenario(name, k=spec["k"], m=spec.get("m", 512))[0])[0]) for name in SCENARIOS]
+    assert sum(s % spec["tuning"]["tile_group"] != 0 for s in slices) >= 9, slices
+
+
 def _route_is_taken(route, plan_info):
     if route.startswith("mfma"):
         assert plan_info["n_tiles"] > 0, plan_info
@@ -67,8 +104,10 @@ def _route_is_taken(route, plan_info):
 @pytest.mark.parametrize("route", list(ROUTES))
 def test_route_within_the_float64_bound(route, name):
     spec = ROUTES[route]
-    a, B = scenario(name, k=spec["k"], pattern=spec.get("pattern", "random"))
-    _route_is_taken(route, plan_for_route(route, a)[0].info())
+    a, B = scenario(name, k=spec["k"], m=spec.get("m", 512), pattern=spec.get("pattern", "random"))
+    plan = plan_for_route(route, a)[0]
+    _route_is_taken(route, plan.info())
+    _knobs_took_effect(route, plan)
     assert_within_f64_bound(a, B, run_route(route, a, B), route=f"{route}/{name}")
 
 
@@ -95,3 +134,17 @@ def test_the_documented_padding_residual():
     B[1, :] = np.inf
     C = run_route("flat_g4", a, B)
     assert np.all(C[0] == np.inf)
+
+
+def test_the_stamped_twin_refuses_row_blocks():
+    """flex_plan_measure_imbalance exists for the vector kernel only: a plan with row blocks is refused with FLEX_ERR_UNSUPPORTED and C
+    is left as it was."""
+    a, B = scenario("wide", k=64, pattern="block")
+    p = plan_for_route("blocks", a)[0]
+    assert p.info()["n_blocks"] > 0
+    Bd = torch.from_numpy(B).cuda()
+    Cd = torch.full((a.m, 64), -7.0, device="cuda")
+    with pytest.raises(flex_amd.FlexError, match=r"\(-4\)"):
+        p.measure_imbalance(Bd.data_ptr(), Cd.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert bool((Cd == -7.0).all())
