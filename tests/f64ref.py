@@ -342,46 +342,92 @@ def with_uniform_values(a, seed=0):
 # dense 32 x 32 tiles for the MFMA route, columns reused inside a block of rows for the hot-block route).  "ld": strided B / C;
 # "unaligned": B and C one float off 16-byte alignment (the generic kernels); "mapped": a CSR permuted by RCM planned with its map;
 # "shards": three row shards concatenated.
+# "kernels": the kernel instantiations every plan of the route launches, in launch order, named as `nm -C` prints them.
+# tests/test_kernel_routes.py checks each declaration against the host simulator's launch log, on every scenario, and that every
+# SpMM kernel of libflex_spmm.so is declared by some route (here or in tests/test_gpu_address_limits.py).
+
+
+def flat(G, off32=True, unroll=None, stamped=False):
+    """spmm_flat_kernel<G, OFF32, U, waves per workgroup, STAMP>: U = 4 on G <= 16, 8 on G >= 32, unless the unroll knob asks for 8."""
+    U = unroll or (4 if G <= 16 else 8)
+    return f"spmm_flat_kernel<{G}, {str(off32).lower()}, {U}, 4, {str(stamped).lower()}>"
+
+
+def generic(off32=True):
+    return f"spmm_generic_kernel<{str(off32).lower()}>"
+
+
+def tile(off32=True):
+    return f"spmm_tile_kernel<{str(off32).lower()}>"
+
+
+def hot(rounds, vec4=True):
+    return f"spmm_hot_kernel<{rounds}>" if vec4 else f"spmm_hot_generic_kernel<{rounds}>"
+
+
+FIXUP = "spmm_fixup_kernel"
 SPLIT = {"long_row": 24, "piece_records": 16}
 ROUTES = {
-    "flat_g4": {"k": 16, "tuning": {"lanes_per_nz": 4, "bundle": 2}},
-    "flat_g8": {"k": 32, "tuning": {"lanes_per_nz": 8, "bundle": 2}},
-    "flat_g16": {"k": 64, "tuning": {"lanes_per_nz": 16, "bundle": 2}},
-    "flat_g32": {"k": 128, "tuning": {"lanes_per_nz": 32}},
-    "flat_g64": {"k": 256, "tuning": {"lanes_per_nz": 64}},
-    "generic_odd_k": {"k": 7, "tuning": {}},
-    "generic_unaligned": {"k": 32, "tuning": {}, "unaligned": True},
-    "bundles_g4": {"k": 16, "tuning": {"lanes_per_nz": 4, "bundle": 1}},
-    "bundles_g8": {"k": 32, "tuning": {"lanes_per_nz": 8, "bundle": 1}},
-    "bundles_g16": {"k": 64, "tuning": {"lanes_per_nz": 16, "bundle": 1}},
-    "split_rows1": {"k": 32, "tuning": dict(SPLIT, split_rows=1, bundle=2)},
-    "split_rows2": {"k": 32, "tuning": dict(SPLIT, split_rows=2, bundle=1)},
-    "split_g4": {"k": 12, "tuning": dict(SPLIT, split_rows=2, lanes_per_nz=4)},
-    "two_d": {"k": 32, "tuning": {"two_d": 1, "panel_kb": 1}},
-    "far_first": {"k": 32, "tuning": {"far_first": 8}},
-    "order_cluster": {"k": 32, "tuning": {}, "order": 2},
-    "order_rcm": {"k": 64, "tuning": dict(SPLIT), "order": 1},
-    "mapped": {"k": 32, "tuning": {}, "mapped": True},
-    "shards": {"k": 32, "tuning": dict(SPLIT), "shards": 3},
-    "strided": {"k": 20, "tuning": {}, "ld": (28, 24)},
-    "mfma": {"k": 32, "tuning": {"mfma": 1, "mfma_fill_pct": 50}, "pattern": "block"},
-    "mfma_k100": {"k": 100, "tuning": {"mfma": 1, "mfma_fill_pct": 50}, "pattern": "block"},
-    "blocks": {"k": 64, "tuning": {"blocks": 1}, "pattern": "block"},
+    "flat_g4": {"k": 16, "tuning": {"lanes_per_nz": 4, "bundle": 2}, "kernels": [flat(4)]},
+    "flat_g8": {"k": 32, "tuning": {"lanes_per_nz": 8, "bundle": 2}, "kernels": [flat(8)]},
+    "flat_g16": {"k": 64, "tuning": {"lanes_per_nz": 16, "bundle": 2}, "kernels": [flat(16)]},
+    "flat_g32": {"k": 128, "tuning": {"lanes_per_nz": 32}, "kernels": [flat(32)]},
+    "flat_g64": {"k": 256, "tuning": {"lanes_per_nz": 64}, "kernels": [flat(64)]},
+    "generic_odd_k": {"k": 7, "tuning": {}, "kernels": [generic(), FIXUP]},
+    "generic_unaligned": {"k": 32, "tuning": {}, "unaligned": True, "kernels": [generic(), FIXUP]},
+    "bundles_g4": {"k": 16, "tuning": {"lanes_per_nz": 4, "bundle": 1}, "kernels": [flat(4)]},
+    "bundles_g8": {"k": 32, "tuning": {"lanes_per_nz": 8, "bundle": 1}, "kernels": [flat(8)]},
+    "bundles_g16": {"k": 64, "tuning": {"lanes_per_nz": 16, "bundle": 1}, "kernels": [flat(16)]},
+    "split_rows1": {"k": 32, "tuning": dict(SPLIT, split_rows=1, bundle=2), "kernels": [flat(8)]},
+    "split_rows2": {"k": 32, "tuning": dict(SPLIT, split_rows=2, bundle=1), "kernels": [flat(8), FIXUP]},
+    "split_g4": {"k": 12, "tuning": dict(SPLIT, split_rows=2, lanes_per_nz=4), "kernels": [flat(4), FIXUP]},
+    "two_d": {"k": 32, "tuning": {"two_d": 1, "panel_kb": 1}, "kernels": [flat(8)]},
+    "far_first": {"k": 32, "tuning": {"far_first": 8}, "kernels": [flat(8)]},
+    "order_cluster": {"k": 32, "tuning": {}, "order": 2, "kernels": [flat(8)]},
+    "order_rcm": {"k": 64, "tuning": dict(SPLIT), "order": 1, "kernels": [flat(16)]},
+    "mapped": {"k": 32, "tuning": {}, "mapped": True, "kernels": [flat(8)]},
+    "shards": {"k": 32, "tuning": dict(SPLIT), "shards": 3, "kernels": [flat(8)]},
+    "strided": {"k": 20, "tuning": {}, "ld": (28, 24), "kernels": [flat(8)]},
+    "mfma": {"k": 32, "tuning": {"mfma": 1, "mfma_fill_pct": 50}, "pattern": "block", "kernels": [flat(8), tile()]},
+    "mfma_k100": {"k": 100, "tuning": {"mfma": 1, "mfma_fill_pct": 50}, "pattern": "block", "kernels": [flat(16), tile()]},
+    "blocks": {"k": 64, "tuning": {"blocks": 1}, "pattern": "block", "kernels": [flat(16), hot(2)]},  # 2 rounds: the rule on few blocks
+    # the other hot-block instantiations: 4 and 8 rounds on the vector kernel, and the generic hot kernel (unaligned operands) at each
+    "blocks_r4": {"k": 64, "tuning": {"blocks": 1, "block_rounds": 4}, "pattern": "block", "kernels": [flat(16), hot(4)]},
+    "blocks_r8": {"k": 64, "tuning": {"blocks": 1, "block_rounds": 8}, "pattern": "block", "kernels": [flat(16), hot(8)]},
+    "blocks_generic_r2": {"k": 64, "tuning": {"blocks": 1, "block_rounds": 2}, "pattern": "block", "unaligned": True,
+                          "kernels": [generic(), hot(2, vec4=False)]},
+    "blocks_generic_r4": {"k": 64, "tuning": {"blocks": 1, "block_rounds": 4}, "pattern": "block", "unaligned": True,
+                          "kernels": [generic(), hot(4, vec4=False)]},
+    "blocks_generic_r8": {"k": 64, "tuning": {"blocks": 1, "block_rounds": 8}, "pattern": "block", "unaligned": True,
+                          "kernels": [generic(), hot(8, vec4=False)]},
     # launch and grid-decode variants: the grouped 1-D grid (tile_group) with its short last group, the unroll-8 narrow tiles, the
     # dealt XCD stretches, non-temporal record loads with an occupancy throttle; "stamped": through flex_plan_measure_imbalance (the
     # stamped twin of the vector kernel, then the split-row fix-up and the MFMA tiles), which must leave the ordinary result in C.
     # "m": rows of the scenario where 512 does not reach the route: the XCD slices of the grouped grid end in a short group of 3 at
     # these sizes, and stretches are dealt only from 256 chunks on.
-    "tile_group_g16": {"k": 128, "tuning": {"lanes_per_nz": 16, "tile_group": 3}},
-    "tile_group_rcm": {"k": 128, "tuning": {"lanes_per_nz": 16, "tile_group": 3}, "order": 1, "m": 448},
-    "tile_group_split": {"k": 128, "tuning": dict(SPLIT, lanes_per_nz=16, tile_group=3, split_rows=1), "m": 640},
-    "unroll8_g8": {"k": 32, "tuning": {"unroll": 8}},
-    "unroll8_g16": {"k": 64, "tuning": {"unroll": 8}},
-    "xcd_dealt": {"k": 32, "tuning": {"xcd_slices": 3, "xcd_stretch": 1}, "m": 2048},
-    "rec_nt_lds": {"k": 64, "tuning": {"rec_nt": 1, "lds_extra": 16384}},
-    "stamped": {"k": 128, "tuning": dict(SPLIT, split_rows=1), "stamped": True},
-    "stamped_g4": {"k": 16, "tuning": dict(SPLIT, lanes_per_nz=4, split_rows=2), "stamped": True},
+    "tile_group_g16": {"k": 128, "tuning": {"lanes_per_nz": 16, "tile_group": 3}, "kernels": [flat(16)]},
+    "tile_group_rcm": {"k": 128, "tuning": {"lanes_per_nz": 16, "tile_group": 3}, "order": 1, "m": 448, "kernels": [flat(16)]},
+    "tile_group_split": {"k": 128, "tuning": dict(SPLIT, lanes_per_nz=16, tile_group=3, split_rows=1), "m": 640, "kernels": [flat(16)]},
+    "unroll8_g8": {"k": 32, "tuning": {"unroll": 8}, "kernels": [flat(8, unroll=8)]},
+    "unroll8_g16": {"k": 64, "tuning": {"unroll": 8}, "kernels": [flat(16, unroll=8)]},
+    "xcd_dealt": {"k": 32, "tuning": {"xcd_slices": 3, "xcd_stretch": 1}, "m": 2048, "kernels": [flat(8)]},
+    "rec_nt_lds": {"k": 64, "tuning": {"rec_nt": 1, "lds_extra": 16384}, "kernels": [flat(16)]},
+    "stamped": {"k": 128, "tuning": dict(SPLIT, split_rows=1), "stamped": True, "kernels": [flat(16, stamped=True)]},
+    "stamped_g4": {"k": 16, "tuning": dict(SPLIT, lanes_per_nz=4, split_rows=2), "stamped": True, "kernels": [flat(4, stamped=True), FIXUP]},
 }
+
+# fake device addresses for the host simulator's launch log: 16-byte aligned, and one float off for the unaligned routes
+FAKE_B, FAKE_C = 0x7F0000000000, 0x7F4000000000
+
+
+def fake_launch(plans, unaligned=False, stamped=False):
+    """Launch every plan once on fake operands (host simulator with its launch log on: nothing is read or written)."""
+    off = 4 if unaligned else 0
+    for p in plans:
+        if stamped:
+            p.measure_imbalance(FAKE_B + off, FAKE_C + off)
+        else:
+            p.spmm(FAKE_B + off, FAKE_C + off)
 
 
 def plan_for_route(route, a):
@@ -397,6 +443,193 @@ def plan_for_route(route, a):
         return [flex_amd.Plan(a, k, rows=(int(b[i]), int(b[i + 1])), tuning=tn) for i in range(spec["shards"])]
     ldb, ldc = spec.get("ld", (None, None))
     return [flex_amd.Plan(a, k, order=spec.get("order", 0), ldb=ldb, ldc=ldc, tuning=tn)]
+
+
+# ---- the 2 and 4 GiB address marks (tests/test_gpu_address_limits.py) -------------------------------------------------------------
+# A scenario's columns (B side) or rows (C side) are embedded into a large operand by a map that keeps every 32-aligned block of 32
+# contiguous and 32-aligned, so the "block" pattern still yields dense tiles and hot blocks; the arithmetic does not change, so the result
+# is judged against the scenario's own small (a, B).  Everything the map does not use is poisoned (NaN in B, a sentinel in C), and the
+# operand sits 2 GiB into an allocation whose front is poisoned too: a wrapped 32-bit offset lands on a used row that holds other values,
+# a sign-extended one in the guard in front -- a wrong value or class, never a fault.
+#
+# B side, ldb = 256 (1 KiB a row): row 2^21 starts at 2 GiB, row 2^22 at 4 GiB.  n = 2^22 is the largest plan with 32-bit B offsets
+# (n ldb 4 = 2^32 exactly, plan_build.cpp); n = 2^22 + 8192 makes every plan 64-bit.
+# C side, ldc = 1024 (4 KiB a row): row 2^19 starts at 2 GiB, row 2^20 at 4 GiB.
+BIG_LDB = 256
+TOP32_N = 1 << 22
+WIDE64_N = (1 << 22) + 8192
+BIG_LDC = 1024
+C_MARK2, C_MARK4 = 1 << 19, 1 << 20
+C_ROWS = (1 << 20) + 4096
+GUARD_BYTES = 1 << 31  # a sign-extended 32-bit byte offset reaches at most 2 GiB below the operand
+
+
+def _spread(lo, hi, count):
+    """count distinct 32-aligned block starts in [lo, hi - 32], the first at lo and the last at hi - 32."""
+    s = np.unique(np.linspace(lo // 32, hi // 32 - 1, count).astype(np.int64)) * 32
+    assert len(s) == count, (lo, hi, count)
+    return s
+
+
+def block_slots(table, blocks):
+    """Where each 32-block of a scenario's columns (B side) or rows (C side) goes, by table:
+    top32:  two blocks below the 2 GiB mark (one ends at it), the rest in [2^21, 2^22) up to row 2^22 - 1;
+    wide64: half in the window [2^22, 2^22 + 8192) above 4 GiB, the other half on their aliases c - 2^22;
+    c_side: a quarter in the window [2^20, 2^20 + 4096) above 4 GiB with the next quarter on their aliases r - 2^20, the rest in
+            [2^19, 2^20) (past 2 GiB)."""
+    if table == "top32":
+        assert blocks >= 4
+        return np.concatenate([[0, (1 << 21) - 32], _spread(1 << 21, TOP32_N, blocks - 2)])
+    if table == "wide64":
+        assert blocks % 2 == 0
+        win = _spread(TOP32_N, WIDE64_N, blocks // 2)
+        return np.concatenate([win, np.roll(win, 1) - TOP32_N])  # rolled: "cancel" repeats B's first half in its second
+    if table == "c_side":
+        q = blocks // 4
+        win = _spread(C_MARK4, C_ROWS, q)
+        return np.concatenate([win, win - C_MARK4, _spread(C_MARK2, C_MARK4, blocks - 2 * q)])
+    raise ValueError(table)
+
+
+def block_map(count, table):
+    """index -> big index for `count` scenario columns or rows: 32-block b goes to block_slots(table)[b], order kept inside a block."""
+    i = np.arange(count, dtype=np.int64)
+    return block_slots(table, -(-count // 32))[i // 32] + i % 32
+
+
+def embed_cols(a, cmap, n_big):
+    """The scenario's A with column c renamed cmap[c], over n_big columns."""
+    return HostCsr(a.rowPtr, cmap[a.col.astype(np.int64)].astype(np.uint32), a.vals, n=n_big)
+
+
+def embed_rows(a, rmap, m_big):
+    """The scenario's A with row r moved to row rmap[r] of an m_big-row matrix; every other row empty."""
+    rp = a.rowPtr.astype(np.int64)
+    deg = np.zeros(m_big, np.int64)
+    deg[rmap] = np.diff(rp)
+    rp_big = np.zeros(m_big + 1, np.int64)
+    np.cumsum(deg, out=rp_big[1:])
+    order = np.argsort(rmap)
+    e = np.concatenate([np.arange(rp[r], rp[r + 1]) for r in order] + [np.zeros(0, np.int64)])
+    return HostCsr(rp_big.astype(np.uint32), a.col[e], a.vals[e], n=a.n)
+
+
+class BigB:
+    """A model of the large B the GPU test builds, without its 4 GiB: row cmap[c] holds B[c], every other row -- and the guard in front
+    of row 0 (negative rows) -- holds NaN.  rows(big) returns those rows."""
+
+    def __init__(self, B, cmap):
+        self.B, self.cmap = np.asarray(B, np.float32), np.asarray(cmap, np.int64)
+        self.where = dict(zip(self.cmap.tolist(), range(len(self.cmap))))
+
+    def rows(self, big):
+        small = np.array([self.where.get(int(r), -1) for r in np.asarray(big).ravel()], np.int64)
+        out = np.full((len(small), self.B.shape[1]), np.nan, np.float32)
+        out[small >= 0] = self.B[small[small >= 0]]
+        return out
+
+
+def spmm_big_b(a_big, big_b, read=lambda c: c):
+    """C of the embedded A read through the model, in float64 rounded to fp32 (an engine that is exact up to its order); read: the B row
+    an addressing model makes of a column id (identity = right)."""
+    col = read(a_big.col.astype(np.int64))
+    uniq, inv = np.unique(col, return_inverse=True)
+    Bu = big_b.rows(uniq)
+    a_u = HostCsr(a_big.rowPtr, inv.astype(np.uint32), a_big.vals, n=len(uniq))
+    return spmm_f64(a_u, Bu).astype(np.float32)
+
+
+def wrap32(c, ldb=BIG_LDB):
+    """A 64-bit plan's B row, had the byte offset c ldb 4 been kept in 32 bits: c >= 2^22 reads c - 2^22."""
+    return ((np.asarray(c, np.int64) * ldb * 4) & 0xFFFFFFFF) // (ldb * 4)
+
+
+def sign_extend32(c, ldb=BIG_LDB):
+    """A 32-bit plan's B row, had its byte offset been sign-extended: offsets >= 2^31 land up to 2 GiB in front of B (negative rows)."""
+    off = np.asarray(c, np.int64) * ldb * 4
+    return np.where(off >= 1 << 31, off - (1 << 32), off) // (ldb * 4)
+
+
+def _b_routes(o):
+    """The B-side routes at ldb = 256; o: the plans have 32-bit B offsets (top32) or not (wide64).  "shards": three row shards;
+    "stamped": through flex_plan_measure_imbalance; "unaligned": B and C one float off (the generic kernels)."""
+    r = {
+        "flat_g4": {"k": 16, "tuning": {"lanes_per_nz": 4, "bundle": 2}, "kernels": [flat(4, o)]},
+        "flat_g8": {"k": 32, "tuning": {"lanes_per_nz": 8, "bundle": 2}, "kernels": [flat(8, o)]},
+        "flat_g16": {"k": 64, "tuning": {"lanes_per_nz": 16, "bundle": 2}, "kernels": [flat(16, o)]},
+        "flat_g32": {"k": 128, "tuning": {"lanes_per_nz": 32}, "kernels": [flat(32, o)]},
+        "flat_g64": {"k": 256, "tuning": {"lanes_per_nz": 64}, "kernels": [flat(64, o)]},  # k = ldb: the last float4 ends the row
+        "unroll8_g8": {"k": 32, "tuning": {"lanes_per_nz": 8, "unroll": 8}, "kernels": [flat(8, o, unroll=8)]},
+        "unroll8_g16": {"k": 64, "tuning": {"lanes_per_nz": 16, "unroll": 8}, "kernels": [flat(16, o, unroll=8)]},
+        "bundles_g4": {"k": 16, "tuning": {"lanes_per_nz": 4, "bundle": 1}, "kernels": [flat(4, o)]},
+        "bundles_g8": {"k": 32, "tuning": {"lanes_per_nz": 8, "bundle": 1}, "kernels": [flat(8, o)]},
+        "bundles_g16": {"k": 64, "tuning": {"lanes_per_nz": 16, "bundle": 1}, "kernels": [flat(16, o)]},
+        "split_rows1": {"k": 32, "tuning": dict(SPLIT, split_rows=1, bundle=2), "kernels": [flat(8, o)]},
+        "split_rows2": {"k": 32, "tuning": dict(SPLIT, split_rows=2, bundle=1), "kernels": [flat(8, o), FIXUP]},
+        "generic_odd_k": {"k": 7, "tuning": {}, "kernels": [generic(o), FIXUP]},
+        "generic_unaligned": {"k": 32, "tuning": {}, "unaligned": True, "kernels": [generic(o), FIXUP]},
+        "two_d": {"k": 32, "tuning": {"two_d": 1, "panel_kb": 1}, "kernels": [flat(8, o)]},
+        "tile_group": {"k": 128, "tuning": {"lanes_per_nz": 16, "tile_group": 3}, "kernels": [flat(16, o)]},
+        "mfma": {"k": 32, "tuning": {"mfma": 1, "mfma_fill_pct": 50}, "pattern": "block", "kernels": [flat(8, o), tile(o)]},
+        "mfma_k100": {"k": 100, "tuning": {"mfma": 1, "mfma_fill_pct": 50}, "pattern": "block", "kernels": [flat(16, o), tile(o)]},
+        "shards": {"k": 32, "tuning": dict(SPLIT), "shards": 3, "kernels": [flat(8, o)]},
+        "stamped_g4": {"k": 16, "tuning": dict(SPLIT, lanes_per_nz=4, split_rows=2), "stamped": True,
+                       "kernels": [flat(4, o, stamped=True), FIXUP]},
+        "stamped_g8": {"k": 32, "tuning": dict(SPLIT, lanes_per_nz=8, split_rows=1), "stamped": True, "kernels": [flat(8, o, stamped=True)]},
+        "stamped_g16": {"k": 64, "tuning": {"lanes_per_nz": 16}, "stamped": True, "kernels": [flat(16, o, stamped=True)]},
+        "stamped_g32": {"k": 128, "tuning": dict(SPLIT, lanes_per_nz=32, split_rows=2), "stamped": True,
+                        "kernels": [flat(32, o, stamped=True), FIXUP]},
+        "stamped_g64": {"k": 256, "tuning": {"lanes_per_nz": 64}, "stamped": True, "kernels": [flat(64, o, stamped=True)]},
+    }
+    for rounds in (2, 4, 8):  # hot blocks need 32-bit B offsets: a 64-bit plan must stay flat (and right)
+        r[f"blocks_r{rounds}"] = {"k": 64, "tuning": {"blocks": 1, "block_rounds": rounds}, "pattern": "block",
+                                  "kernels": [flat(16, o), hot(rounds)] if o else [flat(16, o)]}
+    return r
+
+
+B_TOP32 = _b_routes(True)
+B_WIDE64 = _b_routes(False)
+# C side: B small (32-bit plans), ldc = 1024, every row of the 2^20 + 4096 planned; "rows": a row shard above the 4 GiB mark
+C_ROUTES = {
+    "flat_g4": {"k": 16, "tuning": {"lanes_per_nz": 4, "bundle": 2}, "kernels": [flat(4)]},
+    "flat_g8": {"k": 32, "tuning": {"lanes_per_nz": 8, "bundle": 2}, "kernels": [flat(8)]},
+    "flat_g16": {"k": 64, "tuning": {"lanes_per_nz": 16, "bundle": 2}, "kernels": [flat(16)]},
+    "flat_g32": {"k": 128, "tuning": {"lanes_per_nz": 32}, "kernels": [flat(32)]},
+    "flat_g64": {"k": 256, "tuning": {"lanes_per_nz": 64}, "kernels": [flat(64)]},
+    "bundles_g8": {"k": 32, "tuning": {"lanes_per_nz": 8, "bundle": 1}, "kernels": [flat(8)]},
+    "split_rows1": {"k": 32, "tuning": dict(SPLIT, split_rows=1, bundle=2), "kernels": [flat(8)]},
+    "split_rows2": {"k": 32, "tuning": dict(SPLIT, split_rows=2, bundle=1), "kernels": [flat(8), FIXUP]},
+    "generic_odd_k": {"k": 7, "tuning": {}, "kernels": [generic(), FIXUP]},
+    "two_d": {"k": 32, "tuning": {"two_d": 1, "panel_kb": 1}, "kernels": [flat(8)]},
+    "mfma": {"k": 32, "tuning": {"mfma": 1, "mfma_fill_pct": 50}, "pattern": "block", "kernels": [flat(8), tile()]},
+    "blocks": {"k": 64, "tuning": {"blocks": 1}, "pattern": "block", "kernels": [flat(16), hot(8)]},  # 8 rounds: the rule on 2^20 rows
+    "rows_above_4GiB": {"k": 64, "tuning": {}, "rows": (C_MARK4, C_ROWS), "kernels": [flat(16)]},
+}
+ADDRESS_TABLES = {"top32": B_TOP32, "wide64": B_WIDE64, "c_side": C_ROUTES}
+
+
+def address_case(table, route, name, seed=0):
+    """(small a, B, big A) of scenario `name` for a route of an address table: the scenario's columns embedded into the 4 GiB B (B side),
+    or its rows into the 4 GiB C (c_side)."""
+    spec = ADDRESS_TABLES[table][route]
+    a, B = scenario(name, k=spec["k"], m=512, seed=seed, pattern=spec.get("pattern", "random"))
+    if table == "c_side":
+        return a, B, embed_rows(a, block_map(a.m, table), C_ROWS)
+    return a, B, embed_cols(a, block_map(a.n, table), TOP32_N if table == "top32" else WIDE64_N)
+
+
+def address_plans(table, route, a_big):
+    """The plans of an address-table route for the embedded A."""
+    import flex_amd
+    spec = ADDRESS_TABLES[table][route]
+    k, tn = spec["k"], spec["tuning"]
+    if table == "c_side":
+        rows = spec.get("rows")
+        return [flex_amd.Plan(a_big, k, ldb=k, ldc=BIG_LDC, rows=rows, tuning=tn)]
+    if spec.get("shards"):
+        b = flex_amd.shard_rows(a_big, k, spec["shards"])
+        return [flex_amd.Plan(a_big, k, rows=(int(b[i]), int(b[i + 1])), ldb=BIG_LDB, ldc=k, tuning=tn) for i in range(spec["shards"])]
+    return [flex_amd.Plan(a_big, k, ldb=BIG_LDB, ldc=k, tuning=tn)]
 
 
 # ---- A*X*W (libflex_axw.so) -----------------------------------------------------------------------------------------------------

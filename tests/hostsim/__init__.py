@@ -21,3 +21,17 @@ def build(extra_flags=(), out=_OUT):
            "-Wl,-Bsymbolic-functions", "-o", out] + list(extra_flags) + srcs + ["-lpthread", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib"]  # the HIP calls the shim does not replace are never reached
     subprocess.check_call(cmd)
     return out
+
+
+def launch_log(L, fn):
+    """The kernel instantiations that fn() launched through L (a host-simulated library), in order, as `nm -C` names them: fn runs with
+    the shim's launch log on (tests/hostsim/shim.cpp), where every launcher records what the real one would launch and computes nothing."""
+    import ctypes
+    L.hostsim_launch_log.argtypes = [ctypes.c_int]
+    L.hostsim_launch_log_read.restype = ctypes.c_char_p
+    L.hostsim_launch_log(1)
+    try:
+        fn()
+        return L.hostsim_launch_log_read().decode().splitlines()
+    finally:
+        L.hostsim_launch_log(0)

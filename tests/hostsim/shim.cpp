@@ -3,23 +3,81 @@
 // reads that image back; linked against this file instead of the kernels, "device memory" is malloc'ed host memory, so the
 // CPU suite (and the ASan/UBSan build of tools/asan_host.sh) can create every kind of plan and verify the image the kernels
 // would read.  There is no compute here: every launcher reports FLEX_ERR_UNSUPPORTED, flex_spmm cannot produce a result.
+// The one exception is the opt-in launch log (hostsim_launch_log(1)): while it is on, each launcher appends the name of the kernel
+// instantiation the real launcher would launch -- as `nm -C` prints it, e.g. "spmm_flat_kernel<8, false, 4, 4, false>" -- and
+// reports FLEX_OK, still computing nothing.  The selection below MIRRORS the rules of launch_spmm / launch_spmm_stamped / launch_fixup
+// (spmm_kernels.hip), launch_tiles (tile_kernels.hip) and launch_blocks (block_kernels.hip): a change there must be made here too.
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 
 #include "internal.h"
 
+namespace {
+bool g_log_on = false;
+std::string g_log;  // one instantiation per line, in launch order
+
+int logged(const char *name) {
+    g_log += name;
+    g_log += '\n';
+    return FLEX_OK;
+}
+
+// U of launch_spmm's switch: 4 KiB in flight per wave on the narrow tiles, 8 KiB on the wide ones; 0 = no such tile
+int unroll_of(int lanes_per_nz) { return lanes_per_nz == 4 || lanes_per_nz == 8 || lanes_per_nz == 16 ? 4 : lanes_per_nz == 32 || lanes_per_nz == 64 ? 8 : 0; }
+
+int log_flat(int G, bool off32, int U, bool stamp) {
+    if (U == 0) return FLEX_ERR_UNSUPPORTED;
+    char name[96];
+    std::snprintf(name, sizeof name, "spmm_flat_kernel<%d, %s, %d, %d, %s>", G, off32 ? "true" : "false", U, flex::kWavesPerBlock, stamp ? "true" : "false");
+    return logged(name);
+}
+}  // namespace
+
 namespace flex {
-int launch_spmm(const PlanView &, int, bool, bool, const float *, float *, hipStream_t, int) { return FLEX_ERR_UNSUPPORTED; }
-int launch_spmm_stamped(const PlanView &, int, bool, const float *, float *, hipStream_t) { return FLEX_ERR_UNSUPPORTED; }
-int launch_tiles(const TileView &, bool, const float *, float *, int, int, int, hipStream_t) { return FLEX_ERR_UNSUPPORTED; }
-int launch_blocks(const BlockView &, const float *, float *, hipStream_t, bool) { return FLEX_ERR_UNSUPPORTED; }
-int launch_fixup(const float *, const SplitRow *, uint32_t, int, int, float *, hipStream_t) { return FLEX_ERR_UNSUPPORTED; }
+int launch_spmm(const PlanView &v, int lanes_per_nz, bool off32, bool vec4, const float *, float *, hipStream_t, int unroll) {
+    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
+    if (v.n_chunks == 0) return FLEX_OK;
+    if (!vec4) return logged(off32 ? "spmm_generic_kernel<true>" : "spmm_generic_kernel<false>");
+    if (unroll == 8 && (lanes_per_nz == 8 || lanes_per_nz == 16)) return log_flat(lanes_per_nz, off32, 8, false);
+    return log_flat(lanes_per_nz, off32, unroll_of(lanes_per_nz), false);
+}
+int launch_spmm_stamped(const PlanView &v, int lanes_per_nz, bool off32, const float *, float *, hipStream_t) {
+    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
+    if (v.n_chunks == 0) return FLEX_OK;
+    return log_flat(lanes_per_nz, off32, unroll_of(lanes_per_nz), true);
+}
+int launch_tiles(const TileView &tv, bool off32, const float *, float *, int, int, int, hipStream_t) {
+    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
+    if (tv.n_row_tiles == 0) return FLEX_OK;
+    return logged(off32 ? "spmm_tile_kernel<true>" : "spmm_tile_kernel<false>");
+}
+int launch_blocks(const BlockView &bv, const float *, float *, hipStream_t, bool vec4) {
+    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
+    if (bv.n_blocks == 0) return FLEX_OK;
+    if (bv.rounds != 2 && bv.rounds != 4 && bv.rounds != 8) return FLEX_ERR_UNSUPPORTED;
+    char name[64];
+    std::snprintf(name, sizeof name, "%s<%u>", vec4 ? "spmm_hot_kernel" : "spmm_hot_generic_kernel", bv.rounds);
+    return logged(name);
+}
+int launch_fixup(const float *, const SplitRow *, uint32_t n_rows, int, int, float *, hipStream_t) {
+    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
+    return n_rows == 0 ? FLEX_OK : logged("spmm_fixup_kernel");
+}
 int launch_gather_rows(float *, const float *, const int32_t *, int64_t, int, hipStream_t) { return FLEX_ERR_UNSUPPORTED; }
 int kernel_attributes(int, bool, bool, hipFuncAttributes *, int *) { return FLEX_ERR_UNSUPPORTED; }
 }  // namespace flex
 
 extern "C" {
 int flex_hbm_probe(int, int64_t, int, int, double *, double *) { return FLEX_ERR_UNSUPPORTED; }
+// the launch log: on != 0 turns it on, 0 off; either way it is emptied
+void hostsim_launch_log(int on) {
+    g_log_on = on != 0;
+    g_log.clear();
+}
+// what was launched since the log was last emptied, one instantiation per line (valid until the next launch or hostsim_launch_log)
+const char *hostsim_launch_log_read(void) { return g_log.c_str(); }
 #ifdef FLEX_HOSTSIM  // malloc-backed stand-ins for the few HIP runtime calls the planner makes (bound locally: -Bsymbolic-functions)
 hipError_t hipGetDevice(int *d) { *d = 0; return hipSuccess; }
 hipError_t hipSetDevice(int) { return hipSuccess; }
@@ -40,6 +98,8 @@ uint64_t hostsim_upload_hash(int reset) {
     return h;
 }
 hipError_t hipMemset(void *d, int v, size_t n) { if (n) std::memset(d, v, n); return hipSuccess; }
+hipError_t hipMemsetAsync(void *d, int v, size_t n, hipStream_t) { if (n) std::memset(d, v, n); return hipSuccess; }  // measure_imbalance's log
+hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
 hipError_t hipDeviceSynchronize(void) { return hipSuccess; }
 hipError_t hipGetLastError(void) { return hipSuccess; }
 const char *hipGetErrorString(hipError_t) { return "hostsim"; }

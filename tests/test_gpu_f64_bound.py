@@ -59,7 +59,7 @@ def run_route(route, a, B):
 def _knobs_took_effect(route, plan):
     """The tuning knobs of `route` as the plan resolved them (flex_plan_get_tuning), and what they imply for the launch."""
     spec, tn, info = ROUTES[route], plan.tuning(), plan.info()
-    for knob in ("lanes_per_nz", "tile_group", "unroll", "xcd_slices", "xcd_stretch", "rec_nt", "lds_extra", "split_rows"):
+    for knob in ("lanes_per_nz", "tile_group", "unroll", "xcd_slices", "xcd_stretch", "rec_nt", "lds_extra", "split_rows", "block_rounds"):
         if knob in spec["tuning"]:
             assert tn[knob] == spec["tuning"][knob], (route, knob, tn[knob])
     if "order" in spec:
@@ -90,7 +90,7 @@ def test_the_grouped_routes_end_slices_in_a_short_group(route):
 def _route_is_taken(route, plan_info):
     if route.startswith("mfma"):
         assert plan_info["n_tiles"] > 0, plan_info
-    if route == "blocks":
+    if route.startswith("blocks"):
         assert plan_info["n_blocks"] > 0, plan_info
     if route.startswith("bundles"):
         assert plan_info["n_bundles"] > 0, plan_info
