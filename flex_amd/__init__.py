@@ -15,6 +15,7 @@ from .binding import (  # noqa: F401
     FLEX_PLAN_AUTOTUNE,
     FLEX_PLAN_ROW_RANGE,
     FLEX_PLAN_XCD_INTERLEAVE,
+    FLEX_PLAN_TRANSPOSE,
     FlexError,
     HostCsr,
     Plan,
@@ -45,4 +46,5 @@ from .binding import (  # noqa: F401
     synth_graph,
     SYNTH_PRESETS,
 )
+from .autograd import SparseOperator  # noqa: F401
 from .multigpu import RowShard, broadcast_dense, make_shard  # noqa: F401

@@ -9,6 +9,7 @@ from . import binding
 
 FLEX_AXW_AUTO, FLEX_AXW_A_XW, FLEX_AXW_AX_W = 0, 1, 2
 FLEX_AXW_USE_BLAS = 0x10000  # flex_axw_create flag: rocBLAS for the dense half
+FLEX_AXW_BACKWARD = 0x20000  # flex_axw_create flag: plan A^T too, for flex_axw_backward
 _lib = None
 
 
@@ -23,6 +24,7 @@ def lib():
         vp = C.c_void_p
         L.flex_axw_create.argtypes = [C.POINTER(vp), C.POINTER(binding._Csr), C.c_int, C.c_int, C.c_int, C.c_uint]
         L.flex_axw_run.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.flex_axw_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         L.flex_axw_destroy.argtypes = [vp]
         L.flex_axw_ld.argtypes = [C.c_int]
         L.flex_axw_gemm_launch.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
@@ -40,11 +42,15 @@ def _gemm_launch(L_ptr: int, Wp_ptr: int, Out_ptr: int, n: int, dim: int, c: int
 class Axw:
     """flex_axw handle: plans A for both SpMM widths once; run() computes A @ X @ W in either order."""
 
-    def __init__(self, a: binding.HostCsr, dim: int, c: int, device: int = 0, order: int = binding.FLEX_ORDER_CLUSTER):
+    def __init__(self, a: binding.HostCsr, dim: int, c: int, device: int = 0, order: int = binding.FLEX_ORDER_CLUSTER,
+                 backward: bool = False):
+        """backward: also plan A^T (FLEX_AXW_BACKWARD), for backward() and layer()."""
         self._h = C.c_void_p()
         v = a.view()
-        binding._check(lib().flex_axw_create(C.byref(self._h), C.byref(v), dim, c, device, order), "flex_axw_create")
+        flags = order | (FLEX_AXW_BACKWARD if backward else 0)
+        binding._check(lib().flex_axw_create(C.byref(self._h), C.byref(v), dim, c, device, flags), "flex_axw_create")
         self.n, self.dim, self.c, self.ld = a.n, dim, c, lib().flex_axw_ld(c)
+        self.has_backward = backward
 
     def run(self, X, W, order: int = FLEX_AXW_AUTO, timed: bool = False):
         """X [n, dim], W [dim, c]: contiguous float32 cuda tensors.  Returns Out [n, ld] (columns >= c are zero)
@@ -58,6 +64,31 @@ class Axw:
                                           torch.cuda.current_stream(X.device).cuda_stream,
                                           C.byref(g) if timed else None, C.byref(s) if timed else None), "flex_axw_run")
         return (out, (g.value, s.value)) if timed else out
+
+    def backward(self, dOut, X, W, need_x: bool = True, need_w: bool = True):
+        """flex_axw_backward: dOut [n, ld] (its padding columns are never read) -> (dX [n, dim] or None, dW [dim, c] or None),
+        dX = A^T dOut W^T and dW = X^T (A^T dOut).  X and W are the forward's inputs (only the ones a requested gradient needs)."""
+        import torch
+        if not self.has_backward:
+            raise binding.FlexError("Axw.backward: the handle was made without backward=True (FLEX_AXW_BACKWARD)")
+        assert dOut.is_cuda and dOut.dtype == torch.float32 and dOut.is_contiguous() and tuple(dOut.shape) == (self.n, self.ld)
+        for t, need, shape in ((X, need_w, (self.n, self.dim)), (W, need_x, (self.dim, self.c))):
+            if need:
+                assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape
+        gx = torch.empty((self.n, self.dim), dtype=torch.float32, device=dOut.device) if need_x else None
+        gw = torch.empty((self.dim, self.c), dtype=torch.float32, device=dOut.device) if need_w else None
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        binding._check(lib().flex_axw_backward(self._h, ptr(X) if need_w else None, ptr(W) if need_x else None, dOut.data_ptr(),
+                                               ptr(gx), ptr(gw), torch.cuda.current_stream(dOut.device).cuda_stream),
+                       "flex_axw_backward")
+        return gx, gw
+
+    def layer(self, X, W, order: int = FLEX_AXW_AUTO):
+        """Differentiable A X W: Out [n, c] (a view of the padded product); its gradient flows to X and W through backward()."""
+        if not self.has_backward:
+            raise binding.FlexError("Axw.layer: the handle was made without backward=True (FLEX_AXW_BACKWARD)")
+        from .autograd import functions
+        return functions()[1].apply(X, W, self, order)
 
     def destroy(self):
         if getattr(self, "_h", None) and self._h.value:

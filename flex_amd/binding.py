@@ -25,6 +25,7 @@ FLEX_PLAN_STATS = 0x100
 FLEX_PLAN_AUTOTUNE = 0x200
 FLEX_PLAN_ROW_RANGE = 0x1000
 FLEX_PLAN_XCD_INTERLEAVE = 0x2000
+FLEX_PLAN_TRANSPOSE = 0x8000
 
 
 class FlexError(RuntimeError):
@@ -420,10 +421,14 @@ class Plan:
     """flex_plan handle (≙ Mat after csr2_DiagTiling + alpha_transfer)."""
 
     def __init__(self, a: HostCsr, k: int, device: int = 0, order: int = FLEX_ORDER_NATURAL,
-                 vo_mp=None, rows=None, col_map=None, ldb: int | None = None, ldc: int | None = None, tuning: dict | None = None):
+                 vo_mp=None, rows=None, col_map=None, ldb: int | None = None, ldc: int | None = None, tuning: dict | None = None,
+                 transpose: bool = False):
         """tuning: plan-time knobs as a dict of flex_plan_tuning fields (0 / absent = the planner's rule), e.g.
-        {"lanes_per_nz": 16, "split_rows": 1, "cluster_no_refine": 1}."""
+        {"lanes_per_nz": 16, "split_rows": 1, "cluster_no_refine": 1}.
+        transpose: plan A^T (FLEX_PLAN_TRANSPOSE): C [a.n, k] = A^T B [a.m, k]; every other argument refers to A^T."""
         self._h = C.c_void_p()
+        if transpose:
+            order |= FLEX_PLAN_TRANSPOSE
         self._keep = (a, vo_mp, col_map)
         v = a.view()
         L = lib()

@@ -5,6 +5,7 @@
 #include <rocblas/rocblas.h>
 
 #include <cmath>
+#include <algorithm>
 #include <cstdint>
 #include <new>
 
@@ -12,6 +13,10 @@
 
 extern "C" hipError_t flex_axw_gemm_launch(const float *L, const float *Wp, float *Out, int n, int dim, int c, int cp, int n_cus,
                                            hipStream_t s);  // axw_kernels.hip
+extern "C" hipError_t flex_axw_dw_launch(const float *X, const float *G, float *dW, float *part, int n, int dim, int c, int cp, int n_cus,
+                                         hipStream_t s);
+extern "C" hipError_t flex_axw_transpose_launch(const float *W, float *Wt, int dim, int c, int ld, hipStream_t s);
+extern "C" int flex_axw_dw_slices(int n, int n_cus);
 
 struct flex_axw {
     int32_t n = 0;
@@ -25,6 +30,11 @@ struct flex_axw {
     float *d_wp = nullptr;  // dim x cp (W with zero columns appended)
     rocblas_handle blas = nullptr;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    // FLEX_AXW_BACKWARD only
+    flex_plan *plan_t = nullptr;  // A^T at k = c, ldb = ldc = cp
+    float *d_g = nullptr;         // G = A^T dOut, n x cp; its padding columns are +0 for good
+    float *d_wt = nullptr;        // W^T, cp x ld(dim), rows c .. cp-1 and columns dim .. zero
+    float *d_part = nullptr;      // dW partial sums: flex_axw_dw_slices(n, n_cus) x dim x c
 };
 
 static thread_local int g_blas_status = 0;
@@ -72,6 +82,10 @@ int flex_axw_destroy(flex_axw *h) {
     (void)hipSetDevice(h->device);
     flex_plan_destroy(h->plan_c);
     flex_plan_destroy(h->plan_dim);
+    flex_plan_destroy(h->plan_t);
+    (void)hipFree(h->d_g);
+    (void)hipFree(h->d_wt);
+    (void)hipFree(h->d_part);
     (void)hipFree(h->d_xw);
     (void)hipFree(h->d_ax);
     (void)hipFree(h->d_wp);
@@ -98,7 +112,8 @@ int flex_axw_create(flex_axw **out, const flex_csr *A, int dim, int c, int devic
     (void)hipGetDevice(&prev);
     int rc = hip_fail(hipSetDevice(device));
     const bool want_blas = (flags & FLEX_AXW_USE_BLAS) != 0;
-    flags &= ~FLEX_AXW_USE_BLAS;
+    const bool backward = (flags & FLEX_AXW_BACKWARD) != 0;
+    flags &= ~(FLEX_AXW_USE_BLAS | FLEX_AXW_BACKWARD);
     if (!rc) rc = flex_plan_create(&h->plan_c, A, h->cp, device, flags);
     if (!rc) rc = flex_plan_create(&h->plan_dim, A, dim, device, flags);
     const size_t n1 = static_cast<size_t>(h->n > 0 ? h->n : 1);
@@ -115,6 +130,16 @@ int flex_axw_create(flex_axw **out, const flex_csr *A, int dim, int c, int devic
         rc = hip_fail(hipGetDeviceProperties(&prop, device));
         h->n_cus = prop.multiProcessorCount;
         h->use_blas = want_blas || dim % 4 != 0 || dim > 256 || h->n < 32;
+    }
+    if (!rc && backward) {
+        const size_t wt = static_cast<size_t>(h->cp) * flex_axw_ld(dim);
+        const size_t part = static_cast<size_t>(std::max(1, flex_axw_dw_slices(h->n, h->n_cus))) * dim * c;
+        rc = flex_plan_create_ld(&h->plan_t, A, c, h->cp, h->cp, device, flags | FLEX_PLAN_TRANSPOSE);
+        if (!rc) rc = hip_fail(hipMalloc(reinterpret_cast<void **>(&h->d_g), n1 * h->cp * sizeof(float)));
+        if (!rc) rc = hip_fail(hipMemset(h->d_g, 0, n1 * h->cp * sizeof(float)));  // its padding columns are never written
+        if (!rc) rc = hip_fail(hipMalloc(reinterpret_cast<void **>(&h->d_wt), wt * sizeof(float)));
+        if (!rc) rc = hip_fail(hipMemset(h->d_wt, 0, wt * sizeof(float)));
+        if (!rc) rc = hip_fail(hipMalloc(reinterpret_cast<void **>(&h->d_part), part * sizeof(float)));
     }
     if (prev >= 0) (void)hipSetDevice(prev);
     if (rc) {
@@ -162,6 +187,45 @@ int flex_axw_run(flex_axw *h, int order, const float *dX, const float *dW, float
         const bool gemm_first = order == FLEX_AXW_A_XW;
         if (gemm_ms) *gemm_ms = gemm_first ? a : b;
         if (spmm_ms) *spmm_ms = gemm_first ? b : a;
+    }
+    if (cur >= 0 && cur != h->device) (void)hipSetDevice(cur);
+    return rc;
+}
+
+// G = A^T dOut (the transposed plan), then dGradX = G W^T and dGradW = X^T G (axw_kernels.hip; rocBLAS where the kernels do not take
+// the shape or FLEX_AXW_USE_BLAS asked for it).  Everything is queued on `stream`: no allocation, no host sync.
+int flex_axw_backward(flex_axw *h, const float *dX, const float *dW, const float *dOut, float *dGradX, float *dGradW, flex_stream_t stream) {
+    if (!h || !h->plan_t || !dOut || (dGradX && !dW) || (dGradW && !dX)) return FLEX_ERR_INVALID;
+    if (h->n == 0 || (!dGradX && !dGradW)) return FLEX_OK;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    int cur = -1;
+    (void)hipGetDevice(&cur);
+    int rc = hip_fail(hipSetDevice(h->device));
+    if (!rc && rocblas_set_stream(h->blas, s) != rocblas_status_success) rc = FLEX_ERR_UNSUPPORTED;
+    if (!rc) rc = flex_spmm(h->plan_t, dOut, h->d_g, stream);  // reads columns 0 .. c-1 of dOut, writes columns 0 .. c-1 of G
+    const float one = 1.0f, zero = 0.0f;
+    auto blas = [&](rocblas_status st) -> int {
+        if (st == rocblas_status_success) return FLEX_OK;
+        g_blas_status = static_cast<int>(st);
+        return FLEX_ERR_UNSUPPORTED;
+    };
+    if (!rc && dGradX) {
+        // dGradX[n x dim] = G[n x cp] Wt[cp x dim]: the forward's MFMA kernel when dim is a whole number of 32-column tiles
+        if (!h->use_blas && h->dim % 32 == 0 && h->cp <= 256 && h->n >= 32) {
+            rc = hip_fail(flex_axw_transpose_launch(dW, h->d_wt, h->dim, h->c, h->dim, s));
+            if (!rc) rc = hip_fail(flex_axw_gemm_launch(h->d_g, h->d_wt, dGradX, h->n, h->cp, h->dim, h->dim, h->n_cus, s));
+        } else {  // column-major: dGradX^T[dim x n] = W[dim x c] G^T[c x n]
+            rc = blas(rocblas_sgemm(h->blas, rocblas_operation_transpose, rocblas_operation_none, h->dim, h->n, h->c, &one, dW, h->c, h->d_g,
+                                    h->cp, &zero, dGradX, h->dim));
+        }
+    }
+    if (!rc && dGradW) {
+        if (!h->use_blas && h->dim % 4 == 0 && h->dim <= 256 && h->cp <= 256 && h->n >= 32) {
+            rc = hip_fail(flex_axw_dw_launch(dX, h->d_g, dGradW, h->d_part, h->n, h->dim, h->c, h->cp, h->n_cus, s));
+        } else {  // column-major: dGradW^T[c x dim] = G^T[c x n] X[n x dim]
+            rc = blas(rocblas_sgemm(h->blas, rocblas_operation_none, rocblas_operation_transpose, h->c, h->dim, h->n, &one, h->d_g, h->cp, dX,
+                                    h->dim, &zero, dGradW, h->c));
+        }
     }
     if (cur >= 0 && cur != h->device) (void)hipSetDevice(cur);
     return rc;

@@ -207,3 +207,135 @@ extern "C" hipError_t flex_axw_gemm_launch(const float *L, const float *Wp, floa
     }
     return hipSuccess;
 }
+
+// ---- the backward pass (flex_axw_backward): dW = X^T G, a tall-skinny reduction over n -------------------------------------------
+// dW[dim x c] = X[n x dim]^T G[n x cp] with n in the 10^5..10^6 range and dim, c <= 256.  v_mfma_f32_32x32x2_f32 with its k = the n
+// dimension: A operand lane l = X[r + (l>>5)][i0 + (l&31)], B operand lane l = G[r + (l>>5)][j0 + (l&31)] -- both one 4-byte load
+// per lane of two 128-byte row runs, so X needs only 4-byte alignment.  C/D: col j = l&31, row i = (reg&3) + 8*(reg>>2) + 4*(l>>5).
+//   * a workgroup of 4 waves owns one n-slice and a 128 x 128 block of dW: wave w the 32 rows i0 = 128 gi + 32 w, its four accumulators
+//     the column tiles j0 = 128 gj + 32 t (the four waves read the same G runs: L1 hits);
+//   * each (slice, block) writes one partial dim x c sum, summed afterwards in slice order by axw_dw_reduce_kernel: no atomics, the
+//     result is the same bits on every run.  Every entry is one fp32 fmaf chain over its slice's rows in ascending order (two rows per
+//     MFMA step, row r then r+1), then S - 1 additions of the partials: L_dW = ceil(n / S) + S roundings at most (include/flex_axw.h);
+//   * rows past the slice end and columns i >= dim read as 0 and are not stored; G's padding columns c .. cp-1 are computed and dropped.
+namespace flex_axw_detail {
+
+constexpr int kDwPairs = 16;  // row pairs loaded ahead of the MFMAs that use them (4 and 16 measured the same on the flickr and reddit shapes)
+
+__global__ __launch_bounds__(256) void axw_dw_kernel(const float *__restrict__ X, const float *__restrict__ G, float *__restrict__ part,
+                                                     int n, int dim, int c, int cp, int rows_per_slice) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int slice = blockIdx.x;
+    const int gi = blockIdx.y % ((dim + 127) / 128), gj = blockIdx.y / ((dim + 127) / 128);
+    const int i0 = gi * 128 + wave * 32;
+    if (i0 >= dim) return;  // wave-uniform, and there is no barrier
+    const int j0 = gj * 128;
+    const int nt = min(4, (cp - j0) / 32);
+    const int r_beg = slice * rows_per_slice, r_end = min(n, r_beg + rows_per_slice);
+    const int i = i0 + (lane & 31), h = lane >> 5;
+    const bool i_ok = i < dim;
+    f32x16 acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) acc[t][q] = 0.f;
+
+    float a[kDwPairs], b[kDwPairs][4];
+    auto load = [&](int r0) {
+#pragma unroll
+        for (int p = 0; p < kDwPairs; ++p) {
+            const int r = r0 + 2 * p + h;
+            const bool ok = r < r_end;
+            a[p] = ok && i_ok ? X[static_cast<size_t>(r) * dim + i] : 0.f;
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                b[p][t] = ok && t < nt ? G[static_cast<size_t>(r) * cp + j0 + 32 * t + (lane & 31)] : 0.f;
+        }
+    };
+    load(r_beg);
+    for (int r0 = r_beg; r0 < r_end; r0 += 2 * kDwPairs) {
+        float ca[kDwPairs], cb[kDwPairs][4];
+#pragma unroll
+        for (int p = 0; p < kDwPairs; ++p) {
+            ca[p] = a[p];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) cb[p][t] = b[p][t];
+        }
+        if (r0 + 2 * kDwPairs < r_end) load(r0 + 2 * kDwPairs);  // wave-uniform
+#pragma unroll
+        for (int p = 0; p < kDwPairs; ++p)
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                if (t < nt) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ca[p], cb[p][t], acc[t], 0, 0, 0);
+    }
+    float *dst = part + static_cast<size_t>(slice) * dim * c;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int j = j0 + 32 * t + (lane & 31);
+        if (t >= nt || j >= c) continue;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const int ii = i0 + (q & 3) + 8 * (q >> 2) + 4 * h;
+            if (ii < dim) dst[static_cast<size_t>(ii) * c + j] = acc[t][q];
+        }
+    }
+}
+
+// dW[e] = part[0][e] + part[1][e] + ... + part[S-1][e], left to right; the loads go out 16 at a time (one per add, each waiting for the
+// last, cost 256 L2 round trips: 80 us at S = 256), the adds stay in slice order
+__global__ __launch_bounds__(256) void axw_dw_reduce_kernel(const float *__restrict__ part, float *__restrict__ dW, int count, int slices) {
+    constexpr int kBatch = 16;
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= count) return;
+    float s = part[e];
+    int k = 1;
+    for (; k + kBatch <= slices; k += kBatch) {
+        float v[kBatch];
+#pragma unroll
+        for (int j = 0; j < kBatch; ++j) v[j] = part[static_cast<size_t>(k + j) * count + e];
+#pragma unroll
+        for (int j = 0; j < kBatch; ++j) s += v[j];
+    }
+    for (; k < slices; ++k) s += part[static_cast<size_t>(k) * count + e];
+    dW[e] = s;
+}
+
+// Wt[k][i] = W[i][k] for i < dim, k < c (W: dim x c, Wt: ld floats a row); Wt's other entries are left as they are
+__global__ __launch_bounds__(256) void axw_transpose_kernel(const float *__restrict__ W, float *__restrict__ Wt, int dim, int c, int ld) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= dim * c) return;
+    const int k = e / dim, i = e % dim;
+    Wt[static_cast<size_t>(k) * ld + i] = W[static_cast<size_t>(i) * c + k];
+}
+
+}  // namespace flex_axw_detail
+
+// n-slices of the dW kernel: about 256 rows each, at most one per CU (each slice's 4 waves per 128 x 128 block of dW)
+extern "C" int flex_axw_dw_slices(int n, int n_cus) { return n <= 0 ? 0 : std::max(1, std::min(n_cus, (n + 255) / 256)); }
+
+// dW[dim x c] = X[n x dim]^T G[n x cp] through `part` (flex_axw_dw_slices(n, n_cus) * dim * c floats).  Takes n >= 32, 0 < dim <= 256,
+// dim % 4 == 0, 0 < c <= cp <= 256, cp % 32 == 0, n_cus > 0; anything else returns hipErrorInvalidValue before a launch.
+extern "C" hipError_t flex_axw_dw_launch(const float *X, const float *G, float *dW, float *part, int n, int dim, int c, int cp, int n_cus,
+                                         hipStream_t s) {
+    using namespace flex_axw_detail;
+    if (!X || !G || !dW || !part || n < 32 || dim <= 0 || dim > 256 || dim % 4 != 0 || c <= 0 || c > cp || cp > 256 || cp % 32 != 0 ||
+        n_cus <= 0)
+        return hipErrorInvalidValue;
+    const int slices = flex_axw_dw_slices(n, n_cus);
+    const int rows = (n + slices - 1) / slices;
+    const dim3 grid(static_cast<unsigned>(slices), static_cast<unsigned>(((dim + 127) / 128) * ((cp + 127) / 128)));
+    hipLaunchKernelGGL(axw_dw_kernel, grid, dim3(256), 0, s, X, G, part, n, dim, c, cp, rows);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const int count = dim * c;
+    hipLaunchKernelGGL(axw_dw_reduce_kernel, dim3(static_cast<unsigned>((count + 255) / 256)), dim3(256), 0, s, part, dW, count, slices);
+    return hipGetLastError();
+}
+
+// Wt[c x ld] := W[dim x c]^T in its first dim columns (ld >= dim); the rest of Wt is not written
+extern "C" hipError_t flex_axw_transpose_launch(const float *W, float *Wt, int dim, int c, int ld, hipStream_t s) {
+    using namespace flex_axw_detail;
+    if (!W || !Wt || dim <= 0 || c <= 0 || ld < dim) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(axw_transpose_kernel, dim3(static_cast<unsigned>((dim * c + 255) / 256)), dim3(256), 0, s, W, Wt, dim, c, ld);
+    return hipGetLastError();
+}

@@ -18,6 +18,7 @@
 #include <cstddef>
 #include <cstdlib>
 #include <new>
+#include <vector>
 
 #include "host_parallel.h"
 #include "plan.h"
@@ -182,7 +183,48 @@ static bool tuning_ok(const flex_plan_tuning &t) {
     return true;
 }
 
-static int create_common(flex_plan **out, const flex_csr *hostA, int64_t row_begin, int64_t row_end,
+// FLEX_PLAN_TRANSPOSE: the CSR of A^T, built by a stable counting sort -- row c of A^T lists the rows of A that hold column c in
+// ascending order, a duplicate (r, c) pair keeping its CSR order -- so that the plan is exactly the plan of that CSR passed as given.
+// One sequential pass: the result cannot depend on the host thread count.  Owned by the caller's create call and freed with it.
+struct TransposedCsr {
+    std::vector<uint32_t> rowPtr, col;
+    std::vector<float> vals;
+    flex_csr csr{};
+};
+
+static int transpose_csr(const flex_csr *A, TransposedCsr *t) {
+    int rc = validate_csr(A);
+    if (rc) return rc;
+    if (A->n >= INT32_MAX) return FLEX_ERR_UNSUPPORTED;
+    const size_t nnz = static_cast<size_t>(A->nnz);
+    try {
+        t->rowPtr.assign(static_cast<size_t>(A->n) + 1, 0u);
+        t->col.resize(nnz);
+        t->vals.resize(nnz);
+    } catch (const std::bad_alloc &) {
+        return FLEX_ERR_NOMEM;
+    }
+    for (size_t e = 0; e < nnz; ++e) ++t->rowPtr[A->col[e] + 1];
+    for (int32_t c = 0; c < A->n; ++c) t->rowPtr[c + 1] += t->rowPtr[c];
+    std::vector<uint32_t> pos;  // next free slot of every row of A^T
+    try {
+        pos.assign(t->rowPtr.begin(), t->rowPtr.end() - 1);
+    } catch (const std::bad_alloc &) {
+        return FLEX_ERR_NOMEM;
+    }
+    for (int32_t r = 0; r < A->m; ++r)
+        for (uint32_t e = A->rowPtr[r]; e < A->rowPtr[r + 1]; ++e) {
+            const uint32_t d = pos[A->col[e]]++;
+            t->col[d] = static_cast<uint32_t>(r);
+            t->vals[d] = A->vals[e];
+        }
+    t->csr = flex_csr{A->n, A->m, A->nnz, t->rowPtr.data(), nnz ? t->col.data() : nullptr, nnz ? t->vals.data() : nullptr};
+    return FLEX_OK;
+}
+
+// all_rows: every row of the CSR that is planned (A's, or A^T's under FLEX_PLAN_TRANSPOSE; row_begin / row_end are not read),
+// otherwise the caller's range [row_begin, row_end) of that CSR
+static int create_common(flex_plan **out, const flex_csr *hostA, bool all_rows, int64_t row_begin, int64_t row_end,
                          const int32_t *col_map, const int32_t *dst_map, int k, int device, unsigned flags,
                          int ldb = 0, int ldc = 0, const flex_plan_tuning *tuning_in = nullptr) {
     if (!out) return FLEX_ERR_INVALID;
@@ -195,10 +237,24 @@ static int create_common(flex_plan **out, const flex_csr *hostA, int64_t row_beg
     if (ldc == 0) ldc = k;
     if (ldb < k || ldc < k) return FLEX_ERR_INVALID;
     const unsigned order = flags & FLEX_ORDER_MASK;
-    if (order > FLEX_ORDER_GORDER || (flags & ~(FLEX_ORDER_MASK | FLEX_PLAN_STATS | FLEX_PLAN_AUTOTUNE | FLEX_PLAN_XCD_INTERLEAVE))) return FLEX_ERR_INVALID;
-    int rc = validate_csr(hostA);
+    if (order > FLEX_ORDER_GORDER ||
+        (flags & ~(FLEX_ORDER_MASK | FLEX_PLAN_STATS | FLEX_PLAN_AUTOTUNE | FLEX_PLAN_XCD_INTERLEAVE | FLEX_PLAN_TRANSPOSE)))
+        return FLEX_ERR_INVALID;
+    int rc = FLEX_OK;
+    TransposedCsr at;
+    if (flags & FLEX_PLAN_TRANSPOSE) {
+        rc = transpose_csr(hostA, &at);
+        if (rc) return rc;
+        hostA = &at.csr;
+        flags &= ~FLEX_PLAN_TRANSPOSE;
+    }
+    rc = validate_csr(hostA);
     if (rc) return rc;
     if (hostA->m >= INT32_MAX) return FLEX_ERR_UNSUPPORTED;
+    if (all_rows) {
+        row_begin = 0;
+        row_end = hostA->m;
+    }
     if (row_begin < 0 || row_end < row_begin || row_end > hostA->m) return FLEX_ERR_INVALID;
     if (col_map)
         for (int32_t c = 0; c < hostA->n; ++c)
@@ -245,25 +301,25 @@ static int create_common(flex_plan **out, const flex_csr *hostA, int64_t row_beg
 int flex_plan_create(flex_plan **out, const flex_csr *hostA, int k, int device, unsigned flags) {
     if (!hostA) return FLEX_ERR_INVALID;
     // dst_map == NULL means slice-local rows, which for the full range is the identity
-    return create_common(out, hostA, 0, hostA->m, nullptr, nullptr, k, device, flags);
+    return create_common(out, hostA, true, 0, 0, nullptr, nullptr, k, device, flags);
 }
 
 int flex_plan_create_ld(flex_plan **out, const flex_csr *hostA, int k, int ldb, int ldc, int device, unsigned flags) {
     if (!hostA || ldb < k || ldc < k) return FLEX_ERR_INVALID;
-    return create_common(out, hostA, 0, hostA->m, nullptr, nullptr, k, device, flags, ldb, ldc);
+    return create_common(out, hostA, true, 0, 0, nullptr, nullptr, k, device, flags, ldb, ldc);
 }
 
 int flex_plan_create_mapped(flex_plan **out, const flex_csr *hostA, const int32_t *vo_mp, int k, int device,
                             unsigned flags) {
     if (!hostA) return FLEX_ERR_INVALID;
     if (vo_mp && hostA->m != hostA->n) return FLEX_ERR_INVALID;
-    return create_common(out, hostA, 0, hostA->m, vo_mp, vo_mp, k, device, flags);
+    return create_common(out, hostA, true, 0, 0, vo_mp, vo_mp, k, device, flags);
 }
 
 int flex_plan_create_rows(flex_plan **out, const flex_csr *hostA, int64_t row_begin, int64_t row_end,
                           const int32_t *col_map, int k, int device, unsigned flags) {
     if ((flags & FLEX_ORDER_MASK) != FLEX_ORDER_NATURAL) return FLEX_ERR_INVALID;
-    return create_common(out, hostA, row_begin, row_end, col_map, nullptr, k, device, flags);
+    return create_common(out, hostA, false, row_begin, row_end, col_map, nullptr, k, device, flags);
 }
 
 int flex_plan_create_ex(flex_plan **out, const flex_plan_desc *d) {
@@ -274,10 +330,10 @@ int flex_plan_create_ex(flex_plan **out, const flex_plan_desc *d) {
     // without the flag the range members must be zero: a shard range passed by a caller that forgot the flag (or was built before
     // the flag existed) would otherwise get a plan over ALL rows and flex_spmm would write past the shard's C buffer
     if (all_rows && (d->row_begin != 0 || d->row_end != 0)) return FLEX_ERR_INVALID;
-    const int64_t r0 = d->row_begin, r1 = all_rows ? d->A->m : d->row_end;
+    const int64_t r0 = d->row_begin, r1 = d->row_end;
     if (d->row_map && (!all_rows || d->A->m != d->A->n)) return FLEX_ERR_INVALID;  // a row map renames ALL rows of a graph
     if (!all_rows && (d->flags & FLEX_ORDER_MASK) != FLEX_ORDER_NATURAL) return FLEX_ERR_INVALID;  // reorder first, then shard
-    return create_common(out, d->A, all_rows ? 0 : r0, r1, d->col_map, d->row_map, d->k, d->device, d->flags & ~FLEX_PLAN_ROW_RANGE, d->ldb, d->ldc, tuning);
+    return create_common(out, d->A, all_rows, r0, r1, d->col_map, d->row_map, d->k, d->device, d->flags & ~FLEX_PLAN_ROW_RANGE, d->ldb, d->ldc, tuning);
 }
 
 int flex_spmm(flex_plan *p, const float *dB, float *dC, flex_stream_t stream) {

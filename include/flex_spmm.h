@@ -76,6 +76,15 @@ typedef struct flex_plan flex_plan;
                                             (a loader reordered by RCM / Gorder and planned as given): eighths of
                                             such an order run at different speeds.  FLEX_ORDER_RCM and FLEX_ORDER_GORDER
                                             imply it */
+#define FLEX_PLAN_TRANSPOSE 0x8000u /* plan A^T instead of A: the plan is exactly the plan of the CSR of A^T passed as given (row c
+                                       of A^T lists the rows of A that hold column c in ascending order, duplicates in CSR order),
+                                       built on the host and freed before the call returns.  Every other argument refers to that
+                                       CSR: k, ldb / ldc, the order bits, the shard rows of FLEX_PLAN_ROW_RANGE (columns of A),
+                                       col_map, row_map, vo_mp (right as it is for a loader-permuted A' = P A P^T, whose transpose
+                                       is P A^T P^T), tuning, autotune and stats.  flex_spmm then computes
+                                       C[A.n x k] = A^T B[A.m x k] (the gradient of A B with respect to B), with the accuracy stated
+                                       there for nnz(row) read as nnz(column of A); flex_plan_get_info reports m = A.n, n = A.m.
+                                       A.n >= INT32_MAX: FLEX_ERR_UNSUPPORTED.  All five flex_plan_create* entry points take it */
 
 /* ≙ Mat::Mat + csr2_DiagTiling + alpha_transfer (mat.cu:7-31, 680-942, 268-293):
  * builds the row-panel plan for `hostA` and uploads it to `device`.  The reference's
