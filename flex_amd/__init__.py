@@ -16,6 +16,7 @@ from .binding import (  # noqa: F401
     FLEX_PLAN_ROW_RANGE,
     FLEX_PLAN_XCD_INTERLEAVE,
     FLEX_PLAN_TRANSPOSE,
+    FLEX_PLAN_MUTABLE_VALUES,
     FlexError,
     HostCsr,
     Plan,

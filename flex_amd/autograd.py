@@ -1,6 +1,7 @@
 """torch autograd over the engine: the gradient of C = A B with respect to B is A^T grad_C (a plan made with FLEX_PLAN_TRANSPOSE),
-and the GCN layer Out = A X W (flex_amd.axw.Axw.layer) differentiates through flex_axw_backward.  Gradients for A's values (SDDMM) are
-not computed: asking for them raises.  torch is imported lazily, as in binding.py."""
+and the GCN layer Out = A X W (flex_amd.axw.Axw.layer) differentiates through flex_axw_backward.  With learn_values=True, SparseOperator
+is differentiable in A's values as well: grad_v = SDDMM(grad_C, B) over A's pattern (flex_sddmm), and the values of every forward are
+set into the plans (flex_plan_set_values) without planning again.  torch is imported lazily, as in binding.py."""
 from __future__ import annotations
 
 from . import binding
@@ -36,14 +37,39 @@ def _function():
             gx, gw = h.backward(dOut, X, W, need_x=ctx.needs_input_grad[0], need_w=ctx.needs_input_grad[1])
             return gx, gw, None, None
 
-    return _SpMM, _AxwLayer
+    class _SpMMValues(torch.autograd.Function):
+        """C = A(v) B.  Backward: grad_B = A(v)^T grad_C on the transposed plan, set to THIS forward's v first (another forward may have
+        set other values since); grad_v = SDDMM(grad_C, B) on the forward plan (it reads the pattern only)."""
+
+        @staticmethod
+        def forward(ctx, B, v, op):
+            B, v = B.contiguous(), v.detach().contiguous()
+            op.plan.set_values(v)
+            ctx.op = op
+            ctx.save_for_backward(B, v)
+            return op.plan(B)
+
+        @staticmethod
+        def backward(ctx, grad_C):
+            B, v = ctx.saved_tensors
+            op = ctx.op
+            grad_C = grad_C.contiguous()
+            gB = gv = None
+            if ctx.needs_input_grad[0]:
+                op.plan_t.set_values(v)
+                gB = op.plan_t(grad_C)
+            if ctx.needs_input_grad[1]:
+                gv = op.plan.sddmm(grad_C, B)
+            return gB, gv, None
+
+    return _SpMM, _AxwLayer, _SpMMValues
 
 
 _cache = None
 
 
 def functions():
-    """(_SpMM, _AxwLayer): the autograd Functions, built at first use (torch is imported then)."""
+    """(_SpMM, _AxwLayer, _SpMMValues): the autograd Functions, built at first use (torch is imported then)."""
     global _cache
     if _cache is None:
         _cache = _function()
@@ -51,13 +77,22 @@ def functions():
 
 
 class SparseOperator:
-    """C = A B for a fixed sparse A, differentiable in B: grad_B = A^T grad_C.  Keeps the plan of A (k columns) and the plan of A^T.
-    `a` is an m x n HostCsr; op(B) takes B [n, k] and returns C [m, k], float32 cuda tensors."""
+    """C = A B for a fixed sparse pattern A, differentiable in B: grad_B = A^T grad_C.  Keeps the plan of A (k columns) and the plan of A^T.
+    `a` is an m x n HostCsr; op(B) takes B [n, k] and returns C [m, k], float32 cuda tensors.
+    learn_values=True: both plans are made with FLEX_PLAN_MUTABLE_VALUES and op(B, values=v) -- v a float32 cuda tensor of a.nnz values
+    in a's CSR order -- computes A(v) B, differentiable in B and in v (grad_v = SDDMM(grad_C, B) over A's pattern).  op(B) alone then
+    uses a's own values."""
 
-    def __init__(self, a: binding.HostCsr, k: int, device: int = 0, order: int = binding.FLEX_ORDER_NATURAL, tuning: dict | None = None):
-        self.m, self.n, self.k = a.m, a.n, k
-        self.plan = binding.Plan(a, k, device=device, order=order, tuning=tuning)
-        self.plan_t = binding.Plan(a, k, device=device, order=order, tuning=tuning, transpose=True)
+    def __init__(self, a: binding.HostCsr, k: int, device: int = 0, order: int = binding.FLEX_ORDER_NATURAL, tuning: dict | None = None,
+                 learn_values: bool = False):
+        self.m, self.n, self.k, self.nnz = a.m, a.n, k, a.nnz
+        self.learn_values = learn_values
+        self.plan = binding.Plan(a, k, device=device, order=order, tuning=tuning, mutable_values=learn_values)
+        self.plan_t = binding.Plan(a, k, device=device, order=order, tuning=tuning, transpose=True, mutable_values=learn_values)
+        self._v0 = None
+        if learn_values:
+            import torch
+            self._v0 = torch.from_numpy(a.vals.copy()).to(f"cuda:{device}")
 
     def forward_plan(self, B):
         return self.plan(B)
@@ -66,8 +101,14 @@ class SparseOperator:
         return self.plan_t(G)
 
     def __call__(self, B, values=None):
-        """values: must be None -- A's values are constants of the plan; a gradient for them (SDDMM) is not computed."""
-        if values is not None:
-            raise NotImplementedError("gradients for A's values (SDDMM) are not computed by SparseOperator")
-        return functions()[0].apply(B, self)
+        """values: A's values for this product (learn_values=True only; without it they are constants of the plan and passing them
+        raises).  Differentiable in B and in values."""
+        if not self.learn_values:
+            if values is not None:
+                raise NotImplementedError("gradients for A's values (SDDMM) need SparseOperator(..., learn_values=True)")
+            return functions()[0].apply(B, self)
+        if values is None:
+            values = self._v0
+        assert values.numel() == self.nnz, (values.numel(), self.nnz)
+        return functions()[2].apply(B, values, self)
 

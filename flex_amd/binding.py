@@ -26,6 +26,7 @@ FLEX_PLAN_AUTOTUNE = 0x200
 FLEX_PLAN_ROW_RANGE = 0x1000
 FLEX_PLAN_XCD_INTERLEAVE = 0x2000
 FLEX_PLAN_TRANSPOSE = 0x8000
+FLEX_PLAN_MUTABLE_VALUES = 0x10000
 
 
 class FlexError(RuntimeError):
@@ -138,7 +139,7 @@ SYMBOLS = [
     "flex_csv_save", "flex_csr_save_bin", "flex_csr_load_bin", "flex_csr_fingerprint", "flex_perm_save", "flex_perm_load",
     "flex_host_csr_free", "flex_fill_dense_rand", "flex_order_rcm", "flex_order_cluster", "flex_order_gorder", "flex_perm_csr",
     "flex_order_deg", "flex_order_dfs", "flex_order_rabbit", "flex_shard_rows", "flex_synth_graph", "flex_synth_preset", "flex_strerror", "flex_last_hip_error",
-    "flex_last_hip_error_string", "flex_abi_version",
+    "flex_last_hip_error_string", "flex_abi_version", "flex_plan_set_values", "flex_sddmm",
 ]
 
 _lib = None
@@ -218,6 +219,17 @@ def lib():
         L.flex_abi_version.restype = i32
         _lib = L
     return _lib
+
+
+def _values_fn(name: str):
+    """flex_plan_set_values / flex_sddmm, looked up at first use and not when the library loads: the host-only builds the CPU suite
+    runs against (tests/hostsim, tools/asan_host.sh) have no kernels and so do not define them."""
+    L = lib()
+    f = getattr(L, name)
+    if f.argtypes is None:
+        vp = C.c_void_p
+        f.argtypes = [vp, vp, vp] if name == "flex_plan_set_values" else [vp, vp, vp, vp, vp]
+    return f
 
 
 def _check(rc: int, what: str):
@@ -422,13 +434,18 @@ class Plan:
 
     def __init__(self, a: HostCsr, k: int, device: int = 0, order: int = FLEX_ORDER_NATURAL,
                  vo_mp=None, rows=None, col_map=None, ldb: int | None = None, ldc: int | None = None, tuning: dict | None = None,
-                 transpose: bool = False):
+                 transpose: bool = False, mutable_values: bool = False):
         """tuning: plan-time knobs as a dict of flex_plan_tuning fields (0 / absent = the planner's rule), e.g.
         {"lanes_per_nz": 16, "split_rows": 1, "cluster_no_refine": 1}.
-        transpose: plan A^T (FLEX_PLAN_TRANSPOSE): C [a.n, k] = A^T B [a.m, k]; every other argument refers to A^T."""
+        transpose: plan A^T (FLEX_PLAN_TRANSPOSE): C [a.n, k] = A^T B [a.m, k]; every other argument refers to A^T.
+        mutable_values: FLEX_PLAN_MUTABLE_VALUES -- set_values() and sddmm() work on the plan; both index A's entries in a's CSR
+        order, whatever the plan (transposed, mapped, a shard)."""
         self._h = C.c_void_p()
+        self.src_nnz = a.nnz
         if transpose:
             order |= FLEX_PLAN_TRANSPOSE
+        if mutable_values:
+            order |= FLEX_PLAN_MUTABLE_VALUES
         self._keep = (a, vo_mp, col_map)
         v = a.view()
         L = lib()
@@ -505,6 +522,31 @@ class Plan:
         if out is None:
             out = torch.empty((i["m"], i["k"]), dtype=torch.float32, device=B.device)
         self.spmm(B.data_ptr(), out.data_ptr(), torch.cuda.current_stream(B.device).cuda_stream)
+        return out
+
+    def set_values(self, vals, stream: int | None = None):
+        """flex_plan_set_values: vals is a float32 cuda tensor of a.nnz values in the CSR order of the `a` the plan was made from.
+        Stream-ordered (torch's current stream by default): launches of the plan queued before it read the old values."""
+        import torch
+        assert vals.is_cuda and vals.dtype == torch.float32 and vals.is_contiguous() and vals.numel() == self.src_nnz, "float32 cuda [nnz]"
+        s = torch.cuda.current_stream(vals.device).cuda_stream if stream is None else stream
+        _check(_values_fn("flex_plan_set_values")(self._h, vals.data_ptr(), s), "flex_plan_set_values")
+
+    def sddmm_ptr(self, dG_ptr: int, dB_ptr: int, dOut_ptr: int, stream: int = 0):
+        _check(_values_fn("flex_sddmm")(self._h, dG_ptr, dB_ptr, dOut_ptr, stream), "flex_sddmm")
+
+    def sddmm(self, G, B, out=None):
+        """flex_sddmm: out[e] = <G[dst(e)], B[src(e)]> for the entries e the plan holds (the gradient of C = A(v) B with respect to v),
+        a float32 cuda tensor [a.nnz] in a's CSR order.  G: [m, k] like C, B: [n, k] like B.  Entries the plan does not hold (other
+        shards) keep what `out` held; a new `out` starts at zero."""
+        import torch
+        i = self.info()
+        assert G.is_cuda and G.dtype == torch.float32 and G.is_contiguous() and tuple(G.shape) == (i["m"], i["k"])
+        assert B.is_cuda and B.dtype == torch.float32 and B.is_contiguous() and tuple(B.shape) == (i["n"], i["k"])
+        if out is None:
+            out = torch.zeros(self.src_nnz, dtype=torch.float32, device=G.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == self.src_nnz
+        self.sddmm_ptr(G.data_ptr(), B.data_ptr(), out.data_ptr(), torch.cuda.current_stream(G.device).cuda_stream)
         return out
 
     def destroy(self):

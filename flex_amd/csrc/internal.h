@@ -122,6 +122,78 @@ constexpr uint32_t kBundleMinSlots = 4;             // bundles only on tiles wit
 constexpr int kWavesPerBlock = 4;  // 256-thread workgroups
 constexpr int kXcds = 8;           // MI355X: 8 XCDs, each with a private 4 MiB L2
 
+// ---- the value rule of a task's padding, shared by the planner (plan_build.cpp, fill_records) and the value refresh on the GPU
+// (values_kernels.hip, flex_plan_set_values), so that a refreshed plan is bit for bit the plan the planner would have built.
+//
+// Padding behind the `len` real records of a row (or piece, or bundle slot) at `first`, `stride` apart: n_pad more records.
+// The padding never carries value 0 at a live B row where that could change the row's class -- 0 x inf would turn a row's
+// +-inf into NaN (the oracle and the reference have no padding) -- but SHARES the value of one real record (c, v), so a
+// non-finite B row contributes what v itself would and a finite one the same product up to the extra roundings:
+//   * the last record, v normal and at least 2^(n_pad+1) above the subnormal range: v = v/2 + v/4 + ... + v/2^p + v/2^p, every
+//     part exact (power-of-two scaling) -- the form of every plan of values of ordinary size;
+//   * otherwise the last record that allows one of: v = +-inf / NaN / +-0: n_pad copies of (c, v) (the row holds v x B[c]
+//     already, and adding it again keeps the class: inf + inf, NaN, +-0); v finite with an integer significand of at least
+//     n_pad + 1 units (every normal value, a subnormal of at least n_pad + 1 units of 2^-149): n_pad + 1 same-sign parts of that
+//     significand at v's scale, each exact, one of them replacing v;
+//   * none does (every value a nonzero subnormal of at most n_pad units of 2^-149): (c_last, 0) -- the one residual,
+//     include/flex_spmm.h.
+// Integer arithmetic on the bits only: the result cannot depend on a floating-point mode of the host or of the device.
+constexpr uint32_t kNoEntry = 0xFFFFFFFFu;  // FLEX_PLAN_MUTABLE_VALUES: the record -> entry map's mark of a padding record
+
+// bits of the fp32 value u x 2^(e - 150), which the caller knows to be exact: 1 <= u < 2^24, 1 <= e <= 254
+__host__ __device__ inline uint32_t units_at_scale(uint32_t u, uint32_t e) {
+    const int lead = 31 - __builtin_clz(u);  // u in [2^lead, 2^(lead+1))
+    const int biased = static_cast<int>(e) - 23 + lead;
+    if (biased >= 1) return (static_cast<uint32_t>(biased - 1) << 23) + (u << (23 - lead));  // normal: the implicit bit lands on the exponent
+    return u << (e - 1);  // subnormal: u x 2^(e-1) units of 2^-149 (< 2^23 because the value is exact and below 2^-126)
+}
+
+__host__ __device__ inline void pad_values(uint2 *first, uint32_t len, uint32_t n_pad, uint32_t stride) {
+    if (n_pad == 0) return;
+    uint2 *const last = first + static_cast<size_t>(len - 1) * stride;
+    const uint32_t ex = (last->y >> 23) & 0xFFu;  // biased exponent of v
+    if (ex > n_pad + 1 && ex < 0xFFu) {
+        uint32_t bits = last->y;
+        uint2 *q = last;  // the last real record takes v/2, the paddings v/4 ... v/2^p, v/2^p
+        for (uint32_t i = 0; i < n_pad; ++i, q += stride) {
+            bits -= 1u << 23;  // halving: the exponent stays >= 2, so it is exact
+            q->y = bits;
+            q[stride] = make_uint2(q->x, bits);
+        }
+        return;
+    }
+    uint2 *const pad = last + stride;
+    for (uint32_t j = len; j-- > 0;) {
+        uint2 *const d = first + static_cast<size_t>(j) * stride;
+        const uint32_t dex = (d->y >> 23) & 0xFFu, man = d->y & 0x7FFFFFu;
+        if (dex == 0xFFu || (dex == 0 && man == 0)) {  // +-inf, NaN, +-0: copies
+            for (uint32_t i = 0; i < n_pad; ++i) pad[static_cast<size_t>(i) * stride] = *d;
+            return;
+        }
+        const uint32_t sig = dex ? (man | 0x800000u) : man, parts = n_pad + 1;
+        if (sig >= parts) {  // sig = parts * q + r: r parts of q + 1 units, the rest of q, all at v's scale (exact: < 2^24 units)
+            const uint32_t q = sig / parts, r = sig % parts, sign = d->y & 0x80000000u, e = dex ? dex : 1u;
+            d->y = units_at_scale(q + (0 < r ? 1u : 0u), e) | sign;
+            for (uint32_t i = 0; i < n_pad; ++i)
+                pad[static_cast<size_t>(i) * stride] = make_uint2(d->x, units_at_scale(q + (i + 1 < r ? 1u : 0u), e) | sign);
+            return;
+        }
+    }
+    for (uint32_t i = 0; i < n_pad; ++i) pad[static_cast<size_t>(i) * stride] = make_uint2(last->x, 0u);
+}
+
+// FLEX_PLAN_MUTABLE_VALUES: the work items of flex_sddmm -- runs of at most kSdItemRecords real records of one C row, {first record,
+// records, stride between them (1, or S inside a bundle), C row} -- in task order, packed into one group per wave
+constexpr uint32_t kSdItemRecords = 64;
+constexpr uint32_t kSdGroupCost = 32;   // per wave: sum over its items of (passes of 4 records per slot + 1 for the G row)
+constexpr uint32_t kSdGroupItems = 64;
+// lanes of one SDDMM slot: a float4 of the G row each, the smallest power of two >= k / 4 in [4, 64]
+inline int sddmm_lanes(int k) {
+    int w = 4;
+    while (4 * w < k && w < 64) w <<= 1;
+    return w;
+}
+
 // per-thread record of the last HIP failure (flex_last_hip_error)
 void note_hip_error(hipError_t e);
 

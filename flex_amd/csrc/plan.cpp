@@ -75,6 +75,11 @@ void free_plan_device(flex_plan *p) {
     (void)hipFree(p->d_bk_brow);
     (void)hipFree(p->d_bk_link);
     (void)hipFree(p->d_bk_rec);
+    (void)hipFree(p->d_src);
+    (void)hipFree(p->d_vrec);
+    (void)hipFree(p->d_seg);
+    (void)hipFree(p->d_sd_item);
+    (void)hipFree(p->d_sd_grp);
 }
 
 }  // namespace flex
@@ -91,7 +96,7 @@ namespace {
 // not on the value), and the fastest plan is kept.  Costs up to three extra plans and 2 * 4*(n*ldb + m*ldc) bytes for
 // the duration of the call.
 int autotune(flex_plan **pp, const flex_csr *A, int32_t r0, int32_t r1, const int32_t *col_map, const int32_t *dst_map,
-             unsigned flags, const flex_plan_tuning &tuning, std::vector<uint32_t> &sched_cache) {
+             unsigned flags, const flex_plan_tuning &tuning, std::vector<uint32_t> &sched_cache, const uint32_t *entry_of) {
     flex_plan *best = *pp;
     if (best->m == 0 || best->k % 4 != 0 || best->ldb % 4 != 0 || best->ldc % 4 != 0) return FLEX_OK;
     int g_max = 8;
@@ -129,7 +134,7 @@ int autotune(flex_plan **pp, const flex_csr *A, int32_t r0, int32_t r1, const in
         q->m = best->m; q->n = best->n; q->k = best->k; q->device = best->device;
         q->ldb = best->ldb; q->ldc = best->ldc; q->nnz = best->nnz;
         double us = 0.0;
-        int rq = build_plan(q, A, r0, r1, col_map, dst_map, flags, tuning, &sched_cache, g);
+        int rq = build_plan(q, A, r0, r1, col_map, dst_map, flags, tuning, &sched_cache, g, entry_of);
         if (rq == FLEX_OK && hipDeviceSynchronize() != hipSuccess) rq = FLEX_ERR_HIP;
         if (rq == FLEX_OK) time_plan(q, &us);
         if (rq == FLEX_OK && !rc && us < best_us) {
@@ -149,7 +154,7 @@ int autotune(flex_plan **pp, const flex_csr *A, int32_t r0, int32_t r1, const in
             q->m = best->m; q->n = best->n; q->k = best->k; q->device = best->device;
             q->ldb = best->ldb; q->ldc = best->ldc; q->nnz = best->nnz;
             double us = 0.0;
-            int rq = build_plan(q, A, r0, r1, col_map, dst_map, flags, other, &sched_cache, best->lanes_per_nz);
+            int rq = build_plan(q, A, r0, r1, col_map, dst_map, flags, other, &sched_cache, best->lanes_per_nz, entry_of);
             if (rq == FLEX_OK && hipDeviceSynchronize() != hipSuccess) rq = FLEX_ERR_HIP;
             if (rq == FLEX_OK && q->lanes_per_nz == best->lanes_per_nz && (q->n_bundles != 0) != (best->n_bundles != 0)) time_plan(q, &us);
             else rq = FLEX_ERR_UNSUPPORTED;  // nothing to compare (e.g. no row short enough to bundle)
@@ -186,13 +191,15 @@ static bool tuning_ok(const flex_plan_tuning &t) {
 // FLEX_PLAN_TRANSPOSE: the CSR of A^T, built by a stable counting sort -- row c of A^T lists the rows of A that hold column c in
 // ascending order, a duplicate (r, c) pair keeping its CSR order -- so that the plan is exactly the plan of that CSR passed as given.
 // One sequential pass: the result cannot depend on the host thread count.  Owned by the caller's create call and freed with it.
+// want_entries (FLEX_PLAN_MUTABLE_VALUES): also entry[d] = the entry of A that became entry d of A^T -- the sort's permutation, so
+// that the plan's record -> entry map refers to A's CSR order.
 struct TransposedCsr {
-    std::vector<uint32_t> rowPtr, col;
+    std::vector<uint32_t> rowPtr, col, entry;
     std::vector<float> vals;
     flex_csr csr{};
 };
 
-static int transpose_csr(const flex_csr *A, TransposedCsr *t) {
+static int transpose_csr(const flex_csr *A, TransposedCsr *t, bool want_entries) {
     int rc = validate_csr(A);
     if (rc) return rc;
     if (A->n >= INT32_MAX) return FLEX_ERR_UNSUPPORTED;
@@ -201,6 +208,7 @@ static int transpose_csr(const flex_csr *A, TransposedCsr *t) {
         t->rowPtr.assign(static_cast<size_t>(A->n) + 1, 0u);
         t->col.resize(nnz);
         t->vals.resize(nnz);
+        if (want_entries) t->entry.resize(nnz);
     } catch (const std::bad_alloc &) {
         return FLEX_ERR_NOMEM;
     }
@@ -217,9 +225,26 @@ static int transpose_csr(const flex_csr *A, TransposedCsr *t) {
             const uint32_t d = pos[A->col[e]]++;
             t->col[d] = static_cast<uint32_t>(r);
             t->vals[d] = A->vals[e];
+            if (want_entries) t->entry[d] = e;
         }
     t->csr = flex_csr{A->n, A->m, A->nnz, t->rowPtr.data(), nnz ? t->col.data() : nullptr, nnz ? t->vals.data() : nullptr};
     return FLEX_OK;
+}
+
+// FLEX_PLAN_MUTABLE_VALUES: the fingerprint (entry_fp) of the (entry, B row) pairs a plan of rows [r0, r1) holds, taken straight from
+// the caller's CSR A -- for a transposed plan, the entries of A whose COLUMN lies in [r0, r1), each reading B row col_map(its row) --
+// so that flex_plan_self_check compares the device image with the input and not with the planner's own arrays.
+static uint64_t held_entries_fp(const flex_csr *A, bool transposed, int64_t r0, int64_t r1, const int32_t *col_map) {
+    auto brow = [&](uint32_t c) { return col_map ? static_cast<uint32_t>(col_map[c]) : c; };
+    uint64_t fp = 0;
+    if (!transposed) {
+        for (uint32_t e = A->rowPtr[r0]; e < A->rowPtr[r1]; ++e) fp += entry_fp(e, brow(A->col[e]));
+        return fp;
+    }
+    for (int32_t r = 0; r < A->m; ++r)
+        for (uint32_t e = A->rowPtr[r]; e < A->rowPtr[r + 1]; ++e)
+            if (A->col[e] >= r0 && A->col[e] < r1) fp += entry_fp(e, brow(static_cast<uint32_t>(r)));
+    return fp;
 }
 
 // all_rows: every row of the CSR that is planned (A's, or A^T's under FLEX_PLAN_TRANSPOSE; row_begin / row_end are not read),
@@ -229,7 +254,7 @@ static int create_common(flex_plan **out, const flex_csr *hostA, bool all_rows, 
                          int ldb = 0, int ldc = 0, const flex_plan_tuning *tuning_in = nullptr) {
     if (!out) return FLEX_ERR_INVALID;
     *out = nullptr;
-    const flex_plan_tuning tuning = tuning_in ? *tuning_in : flex_plan_tuning{};
+    flex_plan_tuning tuning = tuning_in ? *tuning_in : flex_plan_tuning{};
     if (!tuning_ok(tuning)) return FLEX_ERR_INVALID;
     const HostThreadsScope threads_for_this_call(tuning.host_threads);
     if (k <= 0 || device < 0) return FLEX_ERR_INVALID;
@@ -238,12 +263,20 @@ static int create_common(flex_plan **out, const flex_csr *hostA, bool all_rows, 
     if (ldb < k || ldc < k) return FLEX_ERR_INVALID;
     const unsigned order = flags & FLEX_ORDER_MASK;
     if (order > FLEX_ORDER_GORDER ||
-        (flags & ~(FLEX_ORDER_MASK | FLEX_PLAN_STATS | FLEX_PLAN_AUTOTUNE | FLEX_PLAN_XCD_INTERLEAVE | FLEX_PLAN_TRANSPOSE)))
+        (flags & ~(FLEX_ORDER_MASK | FLEX_PLAN_STATS | FLEX_PLAN_AUTOTUNE | FLEX_PLAN_XCD_INTERLEAVE | FLEX_PLAN_TRANSPOSE | FLEX_PLAN_MUTABLE_VALUES)))
         return FLEX_ERR_INVALID;
+    const bool mut = (flags & FLEX_PLAN_MUTABLE_VALUES) != 0;
+    if (mut) {  // every nonzero on the flat record stream: the dense-tile and hot-block routes keep values in layouts of their own
+        if (tuning.mfma == 1 || tuning.blocks == 1) return FLEX_ERR_UNSUPPORTED;
+        tuning.mfma = 2;
+        tuning.blocks = 2;
+    }
     int rc = FLEX_OK;
+    const flex_csr *const callerA = hostA;
+    const bool transposed = (flags & FLEX_PLAN_TRANSPOSE) != 0;
     TransposedCsr at;
-    if (flags & FLEX_PLAN_TRANSPOSE) {
-        rc = transpose_csr(hostA, &at);
+    if (transposed) {
+        rc = transpose_csr(hostA, &at, mut);
         if (rc) return rc;
         hostA = &at.csr;
         flags &= ~FLEX_PLAN_TRANSPOSE;
@@ -277,10 +310,15 @@ static int create_common(flex_plan **out, const flex_csr *hostA, bool all_rows, 
     p->device = device;
     std::vector<uint32_t> sched_cache;
     const bool tune = (flags & FLEX_PLAN_AUTOTUNE) != 0;
+    const uint32_t *entry_of = transposed && mut && hostA->nnz > 0 ? at.entry.data() : nullptr;
     try {
         rc = build_plan(p, hostA, static_cast<int32_t>(row_begin), static_cast<int32_t>(row_end), col_map, dst_map, flags, tuning,
-                        tune ? &sched_cache : nullptr);
-        if (rc == FLEX_OK && tune) rc = autotune(&p, hostA, static_cast<int32_t>(row_begin), static_cast<int32_t>(row_end), col_map, dst_map, flags, tuning, sched_cache);
+                        tune ? &sched_cache : nullptr, 0, entry_of);
+        if (rc == FLEX_OK && tune) rc = autotune(&p, hostA, static_cast<int32_t>(row_begin), static_cast<int32_t>(row_end), col_map, dst_map, flags, tuning, sched_cache, entry_of);
+        if (rc == FLEX_OK && mut) {
+            p->src_nnz = callerA->nnz;
+            p->ent_fp = held_entries_fp(callerA, transposed, row_begin, row_end, col_map);
+        }
     } catch (const std::bad_alloc &) {  // nothing crosses the C ABI as an exception
         rc = FLEX_ERR_NOMEM;
     } catch (...) {

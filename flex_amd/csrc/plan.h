@@ -68,6 +68,16 @@ struct flex_plan {
     // in-flight guard of a plan that owns a split-row workspace (flex_spmm): the stream of its latest launch
     hipStream_t last_stream = nullptr;
     bool launched = false;
+    // FLEX_PLAN_MUTABLE_VALUES (values_kernels.hip: flex_plan_set_values, flex_sddmm); nullptr / 0 on other plans
+    bool mutable_vals = false;
+    uint32_t *d_src = nullptr;    // [n_records] entry of hostA (CSR order) each record holds; kNoEntry = padding
+    float *d_vrec = nullptr;      // [n_records] the current value of each real record (the plan's copy; 0 on padding)
+    uint4 *d_seg = nullptr;       // [n_segs] padded runs {first record, real records, padding records, stride}: pad_values redoes them
+    uint4 *d_sd_item = nullptr;   // [n_sd_items] SDDMM work items (internal.h, kSdItemRecords)
+    uint32_t *d_sd_grp = nullptr; // [n_sd_groups + 1] first item of each wave's group
+    uint32_t n_segs = 0, n_sd_items = 0, n_sd_groups = 0;
+    int64_t src_nnz = 0;          // nnz of hostA: entry ids are below it
+    uint64_t ent_fp = 0;          // order-free fingerprint of the (entry, B row) pairs the plan holds, taken from hostA (self-check)
 };
 
 namespace flex {
@@ -125,8 +135,19 @@ inline bool operands_vec4(const flex_plan *p, const float *dB, const float *dC) 
 // Rows [r0,r1) of A.  col_map: B row read by column c (NULL = c).  dst_map: C row written by row r (NULL = r - r0,
 // i.e. slice-local).  sched_cache (or NULL): holds the row schedule once it has been computed, so that several
 // candidate plans of one matrix (autotune) order it only once.  force_G (or 0): lanes per record instead of the degree rule.
+// entry_of (or NULL = identity): FLEX_PLAN_MUTABLE_VALUES, the index into the caller's CSR of entry e of A (a transposed plan's A
+// is the caller's A^T, whose entries are a permutation of the caller's).
 int build_plan(flex_plan *p, const flex_csr *A, int32_t r0, int32_t r1, const int32_t *col_map, const int32_t *dst_map,
-               unsigned flags, const flex_plan_tuning &tuning, std::vector<uint32_t> *sched_cache = nullptr, int force_G = 0);
+               unsigned flags, const flex_plan_tuning &tuning, std::vector<uint32_t> *sched_cache = nullptr, int force_G = 0,
+               const uint32_t *entry_of = nullptr);
+
+// FLEX_PLAN_MUTABLE_VALUES: a term of the order-free fingerprint of the (entry, B row) pairs a plan holds (flex_plan_self_check)
+inline uint64_t entry_fp(uint32_t entry, uint32_t brow) {
+    uint64_t z = ((static_cast<uint64_t>(entry) << 32) | brow) + 0x9E3779B97F4A7C15ull;  // splitmix64
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
 
 // ---- block-density detector (dense_tiles.cpp)
 struct DenseTiles {

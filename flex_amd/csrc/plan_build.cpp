@@ -16,6 +16,7 @@
 //   upload_tasks           records / tasks / dense tiles to the device
 //   build_chunk_table      chunk headers in launch order, cut into eight cost-balanced XCD slices; statistics; the
 //                          split-row workspace
+//   upload_value_image     FLEX_PLAN_MUTABLE_VALUES only: record -> entry map, values, padded runs, the SDDMM's walk
 //
 // The result does not depend on the number of host threads (tests/test_planner_host.py compares the images).
 #include <algorithm>
@@ -54,9 +55,11 @@ constexpr uint32_t kMaxTasksPerWave = 63;  // the kernel hands descriptors out b
 class PlanBuilder {
    public:
     PlanBuilder(flex_plan *plan, const flex_csr *csr, int32_t row_begin, int32_t row_end, const int32_t *col_map_, const int32_t *dst_map_,
-                unsigned flags_, const flex_plan_tuning &tuning, std::vector<uint32_t> *sched_cache_, int force_G_, bool want_blocks_ = false)
+                unsigned flags_, const flex_plan_tuning &tuning, std::vector<uint32_t> *sched_cache_, int force_G_, bool want_blocks_ = false,
+                const uint32_t *entry_of_ = nullptr)
         : p(plan), A(csr), r0(row_begin), r1(row_end), m(row_end - row_begin), k(plan->k), col_map(col_map_), dst_map(dst_map_),
-          flags(flags_), order(flags_ & FLEX_ORDER_MASK), force_G(force_G_), want_blocks(want_blocks_), tn(tuning), sched(sched_cache_ ? *sched_cache_ : sched_local),
+          flags(flags_), order(flags_ & FLEX_ORDER_MASK), force_G(force_G_), want_blocks(want_blocks_), mut((flags_ & FLEX_PLAN_MUTABLE_VALUES) != 0),
+          entry_of(entry_of_), tn(tuning), sched(sched_cache_ ? *sched_cache_ : sched_local),
           have_cache(sched_cache_ != nullptr), timing(plan_timing_enabled()), t_last(std::chrono::steady_clock::now()) {}
 
     // The first two stages alone, for the row-block route (build_plan below): the schedule and its inverse.
@@ -90,6 +93,7 @@ class PlanBuilder {
             if ((rc = route_hot_blocks())) return rc;
             lap("hot blocks");
         }
+        if (mut && (tiles.nnz || p->bk_blocks)) return FLEX_ERR_UNSUPPORTED;  // both routes keep values in layouts of their own
         read_knobs();
         if ((rc = cut_rows_into_pieces())) return rc;
         lap("pieces");
@@ -105,6 +109,10 @@ class PlanBuilder {
         lap("upload records/tasks");
         if ((rc = build_chunk_table())) return rc;
         lap("chunk table, stats");
+        if (mut) {
+            if ((rc = upload_value_image())) return rc;
+            lap("value image");
+        }
         return FLEX_OK;
     }
 
@@ -119,6 +127,8 @@ class PlanBuilder {
     const unsigned flags, order;
     const int force_G;
     const bool want_blocks;  // split the matrix: nonzeros with reuse inside a block of rows go to the hot-block image (block_plan.cpp)
+    const bool mut;          // FLEX_PLAN_MUTABLE_VALUES: also the record -> entry map, the padded runs and the SDDMM items
+    const uint32_t *const entry_of;  // ... entry of the caller's CSR behind entry e of A (NULL = e)
     const flex_plan_tuning &tn;  // the caller's knobs: 0 = the rule of the stage that reads it; p->tuning receives what was used
     std::vector<uint32_t> sched_local;
     std::vector<uint32_t> &sched;  // sched[i] = row of A processed i-th
@@ -144,6 +154,7 @@ class PlanBuilder {
     std::vector<uint32_t> row_first_piece;  // [m+1] pieces of schedule position i
     std::vector<uint32_t> pcol;             // 2-D: the records of every row re-grouped by piece (index e - e_base)
     std::vector<float> pval;
+    std::vector<uint32_t> pent;             // 2-D, mutable plans: the index into A's arrays of each entry of pcol/pval
     const uint32_t *rcol = nullptr;  // where piece ranges point: A's arrays (1-D) or pcol/pval (2-D)
     const float *rval = nullptr;
     uint32_t slice_row[kXcds + 1] = {0};  // 2-D: schedule positions of the XCD slices
@@ -166,6 +177,8 @@ class PlanBuilder {
     std::vector<uint32_t> t_beg, t_dst, w_task;  // w_task[c] = first task of chunk c (+ sentinel)
     std::vector<uint2> t_aux;
     RecordVec rec;  // filled in parallel right after it is sized: no zero-fill pass (plan.h)
+    std::vector<uint32_t> rsrc;  // mutable plans: [records] the entry each record holds (kNoEntry = padding)
+    std::vector<float> rvals;    // ... and its value as given (before the padding rule)
     uint32_t slice_chunk[kXcds + 1] = {0};  // 2-D: first chunk of each XCD slice
 
     void lap(const char *what) {
@@ -546,6 +559,7 @@ class PlanBuilder {
         const uint32_t e_base = A->rowPtr[r0];
         pcol.resize(static_cast<size_t>(slice_nnz()));
         pval.resize(static_cast<size_t>(slice_nnz()));
+        if (mut) pent.resize(static_cast<size_t>(slice_nnz()));
         constexpr int64_t kBlk = 1024;  // schedule positions per work item
         const int64_t nblk = (m + kBlk - 1) / kBlk;
         std::vector<std::vector<Piece>> blk(static_cast<size_t>(nblk));
@@ -590,6 +604,7 @@ class PlanBuilder {
                             const uint32_t e = e0 + static_cast<uint32_t>(key[z] & 0xFFFFFFFFu);
                             pcol[o] = A->col[e];
                             pval[o] = A->vals[e];
+                            if (mut) pent[o] = e;
                             ++o;
                         }
                     };
@@ -796,60 +811,19 @@ class PlanBuilder {
             std::memcpy(&bits, &rval[e], 4);
             return make_uint2(p->off32 ? c * row_bytes32 : c, bits);
         };
-        // Padding behind the `len` real records of a row (or piece, or bundle slot) at `first`, `stride` apart: n_pad more records.
-        // The padding never carries value 0 at a live B row where that could change the row's class -- 0 x inf would turn a row's
-        // +-inf into NaN (the oracle and the reference have no padding) -- but SHARES the value of one real record (c, v), so a
-        // non-finite B row contributes what v itself would and a finite one the same product up to the extra roundings:
-        //   * the last record, v normal and at least 2^(n_pad+1) above the subnormal range: v = v/2 + v/4 + ... + v/2^p + v/2^p, every
-        //     part exact (power-of-two scaling) -- the form of every plan of values of ordinary size;
-        //   * otherwise the last record that allows one of: v = +-inf / NaN / +-0: n_pad copies of (c, v) (the row holds v x B[c]
-        //     already, and adding it again keeps the class: inf + inf, NaN, +-0); v finite with an integer significand of at least
-        //     n_pad + 1 units (every normal value, a subnormal of at least n_pad + 1 units of 2^-149): n_pad + 1 same-sign parts of that
-        //     significand at v's scale, each exact, one of them replacing v;
-        //   * none does (every value a nonzero subnormal of at most n_pad units of 2^-149): (c_last, 0) -- the one residual,
-        //     include/flex_spmm.h.
-        auto pad_row = [](uint2 *first, uint32_t len, uint32_t n_pad, uint32_t stride) {
-            if (n_pad == 0) return;
-            uint2 *const last = first + static_cast<size_t>(len - 1) * stride;
-            const uint32_t ex = (last->y >> 23) & 0xFFu;  // biased exponent of v
-            if (ex > n_pad + 1 && ex < 0xFFu) {
-                float part;
-                std::memcpy(&part, &last->y, 4);
-                uint2 *q = last;  // the last real record takes v/2, the paddings v/4 ... v/2^p, v/2^p
-                for (uint32_t i = 0; i < n_pad; ++i, q += stride) {
-                    part *= 0.5f;
-                    uint32_t bits;
-                    std::memcpy(&bits, &part, 4);
-                    q->y = bits;
-                    q[stride] = make_uint2(q->x, bits);
-                }
-                return;
-            }
-            uint2 *const pad = last + stride;
-            for (uint32_t j = len; j-- > 0;) {
-                uint2 *const d = first + static_cast<size_t>(j) * stride;
-                const uint32_t dex = (d->y >> 23) & 0xFFu, man = d->y & 0x7FFFFFu;
-                if (dex == 0xFFu || (dex == 0 && man == 0)) {  // +-inf, NaN, +-0: copies
-                    for (uint32_t i = 0; i < n_pad; ++i) pad[static_cast<size_t>(i) * stride] = *d;
-                    return;
-                }
-                const uint32_t sig = dex ? (man | 0x800000u) : man, parts = n_pad + 1;
-                if (sig >= parts) {  // sig = parts * q + r: r parts of q + 1 units, the rest of q, all at v's scale (exact: < 2^24 units)
-                    const uint32_t q = sig / parts, r = sig % parts, sign = d->y & 0x80000000u;
-                    const int scale = static_cast<int>(dex ? dex : 1u) - 150;
-                    auto part = [&](uint32_t i) {
-                        const float f = std::ldexp(static_cast<float>(q + (i < r ? 1u : 0u)), scale);
-                        uint32_t bits;
-                        std::memcpy(&bits, &f, 4);
-                        return bits | sign;
-                    };
-                    d->y = part(0);
-                    for (uint32_t i = 0; i < n_pad; ++i) pad[static_cast<size_t>(i) * stride] = make_uint2(d->x, part(i + 1));
-                    return;
-                }
-            }
-            for (uint32_t i = 0; i < n_pad; ++i) pad[static_cast<size_t>(i) * stride] = make_uint2(last->x, 0u);
+        // mutable plans: which entry of the caller's CSR record `at` holds, and its value as given (the padding rule may change the
+        // record's value; flex_plan_set_values starts from these)
+        if (mut) {
+            rsrc.assign(rec.size(), kNoEntry);
+            rvals.assign(rec.size(), 0.0f);
+        }
+        auto note_entry = [&](size_t at, uint32_t e) {
+            if (!mut) return;
+            const uint32_t i = two_d ? pent[e] : e;  // index into A's arrays
+            rsrc[at] = entry_of ? entry_of[i] : i;
+            rvals[at] = rval[e];
         };
+        // the padding of a run of records: internal.h, pad_values (shared with the refresh on the GPU)
         parallel_chunks((static_cast<int64_t>(n_tasks) + kTaskBlk - 1) / kTaskBlk, [&](int64_t b) {
             for (int64_t t = b * kTaskBlk; t < std::min<int64_t>(n_tasks, (b + 1) * kTaskBlk); ++t) {
                 const TaskSpec &ts = tasks[t];
@@ -863,9 +837,12 @@ class PlanBuilder {
                         if (s < ts.rows) {
                             const Piece &pc = pieces[emit[bundle_piece[ts.ref + s]]];
                             len = pc.end - pc.beg;
-                            for (uint32_t j = 0; j < len; ++j) base[static_cast<size_t>(j) * S + s] = record_of(pc.beg + j);
+                            for (uint32_t j = 0; j < len; ++j) {
+                                base[static_cast<size_t>(j) * S + s] = record_of(pc.beg + j);
+                                note_entry(t_beg[t] + static_cast<size_t>(j) * S + s, pc.beg + j);
+                            }
                         }
-                        if (len > 0) pad_row(base + s, len, ts.steps - len, S);
+                        if (len > 0) pad_values(base + s, len, ts.steps - len, S);
                         else
                             for (uint32_t j = 0; j < ts.steps; ++j) base[static_cast<size_t>(j) * S + s] = make_uint2(base[static_cast<size_t>(j) * S].x, 0u);
                     }
@@ -884,7 +861,10 @@ class PlanBuilder {
                 }
                 uint2 *o = base;
                 if (far_window == 0) {
-                    for (uint32_t e = pc.beg; e < pc.end; ++e) *o++ = record_of(e);
+                    for (uint32_t e = pc.beg; e < pc.end; ++e) {
+                        note_entry(static_cast<size_t>(o - rec.data()), e);
+                        *o++ = record_of(e);
+                    }
                 } else {
                     // FAR records first (tuning.far_first): a column whose vertex sits far from the row in the schedule is a likely L2
                     // miss, a near one a likely hit.  A wave's gathers return in issue order, so a group of U gathers waits for its
@@ -897,18 +877,21 @@ class PlanBuilder {
                         const int64_t d = cp - static_cast<int64_t>(colpos.empty() ? r : i);
                         return (d < 0 ? -d : d) > static_cast<int64_t>(far_window);
                     };
-                    for (uint32_t e = pc.beg; e < pc.end; ++e)
-                        if (is_far(e)) *o++ = record_of(e);
-                    for (uint32_t e = pc.beg; e < pc.end; ++e)
-                        if (!is_far(e)) *o++ = record_of(e);
+                    for (int near = 0; near < 2; ++near)
+                        for (uint32_t e = pc.beg; e < pc.end; ++e)
+                            if (is_far(e) != (near == 1)) {
+                                note_entry(static_cast<size_t>(o - rec.data()), e);
+                                *o++ = record_of(e);
+                            }
                 }
                 // pad to a whole number of steps
                 uint2 *const end = rec.data() + t_beg[t + 1];
-                if (o > base) pad_row(base, static_cast<uint32_t>(o - base), static_cast<uint32_t>(end - o), 1u);
+                if (o > base) pad_values(base, static_cast<uint32_t>(o - base), static_cast<uint32_t>(end - o), 1u);
             }
         });
         pcol = std::vector<uint32_t>();
         pval = std::vector<float>();
+        pent = std::vector<uint32_t>();
     }
 
     int upload_tasks() {
@@ -939,6 +922,61 @@ class PlanBuilder {
             if ((rc = upload(&p->d_rt_ptr, tiles.rt_ptr, &p->device_bytes))) return rc;
             if ((rc = upload(&p->d_rt_rows, tiles.rt_rows, &p->device_bytes))) return rc;
         }
+        return FLEX_OK;
+    }
+
+    // FLEX_PLAN_MUTABLE_VALUES: what flex_plan_set_values and flex_sddmm read besides the plan itself (values_kernels.hip).
+    //   d_src / d_vrec  the entry and the value as given of every record (kNoEntry / 0 on padding): the refresh scatters the new values
+    //                   into the real records, the SDDMM writes its result by entry
+    //   d_seg           every run of real records with padding behind it: the refresh redoes pad_values on each (runs are disjoint)
+    //   d_sd_item/grp   the SDDMM's walk: runs of at most kSdItemRecords real records of one C row in task order -- the schedule the
+    //                   SpMM of the plan walks -- packed into one group per wave
+    int upload_value_image() {
+        std::vector<uint4> seg, item;
+        std::vector<uint32_t> grp;
+        const uint32_t W = static_cast<uint32_t>(sddmm_lanes(k)), per_pass = 4u * (64u / W);
+        uint32_t g_cost = 0, g_items = 0;
+        auto add_run = [&](uint32_t first, uint32_t len, uint32_t n_pad, uint32_t stride, uint32_t row) {
+            if (len > 0 && n_pad > 0) seg.push_back(make_uint4(first, len, n_pad, stride));
+            for (uint32_t j = 0; j < len; j += kSdItemRecords) {
+                const uint32_t cnt = std::min(kSdItemRecords, len - j), cost = (cnt + per_pass - 1) / per_pass + 1;
+                if (grp.empty() || g_cost + cost > kSdGroupCost || g_items == kSdGroupItems) {
+                    grp.push_back(static_cast<uint32_t>(item.size()));
+                    g_cost = g_items = 0;
+                }
+                item.push_back(make_uint4(first + j * stride, cnt, stride, row));
+                g_cost += cost;
+                ++g_items;
+            }
+        };
+        for (size_t t = 0; t < tasks.size(); ++t) {
+            const TaskSpec &ts = tasks[t];
+            if (ts.rows) {
+                for (uint32_t s = 0; s < ts.rows; ++s) {
+                    const Piece &pc = pieces[emit[bundle_piece[ts.ref + s]]];
+                    const uint32_t len = pc.end - pc.beg;
+                    add_run(t_beg[t] + s, len, ts.steps - len, S, dst_of(sched[pc.spos]));
+                }
+            } else {
+                const Piece &pc = pieces[emit[ts.ref]];
+                const uint32_t len = pc.end - pc.beg;
+                add_run(t_beg[t], len, t_beg[t + 1] - t_beg[t] - len, 1u, dst_of(sched[pc.spos]));
+            }
+        }
+        grp.push_back(static_cast<uint32_t>(item.size()));
+        p->mutable_vals = true;
+        p->tuning.blocks = 2;  // (mfma: the caller's tuning was set to 2 by create_common)
+        p->n_segs = static_cast<uint32_t>(seg.size());
+        p->n_sd_items = static_cast<uint32_t>(item.size());
+        p->n_sd_groups = static_cast<uint32_t>(grp.size() - 1);
+        int rc;
+        if ((rc = upload(&p->d_src, rsrc, &p->device_bytes))) return rc;
+        if ((rc = upload(&p->d_vrec, rvals, &p->device_bytes))) return rc;
+        if ((rc = upload(&p->d_seg, seg, &p->device_bytes))) return rc;
+        if ((rc = upload(&p->d_sd_item, item, &p->device_bytes))) return rc;
+        if ((rc = upload(&p->d_sd_grp, grp, &p->device_bytes))) return rc;
+        rsrc = std::vector<uint32_t>();
+        rvals = std::vector<float>();
         return FLEX_OK;
     }
 
@@ -1049,7 +1087,7 @@ class PlanBuilder {
 }  // namespace
 
 int build_plan(flex_plan *p, const flex_csr *A, int32_t r0, int32_t r1, const int32_t *col_map, const int32_t *dst_map, unsigned flags,
-               const flex_plan_tuning &tuning, std::vector<uint32_t> *sched_cache, int force_G) try {
+               const flex_plan_tuning &tuning, std::vector<uint32_t> *sched_cache, int force_G, const uint32_t *entry_of) try {
     // Hot blocks need the float4 path's shapes, 32-bit B offsets, whole 64-column tiles' worth of k, and no forced tile width
     // (autotune candidates stay flat).
     const bool block_shapes = p->k % 4 == 0 && p->k >= 64 && p->ldb % 4 == 0 && p->ldc % 4 == 0 &&
@@ -1076,7 +1114,7 @@ int build_plan(flex_plan *p, const flex_csr *A, int32_t r0, int32_t r1, const in
         if (plan_timing_enabled()) std::fprintf(stderr, "plan: hot share of 480-row blocks (thr 3, every 16th) %.3f\n", share);
         want_blocks = share >= 0.72;
     }
-    return PlanBuilder(p, A, r0, r1, col_map, dst_map, flags, tuning, sched_cache, force_G, want_blocks).run();
+    return PlanBuilder(p, A, r0, r1, col_map, dst_map, flags, tuning, sched_cache, force_G, want_blocks, entry_of).run();
 } catch (const std::bad_alloc &) {  // any host allocation of any stage
     return FLEX_ERR_NOMEM;
 }

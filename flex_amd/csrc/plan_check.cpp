@@ -145,6 +145,69 @@ int flex_plan_measure_imbalance(flex_plan *p, const float *dB, float *dC, flex_s
     return FLEX_ERR_NOMEM;
 }
 
+// FLEX_PLAN_MUTABLE_VALUES: the value image read back.  Every entry the plan holds sits in exactly one real record, and the multiset of
+// (entry, B row) pairs the records name has the fingerprint create_common took from the caller's CSR (so each record reads its entry's
+// column, after col_map); the padded runs lie inside the stream, real records first and padding after; every record's bits are what
+// pad_values -- the rule the planner and the refresh share -- derives from the plan's kept values, and padding outside every run
+// carries value 0 (the empty slots of a bundle); the SDDMM's items cover every real record exactly once, in groups that tile them.
+static int check_value_image(const flex_plan *p, const std::vector<uint2> &rec, uint64_t row_bytes) {
+    const size_t nr = rec.size();
+    std::vector<uint32_t> src(nr), grp(static_cast<size_t>(p->n_sd_groups) + 1);
+    std::vector<float> vrec(nr);
+    std::vector<uint4> seg(p->n_segs), item(p->n_sd_items);
+    int cur = -1;
+    FLEX_HIP_TRY(hipGetDevice(&cur));
+    if (cur != p->device) FLEX_HIP_TRY(hipSetDevice(p->device));
+    auto down = [&](void *dst, const void *s, size_t bytes) { return bytes == 0 || hipMemcpy(dst, s, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
+    const bool ok = down(src.data(), p->d_src, nr * 4) && down(vrec.data(), p->d_vrec, nr * 4) && down(seg.data(), p->d_seg, seg.size() * sizeof(uint4)) &&
+                    down(item.data(), p->d_sd_item, item.size() * sizeof(uint4)) && down(grp.data(), p->d_sd_grp, grp.size() * 4);
+    if (cur != p->device) (void)hipSetDevice(cur);
+    if (!ok) return FLEX_ERR_HIP;
+    // entries: each once, the pairs' fingerprint
+    std::vector<uint8_t> seen(static_cast<size_t>(p->src_nnz), 0);
+    int64_t real = 0;
+    uint64_t fp = 0;
+    for (size_t i = 0; i < nr; ++i) {
+        if (src[i] == kNoEntry) continue;
+        if (src[i] >= static_cast<uint64_t>(p->src_nnz) || seen[src[i]]++) return FLEX_ERR_FORMAT;
+        ++real;
+        fp += entry_fp(src[i], static_cast<uint32_t>(p->off32 ? rec[i].x / row_bytes : rec[i].x));
+    }
+    if (real != p->nnz || fp != p->ent_fp) return FLEX_ERR_FORMAT;
+    // the records' bits, derived again from the kept values by the shared rule
+    std::vector<uint2> want(rec);
+    for (size_t i = 0; i < nr; ++i)
+        if (src[i] != kNoEntry) want[i].y = __builtin_bit_cast(uint32_t, vrec[i]);
+    std::vector<uint8_t> in_run(nr, 0);
+    for (const uint4 &s : seg) {
+        if (s.y == 0 || s.z == 0 || s.w == 0 || s.x + (static_cast<uint64_t>(s.y) + s.z - 1) * s.w >= nr) return FLEX_ERR_FORMAT;
+        for (uint64_t j = 0; j < static_cast<uint64_t>(s.y) + s.z; ++j) {
+            const size_t i = s.x + j * s.w;
+            if (in_run[i]++ || (src[i] == kNoEntry) != (j >= s.y)) return FLEX_ERR_FORMAT;
+        }
+        pad_values(want.data() + s.x, s.y, s.z, s.w);
+    }
+    for (size_t i = 0; i < nr; ++i) {
+        if (want[i].x != rec[i].x || want[i].y != rec[i].y) return FLEX_ERR_FORMAT;
+        if (src[i] == kNoEntry && !in_run[i] && rec[i].y != 0) return FLEX_ERR_FORMAT;
+    }
+    // the SDDMM's walk
+    if (grp.front() != 0 || grp.back() != p->n_sd_items) return FLEX_ERR_FORMAT;
+    for (uint32_t g = 0; g < p->n_sd_groups; ++g)
+        if (grp[g] >= grp[g + 1] || grp[g + 1] - grp[g] > kSdGroupItems) return FLEX_ERR_FORMAT;
+    std::vector<uint8_t> walked(nr, 0);
+    for (const uint4 &it : item) {
+        if (it.y == 0 || it.y > kSdItemRecords || it.z == 0 || it.w >= p->c_rows || it.x + static_cast<uint64_t>(it.y - 1) * it.z >= nr) return FLEX_ERR_FORMAT;
+        for (uint32_t j = 0; j < it.y; ++j) {
+            const size_t i = it.x + static_cast<size_t>(j) * it.z;
+            if (src[i] == kNoEntry || walked[i]++) return FLEX_ERR_FORMAT;
+        }
+    }
+    for (size_t i = 0; i < nr; ++i)
+        if ((src[i] != kNoEntry) != (walked[i] == 1)) return FLEX_ERR_FORMAT;
+    return FLEX_OK;
+}
+
 // ≙ the reference's tiler round-trip (mat.cu:905-940: every entry of the pillar format exists exactly once,
 // the queues are contiguous): read the plan's DEVICE image back and check that it is a partition --
 // chunks tile the tasks, tasks tile the records, every record names a valid B row, every C row is written by
@@ -381,6 +444,10 @@ int flex_plan_self_check(const flex_plan *p) try {
     if (p->c_rows == p->m)
         for (uint8_t w : written)
             if (w != 1) return FLEX_ERR_FORMAT;
+    if (p->mutable_vals) {
+        const int rc = check_value_image(p, rec, row_bytes);
+        if (rc) return rc;
+    }
     return FLEX_OK;
 } catch (const std::bad_alloc &) {
     return FLEX_ERR_NOMEM;

@@ -24,7 +24,8 @@
 extern "C" {
 #endif
 
-#define FLEX_ABI_VERSION 3 /* 3: plan-time knobs leave the environment for the struct flex_plan_tuning, flex_plan_desc.tuning, flex_plan_get_tuning,
+#define FLEX_ABI_VERSION 3 /* 3 also covers the purely additive FLEX_PLAN_MUTABLE_VALUES, flex_plan_set_values and flex_sddmm (no struct grew).
+                              3: plan-time knobs leave the environment for the struct flex_plan_tuning, flex_plan_desc.tuning, flex_plan_get_tuning,
                               flex_order_cluster_ex, flex_set_host_threads; split rows are summed by a second launch by default.
                               2: flex_plan_info / flex_plan_stats grew; FLEX_PLAN_ROW_RANGE; flex_order_rabbit, flex_plan_measure_imbalance */
 
@@ -85,6 +86,16 @@ typedef struct flex_plan flex_plan;
                                        C[A.n x k] = A^T B[A.m x k] (the gradient of A B with respect to B), with the accuracy stated
                                        there for nnz(row) read as nnz(column of A); flex_plan_get_info reports m = A.n, n = A.m.
                                        A.n >= INT32_MAX: FLEX_ERR_UNSUPPORTED.  All five flex_plan_create* entry points take it */
+#define FLEX_PLAN_MUTABLE_VALUES 0x10000u /* the plan's values may be replaced later (flex_plan_set_values) and the plan can run the SDDMM of
+                                       its pattern (flex_sddmm).  Every nonzero stays on the flat record-stream route: the planner treats
+                                       tuning.mfma and tuning.blocks as 2 ("never") and flex_plan_get_tuning reports 2 for both; an explicit
+                                       mfma = 1 or blocks = 1 with this flag is FLEX_ERR_UNSUPPORTED (the dense-tile route picks its entries by
+                                       their VALUES, and both routes store values in layouts of their own; neither is taken on any BASELINE
+                                       graph).  Combines with every other flag and option of the five create entry points.  Extra device memory:
+                                       8 bytes per record (the record -> entry map and the plan's copy of the values; records = nnz + padding,
+                                       flex_plan_info.n_records), 16 bytes per padded run and per SDDMM work item (a run of at most 64 nonzeros
+                                       of one row), 4 per group of items -- measured 8.6 bytes per nonzero on the reddit shape, 11-13 on graphs of short
+                                       rows (more padding per nonzero), all counted in flex_plan_info.device_bytes.  Without the flag a plan is byte for byte what it was before the flag existed */
 
 /* ≙ Mat::Mat + csr2_DiagTiling + alpha_transfer (mat.cu:7-31, 680-942, 268-293):
  * builds the row-panel plan for `hostA` and uploads it to `device`.  The reference's
@@ -222,6 +233,34 @@ int flex_set_host_threads(int n);
  * nonzero subnormals of at most p units of 2^-149 each, p = the padding records its task needs (< 64 / lanes_per_nz, or < bundle_len
  * in a bundle), may give NaN where C64 is +-inf (its padding carries value 0).  Subnormal inputs and results are kept, not flushed. */
 int flex_spmm(flex_plan *plan, const float *dB, float *dC, flex_stream_t stream);
+
+/* Learnable edge values (FLEX_PLAN_MUTABLE_VALUES plans only; FLEX_ERR_INVALID on any other plan).  No reference counterpart.
+ *
+ * Value refresh: dVals is a device array of hostA->nnz floats in the CSR order of the hostA passed to the create call -- for EVERY
+ * kind of plan: a transposed plan takes the same vector as the plan of A, a shard plan reads its own rows' entries of the full
+ * vector.  The value half of every record is rewritten on the GPU, padding included, so that afterwards the plan's device image is
+ * bit for bit the image the create call would have built from the same CSR with these values (one padding rule for both:
+ * flex_amd/csrc/internal.h, pad_values).  Asynchronous on `stream`; no allocation, no host synchronisation (safe to capture in a
+ * hipGraph).  Ordering is the caller's, as for writing B: the call must be ordered after every launch of the plan that still reads
+ * the old values, and the launches that should see the new values after it (one stream does both).  Moves 20 bytes per record
+ * (map, value, the plan's copy, the record's value half) plus the padded runs again. */
+int flex_plan_set_values(flex_plan *plan, const float *dVals, flex_stream_t stream);
+
+/* SDDMM over the plan's pattern, defined as the adjoint of the plan's own SpMM with respect to its values: the plan computes
+ * C[dst(e)] += v_e B[src(e)] over the entries e it holds, and this writes
+ *     dOut[e] = sum_j G[dst(e), j] B[src(e), j]      (= d<G, C> / d v_e)
+ * for every entry the plan holds, indexed like dVals above (hostA's CSR order); entries the plan does not hold (other shards) are
+ * left untouched.  This one definition covers transposed, mapped and shard plans: for the plan of A it is the gradient of C = A(v) B
+ * with respect to v (and the score kernel of graph attention, <G[row], B[col]>); for the plan of A^T, G is n x k and B is m x k.
+ * G has C's shape and row stride (ldc), B has B's (ldb).  Operands that are not 16-byte aligned, or k % 4 != 0, run a generic
+ * kernel: correct, slower.  k <= 1024 (wider: FLEX_ERR_UNSUPPORTED).  Asynchronous on `stream`, no allocation, no host
+ * synchronisation; deterministic (bit-identical run to run: fixed reduction order, no atomics).  Reads no value of the plan, so it
+ * needs no ordering against flex_plan_set_values.
+ * Accuracy, against D64 = the float64 dot of the fp32 inputs, T = sum_j |G B| and u = 2^-24: where D64 is finite the result is finite
+ * and within gamma(k) T + k 2^-149 of it (gamma(n) = n u / (1 - n u)); where D64 is not finite the result is NaN / +inf / -inf exactly
+ * as D64, while no fp32 partial sum overflows (T over the finite terms < 2^120).  Columns past k (padding lanes, the ld - k tail of
+ * a strided row) contribute nothing: they are never read, so no 0 x inf can turn an inf into NaN. */
+int flex_sddmm(const flex_plan *plan, const float *dG, const float *dB, float *dOut, flex_stream_t stream);
 
 /* ≙ alpha_freeMatGPU (mat.cuh:184-193). */
 int flex_plan_destroy(flex_plan *plan);
