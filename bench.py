@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- SpMM GFLOPS (2*nnz*k/t) of the MI355X-native engine, one process per GPU.
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload amazon] [--k 128] [--dump-outputs DIR]
+    python bench.py [--gpus N --steps K --warmup W] [--workload amazon] [--k 128] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one flex_spmm() over the whole (sharded) matrix with A's plan and B resident
@@ -13,8 +13,10 @@ broadcast once"): every rank derives the same community re-ordering, rows are sh
 broadcast once over RCCL (torch.distributed "nccl") before the timed region; no collective on the data path.
 `--workload flickr|reddit|yelp|ppi|pubmed`, `--scaling weak` and `--graph file` remain as options.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and
-`cpu_baseline` objects.  The oracle is used here only for the reported CPU baseline.
+Prints ONE JSON line on rank 0 (contract in the task statement) with `config` and `roofline` objects.  A plain run does only
+what that line's headline needs: set up, warm up, time the steps, dump C if asked, print.  `--full` (N=1) adds, after the timed
+steps, what takes runs of its own: the in-run memory counters, the plan statistics, the per-CU imbalance launch, the HBM probe,
+hipSPARSE side by side and the `cpu_baseline` object.  The oracle is used here only for --check and the CPU baseline.
 """
 import argparse
 import json
@@ -57,12 +59,16 @@ def parse():
     ap.add_argument("--autotune", action="store_true", help="FLEX_PLAN_AUTOTUNE: measure the column-tile width instead of trusting the degree rule (N=1)")
     ap.add_argument("--bcast", default="broadcast", choices=["broadcast", "scatter_allgather"],
                     help="how B reaches the other ranks (untimed, reported as b_bcast_ms)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-copy-probe", action="store_true", help="skip the streaming read / copy probe that measures achievable HBM GB/s")
-    ap.add_argument("--no-vendor", action="store_true", help="skip the hipSPARSE side-by-side (N=1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="N=1: after the timed steps also measure what the headline does not need: the card's memory counters, the plan "
+                         "statistics (graphs up to 50 M nonzeros), the per-CU imbalance launch, the HBM probe, hipSPARSE and the CPU baseline; "
+                         "the --no-* options below leave single ones out.  Without it none of them runs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-copy-probe", action="store_true", help="with --full: skip the streaming read / copy probe that measures achievable HBM GB/s")
+    ap.add_argument("--no-vendor", action="store_true", help="with --full: skip the hipSPARSE side-by-side (N=1 only)")
     ap.add_argument("--no-live-counters", action="store_true",
-                    help="do not read the card's memory counters inside the run (N=1 reads them by default, after the timed region: "
-                         "flex_amd/counters.py); roofline.traffic then falls back to the committed rocprofv3 figure")
+                    help="with --full: do not read the card's memory counters inside the run (--full reads them by default, after the timed "
+                         "region: flex_amd/counters.py); roofline.traffic then falls back to the committed rocprofv3 figure")
     ap.add_argument("--check", action="store_true", help="verify rank 0's shard against the oracle (small workloads)")
     ap.add_argument("--shrink", type=int, default=1, help="rehearsals only: the preset with n and nnz divided by this (same generator and code path)")
     ap.add_argument("--host-threads", type=int, default=0, help="worker threads of the planner / orderings / generator in THIS process "
@@ -97,9 +103,9 @@ def _under_a_profiler():
 def main():
     args = parse()
     # In-run memory counters (≙ the NPerf metrics of the reference's run(), flex.cu:4583-4656): the profiler has to be asked for
-    # BEFORE the first HIP call of the process.  N=1 only (one process, one card), never under rocprofv3, never in a dry run.
+    # BEFORE the first HIP call of the process.  --full and N=1 only (one process, one card), never under rocprofv3, never in a dry run.
     live = None
-    if args.gpus == 1 and not args.dry_run and not args.no_live_counters and not _under_a_profiler():
+    if args.full and args.gpus == 1 and not args.dry_run and not args.no_live_counters and not _under_a_profiler():
         try:
             from flex_amd import counters as live
             live.init()
@@ -224,7 +230,7 @@ def main():
             ordering_failed(e)
         cache_state = timings.get("perm_cache")
     if world == 1 and not args.dry_run:
-        want_stats = a.nnz <= 50_000_000  # one extra pass over the records: skipped on amazon-size inputs
+        want_stats = args.full and a.nnz <= 50_000_000  # one extra pass over the records: skipped on amazon-size inputs
         flags = (flex_amd.FLEX_PLAN_STATS if want_stats else 0) | (flex_amd.FLEX_PLAN_AUTOTUNE if args.autotune else 0)
         if args.order == "rcm":
             # configs[2]: the RCM-reordered LOADER is the input (the reference's flow: permuted CSR + vo_mp, B and C stay in the
@@ -300,8 +306,8 @@ def main():
     ev1.record()
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
-    # what the last timed step computed, taken now: the counter passes launch the plan again and the hipSPARSE side-by-side
-    # below writes its own result into the same C
+    # what the last timed step computed, taken now: with --full the counter passes launch the plan again and the hipSPARSE
+    # side-by-side below writes its own result into the same C
     dumped = dump_outputs(args.dump_outputs, C) if args.dump_outputs else None
     if world > 1:
         dist.barrier()
@@ -502,14 +508,14 @@ def main():
             except Exception as e:  # noqa: BLE001
                 return {"error": f"{name}: {type(e).__name__}: {e}"}
 
-        if world == 1:
+        if world == 1 and args.full:
             # ≙ the reference's per-SM "Imb" column (flex.cu:5087-5126): one stamped launch AFTER the timed region
             im = side("imbalance", lambda: plan.measure_imbalance(bp, cp, stream))
             out["config"]["plan"]["imbalance"] = im if "error" in im else {
                 "cu_busy_imb_pct": round(im["cu_busy_imb_pct"], 2), "cu_end_spread_pct": round(im["cu_end_spread_pct"], 2),
                 "xcd_busy_imb_pct": round(im["xcd_busy_imb_pct"], 2), "xcd_end_spread_pct": round(im["xcd_end_spread_pct"], 2),
                 "cus_seen": im["cus_seen"], "waves": im["waves"], "wave_us_mean": round(im["wave_us_mean"], 2), "wave_us_max": round(im["wave_us_max"], 2)}
-        if world == 1 and not args.no_copy_probe:
+        if world == 1 and args.full and not args.no_copy_probe:
             # achievable HBM bandwidth on this box, measured by the library's own streaming kernels
             pr = side("hbm_probe", lambda: flex_amd.hbm_probe(local_rank, mib=2048, reps=10))
             if "error" in pr:
@@ -521,9 +527,9 @@ def main():
             out["check"] = ok
         if dumped is not None:
             out["outputs"] = dumped
-        if world == 1 and not args.no_vendor:
+        if world == 1 and args.full and not args.no_vendor:
             out["hipsparse"] = side("hipsparse", lambda: vendor_baseline(a, k, B, C))
-        if world == 1 and not args.no_cpu_baseline:  # a reported baseline, timed at N=1 only
+        if world == 1 and args.full and not args.no_cpu_baseline:  # a reported baseline, timed at N=1 only
             out["cpu_baseline"] = side("cpu_baseline", lambda: cpu_baseline(a, k, B))
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -388,13 +388,13 @@ def test_split_row_reduction_is_stable_under_repetition(knobs, split_rows):
 
 
 def test_bench_json_contract():
-    """bench.py prints exactly one JSON line with the contract's keys, a roofline object and a CPU baseline."""
+    """bench.py --full prints exactly one JSON line with the contract's keys, a roofline object and a CPU baseline."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "3", "--workload", "pubmed",
-                          "--k", "32", "--check"], capture_output=True, text=True, timeout=600, cwd=root)
+                          "--k", "32", "--check", "--full"], capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stdout + out.stderr
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -413,17 +413,43 @@ def test_bench_json_contract():
     r = j["roofline"]
     assert r["traffic_source"].startswith("in-run") and r["traffic"] == r["traffic_read_bytes"] + r["traffic_write_bytes"] > 0, r
     assert 0 < r["l2_hit_rate"] <= 1 and r["l1_l2_bytes_measured"] > 0 and 0.8 < r["u_l1_measured"] < 2 and r["waves_per_launch"] > 0, r
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "3", "--workload", "flickr", "--no-cpu-baseline",
-                          "--no-vendor", "--no-copy-probe"], capture_output=True, text=True, timeout=600, cwd=root)
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "3", "--workload", "flickr", "--full",
+                          "--no-cpu-baseline", "--no-vendor", "--no-copy-probe"], capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stdout + out.stderr
     r = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])["roofline"]
     # a graph that leaves the L2s: traffic above the algorithmic bytes, u at the L2 level defined and above the L1-level one
     assert r["traffic"] > r["algorithmic_bytes_per_launch"] and r["u_l2_measured"] > r["u_l1_measured"] > 0.8, r
-    off = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "5", "--warmup", "1", "--workload", "pubmed", "--k", "32", "--no-cpu-baseline",
-                          "--no-vendor", "--no-copy-probe", "--no-live-counters"], capture_output=True, text=True, timeout=600, cwd=root)
+    off = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "5", "--warmup", "1", "--workload", "pubmed", "--k", "32", "--full",
+                          "--no-cpu-baseline", "--no-vendor", "--no-copy-probe", "--no-live-counters"], capture_output=True, text=True, timeout=600, cwd=root)
     assert off.returncode == 0, off.stdout + off.stderr
     r = json.loads([ln for ln in off.stdout.splitlines() if ln.startswith("{")][0])["roofline"]
     assert "u_l1_measured" not in r and (r["traffic_source"] is None or r["traffic_source"].startswith("profiles/")), r
+
+
+def test_bench_plain_run_is_lean(tmp_path):
+    """bench.py without --full: the same contract line and --dump-outputs, and nothing measured beside the headline -- no counter
+    passes, plan statistics, imbalance launch, HBM probe, hipSPARSE or CPU baseline."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "5", "--warmup", "1", "--workload", "pubmed", "--k", "32",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=root)
+    assert out.returncode == 0, out.stdout + out.stderr
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    assert j["metric"] == "SpMM GFLOPS (2*nnz*k/t)" and j["unit"] == "GFLOPS" and j["higher_is_better"] is True and j["dtype"] == "f32"
+    assert j["n_gpus"] == 1 and j["steps"] == 5 and j["warmup"] == 1 and j["ms_per_step"] > 0
+    assert abs(j["value"] - 2 * j["config"]["nnz"] * j["config"]["k"] / (j["ms_per_step"] * 1e-3) / 1e9) < 0.01 * j["value"]
+    assert not {"cpu_baseline", "hipsparse", "check"} & set(j), sorted(j)
+    assert "imbalance" not in j["config"]["plan"] and "b_reuse_wave" not in j["config"]["plan"], j["config"]["plan"]
+    r = j["roofline"]
+    assert set(r) >= {"bound", "achieved", "peak", "unit", "frac", "traffic"}
+    assert not {"u_l1_measured", "l2_hit_rate", "hbm_read_GBps_measured", "hbm_probe_error", "private_l2_model_bytes"} & set(r), sorted(r)
+    assert j["outputs"]["dir"] == str(tmp_path) and j["outputs"]["rows"] == "all"
+    C = np.load(tmp_path / "C.npy")
+    assert C.dtype == np.float32 and list(C.shape) == j["outputs"]["C"] == [j["config"]["n"], 32] and np.isfinite(C).all()
 
 
 @pytest.mark.parametrize("dense_block", [False, True])
