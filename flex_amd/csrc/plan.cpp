@@ -17,6 +17,7 @@
 #include <chrono>
 #include <cstddef>
 #include <cstdlib>
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -52,36 +53,6 @@ bool plan_timing_enabled() {
     return on;
 }
 
-void free_plan_device(flex_plan *p) {
-    (void)hipFree(p->d_rec);
-    (void)hipFree(p->d_t_beg);
-    (void)hipFree(p->d_t_dst);
-    (void)hipFree(p->d_t_aux);
-    (void)hipFree(p->d_chunk);
-    (void)hipFree(p->d_bd_rows);
-    (void)hipFree(p->d_chunk_bd);
-    (void)hipFree(p->d_partial);
-    (void)hipFree(p->d_split);
-    (void)hipFree(p->d_split_cnt);
-    (void)hipFree(p->d_tile_a);
-    (void)hipFree(p->d_tile_boff);
-    (void)hipFree(p->d_tile_mask);
-    (void)hipFree(p->d_rt_ptr);
-    (void)hipFree(p->d_rt_rows);
-    (void)hipFree(p->d_bk_hdr);
-    (void)hipFree(p->d_bk_wstart);
-    (void)hipFree(p->d_bk_cnt);
-    (void)hipFree(p->d_bk_hcol);
-    (void)hipFree(p->d_bk_brow);
-    (void)hipFree(p->d_bk_link);
-    (void)hipFree(p->d_bk_rec);
-    (void)hipFree(p->d_src);
-    (void)hipFree(p->d_vrec);
-    (void)hipFree(p->d_seg);
-    (void)hipFree(p->d_sd_item);
-    (void)hipFree(p->d_sd_grp);
-}
-
 }  // namespace flex
 
 using namespace flex;
@@ -95,82 +66,62 @@ namespace {
 // each candidate is timed on zero-filled operands of the real size (what a gather costs depends on its address,
 // not on the value), and the fastest plan is kept.  Costs up to three extra plans and 2 * 4*(n*ldb + m*ldc) bytes for
 // the duration of the call.
-int autotune(flex_plan **pp, const flex_csr *A, int32_t r0, int32_t r1, const int32_t *col_map, const int32_t *dst_map,
+int autotune(std::unique_ptr<flex_plan> &best, const flex_csr *A, int32_t r0, int32_t r1, const int32_t *col_map, const int32_t *dst_map,
              unsigned flags, const flex_plan_tuning &tuning, std::vector<uint32_t> &sched_cache, const uint32_t *entry_of) {
-    flex_plan *best = *pp;
     if (best->m == 0 || best->k % 4 != 0 || best->ldb % 4 != 0 || best->ldc % 4 != 0) return FLEX_OK;
     int g_max = 8;
     while (4 * g_max < best->k && g_max < 32) g_max <<= 1;
-    float *dB = nullptr, *dC = nullptr;
-    const size_t b_bytes = static_cast<size_t>(best->n) * best->ldb * sizeof(float);
-    const size_t c_bytes = static_cast<size_t>(best->c_rows) * best->ldc * sizeof(float);
+    DeviceArray<float> dB, dC;
+    if (dB.allocate(std::max<size_t>(static_cast<size_t>(best->n) * best->ldb, 4)) != hipSuccess ||
+        dC.allocate(std::max<size_t>(static_cast<size_t>(best->c_rows) * best->ldc, 4)) != hipSuccess) {
+        (void)hipGetLastError();
+        return FLEX_OK;  // no room to measure: keep the rule's choice
+    }
     hipEvent_t e0 = nullptr, e1 = nullptr;
     int rc = FLEX_OK;
     auto time_plan = [&](flex_plan *q, double *us) {
-        for (int i = 0; i < 2 && !rc; ++i) rc = flex_spmm(q, dB, dC, nullptr);
+        for (int i = 0; i < 2 && !rc; ++i) rc = flex_spmm(q, dB.get(), dC.get(), nullptr);
         if (!rc && hipEventRecord(e0, nullptr) != hipSuccess) rc = FLEX_ERR_HIP;
-        for (int i = 0; i < 5 && !rc; ++i) rc = flex_spmm(q, dB, dC, nullptr);
+        for (int i = 0; i < 5 && !rc; ++i) rc = flex_spmm(q, dB.get(), dC.get(), nullptr);
         float ms = 0.f;
         if (!rc && (hipEventRecord(e1, nullptr) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
                     hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
             rc = FLEX_ERR_HIP;
         *us = ms * 1e3 / 5;
     };
-    if (hipMalloc(reinterpret_cast<void **>(&dB), std::max<size_t>(b_bytes, 16)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&dC), std::max<size_t>(c_bytes, 16)) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFree(dB);
-        (void)hipFree(dC);
-        return FLEX_OK;  // no room to measure: keep the rule's choice
-    }
-    if (hipMemset(dB, 0, std::max<size_t>(b_bytes, 16)) != hipSuccess || hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)
+    if (hipMemset(dB.get(), 0, dB.size() * sizeof(float)) != hipSuccess || hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)
         rc = FLEX_ERR_HIP;
     double best_us = 0.0;
-    if (!rc) time_plan(best, &best_us);
-    for (int g : {best->lanes_per_nz / 2, best->lanes_per_nz * 2}) {
-        if (rc || g < 8 || g > g_max || g == (*pp)->lanes_per_nz) continue;
-        flex_plan *q = new (std::nothrow) flex_plan();
-        if (!q) break;
+    if (!rc) time_plan(best.get(), &best_us);
+    // a candidate: a blank plan of best's shape, built with `t` at width force_G, kept if it is strictly faster.  toggles_bundles: it
+    // is compared only if it has best's width and the other bundle setting (else there is nothing to compare, e.g. no row short enough)
+    auto consider = [&](const flex_plan_tuning &t, int force_G, bool toggles_bundles) {
+        std::unique_ptr<flex_plan> q(new (std::nothrow) flex_plan());
+        if (!q) return;
         q->m = best->m; q->n = best->n; q->k = best->k; q->device = best->device;
         q->ldb = best->ldb; q->ldc = best->ldc; q->nnz = best->nnz;
+        if (build_plan(q.get(), A, r0, r1, col_map, dst_map, flags, t, &sched_cache, force_G, entry_of) != FLEX_OK || hipDeviceSynchronize() != hipSuccess)
+            return;
+        if (toggles_bundles && (q->lanes_per_nz != best->lanes_per_nz || (q->n_bundles != 0) == (best->n_bundles != 0))) return;
         double us = 0.0;
-        int rq = build_plan(q, A, r0, r1, col_map, dst_map, flags, tuning, &sched_cache, g, entry_of);
-        if (rq == FLEX_OK && hipDeviceSynchronize() != hipSuccess) rq = FLEX_ERR_HIP;
-        if (rq == FLEX_OK) time_plan(q, &us);
-        if (rq == FLEX_OK && !rc && us < best_us) {
+        time_plan(q.get(), &us);
+        if (!rc && us < best_us) {
             std::swap(best, q);
             best_us = us;
         }
-        free_plan_device(q);
-        delete q;
-    }
+    };
+    const int g0 = best->lanes_per_nz;
+    for (int g : {g0 / 2, g0 * 2})
+        if (!rc && g >= 8 && g <= g_max) consider(tuning, g, false);
     // Row bundles the same way: their rule is one threshold (a chunk per wave slot of the card) between two measured regimes, so on
     // the tiles that have them the other setting is planned and timed too, at the width that won above -- unless the caller chose.
     if (!rc && tuning.bundle == 0 && 64 / best->lanes_per_nz >= static_cast<int>(kBundleMinSlots)) {
         flex_plan_tuning other = tuning;
         other.bundle = best->n_bundles ? 2 : 1;
-        flex_plan *q = new (std::nothrow) flex_plan();
-        if (q) {
-            q->m = best->m; q->n = best->n; q->k = best->k; q->device = best->device;
-            q->ldb = best->ldb; q->ldc = best->ldc; q->nnz = best->nnz;
-            double us = 0.0;
-            int rq = build_plan(q, A, r0, r1, col_map, dst_map, flags, other, &sched_cache, best->lanes_per_nz, entry_of);
-            if (rq == FLEX_OK && hipDeviceSynchronize() != hipSuccess) rq = FLEX_ERR_HIP;
-            if (rq == FLEX_OK && q->lanes_per_nz == best->lanes_per_nz && (q->n_bundles != 0) != (best->n_bundles != 0)) time_plan(q, &us);
-            else rq = FLEX_ERR_UNSUPPORTED;  // nothing to compare (e.g. no row short enough to bundle)
-            if (rq == FLEX_OK && !rc && us < best_us) {
-                std::swap(best, q);
-                best_us = us;
-            }
-            free_plan_device(q);
-            delete q;
-        }
+        consider(other, best->lanes_per_nz, true);
     }
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    (void)hipFree(dB);
-    (void)hipFree(dC);
-    *pp = best;
     return rc;
 }
 
@@ -296,10 +247,9 @@ static int create_common(flex_plan **out, const flex_csr *hostA, bool all_rows, 
         for (int64_t r = row_begin; r < row_end; ++r)
             if (dst_map[r] < 0 || dst_map[r] >= hostA->m) return FLEX_ERR_INVALID;
     const auto t0 = std::chrono::steady_clock::now();
-    int prev = -1;
-    FLEX_HIP_TRY(hipGetDevice(&prev));
-    FLEX_HIP_TRY(hipSetDevice(device));
-    flex_plan *p = new (std::nothrow) flex_plan();
+    const DeviceScope on(device);  // before the plans: they are freed while their device is current
+    FLEX_HIP_TRY(on.error());
+    std::unique_ptr<flex_plan> p(new (std::nothrow) flex_plan());
     if (!p) return FLEX_ERR_NOMEM;
     p->m = static_cast<int32_t>(row_end - row_begin);
     p->n = hostA->n;
@@ -312,9 +262,9 @@ static int create_common(flex_plan **out, const flex_csr *hostA, bool all_rows, 
     const bool tune = (flags & FLEX_PLAN_AUTOTUNE) != 0;
     const uint32_t *entry_of = transposed && mut && hostA->nnz > 0 ? at.entry.data() : nullptr;
     try {
-        rc = build_plan(p, hostA, static_cast<int32_t>(row_begin), static_cast<int32_t>(row_end), col_map, dst_map, flags, tuning,
+        rc = build_plan(p.get(), hostA, static_cast<int32_t>(row_begin), static_cast<int32_t>(row_end), col_map, dst_map, flags, tuning,
                         tune ? &sched_cache : nullptr, 0, entry_of);
-        if (rc == FLEX_OK && tune) rc = autotune(&p, hostA, static_cast<int32_t>(row_begin), static_cast<int32_t>(row_end), col_map, dst_map, flags, tuning, sched_cache, entry_of);
+        if (rc == FLEX_OK && tune) rc = autotune(p, hostA, static_cast<int32_t>(row_begin), static_cast<int32_t>(row_end), col_map, dst_map, flags, tuning, sched_cache, entry_of);
         if (rc == FLEX_OK && mut) {
             p->src_nnz = callerA->nnz;
             p->ent_fp = held_entries_fp(callerA, transposed, row_begin, row_end, col_map);
@@ -325,14 +275,9 @@ static int create_common(flex_plan **out, const flex_csr *hostA, bool all_rows, 
         rc = FLEX_ERR_INVALID;
     }
     if (rc == FLEX_OK && hipDeviceSynchronize() != hipSuccess) rc = FLEX_ERR_HIP;
-    (void)hipSetDevice(prev);
-    if (rc) {
-        free_plan_device(p);
-        delete p;
-        return rc;
-    }
+    if (rc) return rc;
     p->plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    *out = p;
+    *out = p.release();
     return FLEX_OK;
 }
 
@@ -378,9 +323,8 @@ int flex_spmm(flex_plan *p, const float *dB, float *dC, flex_stream_t stream) {
     if (!p) return FLEX_ERR_INVALID;
     if (p->m == 0) return FLEX_OK;
     if (!dC || (!dB && p->nnz > 0)) return FLEX_ERR_INVALID;
-    int cur = -1;
-    FLEX_HIP_TRY(hipGetDevice(&cur));
-    if (cur != p->device) FLEX_HIP_TRY(hipSetDevice(p->device));
+    const DeviceScope on(p->device);
+    FLEX_HIP_TRY(on.error());
     const bool vec4 = operands_vec4(p, dB, dC);
     const bool fused = vec4 && p->fused_fixup;  // the generic kernel always leaves the sum to spmm_fixup_kernel
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -399,14 +343,11 @@ int flex_spmm(flex_plan *p, const float *dB, float *dC, flex_stream_t stream) {
     }
     if (guard && p->launched && s != p->last_stream) {
         const hipError_t q = hipStreamQuery(p->last_stream);
-        if (q == hipErrorNotReady) {
-            if (cur != p->device) (void)hipSetDevice(cur);
-            return FLEX_ERR_INVALID;
-        }
+        if (q == hipErrorNotReady) return FLEX_ERR_INVALID;
         if (q != hipSuccess) (void)hipGetLastError();  // e.g. the old stream has been destroyed: nothing of ours can be pending on it
     }
     rc = launch_spmm(plan_view(p, fused, p->trace), p->lanes_per_nz, p->off32, vec4, dB, dC, s, p->unroll);
-    if (rc == FLEX_OK && !fused) rc = launch_fixup(p->d_partial, p->d_split, p->n_split, p->k, p->ldc, dC, s);
+    if (rc == FLEX_OK && !fused) rc = launch_fixup(p->d_partial.get(), p->d_split.get(), p->n_split, p->k, p->ldc, dC, s);
     // the dense tiles' share, added to the rows the kernels above have written
     if (rc == FLEX_OK && p->n_tiles) rc = launch_tiles(tile_view(p), p->off32, dB, dC, p->k, p->ldb, p->ldc, s);
     // the hot blocks' share (the nonzeros with reuse on chip: B rows staged in LDS), added to the rows the flat kernel has written
@@ -415,17 +356,12 @@ int flex_spmm(flex_plan *p, const float *dB, float *dC, flex_stream_t stream) {
         p->last_stream = s;
         p->launched = true;
     }
-    if (cur != p->device) (void)hipSetDevice(cur);
     return rc;
 }
 
 int flex_plan_destroy(flex_plan *p) {
     if (!p) return FLEX_OK;
-    int cur = -1;
-    (void)hipGetDevice(&cur);
-    (void)hipSetDevice(p->device);
-    free_plan_device(p);
-    if (cur >= 0) (void)hipSetDevice(cur);
+    const DeviceScope on(p->device);
     delete p;
     return FLEX_OK;
 }
@@ -449,7 +385,7 @@ int flex_plan_get_info(const flex_plan *p, flex_plan_info *o) {
     o->two_d = p->two_d ? 1 : 0;
     o->n_tiles = p->n_tiles;
     o->tile_nnz = p->tile_nnz;
-    o->n_records = static_cast<int64_t>(p->n_records);
+    o->n_records = static_cast<int64_t>(p->d_rec.size());
     o->panel_rows = p->two_d ? static_cast<int32_t>(p->panel_rows) : 0;
     o->n_blocks = p->bk_blocks;
     o->block_rows = p->bk_rows;
@@ -457,7 +393,7 @@ int flex_plan_get_info(const flex_plan *p, flex_plan_info *o) {
     o->block_hot_nnz = p->bk_hot_nnz;
     o->block_hot_cols = p->bk_hot_cols;
     o->block_panels = p->bk_panels;
-    o->block_records = p->bk_records;
+    o->block_records = static_cast<int64_t>(p->d_bk_rec.size());
     o->n_bundles = p->n_bundles;
     o->bundle_rows = p->bundle_rows;
     return FLEX_OK;
@@ -483,14 +419,12 @@ int flex_plan_get_stats(const flex_plan *p, flex_plan_stats *o) {
 
 int flex_plan_kernel_info(const flex_plan *p, flex_kernel_info *o) {
     if (!p || !o) return FLEX_ERR_INVALID;
-    int cur = -1;
-    FLEX_HIP_TRY(hipGetDevice(&cur));
-    if (cur != p->device) FLEX_HIP_TRY(hipSetDevice(p->device));
+    const DeviceScope on(p->device);
+    FLEX_HIP_TRY(on.error());
     hipFuncAttributes a{};
     int waves = 0;
     const bool vec4 = p->k % 4 == 0 && p->ldb % 4 == 0 && p->ldc % 4 == 0;
     const int rc = kernel_attributes(p->lanes_per_nz, p->off32, vec4, &a, &waves);
-    if (cur != p->device) (void)hipSetDevice(cur);
     if (rc) return rc;
     *o = flex_kernel_info{a.numRegs, 0, static_cast<int32_t>(a.sharedSizeBytes), static_cast<int32_t>(a.localSizeBytes), 64 * kWavesPerBlock, waves};
     return FLEX_OK;

@@ -15,6 +15,70 @@
 
 #include "internal.h"
 
+namespace flex {
+
+// One array of a plan's device image (or a scratch buffer): owns its allocation and frees it when it goes.  size() is the length
+// of the host vector it was uploaded from; the allocation holds at least one element, so an array that was uploaded is never null,
+// and one that was not is empty with a null pointer.
+template <class T>
+class DeviceArray {
+  public:
+    DeviceArray() = default;
+    DeviceArray(DeviceArray &&o) noexcept : ptr_(std::exchange(o.ptr_, nullptr)), n_(std::exchange(o.n_, 0)) {}
+    DeviceArray &operator=(DeviceArray o) noexcept {
+        std::swap(ptr_, o.ptr_);
+        std::swap(n_, o.n_);
+        return *this;
+    }
+    ~DeviceArray() { if (ptr_) (void)hipFree(ptr_); }
+    T *get() const { return ptr_; }
+    size_t size() const { return n_; }
+    // max(1, n) elements, not initialised (what was held before is freed)
+    hipError_t allocate(size_t n) {
+        *this = DeviceArray();
+        const hipError_t e = hipMalloc(reinterpret_cast<void **>(&ptr_), std::max<size_t>(n, 1) * sizeof(T));
+        if (e != hipSuccess) ptr_ = nullptr;
+        else n_ = n;
+        return e;
+    }
+    // a copy of h; the bytes allocated are added to *device_bytes
+    template <class A>
+    int upload(const std::vector<T, A> &h, int64_t *device_bytes) {
+        FLEX_HIP_TRY(allocate(h.size()));
+        if (!h.empty()) FLEX_HIP_TRY(hipMemcpy(ptr_, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+        *device_bytes += static_cast<int64_t>(std::max<size_t>(h.size(), 1) * sizeof(T));
+        return FLEX_OK;
+    }
+
+  private:
+    T *ptr_ = nullptr;
+    size_t n_ = 0;
+};
+
+// `dev` is the current device for the length of a scope: one hipGetDevice, a hipSetDevice only when the device differs, and the
+// caller's device set back on exit only then.  error(): the get or set failed (the scope then changed nothing).
+class DeviceScope {
+  public:
+    explicit DeviceScope(int dev) {
+        err_ = hipGetDevice(&prev_);
+        if (err_ == hipSuccess && prev_ != dev) {
+            err_ = hipSetDevice(dev);
+            switched_ = err_ == hipSuccess;
+        }
+    }
+    ~DeviceScope() { if (switched_) (void)hipSetDevice(prev_); }
+    DeviceScope(const DeviceScope &) = delete;
+    DeviceScope &operator=(const DeviceScope &) = delete;
+    hipError_t error() const { return err_; }
+
+  private:
+    int prev_ = -1;
+    bool switched_ = false;
+    hipError_t err_ = hipSuccess;
+};
+
+}  // namespace flex
+
 struct flex_plan {
     int32_t m = 0, n = 0, k = 0, device = 0;
     int32_t ldb = 0, ldc = 0;  // row strides of B and C in floats (== k unless flex_plan_create_ld)
@@ -28,22 +92,23 @@ struct flex_plan {
     int unroll = 0;
     uint64_t *trace = nullptr;
     unsigned order = 0;
-    uint2 *d_rec = nullptr;
-    uint32_t *d_t_beg = nullptr, *d_t_dst = nullptr;
-    uint2 *d_t_aux = nullptr;
-    uint4 *d_chunk = nullptr;
-    uint32_t *d_bd_rows = nullptr;  // row bundles (internal.h, PlanView): nullptr when the plan has none
-    uint2 *d_chunk_bd = nullptr;
-    uint32_t n_bundles = 0, n_bd_rows = 0;  // bundles; entries of d_bd_rows (S per bundle)
+    // the device image (internal.h, PlanView): records (nnz + padding), tasks, the chunk table
+    flex::DeviceArray<uint2> d_rec;
+    flex::DeviceArray<uint32_t> d_t_beg, d_t_dst;
+    flex::DeviceArray<uint2> d_t_aux;
+    flex::DeviceArray<uint4> d_chunk;
+    flex::DeviceArray<uint32_t> d_bd_rows;  // row bundles (internal.h, PlanView): S entries per bundle; empty when the plan has none
+    flex::DeviceArray<uint2> d_chunk_bd;
+    uint32_t n_bundles = 0;
     int64_t bundle_rows = 0;                // rows that sit in bundles
-    float *d_partial = nullptr;
-    flex::SplitRow *d_split = nullptr;
-    uint32_t *d_split_cnt = nullptr;
+    flex::DeviceArray<float> d_partial;
+    flex::DeviceArray<flex::SplitRow> d_split;
+    flex::DeviceArray<uint32_t> d_split_cnt;
     bool fused_fixup = false;
     bool two_d = false;  // rows cut by column panel (phases), not only by length
     // dense 32x32 tiles routed to the MFMA kernel (tile_kernels.hip)
-    float *d_tile_a = nullptr;
-    uint32_t *d_tile_boff = nullptr, *d_tile_mask = nullptr, *d_rt_ptr = nullptr, *d_rt_rows = nullptr;
+    flex::DeviceArray<float> d_tile_a;
+    flex::DeviceArray<uint32_t> d_tile_boff, d_tile_mask, d_rt_ptr, d_rt_rows;
     uint32_t n_tiles = 0, n_row_tiles = 0;
     int64_t tile_nnz = 0;
     int64_t tile_hist[3] = {0, 0, 0}, tile_cells = 0;  // detector report
@@ -51,13 +116,12 @@ struct flex_plan {
     uint32_t panel_rows = 0;
     // hot blocks (block_kernels.hip): the nonzeros they hold are not in the record stream above; their rows are (the flat kernel
     // writes every row, the hot kernel adds to the rows of its blocks)
-    uint4 *d_bk_hdr = nullptr;
-    uint2 *d_bk_wstart = nullptr, *d_bk_rec = nullptr;
-    uint32_t *d_bk_cnt = nullptr, *d_bk_hcol = nullptr, *d_bk_brow = nullptr, *d_bk_link = nullptr;
+    flex::DeviceArray<uint4> d_bk_hdr;
+    flex::DeviceArray<uint2> d_bk_wstart, d_bk_rec;
+    flex::DeviceArray<uint32_t> d_bk_cnt, d_bk_hcol, d_bk_brow, d_bk_link;
     uint32_t bk_blocks = 0, bk_rounds = 0, bk_panel_rows = 0, bk_ablate = 0;
-    int64_t bk_rows = 0, bk_nnz = 0, bk_hot_nnz = 0, bk_hot_cols = 0, bk_panels = 0, bk_records = 0;
+    int64_t bk_rows = 0, bk_nnz = 0, bk_hot_nnz = 0, bk_hot_cols = 0, bk_panels = 0;
     uint32_t n_tasks = 0, n_chunks = 0, n_slots = 0, n_split = 0, n_partials = 0;  // n_slots: chunk table incl. padding
-    uint64_t n_records = 0;   // nnz + padding
     int64_t c_rows = 0;       // rows of C the plan writes into (m, or hostA->m for a mapped plan)
     int64_t device_bytes = 0;
     double plan_ms = 0;
@@ -68,14 +132,14 @@ struct flex_plan {
     // in-flight guard of a plan that owns a split-row workspace (flex_spmm): the stream of its latest launch
     hipStream_t last_stream = nullptr;
     bool launched = false;
-    // FLEX_PLAN_MUTABLE_VALUES (values_kernels.hip: flex_plan_set_values, flex_sddmm); nullptr / 0 on other plans
+    // FLEX_PLAN_MUTABLE_VALUES (values_kernels.hip: flex_plan_set_values, flex_sddmm); empty / 0 on other plans
     bool mutable_vals = false;
-    uint32_t *d_src = nullptr;    // [n_records] entry of hostA (CSR order) each record holds; kNoEntry = padding
-    float *d_vrec = nullptr;      // [n_records] the current value of each real record (the plan's copy; 0 on padding)
-    uint4 *d_seg = nullptr;       // [n_segs] padded runs {first record, real records, padding records, stride}: pad_values redoes them
-    uint4 *d_sd_item = nullptr;   // [n_sd_items] SDDMM work items (internal.h, kSdItemRecords)
-    uint32_t *d_sd_grp = nullptr; // [n_sd_groups + 1] first item of each wave's group
-    uint32_t n_segs = 0, n_sd_items = 0, n_sd_groups = 0;
+    flex::DeviceArray<uint32_t> d_src;     // [records] entry of hostA (CSR order) each record holds; kNoEntry = padding
+    flex::DeviceArray<float> d_vrec;       // [records] the current value of each real record (the plan's copy; 0 on padding)
+    flex::DeviceArray<uint4> d_seg;        // padded runs {first record, real records, padding records, stride}: pad_values redoes them
+    flex::DeviceArray<uint4> d_sd_item;    // SDDMM work items (internal.h, kSdItemRecords)
+    flex::DeviceArray<uint32_t> d_sd_grp;  // [n_sd_groups + 1] first item of each wave's group
+    uint32_t n_sd_groups = 0;
     int64_t src_nnz = 0;          // nnz of hostA: entry ids are below it
     uint64_t ent_fp = 0;          // order-free fingerprint of the (entry, B row) pairs the plan holds, taken from hostA (self-check)
 };
@@ -103,29 +167,20 @@ struct default_init_allocator : std::allocator<T> {
 };
 using RecordVec = std::vector<uint2, default_init_allocator<uint2>>;
 
-template <typename T, typename A>
-int upload(T **dptr, const std::vector<T, A> &h, int64_t *bytes) {
-    *dptr = nullptr;
-    const size_t nb = (h.empty() ? 1 : h.size()) * sizeof(T);
-    FLEX_HIP_TRY(hipMalloc(reinterpret_cast<void **>(dptr), nb));
-    if (!h.empty()) FLEX_HIP_TRY(hipMemcpy(*dptr, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    *bytes += static_cast<int64_t>(nb);
-    return FLEX_OK;
-}
-
-void free_plan_device(flex_plan *p);
-
 // The kernels' view of a finished plan.  `fused`: split rows are summed inside the launch.
 inline PlanView plan_view(const flex_plan *p, bool fused, uint64_t *trace) {
-    return PlanView{p->d_rec, p->d_t_beg, p->d_t_dst, p->d_t_aux, p->d_chunk, p->d_partial, p->d_split, p->d_split_cnt,
-                    fused ? 1u : 0u, p->n_slots, p->k, p->ldb, p->ldc,
-                    p->xcd_remap ? 1u : 0u, p->lds_extra, p->rec_nt ? 1u : 0u, p->tile_group, trace, p->d_bd_rows, p->d_chunk_bd};
+    return PlanView{p->d_rec.get(), p->d_t_beg.get(), p->d_t_dst.get(), p->d_t_aux.get(), p->d_chunk.get(), p->d_partial.get(), p->d_split.get(),
+                    p->d_split_cnt.get(), fused ? 1u : 0u, p->n_slots, p->k, p->ldb, p->ldc,
+                    p->xcd_remap ? 1u : 0u, p->lds_extra, p->rec_nt ? 1u : 0u, p->tile_group, trace, p->d_bd_rows.get(), p->d_chunk_bd.get()};
 }
 inline BlockView block_view(const flex_plan *p) {
-    return BlockView{p->d_bk_hdr, p->d_bk_wstart, p->d_bk_cnt, p->d_bk_hcol, p->d_bk_brow, p->d_bk_link, p->d_bk_rec, static_cast<uint64_t>(std::max<int64_t>(p->bk_records, 1)),
+    return BlockView{p->d_bk_hdr.get(), p->d_bk_wstart.get(), p->d_bk_cnt.get(), p->d_bk_hcol.get(), p->d_bk_brow.get(), p->d_bk_link.get(), p->d_bk_rec.get(),
+                     static_cast<uint64_t>(std::max<size_t>(p->d_bk_rec.size(), 1)),
                      p->bk_blocks, p->bk_rounds, p->bk_panel_rows, p->k, p->ldb, p->ldc, 1u, p->bk_ablate, p->trace};
 }
-inline TileView tile_view(const flex_plan *p) { return TileView{p->d_tile_a, p->d_tile_boff, p->d_tile_mask, p->d_rt_ptr, p->d_rt_rows, p->n_row_tiles}; }
+inline TileView tile_view(const flex_plan *p) {
+    return TileView{p->d_tile_a.get(), p->d_tile_boff.get(), p->d_tile_mask.get(), p->d_rt_ptr.get(), p->d_rt_rows.get(), p->n_row_tiles};
+}
 // float4 path: k and both strides multiples of 4, both base addresses 16-byte aligned
 inline bool operands_vec4(const flex_plan *p, const float *dB, const float *dC) {
     return (p->k % 4 == 0) && (p->ldb % 4 == 0) && (p->ldc % 4 == 0) &&

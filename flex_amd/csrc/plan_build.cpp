@@ -367,13 +367,13 @@ class PlanBuilder {
                          static_cast<double>(img.hot_nnz) / std::max<int64_t>(img.hot_cols, 1), static_cast<double>(img.rec.size()) / std::max<int64_t>(img.hot_nnz, 1),
                          static_cast<double>(img.panels) / std::max<uint32_t>(img.n_blocks, 1));
         if (img.hot_nnz == 0) return FLEX_OK;  // nothing has reuse: a flat plan
-        if ((rc = upload(&p->d_bk_hdr, img.hdr, &p->device_bytes))) return rc;
-        if ((rc = upload(&p->d_bk_wstart, img.wstart, &p->device_bytes))) return rc;
-        if ((rc = upload(&p->d_bk_cnt, img.cnt, &p->device_bytes))) return rc;
-        if ((rc = upload(&p->d_bk_hcol, img.hcol, &p->device_bytes))) return rc;
-        if ((rc = upload(&p->d_bk_brow, img.brow, &p->device_bytes))) return rc;
-        if ((rc = upload(&p->d_bk_link, img.link, &p->device_bytes))) return rc;
-        if ((rc = upload(&p->d_bk_rec, img.rec, &p->device_bytes))) return rc;
+        if ((rc = p->d_bk_hdr.upload(img.hdr, &p->device_bytes))) return rc;
+        if ((rc = p->d_bk_wstart.upload(img.wstart, &p->device_bytes))) return rc;
+        if ((rc = p->d_bk_cnt.upload(img.cnt, &p->device_bytes))) return rc;
+        if ((rc = p->d_bk_hcol.upload(img.hcol, &p->device_bytes))) return rc;
+        if ((rc = p->d_bk_brow.upload(img.brow, &p->device_bytes))) return rc;
+        if ((rc = p->d_bk_link.upload(img.link, &p->device_bytes))) return rc;
+        if ((rc = p->d_bk_rec.upload(img.rec, &p->device_bytes))) return rc;
         p->bk_blocks = img.n_blocks;
         p->bk_rounds = img.rounds;
         p->bk_panel_rows = img.panel_rows;
@@ -382,7 +382,6 @@ class PlanBuilder {
         p->bk_hot_nnz = img.hot_nnz;
         p->bk_hot_cols = img.hot_cols;
         p->bk_panels = img.panels;
-        p->bk_records = static_cast<int64_t>(img.rec.size());
         p->bk_ablate = static_cast<uint32_t>(tn.block_ablate);
         img = BlockImage{};
         keep_unmarked(hot_mask);
@@ -896,10 +895,8 @@ class PlanBuilder {
 
     int upload_tasks() {
         p->n_tasks = static_cast<uint32_t>(tasks.size());
-        p->n_records = rec.size();
         p->n_bundles = n_bundles;
         p->bundle_rows = bundle_rows;
-        p->n_bd_rows = static_cast<uint32_t>(bd_rows.size());
         p->c_rows = dst_map ? A->m : m;
         p->n_chunks = static_cast<uint32_t>(w_task.size() - 1);
         p->n_split = static_cast<uint32_t>(split.size());
@@ -907,20 +904,20 @@ class PlanBuilder {
         p->two_d = two_d;
         p->panel_rows = 1u << pshift;
         int rc;
-        if ((rc = upload(&p->d_rec, rec, &p->device_bytes))) return rc;
-        if ((rc = upload(&p->d_t_beg, t_beg, &p->device_bytes))) return rc;
-        if ((rc = upload(&p->d_t_dst, t_dst, &p->device_bytes))) return rc;
-        if ((rc = upload(&p->d_t_aux, t_aux, &p->device_bytes))) return rc;
-        if (n_bundles && (rc = upload(&p->d_bd_rows, bd_rows, &p->device_bytes))) return rc;
+        if ((rc = p->d_rec.upload(rec, &p->device_bytes))) return rc;
+        if ((rc = p->d_t_beg.upload(t_beg, &p->device_bytes))) return rc;
+        if ((rc = p->d_t_dst.upload(t_dst, &p->device_bytes))) return rc;
+        if ((rc = p->d_t_aux.upload(t_aux, &p->device_bytes))) return rc;
+        if (n_bundles && (rc = p->d_bd_rows.upload(bd_rows, &p->device_bytes))) return rc;
         p->n_tiles = static_cast<uint32_t>(tiles.boff.size() / 32);
         p->n_row_tiles = tiles.rt_ptr.empty() ? 0u : static_cast<uint32_t>(tiles.rt_ptr.size() - 1);
         p->tile_nnz = tiles.nnz;
         if (p->n_tiles) {
-            if ((rc = upload(&p->d_tile_a, tiles.a, &p->device_bytes))) return rc;
-            if ((rc = upload(&p->d_tile_boff, tiles.boff, &p->device_bytes))) return rc;
-            if ((rc = upload(&p->d_tile_mask, tiles.mask, &p->device_bytes))) return rc;
-            if ((rc = upload(&p->d_rt_ptr, tiles.rt_ptr, &p->device_bytes))) return rc;
-            if ((rc = upload(&p->d_rt_rows, tiles.rt_rows, &p->device_bytes))) return rc;
+            if ((rc = p->d_tile_a.upload(tiles.a, &p->device_bytes))) return rc;
+            if ((rc = p->d_tile_boff.upload(tiles.boff, &p->device_bytes))) return rc;
+            if ((rc = p->d_tile_mask.upload(tiles.mask, &p->device_bytes))) return rc;
+            if ((rc = p->d_rt_ptr.upload(tiles.rt_ptr, &p->device_bytes))) return rc;
+            if ((rc = p->d_rt_rows.upload(tiles.rt_rows, &p->device_bytes))) return rc;
         }
         return FLEX_OK;
     }
@@ -966,15 +963,13 @@ class PlanBuilder {
         grp.push_back(static_cast<uint32_t>(item.size()));
         p->mutable_vals = true;
         p->tuning.blocks = 2;  // (mfma: the caller's tuning was set to 2 by create_common)
-        p->n_segs = static_cast<uint32_t>(seg.size());
-        p->n_sd_items = static_cast<uint32_t>(item.size());
         p->n_sd_groups = static_cast<uint32_t>(grp.size() - 1);
         int rc;
-        if ((rc = upload(&p->d_src, rsrc, &p->device_bytes))) return rc;
-        if ((rc = upload(&p->d_vrec, rvals, &p->device_bytes))) return rc;
-        if ((rc = upload(&p->d_seg, seg, &p->device_bytes))) return rc;
-        if ((rc = upload(&p->d_sd_item, item, &p->device_bytes))) return rc;
-        if ((rc = upload(&p->d_sd_grp, grp, &p->device_bytes))) return rc;
+        if ((rc = p->d_src.upload(rsrc, &p->device_bytes))) return rc;
+        if ((rc = p->d_vrec.upload(rvals, &p->device_bytes))) return rc;
+        if ((rc = p->d_seg.upload(seg, &p->device_bytes))) return rc;
+        if ((rc = p->d_sd_item.upload(item, &p->device_bytes))) return rc;
+        if ((rc = p->d_sd_grp.upload(grp, &p->device_bytes))) return rc;
         rsrc = std::vector<uint32_t>();
         rvals = std::vector<float>();
         return FLEX_OK;
@@ -1057,15 +1052,15 @@ class PlanBuilder {
         p->n_chunks = n_real;
         p->n_slots = static_cast<uint32_t>(chunk.size());
         int rc;
-        if ((rc = upload(&p->d_chunk, chunk, &p->device_bytes))) return rc;
-        if (n_bundles && (rc = upload(&p->d_chunk_bd, cbd, &p->device_bytes))) return rc;
+        if ((rc = p->d_chunk.upload(chunk, &p->device_bytes))) return rc;
+        if (n_bundles && (rc = p->d_chunk_bd.upload(cbd, &p->device_bytes))) return rc;
         if (flags & FLEX_PLAN_STATS) collect_stats(p, rec, chunk, split_nnz);
         // split-row workspace: the rows, one arrival counter per (row, column tile) -- zero between launches -- and the partial sums
-        if ((rc = upload(&p->d_split, split, &p->device_bytes))) return rc;
+        if ((rc = p->d_split.upload(split, &p->device_bytes))) return rc;
         const size_t ktiles = (static_cast<size_t>(k) + 4 * G - 1) / (4 * G);
         std::vector<uint32_t> zeros(std::max<size_t>(1, split.size() * ktiles), 0u);
-        if ((rc = upload(&p->d_split_cnt, zeros, &p->device_bytes))) return rc;
-        const size_t pbytes = std::max<size_t>(1, static_cast<size_t>(n_partials) * k) * sizeof(float);
+        if ((rc = p->d_split_cnt.upload(zeros, &p->device_bytes))) return rc;
+        const size_t n_pfloats = std::max<size_t>(1, static_cast<size_t>(n_partials) * k);
         // Large launches: split rows are summed by spmm_fixup_kernel after the main launch: stream order is all that needs, and it measured
         // FASTER than the in-launch form on the large shapes (MI355X, profiles/r03_fixup_in_launch_vs_two_launch.txt: reddit k=128
         // 638 vs 642 us, amazon 8.22 vs 8.27 ms; flickr 38.5 vs 36.7 us and reddit k=32 151 vs 150 the other way: one kernel
@@ -1078,8 +1073,8 @@ class PlanBuilder {
         const double madds = static_cast<double>(slice_nnz()) * k;
         p->fused_fixup = tn.split_rows == 1 || (tn.split_rows != 2 && madds <= 4e8);
         p->tuning.split_rows = p->fused_fixup ? 1 : 2;
-        FLEX_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&p->d_partial), pbytes));
-        p->device_bytes += static_cast<int64_t>(pbytes);
+        FLEX_HIP_TRY(p->d_partial.allocate(n_pfloats));
+        p->device_bytes += static_cast<int64_t>(n_pfloats * sizeof(float));
         return FLEX_OK;
     }
 };

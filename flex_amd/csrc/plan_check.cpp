@@ -65,6 +65,13 @@ void collect_stats(flex_plan *p, const RecordVec &rec, const std::vector<uint4> 
     p->has_stats = true;
 }
 
+// The whole of one uploaded array, read back into h.
+template <class T>
+static bool read_back(const DeviceArray<T> &d, std::vector<T> &h) {
+    h.resize(d.size());
+    return h.empty() || hipMemcpy(h.data(), d.get(), h.size() * sizeof(T), hipMemcpyDeviceToHost) == hipSuccess;
+}
+
 }  // namespace flex
 
 extern "C" {
@@ -74,27 +81,24 @@ int flex_plan_measure_imbalance(flex_plan *p, const float *dB, float *dC, flex_s
     *out = flex_imbalance{};
     if (p->m == 0 || p->n_slots == 0) return FLEX_OK;
     if (!operands_vec4(p, dB, dC) || p->bk_blocks) return FLEX_ERR_UNSUPPORTED;  // the stamped twin exists for the vector kernel only (not for row blocks)
-    int cur = -1;
-    FLEX_HIP_TRY(hipGetDevice(&cur));
-    if (cur != p->device) FLEX_HIP_TRY(hipSetDevice(p->device));
+    const DeviceScope on(p->device);
+    FLEX_HIP_TRY(on.error());
     const size_t ktiles = (static_cast<size_t>(p->k) + 4 * p->lanes_per_nz - 1) / (4 * p->lanes_per_nz);
     const size_t words = static_cast<size_t>(p->n_slots) * ktiles * 3;
-    uint64_t *d_log = nullptr;
+    DeviceArray<uint64_t> d_log;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     int rc = FLEX_OK;
     std::vector<uint64_t> log(words);
-    if (hipMalloc(reinterpret_cast<void **>(&d_log), words * 8) != hipSuccess) rc = FLEX_ERR_HIP;
-    if (!rc && hipMemsetAsync(d_log, 0, words * 8, s) != hipSuccess) rc = FLEX_ERR_HIP;
+    if (d_log.allocate(words) != hipSuccess) rc = FLEX_ERR_HIP;
+    if (!rc && hipMemsetAsync(d_log.get(), 0, words * 8, s) != hipSuccess) rc = FLEX_ERR_HIP;
     if (!rc) {
-        rc = launch_spmm_stamped(plan_view(p, p->fused_fixup, d_log), p->lanes_per_nz, p->off32, dB, dC, s);
-        if (rc == FLEX_OK && !p->fused_fixup) rc = launch_fixup(p->d_partial, p->d_split, p->n_split, p->k, p->ldc, dC, s);
+        rc = launch_spmm_stamped(plan_view(p, p->fused_fixup, d_log.get()), p->lanes_per_nz, p->off32, dB, dC, s);
+        if (rc == FLEX_OK && !p->fused_fixup) rc = launch_fixup(p->d_partial.get(), p->d_split.get(), p->n_split, p->k, p->ldc, dC, s);
         if (rc == FLEX_OK && p->n_tiles) {
             rc = launch_tiles(tile_view(p), p->off32, dB, dC, p->k, p->ldb, p->ldc, s);
         }
     }
-    if (!rc && (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(log.data(), d_log, words * 8, hipMemcpyDeviceToHost) != hipSuccess)) rc = FLEX_ERR_HIP;
-    (void)hipFree(d_log);
-    if (cur != p->device) (void)hipSetDevice(cur);
+    if (!rc && (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(log.data(), d_log.get(), words * 8, hipMemcpyDeviceToHost) != hipSuccess)) rc = FLEX_ERR_HIP;
     if (rc) return rc;
     // reduce: CU = (XCC id, SE/SH/CU bits of HW_ID [15:8]); clock = 100 MHz
     struct Acc {
@@ -150,19 +154,15 @@ int flex_plan_measure_imbalance(flex_plan *p, const float *dB, float *dC, flex_s
 // column, after col_map); the padded runs lie inside the stream, real records first and padding after; every record's bits are what
 // pad_values -- the rule the planner and the refresh share -- derives from the plan's kept values, and padding outside every run
 // carries value 0 (the empty slots of a bundle); the SDDMM's items cover every real record exactly once, in groups that tile them.
+// Called by flex_plan_self_check, on the plan's device, once the lengths of these arrays have been checked.
 static int check_value_image(const flex_plan *p, const std::vector<uint2> &rec, uint64_t row_bytes) {
     const size_t nr = rec.size();
-    std::vector<uint32_t> src(nr), grp(static_cast<size_t>(p->n_sd_groups) + 1);
-    std::vector<float> vrec(nr);
-    std::vector<uint4> seg(p->n_segs), item(p->n_sd_items);
-    int cur = -1;
-    FLEX_HIP_TRY(hipGetDevice(&cur));
-    if (cur != p->device) FLEX_HIP_TRY(hipSetDevice(p->device));
-    auto down = [&](void *dst, const void *s, size_t bytes) { return bytes == 0 || hipMemcpy(dst, s, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
-    const bool ok = down(src.data(), p->d_src, nr * 4) && down(vrec.data(), p->d_vrec, nr * 4) && down(seg.data(), p->d_seg, seg.size() * sizeof(uint4)) &&
-                    down(item.data(), p->d_sd_item, item.size() * sizeof(uint4)) && down(grp.data(), p->d_sd_grp, grp.size() * 4);
-    if (cur != p->device) (void)hipSetDevice(cur);
-    if (!ok) return FLEX_ERR_HIP;
+    std::vector<uint32_t> src, grp;
+    std::vector<float> vrec;
+    std::vector<uint4> seg, item;
+    if (!read_back(p->d_src, src) || !read_back(p->d_vrec, vrec) || !read_back(p->d_seg, seg) || !read_back(p->d_sd_item, item) ||
+        !read_back(p->d_sd_grp, grp))
+        return FLEX_ERR_HIP;
     // entries: each once, the pairs' fingerprint
     std::vector<uint8_t> seen(static_cast<size_t>(p->src_nnz), 0);
     int64_t real = 0;
@@ -192,7 +192,7 @@ static int check_value_image(const flex_plan *p, const std::vector<uint2> &rec, 
         if (src[i] == kNoEntry && !in_run[i] && rec[i].y != 0) return FLEX_ERR_FORMAT;
     }
     // the SDDMM's walk
-    if (grp.front() != 0 || grp.back() != p->n_sd_items) return FLEX_ERR_FORMAT;
+    if (grp.front() != 0 || grp.back() != item.size()) return FLEX_ERR_FORMAT;
     for (uint32_t g = 0; g < p->n_sd_groups; ++g)
         if (grp[g] >= grp[g + 1] || grp[g + 1] - grp[g] > kSdGroupItems) return FLEX_ERR_FORMAT;
     std::vector<uint8_t> walked(nr, 0);
@@ -216,26 +216,31 @@ static int check_value_image(const flex_plan *p, const std::vector<uint2> &rec, 
 int flex_plan_self_check(const flex_plan *p) try {
     if (!p) return FLEX_ERR_INVALID;
     if (p->m == 0) return FLEX_OK;
-    int cur = -1;
-    FLEX_HIP_TRY(hipGetDevice(&cur));
-    if (cur != p->device) FLEX_HIP_TRY(hipSetDevice(p->device));
-    std::vector<uint2> rec(p->n_records), t_aux(p->n_tasks);
-    std::vector<uint32_t> t_beg(static_cast<size_t>(p->n_tasks) + 1), t_dst(p->n_tasks);
-    std::vector<uint4> chunk(p->n_slots);
-    std::vector<uint2> chunk_bd(p->n_bundles ? p->n_slots : 0u);
-    std::vector<uint32_t> bd_rows(p->n_bd_rows);
-    std::vector<SplitRow> split(p->n_split);
-    auto down = [&](void *dst, const void *src, size_t bytes) { return bytes == 0 || hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
-    const bool ok_copy = down(rec.data(), p->d_rec, rec.size() * sizeof(uint2)) && down(t_beg.data(), p->d_t_beg, t_beg.size() * 4) &&
-                         down(t_dst.data(), p->d_t_dst, t_dst.size() * 4) && down(chunk.data(), p->d_chunk, chunk.size() * sizeof(uint4)) &&
-                         down(split.data(), p->d_split, split.size() * sizeof(SplitRow)) && down(t_aux.data(), p->d_t_aux, t_aux.size() * sizeof(uint2)) &&
-                         down(chunk_bd.data(), p->d_chunk_bd, chunk_bd.size() * sizeof(uint2)) && down(bd_rows.data(), p->d_bd_rows, bd_rows.size() * 4);
-    if (cur != p->device) (void)hipSetDevice(cur);
-    if (!ok_copy) return FLEX_ERR_HIP;
-    if ((p->n_bundles != 0) != (p->d_bd_rows != nullptr) || (p->n_bundles != 0) != (p->d_chunk_bd != nullptr)) return FLEX_ERR_FORMAT;
+    const DeviceScope on(p->device);
+    FLEX_HIP_TRY(on.error());
+    // every array is as long as the plan's counts say, before any of them is read
+    const size_t n_rec = p->d_rec.size(), n_tasks = p->n_tasks, n_slots = p->n_slots, n_blocks = p->bk_blocks;
+    if (p->d_t_beg.size() != n_tasks + 1 || p->d_t_dst.size() != n_tasks || p->d_t_aux.size() != n_tasks || p->d_chunk.size() != n_slots ||
+        p->d_chunk_bd.size() != (p->n_bundles ? n_slots : 0) || p->d_split.size() != p->n_split)
+        return FLEX_ERR_FORMAT;
+    if (p->mutable_vals && (p->d_src.size() != n_rec || p->d_vrec.size() != n_rec || p->d_sd_grp.size() != p->n_sd_groups + size_t(1))) return FLEX_ERR_FORMAT;
+    if (p->n_tiles && (p->d_rt_ptr.size() != p->n_row_tiles + size_t(1) || p->d_rt_rows.size() != 32 * size_t(p->n_row_tiles) ||
+                       p->d_tile_boff.size() != 32 * size_t(p->n_tiles)))
+        return FLEX_ERR_FORMAT;
+    if (n_blocks && (p->d_bk_hdr.size() != n_blocks || p->d_bk_wstart.size() != n_blocks * kBkWaves ||
+                     p->d_bk_brow.size() != n_blocks * p->bk_rounds * kBkRowsPerRound || p->d_bk_link.size() != p->d_bk_brow.size()))
+        return FLEX_ERR_FORMAT;
+    if ((p->n_bundles != 0) != (p->d_bd_rows.get() != nullptr) || (p->n_bundles != 0) != (p->d_chunk_bd.get() != nullptr)) return FLEX_ERR_FORMAT;
+    std::vector<uint2> rec, t_aux, chunk_bd;
+    std::vector<uint32_t> t_beg, t_dst, bd_rows;
+    std::vector<uint4> chunk;
+    std::vector<SplitRow> split;
+    if (!read_back(p->d_rec, rec) || !read_back(p->d_t_beg, t_beg) || !read_back(p->d_t_dst, t_dst) || !read_back(p->d_chunk, chunk) ||
+        !read_back(p->d_split, split) || !read_back(p->d_t_aux, t_aux) || !read_back(p->d_chunk_bd, chunk_bd) || !read_back(p->d_bd_rows, bd_rows))
+        return FLEX_ERR_HIP;
 
     // tasks tile the record stream
-    if (t_beg[0] != 0 || t_beg[p->n_tasks] != p->n_records) return FLEX_ERR_FORMAT;
+    if (t_beg[0] != 0 || t_beg[p->n_tasks] != n_rec) return FLEX_ERR_FORMAT;
     for (uint32_t t = 0; t < p->n_tasks; ++t)
         if (t_beg[t] > t_beg[t + 1]) return FLEX_ERR_FORMAT;
     // chunks tile the tasks (in table order, skipping the empty padding entries), each within the kernel's limits
@@ -333,13 +338,8 @@ int flex_plan_self_check(const flex_plan *p) try {
     // dense tiles: the row-tile directory tiles the tile list, every listed C row is valid and named by one row tile only,
     // every tile column names a valid B row
     if (p->n_tiles) {
-        std::vector<uint32_t> rt_ptr(static_cast<size_t>(p->n_row_tiles) + 1), rt_rows(static_cast<size_t>(p->n_row_tiles) * 32),
-            boff(static_cast<size_t>(p->n_tiles) * 32);
-        if (cur != p->device) FLEX_HIP_TRY(hipSetDevice(p->device));
-        const bool ok_t = down(rt_ptr.data(), p->d_rt_ptr, rt_ptr.size() * 4) && down(rt_rows.data(), p->d_rt_rows, rt_rows.size() * 4) &&
-                          down(boff.data(), p->d_tile_boff, boff.size() * 4);
-        if (cur != p->device) (void)hipSetDevice(cur);
-        if (!ok_t) return FLEX_ERR_HIP;
+        std::vector<uint32_t> rt_ptr, rt_rows, boff;
+        if (!read_back(p->d_rt_ptr, rt_ptr) || !read_back(p->d_rt_rows, rt_rows) || !read_back(p->d_tile_boff, boff)) return FLEX_ERR_HIP;
         if (rt_ptr[0] != 0 || rt_ptr[p->n_row_tiles] != p->n_tiles) return FLEX_ERR_FORMAT;
         for (uint32_t i = 0; i < p->n_row_tiles; ++i)
             if (rt_ptr[i] >= rt_ptr[i + 1]) return FLEX_ERR_FORMAT;
@@ -359,19 +359,17 @@ int flex_plan_self_check(const flex_plan *p) try {
     if (p->bk_blocks) {
         const uint32_t nb = p->bk_blocks, rounds = p->bk_rounds, P = p->bk_panel_rows, RB = rounds * kBkRowsPerRound;
         if ((rounds != 2 && rounds != 4 && rounds != 8) || P == 0 || P % 4 != 0 || P > kBkPanelMax || !p->off32) return FLEX_ERR_FORMAT;
-        std::vector<uint4> hdr(nb);
-        std::vector<uint2> wstart(static_cast<size_t>(nb) * kBkWaves), brec(static_cast<size_t>(p->bk_records));
-        std::vector<uint32_t> brow(static_cast<size_t>(nb) * RB), link(static_cast<size_t>(nb) * RB);
-        if (cur != p->device) FLEX_HIP_TRY(hipSetDevice(p->device));
-        bool ok_b = down(hdr.data(), p->d_bk_hdr, hdr.size() * sizeof(uint4)) && down(wstart.data(), p->d_bk_wstart, wstart.size() * sizeof(uint2)) &&
-                    down(brec.data(), p->d_bk_rec, brec.size() * sizeof(uint2)) && down(brow.data(), p->d_bk_brow, brow.size() * 4) &&
-                    down(link.data(), p->d_bk_link, link.size() * 4);
+        std::vector<uint4> hdr;
+        std::vector<uint2> wstart, brec;
+        std::vector<uint32_t> brow, link, cnt, hcol;
+        if (!read_back(p->d_bk_hdr, hdr) || !read_back(p->d_bk_wstart, wstart) || !read_back(p->d_bk_rec, brec) || !read_back(p->d_bk_brow, brow) ||
+            !read_back(p->d_bk_link, link))
+            return FLEX_ERR_HIP;
+        // hcol and cnt: as long as the headers just read say
         uint64_t n_cnt = 0, n_hcol = 0;
         for (const uint4 &h : hdr) n_cnt += static_cast<uint64_t>(h.w) * kBkWaves, n_hcol += static_cast<uint64_t>(h.x & 0x7FFFFFFFu) * P;
-        std::vector<uint32_t> cnt(static_cast<size_t>(n_cnt)), hcol(static_cast<size_t>(n_hcol));
-        ok_b = ok_b && down(cnt.data(), p->d_bk_cnt, cnt.size() * 4) && down(hcol.data(), p->d_bk_hcol, hcol.size() * 4);
-        if (cur != p->device) (void)hipSetDevice(cur);
-        if (!ok_b) return FLEX_ERR_HIP;
+        if (n_cnt != p->d_bk_cnt.size() || n_hcol != p->d_bk_hcol.size()) return FLEX_ERR_FORMAT;
+        if (!read_back(p->d_bk_cnt, cnt) || !read_back(p->d_bk_hcol, hcol)) return FLEX_ERR_HIP;
         for (uint32_t o : hcol)
             if (o % row_bytes != 0 || o / row_bytes >= static_cast<uint64_t>(p->n)) return FLEX_ERR_FORMAT;
         uint64_t at_hcol = 0, at_cnt = 0, at_step = 0;

@@ -159,19 +159,6 @@ int launch_sddmm_w(const SddmmView &v, bool off32, bool vec4, const float *G, co
     return FLEX_OK;
 }
 
-// the plan's device, for the length of one entry point
-struct OnDevice {
-    int prev = -1;
-    hipError_t err = hipSuccess;
-    explicit OnDevice(int dev) {
-        err = hipGetDevice(&prev);
-        if (err == hipSuccess && prev != dev) err = hipSetDevice(dev);
-    }
-    ~OnDevice() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
 }  // namespace values
 }  // namespace flex
 
@@ -181,16 +168,16 @@ extern "C" {
 
 int flex_plan_set_values(flex_plan *p, const float *dVals, flex_stream_t stream) {
     if (!p || !p->mutable_vals) return FLEX_ERR_INVALID;
-    if (p->n_records == 0) return FLEX_OK;
+    const uint64_t n = p->d_rec.size();
+    if (n == 0) return FLEX_OK;
     if (!dVals && p->nnz > 0) return FLEX_ERR_INVALID;
-    values::OnDevice on(p->device);
-    FLEX_HIP_TRY(on.err);
+    const DeviceScope on(p->device);
+    FLEX_HIP_TRY(on.error());
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const uint64_t n = p->n_records;
-    hipLaunchKernelGGL(values::refresh_records, dim3(static_cast<uint32_t>((n + 255) / 256)), dim3(256), 0, s, p->d_rec, p->d_vrec, p->d_src, dVals, n);
+    hipLaunchKernelGGL(values::refresh_records, dim3(static_cast<uint32_t>((n + 255) / 256)), dim3(256), 0, s, p->d_rec.get(), p->d_vrec.get(), p->d_src.get(), dVals, n);
     FLEX_HIP_TRY(hipGetLastError());
-    if (p->n_segs) {
-        hipLaunchKernelGGL(values::refresh_padding, dim3((p->n_segs + 255) / 256), dim3(256), 0, s, p->d_rec, p->d_seg, p->n_segs);
+    if (const uint32_t n_segs = static_cast<uint32_t>(p->d_seg.size())) {
+        hipLaunchKernelGGL(values::refresh_padding, dim3((n_segs + 255) / 256), dim3(256), 0, s, p->d_rec.get(), p->d_seg.get(), n_segs);
         FLEX_HIP_TRY(hipGetLastError());
     }
     return FLEX_OK;
@@ -203,10 +190,10 @@ int flex_sddmm(const flex_plan *p, const float *dG, const float *dB, float *dOut
     const int W = sddmm_lanes(p->k);
     const int ns = (p->k + 4 * W - 1) / (4 * W);
     if (ns > values::kMaxSlabs) return FLEX_ERR_UNSUPPORTED;
-    values::OnDevice on(p->device);
-    FLEX_HIP_TRY(on.err);
+    const DeviceScope on(p->device);
+    FLEX_HIP_TRY(on.error());
     const bool vec4 = p->k % 4 == 0 && p->ldb % 4 == 0 && p->ldc % 4 == 0 && ((reinterpret_cast<uintptr_t>(dG) | reinterpret_cast<uintptr_t>(dB)) % 16 == 0);
-    const values::SddmmView v{p->d_rec, p->d_src, p->d_sd_item, p->d_sd_grp, p->n_sd_groups, p->xcd_remap ? 1u : 0u, p->k, p->ldb, p->ldc, ns};
+    const values::SddmmView v{p->d_rec.get(), p->d_src.get(), p->d_sd_item.get(), p->d_sd_grp.get(), p->n_sd_groups, p->xcd_remap ? 1u : 0u, p->k, p->ldb, p->ldc, ns};
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     switch (W) {
         case 4: values::launch_sddmm_w<4>(v, p->off32, vec4, dG, dB, dOut, s); break;

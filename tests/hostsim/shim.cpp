@@ -7,6 +7,8 @@
 // instantiation the real launcher would launch -- as `nm -C` prints it, e.g. "spmm_flat_kernel<8, false, 4, 4, false>" -- and
 // reports FLEX_OK, still computing nothing.  The selection below MIRRORS the rules of launch_spmm / launch_spmm_stamped / launch_fixup
 // (spmm_kernels.hip), launch_tiles (tile_kernels.hip) and launch_blocks (block_kernels.hip): a change there must be made here too.
+// The "device memory" is counted (hostsim_live_allocations) and an allocation can be made to fail (hostsim_fail_malloc_at), so that
+// a test can check that a plan gives back everything it allocated, also when its creation fails half way.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -81,8 +83,28 @@ const char *hostsim_launch_log_read(void) { return g_log.c_str(); }
 #ifdef FLEX_HOSTSIM  // malloc-backed stand-ins for the few HIP runtime calls the planner makes (bound locally: -Bsymbolic-functions)
 hipError_t hipGetDevice(int *d) { *d = 0; return hipSuccess; }
 hipError_t hipSetDevice(int) { return hipSuccess; }
-hipError_t hipMalloc(void **p, size_t n) { *p = std::malloc(n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
-hipError_t hipFree(void *p) { std::free(p); return hipSuccess; }
+static int64_t g_live = 0;      // hipMalloc successes minus hipFree calls on non-null pointers
+static int64_t g_fail_at = -1;  // the g_fail_at-th hipMalloc from now reports hipErrorOutOfMemory (1 = the next one); -1 = none
+hipError_t hipMalloc(void **p, size_t n) {
+    *p = nullptr;
+    if (g_fail_at > 0 && --g_fail_at == 0) {
+        g_fail_at = -1;
+        return hipErrorOutOfMemory;
+    }
+    *p = std::malloc(n ? n : 1);
+    if (!*p) return hipErrorOutOfMemory;
+    ++g_live;
+    return hipSuccess;
+}
+hipError_t hipFree(void *p) {
+    if (p) --g_live;
+    std::free(p);
+    return hipSuccess;
+}
+// device allocations alive now (a plan that leaks one, or frees one twice, moves the count)
+int64_t hostsim_live_allocations(void) { return g_live; }
+// make the n-th hipMalloc from now (n >= 1) fail once with hipErrorOutOfMemory; -1 (or anything below 1) turns this off
+void hostsim_fail_malloc_at(int64_t n) { g_fail_at = n > 0 ? n : -1; }
 static uint64_t g_upload_hash = 1469598103934665603ull;  // FNV-1a over every byte "uploaded" since the last reset: a fingerprint of the plan image
 hipError_t hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind) {
     if (n) std::memcpy(d, s, n);

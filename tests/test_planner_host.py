@@ -381,3 +381,40 @@ def test_row_bundles_by_rule_where_the_plan_fills_the_chip_or_the_rows_are_short
     assert flex_amd.Plan(fl, 128, tuning={"bundle": 2}).info()["lanes_per_nz"] == 32  # without bundles the wide tile stays the rule
     off = flex_amd.Plan(fl, 32, tuning={"bundle": 2})
     assert off.info()["n_bundles"] == 0 and off.info()["n_tasks"] > 3 * flex_amd.Plan(fl, 32).info()["n_tasks"]
+
+
+def test_plans_give_back_every_device_allocation_also_when_one_fails(sim):
+    """A plan owns its device image: destroying it frees every allocation create made, and a create whose n-th hipMalloc fails
+    reports the HIP failure and frees the n - 1 before it -- for every n, on every kind of plan (the shim counts live allocations)."""
+    import gc
+    sim.hostsim_live_allocations.restype = C.c_int64
+    sim.hostsim_fail_malloc_at.argtypes = [C.c_int64]
+    g = flex_amd.synth_graph(n=6000, nnz=6000 + 2 * 90000, community=200, p_in=0.55, p_near=0.3, seed=5)
+    a = random_csr(3000, 3000, 6, seed=21, long_rows={17: 2500, 2000: 900}, empty_frac=0.3)
+    bd = block_dense(1024, 64, 0.85, 3, seed=2)
+    kinds = {
+        "1-D, split rows, bundles": (lambda: flex_amd.Plan(a, 32, tuning={"bundle": 1}),
+                                     lambda i: i["n_split_rows"] > 0 and i["n_bundles"] > 0),
+        "2-D": (lambda: flex_amd.Plan(g, 128, tuning={"two_d": 1}), lambda i: i["two_d"] == 1),
+        "dense tiles": (lambda: flex_amd.Plan(bd, 128, tuning={"mfma": 1}), lambda i: i["n_tiles"] > 0),
+        "hot blocks": (lambda: flex_amd.Plan(g, 64, order=flex_amd.FLEX_ORDER_CLUSTER, tuning={"blocks": 1}), lambda i: i["n_blocks"] > 0),
+        "transposed, mutable values": (lambda: flex_amd.Plan(a, 32, transpose=True, mutable_values=True), lambda i: i["n_records"] >= a.nnz),
+        "statistics": (lambda: flex_amd.Plan(g, 32, order=flex_amd.FLEX_ORDER_RCM | flex_amd.FLEX_PLAN_STATS), lambda i: i["n_records"] >= g.nnz),
+    }
+    gc.collect()  # plans of earlier tests held in reference cycles would otherwise be freed in the middle of the count
+    start = sim.hostsim_live_allocations()
+    for name, (make, is_kind) in kinds.items():
+        p = make()
+        assert is_kind(p.info()), name
+        n_alloc = sim.hostsim_live_allocations() - start
+        assert n_alloc > 0, name
+        p.destroy()
+        assert sim.hostsim_live_allocations() == start, name
+        for n in range(1, n_alloc + 1):
+            sim.hostsim_fail_malloc_at(n)
+            try:
+                with pytest.raises(flex_amd.FlexError, match="HIP runtime call failed"):
+                    make()
+            finally:
+                sim.hostsim_fail_malloc_at(-1)
+            assert sim.hostsim_live_allocations() == start, (name, n)
