@@ -15,10 +15,10 @@
 //     the lane owns 4 of the tile's 64 columns): no cross-lane reduction, C read once and written once.
 //   * The block's hot B rows are staged panel by panel (up to 304 rows x 256 bytes) by the loader wave with LDS-DMA
 //     (global_load_lds_dwordx4, per-lane source = a row gather) into the other of two buffers while the consumers work on the
-//     current one: one s_barrier per panel.  (An experiment build, -DFLEX_BK_NBUF=3, keeps a ring of three 200-row buffers with the
-//     loader two panels ahead behind counted vmcnt waits: measured slower -- shorter panels mean more runs and more barriers.)  A slot's ds_read_b128 covers one whole 256-byte row = all 64 banks once, so the
-//     reads are conflict-free whatever rows the four slots of a wave are on (MI355X_MICROARCH.md, LDS: the 16-lane service
-//     groups hold quarter-rows of different slots, whose banks depend only on the lane).
+//     current one: one s_barrier per panel.  (A ring of three 200-row buffers with the loader two panels ahead was measured
+//     slower -- shorter panels mean more runs and more barriers: DESIGN.md 3.7.)  A slot's ds_read_b128 covers one whole
+//     256-byte row = all 64 banks once, so the reads are conflict-free whatever rows the four slots of a wave are on
+//     (MI355X_MICROARCH.md, LDS: the 16-lane service groups hold quarter-rows of different slots, whose banks depend only on the lane).
 //   * Records {offset inside the panel buffer, value} never touch LDS.  The stream of a wave is [step][slot], panel-major; the
 //     <= 16 steps of one RUN (one panel, one round) are fetched by ONE coalesced 512-byte load -- lane 16 s + j takes the record
 //     of (step j, slot s) -- a whole panel ahead of their use, and at step j the 16 lanes of a slot get their record by a DPP
@@ -86,19 +86,6 @@ __device__ __forceinline__ void dma_panel(char *lds, const char *__restrict__ Bb
         __builtin_amdgcn_global_load_lds((gl_void *)(Bb + boff[g * 4] + lane_goff), (lds_void *)(dst + g * 1024), 16, 0, 0);
 }
 
-// Diagnostic build only (make -C flex_amd/csrc trace; tools/trace_blocks.py): where a wave's cycles go.  Counters per wave:
-// 0 prologue (C rows, first records), 2 panel work, 3 waiting at barriers, 5 epilogue, 6 total, 7 steps.
-#ifdef FLEX_TRACE
-#define BK_STAMP(i)                                        \
-    do {                                                   \
-        const uint64_t now_ = __builtin_amdgcn_s_memtime(); \
-        bk_ph[i] += now_ - bk_last;                        \
-        bk_last = now_;                                    \
-    } while (0)
-#else
-#define BK_STAMP(i) do {} while (0)
-#endif
-
 template <int ROUNDS>
 __global__ __launch_bounds__(64 * (kBkWaves + 1)) void spmm_hot_kernel(BlockView v, const float *__restrict__ B, float *__restrict__ C) {
     __shared__ __attribute__((aligned(256))) char lds[kBkLdsBytes];
@@ -124,82 +111,27 @@ __global__ __launch_bounds__(64 * (kBkWaves + 1)) void spmm_hot_kernel(BlockView
 
     if (w == kBkWaves) {
         // ---- the loader wave: np + 1 barriers (+ 1 when rows have several parts), exactly as many as every consumer wave.
-        // It runs kBkNBuf - 1 panels ahead of the consumers.  vmcnt retires in order, so what it waits for is counted in
-        // instructions: H(q) = the DMA of panel q's byte offsets into the scratch (ONE instruction: panel_rows <= 256 on the fast
-        // path), D(q) = the panel's rows (panel_rows / 4 instructions of 1 KiB).  Issue order: ... H(q+1) D(q) H(q+2) D(q+1) ...:
-        // H(q+1) precedes D(q), so waiting for the offsets of the NEXT panel never waits for the rows of this one.
+        // It runs one panel ahead of the consumers, and every wait is a full drain.
         for (uint32_t b = 0; b < kBkNBuf; ++b) *reinterpret_cast<uint32_t *>(lds + b * kBkBufBytes + kBkZeroRow + lane * 4) = 0u;  // the rows of zeros padding records point at
         const uint32_t P = v.panel_rows;
         const uint32_t *__restrict__ hcol = v.hcol + hdr.y;
-        const bool stage = !(v.ablate & 1);
         auto H = [&](uint32_t q) { dma_hcol(lds, hcol + static_cast<uint64_t>(q) * P, P, q & 1, lane); };
-        auto D = [&](uint32_t q) {
-            if (stage) dma_panel(lds, Bb, lane_goff, P, q & 1, q % kBkNBuf, lane);
-        };
-        constexpr uint32_t kD = kBkPanelMax / 4;  // instructions of one D on the fast path
-        const bool fast = kBkNBuf == 3 && P == kBkPanelMax && P <= 256 && stage;  // counted waits need compile-time counts
-        if (fast) {
-            // exactly ONE instruction per H (lane 0 is always active): the counts below depend on it
-            auto H = [&](uint32_t q) {
-                if (static_cast<uint32_t>(lane) * 4u < P)
-                    __builtin_amdgcn_global_load_lds((gl_void *)(hcol + static_cast<uint64_t>(q) * P + lane * 4), (lds_void *)(lds + kBkLdsHcol + (q & 1) * (kBkPanelMax * 4)), 16, 0, 0);
-            };
-            // prologue: H0 H1 | D0 H2 | D1, panel 0 landed.  After it: issued ... H(p+2) D(p+1) at the top of iteration p.
-            H(0);
-            if (np > 1) {
-                H(1);
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(1) : "memory");  // H0: behind it H1
-            } else {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            D(0);
-            if (np > 2) H(2);
-            if (np > 1) {
-                if (np > 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kD + 1) : "memory");  // H1: behind it D0 and H2
-                else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kD) : "memory");            //     behind it D0
-                D(1);
-            }
-            if (np > 2) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(kD + 1) : "memory");  // D0: behind it H2 and D1
-            else loader_barrier();
-            for (uint32_t p = 0; p < np; ++p) {
-                if (p + 3 < np) {  // the steady state: H(p+3), D(p+2) go out; D(p+1) must have landed by the barrier
-                    H(p + 3);
-                    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kD + 1) : "memory");  // H(p+2): behind it D(p+1) and H(p+3)
-                    D(p + 2);
-                    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(kD + 1) : "memory");  // D(p+1): behind it H(p+3) and D(p+2)
-                } else {           // the last panels: nothing left to count against -- whatever is in flight has to land anyway
-                    if (p + 2 < np) {
-                        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kD) : "memory");  // H(p+2): behind it D(p+1)
-                        D(p + 2);
-                        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(kD) : "memory");  // D(p+1): behind it D(p+2)
-                    } else {
-                        loader_barrier();
-                    }
-                }
-            }
-        } else {
-            // any panel size, two or three buffers: one panel ahead, every wait a full drain
-            H(0);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            D(0);
-            if (np > 1) H(1);
-            loader_barrier();  // panel 0 staged (the consumers were fetching their C rows and first records meanwhile)
-            for (uint32_t p = 0; p < np; ++p) {
-                if (p + 1 < np) D(p + 1);
-                if (p + 2 < np) H(p + 2);
-                loader_barrier();  // consumers are done with panel p; panel p+1 has landed
-            }
+        auto D = [&](uint32_t q) { dma_panel(lds, Bb, lane_goff, P, q & 1, q & 1, lane); };
+        H(0);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        D(0);
+        if (np > 1) H(1);
+        loader_barrier();  // panel 0 staged (the consumers were fetching their C rows and first records meanwhile)
+        for (uint32_t p = 0; p < np; ++p) {
+            if (p + 1 < np) D(p + 1);
+            if (p + 2 < np) H(p + 2);
+            loader_barrier();  // consumers are done with panel p; panel p+1 has landed
         }
         if (chains) loader_barrier();
         return;
     }
 
     // ---- a consumer wave
-#ifdef FLEX_TRACE
-    uint64_t bk_ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t bk_last = __builtin_amdgcn_s_memtime();
-    const uint64_t bk_t0 = bk_last;
-#endif
     const uint32_t slot = static_cast<uint32_t>(lane) >> 4;
     const uint2 ws = v.wstart[static_cast<uint64_t>(blk) * kBkWaves + w];
     // Loads that run past the end of this wave's stream read the NEXT wave's records (harmless: such steps are never executed);
@@ -221,15 +153,14 @@ __global__ __launch_bounds__(64 * (kBkWaves + 1)) void spmm_hot_kernel(BlockView
 #pragma unroll
     for (int r = 0; r < ROUNDS; ++r) {  // the flat kernel's part of the row: this kernel adds to it
         const uint32_t row = rows[r] == kBkEmptyRow ? 0u : rows[r];
-        v4f cur = {0.f, 0.f, 0.f, 0.f};
-        if (!(v.ablate & 16)) cur = *reinterpret_cast<const v4f *>(C + static_cast<uint64_t>(row) * v.ldc + (col_ok ? c0 : 0));  // (wave-uniform; timing-only)
+        const v4f cur = *reinterpret_cast<const v4f *>(C + static_cast<uint64_t>(row) * v.ldc + (col_ok ? c0 : 0));
         acc[r] = (rows[r] != kBkEmptyRow && col_ok) ? cur : v4f{0.f, 0.f, 0.f, 0.f};
     }
     // run r of the next panel is fetched as soon as run r of this one is done with its registers: one panel of lead
     uint32_t rx[ROUNDS], ry[ROUNDS];
     uint32_t pos_pf = 0;  // step (wave-relative) at which the next run to fetch begins
     auto fetch_run = [&](int r, uint32_t n_run) {  // n_run: the steps of the run being fetched (the next one starts behind it)
-        const uint32_t idx = (v.ablate & 32) ? static_cast<uint32_t>(lane) : min((pos_pf + static_cast<uint32_t>(l16)) * kBkSlots + slot, last_rec);  // 32: timing-only, one hot line
+        const uint32_t idx = min((pos_pf + static_cast<uint32_t>(l16)) * kBkSlots + slot, last_rec);
         const v2u q = __builtin_nontemporal_load(reinterpret_cast<const v2u *>(rec + idx));  // read once per tile
         rx[r] = q.x;
         ry[r] = q.y;
@@ -240,19 +171,17 @@ __global__ __launch_bounds__(64 * (kBkWaves + 1)) void spmm_hot_kernel(BlockView
 #pragma unroll
         for (int r = 0; r < ROUNDS; ++r) fetch_run(r, count_of(lo, hi, r));
     }
-    BK_STAMP(0);
     consumer_barrier();  // panel 0 has landed
-    BK_STAMP(3);
 
     for (uint32_t p = 0; p < np; ++p) {
-        const uint32_t base = (p % kBkNBuf) * kBkBufBytes + static_cast<uint32_t>(l16) * 16u;
+        const uint32_t base = (p & 1) * kBkBufBytes + static_cast<uint32_t>(l16) * 16u;
         const char *panel = lds + base;
         // this panel's eight run counts and the next panel's (lane np holds 0): four v_readlane per panel, a bit-field extract per run
         const uint32_t lo = __builtin_amdgcn_readlane(c_lo, p), hi = __builtin_amdgcn_readlane(c_hi, p);
         const uint32_t nlo = __builtin_amdgcn_readlane(c_lo, p + 1), nhi = __builtin_amdgcn_readlane(c_hi, p + 1);
 #pragma unroll
         for (int r = 0; r < ROUNDS; ++r) {
-            const uint32_t n = (v.ablate & 2) ? 0u : count_of(lo, hi, r);
+            const uint32_t n = count_of(lo, hi, r);
             const uint32_t x = rx[r], y = ry[r];
             v4f a = acc[r];
             // four steps at a time while the run has them (wave-uniform branches; step indices are compile-time: DPP controls are immediates)
@@ -298,9 +227,7 @@ __global__ __launch_bounds__(64 * (kBkWaves + 1)) void spmm_hot_kernel(BlockView
             // unconditional (an index past the stream is clamped, its count is 0): a load inside a branch costs an s_waitcnt vmcnt(0)
             fetch_run(r, count_of(nlo, nhi, r));
         }
-        BK_STAMP(2);
         consumer_barrier();
-        BK_STAMP(3);
     }
     // A long row's parts: every later part leaves its sum (and the slot of the part after it) in LDS -- the panel buffers are free
     // now -- and after one more barrier the owner adds them in chain order: a fixed order, so the result is reproducible.
@@ -331,17 +258,7 @@ __global__ __launch_bounds__(64 * (kBkWaves + 1)) void spmm_hot_kernel(BlockView
     }
 #pragma unroll
     for (int r = 0; r < ROUNDS; ++r)
-        if (rows[r] != kBkEmptyRow && col_ok && !(v.ablate & 16)) *reinterpret_cast<v4f *>(C + static_cast<uint64_t>(rows[r]) * v.ldc + c0) = acc[r];
-#ifdef FLEX_TRACE
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    BK_STAMP(5);
-    bk_ph[6] = bk_last - bk_t0;
-    bk_ph[7] = ws.y;
-    if (lane == 0 && v.trace != nullptr) {
-        uint64_t *o = v.trace + ((static_cast<uint64_t>(blockIdx.y) * v.n_blocks + blk) * kBkWaves + w) * 8;
-        for (int i = 0; i < 8; ++i) o[i] = bk_ph[i];
-    }
-#endif
+        if (rows[r] != kBkEmptyRow && col_ok) *reinterpret_cast<v4f *>(C + static_cast<uint64_t>(rows[r]) * v.ldc + c0) = acc[r];
 }
 
 // The same block image for operands the fast kernel cannot take (B or C not 16-byte aligned: LDS-DMA and the float4 accesses need

@@ -36,7 +36,7 @@ struct PlanView {
     uint32_t tile_group;     // 0: column tiles are the slow grid dimension (one pass over all chunks per tile).  Else: workgroups per group --
                              // every XCD slice of the chunk table is walked group by group, all column tiles of a group back to back, so that
                              // a group's records are re-read while they are still in the Infinity Cache (1-D grid of n_workgroups x tiles)
-    uint64_t *trace;         // flex_plan_measure_imbalance: 3 words per (k-tile, chunk-table entry); diagnostic -DFLEX_TRACE builds: 12 per wave; else nullptr
+    uint64_t *trace;         // the stamped twin's log (flex_plan_measure_imbalance): 3 words per (k-tile, chunk-table entry); else nullptr
     // Row bundles (plan_build.cpp, form_tasks): a task that holds up to S = 64 / G SHORT rows side by side, slot s of every step working
     // on row s -- no cross-slot reduction, one 16-byte store per lane at the end.  nullptr when the plan has none.
     const uint32_t *bd_rows; // per bundle S entries: C row of slot s | kBundleZero (the row holds no nonzero: zeros are stored), or kBundleNoRow
@@ -65,29 +65,23 @@ struct TileView {
 // whole 256-byte row = all 64 banks).  Records never touch LDS: a RUN (the <= 16 steps of one (wave, panel, round)) is one coalesced
 // 512-byte load into a register pair a whole panel ahead, and step j's record reaches the 16 lanes of its slot by a DPP row
 // broadcast (row_newbcast:j) -- the LDS pipe carries nothing but B.
-#ifndef FLEX_BK_WAVES
-#define FLEX_BK_WAVES 15
-#endif
-constexpr int kBkWaves = FLEX_BK_WAVES;                   // consumer waves per workgroup
+constexpr int kBkWaves = 15;                              // consumer waves per workgroup
 constexpr int kBkSlots = 4;                               // slots per wave (16 lanes x float4 = one 64-column tile of one row)
 constexpr int kBkTileCols = 64;                           // columns of C per pass
 constexpr int kBkRowsPerRound = kBkWaves * kBkSlots;      // 60 row slots per round
 constexpr int kBkMaxRounds = 8;
 constexpr uint32_t kBkRunMax = 16;                        // steps of one run = lanes of a slot: what one DPP row holds
-#ifndef FLEX_BK_NBUF       // experiment builds (make -C flex_amd/csrc block_variants) may vary the two; the product has one pair
-#define FLEX_BK_NBUF 2     // measured (profiles/r04_hot_block_ring_probe.txt): three buffers of 200 rows with the loader two panels ahead are
-#endif                     // SLOWER than two of 304 -- more panels mean more runs and barriers, and those, not staging latency, are what the kernel pays for
-#ifndef FLEX_BK_PANEL_MAX
-#define FLEX_BK_PANEL_MAX (FLEX_BK_NBUF == 2 ? 304 : 200)
-#endif
-constexpr uint32_t kBkNBuf = FLEX_BK_NBUF;                // panel buffers: the loader runs kBkNBuf - 1 panels ahead of the consumers
-constexpr uint32_t kBkPanelMax = FLEX_BK_PANEL_MAX;       // B rows per LDS panel
+// Two panel buffers of 304 rows, the loader one panel ahead.  Measured (profiles/r04_hot_block_ring_probe.txt): three buffers of 200
+// rows with the loader two panels ahead are SLOWER -- more panels mean more runs and barriers, and those, not staging latency, are
+// what the kernel pays for.
+constexpr uint32_t kBkNBuf = 2;                           // panel buffers
+constexpr uint32_t kBkPanelMax = 304;                     // B rows per LDS panel
 constexpr uint32_t kBkRowBytes = 256;                     // one B row of one column tile
 constexpr uint32_t kBkZeroRow = kBkPanelMax * kBkRowBytes; // byte offset, inside a panel buffer, of a row of zeros (padding records point at it)
 constexpr uint32_t kBkBufBytes = kBkZeroRow + kBkRowBytes;
 constexpr uint32_t kBkLdsHcol = kBkNBuf * kBkBufBytes;    // two scratch slots for the byte offsets of the panels about to be staged
 constexpr uint32_t kBkLdsBytes = kBkLdsHcol + 2 * kBkPanelMax * 4;  // 158 592 of the CU's 163 840 (two buffers of 304 rows)
-static_assert(kBkLdsBytes <= 163840 && kBkPanelMax % 4 == 0 && kBkPanelMax <= 256 + 48 && (kBkNBuf == 2 || kBkNBuf == 3), "the hot kernel's LDS image must fit one CU");
+static_assert(kBkLdsBytes <= 163840 && kBkPanelMax % 4 == 0 && kBkPanelMax <= 256 + 48 && kBkNBuf == 2, "the hot kernel's LDS image must fit one CU");
 constexpr uint32_t kBkLdsNext = kBkMaxRounds * kBkRowsPerRound * kBkRowBytes;  // after the last panel: [slots] sums of later parts, then [slots] next part + 1
 static_assert(kBkLdsNext + kBkMaxRounds * kBkRowsPerRound * 4 <= kBkLdsHcol, "the parts of long rows meet in the panel buffers");
 constexpr uint32_t kBkEmptyRow = 0xFFFFFFFFu;             // brow entry of a slot that holds no row
@@ -109,8 +103,6 @@ struct BlockView {
     uint32_t n_blocks, rounds, panel_rows;
     int32_t k, ldb, ldc;
     uint32_t xcd_remap;
-    uint32_t ablate;         // timing-only (tools/probe_blocks.py; results are WRONG): 1 no panel DMA, 2 no panel work, 16 no read-modify-write of C, 32 every record load hits one line
-    uint64_t *trace;         // -DFLEX_TRACE builds only (tools/trace_blocks.py): 8 cycle counters per (tile, block, wave); else nullptr
 };
 
 constexpr uint32_t kPartialFlag = 0x80000000u;

@@ -129,6 +129,9 @@ int autotune(std::unique_ptr<flex_plan> &best, const flex_csr *A, int32_t r0, in
 
 extern "C" {
 
+// ABI 3's layout: block_ablate_retired holds the place of a retired knob, so that no later field moves
+static_assert(sizeof(flex_plan_tuning) == 160 && offsetof(flex_plan_tuning, block_ablate_retired) == 116 && sizeof(flex_plan_desc) == 80);
+
 // every knob is "0 = rule" or a small positive number; anything negative or absurd is a caller bug, not a request
 static bool tuning_ok(const flex_plan_tuning &t) {
     const int32_t *f = reinterpret_cast<const int32_t *>(&t);
@@ -136,7 +139,7 @@ static bool tuning_ok(const flex_plan_tuning &t) {
         if (f[i] < 0 || f[i] > (1 << 28)) return false;
     for (int32_t r : t.reserved)
         if (r != 0) return false;
-    return true;
+    return t.block_ablate_retired == 0;
 }
 
 // FLEX_PLAN_TRANSPOSE: the CSR of A^T, built by a stable counting sort -- row c of A^T lists the rows of A that hold column c in
@@ -346,7 +349,7 @@ int flex_spmm(flex_plan *p, const float *dB, float *dC, flex_stream_t stream) {
         if (q == hipErrorNotReady) return FLEX_ERR_INVALID;
         if (q != hipSuccess) (void)hipGetLastError();  // e.g. the old stream has been destroyed: nothing of ours can be pending on it
     }
-    rc = launch_spmm(plan_view(p, fused, p->trace), p->lanes_per_nz, p->off32, vec4, dB, dC, s, p->unroll);
+    rc = launch_spmm(plan_view(p, fused, nullptr), p->lanes_per_nz, p->off32, vec4, dB, dC, s, p->unroll);
     if (rc == FLEX_OK && !fused) rc = launch_fixup(p->d_partial.get(), p->d_split.get(), p->n_split, p->k, p->ldc, dC, s);
     // the dense tiles' share, added to the rows the kernels above have written
     if (rc == FLEX_OK && p->n_tiles) rc = launch_tiles(tile_view(p), p->off32, dB, dC, p->k, p->ldb, p->ldc, s);
@@ -436,15 +439,6 @@ int flex_gather_rows(float *dst, const float *src, const int32_t *idx, int64_t n
     if (!dst || !src || !idx) return FLEX_ERR_INVALID;
     return launch_gather_rows(dst, src, idx, n, k, reinterpret_cast<hipStream_t>(stream));
 }
-
-#ifdef FLEX_TRACE
-// diagnostic build only (libflex_spmm_trace.so, tools/trace.py); not part of the ABI
-int flex_debug_set_trace(flex_plan *p, uint64_t *dev_log) {
-    if (!p) return FLEX_ERR_INVALID;
-    p->trace = dev_log;
-    return FLEX_OK;
-}
-#endif
 
 const char *flex_strerror(int status) {
     switch (status) {

@@ -90,7 +90,6 @@ struct flex_plan {
     bool rec_nt = false;
     uint32_t tile_group = 0;
     int unroll = 0;
-    uint64_t *trace = nullptr;
     unsigned order = 0;
     // the device image (internal.h, PlanView): records (nnz + padding), tasks, the chunk table
     flex::DeviceArray<uint2> d_rec;
@@ -119,7 +118,7 @@ struct flex_plan {
     flex::DeviceArray<uint4> d_bk_hdr;
     flex::DeviceArray<uint2> d_bk_wstart, d_bk_rec;
     flex::DeviceArray<uint32_t> d_bk_cnt, d_bk_hcol, d_bk_brow, d_bk_link;
-    uint32_t bk_blocks = 0, bk_rounds = 0, bk_panel_rows = 0, bk_ablate = 0;
+    uint32_t bk_blocks = 0, bk_rounds = 0, bk_panel_rows = 0;
     int64_t bk_rows = 0, bk_nnz = 0, bk_hot_nnz = 0, bk_hot_cols = 0, bk_panels = 0;
     uint32_t n_tasks = 0, n_chunks = 0, n_slots = 0, n_split = 0, n_partials = 0;  // n_slots: chunk table incl. padding
     int64_t c_rows = 0;       // rows of C the plan writes into (m, or hostA->m for a mapped plan)
@@ -176,7 +175,7 @@ inline PlanView plan_view(const flex_plan *p, bool fused, uint64_t *trace) {
 inline BlockView block_view(const flex_plan *p) {
     return BlockView{p->d_bk_hdr.get(), p->d_bk_wstart.get(), p->d_bk_cnt.get(), p->d_bk_hcol.get(), p->d_bk_brow.get(), p->d_bk_link.get(), p->d_bk_rec.get(),
                      static_cast<uint64_t>(std::max<size_t>(p->d_bk_rec.size(), 1)),
-                     p->bk_blocks, p->bk_rounds, p->bk_panel_rows, p->k, p->ldb, p->ldc, 1u, p->bk_ablate, p->trace};
+                     p->bk_blocks, p->bk_rounds, p->bk_panel_rows, p->k, p->ldb, p->ldc, 1u};
 }
 inline TileView tile_view(const flex_plan *p) {
     return TileView{p->d_tile_a.get(), p->d_tile_boff.get(), p->d_tile_mask.get(), p->d_rt_ptr.get(), p->d_rt_rows.get(), p->n_row_tiles};

@@ -382,7 +382,6 @@ class PlanBuilder {
         p->bk_hot_nnz = img.hot_nnz;
         p->bk_hot_cols = img.hot_cols;
         p->bk_panels = img.panels;
-        p->bk_ablate = static_cast<uint32_t>(tn.block_ablate);
         img = BlockImage{};
         keep_unmarked(hot_mask);
         // what stays flat is a different matrix -- by construction the nonzeros WITHOUT reuse nearby: its tile width and chunk budget

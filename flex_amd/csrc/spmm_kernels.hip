@@ -248,19 +248,6 @@ constexpr bool kTileHasBundles = 64 / G >= static_cast<int>(kBundleMinSlots);
 }
 
 // One chunk = tasks [w_task[c], w_task[c+1]) = one contiguous run of the record stream.
-#ifdef FLEX_TRACE
-#define FLEX_STAMP(i)                                                       \
-    do {                                                                    \
-        uint64_t now_;                                                      \
-        __builtin_amdgcn_sched_barrier(0);                                  \
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now_)::"memory"); \
-        __builtin_amdgcn_sched_barrier(0);                                  \
-        phase[i] += now_ - last_;                                           \
-        last_ = now_;                                                       \
-    } while (0)
-#else
-#define FLEX_STAMP(i) do {} while (0)
-#endif
 
 // Stage records [wz, wz+wn) of the stream into the wave's LDS slice: coalesced 512-B loads, lane l takes
 // records l, l+64, l+128, l+192.  Indices are clamped, not predicated (slots >= wn get a copy of the last
@@ -311,11 +298,7 @@ __device__ __forceinline__ void stage_window(uint2 *my_lds, const uint2 *__restr
 template <int G, bool OFF32, int U>
 __device__ __forceinline__ void compute_chunk(const PlanView &p, uint4 hdr, uint32_t my_beg, uint32_t my_dst, uint2 my_aux,
                                               uint32_t my_bd0, uint32_t my_bd1, uint2 *my_lds, const char *__restrict__ Bb,
-                                              float *__restrict__ C, int lane, int c0, bool col_ok, uint32_t tile, uint32_t ktiles
-#ifdef FLEX_TRACE
-                                              , uint64_t *phase, uint64_t &last_
-#endif
-) {
+                                              float *__restrict__ C, int lane, int c0, bool col_ok, uint32_t tile, uint32_t ktiles) {
     constexpr int S = 64 / G;
     const int slot = lane / G;
     const int k = p.k;
@@ -327,7 +310,6 @@ __device__ __forceinline__ void compute_chunk(const PlanView &p, uint4 hdr, uint
     const uint2 *__restrict__ rec = p.rec;
 
     const uint32_t nt = hdr.y, zb = hdr.z, ze = hdr.w;
-    FLEX_STAMP(0);  // descriptors
 
     uint32_t ti = 0;                                          // current task
     uint32_t row_end = __builtin_amdgcn_readlane(my_beg, 1);  // where it ends in the record stream
@@ -371,12 +353,7 @@ __device__ __forceinline__ void compute_chunk(const PlanView &p, uint4 hdr, uint
                 }
             } else {
                 const RowOut<G> o = reduce_row<G>(acc);
-#ifdef FLEX_ABL_NOSTORE  // timing-only ablation: the store is kept in the code but never executes
-                if (out_ok && p.k < 0)
-#else
-                if (out_ok)
-#endif
-                    store_row_out<G>(C + static_cast<uint64_t>(dst) * ldc + out_col, o);
+                if (out_ok) store_row_out<G>(C + static_cast<uint64_t>(dst) * ldc + out_col, o);
             }
             acc = {0.f, 0.f, 0.f, 0.f};
             ++ti;
@@ -391,13 +368,6 @@ __device__ __forceinline__ void compute_chunk(const PlanView &p, uint4 hdr, uint
         const uint32_t wn = min(static_cast<uint32_t>(kWindowRecs<G>), ze - wz);
         // stage this window's records: coalesced 512-B loads, one ds_write_b64 per lane and load
         stage_window<G>(my_lds, rec, wz, wn, lane, p.rec_nt != 0);
-        FLEX_STAMP(1);  // records -> LDS
-#ifdef FLEX_ABL_STAGEONLY  // timing-only ablation: header, descriptors and records fetched, then leave
-        if (p.k > 0) {
-            if (lane == 0 && my_lds[wn - 1].x == 0xFFFFFFFEu) C[0] = as_f32(my_beg + my_dst);
-            return;
-        }
-#endif
         const uint32_t nsteps = wn / S;  // rows are padded to multiples of S
         const uint2 *lds_slot = my_lds + slot;
         uint32_t j = 0;
@@ -406,54 +376,32 @@ __device__ __forceinline__ void compute_chunk(const PlanView &p, uint4 hdr, uint
             float4 b[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) r[u] = lds_slot[(j + u) * S];
-#ifdef FLEX_ABL_NOGATHER  // timing-only ablation: no B traffic at all, values faked from the record
-#pragma unroll
-            for (int u = 0; u < U; ++u) b[u] = make_float4(as_f32(r[u].x), as_f32(r[u].y), 1.f, 2.f);
-#else
 #pragma unroll
             for (int u = 0; u < U; ++u) b[u] = gather4<OFF32>(Bb, r[u].x, lane_off, row_bytes);
-#endif
-            FLEX_STAMP(2);  // gathers
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 fma4(acc, as_f32(r[u].y), b[u]);
                 pos += S;
-#ifndef FLEX_ABL_NOFLUSH  // timing-only ablation: rows are never written out (one flush at the very end)
                 if (pos == row_end) flush(pos);
-#endif
             }
-            FLEX_STAMP(3);  // fma + row flushes
         }
         if (j < nsteps) {  // the window's last, partial block
             uint2 r[U];
             float4 b[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) r[u] = lds_slot[min(j + u, nsteps - 1) * S];
-#ifdef FLEX_ABL_NOGATHER
-#pragma unroll
-            for (int u = 0; u < U; ++u) b[u] = make_float4(as_f32(r[u].x), as_f32(r[u].y), 1.f, 2.f);
-#else
 #pragma unroll
             for (int u = 0; u < U; ++u) b[u] = gather4<OFF32>(Bb, r[u].x, lane_off, row_bytes);
-#endif
-            FLEX_STAMP(2);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 if (j + u < nsteps) {  // wave-uniform
                     fma4(acc, as_f32(r[u].y), b[u]);
                     pos += S;
-#ifndef FLEX_ABL_NOFLUSH
                     if (pos == row_end) flush(pos);
-#endif
                 }
             }
-            FLEX_STAMP(3);
         }
     }
-#ifdef FLEX_ABL_NOFLUSH
-    // pos != the ~0 sentinel, or the do-while never ends
-    if (nt > 0) { ti = nt - 1; flush(0xFFFFFFFEu); }
-#endif
     // Pieces are combined INSIDE this launch by whichever piece arrives last (cdna guide G16, counter form with
     // write-through payload): (1) every partial sum of this chunk was stored write-through (sc1), so it is at
     // device scope once the store completes; (2) the wave drains its stores; (3) lane i bumps the arrival counter of
@@ -560,42 +508,8 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(OFF32 
     }
     const uint32_t chunk = bid * WPB + wib;
     if (chunk >= p.n_chunks) return;
-#ifdef FLEX_ABL_EMPTY  // timing-only ablation: dispatch + one header load per wave, nothing else
-    if (p.chunk[chunk].y != 0xFFFFFFFFu) return;
-#endif
     const int c0 = tile * (4 * G) + (lane % G) * 4;  // first of this lane's 4 columns
     const bool col_ok = c0 < p.k;                            // k % 4 == 0 on this path
-#ifdef FLEX_TRACE  // diagnostic build only (tools/trace.py)
-    const uint64_t trace_t0 = __builtin_amdgcn_s_memrealtime();
-    uint64_t phase[5] = {0, 0, 0, 0, 0};
-    uint64_t last_ = trace_t0;
-    const uint4 hdr = p.chunk[chunk];
-    const uint32_t my_beg = (static_cast<uint32_t>(lane) <= hdr.y) ? p.t_beg[hdr.x + lane] : 0u;
-    const uint32_t my_dst = (static_cast<uint32_t>(lane) < hdr.y) ? p.t_dst[hdr.x + lane] : 0u;
-    const uint2 my_aux = (static_cast<uint32_t>(lane) < hdr.y) ? p.t_aux[hdr.x + lane] : make_uint2(0u, 0u);
-    uint32_t my_bd0 = kBundleNoRow, my_bd1 = kBundleNoRow;
-    if constexpr (kTileHasBundles<G>) {
-        if (p.bd_rows != nullptr) {
-            const uint2 cb = p.chunk_bd[chunk];
-            if (static_cast<uint32_t>(lane) < cb.y) my_bd0 = p.bd_rows[cb.x + lane];
-            if (static_cast<uint32_t>(lane) + 64u < cb.y) my_bd1 = p.bd_rows[cb.x + 64u + lane];
-        }
-    }
-    compute_chunk<G, OFF32, U>(p, hdr, my_beg, my_dst, my_aux, my_bd0, my_bd1, lds_rec[wib], reinterpret_cast<const char *>(B), C, lane, c0, col_ok, tile, ktiles, phase, last_);
-    if (lane == 0 && p.trace != nullptr) {
-        uint64_t *log = p.trace + static_cast<uint64_t>(chunk) * 12;
-        log[0] = xcc_id();
-        log[1] = trace_t0;
-        log[2] = __builtin_amdgcn_s_memrealtime();
-        log[3] = p.chunk[chunk].w - p.chunk[chunk].z;
-        log[4] = 1;
-        log[5] = blockIdx.x % kXcds;
-        for (int i = 0; i < 5; ++i) log[6 + i] = phase[i];
-        uint32_t hw_id;  // wave / SIMD / CU / SH / SE the wave ran on (≙ the reference's per-SM timing, flex.cu:27-79)
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_id));
-        log[11] = hw_id;
-    }
-#else
     // A chunk holds at most 63 tasks (planner invariant): all descriptors come with one coalesced
     // load per array and are handed out with v_readlane; the header carries the record range, so
     // the record fetch does not wait for them: header -> {descriptors, records} -> gathers.
@@ -628,7 +542,6 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(OFF32 
             log[2] = (static_cast<uint64_t>(xcc_id()) << 32) | hw_id;
         }
     }
-#endif
 }
 
 // Any k (k % 4 != 0 or unaligned B/C): one wave per task, lane owns columns

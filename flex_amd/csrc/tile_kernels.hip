@@ -25,16 +25,14 @@ namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-#ifndef FLEX_TILE_WAVES
-#define FLEX_TILE_WAVES 3  // waves per SIMD the register allocator aims for (two whole tiles of operands are live in the loop)
-#endif
+constexpr int kTileWaves = 3;  // waves per SIMD the register allocator aims for (two whole tiles of operands are live in the loop)
 constexpr int kTileNT = 2;  // 32-column output tiles per wave: 64 columns of C per wave, grid.y = ceil(k / 64)
 
 // One wave = one row tile x 64 columns of C.  The loop is software-pipelined by hand, a whole tile deep: the 32 B values per lane
 // and the A block of the NEXT tile, and the column offsets of the tile after it, are in flight while the MFMAs of the current tile
 // issue (the matrix cores need 21 us for the 12 500-tile probe, the fabric 69 us for its 415 MB).
 template <bool OFF32>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FLEX_TILE_WAVES))) void spmm_tile_kernel(TileView tv, const float *__restrict__ B, float *__restrict__ C, int k,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kTileWaves))) void spmm_tile_kernel(TileView tv, const float *__restrict__ B, float *__restrict__ C, int k,
                                                         int ldb, int ldc) {
     constexpr int NT = kTileNT;
     const int lane = threadIdx.x & 63;

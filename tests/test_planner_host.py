@@ -231,6 +231,27 @@ def test_descriptor_without_the_range_flag_refuses_a_range(sim):
     L.flex_plan_destroy(h)
 
 
+def test_retired_block_ablate_keeps_its_place_and_must_be_zero(sim):
+    """flex_plan_tuning.block_ablate (timing-only, wrong results by design) is retired inside ABI 3: the field keeps its offset as
+    block_ablate_retired, a nonzero value is refused like `reserved`, and the binding no longer offers it as a knob."""
+    assert C.sizeof(binding._PlanTuning) == 160 and binding._PlanTuning.block_ablate_retired.offset == 116
+    assert C.sizeof(binding._PlanDesc) == 80
+    assert "block_ablate" not in binding.TUNING_FIELDS and "block_ablate_retired" not in binding.TUNING_FIELDS
+    a = random_csr(300, 300, 6, seed=3)
+    v = a.view()
+    L = binding.lib()
+    for retired, want in ((0, 0), (1, -1)):  # FLEX_OK, FLEX_ERR_INVALID
+        t = binding._PlanTuning()
+        t.block_ablate_retired = retired
+        d = binding._PlanDesc(C.sizeof(binding._PlanDesc), C.pointer(v), 32, 0, 0, 0, 0, 0, 0, None, None, C.pointer(t))
+        h = C.c_void_p()
+        assert L.flex_plan_create_ex(C.byref(h), C.byref(d)) == want, retired
+        if want == 0:
+            L.flex_plan_destroy(h)
+    with pytest.raises(flex_amd.FlexError, match="unknown tuning knob"):
+        flex_amd.Plan(a, 32, tuning={"block_ablate": 3})
+
+
 def test_far_first_reorders_records_inside_tasks(sim):
     """tuning.far_first only permutes the records of each task: same tasks, chunks and record count, a different image, still a partition."""
     g = flex_amd.synth_graph(n=12000, nnz=12000 + 2 * 240000, community=300, p_in=0.6, p_near=0.25, seed=12)
