@@ -1,7 +1,9 @@
 """torch autograd over the engine: the gradient of C = A B with respect to B is A^T grad_C (a plan made with FLEX_PLAN_TRANSPOSE),
 and the GCN layer Out = A X W (flex_amd.axw.Axw.layer) differentiates through flex_axw_backward.  With learn_values=True, SparseOperator
 is differentiable in A's values as well: grad_v = SDDMM(grad_C, B) over A's pattern (flex_sddmm), and the values of every forward are
-set into the plans (flex_plan_set_values) without planning again.  torch is imported lazily, as in binding.py."""
+set into the plans (flex_plan_set_values) without planning again.  The same two plans run a graph-attention layer end to end:
+scores by flex_sddmm as a forward op, their softmax over each row of A (flex_edge_softmax), and the SpMM with the result as A's values
+(SparseOperator.attention).  torch is imported lazily, as in binding.py."""
 from __future__ import annotations
 
 from . import binding
@@ -62,14 +64,54 @@ def _function():
                 gv = op.plan.sddmm(grad_C, B)
             return gB, gv, None
 
-    return _SpMM, _AxwLayer, _SpMMValues
+    class _Sddmm(torch.autograd.Function):
+        """s[e] = <Q[row(e)], K[col(e)]> over A's pattern.  Backward, with g = grad_s as A's values: grad_Q = A(g) K on the forward plan,
+        grad_K = A(g)^T Q on the transposed plan, each set to g immediately before it runs (the plans are shared with the other Functions)."""
+
+        @staticmethod
+        def forward(ctx, Q, K, op):
+            Q, K = Q.contiguous(), K.contiguous()
+            ctx.op = op
+            ctx.save_for_backward(Q, K)
+            return op.plan.sddmm(Q, K)
+
+        @staticmethod
+        def backward(ctx, grad_s):
+            Q, K = ctx.saved_tensors
+            op = ctx.op
+            g = grad_s.contiguous()
+            gQ = gK = None
+            if ctx.needs_input_grad[0]:
+                op.plan.set_values(g)
+                gQ = op.plan(K)
+            if ctx.needs_input_grad[1]:
+                op.plan_t.set_values(g)
+                gK = op.plan_t(Q)
+            return gQ, gK, None
+
+    class _EdgeSoftmax(torch.autograd.Function):
+        """p = softmax of scale * s over each row of A; keeps p.  Backward: grad_s = scale p (grad_p - sum over the row of p grad_p)."""
+
+        @staticmethod
+        def forward(ctx, s, op, scale):
+            p = op.plan.edge_softmax(s.contiguous(), scale)
+            ctx.op, ctx.scale = op, scale
+            ctx.save_for_backward(p)
+            return p
+
+        @staticmethod
+        def backward(ctx, grad_p):
+            (p,) = ctx.saved_tensors
+            return ctx.op.plan.edge_softmax_backward(p, grad_p.contiguous(), ctx.scale), None, None
+
+    return _SpMM, _AxwLayer, _SpMMValues, _Sddmm, _EdgeSoftmax
 
 
 _cache = None
 
 
 def functions():
-    """(_SpMM, _AxwLayer, _SpMMValues): the autograd Functions, built at first use (torch is imported then)."""
+    """(_SpMM, _AxwLayer, _SpMMValues, _Sddmm, _EdgeSoftmax): the autograd Functions, built at first use (torch is imported then)."""
     global _cache
     if _cache is None:
         _cache = _function()
@@ -81,7 +123,9 @@ class SparseOperator:
     `a` is an m x n HostCsr; op(B) takes B [n, k] and returns C [m, k], float32 cuda tensors.
     learn_values=True: both plans are made with FLEX_PLAN_MUTABLE_VALUES and op(B, values=v) -- v a float32 cuda tensor of a.nnz values
     in a's CSR order -- computes A(v) B, differentiable in B and in v (grad_v = SDDMM(grad_C, B) over A's pattern).  op(B) alone then
-    uses a's own values."""
+    uses a's own values.  With learn_values the operator also offers the pieces of graph attention over A's pattern, each differentiable:
+    op.sddmm(Q, K) (scores per entry, Q [m, k], K [n, k]), op.edge_softmax(s, scale) (softmax over each row of A) and
+    op.attention(Q, K, V, scale) = op(V, values=op.edge_softmax(op.sddmm(Q, K), scale))."""
 
     def __init__(self, a: binding.HostCsr, k: int, device: int = 0, order: int = binding.FLEX_ORDER_NATURAL, tuning: dict | None = None,
                  learn_values: bool = False):
@@ -112,3 +156,26 @@ class SparseOperator:
         assert values.numel() == self.nnz, (values.numel(), self.nnz)
         return functions()[2].apply(B, values, self)
 
+
+    def _needs_learn_values(self, what):
+        if not self.learn_values:
+            raise NotImplementedError(f"{what} needs SparseOperator(..., learn_values=True)")
+
+    def sddmm(self, Q, K):
+        """s [nnz] in a's CSR order: s[e] = <Q[row(e)], K[col(e)]>.  Differentiable in Q [m, k] and K [n, k]."""
+        self._needs_learn_values("sddmm")
+        return functions()[3].apply(Q, K, self)
+
+    def edge_softmax(self, s, scale: float = 1.0):
+        """The softmax of scale * s over each row of A (-inf = a masked edge).  Differentiable in s."""
+        self._needs_learn_values("edge_softmax")
+        assert s.numel() == self.nnz, (s.numel(), self.nnz)
+        return functions()[4].apply(s, self, float(scale))
+
+    def attention(self, Q, K, V, scale: float | None = None):
+        """Out [m, k] = A(alpha) V with alpha = softmax over each row of A of scale * <Q[row], K[col]>; scale defaults to k ** -0.5.
+        Differentiable in Q [m, k], K [n, k] and V [n, k]."""
+        self._needs_learn_values("attention")
+        if scale is None:
+            scale = self.k ** -0.5
+        return self(V, values=self.edge_softmax(self.sddmm(Q, K), scale))

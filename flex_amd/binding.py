@@ -125,6 +125,11 @@ class _Imbalance(C.Structure):  # flex_imbalance
                 ("xcd_end_spread_pct", C.c_double), ("wave_us_mean", C.c_double), ("wave_us_max", C.c_double)]
 
 
+class _SoftmaxInfo(C.Structure):  # flex_softmax_info
+    _fields_ = [(f, C.c_int64) for f in ("rows", "entries", "items", "groups", "rows_empty", "rows_packed", "rows_wave", "rows_block",
+                                          "group_entries", "device_bytes")]
+
+
 class _SynthParams(C.Structure):  # flex_synth_params
     _fields_ = [("n", C.c_int64), ("nnz", C.c_int64), ("alpha", C.c_double),
                 ("community", C.c_int64), ("p_in", C.c_double), ("p_near", C.c_double),
@@ -140,6 +145,7 @@ SYMBOLS = [
     "flex_host_csr_free", "flex_fill_dense_rand", "flex_order_rcm", "flex_order_cluster", "flex_order_gorder", "flex_perm_csr",
     "flex_order_deg", "flex_order_dfs", "flex_order_rabbit", "flex_shard_rows", "flex_synth_graph", "flex_synth_preset", "flex_strerror", "flex_last_hip_error",
     "flex_last_hip_error_string", "flex_abi_version", "flex_plan_set_values", "flex_sddmm",
+    "flex_edge_softmax", "flex_edge_softmax_backward", "flex_plan_softmax_info",
 ]
 
 _lib = None
@@ -217,18 +223,21 @@ def lib():
         L.flex_last_hip_error.restype = i32
         L.flex_last_hip_error_string.restype = C.c_char_p
         L.flex_abi_version.restype = i32
+        L.flex_plan_softmax_info.argtypes = [vp, C.POINTER(_SoftmaxInfo)]
         _lib = L
     return _lib
 
 
 def _values_fn(name: str):
-    """flex_plan_set_values / flex_sddmm, looked up at first use and not when the library loads: the host-only builds the CPU suite
-    runs against (tests/hostsim, tools/asan_host.sh) have no kernels and so do not define them."""
+    """flex_plan_set_values / flex_sddmm / flex_edge_softmax / flex_edge_softmax_backward, looked up at first use and not when the
+    library loads: the host-only builds the CPU suite runs against (tests/hostsim, tools/asan_host.sh) have no kernels and so do not
+    define them."""
     L = lib()
     f = getattr(L, name)
     if f.argtypes is None:
-        vp = C.c_void_p
-        f.argtypes = [vp, vp, vp] if name == "flex_plan_set_values" else [vp, vp, vp, vp, vp]
+        vp, fl = C.c_void_p, C.c_float
+        f.argtypes = {"flex_plan_set_values": [vp, vp, vp], "flex_sddmm": [vp, vp, vp, vp, vp], "flex_edge_softmax": [vp, vp, fl, vp, vp],
+                      "flex_edge_softmax_backward": [vp, vp, vp, fl, vp, vp]}[name]
     return f
 
 
@@ -547,6 +556,43 @@ class Plan:
             out = torch.zeros(self.src_nnz, dtype=torch.float32, device=G.device)
         assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == self.src_nnz
         self.sddmm_ptr(G.data_ptr(), B.data_ptr(), out.data_ptr(), torch.cuda.current_stream(G.device).cuda_stream)
+        return out
+
+    def softmax_info(self) -> dict:
+        """flex_plan_softmax_info: the schedule of edge_softmax on this plan (rows, entries, items, groups, rows by class)."""
+        i = _SoftmaxInfo()
+        _check(lib().flex_plan_softmax_info(self._h, C.byref(i)), "flex_plan_softmax_info")
+        return {f: getattr(i, f) for f, _ in _SoftmaxInfo._fields_}
+
+    def edge_softmax_ptr(self, dScores_ptr: int, scale: float, dOut_ptr: int, stream: int = 0):
+        _check(_values_fn("flex_edge_softmax")(self._h, dScores_ptr, scale, dOut_ptr, stream), "flex_edge_softmax")
+
+    def edge_softmax_backward_ptr(self, dP_ptr: int, dGradP_ptr: int, scale: float, dGradS_ptr: int, stream: int = 0):
+        _check(_values_fn("flex_edge_softmax_backward")(self._h, dP_ptr, dGradP_ptr, scale, dGradS_ptr, stream), "flex_edge_softmax_backward")
+
+    def _edge_vectors(self, *ts):
+        import torch
+        for t in ts:
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == self.src_nnz, "float32 cuda [nnz]"
+
+    def edge_softmax(self, s, scale: float = 1.0, out=None):
+        """flex_edge_softmax: the softmax of scale * s over each row of `a`; s and the result are float32 cuda tensors [a.nnz] in a's CSR
+        order (out=s: in place).  -inf scores are masked edges (p = +0).  Entries the plan does not hold (other shards) keep what `out`
+        held; a new `out` starts at zero."""
+        import torch
+        if out is None:
+            out = torch.zeros_like(s)
+        self._edge_vectors(s, out)
+        self.edge_softmax_ptr(s.data_ptr(), scale, out.data_ptr(), torch.cuda.current_stream(s.device).cuda_stream)
+        return out
+
+    def edge_softmax_backward(self, p, gp, scale: float = 1.0, out=None):
+        """flex_edge_softmax_backward: scale * p * (gp - sum over the row of p * gp), p the forward's output (out=gp: in place)."""
+        import torch
+        if out is None:
+            out = torch.zeros_like(gp)
+        self._edge_vectors(p, gp, out)
+        self.edge_softmax_backward_ptr(p.data_ptr(), gp.data_ptr(), scale, out.data_ptr(), torch.cuda.current_stream(p.device).cuda_stream)
         return out
 
     def destroy(self):

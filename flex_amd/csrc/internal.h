@@ -186,6 +186,40 @@ inline int sddmm_lanes(int k) {
     return w;
 }
 
+// FLEX_PLAN_MUTABLE_VALUES: the walk of flex_edge_softmax / flex_edge_softmax_backward (softmax_kernels.hip; plan_build.cpp,
+// upload_softmax_image).  It is made from hostA's row pointer alone.  A wave looks at its entries through WINDOWS of kSmWindow
+// consecutive entries that start at a multiple of 4 (a lane owns 4 consecutive entries: one 16-byte load where the arrays are aligned).
+//   packed item   consecutive whole rows that fit ONE window together: (first entry % 4) + entries <= kSmWindow, at most kSmItemRows rows
+//                 (empty ones count); the wave reduces them side by side under row-boundary flags
+//   wave row      a row that does not fit a window but fits kSmChunk entries counted the same way: one wave, 4 windows held in registers
+//   block row     a longer row: a workgroup of its own, wave w takes chunks w, w + 4, ...; up to 4 kSmChunk entries stay in registers,
+//                 a longer row is read a second time for the write (from the L2 where it fits)
+// Items are {first entry, entries, first row (index into the plan's row pointer), rows}.  Packed items and wave rows are packed, in row
+// order, into one group per wave: a group of more than one item holds at most the plan's group budget of entries.
+constexpr uint32_t kSmWindow = 256;
+constexpr uint32_t kSmItemRows = 256;
+constexpr uint32_t kSmChunk = 4 * kSmWindow;      // what a lane keeps in registers: 4 x 4 entries.  Also the block-row threshold
+constexpr uint32_t kSmGroupMin = kSmWindow;       // group budget (entries): total / kSmTargetGroups rounded up to a window, within these
+constexpr uint32_t kSmGroupMax = 8 * kSmWindow;
+constexpr uint32_t kSmTargetGroups = 4096;        // 16 waves on each of the 256 CUs before a wave takes a second item
+enum SmClass : int { kSmPacked = 0, kSmWaveRow = 1, kSmBlockRow = 2 };
+// the class of a nonempty row of `len` entries whose first entry is `first`
+inline int softmax_row_class(uint32_t first, uint32_t len) {
+    const uint64_t span = static_cast<uint64_t>(first % 4u) + len;
+    return span <= kSmWindow ? kSmPacked : span <= kSmChunk ? kSmWaveRow : kSmBlockRow;
+}
+inline uint32_t softmax_group_budget(uint64_t entries) {
+    const uint64_t b = (entries / kSmTargetGroups + kSmWindow - 1) / kSmWindow * kSmWindow;
+    return static_cast<uint32_t>(b < kSmGroupMin ? kSmGroupMin : b > kSmGroupMax ? kSmGroupMax : b);
+}
+// a term of the order-free fingerprint of a row pointer slice (flex_plan_self_check)
+inline uint64_t rowptr_fp(uint32_t local_row, uint32_t first_entry) {
+    uint64_t z = ((static_cast<uint64_t>(local_row) << 32) | first_entry) + 0x9E3779B97F4A7C15ull;  // splitmix64
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
 // per-thread record of the last HIP failure (flex_last_hip_error)
 void note_hip_error(hipError_t e);
 

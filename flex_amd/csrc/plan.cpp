@@ -271,6 +271,10 @@ static int create_common(flex_plan **out, const flex_csr *hostA, bool all_rows, 
         if (rc == FLEX_OK && mut) {
             p->src_nnz = callerA->nnz;
             p->ent_fp = held_entries_fp(callerA, transposed, row_begin, row_end, col_map);
+            // the edge softmax runs over hostA's rows: all of them under a transposed plan of every row, none under a transposed shard
+            // (it holds pieces of hostA's rows)
+            if (!transposed) rc = upload_softmax_image(p.get(), callerA->rowPtr, row_begin, row_end);
+            else if (all_rows) rc = upload_softmax_image(p.get(), callerA->rowPtr, 0, callerA->m);
         }
     } catch (const std::bad_alloc &) {  // nothing crosses the C ABI as an exception
         rc = FLEX_ERR_NOMEM;
@@ -399,6 +403,14 @@ int flex_plan_get_info(const flex_plan *p, flex_plan_info *o) {
     o->block_records = static_cast<int64_t>(p->d_bk_rec.size());
     o->n_bundles = p->n_bundles;
     o->bundle_rows = p->bundle_rows;
+    return FLEX_OK;
+}
+
+int flex_plan_softmax_info(const flex_plan *p, flex_softmax_info *o) {
+    if (!p || !o || !p->mutable_vals) return FLEX_ERR_INVALID;
+    if (!p->sm_ok) return FLEX_ERR_UNSUPPORTED;
+    *o = flex_softmax_info{p->sm_rows, p->sm_entries, static_cast<int64_t>(p->d_sm_item.size()), p->n_sm_groups, p->sm_class_rows[3],
+                           p->sm_class_rows[kSmPacked], p->sm_class_rows[kSmWaveRow], p->sm_class_rows[kSmBlockRow], p->sm_group_budget, p->sm_bytes};
     return FLEX_OK;
 }
 

@@ -141,6 +141,15 @@ struct flex_plan {
     uint32_t n_sd_groups = 0;
     int64_t src_nnz = 0;          // nnz of hostA: entry ids are below it
     uint64_t ent_fp = 0;          // order-free fingerprint of the (entry, B row) pairs the plan holds, taken from hostA (self-check)
+    // the edge softmax's walk (internal.h, kSmWindow; softmax_kernels.hip).  Empty on a transposed plan with a row range (sm_ok false)
+    bool sm_ok = false;
+    flex::DeviceArray<uint32_t> d_sm_rowptr;  // [sm_rows + 1] hostA's row pointer for the rows whose softmax the plan computes
+    flex::DeviceArray<uint4> d_sm_item;       // wave items (packed items and wave rows, grouped), then the block rows
+    flex::DeviceArray<uint32_t> d_sm_grp;     // [n_sm_groups + 1] first item of each wave's group
+    uint32_t n_sm_groups = 0, n_sm_wave_items = 0, n_sm_block_rows = 0, sm_group_budget = 0;
+    int64_t sm_rows = 0, sm_entries = 0, sm_bytes = 0;
+    int64_t sm_class_rows[4] = {0, 0, 0, 0};  // rows that are packed / wave rows / block rows / empty
+    uint64_t sm_fp = 0;                       // fingerprint of the row pointer slice, taken from hostA (self-check)
 };
 
 namespace flex {
@@ -194,6 +203,9 @@ inline bool operands_vec4(const flex_plan *p, const float *dB, const float *dC) 
 int build_plan(flex_plan *p, const flex_csr *A, int32_t r0, int32_t r1, const int32_t *col_map, const int32_t *dst_map,
                unsigned flags, const flex_plan_tuning &tuning, std::vector<uint32_t> *sched_cache = nullptr, int force_G = 0,
                const uint32_t *entry_of = nullptr);
+
+// FLEX_PLAN_MUTABLE_VALUES: builds and uploads the edge softmax's walk over rows [r0, r1) of the row pointer `rowPtr` (hostA's)
+int upload_softmax_image(flex_plan *p, const uint32_t *rowPtr, int64_t r0, int64_t r1);
 
 // FLEX_PLAN_MUTABLE_VALUES: a term of the order-free fingerprint of the (entry, B row) pairs a plan holds (flex_plan_self_check)
 inline uint64_t entry_fp(uint32_t entry, uint32_t brow) {

@@ -1113,4 +1113,73 @@ int build_plan(flex_plan *p, const flex_csr *A, int32_t r0, int32_t r1, const in
     return FLEX_ERR_NOMEM;
 }
 
+// The edge softmax's walk (internal.h, kSmWindow): one pass over the row pointer in row order, so the image depends on nothing but
+// the row pointer slice -- the plan of A and the transposed plan of the same hostA upload the same bytes.
+int upload_softmax_image(flex_plan *p, const uint32_t *rowPtr, int64_t r0, int64_t r1) try {
+    const size_t rows = static_cast<size_t>(r1 - r0);
+    std::vector<uint32_t> rp(rowPtr + r0, rowPtr + r1 + 1), grp;
+    std::vector<uint4> item, block;
+    const uint64_t entries = rp.back() - rp.front();
+    const uint32_t budget = softmax_group_budget(entries);
+    uint32_t g_entries = 0;
+    auto add_item = [&](uint32_t first, uint32_t cnt, uint32_t row, uint32_t n_rows) {
+        if (grp.empty() || g_entries + cnt > budget) {
+            grp.push_back(static_cast<uint32_t>(item.size()));
+            g_entries = 0;
+        }
+        item.push_back(make_uint4(first, cnt, row, n_rows));
+        g_entries += cnt;
+    };
+    uint64_t fp = 0;
+    int64_t by_class[4] = {0, 0, 0, 0};
+    uint32_t run_row = 0, run_rows = 0, run_first = 0, run_cnt = 0;  // the packed item being filled
+    auto close_run = [&] {
+        if (run_cnt) add_item(run_first, run_cnt, run_row, run_rows);
+        run_rows = run_cnt = 0;
+    };
+    for (size_t r = 0; r < rows; ++r) {
+        const uint32_t first = rp[r], len = rp[r + 1] - rp[r];
+        fp += rowptr_fp(static_cast<uint32_t>(r), first);
+        if (len == 0) {  // inside a run it is one of the run's rows; it never opens one
+            ++by_class[3];
+            if (run_cnt && run_rows < kSmItemRows) ++run_rows;
+            else close_run();
+            continue;
+        }
+        const int cls = softmax_row_class(first, len);
+        ++by_class[cls];
+        if (cls != kSmPacked) {
+            close_run();
+            (cls == kSmWaveRow ? add_item(first, len, static_cast<uint32_t>(r), 1u) : block.push_back(make_uint4(first, len, static_cast<uint32_t>(r), 1u)));
+            continue;
+        }
+        if (run_cnt && (run_first % 4u + run_cnt + len > kSmWindow || run_rows == kSmItemRows)) close_run();
+        if (run_cnt == 0) run_row = static_cast<uint32_t>(r), run_first = first;
+        run_cnt += len;
+        ++run_rows;
+    }
+    close_run();
+    fp += rowptr_fp(static_cast<uint32_t>(rows), rp.back());
+    grp.push_back(static_cast<uint32_t>(item.size()));
+    p->n_sm_groups = static_cast<uint32_t>(grp.size() - 1);
+    p->n_sm_wave_items = static_cast<uint32_t>(item.size());
+    p->n_sm_block_rows = static_cast<uint32_t>(block.size());
+    item.insert(item.end(), block.begin(), block.end());
+    p->sm_group_budget = budget;
+    p->sm_rows = static_cast<int64_t>(rows);
+    p->sm_entries = static_cast<int64_t>(entries);
+    p->sm_fp = fp;
+    for (int c = 0; c < 4; ++c) p->sm_class_rows[c] = by_class[c];
+    const int64_t before = p->device_bytes;
+    int rc;
+    if ((rc = p->d_sm_rowptr.upload(rp, &p->device_bytes))) return rc;
+    if ((rc = p->d_sm_item.upload(item, &p->device_bytes))) return rc;
+    if ((rc = p->d_sm_grp.upload(grp, &p->device_bytes))) return rc;
+    p->sm_bytes = p->device_bytes - before;
+    p->sm_ok = true;
+    return FLEX_OK;
+} catch (const std::bad_alloc &) {
+    return FLEX_ERR_NOMEM;
+}
+
 }  // namespace flex

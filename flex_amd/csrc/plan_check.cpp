@@ -208,6 +208,63 @@ static int check_value_image(const flex_plan *p, const std::vector<uint2> &rec, 
     return FLEX_OK;
 }
 
+// FLEX_PLAN_MUTABLE_VALUES: the edge softmax's walk read back (internal.h, kSmWindow).  The row pointer slice is monotone, spans the
+// plan's entries and has the fingerprint create_common's builder took from hostA; every entry of the plan's rows lies in exactly one
+// item; an item holds whole consecutive rows -- a packed item rows that fit one window together, a wave row or a block row exactly its
+// one row, which it tiles from its first entry to its last -- and every row is of the class its item treats it as; every nonempty row
+// lies in exactly one item; the groups tile the wave items in order, and a group of more than one item stays within the budget.
+static int check_softmax_image(const flex_plan *p) {
+    std::vector<uint32_t> rp, grp;
+    std::vector<uint4> item;
+    if (!read_back(p->d_sm_rowptr, rp) || !read_back(p->d_sm_item, item) || !read_back(p->d_sm_grp, grp)) return FLEX_ERR_HIP;
+    const size_t rows = static_cast<size_t>(p->sm_rows);
+    if (rp.size() != rows + 1 || grp.size() != p->n_sm_groups + size_t(1) || item.size() != size_t(p->n_sm_wave_items) + p->n_sm_block_rows) return FLEX_ERR_FORMAT;
+    uint64_t fp = 0;
+    for (size_t r = 0; r <= rows; ++r) {
+        if (r < rows && rp[r] > rp[r + 1]) return FLEX_ERR_FORMAT;
+        fp += rowptr_fp(static_cast<uint32_t>(r), rp[r]);
+    }
+    if (fp != p->sm_fp || static_cast<int64_t>(rp.back() - rp.front()) != p->sm_entries || p->sm_entries != p->nnz || rp.back() > static_cast<uint64_t>(p->src_nnz)) return FLEX_ERR_FORMAT;
+    if (p->sm_group_budget != softmax_group_budget(static_cast<uint64_t>(p->sm_entries))) return FLEX_ERR_FORMAT;
+    std::vector<uint8_t> row_seen(rows, 0);
+    int64_t covered = 0, by_class[4] = {0, 0, 0, 0};
+    for (size_t i = 0; i < item.size(); ++i) {
+        const uint4 &it = item[i];
+        const bool is_block = i >= p->n_sm_wave_items;
+        if (it.y == 0 || it.w == 0 || static_cast<uint64_t>(it.z) + it.w > rows) return FLEX_ERR_FORMAT;
+        if (rp[it.z] != it.x || static_cast<uint64_t>(it.x) + it.y != rp[it.z + it.w]) return FLEX_ERR_FORMAT;  // whole consecutive rows, first to last entry
+        const bool packed = !is_block && static_cast<uint64_t>(it.x % 4u) + it.y <= kSmWindow;
+        if (packed ? it.w > kSmItemRows : it.w != 1) return FLEX_ERR_FORMAT;
+        for (uint32_t r = it.z; r < it.z + it.w; ++r) {
+            if (row_seen[r]++) return FLEX_ERR_FORMAT;
+            const uint32_t len = rp[r + 1] - rp[r];
+            if (len == 0) continue;
+            const int cls = softmax_row_class(rp[r], len);
+            if (cls != (packed ? kSmPacked : is_block ? kSmBlockRow : kSmWaveRow)) return FLEX_ERR_FORMAT;
+            ++by_class[cls];
+        }
+        covered += it.y;
+    }
+    if (covered != p->sm_entries) return FLEX_ERR_FORMAT;
+    for (size_t r = 0; r < rows; ++r) {
+        if (rp[r + 1] == rp[r]) ++by_class[3];
+        else if (row_seen[r] != 1) return FLEX_ERR_FORMAT;
+    }
+    for (int c = 0; c < 4; ++c)
+        if (by_class[c] != p->sm_class_rows[c]) return FLEX_ERR_FORMAT;
+    // items in row order, so that the groups are runs of rows
+    for (size_t i = 1; i < item.size(); ++i)
+        if (i != p->n_sm_wave_items && item[i].z < item[i - 1].z + item[i - 1].w) return FLEX_ERR_FORMAT;
+    if (grp.front() != 0 || grp.back() != p->n_sm_wave_items) return FLEX_ERR_FORMAT;
+    for (uint32_t g = 0; g < p->n_sm_groups; ++g) {
+        if (grp[g] >= grp[g + 1]) return FLEX_ERR_FORMAT;
+        uint64_t e = 0;
+        for (uint32_t i = grp[g]; i < grp[g + 1]; ++i) e += item[i].y;
+        if (grp[g + 1] - grp[g] > 1 && e > p->sm_group_budget) return FLEX_ERR_FORMAT;
+    }
+    return FLEX_OK;
+}
+
 // ≙ the reference's tiler round-trip (mat.cu:905-940: every entry of the pillar format exists exactly once,
 // the queues are contiguous): read the plan's DEVICE image back and check that it is a partition --
 // chunks tile the tasks, tasks tile the records, every record names a valid B row, every C row is written by
@@ -443,7 +500,8 @@ int flex_plan_self_check(const flex_plan *p) try {
         for (uint8_t w : written)
             if (w != 1) return FLEX_ERR_FORMAT;
     if (p->mutable_vals) {
-        const int rc = check_value_image(p, rec, row_bytes);
+        int rc = check_value_image(p, rec, row_bytes);
+        if (rc == FLEX_OK && p->sm_ok) rc = check_softmax_image(p);
         if (rc) return rc;
     }
     return FLEX_OK;

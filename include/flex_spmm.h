@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FLEX_ABI_VERSION 3 /* 3 also covers the purely additive FLEX_PLAN_MUTABLE_VALUES, flex_plan_set_values and flex_sddmm (no struct grew),
+#define FLEX_ABI_VERSION 3 /* 3 also covers the purely additive FLEX_PLAN_MUTABLE_VALUES, flex_plan_set_values, flex_sddmm and the edge softmax (no struct grew),
                               and the retired flex_plan_tuning.block_ablate, which keeps its place as block_ablate_retired and must be zero.
                               3: plan-time knobs leave the environment for the struct flex_plan_tuning, flex_plan_desc.tuning, flex_plan_get_tuning,
                               flex_order_cluster_ex, flex_set_host_threads; split rows are summed by a second launch by default.
@@ -96,7 +96,8 @@ typedef struct flex_plan flex_plan;
                                        8 bytes per record (the record -> entry map and the plan's copy of the values; records = nnz + padding,
                                        flex_plan_info.n_records), 16 bytes per padded run and per SDDMM work item (a run of at most 64 nonzeros
                                        of one row), 4 per group of items -- measured 8.6 bytes per nonzero on the reddit shape, 11-13 on graphs of short
-                                       rows (more padding per nonzero), all counted in flex_plan_info.device_bytes.  Without the flag a plan is byte for byte what it was before the flag existed */
+                                       rows (more padding per nonzero), all counted in flex_plan_info.device_bytes; and the edge softmax's schedule
+                                       (flex_softmax_info below): 4 bytes per row of hostA, 16 per work item, 4 per wave group.  Without the flag a plan is byte for byte what it was before the flag existed */
 
 /* ≙ Mat::Mat + csr2_DiagTiling + alpha_transfer (mat.cu:7-31, 680-942, 268-293):
  * builds the row-panel plan for `hostA` and uploads it to `device`.  The reference's
@@ -262,6 +263,61 @@ int flex_plan_set_values(flex_plan *plan, const float *dVals, flex_stream_t stre
  * as D64, while no fp32 partial sum overflows (T over the finite terms < 2^120).  Columns past k (padding lanes, the ld - k tail of
  * a strided row) contribute nothing: they are never read, so no 0 x inf can turn an inf into NaN. */
 int flex_sddmm(const flex_plan *plan, const float *dG, const float *dB, float *dOut, flex_stream_t stream);
+
+/* Edge softmax: the softmax of a score per entry over each ROW of hostA, the step between the SDDMM's scores and the SpMM of graph
+ * attention (Out = A(alpha) V, alpha = softmax over each row of scale x <Q[row], K[col]>).  FLEX_PLAN_MUTABLE_VALUES plans only
+ * (FLEX_ERR_INVALID on any other plan).  No reference counterpart.
+ *
+ * All arrays are device arrays of hostA->nnz floats in the CSR order of the hostA passed to the create call, for every kind of plan, and
+ * the rows are ALWAYS the rows of hostA: a transposed plan takes the same vectors as the plan of A and gives the same bits (the
+ * schedule is made from hostA's row pointer alone).  A shard plan reads and writes the entries of its own rows only and leaves the rest
+ * of the output untouched; a transposed plan with a row range holds pieces of hostA's rows: FLEX_ERR_UNSUPPORTED.
+ *
+ * Forward, row r with entries e:   dOut[e] = exp(scale (s_e - M_r)) / sum_j exp(scale (s_j - M_r)),   M_r = the row's largest score.
+ * The difference is taken before the multiplication by scale.  scale must be finite and > 0 (else FLEX_ERR_INVALID).
+ * Backward, p = dP (the forward's output), g = dGradP:   dGradS[e] = scale p_e (g_e - sum_j p_j g_j).
+ * Special values of the forward:
+ *   - a score of -inf is a masked edge: its p is exactly +0;
+ *   - a row whose scores are ALL -inf gives +0 everywhere (a definition: the row attends to nothing and the SpMM writes a zero row);
+ *   - a row that holds a +inf or a NaN gives NaN in every entry of that row (what exp(s - max) / sum gives in float64);
+ *   - a row without entries: nothing is read, nothing written; nnz == 0: FLEX_OK, no launch.
+ * The backward has no special cases: it is the formula in fp32, so a NaN row of p gives a NaN row, 0 x inf gives NaN.
+ * In place is allowed (dOut == dScores, dGradS == dGradP); any other overlap is the caller's error.  Asynchronous on `stream`, one
+ * launch, no allocation, no host synchronisation (safe to capture in a hipGraph), no atomics, fixed reduction order: bit-identical
+ * run to run.  Arrays that are not 16-byte aligned run the same kernel with 4-byte accesses: same bits, slower.
+ * A row is reduced by one wave (up to 1024 entries) or by one workgroup (longer): a row of millions of entries is correct and slow.
+ *
+ * Accuracy, against float64 on the fp32 inputs; u = 2^-24, gamma(n) = n u / (1 - n u), n_r = entries of the row, D_r = min(104, scale x
+ * the spread of the row's finite scores), E = the error of the device's expf in ulp (measured: DESIGN.md 3.10):
+ *   forward    |p - p64| <= gamma(n_r + 4 D_r + 2 E + 4) p64 + 2^-126
+ *   backward   |gs - gs64| <= gamma(n_r + 4) scale p_e (|g_e| + sum_j |p_j g_j|) + max(1, scale) n_r 2^-149, float64 on the SAME fp32 p.
+ * Forward, derivation.  The exponent a = fl(scale fl(s - M)) carries two roundings, |a - a64| <= 2 u |a64| (1 + u), and |a64| <= D_r for every
+ * term that does not underflow (below -104 a term is < 2^-149 and contributes at most the absolute 2^-126 share), so the term
+ * t = expf(a) has the relative error (1 + E u) exp(2 u D_r (1 + u)) - 1 <= gamma(2 D_r + E + 1).  The terms are positive: the sum L of the
+ * computed terms, added in a tree of depth <= n_r, is within gamma(2 D_r + E + 1 + n_r) of the exact sum (>= 1: the largest term is
+ * exactly 1).  p = fl(t / L) adds one rounding; numerator and denominator together: gamma(n_r + 4 D_r + 2 E + 3), stated with + 4.
+ * Terms or quotients below 2^-126 may be flushed or rounded as subnormals: at most 2^-126 absolute.  Where a row is longer than one
+ * wave's registers the partial sums of its parts are rescaled by exp(scale (m_part - M_r)) <= 1 before they are added, which costs each
+ * part E + 3 more roundings: they are covered, because a tree over 64 lanes x parts has depth <= n_r / 64 + 8 where the bound grants n_r.
+ * Backward: the products p_j g_j (one rounding each), their sum in a tree of depth <= n_r, one subtraction and two products. */
+int flex_edge_softmax(const flex_plan *plan, const float *dScores, float scale, float *dOut, flex_stream_t stream);
+int flex_edge_softmax_backward(const flex_plan *plan, const float *dP, const float *dGradP, float scale, float *dGradS, flex_stream_t stream);
+
+/* The schedule of the two calls above (host side; what the plan uploaded for them is counted in flex_plan_info.device_bytes).
+ * FLEX_ERR_INVALID on a plan without FLEX_PLAN_MUTABLE_VALUES, FLEX_ERR_UNSUPPORTED on a transposed plan with a row range. */
+typedef struct flex_softmax_info {
+    int64_t rows;          /* rows of hostA the plan computes the softmax of */
+    int64_t entries;       /* their entries */
+    int64_t items;         /* work items: packed runs of short rows + wave rows + block rows */
+    int64_t groups;        /* wave groups: one wave each, four to a workgroup (block rows are workgroups of their own) */
+    int64_t rows_empty;    /* rows without entries: in no item, or carried inside a packed item */
+    int64_t rows_packed;   /* rows that share a window of 256 entries with their neighbours */
+    int64_t rows_wave;     /* rows reduced by one wave of their own (up to 1024 entries) */
+    int64_t rows_block;    /* rows reduced by a workgroup of their own */
+    int64_t group_entries; /* the balance promised: a group of more than one item holds at most this many entries */
+    int64_t device_bytes;  /* device memory of the schedule: 4 per row, 16 per item, 4 per group */
+} flex_softmax_info;
+int flex_plan_softmax_info(const flex_plan *plan, flex_softmax_info *out);
 
 /* ≙ alpha_freeMatGPU (mat.cuh:184-193). */
 int flex_plan_destroy(flex_plan *plan);

@@ -1,0 +1,112 @@
+#!/usr/bin/env python3
+"""Sparse graph attention, measured: the error of the exponential the edge softmax may use, and the time of flex_edge_softmax,
+flex_edge_softmax_backward and a whole attention step.  Writes profiles/attention_probe.txt (or the file given with --out).
+
+1. tools/exp_error.hip (built here with hipcc into flex_amd/lib if it is not there): the largest error in ulp of expf, __expf and
+   exp2f on the prescaled argument over every fp32 argument in [-104, 0] against float64 exp.
+2. Per graph (natural order, HIP events on torch's stream, warm-up, best of 3): forward and backward, their bytes per second at
+   8 / 12 bytes per entry as a share of flex_hbm_probe's copy rate in the same run, flex_plan_set_values on the same plan, and the
+   torch composition of the same op (scatter_reduce amax + index_add + two gathers over an int64 row index).
+3. One attention step (forward + backward of SparseOperator.attention, k = 32 and 128) against the same step with the softmax done by
+   that torch composition.
+Usage: probe_attention.py [--out FILE] [graph ...]   (default: pubmed.csv flickr reddit soc-sign-epinions)"""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import flex_amd  # noqa: E402
+from tools.probe_values import best_us, load  # noqa: E402
+
+LINES = []
+
+
+def say(line):
+    print(line, flush=True)
+    LINES.append(line)
+
+
+def exp_error():
+    so = os.path.join(ROOT, "flex_amd", "lib", "libexp_error.so")
+    src = os.path.join(ROOT, "tools", "exp_error.hip")
+    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
+        subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-shared", "-o", so, src])
+    worst = (C.c_double * 3)()
+    rc = C.CDLL(so).exp_error_ulp(worst)
+    assert rc == 0, rc
+    say("largest error in ulp over every fp32 argument in [-104, 0] (1 120 927 745 values) against float64 exp: "
+        f"expf {worst[0]:.3f}  __expf {worst[1]:.3f}  exp2f(x * log2 e) {worst[2]:.3f}")
+
+
+def torch_softmax(s, rows, m, scale):
+    """The composition a user needs without the engine: row maximum, exponentials, row sums, two gathers."""
+    mx = torch.full((m,), float("-inf"), device=s.device).scatter_reduce(0, rows, s, "amax")
+    t = torch.exp(scale * (s - mx[rows]))
+    return t / torch.zeros(m, device=s.device).index_add(0, rows, t)[rows]
+
+
+def torch_softmax_backward(p, g, rows, m, scale):
+    return scale * p * (g - torch.zeros(m, device=p.device).index_add(0, rows, p * g)[rows])
+
+
+def probe(name, a, copy_gbps):
+    p = flex_amd.Plan(a, 32, mutable_values=True)
+    i = p.softmax_info()
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    s = torch.rand(a.nnz, device="cuda", generator=gen) * 8 - 4
+    g = torch.rand(a.nnz, device="cuda", generator=gen) * 2 - 1
+    out, gs = torch.empty_like(s), torch.empty_like(s)
+    st = torch.cuda.current_stream().cuda_stream
+    n = max(5, min(200, int(1e9 / max(1, a.nnz))))
+    t_f = best_us(lambda: p.edge_softmax_ptr(s.data_ptr(), 0.125, out.data_ptr(), st), n)
+    t_b = best_us(lambda: p.edge_softmax_backward_ptr(out.data_ptr(), g.data_ptr(), 0.125, gs.data_ptr(), st), n)
+    t_set = best_us(lambda: p.set_values(out), n)
+    rows = torch.repeat_interleave(torch.arange(a.m, device="cuda"), torch.from_numpy(a.rowPtr.astype("int64")).diff().cuda())
+    t_tf = best_us(lambda: torch_softmax(s, rows, a.m, 0.125), max(3, n // 4))
+    t_tb = best_us(lambda: torch_softmax_backward(out, g, rows, a.m, 0.125), max(3, n // 4))
+    diff = (torch_softmax(s, rows, a.m, 0.125) - out).abs().max().item()
+    rec = p.info()["n_records"]
+    share = lambda b, t: f"{b / t / 1e3:.0f} GB/s, {100 * b / t / 1e3 / copy_gbps:.0f} % of copy"  # noqa: E731
+    say(f"{name} m={a.m} nnz={a.nnz} (rows packed {i['rows_packed']} wave {i['rows_wave']} block {i['rows_block']}, {i['items']} items, {i['groups']} groups of <= {i['group_entries']}, "
+        f"{i['device_bytes'] / max(1, a.nnz):.2f} B/nnz): forward {t_f:.1f} us ({share(8 * a.nnz, t_f)})  backward {t_b:.1f} us ({share(12 * a.nnz, t_b)})"
+        f"  set_values {t_set:.1f} us ({share(rec * 16 + a.nnz * 4, t_set)})  torch forward {t_tf:.1f} us ({t_tf / t_f:.1f}x) backward {t_tb:.1f} us ({t_tb / t_b:.1f}x)"
+        f"  max |torch - engine| {diff:.2g}")
+    del p
+    for k in (32, 128):
+        op = flex_amd.SparseOperator(a, k, learn_values=True)
+        Q, K, V = (torch.rand((r, k), device="cuda", generator=gen).requires_grad_() for r in (a.m, a.n, a.n))
+        gO = torch.rand((a.m, k), device="cuda", generator=gen)
+        scale = k ** -0.5
+
+        def step(softmax):
+            for x in (Q, K, V):
+                x.grad = None
+            op(V, values=softmax(op.sddmm(Q, K))).backward(gO)
+
+        nn = max(3, min(50, int(2e8 / max(1, a.nnz * k))))
+        t_eng = best_us(lambda: step(lambda sc: op.edge_softmax(sc, scale)), nn)
+        t_tor = best_us(lambda: step(lambda sc: torch_softmax(sc, rows, a.m, scale)), nn)
+        say(f"{name} k={k}: attention step (forward + backward) {t_eng:.1f} us, with torch's softmax {t_tor:.1f} us ({t_tor / t_eng:.2f}x)")
+        del op
+
+
+def main():
+    args = sys.argv[1:]
+    out = os.path.join(ROOT, "profiles", "attention_probe.txt")
+    if args[:1] == ["--out"]:
+        out, args = args[1], args[2:]
+    exp_error()
+    hbm = flex_amd.hbm_probe(0, 2048, 10)
+    say(f"flex_hbm_probe: read {hbm['read_GBps']:.0f} GB/s, copy {hbm['copy_GBps']:.0f} GB/s")
+    for name in args or ["pubmed.csv", "flickr", "reddit", "soc-sign-epinions"]:
+        probe(name, load(name), hbm["copy_GBps"])
+    with open(out, "w") as f:
+        f.write("\n".join(LINES) + "\n")
+
+
+if __name__ == "__main__":
+    main()
