@@ -230,8 +230,8 @@ def lib():
 
 def _values_fn(name: str):
     """flex_plan_set_values / flex_sddmm / flex_edge_softmax / flex_edge_softmax_backward, looked up at first use and not when the
-    library loads: the host-only builds the CPU suite runs against (tests/hostsim, tools/asan_host.sh) have no kernels and so do not
-    define them."""
+    library loads: a host-only build without the kernel files does not define them (tests/hostsim has stand-ins that only log which
+    kernel the real ones would launch)."""
     L = lib()
     f = getattr(L, name)
     if f.argtypes is None:

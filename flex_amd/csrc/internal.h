@@ -186,6 +186,20 @@ inline int sddmm_lanes(int k) {
     return w;
 }
 
+// The instantiation flex_sddmm launches, sddmm_slots<W, OFF32, VEC> (values_kernels.hip): W from k, OFF32 the plan's record format, VEC
+// (16-byte loads of the G and B rows) where k, both leading dimensions and both operands allow it.  Host code, shared with the launch
+// log of tests/hostsim/shim.cpp, so that the tests declare kernels by the library's own rule.
+struct SddmmPick {
+    int W;
+    bool off32, vec4;
+};
+inline SddmmPick sddmm_pick(int k, int ldb, int ldc, bool off32, const void *dG, const void *dB) {
+    const bool vec4 = k % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0 && ((reinterpret_cast<uintptr_t>(dG) | reinterpret_cast<uintptr_t>(dB)) % 16 == 0);
+    return SddmmPick{sddmm_lanes(k), off32, vec4};
+}
+// The launches of flex_plan_set_values: refresh_records over every record, then refresh_padding where the plan has padded runs
+inline int refresh_passes(uint64_t n_records, uint64_t n_segs) { return n_records == 0 ? 0 : n_segs == 0 ? 1 : 2; }
+
 // FLEX_PLAN_MUTABLE_VALUES: the walk of flex_edge_softmax / flex_edge_softmax_backward (softmax_kernels.hip; plan_build.cpp,
 // upload_softmax_image).  It is made from hostA's row pointer alone.  A wave looks at its entries through WINDOWS of kSmWindow
 // consecutive entries that start at a multiple of 4 (a lane owns 4 consecutive entries: one 16-byte load where the arrays are aligned).
@@ -211,6 +225,11 @@ inline int softmax_row_class(uint32_t first, uint32_t len) {
 inline uint32_t softmax_group_budget(uint64_t entries) {
     const uint64_t b = (entries / kSmTargetGroups + kSmWindow - 1) / kSmWindow * kSmWindow;
     return static_cast<uint32_t>(b < kSmGroupMin ? kSmGroupMin : b > kSmGroupMax ? kSmGroupMax : b);
+}
+// VEC of edge_softmax_rows<VEC, BWD> (softmax_kernels.hip): 16-byte accesses where every array of the call is 16-byte aligned
+// (b: the backward's second input, NULL in the forward).  Shared with the launch log of tests/hostsim/shim.cpp, as sddmm_pick.
+inline bool softmax_vec(const void *a, const void *b, const void *out) {
+    return (reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(out)) % 16 == 0;
 }
 // a term of the order-free fingerprint of a row pointer slice (flex_plan_self_check)
 inline uint64_t rowptr_fp(uint32_t local_row, uint32_t first_entry) {

@@ -3,7 +3,8 @@
 // planner from hostA's row pointer (plan_build.cpp, upload_softmax_image; the classes and constants: internal.h, kSmWindow) and
 // verified by flex_plan_self_check (plan_check.cpp).
 //
-// Not SpMM kernels: a namespace of their own, outside the route table of tests/f64ref.py; tests/test_gpu_attention.py covers them.
+// Not SpMM kernels: a namespace of their own, outside the route table of tests/f64ref.py; tests/test_gpu_attention.py covers them, and
+// tests/test_gpu_values_address_limits.py declares a case for each of the four instantiations (softmax_vec, internal.h).
 //
 // Entry-parallel.  A lane owns 4 consecutive entries of a WINDOW of 256 that starts at a multiple of 4 entries, so where the arrays
 // are 16-byte aligned every full quad is one 16-byte access; the quads at the two ends of an item (and every quad of unaligned arrays:
@@ -378,7 +379,7 @@ static int launch(const flex_plan *p, bool bwd, const float *a, const float *b, 
     uint32_t wgs = (p->n_sm_groups + kWavesPerBlock - 1) / kWavesPerBlock;
     if (v.xcd_remap) wgs = (wgs + kXcds - 1) / kXcds * kXcds;
     const dim3 grid(p->n_sm_block_rows + wgs), block(64 * kWavesPerBlock);
-    const bool vec = (reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(out)) % 16 == 0;
+    const bool vec = softmax_vec(a, b, out);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (bwd && vec) hipLaunchKernelGGL((edge_softmax_rows<true, true>), grid, block, 0, s, v, a, b, scale, out);
     else if (bwd) hipLaunchKernelGGL((edge_softmax_rows<false, true>), grid, block, 0, s, v, a, b, scale, out);

@@ -3,7 +3,8 @@
 // (plan_build.cpp, upload_value_image); flex_plan_self_check verifies it (plan_check.cpp).
 //
 // These are not SpMM kernels: they live in a namespace of their own, outside the route table of the SpMM kernels
-// (tests/f64ref.py, ROUTES); tests/test_gpu_values.py covers them.
+// (tests/f64ref.py, ROUTES); tests/test_gpu_values.py covers them, and tests/test_gpu_values_address_limits.py declares a case for
+// every instantiation (tests/test_kernel_routes.py checks the declarations against sddmm_pick / refresh_passes of internal.h).
 #include <cstdint>
 
 #include "plan.h"
@@ -169,14 +170,16 @@ extern "C" {
 int flex_plan_set_values(flex_plan *p, const float *dVals, flex_stream_t stream) {
     if (!p || !p->mutable_vals) return FLEX_ERR_INVALID;
     const uint64_t n = p->d_rec.size();
-    if (n == 0) return FLEX_OK;
+    const int passes = refresh_passes(n, p->d_seg.size());
+    if (passes == 0) return FLEX_OK;
     if (!dVals && p->nnz > 0) return FLEX_ERR_INVALID;
     const DeviceScope on(p->device);
     FLEX_HIP_TRY(on.error());
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(values::refresh_records, dim3(static_cast<uint32_t>((n + 255) / 256)), dim3(256), 0, s, p->d_rec.get(), p->d_vrec.get(), p->d_src.get(), dVals, n);
     FLEX_HIP_TRY(hipGetLastError());
-    if (const uint32_t n_segs = static_cast<uint32_t>(p->d_seg.size())) {
+    if (passes == 2) {
+        const uint32_t n_segs = static_cast<uint32_t>(p->d_seg.size());
         hipLaunchKernelGGL(values::refresh_padding, dim3((n_segs + 255) / 256), dim3(256), 0, s, p->d_rec.get(), p->d_seg.get(), n_segs);
         FLEX_HIP_TRY(hipGetLastError());
     }
@@ -187,20 +190,20 @@ int flex_sddmm(const flex_plan *p, const float *dG, const float *dB, float *dOut
     if (!p || !p->mutable_vals) return FLEX_ERR_INVALID;
     if (p->n_sd_groups == 0) return FLEX_OK;
     if (!dG || !dB || !dOut) return FLEX_ERR_INVALID;
-    const int W = sddmm_lanes(p->k);
+    const SddmmPick pick = sddmm_pick(p->k, p->ldb, p->ldc, p->off32, dG, dB);
+    const int W = pick.W;
     const int ns = (p->k + 4 * W - 1) / (4 * W);
     if (ns > values::kMaxSlabs) return FLEX_ERR_UNSUPPORTED;
     const DeviceScope on(p->device);
     FLEX_HIP_TRY(on.error());
-    const bool vec4 = p->k % 4 == 0 && p->ldb % 4 == 0 && p->ldc % 4 == 0 && ((reinterpret_cast<uintptr_t>(dG) | reinterpret_cast<uintptr_t>(dB)) % 16 == 0);
     const values::SddmmView v{p->d_rec.get(), p->d_src.get(), p->d_sd_item.get(), p->d_sd_grp.get(), p->n_sd_groups, p->xcd_remap ? 1u : 0u, p->k, p->ldb, p->ldc, ns};
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     switch (W) {
-        case 4: values::launch_sddmm_w<4>(v, p->off32, vec4, dG, dB, dOut, s); break;
-        case 8: values::launch_sddmm_w<8>(v, p->off32, vec4, dG, dB, dOut, s); break;
-        case 16: values::launch_sddmm_w<16>(v, p->off32, vec4, dG, dB, dOut, s); break;
-        case 32: values::launch_sddmm_w<32>(v, p->off32, vec4, dG, dB, dOut, s); break;
-        default: values::launch_sddmm_w<64>(v, p->off32, vec4, dG, dB, dOut, s); break;
+        case 4: values::launch_sddmm_w<4>(v, pick.off32, pick.vec4, dG, dB, dOut, s); break;
+        case 8: values::launch_sddmm_w<8>(v, pick.off32, pick.vec4, dG, dB, dOut, s); break;
+        case 16: values::launch_sddmm_w<16>(v, pick.off32, pick.vec4, dG, dB, dOut, s); break;
+        case 32: values::launch_sddmm_w<32>(v, pick.off32, pick.vec4, dG, dB, dOut, s); break;
+        default: values::launch_sddmm_w<64>(v, pick.off32, pick.vec4, dG, dB, dOut, s); break;
     }
     FLEX_HIP_TRY(hipGetLastError());
     return FLEX_OK;

@@ -7,14 +7,18 @@
 // instantiation the real launcher would launch -- as `nm -C` prints it, e.g. "spmm_flat_kernel<8, false, 4, 4, false>" -- and
 // reports FLEX_OK, still computing nothing.  The selection below MIRRORS the rules of launch_spmm / launch_spmm_stamped / launch_fixup
 // (spmm_kernels.hip), launch_tiles (tile_kernels.hip) and launch_blocks (block_kernels.hip): a change there must be made here too.
+// flex_plan_set_values, flex_sddmm and flex_edge_softmax / _backward (values_kernels.hip, softmax_kernels.hip) are logged by the rules
+// the real ones use -- refresh_passes, sddmm_pick and softmax_vec of internal.h -- so nothing is mirrored for them but their refusals.
 // The "device memory" is counted (hostsim_live_allocations) and an allocation can be made to fail (hostsim_fail_malloc_at), so that
 // a test can check that a plan gives back everything it allocated, also when its creation fails half way.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 
 #include "internal.h"
+#include "plan.h"
 
 namespace {
 bool g_log_on = false;
@@ -71,7 +75,46 @@ int launch_gather_rows(float *, const float *, const int32_t *, int64_t, int, hi
 int kernel_attributes(int, bool, bool, hipFuncAttributes *, int *) { return FLEX_ERR_UNSUPPORTED; }
 }  // namespace flex
 
+namespace {
+int log_softmax(const flex_plan *p, bool bwd, const float *a, const float *b, float scale, float *out) {
+    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
+    if (!p || !p->mutable_vals) return FLEX_ERR_INVALID;
+    if (!p->sm_ok) return FLEX_ERR_UNSUPPORTED;
+    if (!std::isfinite(scale) || !(scale > 0.f)) return FLEX_ERR_INVALID;
+    if (p->sm_entries == 0) return FLEX_OK;
+    if (!a || !out || (bwd && !b)) return FLEX_ERR_INVALID;
+    char name[64];
+    std::snprintf(name, sizeof name, "edge_softmax_rows<%s, %s>", flex::softmax_vec(a, b, out) ? "true" : "false", bwd ? "true" : "false");
+    return logged(name);
+}
+}  // namespace
+
 extern "C" {
+int flex_plan_set_values(flex_plan *p, const float *dVals, flex_stream_t) {
+    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
+    if (!p || !p->mutable_vals) return FLEX_ERR_INVALID;
+    const int passes = flex::refresh_passes(p->d_rec.size(), p->d_seg.size());
+    if (passes == 0) return FLEX_OK;
+    if (!dVals && p->nnz > 0) return FLEX_ERR_INVALID;
+    logged("refresh_records");
+    return passes == 2 ? logged("refresh_padding") : FLEX_OK;
+}
+int flex_sddmm(const flex_plan *p, const float *dG, const float *dB, float *dOut, flex_stream_t) {
+    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
+    if (!p || !p->mutable_vals) return FLEX_ERR_INVALID;
+    if (p->n_sd_groups == 0) return FLEX_OK;
+    if (!dG || !dB || !dOut) return FLEX_ERR_INVALID;
+    const flex::SddmmPick pick = flex::sddmm_pick(p->k, p->ldb, p->ldc, p->off32, dG, dB);
+    char name[64];
+    std::snprintf(name, sizeof name, "sddmm_slots<%d, %s, %s>", pick.W, pick.off32 ? "true" : "false", pick.vec4 ? "true" : "false");
+    return logged(name);
+}
+int flex_edge_softmax(const flex_plan *p, const float *dScores, float scale, float *dOut, flex_stream_t) {
+    return log_softmax(p, false, dScores, nullptr, scale, dOut);
+}
+int flex_edge_softmax_backward(const flex_plan *p, const float *dP, const float *dGradP, float scale, float *dGradS, flex_stream_t) {
+    return log_softmax(p, true, dP, dGradP, scale, dGradS);
+}
 int flex_hbm_probe(int, int64_t, int, int, double *, double *) { return FLEX_ERR_UNSUPPORTED; }
 // the launch log: on != 0 turns it on, 0 off; either way it is emptied
 void hostsim_launch_log(int on) {

@@ -5,7 +5,12 @@ Every route of tests/f64ref.py (ROUTES, and the address tables of tests/test_gpu
 its plans launch.  A plan is created on the host simulator (tests/hostsim) from each scenario and launched on fake 16-byte-aligned
 operands (one float off for the unaligned routes) with the shim's launch log on; the log must equal the declaration.  A planner rule
 that sent a route to another kernel would otherwise go unseen: its float64 test would still pass, on the wrong kernel.  Every SpMM kernel
-that libflex_spmm.so ships must be declared by some route, so a new instantiation needs a route before the suite passes."""
+that libflex_spmm.so ships must be declared by some route, so a new instantiation needs a route before the suite passes.
+
+The kernels of flex::values and flex::softmax (the value refresh, the SDDMM, the edge softmax) get the same treatment through the cases of
+tests/values_marks.py, which tests/test_gpu_values_address_limits.py runs at the 2 and 4 GiB marks: every case is launched on the host
+simulator, whose stand-ins pick the instantiation by the library's own rules (internal.h: sddmm_pick, refresh_passes, softmax_vec), every
+shipped instantiation needs a case, and numpy models of the addressing faults those cases target fail the checkers they use."""
 import os
 import shutil
 import subprocess
@@ -14,10 +19,15 @@ import numpy as np
 import pytest
 
 import oracle
-from f64ref import (ADDRESS_TABLES, BIG_LDB, C_MARK4, C_ROWS, ROUTES, SCENARIOS, TOP32_N, WIDE64_N, BigB, address_case,
+from f64ref import (ADDRESS_TABLES, BIG_LDB, C_MARK4, C_ROWS, FAKE_B, FAKE_C, ROUTES, SCENARIOS, TOP32_N, WIDE64_N, BigB, address_case,
                     address_plans, block_map, block_slots, check_f64_bound, embed_cols, embed_rows, fake_launch, plan_for_route,
                     scenario, sign_extend32, spmm_big_b, wrap32)
 from flex_amd import binding
+from sddmm_ref import _gb, assert_sddmm_within_bound, sddmm64
+from softmax_ref import check_forward, forward_fp32, scores
+from values_marks import (ENTRY_ALIAS, ENTRY_K, ENTRY_OPS, ENTRY_SCALE, SDDMM_TABLES, EntryArray, alias_entry, alias_row, entry_csr,
+                          entry_filler, entry_graph, entry_launch, entry_plan, sddmm_case, sddmm_launch, sddmm_model, sddmm_plan)
+import values_marks
 
 hostsim = pytest.importorskip("hostsim")
 
@@ -175,3 +185,138 @@ def test_a_c_row_wrap_fails(name):
     assert np.array_equal(np.diff(rp)[rmap], np.diff(a.rowPtr.astype(np.int64))) and rp[-1] == a.nnz
     assert check_f64_bound(a, B, c_readback(a, B, rmap)) is None
     assert check_f64_bound(a, B, c_readback(a, B, rmap, wrap_rows=True)) is not None
+
+
+# ---- the values and softmax kernels: every case launches what it declares, every shipped instantiation has a case ------------------
+
+FAKE_G, FAKE_OUT = 0x7F8000000000, 0x7FC000000000
+
+
+@pytest.mark.parametrize("table,case", [(t, c) for t, cases in SDDMM_TABLES.items() for c in cases])
+def test_every_sddmm_case_launches_the_kernel_it_declares(sim, table, case):
+    _, a_big, _, _, _ = sddmm_case(table, case)
+    p = sddmm_plan(table, case, a_big)
+    p.self_check()
+    log = hostsim.launch_log(sim, lambda: sddmm_launch(table, case, p, FAKE_G, FAKE_B, FAKE_OUT))
+    assert log == SDDMM_TABLES[table][case]["kernels"], (table, case)
+
+
+def test_every_entry_side_call_launches_the_kernels_it_declares(sim):
+    """On a stand-in with a small filler: the selection does not look at the entry numbers."""
+    g = entry_graph()
+    p = entry_plan(entry_csr(g, entry_filler(g, 1 << 20, "block")))
+    p.self_check()
+    for op, spec in ENTRY_OPS.items():
+        log = hostsim.launch_log(sim, lambda: entry_launch(op, p, FAKE_B, FAKE_C, FAKE_OUT, FAKE_G, FAKE_B, FAKE_C))
+        assert log == spec["kernels"], op
+    with pytest.raises(binding.FlexError, match="not supported"):  # and without the log the stand-ins refuse, like every launcher
+        p.sddmm_ptr(FAKE_G, FAKE_B, FAKE_OUT)
+
+
+def shipped_values_kernels(so):
+    """The kernel handles (data symbols, not the launchers' code) of flex::values and flex::softmax in a built library, as `nm -C`
+    names them without namespace and parameters."""
+    nm = shutil.which("nm") or "/usr/bin/nm"
+    out = subprocess.run([nm, "-C", "--defined-only", so], capture_output=True, text=True, check=True).stdout
+    names = set()
+    for line in out.splitlines():
+        _, kind, sym = line.split(" ", 2)
+        if kind in "tTwW" or "__device_stub__" in sym:
+            continue
+        for ns in ("flex::values::", "flex::softmax::"):
+            if ns in sym:
+                names.add(sym.split(ns, 1)[1].split("(", 1)[0])
+    return names
+
+
+def test_every_shipped_values_and_softmax_kernel_is_declared_by_a_case():
+    so = os.path.join(os.path.dirname(binding.__file__), "lib", "libflex_spmm.so")  # the GPU build, whatever binding points at
+    assert os.path.exists(so), f"{so} is not built"
+    shipped = shipped_values_kernels(so)
+    assert len(shipped) == 26, sorted(shipped)  # 2 refresh + 20 sddmm_slots + 4 edge_softmax_rows; a new one: give it a case, then count it
+    declared = {k for k in values_marks.declared_kernels() if not k.startswith("spmm_")}
+    assert declared == shipped, (sorted(shipped - declared), sorted(declared - shipped))
+    at_marks = {k for t in ("top32", "wide64") for spec in SDDMM_TABLES[t].values() for k in spec["kernels"]}
+    assert {k for k in shipped if k.startswith("sddmm_slots")} == at_marks  # every SDDMM instantiation runs on the 4 GiB B
+
+
+# ---- the faults the values address-mark tests target -------------------------------------------------------------------------------
+
+def _coo(a):
+    return np.repeat(np.arange(a.m, dtype=np.int64), np.diff(a.rowPtr.astype(np.int64))), a.col.astype(np.int64)
+
+
+def _sddmm_small(kind, k=8):
+    a, _ = scenario("wide", k=k, m=512)
+    G, B = _gb(kind, a.m, a.n, k, 1)
+    rows, cols = _coo(a)
+    return a, G, B, rows, cols, sddmm64(rows, cols, G, B)
+
+
+@pytest.mark.parametrize("kind", ["uniform", "wide"])
+@pytest.mark.parametrize("table", ["top32", "wide64"])
+def test_sddmm_b_row_faults_fail(table, kind):
+    """B read through a 32-bit wrap of a 64-bit plan's offsets (wide64: other values) or a sign-extended 32-bit offset (top32: the NaN
+    guard); the identity model passes."""
+    a, G, B, rows, cols, (ref, T) = _sddmm_small(kind)
+    cmap = block_map(a.n, table)
+    big_g, big_b = BigB(G, np.arange(a.m)), BigB(B, cmap)
+    assert_sddmm_within_bound(sddmm_model(rows, cmap[cols], big_g, big_b), ref, T, 8, "identity")
+    fault, why = (wrap32, "beyond the bound") if table == "wide64" else (sign_extend32, "wrong class")
+    assert np.any(fault(cmap[cols]) != cmap[cols])
+    with pytest.raises(AssertionError, match=why):
+        assert_sddmm_within_bound(sddmm_model(rows, cmap[cols], big_g, big_b, read_b=fault), ref, T, 8, table)
+
+
+@pytest.mark.parametrize("kind", ["uniform", "wide", "nonfinite"])
+def test_sddmm_g_row_wrap_fails(kind):
+    """G rows >= 2^20 read at r - 2^20 (a 32-bit byte offset of G at ldc 1024): the alias is another used row."""
+    a, G, B, rows, cols, (ref, T) = _sddmm_small(kind)
+    rmap = block_map(a.m, "c_side")
+    big_g, big_b = BigB(G, rmap), BigB(B, np.arange(a.n))
+    assert_sddmm_within_bound(sddmm_model(rmap[rows], cols, big_g, big_b), ref, T, 8, "identity")
+    assert np.any(alias_row(rmap[rows]) != rmap[rows])
+    with pytest.raises(AssertionError):
+        assert_sddmm_within_bound(sddmm_model(rmap[rows], cols, big_g, big_b, read_g=alias_row), ref, T, 8, "g wrap")
+
+
+def _entry_case():
+    g = entry_graph()
+    F = entry_filler(g, "4GiB", "block")  # arithmetic only: nothing of 4 GiB is made here
+    e = np.arange(F, F + g.nnz, dtype=np.int64)
+    assert e[0] < ENTRY_ALIAS < e[-1]
+    return g, F, e
+
+
+def test_an_entry_output_written_at_the_alias_fails():
+    """out[e] written at e - 2^30: the shard's own entries keep the sentinel (the bound fails) and entries outside it change."""
+    g, F, e = _entry_case()
+    G, B = _gb("uniform", g.m, g.n, ENTRY_K, 2)
+    rows, cols = _coo(g)
+    ref, T = sddmm64(rows, cols, G, B)
+    val = sddmm_model(rows, cols, BigB(G, np.arange(g.m)), BigB(B, np.arange(g.n)))
+    for fault in (False, True):
+        out = EntryArray(-7.0)
+        out.write(alias_entry(e) if fault else e, val)
+        if not fault:
+            assert_sddmm_within_bound(out.read(e), ref, T, ENTRY_K, "identity")
+            assert out.changed_outside(F, F + g.nnz) == 0
+        else:
+            with pytest.raises(AssertionError):
+                assert_sddmm_within_bound(out.read(e), ref, T, ENTRY_K, "written at the alias")
+            assert out.changed_outside(F, F + g.nnz) == int((e >= ENTRY_ALIAS).sum())
+
+
+@pytest.mark.parametrize("kind", ["spread80", "masked30", "poisoned"])
+def test_softmax_scores_read_at_the_alias_fail(kind):
+    """Scores read at e - 2^30, where the GPU test keeps other finite values: the forward check fails; read where they are, it passes."""
+    g, F, e = _entry_case()
+    rp = F + g.rowPtr.astype(np.int64)
+    s = scores(kind, rp, seed=41)
+    x = EntryArray(np.nan)
+    x.write(e, s)
+    past = e[e >= ENTRY_ALIAS]
+    x.write(past - ENTRY_ALIAS, np.random.default_rng(7).uniform(-3, 3, len(past)).astype(np.float32))
+    check_forward(rp, s, ENTRY_SCALE, forward_fp32(rp, x.read(e), ENTRY_SCALE), "identity")
+    with pytest.raises(AssertionError):
+        check_forward(rp, s, ENTRY_SCALE, forward_fp32(rp, x.read(alias_entry(e)), ENTRY_SCALE), "read at the alias")
