@@ -17,6 +17,7 @@ from .binding import (  # noqa: F401
     FLEX_PLAN_XCD_INTERLEAVE,
     FLEX_PLAN_TRANSPOSE,
     FLEX_PLAN_MUTABLE_VALUES,
+    FLEX_PLAN_ATTENTION,
     FlexError,
     HostCsr,
     Plan,

@@ -104,14 +104,47 @@ def _function():
             (p,) = ctx.saved_tensors
             return ctx.op.plan.edge_softmax_backward(p, grad_p.contiguous(), ctx.scale), None, None
 
-    return _SpMM, _AxwLayer, _SpMMValues, _Sddmm, _EdgeSoftmax
+    class _FusedAttention(torch.autograd.Function):
+        """Out = A(alpha) V, alpha = softmax over each row of A of scale <Q[row], K[col]>, by flex_attention in one launch; alpha is
+        written and kept only when a gradient is needed.  Backward: the chain of _SpMMValues, _EdgeSoftmax and _Sddmm from the kept
+        alpha, every plan set immediately before it is used."""
+
+        @staticmethod
+        def forward(ctx, Q, K, V, op, scale):
+            Q, K, V = Q.contiguous(), K.contiguous(), V.contiguous()
+            p = torch.zeros(op.nnz, dtype=torch.float32, device=Q.device) if any(ctx.needs_input_grad[:3]) else None
+            out = op.plan.attention(Q, K, V, scale, p=p)
+            ctx.op, ctx.scale = op, scale
+            ctx.save_for_backward(Q, K, V, p)
+            return out
+
+        @staticmethod
+        def backward(ctx, grad_out):
+            Q, K, V, p = ctx.saved_tensors
+            op = ctx.op
+            g = grad_out.contiguous()
+            gQ = gK = gV = None
+            if ctx.needs_input_grad[2]:
+                op.plan_t.set_values(p)
+                gV = op.plan_t(g)
+            if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+                gs = op.plan.edge_softmax_backward(p, op.plan.sddmm(g, V), ctx.scale)
+                if ctx.needs_input_grad[0]:
+                    op.plan.set_values(gs)
+                    gQ = op.plan(K)
+                if ctx.needs_input_grad[1]:
+                    op.plan_t.set_values(gs)
+                    gK = op.plan_t(Q)
+            return gQ, gK, gV, None, None
+
+    return _SpMM, _AxwLayer, _SpMMValues, _Sddmm, _EdgeSoftmax, _FusedAttention
 
 
 _cache = None
 
 
 def functions():
-    """(_SpMM, _AxwLayer, _SpMMValues, _Sddmm, _EdgeSoftmax): the autograd Functions, built at first use (torch is imported then)."""
+    """(_SpMM, _AxwLayer, _SpMMValues, _Sddmm, _EdgeSoftmax, _FusedAttention): the autograd Functions, built at first use (torch is imported then)."""
     global _cache
     if _cache is None:
         _cache = _function()
@@ -125,13 +158,18 @@ class SparseOperator:
     in a's CSR order -- computes A(v) B, differentiable in B and in v (grad_v = SDDMM(grad_C, B) over A's pattern).  op(B) alone then
     uses a's own values.  With learn_values the operator also offers the pieces of graph attention over A's pattern, each differentiable:
     op.sddmm(Q, K) (scores per entry, Q [m, k], K [n, k]), op.edge_softmax(s, scale) (softmax over each row of A) and
-    op.attention(Q, K, V, scale) = op(V, values=op.edge_softmax(op.sddmm(Q, K), scale))."""
+    op.attention(Q, K, V, scale) = op(V, values=op.edge_softmax(op.sddmm(Q, K), scale)).
+    fused_attention=True (with learn_values=True): the forward plan is also made with FLEX_PLAN_ATTENTION and op.attention runs its
+    forward as one launch (flex_attention); the backward is the same chain of calls."""
 
     def __init__(self, a: binding.HostCsr, k: int, device: int = 0, order: int = binding.FLEX_ORDER_NATURAL, tuning: dict | None = None,
-                 learn_values: bool = False):
+                 learn_values: bool = False, fused_attention: bool = False):
+        if fused_attention and not learn_values:
+            raise NotImplementedError("fused_attention needs SparseOperator(..., learn_values=True): its backward sets the plans' values")
         self.m, self.n, self.k, self.nnz = a.m, a.n, k, a.nnz
         self.learn_values = learn_values
-        self.plan = binding.Plan(a, k, device=device, order=order, tuning=tuning, mutable_values=learn_values)
+        self.fused_attention = fused_attention
+        self.plan = binding.Plan(a, k, device=device, order=order, tuning=tuning, mutable_values=learn_values, attention=fused_attention)
         self.plan_t = binding.Plan(a, k, device=device, order=order, tuning=tuning, transpose=True, mutable_values=learn_values)
         self._v0 = None
         if learn_values:
@@ -178,4 +216,6 @@ class SparseOperator:
         self._needs_learn_values("attention")
         if scale is None:
             scale = self.k ** -0.5
+        if self.fused_attention:
+            return functions()[5].apply(Q, K, V, self, float(scale))
         return self(V, values=self.edge_softmax(self.sddmm(Q, K), scale))

@@ -27,6 +27,7 @@ FLEX_PLAN_ROW_RANGE = 0x1000
 FLEX_PLAN_XCD_INTERLEAVE = 0x2000
 FLEX_PLAN_TRANSPOSE = 0x8000
 FLEX_PLAN_MUTABLE_VALUES = 0x10000
+FLEX_PLAN_ATTENTION = 0x40000
 
 
 class FlexError(RuntimeError):
@@ -130,6 +131,11 @@ class _SoftmaxInfo(C.Structure):  # flex_softmax_info
                                           "group_entries", "device_bytes")]
 
 
+class _AttentionInfo(C.Structure):  # flex_attention_info
+    _fields_ = [(f, C.c_int64) for f in ("rows", "entries", "items", "groups", "rows_empty", "rows_slot", "rows_wave", "rows_block",
+                                          "group_budget", "device_bytes")]
+
+
 class _SynthParams(C.Structure):  # flex_synth_params
     _fields_ = [("n", C.c_int64), ("nnz", C.c_int64), ("alpha", C.c_double),
                 ("community", C.c_int64), ("p_in", C.c_double), ("p_near", C.c_double),
@@ -145,7 +151,7 @@ SYMBOLS = [
     "flex_host_csr_free", "flex_fill_dense_rand", "flex_order_rcm", "flex_order_cluster", "flex_order_gorder", "flex_perm_csr",
     "flex_order_deg", "flex_order_dfs", "flex_order_rabbit", "flex_shard_rows", "flex_synth_graph", "flex_synth_preset", "flex_strerror", "flex_last_hip_error",
     "flex_last_hip_error_string", "flex_abi_version", "flex_plan_set_values", "flex_sddmm",
-    "flex_edge_softmax", "flex_edge_softmax_backward", "flex_plan_softmax_info",
+    "flex_edge_softmax", "flex_edge_softmax_backward", "flex_plan_softmax_info", "flex_attention", "flex_plan_attention_info",
 ]
 
 _lib = None
@@ -224,12 +230,13 @@ def lib():
         L.flex_last_hip_error_string.restype = C.c_char_p
         L.flex_abi_version.restype = i32
         L.flex_plan_softmax_info.argtypes = [vp, C.POINTER(_SoftmaxInfo)]
+        L.flex_plan_attention_info.argtypes = [vp, C.POINTER(_AttentionInfo)]
         _lib = L
     return _lib
 
 
 def _values_fn(name: str):
-    """flex_plan_set_values / flex_sddmm / flex_edge_softmax / flex_edge_softmax_backward, looked up at first use and not when the
+    """flex_plan_set_values / flex_sddmm / flex_edge_softmax / flex_edge_softmax_backward / flex_attention, looked up at first use and not when the
     library loads: a host-only build without the kernel files does not define them (tests/hostsim has stand-ins that only log which
     kernel the real ones would launch)."""
     L = lib()
@@ -237,7 +244,7 @@ def _values_fn(name: str):
     if f.argtypes is None:
         vp, fl = C.c_void_p, C.c_float
         f.argtypes = {"flex_plan_set_values": [vp, vp, vp], "flex_sddmm": [vp, vp, vp, vp, vp], "flex_edge_softmax": [vp, vp, fl, vp, vp],
-                      "flex_edge_softmax_backward": [vp, vp, vp, fl, vp, vp]}[name]
+                      "flex_edge_softmax_backward": [vp, vp, vp, fl, vp, vp], "flex_attention": [vp, vp, vp, vp, fl, vp, vp, vp]}[name]
     return f
 
 
@@ -443,18 +450,21 @@ class Plan:
 
     def __init__(self, a: HostCsr, k: int, device: int = 0, order: int = FLEX_ORDER_NATURAL,
                  vo_mp=None, rows=None, col_map=None, ldb: int | None = None, ldc: int | None = None, tuning: dict | None = None,
-                 transpose: bool = False, mutable_values: bool = False):
+                 transpose: bool = False, mutable_values: bool = False, attention: bool = False):
         """tuning: plan-time knobs as a dict of flex_plan_tuning fields (0 / absent = the planner's rule), e.g.
         {"lanes_per_nz": 16, "split_rows": 1, "cluster_no_refine": 1}.
         transpose: plan A^T (FLEX_PLAN_TRANSPOSE): C [a.n, k] = A^T B [a.m, k]; every other argument refers to A^T.
         mutable_values: FLEX_PLAN_MUTABLE_VALUES -- set_values() and sddmm() work on the plan; both index A's entries in a's CSR
-        order, whatever the plan (transposed, mapped, a shard)."""
+        order, whatever the plan (transposed, mapped, a shard).
+        attention: FLEX_PLAN_ATTENTION -- attention() works on the plan (not with transpose, vo_mp or col_map)."""
         self._h = C.c_void_p()
         self.src_nnz = a.nnz
         if transpose:
             order |= FLEX_PLAN_TRANSPOSE
         if mutable_values:
             order |= FLEX_PLAN_MUTABLE_VALUES
+        if attention:
+            order |= FLEX_PLAN_ATTENTION
         self._keep = (a, vo_mp, col_map)
         v = a.view()
         L = lib()
@@ -593,6 +603,32 @@ class Plan:
             out = torch.zeros_like(gp)
         self._edge_vectors(p, gp, out)
         self.edge_softmax_backward_ptr(p.data_ptr(), gp.data_ptr(), scale, out.data_ptr(), torch.cuda.current_stream(p.device).cuda_stream)
+        return out
+
+    def attention_info(self) -> dict:
+        """flex_plan_attention_info: the schedule of attention() on this plan (rows, entries, items, groups, rows by class)."""
+        i = _AttentionInfo()
+        _check(lib().flex_plan_attention_info(self._h, C.byref(i)), "flex_plan_attention_info")
+        return {f: getattr(i, f) for f, _ in _AttentionInfo._fields_}
+
+    def attention_ptr(self, dQ_ptr: int, dK_ptr: int, dV_ptr: int, scale: float, dOut_ptr: int, dP_ptr: int | None = None, stream: int = 0):
+        _check(_values_fn("flex_attention")(self._h, dQ_ptr, dK_ptr, dV_ptr, scale, dOut_ptr, dP_ptr, stream), "flex_attention")
+
+    def attention(self, Q, K, V, scale: float, out=None, p=None):
+        """flex_attention: out [m, k] = sum over each row's entries of alpha V[col], alpha = the softmax over the row of
+        scale * <Q[row], K[col]>, in one launch.  Q: [m, k] like C; K, V: [n, k] like B; float32 cuda tensors.  p (optional): a float32
+        cuda tensor [a.nnz] that receives alpha in a's CSR order for the plan's rows (entries of other shards keep what it held)."""
+        import torch
+        i = self.info()
+        for t, rows in ((Q, i["m"]), (K, i["n"]), (V, i["n"])):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (rows, i["k"])
+        if out is None:  # every row is written, except by a plan without entries, which launches nothing
+            out = (torch.empty if i["nnz"] else torch.zeros)((i["m"], i["k"]), dtype=torch.float32, device=Q.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (i["m"], i["k"])
+        if p is not None:
+            self._edge_vectors(p)
+        self.attention_ptr(Q.data_ptr(), K.data_ptr(), V.data_ptr(), scale, out.data_ptr(), None if p is None else p.data_ptr(),
+                           torch.cuda.current_stream(Q.device).cuda_stream)
         return out
 
     def destroy(self):

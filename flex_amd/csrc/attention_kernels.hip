@@ -1,0 +1,401 @@
+// attention_kernels.hip -- the fused attention forward of FLEX_PLAN_ATTENTION plans (include/flex_spmm.h: flex_attention): scores,
+// their softmax over each row of hostA and the SpMM with the result, in one launch and without an nnz-sized intermediate.  The walk
+// is built by the planner from hostA's row pointer and columns (plan_build.cpp, upload_attention_image; the classes and constants:
+// internal.h, kAtPass) and verified by flex_plan_self_check (plan_check.cpp).
+//
+// Not an SpMM kernel and not one of flex::values / flex::softmax: a namespace of its own; tests/test_gpu_fused_attention.py covers it.
+//
+// Row-owned.  A SLOT of W lanes holds its Q row and its Out row (4 columns per lane and slab) in registers, with the running maximum m
+// and the running sum l of the row's terms exp(scale (s - m)).  Per pass the slot takes kAtPass = 4 consecutive entries: its first
+// four lanes load their K / V row indices (one coalesced access) and broadcast them, the four K rows and the four V rows are gathered
+// together, K is folded into four fma chains that are reduced across the slot so that every lane holds all four scores, the maximum is
+// raised once (one expf rescales l and the Out row), and the four terms are added.  A masked entry (-inf) adds a term of exactly 0 --
+// but still multiplies its V row, as the composition's p = +0 does -- and a NaN or +inf score turns the maximum into +inf, the mark
+// of a poisoned row (softmax_kernels.hip, max_key); nothing depends on inf - inf.
+//   slot item   up to 64 / W consecutive short rows, slot s on row s: no slot meets another
+//   wave row    the 64 / W slots take passes s, s + 64 / W, ...; their states merge in a butterfly over the slots, lower slot first
+//   block row   a workgroup: the 4 x 64 / W slots stride the row, every wave merges as above, the waves meet in LDS in wave order
+// dP: the raw score is written in the sweep by lane u of the slot for entry u of the pass; once the row's (M, L) is final the same lane
+// reads it back and overwrites it with the probability -- no second gather of K.  Fixed order everywhere, no atomics.
+#include <cmath>
+#include <cstdint>
+
+#include "plan.h"
+
+namespace flex {
+namespace attention {
+
+struct View {
+    const uint32_t *rowptr;  // the plan's rows, entries as hostA numbers them
+    const uint32_t *src;     // K / V row of entry e at src[e - e0]
+    const uint4 *item;
+    const uint32_t *grp;
+    uint32_t e0;
+    uint32_t n_groups, n_wave_items, n_block_rows;
+    uint32_t xcd_remap;
+    int32_t k, ldb, ldc;
+};
+
+constexpr int U = static_cast<int>(kAtPass);
+static_assert(U == 4, "the slot reduction below hands four scores to every lane");
+
+// columns c .. c + 3 of a row; a column at or past k is not read and reads as 0
+template <bool VEC>
+__device__ __forceinline__ float4 load_cols(const float *__restrict__ row, int c, int k) {
+    if constexpr (VEC) {
+        if (c < k) return *reinterpret_cast<const float4 *>(row + c);
+        return make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+        float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (c < k) r.x = row[c];
+        if (c + 1 < k) r.y = row[c + 1];
+        if (c + 2 < k) r.z = row[c + 2];
+        if (c + 3 < k) r.w = row[c + 3];
+        return r;
+    }
+}
+
+template <bool VEC>
+__device__ __forceinline__ void store_cols(float *__restrict__ row, int c, int k, const float4 &x) {
+    if constexpr (VEC) {
+        if (c < k) *reinterpret_cast<float4 *>(row + c) = x;
+    } else {
+        if (c < k) row[c] = x.x;
+        if (c + 1 < k) row[c + 1] = x.y;
+        if (c + 2 < k) row[c + 2] = x.z;
+        if (c + 3 < k) row[c + 3] = x.w;
+    }
+}
+
+// sum over the lane's columns of q * b; columns at or past k add nothing (not even 0 x b)
+template <bool VEC>
+__device__ __forceinline__ float dot_cols(float acc, const float4 &q, const float4 &b, int c, int k) {
+    if (c < k) acc = __builtin_fmaf(q.x, b.x, acc);
+    if (VEC ? c < k : c + 1 < k) acc = __builtin_fmaf(q.y, b.y, acc);  // VEC: k % 4 == 0, the four columns stand or fall together
+    if (VEC ? c < k : c + 2 < k) acc = __builtin_fmaf(q.z, b.z, acc);
+    if (VEC ? c < k : c + 3 < k) acc = __builtin_fmaf(q.w, b.w, acc);
+    return acc;
+}
+
+// acc += t * v on the lane's columns; columns at or past k hold v = 0 and stay 0
+__device__ __forceinline__ void axpy(float4 &acc, float t, const float4 &v) {
+    acc.x = __builtin_fmaf(t, v.x, acc.x);
+    acc.y = __builtin_fmaf(t, v.y, acc.y);
+    acc.z = __builtin_fmaf(t, v.z, acc.z);
+    acc.w = __builtin_fmaf(t, v.w, acc.w);
+}
+__device__ __forceinline__ float4 scaled(const float4 &a, float f) { return make_float4(a.x * f, a.y * f, a.z * f, a.w * f); }
+__device__ __forceinline__ float4 shfl_xor4(const float4 &a, int off) {
+    return make_float4(__shfl_xor(a.x, off), __shfl_xor(a.y, off), __shfl_xor(a.z, off), __shfl_xor(a.w, off));
+}
+
+// as softmax_kernels.hip: the score as the row maximum sees it, a term of the row sum under the finite maximum m, the probability
+__device__ __forceinline__ float max_key(float s) { return (s != s || s == INFINITY) ? INFINITY : s; }
+__device__ __forceinline__ float term(float s, float m, float scale) { return s == -INFINITY ? 0.f : expf(scale * (s - m)); }
+__device__ __forceinline__ float prob(float s, float m, float sum, float scale) {
+    return m == INFINITY ? __builtin_nanf("") : m == -INFINITY ? 0.f : term(s, m, scale) / sum;
+}
+// the factor that carries a state from its maximum m to the maximum M >= m of a merge (M finite or -inf)
+__device__ __forceinline__ float carry(float m, float M, float scale) { return m == -INFINITY ? 0.f : expf(scale * (m - M)); }
+
+// The four totals of the four per-lane partial sums over the W lanes of a slot, on every lane: the SDDMM's transposed reduction (two
+// exchange steps leave each lane one record), a butterfly over the rest, and two exchange steps back.  Every addition has the same two
+// operands on both lanes of its pair, so all lanes of the slot hold the same bits.
+template <int W>
+__device__ __forceinline__ void slot_totals(const float (&pr)[U], uint32_t li, float (&s)[U]) {
+    const bool hi2 = (li & (W / 2)) != 0, hi4 = (li & (W / 4)) != 0;
+    const float a0 = (hi2 ? pr[2] : pr[0]) + __shfl_xor(hi2 ? pr[0] : pr[2], W / 2);
+    const float a1 = (hi2 ? pr[3] : pr[1]) + __shfl_xor(hi2 ? pr[1] : pr[3], W / 2);
+    float t = (hi4 ? a1 : a0) + __shfl_xor(hi4 ? a0 : a1, W / 4);  // record 2 hi2 + hi4
+#pragma unroll
+    for (int o = W / 8; o >= 1; o >>= 1) t += __shfl_xor(t, o);
+    const float x = __shfl_xor(t, W / 4);  // record 2 hi2 + !hi4
+    const float even = hi4 ? x : t, odd = hi4 ? t : x;
+    const float oe = __shfl_xor(even, W / 2), oo = __shfl_xor(odd, W / 2);
+    s[0] = hi2 ? oe : even;
+    s[1] = hi2 ? oo : odd;
+    s[2] = hi2 ? even : oe;
+    s[3] = hi2 ? odd : oo;
+}
+
+template <int NS>
+struct State {
+    float m, l;
+    float4 acc[NS];
+};
+
+// The sweep of one slot over its share of a row: member t of a team of T slots takes the passes t, t + T, ... of kAtPass entries.
+// n_pass is the same for every lane of the wave (a slot past its row's end idles under a predicate), so every shuffle is wave-wide.
+template <int W, int NS, bool VEC>
+__device__ __forceinline__ void sweep(const View &v, const float4 (&q)[NS], const float *__restrict__ K, const float *__restrict__ V, float scale,
+                                      float *__restrict__ P, uint64_t first, uint32_t len, uint32_t t, uint32_t T, uint32_t n_pass, uint32_t lane,
+                                      uint32_t li, State<NS> &st) {
+    const int slot_lane0 = static_cast<int>(lane - li);
+    for (uint32_t pass = 0; pass < n_pass; ++pass) {
+        const uint64_t j0 = (static_cast<uint64_t>(pass) * T + t) * U;
+        const bool mine = li < static_cast<uint32_t>(U) && j0 + li < len;
+        const uint32_t idx = mine ? v.src[first - v.e0 + j0 + li] : 0u;
+        bool valid[U];
+        float4 kv[U][NS], vv[U][NS];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint32_t col = __shfl(idx, slot_lane0 + u);
+            valid[u] = j0 + u < len;
+            const float *kr = K + static_cast<size_t>(col) * v.ldb, *vr = V + static_cast<size_t>(col) * v.ldb;
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                const int c = 4 * static_cast<int>(li) + 4 * W * s;
+                kv[u][s] = valid[u] ? load_cols<VEC>(kr, c, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
+                vv[u][s] = valid[u] ? load_cols<VEC>(vr, c, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        }
+        float pr[U], sc[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            float a = 0.f;
+#pragma unroll
+            for (int s = 0; s < NS; ++s) a = dot_cols<VEC>(a, q[s], kv[u][s], 4 * static_cast<int>(li) + 4 * W * s, v.k);
+            pr[u] = a;
+        }
+        slot_totals<W>(pr, li, sc);
+        float pm = -INFINITY;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (!valid[u]) sc[u] = -INFINITY;
+            pm = fmaxf(pm, max_key(sc[u]));
+        }
+        if (P && mine) P[first + j0 + li] = li == 0 ? sc[0] : li == 1 ? sc[1] : li == 2 ? sc[2] : sc[3];
+        if (pm > st.m) {  // one rescale per pass of what the slot has summed under the old maximum
+            const float f = carry(st.m, pm, scale);
+            st.l *= f;
+#pragma unroll
+            for (int s = 0; s < NS; ++s) st.acc[s] = scaled(st.acc[s], f);
+            st.m = pm;
+        }
+        if (st.m != INFINITY) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (valid[u]) {
+                    const float tm = term(sc[u], st.m, scale);  // 0 for a masked entry, and for every entry while the maximum is -inf
+                    st.l += tm;
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) axpy(st.acc[s], tm, vv[u][s]);
+                }
+            }
+        }
+    }
+}
+
+// a <- a merged with b, `a` being the state that comes first in the fixed order
+template <int NS>
+__device__ __forceinline__ void merge(State<NS> &a, const State<NS> &b, float scale) {
+    const float M = fmaxf(a.m, b.m);
+    if (M == INFINITY) {
+        a.m = INFINITY;
+        return;
+    }
+    const float fa = carry(a.m, M, scale), fb = carry(b.m, M, scale);
+    a.m = M;
+    a.l = __builtin_fmaf(b.l, fb, a.l * fa);
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        float4 x = scaled(a.acc[s], fa);
+        axpy(x, fb, b.acc[s]);
+        a.acc[s] = x;
+    }
+}
+
+// the states of the 64 / W slots of a wave, merged on every lane: a butterfly over the slots, the lower slot's state first
+template <int W, int NS>
+__device__ __forceinline__ void merge_slots(State<NS> &st, uint32_t lane, float scale) {
+#pragma unroll
+    for (int off = W; off < 64; off <<= 1) {
+        State<NS> o;
+        o.m = __shfl_xor(st.m, off);
+        o.l = __shfl_xor(st.l, off);
+#pragma unroll
+        for (int s = 0; s < NS; ++s) o.acc[s] = shfl_xor4(st.acc[s], off);
+        if (lane & static_cast<uint32_t>(off)) {
+            merge(o, st, scale);
+            st = o;
+        } else {
+            merge(st, o, scale);
+        }
+    }
+}
+
+// the second sweep of dP: the lane that wrote a raw score reads it back and writes the probability under the row's final (M, L)
+__device__ __forceinline__ void write_probs(float *__restrict__ P, uint64_t first, uint32_t len, uint32_t t, uint32_t T, uint32_t n_pass, uint32_t li,
+                                            float M, float L, float scale) {
+    if (li >= static_cast<uint32_t>(U)) return;
+    for (uint32_t pass = 0; pass < n_pass; ++pass) {
+        const uint64_t j = (static_cast<uint64_t>(pass) * T + t) * U + li;
+        if (j < len) P[first + j] = prob(P[first + j], M, L, scale);
+    }
+}
+
+template <int NS, bool VEC>
+__device__ __forceinline__ void write_row(float *__restrict__ orow, const State<NS> &st, uint32_t li, int W, int k) {
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        float4 o;
+        if (st.m == INFINITY) {
+            const float nan = __builtin_nanf("");
+            o = make_float4(nan, nan, nan, nan);
+        } else if (st.m == -INFINITY) {
+            o = st.acc[s];  // no live entry: +0, or what 0 x a non-finite V left
+        } else {
+            o = make_float4(st.acc[s].x / st.l, st.acc[s].y / st.l, st.acc[s].z / st.l, st.acc[s].w / st.l);
+        }
+        store_cols<VEC>(orow, 4 * static_cast<int>(li) + 4 * W * s, k, o);
+    }
+}
+
+enum Kind : int { kSlotItem = 0, kWaveItem = 1, kBlockItem = 2 };
+
+// where the waves of a block row meet: (m, l) and the Out row of every wave
+template <int W, int NS>
+struct Shared {
+    float2 ml[kWavesPerBlock];
+    alignas(16) float acc[kWavesPerBlock][4 * W * NS];
+};
+
+template <int W, int NS, bool VEC>
+__device__ __forceinline__ void run_item(const View &v, const uint4 &it, int kind, const float *__restrict__ Q, const float *__restrict__ K,
+                                         const float *__restrict__ V, float scale, float *__restrict__ Out, float *__restrict__ P, uint32_t lane, uint32_t w,
+                                         Shared<W, NS> &sh) {
+    constexpr uint32_t S = 64 / W;
+    const uint32_t slot = lane / W, li = lane % W;
+    // the slot's row, its entries, and its place in the team that shares the row
+    uint32_t row = it.z, len = it.y, t = slot, T = S, n_pass;
+    uint64_t first = it.x;
+    bool has_row = true;
+    if (kind == kSlotItem) {
+        has_row = slot < it.w;
+        row = it.z + (has_row ? slot : 0u);
+        first = v.rowptr[row];
+        len = has_row ? v.rowptr[row + 1] - v.rowptr[row] : 0u;
+        t = 0;
+        T = 1;
+        uint32_t mx = (len + U - 1) / U;
+#pragma unroll
+        for (int o = 32; o >= W; o >>= 1) {
+            const uint32_t other = static_cast<uint32_t>(__shfl_xor(static_cast<int>(mx), o));
+            mx = other > mx ? other : mx;
+        }
+        n_pass = mx;
+    } else {
+        if (kind == kBlockItem) {
+            t = w * S + slot;
+            T = kWavesPerBlock * S;
+        }
+        n_pass = static_cast<uint32_t>((static_cast<uint64_t>(len) + static_cast<uint64_t>(T) * U - 1) / (static_cast<uint64_t>(T) * U));
+    }
+    float4 q[NS];
+    State<NS> st;
+    st.m = -INFINITY;
+    st.l = 0.f;
+    const float *qrow = Q + static_cast<size_t>(row) * v.ldc;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        q[s] = has_row ? load_cols<VEC>(qrow, 4 * static_cast<int>(li) + 4 * W * s, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
+        st.acc[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    sweep<W, NS, VEC>(v, q, K, V, scale, P, first, len, t, T, n_pass, lane, li, st);
+    if (kind != kSlotItem) merge_slots<W, NS>(st, lane, scale);
+    bool writer = kind == kSlotItem ? has_row : slot == 0;
+    if (kind == kBlockItem) {
+        if (slot == 0) {
+#pragma unroll
+            for (int s = 0; s < NS; ++s) *reinterpret_cast<float4 *>(&sh.acc[w][4 * li + 4 * W * s]) = st.acc[s];
+        }
+        if (lane == 0) sh.ml[w] = make_float2(st.m, st.l);
+        __syncthreads();
+        writer = w == 0 && slot == 0;
+        State<NS> tot;  // the waves in wave order: every lane folds (m, l), the writing lanes their columns as well
+        tot.m = sh.ml[0].x;
+        tot.l = sh.ml[0].y;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) tot.acc[s] = writer ? *reinterpret_cast<const float4 *>(&sh.acc[0][4 * li + 4 * W * s]) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int i = 1; i < kWavesPerBlock; ++i) {
+            State<NS> o;
+            o.m = sh.ml[i].x;
+            o.l = sh.ml[i].y;
+#pragma unroll
+            for (int s = 0; s < NS; ++s) o.acc[s] = writer ? *reinterpret_cast<const float4 *>(&sh.acc[i][4 * li + 4 * W * s]) : make_float4(0.f, 0.f, 0.f, 0.f);
+            merge(tot, o, scale);
+        }
+        st = tot;
+    }
+    if (writer) write_row<NS, VEC>(Out + static_cast<size_t>(row) * v.ldc, st, li, W, v.k);
+    if (P) write_probs(P, first, len, t, T, n_pass, li, st.m, st.l, scale);
+}
+
+// Grid: the block rows first (the longest work starts first), then the workgroups of the wave groups.
+template <int W, int NS, bool VEC>
+__global__ __launch_bounds__(256) void attention_rows(View v, const float *__restrict__ Q, const float *__restrict__ K, const float *__restrict__ V,
+                                                       float scale, float *__restrict__ Out, float *__restrict__ P) {
+    __shared__ Shared<W, NS> sh;
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    if (blockIdx.x < v.n_block_rows) {
+        run_item<W, NS, VEC>(v, v.item[v.n_wave_items + blockIdx.x], kBlockItem, Q, K, V, scale, Out, P, lane, w, sh);
+        return;
+    }
+    uint32_t wg = blockIdx.x - v.n_block_rows;
+    if (v.xcd_remap) {  // give each XCD one contiguous slice of the groups (the hardware deals workgroups round-robin)
+        const uint32_t per = (gridDim.x - v.n_block_rows) / kXcds;
+        wg = (wg % kXcds) * per + wg / kXcds;
+    }
+    const uint32_t grp = wg * kWavesPerBlock + w;
+    if (grp >= v.n_groups) return;
+    const uint32_t i1 = v.grp[grp + 1];
+    for (uint32_t i = v.grp[grp]; i < i1; ++i) {
+        const uint4 it = v.item[i];  // {first entry, entries, first row, rows}: the same for every lane
+        const int kind = (it.w > 1 || it.y <= kAtSlotRow) ? kSlotItem : kWaveItem;  // internal.h, attention_row_class
+        run_item<W, NS, VEC>(v, it, kind, Q, K, V, scale, Out, P, lane, w, sh);
+    }
+}
+
+template <int W, int NS>
+static void launch_w(const View &v, bool vec, dim3 grid, const float *Q, const float *K, const float *V, float scale, float *Out, float *P, hipStream_t s) {
+    if (vec) hipLaunchKernelGGL((attention_rows<W, NS, true>), grid, dim3(64 * kWavesPerBlock), 0, s, v, Q, K, V, scale, Out, P);
+    else hipLaunchKernelGGL((attention_rows<W, NS, false>), grid, dim3(64 * kWavesPerBlock), 0, s, v, Q, K, V, scale, Out, P);
+}
+
+}  // namespace attention
+}  // namespace flex
+
+using namespace flex;
+
+extern "C" {
+
+int flex_attention(const flex_plan *p, const float *dQ, const float *dK, const float *dV, float scale, float *dOut, float *dP, flex_stream_t stream) {
+    if (!p || !p->at_ok) return FLEX_ERR_INVALID;
+    if (!std::isfinite(scale) || !(scale > 0.f)) return FLEX_ERR_INVALID;
+    if (p->at_entries == 0) return FLEX_OK;
+    if (!dQ || !dK || !dV || !dOut) return FLEX_ERR_INVALID;
+    const AttentionPick pick = attention_pick(p->k, p->ldb, p->ldc, dQ, dK, dV, dOut);
+    if (p->k > 4 * 64 * kAtMaxSlabs) return FLEX_ERR_UNSUPPORTED;
+    const DeviceScope on(p->device);
+    FLEX_HIP_TRY(on.error());
+    const attention::View v{p->d_at_rowptr.get(), p->d_at_src.get(), p->d_at_item.get(), p->d_at_grp.get(), p->at_first_entry,
+                            p->n_at_groups, p->n_at_wave_items, p->n_at_block_rows, p->xcd_remap ? 1u : 0u, p->k, p->ldb, p->ldc};
+    uint32_t wgs = (p->n_at_groups + kWavesPerBlock - 1) / kWavesPerBlock;
+    if (v.xcd_remap) wgs = (wgs + kXcds - 1) / kXcds * kXcds;
+    const dim3 grid(p->n_at_block_rows + wgs);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    switch (pick.W * 8 + pick.NS) {
+        case 4 * 8 + 1: attention::launch_w<4, 1>(v, pick.vec4, grid, dQ, dK, dV, scale, dOut, dP, s); break;
+        case 8 * 8 + 1: attention::launch_w<8, 1>(v, pick.vec4, grid, dQ, dK, dV, scale, dOut, dP, s); break;
+        case 16 * 8 + 1: attention::launch_w<16, 1>(v, pick.vec4, grid, dQ, dK, dV, scale, dOut, dP, s); break;
+        case 32 * 8 + 1: attention::launch_w<32, 1>(v, pick.vec4, grid, dQ, dK, dV, scale, dOut, dP, s); break;
+        case 64 * 8 + 1: attention::launch_w<64, 1>(v, pick.vec4, grid, dQ, dK, dV, scale, dOut, dP, s); break;
+        case 64 * 8 + 2: attention::launch_w<64, 2>(v, pick.vec4, grid, dQ, dK, dV, scale, dOut, dP, s); break;
+        default: attention::launch_w<64, 4>(v, pick.vec4, grid, dQ, dK, dV, scale, dOut, dP, s); break;
+    }
+    FLEX_HIP_TRY(hipGetLastError());
+    return FLEX_OK;
+}
+
+}  // extern "C"

@@ -239,6 +239,46 @@ inline uint64_t rowptr_fp(uint32_t local_row, uint32_t first_entry) {
     return z ^ (z >> 31);
 }
 
+// FLEX_PLAN_ATTENTION: the walk of flex_attention (attention_kernels.hip; plan_build.cpp, upload_attention_image).  It is made from
+// hostA's row pointer and columns alone and walks hostA's rows in their order.  A SLOT is W = sddmm_lanes(k) lanes, each holding four
+// columns per slab of its Q row and of its Out row in registers; a slot takes kAtPass entries per pass.  Rows are whole: by length a row is a
+//   slot row    at most kAtSlotRow entries (an empty row too): one slot owns the row, the 64 / W slots of a wave work on 64 / W
+//               consecutive rows side by side and never meet
+//   wave row    at most kAtWaveRow entries: the slots of one wave stride the row pass by pass, their states (running maximum, sum, Out
+//               row) are merged by shuffles, lower slot first
+//   block row   longer: a workgroup of its own, its kWavesPerBlock x 64 / W slots stride the row, the waves meet in LDS in wave order
+// kAtSlotRow: up to 8 passes of one slot; beyond that the log2(64 / W) merge steps of a wave row (two expf and a shuffle of the Out row
+// each) cost less than the passes they save.  kAtWaveRow: 32 passes of the 4 slots of k = 64; a longer row takes the four waves.
+// Items are {first entry, entries, first row (index into the plan's row pointer), rows}: a slot item holds up to 64 / W consecutive
+// slot rows, a wave or block item its one row.  Slot items and wave rows are packed, in row order, into one group per wave: a group of
+// more than one item costs at most the plan's group budget, an item costing its entries + its rows.
+constexpr uint32_t kAtPass = 4;
+constexpr uint32_t kAtSlotRow = 32;
+constexpr uint32_t kAtWaveRow = 512;
+constexpr uint32_t kAtGroupMin = 64;            // group budget: total cost / kAtTargetGroups rounded up to 64, within these
+constexpr uint32_t kAtGroupMax = 2048;
+constexpr uint32_t kAtTargetGroups = 4096;      // 16 waves on each of the 256 CUs before a wave takes a second item
+constexpr int kAtMaxSlabs = 4;                  // k <= 4 x 64 lanes x 4 slabs
+enum AtClass : int { kAtSlot = 0, kAtWave = 1, kAtBlock = 2 };
+// the class of a nonempty row of `len` entries
+inline int attention_row_class(uint32_t len) { return len <= kAtSlotRow ? kAtSlot : len <= kAtWaveRow ? kAtWave : kAtBlock; }
+inline uint32_t attention_group_budget(uint64_t cost) {
+    const uint64_t b = (cost / kAtTargetGroups + 63) / 64 * 64;
+    return static_cast<uint32_t>(b < kAtGroupMin ? kAtGroupMin : b > kAtGroupMax ? kAtGroupMax : b);
+}
+// The instantiation flex_attention launches, attention_rows<W, NS, VEC> (attention_kernels.hip): W from k as the SDDMM, NS slabs of
+// 4 W columns (1 below k = 257, then 2 or 4), VEC (16-byte loads and stores of the Q, K, V and Out rows) where k, both leading
+// dimensions and all four operands allow it.  A host rule, as sddmm_pick.
+struct AttentionPick {
+    int W, NS;
+    bool vec4;
+};
+inline AttentionPick attention_pick(int k, int ldb, int ldc, const void *dQ, const void *dK, const void *dV, const void *dOut) {
+    const int W = sddmm_lanes(k), slabs = (k + 4 * W - 1) / (4 * W);
+    const uintptr_t ptrs = reinterpret_cast<uintptr_t>(dQ) | reinterpret_cast<uintptr_t>(dK) | reinterpret_cast<uintptr_t>(dV) | reinterpret_cast<uintptr_t>(dOut);
+    return AttentionPick{W, slabs <= 1 ? 1 : slabs == 2 ? 2 : 4, k % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0 && ptrs % 16 == 0};
+}
+
 // per-thread record of the last HIP failure (flex_last_hip_error)
 void note_hip_error(hipError_t e);
 

@@ -217,7 +217,7 @@ static int create_common(flex_plan **out, const flex_csr *hostA, bool all_rows, 
     if (ldb < k || ldc < k) return FLEX_ERR_INVALID;
     const unsigned order = flags & FLEX_ORDER_MASK;
     if (order > FLEX_ORDER_GORDER ||
-        (flags & ~(FLEX_ORDER_MASK | FLEX_PLAN_STATS | FLEX_PLAN_AUTOTUNE | FLEX_PLAN_XCD_INTERLEAVE | FLEX_PLAN_TRANSPOSE | FLEX_PLAN_MUTABLE_VALUES)))
+        (flags & ~(FLEX_ORDER_MASK | FLEX_PLAN_STATS | FLEX_PLAN_AUTOTUNE | FLEX_PLAN_XCD_INTERLEAVE | FLEX_PLAN_TRANSPOSE | FLEX_PLAN_MUTABLE_VALUES | FLEX_PLAN_ATTENTION)))
         return FLEX_ERR_INVALID;
     const bool mut = (flags & FLEX_PLAN_MUTABLE_VALUES) != 0;
     if (mut) {  // every nonzero on the flat record stream: the dense-tile and hot-block routes keep values in layouts of their own
@@ -228,6 +228,10 @@ static int create_common(flex_plan **out, const flex_csr *hostA, bool all_rows, 
     int rc = FLEX_OK;
     const flex_csr *const callerA = hostA;
     const bool transposed = (flags & FLEX_PLAN_TRANSPOSE) != 0;
+    // the fused attention walks hostA's rows and reads K / V by hostA's columns: no transposed plan, no map
+    const bool attn = (flags & FLEX_PLAN_ATTENTION) != 0;
+    if (attn && (transposed || col_map || dst_map)) return FLEX_ERR_UNSUPPORTED;
+    flags &= ~FLEX_PLAN_ATTENTION;  // the planner proper never sees it: the record stream is what it is without the flag
     TransposedCsr at;
     if (transposed) {
         rc = transpose_csr(hostA, &at, mut);
@@ -275,6 +279,10 @@ static int create_common(flex_plan **out, const flex_csr *hostA, bool all_rows, 
             // (it holds pieces of hostA's rows)
             if (!transposed) rc = upload_softmax_image(p.get(), callerA->rowPtr, row_begin, row_end);
             else if (all_rows) rc = upload_softmax_image(p.get(), callerA->rowPtr, 0, callerA->m);
+        }
+        if (rc == FLEX_OK && attn) {
+            p->at_ent_fp = held_entries_fp(callerA, false, row_begin, row_end, nullptr);
+            rc = upload_attention_image(p.get(), callerA, row_begin, row_end);
         }
     } catch (const std::bad_alloc &) {  // nothing crosses the C ABI as an exception
         rc = FLEX_ERR_NOMEM;
@@ -411,6 +419,13 @@ int flex_plan_softmax_info(const flex_plan *p, flex_softmax_info *o) {
     if (!p->sm_ok) return FLEX_ERR_UNSUPPORTED;
     *o = flex_softmax_info{p->sm_rows, p->sm_entries, static_cast<int64_t>(p->d_sm_item.size()), p->n_sm_groups, p->sm_class_rows[3],
                            p->sm_class_rows[kSmPacked], p->sm_class_rows[kSmWaveRow], p->sm_class_rows[kSmBlockRow], p->sm_group_budget, p->sm_bytes};
+    return FLEX_OK;
+}
+
+int flex_plan_attention_info(const flex_plan *p, flex_attention_info *o) {
+    if (!p || !o || !p->at_ok) return FLEX_ERR_INVALID;
+    *o = flex_attention_info{p->at_rows, p->at_entries, static_cast<int64_t>(p->d_at_item.size()), p->n_at_groups, p->at_class_rows[3],
+                             p->at_class_rows[kAtSlot], p->at_class_rows[kAtWave], p->at_class_rows[kAtBlock], p->at_group_budget, p->at_bytes};
     return FLEX_OK;
 }
 

@@ -150,6 +150,16 @@ struct flex_plan {
     int64_t sm_rows = 0, sm_entries = 0, sm_bytes = 0;
     int64_t sm_class_rows[4] = {0, 0, 0, 0};  // rows that are packed / wave rows / block rows / empty
     uint64_t sm_fp = 0;                       // fingerprint of the row pointer slice, taken from hostA (self-check)
+    // FLEX_PLAN_ATTENTION: the walk of flex_attention (internal.h, kAtPass; attention_kernels.hip); empty / 0 on other plans
+    bool at_ok = false;
+    flex::DeviceArray<uint32_t> d_at_rowptr;  // [at_rows + 1] hostA's row pointer for the plan's rows
+    flex::DeviceArray<uint32_t> d_at_src;     // [at_entries] K / V row of every entry of those rows, in hostA's CSR order (entry - the first one)
+    flex::DeviceArray<uint4> d_at_item;       // wave items (slot items and wave rows, grouped), then the block rows
+    flex::DeviceArray<uint32_t> d_at_grp;     // [n_at_groups + 1] first item of each wave's group
+    uint32_t n_at_groups = 0, n_at_wave_items = 0, n_at_block_rows = 0, at_group_budget = 0, at_first_entry = 0;
+    int64_t at_rows = 0, at_entries = 0, at_bytes = 0;
+    int64_t at_class_rows[4] = {0, 0, 0, 0};  // slot rows / wave rows / block rows / empty rows
+    uint64_t at_fp = 0, at_ent_fp = 0;        // fingerprints of the row pointer slice and of the (entry, K / V row) pairs, taken from hostA (self-check)
 };
 
 namespace flex {
@@ -206,6 +216,9 @@ int build_plan(flex_plan *p, const flex_csr *A, int32_t r0, int32_t r1, const in
 
 // FLEX_PLAN_MUTABLE_VALUES: builds and uploads the edge softmax's walk over rows [r0, r1) of the row pointer `rowPtr` (hostA's)
 int upload_softmax_image(flex_plan *p, const uint32_t *rowPtr, int64_t r0, int64_t r1);
+
+// FLEX_PLAN_ATTENTION: builds and uploads the walk of flex_attention over rows [r0, r1) of A (hostA as the caller passed it)
+int upload_attention_image(flex_plan *p, const flex_csr *A, int64_t r0, int64_t r1);
 
 // FLEX_PLAN_MUTABLE_VALUES: a term of the order-free fingerprint of the (entry, B row) pairs a plan holds (flex_plan_self_check)
 inline uint64_t entry_fp(uint32_t entry, uint32_t brow) {

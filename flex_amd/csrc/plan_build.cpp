@@ -1182,4 +1182,72 @@ int upload_softmax_image(flex_plan *p, const uint32_t *rowPtr, int64_t r0, int64
     return FLEX_ERR_NOMEM;
 }
 
+// The walk of flex_attention (internal.h, kAtPass): one sequential pass over the rows in their order, so the image depends on nothing
+// but the row pointer slice, the columns of its entries and k (through the slots of a wave) -- not on the host thread count.
+int upload_attention_image(flex_plan *p, const flex_csr *A, int64_t r0, int64_t r1) try {
+    const size_t rows = static_cast<size_t>(r1 - r0);
+    const uint32_t slots = 64u / static_cast<uint32_t>(sddmm_lanes(p->k));
+    std::vector<uint32_t> rp(A->rowPtr + r0, A->rowPtr + r1 + 1), grp;
+    const uint64_t entries = rp.back() - rp.front();
+    std::vector<uint32_t> src(entries ? A->col + rp.front() : nullptr, entries ? A->col + rp.back() : nullptr);
+    std::vector<uint4> item, block;
+    const uint32_t budget = attention_group_budget(entries + rows);
+    uint64_t g_cost = 0;
+    auto add_item = [&](uint32_t first, uint32_t cnt, uint32_t row, uint32_t n_rows) {
+        const uint64_t cost = static_cast<uint64_t>(cnt) + n_rows;
+        if (grp.empty() || g_cost + cost > budget) {
+            grp.push_back(static_cast<uint32_t>(item.size()));
+            g_cost = 0;
+        }
+        item.push_back(make_uint4(first, cnt, row, n_rows));
+        g_cost += cost;
+    };
+    uint64_t fp = 0;
+    int64_t by_class[4] = {0, 0, 0, 0};
+    uint32_t run_row = 0, run_rows = 0, run_cnt = 0;  // the slot item being filled: consecutive slot rows, empty ones included
+    auto close_run = [&] {
+        if (run_rows) add_item(rp[run_row], run_cnt, run_row, run_rows);
+        run_rows = run_cnt = 0;
+    };
+    for (size_t r = 0; r < rows; ++r) {
+        const uint32_t first = rp[r], len = rp[r + 1] - rp[r];
+        fp += rowptr_fp(static_cast<uint32_t>(r), first);
+        const int cls = len == 0 ? kAtSlot : attention_row_class(len);
+        ++by_class[len == 0 ? 3 : cls];
+        if (cls != kAtSlot) {
+            close_run();
+            (cls == kAtWave ? add_item(first, len, static_cast<uint32_t>(r), 1u) : block.push_back(make_uint4(first, len, static_cast<uint32_t>(r), 1u)));
+            continue;
+        }
+        if (run_rows == slots) close_run();
+        if (run_rows == 0) run_row = static_cast<uint32_t>(r);
+        run_cnt += len;
+        ++run_rows;
+    }
+    close_run();
+    fp += rowptr_fp(static_cast<uint32_t>(rows), rp.back());
+    grp.push_back(static_cast<uint32_t>(item.size()));
+    p->n_at_groups = static_cast<uint32_t>(grp.size() - 1);
+    p->n_at_wave_items = static_cast<uint32_t>(item.size());
+    p->n_at_block_rows = static_cast<uint32_t>(block.size());
+    item.insert(item.end(), block.begin(), block.end());
+    p->at_group_budget = budget;
+    p->at_rows = static_cast<int64_t>(rows);
+    p->at_entries = static_cast<int64_t>(entries);
+    p->at_first_entry = rp.front();
+    p->at_fp = fp;
+    for (int c = 0; c < 4; ++c) p->at_class_rows[c] = by_class[c];
+    const int64_t before = p->device_bytes;
+    int rc;
+    if ((rc = p->d_at_rowptr.upload(rp, &p->device_bytes))) return rc;
+    if ((rc = p->d_at_src.upload(src, &p->device_bytes))) return rc;
+    if ((rc = p->d_at_item.upload(item, &p->device_bytes))) return rc;
+    if ((rc = p->d_at_grp.upload(grp, &p->device_bytes))) return rc;
+    p->at_bytes = p->device_bytes - before;
+    p->at_ok = true;
+    return FLEX_OK;
+} catch (const std::bad_alloc &) {
+    return FLEX_ERR_NOMEM;
+}
+
 }  // namespace flex

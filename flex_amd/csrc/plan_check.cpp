@@ -265,6 +265,71 @@ static int check_softmax_image(const flex_plan *p) {
     return FLEX_OK;
 }
 
+// FLEX_PLAN_ATTENTION: the walk of flex_attention read back (internal.h, kAtPass).  The row pointer slice is monotone and has the
+// fingerprint the builder took from hostA; the (entry, K / V row) pairs have the fingerprint create_common took from hostA's columns;
+// every row of the plan, empty ones included, lies in exactly one item (each writes its row of Out) and so does every entry; an item
+// holds whole consecutive rows -- a slot item at most 64 / W rows that are all slot rows or empty, a wave or block item exactly its one
+// row -- and every row is of the class its item treats it as; the groups tile the wave items in order within the budget.
+static int check_attention_image(const flex_plan *p) {
+    std::vector<uint32_t> rp, src, grp;
+    std::vector<uint4> item;
+    if (!read_back(p->d_at_rowptr, rp) || !read_back(p->d_at_src, src) || !read_back(p->d_at_item, item) || !read_back(p->d_at_grp, grp)) return FLEX_ERR_HIP;
+    const size_t rows = static_cast<size_t>(p->at_rows);
+    if (p->at_rows != p->m || rp.size() != rows + 1 || grp.size() != p->n_at_groups + size_t(1) || item.size() != size_t(p->n_at_wave_items) + p->n_at_block_rows) return FLEX_ERR_FORMAT;
+    uint64_t fp = 0;
+    for (size_t r = 0; r <= rows; ++r) {
+        if (r < rows && rp[r] > rp[r + 1]) return FLEX_ERR_FORMAT;
+        fp += rowptr_fp(static_cast<uint32_t>(r), rp[r]);
+    }
+    if (fp != p->at_fp || static_cast<int64_t>(rp.back() - rp.front()) != p->at_entries || p->at_entries != p->nnz || src.size() != static_cast<size_t>(p->at_entries)) return FLEX_ERR_FORMAT;
+    uint64_t efp = 0;
+    for (size_t i = 0; i < src.size(); ++i) {
+        if (src[i] >= static_cast<uint64_t>(p->n)) return FLEX_ERR_FORMAT;
+        efp += entry_fp(static_cast<uint32_t>(rp.front() + i), src[i]);
+    }
+    if (efp != p->at_ent_fp) return FLEX_ERR_FORMAT;
+    if (p->at_group_budget != attention_group_budget(static_cast<uint64_t>(p->at_entries) + rows)) return FLEX_ERR_FORMAT;
+    const uint32_t slots = 64u / static_cast<uint32_t>(sddmm_lanes(p->k));
+    std::vector<uint8_t> row_seen(rows, 0);
+    int64_t covered = 0, by_class[4] = {0, 0, 0, 0};
+    for (size_t i = 0; i < item.size(); ++i) {
+        const uint4 &it = item[i];
+        const bool is_block = i >= p->n_at_wave_items;
+        if (it.w == 0 || static_cast<uint64_t>(it.z) + it.w > rows) return FLEX_ERR_FORMAT;
+        if (rp[it.z] != it.x || static_cast<uint64_t>(it.x) + it.y != rp[it.z + it.w]) return FLEX_ERR_FORMAT;  // whole consecutive rows, first to last entry
+        const bool slot_item = !is_block && (it.w > 1 || it.y <= kAtSlotRow);  // the kernel's own test
+        if (slot_item ? it.w > slots : it.w != 1) return FLEX_ERR_FORMAT;
+        for (uint32_t r = it.z; r < it.z + it.w; ++r) {
+            if (row_seen[r]++) return FLEX_ERR_FORMAT;
+            const uint32_t len = rp[r + 1] - rp[r];
+            if (len == 0) {
+                if (!slot_item) return FLEX_ERR_FORMAT;
+                ++by_class[3];
+                continue;
+            }
+            const int cls = attention_row_class(len);
+            if (cls != (slot_item ? kAtSlot : is_block ? kAtBlock : kAtWave)) return FLEX_ERR_FORMAT;
+            ++by_class[cls];
+        }
+        covered += it.y;
+    }
+    if (covered != p->at_entries) return FLEX_ERR_FORMAT;
+    for (size_t r = 0; r < rows; ++r)
+        if (row_seen[r] != 1) return FLEX_ERR_FORMAT;
+    for (int c = 0; c < 4; ++c)
+        if (by_class[c] != p->at_class_rows[c]) return FLEX_ERR_FORMAT;
+    for (size_t i = 1; i < item.size(); ++i)
+        if (i != p->n_at_wave_items && item[i].z < item[i - 1].z + item[i - 1].w) return FLEX_ERR_FORMAT;
+    if (grp.front() != 0 || grp.back() != p->n_at_wave_items) return FLEX_ERR_FORMAT;
+    for (uint32_t g = 0; g < p->n_at_groups; ++g) {
+        if (grp[g] >= grp[g + 1]) return FLEX_ERR_FORMAT;
+        uint64_t cost = 0;
+        for (uint32_t i = grp[g]; i < grp[g + 1]; ++i) cost += static_cast<uint64_t>(item[i].y) + item[i].w;
+        if (grp[g + 1] - grp[g] > 1 && cost > p->at_group_budget) return FLEX_ERR_FORMAT;
+    }
+    return FLEX_OK;
+}
+
 // ≙ the reference's tiler round-trip (mat.cu:905-940: every entry of the pillar format exists exactly once,
 // the queues are contiguous): read the plan's DEVICE image back and check that it is a partition --
 // chunks tile the tasks, tasks tile the records, every record names a valid B row, every C row is written by
@@ -502,6 +567,10 @@ int flex_plan_self_check(const flex_plan *p) try {
     if (p->mutable_vals) {
         int rc = check_value_image(p, rec, row_bytes);
         if (rc == FLEX_OK && p->sm_ok) rc = check_softmax_image(p);
+        if (rc) return rc;
+    }
+    if (p->at_ok) {
+        const int rc = check_attention_image(p);
         if (rc) return rc;
     }
     return FLEX_OK;

@@ -25,6 +25,7 @@ extern "C" {
 #endif
 
 #define FLEX_ABI_VERSION 3 /* 3 also covers the purely additive FLEX_PLAN_MUTABLE_VALUES, flex_plan_set_values, flex_sddmm and the edge softmax (no struct grew),
+                              the equally additive FLEX_PLAN_ATTENTION, flex_attention and flex_plan_attention_info (a new flag, two new calls, one new struct),
                               and the retired flex_plan_tuning.block_ablate, which keeps its place as block_ablate_retired and must be zero.
                               3: plan-time knobs leave the environment for the struct flex_plan_tuning, flex_plan_desc.tuning, flex_plan_get_tuning,
                               flex_order_cluster_ex, flex_set_host_threads; split rows are summed by a second launch by default.
@@ -98,6 +99,14 @@ typedef struct flex_plan flex_plan;
                                        of one row), 4 per group of items -- measured 8.6 bytes per nonzero on the reddit shape, 11-13 on graphs of short
                                        rows (more padding per nonzero), all counted in flex_plan_info.device_bytes; and the edge softmax's schedule
                                        (flex_softmax_info below): 4 bytes per row of hostA, 16 per work item, 4 per wave group.  Without the flag a plan is byte for byte what it was before the flag existed */
+
+#define FLEX_PLAN_ATTENTION 0x40000u /* the plan can run the fused attention forward (flex_attention below).  Independent of
+                                       FLEX_PLAN_MUTABLE_VALUES (an inference-only caller does not pay for the record -> entry map); the two
+                                       combine.  Taken by flex_plan_create, _ld, _rows and _ex, in each case without a column or row map;
+                                       FLEX_ERR_UNSUPPORTED together with FLEX_PLAN_TRANSPOSE or with a map (the softmax runs over hostA's rows:
+                                       the transposed plan stays the gradient's tool).  Extra device memory, counted in
+                                       flex_plan_info.device_bytes and reported by flex_plan_attention_info: 4 bytes per row and per entry of the
+                                       plan's rows, 16 per work item, 4 per wave group.  Without the flag nothing is uploaded for it */
 
 /* ≙ Mat::Mat + csr2_DiagTiling + alpha_transfer (mat.cu:7-31, 680-942, 268-293):
  * builds the row-panel plan for `hostA` and uploads it to `device`.  The reference's
@@ -318,6 +327,63 @@ typedef struct flex_softmax_info {
     int64_t device_bytes;  /* device memory of the schedule: 4 per row, 16 per item, 4 per group */
 } flex_softmax_info;
 int flex_plan_softmax_info(const flex_plan *plan, flex_softmax_info *out);
+
+/* Fused attention forward (FLEX_PLAN_ATTENTION plans only; FLEX_ERR_INVALID on any other plan): scores, softmax and the SpMM with the
+ * result in ONE launch, without the nnz-sized arrays of the composition flex_sddmm -> flex_edge_softmax -> flex_plan_set_values ->
+ * flex_spmm.  No reference counterpart.  For every row r of the plan, with entries e in hostA's CSR order and src(e) = hostA->col[e]:
+ *     s_e     = <Q[r], K[src(e)]>                                   (over the k columns)
+ *     alpha_e = exp(scale (s_e - M_r)) / sum_j exp(scale (s_j - M_r)),   M_r = the row's largest score     (flex_edge_softmax's definition)
+ *     Out[r]  = sum_e alpha_e V[src(e)]
+ * Q and Out have C's shape, row stride (ldc) and row convention (flex_sddmm's G: a shard's row r0 + i is row i); K and V have B's, with
+ * stride ldb.  Special values follow flex_edge_softmax: a score of -inf is a masked edge (alpha = +0); a row whose scores are all -inf,
+ * and a row without entries, write a +0 row of Out; a row that holds a +inf or NaN score writes NaN in all k columns of Out and in all
+ * its entries of dP.  Non-finite Q, K and V follow IEEE through the formulas: every entry of the row, masked or not, multiplies its V
+ * row (+0 x inf = NaN), so a NaN or inf in a V row reaches exactly the Out rows that have an entry to it, as in the composition.
+ * dP == NULL: nothing nnz-sized is written.  Otherwise dP (hostA->nnz floats, hostA's CSR order) receives alpha_e for the entries of the
+ * plan's rows -- what flex_edge_softmax_backward and the existing backward chain start from -- and entries of other shards are untouched;
+ * Out has the same bits either way.  scale must be finite and > 0 (else FLEX_ERR_INVALID); NULL Q, K, V or Out: FLEX_ERR_INVALID; a
+ * plan without entries: FLEX_OK, no launch, nothing written.  k <= 1024 (wider: FLEX_ERR_UNSUPPORTED); no column at or past k is read.
+ * Operands that are not 16-byte aligned, or k, ldb or ldc not a multiple of 4, run a generic instantiation: correct, slower.
+ * One launch, asynchronous on `stream`, no allocation, no host synchronisation (safe to capture in a hipGraph), no atomics, fixed
+ * reduction order: bit-identical run to run.  A row is owned by one slot of lanes, one wave or one workgroup (by its length, see
+ * flex_attention_info); no row is split over workgroups: a row of millions of entries is correct and slow.
+ *
+ * Accuracy, against float64 on the fp32 inputs.  u = 2^-24, gamma(n) = n u / (1 - n u), n_r = entries of the row, E = the error of the
+ * device's expf in ulp, D_r = min(104, scale x the spread of the row's finite scores) as for flex_edge_softmax, and R_r = the number of
+ * times the state that reaches the result can be rescaled: R_r = ceil(n_r / 4) + 8 (the maximum is raised at most once per pass of
+ * four entries, and no slot makes more passes than the row has; then at most 4 merges between the up to 16 slots of a wave and 3
+ * between the waves of a workgroup, stated as 8).
+ *   score   ds_e     = gamma(k) sum_j |Q K| + k 2^-149                     (flex_sddmm's bound: the reduction depth stays <= k)
+ *   alpha   dalpha_e = alpha_e [gamma(n_r + 4 D_r + (E + 3) R_r + 2 E + 4) + expm1(2 scale max_row(ds + |s| u))] + 2^-126
+ *   Out     |Out - Out64| <= sum_e (gamma(n_r + 3) alpha_e + dalpha_e) |V| + 2^-126
+ * dP is held to dalpha on its own.  Derivation.  The scores are the SDDMM's: per lane a chain of fmas over its columns, then a tree over
+ * the lanes of the slot, columns at or past k adding nothing, depth <= k.  Moving every score of a row by at most d = max_row(ds + |s| u)
+ * (|s| u: the rounding of the float64 score to the fp32 one the softmax starts from) moves a softmax by at most the factor
+ * exp(2 scale d): the expm1 term.  From the fp32 scores on it is flex_edge_softmax's derivation -- a term expf(fl(scale fl(s - m)))
+ * carries gamma(2 D_r + E + 1), the positive terms are summed in a tree of depth <= n_r, one division -- with one addition: a term is
+ * taken under the maximum m of the moment, and each later rise of the maximum (and each merge of two partial states) multiplies the
+ * running sum and the running Out row by one more factor expf(fl(scale fl(m - m'))), E + 3 roundings each (two in the argument, whose
+ * effect is bounded as for the terms inside the 4 D_r already granted once the chain's arguments add up to at most D_r, E for expf, one
+ * for the product): (E + 3) R_r.  dP's numerator is taken directly under the final maximum and divided by the same sum.  The Out row adds
+ * its terms alpha V by fma (one rounding per addition: n_r, inside a tree of the same shape as the sum's), is rescaled with the sum (the
+ * roundings differ from the sum's by one product per rescale, already counted in R_r for both), and is divided once: c = 3 covers the
+ * product-free fma, the division and the merge's final addition.  Results below 2^-126 may be flushed or rounded as subnormals: 2^-126. */
+int flex_attention(const flex_plan *plan, const float *dQ, const float *dK, const float *dV, float scale, float *dOut, float *dP, flex_stream_t stream);
+
+/* The schedule of flex_attention (host side).  FLEX_ERR_INVALID on a plan without FLEX_PLAN_ATTENTION. */
+typedef struct flex_attention_info {
+    int64_t rows;         /* rows of the plan: each writes one row of Out */
+    int64_t entries;      /* their entries */
+    int64_t items;        /* work items: runs of slot rows (one per slot of a wave) + wave rows + block rows */
+    int64_t groups;       /* wave groups: one wave each, four to a workgroup (block rows are workgroups of their own) */
+    int64_t rows_empty;   /* rows without entries: they ride in the slot items and write +0 */
+    int64_t rows_slot;    /* rows of at most 32 entries: one slot of W lanes (W = 4 .. 64 by k, as the SDDMM) owns the row, 64 / W rows side by side */
+    int64_t rows_wave;    /* rows of at most 512 entries: the slots of one wave stride the row and merge by shuffles */
+    int64_t rows_block;   /* longer rows: the four waves of a workgroup share the row and merge through LDS */
+    int64_t group_budget; /* the balance promised: a group of more than one item costs at most this much (an item costs its entries + its rows) */
+    int64_t device_bytes; /* device memory of the image: 4 per row, 4 per entry, 16 per item, 4 per group */
+} flex_attention_info;
+int flex_plan_attention_info(const flex_plan *plan, flex_attention_info *out);
 
 /* ≙ alpha_freeMatGPU (mat.cuh:184-193). */
 int flex_plan_destroy(flex_plan *plan);

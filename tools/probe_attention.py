@@ -9,7 +9,11 @@ flex_edge_softmax_backward and a whole attention step.  Writes profiles/attentio
    torch composition of the same op (scatter_reduce amax + index_add + two gathers over an int64 row index).
 3. One attention step (forward + backward of SparseOperator.attention, k = 32 and 128) against the same step with the softmax done by
    that torch composition.
-Usage: probe_attention.py [--out FILE] [graph ...]   (default: pubmed.csv flickr reddit soc-sign-epinions)"""
+4. The fused forward (flex_attention, FLEX_PLAN_ATTENTION) with and without dP against the four-call forward (flex_sddmm,
+   flex_edge_softmax, flex_plan_set_values, flex_spmm) on the same operator, k = 32 and 128: one process, the two alternating round by
+   round, best of 3 rounds after warm-up and the spread over the rounds; the image's bytes per nonzero and the step's extra memory.
+   --fused: only this part (and the copy rate).
+Usage: probe_attention.py [--out FILE] [--fused] [graph ...]   (default: pubmed.csv flickr reddit soc-sign-epinions)"""
 import ctypes as C
 import os
 import subprocess
@@ -94,16 +98,56 @@ def probe(name, a, copy_gbps):
         del op
 
 
+def probe_fused(name, a):
+    gen = torch.Generator(device="cuda").manual_seed(2)
+    for k in (32, 128):
+        op = flex_amd.SparseOperator(a, k, learn_values=True, fused_attention=True)
+        plan = op.plan
+        i = plan.attention_info()
+        Q, K, V = (torch.rand((r, k), device="cuda", generator=gen) * 2 - 1 for r in (a.m, a.n, a.n))
+        scale = k ** -0.5
+        out, s, alpha = torch.empty((a.m, k), device="cuda"), torch.empty(a.nnz, device="cuda"), torch.empty(a.nnz, device="cuda")
+
+        def four_calls():
+            plan.sddmm(Q, K, out=s)
+            plan.edge_softmax(s, scale, out=alpha)
+            plan.set_values(alpha)
+            plan(V, out=out)
+
+        fns = {"four calls": four_calls, "fused": lambda: plan.attention(Q, K, V, scale, out=out),
+               "fused + dP": lambda: plan.attention(Q, K, V, scale, out=out, p=alpha)}
+        n = max(3, min(100, int(2e8 / max(1, a.nnz * k))))
+        rounds = {key: [] for key in fns}
+        for _ in range(3):  # alternating: every round times each of the three once
+            for key, fn in fns.items():
+                rounds[key].append(best_us(fn, n, rounds=1))
+        best = {key: min(v) for key, v in rounds.items()}
+        spread = {key: 100 * (max(v) - min(v)) / min(v) for key, v in rounds.items()}
+        say(f"{name} k={k} forward (slot {i['rows_slot']} wave {i['rows_wave']} block {i['rows_block']} empty {i['rows_empty']} rows, {i['items']} items, "
+            f"{i['groups']} groups of cost <= {i['group_budget']}, image {i['device_bytes'] / max(1, a.nnz):.2f} B/nnz): "
+            + "  ".join(f"{key} {best[key]:.1f} us (+{spread[key]:.0f} % over 3 rounds)" for key in fns)
+            + f"  four calls / fused {best['four calls'] / best['fused']:.2f}x, / fused + dP {best['four calls'] / best['fused + dP']:.2f}x"
+            + f"  extra memory of a step: four calls {8 * a.nnz / 2 ** 20:.1f} MiB (s, alpha), fused + dP {4 * a.nnz / 2 ** 20:.1f} MiB, fused 0")
+        del op, plan
+
+
 def main():
     args = sys.argv[1:]
     out = os.path.join(ROOT, "profiles", "attention_probe.txt")
     if args[:1] == ["--out"]:
         out, args = args[1], args[2:]
-    exp_error()
+    fused_only = args[:1] == ["--fused"]
+    if fused_only:
+        args = args[1:]
+    else:
+        exp_error()
     hbm = flex_amd.hbm_probe(0, 2048, 10)
     say(f"flex_hbm_probe: read {hbm['read_GBps']:.0f} GB/s, copy {hbm['copy_GBps']:.0f} GB/s")
     for name in args or ["pubmed.csv", "flickr", "reddit", "soc-sign-epinions"]:
-        probe(name, load(name), hbm["copy_GBps"])
+        a = load(name)
+        if not fused_only:
+            probe(name, a, hbm["copy_GBps"])
+        probe_fused(name, a)
     with open(out, "w") as f:
         f.write("\n".join(LINES) + "\n")
 
