@@ -82,7 +82,7 @@ class _PlanTuning(C.Structure):  # flex_plan_tuning: every field 0 = the planner
         "lanes_per_nz", "chunk_records", "long_row", "piece_records", "row_cost", "xcd_slices", "xcd_balance",
         "chunk_cost", "task_cost", "split_rows", "rec_nt", "unroll", "two_d", "panel_kb", "seg_min", "mfma",
         "mfma_fill_pct", "lds_extra", "host_threads")] + [("cluster", _ClusterTuning)] + [(f, C.c_int32) for f in (
-        "blocks", "block_rounds", "block_panel_rows", "block_thr", "block_cap", "block_ablate_retired", "tile_group", "xcd_stretch", "far_first", "bundle", "bundle_len")] + [("reserved", C.c_int32 * 5)]
+        "blocks", "block_rounds", "block_panel_rows", "block_thr", "block_cap", "block_ablate_retired", "tile_group", "xcd_stretch", "far_first", "bundle", "bundle_len", "rec_pack")] + [("reserved", C.c_int32 * 4)]
 
 
 TUNING_FIELDS = tuple(f for f, _ in _PlanTuning._fields_ if f not in ("cluster", "block_ablate_retired", "reserved"))
@@ -136,6 +136,10 @@ class _AttentionInfo(C.Structure):  # flex_attention_info
                                           "group_budget", "device_bytes")]
 
 
+class _RecordInfo(C.Structure):  # flex_record_info
+    _fields_ = [("packed", C.c_int32), ("reserved", C.c_int32)] + [(f, C.c_int64) for f in ("records", "wide_records", "exceptions", "stream_bytes")]
+
+
 class _SynthParams(C.Structure):  # flex_synth_params
     _fields_ = [("n", C.c_int64), ("nnz", C.c_int64), ("alpha", C.c_double),
                 ("community", C.c_int64), ("p_in", C.c_double), ("p_near", C.c_double),
@@ -152,6 +156,7 @@ SYMBOLS = [
     "flex_order_deg", "flex_order_dfs", "flex_order_rabbit", "flex_shard_rows", "flex_synth_graph", "flex_synth_preset", "flex_strerror", "flex_last_hip_error",
     "flex_last_hip_error_string", "flex_abi_version", "flex_plan_set_values", "flex_sddmm",
     "flex_edge_softmax", "flex_edge_softmax_backward", "flex_plan_softmax_info", "flex_attention", "flex_plan_attention_info",
+    "flex_plan_record_info", "flex_plan_read_records",
 ]
 
 _lib = None
@@ -231,6 +236,8 @@ def lib():
         L.flex_abi_version.restype = i32
         L.flex_plan_softmax_info.argtypes = [vp, C.POINTER(_SoftmaxInfo)]
         L.flex_plan_attention_info.argtypes = [vp, C.POINTER(_AttentionInfo)]
+        L.flex_plan_record_info.argtypes = [vp, C.POINTER(_RecordInfo)]
+        L.flex_plan_read_records.argtypes = [vp, vp, i64]
         _lib = L
     return _lib
 
@@ -499,7 +506,23 @@ class Plan:
     def info(self) -> dict:
         i = _PlanInfo()
         _check(lib().flex_plan_get_info(self._h, C.byref(i)), "flex_plan_get_info")
-        return {f: getattr(i, f) for f, _ in _PlanInfo._fields_}
+        d = {f: getattr(i, f) for f, _ in _PlanInfo._fields_}
+        d["rec_packed"] = self.record_info()["packed"]
+        return d
+
+    def record_info(self) -> dict:
+        """flex_plan_record_info: how the record stream is stored (packed, records, wide_records, exceptions, stream_bytes)."""
+        ri = _RecordInfo()
+        _check(lib().flex_plan_record_info(self._h, C.byref(ri)), "flex_plan_record_info")
+        return {f: getattr(ri, f) for f, _ in _RecordInfo._fields_ if f != "reserved"}
+
+    def records(self) -> np.ndarray:
+        """flex_plan_read_records: the record stream read back from the device image, decoded where it is packed: uint32 [n_records, 2] =
+        {B-row byte offset or column id, value bits}."""
+        n = self.record_info()["records"]
+        out = np.empty((max(n, 1), 2), dtype=np.uint32)
+        _check(lib().flex_plan_read_records(self._h, out.ctypes.data, n), "flex_plan_read_records")
+        return out[:n]
 
     def stats(self) -> dict:
         """flex_plan_stats (≙ alpha_stats_collect + B-Re1/B-Re2); the plan must be made with FLEX_PLAN_STATS."""

@@ -41,7 +41,17 @@ struct PlanView {
     // on row s -- no cross-slot reduction, one 16-byte store per lane at the end.  nullptr when the plan has none.
     const uint32_t *bd_rows; // per bundle S entries: C row of slot s | kBundleZero (the row holds no nonzero: zeros are stored), or kBundleNoRow
     const uint2 *chunk_bd;   // [chunk-table entries] {first entry in bd_rows, entries (a multiple of S, <= kBundleRowsPerChunk)} of the chunk's bundles
+    // The PACKED record stream (plan_build.cpp, pack_records): 6 bytes per record instead of 8.  rec_packed != 0: the
+    // stream is rec_val / rec_dcol under the same record indices, and `rec` holds nothing but the records of the WIDE chunks (those with
+    // a bundle task keep the 8-byte form), one chunk after the other; nullptr when the plan has none.
+    uint32_t rec_packed;
+    const float *rec_val;      // [records] the value of each record, after the padding rule
+    const uint16_t *rec_dcol;  // [records] low 16 bits of (column - column of the record before it in the task) mod 2^32; 0 on a task's first record
+    const uint32_t *t_col0;    // [n_tasks] column of the task's first record
+    const uint2 *chunk_exc;    // [chunk-table entries] {first entry in `exc`, entries}; with kChunkWide in y: {first record of the chunk in `rec`, kChunkWide}
+    const uint2 *exc;          // differences that do not fit 16 bits: {record's position in its chunk, the difference's high 16 bits << 16}, by position
 };
+constexpr uint32_t kChunkWide = 0x80000000u;  // in chunk_exc.y: the chunk keeps 8-byte records
 
 
 // What the dense-tile kernel reads (tile_kernels.hip): 32x32 blocks of A that left the record stream.

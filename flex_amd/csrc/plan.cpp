@@ -221,16 +221,18 @@ static int create_common(flex_plan **out, const flex_csr *hostA, bool all_rows, 
         return FLEX_ERR_INVALID;
     const bool mut = (flags & FLEX_PLAN_MUTABLE_VALUES) != 0;
     if (mut) {  // every nonzero on the flat record stream: the dense-tile and hot-block routes keep values in layouts of their own
-        if (tuning.mfma == 1 || tuning.blocks == 1) return FLEX_ERR_UNSUPPORTED;
+        if (tuning.mfma == 1 || tuning.blocks == 1 || tuning.rec_pack == 1) return FLEX_ERR_UNSUPPORTED;
         tuning.mfma = 2;
         tuning.blocks = 2;
+        tuning.rec_pack = 2;  // the refresh, the SDDMM and the softmax read or write the 8-byte records
     }
     int rc = FLEX_OK;
     const flex_csr *const callerA = hostA;
     const bool transposed = (flags & FLEX_PLAN_TRANSPOSE) != 0;
     // the fused attention walks hostA's rows and reads K / V by hostA's columns: no transposed plan, no map
     const bool attn = (flags & FLEX_PLAN_ATTENTION) != 0;
-    if (attn && (transposed || col_map || dst_map)) return FLEX_ERR_UNSUPPORTED;
+    if (attn && (transposed || col_map || dst_map || tuning.rec_pack == 1)) return FLEX_ERR_UNSUPPORTED;
+    if (attn) tuning.rec_pack = 2;
     flags &= ~FLEX_PLAN_ATTENTION;  // the planner proper never sees it: the record stream is what it is without the flag
     TransposedCsr at;
     if (transposed) {
@@ -400,7 +402,7 @@ int flex_plan_get_info(const flex_plan *p, flex_plan_info *o) {
     o->two_d = p->two_d ? 1 : 0;
     o->n_tiles = p->n_tiles;
     o->tile_nnz = p->tile_nnz;
-    o->n_records = static_cast<int64_t>(p->d_rec.size());
+    o->n_records = p->n_records;
     o->panel_rows = p->two_d ? static_cast<int32_t>(p->panel_rows) : 0;
     o->n_blocks = p->bk_blocks;
     o->block_rows = p->bk_rows;
@@ -411,6 +413,14 @@ int flex_plan_get_info(const flex_plan *p, flex_plan_info *o) {
     o->block_records = static_cast<int64_t>(p->d_bk_rec.size());
     o->n_bundles = p->n_bundles;
     o->bundle_rows = p->bundle_rows;
+    return FLEX_OK;
+}
+
+int flex_plan_record_info(const flex_plan *p, flex_record_info *o) {
+    if (!p || !o) return FLEX_ERR_INVALID;
+    const int64_t exceptions = static_cast<int64_t>(p->d_exc.size());
+    const int64_t bytes = p->rec_packed ? 6 * (p->n_records - p->wide_records) + 8 * (p->wide_records + exceptions) : 8 * p->n_records;
+    *o = flex_record_info{p->rec_packed ? 1 : 0, 0, p->n_records, p->wide_records, exceptions, bytes};
     return FLEX_OK;
 }
 

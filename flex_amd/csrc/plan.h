@@ -98,6 +98,15 @@ struct flex_plan {
     flex::DeviceArray<uint4> d_chunk;
     flex::DeviceArray<uint32_t> d_bd_rows;  // row bundles (internal.h, PlanView): S entries per bundle; empty when the plan has none
     flex::DeviceArray<uint2> d_chunk_bd;
+    // the packed record stream (internal.h, PlanView::rec_packed): d_rec then holds the wide chunks' records only
+    bool rec_packed = false;
+    flex::DeviceArray<float> d_rec_val;
+    flex::DeviceArray<uint16_t> d_rec_dcol;
+    flex::DeviceArray<uint32_t> d_t_col0;
+    flex::DeviceArray<uint2> d_chunk_exc, d_exc;
+    int64_t n_records = 0;        // records of the stream (nnz - what left for tiles or blocks + padding), packed or not
+    int64_t wide_records = 0;     // packed plans: records in chunks that keep the 8-byte form
+    uint64_t rec_fp = 0;          // packed plans: fingerprint of the 8-byte stream the image encodes (self-check)
     uint32_t n_bundles = 0;
     int64_t bundle_rows = 0;                // rows that sit in bundles
     flex::DeviceArray<float> d_partial;
@@ -189,7 +198,8 @@ using RecordVec = std::vector<uint2, default_init_allocator<uint2>>;
 inline PlanView plan_view(const flex_plan *p, bool fused, uint64_t *trace) {
     return PlanView{p->d_rec.get(), p->d_t_beg.get(), p->d_t_dst.get(), p->d_t_aux.get(), p->d_chunk.get(), p->d_partial.get(), p->d_split.get(),
                     p->d_split_cnt.get(), fused ? 1u : 0u, p->n_slots, p->k, p->ldb, p->ldc,
-                    p->xcd_remap ? 1u : 0u, p->lds_extra, p->rec_nt ? 1u : 0u, p->tile_group, trace, p->d_bd_rows.get(), p->d_chunk_bd.get()};
+                    p->xcd_remap ? 1u : 0u, p->lds_extra, p->rec_nt ? 1u : 0u, p->tile_group, trace, p->d_bd_rows.get(), p->d_chunk_bd.get(),
+                    p->rec_packed ? 1u : 0u, p->d_rec_val.get(), p->d_rec_dcol.get(), p->d_t_col0.get(), p->d_chunk_exc.get(), p->d_exc.get()};
 }
 inline BlockView block_view(const flex_plan *p) {
     return BlockView{p->d_bk_hdr.get(), p->d_bk_wstart.get(), p->d_bk_cnt.get(), p->d_bk_hcol.get(), p->d_bk_brow.get(), p->d_bk_link.get(), p->d_bk_rec.get(),
@@ -264,6 +274,15 @@ double estimate_hot_share(const flex_csr *A, const std::vector<uint32_t> &sched,
 // into the block image; the caller plans the OTHER nonzeros with the flat planner.
 int build_blocks(const flex_csr *A, const std::vector<uint32_t> &sched, const std::vector<uint32_t> &colpos, const int32_t *col_map,
                  const int32_t *dst_map, int32_t r0, uint32_t row_bytes32, const BlockKnobs &kn, BlockImage &img, std::vector<uint8_t> &hot_mask);
+
+// a term of the order-free fingerprint of a record stream (packed plans: taken from the planner's 8-byte records, compared with what
+// flex_plan_self_check decodes from the device image)
+inline uint64_t record_fp(uint64_t index, uint2 r) {
+    uint64_t z = index * 0xD6E8FEB86659FD93ull + ((static_cast<uint64_t>(r.x) << 32) | r.y) + 0x9E3779B97F4A7C15ull;  // splitmix64
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
 
 // ---- plan_check.cpp
 void collect_stats(flex_plan *p, const RecordVec &rec, const std::vector<uint4> &chunk, int64_t split_nnz);

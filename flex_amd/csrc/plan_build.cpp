@@ -13,6 +13,7 @@
 //   number_split_rows      rows summed from several pieces: consecutive partial slots + the arrival bookkeeping
 //   pack_tasks_into_chunks one task per piece, tasks packed into per-wave chunks of about one budget
 //   fill_records           {B-row offset, value} per nonzero, padded to whole steps (parallel over tasks)
+//   pack_records           where the plan qualifies: the stream re-coded at 6 bytes per record (value + 16-bit column difference)
 //   upload_tasks           records / tasks / dense tiles to the device
 //   build_chunk_table      chunk headers in launch order, cut into eight cost-balanced XCD slices; statistics; the
 //                          split-row workspace
@@ -105,6 +106,8 @@ class PlanBuilder {
         if ((rc = pack_tasks_into_chunks())) return rc;
         fill_records();
         lap("records and tasks");
+        pack_records();
+        lap("record packing");
         if ((rc = upload_tasks())) return rc;
         lap("upload records/tasks");
         if ((rc = build_chunk_table())) return rc;
@@ -180,6 +183,16 @@ class PlanBuilder {
     std::vector<uint32_t> rsrc;  // mutable plans: [records] the entry each record holds (kNoEntry = padding)
     std::vector<float> rvals;    // ... and its value as given (before the padding rule)
     uint32_t slice_chunk[kXcds + 1] = {0};  // 2-D: first chunk of each XCD slice
+    // the packed stream (pack_records; internal.h, PlanView::rec_packed)
+    size_t n_records = 0;  // of the stream, whether `rec` still holds it or not
+    int pack_mode = 0;  // 0: 8-byte records; 1: pack if the rule's conditions on the finished stream hold too; 2: pack (tuning.rec_pack = 1)
+    bool packed = false;
+    std::vector<float, default_init_allocator<float>> pk_val;
+    std::vector<uint16_t, default_init_allocator<uint16_t>> pk_dcol;
+    std::vector<uint32_t> pk_col0;
+    std::vector<uint2> pk_exc, pk_chunk_exc;  // pk_chunk_exc: per chunk, in the order of w_task (build_chunk_table places them like the headers)
+    RecordVec pk_wide;
+    int64_t pk_wide_records = 0;
 
     void lap(const char *what) {
         if (!timing) return;
@@ -477,6 +490,13 @@ class PlanBuilder {
         // and not on 2-D plans (their tasks are runs of a row, not rows)
         bundles_on = bundles_expected && !two_d;
         bundle_len = static_cast<uint32_t>(pick(tn.bundle_len, S >= 8 ? 12 : 16));
+        // The packed stream (pack_records): the records are the one large term of a multi-tile launch's traffic that is read once per
+        // column tile, so two bytes less per record are two bytes less per record and tile.  The rule takes the launches the
+        // non-temporal rule above takes; a single tile reads the stream once and gains a quarter of that at the price of the decode.
+        // The kernels that write or re-read the 8-byte records (value refresh, SDDMM, softmax: mutable plans) and the 2-D schedule
+        // keep them, and so do shapes that run the generic kernel whatever the operands' alignment.
+        const bool pack_shape = !two_d && !mut && k % 4 == 0 && p->ldb % 4 == 0 && p->ldc % 4 == 0;
+        pack_mode = !pack_shape || tn.rec_pack == 2 ? 0 : tn.rec_pack == 1 ? 2 : (ktiles >= 2 && stream_bytes >= (32ull << 20)) ? 1 : 0;
         far_window = two_d ? 0u : static_cast<uint32_t>(std::max(0, tn.far_first));  // (2-D pieces are cut by column panel already)
         p->tuning.far_first = static_cast<int32_t>(far_window);
         // what this plan was built with (flex_plan_get_tuning)
@@ -892,8 +912,94 @@ class PlanBuilder {
         pent = std::vector<uint32_t>();
     }
 
+    // The stream at 6 bytes per record (internal.h, PlanView::rec_packed).  Record indices stay: rec_val[i] is record i's value and
+    // rec_dcol[i] the low half of its column's difference to record i - 1 of the same task, modulo 2^32 -- so columns in any order
+    // (unsorted rows, far_first) decode, they only cost exceptions: a difference whose high half is not zero is listed, by position, in
+    // its chunk's part of `exc`.  A task's first record stores 0 and its column is t_col0[task].  Chunks with a bundle task (slots of a
+    // step belong to different rows there) keep their 8-byte records, packed one chunk after the other into what `rec` then holds.
+    // Parallel over chunks, two passes (count, fill): the image does not depend on the thread count.
+    void pack_records() {
+        p->tuning.rec_pack = 2;
+        const uint32_t n_real = static_cast<uint32_t>(w_task.size() - 1);
+        if (pack_mode == 0 || rec.empty() || n_real == 0) return;
+        const uint32_t row_bytes32 = static_cast<uint32_t>(p->ldb) * 4u;
+        const bool off32 = p->off32;
+        auto col_of = [&](const uint2 &r) { return off32 ? r.x / row_bytes32 : r.x; };
+        std::vector<uint8_t> wide(n_real, 0);
+        std::vector<uint64_t> wide_at(static_cast<size_t>(n_real) + 1, 0), exc_at(static_cast<size_t>(n_real) + 1, 0);
+        constexpr int64_t kChunkBlk = 256;
+        const int64_t nblk = (static_cast<int64_t>(n_real) + kChunkBlk - 1) / kChunkBlk;
+        std::vector<uint64_t> blk_fp(static_cast<size_t>(nblk), 0);
+        parallel_chunks(nblk, [&](int64_t b) {
+            uint64_t fp = 0;
+            for (int64_t c = b * kChunkBlk; c < std::min<int64_t>(n_real, (b + 1) * kChunkBlk); ++c) {
+                for (uint32_t t = w_task[c]; t < w_task[c + 1]; ++t) wide[c] |= tasks[t].rows ? 1 : 0;
+                const uint32_t zb = t_beg[w_task[c]], ze = t_beg[w_task[c + 1]];
+                for (uint32_t i = zb; i < ze; ++i) fp += record_fp(i, rec[i]);
+                if (wide[c]) {
+                    wide_at[c + 1] = ze - zb;
+                    continue;
+                }
+                uint64_t n_exc = 0;
+                for (uint32_t t = w_task[c]; t < w_task[c + 1]; ++t)
+                    for (uint32_t i = t_beg[t] + 1; i < t_beg[t + 1]; ++i) n_exc += ((col_of(rec[i]) - col_of(rec[i - 1])) >> 16) ? 1 : 0;
+                exc_at[c + 1] = n_exc;
+            }
+            blk_fp[static_cast<size_t>(b)] = fp;
+        });
+        for (uint32_t c = 0; c < n_real; ++c) {
+            wide_at[c + 1] += wide_at[c];
+            exc_at[c + 1] += exc_at[c];
+        }
+        const uint64_t n_wide = wide_at[n_real], n_exc = exc_at[n_real];
+        if (timing)
+            std::fprintf(stderr, "plan: record packing: %zu records, %.3f %% in wide chunks, %llu exceptions (%.3f %%)\n", rec.size(), 100.0 * n_wide / rec.size(),
+                         static_cast<unsigned long long>(n_exc), 100.0 * n_exc / rec.size());
+        if (n_exc >= (uint64_t(1) << 32)) return;  // chunk_exc holds 32-bit positions in `exc`
+        // the rule: less than 5 % of the records in wide chunks, and exceptions (8 bytes each) that leave most of the 2 bytes per record
+        if (pack_mode == 1 && (n_wide * 20 >= rec.size() || n_exc * 16 >= rec.size())) return;
+        pk_val.resize(rec.size());
+        pk_dcol.resize(rec.size());
+        pk_col0.assign(tasks.size(), 0u);
+        pk_exc.resize(static_cast<size_t>(n_exc));
+        pk_chunk_exc.resize(n_real);
+        pk_wide.resize(static_cast<size_t>(n_wide));
+        parallel_chunks(nblk, [&](int64_t b) {
+            for (int64_t c = b * kChunkBlk; c < std::min<int64_t>(n_real, (b + 1) * kChunkBlk); ++c) {
+                const uint32_t zb = t_beg[w_task[c]], ze = t_beg[w_task[c + 1]];
+                if (wide[c]) {  // the packed arrays keep the chunk's indices, unused: zeros, so that the image is defined
+                    std::copy(rec.begin() + zb, rec.begin() + ze, pk_wide.begin() + static_cast<ptrdiff_t>(wide_at[c]));
+                    std::fill(pk_val.begin() + zb, pk_val.begin() + ze, 0.0f);
+                    std::fill(pk_dcol.begin() + zb, pk_dcol.begin() + ze, uint16_t(0));
+                    pk_chunk_exc[c] = make_uint2(static_cast<uint32_t>(wide_at[c]), kChunkWide);
+                    continue;
+                }
+                uint2 *e = pk_exc.data() + exc_at[c];
+                for (uint32_t t = w_task[c]; t < w_task[c + 1]; ++t) {
+                    uint32_t prev = 0;
+                    for (uint32_t i = t_beg[t]; i < t_beg[t + 1]; ++i) {
+                        const uint32_t col = col_of(rec[i]), d = i == t_beg[t] ? 0u : col - prev;
+                        if (i == t_beg[t]) pk_col0[t] = col;
+                        std::memcpy(&pk_val[i], &rec[i].y, 4);
+                        pk_dcol[i] = static_cast<uint16_t>(d);
+                        if (d >> 16) *e++ = make_uint2(i - zb, d & 0xFFFF0000u);
+                        prev = col;
+                    }
+                }
+                pk_chunk_exc[c] = make_uint2(static_cast<uint32_t>(exc_at[c]), static_cast<uint32_t>(exc_at[c + 1] - exc_at[c]));
+            }
+        });
+        p->rec_fp = std::accumulate(blk_fp.begin(), blk_fp.end(), uint64_t(0));
+        pk_wide_records = static_cast<int64_t>(n_wide);
+        packed = true;
+        p->tuning.rec_pack = 1;
+        n_records = rec.size();
+        if (!(flags & FLEX_PLAN_STATS)) rec = RecordVec();  // only collect_stats reads the 8-byte records from here on: 2.2 GB of host memory on the Amazon shape
+    }
+
     int upload_tasks() {
         p->n_tasks = static_cast<uint32_t>(tasks.size());
+        p->n_records = static_cast<int64_t>(packed ? n_records : rec.size());
         p->n_bundles = n_bundles;
         p->bundle_rows = bundle_rows;
         p->c_rows = dst_map ? A->m : m;
@@ -903,7 +1009,20 @@ class PlanBuilder {
         p->two_d = two_d;
         p->panel_rows = 1u << pshift;
         int rc;
-        if ((rc = p->d_rec.upload(rec, &p->device_bytes))) return rc;
+        if (packed) {  // the 8-byte stream is neither allocated nor uploaded: `rec` holds the wide chunks' records, if there are any
+            p->rec_packed = true;
+            p->wide_records = pk_wide_records;
+            if (!pk_wide.empty() && (rc = p->d_rec.upload(pk_wide, &p->device_bytes))) return rc;
+            if ((rc = p->d_rec_val.upload(pk_val, &p->device_bytes))) return rc;
+            if ((rc = p->d_rec_dcol.upload(pk_dcol, &p->device_bytes))) return rc;
+            if ((rc = p->d_t_col0.upload(pk_col0, &p->device_bytes))) return rc;
+            if ((rc = p->d_exc.upload(pk_exc, &p->device_bytes))) return rc;
+            pk_wide = RecordVec();
+            pk_val = decltype(pk_val)();
+            pk_dcol = decltype(pk_dcol)();
+        } else if ((rc = p->d_rec.upload(rec, &p->device_bytes))) {
+            return rc;
+        }
         if ((rc = p->d_t_beg.upload(t_beg, &p->device_bytes))) return rc;
         if ((rc = p->d_t_dst.upload(t_dst, &p->device_bytes))) return rc;
         if ((rc = p->d_t_aux.upload(t_aux, &p->device_bytes))) return rc;
@@ -986,9 +1105,11 @@ class PlanBuilder {
         };
         std::vector<uint4> chunk;
         std::vector<uint2> cbd;  // the chunks' bundle tables, placed like the headers (left empty when the plan has no bundle)
+        std::vector<uint2> cex;  // packed plans: the chunks' exception tables, placed like the headers
         auto place = [&](size_t at, uint32_t c) {
             chunk[at] = header(c);
             if (n_bundles) cbd[at] = chunk_bd[c];
+            if (packed) cex[at] = pk_chunk_exc[c];
         };
         p->tuning.xcd_balance = tn.xcd_balance == 2 ? 2 : 1;
         if (xcd_dealt && !two_d && n_real >= 8u * kXcds * kWavesPerBlock) {
@@ -1006,6 +1127,7 @@ class PlanBuilder {
             longest = (longest + kWavesPerBlock - 1) / kWavesPerBlock * kWavesPerBlock;
             chunk.assign(static_cast<size_t>(longest) * kXcds, make_uint4(0u, 0u, 0u, 0u));
             if (n_bundles) cbd.assign(chunk.size(), make_uint2(0u, 0u));
+            if (packed) cex.assign(chunk.size(), make_uint2(0u, 0u));
             uint32_t at[kXcds] = {};
             for (uint32_t s = 0; s < n_st; ++s) {
                 const uint32_t x = s % kXcds, c0 = s * per, c1 = std::min(n_real, c0 + per);
@@ -1041,11 +1163,13 @@ class PlanBuilder {
             longest = (longest + kWavesPerBlock - 1) / kWavesPerBlock * kWavesPerBlock;
             chunk.assign(static_cast<size_t>(longest) * kXcds, make_uint4(0u, 0u, 0u, 0u));  // empty: no tasks, no records
             if (n_bundles) cbd.assign(chunk.size(), make_uint2(0u, 0u));
+            if (packed) cex.assign(chunk.size(), make_uint2(0u, 0u));
             for (uint32_t x = 0; x < kXcds; ++x)
                 for (uint32_t c = cut[x]; c < cut[x + 1]; ++c) place(static_cast<size_t>(x) * longest + (c - cut[x]), c);
         } else {
             chunk.resize(n_real);
             if (n_bundles) cbd.resize(n_real);
+            if (packed) cex.resize(n_real);
             for (uint32_t c = 0; c < n_real; ++c) place(c, c);
         }
         p->n_chunks = n_real;
@@ -1053,6 +1177,7 @@ class PlanBuilder {
         int rc;
         if ((rc = p->d_chunk.upload(chunk, &p->device_bytes))) return rc;
         if (n_bundles && (rc = p->d_chunk_bd.upload(cbd, &p->device_bytes))) return rc;
+        if (packed && (rc = p->d_chunk_exc.upload(cex, &p->device_bytes))) return rc;
         if (flags & FLEX_PLAN_STATS) collect_stats(p, rec, chunk, split_nnz);
         // split-row workspace: the rows, one arrival counter per (row, column tile) -- zero between launches -- and the partial sums
         if ((rc = p->d_split.upload(split, &p->device_bytes))) return rc;

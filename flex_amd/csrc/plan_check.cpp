@@ -72,9 +72,96 @@ static bool read_back(const DeviceArray<T> &d, std::vector<T> &h) {
     return h.empty() || hipMemcpy(h.data(), d.get(), h.size() * sizeof(T), hipMemcpyDeviceToHost) == hipSuccess;
 }
 
+// The record stream of the DEVICE image as 8-byte records {B-row byte offset or column id, value bits}: read back as it is, or, for a
+// packed plan (internal.h, PlanView::rec_packed), decoded -- the host twin of the kernels' staging step.  t_beg and chunk are the
+// plan's, read back by the caller with their lengths checked; nothing else of the image is trusted: every index is bounded before it
+// is used, the exception lists must be sorted by position, name no task's first record and carry a high half only, a wide chunk's
+// records must lie inside `rec`, the lists and the wide records must be used up exactly, every column must be a row of B, and the
+// decoded stream must have the fingerprint the planner took from its own 8-byte records.
+static int load_records(const flex_plan *p, const std::vector<uint32_t> &t_beg, const std::vector<uint4> &chunk, std::vector<uint2> &rec) {
+    const size_t n_rec = static_cast<size_t>(p->n_records);
+    if (!p->rec_packed) {
+        if (p->d_rec.size() != n_rec) return FLEX_ERR_FORMAT;
+        return read_back(p->d_rec, rec) ? FLEX_OK : FLEX_ERR_HIP;
+    }
+    if (p->d_rec_val.size() != n_rec || p->d_rec_dcol.size() != n_rec || p->d_t_col0.size() != p->n_tasks || p->d_chunk_exc.size() != chunk.size() ||
+        p->d_rec.size() != static_cast<size_t>(p->wide_records) || (p->wide_records == 0) != (p->d_rec.get() == nullptr))
+        return FLEX_ERR_FORMAT;
+    std::vector<float> val;
+    std::vector<uint16_t> dcol;
+    std::vector<uint32_t> col0;
+    std::vector<uint2> cex, exc, wide;
+    if (!read_back(p->d_rec_val, val) || !read_back(p->d_rec_dcol, dcol) || !read_back(p->d_t_col0, col0) || !read_back(p->d_chunk_exc, cex) ||
+        !read_back(p->d_exc, exc) || !read_back(p->d_rec, wide))
+        return FLEX_ERR_HIP;
+    const uint32_t row_bytes32 = static_cast<uint32_t>(p->ldb) * 4u;
+    rec.assign(n_rec, make_uint2(0u, 0u));
+    uint64_t exc_used = 0, wide_used = 0;
+    for (size_t ci = 0; ci < chunk.size(); ++ci) {
+        const uint4 &c = chunk[ci];
+        const uint2 ce = cex[ci];
+        if (c.y == 0) {
+            if (ce.x | ce.y) return FLEX_ERR_FORMAT;
+            continue;
+        }
+        if (static_cast<uint64_t>(c.x) + c.y > p->n_tasks || c.z != t_beg[c.x] || c.w != t_beg[c.x + c.y] || c.z > c.w || c.w > n_rec) return FLEX_ERR_FORMAT;
+        if (ce.y & kChunkWide) {
+            if (ce.y != kChunkWide || ce.x != wide_used || wide_used + (c.w - c.z) > wide.size()) return FLEX_ERR_FORMAT;
+            std::copy(wide.begin() + static_cast<ptrdiff_t>(wide_used), wide.begin() + static_cast<ptrdiff_t>(wide_used + (c.w - c.z)), rec.begin() + c.z);
+            wide_used += c.w - c.z;
+            continue;
+        }
+        if (ce.x != exc_used || exc_used + ce.y > exc.size()) return FLEX_ERR_FORMAT;
+        const uint2 *e = exc.data() + exc_used, *const e_end = e + ce.y;
+        for (uint32_t t = c.x; t < c.x + c.y; ++t) {
+            if (t_beg[t] > t_beg[t + 1] || t_beg[t + 1] > c.w) return FLEX_ERR_FORMAT;
+            uint32_t col = col0[t];
+            for (uint32_t i = t_beg[t]; i < t_beg[t + 1]; ++i) {
+                uint32_t d = dcol[i];
+                if (e < e_end && e->x == i - c.z) {
+                    if (i == t_beg[t] || (e->y & 0xFFFFu) != 0 || e->y == 0) return FLEX_ERR_FORMAT;
+                    d |= e->y;
+                    ++e;
+                }
+                if (i == t_beg[t] && d != 0) return FLEX_ERR_FORMAT;
+                col += d;
+                if (col >= static_cast<uint64_t>(p->n)) return FLEX_ERR_FORMAT;
+                rec[i] = make_uint2(p->off32 ? col * row_bytes32 : col, __builtin_bit_cast(uint32_t, val[i]));
+            }
+        }
+        if (e != e_end) return FLEX_ERR_FORMAT;  // an entry out of order, or one that names no record of the chunk
+        exc_used += ce.y;
+    }
+    if (exc_used != exc.size() || wide_used != wide.size()) return FLEX_ERR_FORMAT;
+    uint64_t fp = 0;
+    for (size_t i = 0; i < n_rec; ++i) fp += record_fp(i, rec[i]);
+    return fp == p->rec_fp ? FLEX_OK : FLEX_ERR_FORMAT;
+}
+
 }  // namespace flex
 
 extern "C" {
+
+int flex_plan_read_records(const flex_plan *p, uint32_t *out, int64_t records) try {
+    if (!p || records != p->n_records || (!out && records > 0)) return FLEX_ERR_INVALID;
+    if (records == 0) return FLEX_OK;
+    const DeviceScope on(p->device);
+    FLEX_HIP_TRY(on.error());
+    if (p->d_t_beg.size() != p->n_tasks + size_t(1) || p->d_chunk.size() != p->n_slots) return FLEX_ERR_FORMAT;
+    std::vector<uint32_t> t_beg;
+    std::vector<uint4> chunk;
+    std::vector<uint2> rec;
+    if (!read_back(p->d_t_beg, t_beg) || !read_back(p->d_chunk, chunk)) return FLEX_ERR_HIP;
+    const int rc = load_records(p, t_beg, chunk, rec);
+    if (rc) return rc;
+    for (size_t i = 0; i < rec.size(); ++i) {
+        out[2 * i] = rec[i].x;
+        out[2 * i + 1] = rec[i].y;
+    }
+    return FLEX_OK;
+} catch (const std::bad_alloc &) {
+    return FLEX_ERR_NOMEM;
+}
 
 int flex_plan_measure_imbalance(flex_plan *p, const float *dB, float *dC, flex_stream_t stream, flex_imbalance *out) try {
     if (!p || !out || !dC || (!dB && p->nnz > 0)) return FLEX_ERR_INVALID;
@@ -341,7 +428,7 @@ int flex_plan_self_check(const flex_plan *p) try {
     const DeviceScope on(p->device);
     FLEX_HIP_TRY(on.error());
     // every array is as long as the plan's counts say, before any of them is read
-    const size_t n_rec = p->d_rec.size(), n_tasks = p->n_tasks, n_slots = p->n_slots, n_blocks = p->bk_blocks;
+    const size_t n_rec = static_cast<size_t>(p->n_records), n_tasks = p->n_tasks, n_slots = p->n_slots, n_blocks = p->bk_blocks;
     if (p->d_t_beg.size() != n_tasks + 1 || p->d_t_dst.size() != n_tasks || p->d_t_aux.size() != n_tasks || p->d_chunk.size() != n_slots ||
         p->d_chunk_bd.size() != (p->n_bundles ? n_slots : 0) || p->d_split.size() != p->n_split)
         return FLEX_ERR_FORMAT;
@@ -357,9 +444,11 @@ int flex_plan_self_check(const flex_plan *p) try {
     std::vector<uint32_t> t_beg, t_dst, bd_rows;
     std::vector<uint4> chunk;
     std::vector<SplitRow> split;
-    if (!read_back(p->d_rec, rec) || !read_back(p->d_t_beg, t_beg) || !read_back(p->d_t_dst, t_dst) || !read_back(p->d_chunk, chunk) ||
+    if (!read_back(p->d_t_beg, t_beg) || !read_back(p->d_t_dst, t_dst) || !read_back(p->d_chunk, chunk) ||
         !read_back(p->d_split, split) || !read_back(p->d_t_aux, t_aux) || !read_back(p->d_chunk_bd, chunk_bd) || !read_back(p->d_bd_rows, bd_rows))
         return FLEX_ERR_HIP;
+    // the record stream, decoded where it is packed: everything below checks the records the kernels will see
+    if (const int rc = load_records(p, t_beg, chunk, rec)) return rc;
 
     // tasks tile the record stream
     if (t_beg[0] != 0 || t_beg[p->n_tasks] != n_rec) return FLEX_ERR_FORMAT;

@@ -293,11 +293,147 @@ __device__ __forceinline__ void stage_window(uint2 *my_lds, const uint2 *__restr
     else stage_window_t<false, G>(my_lds, rec, wz, wn, lane);
 }
 
+// ---- the packed stream (internal.h, PlanView::rec_packed): 6 bytes per record in global memory, and after this staging
+// step exactly the window of 8-byte records {byte offset or column, value} the step loop reads above.
+//   1. coalesced loads of the window's values and 16-bit differences, clamped and unpredicated as in stage_n, all issued before the
+//      first is used; the differences go to the wave's LDS slice as {32-bit word, 0}, the values wait in registers: until the scan is
+//      done the .y half of a record's slot is its segment flag, so the decode needs no LDS beyond the window itself;
+//   2. the chunk's exceptions add their high halves (one lane each); lane 0 adds the column the previous window ended on to word 0 (a
+//      window that starts inside a task); the lanes of the tasks that start in the window overwrite their first slot with
+//      {t_col0, 1} -- now every word is a difference to its predecessor, or the flagged start of a segment;
+//   3. a segmented inclusive scan: lane l takes the R = window / 64 consecutive words l R .. l R + R - 1 serially from 0 (x = where it
+//      ends up: the sum of all of them, or of those from its last segment start on), one unsegmented wave scan gives E[l] = x[0] +
+//      ... + x[l - 1], and what enters lane l from below is E[l] - E[q], q the highest lane below l that holds a segment start
+//      (a ballot and a count of leading zeros), or E[l] when there is none;
+//   4. the columns go back as byte offsets (OFF32) or as they are (the values took their .y halves once every lane had read its flags).
+// Returns the column of the window's last slot: the next window's carry (read only when this window was full).
+// LDS operations of one wave complete in order, and the record slice is private to the wave: no barrier, as above.
+// PAIR (tiles of two or more slots per step: every task, hence every window, starts at an even record): a lane takes two
+// consecutive records per load -- 8 bytes of values, 4 of differences, one 16-byte LDS write -- so a window costs as many loads as
+// it did at 8 bytes per record.  The one-slot tile (G = 64) may start at an odd record and loads record by record.
+template <bool NT, class T>
+__device__ __forceinline__ T load_stream(const T *ptr) {
+    if constexpr (NT) return __builtin_nontemporal_load(ptr);
+    else return *ptr;
+}
+
+// loads of LOADS <= FULL wave loads; vv: the values, in load order (PAIR: two per load); those of loads not made are 0
+template <bool NT, bool PAIR, int LOADS, int R>
+__device__ __forceinline__ void stage_packed_n(uint2 *my_lds, const float *__restrict__ val, const uint16_t *__restrict__ dcol, uint32_t wn, int lane,
+                                               uint32_t (&vv)[R]) {
+    // addresses as base (SGPR pair) + 32-bit byte offset in a VGPR, as gather4: a window is a few KiB, and one register per load
+    // instead of an address pair keeps the staging step below the gather loop's register count
+    const char *const vb = reinterpret_cast<const char *>(val), *const db = reinterpret_cast<const char *>(dcol);
+#pragma unroll
+    for (int i = 0; i < R; ++i) vv[i] = 0u;
+    if constexpr (PAIR) {
+        uint32_t d[LOADS];
+#pragma unroll
+        for (int i = 0; i < LOADS; ++i) {
+            const uint32_t off = min(static_cast<uint32_t>(i * 64 + lane), wn / 2 - 1) * 4u;  // wn is even
+            const v2u v = load_stream<NT>(reinterpret_cast<const v2u *>(vb + static_cast<uint32_t>(off * 2u)));
+            vv[2 * i] = v.x;
+            vv[2 * i + 1] = v.y;
+            d[i] = load_stream<NT>(reinterpret_cast<const uint32_t *>(db + off));
+        }
+#pragma unroll
+        for (int i = 0; i < LOADS; ++i) *reinterpret_cast<uint4 *>(my_lds + 2 * (i * 64 + lane)) = make_uint4(d[i] & 0xFFFFu, 0u, d[i] >> 16, 0u);
+    } else {
+        uint16_t d[LOADS];
+#pragma unroll
+        for (int i = 0; i < LOADS; ++i) {
+            const uint32_t off = min(static_cast<uint32_t>(i * 64 + lane), wn - 1) * 2u;
+            vv[i] = __float_as_uint(load_stream<NT>(reinterpret_cast<const float *>(vb + static_cast<uint32_t>(off * 2u))));
+            d[i] = load_stream<NT>(reinterpret_cast<const uint16_t *>(db + off));
+        }
+#pragma unroll
+        for (int i = 0; i < LOADS; ++i) my_lds[i * 64 + lane] = make_uint2(d[i], 0u);
+    }
+}
+
+template <bool NT, int G, int R>
+__device__ __forceinline__ void stage_packed_t(uint2 *my_lds, const float *__restrict__ val, const uint16_t *__restrict__ dcol, uint32_t wn, int lane,
+                                               uint32_t (&vv)[R]) {
+    constexpr bool PAIR = 64 / G >= 2;
+    constexpr int PER = PAIR ? 128 : 64, FULL = kWindowRecs<G> / PER;  // records per load of the wave, loads of a full window
+    if (wn <= PER) stage_packed_n<NT, PAIR, 1>(my_lds, val, dcol, wn, lane, vv);
+    else if (FULL > 2 && wn <= 2 * PER) stage_packed_n<NT, PAIR, 2>(my_lds, val, dcol, wn, lane, vv);
+    else stage_packed_n<NT, PAIR, FULL>(my_lds, val, dcol, wn, lane, vv);
+}
+
+template <int G, bool OFF32>
+__device__ __forceinline__ uint32_t stage_window_packed(const PlanView &p, uint2 *my_lds, uint32_t zb, uint32_t wz, uint32_t wn, uint2 cx,
+                                                        uint32_t t0, uint32_t nt, uint32_t my_beg, uint32_t carry, uint32_t row_bytes32, int lane) {
+    constexpr int W = kWindowRecs<G>, R = W / 64;
+    constexpr bool PAIR = 64 / G >= 2;
+    // everything below that depends on the lane alone (indices, LDS addresses, masks) is recomputed per window: hoisted out of the
+    // window loop it would stay in registers across the gather loop, which is where the kernel's register count is decided
+    asm volatile("" : "+v"(lane));
+    uint32_t vv[R];
+    if (p.rec_nt != 0) stage_packed_t<true, G>(my_lds, p.rec_val + wz, p.rec_dcol + wz, wn, lane, vv);  // wave-uniform
+    else stage_packed_t<false, G>(my_lds, p.rec_val + wz, p.rec_dcol + wz, wn, lane, vv);
+    // exceptions of the chunk that fall into this window (rare: the loop body runs for one chunk in a few)
+    for (uint32_t j = lane; j < cx.y; j += 64) {
+        const uint2 e = p.exc[cx.x + j];
+        const uint32_t at = zb + e.x - wz;  // position in the window, if below wn
+        if (at < wn) my_lds[at].x += e.y;
+    }
+    if (lane == 0) my_lds[0].x += carry;
+    // task starts: lane i holds t_beg[t0 + i] (i <= nt); an empty task starts where its successor does and owns no record
+    const uint32_t next_beg = __shfl_down(my_beg, 1);
+    const uint32_t at = my_beg - wz;
+    if (static_cast<uint32_t>(lane) < nt && next_beg != my_beg && at < wn) my_lds[at] = make_uint2(p.t_col0[t0 + lane], 1u);
+    __builtin_amdgcn_wave_barrier();
+    // the lane's R words, serially from 0
+    uint32_t w[R], fbits = 0;
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+        const uint2 s = my_lds[lane * R + i];
+        w[i] = s.x;
+        fbits |= s.y << i;  // 0 or 1; slots past what this window loaded hold old records: never read, whatever they scan to
+    }
+    fbits &= (1u << R) - 1u;
+    // every lane has read its flags: the values take their .y halves now, where the loads' layout puts them, and leave their registers
+    // to the scan.  The hardware completes a wave's LDS operations in order; the barrier keeps the compiler from moving a value write
+    // (another lane's slot, a provably different address for this thread) above a flag read.
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int i = 0; i < R; ++i) my_lds[PAIR ? 2 * ((i / 2) * 64 + lane) + (i & 1) : i * 64 + lane].y = vv[i];
+    uint32_t run = 0;
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+        run = ((fbits >> i) & 1u) ? w[i] : run + w[i];
+        w[i] = run;
+    }
+    // unsegmented inclusive scan of the lanes' results, then the part that belongs to the lane's open segment
+    uint32_t inc = run;
+#pragma unroll
+    for (int dlt = 1; dlt < 64; dlt <<= 1) {
+        const uint32_t up = __shfl_up(inc, dlt);
+        if (lane >= dlt) inc += up;
+    }
+    const uint32_t exc_sum = inc - run;  // E[lane]
+    const uint64_t below = __builtin_amdgcn_ballot_w64(fbits != 0) & ((uint64_t(1) << lane) - 1u);
+    const int q = below ? 63 - __builtin_clzll(below) : 0;
+    const uint32_t e_q = __shfl(exc_sum, q);
+    const uint32_t enter = below ? exc_sum - e_q : exc_sum;
+    uint32_t last = 0;
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+        const bool open = (fbits & ((2u << i) - 1u)) == 0;  // no segment start at or before word i in this lane
+        const uint32_t col = w[i] + (open ? enter : 0u);
+        my_lds[lane * R + i].x = OFF32 ? col * row_bytes32 : col;
+        last = col;
+    }
+    __builtin_amdgcn_wave_barrier();
+    return __builtin_amdgcn_readlane(last, 63);
+}
+
 // All the work of one chunk once its header {first task, #tasks, first record, end record} and its
 // task descriptors (lane i: t_beg[t0+i], t_dst[t0+i]) are in registers.
 template <int G, bool OFF32, int U>
 __device__ __forceinline__ void compute_chunk(const PlanView &p, uint4 hdr, uint32_t my_beg, uint32_t my_dst, uint2 my_aux,
-                                              uint32_t my_bd0, uint32_t my_bd1, uint2 *my_lds, const char *__restrict__ Bb,
+                                              uint32_t my_bd0, uint32_t my_bd1, uint2 cx, uint2 *my_lds, const char *__restrict__ Bb,
                                               float *__restrict__ C, int lane, int c0, bool col_ok, uint32_t tile, uint32_t ktiles) {
     constexpr int S = 64 / G;
     const int slot = lane / G;
@@ -307,9 +443,13 @@ __device__ __forceinline__ void compute_chunk(const PlanView &p, uint4 hdr, uint
     // (column 0 of the row would add a cache line per record to the last tile of a k that is not a multiple of 4G)
     const uint32_t lane_off = (col_ok ? c0 : c0 - (lane % G) * 4) * 4u;
     const uint64_t row_bytes = static_cast<uint64_t>(p.ldb) * 4u;
-    const uint2 *__restrict__ rec = p.rec;
 
     const uint32_t nt = hdr.y, zb = hdr.z, ze = hdr.w;
+    // A packed plan (wave-uniform): this chunk's records are values + 16-bit column differences, decoded by the staging step -- or, in a
+    // wide chunk (one with a bundle), 8-byte records that start at cx.x of what `rec` holds instead of at zb.
+    const bool packed_chunk = p.rec_packed != 0 && (cx.y & kChunkWide) == 0;
+    const uint2 *__restrict__ rec = p.rec_packed != 0 ? p.rec + cx.x - zb : p.rec;
+    uint32_t carry = 0;  // packed: the column the previous window ended on
 
     uint32_t ti = 0;                                          // current task
     uint32_t row_end = __builtin_amdgcn_readlane(my_beg, 1);  // where it ends in the record stream
@@ -343,12 +483,17 @@ __device__ __forceinline__ void compute_chunk(const PlanView &p, uint4 hdr, uint
                 const float4 r = reduce_full<G>(acc);
                 float *prow = p.partial + static_cast<uint64_t>(dst & ~kPartialFlag) * k;  // uniform
                 if (slot == 0 && col_ok) {
+                    // the lane's first column (c0) again, from the lane id: offsets and addresses of this rare path are formed here and not
+                    // kept in registers across the gather loops
+                    int l = lane;
+                    asm volatile("" : "+v"(l));
+                    const int col = static_cast<int>(tile) * (4 * G) + (l % G) * 4;
                     if (p.fused_fixup) {
                         const auto prsrc = __builtin_amdgcn_make_buffer_rsrc(prow, 0, k * 4, 0x00020000);
                         const v4u pv = {__float_as_uint(r.x), __float_as_uint(r.y), __float_as_uint(r.z), __float_as_uint(r.w)};
-                        __builtin_amdgcn_raw_buffer_store_b128(pv, prsrc, c0 * 4, 0, 16 /* sc1 */);
+                        __builtin_amdgcn_raw_buffer_store_b128(pv, prsrc, col * 4, 0, 16 /* sc1 */);
                     } else {  // combined by spmm_fixup_kernel after this launch
-                        *reinterpret_cast<float4 *>(prow + c0) = r;
+                        *reinterpret_cast<float4 *>(prow + col) = r;
                     }
                 }
             } else {
@@ -367,7 +512,8 @@ __device__ __forceinline__ void compute_chunk(const PlanView &p, uint4 hdr, uint
     for (uint32_t wz = zb; wz < ze; wz += kWindowRecs<G>) {
         const uint32_t wn = min(static_cast<uint32_t>(kWindowRecs<G>), ze - wz);
         // stage this window's records: coalesced 512-B loads, one ds_write_b64 per lane and load
-        stage_window<G>(my_lds, rec, wz, wn, lane, p.rec_nt != 0);
+        if (packed_chunk) carry = stage_window_packed<G, OFF32>(p, my_lds, zb, wz, wn, cx, hdr.x, nt, my_beg, carry, static_cast<uint32_t>(row_bytes), lane);
+        else stage_window<G>(my_lds, rec, wz, wn, lane, p.rec_nt != 0);
         const uint32_t nsteps = wn / S;  // rows are padded to multiples of S
         const uint2 *lds_slot = my_lds + slot;
         uint32_t j = 0;
@@ -440,6 +586,9 @@ __device__ __forceinline__ void compute_chunk(const PlanView &p, uint4 hdr, uint
             if (take >= 0) {
                 const SplitRow sr = p.split[sidx];
                 if (col_ok) {
+                    int l = lane;  // c0 again, from the lane id (as in flush: nothing of this tail stays in registers across the gather loops)
+                    asm volatile("" : "+v"(l));
+                    const int c0 = static_cast<int>(tile) * (4 * G) + (l % G) * 4;
                     const float *base = p.partial + static_cast<uint64_t>(sr.first) * k + c0;
                     float4 s4 = {0.f, 0.f, 0.f, 0.f};
                     for (uint32_t j = 0; j < sr.count; j += 8) {
@@ -477,12 +626,12 @@ __device__ __forceinline__ void compute_chunk(const PlanView &p, uint4 hdr, uint
 // STAMP = true is the measuring twin of the product kernel (flex_plan_measure_imbalance; ≙ the reference's per-warp
 // %smid + clock() stamps, flex.cu:27-79): the same code plus, per wave, two reads of the 100 MHz constant clock and one
 // 24-byte record {start, end, XCC id << 32 | HW_ID}.  The product launches (flex_spmm) never use it.
-// amdgpu_waves_per_eu: the wide tiles (G >= 32, U = 8, 32-bit offsets) come out at 76 VGPRs = 6 waves per SIMD unless the
-// allocator is told that a seventh wave is worth a few moves (72 VGPRs, no scratch: checked with `make asm`); the narrow
-// tiles are at 8 waves per SIMD either way, and the variants that would spill under the hint (64-bit row addressing, the
-// FLEX_U=8 experiment) are left alone.
+// amdgpu_waves_per_eu: the register count is decided in the gather loop (U float4 + U records + the chunk's descriptors); the hint tells
+// the allocator what the next wave is worth, so that loop invariants of the staging step and of the rare flush paths are recomputed
+// instead of kept.  G <= 8: 8 waves per SIMD (64 VGPRs); G = 16: 7 asked, 8 reached (56-58 VGPRs); wide tiles (U = 8): 7 with 32-bit
+// offsets (72 VGPRs), 6 with 64-bit row addressing (76-78); all without scratch, checked with `make asm`.  The FLEX_U=8 experiment on the narrow tiles is left alone.
 template <int G, bool OFF32, int U, int WPB, bool STAMP = false>
-__global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(OFF32 && U == (G >= 32 ? 8 : 4) ? 7 : 4))) void spmm_flat_kernel(PlanView p, const float *__restrict__ B,
+__global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(U == (G >= 32 ? 8 : 4) ? (G >= 32 ? (OFF32 ? 7 : 6) : G >= 16 ? 7 : 8) : 4))) void spmm_flat_kernel(PlanView p, const float *__restrict__ B,
                                                              float *__restrict__ C) {
     __shared__ uint2 lds_rec[WPB][kWindowRecs<G>];
     const int lane = threadIdx.x & 63;
@@ -518,6 +667,9 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(OFF32 
     uint2 cb = make_uint2(0u, 0u);
     if constexpr (kTileHasBundles<G>)
         if (p.bd_rows != nullptr) cb = p.chunk_bd[chunk];  // uniform
+    // packed plans: the chunk's exception table {first, entries}, or {first wide record, kChunkWide}
+    uint2 cx = make_uint2(0u, 0u);
+    if (p.rec_packed != 0) cx = p.chunk_exc[chunk];  // uniform
     if (hdr.y == 0) return;  // an empty entry that pads this XCD's slice of the table (plan_build.cpp, build_chunk_table)
     const uint32_t my_beg = (static_cast<uint32_t>(lane) <= hdr.y) ? p.t_beg[hdr.x + lane] : 0u;
     const uint32_t my_dst = (static_cast<uint32_t>(lane) < hdr.y) ? p.t_dst[hdr.x + lane] : 0u;
@@ -529,7 +681,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(OFF32 
     }
     uint64_t stamp_t0 = 0;
     if constexpr (STAMP) stamp_t0 = __builtin_amdgcn_s_memrealtime();
-    compute_chunk<G, OFF32, U>(p, hdr, my_beg, my_dst, my_aux, my_bd0, my_bd1, lds_rec[wib], reinterpret_cast<const char *>(B), C, lane, c0, col_ok, tile, ktiles);
+    compute_chunk<G, OFF32, U>(p, hdr, my_beg, my_dst, my_aux, my_bd0, my_bd1, cx, lds_rec[wib], reinterpret_cast<const char *>(B), C, lane, c0, col_ok, tile, ktiles);
     if constexpr (STAMP) {
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // the wave's last stores have left
         const uint64_t stamp_t1 = __builtin_amdgcn_s_memrealtime();
@@ -557,8 +709,15 @@ __global__ __launch_bounds__(256) void spmm_generic_kernel(PlanView p, const flo
     if (w >= p.n_chunks) return;
     const int k = p.k;
     const int cb = blockIdx.y * 256 + lane;
-    const uint2 *__restrict__ rec = p.rec;
     const uint32_t t0 = p.chunk[w].x, t1 = t0 + p.chunk[w].y;
+    // A packed plan launched with operands that are not 16-byte aligned: a wide chunk's records start at cx.x of what `rec` holds;
+    // any other chunk is decoded record by record, every lane for itself (the exceptions are sorted by position, tasks run in order).
+    uint2 cx = make_uint2(0u, 0u);
+    if (p.rec_packed != 0 && t1 > t0) cx = p.chunk_exc[w];
+    const bool packed_chunk = p.rec_packed != 0 && (cx.y & kChunkWide) == 0;
+    const uint32_t cz = p.chunk[w].z;
+    const uint2 *__restrict__ rec = p.rec_packed != 0 ? p.rec + cx.x - cz : p.rec;
+    uint32_t ei = 0;  // packed: exceptions of the chunk consumed so far
     for (uint32_t t = t0; t < t1; ++t) {
         const uint32_t zb = p.t_beg[t], ze = p.t_beg[t + 1];
         const uint32_t dst = p.t_dst[t];
@@ -592,8 +751,17 @@ __global__ __launch_bounds__(256) void spmm_generic_kernel(PlanView p, const flo
             continue;
         }
         float acc[4] = {0.f, 0.f, 0.f, 0.f};
+        uint32_t col = packed_chunk ? p.t_col0[t] : 0u;
         for (uint32_t z = zb; z < ze; ++z) {
-            const uint2 r = rec[z];
+            uint2 r;
+            if (packed_chunk) {
+                uint32_t d = p.rec_dcol[z];  // 0 on the task's first record
+                if (ei < cx.y && p.exc[cx.x + ei].x == z - cz) d += p.exc[cx.x + ei++].y;
+                col += d;
+                r = make_uint2(OFF32 ? col * (static_cast<uint32_t>(p.ldb) * 4u) : col, __float_as_uint(p.rec_val[z]));
+            } else {
+                r = rec[z];
+            }
             const float v = as_f32(r.y);
             const float *brow = OFF32 ? reinterpret_cast<const float *>(reinterpret_cast<const char *>(B) + r.x)
                                       : B + static_cast<uint64_t>(r.x) * p.ldb;

@@ -203,7 +203,13 @@ typedef struct flex_plan_tuning {
                                 -- and then on the tiles of 4 or more slots per step: wider k runs the 16-lane tile instead of the
                                 32-lane one; plan_build.cpp, bundle_rule) */
     int32_t bundle_len;      /* ... rows of at most this many nonzeros are candidates (12 on the tiles of 8 or 16 slots per step, 16 on the 4-slot tile) */
-    int32_t reserved[5];     /* zero */
+    int32_t rec_pack;        /* the record stream at 6 bytes per record (value + 16-bit column difference) instead of 8: 1 on, 2 off
+                                (rule: on for launches of two or more column tiles whose stream is at least 32 MB, holds less than 5 % of
+                                its records in chunks with row bundles, which keep the 8-byte form, and needs fewer than one exception --
+                                a column difference beyond 16 bits, 8 bytes each -- per 16 records).  Never on 2-D plans, on plans with
+                                FLEX_PLAN_MUTABLE_VALUES or FLEX_PLAN_ATTENTION, or where k, ldb or ldc is no multiple of 4: flex_plan_get_tuning
+                                then reports 2.  C is bit for bit the same either way */
+    int32_t reserved[4];     /* zero */
 } flex_plan_tuning;
 
 typedef struct flex_plan_desc {
@@ -418,6 +424,21 @@ typedef struct flex_plan_info {
     int64_t bundle_rows;      /* rows inside them */
 } flex_plan_info;
 int flex_plan_get_info(const flex_plan *plan, flex_plan_info *out);
+
+/* The record stream of a plan and how it is stored on the device (flex_plan_tuning.rec_pack). */
+typedef struct flex_record_info {
+    int32_t packed;        /* 1: 6 bytes per record (value + 16-bit column difference), 0: 8 bytes */
+    int32_t reserved;      /* zero */
+    int64_t records;       /* = flex_plan_info.n_records */
+    int64_t wide_records;  /* packed: records of the chunks that keep the 8-byte form (those with a row bundle) */
+    int64_t exceptions;    /* packed: column differences that do not fit 16 bits (8 bytes each, listed per chunk) */
+    int64_t stream_bytes;  /* device bytes one column tile reads of the stream: values, differences, exceptions, wide records */
+} flex_record_info;
+int flex_plan_record_info(const flex_plan *plan, flex_record_info *out);
+/* Debug / test aid, synchronous: the record stream read back from the device image -- decoded, where it is packed, by the decoder of
+ * flex_plan_self_check -- as `records` pairs {B-row byte offset or column id, value bits} (2 x uint32 each) in stream order.
+ * records must equal flex_plan_info.n_records (else FLEX_ERR_INVALID); FLEX_ERR_FORMAT if a packed image does not decode. */
+int flex_plan_read_records(const flex_plan *plan, uint32_t *out, int64_t records);
 
 /* ≙ Mat::alpha_stats_collect (mat.cu:944-1065) and the B-Re1 / B-Re2 columns of run()'s table
  * (flex.cu:5217-5223): how much B-row reuse the schedule exposes to each level of the machine,
