@@ -18,6 +18,7 @@ from .binding import (  # noqa: F401
     FLEX_PLAN_TRANSPOSE,
     FLEX_PLAN_MUTABLE_VALUES,
     FLEX_PLAN_ATTENTION,
+    FLEX_PLAN_ATTENTION_BACKWARD,
     FlexError,
     HostCsr,
     Plan,

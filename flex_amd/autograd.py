@@ -3,7 +3,8 @@ and the GCN layer Out = A X W (flex_amd.axw.Axw.layer) differentiates through fl
 is differentiable in A's values as well: grad_v = SDDMM(grad_C, B) over A's pattern (flex_sddmm), and the values of every forward are
 set into the plans (flex_plan_set_values) without planning again.  The same two plans run a graph-attention layer end to end:
 scores by flex_sddmm as a forward op, their softmax over each row of A (flex_edge_softmax), and the SpMM with the result as A's values
-(SparseOperator.attention).  torch is imported lazily, as in binding.py."""
+(SparseOperator.attention).  fused_attention=True runs that forward as one launch (flex_attention), and fused_backward=True its backward as
+two (flex_attention_backward) instead of the chain of eight calls.  torch is imported lazily, as in binding.py."""
 from __future__ import annotations
 
 from . import binding
@@ -107,7 +108,8 @@ def _function():
     class _FusedAttention(torch.autograd.Function):
         """Out = A(alpha) V, alpha = softmax over each row of A of scale <Q[row], K[col]>, by flex_attention in one launch; alpha is
         written and kept only when a gradient is needed.  Backward: the chain of _SpMMValues, _EdgeSoftmax and _Sddmm from the kept
-        alpha, every plan set immediately before it is used."""
+        alpha, every plan set immediately before it is used -- or, on an operator made with fused_backward=True, the one call
+        flex_attention_backward for the gradients that are needed (it sets no plan's values)."""
 
         @staticmethod
         def forward(ctx, Q, K, V, op, scale):
@@ -123,6 +125,8 @@ def _function():
             Q, K, V, p = ctx.saved_tensors
             op = ctx.op
             g = grad_out.contiguous()
+            if op.fused_backward:
+                return (*op.plan.attention_backward(Q, K, V, p, g, ctx.scale, want=tuple(ctx.needs_input_grad[:3])), None, None)
             gQ = gK = gV = None
             if ctx.needs_input_grad[2]:
                 op.plan_t.set_values(p)
@@ -160,16 +164,22 @@ class SparseOperator:
     op.sddmm(Q, K) (scores per entry, Q [m, k], K [n, k]), op.edge_softmax(s, scale) (softmax over each row of A) and
     op.attention(Q, K, V, scale) = op(V, values=op.edge_softmax(op.sddmm(Q, K), scale)).
     fused_attention=True (with learn_values=True): the forward plan is also made with FLEX_PLAN_ATTENTION and op.attention runs its
-    forward as one launch (flex_attention); the backward is the same chain of calls."""
+    forward as one launch (flex_attention); the backward is the same chain of calls.
+    fused_backward=True (with fused_attention=True): the forward plan is also made with FLEX_PLAN_ATTENTION_BACKWARD and the backward of
+    op.attention is one call of two launches (flex_attention_backward) that sets no plan's values.  Off by default."""
 
     def __init__(self, a: binding.HostCsr, k: int, device: int = 0, order: int = binding.FLEX_ORDER_NATURAL, tuning: dict | None = None,
-                 learn_values: bool = False, fused_attention: bool = False):
+                 learn_values: bool = False, fused_attention: bool = False, fused_backward: bool = False):
         if fused_attention and not learn_values:
             raise NotImplementedError("fused_attention needs SparseOperator(..., learn_values=True): its backward sets the plans' values")
+        if fused_backward and not fused_attention:
+            raise NotImplementedError("fused_backward needs SparseOperator(..., fused_attention=True): it starts from the probabilities flex_attention keeps")
         self.m, self.n, self.k, self.nnz = a.m, a.n, k, a.nnz
         self.learn_values = learn_values
         self.fused_attention = fused_attention
-        self.plan = binding.Plan(a, k, device=device, order=order, tuning=tuning, mutable_values=learn_values, attention=fused_attention)
+        self.fused_backward = fused_backward
+        self.plan = binding.Plan(a, k, device=device, order=order, tuning=tuning, mutable_values=learn_values, attention=fused_attention,
+                                 attention_backward=fused_backward)
         self.plan_t = binding.Plan(a, k, device=device, order=order, tuning=tuning, transpose=True, mutable_values=learn_values)
         self._v0 = None
         if learn_values:

@@ -28,6 +28,7 @@ FLEX_PLAN_XCD_INTERLEAVE = 0x2000
 FLEX_PLAN_TRANSPOSE = 0x8000
 FLEX_PLAN_MUTABLE_VALUES = 0x10000
 FLEX_PLAN_ATTENTION = 0x40000
+FLEX_PLAN_ATTENTION_BACKWARD = 0x80000
 
 
 class FlexError(RuntimeError):
@@ -136,6 +137,11 @@ class _AttentionInfo(C.Structure):  # flex_attention_info
                                           "group_budget", "device_bytes")]
 
 
+class _AttentionBackwardInfo(C.Structure):  # flex_attention_backward_info
+    _fields_ = [(f, C.c_int64) for f in ("columns", "entries", "items", "groups", "columns_empty", "columns_slot", "columns_wave", "columns_block",
+                                          "group_budget", "device_bytes")]
+
+
 class _RecordInfo(C.Structure):  # flex_record_info
     _fields_ = [("packed", C.c_int32), ("reserved", C.c_int32)] + [(f, C.c_int64) for f in ("records", "wide_records", "exceptions", "stream_bytes")]
 
@@ -156,6 +162,7 @@ SYMBOLS = [
     "flex_order_deg", "flex_order_dfs", "flex_order_rabbit", "flex_shard_rows", "flex_synth_graph", "flex_synth_preset", "flex_strerror", "flex_last_hip_error",
     "flex_last_hip_error_string", "flex_abi_version", "flex_plan_set_values", "flex_sddmm",
     "flex_edge_softmax", "flex_edge_softmax_backward", "flex_plan_softmax_info", "flex_attention", "flex_plan_attention_info",
+    "flex_attention_backward", "flex_plan_attention_backward_info",
     "flex_plan_record_info", "flex_plan_read_records",
 ]
 
@@ -236,6 +243,7 @@ def lib():
         L.flex_abi_version.restype = i32
         L.flex_plan_softmax_info.argtypes = [vp, C.POINTER(_SoftmaxInfo)]
         L.flex_plan_attention_info.argtypes = [vp, C.POINTER(_AttentionInfo)]
+        L.flex_plan_attention_backward_info.argtypes = [vp, C.POINTER(_AttentionBackwardInfo)]
         L.flex_plan_record_info.argtypes = [vp, C.POINTER(_RecordInfo)]
         L.flex_plan_read_records.argtypes = [vp, vp, i64]
         _lib = L
@@ -243,7 +251,7 @@ def lib():
 
 
 def _values_fn(name: str):
-    """flex_plan_set_values / flex_sddmm / flex_edge_softmax / flex_edge_softmax_backward / flex_attention, looked up at first use and not when the
+    """flex_plan_set_values / flex_sddmm / flex_edge_softmax / flex_edge_softmax_backward / flex_attention / flex_attention_backward, looked up at first use and not when the
     library loads: a host-only build without the kernel files does not define them (tests/hostsim has stand-ins that only log which
     kernel the real ones would launch)."""
     L = lib()
@@ -251,7 +259,8 @@ def _values_fn(name: str):
     if f.argtypes is None:
         vp, fl = C.c_void_p, C.c_float
         f.argtypes = {"flex_plan_set_values": [vp, vp, vp], "flex_sddmm": [vp, vp, vp, vp, vp], "flex_edge_softmax": [vp, vp, fl, vp, vp],
-                      "flex_edge_softmax_backward": [vp, vp, vp, fl, vp, vp], "flex_attention": [vp, vp, vp, vp, fl, vp, vp, vp]}[name]
+                      "flex_edge_softmax_backward": [vp, vp, vp, fl, vp, vp], "flex_attention": [vp, vp, vp, vp, fl, vp, vp, vp],
+                      "flex_attention_backward": [vp, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp]}[name]
     return f
 
 
@@ -457,13 +466,14 @@ class Plan:
 
     def __init__(self, a: HostCsr, k: int, device: int = 0, order: int = FLEX_ORDER_NATURAL,
                  vo_mp=None, rows=None, col_map=None, ldb: int | None = None, ldc: int | None = None, tuning: dict | None = None,
-                 transpose: bool = False, mutable_values: bool = False, attention: bool = False):
+                 transpose: bool = False, mutable_values: bool = False, attention: bool = False, attention_backward: bool = False):
         """tuning: plan-time knobs as a dict of flex_plan_tuning fields (0 / absent = the planner's rule), e.g.
         {"lanes_per_nz": 16, "split_rows": 1, "cluster_no_refine": 1}.
         transpose: plan A^T (FLEX_PLAN_TRANSPOSE): C [a.n, k] = A^T B [a.m, k]; every other argument refers to A^T.
         mutable_values: FLEX_PLAN_MUTABLE_VALUES -- set_values() and sddmm() work on the plan; both index A's entries in a's CSR
         order, whatever the plan (transposed, mapped, a shard).
-        attention: FLEX_PLAN_ATTENTION -- attention() works on the plan (not with transpose, vo_mp or col_map)."""
+        attention: FLEX_PLAN_ATTENTION -- attention() works on the plan (not with transpose, vo_mp or col_map).
+        attention_backward: FLEX_PLAN_ATTENTION_BACKWARD -- attention_backward() works on the plan too (needs attention; not with rows)."""
         self._h = C.c_void_p()
         self.src_nnz = a.nnz
         if transpose:
@@ -472,6 +482,8 @@ class Plan:
             order |= FLEX_PLAN_MUTABLE_VALUES
         if attention:
             order |= FLEX_PLAN_ATTENTION
+        if attention_backward:
+            order |= FLEX_PLAN_ATTENTION_BACKWARD
         self._keep = (a, vo_mp, col_map)
         v = a.view()
         L = lib()
@@ -653,6 +665,40 @@ class Plan:
         self.attention_ptr(Q.data_ptr(), K.data_ptr(), V.data_ptr(), scale, out.data_ptr(), None if p is None else p.data_ptr(),
                            torch.cuda.current_stream(Q.device).cuda_stream)
         return out
+
+    def attention_backward_info(self) -> dict:
+        """flex_plan_attention_backward_info: the schedule of attention_backward()'s column launch (columns, entries, items, groups, columns by class)."""
+        i = _AttentionBackwardInfo()
+        _check(lib().flex_plan_attention_backward_info(self._h, C.byref(i)), "flex_plan_attention_backward_info")
+        return {f: getattr(i, f) for f, _ in _AttentionBackwardInfo._fields_}
+
+    def attention_backward_ptr(self, dQ_ptr: int, dK_ptr: int, dV_ptr: int, dP_ptr: int, dGradOut_ptr: int, scale: float, dGradQ_ptr: int | None,
+                               dGradK_ptr: int | None, dGradV_ptr: int | None, dWork_ptr: int, stream: int = 0):
+        _check(_values_fn("flex_attention_backward")(self._h, dQ_ptr, dK_ptr, dV_ptr, dP_ptr, dGradOut_ptr, scale, dGradQ_ptr, dGradK_ptr, dGradV_ptr,
+                                                     dWork_ptr, stream), "flex_attention_backward")
+
+    def attention_backward(self, Q, K, V, p, grad_out, scale: float, grad_q=None, grad_k=None, grad_v=None, work=None, want=(True, True, True)):
+        """flex_attention_backward: (gQ [m, k], gK [n, k], gV [n, k]) of attention()'s out from its p and grad_out [m, k], in two launches; an
+        output that `want` does not ask for is None and is not computed.  work (optional): a float32 cuda tensor [a.nnz], not p, that
+        receives the gradient in the scores whenever gQ or gK is wanted."""
+        import torch
+        i = self.info()
+        for t, rows in ((Q, i["m"]), (K, i["n"]), (V, i["n"]), (grad_out, i["m"])):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (rows, i["k"])
+        if work is None:
+            work = torch.empty(self.src_nnz, dtype=torch.float32, device=Q.device)
+        self._edge_vectors(p, work)
+        outs = []
+        for wanted, t, rows in zip(want, (grad_q, grad_k, grad_v), (i["m"], i["n"], i["n"])):
+            if wanted and t is None:  # every row is written, except by a plan without entries, which launches nothing
+                t = (torch.empty if i["nnz"] else torch.zeros)((rows, i["k"]), dtype=torch.float32, device=Q.device)
+            if wanted:
+                assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (rows, i["k"])
+            outs.append(t if wanted else None)
+        self.attention_backward_ptr(Q.data_ptr(), K.data_ptr(), V.data_ptr(), p.data_ptr(), grad_out.data_ptr(), scale,
+                                    *(None if t is None else t.data_ptr() for t in outs), work.data_ptr(),
+                                    torch.cuda.current_stream(Q.device).cuda_stream)
+        return tuple(outs)
 
     def destroy(self):
         if getattr(self, "_h", None) and self._h.value:

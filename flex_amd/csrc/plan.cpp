@@ -217,7 +217,7 @@ static int create_common(flex_plan **out, const flex_csr *hostA, bool all_rows, 
     if (ldb < k || ldc < k) return FLEX_ERR_INVALID;
     const unsigned order = flags & FLEX_ORDER_MASK;
     if (order > FLEX_ORDER_GORDER ||
-        (flags & ~(FLEX_ORDER_MASK | FLEX_PLAN_STATS | FLEX_PLAN_AUTOTUNE | FLEX_PLAN_XCD_INTERLEAVE | FLEX_PLAN_TRANSPOSE | FLEX_PLAN_MUTABLE_VALUES | FLEX_PLAN_ATTENTION)))
+        (flags & ~(FLEX_ORDER_MASK | FLEX_PLAN_STATS | FLEX_PLAN_AUTOTUNE | FLEX_PLAN_XCD_INTERLEAVE | FLEX_PLAN_TRANSPOSE | FLEX_PLAN_MUTABLE_VALUES | FLEX_PLAN_ATTENTION | FLEX_PLAN_ATTENTION_BACKWARD)))
         return FLEX_ERR_INVALID;
     const bool mut = (flags & FLEX_PLAN_MUTABLE_VALUES) != 0;
     if (mut) {  // every nonzero on the flat record stream: the dense-tile and hot-block routes keep values in layouts of their own
@@ -233,7 +233,11 @@ static int create_common(flex_plan **out, const flex_csr *hostA, bool all_rows, 
     const bool attn = (flags & FLEX_PLAN_ATTENTION) != 0;
     if (attn && (transposed || col_map || dst_map || tuning.rec_pack == 1)) return FLEX_ERR_UNSUPPORTED;
     if (attn) tuning.rec_pack = 2;
-    flags &= ~FLEX_PLAN_ATTENTION;  // the planner proper never sees it: the record stream is what it is without the flag
+    // the fused backward's column walk is over every entry of hostA: with a row range gK / gV would be partial sums
+    const bool attn_bwd = (flags & FLEX_PLAN_ATTENTION_BACKWARD) != 0;
+    if (attn_bwd && !attn) return FLEX_ERR_INVALID;
+    if (attn_bwd && !all_rows) return FLEX_ERR_UNSUPPORTED;
+    flags &= ~(FLEX_PLAN_ATTENTION | FLEX_PLAN_ATTENTION_BACKWARD);  // the planner proper never sees them: the record stream is what it is without the flags
     TransposedCsr at;
     if (transposed) {
         rc = transpose_csr(hostA, &at, mut);
@@ -284,7 +288,10 @@ static int create_common(flex_plan **out, const flex_csr *hostA, bool all_rows, 
         }
         if (rc == FLEX_OK && attn) {
             p->at_ent_fp = held_entries_fp(callerA, false, row_begin, row_end, nullptr);
-            rc = upload_attention_image(p.get(), callerA, row_begin, row_end);
+            if (attn_bwd)
+                for (int32_t r = 0; r < callerA->m; ++r)
+                    for (uint32_t e = callerA->rowPtr[r]; e < callerA->rowPtr[r + 1]; ++e) p->ab_fp += rowptr_fp(static_cast<uint32_t>(r), e);
+            rc = upload_attention_image(p.get(), callerA, row_begin, row_end, attn_bwd);
         }
     } catch (const std::bad_alloc &) {  // nothing crosses the C ABI as an exception
         rc = FLEX_ERR_NOMEM;
@@ -429,6 +436,13 @@ int flex_plan_softmax_info(const flex_plan *p, flex_softmax_info *o) {
     if (!p->sm_ok) return FLEX_ERR_UNSUPPORTED;
     *o = flex_softmax_info{p->sm_rows, p->sm_entries, static_cast<int64_t>(p->d_sm_item.size()), p->n_sm_groups, p->sm_class_rows[3],
                            p->sm_class_rows[kSmPacked], p->sm_class_rows[kSmWaveRow], p->sm_class_rows[kSmBlockRow], p->sm_group_budget, p->sm_bytes};
+    return FLEX_OK;
+}
+
+int flex_plan_attention_backward_info(const flex_plan *p, flex_attention_backward_info *o) {
+    if (!p || !o || !p->ab_ok) return FLEX_ERR_INVALID;
+    *o = flex_attention_backward_info{p->ab_cols, p->at_entries, static_cast<int64_t>(p->d_ab_item.size()), p->n_ab_groups, p->ab_class_cols[3],
+                                      p->ab_class_cols[kAtSlot], p->ab_class_cols[kAtWave], p->ab_class_cols[kAtBlock], p->ab_group_budget, p->ab_bytes};
     return FLEX_OK;
 }
 

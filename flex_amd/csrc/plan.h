@@ -169,6 +169,17 @@ struct flex_plan {
     int64_t at_rows = 0, at_entries = 0, at_bytes = 0;
     int64_t at_class_rows[4] = {0, 0, 0, 0};  // slot rows / wave rows / block rows / empty rows
     uint64_t at_fp = 0, at_ent_fp = 0;        // fingerprints of the row pointer slice and of the (entry, K / V row) pairs, taken from hostA (self-check)
+    // FLEX_PLAN_ATTENTION_BACKWARD: the column walk of flex_attention_backward (internal.h, kAtPass; attention_backward_kernels.hip),
+    // the second part of the attention image; empty / 0 on other plans
+    bool ab_ok = false;
+    flex::DeviceArray<uint32_t> d_ab_colptr;  // [ab_cols + 1] first entry of every column of hostA in the (column, then CSR) order
+    flex::DeviceArray<uint2> d_ab_ent;        // [at_entries] {row, entry index} of every entry, by column and within a column in CSR order
+    flex::DeviceArray<uint4> d_ab_item;       // as d_at_item over whole columns: {first position, entries, first column, columns}
+    flex::DeviceArray<uint32_t> d_ab_grp;     // [n_ab_groups + 1] first item of each wave's group
+    uint32_t n_ab_groups = 0, n_ab_wave_items = 0, n_ab_block_cols = 0, ab_group_budget = 0;
+    int64_t ab_cols = 0, ab_bytes = 0;
+    int64_t ab_class_cols[4] = {0, 0, 0, 0};  // slot columns / wave columns / block columns / empty columns
+    uint64_t ab_fp = 0;                       // fingerprint of the (row, entry) pairs, taken from hostA (self-check; the (entry, column) pairs: at_ent_fp)
 };
 
 namespace flex {
@@ -227,8 +238,9 @@ int build_plan(flex_plan *p, const flex_csr *A, int32_t r0, int32_t r1, const in
 // FLEX_PLAN_MUTABLE_VALUES: builds and uploads the edge softmax's walk over rows [r0, r1) of the row pointer `rowPtr` (hostA's)
 int upload_softmax_image(flex_plan *p, const uint32_t *rowPtr, int64_t r0, int64_t r1);
 
-// FLEX_PLAN_ATTENTION: builds and uploads the walk of flex_attention over rows [r0, r1) of A (hostA as the caller passed it)
-int upload_attention_image(flex_plan *p, const flex_csr *A, int64_t r0, int64_t r1);
+// FLEX_PLAN_ATTENTION: builds and uploads the walk of flex_attention over rows [r0, r1) of A (hostA as the caller passed it);
+// backward (FLEX_PLAN_ATTENTION_BACKWARD, every row of A only): the column walk of flex_attention_backward after it
+int upload_attention_image(flex_plan *p, const flex_csr *A, int64_t r0, int64_t r1, bool backward = false);
 
 // FLEX_PLAN_MUTABLE_VALUES: a term of the order-free fingerprint of the (entry, B row) pairs a plan holds (flex_plan_self_check)
 inline uint64_t entry_fp(uint32_t entry, uint32_t brow) {

@@ -1307,16 +1307,16 @@ int upload_softmax_image(flex_plan *p, const uint32_t *rowPtr, int64_t r0, int64
     return FLEX_ERR_NOMEM;
 }
 
-// The walk of flex_attention (internal.h, kAtPass): one sequential pass over the rows in their order, so the image depends on nothing
-// but the row pointer slice, the columns of its entries and k (through the slots of a wave) -- not on the host thread count.
-int upload_attention_image(flex_plan *p, const flex_csr *A, int64_t r0, int64_t r1) try {
-    const size_t rows = static_cast<size_t>(r1 - r0);
-    const uint32_t slots = 64u / static_cast<uint32_t>(sddmm_lanes(p->k));
-    std::vector<uint32_t> rp(A->rowPtr + r0, A->rowPtr + r1 + 1), grp;
-    const uint64_t entries = rp.back() - rp.front();
-    std::vector<uint32_t> src(entries ? A->col + rp.front() : nullptr, entries ? A->col + rp.back() : nullptr);
-    std::vector<uint4> item, block;
-    const uint32_t budget = attention_group_budget(entries + rows);
+// The work list of an attention walk (internal.h, kAtPass) over the `rows` lines of the pointer `rp` -- hostA's rows for flex_attention,
+// its columns for the column kernel of flex_attention_backward: one sequential pass over the lines in their order.
+struct AttentionWalk {
+    std::vector<uint4> item, block;  // wave items (slot items and wave lines, grouped) and the block lines
+    std::vector<uint32_t> grp;
+    int64_t by_class[4] = {0, 0, 0, 0};
+};
+static void build_attention_walk(const std::vector<uint32_t> &rp, size_t rows, uint32_t slots, uint32_t budget, AttentionWalk &w) {
+    std::vector<uint4> &item = w.item, &block = w.block;
+    std::vector<uint32_t> &grp = w.grp;
     uint64_t g_cost = 0;
     auto add_item = [&](uint32_t first, uint32_t cnt, uint32_t row, uint32_t n_rows) {
         const uint64_t cost = static_cast<uint64_t>(cnt) + n_rows;
@@ -1327,8 +1327,6 @@ int upload_attention_image(flex_plan *p, const flex_csr *A, int64_t r0, int64_t 
         item.push_back(make_uint4(first, cnt, row, n_rows));
         g_cost += cost;
     };
-    uint64_t fp = 0;
-    int64_t by_class[4] = {0, 0, 0, 0};
     uint32_t run_row = 0, run_rows = 0, run_cnt = 0;  // the slot item being filled: consecutive slot rows, empty ones included
     auto close_run = [&] {
         if (run_rows) add_item(rp[run_row], run_cnt, run_row, run_rows);
@@ -1336,9 +1334,8 @@ int upload_attention_image(flex_plan *p, const flex_csr *A, int64_t r0, int64_t 
     };
     for (size_t r = 0; r < rows; ++r) {
         const uint32_t first = rp[r], len = rp[r + 1] - rp[r];
-        fp += rowptr_fp(static_cast<uint32_t>(r), first);
         const int cls = len == 0 ? kAtSlot : attention_row_class(len);
-        ++by_class[len == 0 ? 3 : cls];
+        ++w.by_class[len == 0 ? 3 : cls];
         if (cls != kAtSlot) {
             close_run();
             (cls == kAtWave ? add_item(first, len, static_cast<uint32_t>(r), 1u) : block.push_back(make_uint4(first, len, static_cast<uint32_t>(r), 1u)));
@@ -1350,26 +1347,71 @@ int upload_attention_image(flex_plan *p, const flex_csr *A, int64_t r0, int64_t 
         ++run_rows;
     }
     close_run();
-    fp += rowptr_fp(static_cast<uint32_t>(rows), rp.back());
     grp.push_back(static_cast<uint32_t>(item.size()));
-    p->n_at_groups = static_cast<uint32_t>(grp.size() - 1);
-    p->n_at_wave_items = static_cast<uint32_t>(item.size());
-    p->n_at_block_rows = static_cast<uint32_t>(block.size());
-    item.insert(item.end(), block.begin(), block.end());
+}
+
+// The walk of flex_attention (internal.h, kAtPass): one sequential pass over the rows in their order, so the image depends on nothing
+// but the row pointer slice, the columns of its entries and k (through the slots of a wave) -- not on the host thread count.
+// backward: the second part, the column walk of flex_attention_backward -- one sequential, stable counting sort of the entries by
+// column (within a column they stay in CSR order: the kernel's fixed order of summation), then the same work list over whole columns.
+int upload_attention_image(flex_plan *p, const flex_csr *A, int64_t r0, int64_t r1, bool backward) try {
+    const size_t rows = static_cast<size_t>(r1 - r0);
+    const uint32_t slots = 64u / static_cast<uint32_t>(sddmm_lanes(p->k));
+    std::vector<uint32_t> rp(A->rowPtr + r0, A->rowPtr + r1 + 1);
+    const uint64_t entries = rp.back() - rp.front();
+    std::vector<uint32_t> src(entries ? A->col + rp.front() : nullptr, entries ? A->col + rp.back() : nullptr);
+    const uint32_t budget = attention_group_budget(entries + rows);
+    AttentionWalk w;
+    build_attention_walk(rp, rows, slots, budget, w);
+    uint64_t fp = 0;
+    for (size_t r = 0; r <= rows; ++r) fp += rowptr_fp(static_cast<uint32_t>(r), rp[r]);
+    p->n_at_groups = static_cast<uint32_t>(w.grp.size() - 1);
+    p->n_at_wave_items = static_cast<uint32_t>(w.item.size());
+    p->n_at_block_rows = static_cast<uint32_t>(w.block.size());
+    w.item.insert(w.item.end(), w.block.begin(), w.block.end());
     p->at_group_budget = budget;
     p->at_rows = static_cast<int64_t>(rows);
     p->at_entries = static_cast<int64_t>(entries);
     p->at_first_entry = rp.front();
     p->at_fp = fp;
-    for (int c = 0; c < 4; ++c) p->at_class_rows[c] = by_class[c];
+    for (int c = 0; c < 4; ++c) p->at_class_rows[c] = w.by_class[c];
     const int64_t before = p->device_bytes;
     int rc;
     if ((rc = p->d_at_rowptr.upload(rp, &p->device_bytes))) return rc;
     if ((rc = p->d_at_src.upload(src, &p->device_bytes))) return rc;
-    if ((rc = p->d_at_item.upload(item, &p->device_bytes))) return rc;
-    if ((rc = p->d_at_grp.upload(grp, &p->device_bytes))) return rc;
+    if ((rc = p->d_at_item.upload(w.item, &p->device_bytes))) return rc;
+    if ((rc = p->d_at_grp.upload(w.grp, &p->device_bytes))) return rc;
     p->at_bytes = p->device_bytes - before;
     p->at_ok = true;
+    if (!backward) return FLEX_OK;
+    if (r0 != 0 || r1 != A->m) return FLEX_ERR_UNSUPPORTED;  // a shard's gK / gV would be partial sums
+    const size_t cols = static_cast<size_t>(A->n);
+    std::vector<uint32_t> cp(cols + 1, 0u);
+    for (uint64_t e = 0; e < entries; ++e) ++cp[src[e] + 1];
+    for (size_t c = 0; c < cols; ++c) cp[c + 1] += cp[c];
+    std::vector<uint2> ent(entries);
+    {
+        std::vector<uint32_t> at(cp.begin(), cp.end() - 1);
+        for (size_t r = 0; r < rows; ++r)
+            for (uint32_t e = rp[r]; e < rp[r + 1]; ++e) ent[at[src[e]]++] = make_uint2(static_cast<uint32_t>(r), e);
+    }
+    const uint32_t cbudget = attention_group_budget(entries + cols);
+    AttentionWalk cw;
+    build_attention_walk(cp, cols, slots, cbudget, cw);
+    p->n_ab_groups = static_cast<uint32_t>(cw.grp.size() - 1);
+    p->n_ab_wave_items = static_cast<uint32_t>(cw.item.size());
+    p->n_ab_block_cols = static_cast<uint32_t>(cw.block.size());
+    cw.item.insert(cw.item.end(), cw.block.begin(), cw.block.end());
+    p->ab_group_budget = cbudget;
+    p->ab_cols = static_cast<int64_t>(cols);
+    for (int c = 0; c < 4; ++c) p->ab_class_cols[c] = cw.by_class[c];
+    const int64_t before_ab = p->device_bytes;
+    if ((rc = p->d_ab_colptr.upload(cp, &p->device_bytes))) return rc;
+    if ((rc = p->d_ab_ent.upload(ent, &p->device_bytes))) return rc;
+    if ((rc = p->d_ab_item.upload(cw.item, &p->device_bytes))) return rc;
+    if ((rc = p->d_ab_grp.upload(cw.grp, &p->device_bytes))) return rc;
+    p->ab_bytes = p->device_bytes - before_ab;
+    p->ab_ok = true;
     return FLEX_OK;
 } catch (const std::bad_alloc &) {
     return FLEX_ERR_NOMEM;

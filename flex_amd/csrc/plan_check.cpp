@@ -417,6 +417,81 @@ static int check_attention_image(const flex_plan *p) {
     return FLEX_OK;
 }
 
+// FLEX_PLAN_ATTENTION_BACKWARD: the column walk of flex_attention_backward read back, against the first part's read-back columns (which
+// check_attention_image has compared with hostA).  The column pointer is monotone and ends at the entry count; every entry index occurs
+// once, under the column the first part holds for it and with a row whose range of the row pointer contains it -- and the (row, entry)
+// pairs have the fingerprint create_common took from hostA, the (entry, column) pairs the first part's; within a column the entries
+// ascend (the kernel's order of summation is hostA's); every column, empty ones included, lies in exactly one item of the class its
+// length dictates, and the groups tile the wave items in order within the budget -- as for the rows.
+static int check_attention_backward_image(const flex_plan *p) {
+    std::vector<uint32_t> rp, src, cp, grp;
+    std::vector<uint2> ent;
+    std::vector<uint4> item;
+    if (!read_back(p->d_at_rowptr, rp) || !read_back(p->d_at_src, src) || !read_back(p->d_ab_colptr, cp) || !read_back(p->d_ab_ent, ent) ||
+        !read_back(p->d_ab_item, item) || !read_back(p->d_ab_grp, grp))
+        return FLEX_ERR_HIP;
+    const size_t cols = static_cast<size_t>(p->ab_cols), rows = static_cast<size_t>(p->at_rows);
+    if (p->ab_cols != p->n || p->at_first_entry != 0 || cp.size() != cols + 1 || ent.size() != src.size() || rp.size() != rows + 1 ||
+        grp.size() != p->n_ab_groups + size_t(1) || item.size() != size_t(p->n_ab_wave_items) + p->n_ab_block_cols)
+        return FLEX_ERR_FORMAT;
+    if (cp.front() != 0 || cp.back() != ent.size()) return FLEX_ERR_FORMAT;
+    for (size_t c = 0; c < cols; ++c)
+        if (cp[c] > cp[c + 1]) return FLEX_ERR_FORMAT;
+    std::vector<uint8_t> seen(ent.size(), 0);
+    uint64_t fp = 0, efp = 0;
+    for (size_t c = 0; c < cols; ++c) {
+        for (uint32_t i = cp[c]; i < cp[c + 1]; ++i) {
+            const uint2 re = ent[i];
+            if (re.y >= ent.size() || re.x >= rows || seen[re.y]++) return FLEX_ERR_FORMAT;
+            if (src[re.y] != c || re.y < rp[re.x] || re.y >= rp[re.x + 1]) return FLEX_ERR_FORMAT;
+            if (i > cp[c] && ent[i - 1].y >= re.y) return FLEX_ERR_FORMAT;
+            fp += rowptr_fp(re.x, re.y);
+            efp += entry_fp(re.y, static_cast<uint32_t>(c));
+        }
+    }
+    if (fp != p->ab_fp || efp != p->at_ent_fp) return FLEX_ERR_FORMAT;
+    if (p->ab_group_budget != attention_group_budget(static_cast<uint64_t>(p->at_entries) + cols)) return FLEX_ERR_FORMAT;
+    const uint32_t slots = 64u / static_cast<uint32_t>(sddmm_lanes(p->k));
+    std::vector<uint8_t> col_seen(cols, 0);
+    int64_t covered = 0, by_class[4] = {0, 0, 0, 0};
+    for (size_t i = 0; i < item.size(); ++i) {
+        const uint4 &it = item[i];
+        const bool is_block = i >= p->n_ab_wave_items;
+        if (it.w == 0 || static_cast<uint64_t>(it.z) + it.w > cols) return FLEX_ERR_FORMAT;
+        if (cp[it.z] != it.x || static_cast<uint64_t>(it.x) + it.y != cp[it.z + it.w]) return FLEX_ERR_FORMAT;  // whole consecutive columns
+        const bool slot_item = !is_block && (it.w > 1 || it.y <= kAtSlotRow);  // the kernel's own test
+        if (slot_item ? it.w > slots : it.w != 1) return FLEX_ERR_FORMAT;
+        for (uint32_t c = it.z; c < it.z + it.w; ++c) {
+            if (col_seen[c]++) return FLEX_ERR_FORMAT;
+            const uint32_t len = cp[c + 1] - cp[c];
+            if (len == 0) {
+                if (!slot_item) return FLEX_ERR_FORMAT;
+                ++by_class[3];
+                continue;
+            }
+            const int cls = attention_row_class(len);
+            if (cls != (slot_item ? kAtSlot : is_block ? kAtBlock : kAtWave)) return FLEX_ERR_FORMAT;
+            ++by_class[cls];
+        }
+        covered += it.y;
+    }
+    if (covered != p->at_entries) return FLEX_ERR_FORMAT;
+    for (size_t c = 0; c < cols; ++c)
+        if (col_seen[c] != 1) return FLEX_ERR_FORMAT;
+    for (int c = 0; c < 4; ++c)
+        if (by_class[c] != p->ab_class_cols[c]) return FLEX_ERR_FORMAT;
+    for (size_t i = 1; i < item.size(); ++i)
+        if (i != p->n_ab_wave_items && item[i].z < item[i - 1].z + item[i - 1].w) return FLEX_ERR_FORMAT;
+    if (grp.front() != 0 || grp.back() != p->n_ab_wave_items) return FLEX_ERR_FORMAT;
+    for (uint32_t g = 0; g < p->n_ab_groups; ++g) {
+        if (grp[g] >= grp[g + 1]) return FLEX_ERR_FORMAT;
+        uint64_t cost = 0;
+        for (uint32_t i = grp[g]; i < grp[g + 1]; ++i) cost += static_cast<uint64_t>(item[i].y) + item[i].w;
+        if (grp[g + 1] - grp[g] > 1 && cost > p->ab_group_budget) return FLEX_ERR_FORMAT;
+    }
+    return FLEX_OK;
+}
+
 // ≙ the reference's tiler round-trip (mat.cu:905-940: every entry of the pillar format exists exactly once,
 // the queues are contiguous): read the plan's DEVICE image back and check that it is a partition --
 // chunks tile the tasks, tasks tile the records, every record names a valid B row, every C row is written by
@@ -659,7 +734,8 @@ int flex_plan_self_check(const flex_plan *p) try {
         if (rc) return rc;
     }
     if (p->at_ok) {
-        const int rc = check_attention_image(p);
+        int rc = check_attention_image(p);
+        if (rc == FLEX_OK && p->ab_ok) rc = check_attention_backward_image(p);
         if (rc) return rc;
     }
     return FLEX_OK;

@@ -26,6 +26,7 @@ extern "C" {
 
 #define FLEX_ABI_VERSION 3 /* 3 also covers the purely additive FLEX_PLAN_MUTABLE_VALUES, flex_plan_set_values, flex_sddmm and the edge softmax (no struct grew),
                               the equally additive FLEX_PLAN_ATTENTION, flex_attention and flex_plan_attention_info (a new flag, two new calls, one new struct),
+                              the equally additive FLEX_PLAN_ATTENTION_BACKWARD, flex_attention_backward and flex_plan_attention_backward_info (the same again),
                               and the retired flex_plan_tuning.block_ablate, which keeps its place as block_ablate_retired and must be zero.
                               3: plan-time knobs leave the environment for the struct flex_plan_tuning, flex_plan_desc.tuning, flex_plan_get_tuning,
                               flex_order_cluster_ex, flex_set_host_threads; split rows are summed by a second launch by default.
@@ -107,6 +108,15 @@ typedef struct flex_plan flex_plan;
                                        the transposed plan stays the gradient's tool).  Extra device memory, counted in
                                        flex_plan_info.device_bytes and reported by flex_plan_attention_info: 4 bytes per row and per entry of the
                                        plan's rows, 16 per work item, 4 per wave group.  Without the flag nothing is uploaded for it */
+
+#define FLEX_PLAN_ATTENTION_BACKWARD 0x80000u /* (0x20000u is taken by flex_axw.h) the plan can also run the fused attention backward
+                                       (flex_attention_backward below).  Requires FLEX_PLAN_ATTENTION (FLEX_ERR_INVALID without it) and is
+                                       independent of FLEX_PLAN_MUTABLE_VALUES.  FLEX_ERR_UNSUPPORTED wherever FLEX_PLAN_ATTENTION is, and with
+                                       FLEX_PLAN_ROW_RANGE or flex_plan_create_rows (a shard's gradients in K and V would be partial sums).
+                                       Extra device memory, counted in flex_plan_info.device_bytes and reported by
+                                       flex_plan_attention_backward_info: hostA's entries sorted by column -- 4 bytes per column, 8 per entry
+                                       ({row, entry index}), 16 per work item, 4 per wave group.  Without the flag a plan uploads exactly what
+                                       it uploads with FLEX_PLAN_ATTENTION alone */
 
 /* ≙ Mat::Mat + csr2_DiagTiling + alpha_transfer (mat.cu:7-31, 680-942, 268-293):
  * builds the row-panel plan for `hostA` and uploads it to `device`.  The reference's
@@ -390,6 +400,68 @@ typedef struct flex_attention_info {
     int64_t device_bytes; /* device memory of the image: 4 per row, 4 per entry, 16 per item, 4 per group */
 } flex_attention_info;
 int flex_plan_attention_info(const flex_plan *plan, flex_attention_info *out);
+
+/* Fused attention backward (FLEX_PLAN_ATTENTION_BACKWARD plans only; FLEX_ERR_INVALID on any other plan): the gradients of flex_attention's
+ * Out in Q, K and V from the probabilities it kept, in TWO launches, in place of the chain of three flex_plan_set_values, three flex_spmm
+ * (two on a transposed plan), flex_sddmm and flex_edge_softmax_backward.  No reference counterpart.  Entries e of row r in hostA's CSR order,
+ * src(e) = hostA->col[e], g = dGradOut (Out's shape and stride ldc), p = the dP that flex_attention wrote:
+ *     da_e    = <g[r], V[src(e)]>                       (over the k columns)
+ *     delta_r = sum_j p_j da_j                          (over the row's entries)
+ *     ds_e    = scale p_e (da_e - delta_r)              (flex_edge_softmax_backward's formula)
+ *     gQ[r]   = sum_{e in row r}      ds_e K[src(e)]
+ *     gK[c]   = sum_{e: src(e) == c}  ds_e Q[row(e)]
+ *     gV[c]   = sum_{e: src(e) == c}  p_e  g[row(e)]
+ * No special cases, as in flex_edge_softmax_backward: the formulas in fp32 under IEEE.  A NaN row of p gives a NaN row of ds and of gQ and
+ * NaN in the gK and gV rows of the columns it touches; a masked entry (p = +0) still multiplies (0 x inf = NaN).  No column at or past k
+ * is read.  dWork: hostA->nnz floats in hostA's CSR order; on return it holds ds, the gradient in the scores, whenever dGradQ or dGradK
+ * was asked for.  It must not alias dP (FLEX_ERR_INVALID where the two pointers are equal; any other overlap is the caller's error).
+ * Each of dGradQ, dGradK, dGradV may be NULL: that output is not written, a launch whose outputs are all NULL is skipped, and an output
+ * has the same bits whichever others are asked for.  gQ has Out's shape and stride (ldc), gK and gV have K's and V's (ldb).  Rows of gQ
+ * without entries, and rows of gK / gV whose column has no entry, are written as +0.  The checks are flex_attention's: scale finite and
+ * > 0 (else FLEX_ERR_INVALID); a plan without entries: FLEX_OK, no launch, nothing written; NULL Q, K, V, P, GradOut or Work:
+ * FLEX_ERR_INVALID; k <= 1024 (wider: FLEX_ERR_UNSUPPORTED).  Operands that are not 16-byte aligned, or k, ldb or ldc not a multiple of
+ * 4, run a generic instantiation: correct, slower.  Asynchronous on `stream`, no allocation, no host synchronisation (safe to capture in
+ * a hipGraph), no atomics, fixed reduction order: bit-identical run to run.  The first launch walks the rows as flex_attention does
+ * (every entry gathers its V row once and its K row once) and writes ds and gQ; the second walks hostA's columns (entries of a column in
+ * CSR order) and writes gK and gV.  No row and no column is split over workgroups: one of millions of entries is correct and slow.
+ *
+ * Accuracy, against float64 on the SAME fp32 Q, K, V, p and g (as for flex_edge_softmax_backward).  u = 2^-24, gamma(n) = n u / (1 - n u),
+ * n_r = entries of the row, n_c = entries of the column, a = 3, b = 0:
+ *   dda_e    = gamma(k) sum_j |g V| + k 2^-149                                             (flex_sddmm's bound)
+ *   dds_e    = gamma(n_r + a) scale p_e (|da_e| + sum_j |p_j da_j|) + scale p_e (dda_e + sum_j p_j dda_j) + max(1, scale) n_r 2^-149
+ *   |gQ - gQ64| <= sum_{e in r} (gamma(n_r + b) |ds_e| + dds_e) |K[src]| + 2^-126
+ *   |gK - gK64| <= sum_{e in c} (gamma(n_c + b) |ds_e| + dds_e) |Q[row]| + 2^-126
+ *   |gV - gV64| <= sum_{e in c}  gamma(n_c + b) p_e |g[row]|            + 2^-126
+ * Derivation.  da is the SDDMM's reduction (per lane a chain of fmas over its columns, a tree over the lanes of the slot, depth <= k).
+ * delta: every slot adds its terms by delta = fma(p_j, da_j, delta) -- the product is not rounded, one rounding per addition -- and the
+ * partial sums of the slots of a wave (at most 4 butterfly steps) and of the waves of a workgroup (3 additions) are added plainly: a tree
+ * of depth <= n_r for every class of row (a slot row is a chain of exactly n_r; a wave row has n_r >= 33 and a slot of it at most
+ * 4 ceil(n_r / (4 slots)) additions and 4 merges; a block row has n_r >= 513), so delta carries gamma(n_r) sum_j |p_j da_j| and the
+ * da's own errors weighted by p.  ds = fl(fl(scale p_e) fl(da_e - delta)): one subtraction and two products, a = 3 -- one fewer than
+ * flex_edge_softmax_backward, whose products p_j g_j are rounded.  Products below 2^-126 round as subnormals: the n_r 2^-149 term.
+ * gQ, gK and gV add their terms by fma on each lane's own columns (no reduction across lanes) in a chain per slot, then the same
+ * merges: depth <= n_r (n_c), the first fma into +0 being the rounding of the product, and no rounding besides: b = 0.  The ds that
+ * enters gQ and gK is the computed fp32 one: dds.  gV takes p and g as given: a lone entry's term is rounded once, so err / bound can
+ * come close to 1 there (|fl(x) - x| <= u |x| against gamma(1) |x|) -- tightness of the bound, not a fault.  First order, as the bounds above. */
+int flex_attention_backward(const flex_plan *plan, const float *dQ, const float *dK, const float *dV, const float *dP,
+                            const float *dGradOut, float scale, float *dGradQ, float *dGradK, float *dGradV, float *dWork,
+                            flex_stream_t stream);
+
+/* The schedule of flex_attention_backward's second launch (host side; its first launch walks flex_attention_info's items).
+ * FLEX_ERR_INVALID on a plan without FLEX_PLAN_ATTENTION_BACKWARD. */
+typedef struct flex_attention_backward_info {
+    int64_t columns;       /* columns of hostA: each writes one row of gK and of gV */
+    int64_t entries;       /* hostA's entries */
+    int64_t items;         /* work items: runs of slot columns (one per slot of a wave) + wave columns + block columns */
+    int64_t groups;        /* wave groups: one wave each, four to a workgroup (block columns are workgroups of their own) */
+    int64_t columns_empty; /* columns without entries: they ride in the slot items and write +0 */
+    int64_t columns_slot;  /* columns of at most 32 entries (flex_attention_info's classes, by the column's entry count) */
+    int64_t columns_wave;  /* columns of at most 512 entries */
+    int64_t columns_block; /* longer columns */
+    int64_t group_budget;  /* a group of more than one item costs at most this much (an item costs its entries + its columns) */
+    int64_t device_bytes;  /* device memory of the second part of the image: 4 per column, 8 per entry, 16 per item, 4 per group */
+} flex_attention_backward_info;
+int flex_plan_attention_backward_info(const flex_plan *plan, flex_attention_backward_info *out);
 
 /* ≙ alpha_freeMatGPU (mat.cuh:184-193). */
 int flex_plan_destroy(flex_plan *plan);

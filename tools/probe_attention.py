@@ -13,7 +13,11 @@ flex_edge_softmax_backward and a whole attention step.  Writes profiles/attentio
    flex_edge_softmax, flex_plan_set_values, flex_spmm) on the same operator, k = 32 and 128: one process, the two alternating round by
    round, best of 3 rounds after warm-up and the spread over the rounds; the image's bytes per nonzero and the step's extra memory.
    --fused: only this part (and the copy rate).
-Usage: probe_attention.py [--out FILE] [--fused] [graph ...]   (default: pubmed.csv flickr reddit soc-sign-epinions)"""
+5. The fused backward (flex_attention_backward, FLEX_PLAN_ATTENTION_BACKWARD), same graphs, k and protocol: the backward alone -- the
+   chain of eight engine calls on the same operator against the one call, from the same kept alpha -- and the whole step (forward +
+   backward through autograd) of fused_attention=True against fused_attention=True, fused_backward=True; the second part of the image
+   in bytes per nonzero.  --backward: only this part (and the copy rate).
+Usage: probe_attention.py [--out FILE] [--fused | --backward] [graph ...]   (default: pubmed.csv flickr reddit soc-sign-epinions)"""
 import ctypes as C
 import os
 import subprocess
@@ -131,13 +135,62 @@ def probe_fused(name, a):
         del op, plan
 
 
+def probe_backward(name, a):
+    gen = torch.Generator(device="cuda").manual_seed(3)
+    for k in (32, 128):
+        chain = flex_amd.SparseOperator(a, k, learn_values=True, fused_attention=True)
+        fused = flex_amd.SparseOperator(a, k, learn_values=True, fused_attention=True, fused_backward=True)
+        i = fused.plan.attention_backward_info()
+        Q, K, V = (torch.rand((r, k), device="cuda", generator=gen) * 2 - 1 for r in (a.m, a.n, a.n))
+        g = torch.rand((a.m, k), device="cuda", generator=gen) * 2 - 1
+        scale = k ** -0.5
+        alpha = torch.empty(a.nnz, device="cuda")
+        fused.plan.attention(Q, K, V, scale, p=alpha)
+        gq, gk, gv = torch.empty((a.m, k), device="cuda"), torch.empty((a.n, k), device="cuda"), torch.empty((a.n, k), device="cuda")
+        da, gs = torch.empty(a.nnz, device="cuda"), torch.empty(a.nnz, device="cuda")
+
+        def eight_calls():  # _FusedAttention.backward without fused_backward
+            chain.plan_t.set_values(alpha)
+            chain.plan_t(g, out=gv)
+            chain.plan.sddmm(g, V, out=da)
+            chain.plan.edge_softmax_backward(alpha, da, scale, out=gs)
+            chain.plan.set_values(gs)
+            chain.plan(K, out=gq)
+            chain.plan_t.set_values(gs)
+            chain.plan_t(Q, out=gk)
+
+        Qg, Kg, Vg = (x.clone().requires_grad_() for x in (Q, K, V))
+
+        def step(op):
+            for x in (Qg, Kg, Vg):
+                x.grad = None
+            op.attention(Qg, Kg, Vg, scale).backward(g)
+
+        fns = {"eight calls": eight_calls,
+               "fused backward": lambda: fused.plan.attention_backward(Q, K, V, alpha, g, scale, grad_q=gq, grad_k=gk, grad_v=gv, work=gs),
+               "step, chain backward": lambda: step(chain), "step, fused backward": lambda: step(fused)}
+        n = max(3, min(100, int(1e8 / max(1, a.nnz * k))))
+        rounds = {key: [] for key in fns}
+        for _ in range(3):  # alternating: every round times each contender once
+            for key, fn in fns.items():
+                rounds[key].append(best_us(fn, n, rounds=1))
+        best = {key: min(v) for key, v in rounds.items()}
+        spread = {key: 100 * (max(v) - min(v)) / min(v) for key, v in rounds.items()}
+        say(f"{name} k={k} backward (columns: slot {i['columns_slot']} wave {i['columns_wave']} block {i['columns_block']} empty {i['columns_empty']}, {i['items']} items, "
+            f"{i['groups']} groups of cost <= {i['group_budget']}, second part of the image {i['device_bytes'] / max(1, a.nnz):.2f} B/nnz): "
+            + "  ".join(f"{key} {best[key]:.1f} us (+{spread[key]:.0f} % over 3 rounds)" for key in fns)
+            + f"  eight calls / fused backward {best['eight calls'] / best['fused backward']:.2f}x"
+            + f"  step / step with the fused backward {best['step, chain backward'] / best['step, fused backward']:.2f}x")
+        del chain, fused
+
+
 def main():
     args = sys.argv[1:]
     out = os.path.join(ROOT, "profiles", "attention_probe.txt")
     if args[:1] == ["--out"]:
         out, args = args[1], args[2:]
-    fused_only = args[:1] == ["--fused"]
-    if fused_only:
+    fused_only, backward_only = args[:1] == ["--fused"], args[:1] == ["--backward"]
+    if fused_only or backward_only:
         args = args[1:]
     else:
         exp_error()
@@ -145,9 +198,12 @@ def main():
     say(f"flex_hbm_probe: read {hbm['read_GBps']:.0f} GB/s, copy {hbm['copy_GBps']:.0f} GB/s")
     for name in args or ["pubmed.csv", "flickr", "reddit", "soc-sign-epinions"]:
         a = load(name)
-        if not fused_only:
+        if not fused_only and not backward_only:
             probe(name, a, hbm["copy_GBps"])
-        probe_fused(name, a)
+        if not backward_only:
+            probe_fused(name, a)
+        if not fused_only:
+            probe_backward(name, a)
     with open(out, "w") as f:
         f.write("\n".join(LINES) + "\n")
 
