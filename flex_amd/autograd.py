@@ -4,7 +4,8 @@ is differentiable in A's values as well: grad_v = SDDMM(grad_C, B) over A's patt
 set into the plans (flex_plan_set_values) without planning again.  The same two plans run a graph-attention layer end to end:
 scores by flex_sddmm as a forward op, their softmax over each row of A (flex_edge_softmax), and the SpMM with the result as A's values
 (SparseOperator.attention).  fused_attention=True runs that forward as one launch (flex_attention), and fused_backward=True its backward as
-two (flex_attention_backward) instead of the chain of eight calls.  torch is imported lazily, as in binding.py."""
+two (flex_attention_backward) instead of the chain of eight calls; with both, attention(..., heads=H) runs H heads in the same three
+launches (flex_attention_heads, flex_attention_heads_backward).  torch is imported lazily, as in binding.py."""
 from __future__ import annotations
 
 from . import binding
@@ -141,14 +142,34 @@ def _function():
                     gK = op.plan_t(Q)
             return gQ, gK, gV, None, None
 
-    return _SpMM, _AxwLayer, _SpMMValues, _Sddmm, _EdgeSoftmax, _FusedAttention
+    class _FusedAttentionHeads(torch.autograd.Function):
+        """_FusedAttention over `heads` heads of k / heads columns each, every head with its own softmax: flex_attention_heads in one
+        launch, alpha [nnz, heads] kept only when a gradient is needed; backward: the one call flex_attention_heads_backward (two launches)
+        for the gradients that are needed.  Only on an operator made with fused_attention=True and fused_backward=True."""
+
+        @staticmethod
+        def forward(ctx, Q, K, V, op, scale, heads):
+            Q, K, V = Q.contiguous(), K.contiguous(), V.contiguous()
+            p = torch.zeros((op.nnz, heads), dtype=torch.float32, device=Q.device) if any(ctx.needs_input_grad[:3]) else None
+            out = op.plan.attention(Q, K, V, scale, p=p, heads=heads)
+            ctx.op, ctx.scale, ctx.heads = op, scale, heads
+            ctx.save_for_backward(Q, K, V, p)
+            return out
+
+        @staticmethod
+        def backward(ctx, grad_out):
+            Q, K, V, p = ctx.saved_tensors
+            grads = ctx.op.plan.attention_backward(Q, K, V, p, grad_out.contiguous(), ctx.scale, want=tuple(ctx.needs_input_grad[:3]), heads=ctx.heads)
+            return (*grads, None, None, None)
+
+    return _SpMM, _AxwLayer, _SpMMValues, _Sddmm, _EdgeSoftmax, _FusedAttention, _FusedAttentionHeads
 
 
 _cache = None
 
 
 def functions():
-    """(_SpMM, _AxwLayer, _SpMMValues, _Sddmm, _EdgeSoftmax, _FusedAttention): the autograd Functions, built at first use (torch is imported then)."""
+    """(_SpMM, _AxwLayer, _SpMMValues, _Sddmm, _EdgeSoftmax, _FusedAttention, _FusedAttentionHeads): the autograd Functions, built at first use (torch is imported then)."""
     global _cache
     if _cache is None:
         _cache = _function()
@@ -220,12 +241,21 @@ class SparseOperator:
         assert s.numel() == self.nnz, (s.numel(), self.nnz)
         return functions()[4].apply(s, self, float(scale))
 
-    def attention(self, Q, K, V, scale: float | None = None):
-        """Out [m, k] = A(alpha) V with alpha = softmax over each row of A of scale * <Q[row], K[col]>; scale defaults to k ** -0.5.
-        Differentiable in Q [m, k], K [n, k] and V [n, k]."""
+    def attention(self, Q, K, V, scale: float | None = None, heads: int = 1):
+        """Out [m, k] = A(alpha) V with alpha = softmax over each row of A of scale * <Q[row], K[col]>; scale defaults to
+        (k / heads) ** -0.5.  Differentiable in Q [m, k], K [n, k] and V [n, k].  heads > 1: head h is columns [h k / heads, (h + 1) k / heads)
+        of Q, K, V and Out and has its own scores and softmax, all heads in one forward launch and two backward launches
+        (flex_attention_heads); needs fused_attention=True and fused_backward=True."""
         self._needs_learn_values("attention")
+        if heads < 1:
+            raise ValueError(f"heads must be at least 1, not {heads}")
         if scale is None:
-            scale = self.k ** -0.5
+            scale = (self.k / heads) ** -0.5
+        if heads > 1:
+            if not (self.fused_attention and self.fused_backward):
+                raise NotImplementedError("attention(..., heads > 1) needs SparseOperator(..., fused_attention=True, fused_backward=True): "
+                                          "only the fused forward and backward run several heads in one launch")
+            return functions()[6].apply(Q, K, V, self, float(scale), int(heads))
         if self.fused_attention:
             return functions()[5].apply(Q, K, V, self, float(scale))
         return self(V, values=self.edge_softmax(self.sddmm(Q, K), scale))

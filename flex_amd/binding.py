@@ -162,7 +162,7 @@ SYMBOLS = [
     "flex_order_deg", "flex_order_dfs", "flex_order_rabbit", "flex_shard_rows", "flex_synth_graph", "flex_synth_preset", "flex_strerror", "flex_last_hip_error",
     "flex_last_hip_error_string", "flex_abi_version", "flex_plan_set_values", "flex_sddmm",
     "flex_edge_softmax", "flex_edge_softmax_backward", "flex_plan_softmax_info", "flex_attention", "flex_plan_attention_info",
-    "flex_attention_backward", "flex_plan_attention_backward_info",
+    "flex_attention_backward", "flex_plan_attention_backward_info", "flex_attention_heads", "flex_attention_heads_backward",
     "flex_plan_record_info", "flex_plan_read_records",
 ]
 
@@ -251,16 +251,18 @@ def lib():
 
 
 def _values_fn(name: str):
-    """flex_plan_set_values / flex_sddmm / flex_edge_softmax / flex_edge_softmax_backward / flex_attention / flex_attention_backward, looked up at first use and not when the
-    library loads: a host-only build without the kernel files does not define them (tests/hostsim has stand-ins that only log which
+    """flex_plan_set_values / flex_sddmm / flex_edge_softmax / flex_edge_softmax_backward / flex_attention / flex_attention_backward and the
+    two multi-head calls, looked up at first use and not when the library loads: a host-only build without the kernel files does not define them (tests/hostsim has stand-ins that only log which
     kernel the real ones would launch)."""
     L = lib()
     f = getattr(L, name)
     if f.argtypes is None:
-        vp, fl = C.c_void_p, C.c_float
+        vp, fl, i32 = C.c_void_p, C.c_float, C.c_int
         f.argtypes = {"flex_plan_set_values": [vp, vp, vp], "flex_sddmm": [vp, vp, vp, vp, vp], "flex_edge_softmax": [vp, vp, fl, vp, vp],
                       "flex_edge_softmax_backward": [vp, vp, vp, fl, vp, vp], "flex_attention": [vp, vp, vp, vp, fl, vp, vp, vp],
-                      "flex_attention_backward": [vp, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp]}[name]
+                      "flex_attention_backward": [vp, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp],
+                      "flex_attention_heads": [vp, i32, vp, vp, vp, fl, vp, vp, vp],
+                      "flex_attention_heads_backward": [vp, i32, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp]}[name]
     return f
 
 
@@ -646,13 +648,28 @@ class Plan:
         _check(lib().flex_plan_attention_info(self._h, C.byref(i)), "flex_plan_attention_info")
         return {f: getattr(i, f) for f, _ in _AttentionInfo._fields_}
 
-    def attention_ptr(self, dQ_ptr: int, dK_ptr: int, dV_ptr: int, scale: float, dOut_ptr: int, dP_ptr: int | None = None, stream: int = 0):
-        _check(_values_fn("flex_attention")(self._h, dQ_ptr, dK_ptr, dV_ptr, scale, dOut_ptr, dP_ptr, stream), "flex_attention")
+    def attention_ptr(self, dQ_ptr: int, dK_ptr: int, dV_ptr: int, scale: float, dOut_ptr: int, dP_ptr: int | None = None, stream: int = 0,
+                      heads: int | None = None):
+        """heads=None: flex_attention.  heads=H (1 included): flex_attention_heads with that H; dP is then nnz x H floats, entry-major."""
+        if heads is None:
+            _check(_values_fn("flex_attention")(self._h, dQ_ptr, dK_ptr, dV_ptr, scale, dOut_ptr, dP_ptr, stream), "flex_attention")
+        else:
+            _check(_values_fn("flex_attention_heads")(self._h, heads, dQ_ptr, dK_ptr, dV_ptr, scale, dOut_ptr, dP_ptr, stream), "flex_attention_heads")
 
-    def attention(self, Q, K, V, scale: float, out=None, p=None):
+    def _edge_arrays(self, heads, *ts):
+        import torch
+        if heads == 1:
+            self._edge_vectors(*ts)
+            return
+        for t in ts:
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (self.src_nnz, heads), "float32 cuda [nnz, heads]"
+
+    def attention(self, Q, K, V, scale: float, out=None, p=None, heads: int = 1):
         """flex_attention: out [m, k] = sum over each row's entries of alpha V[col], alpha = the softmax over the row of
         scale * <Q[row], K[col]>, in one launch.  Q: [m, k] like C; K, V: [n, k] like B; float32 cuda tensors.  p (optional): a float32
-        cuda tensor [a.nnz] that receives alpha in a's CSR order for the plan's rows (entries of other shards keep what it held)."""
+        cuda tensor [a.nnz] that receives alpha in a's CSR order for the plan's rows (entries of other shards keep what it held).
+        heads > 1 (flex_attention_heads): head h is columns [h k / heads, (h + 1) k / heads) and has its own softmax, still in one launch;
+        p is then [a.nnz, heads]."""
         import torch
         i = self.info()
         for t, rows in ((Q, i["m"]), (K, i["n"]), (V, i["n"])):
@@ -661,9 +678,9 @@ class Plan:
             out = (torch.empty if i["nnz"] else torch.zeros)((i["m"], i["k"]), dtype=torch.float32, device=Q.device)
         assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (i["m"], i["k"])
         if p is not None:
-            self._edge_vectors(p)
+            self._edge_arrays(heads, p)
         self.attention_ptr(Q.data_ptr(), K.data_ptr(), V.data_ptr(), scale, out.data_ptr(), None if p is None else p.data_ptr(),
-                           torch.cuda.current_stream(Q.device).cuda_stream)
+                           torch.cuda.current_stream(Q.device).cuda_stream, heads=None if heads == 1 else heads)
         return out
 
     def attention_backward_info(self) -> dict:
@@ -673,21 +690,29 @@ class Plan:
         return {f: getattr(i, f) for f, _ in _AttentionBackwardInfo._fields_}
 
     def attention_backward_ptr(self, dQ_ptr: int, dK_ptr: int, dV_ptr: int, dP_ptr: int, dGradOut_ptr: int, scale: float, dGradQ_ptr: int | None,
-                               dGradK_ptr: int | None, dGradV_ptr: int | None, dWork_ptr: int, stream: int = 0):
-        _check(_values_fn("flex_attention_backward")(self._h, dQ_ptr, dK_ptr, dV_ptr, dP_ptr, dGradOut_ptr, scale, dGradQ_ptr, dGradK_ptr, dGradV_ptr,
-                                                     dWork_ptr, stream), "flex_attention_backward")
+                               dGradK_ptr: int | None, dGradV_ptr: int | None, dWork_ptr: int, stream: int = 0, heads: int | None = None):
+        """heads=None: flex_attention_backward.  heads=H (1 included): flex_attention_heads_backward with that H; dP and dWork are then
+        nnz x H floats, entry-major."""
+        if heads is None:
+            _check(_values_fn("flex_attention_backward")(self._h, dQ_ptr, dK_ptr, dV_ptr, dP_ptr, dGradOut_ptr, scale, dGradQ_ptr, dGradK_ptr, dGradV_ptr,
+                                                         dWork_ptr, stream), "flex_attention_backward")
+        else:
+            _check(_values_fn("flex_attention_heads_backward")(self._h, heads, dQ_ptr, dK_ptr, dV_ptr, dP_ptr, dGradOut_ptr, scale, dGradQ_ptr, dGradK_ptr,
+                                                               dGradV_ptr, dWork_ptr, stream), "flex_attention_heads_backward")
 
-    def attention_backward(self, Q, K, V, p, grad_out, scale: float, grad_q=None, grad_k=None, grad_v=None, work=None, want=(True, True, True)):
+    def attention_backward(self, Q, K, V, p, grad_out, scale: float, grad_q=None, grad_k=None, grad_v=None, work=None, want=(True, True, True),
+                           heads: int = 1):
         """flex_attention_backward: (gQ [m, k], gK [n, k], gV [n, k]) of attention()'s out from its p and grad_out [m, k], in two launches; an
         output that `want` does not ask for is None and is not computed.  work (optional): a float32 cuda tensor [a.nnz], not p, that
-        receives the gradient in the scores whenever gQ or gK is wanted."""
+        receives the gradient in the scores whenever gQ or gK is wanted.  heads > 1 (flex_attention_heads_backward): the backward of
+        attention(..., heads=heads); p and work are [a.nnz, heads]."""
         import torch
         i = self.info()
         for t, rows in ((Q, i["m"]), (K, i["n"]), (V, i["n"]), (grad_out, i["m"])):
             assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (rows, i["k"])
         if work is None:
-            work = torch.empty(self.src_nnz, dtype=torch.float32, device=Q.device)
-        self._edge_vectors(p, work)
+            work = torch.empty(self.src_nnz if heads == 1 else (self.src_nnz, heads), dtype=torch.float32, device=Q.device)
+        self._edge_arrays(heads, p, work)
         outs = []
         for wanted, t, rows in zip(want, (grad_q, grad_k, grad_v), (i["m"], i["n"], i["n"])):
             if wanted and t is None:  # every row is written, except by a plan without entries, which launches nothing
@@ -697,7 +722,7 @@ class Plan:
             outs.append(t if wanted else None)
         self.attention_backward_ptr(Q.data_ptr(), K.data_ptr(), V.data_ptr(), p.data_ptr(), grad_out.data_ptr(), scale,
                                     *(None if t is None else t.data_ptr() for t in outs), work.data_ptr(),
-                                    torch.cuda.current_stream(Q.device).cuda_stream)
+                                    torch.cuda.current_stream(Q.device).cuda_stream, heads=None if heads == 1 else heads)
         return tuple(outs)
 
     def destroy(self):

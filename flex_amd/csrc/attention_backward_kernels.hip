@@ -26,68 +26,6 @@
 namespace flex {
 namespace attention {
 
-struct ColumnView {
-    const uint32_t *colptr;  // first position of every column in ent
-    const uint2 *ent;        // {row, entry index}, by column, CSR order within a column
-    const uint4 *item;
-    const uint32_t *grp;
-    uint32_t n_groups, n_wave_items, n_block_cols;
-    uint32_t xcd_remap;
-    int32_t k, ldb, ldc;
-};
-
-enum BackwardKind : int { kSlotLine = 0, kWaveLine = 1, kBlockLine = 2 };
-
-__device__ __forceinline__ float4 add4(const float4 &a, const float4 &b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-
-// a <- the sum of the rows `a` of the 64 / W slots of a wave, on every lane: a butterfly over the slots, the lower slot's row first
-template <int W, int NS>
-__device__ __forceinline__ void sum_slots(float4 (&a)[NS], uint32_t lane) {
-#pragma unroll
-    for (int off = W; off < 64; off <<= 1) {
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const float4 o = shfl_xor4(a[s], off);
-            a[s] = (lane & static_cast<uint32_t>(off)) ? add4(o, a[s]) : add4(a[s], o);
-        }
-    }
-}
-
-// The slot's line (a row of the row kernel, a column of the column kernel), its entries and its place in the team that shares the line:
-// the forward's ownership (attention_kernels.hip, run_item).  ptr is the row pointer or the column pointer.
-struct Place {
-    uint32_t line, len, t, T, n_pass;
-    uint64_t first;
-    bool has_line;
-};
-template <int W>
-__device__ __forceinline__ Place place_of(const uint32_t *__restrict__ ptr, const uint4 &it, int kind, uint32_t slot, uint32_t w) {
-    constexpr uint32_t S = 64 / W;
-    Place pl{it.z, it.y, slot, S, 0u, it.x, true};
-    if (kind == kSlotLine) {
-        pl.has_line = slot < it.w;
-        pl.line = it.z + (pl.has_line ? slot : 0u);
-        pl.first = ptr[pl.line];
-        pl.len = pl.has_line ? ptr[pl.line + 1] - ptr[pl.line] : 0u;
-        pl.t = 0;
-        pl.T = 1;
-        uint32_t mx = (pl.len + U - 1) / U;
-#pragma unroll
-        for (int o = 32; o >= W; o >>= 1) {
-            const uint32_t other = static_cast<uint32_t>(__shfl_xor(static_cast<int>(mx), o));
-            mx = other > mx ? other : mx;
-        }
-        pl.n_pass = mx;
-    } else {
-        if (kind == kBlockLine) {
-            pl.t = w * S + slot;
-            pl.T = kWavesPerBlock * S;
-        }
-        pl.n_pass = static_cast<uint32_t>((static_cast<uint64_t>(pl.len) + static_cast<uint64_t>(pl.T) * U - 1) / (static_cast<uint64_t>(pl.T) * U));
-    }
-    return pl;
-}
-
 // ---- the row kernel
 
 template <int W, int NS>

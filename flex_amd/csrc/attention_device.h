@@ -1,6 +1,8 @@
 // attention_device.h -- what the kernels of the fused attention share (device side): the view of the row walk and the column, dot,
-// axpy and slot-reduction helpers of attention_kernels.hip (flex_attention) and attention_backward_kernels.hip (flex_attention_backward).
+// axpy and slot-reduction helpers, the forward's softmax state and the backward's line ownership, of attention_kernels.hip (flex_attention),
+// attention_backward_kernels.hip (flex_attention_backward) and attention_heads_kernels.hip (their multi-head forms).
 #pragma once
+#include <cmath>
 #include <cstdint>
 
 #include "internal.h"
@@ -90,6 +92,124 @@ __device__ __forceinline__ void slot_totals(const float (&pr)[U], uint32_t li, f
     s[1] = hi2 ? oo : odd;
     s[2] = hi2 ? even : oe;
     s[3] = hi2 ? odd : oo;
+}
+
+// ---- the forward's softmax state (attention_kernels.hip, attention_heads_kernels.hip)
+
+// as softmax_kernels.hip: the score as the row maximum sees it, a term of the row sum under the finite maximum m, the probability
+__device__ __forceinline__ float max_key(float s) { return (s != s || s == INFINITY) ? INFINITY : s; }
+__device__ __forceinline__ float term(float s, float m, float scale) { return s == -INFINITY ? 0.f : expf(scale * (s - m)); }
+__device__ __forceinline__ float prob(float s, float m, float sum, float scale) {
+    return m == INFINITY ? __builtin_nanf("") : m == -INFINITY ? 0.f : term(s, m, scale) / sum;
+}
+// the factor that carries a state from its maximum m to the maximum M >= m of a merge (M finite or -inf)
+__device__ __forceinline__ float carry(float m, float M, float scale) { return m == -INFINITY ? 0.f : expf(scale * (m - M)); }
+
+template <int NS>
+struct State {
+    float m, l;
+    float4 acc[NS];
+};
+
+// a <- a merged with b, `a` being the state that comes first in the fixed order
+template <int NS>
+__device__ __forceinline__ void merge(State<NS> &a, const State<NS> &b, float scale) {
+    const float M = fmaxf(a.m, b.m);
+    if (M == INFINITY) {
+        a.m = INFINITY;
+        return;
+    }
+    const float fa = carry(a.m, M, scale), fb = carry(b.m, M, scale);
+    a.m = M;
+    a.l = __builtin_fmaf(b.l, fb, a.l * fa);
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        float4 x = scaled(a.acc[s], fa);
+        axpy(x, fb, b.acc[s]);
+        a.acc[s] = x;
+    }
+}
+
+// the Out row of a final state: NaN on a poisoned row, the sums as they are where no entry is live
+template <int NS, bool VEC>
+__device__ __forceinline__ void write_row(float *__restrict__ orow, const State<NS> &st, uint32_t li, int W, int k) {
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        float4 o;
+        if (st.m == INFINITY) {
+            const float nan = __builtin_nanf("");
+            o = make_float4(nan, nan, nan, nan);
+        } else if (st.m == -INFINITY) {
+            o = st.acc[s];  // no live entry: +0, or what 0 x a non-finite V left
+        } else {
+            o = make_float4(st.acc[s].x / st.l, st.acc[s].y / st.l, st.acc[s].z / st.l, st.acc[s].w / st.l);
+        }
+        store_cols<VEC>(orow, 4 * static_cast<int>(li) + 4 * W * s, k, o);
+    }
+}
+
+// ---- the backward's column view, plain sums and line ownership (attention_backward_kernels.hip, attention_heads_kernels.hip)
+
+struct ColumnView {
+    const uint32_t *colptr;  // first position of every column in ent
+    const uint2 *ent;        // {row, entry index}, by column, CSR order within a column
+    const uint4 *item;
+    const uint32_t *grp;
+    uint32_t n_groups, n_wave_items, n_block_cols;
+    uint32_t xcd_remap;
+    int32_t k, ldb, ldc;
+};
+
+enum BackwardKind : int { kSlotLine = 0, kWaveLine = 1, kBlockLine = 2 };
+
+__device__ __forceinline__ float4 add4(const float4 &a, const float4 &b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+
+// a <- the sum of the rows `a` of the 64 / W slots of a wave, on every lane: a butterfly over the slots, the lower slot's row first
+template <int W, int NS>
+__device__ __forceinline__ void sum_slots(float4 (&a)[NS], uint32_t lane) {
+#pragma unroll
+    for (int off = W; off < 64; off <<= 1) {
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const float4 o = shfl_xor4(a[s], off);
+            a[s] = (lane & static_cast<uint32_t>(off)) ? add4(o, a[s]) : add4(a[s], o);
+        }
+    }
+}
+
+// The slot's line (a row of the row kernel, a column of the column kernel), its entries and its place in the team that shares the line:
+// the forward's ownership (attention_kernels.hip, run_item).  ptr is the row pointer or the column pointer.
+struct Place {
+    uint32_t line, len, t, T, n_pass;
+    uint64_t first;
+    bool has_line;
+};
+template <int W>
+__device__ __forceinline__ Place place_of(const uint32_t *__restrict__ ptr, const uint4 &it, int kind, uint32_t slot, uint32_t w) {
+    constexpr uint32_t S = 64 / W;
+    Place pl{it.z, it.y, slot, S, 0u, it.x, true};
+    if (kind == kSlotLine) {
+        pl.has_line = slot < it.w;
+        pl.line = it.z + (pl.has_line ? slot : 0u);
+        pl.first = ptr[pl.line];
+        pl.len = pl.has_line ? ptr[pl.line + 1] - ptr[pl.line] : 0u;
+        pl.t = 0;
+        pl.T = 1;
+        uint32_t mx = (pl.len + U - 1) / U;
+#pragma unroll
+        for (int o = 32; o >= W; o >>= 1) {
+            const uint32_t other = static_cast<uint32_t>(__shfl_xor(static_cast<int>(mx), o));
+            mx = other > mx ? other : mx;
+        }
+        pl.n_pass = mx;
+    } else {
+        if (kind == kBlockLine) {
+            pl.t = w * S + slot;
+            pl.T = kWavesPerBlock * S;
+        }
+        pl.n_pass = static_cast<uint32_t>((static_cast<uint64_t>(pl.len) + static_cast<uint64_t>(pl.T) * U - 1) / (static_cast<uint64_t>(pl.T) * U));
+    }
+    return pl;
 }
 
 }  // namespace attention

@@ -1,0 +1,656 @@
+// attention_heads_kernels.hip -- the multi-head forms of the fused attention (include/flex_spmm.h: flex_attention_heads,
+// flex_attention_heads_backward): H heads of d = k / H columns each in the one forward launch and the two backward launches of
+// flex_attention and flex_attention_backward, on the same plans.  tests/test_gpu_multihead_attention.py covers it.
+//
+// The walk is the single-head kernels' (attention_kernels.hip, attention_backward_kernels.hip; attention_device.h): the same view, items,
+// groups, slot / wave / block ownership, W = sddmm_lanes(k) lanes per slot, four entries per pass and four columns per lane and slab.
+// d is a power of two in [4, 256], so a head is HW = d / 4 whole lanes of one slab: the lane that holds columns c .. c + 3 belongs to
+// head c / d, and the lanes of a head are HW consecutive lanes that start at a multiple of HW.  HW is a launch argument (its log2),
+// the same for every lane.  Where k / 4 < W (k = 48: 12 of 16 lanes) the lanes past k hold zeros, form groups of their own and neither
+// read nor write an edge array.  What changes against one head:
+//   forward        a score is reduced over the HW lanes of the lane's head, per slab (head_total), so every lane holds the four scores
+//                  of ITS head; the running maximum, the running sum, the rescale, the mask and poison rules and every merge are kept
+//                  per lane and slab, i.e. per head (State<1> per slab: all lanes of a head hold the same bits); a block row's waves
+//                  meet in LDS with one (m, l) per group of four columns
+//   row backward   da is reduced the same way, delta is per lane and slab, ds of the lane's own head enters gQ
+//   column backward p and ds are read at the lane's head; nothing else (there was never a reduction across lanes)
+// Edge arrays (dP, dWork) are entry-major: (entry e, head h) at e H + h.  Of the HW lanes of a head, lane r (r = lane % HW) writes
+// entry u of a pass where u == r (HW >= 4) or u % HW == r (HW = 1, 2); the same lane reads its element back in the second sweep.
+// Fixed order everywhere, no atomics.  Only the 16-byte form is built (the host refuses the rest).
+#include <cmath>
+#include <cstdint>
+
+#include "attention_device.h"
+#include "plan.h"
+
+namespace flex {
+namespace attention {
+
+// how the lanes of a slot split into heads: lg = log2(HW); H floats per entry in the edge arrays
+struct HeadSplit {
+    int32_t H, lg;
+};
+
+// what a lane knows about its place in its head: r = its index among the head's lanes, wm = the mask of the writer rule above
+struct HeadLane {
+    uint32_t hw, r, wm;
+    __device__ __forceinline__ HeadLane(const HeadSplit &hs, uint32_t li) : hw(1u << hs.lg), r(li & (hw - 1u)), wm((hw < static_cast<uint32_t>(U) ? hw : static_cast<uint32_t>(U)) - 1u) {}
+    __device__ __forceinline__ bool writes(int u) const { return (static_cast<uint32_t>(u) & wm) == r; }
+};
+
+// The sum of x over the hw lanes of the lane's head, on every one of them: a butterfly from the widest step down -- the tree of
+// slot_totals<hw>.  Both lanes of a pair add the same two operands, so all lanes of the head hold the same bits.  hw is the same for the
+// whole wave: every shuffle is wave-wide.
+template <int W>
+__device__ __forceinline__ float head_total(float x, uint32_t hw) {
+#pragma unroll
+    for (int o = W / 2; o >= 1; o >>= 1) {
+        if (static_cast<uint32_t>(o) < hw) x += __shfl_xor(x, o);
+    }
+    return x;
+}
+
+// ---- forward
+
+// attention_kernels.hip, sweep, with the state per slab
+template <int W, int NS>
+__device__ __forceinline__ void sweep_heads(const View &v, const HeadSplit &hs, const HeadLane &hl, const float4 (&q)[NS], const float *__restrict__ K,
+                                            const float *__restrict__ V, float scale, float *__restrict__ P, const Place &pl, uint32_t lane, uint32_t li,
+                                            State<1> (&st)[NS]) {
+    const int slot_lane0 = static_cast<int>(lane - li);
+    // four slabs: the V rows of a slab are gathered when its scores are done, not with the K rows -- the per-slab state would otherwise
+    // take the kernel past 256 registers, to one wave per SIMD
+    constexpr bool kLateV = NS == 4;
+    for (uint32_t pass = 0; pass < pl.n_pass; ++pass) {
+        const uint64_t j0 = (static_cast<uint64_t>(pass) * pl.T + pl.t) * U;
+        const bool mine = li < static_cast<uint32_t>(U) && j0 + li < pl.len;
+        const uint32_t idx = mine ? v.src[pl.first - v.e0 + j0 + li] : 0u;
+        bool valid[U];
+        float4 kv[U][NS], vv[U][NS];
+        const float *vrow[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint32_t col = __shfl(idx, slot_lane0 + u);
+            valid[u] = j0 + u < pl.len;
+            const float *kr = K + static_cast<size_t>(col) * v.ldb, *vr = V + static_cast<size_t>(col) * v.ldb;
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                const int c = 4 * static_cast<int>(li) + 4 * W * s;
+                kv[u][s] = valid[u] ? load_cols<true>(kr, c, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
+                if constexpr (!kLateV) vv[u][s] = valid[u] ? load_cols<true>(vr, c, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+            vrow[u] = vr;
+        }
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const int c = 4 * static_cast<int>(li) + 4 * W * s;
+            if constexpr (kLateV) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) vv[u][s] = valid[u] ? load_cols<true>(vrow[u], c, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+            float sc[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) sc[u] = head_total<W>(dot_cols<true>(0.f, q[s], kv[u][s], c, v.k), hl.hw);
+            float pm = -INFINITY;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (!valid[u]) sc[u] = -INFINITY;
+                pm = fmaxf(pm, max_key(sc[u]));
+            }
+            if (P && c < v.k) {
+                const uint32_t head = (li + static_cast<uint32_t>(W * s)) >> hs.lg;
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    if (valid[u] && hl.writes(u)) P[(pl.first + j0 + u) * static_cast<uint64_t>(hs.H) + head] = sc[u];
+                }
+            }
+            State<1> &x = st[s];
+            if (pm > x.m) {
+                const float f = carry(x.m, pm, scale);
+                x.l *= f;
+                x.acc[0] = scaled(x.acc[0], f);
+                x.m = pm;
+            }
+            if (x.m != INFINITY) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    if (valid[u]) {
+                        const float tm = term(sc[u], x.m, scale);
+                        x.l += tm;
+                        axpy(x.acc[0], tm, vv[u][s]);
+                    }
+                }
+            }
+        }
+    }
+}
+
+// attention_kernels.hip, merge_slots, slab by slab
+template <int W, int NS>
+__device__ __forceinline__ void merge_slots_heads(State<1> (&st)[NS], uint32_t lane, float scale) {
+#pragma unroll
+    for (int off = W; off < 64; off <<= 1) {
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            State<1> o;
+            o.m = __shfl_xor(st[s].m, off);
+            o.l = __shfl_xor(st[s].l, off);
+            o.acc[0] = shfl_xor4(st[s].acc[0], off);
+            if (lane & static_cast<uint32_t>(off)) {
+                merge(o, st[s], scale);
+                st[s] = o;
+            } else {
+                merge(st[s], o, scale);
+            }
+        }
+    }
+}
+
+// where the waves of a block row meet: (m, l) of every group of four columns (the lanes of a head hold the same pair) and the Out rows
+template <int W, int NS>
+struct HeadsShared {
+    float2 ml[kWavesPerBlock][W * NS];
+    alignas(16) float acc[kWavesPerBlock][4 * W * NS];
+};
+
+template <int W, int NS>
+__device__ __forceinline__ void run_item_heads(const View &v, const HeadSplit &hs, const uint4 &it, int kind, const float *__restrict__ Q,
+                                               const float *__restrict__ K, const float *__restrict__ V, float scale, float *__restrict__ Out,
+                                               float *__restrict__ P, uint32_t lane, uint32_t w, HeadsShared<W, NS> &sh) {
+    const uint32_t slot = lane / W, li = lane % W;
+    const HeadLane hl(hs, li);
+    const Place pl = place_of<W>(v.rowptr, it, kind, slot, w);
+    float4 q[NS];
+    State<1> st[NS];
+    const float *qrow = Q + static_cast<size_t>(pl.line) * v.ldc;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        q[s] = pl.has_line ? load_cols<true>(qrow, 4 * static_cast<int>(li) + 4 * W * s, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
+        st[s].m = -INFINITY;
+        st[s].l = 0.f;
+        st[s].acc[0] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    sweep_heads<W, NS>(v, hs, hl, q, K, V, scale, P, pl, lane, li, st);
+    if (kind != kSlotLine) merge_slots_heads<W, NS>(st, lane, scale);
+    bool writer = kind == kSlotLine ? pl.has_line : slot == 0;
+    if (kind == kBlockLine) {
+        if (slot == 0) {
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                *reinterpret_cast<float4 *>(&sh.acc[w][4 * li + 4 * W * s]) = st[s].acc[0];
+                sh.ml[w][li + W * s] = make_float2(st[s].m, st[s].l);
+            }
+        }
+        __syncthreads();
+        writer = w == 0 && slot == 0;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {  // the waves in wave order: every lane folds (m, l) of its head, the writing lanes their columns as well
+            State<1> tot;
+            tot.m = sh.ml[0][li + W * s].x;
+            tot.l = sh.ml[0][li + W * s].y;
+            tot.acc[0] = writer ? *reinterpret_cast<const float4 *>(&sh.acc[0][4 * li + 4 * W * s]) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int i = 1; i < kWavesPerBlock; ++i) {
+                State<1> o;
+                o.m = sh.ml[i][li + W * s].x;
+                o.l = sh.ml[i][li + W * s].y;
+                o.acc[0] = writer ? *reinterpret_cast<const float4 *>(&sh.acc[i][4 * li + 4 * W * s]) : make_float4(0.f, 0.f, 0.f, 0.f);
+                merge(tot, o, scale);
+            }
+            st[s] = tot;
+        }
+    }
+    if (writer) {
+        float *orow = Out + static_cast<size_t>(pl.line) * v.ldc;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) write_row<1, true>(orow + 4 * W * s, st[s], li, W, v.k - 4 * W * s);
+    }
+    if (P) {  // the second sweep of dP: the lane that wrote a raw score overwrites it with the probability under its head's final (M, L)
+        for (uint32_t pass = 0; pass < pl.n_pass; ++pass) {
+            const uint64_t j0 = (static_cast<uint64_t>(pass) * pl.T + pl.t) * U;
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                if (4 * static_cast<int>(li) + 4 * W * s >= v.k) continue;
+                const uint32_t head = (li + static_cast<uint32_t>(W * s)) >> hs.lg;
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    if (j0 + u < pl.len && hl.writes(u)) {
+                        const uint64_t e = (pl.first + j0 + u) * static_cast<uint64_t>(hs.H) + head;
+                        P[e] = prob(P[e], st[s].m, st[s].l, scale);
+                    }
+                }
+            }
+        }
+    }
+}
+
+// Grid: as attention_rows.
+template <int W, int NS>
+__global__ __launch_bounds__(256) void attention_heads_rows(View v, HeadSplit hs, const float *__restrict__ Q, const float *__restrict__ K,
+                                                             const float *__restrict__ V, float scale, float *__restrict__ Out, float *__restrict__ P) {
+    __shared__ HeadsShared<W, NS> sh;
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    if (blockIdx.x < v.n_block_rows) {
+        run_item_heads<W, NS>(v, hs, v.item[v.n_wave_items + blockIdx.x], kBlockLine, Q, K, V, scale, Out, P, lane, w, sh);
+        return;
+    }
+    uint32_t wg = blockIdx.x - v.n_block_rows;
+    if (v.xcd_remap) {
+        const uint32_t per = (gridDim.x - v.n_block_rows) / kXcds;
+        wg = (wg % kXcds) * per + wg / kXcds;
+    }
+    const uint32_t grp = wg * kWavesPerBlock + w;
+    if (grp >= v.n_groups) return;
+    const uint32_t i1 = v.grp[grp + 1];
+    for (uint32_t i = v.grp[grp]; i < i1; ++i) {
+        const uint4 it = v.item[i];
+        const int kind = (it.w > 1 || it.y <= kAtSlotRow) ? kSlotLine : kWaveLine;  // internal.h, attention_row_class
+        run_item_heads<W, NS>(v, hs, it, kind, Q, K, V, scale, Out, P, lane, w, sh);
+    }
+}
+
+// ---- row backward
+
+template <int W, int NS>
+struct HeadsRowShared {
+    float delta[kWavesPerBlock][W * NS];
+    alignas(16) float acc[kWavesPerBlock][4 * W * NS];
+};
+
+// attention_backward_kernels.hip, run_row, with da, delta and ds per slab
+template <int W, int NS>
+__device__ __forceinline__ void run_row_heads(const View &v, const HeadSplit &hs, const uint4 &it, int kind, const float *__restrict__ K,
+                                              const float *__restrict__ V, const float *__restrict__ P, const float *__restrict__ G, float scale,
+                                              float *__restrict__ GQ, float *__restrict__ Work, uint32_t lane, uint32_t w, HeadsRowShared<W, NS> &sh) {
+    const uint32_t slot = lane / W, li = lane % W;
+    const int slot_lane0 = static_cast<int>(lane - li);
+    const HeadLane hl(hs, li);
+    const Place pl = place_of<W>(v.rowptr, it, kind, slot, w);
+    float4 g[NS];
+    const float *grow = G + static_cast<size_t>(pl.line) * v.ldc;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) g[s] = pl.has_line ? load_cols<true>(grow, 4 * static_cast<int>(li) + 4 * W * s, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
+    // sweep 1: da into dWork, delta of the lane's heads
+    float delta[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) delta[s] = 0.f;
+    for (uint32_t pass = 0; pass < pl.n_pass; ++pass) {
+        const uint64_t j0 = (static_cast<uint64_t>(pass) * pl.T + pl.t) * U;
+        const bool mine = li < static_cast<uint32_t>(U) && j0 + li < pl.len;
+        const uint32_t idx = mine ? v.src[pl.first - v.e0 + j0 + li] : 0u;
+        bool valid[U];
+        float4 vv[U][NS];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint32_t col = __shfl(idx, slot_lane0 + u);
+            valid[u] = j0 + u < pl.len;
+            const float *vr = V + static_cast<size_t>(col) * v.ldb;
+#pragma unroll
+            for (int s = 0; s < NS; ++s) vv[u][s] = valid[u] ? load_cols<true>(vr, 4 * static_cast<int>(li) + 4 * W * s, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const int c = 4 * static_cast<int>(li) + 4 * W * s;
+            const uint32_t head = (li + static_cast<uint32_t>(W * s)) >> hs.lg;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const float da = head_total<W>(dot_cols<true>(0.f, g[s], vv[u][s], c, v.k), hl.hw);
+                if (valid[u] && c < v.k) {
+                    const uint64_t e = (pl.first + j0 + u) * static_cast<uint64_t>(hs.H) + head;
+                    if (hl.writes(u)) Work[e] = da;
+                    delta[s] = __builtin_fmaf(P[e], da, delta[s]);
+                }
+            }
+        }
+    }
+    if (kind != kSlotLine) {
+#pragma unroll
+        for (int off = W; off < 64; off <<= 1) {
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                const float o = __shfl_xor(delta[s], off);
+                delta[s] = (lane & static_cast<uint32_t>(off)) ? o + delta[s] : delta[s] + o;
+            }
+        }
+    }
+    if (kind == kBlockLine) {
+        if (slot == 0) {
+#pragma unroll
+            for (int s = 0; s < NS; ++s) sh.delta[w][li + W * s] = delta[s];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            delta[s] = sh.delta[0][li + W * s];
+#pragma unroll
+            for (int i = 1; i < kWavesPerBlock; ++i) delta[s] += sh.delta[i][li + W * s];
+        }
+    }
+    // sweep 2: ds over da in dWork, gQ
+    float4 acc[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) acc[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int head_lane0 = static_cast<int>(lane - hl.r);
+    for (uint32_t pass = 0; pass < pl.n_pass; ++pass) {
+        const uint64_t j0 = (static_cast<uint64_t>(pass) * pl.T + pl.t) * U;
+        float dse[NS][U];  // on the lane that owns (entry u, the head of slab s); 0 elsewhere
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const bool live = 4 * static_cast<int>(li) + 4 * W * s < v.k;
+            const uint32_t head = (li + static_cast<uint32_t>(W * s)) >> hs.lg;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                dse[s][u] = 0.f;
+                if (live && j0 + u < pl.len && hl.writes(u)) {
+                    const uint64_t e = (pl.first + j0 + u) * static_cast<uint64_t>(hs.H) + head;
+                    const float d = Work[e] - delta[s];
+                    dse[s][u] = (scale * P[e]) * d;
+                    Work[e] = dse[s][u];
+                }
+            }
+        }
+        if (!GQ) continue;
+        const bool mine = li < static_cast<uint32_t>(U) && j0 + li < pl.len;
+        const uint32_t idx = mine ? v.src[pl.first - v.e0 + j0 + li] : 0u;
+        bool valid[U];
+        float4 kv[U][NS];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint32_t col = __shfl(idx, slot_lane0 + u);
+            valid[u] = j0 + u < pl.len;
+            const float *kr = K + static_cast<size_t>(col) * v.ldb;
+#pragma unroll
+            for (int s = 0; s < NS; ++s) kv[u][s] = valid[u] ? load_cols<true>(kr, 4 * static_cast<int>(li) + 4 * W * s, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int owner = head_lane0 + static_cast<int>(static_cast<uint32_t>(u) & hl.wm);
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                const float d = __shfl(dse[s][u], owner);
+                if (valid[u]) axpy(acc[s], d, kv[u][s]);
+            }
+        }
+    }
+    if (!GQ) return;
+    if (kind != kSlotLine) sum_slots<W, NS>(acc, lane);
+    bool writer = kind == kSlotLine ? pl.has_line : slot == 0;
+    if (kind == kBlockLine) {
+        if (slot == 0) {
+#pragma unroll
+            for (int s = 0; s < NS; ++s) *reinterpret_cast<float4 *>(&sh.acc[w][4 * li + 4 * W * s]) = acc[s];
+        }
+        __syncthreads();
+        writer = w == 0 && slot == 0;
+        if (writer) {
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                float4 tot = *reinterpret_cast<const float4 *>(&sh.acc[0][4 * li + 4 * W * s]);
+#pragma unroll
+                for (int i = 1; i < kWavesPerBlock; ++i) tot = add4(tot, *reinterpret_cast<const float4 *>(&sh.acc[i][4 * li + 4 * W * s]));
+                acc[s] = tot;
+            }
+        }
+    }
+    if (writer) {
+        float *orow = GQ + static_cast<size_t>(pl.line) * v.ldc;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) store_cols<true>(orow, 4 * static_cast<int>(li) + 4 * W * s, v.k, acc[s]);
+    }
+}
+
+template <int W, int NS>
+__global__ __launch_bounds__(256) void attention_heads_rows_backward(View v, HeadSplit hs, const float *__restrict__ K, const float *__restrict__ V,
+                                                                      const float *__restrict__ P, const float *__restrict__ G, float scale,
+                                                                      float *__restrict__ GQ, float *__restrict__ Work) {
+    __shared__ HeadsRowShared<W, NS> sh;
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    if (blockIdx.x < v.n_block_rows) {
+        run_row_heads<W, NS>(v, hs, v.item[v.n_wave_items + blockIdx.x], kBlockLine, K, V, P, G, scale, GQ, Work, lane, w, sh);
+        return;
+    }
+    uint32_t wg = blockIdx.x - v.n_block_rows;
+    if (v.xcd_remap) {
+        const uint32_t per = (gridDim.x - v.n_block_rows) / kXcds;
+        wg = (wg % kXcds) * per + wg / kXcds;
+    }
+    const uint32_t grp = wg * kWavesPerBlock + w;
+    if (grp >= v.n_groups) return;
+    const uint32_t i1 = v.grp[grp + 1];
+    for (uint32_t i = v.grp[grp]; i < i1; ++i) {
+        const uint4 it = v.item[i];
+        const int kind = (it.w > 1 || it.y <= kAtSlotRow) ? kSlotLine : kWaveLine;
+        run_row_heads<W, NS>(v, hs, it, kind, K, V, P, G, scale, GQ, Work, lane, w, sh);
+    }
+}
+
+// ---- column backward
+
+template <int W, int NS>
+struct HeadsColumnShared {
+    alignas(16) float acc[2][kWavesPerBlock][4 * W * NS];
+};
+
+// attention_backward_kernels.hip, run_column, with p and ds of the lane's head
+template <int W, int NS>
+__device__ __forceinline__ void run_column_heads(const ColumnView &v, const HeadSplit &hs, const uint4 &it, int kind, const float *__restrict__ Q,
+                                                 const float *__restrict__ G, const float *__restrict__ P, const float *__restrict__ DS,
+                                                 float *__restrict__ GK, float *__restrict__ GV, uint32_t lane, uint32_t w, HeadsColumnShared<W, NS> &sh) {
+    const uint32_t slot = lane / W, li = lane % W;
+    const int slot_lane0 = static_cast<int>(lane - li);
+    const Place pl = place_of<W>(v.colptr, it, kind, slot, w);
+    float4 ak[NS], av[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) ak[s] = av[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (uint32_t pass = 0; pass < pl.n_pass; ++pass) {
+        const uint64_t j0 = (static_cast<uint64_t>(pass) * pl.T + pl.t) * U;
+        const bool mine = li < static_cast<uint32_t>(U) && j0 + li < pl.len;
+        const uint2 re = mine ? v.ent[pl.first + j0 + li] : make_uint2(0u, 0u);
+        bool valid[U];
+        float pe[U][NS], de[U][NS];
+        float4 gg[U][NS], qq[U][NS];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint32_t row = __shfl(re.x, slot_lane0 + u), e = __shfl(re.y, slot_lane0 + u);
+            valid[u] = j0 + u < pl.len;
+            const float *gr = G + static_cast<size_t>(row) * v.ldc, *qr = Q + static_cast<size_t>(row) * v.ldc;
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                const int c = 4 * static_cast<int>(li) + 4 * W * s;
+                const bool live = valid[u] && c < v.k;
+                const uint64_t eh = static_cast<uint64_t>(e) * static_cast<uint64_t>(hs.H) + ((li + static_cast<uint32_t>(W * s)) >> hs.lg);
+                pe[u][s] = (GV && live) ? P[eh] : 0.f;
+                de[u][s] = (GK && live) ? DS[eh] : 0.f;
+                gg[u][s] = (GV && valid[u]) ? load_cols<true>(gr, c, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
+                qq[u][s] = (GK && valid[u]) ? load_cols<true>(qr, c, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (valid[u]) {
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    axpy(av[s], pe[u][s], gg[u][s]);
+                    axpy(ak[s], de[u][s], qq[u][s]);
+                }
+            }
+        }
+    }
+    if (kind != kSlotLine) {
+        sum_slots<W, NS>(ak, lane);
+        sum_slots<W, NS>(av, lane);
+    }
+    bool writer = kind == kSlotLine ? pl.has_line : slot == 0;
+    if (kind == kBlockLine) {
+        if (slot == 0) {
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                *reinterpret_cast<float4 *>(&sh.acc[0][w][4 * li + 4 * W * s]) = ak[s];
+                *reinterpret_cast<float4 *>(&sh.acc[1][w][4 * li + 4 * W * s]) = av[s];
+            }
+        }
+        __syncthreads();
+        writer = w == 0 && slot == 0;
+        if (writer) {
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                float4 tk = *reinterpret_cast<const float4 *>(&sh.acc[0][0][4 * li + 4 * W * s]);
+                float4 tv = *reinterpret_cast<const float4 *>(&sh.acc[1][0][4 * li + 4 * W * s]);
+#pragma unroll
+                for (int i = 1; i < kWavesPerBlock; ++i) {
+                    tk = add4(tk, *reinterpret_cast<const float4 *>(&sh.acc[0][i][4 * li + 4 * W * s]));
+                    tv = add4(tv, *reinterpret_cast<const float4 *>(&sh.acc[1][i][4 * li + 4 * W * s]));
+                }
+                ak[s] = tk;
+                av[s] = tv;
+            }
+        }
+    }
+    if (writer) {
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const int c = 4 * static_cast<int>(li) + 4 * W * s;
+            if (GK) store_cols<true>(GK + static_cast<size_t>(pl.line) * v.ldb, c, v.k, ak[s]);
+            if (GV) store_cols<true>(GV + static_cast<size_t>(pl.line) * v.ldb, c, v.k, av[s]);
+        }
+    }
+}
+
+template <int W, int NS>
+__global__ __launch_bounds__(256) void attention_heads_columns_backward(ColumnView v, HeadSplit hs, const float *__restrict__ Q, const float *__restrict__ G,
+                                                                         const float *__restrict__ P, const float *__restrict__ DS, float *__restrict__ GK,
+                                                                         float *__restrict__ GV) {
+    __shared__ HeadsColumnShared<W, NS> sh;
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    if (blockIdx.x < v.n_block_cols) {
+        run_column_heads<W, NS>(v, hs, v.item[v.n_wave_items + blockIdx.x], kBlockLine, Q, G, P, DS, GK, GV, lane, w, sh);
+        return;
+    }
+    uint32_t wg = blockIdx.x - v.n_block_cols;
+    if (v.xcd_remap) {
+        const uint32_t per = (gridDim.x - v.n_block_cols) / kXcds;
+        wg = (wg % kXcds) * per + wg / kXcds;
+    }
+    const uint32_t grp = wg * kWavesPerBlock + w;
+    if (grp >= v.n_groups) return;
+    const uint32_t i1 = v.grp[grp + 1];
+    for (uint32_t i = v.grp[grp]; i < i1; ++i) {
+        const uint4 it = v.item[i];
+        const int kind = (it.w > 1 || it.y <= kAtSlotRow) ? kSlotLine : kWaveLine;
+        run_column_heads<W, NS>(v, hs, it, kind, Q, G, P, DS, GK, GV, lane, w, sh);
+    }
+}
+
+// ---- launches
+
+struct HeadsOperands {
+    const float *Q, *K, *V, *P, *G;
+    float scale;
+    float *GQ, *GK, *GV, *Work;
+};
+
+template <int W, int NS>
+static void launch_heads(const View &v, const HeadSplit &hs, dim3 grid, const float *Q, const float *K, const float *V, float scale, float *Out, float *P,
+                         hipStream_t s) {
+    hipLaunchKernelGGL((attention_heads_rows<W, NS>), grid, dim3(64 * kWavesPerBlock), 0, s, v, hs, Q, K, V, scale, Out, P);
+}
+
+template <int W, int NS>
+static void launch_heads_backward(const View &rv, const ColumnView &cv, const HeadSplit &hs, dim3 rgrid, dim3 cgrid, const HeadsOperands &o, hipStream_t s) {
+    const dim3 block(64 * kWavesPerBlock);
+    if (o.GQ || o.GK) hipLaunchKernelGGL((attention_heads_rows_backward<W, NS>), rgrid, block, 0, s, rv, hs, o.K, o.V, o.P, o.G, o.scale, o.GQ, o.Work);
+    if (o.GK || o.GV) hipLaunchKernelGGL((attention_heads_columns_backward<W, NS>), cgrid, block, 0, s, cv, hs, o.Q, o.G, o.P, o.Work, o.GK, o.GV);
+}
+
+// heads > 1: FLEX_OK and the split where heads divides k into heads of d = 4 .. 256 columns, d a power of two
+static int split_of(int k, int heads, HeadSplit *out) {
+    if (k > 4 * 64 * kAtMaxSlabs || k % heads) return FLEX_ERR_UNSUPPORTED;
+    const int d = k / heads;
+    int lg = 0;
+    while ((4 << lg) < d) ++lg;
+    if (d < 4 || d > 256 || (4 << lg) != d) return FLEX_ERR_UNSUPPORTED;
+    *out = HeadSplit{heads, lg};
+    return FLEX_OK;
+}
+
+}  // namespace attention
+}  // namespace flex
+
+using namespace flex;
+
+extern "C" {
+
+int flex_attention_heads(const flex_plan *p, int heads, const float *dQ, const float *dK, const float *dV, float scale, float *dOut, float *dP,
+                         flex_stream_t stream) {
+    if (!p || !p->at_ok || heads < 1) return FLEX_ERR_INVALID;
+    if (heads == 1) return flex_attention(p, dQ, dK, dV, scale, dOut, dP, stream);
+    if (!std::isfinite(scale) || !(scale > 0.f)) return FLEX_ERR_INVALID;
+    attention::HeadSplit hs;
+    if (const int rc = attention::split_of(p->k, heads, &hs)) return rc;
+    if (p->at_entries == 0) return FLEX_OK;
+    if (!dQ || !dK || !dV || !dOut) return FLEX_ERR_INVALID;
+    const AttentionPick pick = attention_pick(p->k, p->ldb, p->ldc, dQ, dK, dV, dOut);
+    if (!pick.vec4) return FLEX_ERR_UNSUPPORTED;
+    const DeviceScope on(p->device);
+    FLEX_HIP_TRY(on.error());
+    const attention::View v{p->d_at_rowptr.get(), p->d_at_src.get(), p->d_at_item.get(), p->d_at_grp.get(), p->at_first_entry,
+                            p->n_at_groups, p->n_at_wave_items, p->n_at_block_rows, p->xcd_remap ? 1u : 0u, p->k, p->ldb, p->ldc};
+    uint32_t wgs = (p->n_at_groups + kWavesPerBlock - 1) / kWavesPerBlock;
+    if (v.xcd_remap) wgs = (wgs + kXcds - 1) / kXcds * kXcds;
+    const dim3 grid(p->n_at_block_rows + wgs);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    switch (pick.W * 8 + pick.NS) {
+        case 4 * 8 + 1: attention::launch_heads<4, 1>(v, hs, grid, dQ, dK, dV, scale, dOut, dP, s); break;
+        case 8 * 8 + 1: attention::launch_heads<8, 1>(v, hs, grid, dQ, dK, dV, scale, dOut, dP, s); break;
+        case 16 * 8 + 1: attention::launch_heads<16, 1>(v, hs, grid, dQ, dK, dV, scale, dOut, dP, s); break;
+        case 32 * 8 + 1: attention::launch_heads<32, 1>(v, hs, grid, dQ, dK, dV, scale, dOut, dP, s); break;
+        case 64 * 8 + 1: attention::launch_heads<64, 1>(v, hs, grid, dQ, dK, dV, scale, dOut, dP, s); break;
+        case 64 * 8 + 2: attention::launch_heads<64, 2>(v, hs, grid, dQ, dK, dV, scale, dOut, dP, s); break;
+        default: attention::launch_heads<64, 4>(v, hs, grid, dQ, dK, dV, scale, dOut, dP, s); break;
+    }
+    FLEX_HIP_TRY(hipGetLastError());
+    return FLEX_OK;
+}
+
+int flex_attention_heads_backward(const flex_plan *p, int heads, const float *dQ, const float *dK, const float *dV, const float *dP,
+                                  const float *dGradOut, float scale, float *dGradQ, float *dGradK, float *dGradV, float *dWork, flex_stream_t stream) {
+    if (!p || !p->ab_ok || heads < 1) return FLEX_ERR_INVALID;
+    if (heads == 1) return flex_attention_backward(p, dQ, dK, dV, dP, dGradOut, scale, dGradQ, dGradK, dGradV, dWork, stream);
+    if (!std::isfinite(scale) || !(scale > 0.f)) return FLEX_ERR_INVALID;
+    attention::HeadSplit hs;
+    if (const int rc = attention::split_of(p->k, heads, &hs)) return rc;
+    if (p->at_entries == 0) return FLEX_OK;
+    if (!dQ || !dK || !dV || !dP || !dGradOut || !dWork || dWork == dP) return FLEX_ERR_INVALID;
+    // the forward's rule over every row operand of the two launches (a NULL output is aligned)
+    const AttentionPick pick = attention_pick(p->k, p->ldb, p->ldc, dQ, dK, dV, dGradOut);
+    if (!pick.vec4 || !attention_pick(p->k, p->ldb, p->ldc, dGradQ, dGradK, dGradV, nullptr).vec4) return FLEX_ERR_UNSUPPORTED;
+    if (!dGradQ && !dGradK && !dGradV) return FLEX_OK;
+    const DeviceScope on(p->device);
+    FLEX_HIP_TRY(on.error());
+    const uint32_t remap = p->xcd_remap ? 1u : 0u;
+    const attention::View rv{p->d_at_rowptr.get(), p->d_at_src.get(), p->d_at_item.get(), p->d_at_grp.get(), p->at_first_entry,
+                             p->n_at_groups, p->n_at_wave_items, p->n_at_block_rows, remap, p->k, p->ldb, p->ldc};
+    const attention::ColumnView cv{p->d_ab_colptr.get(), p->d_ab_ent.get(), p->d_ab_item.get(), p->d_ab_grp.get(),
+                                   p->n_ab_groups, p->n_ab_wave_items, p->n_ab_block_cols, remap, p->k, p->ldb, p->ldc};
+    auto grid_of = [&](uint32_t groups, uint32_t blocks) {
+        uint32_t wgs = (groups + kWavesPerBlock - 1) / kWavesPerBlock;
+        if (remap) wgs = (wgs + kXcds - 1) / kXcds * kXcds;
+        return dim3(blocks + wgs);
+    };
+    const dim3 rgrid = grid_of(p->n_at_groups, p->n_at_block_rows), cgrid = grid_of(p->n_ab_groups, p->n_ab_block_cols);
+    const attention::HeadsOperands o{dQ, dK, dV, dP, dGradOut, scale, dGradQ, dGradK, dGradV, dWork};
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    switch (pick.W * 8 + pick.NS) {
+        case 4 * 8 + 1: attention::launch_heads_backward<4, 1>(rv, cv, hs, rgrid, cgrid, o, s); break;
+        case 8 * 8 + 1: attention::launch_heads_backward<8, 1>(rv, cv, hs, rgrid, cgrid, o, s); break;
+        case 16 * 8 + 1: attention::launch_heads_backward<16, 1>(rv, cv, hs, rgrid, cgrid, o, s); break;
+        case 32 * 8 + 1: attention::launch_heads_backward<32, 1>(rv, cv, hs, rgrid, cgrid, o, s); break;
+        case 64 * 8 + 1: attention::launch_heads_backward<64, 1>(rv, cv, hs, rgrid, cgrid, o, s); break;
+        case 64 * 8 + 2: attention::launch_heads_backward<64, 2>(rv, cv, hs, rgrid, cgrid, o, s); break;
+        default: attention::launch_heads_backward<64, 4>(rv, cv, hs, rgrid, cgrid, o, s); break;
+    }
+    FLEX_HIP_TRY(hipGetLastError());
+    return FLEX_OK;
+}
+
+}  // extern "C"

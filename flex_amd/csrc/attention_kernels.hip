@@ -27,21 +27,6 @@
 namespace flex {
 namespace attention {
 
-// as softmax_kernels.hip: the score as the row maximum sees it, a term of the row sum under the finite maximum m, the probability
-__device__ __forceinline__ float max_key(float s) { return (s != s || s == INFINITY) ? INFINITY : s; }
-__device__ __forceinline__ float term(float s, float m, float scale) { return s == -INFINITY ? 0.f : expf(scale * (s - m)); }
-__device__ __forceinline__ float prob(float s, float m, float sum, float scale) {
-    return m == INFINITY ? __builtin_nanf("") : m == -INFINITY ? 0.f : term(s, m, scale) / sum;
-}
-// the factor that carries a state from its maximum m to the maximum M >= m of a merge (M finite or -inf)
-__device__ __forceinline__ float carry(float m, float M, float scale) { return m == -INFINITY ? 0.f : expf(scale * (m - M)); }
-
-template <int NS>
-struct State {
-    float m, l;
-    float4 acc[NS];
-};
-
 // The sweep of one slot over its share of a row: member t of a team of T slots takes the passes t, t + T, ... of kAtPass entries.
 // n_pass is the same for every lane of the wave (a slot past its row's end idles under a predicate), so every shuffle is wave-wide.
 template <int W, int NS, bool VEC>
@@ -104,25 +89,6 @@ __device__ __forceinline__ void sweep(const View &v, const float4 (&q)[NS], cons
     }
 }
 
-// a <- a merged with b, `a` being the state that comes first in the fixed order
-template <int NS>
-__device__ __forceinline__ void merge(State<NS> &a, const State<NS> &b, float scale) {
-    const float M = fmaxf(a.m, b.m);
-    if (M == INFINITY) {
-        a.m = INFINITY;
-        return;
-    }
-    const float fa = carry(a.m, M, scale), fb = carry(b.m, M, scale);
-    a.m = M;
-    a.l = __builtin_fmaf(b.l, fb, a.l * fa);
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        float4 x = scaled(a.acc[s], fa);
-        axpy(x, fb, b.acc[s]);
-        a.acc[s] = x;
-    }
-}
-
 // the states of the 64 / W slots of a wave, merged on every lane: a butterfly over the slots, the lower slot's state first
 template <int W, int NS>
 __device__ __forceinline__ void merge_slots(State<NS> &st, uint32_t lane, float scale) {
@@ -149,23 +115,6 @@ __device__ __forceinline__ void write_probs(float *__restrict__ P, uint64_t firs
     for (uint32_t pass = 0; pass < n_pass; ++pass) {
         const uint64_t j = (static_cast<uint64_t>(pass) * T + t) * U + li;
         if (j < len) P[first + j] = prob(P[first + j], M, L, scale);
-    }
-}
-
-template <int NS, bool VEC>
-__device__ __forceinline__ void write_row(float *__restrict__ orow, const State<NS> &st, uint32_t li, int W, int k) {
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        float4 o;
-        if (st.m == INFINITY) {
-            const float nan = __builtin_nanf("");
-            o = make_float4(nan, nan, nan, nan);
-        } else if (st.m == -INFINITY) {
-            o = st.acc[s];  // no live entry: +0, or what 0 x a non-finite V left
-        } else {
-            o = make_float4(st.acc[s].x / st.l, st.acc[s].y / st.l, st.acc[s].z / st.l, st.acc[s].w / st.l);
-        }
-        store_cols<VEC>(orow, 4 * static_cast<int>(li) + 4 * W * s, k, o);
     }
 }
 

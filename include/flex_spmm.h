@@ -27,6 +27,7 @@ extern "C" {
 #define FLEX_ABI_VERSION 3 /* 3 also covers the purely additive FLEX_PLAN_MUTABLE_VALUES, flex_plan_set_values, flex_sddmm and the edge softmax (no struct grew),
                               the equally additive FLEX_PLAN_ATTENTION, flex_attention and flex_plan_attention_info (a new flag, two new calls, one new struct),
                               the equally additive FLEX_PLAN_ATTENTION_BACKWARD, flex_attention_backward and flex_plan_attention_backward_info (the same again),
+                              the equally additive flex_attention_heads and flex_attention_heads_backward (two new calls, no flag, no struct),
                               and the retired flex_plan_tuning.block_ablate, which keeps its place as block_ablate_retired and must be zero.
                               3: plan-time knobs leave the environment for the struct flex_plan_tuning, flex_plan_desc.tuning, flex_plan_get_tuning,
                               flex_order_cluster_ex, flex_set_host_threads; split rows are summed by a second launch by default.
@@ -462,6 +463,36 @@ typedef struct flex_attention_backward_info {
     int64_t device_bytes;  /* device memory of the second part of the image: 4 per column, 8 per entry, 16 per item, 4 per group */
 } flex_attention_backward_info;
 int flex_plan_attention_backward_info(const flex_plan *plan, flex_attention_backward_info *out);
+
+/* Multi-head fused attention: `heads` = H heads in the ONE forward launch and the TWO backward launches of flex_attention and
+ * flex_attention_backward, on the same plans (FLEX_PLAN_ATTENTION; FLEX_PLAN_ATTENTION_BACKWARD for the second call; FLEX_ERR_INVALID on
+ * any other plan).  No new plan flag and no new image: the schedule depends on k and the pattern only, so one plan serves every H.  No
+ * reference counterpart.  k = H d.  Head h owns columns [h d, (h + 1) d) of Q, K, V, Out, g, gQ, gK and gV, and for every head on its
+ * own everything is what flex_attention and flex_attention_backward define at width d on those columns, with the one `scale`: the
+ * scores, the masked (-inf) and poisoned (+inf / NaN) rules, +0 rows, da, delta, ds, gQ, gK, gV, and "every entry multiplies its V
+ * row".  Heads never mix: a poisoned row of head h writes NaN into head h's d columns of Out and head h's entries of dP, nowhere else.
+ * dP and dWork hold hostA->nnz x H floats, entry-major: (entry e, head h) at e H + h, e in hostA's CSR order (a torch tensor [nnz, H]
+ * is contiguous).  heads == 1, for any k: the call IS flex_attention / flex_attention_backward (forwarded before any other check of
+ * this paragraph; bit-identical in every output, the generic instantiation included).  heads > 1: k % H == 0 and d in {4, 8, 16, 32,
+ * 64, 128, 256} (a power of two: a head never straddles a slab of 256 columns; H itself need not be one, k = 48 = 3 x 16 is valid),
+ * k <= 1024, and only the 16-byte form is built -- ldb % 4 == 0, ldc % 4 == 0 and every row operand 16-byte aligned; anything else
+ * is FLEX_ERR_UNSUPPORTED.  heads < 1, a scale that is not finite and > 0, a NULL operand (Q, K, V, Out; in the backward Q, K, V, P,
+ * GradOut, Work) and dWork == dP: FLEX_ERR_INVALID.  A plan without entries: FLEX_OK, no launch, nothing written.  Otherwise as the
+ * single-head calls: dP may be NULL (Out has the same bits either way); the forward on a row-range shard writes the dP entries of its
+ * rows and leaves the others untouched (the backward is not defined on shards); each of dGradQ, dGradK, dGradV may be NULL and an
+ * output has the same bits whichever others are asked for; on return dWork holds ds whenever dGradQ or dGradK was asked for.
+ * Asynchronous on `stream`, no allocation, no host synchronisation (safe to capture in a hipGraph), no atomics, fixed reduction
+ * order: bit-identical run to run.  The walk is the single-head one; a score (and da) is reduced over the d / 4 lanes of its head, and
+ * the running maximum and sum, delta and ds are kept per head.
+ *
+ * Accuracy: per head, flex_attention's and flex_attention_backward's bounds with k replaced by d -- the reduction of a score and of da
+ * has depth <= d (a chain of four fmas per lane, then a tree over the d / 4 lanes of the head); the passes, rescales and merges
+ * (R_r) and the depths of the sums of l, Out, delta, gQ, gK and gV are the single-head kernels', so c = 3, a = 3, b = 0 stand. */
+int flex_attention_heads(const flex_plan *plan, int heads, const float *dQ, const float *dK, const float *dV, float scale, float *dOut,
+                         float *dP, flex_stream_t stream);
+int flex_attention_heads_backward(const flex_plan *plan, int heads, const float *dQ, const float *dK, const float *dV, const float *dP,
+                                  const float *dGradOut, float scale, float *dGradQ, float *dGradK, float *dGradV, float *dWork,
+                                  flex_stream_t stream);
 
 /* ≙ alpha_freeMatGPU (mat.cuh:184-193). */
 int flex_plan_destroy(flex_plan *plan);

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Sparse graph attention, measured: the error of the exponential the edge softmax may use, and the time of flex_edge_softmax,
-flex_edge_softmax_backward and a whole attention step.  Writes profiles/attention_probe.txt (or the file given with --out).
+flex_edge_softmax_backward and a whole attention step.  Writes profiles/attention_probe.txt (or the file given with --out): the whole run
+starts the file, a run of one part (--fused, --backward, --heads) appends to it.
 
 1. tools/exp_error.hip (built here with hipcc into flex_amd/lib if it is not there): the largest error in ulp of expf, __expf and
    exp2f on the prescaled argument over every fp32 argument in [-104, 0] against float64 exp.
@@ -17,7 +18,11 @@ flex_edge_softmax_backward and a whole attention step.  Writes profiles/attentio
    chain of eight engine calls on the same operator against the one call, from the same kept alpha -- and the whole step (forward +
    backward through autograd) of fused_attention=True against fused_attention=True, fused_backward=True; the second part of the image
    in bytes per nonzero.  --backward: only this part (and the copy rate).
-Usage: probe_attention.py [--out FILE] [--fused | --backward] [graph ...]   (default: pubmed.csv flickr reddit soc-sign-epinions)"""
+6. Several heads (flex_attention_heads, flex_attention_heads_backward), (k, H) = (64, 4), (128, 4), (128, 8), same graphs and protocol:
+   the one-launch forward (with dP), the two-launch backward and the autograd step of attention(..., heads=H) against the loop a user
+   had before -- H single-head calls on offset pointers of a strided plan (k = d, ldb = ldc = H d); for the step, H single-head
+   attention calls of an operator of width d on column slices and a concatenation.  --heads: only this part (and the copy rate).
+Usage: probe_attention.py [--out FILE] [--fused | --backward | --heads] [graph ...]   (default: pubmed.csv flickr reddit soc-sign-epinions)"""
 import ctypes as C
 import os
 import subprocess
@@ -184,13 +189,71 @@ def probe_backward(name, a):
         del chain, fused
 
 
+def probe_heads(name, a):
+    gen = torch.Generator(device="cuda").manual_seed(4)
+    st = torch.cuda.current_stream().cuda_stream
+    for k, H in ((64, 4), (128, 4), (128, 8)):
+        d = k // H
+        multi = flex_amd.SparseOperator(a, k, learn_values=True, fused_attention=True, fused_backward=True)
+        one = flex_amd.SparseOperator(a, d, learn_values=True, fused_attention=True, fused_backward=True)  # the step of the loop
+        strided = flex_amd.Plan(a, d, ldb=k, ldc=k, attention=True, attention_backward=True)               # the calls of the loop
+        Q, K, V = (torch.rand((r, k), device="cuda", generator=gen) * 2 - 1 for r in (a.m, a.n, a.n))
+        g = torch.rand((a.m, k), device="cuda", generator=gen) * 2 - 1
+        scale = d ** -0.5
+        out, gq, gk, gv = (torch.empty((r, k), device="cuda") for r in (a.m, a.m, a.n, a.n))
+        P, W = torch.empty((a.nnz, H), device="cuda"), torch.empty((a.nnz, H), device="cuda")    # entry-major: the one call
+        P1, W1 = torch.empty((H, a.nnz), device="cuda"), torch.empty((H, a.nnz), device="cuda")  # a vector per head: the loop
+        ptr = lambda t, h: t.data_ptr() + 4 * h * d  # noqa: E731
+
+        def loop_forward():
+            for h in range(H):
+                strided.attention_ptr(ptr(Q, h), ptr(K, h), ptr(V, h), scale, ptr(out, h), P1[h].data_ptr(), st)
+
+        def loop_backward():
+            for h in range(H):
+                strided.attention_backward_ptr(ptr(Q, h), ptr(K, h), ptr(V, h), P1[h].data_ptr(), ptr(g, h), scale, ptr(gq, h), ptr(gk, h), ptr(gv, h),
+                                               W1[h].data_ptr(), st)
+
+        Qg, Kg, Vg = (x.clone().requires_grad_() for x in (Q, K, V))
+
+        def clear():
+            for x in (Qg, Kg, Vg):
+                x.grad = None
+
+        def loop_step():
+            clear()
+            torch.cat([one.attention(Qg[:, h * d:(h + 1) * d], Kg[:, h * d:(h + 1) * d], Vg[:, h * d:(h + 1) * d], scale) for h in range(H)], 1).backward(g)
+
+        def heads_step():
+            clear()
+            multi.attention(Qg, Kg, Vg, scale, heads=H).backward(g)
+
+        loop_forward()
+        multi.plan.attention(Q, K, V, scale, out=out, p=P, heads=H)
+        fns = {"forward, loop": loop_forward, "forward, heads": lambda: multi.plan.attention(Q, K, V, scale, out=out, p=P, heads=H),
+               "backward, loop": loop_backward,
+               "backward, heads": lambda: multi.plan.attention_backward(Q, K, V, P, g, scale, grad_q=gq, grad_k=gk, grad_v=gv, work=W, heads=H),
+               "step, loop": loop_step, "step, heads": heads_step}
+        n = max(3, min(100, int(1e8 / max(1, a.nnz * k))))
+        rounds = {key: [] for key in fns}
+        for _ in range(3):  # alternating: every round times each contender once
+            for key, fn in fns.items():
+                rounds[key].append(best_us(fn, n, rounds=1))
+        best = {key: min(v) for key, v in rounds.items()}
+        spread = {key: 100 * (max(v) - min(v)) / min(v) for key, v in rounds.items()}
+        say(f"{name} k={k} H={H} d={d} heads: " + "  ".join(f"{key} {best[key]:.1f} us (+{spread[key]:.0f} % over 3 rounds)" for key in fns)
+            + "  loop / heads: " + "  ".join(f"{w} {best[w + ', loop'] / best[w + ', heads']:.2f}x" for w in ("forward", "backward", "step"))
+            + f"  edge arrays of a step: {8 * a.nnz * H / 2 ** 20:.1f} MiB (P and work, nnz x H floats each) either way")
+        del multi, one, strided
+
+
 def main():
     args = sys.argv[1:]
     out = os.path.join(ROOT, "profiles", "attention_probe.txt")
     if args[:1] == ["--out"]:
         out, args = args[1], args[2:]
-    fused_only, backward_only = args[:1] == ["--fused"], args[:1] == ["--backward"]
-    if fused_only or backward_only:
+    fused_only, backward_only, heads_only = args[:1] == ["--fused"], args[:1] == ["--backward"], args[:1] == ["--heads"]
+    if fused_only or backward_only or heads_only:
         args = args[1:]
     else:
         exp_error()
@@ -198,13 +261,16 @@ def main():
     say(f"flex_hbm_probe: read {hbm['read_GBps']:.0f} GB/s, copy {hbm['copy_GBps']:.0f} GB/s")
     for name in args or ["pubmed.csv", "flickr", "reddit", "soc-sign-epinions"]:
         a = load(name)
-        if not fused_only and not backward_only:
+        only = fused_only or backward_only or heads_only
+        if not only:
             probe(name, a, hbm["copy_GBps"])
-        if not backward_only:
+        if fused_only or not only:
             probe_fused(name, a)
-        if not fused_only:
+        if backward_only or not only:
             probe_backward(name, a)
-    with open(out, "w") as f:
+        if heads_only or not only:
+            probe_heads(name, a)
+    with open(out, "a" if fused_only or backward_only or heads_only else "w") as f:  # a part is appended, the whole run starts the file
         f.write("\n".join(LINES) + "\n")
 
 
