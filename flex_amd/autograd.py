@@ -5,7 +5,9 @@ set into the plans (flex_plan_set_values) without planning again.  The same two 
 scores by flex_sddmm as a forward op, their softmax over each row of A (flex_edge_softmax), and the SpMM with the result as A's values
 (SparseOperator.attention).  fused_attention=True runs that forward as one launch (flex_attention), and fused_backward=True its backward as
 two (flex_attention_backward) instead of the chain of eight calls; with both, attention(..., heads=H) runs H heads in the same three
-launches (flex_attention_heads, flex_attention_heads_backward).  torch is imported lazily, as in binding.py."""
+launches (flex_attention_heads, flex_attention_heads_backward), and gat_attention(el, er, V) runs GAT's additive score
+LeakyReLU(el[row] + er[col]) per head in the same three launches (flex_gat_attention, flex_gat_attention_backward).  torch is imported
+lazily, as in binding.py."""
 from __future__ import annotations
 
 from . import binding
@@ -162,14 +164,35 @@ def _function():
             grads = ctx.op.plan.attention_backward(Q, K, V, p, grad_out.contiguous(), ctx.scale, want=tuple(ctx.needs_input_grad[:3]), heads=ctx.heads)
             return (*grads, None, None, None)
 
-    return _SpMM, _AxwLayer, _SpMMValues, _Sddmm, _EdgeSoftmax, _FusedAttention, _FusedAttentionHeads
+    class _FusedGatAttention(torch.autograd.Function):
+        """Out = A(alpha) V per head, alpha = softmax over each row of A of leaky_relu(el[row, h] + er[col, h], slope): flex_gat_attention
+        in one launch, alpha [nnz, heads] kept only when a gradient is needed; backward: the one call flex_gat_attention_backward (two
+        launches) for the gradients that are needed, in el, er and V.  It sets no plan's values.  Only on an operator made with
+        fused_attention=True and fused_backward=True."""
+
+        @staticmethod
+        def forward(ctx, el, er, V, op, slope):
+            el, er, V = el.contiguous(), er.contiguous(), V.contiguous()
+            p = torch.zeros((op.nnz, el.shape[1]), dtype=torch.float32, device=V.device) if any(ctx.needs_input_grad[:3]) else None
+            out = op.plan.gat_attention(el, er, V, slope, p=p)
+            ctx.op, ctx.slope = op, slope
+            ctx.save_for_backward(el, er, V, p)
+            return out
+
+        @staticmethod
+        def backward(ctx, grad_out):
+            el, er, V, p = ctx.saved_tensors
+            grads = ctx.op.plan.gat_attention_backward(el, er, V, p, grad_out.contiguous(), ctx.slope, want=tuple(ctx.needs_input_grad[:3]))
+            return (*grads, None, None)
+
+    return _SpMM, _AxwLayer, _SpMMValues, _Sddmm, _EdgeSoftmax, _FusedAttention, _FusedAttentionHeads, _FusedGatAttention
 
 
 _cache = None
 
 
 def functions():
-    """(_SpMM, _AxwLayer, _SpMMValues, _Sddmm, _EdgeSoftmax, _FusedAttention, _FusedAttentionHeads): the autograd Functions, built at first use (torch is imported then)."""
+    """(_SpMM, _AxwLayer, _SpMMValues, _Sddmm, _EdgeSoftmax, _FusedAttention, _FusedAttentionHeads, _FusedGatAttention): the autograd Functions, built at first use (torch is imported then)."""
     global _cache
     if _cache is None:
         _cache = _function()
@@ -187,7 +210,9 @@ class SparseOperator:
     fused_attention=True (with learn_values=True): the forward plan is also made with FLEX_PLAN_ATTENTION and op.attention runs its
     forward as one launch (flex_attention); the backward is the same chain of calls.
     fused_backward=True (with fused_attention=True): the forward plan is also made with FLEX_PLAN_ATTENTION_BACKWARD and the backward of
-    op.attention is one call of two launches (flex_attention_backward) that sets no plan's values.  Off by default."""
+    op.attention is one call of two launches (flex_attention_backward) that sets no plan's values.  Off by default.
+    With both fused flags the operator also offers op.gat_attention(el, er, V, negative_slope): GAT's additive attention, H = el.shape[1]
+    heads in one forward launch and two backward launches (flex_gat_attention), differentiable in el [m, H], er [n, H] and V [n, k]."""
 
     def __init__(self, a: binding.HostCsr, k: int, device: int = 0, order: int = binding.FLEX_ORDER_NATURAL, tuning: dict | None = None,
                  learn_values: bool = False, fused_attention: bool = False, fused_backward: bool = False):
@@ -259,3 +284,13 @@ class SparseOperator:
         if self.fused_attention:
             return functions()[5].apply(Q, K, V, self, float(scale))
         return self(V, values=self.edge_softmax(self.sddmm(Q, K), scale))
+
+    def gat_attention(self, el, er, V, negative_slope: float = 0.2):
+        """Out [m, k] = A(alpha) V per head with alpha = softmax over each row of A of leaky_relu(el[row, h] + er[col, h], negative_slope):
+        the attention of a GAT layer, el = <h W, a_l> and er = <h W, a_r> being one scalar per node and head.  H = el.shape[1] heads; head h
+        is columns [h k / H, (h + 1) k / H) of V and Out.  Differentiable in el [m, H], er [n, H] and V [n, k]; all heads in one forward
+        launch and two backward launches (flex_gat_attention); needs fused_attention=True and fused_backward=True."""
+        if not (self.fused_attention and self.fused_backward):
+            raise NotImplementedError("gat_attention needs SparseOperator(..., learn_values=True, fused_attention=True, fused_backward=True): "
+                                      "only the fused forward and backward compute the additive score")
+        return functions()[7].apply(el, er, V, self, float(negative_slope))

@@ -163,7 +163,7 @@ SYMBOLS = [
     "flex_last_hip_error_string", "flex_abi_version", "flex_plan_set_values", "flex_sddmm",
     "flex_edge_softmax", "flex_edge_softmax_backward", "flex_plan_softmax_info", "flex_attention", "flex_plan_attention_info",
     "flex_attention_backward", "flex_plan_attention_backward_info", "flex_attention_heads", "flex_attention_heads_backward",
-    "flex_plan_record_info", "flex_plan_read_records",
+    "flex_gat_attention", "flex_gat_attention_backward", "flex_plan_record_info", "flex_plan_read_records",
 ]
 
 _lib = None
@@ -252,7 +252,7 @@ def lib():
 
 def _values_fn(name: str):
     """flex_plan_set_values / flex_sddmm / flex_edge_softmax / flex_edge_softmax_backward / flex_attention / flex_attention_backward and the
-    two multi-head calls, looked up at first use and not when the library loads: a host-only build without the kernel files does not define them (tests/hostsim has stand-ins that only log which
+    two multi-head and the two GAT calls, looked up at first use and not when the library loads: a host-only build without the kernel files does not define them (tests/hostsim has stand-ins that only log which
     kernel the real ones would launch)."""
     L = lib()
     f = getattr(L, name)
@@ -262,7 +262,9 @@ def _values_fn(name: str):
                       "flex_edge_softmax_backward": [vp, vp, vp, fl, vp, vp], "flex_attention": [vp, vp, vp, vp, fl, vp, vp, vp],
                       "flex_attention_backward": [vp, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp],
                       "flex_attention_heads": [vp, i32, vp, vp, vp, fl, vp, vp, vp],
-                      "flex_attention_heads_backward": [vp, i32, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp]}[name]
+                      "flex_attention_heads_backward": [vp, i32, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp],
+                      "flex_gat_attention": [vp, i32, vp, vp, vp, fl, vp, vp, vp],
+                      "flex_gat_attention_backward": [vp, i32, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp]}[name]
     return f
 
 
@@ -723,6 +725,75 @@ class Plan:
         self.attention_backward_ptr(Q.data_ptr(), K.data_ptr(), V.data_ptr(), p.data_ptr(), grad_out.data_ptr(), scale,
                                     *(None if t is None else t.data_ptr() for t in outs), work.data_ptr(),
                                     torch.cuda.current_stream(Q.device).cuda_stream, heads=None if heads == 1 else heads)
+        return tuple(outs)
+
+    def gat_attention_ptr(self, heads: int, dEl_ptr: int, dEr_ptr: int, dV_ptr: int, slope: float, dOut_ptr: int, dP_ptr: int | None = None,
+                          stream: int = 0):
+        """flex_gat_attention; dEl is rows x H floats, dEr n x H, dP (optional) nnz x H, entry-major."""
+        _check(_values_fn("flex_gat_attention")(self._h, heads, dEl_ptr, dEr_ptr, dV_ptr, slope, dOut_ptr, dP_ptr, stream), "flex_gat_attention")
+
+    def _node_scalars(self, el, er):
+        """heads, from el [m, H] and er [n, H]: one float32 per node and head."""
+        import torch
+        i = self.info()
+        assert el.dim() == 2 and el.shape[1] >= 1, "el is [m, heads]"
+        heads = int(el.shape[1])
+        for t, rows in ((el, i["m"]), (er, i["n"])):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (rows, heads), "float32 cuda [rows, heads]"
+        return heads
+
+    def _gat_edge_arrays(self, heads, *ts):
+        import torch
+        for t in ts:
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (self.src_nnz, heads), "float32 cuda [nnz, heads]"
+
+    def gat_attention(self, el, er, V, slope: float = 0.2, out=None, p=None):
+        """flex_gat_attention: out [m, k] = sum over each row's entries of alpha V[col] per head, alpha = the softmax over the row of
+        leaky_relu(el[row, h] + er[col, h], slope), in one launch.  el: [m, H], er: [n, H] (H = el.shape[1] heads of k / H columns),
+        V: [n, k] like B; float32 cuda tensors.  p (optional): a float32 cuda tensor [a.nnz, H] that receives alpha in a's CSR order
+        for the plan's rows (entries of other shards keep what it held)."""
+        import torch
+        i = self.info()
+        heads = self._node_scalars(el, er)
+        assert V.is_cuda and V.dtype == torch.float32 and V.is_contiguous() and tuple(V.shape) == (i["n"], i["k"])
+        if out is None:  # every row is written, except by a plan without entries, which launches nothing
+            out = (torch.empty if i["nnz"] else torch.zeros)((i["m"], i["k"]), dtype=torch.float32, device=V.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (i["m"], i["k"])
+        if p is not None:
+            self._gat_edge_arrays(heads, p)
+        self.gat_attention_ptr(heads, el.data_ptr(), er.data_ptr(), V.data_ptr(), slope, out.data_ptr(), None if p is None else p.data_ptr(),
+                               torch.cuda.current_stream(V.device).cuda_stream)
+        return out
+
+    def gat_attention_backward_ptr(self, heads: int, dEl_ptr: int, dEr_ptr: int, dV_ptr: int, dP_ptr: int, dGradOut_ptr: int, slope: float,
+                                   dGradEl_ptr: int | None, dGradEr_ptr: int | None, dGradV_ptr: int | None, dWork_ptr: int, stream: int = 0):
+        """flex_gat_attention_backward; dP and dWork are nnz x H floats, entry-major."""
+        _check(_values_fn("flex_gat_attention_backward")(self._h, heads, dEl_ptr, dEr_ptr, dV_ptr, dP_ptr, dGradOut_ptr, slope, dGradEl_ptr, dGradEr_ptr,
+                                                         dGradV_ptr, dWork_ptr, stream), "flex_gat_attention_backward")
+
+    def gat_attention_backward(self, el, er, V, p, grad_out, slope: float = 0.2, grad_el=None, grad_er=None, grad_v=None, work=None,
+                               want=(True, True, True)):
+        """flex_gat_attention_backward: (gEl [m, H], gEr [n, H], gV [n, k]) of gat_attention()'s out from its p [a.nnz, H] and grad_out
+        [m, k], in two launches; an output that `want` does not ask for is None and is not computed.  work (optional): a float32 cuda
+        tensor [a.nnz, H], not p, that receives the gradient in el + er per entry whenever gEl or gEr is wanted."""
+        import torch
+        i = self.info()
+        heads = self._node_scalars(el, er)
+        for t, rows in ((V, i["n"]), (grad_out, i["m"])):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (rows, i["k"])
+        if work is None:
+            work = torch.empty((self.src_nnz, heads), dtype=torch.float32, device=V.device)
+        self._gat_edge_arrays(heads, p, work)
+        outs = []
+        for wanted, t, shape in zip(want, (grad_el, grad_er, grad_v), ((i["m"], heads), (i["n"], heads), (i["n"], i["k"]))):
+            if wanted and t is None:  # every row is written, except by a plan without entries, which launches nothing
+                t = (torch.empty if i["nnz"] else torch.zeros)(shape, dtype=torch.float32, device=V.device)
+            if wanted:
+                assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape
+            outs.append(t if wanted else None)
+        self.gat_attention_backward_ptr(heads, el.data_ptr(), er.data_ptr(), V.data_ptr(), p.data_ptr(), grad_out.data_ptr(), slope,
+                                        *(None if t is None else t.data_ptr() for t in outs), work.data_ptr(),
+                                        torch.cuda.current_stream(V.device).cuda_stream)
         return tuple(outs)
 
     def destroy(self):

@@ -28,6 +28,7 @@ extern "C" {
                               the equally additive FLEX_PLAN_ATTENTION, flex_attention and flex_plan_attention_info (a new flag, two new calls, one new struct),
                               the equally additive FLEX_PLAN_ATTENTION_BACKWARD, flex_attention_backward and flex_plan_attention_backward_info (the same again),
                               the equally additive flex_attention_heads and flex_attention_heads_backward (two new calls, no flag, no struct),
+                              the equally additive flex_gat_attention and flex_gat_attention_backward (the same again),
                               and the retired flex_plan_tuning.block_ablate, which keeps its place as block_ablate_retired and must be zero.
                               3: plan-time knobs leave the environment for the struct flex_plan_tuning, flex_plan_desc.tuning, flex_plan_get_tuning,
                               flex_order_cluster_ex, flex_set_host_threads; split rows are summed by a second launch by default.
@@ -493,6 +494,75 @@ int flex_attention_heads(const flex_plan *plan, int heads, const float *dQ, cons
 int flex_attention_heads_backward(const flex_plan *plan, int heads, const float *dQ, const float *dK, const float *dV, const float *dP,
                                   const float *dGradOut, float scale, float *dGradQ, float *dGradK, float *dGradV, float *dWork,
                                   flex_stream_t stream);
+
+/* Fused GAT attention: the additive score of graph attention networks in place of the dot product, H heads in the ONE forward launch and
+ * the TWO backward launches of flex_attention_heads and flex_attention_heads_backward, on the same plans (FLEX_PLAN_ATTENTION;
+ * FLEX_PLAN_ATTENTION_BACKWARD for the second call; FLEX_ERR_INVALID on any other plan).  No new plan flag and no new image: the
+ * schedule depends on k and the pattern only, so one plan serves dot-product and GAT attention alike, for every H.  No reference
+ * counterpart.  k = H d.  Head h owns columns [h d, (h + 1) d) of V, Out, g and gV.  dEl is [rows of the plan, H] floats, contiguous,
+ * with Q's row convention (a shard's row r0 + i is row i); dEr is [hostA->n, H] floats, contiguous; both hold one scalar per node and
+ * head (in a GAT layer el = <h_r W, a_l>, er = <h_c W, a_r>).  dP and dWork hold hostA->nnz x H floats, entry-major, exactly as for
+ * flex_attention_heads.  For row r, entry e in hostA's CSR order, src(e) = hostA->col[e], head h:
+ *     x_eh     = el[r, h] + er[src(e), h]
+ *     s_eh     = x_eh > 0 ? x_eh : slope x_eh                   (torch.nn.functional.leaky_relu: 0 takes the slope branch)
+ *     alpha_eh = flex_edge_softmax's softmax of s_.h over the row, scale 1
+ *     Out[r, head h] = sum_e alpha_eh V[src(e), head h]
+ * Backward, with p = the dP the forward wrote and g = dGradOut (Out's shape and stride ldc):
+ *     da_eh    = <g[r, head h], V[src(e), head h]>              (over the head's d columns)
+ *     delta_rh = sum_j p_jh da_jh                               (over the row's entries)
+ *     dz_eh    = p_eh (da_eh - delta_rh)
+ *     dx_eh    = x_eh > 0 ? dz_eh : slope dz_eh                 (x recomputed from el and er; nothing else is kept)
+ *     gEl[r, h]      = sum_{e in row r}      dx_eh
+ *     gEr[c, h]      = sum_{e: src(e) == c}  dx_eh
+ *     gV[c, head h]  = sum_{e: src(e) == c}  p_eh g[row(e), head h]
+ * gEl has dEl's shape, gEr has dEr's, gV has V's (stride ldb).  Special values follow the existing calls through the formulas, with no
+ * new rule.  slope must be finite with 0 < slope <= 1 (else FLEX_ERR_INVALID); with slope > 0 a -inf sum stays -inf, so er[c, h] = -inf
+ * masks source node c for head h and el[r, h] = -inf masks row r for head h: such entries have p exactly +0, and a fully masked row
+ * and a row without entries write +0.  A NaN or +inf score (+inf + -inf included) poisons its row for that head only: NaN in that
+ * head's d columns of Out and that head's entries of dP.  Every entry, masked or not, multiplies its V row.  The backward is the
+ * formulas in fp32 under IEEE; a NaN x takes the slope branch, the comparison being false.  Rows of gEl without entries, and rows of
+ * gEr / gV whose column has no entry, are written as +0.
+ * Checks: heads < 1, a bad slope, a NULL operand (El, Er, V, Out; in the backward El, Er, V, P, GradOut, Work) and dWork == dP:
+ * FLEX_ERR_INVALID.  k % heads != 0; d outside {4, 8, 16, 32, 64, 128, 256}, for every H, H = 1 included (there is no single-head
+ * form to forward to: k = 300 is refused here); k > 1024; ldb % 4, ldc % 4 or a row operand (V, Out, g, gV) that is not 16-byte
+ * aligned (only the 16-byte form is built, as for flex_attention_heads; el, er, gEl and gEr need the alignment of a float only):
+ * FLEX_ERR_UNSUPPORTED.  A plan without entries: FLEX_OK, no launch, nothing written.  dP may be NULL (Out has the same bits either
+ * way); the forward on a row-range shard writes the dP entries of its rows and leaves the others untouched (the backward is not
+ * defined on shards, as for flex_attention_heads_backward); each of dGradEl, dGradEr, dGradV may be NULL, an output has the same bits
+ * whichever others are asked for, and a launch without outputs is skipped (the rows' launch writes gEl, the columns' gEr and gV); on
+ * return dWork holds dx whenever dGradEl or dGradEr was asked for.  Asynchronous on `stream`, no allocation, no host synchronisation
+ * (safe to capture in a hipGraph), no atomics, fixed reduction order: bit-identical run to run.  The walk is flex_attention_heads's;
+ * a score needs no K row and no reduction across lanes (per entry one V row and H floats of er are gathered), the second sweep of the
+ * rows' backward launch gathers nothing, and the columns' launch gathers g alone.
+ *
+ * Accuracy, with the u, gamma, E, D_r and R_r of flex_attention; forward against float64 on the fp32 inputs, backward against float64 on
+ * the SAME fp32 el, er, V, p and g.  The float64 reference takes the branch of the leaky ReLU from the sign of the fp32 sum
+ * fl(el + er), which is what the kernel sees (the sum of two floats is zero only where it is exactly zero, so the signs agree wherever
+ * the float64 sum is finite), and uses the fp32 value of slope.
+ *   score   ds_e     = gamma(2) |s_e| + 2^-149                  (in place of gamma(k) sum |Q K| + k 2^-149)
+ *   alpha   dalpha_e = alpha_e [gamma(n_r + 4 D_r + (E + 3) R_r + 2 E + 4) + expm1(2 max_row(ds + |s| u))] + 2^-126
+ *   Out     |Out - Out64| <= sum_e (gamma(n_r + 3) alpha_e + dalpha_e) |V| + 2^-126
+ *   dda_e    = gamma(d) sum_j |g V| + d 2^-149                  (over the head's d columns)
+ *   ddz_e    = gamma(n_r + 3) p_e (|da_e| + sum_j |p_j da_j|) + p_e (dda_e + sum_j p_j dda_j) + n_r 2^-149
+ *   ddx_e    = f_e ddz_e + u |dx_e| + 2^-149,   f_e = 1 where x_e > 0, else slope
+ *   |gEl - gEl64| <= sum_{e in r} (gamma(n_r) |dx_e| + ddx_e) + 2^-126
+ *   |gEr - gEr64| <= sum_{e in c} (gamma(n_c) |dx_e| + ddx_e) + 2^-126
+ *   |gV  - gV64|  <= sum_{e in c}  gamma(n_c) p_e |g[row]|    + 2^-126
+ * dP is held to dalpha and dWork to ddx on their own.  Derivation.  x = fl(el + er) is one rounded sum and s = fl(slope x) at most one
+ * more product, which may round as a subnormal: gamma(2) |s| + 2^-149.  From the scores on, alpha and Out are flex_attention's derivation
+ * with scale = 1: the passes, rescales and merges are the same code, so R_r and c = 3 stand.  da is flex_attention_heads_backward's
+ * reduction over the d columns of the head (a chain of four fmas per lane, a tree over the d / 4 lanes).  delta is summed by fma in a tree
+ * of depth <= n_r and dz = fl(p fl(da - delta)) is one subtraction and one product, inside flex_attention_backward's a = 3 (which counted a
+ * second product, scale p): ddz is its dds with scale = 1.  dx = dz exactly or fl(slope dz), one rounding that may be subnormal: ddx.
+ * gEl adds the computed dx plainly: a chain on each owning lane, a butterfly over the lanes of the head, then the merges over slots and
+ * waves; additions of the zeros that the other lanes hold are exact, so the n_r terms meet in a tree of depth < n_r: gamma(n_r) |dx|.
+ * gEr adds dx in a chain per slot and the same merges, depth <= n_c.  gV is flex_attention_backward's with b = 0, and its ratio comes
+ * close to 1 on columns of one entry for the reason given there.  First order, as the bounds above. */
+int flex_gat_attention(const flex_plan *plan, int heads, const float *dEl, const float *dEr, const float *dV, float slope, float *dOut,
+                       float *dP, flex_stream_t stream);
+int flex_gat_attention_backward(const flex_plan *plan, int heads, const float *dEl, const float *dEr, const float *dV, const float *dP,
+                                const float *dGradOut, float slope, float *dGradEl, float *dGradEr, float *dGradV, float *dWork,
+                                flex_stream_t stream);
 
 /* ≙ alpha_freeMatGPU (mat.cuh:184-193). */
 int flex_plan_destroy(flex_plan *plan);

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Sparse graph attention, measured: the error of the exponential the edge softmax may use, and the time of flex_edge_softmax,
 flex_edge_softmax_backward and a whole attention step.  Writes profiles/attention_probe.txt (or the file given with --out): the whole run
-starts the file, a run of one part (--fused, --backward, --heads) appends to it.
+starts the file, a run of one part (--fused, --backward, --heads, --gat) appends to it.
 
 1. tools/exp_error.hip (built here with hipcc into flex_amd/lib if it is not there): the largest error in ulp of expf, __expf and
    exp2f on the prescaled argument over every fp32 argument in [-104, 0] against float64 exp.
@@ -22,7 +22,12 @@ starts the file, a run of one part (--fused, --backward, --heads) appends to it.
    the one-launch forward (with dP), the two-launch backward and the autograd step of attention(..., heads=H) against the loop a user
    had before -- H single-head calls on offset pointers of a strided plan (k = d, ldb = ldc = H d); for the step, H single-head
    attention calls of an operator of width d on column slices and a concatenation.  --heads: only this part (and the copy rate).
-Usage: probe_attention.py [--out FILE] [--fused | --backward | --heads] [graph ...]   (default: pubmed.csv flickr reddit soc-sign-epinions)"""
+7. GAT's additive attention (flex_gat_attention, flex_gat_attention_backward), (k, H) = (64, 8), (128, 4), (256, 8), same graphs and
+   protocol: the one-launch forward (with dP), the two-launch backward and the autograd step of gat_attention against what a user had
+   before -- per head, torch index arithmetic for the scores on a row / col copy of the pattern, edge_softmax and the SpMM with
+   values=alpha of an operator of width d on a column slice, torch autograd carrying the gradients of el and er.  --gat: only this
+   part (and the copy rate).
+Usage: probe_attention.py [--out FILE] [--fused | --backward | --heads | --gat] [graph ...]   (default: pubmed.csv flickr reddit soc-sign-epinions)"""
 import ctypes as C
 import os
 import subprocess
@@ -247,13 +252,79 @@ def probe_heads(name, a):
         del multi, one, strided
 
 
+def probe_gat(name, a):
+    import numpy as np
+    gen = torch.Generator(device="cuda").manual_seed(5)
+    rp = a.rowPtr.astype(np.int64)
+    rows = torch.from_numpy(np.repeat(np.arange(a.m), np.diff(rp))).cuda()
+    cols = torch.from_numpy(a.col.astype(np.int64)).cuda()
+    slope = 0.2
+    for k, H in ((64, 8), (128, 4), (256, 8)):
+        d = k // H
+        fused = flex_amd.SparseOperator(a, k, learn_values=True, fused_attention=True, fused_backward=True)
+        one = flex_amd.SparseOperator(a, d, learn_values=True)  # what a user had: one head at a time on a column slice
+        el, er = (torch.rand((r, H), device="cuda", generator=gen) * 4 - 2 for r in (a.m, a.n))
+        V = torch.rand((a.n, k), device="cuda", generator=gen) * 2 - 1
+        g = torch.rand((a.m, k), device="cuda", generator=gen) * 2 - 1
+        out, gv = torch.empty((a.m, k), device="cuda"), torch.empty((a.n, k), device="cuda")
+        gel, ger = torch.empty((a.m, H), device="cuda"), torch.empty((a.n, H), device="cuda")
+        P, W = torch.empty((a.nnz, H), device="cuda"), torch.empty((a.nnz, H), device="cuda")
+        elg, erg, Vg = (x.clone().requires_grad_() for x in (el, er, V))
+
+        def loop(el, er, V):
+            outs = []
+            for h in range(H):
+                s = torch.nn.functional.leaky_relu(el[rows, h] + er[cols, h], slope)
+                outs.append(one(V[:, h * d:(h + 1) * d].contiguous(), values=one.edge_softmax(s)))
+            return torch.cat(outs, 1)
+
+        def loop_forward():
+            with torch.no_grad():
+                loop(el, er, V)
+
+        def clear():
+            for x in (elg, erg, Vg):
+                x.grad = None
+
+        kept = loop(elg, erg, Vg)
+
+        def loop_backward():
+            clear()
+            kept.backward(g, retain_graph=True)
+
+        def loop_step():
+            clear()
+            loop(elg, erg, Vg).backward(g)
+
+        def fused_step():
+            clear()
+            fused.gat_attention(elg, erg, Vg, slope).backward(g)
+
+        fused.plan.gat_attention(el, er, V, slope, out=out, p=P)
+        fns = {"forward, loop": loop_forward, "forward, fused": lambda: fused.plan.gat_attention(el, er, V, slope, out=out, p=P),
+               "backward, loop": loop_backward,
+               "backward, fused": lambda: fused.plan.gat_attention_backward(el, er, V, P, g, slope, grad_el=gel, grad_er=ger, grad_v=gv, work=W),
+               "step, loop": loop_step, "step, fused": fused_step}
+        n = max(3, min(100, int(1e8 / max(1, a.nnz * k))))
+        rounds = {key: [] for key in fns}
+        for _ in range(3):  # alternating: every round times each contender once
+            for key, fn in fns.items():
+                rounds[key].append(best_us(fn, n, rounds=1))
+        best = {key: min(v) for key, v in rounds.items()}
+        spread = {key: 100 * (max(v) - min(v)) / min(v) for key, v in rounds.items()}
+        say(f"{name} k={k} H={H} d={d} gat: " + "  ".join(f"{key} {best[key]:.1f} us (+{spread[key]:.0f} % over 3 rounds)" for key in fns)
+            + "  loop / fused: " + "  ".join(f"{w} {best[w + ', loop'] / best[w + ', fused']:.2f}x" for w in ("forward", "backward", "step"))
+            + f"  edge arrays of a step: {8 * a.nnz * H / 2 ** 20:.1f} MiB (P and work, nnz x H floats each)")
+        del fused, one, kept
+
+
 def main():
     args = sys.argv[1:]
     out = os.path.join(ROOT, "profiles", "attention_probe.txt")
     if args[:1] == ["--out"]:
         out, args = args[1], args[2:]
-    fused_only, backward_only, heads_only = args[:1] == ["--fused"], args[:1] == ["--backward"], args[:1] == ["--heads"]
-    if fused_only or backward_only or heads_only:
+    fused_only, backward_only, heads_only, gat_only = (args[:1] == [flag] for flag in ("--fused", "--backward", "--heads", "--gat"))
+    if fused_only or backward_only or heads_only or gat_only:
         args = args[1:]
     else:
         exp_error()
@@ -261,7 +332,7 @@ def main():
     say(f"flex_hbm_probe: read {hbm['read_GBps']:.0f} GB/s, copy {hbm['copy_GBps']:.0f} GB/s")
     for name in args or ["pubmed.csv", "flickr", "reddit", "soc-sign-epinions"]:
         a = load(name)
-        only = fused_only or backward_only or heads_only
+        only = fused_only or backward_only or heads_only or gat_only
         if not only:
             probe(name, a, hbm["copy_GBps"])
         if fused_only or not only:
@@ -270,7 +341,9 @@ def main():
             probe_backward(name, a)
         if heads_only or not only:
             probe_heads(name, a)
-    with open(out, "a" if fused_only or backward_only or heads_only else "w") as f:  # a part is appended, the whole run starts the file
+        if gat_only or not only:
+            probe_gat(name, a)
+    with open(out, "a" if fused_only or backward_only or heads_only or gat_only else "w") as f:  # a part is appended, the whole run starts the file
         f.write("\n".join(LINES) + "\n")
 
 
