@@ -20,8 +20,7 @@
 #include <cmath>
 #include <cstdint>
 
-#include "attention_device.h"
-#include "plan.h"
+#include "attention_host.h"
 
 namespace flex {
 namespace attention {
@@ -299,19 +298,6 @@ struct Operands {
     float *GQ, *GK, *GV, *Work;
 };
 
-template <int W, int NS>
-static void launch_backward(const View &rv, const ColumnView &cv, bool vec, dim3 rgrid, dim3 cgrid, const Operands &o, hipStream_t s) {
-    const dim3 block(64 * kWavesPerBlock);
-    if (o.GQ || o.GK) {
-        if (vec) hipLaunchKernelGGL((attention_rows_backward<W, NS, true>), rgrid, block, 0, s, rv, o.K, o.V, o.P, o.G, o.scale, o.GQ, o.Work);
-        else hipLaunchKernelGGL((attention_rows_backward<W, NS, false>), rgrid, block, 0, s, rv, o.K, o.V, o.P, o.G, o.scale, o.GQ, o.Work);
-    }
-    if (o.GK || o.GV) {
-        if (vec) hipLaunchKernelGGL((attention_columns_backward<W, NS, true>), cgrid, block, 0, s, cv, o.Q, o.G, o.P, o.Work, o.GK, o.GV);
-        else hipLaunchKernelGGL((attention_columns_backward<W, NS, false>), cgrid, block, 0, s, cv, o.Q, o.G, o.P, o.Work, o.GK, o.GV);
-    }
-}
-
 }  // namespace attention
 }  // namespace flex
 
@@ -332,28 +318,22 @@ int flex_attention_backward(const flex_plan *p, const float *dQ, const float *dK
     pick.vec4 = pick.vec4 && attention_pick(p->k, p->ldb, p->ldc, dGradQ, dGradK, dGradV, nullptr).vec4;
     const DeviceScope on(p->device);
     FLEX_HIP_TRY(on.error());
-    const uint32_t remap = p->xcd_remap ? 1u : 0u;
-    const attention::View rv{p->d_at_rowptr.get(), p->d_at_src.get(), p->d_at_item.get(), p->d_at_grp.get(), p->at_first_entry,
-                             p->n_at_groups, p->n_at_wave_items, p->n_at_block_rows, remap, p->k, p->ldb, p->ldc};
-    const attention::ColumnView cv{p->d_ab_colptr.get(), p->d_ab_ent.get(), p->d_ab_item.get(), p->d_ab_grp.get(),
-                                   p->n_ab_groups, p->n_ab_wave_items, p->n_ab_block_cols, remap, p->k, p->ldb, p->ldc};
-    auto grid_of = [&](uint32_t groups, uint32_t blocks) {
-        uint32_t wgs = (groups + kWavesPerBlock - 1) / kWavesPerBlock;
-        if (remap) wgs = (wgs + kXcds - 1) / kXcds * kXcds;
-        return dim3(blocks + wgs);
-    };
-    const dim3 rgrid = grid_of(p->n_at_groups, p->n_at_block_rows), cgrid = grid_of(p->n_ab_groups, p->n_ab_block_cols);
+    const attention::View rv = attention::row_view(p);
+    const attention::ColumnView cv = attention::column_view(p);
+    const dim3 rgrid = attention::launch_grid(rv), cgrid = attention::launch_grid(cv), block(64 * kWavesPerBlock);
     const attention::Operands o{dQ, dK, dV, dP, dGradOut, scale, dGradQ, dGradK, dGradV, dWork};
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    switch (pick.W * 8 + pick.NS) {
-        case 4 * 8 + 1: attention::launch_backward<4, 1>(rv, cv, pick.vec4, rgrid, cgrid, o, s); break;
-        case 8 * 8 + 1: attention::launch_backward<8, 1>(rv, cv, pick.vec4, rgrid, cgrid, o, s); break;
-        case 16 * 8 + 1: attention::launch_backward<16, 1>(rv, cv, pick.vec4, rgrid, cgrid, o, s); break;
-        case 32 * 8 + 1: attention::launch_backward<32, 1>(rv, cv, pick.vec4, rgrid, cgrid, o, s); break;
-        case 64 * 8 + 1: attention::launch_backward<64, 1>(rv, cv, pick.vec4, rgrid, cgrid, o, s); break;
-        case 64 * 8 + 2: attention::launch_backward<64, 2>(rv, cv, pick.vec4, rgrid, cgrid, o, s); break;
-        default: attention::launch_backward<64, 4>(rv, cv, pick.vec4, rgrid, cgrid, o, s); break;
-    }
+    attention::dispatch(pick, [&](auto W, auto NS) {
+        using namespace attention;
+        if (o.GQ || o.GK) {
+            if (pick.vec4) hipLaunchKernelGGL((attention_rows_backward<W(), NS(), true>), rgrid, block, 0, s, rv, o.K, o.V, o.P, o.G, o.scale, o.GQ, o.Work);
+            else hipLaunchKernelGGL((attention_rows_backward<W(), NS(), false>), rgrid, block, 0, s, rv, o.K, o.V, o.P, o.G, o.scale, o.GQ, o.Work);
+        }
+        if (o.GK || o.GV) {
+            if (pick.vec4) hipLaunchKernelGGL((attention_columns_backward<W(), NS(), true>), cgrid, block, 0, s, cv, o.Q, o.G, o.P, o.Work, o.GK, o.GV);
+            else hipLaunchKernelGGL((attention_columns_backward<W(), NS(), false>), cgrid, block, 0, s, cv, o.Q, o.G, o.P, o.Work, o.GK, o.GV);
+        }
+    });
     FLEX_HIP_TRY(hipGetLastError());
     return FLEX_OK;
 }

@@ -1,6 +1,8 @@
-// attention_device.h -- what the kernels of the fused attention share (device side): the view of the row walk and the column, dot,
-// axpy and slot-reduction helpers, the forward's softmax state and the backward's line ownership, of attention_kernels.hip (flex_attention),
-// attention_backward_kernels.hip (flex_attention_backward) and attention_heads_kernels.hip (their multi-head forms).
+// attention_device.h -- what the kernels of the fused attention share on the device: the views of the row walk and of the column walk,
+// the column, dot, axpy and slot-reduction helpers, the forward's softmax state, the backward's plain sums, the one slot placement of all
+// nine kernels (place_of) and the head split of the per-head kernels.  Used by attention_kernels.hip (flex_attention),
+// attention_backward_kernels.hip (flex_attention_backward), attention_heads_kernels.hip (their multi-head forms) and
+// attention_gat_kernels.hip (the GAT forms); what their entry points share on the host is attention_host.h.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -148,7 +150,7 @@ __device__ __forceinline__ void write_row(float *__restrict__ orow, const State<
     }
 }
 
-// ---- the backward's column view, plain sums and line ownership (attention_backward_kernels.hip, attention_heads_kernels.hip)
+// ---- the backward's column view and plain sums, and the ownership of a line in every kernel
 
 struct ColumnView {
     const uint32_t *colptr;  // first position of every column in ent
@@ -160,7 +162,8 @@ struct ColumnView {
     int32_t k, ldb, ldc;
 };
 
-enum BackwardKind : int { kSlotLine = 0, kWaveLine = 1, kBlockLine = 2 };
+// how a line (a row of View, a column of ColumnView) is owned: internal.h, attention_row_class
+enum LineKind : int { kSlotLine = 0, kWaveLine = 1, kBlockLine = 2 };
 
 __device__ __forceinline__ float4 add4(const float4 &a, const float4 &b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 
@@ -177,8 +180,22 @@ __device__ __forceinline__ void sum_slots(float4 (&a)[NS], uint32_t lane) {
     }
 }
 
-// The slot's line (a row of the row kernel, a column of the column kernel), its entries and its place in the team that shares the line:
-// the forward's ownership (attention_kernels.hip, run_item).  ptr is the row pointer or the column pointer.
+// a <- the sum of the scalars `a` of the 64 / W slots of a wave, on every lane: a butterfly over the slots, the lower slot's first
+template <int W, int NS>
+__device__ __forceinline__ void sum_slot_scalars(float (&a)[NS], uint32_t lane) {
+#pragma unroll
+    for (int off = W; off < 64; off <<= 1) {
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const float o = __shfl_xor(a[s], off);
+            a[s] = (lane & static_cast<uint32_t>(off)) ? o + a[s] : a[s] + o;
+        }
+    }
+}
+
+// The slot's line (a row of a row kernel, a column of a column kernel), its entries and its place in the team that shares the line: member
+// t of a team of T slots takes the passes t, t + T, ... of kAtPass entries.  n_pass is the same for every lane of the wave (a slot past
+// its line's end idles under a predicate), so every shuffle of a sweep is wave-wide.  ptr is the row pointer or the column pointer.
 struct Place {
     uint32_t line, len, t, T, n_pass;
     uint64_t first;
@@ -211,6 +228,75 @@ __device__ __forceinline__ Place place_of(const uint32_t *__restrict__ ptr, cons
     }
     return pl;
 }
+
+// ---- the head split of the per-head kernels (attention_heads_kernels.hip, attention_gat_kernels.hip)
+
+// how the lanes of a slot split into heads: lg = log2(HW); H floats per entry in the edge arrays (and per row in GAT's el / er)
+struct HeadSplit {
+    int32_t H, lg;
+};
+
+// what a lane knows about its place in its head: r = its index among the head's lanes, wm = the mask of the writer rule: of the HW lanes
+// of a head, lane r writes entry u of a pass where u == r (HW >= 4) or u % HW == r (HW = 1, 2)
+struct HeadLane {
+    uint32_t hw, r, wm;
+    __device__ __forceinline__ HeadLane(const HeadSplit &hs, uint32_t li) : hw(1u << hs.lg), r(li & (hw - 1u)), wm((hw < static_cast<uint32_t>(U) ? hw : static_cast<uint32_t>(U)) - 1u) {}
+    __device__ __forceinline__ bool writes(int u) const { return (static_cast<uint32_t>(u) & wm) == r; }
+};
+
+// what a lane knows of its columns per slab: the head they belong to and whether they lie below k
+template <int W, int NS>
+struct LaneHeads {
+    uint32_t head[NS];
+    bool live[NS];
+    __device__ __forceinline__ LaneHeads(const HeadSplit &hs, uint32_t li, int k) {
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            head[s] = (li + static_cast<uint32_t>(W * s)) >> hs.lg;
+            live[s] = 4 * static_cast<int>(li) + 4 * W * s < k;
+        }
+    }
+};
+
+// The sum of x over the hw lanes of the lane's head, on every one of them: a butterfly from the widest step down -- the tree of
+// slot_totals<hw>.  Both lanes of a pair add the same two operands, so all lanes of the head hold the same bits.  hw is the same for the
+// whole wave: every shuffle is wave-wide.
+template <int W>
+__device__ __forceinline__ float head_total(float x, uint32_t hw) {
+#pragma unroll
+    for (int o = W / 2; o >= 1; o >>= 1) {
+        if (static_cast<uint32_t>(o) < hw) x += __shfl_xor(x, o);
+    }
+    return x;
+}
+
+// the per-slab states of the 64 / W slots of a wave, merged on every lane: a butterfly over the slots, the lower slot's state first
+template <int W, int NS>
+__device__ __forceinline__ void merge_slots_heads(State<1> (&st)[NS], uint32_t lane, float scale) {
+#pragma unroll
+    for (int off = W; off < 64; off <<= 1) {
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            State<1> o;
+            o.m = __shfl_xor(st[s].m, off);
+            o.l = __shfl_xor(st[s].l, off);
+            o.acc[0] = shfl_xor4(st[s].acc[0], off);
+            if (lane & static_cast<uint32_t>(off)) {
+                merge(o, st[s], scale);
+                st[s] = o;
+            } else {
+                merge(st[s], o, scale);
+            }
+        }
+    }
+}
+
+// where the waves of a block row meet: (m, l) of every group of four columns (the lanes of a head hold the same pair) and the Out rows
+template <int W, int NS>
+struct HeadsShared {
+    float2 ml[kWavesPerBlock][W * NS];
+    alignas(16) float acc[kWavesPerBlock][4 * W * NS];
+};
 
 }  // namespace attention
 }  // namespace flex

@@ -5,9 +5,9 @@
 // The walk is attention_heads_kernels.hip's (attention_device.h): the same view, items, groups, slot / wave / block ownership by
 // place_of, W = sddmm_lanes(k) lanes per slot, four entries per pass, four columns per lane and slab, the XCD remap, State<1> per lane
 // and slab, merge, write_row, the mask and poison logic, ColumnView for the second backward launch.  A head is HW = d / 4 whole lanes
-// of one slab; HW is a launch argument (its log2), so there is one instantiation per (W, NS).  Split, HeadLane, head_total and
-// merge_slots below restate HeadSplit, HeadLane, head_total and merge_slots_heads of attention_heads_kernels.hip word for word: that
-// file keeps its own so that none of its instantiations changes.  What differs from the dot-product heads:
+// of one slab; HW is a launch argument (its log2), so there is one instantiation per (W, NS).  The head split (HeadSplit, HeadLane,
+// LaneHeads, head_total, merge_slots_heads, HeadsShared, sum_slot_scalars) is attention_device.h's, split_of attention_host.h's; namespace
+// gat holds what is GAT's alone.  What differs from the dot-product heads:
 //   forward        no K gather and no reduction across lanes for a score: per row a lane loads el[r, head] once, per entry
 //                  er[src, head] -- one float, the lanes of a head reading the same address, the H heads of an entry one contiguous run --
 //                  together with the four V gathers of the pass; scale = 1
@@ -19,106 +19,26 @@
 #include <cmath>
 #include <cstdint>
 
-#include "attention_device.h"
-#include "plan.h"
+#include "attention_host.h"
 
 namespace flex {
 namespace attention {
 namespace gat {
 
-// how the lanes of a slot split into heads: lg = log2(HW); H floats per entry in the edge arrays and per row in el / er
-struct Split {
-    int32_t H, lg;
-};
-
-// what a lane knows about its place in its head: r = its index among the head's lanes, wm = the mask of the writer rule
-struct HeadLane {
-    uint32_t hw, r, wm;
-    __device__ __forceinline__ HeadLane(const Split &hs, uint32_t li) : hw(1u << hs.lg), r(li & (hw - 1u)), wm((hw < static_cast<uint32_t>(U) ? hw : static_cast<uint32_t>(U)) - 1u) {}
-    __device__ __forceinline__ bool writes(int u) const { return (static_cast<uint32_t>(u) & wm) == r; }
-};
-
-// The sum of x over the hw lanes of the lane's head, on every one of them: a butterfly from the widest step down.  Both lanes of a pair
-// add the same two operands, so all lanes of the head hold the same bits.  hw is the same for the whole wave: every shuffle is wave-wide.
-template <int W>
-__device__ __forceinline__ float head_total(float x, uint32_t hw) {
-#pragma unroll
-    for (int o = W / 2; o >= 1; o >>= 1) {
-        if (static_cast<uint32_t>(o) < hw) x += __shfl_xor(x, o);
-    }
-    return x;
-}
-
-// a <- the sum of the scalars `a` of the 64 / W slots of a wave, on every lane: a butterfly over the slots, the lower slot's first
-template <int W, int NS>
-__device__ __forceinline__ void sum_slot_scalars(float (&a)[NS], uint32_t lane) {
-#pragma unroll
-    for (int off = W; off < 64; off <<= 1) {
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const float o = __shfl_xor(a[s], off);
-            a[s] = (lane & static_cast<uint32_t>(off)) ? o + a[s] : a[s] + o;
-        }
-    }
-}
-
 // torch.nn.functional.leaky_relu: 0 and NaN take the slope branch (the comparison is false)
 __device__ __forceinline__ float leaky(float x, float slope) { return x > 0.f ? x : slope * x; }
-
-// what a lane holds of its row (or knows of its columns) per slab: the head, whether its columns lie below k, el[r, head]
-template <int NS>
-struct LaneHeads {
-    uint32_t head[NS];
-    bool live[NS];
-    template <int W>
-    __device__ __forceinline__ void init(const Split &hs, uint32_t li, int k) {
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            head[s] = (li + static_cast<uint32_t>(W * s)) >> hs.lg;
-            live[s] = 4 * static_cast<int>(li) + 4 * W * s < k;
-        }
-    }
-};
 
 // ---- forward
 
 template <int W, int NS>
-__device__ __forceinline__ void merge_slots(State<1> (&st)[NS], uint32_t lane) {
-#pragma unroll
-    for (int off = W; off < 64; off <<= 1) {
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            State<1> o;
-            o.m = __shfl_xor(st[s].m, off);
-            o.l = __shfl_xor(st[s].l, off);
-            o.acc[0] = shfl_xor4(st[s].acc[0], off);
-            if (lane & static_cast<uint32_t>(off)) {
-                merge(o, st[s], 1.f);
-                st[s] = o;
-            } else {
-                merge(st[s], o, 1.f);
-            }
-        }
-    }
-}
-
-// where the waves of a block row meet: (m, l) of every group of four columns (the lanes of a head hold the same pair) and the Out rows
-template <int W, int NS>
-struct Shared {
-    float2 ml[kWavesPerBlock][W * NS];
-    alignas(16) float acc[kWavesPerBlock][4 * W * NS];
-};
-
-template <int W, int NS>
-__device__ __forceinline__ void run_item(const View &v, const Split &hs, const uint4 &it, int kind, const float *__restrict__ El,
+__device__ __forceinline__ void run_item(const View &v, const HeadSplit &hs, const uint4 &it, int kind, const float *__restrict__ El,
                                          const float *__restrict__ Er, const float *__restrict__ V, float slope, float *__restrict__ Out,
-                                         float *__restrict__ P, uint32_t lane, uint32_t w, Shared<W, NS> &sh) {
+                                         float *__restrict__ P, uint32_t lane, uint32_t w, HeadsShared<W, NS> &sh) {
     const uint32_t slot = lane / W, li = lane % W;
     const int slot_lane0 = static_cast<int>(lane - li);
     const HeadLane hl(hs, li);
     const Place pl = place_of<W>(v.rowptr, it, kind, slot, w);
-    LaneHeads<NS> lh;
-    lh.template init<W>(hs, li, v.k);
+    const LaneHeads<W, NS> lh(hs, li, v.k);
     float elr[NS];
     State<1> st[NS];
 #pragma unroll
@@ -180,7 +100,7 @@ __device__ __forceinline__ void run_item(const View &v, const Split &hs, const u
             }
         }
     }
-    if (kind != kSlotLine) merge_slots<W, NS>(st, lane);
+    if (kind != kSlotLine) merge_slots_heads<W, NS>(st, lane, 1.f);
     bool writer = kind == kSlotLine ? pl.has_line : slot == 0;
     if (kind == kBlockLine) {
         if (slot == 0) {
@@ -234,9 +154,9 @@ __device__ __forceinline__ void run_item(const View &v, const Split &hs, const u
 
 // Grid: as attention_rows.
 template <int W, int NS>
-__global__ __launch_bounds__(256) void gat_rows(View v, Split hs, const float *__restrict__ El, const float *__restrict__ Er, const float *__restrict__ V,
+__global__ __launch_bounds__(256) void gat_rows(View v, HeadSplit hs, const float *__restrict__ El, const float *__restrict__ Er, const float *__restrict__ V,
                                                  float slope, float *__restrict__ Out, float *__restrict__ P) {
-    __shared__ Shared<W, NS> sh;
+    __shared__ HeadsShared<W, NS> sh;
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
     if (blockIdx.x < v.n_block_rows) {
         run_item<W, NS>(v, hs, v.item[v.n_wave_items + blockIdx.x], kBlockLine, El, Er, V, slope, Out, P, lane, w, sh);
@@ -266,7 +186,7 @@ struct RowShared {
 };
 
 template <int W, int NS>
-__device__ __forceinline__ void run_row(const View &v, const Split &hs, const uint4 &it, int kind, const float *__restrict__ El,
+__device__ __forceinline__ void run_row(const View &v, const HeadSplit &hs, const uint4 &it, int kind, const float *__restrict__ El,
                                         const float *__restrict__ Er, const float *__restrict__ V, const float *__restrict__ P,
                                         const float *__restrict__ G, float slope, float *__restrict__ GEl, float *__restrict__ Work, uint32_t lane,
                                         uint32_t w, RowShared<W, NS> &sh) {
@@ -274,8 +194,7 @@ __device__ __forceinline__ void run_row(const View &v, const Split &hs, const ui
     const int slot_lane0 = static_cast<int>(lane - li);
     const HeadLane hl(hs, li);
     const Place pl = place_of<W>(v.rowptr, it, kind, slot, w);
-    LaneHeads<NS> lh;
-    lh.template init<W>(hs, li, v.k);
+    const LaneHeads<W, NS> lh(hs, li, v.k);
     float4 g[NS];
     float elr[NS], delta[NS];
     const float *grow = G + static_cast<size_t>(pl.line) * v.ldc;
@@ -382,7 +301,7 @@ __device__ __forceinline__ void run_row(const View &v, const Split &hs, const ui
 }
 
 template <int W, int NS>
-__global__ __launch_bounds__(256) void gat_rows_backward(View v, Split hs, const float *__restrict__ El, const float *__restrict__ Er,
+__global__ __launch_bounds__(256) void gat_rows_backward(View v, HeadSplit hs, const float *__restrict__ El, const float *__restrict__ Er,
                                                           const float *__restrict__ V, const float *__restrict__ P, const float *__restrict__ G,
                                                           float slope, float *__restrict__ GEl, float *__restrict__ Work) {
     __shared__ RowShared<W, NS> sh;
@@ -415,15 +334,14 @@ struct ColumnShared {
 };
 
 template <int W, int NS>
-__device__ __forceinline__ void run_column(const ColumnView &v, const Split &hs, const uint4 &it, int kind, const float *__restrict__ G,
+__device__ __forceinline__ void run_column(const ColumnView &v, const HeadSplit &hs, const uint4 &it, int kind, const float *__restrict__ G,
                                            const float *__restrict__ P, const float *__restrict__ DX, float *__restrict__ GEr,
                                            float *__restrict__ GV, uint32_t lane, uint32_t w, ColumnShared<W, NS> &sh) {
     const uint32_t slot = lane / W, li = lane % W;
     const int slot_lane0 = static_cast<int>(lane - li);
     const HeadLane hl(hs, li);
     const Place pl = place_of<W>(v.colptr, it, kind, slot, w);
-    LaneHeads<NS> lh;
-    lh.template init<W>(hs, li, v.k);
+    const LaneHeads<W, NS> lh(hs, li, v.k);
     float4 av[NS];
     float ger[NS];
 #pragma unroll
@@ -503,7 +421,7 @@ __device__ __forceinline__ void run_column(const ColumnView &v, const Split &hs,
 }
 
 template <int W, int NS>
-__global__ __launch_bounds__(256) void gat_columns_backward(ColumnView v, Split hs, const float *__restrict__ G, const float *__restrict__ P,
+__global__ __launch_bounds__(256) void gat_columns_backward(ColumnView v, HeadSplit hs, const float *__restrict__ G, const float *__restrict__ P,
                                                              const float *__restrict__ DX, float *__restrict__ GEr, float *__restrict__ GV) {
     __shared__ ColumnShared<W, NS> sh;
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
@@ -534,30 +452,6 @@ struct Operands {
     float *GEl, *GEr, *GV, *Work;
 };
 
-template <int W, int NS>
-static void launch(const View &v, const Split &hs, dim3 grid, const float *El, const float *Er, const float *V, float slope, float *Out, float *P,
-                   hipStream_t s) {
-    hipLaunchKernelGGL((gat_rows<W, NS>), grid, dim3(64 * kWavesPerBlock), 0, s, v, hs, El, Er, V, slope, Out, P);
-}
-
-template <int W, int NS>
-static void launch_backward(const View &rv, const ColumnView &cv, const Split &hs, dim3 rgrid, dim3 cgrid, const Operands &o, hipStream_t s) {
-    const dim3 block(64 * kWavesPerBlock);
-    if (o.GEl || o.GEr) hipLaunchKernelGGL((gat_rows_backward<W, NS>), rgrid, block, 0, s, rv, hs, o.El, o.Er, o.V, o.P, o.G, o.slope, o.GEl, o.Work);
-    if (o.GEr || o.GV) hipLaunchKernelGGL((gat_columns_backward<W, NS>), cgrid, block, 0, s, cv, hs, o.G, o.P, o.Work, o.GEr, o.GV);
-}
-
-// FLEX_OK and the split where heads (1 included) divides k into heads of d = 4 .. 256 columns, d a power of two
-static int split_of(int k, int heads, Split *out) {
-    if (k % heads) return FLEX_ERR_UNSUPPORTED;
-    const int d = k / heads;
-    int lg = 0;
-    while ((4 << lg) < d) ++lg;
-    if (d < 4 || d > 256 || (4 << lg) != d || k > 4 * 64 * kAtMaxSlabs) return FLEX_ERR_UNSUPPORTED;
-    *out = Split{heads, lg};
-    return FLEX_OK;
-}
-
 static bool slope_ok(float slope) { return std::isfinite(slope) && slope > 0.f && slope <= 1.f; }
 
 }  // namespace gat
@@ -572,29 +466,18 @@ int flex_gat_attention(const flex_plan *p, int heads, const float *dEl, const fl
                        flex_stream_t stream) {
     namespace gat = attention::gat;
     if (!p || !p->at_ok || heads < 1 || !gat::slope_ok(slope)) return FLEX_ERR_INVALID;
-    gat::Split hs;
-    if (const int rc = gat::split_of(p->k, heads, &hs)) return rc;
+    attention::HeadSplit hs;
+    if (const int rc = attention::split_of(p->k, heads, &hs)) return rc;
     if (p->at_entries == 0) return FLEX_OK;
     if (!dEl || !dEr || !dV || !dOut) return FLEX_ERR_INVALID;
     const AttentionPick pick = attention_pick(p->k, p->ldb, p->ldc, dV, dOut, nullptr, nullptr);
     if (!pick.vec4) return FLEX_ERR_UNSUPPORTED;
     const DeviceScope on(p->device);
     FLEX_HIP_TRY(on.error());
-    const attention::View v{p->d_at_rowptr.get(), p->d_at_src.get(), p->d_at_item.get(), p->d_at_grp.get(), p->at_first_entry,
-                            p->n_at_groups, p->n_at_wave_items, p->n_at_block_rows, p->xcd_remap ? 1u : 0u, p->k, p->ldb, p->ldc};
-    uint32_t wgs = (p->n_at_groups + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (v.xcd_remap) wgs = (wgs + kXcds - 1) / kXcds * kXcds;
-    const dim3 grid(p->n_at_block_rows + wgs);
+    const attention::View v = attention::row_view(p);
+    const dim3 grid = attention::launch_grid(v), block(64 * kWavesPerBlock);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    switch (pick.W * 8 + pick.NS) {
-        case 4 * 8 + 1: gat::launch<4, 1>(v, hs, grid, dEl, dEr, dV, slope, dOut, dP, s); break;
-        case 8 * 8 + 1: gat::launch<8, 1>(v, hs, grid, dEl, dEr, dV, slope, dOut, dP, s); break;
-        case 16 * 8 + 1: gat::launch<16, 1>(v, hs, grid, dEl, dEr, dV, slope, dOut, dP, s); break;
-        case 32 * 8 + 1: gat::launch<32, 1>(v, hs, grid, dEl, dEr, dV, slope, dOut, dP, s); break;
-        case 64 * 8 + 1: gat::launch<64, 1>(v, hs, grid, dEl, dEr, dV, slope, dOut, dP, s); break;
-        case 64 * 8 + 2: gat::launch<64, 2>(v, hs, grid, dEl, dEr, dV, slope, dOut, dP, s); break;
-        default: gat::launch<64, 4>(v, hs, grid, dEl, dEr, dV, slope, dOut, dP, s); break;
-    }
+    attention::dispatch(pick, [&](auto W, auto NS) { hipLaunchKernelGGL((gat::gat_rows<W(), NS()>), grid, block, 0, s, v, hs, dEl, dEr, dV, slope, dOut, dP); });
     FLEX_HIP_TRY(hipGetLastError());
     return FLEX_OK;
 }
@@ -603,8 +486,8 @@ int flex_gat_attention_backward(const flex_plan *p, int heads, const float *dEl,
                                 const float *dGradOut, float slope, float *dGradEl, float *dGradEr, float *dGradV, float *dWork, flex_stream_t stream) {
     namespace gat = attention::gat;
     if (!p || !p->ab_ok || heads < 1 || !gat::slope_ok(slope)) return FLEX_ERR_INVALID;
-    gat::Split hs;
-    if (const int rc = gat::split_of(p->k, heads, &hs)) return rc;
+    attention::HeadSplit hs;
+    if (const int rc = attention::split_of(p->k, heads, &hs)) return rc;
     if (p->at_entries == 0) return FLEX_OK;
     if (!dEl || !dEr || !dV || !dP || !dGradOut || !dWork || dWork == dP) return FLEX_ERR_INVALID;
     // the forward's rule over every row operand of the two launches (a NULL output is aligned)
@@ -613,28 +496,15 @@ int flex_gat_attention_backward(const flex_plan *p, int heads, const float *dEl,
     if (!dGradEl && !dGradEr && !dGradV) return FLEX_OK;
     const DeviceScope on(p->device);
     FLEX_HIP_TRY(on.error());
-    const uint32_t remap = p->xcd_remap ? 1u : 0u;
-    const attention::View rv{p->d_at_rowptr.get(), p->d_at_src.get(), p->d_at_item.get(), p->d_at_grp.get(), p->at_first_entry,
-                             p->n_at_groups, p->n_at_wave_items, p->n_at_block_rows, remap, p->k, p->ldb, p->ldc};
-    const attention::ColumnView cv{p->d_ab_colptr.get(), p->d_ab_ent.get(), p->d_ab_item.get(), p->d_ab_grp.get(),
-                                   p->n_ab_groups, p->n_ab_wave_items, p->n_ab_block_cols, remap, p->k, p->ldb, p->ldc};
-    auto grid_of = [&](uint32_t groups, uint32_t blocks) {
-        uint32_t wgs = (groups + kWavesPerBlock - 1) / kWavesPerBlock;
-        if (remap) wgs = (wgs + kXcds - 1) / kXcds * kXcds;
-        return dim3(blocks + wgs);
-    };
-    const dim3 rgrid = grid_of(p->n_at_groups, p->n_at_block_rows), cgrid = grid_of(p->n_ab_groups, p->n_ab_block_cols);
+    const attention::View rv = attention::row_view(p);
+    const attention::ColumnView cv = attention::column_view(p);
+    const dim3 rgrid = attention::launch_grid(rv), cgrid = attention::launch_grid(cv), block(64 * kWavesPerBlock);
     const gat::Operands o{dEl, dEr, dV, dP, dGradOut, slope, dGradEl, dGradEr, dGradV, dWork};
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    switch (pick.W * 8 + pick.NS) {
-        case 4 * 8 + 1: gat::launch_backward<4, 1>(rv, cv, hs, rgrid, cgrid, o, s); break;
-        case 8 * 8 + 1: gat::launch_backward<8, 1>(rv, cv, hs, rgrid, cgrid, o, s); break;
-        case 16 * 8 + 1: gat::launch_backward<16, 1>(rv, cv, hs, rgrid, cgrid, o, s); break;
-        case 32 * 8 + 1: gat::launch_backward<32, 1>(rv, cv, hs, rgrid, cgrid, o, s); break;
-        case 64 * 8 + 1: gat::launch_backward<64, 1>(rv, cv, hs, rgrid, cgrid, o, s); break;
-        case 64 * 8 + 2: gat::launch_backward<64, 2>(rv, cv, hs, rgrid, cgrid, o, s); break;
-        default: gat::launch_backward<64, 4>(rv, cv, hs, rgrid, cgrid, o, s); break;
-    }
+    attention::dispatch(pick, [&](auto W, auto NS) {
+        if (o.GEl || o.GEr) hipLaunchKernelGGL((gat::gat_rows_backward<W(), NS()>), rgrid, block, 0, s, rv, hs, o.El, o.Er, o.V, o.P, o.G, o.slope, o.GEl, o.Work);
+        if (o.GEr || o.GV) hipLaunchKernelGGL((gat::gat_columns_backward<W(), NS()>), cgrid, block, 0, s, cv, hs, o.G, o.P, o.Work, o.GEr, o.GV);
+    });
     FLEX_HIP_TRY(hipGetLastError());
     return FLEX_OK;
 }

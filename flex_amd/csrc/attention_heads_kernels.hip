@@ -2,7 +2,8 @@
 // flex_attention_heads_backward): H heads of d = k / H columns each in the one forward launch and the two backward launches of
 // flex_attention and flex_attention_backward, on the same plans.  tests/test_gpu_multihead_attention.py covers it.
 //
-// The walk is the single-head kernels' (attention_kernels.hip, attention_backward_kernels.hip; attention_device.h): the same view, items,
+// The walk is the single-head kernels' (attention_kernels.hip, attention_backward_kernels.hip; attention_device.h, which also holds the
+// head split: HeadSplit, HeadLane, head_total, merge_slots_heads, HeadsShared; split_of is in attention_host.h): the same view, items,
 // groups, slot / wave / block ownership, W = sddmm_lanes(k) lanes per slot, four entries per pass and four columns per lane and slab.
 // d is a power of two in [4, 256], so a head is HW = d / 4 whole lanes of one slab: the lane that holds columns c .. c + 3 belongs to
 // head c / d, and the lanes of a head are HW consecutive lanes that start at a multiple of HW.  HW is a launch argument (its log2),
@@ -20,35 +21,10 @@
 #include <cmath>
 #include <cstdint>
 
-#include "attention_device.h"
-#include "plan.h"
+#include "attention_host.h"
 
 namespace flex {
 namespace attention {
-
-// how the lanes of a slot split into heads: lg = log2(HW); H floats per entry in the edge arrays
-struct HeadSplit {
-    int32_t H, lg;
-};
-
-// what a lane knows about its place in its head: r = its index among the head's lanes, wm = the mask of the writer rule above
-struct HeadLane {
-    uint32_t hw, r, wm;
-    __device__ __forceinline__ HeadLane(const HeadSplit &hs, uint32_t li) : hw(1u << hs.lg), r(li & (hw - 1u)), wm((hw < static_cast<uint32_t>(U) ? hw : static_cast<uint32_t>(U)) - 1u) {}
-    __device__ __forceinline__ bool writes(int u) const { return (static_cast<uint32_t>(u) & wm) == r; }
-};
-
-// The sum of x over the hw lanes of the lane's head, on every one of them: a butterfly from the widest step down -- the tree of
-// slot_totals<hw>.  Both lanes of a pair add the same two operands, so all lanes of the head hold the same bits.  hw is the same for the
-// whole wave: every shuffle is wave-wide.
-template <int W>
-__device__ __forceinline__ float head_total(float x, uint32_t hw) {
-#pragma unroll
-    for (int o = W / 2; o >= 1; o >>= 1) {
-        if (static_cast<uint32_t>(o) < hw) x += __shfl_xor(x, o);
-    }
-    return x;
-}
 
 // ---- forward
 
@@ -124,34 +100,6 @@ __device__ __forceinline__ void sweep_heads(const View &v, const HeadSplit &hs, 
         }
     }
 }
-
-// attention_kernels.hip, merge_slots, slab by slab
-template <int W, int NS>
-__device__ __forceinline__ void merge_slots_heads(State<1> (&st)[NS], uint32_t lane, float scale) {
-#pragma unroll
-    for (int off = W; off < 64; off <<= 1) {
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            State<1> o;
-            o.m = __shfl_xor(st[s].m, off);
-            o.l = __shfl_xor(st[s].l, off);
-            o.acc[0] = shfl_xor4(st[s].acc[0], off);
-            if (lane & static_cast<uint32_t>(off)) {
-                merge(o, st[s], scale);
-                st[s] = o;
-            } else {
-                merge(st[s], o, scale);
-            }
-        }
-    }
-}
-
-// where the waves of a block row meet: (m, l) of every group of four columns (the lanes of a head hold the same pair) and the Out rows
-template <int W, int NS>
-struct HeadsShared {
-    float2 ml[kWavesPerBlock][W * NS];
-    alignas(16) float acc[kWavesPerBlock][4 * W * NS];
-};
 
 template <int W, int NS>
 __device__ __forceinline__ void run_item_heads(const View &v, const HeadSplit &hs, const uint4 &it, int kind, const float *__restrict__ Q,
@@ -303,16 +251,7 @@ __device__ __forceinline__ void run_row_heads(const View &v, const HeadSplit &hs
             }
         }
     }
-    if (kind != kSlotLine) {
-#pragma unroll
-        for (int off = W; off < 64; off <<= 1) {
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                const float o = __shfl_xor(delta[s], off);
-                delta[s] = (lane & static_cast<uint32_t>(off)) ? o + delta[s] : delta[s] + o;
-            }
-        }
-    }
+    if (kind != kSlotLine) sum_slot_scalars<W, NS>(delta, lane);
     if (kind == kBlockLine) {
         if (slot == 0) {
 #pragma unroll
@@ -549,30 +488,6 @@ struct HeadsOperands {
     float *GQ, *GK, *GV, *Work;
 };
 
-template <int W, int NS>
-static void launch_heads(const View &v, const HeadSplit &hs, dim3 grid, const float *Q, const float *K, const float *V, float scale, float *Out, float *P,
-                         hipStream_t s) {
-    hipLaunchKernelGGL((attention_heads_rows<W, NS>), grid, dim3(64 * kWavesPerBlock), 0, s, v, hs, Q, K, V, scale, Out, P);
-}
-
-template <int W, int NS>
-static void launch_heads_backward(const View &rv, const ColumnView &cv, const HeadSplit &hs, dim3 rgrid, dim3 cgrid, const HeadsOperands &o, hipStream_t s) {
-    const dim3 block(64 * kWavesPerBlock);
-    if (o.GQ || o.GK) hipLaunchKernelGGL((attention_heads_rows_backward<W, NS>), rgrid, block, 0, s, rv, hs, o.K, o.V, o.P, o.G, o.scale, o.GQ, o.Work);
-    if (o.GK || o.GV) hipLaunchKernelGGL((attention_heads_columns_backward<W, NS>), cgrid, block, 0, s, cv, hs, o.Q, o.G, o.P, o.Work, o.GK, o.GV);
-}
-
-// heads > 1: FLEX_OK and the split where heads divides k into heads of d = 4 .. 256 columns, d a power of two
-static int split_of(int k, int heads, HeadSplit *out) {
-    if (k > 4 * 64 * kAtMaxSlabs || k % heads) return FLEX_ERR_UNSUPPORTED;
-    const int d = k / heads;
-    int lg = 0;
-    while ((4 << lg) < d) ++lg;
-    if (d < 4 || d > 256 || (4 << lg) != d) return FLEX_ERR_UNSUPPORTED;
-    *out = HeadSplit{heads, lg};
-    return FLEX_OK;
-}
-
 }  // namespace attention
 }  // namespace flex
 
@@ -593,21 +508,12 @@ int flex_attention_heads(const flex_plan *p, int heads, const float *dQ, const f
     if (!pick.vec4) return FLEX_ERR_UNSUPPORTED;
     const DeviceScope on(p->device);
     FLEX_HIP_TRY(on.error());
-    const attention::View v{p->d_at_rowptr.get(), p->d_at_src.get(), p->d_at_item.get(), p->d_at_grp.get(), p->at_first_entry,
-                            p->n_at_groups, p->n_at_wave_items, p->n_at_block_rows, p->xcd_remap ? 1u : 0u, p->k, p->ldb, p->ldc};
-    uint32_t wgs = (p->n_at_groups + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (v.xcd_remap) wgs = (wgs + kXcds - 1) / kXcds * kXcds;
-    const dim3 grid(p->n_at_block_rows + wgs);
+    const attention::View v = attention::row_view(p);
+    const dim3 grid = attention::launch_grid(v), block(64 * kWavesPerBlock);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    switch (pick.W * 8 + pick.NS) {
-        case 4 * 8 + 1: attention::launch_heads<4, 1>(v, hs, grid, dQ, dK, dV, scale, dOut, dP, s); break;
-        case 8 * 8 + 1: attention::launch_heads<8, 1>(v, hs, grid, dQ, dK, dV, scale, dOut, dP, s); break;
-        case 16 * 8 + 1: attention::launch_heads<16, 1>(v, hs, grid, dQ, dK, dV, scale, dOut, dP, s); break;
-        case 32 * 8 + 1: attention::launch_heads<32, 1>(v, hs, grid, dQ, dK, dV, scale, dOut, dP, s); break;
-        case 64 * 8 + 1: attention::launch_heads<64, 1>(v, hs, grid, dQ, dK, dV, scale, dOut, dP, s); break;
-        case 64 * 8 + 2: attention::launch_heads<64, 2>(v, hs, grid, dQ, dK, dV, scale, dOut, dP, s); break;
-        default: attention::launch_heads<64, 4>(v, hs, grid, dQ, dK, dV, scale, dOut, dP, s); break;
-    }
+    attention::dispatch(pick, [&](auto W, auto NS) {
+        hipLaunchKernelGGL((attention::attention_heads_rows<W(), NS()>), grid, block, 0, s, v, hs, dQ, dK, dV, scale, dOut, dP);
+    });
     FLEX_HIP_TRY(hipGetLastError());
     return FLEX_OK;
 }
@@ -627,28 +533,16 @@ int flex_attention_heads_backward(const flex_plan *p, int heads, const float *dQ
     if (!dGradQ && !dGradK && !dGradV) return FLEX_OK;
     const DeviceScope on(p->device);
     FLEX_HIP_TRY(on.error());
-    const uint32_t remap = p->xcd_remap ? 1u : 0u;
-    const attention::View rv{p->d_at_rowptr.get(), p->d_at_src.get(), p->d_at_item.get(), p->d_at_grp.get(), p->at_first_entry,
-                             p->n_at_groups, p->n_at_wave_items, p->n_at_block_rows, remap, p->k, p->ldb, p->ldc};
-    const attention::ColumnView cv{p->d_ab_colptr.get(), p->d_ab_ent.get(), p->d_ab_item.get(), p->d_ab_grp.get(),
-                                   p->n_ab_groups, p->n_ab_wave_items, p->n_ab_block_cols, remap, p->k, p->ldb, p->ldc};
-    auto grid_of = [&](uint32_t groups, uint32_t blocks) {
-        uint32_t wgs = (groups + kWavesPerBlock - 1) / kWavesPerBlock;
-        if (remap) wgs = (wgs + kXcds - 1) / kXcds * kXcds;
-        return dim3(blocks + wgs);
-    };
-    const dim3 rgrid = grid_of(p->n_at_groups, p->n_at_block_rows), cgrid = grid_of(p->n_ab_groups, p->n_ab_block_cols);
+    const attention::View rv = attention::row_view(p);
+    const attention::ColumnView cv = attention::column_view(p);
+    const dim3 rgrid = attention::launch_grid(rv), cgrid = attention::launch_grid(cv), block(64 * kWavesPerBlock);
     const attention::HeadsOperands o{dQ, dK, dV, dP, dGradOut, scale, dGradQ, dGradK, dGradV, dWork};
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    switch (pick.W * 8 + pick.NS) {
-        case 4 * 8 + 1: attention::launch_heads_backward<4, 1>(rv, cv, hs, rgrid, cgrid, o, s); break;
-        case 8 * 8 + 1: attention::launch_heads_backward<8, 1>(rv, cv, hs, rgrid, cgrid, o, s); break;
-        case 16 * 8 + 1: attention::launch_heads_backward<16, 1>(rv, cv, hs, rgrid, cgrid, o, s); break;
-        case 32 * 8 + 1: attention::launch_heads_backward<32, 1>(rv, cv, hs, rgrid, cgrid, o, s); break;
-        case 64 * 8 + 1: attention::launch_heads_backward<64, 1>(rv, cv, hs, rgrid, cgrid, o, s); break;
-        case 64 * 8 + 2: attention::launch_heads_backward<64, 2>(rv, cv, hs, rgrid, cgrid, o, s); break;
-        default: attention::launch_heads_backward<64, 4>(rv, cv, hs, rgrid, cgrid, o, s); break;
-    }
+    attention::dispatch(pick, [&](auto W, auto NS) {
+        using namespace attention;
+        if (o.GQ || o.GK) hipLaunchKernelGGL((attention_heads_rows_backward<W(), NS()>), rgrid, block, 0, s, rv, hs, o.K, o.V, o.P, o.G, o.scale, o.GQ, o.Work);
+        if (o.GK || o.GV) hipLaunchKernelGGL((attention_heads_columns_backward<W(), NS()>), cgrid, block, 0, s, cv, hs, o.Q, o.G, o.P, o.Work, o.GK, o.GV);
+    });
     FLEX_HIP_TRY(hipGetLastError());
     return FLEX_OK;
 }

@@ -4,7 +4,8 @@
 // internal.h, kAtPass) and verified by flex_plan_self_check (plan_check.cpp).
 //
 // Not an SpMM kernel and not one of flex::values / flex::softmax: a namespace of its own; tests/test_gpu_fused_attention.py covers it.
-// The view of the walk and the helpers it shares with the backward (attention_backward_kernels.hip): attention_device.h.
+// The view of the walk, the slot placement (place_of) and the helpers it shares with the other attention kernels: attention_device.h;
+// the view, the grid and the (W, NS) dispatch of the entry point: attention_host.h.
 //
 // Row-owned.  A SLOT of W lanes holds its Q row and its Out row (4 columns per lane and slab) in registers, with the running maximum m
 // and the running sum l of the row's terms exp(scale (s - m)).  Per pass the slot takes kAtPass = 4 consecutive entries: its first
@@ -21,14 +22,12 @@
 #include <cmath>
 #include <cstdint>
 
-#include "attention_device.h"
-#include "plan.h"
+#include "attention_host.h"
 
 namespace flex {
 namespace attention {
 
-// The sweep of one slot over its share of a row: member t of a team of T slots takes the passes t, t + T, ... of kAtPass entries.
-// n_pass is the same for every lane of the wave (a slot past its row's end idles under a predicate), so every shuffle is wave-wide.
+// The sweep of one slot over its share of a row: first, len, t, T and n_pass are the slot's Place (attention_device.h).
 template <int W, int NS, bool VEC>
 __device__ __forceinline__ void sweep(const View &v, const float4 (&q)[NS], const float *__restrict__ K, const float *__restrict__ V, float scale,
                                       float *__restrict__ P, uint64_t first, uint32_t len, uint32_t t, uint32_t T, uint32_t n_pass, uint32_t lane,
@@ -118,8 +117,6 @@ __device__ __forceinline__ void write_probs(float *__restrict__ P, uint64_t firs
     }
 }
 
-enum Kind : int { kSlotItem = 0, kWaveItem = 1, kBlockItem = 2 };
-
 // where the waves of a block row meet: (m, l) and the Out row of every wave
 template <int W, int NS>
 struct Shared {
@@ -131,47 +128,22 @@ template <int W, int NS, bool VEC>
 __device__ __forceinline__ void run_item(const View &v, const uint4 &it, int kind, const float *__restrict__ Q, const float *__restrict__ K,
                                          const float *__restrict__ V, float scale, float *__restrict__ Out, float *__restrict__ P, uint32_t lane, uint32_t w,
                                          Shared<W, NS> &sh) {
-    constexpr uint32_t S = 64 / W;
     const uint32_t slot = lane / W, li = lane % W;
-    // the slot's row, its entries, and its place in the team that shares the row
-    uint32_t row = it.z, len = it.y, t = slot, T = S, n_pass;
-    uint64_t first = it.x;
-    bool has_row = true;
-    if (kind == kSlotItem) {
-        has_row = slot < it.w;
-        row = it.z + (has_row ? slot : 0u);
-        first = v.rowptr[row];
-        len = has_row ? v.rowptr[row + 1] - v.rowptr[row] : 0u;
-        t = 0;
-        T = 1;
-        uint32_t mx = (len + U - 1) / U;
-#pragma unroll
-        for (int o = 32; o >= W; o >>= 1) {
-            const uint32_t other = static_cast<uint32_t>(__shfl_xor(static_cast<int>(mx), o));
-            mx = other > mx ? other : mx;
-        }
-        n_pass = mx;
-    } else {
-        if (kind == kBlockItem) {
-            t = w * S + slot;
-            T = kWavesPerBlock * S;
-        }
-        n_pass = static_cast<uint32_t>((static_cast<uint64_t>(len) + static_cast<uint64_t>(T) * U - 1) / (static_cast<uint64_t>(T) * U));
-    }
+    const Place pl = place_of<W>(v.rowptr, it, kind, slot, w);
     float4 q[NS];
     State<NS> st;
     st.m = -INFINITY;
     st.l = 0.f;
-    const float *qrow = Q + static_cast<size_t>(row) * v.ldc;
+    const float *qrow = Q + static_cast<size_t>(pl.line) * v.ldc;
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
-        q[s] = has_row ? load_cols<VEC>(qrow, 4 * static_cast<int>(li) + 4 * W * s, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
+        q[s] = pl.has_line ? load_cols<VEC>(qrow, 4 * static_cast<int>(li) + 4 * W * s, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
         st.acc[s] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    sweep<W, NS, VEC>(v, q, K, V, scale, P, first, len, t, T, n_pass, lane, li, st);
-    if (kind != kSlotItem) merge_slots<W, NS>(st, lane, scale);
-    bool writer = kind == kSlotItem ? has_row : slot == 0;
-    if (kind == kBlockItem) {
+    sweep<W, NS, VEC>(v, q, K, V, scale, P, pl.first, pl.len, pl.t, pl.T, pl.n_pass, lane, li, st);
+    if (kind != kSlotLine) merge_slots<W, NS>(st, lane, scale);
+    bool writer = kind == kSlotLine ? pl.has_line : slot == 0;
+    if (kind == kBlockLine) {
         if (slot == 0) {
 #pragma unroll
             for (int s = 0; s < NS; ++s) *reinterpret_cast<float4 *>(&sh.acc[w][4 * li + 4 * W * s]) = st.acc[s];
@@ -195,8 +167,8 @@ __device__ __forceinline__ void run_item(const View &v, const uint4 &it, int kin
         }
         st = tot;
     }
-    if (writer) write_row<NS, VEC>(Out + static_cast<size_t>(row) * v.ldc, st, li, W, v.k);
-    if (P) write_probs(P, first, len, t, T, n_pass, li, st.m, st.l, scale);
+    if (writer) write_row<NS, VEC>(Out + static_cast<size_t>(pl.line) * v.ldc, st, li, W, v.k);
+    if (P) write_probs(P, pl.first, pl.len, pl.t, pl.T, pl.n_pass, li, st.m, st.l, scale);
 }
 
 // Grid: the block rows first (the longest work starts first), then the workgroups of the wave groups.
@@ -206,7 +178,7 @@ __global__ __launch_bounds__(256) void attention_rows(View v, const float *__res
     __shared__ Shared<W, NS> sh;
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
     if (blockIdx.x < v.n_block_rows) {
-        run_item<W, NS, VEC>(v, v.item[v.n_wave_items + blockIdx.x], kBlockItem, Q, K, V, scale, Out, P, lane, w, sh);
+        run_item<W, NS, VEC>(v, v.item[v.n_wave_items + blockIdx.x], kBlockLine, Q, K, V, scale, Out, P, lane, w, sh);
         return;
     }
     uint32_t wg = blockIdx.x - v.n_block_rows;
@@ -219,15 +191,9 @@ __global__ __launch_bounds__(256) void attention_rows(View v, const float *__res
     const uint32_t i1 = v.grp[grp + 1];
     for (uint32_t i = v.grp[grp]; i < i1; ++i) {
         const uint4 it = v.item[i];  // {first entry, entries, first row, rows}: the same for every lane
-        const int kind = (it.w > 1 || it.y <= kAtSlotRow) ? kSlotItem : kWaveItem;  // internal.h, attention_row_class
+        const int kind = (it.w > 1 || it.y <= kAtSlotRow) ? kSlotLine : kWaveLine;  // internal.h, attention_row_class
         run_item<W, NS, VEC>(v, it, kind, Q, K, V, scale, Out, P, lane, w, sh);
     }
-}
-
-template <int W, int NS>
-static void launch_w(const View &v, bool vec, dim3 grid, const float *Q, const float *K, const float *V, float scale, float *Out, float *P, hipStream_t s) {
-    if (vec) hipLaunchKernelGGL((attention_rows<W, NS, true>), grid, dim3(64 * kWavesPerBlock), 0, s, v, Q, K, V, scale, Out, P);
-    else hipLaunchKernelGGL((attention_rows<W, NS, false>), grid, dim3(64 * kWavesPerBlock), 0, s, v, Q, K, V, scale, Out, P);
 }
 
 }  // namespace attention
@@ -246,21 +212,13 @@ int flex_attention(const flex_plan *p, const float *dQ, const float *dK, const f
     if (p->k > 4 * 64 * kAtMaxSlabs) return FLEX_ERR_UNSUPPORTED;
     const DeviceScope on(p->device);
     FLEX_HIP_TRY(on.error());
-    const attention::View v{p->d_at_rowptr.get(), p->d_at_src.get(), p->d_at_item.get(), p->d_at_grp.get(), p->at_first_entry,
-                            p->n_at_groups, p->n_at_wave_items, p->n_at_block_rows, p->xcd_remap ? 1u : 0u, p->k, p->ldb, p->ldc};
-    uint32_t wgs = (p->n_at_groups + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (v.xcd_remap) wgs = (wgs + kXcds - 1) / kXcds * kXcds;
-    const dim3 grid(p->n_at_block_rows + wgs);
+    const attention::View v = attention::row_view(p);
+    const dim3 grid = attention::launch_grid(v), block(64 * kWavesPerBlock);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    switch (pick.W * 8 + pick.NS) {
-        case 4 * 8 + 1: attention::launch_w<4, 1>(v, pick.vec4, grid, dQ, dK, dV, scale, dOut, dP, s); break;
-        case 8 * 8 + 1: attention::launch_w<8, 1>(v, pick.vec4, grid, dQ, dK, dV, scale, dOut, dP, s); break;
-        case 16 * 8 + 1: attention::launch_w<16, 1>(v, pick.vec4, grid, dQ, dK, dV, scale, dOut, dP, s); break;
-        case 32 * 8 + 1: attention::launch_w<32, 1>(v, pick.vec4, grid, dQ, dK, dV, scale, dOut, dP, s); break;
-        case 64 * 8 + 1: attention::launch_w<64, 1>(v, pick.vec4, grid, dQ, dK, dV, scale, dOut, dP, s); break;
-        case 64 * 8 + 2: attention::launch_w<64, 2>(v, pick.vec4, grid, dQ, dK, dV, scale, dOut, dP, s); break;
-        default: attention::launch_w<64, 4>(v, pick.vec4, grid, dQ, dK, dV, scale, dOut, dP, s); break;
-    }
+    attention::dispatch(pick, [&](auto W, auto NS) {
+        if (pick.vec4) hipLaunchKernelGGL((attention::attention_rows<W(), NS(), true>), grid, block, 0, s, v, dQ, dK, dV, scale, dOut, dP);
+        else hipLaunchKernelGGL((attention::attention_rows<W(), NS(), false>), grid, block, 0, s, v, dQ, dK, dV, scale, dOut, dP);
+    });
     FLEX_HIP_TRY(hipGetLastError());
     return FLEX_OK;
 }
