@@ -5,7 +5,8 @@ set into the plans (flex_plan_set_values) without planning again.  The same two 
 scores by flex_sddmm as a forward op, their softmax over each row of A (flex_edge_softmax), and the SpMM with the result as A's values
 (SparseOperator.attention).  fused_attention=True runs that forward as one launch (flex_attention), and fused_backward=True its backward as
 two (flex_attention_backward) instead of the chain of eight calls; with both, attention(..., heads=H) runs H heads in the same three
-launches (flex_attention_heads, flex_attention_heads_backward), and gat_attention(el, er, V) runs GAT's additive score
+launches (flex_attention_heads, flex_attention_heads_backward), on torch.bfloat16 Q, K and V as well (flex_attention_bf16,
+flex_attention_bf16_backward: bf16 rows, float32 accumulation), and gat_attention(el, er, V) runs GAT's additive score
 LeakyReLU(el[row] + er[col]) per head in the same three launches (flex_gat_attention, flex_gat_attention_backward).  torch is imported
 lazily, as in binding.py."""
 from __future__ import annotations
@@ -185,14 +186,35 @@ def _function():
             grads = ctx.op.plan.gat_attention_backward(el, er, V, p, grad_out.contiguous(), ctx.slope, want=tuple(ctx.needs_input_grad[:3]))
             return (*grads, None, None)
 
-    return _SpMM, _AxwLayer, _SpMMValues, _Sddmm, _EdgeSoftmax, _FusedAttention, _FusedAttentionHeads, _FusedGatAttention
+    class _FusedAttentionBf16(torch.autograd.Function):
+        """_FusedAttentionHeads on torch.bfloat16 Q, K, V (heads = 1 included): flex_attention_bf16 in one launch, scores, softmax and sums
+        in float32, alpha [nnz, heads] kept in float32 only when a gradient is needed; backward: the one call flex_attention_bf16_backward
+        (two launches) for the gradients that are needed, which come back in bfloat16.  Only on an operator made with fused_attention=True
+        and fused_backward=True."""
+
+        @staticmethod
+        def forward(ctx, Q, K, V, op, scale, heads):
+            Q, K, V = Q.contiguous(), K.contiguous(), V.contiguous()
+            p = torch.zeros((op.nnz, heads), dtype=torch.float32, device=Q.device) if any(ctx.needs_input_grad[:3]) else None
+            out = op.plan.attention_bf16(Q, K, V, scale, heads=heads, p=p)
+            ctx.op, ctx.scale, ctx.heads = op, scale, heads
+            ctx.save_for_backward(Q, K, V, p)
+            return out
+
+        @staticmethod
+        def backward(ctx, grad_out):
+            Q, K, V, p = ctx.saved_tensors
+            grads = ctx.op.plan.attention_bf16_backward(Q, K, V, p, grad_out.contiguous(), ctx.scale, heads=ctx.heads, want=tuple(ctx.needs_input_grad[:3]))
+            return (*grads, None, None, None)
+
+    return _SpMM, _AxwLayer, _SpMMValues, _Sddmm, _EdgeSoftmax, _FusedAttention, _FusedAttentionHeads, _FusedGatAttention, _FusedAttentionBf16
 
 
 _cache = None
 
 
 def functions():
-    """(_SpMM, _AxwLayer, _SpMMValues, _Sddmm, _EdgeSoftmax, _FusedAttention, _FusedAttentionHeads, _FusedGatAttention): the autograd Functions, built at first use (torch is imported then)."""
+    """(_SpMM, _AxwLayer, _SpMMValues, _Sddmm, _EdgeSoftmax, _FusedAttention, _FusedAttentionHeads, _FusedGatAttention, _FusedAttentionBf16): the autograd Functions, built at first use (torch is imported then)."""
     global _cache
     if _cache is None:
         _cache = _function()
@@ -270,12 +292,23 @@ class SparseOperator:
         """Out [m, k] = A(alpha) V with alpha = softmax over each row of A of scale * <Q[row], K[col]>; scale defaults to
         (k / heads) ** -0.5.  Differentiable in Q [m, k], K [n, k] and V [n, k].  heads > 1: head h is columns [h k / heads, (h + 1) k / heads)
         of Q, K, V and Out and has its own scores and softmax, all heads in one forward launch and two backward launches
-        (flex_attention_heads); needs fused_attention=True and fused_backward=True."""
+        (flex_attention_heads); needs fused_attention=True and fused_backward=True.  Q, K and V all torch.bfloat16, for any heads: the same
+        three launches on bf16 rows with float32 scores, softmax and sums (flex_attention_bf16); Out and the gradients are bfloat16; needs
+        both fused flags as well, and k / heads a power of two in 4 .. 256.  Mixed dtypes raise TypeError."""
+        import torch
         self._needs_learn_values("attention")
         if heads < 1:
             raise ValueError(f"heads must be at least 1, not {heads}")
         if scale is None:
             scale = (self.k / heads) ** -0.5
+        dtypes = {t.dtype for t in (Q, K, V)}
+        if torch.bfloat16 in dtypes:
+            if len(dtypes) > 1:
+                raise TypeError(f"attention takes Q, K and V of one dtype, all float32 or all bfloat16, not {[str(t.dtype) for t in (Q, K, V)]}")
+            if not (self.fused_attention and self.fused_backward):
+                raise NotImplementedError("attention(...) on bfloat16 needs SparseOperator(..., fused_attention=True, fused_backward=True): "
+                                          "only the fused forward and backward read bf16 rows")
+            return functions()[8].apply(Q, K, V, self, float(scale), int(heads))
         if heads > 1:
             if not (self.fused_attention and self.fused_backward):
                 raise NotImplementedError("attention(..., heads > 1) needs SparseOperator(..., fused_attention=True, fused_backward=True): "

@@ -164,6 +164,7 @@ SYMBOLS = [
     "flex_edge_softmax", "flex_edge_softmax_backward", "flex_plan_softmax_info", "flex_attention", "flex_plan_attention_info",
     "flex_attention_backward", "flex_plan_attention_backward_info", "flex_attention_heads", "flex_attention_heads_backward",
     "flex_gat_attention", "flex_gat_attention_backward", "flex_plan_record_info", "flex_plan_read_records",
+    "flex_attention_bf16", "flex_attention_bf16_backward",
 ]
 
 _lib = None
@@ -252,7 +253,7 @@ def lib():
 
 def _values_fn(name: str):
     """flex_plan_set_values / flex_sddmm / flex_edge_softmax / flex_edge_softmax_backward / flex_attention / flex_attention_backward and the
-    two multi-head and the two GAT calls, looked up at first use and not when the library loads: a host-only build without the kernel files does not define them (tests/hostsim has stand-ins that only log which
+    two multi-head, the two bf16 and the two GAT calls, looked up at first use and not when the library loads: a host-only build without the kernel files does not define them (tests/hostsim has stand-ins that only log which
     kernel the real ones would launch)."""
     L = lib()
     f = getattr(L, name)
@@ -263,6 +264,8 @@ def _values_fn(name: str):
                       "flex_attention_backward": [vp, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp],
                       "flex_attention_heads": [vp, i32, vp, vp, vp, fl, vp, vp, vp],
                       "flex_attention_heads_backward": [vp, i32, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp],
+                      "flex_attention_bf16": [vp, i32, vp, vp, vp, fl, vp, vp, vp],
+                      "flex_attention_bf16_backward": [vp, i32, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp],
                       "flex_gat_attention": [vp, i32, vp, vp, vp, fl, vp, vp, vp],
                       "flex_gat_attention_backward": [vp, i32, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp]}[name]
     return f
@@ -725,6 +728,63 @@ class Plan:
         self.attention_backward_ptr(Q.data_ptr(), K.data_ptr(), V.data_ptr(), p.data_ptr(), grad_out.data_ptr(), scale,
                                     *(None if t is None else t.data_ptr() for t in outs), work.data_ptr(),
                                     torch.cuda.current_stream(Q.device).cuda_stream, heads=None if heads == 1 else heads)
+        return tuple(outs)
+
+    def attention_bf16_ptr(self, dQ_ptr: int, dK_ptr: int, dV_ptr: int, scale: float, dOut_ptr: int, dP_ptr: int | None = None, stream: int = 0,
+                           heads: int = 1):
+        """flex_attention_bf16: Q, K, V and Out are bf16 rows, dP (optional) is nnz x H floats, entry-major."""
+        _check(_values_fn("flex_attention_bf16")(self._h, heads, dQ_ptr, dK_ptr, dV_ptr, scale, dOut_ptr, dP_ptr, stream), "flex_attention_bf16")
+
+    def _bf16_edge_arrays(self, heads, *ts):
+        import torch
+        for t in ts:
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (self.src_nnz, heads), "float32 cuda [nnz, heads]"
+
+    def attention_bf16(self, Q, K, V, scale: float, heads: int = 1, out=None, p=None):
+        """flex_attention_bf16: attention(..., heads=heads) on torch.bfloat16 cuda tensors Q [m, k], K, V [n, k]; scores, softmax and sums
+        in float32, out [m, k] bfloat16 rounded once at its store.  p (optional): a float32 cuda tensor [a.nnz, heads] that receives alpha,
+        not rounded.  heads = 1 runs here too: k / heads is a power of two in 4 .. 256 for every heads."""
+        import torch
+        i = self.info()
+        for t, rows in ((Q, i["m"]), (K, i["n"]), (V, i["n"])):
+            assert t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous() and tuple(t.shape) == (rows, i["k"]), "bfloat16 cuda [rows, k]"
+        if out is None:  # every row is written, except by a plan without entries, which launches nothing
+            out = (torch.empty if i["nnz"] else torch.zeros)((i["m"], i["k"]), dtype=torch.bfloat16, device=Q.device)
+        assert out.is_cuda and out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (i["m"], i["k"])
+        if p is not None:
+            self._bf16_edge_arrays(heads, p)
+        self.attention_bf16_ptr(Q.data_ptr(), K.data_ptr(), V.data_ptr(), scale, out.data_ptr(), None if p is None else p.data_ptr(),
+                                torch.cuda.current_stream(Q.device).cuda_stream, heads=heads)
+        return out
+
+    def attention_bf16_backward_ptr(self, dQ_ptr: int, dK_ptr: int, dV_ptr: int, dP_ptr: int, dGradOut_ptr: int, scale: float, dGradQ_ptr: int | None,
+                                    dGradK_ptr: int | None, dGradV_ptr: int | None, dWork_ptr: int, stream: int = 0, heads: int = 1):
+        """flex_attention_bf16_backward: the row operands and the gradients are bf16 rows, dP and dWork nnz x H floats, entry-major."""
+        _check(_values_fn("flex_attention_bf16_backward")(self._h, heads, dQ_ptr, dK_ptr, dV_ptr, dP_ptr, dGradOut_ptr, scale, dGradQ_ptr, dGradK_ptr,
+                                                          dGradV_ptr, dWork_ptr, stream), "flex_attention_bf16_backward")
+
+    def attention_bf16_backward(self, Q, K, V, p, grad_out, scale: float, heads: int = 1, grad_q=None, grad_k=None, grad_v=None, work=None,
+                                want=(True, True, True)):
+        """flex_attention_bf16_backward: (gQ [m, k], gK [n, k], gV [n, k]) in bfloat16 of attention_bf16()'s out from its p [a.nnz, heads]
+        (float32) and grad_out [m, k] (bfloat16), in two launches; an output that `want` does not ask for is None and is not computed.
+        work (optional): a float32 cuda tensor [a.nnz, heads], not p, that receives the gradient in the scores whenever gQ or gK is wanted."""
+        import torch
+        i = self.info()
+        for t, rows in ((Q, i["m"]), (K, i["n"]), (V, i["n"]), (grad_out, i["m"])):
+            assert t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous() and tuple(t.shape) == (rows, i["k"]), "bfloat16 cuda [rows, k]"
+        if work is None:
+            work = torch.empty((self.src_nnz, heads), dtype=torch.float32, device=Q.device)
+        self._bf16_edge_arrays(heads, p, work)
+        outs = []
+        for wanted, t, rows in zip(want, (grad_q, grad_k, grad_v), (i["m"], i["n"], i["n"])):
+            if wanted and t is None:  # every row is written, except by a plan without entries, which launches nothing
+                t = (torch.empty if i["nnz"] else torch.zeros)((rows, i["k"]), dtype=torch.bfloat16, device=Q.device)
+            if wanted:
+                assert t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous() and tuple(t.shape) == (rows, i["k"])
+            outs.append(t if wanted else None)
+        self.attention_bf16_backward_ptr(Q.data_ptr(), K.data_ptr(), V.data_ptr(), p.data_ptr(), grad_out.data_ptr(), scale,
+                                         *(None if t is None else t.data_ptr() for t in outs), work.data_ptr(),
+                                         torch.cuda.current_stream(Q.device).cuda_stream, heads=heads)
         return tuple(outs)
 
     def gat_attention_ptr(self, heads: int, dEl_ptr: int, dEr_ptr: int, dV_ptr: int, slope: float, dOut_ptr: int, dP_ptr: int | None = None,

@@ -1,8 +1,9 @@
 // attention_device.h -- what the kernels of the fused attention share on the device: the views of the row walk and of the column walk,
 // the column, dot, axpy and slot-reduction helpers, the forward's softmax state, the backward's plain sums, the one slot placement of all
 // nine kernels (place_of) and the head split of the per-head kernels.  Used by attention_kernels.hip (flex_attention),
-// attention_backward_kernels.hip (flex_attention_backward), attention_heads_kernels.hip (their multi-head forms) and
-// attention_gat_kernels.hip (the GAT forms); what their entry points share on the host is attention_host.h.
+// attention_backward_kernels.hip (flex_attention_backward), attention_heads_kernels.hip and attention_bf16_kernels.hip (their multi-head
+// forms in fp32 and in bf16, through attention_heads_device.h) and attention_gat_kernels.hip (the GAT forms); what their entry points
+// share on the host is attention_host.h.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -52,6 +53,29 @@ __device__ __forceinline__ void store_cols(float *__restrict__ row, int c, int k
         if (c + 2 < k) row[c + 2] = x.z;
         if (c + 3 < k) row[c + 3] = x.w;
     }
+}
+
+// The same four columns of a row of flex_bf16 (the upper 16 bits of a float each), as the fp32 numbers they are: one 8-byte load,
+// widened by shifts.  Only the vector form is built: the row and c are multiples of four elements.
+template <bool VEC>
+__device__ __forceinline__ float4 load_cols(const flex_bf16 *__restrict__ row, int c, int k) {
+    static_assert(VEC, "bf16 rows have the 8-byte form only");
+    if (c >= k) return make_float4(0.f, 0.f, 0.f, 0.f);
+    const uint2 r = *reinterpret_cast<const uint2 *>(row + c);
+    return make_float4(__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xFFFF0000u), __uint_as_float(r.y << 16), __uint_as_float(r.y & 0xFFFF0000u));
+}
+
+// fp32 to bf16, round to nearest even; +-inf stays, what rounds past the largest finite bf16 becomes +-inf, a NaN stays a (quiet) NaN
+__device__ __forceinline__ uint32_t bf16_bits(float x) {
+    const uint32_t u = __float_as_uint(x);
+    return x != x ? (u >> 16) | 0x40u : (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+}
+
+// four fp32 narrowed to flex_bf16 and stored by one 8-byte store: the one rounding of an output element
+template <bool VEC>
+__device__ __forceinline__ void store_cols(flex_bf16 *__restrict__ row, int c, int k, const float4 &x) {
+    static_assert(VEC, "bf16 rows have the 8-byte form only");
+    if (c < k) *reinterpret_cast<uint2 *>(row + c) = make_uint2(bf16_bits(x.x) | (bf16_bits(x.y) << 16), bf16_bits(x.z) | (bf16_bits(x.w) << 16));
 }
 
 // sum over the lane's columns of q * b; columns at or past k add nothing (not even 0 x b)
@@ -133,8 +157,8 @@ __device__ __forceinline__ void merge(State<NS> &a, const State<NS> &b, float sc
 }
 
 // the Out row of a final state: NaN on a poisoned row, the sums as they are where no entry is live
-template <int NS, bool VEC>
-__device__ __forceinline__ void write_row(float *__restrict__ orow, const State<NS> &st, uint32_t li, int W, int k) {
+template <int NS, bool VEC, class E>
+__device__ __forceinline__ void write_row(E *__restrict__ orow, const State<NS> &st, uint32_t li, int W, int k) {
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
         float4 o;

@@ -2,340 +2,24 @@
 // flex_attention_heads_backward): H heads of d = k / H columns each in the one forward launch and the two backward launches of
 // flex_attention and flex_attention_backward, on the same plans.  tests/test_gpu_multihead_attention.py covers it.
 //
-// The walk is the single-head kernels' (attention_kernels.hip, attention_backward_kernels.hip; attention_device.h, which also holds the
-// head split: HeadSplit, HeadLane, head_total, merge_slots_heads, HeadsShared; split_of is in attention_host.h): the same view, items,
-// groups, slot / wave / block ownership, W = sddmm_lanes(k) lanes per slot, four entries per pass and four columns per lane and slab.
-// d is a power of two in [4, 256], so a head is HW = d / 4 whole lanes of one slab: the lane that holds columns c .. c + 3 belongs to
-// head c / d, and the lanes of a head are HW consecutive lanes that start at a multiple of HW.  HW is a launch argument (its log2),
-// the same for every lane.  Where k / 4 < W (k = 48: 12 of 16 lanes) the lanes past k hold zeros, form groups of their own and neither
-// read nor write an edge array.  What changes against one head:
-//   forward        a score is reduced over the HW lanes of the lane's head, per slab (head_total), so every lane holds the four scores
-//                  of ITS head; the running maximum, the running sum, the rescale, the mask and poison rules and every merge are kept
-//                  per lane and slab, i.e. per head (State<1> per slab: all lanes of a head hold the same bits); a block row's waves
-//                  meet in LDS with one (m, l) per group of four columns
-//   row backward   da is reduced the same way, delta is per lane and slab, ds of the lane's own head enters gQ
-//   column backward p and ds are read at the lane's head; nothing else (there was never a reduction across lanes)
-// Edge arrays (dP, dWork) are entry-major: (entry e, head h) at e H + h.  Of the HW lanes of a head, lane r (r = lane % HW) writes
-// entry u of a pass where u == r (HW >= 4) or u % HW == r (HW = 1, 2); the same lane reads its element back in the second sweep.
-// Fixed order everywhere, no atomics.  Only the 16-byte form is built (the host refuses the rest).
+// The sweeps are attention_heads_device.h's with the element type float (attention_bf16_kernels.hip instantiates the same sweeps with
+// flex_bf16); the kernels below declare the LDS and call them.
+//
+// The walk, the head split and the layout of the edge arrays are described there.  Only the 16-byte form is built (the host refuses
+// the rest).
 #include <cmath>
 #include <cstdint>
 
-#include "attention_host.h"
+#include "attention_heads_device.h"
 
 namespace flex {
 namespace attention {
 
-// ---- forward
-
-// attention_kernels.hip, sweep, with the state per slab
-template <int W, int NS>
-__device__ __forceinline__ void sweep_heads(const View &v, const HeadSplit &hs, const HeadLane &hl, const float4 (&q)[NS], const float *__restrict__ K,
-                                            const float *__restrict__ V, float scale, float *__restrict__ P, const Place &pl, uint32_t lane, uint32_t li,
-                                            State<1> (&st)[NS]) {
-    const int slot_lane0 = static_cast<int>(lane - li);
-    // four slabs: the V rows of a slab are gathered when its scores are done, not with the K rows -- the per-slab state would otherwise
-    // take the kernel past 256 registers, to one wave per SIMD
-    constexpr bool kLateV = NS == 4;
-    for (uint32_t pass = 0; pass < pl.n_pass; ++pass) {
-        const uint64_t j0 = (static_cast<uint64_t>(pass) * pl.T + pl.t) * U;
-        const bool mine = li < static_cast<uint32_t>(U) && j0 + li < pl.len;
-        const uint32_t idx = mine ? v.src[pl.first - v.e0 + j0 + li] : 0u;
-        bool valid[U];
-        float4 kv[U][NS], vv[U][NS];
-        const float *vrow[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const uint32_t col = __shfl(idx, slot_lane0 + u);
-            valid[u] = j0 + u < pl.len;
-            const float *kr = K + static_cast<size_t>(col) * v.ldb, *vr = V + static_cast<size_t>(col) * v.ldb;
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                const int c = 4 * static_cast<int>(li) + 4 * W * s;
-                kv[u][s] = valid[u] ? load_cols<true>(kr, c, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
-                if constexpr (!kLateV) vv[u][s] = valid[u] ? load_cols<true>(vr, c, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-            vrow[u] = vr;
-        }
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const int c = 4 * static_cast<int>(li) + 4 * W * s;
-            if constexpr (kLateV) {
-#pragma unroll
-                for (int u = 0; u < U; ++u) vv[u][s] = valid[u] ? load_cols<true>(vrow[u], c, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-            float sc[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) sc[u] = head_total<W>(dot_cols<true>(0.f, q[s], kv[u][s], c, v.k), hl.hw);
-            float pm = -INFINITY;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                if (!valid[u]) sc[u] = -INFINITY;
-                pm = fmaxf(pm, max_key(sc[u]));
-            }
-            if (P && c < v.k) {
-                const uint32_t head = (li + static_cast<uint32_t>(W * s)) >> hs.lg;
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    if (valid[u] && hl.writes(u)) P[(pl.first + j0 + u) * static_cast<uint64_t>(hs.H) + head] = sc[u];
-                }
-            }
-            State<1> &x = st[s];
-            if (pm > x.m) {
-                const float f = carry(x.m, pm, scale);
-                x.l *= f;
-                x.acc[0] = scaled(x.acc[0], f);
-                x.m = pm;
-            }
-            if (x.m != INFINITY) {
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    if (valid[u]) {
-                        const float tm = term(sc[u], x.m, scale);
-                        x.l += tm;
-                        axpy(x.acc[0], tm, vv[u][s]);
-                    }
-                }
-            }
-        }
-    }
-}
-
-template <int W, int NS>
-__device__ __forceinline__ void run_item_heads(const View &v, const HeadSplit &hs, const uint4 &it, int kind, const float *__restrict__ Q,
-                                               const float *__restrict__ K, const float *__restrict__ V, float scale, float *__restrict__ Out,
-                                               float *__restrict__ P, uint32_t lane, uint32_t w, HeadsShared<W, NS> &sh) {
-    const uint32_t slot = lane / W, li = lane % W;
-    const HeadLane hl(hs, li);
-    const Place pl = place_of<W>(v.rowptr, it, kind, slot, w);
-    float4 q[NS];
-    State<1> st[NS];
-    const float *qrow = Q + static_cast<size_t>(pl.line) * v.ldc;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        q[s] = pl.has_line ? load_cols<true>(qrow, 4 * static_cast<int>(li) + 4 * W * s, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
-        st[s].m = -INFINITY;
-        st[s].l = 0.f;
-        st[s].acc[0] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    sweep_heads<W, NS>(v, hs, hl, q, K, V, scale, P, pl, lane, li, st);
-    if (kind != kSlotLine) merge_slots_heads<W, NS>(st, lane, scale);
-    bool writer = kind == kSlotLine ? pl.has_line : slot == 0;
-    if (kind == kBlockLine) {
-        if (slot == 0) {
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                *reinterpret_cast<float4 *>(&sh.acc[w][4 * li + 4 * W * s]) = st[s].acc[0];
-                sh.ml[w][li + W * s] = make_float2(st[s].m, st[s].l);
-            }
-        }
-        __syncthreads();
-        writer = w == 0 && slot == 0;
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {  // the waves in wave order: every lane folds (m, l) of its head, the writing lanes their columns as well
-            State<1> tot;
-            tot.m = sh.ml[0][li + W * s].x;
-            tot.l = sh.ml[0][li + W * s].y;
-            tot.acc[0] = writer ? *reinterpret_cast<const float4 *>(&sh.acc[0][4 * li + 4 * W * s]) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int i = 1; i < kWavesPerBlock; ++i) {
-                State<1> o;
-                o.m = sh.ml[i][li + W * s].x;
-                o.l = sh.ml[i][li + W * s].y;
-                o.acc[0] = writer ? *reinterpret_cast<const float4 *>(&sh.acc[i][4 * li + 4 * W * s]) : make_float4(0.f, 0.f, 0.f, 0.f);
-                merge(tot, o, scale);
-            }
-            st[s] = tot;
-        }
-    }
-    if (writer) {
-        float *orow = Out + static_cast<size_t>(pl.line) * v.ldc;
-#pragma unroll
-        for (int s = 0; s < NS; ++s) write_row<1, true>(orow + 4 * W * s, st[s], li, W, v.k - 4 * W * s);
-    }
-    if (P) {  // the second sweep of dP: the lane that wrote a raw score overwrites it with the probability under its head's final (M, L)
-        for (uint32_t pass = 0; pass < pl.n_pass; ++pass) {
-            const uint64_t j0 = (static_cast<uint64_t>(pass) * pl.T + pl.t) * U;
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                if (4 * static_cast<int>(li) + 4 * W * s >= v.k) continue;
-                const uint32_t head = (li + static_cast<uint32_t>(W * s)) >> hs.lg;
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    if (j0 + u < pl.len && hl.writes(u)) {
-                        const uint64_t e = (pl.first + j0 + u) * static_cast<uint64_t>(hs.H) + head;
-                        P[e] = prob(P[e], st[s].m, st[s].l, scale);
-                    }
-                }
-            }
-        }
-    }
-}
-
-// Grid: as attention_rows.
 template <int W, int NS>
 __global__ __launch_bounds__(256) void attention_heads_rows(View v, HeadSplit hs, const float *__restrict__ Q, const float *__restrict__ K,
                                                              const float *__restrict__ V, float scale, float *__restrict__ Out, float *__restrict__ P) {
     __shared__ HeadsShared<W, NS> sh;
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    if (blockIdx.x < v.n_block_rows) {
-        run_item_heads<W, NS>(v, hs, v.item[v.n_wave_items + blockIdx.x], kBlockLine, Q, K, V, scale, Out, P, lane, w, sh);
-        return;
-    }
-    uint32_t wg = blockIdx.x - v.n_block_rows;
-    if (v.xcd_remap) {
-        const uint32_t per = (gridDim.x - v.n_block_rows) / kXcds;
-        wg = (wg % kXcds) * per + wg / kXcds;
-    }
-    const uint32_t grp = wg * kWavesPerBlock + w;
-    if (grp >= v.n_groups) return;
-    const uint32_t i1 = v.grp[grp + 1];
-    for (uint32_t i = v.grp[grp]; i < i1; ++i) {
-        const uint4 it = v.item[i];
-        const int kind = (it.w > 1 || it.y <= kAtSlotRow) ? kSlotLine : kWaveLine;  // internal.h, attention_row_class
-        run_item_heads<W, NS>(v, hs, it, kind, Q, K, V, scale, Out, P, lane, w, sh);
-    }
-}
-
-// ---- row backward
-
-template <int W, int NS>
-struct HeadsRowShared {
-    float delta[kWavesPerBlock][W * NS];
-    alignas(16) float acc[kWavesPerBlock][4 * W * NS];
-};
-
-// attention_backward_kernels.hip, run_row, with da, delta and ds per slab
-template <int W, int NS>
-__device__ __forceinline__ void run_row_heads(const View &v, const HeadSplit &hs, const uint4 &it, int kind, const float *__restrict__ K,
-                                              const float *__restrict__ V, const float *__restrict__ P, const float *__restrict__ G, float scale,
-                                              float *__restrict__ GQ, float *__restrict__ Work, uint32_t lane, uint32_t w, HeadsRowShared<W, NS> &sh) {
-    const uint32_t slot = lane / W, li = lane % W;
-    const int slot_lane0 = static_cast<int>(lane - li);
-    const HeadLane hl(hs, li);
-    const Place pl = place_of<W>(v.rowptr, it, kind, slot, w);
-    float4 g[NS];
-    const float *grow = G + static_cast<size_t>(pl.line) * v.ldc;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) g[s] = pl.has_line ? load_cols<true>(grow, 4 * static_cast<int>(li) + 4 * W * s, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
-    // sweep 1: da into dWork, delta of the lane's heads
-    float delta[NS];
-#pragma unroll
-    for (int s = 0; s < NS; ++s) delta[s] = 0.f;
-    for (uint32_t pass = 0; pass < pl.n_pass; ++pass) {
-        const uint64_t j0 = (static_cast<uint64_t>(pass) * pl.T + pl.t) * U;
-        const bool mine = li < static_cast<uint32_t>(U) && j0 + li < pl.len;
-        const uint32_t idx = mine ? v.src[pl.first - v.e0 + j0 + li] : 0u;
-        bool valid[U];
-        float4 vv[U][NS];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const uint32_t col = __shfl(idx, slot_lane0 + u);
-            valid[u] = j0 + u < pl.len;
-            const float *vr = V + static_cast<size_t>(col) * v.ldb;
-#pragma unroll
-            for (int s = 0; s < NS; ++s) vv[u][s] = valid[u] ? load_cols<true>(vr, 4 * static_cast<int>(li) + 4 * W * s, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const int c = 4 * static_cast<int>(li) + 4 * W * s;
-            const uint32_t head = (li + static_cast<uint32_t>(W * s)) >> hs.lg;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const float da = head_total<W>(dot_cols<true>(0.f, g[s], vv[u][s], c, v.k), hl.hw);
-                if (valid[u] && c < v.k) {
-                    const uint64_t e = (pl.first + j0 + u) * static_cast<uint64_t>(hs.H) + head;
-                    if (hl.writes(u)) Work[e] = da;
-                    delta[s] = __builtin_fmaf(P[e], da, delta[s]);
-                }
-            }
-        }
-    }
-    if (kind != kSlotLine) sum_slot_scalars<W, NS>(delta, lane);
-    if (kind == kBlockLine) {
-        if (slot == 0) {
-#pragma unroll
-            for (int s = 0; s < NS; ++s) sh.delta[w][li + W * s] = delta[s];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            delta[s] = sh.delta[0][li + W * s];
-#pragma unroll
-            for (int i = 1; i < kWavesPerBlock; ++i) delta[s] += sh.delta[i][li + W * s];
-        }
-    }
-    // sweep 2: ds over da in dWork, gQ
-    float4 acc[NS];
-#pragma unroll
-    for (int s = 0; s < NS; ++s) acc[s] = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int head_lane0 = static_cast<int>(lane - hl.r);
-    for (uint32_t pass = 0; pass < pl.n_pass; ++pass) {
-        const uint64_t j0 = (static_cast<uint64_t>(pass) * pl.T + pl.t) * U;
-        float dse[NS][U];  // on the lane that owns (entry u, the head of slab s); 0 elsewhere
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const bool live = 4 * static_cast<int>(li) + 4 * W * s < v.k;
-            const uint32_t head = (li + static_cast<uint32_t>(W * s)) >> hs.lg;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                dse[s][u] = 0.f;
-                if (live && j0 + u < pl.len && hl.writes(u)) {
-                    const uint64_t e = (pl.first + j0 + u) * static_cast<uint64_t>(hs.H) + head;
-                    const float d = Work[e] - delta[s];
-                    dse[s][u] = (scale * P[e]) * d;
-                    Work[e] = dse[s][u];
-                }
-            }
-        }
-        if (!GQ) continue;
-        const bool mine = li < static_cast<uint32_t>(U) && j0 + li < pl.len;
-        const uint32_t idx = mine ? v.src[pl.first - v.e0 + j0 + li] : 0u;
-        bool valid[U];
-        float4 kv[U][NS];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const uint32_t col = __shfl(idx, slot_lane0 + u);
-            valid[u] = j0 + u < pl.len;
-            const float *kr = K + static_cast<size_t>(col) * v.ldb;
-#pragma unroll
-            for (int s = 0; s < NS; ++s) kv[u][s] = valid[u] ? load_cols<true>(kr, 4 * static_cast<int>(li) + 4 * W * s, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int owner = head_lane0 + static_cast<int>(static_cast<uint32_t>(u) & hl.wm);
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                const float d = __shfl(dse[s][u], owner);
-                if (valid[u]) axpy(acc[s], d, kv[u][s]);
-            }
-        }
-    }
-    if (!GQ) return;
-    if (kind != kSlotLine) sum_slots<W, NS>(acc, lane);
-    bool writer = kind == kSlotLine ? pl.has_line : slot == 0;
-    if (kind == kBlockLine) {
-        if (slot == 0) {
-#pragma unroll
-            for (int s = 0; s < NS; ++s) *reinterpret_cast<float4 *>(&sh.acc[w][4 * li + 4 * W * s]) = acc[s];
-        }
-        __syncthreads();
-        writer = w == 0 && slot == 0;
-        if (writer) {
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                float4 tot = *reinterpret_cast<const float4 *>(&sh.acc[0][4 * li + 4 * W * s]);
-#pragma unroll
-                for (int i = 1; i < kWavesPerBlock; ++i) tot = add4(tot, *reinterpret_cast<const float4 *>(&sh.acc[i][4 * li + 4 * W * s]));
-                acc[s] = tot;
-            }
-        }
-    }
-    if (writer) {
-        float *orow = GQ + static_cast<size_t>(pl.line) * v.ldc;
-#pragma unroll
-        for (int s = 0; s < NS; ++s) store_cols<true>(orow, 4 * static_cast<int>(li) + 4 * W * s, v.k, acc[s]);
-    }
+    walk_rows_heads<W, NS>(v, hs, Q, K, V, scale, Out, P, sh);
 }
 
 template <int W, int NS>
@@ -343,116 +27,7 @@ __global__ __launch_bounds__(256) void attention_heads_rows_backward(View v, Hea
                                                                       const float *__restrict__ P, const float *__restrict__ G, float scale,
                                                                       float *__restrict__ GQ, float *__restrict__ Work) {
     __shared__ HeadsRowShared<W, NS> sh;
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    if (blockIdx.x < v.n_block_rows) {
-        run_row_heads<W, NS>(v, hs, v.item[v.n_wave_items + blockIdx.x], kBlockLine, K, V, P, G, scale, GQ, Work, lane, w, sh);
-        return;
-    }
-    uint32_t wg = blockIdx.x - v.n_block_rows;
-    if (v.xcd_remap) {
-        const uint32_t per = (gridDim.x - v.n_block_rows) / kXcds;
-        wg = (wg % kXcds) * per + wg / kXcds;
-    }
-    const uint32_t grp = wg * kWavesPerBlock + w;
-    if (grp >= v.n_groups) return;
-    const uint32_t i1 = v.grp[grp + 1];
-    for (uint32_t i = v.grp[grp]; i < i1; ++i) {
-        const uint4 it = v.item[i];
-        const int kind = (it.w > 1 || it.y <= kAtSlotRow) ? kSlotLine : kWaveLine;
-        run_row_heads<W, NS>(v, hs, it, kind, K, V, P, G, scale, GQ, Work, lane, w, sh);
-    }
-}
-
-// ---- column backward
-
-template <int W, int NS>
-struct HeadsColumnShared {
-    alignas(16) float acc[2][kWavesPerBlock][4 * W * NS];
-};
-
-// attention_backward_kernels.hip, run_column, with p and ds of the lane's head
-template <int W, int NS>
-__device__ __forceinline__ void run_column_heads(const ColumnView &v, const HeadSplit &hs, const uint4 &it, int kind, const float *__restrict__ Q,
-                                                 const float *__restrict__ G, const float *__restrict__ P, const float *__restrict__ DS,
-                                                 float *__restrict__ GK, float *__restrict__ GV, uint32_t lane, uint32_t w, HeadsColumnShared<W, NS> &sh) {
-    const uint32_t slot = lane / W, li = lane % W;
-    const int slot_lane0 = static_cast<int>(lane - li);
-    const Place pl = place_of<W>(v.colptr, it, kind, slot, w);
-    float4 ak[NS], av[NS];
-#pragma unroll
-    for (int s = 0; s < NS; ++s) ak[s] = av[s] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (uint32_t pass = 0; pass < pl.n_pass; ++pass) {
-        const uint64_t j0 = (static_cast<uint64_t>(pass) * pl.T + pl.t) * U;
-        const bool mine = li < static_cast<uint32_t>(U) && j0 + li < pl.len;
-        const uint2 re = mine ? v.ent[pl.first + j0 + li] : make_uint2(0u, 0u);
-        bool valid[U];
-        float pe[U][NS], de[U][NS];
-        float4 gg[U][NS], qq[U][NS];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const uint32_t row = __shfl(re.x, slot_lane0 + u), e = __shfl(re.y, slot_lane0 + u);
-            valid[u] = j0 + u < pl.len;
-            const float *gr = G + static_cast<size_t>(row) * v.ldc, *qr = Q + static_cast<size_t>(row) * v.ldc;
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                const int c = 4 * static_cast<int>(li) + 4 * W * s;
-                const bool live = valid[u] && c < v.k;
-                const uint64_t eh = static_cast<uint64_t>(e) * static_cast<uint64_t>(hs.H) + ((li + static_cast<uint32_t>(W * s)) >> hs.lg);
-                pe[u][s] = (GV && live) ? P[eh] : 0.f;
-                de[u][s] = (GK && live) ? DS[eh] : 0.f;
-                gg[u][s] = (GV && valid[u]) ? load_cols<true>(gr, c, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
-                qq[u][s] = (GK && valid[u]) ? load_cols<true>(qr, c, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (valid[u]) {
-#pragma unroll
-                for (int s = 0; s < NS; ++s) {
-                    axpy(av[s], pe[u][s], gg[u][s]);
-                    axpy(ak[s], de[u][s], qq[u][s]);
-                }
-            }
-        }
-    }
-    if (kind != kSlotLine) {
-        sum_slots<W, NS>(ak, lane);
-        sum_slots<W, NS>(av, lane);
-    }
-    bool writer = kind == kSlotLine ? pl.has_line : slot == 0;
-    if (kind == kBlockLine) {
-        if (slot == 0) {
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                *reinterpret_cast<float4 *>(&sh.acc[0][w][4 * li + 4 * W * s]) = ak[s];
-                *reinterpret_cast<float4 *>(&sh.acc[1][w][4 * li + 4 * W * s]) = av[s];
-            }
-        }
-        __syncthreads();
-        writer = w == 0 && slot == 0;
-        if (writer) {
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                float4 tk = *reinterpret_cast<const float4 *>(&sh.acc[0][0][4 * li + 4 * W * s]);
-                float4 tv = *reinterpret_cast<const float4 *>(&sh.acc[1][0][4 * li + 4 * W * s]);
-#pragma unroll
-                for (int i = 1; i < kWavesPerBlock; ++i) {
-                    tk = add4(tk, *reinterpret_cast<const float4 *>(&sh.acc[0][i][4 * li + 4 * W * s]));
-                    tv = add4(tv, *reinterpret_cast<const float4 *>(&sh.acc[1][i][4 * li + 4 * W * s]));
-                }
-                ak[s] = tk;
-                av[s] = tv;
-            }
-        }
-    }
-    if (writer) {
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const int c = 4 * static_cast<int>(li) + 4 * W * s;
-            if (GK) store_cols<true>(GK + static_cast<size_t>(pl.line) * v.ldb, c, v.k, ak[s]);
-            if (GV) store_cols<true>(GV + static_cast<size_t>(pl.line) * v.ldb, c, v.k, av[s]);
-        }
-    }
+    walk_rows_heads_backward<W, NS>(v, hs, K, V, P, G, scale, GQ, Work, sh);
 }
 
 template <int W, int NS>
@@ -460,24 +35,7 @@ __global__ __launch_bounds__(256) void attention_heads_columns_backward(ColumnVi
                                                                          const float *__restrict__ P, const float *__restrict__ DS, float *__restrict__ GK,
                                                                          float *__restrict__ GV) {
     __shared__ HeadsColumnShared<W, NS> sh;
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    if (blockIdx.x < v.n_block_cols) {
-        run_column_heads<W, NS>(v, hs, v.item[v.n_wave_items + blockIdx.x], kBlockLine, Q, G, P, DS, GK, GV, lane, w, sh);
-        return;
-    }
-    uint32_t wg = blockIdx.x - v.n_block_cols;
-    if (v.xcd_remap) {
-        const uint32_t per = (gridDim.x - v.n_block_cols) / kXcds;
-        wg = (wg % kXcds) * per + wg / kXcds;
-    }
-    const uint32_t grp = wg * kWavesPerBlock + w;
-    if (grp >= v.n_groups) return;
-    const uint32_t i1 = v.grp[grp + 1];
-    for (uint32_t i = v.grp[grp]; i < i1; ++i) {
-        const uint4 it = v.item[i];
-        const int kind = (it.w > 1 || it.y <= kAtSlotRow) ? kSlotLine : kWaveLine;
-        run_column_heads<W, NS>(v, hs, it, kind, Q, G, P, DS, GK, GV, lane, w, sh);
-    }
+    walk_columns_heads_backward<W, NS>(v, hs, Q, G, P, DS, GK, GV, sh);
 }
 
 // ---- launches

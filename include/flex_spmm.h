@@ -29,6 +29,7 @@ extern "C" {
                               the equally additive FLEX_PLAN_ATTENTION_BACKWARD, flex_attention_backward and flex_plan_attention_backward_info (the same again),
                               the equally additive flex_attention_heads and flex_attention_heads_backward (two new calls, no flag, no struct),
                               the equally additive flex_gat_attention and flex_gat_attention_backward (the same again),
+                              the equally additive flex_bf16, flex_attention_bf16 and flex_attention_bf16_backward (a typedef and two new calls, no flag, no struct),
                               and the retired flex_plan_tuning.block_ablate, which keeps its place as block_ablate_retired and must be zero.
                               3: plan-time knobs leave the environment for the struct flex_plan_tuning, flex_plan_desc.tuning, flex_plan_get_tuning,
                               flex_order_cluster_ex, flex_set_host_threads; split rows are summed by a second launch by default.
@@ -494,6 +495,42 @@ int flex_attention_heads(const flex_plan *plan, int heads, const float *dQ, cons
 int flex_attention_heads_backward(const flex_plan *plan, int heads, const float *dQ, const float *dK, const float *dV, const float *dP,
                                   const float *dGradOut, float scale, float *dGradQ, float *dGradK, float *dGradV, float *dWork,
                                   flex_stream_t stream);
+
+/* Multi-head fused attention on bf16 row operands: flex_attention_heads and flex_attention_heads_backward with Q, K, V, Out, g, gQ, gK
+ * and gV held as bf16 -- half the bytes of every gathered row -- in the same ONE forward launch and TWO backward launches, on the same
+ * plans (FLEX_PLAN_ATTENTION; FLEX_PLAN_ATTENTION_BACKWARD for the second call; FLEX_ERR_INVALID on any other plan).  No new plan flag
+ * and no new image.  No reference counterpart.  A flex_bf16 is the upper 16 bits of an IEEE float (torch.bfloat16).  Definition: read
+ * every bf16 operand as the fp32 number it is (the conversion is exact); then everything is what flex_attention_heads and
+ * flex_attention_heads_backward define, in fp32 -- the scores, the masked (-inf) and poisoned (+inf / NaN) rules per head, +0 rows,
+ * "every entry multiplies its V row", da, delta, ds, gQ, gK, gV -- with accumulation and softmax in fp32, and at the single store of
+ * each element of Out, gQ, gK and gV the fp32 value is rounded to bf16, round to nearest even: a NaN stays a NaN, +-inf stays +-inf, a
+ * finite value beyond the largest finite bf16 becomes +-inf, and a poisoned head still writes NaN into its own d columns only.  dP and
+ * dWork are fp32, hostA->nnz x H floats, entry-major, and are NOT rounded: they hold the values flex_attention_heads and
+ * flex_attention_heads_backward write for the widened operands, bit for bit, and Out, gQ, gK and gV are the bf16 roundings of theirs.
+ * The plan's ldb and ldc are element strides, as before (a row of K is ldb flex_bf16 after the one before it).
+ * heads >= 1, and heads == 1 is served here directly: there is no forwarding to a generic form (as for flex_gat_attention), so for
+ * every H, H = 1 included: k % H == 0, d = k / H in {4, 8, 16, 32, 64, 128, 256} (k = 48 with H = 1 and k = 300 are refused), k <= 1024,
+ * and only the vector form is built -- ldb % 4 == 0, ldc % 4 == 0 and every row operand 8-byte aligned (one 8-byte access of four
+ * elements per lane); anything else is FLEX_ERR_UNSUPPORTED.  A plan without the attention image (without the backward image, for the
+ * second call), heads < 1, a scale that is not finite and > 0, a NULL operand (Q, K, V, Out; in the backward Q, K, V, P, GradOut, Work)
+ * and dWork == dP: FLEX_ERR_INVALID.  A plan without entries: FLEX_OK, no launch, nothing written.  dP may be NULL (Out has the same
+ * bits either way); the forward on a row-range shard writes the Out rows and the dP entries of its rows and leaves the others
+ * untouched (the backward is not defined on shards: such a plan has no backward image); each of dGradQ, dGradK, dGradV may be NULL, an
+ * output has the same bits whichever others are asked for, a launch without outputs is skipped and a call without outputs launches
+ * nothing; on return dWork holds ds whenever dGradQ or dGradK was asked for.  Asynchronous on `stream`, no allocation, no host
+ * synchronisation (safe to capture in a hipGraph), no atomics, fixed reduction order: bit-identical run to run.
+ *
+ * Accuracy, against float64 on the bf16 inputs (backward: on the same bf16 Q, K, V, g and fp32 p): dP and dWork carry the bounds of
+ * flex_attention_heads and flex_attention_heads_backward unchanged.  An output element y = rn_bf16(x32), whose fp32 value x32 lies
+ * within bound32 (the fp32 call's bound for that element) of the float64 value x64, satisfies
+ *     |y - x64| <= bound32 + 2^-8 (|x64| + bound32) + 2^-134
+ * 2^-8 being the unit roundoff of bf16 (8 significant bits) and 2^-134 half its smallest subnormal. */
+typedef uint16_t flex_bf16; /* the upper 16 bits of an IEEE float */
+int flex_attention_bf16(const flex_plan *plan, int heads, const flex_bf16 *dQ, const flex_bf16 *dK, const flex_bf16 *dV, float scale,
+                        flex_bf16 *dOut, float *dP, flex_stream_t stream);
+int flex_attention_bf16_backward(const flex_plan *plan, int heads, const flex_bf16 *dQ, const flex_bf16 *dK, const flex_bf16 *dV, const float *dP,
+                                 const flex_bf16 *dGradOut, float scale, flex_bf16 *dGradQ, flex_bf16 *dGradK, flex_bf16 *dGradV, float *dWork,
+                                 flex_stream_t stream);
 
 /* Fused GAT attention: the additive score of graph attention networks in place of the dot product, H heads in the ONE forward launch and
  * the TWO backward launches of flex_attention_heads and flex_attention_heads_backward, on the same plans (FLEX_PLAN_ATTENTION;

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Sparse graph attention, measured: the error of the exponential the edge softmax may use, and the time of flex_edge_softmax,
 flex_edge_softmax_backward and a whole attention step.  Writes profiles/attention_probe.txt (or the file given with --out): the whole run
-starts the file, a run of one part (--fused, --backward, --heads, --gat) appends to it.
+starts the file, a run of one part (--fused, --backward, --heads, --gat, --bf16) appends to it.
 
 1. tools/exp_error.hip (built here with hipcc into flex_amd/lib if it is not there): the largest error in ulp of expf, __expf and
    exp2f on the prescaled argument over every fp32 argument in [-104, 0] against float64 exp.
@@ -27,7 +27,11 @@ starts the file, a run of one part (--fused, --backward, --heads, --gat) appends
    before -- per head, torch index arithmetic for the scores on a row / col copy of the pattern, edge_softmax and the SpMM with
    values=alpha of an operator of width d on a column slice, torch autograd carrying the gradients of el and er.  --gat: only this
    part (and the copy rate).
-Usage: probe_attention.py [--out FILE] [--fused | --backward | --heads | --gat] [graph ...]   (default: pubmed.csv flickr reddit soc-sign-epinions)"""
+8. bf16 row operands (flex_attention_bf16, flex_attention_bf16_backward), (k, H) = (64, 8), (128, 4), (256, 8), same graphs and protocol:
+   the forward (with dP), the backward and the autograd step of attention(..., heads=H) on bfloat16 tensors against the same three on
+   float32 tensors (flex_attention_heads, flex_attention_heads_backward) on the same operator, in the same process.  --bf16: only this
+   part (and the copy rate).
+Usage: probe_attention.py [--out FILE] [--fused | --backward | --heads | --gat | --bf16] [graph ...]   (default: pubmed.csv flickr reddit soc-sign-epinions)"""
 import ctypes as C
 import os
 import subprocess
@@ -318,13 +322,56 @@ def probe_gat(name, a):
         del fused, one, kept
 
 
+def probe_bf16(name, a):
+    gen = torch.Generator(device="cuda").manual_seed(6)
+    for k, H in ((64, 8), (128, 4), (256, 8)):
+        d = k // H
+        op = flex_amd.SparseOperator(a, k, learn_values=True, fused_attention=True, fused_backward=True)  # one plan serves both element types
+        plan = op.plan
+        Q, K, V = (torch.rand((r, k), device="cuda", generator=gen) * 2 - 1 for r in (a.m, a.n, a.n))
+        g = torch.rand((a.m, k), device="cuda", generator=gen) * 2 - 1
+        Qb, Kb, Vb, gb = (x.bfloat16() for x in (Q, K, V, g))
+        scale = d ** -0.5
+        out, gq, gk, gv = (torch.empty((r, k), device="cuda") for r in (a.m, a.m, a.n, a.n))
+        outb, gqb, gkb, gvb = (torch.empty((r, k), device="cuda", dtype=torch.bfloat16) for r in (a.m, a.m, a.n, a.n))
+        P, W = torch.empty((a.nnz, H), device="cuda"), torch.empty((a.nnz, H), device="cuda")
+        Pb, Wb = torch.empty((a.nnz, H), device="cuda"), torch.empty((a.nnz, H), device="cuda")
+        leaves = {torch.float32: tuple(x.clone().requires_grad_() for x in (Q, K, V)), torch.bfloat16: tuple(x.clone().requires_grad_() for x in (Qb, Kb, Vb))}
+
+        def step(dtype, grad):
+            for x in leaves[dtype]:
+                x.grad = None
+            op.attention(*leaves[dtype], scale, heads=H).backward(grad)
+
+        plan.attention(Q, K, V, scale, out=out, p=P, heads=H)
+        plan.attention_bf16(Qb, Kb, Vb, scale, heads=H, out=outb, p=Pb)
+        fns = {"forward, fp32": lambda: plan.attention(Q, K, V, scale, out=out, p=P, heads=H),
+               "forward, bf16": lambda: plan.attention_bf16(Qb, Kb, Vb, scale, heads=H, out=outb, p=Pb),
+               "backward, fp32": lambda: plan.attention_backward(Q, K, V, P, g, scale, grad_q=gq, grad_k=gk, grad_v=gv, work=W, heads=H),
+               "backward, bf16": lambda: plan.attention_bf16_backward(Qb, Kb, Vb, Pb, gb, scale, heads=H, grad_q=gqb, grad_k=gkb, grad_v=gvb, work=Wb),
+               "step, fp32": lambda: step(torch.float32, g), "step, bf16": lambda: step(torch.bfloat16, gb)}
+        n = max(3, min(100, int(1e8 / max(1, a.nnz * k))))
+        rounds = {key: [] for key in fns}
+        for _ in range(3):  # alternating: every round times each contender once
+            for key, fn in fns.items():
+                rounds[key].append(best_us(fn, n, rounds=1))
+        best = {key: min(v) for key, v in rounds.items()}
+        spread = {key: 100 * (max(v) - min(v)) / min(v) for key, v in rounds.items()}
+        say(f"{name} k={k} H={H} d={d} bf16: " + "  ".join(f"{key} {best[key]:.1f} us (+{spread[key]:.0f} % over 3 rounds)" for key in fns)
+            + "  fp32 / bf16: " + "  ".join(f"{w} {best[w + ', fp32'] / best[w + ', bf16']:.2f}x" for w in ("forward", "backward", "step"))
+            + f"  row operands of a step: {2 * (2 * a.m + 2 * a.n) * k * 2 / 2 ** 20:.1f} MiB in bf16, twice that in fp32 (Q, K, V, Out and their gradients);"
+            + f" edge arrays {8 * a.nnz * H / 2 ** 20:.1f} MiB either way")
+        del op, plan
+
+
 def main():
     args = sys.argv[1:]
     out = os.path.join(ROOT, "profiles", "attention_probe.txt")
     if args[:1] == ["--out"]:
         out, args = args[1], args[2:]
-    fused_only, backward_only, heads_only, gat_only = (args[:1] == [flag] for flag in ("--fused", "--backward", "--heads", "--gat"))
-    if fused_only or backward_only or heads_only or gat_only:
+    fused_only, backward_only, heads_only, gat_only, bf16_only = (args[:1] == [flag] for flag in ("--fused", "--backward", "--heads", "--gat", "--bf16"))
+    only = fused_only or backward_only or heads_only or gat_only or bf16_only
+    if only:
         args = args[1:]
     else:
         exp_error()
@@ -332,7 +379,6 @@ def main():
     say(f"flex_hbm_probe: read {hbm['read_GBps']:.0f} GB/s, copy {hbm['copy_GBps']:.0f} GB/s")
     for name in args or ["pubmed.csv", "flickr", "reddit", "soc-sign-epinions"]:
         a = load(name)
-        only = fused_only or backward_only or heads_only or gat_only
         if not only:
             probe(name, a, hbm["copy_GBps"])
         if fused_only or not only:
@@ -343,7 +389,9 @@ def main():
             probe_heads(name, a)
         if gat_only or not only:
             probe_gat(name, a)
-    with open(out, "a" if fused_only or backward_only or heads_only or gat_only else "w") as f:  # a part is appended, the whole run starts the file
+        if bf16_only or not only:
+            probe_bf16(name, a)
+    with open(out, "a" if only else "w") as f:  # a part is appended, the whole run starts the file
         f.write("\n".join(LINES) + "\n")
 
 
