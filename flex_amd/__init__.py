@@ -19,6 +19,7 @@ from .binding import (  # noqa: F401
     FLEX_PLAN_MUTABLE_VALUES,
     FLEX_PLAN_ATTENTION,
     FLEX_PLAN_ATTENTION_BACKWARD,
+    FLEX_PLAN_BF16,
     FlexError,
     HostCsr,
     Plan,

@@ -1,4 +1,5 @@
-"""torch autograd over the engine: the gradient of C = A B with respect to B is A^T grad_C (a plan made with FLEX_PLAN_TRANSPOSE),
+"""torch autograd over the engine: the gradient of C = A B with respect to B is A^T grad_C (a plan made with FLEX_PLAN_TRANSPOSE; on
+bfloat16 operands with SparseOperator(..., bf16=True): FLEX_PLAN_BF16 plans and flex_spmm_bf16, both ways),
 and the GCN layer Out = A X W (flex_amd.axw.Axw.layer) differentiates through flex_axw_backward.  With learn_values=True, SparseOperator
 is differentiable in A's values as well: grad_v = SDDMM(grad_C, B) over A's pattern (flex_sddmm), and the values of every forward are
 set into the plans (flex_plan_set_values) without planning again.  The same two plans run a graph-attention layer end to end:
@@ -234,10 +235,16 @@ class SparseOperator:
     fused_backward=True (with fused_attention=True): the forward plan is also made with FLEX_PLAN_ATTENTION_BACKWARD and the backward of
     op.attention is one call of two launches (flex_attention_backward) that sets no plan's values.  Off by default.
     With both fused flags the operator also offers op.gat_attention(el, er, V, negative_slope): GAT's additive attention, H = el.shape[1]
-    heads in one forward launch and two backward launches (flex_gat_attention), differentiable in el [m, H], er [n, H] and V [n, k]."""
+    heads in one forward launch and two backward launches (flex_gat_attention), differentiable in el [m, H], er [n, H] and V [n, k].
+    bf16=True: both plans are made with FLEX_PLAN_BF16 (k a multiple of 8): op(B) takes and returns torch.bfloat16 (float32 raises
+    TypeError, as bfloat16 does on an fp32 operator), sums in float32, and backpropagates A^T grad_C in bfloat16 through flex_spmm_bf16 on
+    the transposed plan.  The plain product only: NotImplementedError with learn_values, the fused flags or values=."""
 
     def __init__(self, a: binding.HostCsr, k: int, device: int = 0, order: int = binding.FLEX_ORDER_NATURAL, tuning: dict | None = None,
-                 learn_values: bool = False, fused_attention: bool = False, fused_backward: bool = False):
+                 learn_values: bool = False, fused_attention: bool = False, fused_backward: bool = False, bf16: bool = False):
+        if bf16 and (learn_values or fused_attention or fused_backward):
+            raise NotImplementedError("SparseOperator(..., bf16=True) is the plain product only: learnable values and the attention calls read "
+                                      "fp32 plans (op.attention takes bfloat16 Q, K, V on an fp32 operator with both fused flags)")
         if fused_attention and not learn_values:
             raise NotImplementedError("fused_attention needs SparseOperator(..., learn_values=True): its backward sets the plans' values")
         if fused_backward and not fused_attention:
@@ -246,9 +253,10 @@ class SparseOperator:
         self.learn_values = learn_values
         self.fused_attention = fused_attention
         self.fused_backward = fused_backward
+        self.bf16 = bf16
         self.plan = binding.Plan(a, k, device=device, order=order, tuning=tuning, mutable_values=learn_values, attention=fused_attention,
-                                 attention_backward=fused_backward)
-        self.plan_t = binding.Plan(a, k, device=device, order=order, tuning=tuning, transpose=True, mutable_values=learn_values)
+                                 attention_backward=fused_backward, bf16=bf16)
+        self.plan_t = binding.Plan(a, k, device=device, order=order, tuning=tuning, transpose=True, mutable_values=learn_values, bf16=bf16)
         self._v0 = None
         if learn_values:
             import torch

@@ -29,6 +29,7 @@ FLEX_PLAN_TRANSPOSE = 0x8000
 FLEX_PLAN_MUTABLE_VALUES = 0x10000
 FLEX_PLAN_ATTENTION = 0x40000
 FLEX_PLAN_ATTENTION_BACKWARD = 0x80000
+FLEX_PLAN_BF16 = 0x100000
 
 
 class FlexError(RuntimeError):
@@ -164,7 +165,7 @@ SYMBOLS = [
     "flex_edge_softmax", "flex_edge_softmax_backward", "flex_plan_softmax_info", "flex_attention", "flex_plan_attention_info",
     "flex_attention_backward", "flex_plan_attention_backward_info", "flex_attention_heads", "flex_attention_heads_backward",
     "flex_gat_attention", "flex_gat_attention_backward", "flex_plan_record_info", "flex_plan_read_records",
-    "flex_attention_bf16", "flex_attention_bf16_backward",
+    "flex_attention_bf16", "flex_attention_bf16_backward", "flex_spmm_bf16", "flex_plan_is_bf16",
 ]
 
 _lib = None
@@ -247,13 +248,14 @@ def lib():
         L.flex_plan_attention_backward_info.argtypes = [vp, C.POINTER(_AttentionBackwardInfo)]
         L.flex_plan_record_info.argtypes = [vp, C.POINTER(_RecordInfo)]
         L.flex_plan_read_records.argtypes = [vp, vp, i64]
+        L.flex_plan_is_bf16.argtypes = [vp]
         _lib = L
     return _lib
 
 
 def _values_fn(name: str):
     """flex_plan_set_values / flex_sddmm / flex_edge_softmax / flex_edge_softmax_backward / flex_attention / flex_attention_backward and the
-    two multi-head, the two bf16 and the two GAT calls, looked up at first use and not when the library loads: a host-only build without the kernel files does not define them (tests/hostsim has stand-ins that only log which
+    two multi-head, the two bf16 and the two GAT calls and flex_spmm_bf16, looked up at first use and not when the library loads: a host-only build without the kernel files does not define them (tests/hostsim has stand-ins that only log which
     kernel the real ones would launch)."""
     L = lib()
     f = getattr(L, name)
@@ -266,6 +268,7 @@ def _values_fn(name: str):
                       "flex_attention_heads_backward": [vp, i32, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp],
                       "flex_attention_bf16": [vp, i32, vp, vp, vp, fl, vp, vp, vp],
                       "flex_attention_bf16_backward": [vp, i32, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp],
+                      "flex_spmm_bf16": [vp, vp, vp, vp],
                       "flex_gat_attention": [vp, i32, vp, vp, vp, fl, vp, vp, vp],
                       "flex_gat_attention_backward": [vp, i32, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp]}[name]
     return f
@@ -473,14 +476,17 @@ class Plan:
 
     def __init__(self, a: HostCsr, k: int, device: int = 0, order: int = FLEX_ORDER_NATURAL,
                  vo_mp=None, rows=None, col_map=None, ldb: int | None = None, ldc: int | None = None, tuning: dict | None = None,
-                 transpose: bool = False, mutable_values: bool = False, attention: bool = False, attention_backward: bool = False):
+                 transpose: bool = False, mutable_values: bool = False, attention: bool = False, attention_backward: bool = False,
+                 bf16: bool = False):
         """tuning: plan-time knobs as a dict of flex_plan_tuning fields (0 / absent = the planner's rule), e.g.
         {"lanes_per_nz": 16, "split_rows": 1, "cluster_no_refine": 1}.
         transpose: plan A^T (FLEX_PLAN_TRANSPOSE): C [a.n, k] = A^T B [a.m, k]; every other argument refers to A^T.
         mutable_values: FLEX_PLAN_MUTABLE_VALUES -- set_values() and sddmm() work on the plan; both index A's entries in a's CSR
         order, whatever the plan (transposed, mapped, a shard).
         attention: FLEX_PLAN_ATTENTION -- attention() works on the plan (not with transpose, vo_mp or col_map).
-        attention_backward: FLEX_PLAN_ATTENTION_BACKWARD -- attention_backward() works on the plan too (needs attention; not with rows)."""
+        attention_backward: FLEX_PLAN_ATTENTION_BACKWARD -- attention_backward() works on the plan too (needs attention; not with rows).
+        bf16: FLEX_PLAN_BF16 -- B and C are bfloat16, sums fp32; the plan runs spmm_bf16() / plan(B) on bfloat16 tensors and nothing else
+        (k, ldb, ldc multiples of 8; not with mutable_values, attention or autotune)."""
         self._h = C.c_void_p()
         self.src_nnz = a.nnz
         if transpose:
@@ -491,6 +497,8 @@ class Plan:
             order |= FLEX_PLAN_ATTENTION
         if attention_backward:
             order |= FLEX_PLAN_ATTENTION_BACKWARD
+        if bf16:
+            order |= FLEX_PLAN_BF16
         self._keep = (a, vo_mp, col_map)
         v = a.view()
         L = lib()
@@ -527,6 +535,7 @@ class Plan:
         _check(lib().flex_plan_get_info(self._h, C.byref(i)), "flex_plan_get_info")
         d = {f: getattr(i, f) for f, _ in _PlanInfo._fields_}
         d["rec_packed"] = self.record_info()["packed"]
+        d["bf16"] = int(lib().flex_plan_is_bf16(self._h))  # 1: k above counts bfloat16 elements and the plan runs spmm_bf16()
         return d
 
     def record_info(self) -> dict:
@@ -575,14 +584,25 @@ class Plan:
     def spmm(self, dB_ptr: int, dC_ptr: int, stream: int = 0):
         _check(lib().flex_spmm(self._h, dB_ptr, dC_ptr, stream), "flex_spmm")
 
+    def spmm_bf16(self, dB_ptr: int, dC_ptr: int, stream: int = 0):
+        """flex_spmm_bf16 (bf16=True plans only): dB, dC device pointers to bfloat16 rows, both 16-byte aligned."""
+        _check(_values_fn("flex_spmm_bf16")(self._h, dB_ptr, dC_ptr, stream), "flex_spmm_bf16")
+
     def __call__(self, B, out=None):
-        """torch convenience: B is a cuda float32 [n,k] tensor; returns C [m,k]."""
+        """torch convenience: B is a cuda [n,k] tensor, float32 -- bfloat16 on a bf16 plan (TypeError on the other); returns C [m,k] of
+        the same dtype."""
         import torch
         i = self.info()
-        assert B.is_cuda and B.dtype == torch.float32 and B.is_contiguous() and tuple(B.shape) == (i["n"], i["k"])
+        want = torch.bfloat16 if i["bf16"] else torch.float32
+        if B.dtype != want:
+            raise TypeError(f"this plan takes {want} operands, got {B.dtype}")
+        assert B.is_cuda and B.is_contiguous() and tuple(B.shape) == (i["n"], i["k"])
         if out is None:
-            out = torch.empty((i["m"], i["k"]), dtype=torch.float32, device=B.device)
-        self.spmm(B.data_ptr(), out.data_ptr(), torch.cuda.current_stream(B.device).cuda_stream)
+            out = torch.empty((i["m"], i["k"]), dtype=want, device=B.device)
+        elif out.dtype != want:
+            raise TypeError(f"this plan writes {want}, out is {out.dtype}")
+        run = self.spmm_bf16 if i["bf16"] else self.spmm
+        run(B.data_ptr(), out.data_ptr(), torch.cuda.current_stream(B.device).cuda_stream)
         return out
 
     def set_values(self, vals, stream: int | None = None):

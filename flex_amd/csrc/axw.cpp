@@ -101,6 +101,7 @@ int flex_axw_create(flex_axw **out, const flex_csr *A, int dim, int c, int devic
     if (!out) return FLEX_ERR_INVALID;
     *out = nullptr;
     if (!A || dim <= 0 || c <= 0 || device < 0 || A->m != A->n) return FLEX_ERR_INVALID;
+    if (flags & FLEX_PLAN_BF16) return FLEX_ERR_INVALID;  // the layer is fp32: its plans run flex_spmm
     flex_axw *h = new (std::nothrow) flex_axw();
     if (!h) return FLEX_ERR_NOMEM;
     h->n = A->n;

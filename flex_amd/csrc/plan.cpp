@@ -217,8 +217,25 @@ static int create_common(flex_plan **out, const flex_csr *hostA, bool all_rows, 
     if (ldb < k || ldc < k) return FLEX_ERR_INVALID;
     const unsigned order = flags & FLEX_ORDER_MASK;
     if (order > FLEX_ORDER_GORDER ||
-        (flags & ~(FLEX_ORDER_MASK | FLEX_PLAN_STATS | FLEX_PLAN_AUTOTUNE | FLEX_PLAN_XCD_INTERLEAVE | FLEX_PLAN_TRANSPOSE | FLEX_PLAN_MUTABLE_VALUES | FLEX_PLAN_ATTENTION | FLEX_PLAN_ATTENTION_BACKWARD)))
+        (flags & ~(FLEX_ORDER_MASK | FLEX_PLAN_STATS | FLEX_PLAN_AUTOTUNE | FLEX_PLAN_XCD_INTERLEAVE | FLEX_PLAN_TRANSPOSE | FLEX_PLAN_MUTABLE_VALUES | FLEX_PLAN_ATTENTION | FLEX_PLAN_ATTENTION_BACKWARD | FLEX_PLAN_BF16)))
         return FLEX_ERR_INVALID;
+    // FLEX_PLAN_BF16: the fp32 plan of the row width in 4-byte words.  From here on k, ldb and ldc are words; the planner proper never
+    // sees the flag, only flex_plan::bf16 where fp32 values are counted (plan.h).
+    const bool bf16 = (flags & FLEX_PLAN_BF16) != 0;
+    if (bf16) {
+        if (flags & (FLEX_PLAN_MUTABLE_VALUES | FLEX_PLAN_ATTENTION | FLEX_PLAN_ATTENTION_BACKWARD | FLEX_PLAN_AUTOTUNE)) return FLEX_ERR_UNSUPPORTED;
+        if (k % 8 != 0 || ldb % 8 != 0 || ldc % 8 != 0) return FLEX_ERR_UNSUPPORTED;  // 16-byte gathers and stores only
+        // every nonzero on the flat record stream, split rows summed by the second launch: the dense-tile and hot-block kernels and the
+        // in-launch sum's sc1 hand-off exist for fp32 rows only
+        if (tuning.mfma == 1 || tuning.blocks == 1 || tuning.split_rows == 1 || tuning.two_d == 1) return FLEX_ERR_UNSUPPORTED;
+        tuning.mfma = 2;
+        tuning.blocks = 2;
+        tuning.split_rows = 2;
+        k /= 2;
+        ldb /= 2;
+        ldc /= 2;
+        flags &= ~FLEX_PLAN_BF16;
+    }
     const bool mut = (flags & FLEX_PLAN_MUTABLE_VALUES) != 0;
     if (mut) {  // every nonzero on the flat record stream: the dense-tile and hot-block routes keep values in layouts of their own
         if (tuning.mfma == 1 || tuning.blocks == 1 || tuning.rec_pack == 1) return FLEX_ERR_UNSUPPORTED;
@@ -269,6 +286,7 @@ static int create_common(flex_plan **out, const flex_csr *hostA, bool all_rows, 
     p->k = k;
     p->ldb = ldb;
     p->ldc = ldc;
+    p->bf16 = bf16;
     p->nnz = static_cast<int64_t>(hostA->rowPtr[row_end]) - hostA->rowPtr[row_begin];
     p->device = device;
     std::vector<uint32_t> sched_cache;
@@ -344,7 +362,7 @@ int flex_plan_create_ex(flex_plan **out, const flex_plan_desc *d) {
 }
 
 int flex_spmm(flex_plan *p, const float *dB, float *dC, flex_stream_t stream) {
-    if (!p) return FLEX_ERR_INVALID;
+    if (!p || p->bf16) return FLEX_ERR_INVALID;  // a bf16 plan runs flex_spmm_bf16 (spmm_bf16_kernels.hip) and nothing else
     if (p->m == 0) return FLEX_OK;
     if (!dC || (!dB && p->nnz > 0)) return FLEX_ERR_INVALID;
     const DeviceScope on(p->device);
@@ -353,33 +371,16 @@ int flex_spmm(flex_plan *p, const float *dB, float *dC, flex_stream_t stream) {
     const bool fused = vec4 && p->fused_fixup;  // the generic kernel always leaves the sum to spmm_fixup_kernel
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     int rc = FLEX_OK;
-    // A plan with split rows owns their partial-sum workspace (and, in the in-launch form, their arrival counters): two launches
-    // of it must not overlap.  Launches on ONE stream are ordered by the stream; a launch on ANOTHER stream while the stream of the
-    // latest one still has work pending is refused instead of silently corrupting those rows.  The check is a stream query at the
-    // moment the stream changes -- nothing is added to the launch path of a plan that stays on its stream (an event per launch
-    // cost the Flickr-size launches 2-4 us of device time each).  It is conservative: unrelated work queued behind the plan's launch
-    // on the old stream also counts as pending.  A launch being captured into a graph is neither checked nor remembered.
-    bool guard = p->n_partials > 0;
-    if (guard) {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cap) != hipSuccess) (void)hipGetLastError();
-        if (cap != hipStreamCaptureStatusNone) guard = false;
-    }
-    if (guard && p->launched && s != p->last_stream) {
-        const hipError_t q = hipStreamQuery(p->last_stream);
-        if (q == hipErrorNotReady) return FLEX_ERR_INVALID;
-        if (q != hipSuccess) (void)hipGetLastError();  // e.g. the old stream has been destroyed: nothing of ours can be pending on it
-    }
+    // a plan with split rows owns their partial-sum workspace (and, in the in-launch form, their arrival counters): plan.h, LaunchGuard
+    const LaunchGuard guard(p, s);
+    if (guard.begin() != FLEX_OK) return FLEX_ERR_INVALID;
     rc = launch_spmm(plan_view(p, fused, nullptr), p->lanes_per_nz, p->off32, vec4, dB, dC, s, p->unroll);
     if (rc == FLEX_OK && !fused) rc = launch_fixup(p->d_partial.get(), p->d_split.get(), p->n_split, p->k, p->ldc, dC, s);
     // the dense tiles' share, added to the rows the kernels above have written
     if (rc == FLEX_OK && p->n_tiles) rc = launch_tiles(tile_view(p), p->off32, dB, dC, p->k, p->ldb, p->ldc, s);
     // the hot blocks' share (the nonzeros with reuse on chip: B rows staged in LDS), added to the rows the flat kernel has written
     if (rc == FLEX_OK && p->bk_blocks) rc = launch_blocks(block_view(p), dB, dC, s, vec4);  // unaligned operands: the generic hot kernel
-    if (rc == FLEX_OK && guard) {
-        p->last_stream = s;
-        p->launched = true;
-    }
+    if (rc == FLEX_OK) guard.done();
     return rc;
 }
 
@@ -394,7 +395,7 @@ int flex_plan_get_info(const flex_plan *p, flex_plan_info *o) {
     if (!p || !o) return FLEX_ERR_INVALID;
     o->m = p->m;
     o->n = p->n;
-    o->k = p->k;
+    o->k = p->k * p->elems_per_word();  // elements, also on a bf16 plan
     o->device = p->device;
     o->nnz = p->nnz;
     o->n_tasks = p->n_tasks;
@@ -453,6 +454,8 @@ int flex_plan_attention_info(const flex_plan *p, flex_attention_info *o) {
     return FLEX_OK;
 }
 
+int flex_plan_is_bf16(const flex_plan *p) { return !p ? FLEX_ERR_INVALID : p->bf16 ? 1 : 0; }
+
 int flex_plan_get_tuning(const flex_plan *p, flex_plan_tuning *o) {
     if (!p || !o) return FLEX_ERR_INVALID;
     *o = p->tuning;
@@ -473,6 +476,7 @@ int flex_plan_get_stats(const flex_plan *p, flex_plan_stats *o) {
 
 int flex_plan_kernel_info(const flex_plan *p, flex_kernel_info *o) {
     if (!p || !o) return FLEX_ERR_INVALID;
+    if (p->bf16) return FLEX_ERR_UNSUPPORTED;  // the bf16 kernels' registers: DESIGN.md 3.16
     const DeviceScope on(p->device);
     FLEX_HIP_TRY(on.error());
     hipFuncAttributes a{};

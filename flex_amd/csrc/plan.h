@@ -82,6 +82,11 @@ class DeviceScope {
 struct flex_plan {
     int32_t m = 0, n = 0, k = 0, device = 0;
     int32_t ldb = 0, ldc = 0;  // row strides of B and C in floats (== k unless flex_plan_create_ld)
+    // FLEX_PLAN_BF16: B and C are flex_bf16 and k, ldb and ldc above are in 4-byte WORDS (two elements each): the planner, the record
+    // offsets, the chunk table and PlanView are those of the fp32 plan of that width.  What counts fp32 VALUES instead -- the partial-sum
+    // workspace, the multiply-add estimate, what flex_plan_get_info reports -- multiplies by elems_per_word().
+    bool bf16 = false;
+    int elems_per_word() const { return bf16 ? 2 : 1; }
     int64_t nnz = 0;
     int lanes_per_nz = 0;
     bool off32 = false;
@@ -220,6 +225,41 @@ inline BlockView block_view(const flex_plan *p) {
 inline TileView tile_view(const flex_plan *p) {
     return TileView{p->d_tile_a.get(), p->d_tile_boff.get(), p->d_tile_mask.get(), p->d_rt_ptr.get(), p->d_rt_rows.get(), p->n_row_tiles};
 }
+// The in-flight guard of a plan that owns a split-row workspace, shared by flex_spmm and flex_spmm_bf16.  Two launches of such a plan
+// must not overlap.  Launches on ONE stream are ordered by the stream; a launch on ANOTHER stream while the stream of the latest one
+// still has work pending is refused instead of silently corrupting those rows.  The check is a stream query at the moment the stream
+// changes -- nothing is added to the launch path of a plan that stays on its stream (an event per launch cost the Flickr-size launches
+// 2-4 us of device time each).  It is conservative: unrelated work queued behind the plan's launch on the old stream also counts as
+// pending.  A launch being captured into a graph is neither checked nor remembered.
+//   begin(): FLEX_ERR_INVALID = refuse, enqueue nothing;  done(): the launch went out, remember its stream.
+class LaunchGuard {
+  public:
+    LaunchGuard(flex_plan *p, hipStream_t s) : p_(p), s_(s), on_(p->n_partials > 0) {
+        if (!on_) return;
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cap) != hipSuccess) (void)hipGetLastError();
+        if (cap != hipStreamCaptureStatusNone) on_ = false;
+    }
+    int begin() const {
+        if (on_ && p_->launched && s_ != p_->last_stream) {
+            const hipError_t q = hipStreamQuery(p_->last_stream);
+            if (q == hipErrorNotReady) return FLEX_ERR_INVALID;
+            if (q != hipSuccess) (void)hipGetLastError();  // e.g. the old stream has been destroyed: nothing of ours can be pending on it
+        }
+        return FLEX_OK;
+    }
+    void done() const {
+        if (!on_) return;
+        p_->last_stream = s_;
+        p_->launched = true;
+    }
+
+  private:
+    flex_plan *p_;
+    hipStream_t s_;
+    bool on_;
+};
+
 // float4 path: k and both strides multiples of 4, both base addresses 16-byte aligned
 inline bool operands_vec4(const flex_plan *p, const float *dB, const float *dC) {
     return (p->k % 4 == 0) && (p->ldb % 4 == 0) && (p->ldc % 4 == 0) &&

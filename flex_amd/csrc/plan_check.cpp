@@ -164,7 +164,7 @@ int flex_plan_read_records(const flex_plan *p, uint32_t *out, int64_t records) t
 }
 
 int flex_plan_measure_imbalance(flex_plan *p, const float *dB, float *dC, flex_stream_t stream, flex_imbalance *out) try {
-    if (!p || !out || !dC || (!dB && p->nnz > 0)) return FLEX_ERR_INVALID;
+    if (!p || p->bf16 || !out || !dC || (!dB && p->nnz > 0)) return FLEX_ERR_INVALID;  // no stamped twin of the bf16 kernel
     *out = flex_imbalance{};
     if (p->m == 0 || p->n_slots == 0) return FLEX_OK;
     if (!operands_vec4(p, dB, dC) || p->bk_blocks) return FLEX_ERR_UNSUPPORTED;  // the stamped twin exists for the vector kernel only (not for row blocks)

@@ -30,6 +30,7 @@ extern "C" {
                               the equally additive flex_attention_heads and flex_attention_heads_backward (two new calls, no flag, no struct),
                               the equally additive flex_gat_attention and flex_gat_attention_backward (the same again),
                               the equally additive flex_bf16, flex_attention_bf16 and flex_attention_bf16_backward (a typedef and two new calls, no flag, no struct),
+                              the equally additive FLEX_PLAN_BF16, flex_spmm_bf16 and flex_plan_is_bf16 (a new flag and two new calls, no struct),
                               and the retired flex_plan_tuning.block_ablate, which keeps its place as block_ablate_retired and must be zero.
                               3: plan-time knobs leave the environment for the struct flex_plan_tuning, flex_plan_desc.tuning, flex_plan_get_tuning,
                               flex_order_cluster_ex, flex_set_host_threads; split rows are summed by a second launch by default.
@@ -120,6 +121,17 @@ typedef struct flex_plan flex_plan;
                                        flex_plan_attention_backward_info: hostA's entries sorted by column -- 4 bytes per column, 8 per entry
                                        ({row, entry index}), 16 per work item, 4 per wave group.  Without the flag a plan uploads exactly what
                                        it uploads with FLEX_PLAN_ATTENTION alone */
+#define FLEX_PLAN_BF16 0x100000u /* B and C are flex_bf16, the upper 16 bits of an IEEE float, and sums are fp32: the plan runs flex_spmm_bf16
+                                       below and nothing else.  k, ldb and ldc stay in ELEMENTS and must be multiples of 8
+                                       (FLEX_ERR_UNSUPPORTED otherwise): a bf16 row of k elements is, byte for byte, an fp32 row of k / 2 words,
+                                       and the plan is the fp32 plan of that word width (lanes_per_nz, 32-bit offsets while n x ldb x 2 bytes
+                                       <= 4 GiB, records, chunks, bundles, split rows; flex_plan_info keeps reporting k in elements).  Every
+                                       nonzero stays on the flat record stream: tuning.mfma and tuning.blocks are forced to 2, split rows are
+                                       summed by the second launch (tuning.split_rows = 2), and an explicit 1 in any of the three, or
+                                       tuning.two_d = 1, is FLEX_ERR_UNSUPPORTED, as is the flag together with FLEX_PLAN_MUTABLE_VALUES,
+                                       FLEX_PLAN_ATTENTION or FLEX_PLAN_AUTOTUNE.  Orders, row bundles, packed records, far_first, tile_group,
+                                       FLEX_PLAN_TRANSPOSE, FLEX_PLAN_ROW_RANGE, maps, FLEX_PLAN_STATS and FLEX_PLAN_XCD_INTERLEAVE work as on
+                                       the fp32 plan of the word width.  The partial sums of split rows are fp32: n_partials x k floats */
 
 /* ≙ Mat::Mat + csr2_DiagTiling + alpha_transfer (mat.cu:7-31, 680-942, 268-293):
  * builds the row-panel plan for `hostA` and uploads it to `device`.  The reference's
@@ -263,6 +275,22 @@ int flex_set_host_threads(int n);
  * nonzero subnormals of at most p units of 2^-149 each, p = the padding records its task needs (< 64 / lanes_per_nz, or < bundle_len
  * in a bundle), may give NaN where C64 is +-inf (its padding carries value 0).  Subnormal inputs and results are kept, not flushed. */
 int flex_spmm(flex_plan *plan, const float *dB, float *dC, flex_stream_t stream);
+
+typedef uint16_t flex_bf16; /* the upper 16 bits of an IEEE float */
+/* flex_spmm on bf16 operands (FLEX_PLAN_BF16 plans only; FLEX_ERR_INVALID on any other plan, as flex_spmm, flex_plan_measure_imbalance
+ * and the flex_axw calls are on a bf16 plan; nothing is enqueued).  dB: n x k row-major device flex_bf16, row stride ldb elements;
+ * dC: m x k row-major device flex_bf16, row stride ldc elements, columns [0, k) of every row fully overwritten.  Both must be 16-byte aligned
+ * (FLEX_ERR_UNSUPPORTED otherwise, C untouched): only the vector form is built.  Asynchronous, no allocation, no host sync, not
+ * re-entrant per plan and guarded exactly as flex_spmm is.  Two launches: the row kernel, then the sum of the split rows' pieces.
+ * Definition: read every element of B as the fp32 number it is; with x32 = what flex_spmm's contract allows for that fp32 input
+ * (fp32 products and sums in the plan's order, pieces of a split row added in fp32), C = rn_bf16(x32): ONE rounding to bf16, to
+ * nearest even, at the store; a NaN stays a quiet NaN, +-inf stays, what rounds past the largest finite bf16 becomes +-inf.  A row
+ * without nonzeros is +0.  Accuracy (tests/spmm_bf16_ref.py): with C64 and bound32 = gamma(n_r) S + n_r 2^-149 as for flex_spmm on
+ * the widened B, every entry whose C64 is finite satisfies |C - C64| <= bound32 + 2^-8 (|C64| + bound32) + 2^-134, and is finite
+ * unless |C64| + bound32 reaches the largest finite bf16; every other entry has C64's class exactly, under flex_spmm's residual. */
+int flex_spmm_bf16(flex_plan *plan, const flex_bf16 *dB, flex_bf16 *dC, flex_stream_t stream);
+/* 1 for a FLEX_PLAN_BF16 plan, 0 for any other, FLEX_ERR_INVALID (negative) for NULL */
+int flex_plan_is_bf16(const flex_plan *plan);
 
 /* Learnable edge values (FLEX_PLAN_MUTABLE_VALUES plans only; FLEX_ERR_INVALID on any other plan).  No reference counterpart.
  *
@@ -525,7 +553,6 @@ int flex_attention_heads_backward(const flex_plan *plan, int heads, const float 
  * within bound32 (the fp32 call's bound for that element) of the float64 value x64, satisfies
  *     |y - x64| <= bound32 + 2^-8 (|x64| + bound32) + 2^-134
  * 2^-8 being the unit roundoff of bf16 (8 significant bits) and 2^-134 half its smallest subnormal. */
-typedef uint16_t flex_bf16; /* the upper 16 bits of an IEEE float */
 int flex_attention_bf16(const flex_plan *plan, int heads, const flex_bf16 *dQ, const flex_bf16 *dK, const flex_bf16 *dV, float scale,
                         flex_bf16 *dOut, float *dP, flex_stream_t stream);
 int flex_attention_bf16_backward(const flex_plan *plan, int heads, const flex_bf16 *dQ, const flex_bf16 *dK, const flex_bf16 *dV, const float *dP,
