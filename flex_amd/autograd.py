@@ -8,8 +8,9 @@ scores by flex_sddmm as a forward op, their softmax over each row of A (flex_edg
 two (flex_attention_backward) instead of the chain of eight calls; with both, attention(..., heads=H) runs H heads in the same three
 launches (flex_attention_heads, flex_attention_heads_backward), on torch.bfloat16 Q, K and V as well (flex_attention_bf16,
 flex_attention_bf16_backward: bf16 rows, float32 accumulation), and gat_attention(el, er, V) runs GAT's additive score
-LeakyReLU(el[row] + er[col]) per head in the same three launches (flex_gat_attention, flex_gat_attention_backward).  torch is imported
-lazily, as in binding.py."""
+LeakyReLU(el[row] + er[col]) per head in the same three launches (flex_gat_attention, flex_gat_attention_backward).
+attention(..., bias=b) adds a learned term per entry and head to the scaled score before the softmax, in float32 or bfloat16 rows, still
+in three launches (flex_attention_bias, flex_attention_bf16_bias and their backward calls).  torch is imported lazily, as in binding.py."""
 from __future__ import annotations
 
 from . import binding
@@ -208,14 +209,38 @@ def _function():
             grads = ctx.op.plan.attention_bf16_backward(Q, K, V, p, grad_out.contiguous(), ctx.scale, heads=ctx.heads, want=tuple(ctx.needs_input_grad[:3]))
             return (*grads, None, None, None)
 
-    return _SpMM, _AxwLayer, _SpMMValues, _Sddmm, _EdgeSoftmax, _FusedAttention, _FusedAttentionHeads, _FusedGatAttention, _FusedAttentionBf16
+    class _FusedAttentionBias(torch.autograd.Function):
+        """_FusedAttentionHeads / _FusedAttentionBf16 with bias [nnz, heads] (float32) added to the scaled score of every entry and head
+        before the softmax, differentiable in Q, K, V and the bias: flex_attention_bias or flex_attention_bf16_bias (by the dtype of Q)
+        in one launch, alpha [nnz, heads] kept only when a gradient is needed; backward: the one call of two launches for the gradients
+        that are needed, which never reads the bias.  Only on an operator made with fused_attention=True and fused_backward=True."""
+
+        @staticmethod
+        def forward(ctx, Q, K, V, bias, op, scale, heads):
+            Q, K, V, bias = Q.contiguous(), K.contiguous(), V.contiguous(), bias.detach().contiguous()
+            p = torch.zeros((op.nnz, heads), dtype=torch.float32, device=Q.device) if any(ctx.needs_input_grad[:4]) else None
+            run = op.plan.attention_bf16_bias if Q.dtype == torch.bfloat16 else op.plan.attention_bias
+            out = run(Q, K, V, bias, scale, heads=heads, p=p)
+            ctx.op, ctx.scale, ctx.heads, ctx.bias_shape = op, scale, heads, bias.shape
+            ctx.save_for_backward(Q, K, V, p)
+            return out
+
+        @staticmethod
+        def backward(ctx, grad_out):
+            Q, K, V, p = ctx.saved_tensors
+            run = ctx.op.plan.attention_bf16_bias_backward if Q.dtype == torch.bfloat16 else ctx.op.plan.attention_bias_backward
+            gQ, gK, gV, gB = run(Q, K, V, p, grad_out.contiguous(), ctx.scale, heads=ctx.heads, want=tuple(ctx.needs_input_grad[:4]))
+            return gQ, gK, gV, None if gB is None else gB.reshape(ctx.bias_shape), None, None, None
+
+    return (_SpMM, _AxwLayer, _SpMMValues, _Sddmm, _EdgeSoftmax, _FusedAttention, _FusedAttentionHeads, _FusedGatAttention, _FusedAttentionBf16,
+            _FusedAttentionBias)
 
 
 _cache = None
 
 
 def functions():
-    """(_SpMM, _AxwLayer, _SpMMValues, _Sddmm, _EdgeSoftmax, _FusedAttention, _FusedAttentionHeads, _FusedGatAttention, _FusedAttentionBf16): the autograd Functions, built at first use (torch is imported then)."""
+    """(_SpMM, _AxwLayer, _SpMMValues, _Sddmm, _EdgeSoftmax, _FusedAttention, _FusedAttentionHeads, _FusedGatAttention, _FusedAttentionBf16, _FusedAttentionBias): the autograd Functions, built at first use (torch is imported then)."""
     global _cache
     if _cache is None:
         _cache = _function()
@@ -296,13 +321,17 @@ class SparseOperator:
         assert s.numel() == self.nnz, (s.numel(), self.nnz)
         return functions()[4].apply(s, self, float(scale))
 
-    def attention(self, Q, K, V, scale: float | None = None, heads: int = 1):
+    def attention(self, Q, K, V, scale: float | None = None, heads: int = 1, bias=None):
         """Out [m, k] = A(alpha) V with alpha = softmax over each row of A of scale * <Q[row], K[col]>; scale defaults to
         (k / heads) ** -0.5.  Differentiable in Q [m, k], K [n, k] and V [n, k].  heads > 1: head h is columns [h k / heads, (h + 1) k / heads)
         of Q, K, V and Out and has its own scores and softmax, all heads in one forward launch and two backward launches
         (flex_attention_heads); needs fused_attention=True and fused_backward=True.  Q, K and V all torch.bfloat16, for any heads: the same
         three launches on bf16 rows with float32 scores, softmax and sums (flex_attention_bf16); Out and the gradients are bfloat16; needs
-        both fused flags as well, and k / heads a power of two in 4 .. 256.  Mixed dtypes raise TypeError."""
+        both fused flags as well, and k / heads a power of two in 4 .. 256.  Mixed dtypes raise TypeError.
+        bias (float32 [nnz, heads] in a's CSR order; [nnz] with heads == 1): alpha = softmax of scale * <Q[row], K[col]> + bias[e, h], the
+        edge term of a graph transformer, -inf masking an entry for a head; differentiable in the bias as well, in the same three launches
+        (flex_attention_bias, flex_attention_bf16_bias) for Q, K, V all float32 or all bfloat16; needs both fused flags and, for any
+        heads, k / heads a power of two in 4 .. 256.  bias=None takes every path above exactly as without the argument."""
         import torch
         self._needs_learn_values("attention")
         if heads < 1:
@@ -310,6 +339,15 @@ class SparseOperator:
         if scale is None:
             scale = (self.k / heads) ** -0.5
         dtypes = {t.dtype for t in (Q, K, V)}
+        if bias is not None:
+            if not (self.fused_attention and self.fused_backward):
+                raise NotImplementedError("attention(..., bias=...) needs SparseOperator(..., fused_attention=True, fused_backward=True): "
+                                          "only the fused forward and backward take a per-edge bias")
+            if dtypes not in ({torch.float32}, {torch.bfloat16}):
+                raise TypeError(f"attention takes Q, K and V of one dtype, all float32 or all bfloat16, not {[str(t.dtype) for t in (Q, K, V)]}")
+            if bias.dtype != torch.float32 or tuple(bias.shape) not in ((self.nnz, heads),) + (((self.nnz,),) if heads == 1 else ()):
+                raise TypeError(f"attention takes a float32 bias of shape [nnz, heads] = [{self.nnz}, {heads}], not {bias.dtype} {tuple(bias.shape)}")
+            return functions()[9].apply(Q, K, V, bias, self, float(scale), int(heads))
         if torch.bfloat16 in dtypes:
             if len(dtypes) > 1:
                 raise TypeError(f"attention takes Q, K and V of one dtype, all float32 or all bfloat16, not {[str(t.dtype) for t in (Q, K, V)]}")

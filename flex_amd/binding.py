@@ -166,6 +166,7 @@ SYMBOLS = [
     "flex_attention_backward", "flex_plan_attention_backward_info", "flex_attention_heads", "flex_attention_heads_backward",
     "flex_gat_attention", "flex_gat_attention_backward", "flex_plan_record_info", "flex_plan_read_records",
     "flex_attention_bf16", "flex_attention_bf16_backward", "flex_spmm_bf16", "flex_plan_is_bf16",
+    "flex_attention_bias", "flex_attention_bias_backward", "flex_attention_bf16_bias", "flex_attention_bf16_bias_backward",
 ]
 
 _lib = None
@@ -268,6 +269,10 @@ def _values_fn(name: str):
                       "flex_attention_heads_backward": [vp, i32, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp],
                       "flex_attention_bf16": [vp, i32, vp, vp, vp, fl, vp, vp, vp],
                       "flex_attention_bf16_backward": [vp, i32, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp],
+                      "flex_attention_bias": [vp, i32, vp, vp, vp, vp, fl, vp, vp, vp],
+                      "flex_attention_bias_backward": [vp, i32, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp, vp],
+                      "flex_attention_bf16_bias": [vp, i32, vp, vp, vp, vp, fl, vp, vp, vp],
+                      "flex_attention_bf16_bias_backward": [vp, i32, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp, vp],
                       "flex_spmm_bf16": [vp, vp, vp, vp],
                       "flex_gat_attention": [vp, i32, vp, vp, vp, fl, vp, vp, vp],
                       "flex_gat_attention_backward": [vp, i32, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp]}[name]
@@ -806,6 +811,101 @@ class Plan:
                                          *(None if t is None else t.data_ptr() for t in outs), work.data_ptr(),
                                          torch.cuda.current_stream(Q.device).cuda_stream, heads=heads)
         return tuple(outs)
+
+    def attention_bias_ptr(self, dQ_ptr: int, dK_ptr: int, dV_ptr: int, dBias_ptr: int, scale: float, dOut_ptr: int, dP_ptr: int | None = None,
+                           stream: int = 0, heads: int = 1):
+        """flex_attention_bias: fp32 rows; dBias and dP (optional) are nnz x H floats, entry-major."""
+        _check(_values_fn("flex_attention_bias")(self._h, heads, dQ_ptr, dK_ptr, dV_ptr, dBias_ptr, scale, dOut_ptr, dP_ptr, stream), "flex_attention_bias")
+
+    def attention_bf16_bias_ptr(self, dQ_ptr: int, dK_ptr: int, dV_ptr: int, dBias_ptr: int, scale: float, dOut_ptr: int, dP_ptr: int | None = None,
+                                stream: int = 0, heads: int = 1):
+        """flex_attention_bf16_bias: Q, K, V and Out are bf16 rows; dBias and dP (optional) are nnz x H floats, entry-major."""
+        _check(_values_fn("flex_attention_bf16_bias")(self._h, heads, dQ_ptr, dK_ptr, dV_ptr, dBias_ptr, scale, dOut_ptr, dP_ptr, stream),
+               "flex_attention_bf16_bias")
+
+    def attention_bias_backward_ptr(self, dQ_ptr: int, dK_ptr: int, dV_ptr: int, dP_ptr: int, dGradOut_ptr: int, scale: float, dGradQ_ptr: int | None,
+                                    dGradK_ptr: int | None, dGradV_ptr: int | None, dGradBias_ptr: int | None, dWork_ptr: int, stream: int = 0,
+                                    heads: int = 1):
+        """flex_attention_bias_backward: fp32 rows; dP, dGradBias and dWork are nnz x H floats, entry-major."""
+        _check(_values_fn("flex_attention_bias_backward")(self._h, heads, dQ_ptr, dK_ptr, dV_ptr, dP_ptr, dGradOut_ptr, scale, dGradQ_ptr, dGradK_ptr,
+                                                          dGradV_ptr, dGradBias_ptr, dWork_ptr, stream), "flex_attention_bias_backward")
+
+    def attention_bf16_bias_backward_ptr(self, dQ_ptr: int, dK_ptr: int, dV_ptr: int, dP_ptr: int, dGradOut_ptr: int, scale: float,
+                                         dGradQ_ptr: int | None, dGradK_ptr: int | None, dGradV_ptr: int | None, dGradBias_ptr: int | None,
+                                         dWork_ptr: int, stream: int = 0, heads: int = 1):
+        """flex_attention_bf16_bias_backward: the row operands and gQ, gK, gV are bf16 rows; dP, dGradBias and dWork nnz x H floats."""
+        _check(_values_fn("flex_attention_bf16_bias_backward")(self._h, heads, dQ_ptr, dK_ptr, dV_ptr, dP_ptr, dGradOut_ptr, scale, dGradQ_ptr,
+                                                               dGradK_ptr, dGradV_ptr, dGradBias_ptr, dWork_ptr, stream),
+               "flex_attention_bf16_bias_backward")
+
+    def _attention_bias(self, dtype, run, Q, K, V, bias, scale, heads, out, p):
+        import torch
+        i = self.info()
+        for t, rows in ((Q, i["m"]), (K, i["n"]), (V, i["n"])):
+            assert t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == (rows, i["k"]), f"{dtype} cuda [rows, k]"
+        if heads == 1 and bias.dim() == 1:
+            bias = bias.unsqueeze(1)
+        self._bf16_edge_arrays(heads, bias)
+        if out is None:  # every row is written, except by a plan without entries, which launches nothing
+            out = (torch.empty if i["nnz"] else torch.zeros)((i["m"], i["k"]), dtype=dtype, device=Q.device)
+        assert out.is_cuda and out.dtype == dtype and out.is_contiguous() and tuple(out.shape) == (i["m"], i["k"])
+        if p is not None:
+            self._bf16_edge_arrays(heads, p)
+        run(Q.data_ptr(), K.data_ptr(), V.data_ptr(), bias.data_ptr(), scale, out.data_ptr(), None if p is None else p.data_ptr(),
+            torch.cuda.current_stream(Q.device).cuda_stream, heads=heads)
+        return out
+
+    def _attention_bias_backward(self, dtype, run, Q, K, V, p, grad_out, scale, heads, grads, work, want):
+        import torch
+        i = self.info()
+        for t, rows in ((Q, i["m"]), (K, i["n"]), (V, i["n"]), (grad_out, i["m"])):
+            assert t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == (rows, i["k"]), f"{dtype} cuda [rows, k]"
+        if work is None:
+            work = torch.empty((self.src_nnz, heads), dtype=torch.float32, device=Q.device)
+        self._bf16_edge_arrays(heads, p, work)
+        shapes = ((i["m"], i["k"]), (i["n"], i["k"]), (i["n"], i["k"]), (self.src_nnz, heads))
+        outs = []
+        for wanted, t, shape, dt in zip(want, grads, shapes, (dtype, dtype, dtype, torch.float32)):
+            if wanted and t is None:  # every element is written, except by a plan without entries, which launches nothing
+                t = (torch.empty if i["nnz"] else torch.zeros)(shape, dtype=dt, device=Q.device)
+            if wanted:
+                assert t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape
+            outs.append(t if wanted else None)
+        run(Q.data_ptr(), K.data_ptr(), V.data_ptr(), p.data_ptr(), grad_out.data_ptr(), scale, *(None if t is None else t.data_ptr() for t in outs),
+            work.data_ptr(), torch.cuda.current_stream(Q.device).cuda_stream, heads=heads)
+        return tuple(outs)
+
+    def attention_bias(self, Q, K, V, bias, scale: float, heads: int = 1, out=None, p=None):
+        """flex_attention_bias: attention(..., heads=heads) with bias [a.nnz, heads] (float32 cuda, a's CSR order; [a.nnz] is taken as
+        [a.nnz, 1] when heads == 1) added to the scaled score of every entry and head before the softmax; -inf masks an entry for a head.
+        Q [m, k], K, V [n, k] float32; p (optional): a float32 cuda tensor [a.nnz, heads] that receives alpha.  heads = 1 runs here too:
+        k / heads is a power of two in 4 .. 256 for every heads."""
+        import torch
+        return self._attention_bias(torch.float32, self.attention_bias_ptr, Q, K, V, bias, scale, heads, out, p)
+
+    def attention_bf16_bias(self, Q, K, V, bias, scale: float, heads: int = 1, out=None, p=None):
+        """flex_attention_bf16_bias: attention_bias() on torch.bfloat16 Q, K, V; out is bfloat16, rounded once at its store; bias and p
+        stay float32 and are not rounded."""
+        import torch
+        return self._attention_bias(torch.bfloat16, self.attention_bf16_bias_ptr, Q, K, V, bias, scale, heads, out, p)
+
+    def attention_bias_backward(self, Q, K, V, p, grad_out, scale: float, heads: int = 1, grad_q=None, grad_k=None, grad_v=None, grad_bias=None,
+                                work=None, want=(True, True, True, True)):
+        """flex_attention_bias_backward: (gQ [m, k], gK [n, k], gV [n, k], gBias [a.nnz, heads]) of attention_bias()'s out from its p
+        [a.nnz, heads] and grad_out [m, k], in two launches; it does not take the bias.  An output that `want` does not ask for is None
+        and is not computed.  work (optional): a float32 cuda tensor [a.nnz, heads], neither p nor grad_bias, that receives the gradient
+        in the scores whenever gQ, gK or gBias is wanted."""
+        import torch
+        return self._attention_bias_backward(torch.float32, self.attention_bias_backward_ptr, Q, K, V, p, grad_out, scale, heads,
+                                             (grad_q, grad_k, grad_v, grad_bias), work, want)
+
+    def attention_bf16_bias_backward(self, Q, K, V, p, grad_out, scale: float, heads: int = 1, grad_q=None, grad_k=None, grad_v=None,
+                                     grad_bias=None, work=None, want=(True, True, True, True)):
+        """flex_attention_bf16_bias_backward: attention_bias_backward() on torch.bfloat16 Q, K, V and grad_out; gQ, gK and gV are bfloat16,
+        p, gBias and work float32."""
+        import torch
+        return self._attention_bias_backward(torch.bfloat16, self.attention_bf16_bias_backward_ptr, Q, K, V, p, grad_out, scale, heads,
+                                             (grad_q, grad_k, grad_v, grad_bias), work, want)
 
     def gat_attention_ptr(self, heads: int, dEl_ptr: int, dEr_ptr: int, dV_ptr: int, slope: float, dOut_ptr: int, dP_ptr: int | None = None,
                           stream: int = 0):

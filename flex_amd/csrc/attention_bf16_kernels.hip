@@ -63,6 +63,15 @@ struct Bf16Operands {
     float *Work;
 };
 
+void launch_columns_backward(const flex_plan *p, const AttentionPick &pick, const HeadSplit &hs, const flex_bf16 *Q, const flex_bf16 *G, const float *P,
+                             const float *DS, flex_bf16 *GK, flex_bf16 *GV, hipStream_t s) {
+    const ColumnView cv = column_view(p);
+    const dim3 cgrid = launch_grid(cv), block(64 * kWavesPerBlock);
+    dispatch(pick, [&](auto W, auto NS) {
+        hipLaunchKernelGGL((attention_bf16_columns_backward<W(), NS()>), cgrid, block, 0, s, cv, hs, Q, G, P, DS, GK, GV);
+    });
+}
+
 }  // namespace attention
 }  // namespace flex
 

@@ -1,6 +1,8 @@
 // attention_heads_device.h -- the sweeps of the per-head dot-product attention, over the element type E of the row operands (Q, K, V,
 // Out, g, gQ, gK, gV): float in attention_heads_kernels.hip (flex_attention_heads, flex_attention_heads_backward), flex_bf16 in
-// attention_bf16_kernels.hip (flex_attention_bf16, flex_attention_bf16_backward).  E enters through load_cols, store_cols and write_row
+// attention_bf16_kernels.hip (flex_attention_bf16, flex_attention_bf16_backward), and both, with the row sweeps' compile-time BIAS
+// switch on, in attention_bias_kernels.hip (flex_attention_bias, flex_attention_bf16_bias and their backward calls: a per-edge, per-head
+// term in the score and its gradient; off, the sweeps are what they were).  E enters through load_cols, store_cols and write_row
 // (attention_device.h) and nowhere else: a row is widened to fp32 as it is loaded and narrowed at its one store, so the two objects run
 // the same walk and the same fp32 expressions.  The edge arrays (dP, dWork) and LDS are fp32 for every E.
 //
@@ -32,11 +34,13 @@ namespace attention {
 
 // ---- forward
 
-// attention_kernels.hip, sweep, with the state per slab
-template <int W, int NS, class E>
+// attention_kernels.hip, sweep, with the state per slab.  BIAS (attention_bias_kernels.hip): the score of a valid entry becomes
+// t = fma(scale, s, Bias[e H + head]) -- every lane of a head loads its head's element, one address for the HW lanes -- and `sm`, the
+// scale of everything after the score, is 1
+template <int W, int NS, bool BIAS, class E>
 __device__ __forceinline__ void sweep_heads(const View &v, const HeadSplit &hs, const HeadLane &hl, const float4 (&q)[NS], const E *__restrict__ K,
-                                            const E *__restrict__ V, float scale, float *__restrict__ P, const Place &pl, uint32_t lane, uint32_t li,
-                                            State<1> (&st)[NS]) {
+                                            const E *__restrict__ V, const float *__restrict__ Bias, float scale, float sm, float *__restrict__ P,
+                                            const Place &pl, uint32_t lane, uint32_t li, State<1> (&st)[NS]) {
     const int slot_lane0 = static_cast<int>(lane - li);
     // four slabs: the V rows of a slab are gathered when its scores are done, not with the K rows -- the per-slab state would otherwise
     // take the kernel past 256 registers, to one wave per SIMD
@@ -71,6 +75,13 @@ __device__ __forceinline__ void sweep_heads(const View &v, const HeadSplit &hs, 
             float sc[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) sc[u] = head_total<W>(dot_cols<true>(0.f, q[s], kv[u][s], c, v.k), hl.hw);
+            const uint32_t head = (li + static_cast<uint32_t>(W * s)) >> hs.lg;
+            if constexpr (BIAS) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    if (valid[u] && c < v.k) sc[u] = __builtin_fmaf(scale, sc[u], Bias[(pl.first + j0 + u) * static_cast<uint64_t>(hs.H) + head]);
+                }
+            }
             float pm = -INFINITY;
 #pragma unroll
             for (int u = 0; u < U; ++u) {
@@ -78,7 +89,6 @@ __device__ __forceinline__ void sweep_heads(const View &v, const HeadSplit &hs, 
                 pm = fmaxf(pm, max_key(sc[u]));
             }
             if (P && c < v.k) {
-                const uint32_t head = (li + static_cast<uint32_t>(W * s)) >> hs.lg;
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     if (valid[u] && hl.writes(u)) P[(pl.first + j0 + u) * static_cast<uint64_t>(hs.H) + head] = sc[u];
@@ -86,7 +96,7 @@ __device__ __forceinline__ void sweep_heads(const View &v, const HeadSplit &hs, 
             }
             State<1> &x = st[s];
             if (pm > x.m) {
-                const float f = carry(x.m, pm, scale);
+                const float f = carry(x.m, pm, sm);
                 x.l *= f;
                 x.acc[0] = scaled(x.acc[0], f);
                 x.m = pm;
@@ -95,7 +105,7 @@ __device__ __forceinline__ void sweep_heads(const View &v, const HeadSplit &hs, 
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     if (valid[u]) {
-                        const float tm = term(sc[u], x.m, scale);
+                        const float tm = term(sc[u], x.m, sm);
                         x.l += tm;
                         axpy(x.acc[0], tm, vv[u][s]);
                     }
@@ -105,10 +115,11 @@ __device__ __forceinline__ void sweep_heads(const View &v, const HeadSplit &hs, 
     }
 }
 
-template <int W, int NS, class E>
+template <int W, int NS, bool BIAS, class E>
 __device__ __forceinline__ void run_item_heads(const View &v, const HeadSplit &hs, const uint4 &it, int kind, const E *__restrict__ Q,
-                                               const E *__restrict__ K, const E *__restrict__ V, float scale, E *__restrict__ Out,
-                                               float *__restrict__ P, uint32_t lane, uint32_t w, HeadsShared<W, NS> &sh) {
+                                               const E *__restrict__ K, const E *__restrict__ V, const float *__restrict__ Bias, float scale,
+                                               E *__restrict__ Out, float *__restrict__ P, uint32_t lane, uint32_t w, HeadsShared<W, NS> &sh) {
+    const float sm = BIAS ? 1.f : scale;  // the scale of the softmax: with a bias it is already in the stored score
     const uint32_t slot = lane / W, li = lane % W;
     const HeadLane hl(hs, li);
     const Place pl = place_of<W>(v.rowptr, it, kind, slot, w);
@@ -122,8 +133,8 @@ __device__ __forceinline__ void run_item_heads(const View &v, const HeadSplit &h
         st[s].l = 0.f;
         st[s].acc[0] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    sweep_heads<W, NS>(v, hs, hl, q, K, V, scale, P, pl, lane, li, st);
-    if (kind != kSlotLine) merge_slots_heads<W, NS>(st, lane, scale);
+    sweep_heads<W, NS, BIAS>(v, hs, hl, q, K, V, Bias, scale, sm, P, pl, lane, li, st);
+    if (kind != kSlotLine) merge_slots_heads<W, NS>(st, lane, sm);
     bool writer = kind == kSlotLine ? pl.has_line : slot == 0;
     if (kind == kBlockLine) {
         if (slot == 0) {
@@ -147,7 +158,7 @@ __device__ __forceinline__ void run_item_heads(const View &v, const HeadSplit &h
                 o.m = sh.ml[i][li + W * s].x;
                 o.l = sh.ml[i][li + W * s].y;
                 o.acc[0] = writer ? *reinterpret_cast<const float4 *>(&sh.acc[i][4 * li + 4 * W * s]) : make_float4(0.f, 0.f, 0.f, 0.f);
-                merge(tot, o, scale);
+                merge(tot, o, sm);
             }
             st[s] = tot;
         }
@@ -168,7 +179,7 @@ __device__ __forceinline__ void run_item_heads(const View &v, const HeadSplit &h
                 for (int u = 0; u < U; ++u) {
                     if (j0 + u < pl.len && hl.writes(u)) {
                         const uint64_t e = (pl.first + j0 + u) * static_cast<uint64_t>(hs.H) + head;
-                        P[e] = prob(P[e], st[s].m, st[s].l, scale);
+                        P[e] = prob(P[e], st[s].m, st[s].l, sm);
                     }
                 }
             }
@@ -176,14 +187,15 @@ __device__ __forceinline__ void run_item_heads(const View &v, const HeadSplit &h
     }
 }
 
-// The body of the forward kernel of either element type, which declares `sh`.  Grid: as attention_rows.
-template <int W, int NS, class E>
+// The body of the forward kernel of either element type, which declares `sh`.  Grid: as attention_rows.  BIAS: Bias is nnz x H floats
+// in the layout of P (it is not read otherwise).
+template <int W, int NS, bool BIAS = false, class E>
 __device__ __forceinline__ void walk_rows_heads(const View &v, const HeadSplit &hs, const E *__restrict__ Q, const E *__restrict__ K,
                                                 const E *__restrict__ V, float scale, E *__restrict__ Out, float *__restrict__ P,
-                                                HeadsShared<W, NS> &sh) {
+                                                HeadsShared<W, NS> &sh, const float *__restrict__ Bias = nullptr) {
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
     if (blockIdx.x < v.n_block_rows) {
-        run_item_heads<W, NS>(v, hs, v.item[v.n_wave_items + blockIdx.x], kBlockLine, Q, K, V, scale, Out, P, lane, w, sh);
+        run_item_heads<W, NS, BIAS>(v, hs, v.item[v.n_wave_items + blockIdx.x], kBlockLine, Q, K, V, Bias, scale, Out, P, lane, w, sh);
         return;
     }
     uint32_t wg = blockIdx.x - v.n_block_rows;
@@ -197,7 +209,7 @@ __device__ __forceinline__ void walk_rows_heads(const View &v, const HeadSplit &
     for (uint32_t i = v.grp[grp]; i < i1; ++i) {
         const uint4 it = v.item[i];
         const int kind = (it.w > 1 || it.y <= kAtSlotRow) ? kSlotLine : kWaveLine;  // internal.h, attention_row_class
-        run_item_heads<W, NS>(v, hs, it, kind, Q, K, V, scale, Out, P, lane, w, sh);
+        run_item_heads<W, NS, BIAS>(v, hs, it, kind, Q, K, V, Bias, scale, Out, P, lane, w, sh);
     }
 }
 
@@ -209,11 +221,13 @@ struct HeadsRowShared {
     alignas(16) float acc[kWavesPerBlock][4 * W * NS];
 };
 
-// attention_backward_kernels.hip, run_row, with da, delta and ds per slab
-template <int W, int NS, class E>
+// attention_backward_kernels.hip, run_row, with da, delta and ds per slab.  BIAS (attention_bias_kernels.hip): sweep 2 also stores the
+// gradient in the bias, p (da - delta), into GB where GB is not NULL
+template <int W, int NS, bool BIAS, class E>
 __device__ __forceinline__ void run_row_heads(const View &v, const HeadSplit &hs, const uint4 &it, int kind, const E *__restrict__ K,
                                               const E *__restrict__ V, const float *__restrict__ P, const E *__restrict__ G, float scale,
-                                              E *__restrict__ GQ, float *__restrict__ Work, uint32_t lane, uint32_t w, HeadsRowShared<W, NS> &sh) {
+                                              E *__restrict__ GQ, float *__restrict__ GB, float *__restrict__ Work, uint32_t lane, uint32_t w,
+                                              HeadsRowShared<W, NS> &sh) {
     const uint32_t slot = lane / W, li = lane % W;
     const int slot_lane0 = static_cast<int>(lane - li);
     const HeadLane hl(hs, li);
@@ -289,6 +303,9 @@ __device__ __forceinline__ void run_row_heads(const View &v, const HeadSplit &hs
                     const float d = Work[e] - delta[s];
                     dse[s][u] = (scale * P[e]) * d;
                     Work[e] = dse[s][u];
+                    if constexpr (BIAS) {
+                        if (GB) GB[e] = P[e] * d;
+                    }
                 }
             }
         }
@@ -343,13 +360,13 @@ __device__ __forceinline__ void run_row_heads(const View &v, const HeadSplit &hs
 }
 
 // the body of the row backward kernel of either element type
-template <int W, int NS, class E>
+template <int W, int NS, bool BIAS = false, class E>
 __device__ __forceinline__ void walk_rows_heads_backward(const View &v, const HeadSplit &hs, const E *__restrict__ K, const E *__restrict__ V,
                                                          const float *__restrict__ P, const E *__restrict__ G, float scale, E *__restrict__ GQ,
-                                                         float *__restrict__ Work, HeadsRowShared<W, NS> &sh) {
+                                                         float *__restrict__ Work, HeadsRowShared<W, NS> &sh, float *__restrict__ GB = nullptr) {
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
     if (blockIdx.x < v.n_block_rows) {
-        run_row_heads<W, NS>(v, hs, v.item[v.n_wave_items + blockIdx.x], kBlockLine, K, V, P, G, scale, GQ, Work, lane, w, sh);
+        run_row_heads<W, NS, BIAS>(v, hs, v.item[v.n_wave_items + blockIdx.x], kBlockLine, K, V, P, G, scale, GQ, GB, Work, lane, w, sh);
         return;
     }
     uint32_t wg = blockIdx.x - v.n_block_rows;
@@ -363,7 +380,7 @@ __device__ __forceinline__ void walk_rows_heads_backward(const View &v, const He
     for (uint32_t i = v.grp[grp]; i < i1; ++i) {
         const uint4 it = v.item[i];
         const int kind = (it.w > 1 || it.y <= kAtSlotRow) ? kSlotLine : kWaveLine;
-        run_row_heads<W, NS>(v, hs, it, kind, K, V, P, G, scale, GQ, Work, lane, w, sh);
+        run_row_heads<W, NS, BIAS>(v, hs, it, kind, K, V, P, G, scale, GQ, GB, Work, lane, w, sh);
     }
 }
 

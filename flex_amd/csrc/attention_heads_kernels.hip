@@ -46,6 +46,15 @@ struct HeadsOperands {
     float *GQ, *GK, *GV, *Work;
 };
 
+void launch_columns_backward(const flex_plan *p, const AttentionPick &pick, const HeadSplit &hs, const float *Q, const float *G, const float *P,
+                             const float *DS, float *GK, float *GV, hipStream_t s) {
+    const ColumnView cv = column_view(p);
+    const dim3 cgrid = launch_grid(cv), block(64 * kWavesPerBlock);
+    dispatch(pick, [&](auto W, auto NS) {
+        hipLaunchKernelGGL((attention_heads_columns_backward<W(), NS()>), cgrid, block, 0, s, cv, hs, Q, G, P, DS, GK, GV);
+    });
+}
+
 }  // namespace attention
 }  // namespace flex
 

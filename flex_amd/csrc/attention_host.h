@@ -54,5 +54,13 @@ inline int split_of(int k, int heads, HeadSplit *out) {
     return FLEX_OK;
 }
 
+// The column launch of flex_attention_heads_backward (attention_heads_kernels.hip) and of flex_attention_bf16_backward
+// (attention_bf16_kernels.hip) on an ab_ok plan, for the entry points of another object that share it (attention_bias_kernels.hip): gK
+// and gV (either may be NULL) from p and ds.  The caller has checked the operands and holds the plan's device.
+void launch_columns_backward(const flex_plan *p, const AttentionPick &pick, const HeadSplit &hs, const float *Q, const float *G, const float *P,
+                             const float *DS, float *GK, float *GV, hipStream_t s);
+void launch_columns_backward(const flex_plan *p, const AttentionPick &pick, const HeadSplit &hs, const flex_bf16 *Q, const flex_bf16 *G, const float *P,
+                             const float *DS, flex_bf16 *GK, flex_bf16 *GV, hipStream_t s);
+
 }  // namespace attention
 }  // namespace flex

@@ -31,6 +31,7 @@ extern "C" {
                               the equally additive flex_gat_attention and flex_gat_attention_backward (the same again),
                               the equally additive flex_bf16, flex_attention_bf16 and flex_attention_bf16_backward (a typedef and two new calls, no flag, no struct),
                               the equally additive FLEX_PLAN_BF16, flex_spmm_bf16 and flex_plan_is_bf16 (a new flag and two new calls, no struct),
+                              the equally additive flex_attention_bias, flex_attention_bf16_bias and their backward calls (four new calls, no flag, no struct),
                               and the retired flex_plan_tuning.block_ablate, which keeps its place as block_ablate_retired and must be zero.
                               3: plan-time knobs leave the environment for the struct flex_plan_tuning, flex_plan_desc.tuning, flex_plan_get_tuning,
                               flex_order_cluster_ex, flex_set_host_threads; split rows are summed by a second launch by default.
@@ -558,6 +559,77 @@ int flex_attention_bf16(const flex_plan *plan, int heads, const flex_bf16 *dQ, c
 int flex_attention_bf16_backward(const flex_plan *plan, int heads, const flex_bf16 *dQ, const flex_bf16 *dK, const flex_bf16 *dV, const float *dP,
                                  const flex_bf16 *dGradOut, float scale, flex_bf16 *dGradQ, flex_bf16 *dGradK, flex_bf16 *dGradV, float *dWork,
                                  flex_stream_t stream);
+
+/* Multi-head fused attention with a per-edge bias: flex_attention_heads / flex_attention_bf16 and their backward calls with one learned
+ * term per entry and head added to the score before the softmax -- the edge term of the graph transformers (Graphormer, SAN, GraphGPS,
+ * TransformerConv with edge features), which also mask edges per head with -inf -- in the same ONE forward launch and TWO backward
+ * launches, on the same plans (FLEX_PLAN_ATTENTION; FLEX_PLAN_ATTENTION_BACKWARD for the backward calls; FLEX_ERR_INVALID on any other
+ * plan).  No new plan flag and no new image.  No reference counterpart.  The plans, heads = H, d = k / H, head h on columns
+ * [h d, (h + 1) d) and the layout of dP and dWork are those of flex_attention_heads.  dBias is hostA->nnz x H floats, entry-major, in
+ * hostA's CSR order: (entry e, head h) at e H + h -- the layout of dP, so a contiguous torch tensor [nnz, H] fits; it is fp32 for both
+ * element types and needs the alignment of a float only.  For row r, entry e, head h:
+ *     s_eh     = <Q[r, head h], K[src(e), head h]>             (the reduction of flex_attention_heads: a chain of four fmas per lane,
+ *                                                               a tree over the d / 4 lanes of the head)
+ *     t_eh     = fma(scale, s_eh, bias[e, h])                  (ONE rounding)
+ *     alpha_eh = flex_edge_softmax's softmax of t_.h over the row, scale 1     (flex_gat_attention's passes, rescales and merges)
+ *     Out[r, head h] = sum_e alpha_eh V[src(e), head h]
+ * Special values follow the existing rules through t, with no new rule: bias = -inf masks that entry for that head (its p is exactly
+ * +0); a row whose t are all -inf, and a row without entries, write +0; a +inf or NaN t -- s = +inf against bias = -inf included --
+ * poisons the row for that head only (NaN in that head's d columns of Out and that head's entries of dP); every entry, masked or not,
+ * multiplies its V row.  On a row-range shard dBias is indexed by hostA's entry index, as dP is, and only the entries of the shard's
+ * rows are read.  dP may be NULL (Out has the same bits either way).
+ * Backward, with p = the dP the forward wrote and g = dGradOut.  It does not take the bias:
+ *     da_eh, delta_rh                                          as flex_attention_heads_backward
+ *     gBias[e, h] = fl(p_eh fl(da_eh - delta_rh))              new output: hostA->nnz x H floats, entry-major
+ *     ds_eh       = fl(fl(scale p_eh) fl(da_eh - delta_rh))    -> dWork, the unchanged expression
+ *     gQ, gK, gV                                               as flex_attention_heads_backward from ds and p
+ * No special cases: the formulas in fp32 under IEEE.  Each of dGradQ, dGradK, dGradV and dGradBias may be NULL; an output has the same
+ * bits whichever others are asked for, and a call without outputs launches nothing.  The rows' launch writes dWork, gQ and gBias and
+ * runs when any of gQ, gK, gBias is asked for (dWork then holds ds); the columns' launch is flex_attention_heads_backward's (or
+ * flex_attention_bf16_backward's) own kernel and runs when gK or gV is.  dGradBias must alias neither dP nor dWork (FLEX_ERR_INVALID
+ * where equal; any other overlap is the caller's error).  The backward is not defined on shards.
+ * flex_attention_bf16_bias / flex_attention_bf16_bias_backward: flex_attention_bf16's definition word for word.  Q, K, V, Out, g, gQ,
+ * gK and gV are flex_bf16, read as the fp32 numbers they are, with one rounding to nearest even at the single store of each element
+ * of Out, gQ, gK and gV; bias, gBias, dP and dWork are fp32, are not rounded, and equal the fp32 call's bits on the widened operands.
+ * Checks, for both element types (those of flex_attention_bf16): heads == 1 is served directly -- there is no generic form to forward
+ * to -- so for every H: k % H == 0, d in {4, 8, 16, 32, 64, 128, 256} (k = 48 with H = 1 and k = 300 are refused), k <= 1024, and only
+ * the vector form is built -- ldb % 4 == 0, ldc % 4 == 0, fp32 rows 16-byte aligned, bf16 rows 8-byte aligned; anything else is
+ * FLEX_ERR_UNSUPPORTED.  The wrong kind of plan, heads < 1, a scale that is not finite and > 0, a NULL operand (Q, K, V, Bias, Out; in
+ * the backward Q, K, V, P, GradOut, Work), dWork == dP, dGradBias == dP and dGradBias == dWork: FLEX_ERR_INVALID.  A plan without
+ * entries: FLEX_OK, no launch, nothing written.  Asynchronous on `stream`, no allocation, no host synchronisation (safe to capture in
+ * a hipGraph), no atomics, fixed reduction order: bit-identical run to run.
+ *
+ * Accuracy, with the u, gamma, E, R_r and n_r of flex_attention; forward against float64 on the fp32 inputs (the fp32 value of scale,
+ * the fp32 bias), backward against float64 on the SAME fp32 Q, K, V, p and g.
+ *   score   dt_e     = scale (gamma(d) sum_j |Q K| + d 2^-149) + u |t_e| + 2^-149
+ *   alpha   dalpha_e = alpha_e [gamma(n_r + 4 D_r + (E + 3) R_r + 2 E + 4) + expm1(2 max_row dt)] + 2^-126,
+ *                      D_r = min(104, the spread of the row's finite t)
+ *   Out     |Out - Out64| <= sum_e (gamma(n_r + 3) alpha_e + dalpha_e) |V| + 2^-126
+ *   gBias   |gB - gB64| <= gamma(n_r + 3) p_e (|da_e| + sum_j |p_j da_j|) + p_e (dda_e + sum_j p_j dda_j) + n_r 2^-149
+ *   dWork, gQ, gK, gV   flex_attention_heads_backward's bounds, unchanged (as there, for p that are zero or normal numbers: the
+ *                       n_r 2^-149 they grant products below 2^-126 does not cover fl(scale p) of a SUBNORMAL p -- off by up to
+ *                       2^-150 -- times a da - delta beyond n_r; a bias spread of more than about 87 - ln n_r produces such p)
+ *   bf16 outputs        |y - x64| <= bound32 + 2^-8 (|x64| + bound32) + 2^-134                    (flex_attention_bf16's)
+ * dP is held to dalpha on its own.  Derivation.  s is flex_attention_heads's reduction of depth <= d: |s - s64| <= gamma(d) sum |Q K| +
+ * d 2^-149.  t = fl(scale s + bias) is one fma: the error of s enters multiplied by scale (the product is not rounded), the one rounding
+ * of the sum is u |t|, or 2^-149 where t is subnormal.  From t on, alpha and Out are flex_attention's derivation with scale = 1, run by
+ * the same code as flex_gat_attention runs it: moving every t of a row by at most max_row dt moves the softmax by the factor
+ * exp(2 max_row dt); a term expf(fl(t - m)) carries gamma(2 D_r + E + 1) with D_r the spread of t itself (the product by scale = 1 is
+ * exact); R_r, c = 3 and the depths of the sums are the same passes, rescales and merges.  The rounding of the float64 score to the fp32
+ * one the softmax starts from, |s| u in flex_attention's line, is the u |t| already inside dt.  gBias = fl(p fl(da - delta)) is one
+ * subtraction and one product on flex_attention_heads_backward's da and delta: flex_gat_attention's ddz, which is that call's dds with
+ * scale = 1 (a = 3 covers a second product that is not made here).  ds, gQ, gK and gV are computed by the unchanged expressions from p
+ * and g, which is all they see of the forward. */
+int flex_attention_bias(const flex_plan *plan, int heads, const float *dQ, const float *dK, const float *dV, const float *dBias, float scale,
+                        float *dOut, float *dP, flex_stream_t stream);
+int flex_attention_bias_backward(const flex_plan *plan, int heads, const float *dQ, const float *dK, const float *dV, const float *dP,
+                                 const float *dGradOut, float scale, float *dGradQ, float *dGradK, float *dGradV, float *dGradBias,
+                                 float *dWork, flex_stream_t stream);
+int flex_attention_bf16_bias(const flex_plan *plan, int heads, const flex_bf16 *dQ, const flex_bf16 *dK, const flex_bf16 *dV, const float *dBias,
+                             float scale, flex_bf16 *dOut, float *dP, flex_stream_t stream);
+int flex_attention_bf16_bias_backward(const flex_plan *plan, int heads, const flex_bf16 *dQ, const flex_bf16 *dK, const flex_bf16 *dV,
+                                      const float *dP, const flex_bf16 *dGradOut, float scale, flex_bf16 *dGradQ, flex_bf16 *dGradK,
+                                      flex_bf16 *dGradV, float *dGradBias, float *dWork, flex_stream_t stream);
 
 /* Fused GAT attention: the additive score of graph attention networks in place of the dot product, H heads in the ONE forward launch and
  * the TWO backward launches of flex_attention_heads and flex_attention_heads_backward, on the same plans (FLEX_PLAN_ATTENTION;

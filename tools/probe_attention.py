@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Sparse graph attention, measured: the error of the exponential the edge softmax may use, and the time of flex_edge_softmax,
 flex_edge_softmax_backward and a whole attention step.  Writes profiles/attention_probe.txt (or the file given with --out): the whole run
-starts the file, a run of one part (--fused, --backward, --heads, --gat, --bf16) appends to it.
+starts the file, a run of one part (--fused, --backward, --heads, --gat, --bf16, --bias) appends to it.
 
 1. tools/exp_error.hip (built here with hipcc into flex_amd/lib if it is not there): the largest error in ulp of expf, __expf and
    exp2f on the prescaled argument over every fp32 argument in [-104, 0] against float64 exp.
@@ -31,7 +31,13 @@ starts the file, a run of one part (--fused, --backward, --heads, --gat, --bf16)
    the forward (with dP), the backward and the autograd step of attention(..., heads=H) on bfloat16 tensors against the same three on
    float32 tensors (flex_attention_heads, flex_attention_heads_backward) on the same operator, in the same process.  --bf16: only this
    part (and the copy rate).
-Usage: probe_attention.py [--out FILE] [--fused | --backward | --heads | --gat | --bf16] [graph ...]   (default: pubmed.csv flickr reddit soc-sign-epinions)"""
+9. A per-edge bias (flex_attention_bias, flex_attention_bf16_bias and their backward calls), (k, H) = (64, 8), (128, 4), (256, 8), same
+   graphs and protocol: the forward (with dP), the backward (with gBias) and the autograd step of attention(..., heads=H, bias=b) in fp32
+   and in bf16 against the unbiased flex_attention_heads / flex_attention_bf16 and their backward calls on the same operator in the same
+   process -- what the bias costs: nnz x H floats read forward, nnz x H written backward -- and, at k = 64 with one head, against what a
+   user needed before: flex_sddmm, a torch add, flex_edge_softmax and the SpMM with values=alpha, with their autograd.  --bias: only
+   this part (and the copy rate).
+Usage: probe_attention.py [--out FILE] [--fused | --backward | --heads | --gat | --bf16 | --bias] [graph ...]   (default: pubmed.csv flickr reddit soc-sign-epinions)"""
 import ctypes as C
 import os
 import subprocess
@@ -364,13 +370,81 @@ def probe_bf16(name, a):
         del op, plan
 
 
+def _alternate(fns, n):
+    """best of 3 rounds and the spread over them, every round timing each contender once"""
+    rounds = {key: [] for key in fns}
+    for _ in range(3):
+        for key, fn in fns.items():
+            rounds[key].append(best_us(fn, n, rounds=1))
+    return {key: min(v) for key, v in rounds.items()}, {key: 100 * (max(v) - min(v)) / min(v) for key, v in rounds.items()}
+
+
+def probe_bias(name, a):
+    gen = torch.Generator(device="cuda").manual_seed(7)
+    for k, H in ((64, 8), (128, 4), (256, 8), (64, 1)):
+        d = k // H
+        op = flex_amd.SparseOperator(a, k, learn_values=True, fused_attention=True, fused_backward=True)  # one plan serves every contender
+        plan = op.plan
+        Q, K, V, g = (torch.rand((r, k), device="cuda", generator=gen) * 2 - 1 for r in (a.m, a.n, a.n, a.m))
+        b = torch.rand((a.nnz, H), device="cuda", generator=gen) * 8 - 4
+        scale = d ** -0.5
+        rows = {torch.float32: (Q, K, V, g), torch.bfloat16: tuple(x.bfloat16() for x in (Q, K, V, g))}
+        outs = {dt: tuple(torch.empty((r, k), device="cuda", dtype=dt) for r in (a.m, a.m, a.n, a.n)) for dt in rows}
+        P, W, GB = (torch.empty((a.nnz, H), device="cuda") for _ in range(3))
+        leaves = {dt: tuple(x.clone().requires_grad_() for x in r[:3]) for dt, r in rows.items()}
+        bl = b.clone().requires_grad_()
+
+        def step(dt, biased):
+            for x in leaves[dt] + (bl,):
+                x.grad = None
+            op.attention(*leaves[dt], scale, heads=H, bias=bl if biased else None).backward(rows[dt][3])
+
+        fns = {}
+        for dt, tag, plain, plain_b, biased, biased_b in (
+                (torch.float32, "fp32", plan.attention, plan.attention_backward, plan.attention_bias, plan.attention_bias_backward),
+                (torch.bfloat16, "bf16", plan.attention_bf16, plan.attention_bf16_backward, plan.attention_bf16_bias, plan.attention_bf16_bias_backward)):
+            # one head in fp32 is flex_attention itself, whose edge arrays are [nnz]
+            Pp, Wp = (P.view(-1), W.view(-1)) if H == 1 and dt == torch.float32 else (P, W)
+            (q, kk, v, gg), (o, gq, gk, gv) = rows[dt], outs[dt]
+            fns[f"forward, {tag}"] = lambda q=q, kk=kk, v=v, o=o, f=plain, Pp=Pp: f(q, kk, v, scale, out=o, p=Pp, heads=H)
+            fns[f"forward, {tag} bias"] = lambda q=q, kk=kk, v=v, o=o, f=biased: f(q, kk, v, b, scale, heads=H, out=o, p=P)
+            fns[f"backward, {tag}"] = lambda q=q, kk=kk, v=v, gg=gg, gq=gq, gk=gk, gv=gv, f=plain_b, Pp=Pp, Wp=Wp: f(q, kk, v, Pp, gg, scale, grad_q=gq, grad_k=gk, grad_v=gv, work=Wp, heads=H)
+            fns[f"backward, {tag} bias"] = lambda q=q, kk=kk, v=v, gg=gg, gq=gq, gk=gk, gv=gv, f=biased_b: f(q, kk, v, P, gg, scale, heads=H, grad_q=gq, grad_k=gk, grad_v=gv, grad_bias=GB, work=W)
+            fns[f"step, {tag}"] = lambda dt=dt: step(dt, False)
+            fns[f"step, {tag} bias"] = lambda dt=dt: step(dt, True)
+        if H == 1:  # what a user needed before: four calls and a torch add, with their autograd
+            b1 = b[:, 0].clone().requires_grad_()
+
+            def composed():
+                for x in leaves[torch.float32] + (b1,):
+                    x.grad = None
+                q, kk, v = leaves[torch.float32]
+                return op(v, values=op.edge_softmax(scale * op.sddmm(q, kk) + b1, 1.0))
+
+            def composed_forward():
+                with torch.no_grad():
+                    composed()
+
+            fns["forward, four calls and an add"] = composed_forward
+            fns["step, four calls and an add"] = lambda: composed().backward(g)
+        plan.attention_bias(Q, K, V, b, scale, heads=H, out=outs[torch.float32][0], p=P)  # P holds probabilities for every backward
+        n = max(3, min(100, int(1e8 / max(1, a.nnz * k))))
+        best, spread = _alternate(fns, n)
+        say(f"{name} k={k} H={H} d={d} bias: " + "  ".join(f"{key} {best[key]:.1f} us (+{spread[key]:.0f} % over 3 rounds)" for key in fns)
+            + "  bias / no bias: " + "  ".join(f"{w} {t} {best[f'{w}, {t} bias'] / best[f'{w}, {t}']:.2f}x" for t in ("fp32", "bf16") for w in ("forward", "backward", "step"))
+            + ("  four calls / fused: " + "  ".join(f"{w} {best[w + ', four calls and an add'] / best[w + ', fp32 bias']:.2f}x" for w in ("forward", "step")) if H == 1 else "")
+            + f"  bias and gBias: {4 * a.nnz * H / 2 ** 20:.1f} MiB each (nnz x H floats), beside P and work of the same size")
+        del op, plan
+
+
 def main():
     args = sys.argv[1:]
     out = os.path.join(ROOT, "profiles", "attention_probe.txt")
     if args[:1] == ["--out"]:
         out, args = args[1], args[2:]
-    fused_only, backward_only, heads_only, gat_only, bf16_only = (args[:1] == [flag] for flag in ("--fused", "--backward", "--heads", "--gat", "--bf16"))
-    only = fused_only or backward_only or heads_only or gat_only or bf16_only
+    fused_only, backward_only, heads_only, gat_only, bf16_only, bias_only = (args[:1] == [flag] for flag in
+                                                                             ("--fused", "--backward", "--heads", "--gat", "--bf16", "--bias"))
+    only = fused_only or backward_only or heads_only or gat_only or bf16_only or bias_only
     if only:
         args = args[1:]
     else:
@@ -391,6 +465,8 @@ def main():
             probe_gat(name, a)
         if bf16_only or not only:
             probe_bf16(name, a)
+        if bias_only or not only:
+            probe_bias(name, a)
     with open(out, "a" if only else "w") as f:  # a part is appended, the whole run starts the file
         f.write("\n".join(LINES) + "\n")
 
