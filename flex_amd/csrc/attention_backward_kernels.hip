@@ -1,7 +1,9 @@
 // attention_backward_kernels.hip -- the fused attention backward of FLEX_PLAN_ATTENTION_BACKWARD plans (include/flex_spmm.h:
 // flex_attention_backward): from the probabilities p that flex_attention kept and the gradient g in Out, the gradients in Q, K and V in
 // two launches, without the value refresh, the two transposed SpMMs and two of the three nnz-sized vectors of the chain
-// flex_plan_set_values / flex_spmm / flex_sddmm / flex_edge_softmax_backward.  tests/test_gpu_fused_attention_backward.py covers it.
+// flex_plan_set_values / flex_spmm / flex_sddmm / flex_edge_softmax_backward.  tests/test_gpu_fused_attention_backward.py covers it, the
+// 16-byte and the generic form of every (W, NS), each kernel alone as well: the cases are tests/attention_forms.py's, and
+// tests/test_attention_routes.py holds every instantiation to a case that launches it.
 //
 // Row kernel (attention_rows_backward): the forward's walk, slots, waves and blocks (attention_device.h; internal.h, kAtPass).  A slot
 // holds its g row in registers and sweeps its share of the row twice, so that every entry gathers its V row once and its K row once:

@@ -1,7 +1,8 @@
 // attention_bf16_kernels.hip -- the multi-head fused attention on bf16 row operands (include/flex_spmm.h: flex_attention_bf16,
 // flex_attention_bf16_backward): Q, K, V, Out, g, gQ, gK and gV are flex_bf16, the edge arrays dP and dWork stay fp32, and everything
 // between a row's load and a row's store is the fp32 code of flex_attention_heads and flex_attention_heads_backward.
-// tests/test_gpu_attention_bf16.py covers it.
+// tests/test_gpu_attention_bf16.py covers it; its (k, H) table is tests/attention_forms.py's, and tests/test_attention_routes.py holds
+// every instantiation to a case that launches it.
 //
 // The sweeps are attention_heads_device.h's with the element type flex_bf16: the same walk, head split, slot placement, merges and LDS
 // meeting places (fp32) as attention_heads_kernels.hip, one forward launch and two backward launches on the same plans.  A row load is

@@ -1,7 +1,8 @@
 // attention_bias_kernels.hip -- the multi-head fused attention with a per-edge, per-head additive bias in the score
 // (include/flex_spmm.h: flex_attention_bias, flex_attention_bias_backward on fp32 rows, flex_attention_bf16_bias,
 // flex_attention_bf16_bias_backward on bf16 rows): alpha = the softmax over the row of t = fma(scale, <q, k>, bias[e, h]), a bias of
-// -inf masking an entry for a head.  tests/test_gpu_attention_bias.py covers it.
+// -inf masking an entry for a head.  tests/test_gpu_attention_bias.py covers it; its (k, H) table is tests/attention_forms.py's, and
+// tests/test_attention_routes.py holds every instantiation to a case that launches it.
 //
 // The sweeps are attention_heads_device.h's under their compile-time BIAS switch, for both element types: the same walk, head split, slot
 // placement, merges and LDS meeting places as attention_heads_kernels.hip and attention_bf16_kernels.hip.  Forward: every lane of a head

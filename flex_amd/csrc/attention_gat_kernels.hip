@@ -1,6 +1,7 @@
 // attention_gat_kernels.hip -- the fused GAT attention (include/flex_spmm.h: flex_gat_attention, flex_gat_attention_backward): the
 // additive score s = LeakyReLU(el[r] + er[src]) per head in place of the dot product <Q[r], K[src]>, in the ONE forward launch and the
-// TWO backward launches of the multi-head fused attention, on the same plans.  tests/test_gpu_gat_attention.py covers it.
+// TWO backward launches of the multi-head fused attention, on the same plans.  tests/test_gpu_gat_attention.py covers it; its (k, H)
+// table is tests/attention_forms.py's, and tests/test_attention_routes.py holds every instantiation to a case that launches it.
 //
 // The walk is attention_heads_kernels.hip's (attention_device.h): the same view, items, groups, slot / wave / block ownership by
 // place_of, W = sddmm_lanes(k) lanes per slot, four entries per pass, four columns per lane and slab, the XCD remap, State<1> per lane

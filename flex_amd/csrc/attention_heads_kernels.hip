@@ -1,6 +1,7 @@
 // attention_heads_kernels.hip -- the multi-head forms of the fused attention (include/flex_spmm.h: flex_attention_heads,
 // flex_attention_heads_backward): H heads of d = k / H columns each in the one forward launch and the two backward launches of
-// flex_attention and flex_attention_backward, on the same plans.  tests/test_gpu_multihead_attention.py covers it.
+// flex_attention and flex_attention_backward, on the same plans.  tests/test_gpu_multihead_attention.py covers it; its (k, H) table is
+// tests/attention_forms.py's, and tests/test_attention_routes.py holds every instantiation to a case that launches it.
 //
 // The sweeps are attention_heads_device.h's with the element type float (attention_bf16_kernels.hip instantiates the same sweeps with
 // flex_bf16); the kernels below declare the LDS and call them.

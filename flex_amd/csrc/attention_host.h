@@ -43,13 +43,11 @@ inline void dispatch(const AttentionPick &pick, F &&f) {
     }
 }
 
-// FLEX_OK and the split where heads (1 included) divides k into heads of d = 4 .. 256 columns, d a power of two
+// FLEX_OK and the split where heads (1 included) divides k into heads of d = 4 .. 256 columns, d a power of two: the rule is
+// internal.h's head_split_lg, which the launch log of tests/hostsim/shim.cpp shares
 inline int split_of(int k, int heads, HeadSplit *out) {
-    if (k > 4 * 64 * kAtMaxSlabs || k % heads) return FLEX_ERR_UNSUPPORTED;
-    const int d = k / heads;
     int lg = 0;
-    while ((4 << lg) < d) ++lg;
-    if (d < 4 || d > 256 || (4 << lg) != d) return FLEX_ERR_UNSUPPORTED;
+    if (const int rc = head_split_lg(k, heads, &lg)) return rc;
     *out = HeadSplit{heads, lg};
     return FLEX_OK;
 }

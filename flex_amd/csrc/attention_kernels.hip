@@ -3,7 +3,9 @@
 // is built by the planner from hostA's row pointer and columns (plan_build.cpp, upload_attention_image; the classes and constants:
 // internal.h, kAtPass) and verified by flex_plan_self_check (plan_check.cpp).
 //
-// Not an SpMM kernel and not one of flex::values / flex::softmax: a namespace of its own; tests/test_gpu_fused_attention.py covers it.
+// Not an SpMM kernel and not one of flex::values / flex::softmax: a namespace of its own; tests/test_gpu_fused_attention.py covers it,
+// the 16-byte and the generic form of every (W, NS): the cases are tests/attention_forms.py's, and tests/test_attention_routes.py holds
+// every instantiation of flex::attention to a case that launches it.
 // The view of the walk, the slot placement (place_of) and the helpers it shares with the other attention kernels: attention_device.h;
 // the view, the grid and the (W, NS) dispatch of the entry point: attention_host.h.
 //

@@ -288,6 +288,17 @@ inline AttentionPick attention_pick(int k, int ldb, int ldc, const void *dQ, con
     const uintptr_t ptrs = reinterpret_cast<uintptr_t>(dQ) | reinterpret_cast<uintptr_t>(dK) | reinterpret_cast<uintptr_t>(dV) | reinterpret_cast<uintptr_t>(dOut);
     return AttentionPick{W, slabs <= 1 ? 1 : slabs == 2 ? 2 : 4, k % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0 && ptrs % 16 == 0};
 }
+// The head split of the per-head entry points (attention_host.h, split_of): FLEX_OK and lg, with d = k / heads = 4 << lg, where heads
+// (1 included) divides k into heads of d = 4 .. 256 columns, d a power of two.  A host rule, as attention_pick.
+inline int head_split_lg(int k, int heads, int *lg_out) {
+    if (k > 4 * 64 * kAtMaxSlabs || k % heads) return FLEX_ERR_UNSUPPORTED;
+    const int d = k / heads;
+    int lg = 0;
+    while ((4 << lg) < d) ++lg;
+    if (d < 4 || d > 256 || (4 << lg) != d) return FLEX_ERR_UNSUPPORTED;
+    *lg_out = lg;
+    return FLEX_OK;
+}
 
 // per-thread record of the last HIP failure (flex_last_hip_error)
 void note_hip_error(hipError_t e);

@@ -1,5 +1,6 @@
 // spmm_bf16_kernels.hip -- the SpMM on bf16 operands (include/flex_spmm.h: FLEX_PLAN_BF16, flex_spmm_bf16): B and C are flex_bf16, the
-// sums are fp32.  DESIGN.md 3.16; tests/test_gpu_spmm_bf16.py covers it.
+// sums are fp32.  DESIGN.md 3.16; tests/test_gpu_spmm_bf16.py covers it, both offset forms of every tile width; the cases are
+// tests/spmm_bf16_ref.py's and tests/attention_forms.py's, and tests/test_attention_routes.py holds every instantiation to a case.
 //
 // A bf16 row of k elements is, byte for byte, an fp32 row of k / 2 words, and a FLEX_PLAN_BF16 plan is the fp32 plan of that word width
 // (plan.cpp, create_common): PlanView's k, ldb and ldc are WORDS here, the records hold byte offsets of word rows, a lane owns 4 words

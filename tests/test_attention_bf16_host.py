@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import attention_bf16_ref as bf
+from attention_forms import BF16_PAIRS as PAIRS
 import flex_amd
 import multihead_attention_ref as mh
 from backward_ref import _directed
@@ -22,14 +23,14 @@ torch = pytest.importorskip("torch")
 
 K, HEADS, SCALE = 32, 4, 0.25
 
-# the table of tests/test_gpu_attention_bf16.py: every (W, NS) form, idle lanes past k, d = 4 and d = 256, H = 1
+# the table of tests/test_gpu_attention_bf16.py: the (k, H) pairs are tests/attention_forms.py's (every (W, NS) form, idle lanes past k,
+# d = 4 and d = 256, H = 1)
 GRAPHS = {
     "thresholds": threshold_graph,
     "thresholds_lifted": lambda: both_sides(threshold_graph()),
     "directed_empty": lambda: _directed(250, 260, seed=7),
     "long_rows": long_rows_graph,
 }
-PAIRS = [(4, 1), (64, 1), (8, 2), (32, 4), (48, 3), (128, 8), (256, 4), (512, 4), (1024, 64)]
 CASES = [(name, k, H) for k, H in PAIRS for name in (sorted(GRAPHS) if k < 256 else ["thresholds", "thresholds_lifted"])]
 _graphs = {}
 

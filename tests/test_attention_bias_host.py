@@ -11,6 +11,7 @@ import pytest
 
 import attention_bf16_ref as bf
 import attention_bias_ref as ab
+from attention_forms import BIAS_PAIRS as PAIRS
 import flex_amd
 from backward_ref import _directed
 from conftest import ROOT
@@ -20,14 +21,13 @@ from softmax_ref import long_rows_graph
 
 SCALE = 0.25
 
-# the table of tests/test_gpu_attention_bias.py: every (W, NS) form, idle lanes past k (48), d = 4 and d = 256, H = 1; the wide pairs
-# (k >= 256) run on the graph that holds every class of row and of column
+# the table of tests/test_gpu_attention_bias.py: the (k, H) pairs are tests/attention_forms.py's (every (W, NS) form, idle lanes past k
+# (48), d = 4 and d = 256, H = 1); the wide pairs (k >= 256) run on the graph that holds every class of row and of column
 GRAPHS = {
     "thresholds_lifted": lambda: both_sides(threshold_graph()),
     "directed_empty": lambda: _directed(250, 260, seed=7),
     "long_rows": long_rows_graph,
 }
-PAIRS = [(4, 1), (64, 1), (8, 2), (32, 4), (48, 3), (128, 8), (256, 4), (512, 4), (1024, 64)]
 CASES = [(name, k, H) for k, H in PAIRS for name in (sorted(GRAPHS) if k < 256 else ["thresholds_lifted"])]
 _graphs = {}
 

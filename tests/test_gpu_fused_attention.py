@@ -1,6 +1,7 @@
 """The fused attention forward on the GPU (flex_attention, FLEX_PLAN_ATTENTION): Out and P against the float64 reference and the bounds
-of tests/fused_attention_ref.py on every element, on every row class, slot width and score scenario; against the four-call composition
-on the same plan; on strided, unaligned and shard plans; run to run and inside a captured graph; and SparseOperator(fused_attention=True)
+of tests/fused_attention_ref.py on every element, on every row class, slot width and score scenario, in the 16-byte form and in the
+generic form of every (W, NS) (the k tables are tests/attention_forms.py's, whose cases tests/test_attention_routes.py holds to the
+kernels they launch); against the four-call composition on the same plan; on strided, unaligned and shard plans; run to run and inside a captured graph; and SparseOperator(fused_attention=True)
 with its gradients against a float64 torch evaluation."""
 import os
 
@@ -9,9 +10,11 @@ import pytest
 
 import flex_amd
 import test_gpu_attention as composition
+from attention_forms import GENERIC_ALIGNED_KS, GENERIC_ODD_KS, SINGLE_KS as KS, SINGLE_OTHER_KS, SINGLE_STRIDED_KS
 from backward_ref import _directed
 from conftest import GOLDEN
 from flex_amd import binding
+from fused_attention_backward_ref import both_sides
 from fused_attention_ref import QKV_SCENARIOS, check, coo, operands, reference, threshold_graph
 from softmax_ref import SCALES, boundary_graph, gamma, long_rows_graph
 
@@ -26,13 +29,13 @@ GRAPHS = {
     "rows_256_257": boundary_graph,
     "thresholds": threshold_graph,
 }
-KS = (8, 32, 100, 128, 256)
+LIFTED = {"thresholds_lifted": lambda: both_sides(threshold_graph())}  # the generic forms' second graph: the classes in the columns too
 _graphs, _plans = {}, {}
 
 
 def graph(name):
     if name not in _graphs:
-        _graphs[name] = GRAPHS[name]()
+        _graphs[name] = (GRAPHS.get(name) or LIFTED[name])()
     return _graphs[name]
 
 
@@ -86,7 +89,7 @@ def test_score_scenarios(name, scenario, k):
         print(f"{name} {scenario} k={k} scale {scale}: worst err / bound {worst:.3g}")
 
 
-@pytest.mark.parametrize("k", [30, 64, 300, 600])
+@pytest.mark.parametrize("k", SINGLE_OTHER_KS)
 def test_the_other_slot_widths_and_slabs(k):
     """k = 30: the generic instantiation; 64: slots of 16 lanes; 300 and 600: two and four slabs of 256 columns."""
     a, p = graph("thresholds"), plan("thresholds", k)
@@ -144,7 +147,7 @@ def test_without_p_the_same_out_and_nonfinite_v_rows_reach_their_neighbours_only
     assert hit.any() and np.array_equal(~np.isfinite(out), hit)
 
 
-@pytest.mark.parametrize("k", [30, 32])
+@pytest.mark.parametrize("k", SINGLE_STRIDED_KS)
 def test_strided_and_unaligned_operands(k):
     a = graph("thresholds")
     Q, K, V = operands("uniform4", a, k, seed=6)
@@ -161,6 +164,56 @@ def test_strided_and_unaligned_operands(k):
         got = _host(big[3])[off:off + a.m * ldc].reshape(a.m, ldc)
         assert _same_bits(got[:, :k], want) and np.all(np.isnan(got[:, k:])), (ldb, ldc, off)
         assert _same_bits(_host(pd)[off:off + a.nnz], want_p)
+
+
+# ---- the generic form of every (W, NS): tests/attention_forms.py, GENERIC_ODD_KS and GENERIC_ALIGNED_KS
+
+def _run_embedded(name, k, Q, K, V, scale, ldb, ldc, off):
+    """(Out [m, ldc] with the cells past k, P) of a run whose row operands lie `off` floats into NaN-filled buffers of one float more,
+    ldb / ldc floats from row to row: whatever is read past k, or outside an operand, poisons the result."""
+    a, p = graph(name), plan(name, k, ldb=ldb, ldc=ldc)
+    big = [torch.full((rows * ld + 1,), float("nan"), device="cuda") for rows, ld in ((a.m, ldc), (a.n, ldb), (a.n, ldb), (a.m, ldc))]
+    for t, x, ld in zip(big, (Q, K, V), (ldc, ldb, ldb)):
+        t[off:off + x.shape[0] * ld].view(x.shape[0], ld)[:, :k] = _dev(x)
+    pd = torch.full((a.nnz + 1,), -7.0, device="cuda")
+    p.attention_ptr(*(t.data_ptr() + 4 * off for t in big[:3]), 0.125, big[3].data_ptr() + 4 * off, pd.data_ptr() + 4 * off,
+                    torch.cuda.current_stream().cuda_stream)
+    flat, pr = _host(big[3]), _host(pd)
+    assert np.isnan(flat[0 if off else -1]) and pr[0 if off else -1] == -7.0, (k, ldb, ldc, off)  # the float outside the operand
+    return flat[off:off + a.m * ldc].reshape(a.m, ldc), pr[off:off + a.nnz]
+
+
+@pytest.mark.parametrize("k", GENERIC_ODD_KS)
+@pytest.mark.parametrize("name", ["thresholds", "thresholds_lifted"])
+def test_the_generic_form_of_every_width_at_a_k_that_is_no_multiple_of_4(name, k):
+    """One k per (W, NS) with scalar tails: 6, 50, 101 and 250 on slots of 4, 16, 32 and 64 lanes, 301 on two slabs, 601 on three slabs
+    of the four-slab form (one idle), 1023 on four slabs one column short.  Dense rows, and rows in padded ones whose cells past k must
+    stay NaN."""
+    a = graph(name)
+    for scenario in ("uniform4", "poisoned") + (("rows_masked",) if name == "thresholds_lifted" else ()):
+        Q, K, V = operands(scenario, a, k, seed=12)
+        for ldb, ldc in ((k, k), (k + 3, k + 1)):
+            out, pr = _run_embedded(name, k, Q, K, V, 0.125, ldb, ldc, 0)
+            worst = check(a, Q, K, V, 0.125, out[:, :k], pr, what=f"{name} {scenario} k={k} ldb {ldb} ldc {ldc}")
+            assert np.all(np.isnan(out[:, k:])), (scenario, k, ldb, ldc)
+            print(f"{name} {scenario} k={k} ldb {ldb} ldc {ldc} (generic): worst err / bound {worst:.3g}")
+
+
+@pytest.mark.parametrize("k", GENERIC_ALIGNED_KS)
+@pytest.mark.parametrize("name", ["thresholds", "thresholds_lifted"])
+def test_the_generic_form_of_every_width_through_misaligned_and_oddly_strided_operands(name, k):
+    """An aligned k reaches the generic form when every row operand is one float off 16 bytes, or the leading dimensions are odd: against
+    float64, and bit for bit what the 16-byte form gives on the same numbers, as test_strided_and_unaligned_operands has it at k = 32."""
+    a = graph(name)
+    for scenario in ("uniform4", "poisoned") + (("rows_masked",) if name == "thresholds_lifted" else ()):
+        Q, K, V = operands(scenario, a, k, seed=13)
+        want, want_p = _run(plan(name, k), a, Q, K, V, 0.125)
+        for ldb, ldc, off in ((k + 3, k + 1, 0), (k, k, 1)):
+            out, pr = _run_embedded(name, k, Q, K, V, 0.125, ldb, ldc, off)
+            worst = check(a, Q, K, V, 0.125, out[:, :k], pr, what=f"{name} {scenario} k={k} ldb {ldb} ldc {ldc} off {off}")
+            assert np.all(np.isnan(out[:, k:])), (scenario, k, ldb, ldc, off)
+            print(f"{name} {scenario} k={k} ldb {ldb} ldc {ldc} off {off} (generic): worst err / bound {worst:.3g}")
+            assert _same_bits(out[:, :k], want) and _same_bits(pr, want_p), (scenario, k, ldb, ldc, off)
 
 
 def test_shards_write_their_own_rows_and_entries_only_and_their_union_is_the_unsharded_result():

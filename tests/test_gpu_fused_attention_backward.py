@@ -1,6 +1,7 @@
 """The fused attention backward on the GPU (flex_attention_backward, FLEX_PLAN_ATTENTION_BACKWARD): gQ, gK, gV and ds against the float64
 reference and the bounds of tests/fused_attention_backward_ref.py on every element, on every row and column class, slot width and score
-scenario, with p taken from flex_attention on the same operands; against the chain of eight engine calls on the same p; non-finite
+scenario, in the 16-byte form and in the generic form of every (W, NS) (the k tables are tests/attention_forms.py's, whose cases
+tests/test_attention_routes.py holds to the kernels they launch), with p taken from flex_attention on the same operands; against the chain of eight engine calls on the same p; non-finite
 operands; strided and unaligned operands; subsets of the outputs; run to run and inside a captured graph; and
 SparseOperator(fused_attention=True, fused_backward=True) with its gradients against a float64 torch evaluation.
 
@@ -13,6 +14,8 @@ import pytest
 
 import flex_amd
 import test_gpu_attention as composition
+from attention_forms import (COLUMN_KERNEL_ALONE, GENERIC_ALIGNED_KS, GENERIC_ODD_KS, ROW_KERNEL_ALONE, SINGLE_KS as KS, SINGLE_OTHER_KS,
+                             SINGLE_STRIDED_KS)
 from backward_ref import _directed
 from conftest import GOLDEN
 from flex_amd import binding
@@ -32,14 +35,14 @@ GRAPHS = {
     "rows_256_257_lifted": lambda: both_sides(boundary_graph()),
     "thresholds_lifted": lambda: both_sides(threshold_graph()),
 }
-KS = (8, 32, 100, 128, 256)
+UNLIFTED = {"thresholds": threshold_graph}  # the generic forms' second graph: no long column
 SENTINEL = -12345.5
 _graphs, _plans = {}, {}
 
 
 def graph(name):
     if name not in _graphs:
-        _graphs[name] = GRAPHS[name]()
+        _graphs[name] = (GRAPHS.get(name) or UNLIFTED[name])()
     return _graphs[name]
 
 
@@ -112,7 +115,7 @@ def test_score_scenarios(scenario, k):
         print(f"{name} {scenario} k={k} scale {scale}: worst err / bound {worst:.3g} ({_each(each)})")
 
 
-@pytest.mark.parametrize("k", [30, 64, 300, 600])
+@pytest.mark.parametrize("k", SINGLE_OTHER_KS)
 def test_the_other_slot_widths_and_slabs(k):
     """k = 30: the generic instantiation; 64: slots of 16 lanes; 300 and 600: two and four slabs of 256 columns."""
     name = "thresholds_lifted"
@@ -184,7 +187,7 @@ def test_a_nan_and_an_inf_reach_exactly_the_rows_of_the_adjacent_columns():
     assert np.array_equal(~np.isfinite(ds), row == r_nan)
 
 
-@pytest.mark.parametrize("k", [30, 32])
+@pytest.mark.parametrize("k", SINGLE_STRIDED_KS)
 def test_strided_and_unaligned_operands(k):
     name, scale = "thresholds_lifted", 0.125
     a = graph(name)
@@ -213,6 +216,88 @@ def test_strided_and_unaligned_operands(k):
             assert flat[0 if off else -1] == SENTINEL, (ldb, ldc, off)  # the element outside the operand
         wk = _host(work)
         assert _same_bits(wk[off:off + a.nnz], want[3]) and wk[0 if off else -1] == SENTINEL
+
+
+# ---- the generic form of every (W, NS): tests/attention_forms.py, GENERIC_ODD_KS and GENERIC_ALIGNED_KS
+
+def _run_embedded(name, k, Q, K, V, pr, g, scale, ldb, ldc, off, want=(True, True, True)):
+    """(gQ [m, ldc], gK [n, ldb], gV [n, ldb] with their cells past k, ds) of a run whose row operands lie `off` floats into NaN-filled
+    buffers of one float more, ldb / ldc floats from row to row: whatever is read past k, or outside an operand, poisons the result,
+    and an output that is not wanted is NULL and stays NaN."""
+    a, p = graph(name), plan(name, k, ldb=ldb, ldc=ldc)
+    shapes = ((a.m, ldc), (a.n, ldb), (a.n, ldb), (a.m, ldc))  # Q, K, V, g
+    ins = [torch.full((rows * ld + 1,), float("nan"), device="cuda") for rows, ld in shapes]
+    for t, x, (_, ld) in zip(ins, (Q, K, V, g), shapes):
+        t[off:off + x.shape[0] * ld].view(x.shape[0], ld)[:, :k] = _dev(x)
+    oshapes = ((a.m, ldc), (a.n, ldb), (a.n, ldb))  # gQ, gK, gV
+    outs = [torch.full((rows * ld + 1,), float("nan"), device="cuda") for rows, ld in oshapes]
+    pd, work = torch.full((a.nnz + 1,), 0.5, device="cuda"), torch.full((a.nnz + 1,), SENTINEL, device="cuda")
+    pd[off:off + a.nnz] = _dev(pr)
+    p.attention_backward_ptr(*(t.data_ptr() + 4 * off for t in ins[:3]), pd.data_ptr() + 4 * off, ins[3].data_ptr() + 4 * off, scale,
+                             *(t.data_ptr() + 4 * off if w else None for t, w in zip(outs, want)), work.data_ptr() + 4 * off,
+                             torch.cuda.current_stream().cuda_stream)
+    got = []
+    for t, (rows, ld), w in zip(outs, oshapes, want):
+        flat = _host(t)
+        assert np.isnan(flat[0 if off else -1]) and (w or np.all(np.isnan(flat))), (k, ldb, ldc, off, want)  # the float outside the operand
+        got.append(flat[off:off + rows * ld].reshape(rows, ld))
+    wk = _host(work)
+    assert wk[0 if off else -1] == SENTINEL
+    return tuple(got) + (wk[off:off + a.nnz],)
+
+
+def _check_embedded(a, k, Q, K, V, pr, g, scale, got, what):
+    each = {}
+    worst = check(a, Q, K, V, pr, g, scale, *(x[:, :k] for x in got[:3]), got[3], what=what, ratios=each)
+    assert all(np.all(np.isnan(x[:, k:])) for x in got[:3]), what  # the cells past k
+    print(f"{what} (generic): worst err / bound {worst:.3g} ({_each(each)})")
+
+
+def _each_kernel_alone(name, k, Q, K, V, pr, g, scale, ldb, ldc, off, full):
+    """gQ alone is the row launch alone, gV alone the column launch alone: the bits of the full run, which is checked against float64."""
+    rows_only = _run_embedded(name, k, Q, K, V, pr, g, scale, ldb, ldc, off, want=ROW_KERNEL_ALONE)
+    assert _same_bits(rows_only[0][:, :k], full[0][:, :k]) and _same_bits(rows_only[3], full[3]), (k, "gQ alone")
+    cols_only = _run_embedded(name, k, Q, K, V, pr, g, scale, ldb, ldc, off, want=COLUMN_KERNEL_ALONE)
+    assert _same_bits(cols_only[2][:, :k], full[2][:, :k]) and np.all(cols_only[3] == SENTINEL), (k, "gV alone")
+
+
+@pytest.mark.parametrize("k", GENERIC_ODD_KS)
+@pytest.mark.parametrize("name", ["thresholds", "thresholds_lifted"])
+def test_the_generic_form_of_every_width_at_a_k_that_is_no_multiple_of_4(name, k):
+    """One k per (W, NS) with scalar tails: 6, 50, 101 and 250 on slots of 4, 16, 32 and 64 lanes, 301 on two slabs, 601 on three slabs
+    of the four-slab form (one idle), 1023 on four slabs one column short.  Dense rows, and rows in padded ones whose cells past k must
+    stay NaN; then each of the two kernels alone."""
+    a, scale = graph(name), 0.125
+    g = _grad(a, k, 12)
+    for scenario in ("uniform4", "poisoned") + (("rows_masked",) if name == "thresholds_lifted" else ()):
+        Q, K, V = operands(scenario, a, k, seed=12)
+        pr = _forward_p(plan(name, k), a, Q, K, V, scale)
+        for ldb, ldc in ((k, k), (k + 3, k + 1)):
+            got = _run_embedded(name, k, Q, K, V, pr, g, scale, ldb, ldc, 0)
+            _check_embedded(a, k, Q, K, V, pr, g, scale, got, f"{name} {scenario} k={k} ldb {ldb} ldc {ldc}")
+        if scenario == "uniform4":
+            _each_kernel_alone(name, k, Q, K, V, pr, g, scale, k + 3, k + 1, 0, got)
+
+
+@pytest.mark.parametrize("k", GENERIC_ALIGNED_KS)
+@pytest.mark.parametrize("name", ["thresholds", "thresholds_lifted"])
+def test_the_generic_form_of_every_width_through_misaligned_and_oddly_strided_operands(name, k):
+    """An aligned k reaches the generic form when every row operand is one float off 16 bytes, or the leading dimensions are odd: against
+    float64, and bit for bit what the 16-byte form gives on the same numbers, as test_strided_and_unaligned_operands has it at k = 32."""
+    a, scale = graph(name), 0.125
+    g = _grad(a, k, 13)
+    for scenario in ("uniform4", "poisoned") + (("rows_masked",) if name == "thresholds_lifted" else ()):
+        Q, K, V = operands(scenario, a, k, seed=13)
+        pr = _forward_p(plan(name, k), a, Q, K, V, scale)
+        want = _run(plan(name, k), a, Q, K, V, pr, g, scale)
+        for ldb, ldc, off in ((k + 3, k + 1, 0), (k, k, 1)):
+            got = _run_embedded(name, k, Q, K, V, pr, g, scale, ldb, ldc, off)
+            _check_embedded(a, k, Q, K, V, pr, g, scale, got, f"{name} {scenario} k={k} ldb {ldb} ldc {ldc} off {off}")
+            for x, w in zip(got[:3], want[:3]):
+                assert _same_bits(x[:, :k], w), (scenario, k, ldb, ldc, off)
+            assert _same_bits(got[3], want[3]), (scenario, k, ldb, ldc, off)
+        if scenario == "uniform4":
+            _each_kernel_alone(name, k, Q, K, V, pr, g, scale, k, k, 1, got)
 
 
 def test_every_output_has_the_same_bits_whichever_others_are_asked_for():

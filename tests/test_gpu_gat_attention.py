@@ -1,6 +1,6 @@
 """The fused GAT attention on the GPU (flex_gat_attention, flex_gat_attention_backward): Out, P, gEl, gEr, gV and dx against the float64
 reference and the bounds of tests/gat_attention_ref.py on every element, with a different scenario in every head of a call, over every
-(k, H) of the table below and every row and column class; against the composition of existing calls it replaces; head isolation; the
+(k, H) of tests/attention_forms.py's GAT table and every row and column class; against the composition of existing calls it replaces; head isolation; the
 output invariants (dP = NULL, subsets of the gradients, run to run, a captured graph, sentinels, padded leading dimensions); refusals;
 a row-range shard; and SparseOperator.gat_attention with its gradients against a float64 torch evaluation.
 
@@ -12,6 +12,7 @@ import pytest
 
 import flex_amd
 import gat_attention_ref as gat
+from attention_forms import GAT_PAIRS as PAIRS
 from backward_ref import _directed
 from flex_amd import binding
 from softmax_ref import long_rows_graph
@@ -25,7 +26,6 @@ GRAPHS = {
     "directed_empty": lambda: _directed(250, 260, seed=7),
     "long_rows": long_rows_graph,
 }
-PAIRS = [(4, 1), (8, 2), (16, 4), (48, 3), (64, 8), (96, 3), (128, 1), (128, 8), (256, 1), (512, 2), (1024, 4), (1024, 64)]
 CASES = [(name, k, H) for k, H in PAIRS for name in (sorted(GRAPHS) if k < 256 else ["thresholds", "thresholds_lifted"])]
 SENTINEL = -12345.5
 SLOPE = gat.SLOPE

@@ -1,6 +1,6 @@
 """The multi-head fused attention on the GPU (flex_attention_heads, flex_attention_heads_backward): Out, P, gQ, gK, gV and ds against the
 stacked float64 reference and the per-head bounds of tests/multihead_attention_ref.py on every element, with a different score scenario
-in every head of a call, over every (k, H) of the table below and every row and column class; heads = 1 through the new entry points
+in every head of a call, over every (k, H) of tests/attention_forms.py's table and every row and column class; heads = 1 through the new entry points
 against flex_attention / flex_attention_backward bit for bit; against H single-head calls on a strided plan; head isolation; the output
 invariants (dP = NULL, subsets of the gradients, run to run, a captured graph); refusals; a row-range shard; and
 SparseOperator.attention(..., heads=H) with its gradients against a float64 torch evaluation.
@@ -13,6 +13,7 @@ import pytest
 
 import flex_amd
 import multihead_attention_ref as mh
+from attention_forms import HEADS_PAIRS as PAIRS
 import test_gpu_attention as composition
 from backward_ref import _directed
 from flex_amd import binding
@@ -29,7 +30,6 @@ GRAPHS = {
     "directed_empty": lambda: _directed(250, 260, seed=7),
     "long_rows": long_rows_graph,
 }
-PAIRS = [(8, 2), (16, 4), (32, 4), (48, 3), (64, 4), (96, 3), (128, 2), (128, 8), (256, 4), (512, 4), (1024, 4), (1024, 64)]
 CASES = [(name, k, H) for k, H in PAIRS for name in (sorted(GRAPHS) if k < 256 else ["thresholds", "thresholds_lifted"])]
 SENTINEL = -12345.5
 SCALE = 0.25

@@ -1,10 +1,13 @@
 """flex_spmm_bf16 on the GPU (include/flex_spmm.h, FLEX_PLAN_BF16): every element of C against float64 within the bound
 of tests/spmm_bf16_ref.py on every form of spmm_flat_bf16_kernel and spmm_fixup_bf16_kernel, bit-identical results where the fp32
-engine promises them, the leading dimensions, the other plan flags, the guards, SparseOperator(..., bf16=True) and 64-bit addressing.
+engine promises them, the leading dimensions, the other plan flags, the guards, SparseOperator(..., bf16=True) and 64-bit addressing at
+every tile width.  The cases are tests/spmm_bf16_ref.py's and tests/attention_forms.py's, which tests/test_attention_routes.py holds to
+the kernels they launch.
 Every test prints the worst err / bound it saw (pytest -s)."""
 import numpy as np
 import pytest
 
+import attention_forms as forms
 import f64ref
 import flex_amd
 import spmm_bf16_ref as ref
@@ -13,7 +16,7 @@ from flex_amd import Plan
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-SPLIT = {"long_row": 24, "piece_records": 16}
+SPLIT = forms.SPMM_BF16_SPLIT
 
 
 def dev_bf16(x):
@@ -244,24 +247,58 @@ def test_7_sparse_operator_forward_and_backward(k):
 
 # ---- 8. 64-bit addressing
 
-def test_8_rows_of_b_past_4_gib():
-    """n x ldb x 2 bytes just above 4 GiB: the plan keeps column ids and the kernel forms 64-bit row addresses (OFF32 false, G = 16).
-    Rows of B at and above the 4 GiB mark are used together with their aliases 4 GiB below (what a wrapped 32-bit offset would read);
-    every row the scenario does not use is NaN."""
-    k, ldb, n_big = 128, 1 << 15, (1 << 16) + 8
-    a, B = _square_case(k)
-    rest = np.unique(np.linspace(8, (1 << 16) - 1, a.n - 16).astype(np.int64))
-    assert len(rest) == a.n - 16
-    cmap = np.concatenate([(1 << 16) + np.arange(8), np.arange(8), rest])  # column c of the scenario reads row cmap[c] of the large B
-    a_big = f64ref.embed_cols(a, cmap, n_big)
-    p = Plan(a_big, k, ldb=ldb, tuning={"lanes_per_nz": 16}, bf16=True)
-    assert p.info()["lanes_per_nz"] == 16 and int(p.records()[:, 0].max()) == n_big - 1  # column ids, not byte offsets
+@pytest.fixture(scope="module")
+def big_b():
+    """n = 2^16 + 8 rows of 2^15 bf16, just above 4 GiB, every element NaN: made once; a test fills the rows it uses and puts NaN back."""
+    n_big, ldb = forms.WIDE64_N, forms.WIDE64_LDB
     try:
         big = torch.full((n_big * ldb,), float("nan"), dtype=torch.bfloat16, device="cuda")
     except RuntimeError as e:  # torch.OutOfMemoryError is one
         pytest.skip(f"no room for a B of {n_big * ldb * 2 / 2 ** 30:.2f} GiB: {e}")
-    big.view(n_big, ldb)[torch.from_numpy(cmap).cuda(), :k] = dev_bf16(B)
-    C = torch.empty((a.m, k), dtype=torch.bfloat16, device="cuda")
-    p.spmm_bf16(big.data_ptr(), C.data_ptr(), torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    accept(a, B, bits_of(C), "B past 4 GiB, k128 G16")
+    yield big.view(n_big, ldb)
+    del big
+
+
+def _run_on_big_b(p, big_b, cmap, B, m):
+    """C bits of p on the large B with row cmap[c] holding row c of B; the rows are NaN again afterwards."""
+    k, rows = B.shape[1], torch.from_numpy(cmap).cuda()
+    big_b[rows, :k] = dev_bf16(B)
+    try:
+        C = torch.empty((m, k), dtype=torch.bfloat16, device="cuda")
+        p.spmm_bf16(big_b.data_ptr(), C.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+    finally:
+        big_b[rows, :k] = float("nan")
+    return bits_of(C)
+
+
+def test_8_rows_of_b_past_4_gib(big_b):
+    """n x ldb x 2 bytes just above 4 GiB: the plan keeps column ids and the kernel forms 64-bit row addresses (OFF32 false, G = 16).
+    Rows of B at and above the 4 GiB mark are used together with their aliases 4 GiB below (what a wrapped 32-bit offset would read);
+    every row the scenario does not use is NaN."""
+    k, ldb, n_big = 128, forms.WIDE64_LDB, forms.WIDE64_N
+    assert (ldb, n_big) == (1 << 15, (1 << 16) + 8)
+    a, B = _square_case(k)
+    cmap = forms.wide64_map(a.n)  # column c of the scenario reads row cmap[c] of the large B
+    assert np.array_equal(cmap[:16], np.concatenate([(1 << 16) + np.arange(8), np.arange(8)])) and len(np.unique(cmap)) == a.n
+    a_big = f64ref.embed_cols(a, cmap, n_big)
+    p = Plan(a_big, k, ldb=ldb, tuning={"lanes_per_nz": 16}, bf16=True)
+    assert p.info()["lanes_per_nz"] == 16 and int(p.records()[:, 0].max()) == n_big - 1  # column ids, not byte offsets
+    accept(a, B, _run_on_big_b(p, big_b, cmap, B, a.m), "B past 4 GiB, k128 G16")
+
+
+@pytest.mark.parametrize("c", forms.SPMM_BF16_WIDE64_CASES, ids=forms.case_id)
+def test_8_rows_of_b_past_4_gib_at_every_tile_width(big_b, c):
+    """spmm_flat_bf16_kernel<G, false, ...> for every G, on the same construction.  "split": f64ref's scenario cut into pieces, so that
+    the pieces and spmm_fixup_bf16_kernel run on this route; "bundle": rows of 3 entries, whose bundles store their rows of C from here."""
+    a, B, a_big, cmap, tn = forms.wide64_case(c)
+    k, G = c["k"], c["G"]
+    p = Plan(a_big, k, ldb=forms.WIDE64_LDB, tuning=tn, bf16=True)
+    i = p.info()
+    assert i["lanes_per_nz"] == G and int(p.records()[:, 0].max()) == forms.WIDE64_N - 1  # the forced tile; column ids, not byte offsets
+    if c["wide64"] == "split":
+        assert i["n_partials"] > 0 and i["n_split_rows"] >= 1
+    else:
+        assert i["n_bundles"] > 0 and i["n_partials"] == 0
+    accept(a, B, _run_on_big_b(p, big_b, cmap, B, a.m),
+           f"B past 4 GiB, {c['wide64']} k{k} G{G} (bundles {i['n_bundles']}, partials {i['n_partials']})")

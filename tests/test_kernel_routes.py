@@ -10,7 +10,10 @@ that libflex_spmm.so ships must be declared by some route, so a new instantiatio
 The kernels of flex::values and flex::softmax (the value refresh, the SDDMM, the edge softmax) get the same treatment through the cases of
 tests/values_marks.py, which tests/test_gpu_values_address_limits.py runs at the 2 and 4 GiB marks: every case is launched on the host
 simulator, whose stand-ins pick the instantiation by the library's own rules (internal.h: sddmm_pick, refresh_passes, softmax_vec), every
-shipped instantiation needs a case, and numpy models of the addressing faults those cases target fail the checkers they use."""
+shipped instantiation needs a case, and numpy models of the addressing faults those cases target fail the checkers they use.
+
+The kernels of flex::attention (gat:: included) and flex::spmm_bf16 -- the fused attention in all its forms and the bf16 SpMM -- are
+outside both censuses here; tests/test_attention_routes.py holds them to the cases of tests/attention_forms.py by the same rule."""
 import os
 import shutil
 import subprocess
