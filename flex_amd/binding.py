@@ -256,8 +256,9 @@ def lib():
 
 def _values_fn(name: str):
     """flex_plan_set_values / flex_sddmm / flex_edge_softmax / flex_edge_softmax_backward / flex_attention / flex_attention_backward and the
-    two multi-head, the two bf16 and the two GAT calls and flex_spmm_bf16, looked up at first use and not when the library loads: a host-only build without the kernel files does not define them (tests/hostsim has stand-ins that only log which
-    kernel the real ones would launch)."""
+    two multi-head, the two bf16 and the two GAT calls and flex_spmm_bf16, looked up at first use and not when the library loads: a host-only build without the kernel files does not have to define them.  tests/hostsim
+    defines them all: the attention calls are the library's own entry points (csrc/attention_entry.h) on stand-in launchers that only log which
+    kernel the real ones would launch, the others are stand-ins that log the same way."""
     L = lib()
     f = getattr(L, name)
     if f.argtypes is None:
@@ -686,13 +687,17 @@ class Plan:
         else:
             _check(_values_fn("flex_attention_heads")(self._h, heads, dQ_ptr, dK_ptr, dV_ptr, scale, dOut_ptr, dP_ptr, stream), "flex_attention_heads")
 
-    def _edge_arrays(self, heads, *ts):
+    def _head_edge_arrays(self, heads, *ts):
+        """The edge arrays of the per-head calls (heads, bf16, bias and GAT): float32 cuda [nnz, heads], heads = 1 included."""
         import torch
-        if heads == 1:
-            self._edge_vectors(*ts)
-            return
         for t in ts:
             assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (self.src_nnz, heads), "float32 cuda [nnz, heads]"
+
+    def _edge_arrays(self, heads, *ts):
+        if heads == 1:
+            self._edge_vectors(*ts)
+        else:
+            self._head_edge_arrays(heads, *ts)
 
     def attention(self, Q, K, V, scale: float, out=None, p=None, heads: int = 1):
         """flex_attention: out [m, k] = sum over each row's entries of alpha V[col], alpha = the softmax over the row of
@@ -760,11 +765,6 @@ class Plan:
         """flex_attention_bf16: Q, K, V and Out are bf16 rows, dP (optional) is nnz x H floats, entry-major."""
         _check(_values_fn("flex_attention_bf16")(self._h, heads, dQ_ptr, dK_ptr, dV_ptr, scale, dOut_ptr, dP_ptr, stream), "flex_attention_bf16")
 
-    def _bf16_edge_arrays(self, heads, *ts):
-        import torch
-        for t in ts:
-            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (self.src_nnz, heads), "float32 cuda [nnz, heads]"
-
     def attention_bf16(self, Q, K, V, scale: float, heads: int = 1, out=None, p=None):
         """flex_attention_bf16: attention(..., heads=heads) on torch.bfloat16 cuda tensors Q [m, k], K, V [n, k]; scores, softmax and sums
         in float32, out [m, k] bfloat16 rounded once at its store.  p (optional): a float32 cuda tensor [a.nnz, heads] that receives alpha,
@@ -777,7 +777,7 @@ class Plan:
             out = (torch.empty if i["nnz"] else torch.zeros)((i["m"], i["k"]), dtype=torch.bfloat16, device=Q.device)
         assert out.is_cuda and out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (i["m"], i["k"])
         if p is not None:
-            self._bf16_edge_arrays(heads, p)
+            self._head_edge_arrays(heads, p)
         self.attention_bf16_ptr(Q.data_ptr(), K.data_ptr(), V.data_ptr(), scale, out.data_ptr(), None if p is None else p.data_ptr(),
                                 torch.cuda.current_stream(Q.device).cuda_stream, heads=heads)
         return out
@@ -799,7 +799,7 @@ class Plan:
             assert t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous() and tuple(t.shape) == (rows, i["k"]), "bfloat16 cuda [rows, k]"
         if work is None:
             work = torch.empty((self.src_nnz, heads), dtype=torch.float32, device=Q.device)
-        self._bf16_edge_arrays(heads, p, work)
+        self._head_edge_arrays(heads, p, work)
         outs = []
         for wanted, t, rows in zip(want, (grad_q, grad_k, grad_v), (i["m"], i["n"], i["n"])):
             if wanted and t is None:  # every row is written, except by a plan without entries, which launches nothing
@@ -845,12 +845,12 @@ class Plan:
             assert t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == (rows, i["k"]), f"{dtype} cuda [rows, k]"
         if heads == 1 and bias.dim() == 1:
             bias = bias.unsqueeze(1)
-        self._bf16_edge_arrays(heads, bias)
+        self._head_edge_arrays(heads, bias)
         if out is None:  # every row is written, except by a plan without entries, which launches nothing
             out = (torch.empty if i["nnz"] else torch.zeros)((i["m"], i["k"]), dtype=dtype, device=Q.device)
         assert out.is_cuda and out.dtype == dtype and out.is_contiguous() and tuple(out.shape) == (i["m"], i["k"])
         if p is not None:
-            self._bf16_edge_arrays(heads, p)
+            self._head_edge_arrays(heads, p)
         run(Q.data_ptr(), K.data_ptr(), V.data_ptr(), bias.data_ptr(), scale, out.data_ptr(), None if p is None else p.data_ptr(),
             torch.cuda.current_stream(Q.device).cuda_stream, heads=heads)
         return out
@@ -862,7 +862,7 @@ class Plan:
             assert t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == (rows, i["k"]), f"{dtype} cuda [rows, k]"
         if work is None:
             work = torch.empty((self.src_nnz, heads), dtype=torch.float32, device=Q.device)
-        self._bf16_edge_arrays(heads, p, work)
+        self._head_edge_arrays(heads, p, work)
         shapes = ((i["m"], i["k"]), (i["n"], i["k"]), (i["n"], i["k"]), (self.src_nnz, heads))
         outs = []
         for wanted, t, shape, dt in zip(want, grads, shapes, (dtype, dtype, dtype, torch.float32)):
@@ -922,11 +922,6 @@ class Plan:
             assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (rows, heads), "float32 cuda [rows, heads]"
         return heads
 
-    def _gat_edge_arrays(self, heads, *ts):
-        import torch
-        for t in ts:
-            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (self.src_nnz, heads), "float32 cuda [nnz, heads]"
-
     def gat_attention(self, el, er, V, slope: float = 0.2, out=None, p=None):
         """flex_gat_attention: out [m, k] = sum over each row's entries of alpha V[col] per head, alpha = the softmax over the row of
         leaky_relu(el[row, h] + er[col, h], slope), in one launch.  el: [m, H], er: [n, H] (H = el.shape[1] heads of k / H columns),
@@ -940,7 +935,7 @@ class Plan:
             out = (torch.empty if i["nnz"] else torch.zeros)((i["m"], i["k"]), dtype=torch.float32, device=V.device)
         assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (i["m"], i["k"])
         if p is not None:
-            self._gat_edge_arrays(heads, p)
+            self._head_edge_arrays(heads, p)
         self.gat_attention_ptr(heads, el.data_ptr(), er.data_ptr(), V.data_ptr(), slope, out.data_ptr(), None if p is None else p.data_ptr(),
                                torch.cuda.current_stream(V.device).cuda_stream)
         return out
@@ -963,7 +958,7 @@ class Plan:
             assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (rows, i["k"])
         if work is None:
             work = torch.empty((self.src_nnz, heads), dtype=torch.float32, device=V.device)
-        self._gat_edge_arrays(heads, p, work)
+        self._head_edge_arrays(heads, p, work)
         outs = []
         for wanted, t, shape in zip(want, (grad_el, grad_er, grad_v), ((i["m"], heads), (i["n"], heads), (i["n"], i["k"]))):
             if wanted and t is None:  # every row is written, except by a plan without entries, which launches nothing

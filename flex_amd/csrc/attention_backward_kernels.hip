@@ -294,50 +294,27 @@ __global__ __launch_bounds__(256) void attention_columns_backward(ColumnView v, 
     }
 }
 
-struct Operands {
-    const float *Q, *K, *V, *P, *G;
-    float scale;
-    float *GQ, *GK, *GV, *Work;
-};
-
-}  // namespace attention
-}  // namespace flex
-
-using namespace flex;
-
-extern "C" {
-
-int flex_attention_backward(const flex_plan *p, const float *dQ, const float *dK, const float *dV, const float *dP, const float *dGradOut, float scale,
-                            float *dGradQ, float *dGradK, float *dGradV, float *dWork, flex_stream_t stream) {
-    if (!p || !p->ab_ok) return FLEX_ERR_INVALID;
-    if (!std::isfinite(scale) || !(scale > 0.f)) return FLEX_ERR_INVALID;
-    if (p->at_entries == 0) return FLEX_OK;
-    if (!dQ || !dK || !dV || !dP || !dGradOut || !dWork || dWork == dP) return FLEX_ERR_INVALID;
-    if (p->k > 4 * 64 * kAtMaxSlabs) return FLEX_ERR_UNSUPPORTED;
-    if (!dGradQ && !dGradK && !dGradV) return FLEX_OK;
-    // the forward's rule over every row operand of the two launches (a NULL output is aligned)
-    AttentionPick pick = attention_pick(p->k, p->ldb, p->ldc, dQ, dK, dV, dGradOut);
-    pick.vec4 = pick.vec4 && attention_pick(p->k, p->ldb, p->ldc, dGradQ, dGradK, dGradV, nullptr).vec4;
-    const DeviceScope on(p->device);
-    FLEX_HIP_TRY(on.error());
-    const attention::View rv = attention::row_view(p);
-    const attention::ColumnView cv = attention::column_view(p);
-    const dim3 rgrid = attention::launch_grid(rv), cgrid = attention::launch_grid(cv), block(64 * kWavesPerBlock);
-    const attention::Operands o{dQ, dK, dV, dP, dGradOut, scale, dGradQ, dGradK, dGradV, dWork};
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    attention::dispatch(pick, [&](auto W, auto NS) {
-        using namespace attention;
-        if (o.GQ || o.GK) {
-            if (pick.vec4) hipLaunchKernelGGL((attention_rows_backward<W(), NS(), true>), rgrid, block, 0, s, rv, o.K, o.V, o.P, o.G, o.scale, o.GQ, o.Work);
-            else hipLaunchKernelGGL((attention_rows_backward<W(), NS(), false>), rgrid, block, 0, s, rv, o.K, o.V, o.P, o.G, o.scale, o.GQ, o.Work);
-        }
-        if (o.GK || o.GV) {
-            if (pick.vec4) hipLaunchKernelGGL((attention_columns_backward<W(), NS(), true>), cgrid, block, 0, s, cv, o.Q, o.G, o.P, o.Work, o.GK, o.GV);
-            else hipLaunchKernelGGL((attention_columns_backward<W(), NS(), false>), cgrid, block, 0, s, cv, o.Q, o.G, o.P, o.Work, o.GK, o.GV);
-        }
+int launch_rows_backward(const flex_plan *p, const AttentionPick &pick, const float *K, const float *V, const float *P, const float *G, float scale,
+                         float *GQ, float *Work, hipStream_t s) {
+    const View rv = row_view(p);
+    const dim3 rgrid = launch_grid(rv), block(64 * kWavesPerBlock);
+    dispatch(pick, [&](auto W, auto NS) {
+        if (pick.vec4) hipLaunchKernelGGL((attention_rows_backward<W(), NS(), true>), rgrid, block, 0, s, rv, K, V, P, G, scale, GQ, Work);
+        else hipLaunchKernelGGL((attention_rows_backward<W(), NS(), false>), rgrid, block, 0, s, rv, K, V, P, G, scale, GQ, Work);
     });
-    FLEX_HIP_TRY(hipGetLastError());
     return FLEX_OK;
 }
 
-}  // extern "C"
+int launch_columns_backward(const flex_plan *p, const AttentionPick &pick, const float *Q, const float *G, const float *P, const float *DS, float *GK,
+                            float *GV, hipStream_t s) {
+    const ColumnView cv = column_view(p);
+    const dim3 cgrid = launch_grid(cv), block(64 * kWavesPerBlock);
+    dispatch(pick, [&](auto W, auto NS) {
+        if (pick.vec4) hipLaunchKernelGGL((attention_columns_backward<W(), NS(), true>), cgrid, block, 0, s, cv, Q, G, P, DS, GK, GV);
+        else hipLaunchKernelGGL((attention_columns_backward<W(), NS(), false>), cgrid, block, 0, s, cv, Q, G, P, DS, GK, GV);
+    });
+    return FLEX_OK;
+}
+
+}  // namespace attention
+}  // namespace flex

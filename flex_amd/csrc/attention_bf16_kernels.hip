@@ -11,9 +11,10 @@
 // -ffp-contract=on, the fp32 value that is rounded at the store -- and every element of dP and dWork -- has the bits that
 // flex_attention_heads and flex_attention_heads_backward give on the widened operands.  heads = 1 runs here as well (there is no
 // generic form to forward to), so d = k is then a power of two.  Only the 8-byte form is built (the host refuses the rest).
+// This file holds the kernels and their three launchers (internal.h, launch_heads_* on flex_bf16 rows); the entry points, with the argument
+// checks, the alignment rule (internal.h, pick_rows) and the head split (head_split_lg), are attention_entry.h's.
 #include <cmath>
 #include <cstdint>
-#include <initializer_list>
 
 #include "attention_heads_device.h"
 
@@ -47,87 +48,36 @@ __global__ __launch_bounds__(256) void attention_bf16_columns_backward(ColumnVie
 
 // ---- launches
 
-// W and NS of the plan's k, and whether the 8-byte form serves: k and both strides multiples of four elements, every row operand 8-byte
-// aligned (a NULL output is aligned)
-inline AttentionPick pick_bf16(const flex_plan *p, std::initializer_list<const void *> rows) {
-    AttentionPick pick = attention_pick(p->k, p->ldb, p->ldc, nullptr, nullptr, nullptr, nullptr);
-    for (const void *r : rows) pick.vec4 = pick.vec4 && reinterpret_cast<uintptr_t>(r) % 8 == 0;
-    return pick;
-}
-
-struct Bf16Operands {
-    const flex_bf16 *Q, *K, *V;
-    const float *P;
-    const flex_bf16 *G;
-    float scale;
-    flex_bf16 *GQ, *GK, *GV;
-    float *Work;
-};
-
-void launch_columns_backward(const flex_plan *p, const AttentionPick &pick, const HeadSplit &hs, const flex_bf16 *Q, const flex_bf16 *G, const float *P,
-                             const float *DS, flex_bf16 *GK, flex_bf16 *GV, hipStream_t s) {
+int launch_heads_columns_backward(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const flex_bf16 *Q, const flex_bf16 *G, const float *P,
+                                  const float *DS, flex_bf16 *GK, flex_bf16 *GV, hipStream_t s) {
     const ColumnView cv = column_view(p);
+    const HeadSplit hs{heads, lg};
     const dim3 cgrid = launch_grid(cv), block(64 * kWavesPerBlock);
     dispatch(pick, [&](auto W, auto NS) {
         hipLaunchKernelGGL((attention_bf16_columns_backward<W(), NS()>), cgrid, block, 0, s, cv, hs, Q, G, P, DS, GK, GV);
     });
+    return FLEX_OK;
+}
+
+int launch_heads_rows(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const flex_bf16 *Q, const flex_bf16 *K, const flex_bf16 *V, float scale,
+                      flex_bf16 *Out, float *P, hipStream_t s) {
+    const View v = row_view(p);
+    const HeadSplit hs{heads, lg};
+    const dim3 grid = launch_grid(v), block(64 * kWavesPerBlock);
+    dispatch(pick, [&](auto W, auto NS) { hipLaunchKernelGGL((attention_bf16_rows<W(), NS()>), grid, block, 0, s, v, hs, Q, K, V, scale, Out, P); });
+    return FLEX_OK;
+}
+
+int launch_heads_rows_backward(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const flex_bf16 *K, const flex_bf16 *V, const float *P,
+                               const flex_bf16 *G, float scale, flex_bf16 *GQ, float *Work, hipStream_t s) {
+    const View rv = row_view(p);
+    const HeadSplit hs{heads, lg};
+    const dim3 rgrid = launch_grid(rv), block(64 * kWavesPerBlock);
+    dispatch(pick, [&](auto W, auto NS) {
+        hipLaunchKernelGGL((attention_bf16_rows_backward<W(), NS()>), rgrid, block, 0, s, rv, hs, K, V, P, G, scale, GQ, Work);
+    });
+    return FLEX_OK;
 }
 
 }  // namespace attention
 }  // namespace flex
-
-using namespace flex;
-
-extern "C" {
-
-int flex_attention_bf16(const flex_plan *p, int heads, const flex_bf16 *dQ, const flex_bf16 *dK, const flex_bf16 *dV, float scale, flex_bf16 *dOut,
-                        float *dP, flex_stream_t stream) {
-    if (!p || !p->at_ok || heads < 1) return FLEX_ERR_INVALID;
-    if (!std::isfinite(scale) || !(scale > 0.f)) return FLEX_ERR_INVALID;
-    attention::HeadSplit hs;
-    if (const int rc = attention::split_of(p->k, heads, &hs)) return rc;
-    if (p->at_entries == 0) return FLEX_OK;
-    if (!dQ || !dK || !dV || !dOut) return FLEX_ERR_INVALID;
-    const AttentionPick pick = attention::pick_bf16(p, {dQ, dK, dV, dOut});
-    if (!pick.vec4) return FLEX_ERR_UNSUPPORTED;
-    const DeviceScope on(p->device);
-    FLEX_HIP_TRY(on.error());
-    const attention::View v = attention::row_view(p);
-    const dim3 grid = attention::launch_grid(v), block(64 * kWavesPerBlock);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    attention::dispatch(pick, [&](auto W, auto NS) {
-        hipLaunchKernelGGL((attention::attention_bf16_rows<W(), NS()>), grid, block, 0, s, v, hs, dQ, dK, dV, scale, dOut, dP);
-    });
-    FLEX_HIP_TRY(hipGetLastError());
-    return FLEX_OK;
-}
-
-int flex_attention_bf16_backward(const flex_plan *p, int heads, const flex_bf16 *dQ, const flex_bf16 *dK, const flex_bf16 *dV, const float *dP,
-                                 const flex_bf16 *dGradOut, float scale, flex_bf16 *dGradQ, flex_bf16 *dGradK, flex_bf16 *dGradV, float *dWork,
-                                 flex_stream_t stream) {
-    if (!p || !p->ab_ok || heads < 1) return FLEX_ERR_INVALID;
-    if (!std::isfinite(scale) || !(scale > 0.f)) return FLEX_ERR_INVALID;
-    attention::HeadSplit hs;
-    if (const int rc = attention::split_of(p->k, heads, &hs)) return rc;
-    if (p->at_entries == 0) return FLEX_OK;
-    if (!dQ || !dK || !dV || !dP || !dGradOut || !dWork || dWork == dP) return FLEX_ERR_INVALID;
-    const AttentionPick pick = attention::pick_bf16(p, {dQ, dK, dV, dGradOut, dGradQ, dGradK, dGradV});
-    if (!pick.vec4) return FLEX_ERR_UNSUPPORTED;
-    if (!dGradQ && !dGradK && !dGradV) return FLEX_OK;
-    const DeviceScope on(p->device);
-    FLEX_HIP_TRY(on.error());
-    const attention::View rv = attention::row_view(p);
-    const attention::ColumnView cv = attention::column_view(p);
-    const dim3 rgrid = attention::launch_grid(rv), cgrid = attention::launch_grid(cv), block(64 * kWavesPerBlock);
-    const attention::Bf16Operands o{dQ, dK, dV, dP, dGradOut, scale, dGradQ, dGradK, dGradV, dWork};
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    attention::dispatch(pick, [&](auto W, auto NS) {
-        using namespace attention;
-        if (o.GQ || o.GK) hipLaunchKernelGGL((attention_bf16_rows_backward<W(), NS()>), rgrid, block, 0, s, rv, hs, o.K, o.V, o.P, o.G, o.scale, o.GQ, o.Work);
-        if (o.GK || o.GV) hipLaunchKernelGGL((attention_bf16_columns_backward<W(), NS()>), cgrid, block, 0, s, cv, hs, o.Q, o.G, o.P, o.Work, o.GK, o.GV);
-    });
-    FLEX_HIP_TRY(hipGetLastError());
-    return FLEX_OK;
-}
-
-}  // extern "C"

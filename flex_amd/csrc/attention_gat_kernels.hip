@@ -7,8 +7,8 @@
 // place_of, W = sddmm_lanes(k) lanes per slot, four entries per pass, four columns per lane and slab, the XCD remap, State<1> per lane
 // and slab, merge, write_row, the mask and poison logic, ColumnView for the second backward launch.  A head is HW = d / 4 whole lanes
 // of one slab; HW is a launch argument (its log2), so there is one instantiation per (W, NS).  The head split (HeadSplit, HeadLane,
-// LaneHeads, head_total, merge_slots_heads, HeadsShared, sum_slot_scalars) is attention_device.h's, split_of attention_host.h's; namespace
-// gat holds what is GAT's alone.  What differs from the dot-product heads:
+// LaneHeads, head_total, merge_slots_heads, HeadsShared, sum_slot_scalars) is attention_device.h's, its rule internal.h's head_split_lg;
+// namespace gat holds what is GAT's alone, and the entry points are attention_entry.h's.  What differs from the dot-product heads:
 //   forward        no K gather and no reduction across lanes for a score: per row a lane loads el[r, head] once, per entry
 //                  er[src, head] -- one float, the lanes of a head reading the same address, the H heads of an entry one contiguous run --
 //                  together with the four V gathers of the pass; scale = 1
@@ -445,69 +445,38 @@ __global__ __launch_bounds__(256) void gat_columns_backward(ColumnView v, HeadSp
     }
 }
 
+}  // namespace gat
+
 // ---- launches
 
-struct Operands {
-    const float *El, *Er, *V, *P, *G;
-    float slope;
-    float *GEl, *GEr, *GV, *Work;
-};
+int launch_gat_rows(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const float *El, const float *Er, const float *V, float slope,
+                    float *Out, float *P, hipStream_t s) {
+    const View v = row_view(p);
+    const HeadSplit hs{heads, lg};
+    const dim3 grid = launch_grid(v), block(64 * kWavesPerBlock);
+    dispatch(pick, [&](auto W, auto NS) { hipLaunchKernelGGL((gat::gat_rows<W(), NS()>), grid, block, 0, s, v, hs, El, Er, V, slope, Out, P); });
+    return FLEX_OK;
+}
 
-static bool slope_ok(float slope) { return std::isfinite(slope) && slope > 0.f && slope <= 1.f; }
+int launch_gat_rows_backward(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const float *El, const float *Er, const float *V,
+                             const float *P, const float *G, float slope, float *GEl, float *Work, hipStream_t s) {
+    const View rv = row_view(p);
+    const HeadSplit hs{heads, lg};
+    const dim3 rgrid = launch_grid(rv), block(64 * kWavesPerBlock);
+    dispatch(pick, [&](auto W, auto NS) {
+        hipLaunchKernelGGL((gat::gat_rows_backward<W(), NS()>), rgrid, block, 0, s, rv, hs, El, Er, V, P, G, slope, GEl, Work);
+    });
+    return FLEX_OK;
+}
 
-}  // namespace gat
+int launch_gat_columns_backward(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const float *G, const float *P, const float *DX,
+                                float *GEr, float *GV, hipStream_t s) {
+    const ColumnView cv = column_view(p);
+    const HeadSplit hs{heads, lg};
+    const dim3 cgrid = launch_grid(cv), block(64 * kWavesPerBlock);
+    dispatch(pick, [&](auto W, auto NS) { hipLaunchKernelGGL((gat::gat_columns_backward<W(), NS()>), cgrid, block, 0, s, cv, hs, G, P, DX, GEr, GV); });
+    return FLEX_OK;
+}
+
 }  // namespace attention
 }  // namespace flex
-
-using namespace flex;
-
-extern "C" {
-
-int flex_gat_attention(const flex_plan *p, int heads, const float *dEl, const float *dEr, const float *dV, float slope, float *dOut, float *dP,
-                       flex_stream_t stream) {
-    namespace gat = attention::gat;
-    if (!p || !p->at_ok || heads < 1 || !gat::slope_ok(slope)) return FLEX_ERR_INVALID;
-    attention::HeadSplit hs;
-    if (const int rc = attention::split_of(p->k, heads, &hs)) return rc;
-    if (p->at_entries == 0) return FLEX_OK;
-    if (!dEl || !dEr || !dV || !dOut) return FLEX_ERR_INVALID;
-    const AttentionPick pick = attention_pick(p->k, p->ldb, p->ldc, dV, dOut, nullptr, nullptr);
-    if (!pick.vec4) return FLEX_ERR_UNSUPPORTED;
-    const DeviceScope on(p->device);
-    FLEX_HIP_TRY(on.error());
-    const attention::View v = attention::row_view(p);
-    const dim3 grid = attention::launch_grid(v), block(64 * kWavesPerBlock);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    attention::dispatch(pick, [&](auto W, auto NS) { hipLaunchKernelGGL((gat::gat_rows<W(), NS()>), grid, block, 0, s, v, hs, dEl, dEr, dV, slope, dOut, dP); });
-    FLEX_HIP_TRY(hipGetLastError());
-    return FLEX_OK;
-}
-
-int flex_gat_attention_backward(const flex_plan *p, int heads, const float *dEl, const float *dEr, const float *dV, const float *dP,
-                                const float *dGradOut, float slope, float *dGradEl, float *dGradEr, float *dGradV, float *dWork, flex_stream_t stream) {
-    namespace gat = attention::gat;
-    if (!p || !p->ab_ok || heads < 1 || !gat::slope_ok(slope)) return FLEX_ERR_INVALID;
-    attention::HeadSplit hs;
-    if (const int rc = attention::split_of(p->k, heads, &hs)) return rc;
-    if (p->at_entries == 0) return FLEX_OK;
-    if (!dEl || !dEr || !dV || !dP || !dGradOut || !dWork || dWork == dP) return FLEX_ERR_INVALID;
-    // the forward's rule over every row operand of the two launches (a NULL output is aligned)
-    const AttentionPick pick = attention_pick(p->k, p->ldb, p->ldc, dV, dGradOut, dGradV, nullptr);
-    if (!pick.vec4) return FLEX_ERR_UNSUPPORTED;
-    if (!dGradEl && !dGradEr && !dGradV) return FLEX_OK;
-    const DeviceScope on(p->device);
-    FLEX_HIP_TRY(on.error());
-    const attention::View rv = attention::row_view(p);
-    const attention::ColumnView cv = attention::column_view(p);
-    const dim3 rgrid = attention::launch_grid(rv), cgrid = attention::launch_grid(cv), block(64 * kWavesPerBlock);
-    const gat::Operands o{dEl, dEr, dV, dP, dGradOut, slope, dGradEl, dGradEr, dGradV, dWork};
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    attention::dispatch(pick, [&](auto W, auto NS) {
-        if (o.GEl || o.GEr) hipLaunchKernelGGL((gat::gat_rows_backward<W(), NS()>), rgrid, block, 0, s, rv, hs, o.El, o.Er, o.V, o.P, o.G, o.slope, o.GEl, o.Work);
-        if (o.GEr || o.GV) hipLaunchKernelGGL((gat::gat_columns_backward<W(), NS()>), cgrid, block, 0, s, cv, hs, o.G, o.P, o.Work, o.GEr, o.GV);
-    });
-    FLEX_HIP_TRY(hipGetLastError());
-    return FLEX_OK;
-}
-
-}  // extern "C"

@@ -7,7 +7,7 @@
 // the same walk and the same fp32 expressions.  The edge arrays (dP, dWork) and LDS are fp32 for every E.
 //
 // The walk is the single-head kernels' (attention_kernels.hip, attention_backward_kernels.hip; attention_device.h, which also holds the
-// head split: HeadSplit, HeadLane, head_total, merge_slots_heads, HeadsShared; split_of is in attention_host.h): the same view, items,
+// head split: HeadSplit, HeadLane, head_total, merge_slots_heads, HeadsShared; its rule is internal.h's head_split_lg): the same view, items,
 // groups, slot / wave / block ownership, W = sddmm_lanes(k) lanes per slot, four entries per pass and four columns per lane and slab.
 // d is a power of two in [4, 256], so a head is HW = d / 4 whole lanes of one slab: the lane that holds columns c .. c + 3 belongs to
 // head c / d, and the lanes of a head are HW consecutive lanes that start at a multiple of HW.  HW is a launch argument (its log2),

@@ -1,5 +1,6 @@
-// attention_host.h -- what the entry points of the fused attention share on the host, after their argument checks: the two views of a
-// plan, the launch grid of a walk, the one list of the (W, NS) forms that are built, and the head split of the per-head entry points.
+// attention_host.h -- what the launchers of the fused attention (internal.h, flex::attention::launch_*; one body each in the
+// attention_*_kernels.hip files) share on the host: the two views of a plan, the launch grid of a walk and the one list of the (W, NS)
+// forms that are built.  The entry points, their argument checks and the head split are host code of their own (attention_entry.h).
 #pragma once
 #include <type_traits>
 
@@ -42,23 +43,6 @@ inline void dispatch(const AttentionPick &pick, F &&f) {
         default: f(integral_constant<int, 64>{}, integral_constant<int, 4>{}); break;
     }
 }
-
-// FLEX_OK and the split where heads (1 included) divides k into heads of d = 4 .. 256 columns, d a power of two: the rule is
-// internal.h's head_split_lg, which the launch log of tests/hostsim/shim.cpp shares
-inline int split_of(int k, int heads, HeadSplit *out) {
-    int lg = 0;
-    if (const int rc = head_split_lg(k, heads, &lg)) return rc;
-    *out = HeadSplit{heads, lg};
-    return FLEX_OK;
-}
-
-// The column launch of flex_attention_heads_backward (attention_heads_kernels.hip) and of flex_attention_bf16_backward
-// (attention_bf16_kernels.hip) on an ab_ok plan, for the entry points of another object that share it (attention_bias_kernels.hip): gK
-// and gV (either may be NULL) from p and ds.  The caller has checked the operands and holds the plan's device.
-void launch_columns_backward(const flex_plan *p, const AttentionPick &pick, const HeadSplit &hs, const float *Q, const float *G, const float *P,
-                             const float *DS, float *GK, float *GV, hipStream_t s);
-void launch_columns_backward(const flex_plan *p, const AttentionPick &pick, const HeadSplit &hs, const flex_bf16 *Q, const flex_bf16 *G, const float *P,
-                             const float *DS, flex_bf16 *GK, flex_bf16 *GV, hipStream_t s);
 
 }  // namespace attention
 }  // namespace flex

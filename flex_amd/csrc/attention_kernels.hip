@@ -7,7 +7,8 @@
 // the 16-byte and the generic form of every (W, NS): the cases are tests/attention_forms.py's, and tests/test_attention_routes.py holds
 // every instantiation of flex::attention to a case that launches it.
 // The view of the walk, the slot placement (place_of) and the helpers it shares with the other attention kernels: attention_device.h;
-// the view, the grid and the (W, NS) dispatch of the entry point: attention_host.h.
+// the view, the grid and the (W, NS) dispatch of the launcher: attention_host.h.  The entry points of all six attention files are host
+// code of their own, attention_entry.h, which this file includes at its end: it is their one translation unit in the library.
 //
 // Row-owned.  A SLOT of W lanes holds its Q row and its Out row (4 columns per lane and slab) in registers, with the running maximum m
 // and the running sum l of the row's terms exp(scale (s - m)).  Per pass the slot takes kAtPass = 4 consecutive entries: its first
@@ -198,31 +199,18 @@ __global__ __launch_bounds__(256) void attention_rows(View v, const float *__res
     }
 }
 
-}  // namespace attention
-}  // namespace flex
-
-using namespace flex;
-
-extern "C" {
-
-int flex_attention(const flex_plan *p, const float *dQ, const float *dK, const float *dV, float scale, float *dOut, float *dP, flex_stream_t stream) {
-    if (!p || !p->at_ok) return FLEX_ERR_INVALID;
-    if (!std::isfinite(scale) || !(scale > 0.f)) return FLEX_ERR_INVALID;
-    if (p->at_entries == 0) return FLEX_OK;
-    if (!dQ || !dK || !dV || !dOut) return FLEX_ERR_INVALID;
-    const AttentionPick pick = attention_pick(p->k, p->ldb, p->ldc, dQ, dK, dV, dOut);
-    if (p->k > 4 * 64 * kAtMaxSlabs) return FLEX_ERR_UNSUPPORTED;
-    const DeviceScope on(p->device);
-    FLEX_HIP_TRY(on.error());
-    const attention::View v = attention::row_view(p);
-    const dim3 grid = attention::launch_grid(v), block(64 * kWavesPerBlock);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    attention::dispatch(pick, [&](auto W, auto NS) {
-        if (pick.vec4) hipLaunchKernelGGL((attention::attention_rows<W(), NS(), true>), grid, block, 0, s, v, dQ, dK, dV, scale, dOut, dP);
-        else hipLaunchKernelGGL((attention::attention_rows<W(), NS(), false>), grid, block, 0, s, v, dQ, dK, dV, scale, dOut, dP);
+int launch_rows(const flex_plan *p, const AttentionPick &pick, const float *Q, const float *K, const float *V, float scale, float *Out, float *P,
+                hipStream_t s) {
+    const View v = row_view(p);
+    const dim3 grid = launch_grid(v), block(64 * kWavesPerBlock);
+    dispatch(pick, [&](auto W, auto NS) {
+        if (pick.vec4) hipLaunchKernelGGL((attention_rows<W(), NS(), true>), grid, block, 0, s, v, Q, K, V, scale, Out, P);
+        else hipLaunchKernelGGL((attention_rows<W(), NS(), false>), grid, block, 0, s, v, Q, K, V, scale, Out, P);
     });
-    FLEX_HIP_TRY(hipGetLastError());
     return FLEX_OK;
 }
 
-}  // extern "C"
+}  // namespace attention
+}  // namespace flex
+
+#include "attention_entry.h"  // the entry points of every attention file: this is their one translation unit in the library

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <initializer_list>
 #include <vector>
 
 #include "../../include/flex_spmm.h"
@@ -288,7 +289,16 @@ inline AttentionPick attention_pick(int k, int ldb, int ldc, const void *dQ, con
     const uintptr_t ptrs = reinterpret_cast<uintptr_t>(dQ) | reinterpret_cast<uintptr_t>(dK) | reinterpret_cast<uintptr_t>(dV) | reinterpret_cast<uintptr_t>(dOut);
     return AttentionPick{W, slabs <= 1 ? 1 : slabs == 2 ? 2 : 4, k % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0 && ptrs % 16 == 0};
 }
-// The head split of the per-head entry points (attention_host.h, split_of): FLEX_OK and lg, with d = k / heads = 4 << lg, where heads
+// The one alignment rule of the per-head entry points, for either element type: W and NS of k, the vector form where k and both leading
+// dimensions are multiples of four elements and every row operand is aligned to four elements (16 bytes of float, 8 of flex_bf16; a
+// NULL output is aligned).  On float rows it is attention_pick over the same operands.
+template <class E>
+inline AttentionPick pick_rows(int k, int ldb, int ldc, std::initializer_list<const void *> rows) {
+    AttentionPick pick = attention_pick(k, ldb, ldc, nullptr, nullptr, nullptr, nullptr);
+    for (const void *r : rows) pick.vec4 = pick.vec4 && reinterpret_cast<uintptr_t>(r) % (4 * sizeof(E)) == 0;
+    return pick;
+}
+// The head split of the per-head entry points (attention_entry.h): FLEX_OK and lg, with d = k / heads = 4 << lg, where heads
 // (1 included) divides k into heads of d = 4 .. 256 columns, d a power of two.  A host rule, as attention_pick.
 inline int head_split_lg(int k, int heads, int *lg_out) {
     if (k > 4 * 64 * kAtMaxSlabs || k % heads) return FLEX_ERR_UNSUPPORTED;
@@ -322,6 +332,46 @@ int kernel_attributes(int lanes_per_nz, bool off32, bool vec4, hipFuncAttributes
 int launch_gather_rows(float *dst, const float *src, const int32_t *idx, int64_t n, int k, hipStream_t s);
 int launch_tiles(const TileView &tv, bool off32, const float *dB, float *dC, int k, int ldb, int ldc, hipStream_t s);
 int launch_blocks(const BlockView &bv, const float *dB, float *dC, hipStream_t s, bool vec4 = true);
+
+// The launchers of the fused attention, one per kernel family and role (rows forward, rows backward, columns backward): what the entry
+// points of attention_entry.h call, and all that the host simulator replaces.  The caller has checked the operands, decided that the
+// launch is wanted and holds the plan's device; pick is the entry point's, (heads, lg) the head split of head_split_lg.
+namespace attention {
+// single head (attention_kernels.hip, attention_backward_kernels.hip): the 16-byte or the generic form by pick.vec4
+int launch_rows(const flex_plan *p, const AttentionPick &pick, const float *Q, const float *K, const float *V, float scale, float *Out, float *P,
+                hipStream_t s);
+int launch_rows_backward(const flex_plan *p, const AttentionPick &pick, const float *K, const float *V, const float *P, const float *G, float scale,
+                         float *GQ, float *Work, hipStream_t s);
+int launch_columns_backward(const flex_plan *p, const AttentionPick &pick, const float *Q, const float *G, const float *P, const float *DS, float *GK,
+                            float *GV, hipStream_t s);
+// per head, float rows (attention_heads_kernels.hip) and flex_bf16 rows (attention_bf16_kernels.hip)
+int launch_heads_rows(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const float *Q, const float *K, const float *V, float scale,
+                      float *Out, float *P, hipStream_t s);
+int launch_heads_rows(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const flex_bf16 *Q, const flex_bf16 *K, const flex_bf16 *V,
+                      float scale, flex_bf16 *Out, float *P, hipStream_t s);
+int launch_heads_rows_backward(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const float *K, const float *V, const float *P,
+                               const float *G, float scale, float *GQ, float *Work, hipStream_t s);
+int launch_heads_rows_backward(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const flex_bf16 *K, const flex_bf16 *V, const float *P,
+                               const flex_bf16 *G, float scale, flex_bf16 *GQ, float *Work, hipStream_t s);
+int launch_heads_columns_backward(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const float *Q, const float *G, const float *P,
+                                  const float *DS, float *GK, float *GV, hipStream_t s);
+int launch_heads_columns_backward(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const flex_bf16 *Q, const flex_bf16 *G,
+                                  const float *P, const float *DS, flex_bf16 *GK, flex_bf16 *GV, hipStream_t s);
+// per head with a bias, E = float or flex_bf16 (attention_bias_kernels.hip); the column launch is the unbiased one above
+template <class E>
+int launch_bias_rows(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const E *Q, const E *K, const E *V, const float *Bias, float scale,
+                     E *Out, float *P, hipStream_t s);
+template <class E>
+int launch_bias_rows_backward(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const E *K, const E *V, const float *P, const E *G,
+                              float scale, E *GQ, float *GB, float *Work, hipStream_t s);
+// GAT (attention_gat_kernels.hip)
+int launch_gat_rows(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const float *El, const float *Er, const float *V, float slope,
+                    float *Out, float *P, hipStream_t s);
+int launch_gat_rows_backward(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const float *El, const float *Er, const float *V,
+                             const float *P, const float *G, float slope, float *GEl, float *Work, hipStream_t s);
+int launch_gat_columns_backward(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const float *G, const float *P, const float *DX,
+                                float *GEr, float *GV, hipStream_t s);
+}  // namespace attention
 
 // FLEX_PLAN_TIMING in the environment: phase times of the planner and the clustering on stderr.  The only environment
 // variable the library reads; every tuning knob is a field of flex_plan_tuning (include/flex_spmm.h).

@@ -13,7 +13,7 @@ HOST_SOURCES = ["plan.cpp", "plan_build.cpp", "block_plan.cpp", "plan_check.cpp"
 
 def build(extra_flags=(), out=_OUT):
     srcs = [os.path.join(_CSRC, f) for f in HOST_SOURCES] + [os.path.join(_HERE, "shim.cpp")]
-    deps = srcs + [os.path.join(_CSRC, h) for h in ("internal.h", "plan.h", "host_parallel.h")] + [os.path.join(_ROOT, "include", "flex_spmm.h")]
+    deps = srcs + [os.path.join(_CSRC, h) for h in ("internal.h", "plan.h", "host_parallel.h", "attention_entry.h")] + [os.path.join(_ROOT, "include", "flex_spmm.h")]
     if os.path.exists(out) and all(os.path.getmtime(d) <= os.path.getmtime(out) for d in deps):
         return out
     os.makedirs(os.path.dirname(out), exist_ok=True)

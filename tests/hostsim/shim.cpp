@@ -9,15 +9,14 @@
 // (spmm_kernels.hip), launch_tiles (tile_kernels.hip) and launch_blocks (block_kernels.hip): a change there must be made here too.
 // flex_plan_set_values, flex_sddmm and flex_edge_softmax / _backward (values_kernels.hip, softmax_kernels.hip) are logged by the rules
 // the real ones use -- refresh_passes, sddmm_pick and softmax_vec of internal.h -- so nothing is mirrored for them but their refusals.
-// The fused attention entry points (flex_attention and its heads, GAT, bf16 and bias forms, forward and backward) and flex_spmm_bf16 are
-// logged the same way: the (W, NS) form is attention_pick's and the head split head_split_lg's (internal.h).
+// flex_spmm_bf16 is logged the same way.  The fused attention is logged the way the SpMM is: its twelve entry points are the library's own
+// (attention_entry.h, included at the end of this file), and nothing of it is mirrored here but the names of the kernels its launchers launch.
 // The "device memory" is counted (hostsim_live_allocations) and an allocation can be made to fail (hostsim_fail_malloc_at), so that
 // a test can check that a plan gives back everything it allocated, also when its creation fails half way.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <initializer_list>
 #include <string>
 #include <type_traits>
 
@@ -92,63 +91,82 @@ int log_softmax(const flex_plan *p, bool bwd, const float *a, const float *b, fl
     return logged(name);
 }
 
-bool scale_ok(float scale) { return std::isfinite(scale) && scale > 0.f; }
-bool slope_ok(float slope) { return std::isfinite(slope) && slope > 0.f && slope <= 1.f; }  // attention_gat_kernels.hip
 const char *vec_tail(const flex::AttentionPick &pick) { return pick.vec4 ? ", true" : ", false"; }
-// "kernel<W, NS tail>": the (W, NS) form of attention_host.h's dispatch for a pick of attention_pick
+// "kernel<W, NS tail>": the (W, NS) form of attention_host.h's dispatch for the pick an entry point made
 int log_form(const char *kernel, const flex::AttentionPick &pick, const char *tail) {
     char name[96];
     std::snprintf(name, sizeof name, "%s<%d, %d%s>", kernel, pick.W, pick.NS, tail);
     return logged(name);
 }
-// pick_bf16 (attention_bf16_kernels.hip) and pick_rows<E> (attention_bias_kernels.hip): W and NS of the plan's k, the vector form where
-// k and both strides are multiples of four elements and every row operand is aligned to four elements (a NULL output is aligned)
-template <class E>
-flex::AttentionPick pick_rows(const flex_plan *p, std::initializer_list<const void *> rows) {
-    flex::AttentionPick pick = flex::attention_pick(p->k, p->ldb, p->ldc, nullptr, nullptr, nullptr, nullptr);
-    for (const void *r : rows) pick.vec4 = pick.vec4 && reinterpret_cast<uintptr_t>(r) % (4 * sizeof(E)) == 0;
-    return pick;
-}
 template <class E>
 constexpr const char *kElemTail = std::is_same_v<E, float> ? ", float" : ", unsigned short";
-// flex_attention_bf16 (bias false) and bias_forward<E> (bias true)
-template <class E>
-int log_rows_forward(bool bias, const flex_plan *p, int heads, const E *dQ, const E *dK, const E *dV, const float *dBias, float scale, E *dOut) {
-    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
-    if (!p || !p->at_ok || heads < 1) return FLEX_ERR_INVALID;
-    if (!scale_ok(scale)) return FLEX_ERR_INVALID;
-    int lg;
-    if (const int rc = flex::head_split_lg(p->k, heads, &lg)) return rc;
-    if (p->at_entries == 0) return FLEX_OK;
-    if (!dQ || !dK || !dV || (bias && !dBias) || !dOut) return FLEX_ERR_INVALID;
-    const flex::AttentionPick pick = pick_rows<E>(p, {dQ, dK, dV, dOut});
-    if (!pick.vec4) return FLEX_ERR_UNSUPPORTED;
-    return bias ? log_form("attention_bias_rows", pick, kElemTail<E>) : log_form("attention_bf16_rows", pick, "");
-}
-// flex_attention_bf16_backward (bias false) and bias_backward<E> (bias true), whose column launch is launch_columns_backward: the
-// kernel of attention_heads_kernels.hip on float rows, of attention_bf16_kernels.hip on bf16 rows
-template <class E>
-int log_rows_backward(bool bias, const flex_plan *p, int heads, const E *dQ, const E *dK, const E *dV, const float *dP, const E *dGradOut, float scale,
-                      E *dGradQ, E *dGradK, E *dGradV, float *dGradBias, float *dWork) {
-    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
-    if (!p || !p->ab_ok || heads < 1) return FLEX_ERR_INVALID;
-    if (!scale_ok(scale)) return FLEX_ERR_INVALID;
-    int lg;
-    if (const int rc = flex::head_split_lg(p->k, heads, &lg)) return rc;
-    if (p->at_entries == 0) return FLEX_OK;
-    if (!dQ || !dK || !dV || !dP || !dGradOut || !dWork || dWork == dP) return FLEX_ERR_INVALID;
-    if (dGradBias && (dGradBias == dP || dGradBias == dWork)) return FLEX_ERR_INVALID;
-    const flex::AttentionPick pick = pick_rows<E>(p, {dQ, dK, dV, dGradOut, dGradQ, dGradK, dGradV});
-    if (!pick.vec4) return FLEX_ERR_UNSUPPORTED;
-    if (!dGradQ && !dGradK && !dGradV && !dGradBias) return FLEX_OK;
-    if (dGradQ || dGradK || dGradBias) {
-        if (bias) log_form("attention_bias_rows_backward", pick, kElemTail<E>);
-        else log_form("attention_bf16_rows_backward", pick, "");
-    }
-    if (dGradK || dGradV) log_form(std::is_same_v<E, float> ? "attention_heads_columns_backward" : "attention_bf16_columns_backward", pick, "");
-    return FLEX_OK;
-}
 }  // namespace
+
+// ---- the launchers of the fused attention (internal.h): the kernel each one's body launches in attention_*_kernels.hip, in the form of the pick
+namespace flex::attention {
+using Plan = const flex_plan *;  // short names for the unnamed parameters below
+using Pick = const AttentionPick &;
+using F = const float *;
+using B = const flex_bf16 *;
+int launch_rows(Plan, Pick pick, F, F, F, float, float *, float *, hipStream_t) {
+    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
+    return log_form("attention_rows", pick, vec_tail(pick));
+}
+int launch_rows_backward(Plan, Pick pick, F, F, F, F, float, float *, float *, hipStream_t) {
+    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
+    return log_form("attention_rows_backward", pick, vec_tail(pick));
+}
+int launch_columns_backward(Plan, Pick pick, F, F, F, F, float *, float *, hipStream_t) {
+    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
+    return log_form("attention_columns_backward", pick, vec_tail(pick));
+}
+int launch_heads_rows(Plan, Pick pick, int, int, F, F, F, float, float *, float *, hipStream_t) {
+    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
+    return log_form("attention_heads_rows", pick, "");
+}
+int launch_heads_rows(Plan, Pick pick, int, int, B, B, B, float, flex_bf16 *, float *, hipStream_t) {
+    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
+    return log_form("attention_bf16_rows", pick, "");
+}
+int launch_heads_rows_backward(Plan, Pick pick, int, int, F, F, F, F, float, float *, float *, hipStream_t) {
+    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
+    return log_form("attention_heads_rows_backward", pick, "");
+}
+int launch_heads_rows_backward(Plan, Pick pick, int, int, B, B, F, B, float, flex_bf16 *, float *, hipStream_t) {
+    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
+    return log_form("attention_bf16_rows_backward", pick, "");
+}
+int launch_heads_columns_backward(Plan, Pick pick, int, int, F, F, F, F, float *, float *, hipStream_t) {
+    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
+    return log_form("attention_heads_columns_backward", pick, "");
+}
+int launch_heads_columns_backward(Plan, Pick pick, int, int, B, B, F, F, flex_bf16 *, flex_bf16 *, hipStream_t) {
+    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
+    return log_form("attention_bf16_columns_backward", pick, "");
+}
+template <class E>
+int launch_bias_rows(Plan, Pick pick, int, int, const E *, const E *, const E *, F, float, E *, float *, hipStream_t) {
+    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
+    return log_form("attention_bias_rows", pick, kElemTail<E>);
+}
+template <class E>
+int launch_bias_rows_backward(Plan, Pick pick, int, int, const E *, const E *, F, const E *, float, E *, float *, float *, hipStream_t) {
+    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
+    return log_form("attention_bias_rows_backward", pick, kElemTail<E>);
+}
+int launch_gat_rows(Plan, Pick pick, int, int, F, F, F, float, float *, float *, hipStream_t) {
+    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
+    return log_form("gat::gat_rows", pick, "");
+}
+int launch_gat_rows_backward(Plan, Pick pick, int, int, F, F, F, F, F, float, float *, float *, hipStream_t) {
+    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
+    return log_form("gat::gat_rows_backward", pick, "");
+}
+int launch_gat_columns_backward(Plan, Pick pick, int, int, F, F, F, float *, float *, hipStream_t) {
+    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
+    return log_form("gat::gat_columns_backward", pick, "");
+}
+}  // namespace flex::attention
 
 extern "C" {
 int flex_plan_set_values(flex_plan *p, const float *dVals, flex_stream_t) {
@@ -176,119 +194,7 @@ int flex_edge_softmax(const flex_plan *p, const float *dScores, float scale, flo
 int flex_edge_softmax_backward(const flex_plan *p, const float *dP, const float *dGradP, float scale, float *dGradS, flex_stream_t) {
     return log_softmax(p, true, dP, dGradP, scale, dGradS);
 }
-// ---- the fused attention (attention_*_kernels.hip) and the bf16 SpMM (spmm_bf16_kernels.hip).  W and NS are attention_pick's and the
-// head split is head_split_lg's (internal.h), U is unroll_of's above, as spmm_bf16::launch has it; the refusals and which launch happens
-// for which outputs follow the entry points line by line: a change there must be made here too.
-int flex_attention(const flex_plan *p, const float *dQ, const float *dK, const float *dV, float scale, float *dOut, float *, flex_stream_t) {
-    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
-    if (!p || !p->at_ok) return FLEX_ERR_INVALID;
-    if (!scale_ok(scale)) return FLEX_ERR_INVALID;
-    if (p->at_entries == 0) return FLEX_OK;
-    if (!dQ || !dK || !dV || !dOut) return FLEX_ERR_INVALID;
-    const flex::AttentionPick pick = flex::attention_pick(p->k, p->ldb, p->ldc, dQ, dK, dV, dOut);
-    if (p->k > 4 * 64 * flex::kAtMaxSlabs) return FLEX_ERR_UNSUPPORTED;
-    return log_form("attention_rows", pick, vec_tail(pick));
-}
-int flex_attention_backward(const flex_plan *p, const float *dQ, const float *dK, const float *dV, const float *dP, const float *dGradOut, float scale,
-                            float *dGradQ, float *dGradK, float *dGradV, float *dWork, flex_stream_t) {
-    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
-    if (!p || !p->ab_ok) return FLEX_ERR_INVALID;
-    if (!scale_ok(scale)) return FLEX_ERR_INVALID;
-    if (p->at_entries == 0) return FLEX_OK;
-    if (!dQ || !dK || !dV || !dP || !dGradOut || !dWork || dWork == dP) return FLEX_ERR_INVALID;
-    if (p->k > 4 * 64 * flex::kAtMaxSlabs) return FLEX_ERR_UNSUPPORTED;
-    if (!dGradQ && !dGradK && !dGradV) return FLEX_OK;
-    flex::AttentionPick pick = flex::attention_pick(p->k, p->ldb, p->ldc, dQ, dK, dV, dGradOut);
-    pick.vec4 = pick.vec4 && flex::attention_pick(p->k, p->ldb, p->ldc, dGradQ, dGradK, dGradV, nullptr).vec4;
-    if (dGradQ || dGradK) log_form("attention_rows_backward", pick, vec_tail(pick));
-    if (dGradK || dGradV) log_form("attention_columns_backward", pick, vec_tail(pick));
-    return FLEX_OK;
-}
-int flex_attention_heads(const flex_plan *p, int heads, const float *dQ, const float *dK, const float *dV, float scale, float *dOut, float *dP,
-                         flex_stream_t stream) {
-    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
-    if (!p || !p->at_ok || heads < 1) return FLEX_ERR_INVALID;
-    if (heads == 1) return flex_attention(p, dQ, dK, dV, scale, dOut, dP, stream);
-    if (!scale_ok(scale)) return FLEX_ERR_INVALID;
-    int lg;
-    if (const int rc = flex::head_split_lg(p->k, heads, &lg)) return rc;
-    if (p->at_entries == 0) return FLEX_OK;
-    if (!dQ || !dK || !dV || !dOut) return FLEX_ERR_INVALID;
-    const flex::AttentionPick pick = flex::attention_pick(p->k, p->ldb, p->ldc, dQ, dK, dV, dOut);
-    if (!pick.vec4) return FLEX_ERR_UNSUPPORTED;
-    return log_form("attention_heads_rows", pick, "");
-}
-int flex_attention_heads_backward(const flex_plan *p, int heads, const float *dQ, const float *dK, const float *dV, const float *dP,
-                                  const float *dGradOut, float scale, float *dGradQ, float *dGradK, float *dGradV, float *dWork, flex_stream_t stream) {
-    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
-    if (!p || !p->ab_ok || heads < 1) return FLEX_ERR_INVALID;
-    if (heads == 1) return flex_attention_backward(p, dQ, dK, dV, dP, dGradOut, scale, dGradQ, dGradK, dGradV, dWork, stream);
-    if (!scale_ok(scale)) return FLEX_ERR_INVALID;
-    int lg;
-    if (const int rc = flex::head_split_lg(p->k, heads, &lg)) return rc;
-    if (p->at_entries == 0) return FLEX_OK;
-    if (!dQ || !dK || !dV || !dP || !dGradOut || !dWork || dWork == dP) return FLEX_ERR_INVALID;
-    const flex::AttentionPick pick = flex::attention_pick(p->k, p->ldb, p->ldc, dQ, dK, dV, dGradOut);
-    if (!pick.vec4 || !flex::attention_pick(p->k, p->ldb, p->ldc, dGradQ, dGradK, dGradV, nullptr).vec4) return FLEX_ERR_UNSUPPORTED;
-    if (!dGradQ && !dGradK && !dGradV) return FLEX_OK;
-    if (dGradQ || dGradK) log_form("attention_heads_rows_backward", pick, "");
-    if (dGradK || dGradV) log_form("attention_heads_columns_backward", pick, "");
-    return FLEX_OK;
-}
-int flex_gat_attention(const flex_plan *p, int heads, const float *dEl, const float *dEr, const float *dV, float slope, float *dOut, float *,
-                       flex_stream_t) {
-    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
-    if (!p || !p->at_ok || heads < 1 || !slope_ok(slope)) return FLEX_ERR_INVALID;
-    int lg;
-    if (const int rc = flex::head_split_lg(p->k, heads, &lg)) return rc;
-    if (p->at_entries == 0) return FLEX_OK;
-    if (!dEl || !dEr || !dV || !dOut) return FLEX_ERR_INVALID;
-    const flex::AttentionPick pick = flex::attention_pick(p->k, p->ldb, p->ldc, dV, dOut, nullptr, nullptr);
-    if (!pick.vec4) return FLEX_ERR_UNSUPPORTED;
-    return log_form("gat::gat_rows", pick, "");
-}
-int flex_gat_attention_backward(const flex_plan *p, int heads, const float *dEl, const float *dEr, const float *dV, const float *dP,
-                                const float *dGradOut, float slope, float *dGradEl, float *dGradEr, float *dGradV, float *dWork, flex_stream_t) {
-    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
-    if (!p || !p->ab_ok || heads < 1 || !slope_ok(slope)) return FLEX_ERR_INVALID;
-    int lg;
-    if (const int rc = flex::head_split_lg(p->k, heads, &lg)) return rc;
-    if (p->at_entries == 0) return FLEX_OK;
-    if (!dEl || !dEr || !dV || !dP || !dGradOut || !dWork || dWork == dP) return FLEX_ERR_INVALID;
-    const flex::AttentionPick pick = flex::attention_pick(p->k, p->ldb, p->ldc, dV, dGradOut, dGradV, nullptr);
-    if (!pick.vec4) return FLEX_ERR_UNSUPPORTED;
-    if (!dGradEl && !dGradEr && !dGradV) return FLEX_OK;
-    if (dGradEl || dGradEr) log_form("gat::gat_rows_backward", pick, "");
-    if (dGradEr || dGradV) log_form("gat::gat_columns_backward", pick, "");
-    return FLEX_OK;
-}
-int flex_attention_bf16(const flex_plan *p, int heads, const flex_bf16 *dQ, const flex_bf16 *dK, const flex_bf16 *dV, float scale, flex_bf16 *dOut,
-                        float *, flex_stream_t) {
-    return log_rows_forward<flex_bf16>(false, p, heads, dQ, dK, dV, nullptr, scale, dOut);
-}
-int flex_attention_bf16_backward(const flex_plan *p, int heads, const flex_bf16 *dQ, const flex_bf16 *dK, const flex_bf16 *dV, const float *dP,
-                                 const flex_bf16 *dGradOut, float scale, flex_bf16 *dGradQ, flex_bf16 *dGradK, flex_bf16 *dGradV, float *dWork,
-                                 flex_stream_t) {
-    return log_rows_backward<flex_bf16>(false, p, heads, dQ, dK, dV, dP, dGradOut, scale, dGradQ, dGradK, dGradV, nullptr, dWork);
-}
-int flex_attention_bias(const flex_plan *p, int heads, const float *dQ, const float *dK, const float *dV, const float *dBias, float scale, float *dOut,
-                        float *, flex_stream_t) {
-    return log_rows_forward<float>(true, p, heads, dQ, dK, dV, dBias, scale, dOut);
-}
-int flex_attention_bias_backward(const flex_plan *p, int heads, const float *dQ, const float *dK, const float *dV, const float *dP,
-                                 const float *dGradOut, float scale, float *dGradQ, float *dGradK, float *dGradV, float *dGradBias, float *dWork,
-                                 flex_stream_t) {
-    return log_rows_backward<float>(true, p, heads, dQ, dK, dV, dP, dGradOut, scale, dGradQ, dGradK, dGradV, dGradBias, dWork);
-}
-int flex_attention_bf16_bias(const flex_plan *p, int heads, const flex_bf16 *dQ, const flex_bf16 *dK, const flex_bf16 *dV, const float *dBias,
-                             float scale, flex_bf16 *dOut, float *, flex_stream_t) {
-    return log_rows_forward<flex_bf16>(true, p, heads, dQ, dK, dV, dBias, scale, dOut);
-}
-int flex_attention_bf16_bias_backward(const flex_plan *p, int heads, const flex_bf16 *dQ, const flex_bf16 *dK, const flex_bf16 *dV, const float *dP,
-                                      const flex_bf16 *dGradOut, float scale, flex_bf16 *dGradQ, flex_bf16 *dGradK, flex_bf16 *dGradV,
-                                      float *dGradBias, float *dWork, flex_stream_t) {
-    return log_rows_backward<flex_bf16>(true, p, heads, dQ, dK, dV, dP, dGradOut, scale, dGradQ, dGradK, dGradV, dGradBias, dWork);
-}
+// the bf16 SpMM (spmm_bf16_kernels.hip): U is unroll_of's above, as spmm_bf16::launch has it; the refusals follow the entry point line by line
 int flex_spmm_bf16(flex_plan *p, const flex_bf16 *dB, flex_bf16 *dC, flex_stream_t stream) {
     if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
     if (!p || !p->bf16) return FLEX_ERR_INVALID;
@@ -366,3 +272,5 @@ hipError_t hipStreamIsCapturing(hipStream_t, hipStreamCaptureStatus *st) { *st =
 hipError_t hipStreamQuery(hipStream_t) { return hipSuccess; }
 #endif
 }
+
+#include "attention_entry.h"  // the fused attention's entry points themselves, on the launchers above
