@@ -10,7 +10,10 @@ launches (flex_attention_heads, flex_attention_heads_backward), on torch.bfloat1
 flex_attention_bf16_backward: bf16 rows, float32 accumulation), and gat_attention(el, er, V) runs GAT's additive score
 LeakyReLU(el[row] + er[col]) per head in the same three launches (flex_gat_attention, flex_gat_attention_backward).
 attention(..., bias=b) adds a learned term per entry and head to the scaled score before the softmax, in float32 or bfloat16 rows, still
-in three launches (flex_attention_bias, flex_attention_bf16_bias and their backward calls).  torch is imported lazily, as in binding.py."""
+in three launches (flex_attention_bias, flex_attention_bf16_bias and their backward calls).  attention(..., dropout=p) drops the
+probabilities after the softmax, with or without a bias, in the same three launches (flex_attention_dropout, flex_attention_bf16_dropout
+and their backward calls): the mask is a hash of (seed, entry, head), so autograd keeps the seed and no mask.  torch is imported lazily, as
+in binding.py."""
 from __future__ import annotations
 
 from . import binding
@@ -247,6 +250,50 @@ def functions():
     return _cache
 
 
+def _dropout_function():
+    import torch
+
+    class _FusedAttentionDropout(torch.autograd.Function):
+        """_FusedAttentionHeads / _FusedAttentionBf16 / _FusedAttentionBias with the probabilities dropped after the softmax (probability
+        drop_p, the kept ones scaled by 1 / (1 - drop_p)): flex_attention_dropout or flex_attention_bf16_dropout (by the dtype of Q) in
+        one launch, the UNDROPPED alpha [nnz, heads] kept only when a gradient is needed; backward: the one call of two launches under
+        the same drop_p and seed, which recomputes the mask from the seed -- no mask is stored.  bias may be None.  Only on an operator
+        made with fused_attention=True and fused_backward=True."""
+
+        @staticmethod
+        def forward(ctx, Q, K, V, bias, op, scale, heads, drop_p, seed):
+            Q, K, V = Q.contiguous(), K.contiguous(), V.contiguous()
+            b = None if bias is None else bias.detach().contiguous()
+            p = torch.zeros((op.nnz, heads), dtype=torch.float32, device=Q.device) if any(ctx.needs_input_grad[:4]) else None
+            run = op.plan.attention_bf16_dropout if Q.dtype == torch.bfloat16 else op.plan.attention_dropout
+            out = run(Q, K, V, scale, drop_p, seed, heads=heads, bias=b, probs=p)
+            ctx.op, ctx.scale, ctx.heads, ctx.drop_p, ctx.seed = op, scale, heads, drop_p, seed
+            ctx.bias_shape = None if bias is None else bias.shape
+            ctx.save_for_backward(Q, K, V, p)
+            return out
+
+        @staticmethod
+        def backward(ctx, grad_out):
+            Q, K, V, p = ctx.saved_tensors
+            run = ctx.op.plan.attention_bf16_dropout_backward if Q.dtype == torch.bfloat16 else ctx.op.plan.attention_dropout_backward
+            want = tuple(ctx.needs_input_grad[:3]) + (ctx.bias_shape is not None and ctx.needs_input_grad[3],)
+            gQ, gK, gV, gB = run(Q, K, V, p, grad_out.contiguous(), ctx.scale, ctx.drop_p, ctx.seed, heads=ctx.heads, want=want)
+            return gQ, gK, gV, None if gB is None else gB.reshape(ctx.bias_shape), None, None, None, None, None
+
+    return (_FusedAttentionDropout,)
+
+
+_dropout_cache = None
+
+
+def dropout_functions():
+    """(_FusedAttentionDropout,): the autograd Functions of the attention dropout, built at first use; functions() keeps its ten."""
+    global _dropout_cache
+    if _dropout_cache is None:
+        _dropout_cache = _dropout_function()
+    return _dropout_cache
+
+
 class SparseOperator:
     """C = A B for a fixed sparse pattern A, differentiable in B: grad_B = A^T grad_C.  Keeps the plan of A (k columns) and the plan of A^T.
     `a` is an m x n HostCsr; op(B) takes B [n, k] and returns C [m, k], float32 cuda tensors.
@@ -321,7 +368,8 @@ class SparseOperator:
         assert s.numel() == self.nnz, (s.numel(), self.nnz)
         return functions()[4].apply(s, self, float(scale))
 
-    def attention(self, Q, K, V, scale: float | None = None, heads: int = 1, bias=None):
+    def attention(self, Q, K, V, scale: float | None = None, heads: int = 1, bias=None, dropout: float = 0.0, seed: int | None = None,
+                  training: bool = True):
         """Out [m, k] = A(alpha) V with alpha = softmax over each row of A of scale * <Q[row], K[col]>; scale defaults to
         (k / heads) ** -0.5.  Differentiable in Q [m, k], K [n, k] and V [n, k].  heads > 1: head h is columns [h k / heads, (h + 1) k / heads)
         of Q, K, V and Out and has its own scores and softmax, all heads in one forward launch and two backward launches
@@ -331,7 +379,13 @@ class SparseOperator:
         bias (float32 [nnz, heads] in a's CSR order; [nnz] with heads == 1): alpha = softmax of scale * <Q[row], K[col]> + bias[e, h], the
         edge term of a graph transformer, -inf masking an entry for a head; differentiable in the bias as well, in the same three launches
         (flex_attention_bias, flex_attention_bf16_bias) for Q, K, V all float32 or all bfloat16; needs both fused flags and, for any
-        heads, k / heads a power of two in 4 .. 256.  bias=None takes every path above exactly as without the argument."""
+        heads, k / heads a power of two in 4 .. 256.  bias=None takes every path above exactly as without the argument.
+        dropout (0 <= dropout < 1) with training=True: the probabilities are dropped after the softmax with that probability and the
+        kept ones scaled by 1 / (1 - dropout), with or without a bias, in the same three launches (flex_attention_dropout,
+        flex_attention_bf16_dropout): the mask is a hash of (seed, entry, head) that the backward recomputes, so nothing nnz-sized is added.
+        seed=None draws 63 bits from torch's default generator (torch.manual_seed reproduces a run); the seed is kept for the backward.
+        Needs both fused flags and k / heads a power of two in 4 .. 256.  dropout=0.0 or training=False takes every path above exactly as
+        without the arguments."""
         import torch
         self._needs_learn_values("attention")
         if heads < 1:
@@ -339,6 +393,19 @@ class SparseOperator:
         if scale is None:
             scale = (self.k / heads) ** -0.5
         dtypes = {t.dtype for t in (Q, K, V)}
+        if not 0.0 <= dropout < 1.0:  # a NaN fails this too
+            raise ValueError(f"dropout must be a probability in [0, 1), not {dropout}")
+        if dropout > 0 and training:
+            if not (self.fused_attention and self.fused_backward):
+                raise NotImplementedError("attention(..., dropout=...) needs SparseOperator(..., fused_attention=True, fused_backward=True): "
+                                          "only the fused forward and backward drop attention probabilities")
+            if dtypes not in ({torch.float32}, {torch.bfloat16}):
+                raise TypeError(f"attention takes Q, K and V of one dtype, all float32 or all bfloat16, not {[str(t.dtype) for t in (Q, K, V)]}")
+            if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) not in ((self.nnz, heads),) + (((self.nnz,),) if heads == 1 else ())):
+                raise TypeError(f"attention takes a float32 bias of shape [nnz, heads] = [{self.nnz}, {heads}], not {bias.dtype} {tuple(bias.shape)}")
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+            return dropout_functions()[0].apply(Q, K, V, bias, self, float(scale), int(heads), float(dropout), int(seed) & 0xFFFFFFFFFFFFFFFF)
         if bias is not None:
             if not (self.fused_attention and self.fused_backward):
                 raise NotImplementedError("attention(..., bias=...) needs SparseOperator(..., fused_attention=True, fused_backward=True): "

@@ -167,6 +167,8 @@ SYMBOLS = [
     "flex_gat_attention", "flex_gat_attention_backward", "flex_plan_record_info", "flex_plan_read_records",
     "flex_attention_bf16", "flex_attention_bf16_backward", "flex_spmm_bf16", "flex_plan_is_bf16",
     "flex_attention_bias", "flex_attention_bias_backward", "flex_attention_bf16_bias", "flex_attention_bf16_bias_backward",
+    "flex_attention_dropout", "flex_attention_dropout_backward", "flex_attention_bf16_dropout", "flex_attention_bf16_dropout_backward",
+    "flex_dropout_mask",
 ]
 
 _lib = None
@@ -250,6 +252,7 @@ def lib():
         L.flex_plan_record_info.argtypes = [vp, C.POINTER(_RecordInfo)]
         L.flex_plan_read_records.argtypes = [vp, vp, i64]
         L.flex_plan_is_bf16.argtypes = [vp]
+        L.flex_dropout_mask.argtypes = [C.c_uint64, C.c_float, C.c_uint64, C.c_uint64, vp]
         _lib = L
     return _lib
 
@@ -262,7 +265,7 @@ def _values_fn(name: str):
     L = lib()
     f = getattr(L, name)
     if f.argtypes is None:
-        vp, fl, i32 = C.c_void_p, C.c_float, C.c_int
+        vp, fl, i32, u64 = C.c_void_p, C.c_float, C.c_int, C.c_uint64
         f.argtypes = {"flex_plan_set_values": [vp, vp, vp], "flex_sddmm": [vp, vp, vp, vp, vp], "flex_edge_softmax": [vp, vp, fl, vp, vp],
                       "flex_edge_softmax_backward": [vp, vp, vp, fl, vp, vp], "flex_attention": [vp, vp, vp, vp, fl, vp, vp, vp],
                       "flex_attention_backward": [vp, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp],
@@ -274,6 +277,10 @@ def _values_fn(name: str):
                       "flex_attention_bias_backward": [vp, i32, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp, vp],
                       "flex_attention_bf16_bias": [vp, i32, vp, vp, vp, vp, fl, vp, vp, vp],
                       "flex_attention_bf16_bias_backward": [vp, i32, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp, vp],
+                      "flex_attention_dropout": [vp, i32, vp, vp, vp, vp, fl, fl, u64, vp, vp, vp],
+                      "flex_attention_dropout_backward": [vp, i32, vp, vp, vp, vp, vp, fl, fl, u64, vp, vp, vp, vp, vp, vp],
+                      "flex_attention_bf16_dropout": [vp, i32, vp, vp, vp, vp, fl, fl, u64, vp, vp, vp],
+                      "flex_attention_bf16_dropout_backward": [vp, i32, vp, vp, vp, vp, vp, fl, fl, u64, vp, vp, vp, vp, vp, vp],
                       "flex_spmm_bf16": [vp, vp, vp, vp],
                       "flex_gat_attention": [vp, i32, vp, vp, vp, fl, vp, vp, vp],
                       "flex_gat_attention_backward": [vp, i32, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp]}[name]
@@ -907,6 +914,92 @@ class Plan:
         return self._attention_bias_backward(torch.bfloat16, self.attention_bf16_bias_backward_ptr, Q, K, V, p, grad_out, scale, heads,
                                              (grad_q, grad_k, grad_v, grad_bias), work, want)
 
+    def attention_dropout_ptr(self, dQ_ptr: int, dK_ptr: int, dV_ptr: int, dBias_ptr: int | None, scale: float, p: float, seed: int, dOut_ptr: int,
+                              dP_ptr: int | None = None, stream: int = 0, heads: int = 1):
+        """flex_attention_dropout: fp32 rows; dBias (None: no bias) and dP (optional) are nnz x H floats, entry-major; dP receives the
+        UNDROPPED probabilities.  p: the dropout probability, 0 <= p < 1; seed: 64 bits."""
+        _check(_values_fn("flex_attention_dropout")(self._h, heads, dQ_ptr, dK_ptr, dV_ptr, dBias_ptr, scale, p, seed, dOut_ptr, dP_ptr, stream),
+               "flex_attention_dropout")
+
+    def attention_bf16_dropout_ptr(self, dQ_ptr: int, dK_ptr: int, dV_ptr: int, dBias_ptr: int | None, scale: float, p: float, seed: int,
+                                   dOut_ptr: int, dP_ptr: int | None = None, stream: int = 0, heads: int = 1):
+        """flex_attention_bf16_dropout: attention_dropout_ptr on bf16 rows (Q, K, V, Out)."""
+        _check(_values_fn("flex_attention_bf16_dropout")(self._h, heads, dQ_ptr, dK_ptr, dV_ptr, dBias_ptr, scale, p, seed, dOut_ptr, dP_ptr, stream),
+               "flex_attention_bf16_dropout")
+
+    def attention_dropout_backward_ptr(self, dQ_ptr: int, dK_ptr: int, dV_ptr: int, dP_ptr: int, dGradOut_ptr: int, scale: float, p: float, seed: int,
+                                       dGradQ_ptr: int | None, dGradK_ptr: int | None, dGradV_ptr: int | None, dGradBias_ptr: int | None,
+                                       dWork_ptr: int, stream: int = 0, heads: int = 1):
+        """flex_attention_dropout_backward: fp32 rows; dP, dGradBias (None: not wanted) and dWork are nnz x H floats, entry-major."""
+        _check(_values_fn("flex_attention_dropout_backward")(self._h, heads, dQ_ptr, dK_ptr, dV_ptr, dP_ptr, dGradOut_ptr, scale, p, seed, dGradQ_ptr,
+                                                             dGradK_ptr, dGradV_ptr, dGradBias_ptr, dWork_ptr, stream), "flex_attention_dropout_backward")
+
+    def attention_bf16_dropout_backward_ptr(self, dQ_ptr: int, dK_ptr: int, dV_ptr: int, dP_ptr: int, dGradOut_ptr: int, scale: float, p: float,
+                                            seed: int, dGradQ_ptr: int | None, dGradK_ptr: int | None, dGradV_ptr: int | None,
+                                            dGradBias_ptr: int | None, dWork_ptr: int, stream: int = 0, heads: int = 1):
+        """flex_attention_bf16_dropout_backward: attention_dropout_backward_ptr on bf16 rows (Q, K, V, g, gQ, gK, gV)."""
+        _check(_values_fn("flex_attention_bf16_dropout_backward")(self._h, heads, dQ_ptr, dK_ptr, dV_ptr, dP_ptr, dGradOut_ptr, scale, p, seed,
+                                                                  dGradQ_ptr, dGradK_ptr, dGradV_ptr, dGradBias_ptr, dWork_ptr, stream),
+               "flex_attention_bf16_dropout_backward")
+
+    def _attention_dropout(self, dtype, run, Q, K, V, scale, p, seed, heads, bias, out, probs):
+        import torch
+        i = self.info()
+        for t, rows in ((Q, i["m"]), (K, i["n"]), (V, i["n"])):
+            assert t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == (rows, i["k"]), f"{dtype} cuda [rows, k]"
+        if bias is not None:
+            if heads == 1 and bias.dim() == 1:
+                bias = bias.unsqueeze(1)
+            self._head_edge_arrays(heads, bias)
+        if out is None:  # every row is written, except by a plan without entries, which launches nothing
+            out = (torch.empty if i["nnz"] else torch.zeros)((i["m"], i["k"]), dtype=dtype, device=Q.device)
+        assert out.is_cuda and out.dtype == dtype and out.is_contiguous() and tuple(out.shape) == (i["m"], i["k"])
+        if probs is not None:
+            self._head_edge_arrays(heads, probs)
+        run(Q.data_ptr(), K.data_ptr(), V.data_ptr(), None if bias is None else bias.data_ptr(), scale, p, seed, out.data_ptr(),
+            None if probs is None else probs.data_ptr(), torch.cuda.current_stream(Q.device).cuda_stream, heads=heads)
+        return out
+
+    def attention_dropout(self, Q, K, V, scale: float, p: float, seed: int, heads: int = 1, bias=None, out=None, probs=None):
+        """flex_attention_dropout: attention(..., heads=heads) (attention_bias() with bias [a.nnz, heads]) whose probabilities are dropped
+        with probability p after the softmax and the kept ones scaled by 1 / (1 - p), in the same one launch.  The mask is
+        dropout_mask(seed, p, e * heads + h, 1) for entry e and head h.  probs (optional): a float32 cuda tensor [a.nnz, heads] that
+        receives the UNDROPPED alpha, which attention_dropout_backward() starts from.  heads = 1 runs here too: k / heads is a power of
+        two in 4 .. 256 for every heads.  p = 0 is the undropped call, bit for bit."""
+        import torch
+        return self._attention_dropout(torch.float32, self.attention_dropout_ptr, Q, K, V, scale, p, seed, heads, bias, out, probs)
+
+    def attention_bf16_dropout(self, Q, K, V, scale: float, p: float, seed: int, heads: int = 1, bias=None, out=None, probs=None):
+        """flex_attention_bf16_dropout: attention_dropout() on torch.bfloat16 Q, K, V; out is bfloat16, rounded once at its store; bias and
+        probs stay float32."""
+        import torch
+        return self._attention_dropout(torch.bfloat16, self.attention_bf16_dropout_ptr, Q, K, V, scale, p, seed, heads, bias, out, probs)
+
+    def _attention_dropout_backward(self, dtype, run, Q, K, V, probs, grad_out, scale, p, seed, heads, grads, work, want):
+        import torch
+        if len(want) == 3:
+            want = (*want, False)
+        return self._attention_bias_backward(dtype, lambda q, k, v, pr, g, sc, *rest, heads: run(q, k, v, pr, g, sc, p, seed, *rest, heads=heads),
+                                             Q, K, V, probs, grad_out, scale, heads, grads, work, want)
+
+    def attention_dropout_backward(self, Q, K, V, probs, grad_out, scale: float, p: float, seed: int, heads: int = 1, grad_q=None, grad_k=None,
+                                   grad_v=None, grad_bias=None, work=None, want=(True, True, True, False)):
+        """flex_attention_dropout_backward: (gQ [m, k], gK [n, k], gV [n, k], gBias [a.nnz, heads]) of attention_dropout()'s out from its
+        probs [a.nnz, heads] and grad_out [m, k] under the same p and seed, in two launches.  An output that `want` does not ask for is
+        None and is not computed (gBias: only where the forward had a bias).  work (optional): a float32 cuda tensor [a.nnz, heads],
+        neither probs nor grad_bias, that receives the gradient in the scores whenever gQ, gK or gBias is wanted."""
+        import torch
+        return self._attention_dropout_backward(torch.float32, self.attention_dropout_backward_ptr, Q, K, V, probs, grad_out, scale, p, seed, heads,
+                                                (grad_q, grad_k, grad_v, grad_bias), work, want)
+
+    def attention_bf16_dropout_backward(self, Q, K, V, probs, grad_out, scale: float, p: float, seed: int, heads: int = 1, grad_q=None,
+                                        grad_k=None, grad_v=None, grad_bias=None, work=None, want=(True, True, True, False)):
+        """flex_attention_bf16_dropout_backward: attention_dropout_backward() on torch.bfloat16 Q, K, V and grad_out; gQ, gK and gV are
+        bfloat16, probs, gBias and work float32."""
+        import torch
+        return self._attention_dropout_backward(torch.bfloat16, self.attention_bf16_dropout_backward_ptr, Q, K, V, probs, grad_out, scale, p, seed,
+                                                heads, (grad_q, grad_k, grad_v, grad_bias), work, want)
+
     def gat_attention_ptr(self, heads: int, dEl_ptr: int, dEr_ptr: int, dV_ptr: int, slope: float, dOut_ptr: int, dP_ptr: int | None = None,
                           stream: int = 0):
         """flex_gat_attention; dEl is rows x H floats, dEr n x H, dP (optional) nnz x H, entry-major."""
@@ -981,6 +1074,14 @@ class Plan:
             self.destroy()
         except Exception:
             pass
+
+
+def dropout_mask(seed: int, p: float, first: int, count: int) -> np.ndarray:
+    """flex_dropout_mask: the keep bits (uint8, 1 = kept) of the indices first .. first + count - 1 of the attention dropout's mask under
+    `seed` and the probability p; index e * heads + h is entry e (a's CSR order), head h.  Host code: no GPU is needed."""
+    keep = np.empty(count, np.uint8)
+    _check(lib().flex_dropout_mask(seed & 0xFFFFFFFFFFFFFFFF, p, first, count, keep.ctypes.data), "flex_dropout_mask")
+    return keep
 
 
 def gather_rows(dst_ptr: int, src_ptr: int, idx_ptr: int, n: int, k: int, stream: int = 0):

@@ -23,6 +23,12 @@
 // entry u of a pass where u == r (HW >= 4) or u % HW == r (HW = 1, 2); the same lane reads its element back in the second sweep.
 // Fixed order everywhere, no atomics.  Only the vector form is built: one 16-byte access of four floats, one 8-byte access of four
 // flex_bf16 (the host refuses the rest).
+//
+// DROP (attention_dropout_kernels.hip: flex_attention_dropout and its backward, bf16 and bias forms included; off, the sweeps are what
+// they were): the dropout of the probabilities after the softmax.  Element (e, h) is kept iff dropout_bits(seed, e H + h) < thr
+// (internal.h: DropMask), which every lane recomputes from the index it already holds -- no mask array.  The score, the maximum, the sum
+// and P are untouched; a kept entry enters Out, da and gV with the factor c, a dropped one is selected out (its V and g rows are not
+// even gathered), so a non-finite V row behind a dropped entry reaches nothing.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -37,10 +43,13 @@ namespace attention {
 // attention_kernels.hip, sweep, with the state per slab.  BIAS (attention_bias_kernels.hip): the score of a valid entry becomes
 // t = fma(scale, s, Bias[e H + head]) -- every lane of a head loads its head's element, one address for the HW lanes -- and `sm`, the
 // scale of everything after the score, is 1
-template <int W, int NS, bool BIAS, class E>
+// the keep bit of element i = e H + head of the edge arrays: every lane of a head computes the same bit
+__device__ __forceinline__ bool kept(const DropMask &dm, uint64_t i) { return dropout_bits(dm.seed_lo, dm.seed_hi, i) < dm.thr; }
+
+template <int W, int NS, bool BIAS, bool DROP, class E>
 __device__ __forceinline__ void sweep_heads(const View &v, const HeadSplit &hs, const HeadLane &hl, const float4 (&q)[NS], const E *__restrict__ K,
-                                            const E *__restrict__ V, const float *__restrict__ Bias, float scale, float sm, float *__restrict__ P,
-                                            const Place &pl, uint32_t lane, uint32_t li, State<1> (&st)[NS]) {
+                                            const E *__restrict__ V, const float *__restrict__ Bias, float scale, float sm, const DropMask &dm,
+                                            float *__restrict__ P, const Place &pl, uint32_t lane, uint32_t li, State<1> (&st)[NS]) {
     const int slot_lane0 = static_cast<int>(lane - li);
     // four slabs: the V rows of a slab are gathered when its scores are done, not with the K rows -- the per-slab state would otherwise
     // take the kernel past 256 registers, to one wave per SIMD
@@ -52,6 +61,8 @@ __device__ __forceinline__ void sweep_heads(const View &v, const HeadSplit &hs, 
         bool valid[U];
         float4 kv[U][NS], vv[U][NS];
         const E *vrow[U];
+        bool keep[U][NS];  // DROP: whether (entry u, the head of slab s) is kept; a dropped entry's V row is not gathered and stays 0
+        const uint64_t i0 = DROP ? (pl.first + j0) * static_cast<uint64_t>(hs.H) : 0;  // the pass's first element of the edge arrays
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const uint32_t col = __shfl(idx, slot_lane0 + u);
@@ -60,8 +71,10 @@ __device__ __forceinline__ void sweep_heads(const View &v, const HeadSplit &hs, 
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
                 const int c = 4 * static_cast<int>(li) + 4 * W * s;
+                keep[u][s] = true;
+                if constexpr (DROP) keep[u][s] = valid[u] && kept(dm, i0 + static_cast<uint32_t>(u * hs.H) + ((li + static_cast<uint32_t>(W * s)) >> hs.lg));
                 kv[u][s] = valid[u] ? load_cols<true>(kr, c, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
-                if constexpr (!kLateV) vv[u][s] = valid[u] ? load_cols<true>(vr, c, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
+                if constexpr (!kLateV) vv[u][s] = (valid[u] && keep[u][s]) ? load_cols<true>(vr, c, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
             vrow[u] = vr;
         }
@@ -70,7 +83,7 @@ __device__ __forceinline__ void sweep_heads(const View &v, const HeadSplit &hs, 
             const int c = 4 * static_cast<int>(li) + 4 * W * s;
             if constexpr (kLateV) {
 #pragma unroll
-                for (int u = 0; u < U; ++u) vv[u][s] = valid[u] ? load_cols<true>(vrow[u], c, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
+                for (int u = 0; u < U; ++u) vv[u][s] = (valid[u] && keep[u][s]) ? load_cols<true>(vrow[u], c, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
             float sc[U];
 #pragma unroll
@@ -107,7 +120,11 @@ __device__ __forceinline__ void sweep_heads(const View &v, const HeadSplit &hs, 
                     if (valid[u]) {
                         const float tm = term(sc[u], x.m, sm);
                         x.l += tm;
-                        axpy(x.acc[0], tm, vv[u][s]);
+                        if constexpr (DROP) {  // a dropped entry: vv is the 0 it was set to, whatever V holds
+                            axpy(x.acc[0], keep[u][s] ? tm * dm.c : 0.f, vv[u][s]);
+                        } else {
+                            axpy(x.acc[0], tm, vv[u][s]);
+                        }
                     }
                 }
             }
@@ -115,10 +132,10 @@ __device__ __forceinline__ void sweep_heads(const View &v, const HeadSplit &hs, 
     }
 }
 
-template <int W, int NS, bool BIAS, class E>
+template <int W, int NS, bool BIAS, bool DROP, class E>
 __device__ __forceinline__ void run_item_heads(const View &v, const HeadSplit &hs, const uint4 &it, int kind, const E *__restrict__ Q,
                                                const E *__restrict__ K, const E *__restrict__ V, const float *__restrict__ Bias, float scale,
-                                               E *__restrict__ Out, float *__restrict__ P, uint32_t lane, uint32_t w, HeadsShared<W, NS> &sh) {
+                                               const DropMask &dm, E *__restrict__ Out, float *__restrict__ P, uint32_t lane, uint32_t w, HeadsShared<W, NS> &sh) {
     const float sm = BIAS ? 1.f : scale;  // the scale of the softmax: with a bias it is already in the stored score
     const uint32_t slot = lane / W, li = lane % W;
     const HeadLane hl(hs, li);
@@ -133,7 +150,7 @@ __device__ __forceinline__ void run_item_heads(const View &v, const HeadSplit &h
         st[s].l = 0.f;
         st[s].acc[0] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    sweep_heads<W, NS, BIAS>(v, hs, hl, q, K, V, Bias, scale, sm, P, pl, lane, li, st);
+    sweep_heads<W, NS, BIAS, DROP>(v, hs, hl, q, K, V, Bias, scale, sm, dm, P, pl, lane, li, st);
     if (kind != kSlotLine) merge_slots_heads<W, NS>(st, lane, sm);
     bool writer = kind == kSlotLine ? pl.has_line : slot == 0;
     if (kind == kBlockLine) {
@@ -188,14 +205,14 @@ __device__ __forceinline__ void run_item_heads(const View &v, const HeadSplit &h
 }
 
 // The body of the forward kernel of either element type, which declares `sh`.  Grid: as attention_rows.  BIAS: Bias is nnz x H floats
-// in the layout of P (it is not read otherwise).
-template <int W, int NS, bool BIAS = false, class E>
+// in the layout of P (it is not read otherwise).  DROP: dm is the mask and the factor of the kept entries (it is not read otherwise).
+template <int W, int NS, bool BIAS = false, bool DROP = false, class E>
 __device__ __forceinline__ void walk_rows_heads(const View &v, const HeadSplit &hs, const E *__restrict__ Q, const E *__restrict__ K,
                                                 const E *__restrict__ V, float scale, E *__restrict__ Out, float *__restrict__ P,
-                                                HeadsShared<W, NS> &sh, const float *__restrict__ Bias = nullptr) {
+                                                HeadsShared<W, NS> &sh, const float *__restrict__ Bias = nullptr, const DropMask &dm = DropMask{}) {
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
     if (blockIdx.x < v.n_block_rows) {
-        run_item_heads<W, NS, BIAS>(v, hs, v.item[v.n_wave_items + blockIdx.x], kBlockLine, Q, K, V, Bias, scale, Out, P, lane, w, sh);
+        run_item_heads<W, NS, BIAS, DROP>(v, hs, v.item[v.n_wave_items + blockIdx.x], kBlockLine, Q, K, V, Bias, scale, dm, Out, P, lane, w, sh);
         return;
     }
     uint32_t wg = blockIdx.x - v.n_block_rows;
@@ -209,7 +226,7 @@ __device__ __forceinline__ void walk_rows_heads(const View &v, const HeadSplit &
     for (uint32_t i = v.grp[grp]; i < i1; ++i) {
         const uint4 it = v.item[i];
         const int kind = (it.w > 1 || it.y <= kAtSlotRow) ? kSlotLine : kWaveLine;  // internal.h, attention_row_class
-        run_item_heads<W, NS, BIAS>(v, hs, it, kind, Q, K, V, Bias, scale, Out, P, lane, w, sh);
+        run_item_heads<W, NS, BIAS, DROP>(v, hs, it, kind, Q, K, V, Bias, scale, dm, Out, P, lane, w, sh);
     }
 }
 
@@ -222,11 +239,12 @@ struct HeadsRowShared {
 };
 
 // attention_backward_kernels.hip, run_row, with da, delta and ds per slab.  BIAS (attention_bias_kernels.hip): sweep 2 also stores the
-// gradient in the bias, p (da - delta), into GB where GB is not NULL
-template <int W, int NS, bool BIAS, class E>
+// gradient in the bias, p (da - delta), into GB where GB is not NULL.  DROP: da of a kept entry is c <g, V>, da of a dropped one +0; the
+// rest follows from da
+template <int W, int NS, bool BIAS, bool DROP, class E>
 __device__ __forceinline__ void run_row_heads(const View &v, const HeadSplit &hs, const uint4 &it, int kind, const E *__restrict__ K,
                                               const E *__restrict__ V, const float *__restrict__ P, const E *__restrict__ G, float scale,
-                                              E *__restrict__ GQ, float *__restrict__ GB, float *__restrict__ Work, uint32_t lane, uint32_t w,
+                                              const DropMask &dm, E *__restrict__ GQ, float *__restrict__ GB, float *__restrict__ Work, uint32_t lane, uint32_t w,
                                               HeadsRowShared<W, NS> &sh) {
     const uint32_t slot = lane / W, li = lane % W;
     const int slot_lane0 = static_cast<int>(lane - li);
@@ -246,13 +264,19 @@ __device__ __forceinline__ void run_row_heads(const View &v, const HeadSplit &hs
         const uint32_t idx = mine ? v.src[pl.first - v.e0 + j0 + li] : 0u;
         bool valid[U];
         float4 vv[U][NS];
+        bool keep[U][NS];  // DROP: as in the forward
+        const uint64_t i0 = DROP ? (pl.first + j0) * static_cast<uint64_t>(hs.H) : 0;
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const uint32_t col = __shfl(idx, slot_lane0 + u);
             valid[u] = j0 + u < pl.len;
             const E *vr = V + static_cast<size_t>(col) * v.ldb;
 #pragma unroll
-            for (int s = 0; s < NS; ++s) vv[u][s] = valid[u] ? load_cols<true>(vr, 4 * static_cast<int>(li) + 4 * W * s, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int s = 0; s < NS; ++s) {
+                keep[u][s] = true;
+                if constexpr (DROP) keep[u][s] = valid[u] && kept(dm, i0 + static_cast<uint32_t>(u * hs.H) + ((li + static_cast<uint32_t>(W * s)) >> hs.lg));
+                vv[u][s] = (valid[u] && keep[u][s]) ? load_cols<true>(vr, 4 * static_cast<int>(li) + 4 * W * s, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
         }
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
@@ -260,7 +284,8 @@ __device__ __forceinline__ void run_row_heads(const View &v, const HeadSplit &hs
             const uint32_t head = (li + static_cast<uint32_t>(W * s)) >> hs.lg;
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                const float da = head_total<W>(dot_cols<true>(0.f, g[s], vv[u][s], c, v.k), hl.hw);
+                float da = head_total<W>(dot_cols<true>(0.f, g[s], vv[u][s], c, v.k), hl.hw);
+                if constexpr (DROP) da = keep[u][s] ? dm.c * da : 0.f;
                 if (valid[u] && c < v.k) {
                     const uint64_t e = (pl.first + j0 + u) * static_cast<uint64_t>(hs.H) + head;
                     if (hl.writes(u)) Work[e] = da;
@@ -360,13 +385,14 @@ __device__ __forceinline__ void run_row_heads(const View &v, const HeadSplit &hs
 }
 
 // the body of the row backward kernel of either element type
-template <int W, int NS, bool BIAS = false, class E>
+template <int W, int NS, bool BIAS = false, bool DROP = false, class E>
 __device__ __forceinline__ void walk_rows_heads_backward(const View &v, const HeadSplit &hs, const E *__restrict__ K, const E *__restrict__ V,
                                                          const float *__restrict__ P, const E *__restrict__ G, float scale, E *__restrict__ GQ,
-                                                         float *__restrict__ Work, HeadsRowShared<W, NS> &sh, float *__restrict__ GB = nullptr) {
+                                                         float *__restrict__ Work, HeadsRowShared<W, NS> &sh, float *__restrict__ GB = nullptr,
+                                                         const DropMask &dm = DropMask{}) {
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
     if (blockIdx.x < v.n_block_rows) {
-        run_row_heads<W, NS, BIAS>(v, hs, v.item[v.n_wave_items + blockIdx.x], kBlockLine, K, V, P, G, scale, GQ, GB, Work, lane, w, sh);
+        run_row_heads<W, NS, BIAS, DROP>(v, hs, v.item[v.n_wave_items + blockIdx.x], kBlockLine, K, V, P, G, scale, dm, GQ, GB, Work, lane, w, sh);
         return;
     }
     uint32_t wg = blockIdx.x - v.n_block_rows;
@@ -380,7 +406,7 @@ __device__ __forceinline__ void walk_rows_heads_backward(const View &v, const He
     for (uint32_t i = v.grp[grp]; i < i1; ++i) {
         const uint4 it = v.item[i];
         const int kind = (it.w > 1 || it.y <= kAtSlotRow) ? kSlotLine : kWaveLine;
-        run_row_heads<W, NS, BIAS>(v, hs, it, kind, K, V, P, G, scale, GQ, GB, Work, lane, w, sh);
+        run_row_heads<W, NS, BIAS, DROP>(v, hs, it, kind, K, V, P, G, scale, dm, GQ, GB, Work, lane, w, sh);
     }
 }
 
@@ -391,11 +417,12 @@ struct HeadsColumnShared {
     alignas(16) float acc[2][kWavesPerBlock][4 * W * NS];
 };
 
-// attention_backward_kernels.hip, run_column, with p and ds of the lane's head
-template <int W, int NS, class E>
+// attention_backward_kernels.hip, run_column, with p and ds of the lane's head.  DROP: gV alone sees the mask (ds holds it already): a
+// kept entry adds (p c) g; a dropped one adds 0 x 0, neither its p nor its g row being read for gV
+template <int W, int NS, bool DROP, class E>
 __device__ __forceinline__ void run_column_heads(const ColumnView &v, const HeadSplit &hs, const uint4 &it, int kind, const E *__restrict__ Q,
                                                  const E *__restrict__ G, const float *__restrict__ P, const float *__restrict__ DS,
-                                                 E *__restrict__ GK, E *__restrict__ GV, uint32_t lane, uint32_t w, HeadsColumnShared<W, NS> &sh) {
+                                                 const DropMask &dm, E *__restrict__ GK, E *__restrict__ GV, uint32_t lane, uint32_t w, HeadsColumnShared<W, NS> &sh) {
     const uint32_t slot = lane / W, li = lane % W;
     const int slot_lane0 = static_cast<int>(lane - li);
     const Place pl = place_of<W>(v.colptr, it, kind, slot, w);
@@ -409,6 +436,7 @@ __device__ __forceinline__ void run_column_heads(const ColumnView &v, const Head
         bool valid[U];
         float pe[U][NS], de[U][NS];
         float4 gg[U][NS], qq[U][NS];
+        bool keep[U][NS];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const uint32_t row = __shfl(re.x, slot_lane0 + u), e = __shfl(re.y, slot_lane0 + u);
@@ -419,9 +447,12 @@ __device__ __forceinline__ void run_column_heads(const ColumnView &v, const Head
                 const int c = 4 * static_cast<int>(li) + 4 * W * s;
                 const bool live = valid[u] && c < v.k;
                 const uint64_t eh = static_cast<uint64_t>(e) * static_cast<uint64_t>(hs.H) + ((li + static_cast<uint32_t>(W * s)) >> hs.lg);
-                pe[u][s] = (GV && live) ? P[eh] : 0.f;
+                keep[u][s] = true;
+                if constexpr (DROP) keep[u][s] = GV && live && kept(dm, eh);
+                pe[u][s] = (GV && live && keep[u][s]) ? P[eh] : 0.f;
+                if constexpr (DROP) pe[u][s] *= dm.c;
                 de[u][s] = (GK && live) ? DS[eh] : 0.f;
-                gg[u][s] = (GV && valid[u]) ? load_cols<true>(gr, c, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
+                gg[u][s] = (GV && valid[u] && keep[u][s]) ? load_cols<true>(gr, c, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
                 qq[u][s] = (GK && valid[u]) ? load_cols<true>(qr, c, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
         }
@@ -430,7 +461,7 @@ __device__ __forceinline__ void run_column_heads(const ColumnView &v, const Head
             if (valid[u]) {
 #pragma unroll
                 for (int s = 0; s < NS; ++s) {
-                    axpy(av[s], pe[u][s], gg[u][s]);
+                    axpy(av[s], pe[u][s], gg[u][s]);  // DROP, a dropped entry: pe and gg are the 0 they were set to
                     axpy(ak[s], de[u][s], qq[u][s]);
                 }
             }
@@ -477,13 +508,13 @@ __device__ __forceinline__ void run_column_heads(const ColumnView &v, const Head
 }
 
 // the body of the column backward kernel of either element type
-template <int W, int NS, class E>
+template <int W, int NS, bool DROP = false, class E>
 __device__ __forceinline__ void walk_columns_heads_backward(const ColumnView &v, const HeadSplit &hs, const E *__restrict__ Q, const E *__restrict__ G,
                                                             const float *__restrict__ P, const float *__restrict__ DS, E *__restrict__ GK,
-                                                            E *__restrict__ GV, HeadsColumnShared<W, NS> &sh) {
+                                                            E *__restrict__ GV, HeadsColumnShared<W, NS> &sh, const DropMask &dm = DropMask{}) {
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
     if (blockIdx.x < v.n_block_cols) {
-        run_column_heads<W, NS>(v, hs, v.item[v.n_wave_items + blockIdx.x], kBlockLine, Q, G, P, DS, GK, GV, lane, w, sh);
+        run_column_heads<W, NS, DROP>(v, hs, v.item[v.n_wave_items + blockIdx.x], kBlockLine, Q, G, P, DS, dm, GK, GV, lane, w, sh);
         return;
     }
     uint32_t wg = blockIdx.x - v.n_block_cols;
@@ -497,7 +528,7 @@ __device__ __forceinline__ void walk_columns_heads_backward(const ColumnView &v,
     for (uint32_t i = v.grp[grp]; i < i1; ++i) {
         const uint4 it = v.item[i];
         const int kind = (it.w > 1 || it.y <= kAtSlotRow) ? kSlotLine : kWaveLine;
-        run_column_heads<W, NS>(v, hs, it, kind, Q, G, P, DS, GK, GV, lane, w, sh);
+        run_column_heads<W, NS, DROP>(v, hs, it, kind, Q, G, P, DS, dm, GK, GV, lane, w, sh);
     }
 }
 

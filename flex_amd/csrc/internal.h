@@ -1,6 +1,7 @@
 // internal.h -- shared between the host planner and the HIP kernels of libflex_spmm.so.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdint>
 #include <initializer_list>
 #include <vector>
@@ -310,6 +311,31 @@ inline int head_split_lg(int k, int heads, int *lg_out) {
     return FLEX_OK;
 }
 
+// The mask of the attention dropout (include/flex_spmm.h, flex_attention_dropout; attention_dropout_kernels.hip), one definition for the
+// kernels and for flex_dropout_mask (plan.cpp): element i = e H + h of the edge arrays is kept iff dropout_bits(seed, i) < thr.  The mixer
+// is two rounds of a 32-bit multiply-xorshift on wrapping arithmetic; the high words of i and of the seed enter between the rounds.
+struct DropMask {
+    uint32_t seed_lo, seed_hi, thr;  // thr = min(floor((1 - (double)p) 2^32), 2^32 - 1)
+    float c;                         // 1.0f / (1.0f - p), in fp32: what a kept probability is multiplied by
+};
+__host__ __device__ inline uint32_t dropout_mix(uint32_t x) {
+    x ^= x >> 16;
+    x *= 0x7feb352du;
+    x ^= x >> 15;
+    x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+__host__ __device__ inline uint32_t dropout_bits(uint32_t seed_lo, uint32_t seed_hi, uint64_t i) {
+    return dropout_mix(dropout_mix(static_cast<uint32_t>(i) + seed_lo + 0x9E3779B9u) ^ (static_cast<uint32_t>(i >> 32) + seed_hi));
+}
+inline bool drop_p_ok(float p) { return std::isfinite(p) && p >= 0.f && p < 1.f; }
+inline DropMask drop_mask(float p, uint64_t seed) {
+    const double t = std::floor((1.0 - static_cast<double>(p)) * 4294967296.0);
+    return DropMask{static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32), t >= 4294967295.0 ? 0xFFFFFFFFu : static_cast<uint32_t>(t),
+                    1.0f / (1.0f - p)};
+}
+
 // per-thread record of the last HIP failure (flex_last_hip_error)
 void note_hip_error(hipError_t e);
 
@@ -364,6 +390,17 @@ int launch_bias_rows(const flex_plan *p, const AttentionPick &pick, int heads, i
 template <class E>
 int launch_bias_rows_backward(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const E *K, const E *V, const float *P, const E *G,
                               float scale, E *GQ, float *GB, float *Work, hipStream_t s);
+// per head with dropout after the softmax, E = float or flex_bf16, Bias / GB NULL without a bias (attention_dropout_kernels.hip, which
+// also holds the four entry points: the host simulator has no stand-ins for these)
+template <class E>
+int launch_dropout_rows(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const E *Q, const E *K, const E *V, const float *Bias,
+                        float scale, const DropMask &dm, E *Out, float *P, hipStream_t s);
+template <class E>
+int launch_dropout_rows_backward(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const E *K, const E *V, const float *P,
+                                 const E *G, float scale, const DropMask &dm, E *GQ, float *GB, float *Work, hipStream_t s);
+template <class E>
+int launch_dropout_columns_backward(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const E *Q, const E *G, const float *P,
+                                    const float *DS, const DropMask &dm, E *GK, E *GV, hipStream_t s);
 // GAT (attention_gat_kernels.hip)
 int launch_gat_rows(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const float *El, const float *Er, const float *V, float slope,
                     float *Out, float *P, hipStream_t s);

@@ -495,6 +495,13 @@ int flex_gather_rows(float *dst, const float *src, const int32_t *idx, int64_t n
     return launch_gather_rows(dst, src, idx, n, k, reinterpret_cast<hipStream_t>(stream));
 }
 
+int flex_dropout_mask(uint64_t seed, float drop_p, uint64_t first, uint64_t count, uint8_t *keep_host) {
+    if (!drop_p_ok(drop_p) || (count && !keep_host)) return FLEX_ERR_INVALID;
+    const DropMask dm = drop_mask(drop_p, seed);
+    for (uint64_t j = 0; j < count; ++j) keep_host[j] = dropout_bits(dm.seed_lo, dm.seed_hi, first + j) < dm.thr ? 1 : 0;
+    return FLEX_OK;
+}
+
 const char *flex_strerror(int status) {
     switch (status) {
         case FLEX_OK: return "ok";

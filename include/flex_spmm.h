@@ -32,6 +32,7 @@ extern "C" {
                               the equally additive flex_bf16, flex_attention_bf16 and flex_attention_bf16_backward (a typedef and two new calls, no flag, no struct),
                               the equally additive FLEX_PLAN_BF16, flex_spmm_bf16 and flex_plan_is_bf16 (a new flag and two new calls, no struct),
                               the equally additive flex_attention_bias, flex_attention_bf16_bias and their backward calls (four new calls, no flag, no struct),
+                              the equally additive flex_attention_dropout, flex_attention_bf16_dropout, their backward calls and flex_dropout_mask (five new calls, no flag, no struct),
                               and the retired flex_plan_tuning.block_ablate, which keeps its place as block_ablate_retired and must be zero.
                               3: plan-time knobs leave the environment for the struct flex_plan_tuning, flex_plan_desc.tuning, flex_plan_get_tuning,
                               flex_order_cluster_ex, flex_set_host_threads; split rows are summed by a second launch by default.
@@ -630,6 +631,56 @@ int flex_attention_bf16_bias(const flex_plan *plan, int heads, const flex_bf16 *
 int flex_attention_bf16_bias_backward(const flex_plan *plan, int heads, const flex_bf16 *dQ, const flex_bf16 *dK, const flex_bf16 *dV,
                                       const float *dP, const flex_bf16 *dGradOut, float scale, flex_bf16 *dGradQ, flex_bf16 *dGradK,
                                       flex_bf16 *dGradV, float *dGradBias, float *dWork, flex_stream_t stream);
+
+/* Attention dropout in the multi-head fused attention: flex_attention_heads / flex_attention_bf16 / flex_attention_bias /
+ * flex_attention_bf16_bias and their backward calls with the probabilities dropped after the softmax, as graph transformers and GAT
+ * train (GAT's default p is 0.6), still in ONE forward launch and TWO backward launches on the same plans: the mask is a counter-based
+ * hash of the entry's index, recomputed in all three launches -- no mask array, no extra pass, no new plan image.  No reference
+ * counterpart.  dBias == NULL: no bias (flex_attention_heads's score); otherwise flex_attention_bias's.  Head h, its columns, scale and
+ * the layout of dBias, dP, dGradBias and dWork are those calls'.  With c = 1.0f / (1.0f - drop_p), computed in fp32 on the host, the
+ * factor of entry e and head h is
+ *     w_eh = keep(seed, e H + h) ? c : 0
+ * Forward.   Out[r, head h] = sum_e alpha_eh w_eh V[src(e), head h].  The score, the bias, the maximum, the sum l, the mask (-inf) and
+ *   poison (+inf / NaN) rules and the dP written are those of the undropped call, bit for bit: dP holds the UNDROPPED alpha.  Dropout
+ *   acts after the normalisation; it removes no entry from the softmax.
+ * Dropped entries are SELECTED OUT, not multiplied by zero: a non-finite V row at a dropped entry does not reach Out; in the backward
+ *   da of a dropped entry is exactly +0 and the entry adds nothing to gV.
+ * Zero rows. A head of a row whose live entries are all dropped is +0 in every column of that head; a poisoned head stays NaN.
+ * Backward, from the kept undropped p = dP:
+ *     da_eh   = w_eh <g[r, head h], V[src(e), head h]>
+ *     delta   = sum_e p da             ds = scale p (da - delta), written to dWork            gBias = p (da - delta)
+ *     gQ[r]  += ds K[src(e)]           gK[src(e)] += ds Q[r]                                  gV[src(e)] += (p_eh w_eh) g[r]
+ *   The columns' launch needs the mask for gV only.  dGradBias == NULL: no gradient in the bias (and the kernels without it).
+ * The mask is part of the contract and is bit-defined.  On wrapping uint32 arithmetic
+ *     mix(x):  x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16
+ * and with i = e H + h as uint64, e being the entry's index in the CSR the plan was made from (a row-range shard uses the same global
+ * index, as the bias does),
+ *     r = mix( mix(lo32(i) + lo32(seed) + 0x9E3779B9) ^ (hi32(i) + hi32(seed)) )
+ * and the entry is kept iff r < thr, thr = min(floor((1 - (double)drop_p) 2^32), 2^32 - 1).  r(seed 0, i 0) = 0xae6f80f1; with seed
+ * 0x0123456789abcdef: r(0) = 0x477cb3f3, r(1) = 0x7a8a410e, r(2^32 + 5) = 0xeb2c8d08, r(2^40 + 123) = 0x5cbb10ba.
+ * flex_dropout_mask (host code, in every build): keep_host[j] = 1 if index first + j is kept, else 0, for j < count -- the mask's
+ * reference for users and tests.
+ * Checks: those of flex_attention_bf16 / flex_attention_bias and their backward calls, in their order, for both element types (heads
+ * == 1 is served by the per-head kernels: k / heads a power of two in 4 .. 256 for every heads); drop_p must be finite with 0 <=
+ * drop_p < 1, anything else is FLEX_ERR_INVALID, checked beside scale.  drop_p == 0: once nothing is refused the call forwards to the
+ * undropped entry point (flex_attention_heads, flex_attention_bf16 or the bias form), so every output has its bits.  Nothing is
+ * enqueued by a refused call.  Safe to capture in a hipGraph, no atomics, fixed order: bit-identical run to run for one seed.
+ * Accuracy: the undropped calls' bounds with every rounding count that now includes the product by c grown by one: Out gamma(n_r + 4) in
+ * place of gamma(n_r + 3), on |V| of the kept entries times c; da gamma(d + 1); gV one more rounding per term; dP unchanged.
+ * The four calls are written `extern`: the GPU library alone defines them (attention_dropout_kernels.hip), where the entry points
+ * declared plainly above are attention_entry.h's, which a host-only build of the library's sources defines as well. */
+extern int flex_attention_dropout(const flex_plan *plan, int heads, const float *dQ, const float *dK, const float *dV, const float *dBias /* NULL: no bias */,
+                           float scale, float drop_p, uint64_t seed, float *dOut, float *dP, flex_stream_t stream);
+extern int flex_attention_dropout_backward(const flex_plan *plan, int heads, const float *dQ, const float *dK, const float *dV, const float *dP,
+                                    const float *dGradOut, float scale, float drop_p, uint64_t seed, float *dGradQ, float *dGradK, float *dGradV,
+                                    float *dGradBias /* NULL */, float *dWork, flex_stream_t stream);
+extern int flex_attention_bf16_dropout(const flex_plan *plan, int heads, const flex_bf16 *dQ, const flex_bf16 *dK, const flex_bf16 *dV,
+                                const float *dBias /* NULL: no bias */, float scale, float drop_p, uint64_t seed, flex_bf16 *dOut, float *dP,
+                                flex_stream_t stream);
+extern int flex_attention_bf16_dropout_backward(const flex_plan *plan, int heads, const flex_bf16 *dQ, const flex_bf16 *dK, const flex_bf16 *dV,
+                                         const float *dP, const flex_bf16 *dGradOut, float scale, float drop_p, uint64_t seed, flex_bf16 *dGradQ,
+                                         flex_bf16 *dGradK, flex_bf16 *dGradV, float *dGradBias /* NULL */, float *dWork, flex_stream_t stream);
+int flex_dropout_mask(uint64_t seed, float drop_p, uint64_t first, uint64_t count, uint8_t *keep_host);
 
 /* Fused GAT attention: the additive score of graph attention networks in place of the dot product, H heads in the ONE forward launch and
  * the TWO backward launches of flex_attention_heads and flex_attention_heads_backward, on the same plans (FLEX_PLAN_ATTENTION;

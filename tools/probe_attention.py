@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Sparse graph attention, measured: the error of the exponential the edge softmax may use, and the time of flex_edge_softmax,
 flex_edge_softmax_backward and a whole attention step.  Writes profiles/attention_probe.txt (or the file given with --out): the whole run
-starts the file, a run of one part (--fused, --backward, --heads, --gat, --bf16, --bias) appends to it.
+starts the file, a run of one part (--fused, --backward, --heads, --gat, --bf16, --bias, --dropout) appends to it.
 
 1. tools/exp_error.hip (built here with hipcc into flex_amd/lib if it is not there): the largest error in ulp of expf, __expf and
    exp2f on the prescaled argument over every fp32 argument in [-104, 0] against float64 exp.
@@ -37,7 +37,12 @@ starts the file, a run of one part (--fused, --backward, --heads, --gat, --bf16,
    process -- what the bias costs: nnz x H floats read forward, nnz x H written backward -- and, at k = 64 with one head, against what a
    user needed before: flex_sddmm, a torch add, flex_edge_softmax and the SpMM with values=alpha, with their autograd.  --bias: only
    this part (and the copy rate).
-Usage: probe_attention.py [--out FILE] [--fused | --backward | --heads | --gat | --bf16 | --bias] [graph ...]   (default: pubmed.csv flickr reddit soc-sign-epinions)"""
+10. Attention dropout (flex_attention_dropout, flex_attention_bf16_dropout and their backward calls), (k, H) = (64, 8), (128, 4), (256, 8),
+   p = 0.1 and 0.6, same graphs and protocol: the forward (with dP) and the backward in fp32 and in bf16 against the undropped
+   flex_attention_heads / flex_attention_bf16 and their backward calls on the same plan in the same process -- what the mask costs (four
+   32-bit multiplies per entry and head in each of the three launches) and what the V and g rows that are not gathered behind dropped
+   entries save.  --dropout: only this part (and the copy rate).
+Usage: probe_attention.py [--out FILE] [--fused | --backward | --heads | --gat | --bf16 | --bias | --dropout] [graph ...]   (default: pubmed.csv flickr reddit soc-sign-epinions)"""
 import ctypes as C
 import os
 import subprocess
@@ -437,14 +442,45 @@ def probe_bias(name, a):
         del op, plan
 
 
+def probe_dropout(name, a):
+    gen = torch.Generator(device="cuda").manual_seed(8)
+    seed = 0x0123456789ABCDEF
+    for k, H in ((64, 8), (128, 4), (256, 8)):
+        d = k // H
+        plan = flex_amd.Plan(a, k, attention=True, attention_backward=True)  # one plan serves every contender
+        Q, K, V, g = (torch.rand((r, k), device="cuda", generator=gen) * 2 - 1 for r in (a.m, a.n, a.n, a.m))
+        scale = d ** -0.5
+        rows = {torch.float32: (Q, K, V, g), torch.bfloat16: tuple(x.bfloat16() for x in (Q, K, V, g))}
+        outs = {dt: tuple(torch.empty((r, k), device="cuda", dtype=dt) for r in (a.m, a.m, a.n, a.n)) for dt in rows}
+        P, W = (torch.empty((a.nnz, H), device="cuda") for _ in range(2))
+        fns = {}
+        for dt, tag, plain, plain_b, drop, drop_b in (
+                (torch.float32, "fp32", plan.attention, plan.attention_backward, plan.attention_dropout, plan.attention_dropout_backward),
+                (torch.bfloat16, "bf16", plan.attention_bf16, plan.attention_bf16_backward, plan.attention_bf16_dropout, plan.attention_bf16_dropout_backward)):
+            (q, kk, v, gg), (o, gq, gk, gv) = rows[dt], outs[dt]
+            fns[f"forward, {tag}"] = lambda q=q, kk=kk, v=v, o=o, f=plain: f(q, kk, v, scale, out=o, p=P, heads=H)
+            fns[f"backward, {tag}"] = lambda q=q, kk=kk, v=v, gg=gg, gq=gq, gk=gk, gv=gv, f=plain_b: f(q, kk, v, P, gg, scale, grad_q=gq, grad_k=gk, grad_v=gv, work=W, heads=H)
+            for p_ in (0.1, 0.6):
+                fns[f"forward, {tag} p={p_}"] = lambda q=q, kk=kk, v=v, o=o, f=drop, p_=p_: f(q, kk, v, scale, p_, seed, heads=H, out=o, probs=P)
+                fns[f"backward, {tag} p={p_}"] = lambda q=q, kk=kk, v=v, gg=gg, gq=gq, gk=gk, gv=gv, f=drop_b, p_=p_: f(q, kk, v, P, gg, scale, p_, seed, heads=H, grad_q=gq, grad_k=gk, grad_v=gv, work=W)
+        plan.attention(Q, K, V, scale, out=outs[torch.float32][0], p=P, heads=H)  # P holds probabilities for every backward
+        n = max(3, min(100, int(1e8 / max(1, a.nnz * k))))
+        best, spread = _alternate(fns, n)
+        say(f"{name} k={k} H={H} d={d} dropout: " + "  ".join(f"{key} {best[key]:.1f} us (+{spread[key]:.0f} % over 3 rounds)" for key in fns)
+            + "  dropout / no dropout: " + "  ".join(f"{w} {t} p={p_} {best[f'{w}, {t} p={p_}'] / best[f'{w}, {t}']:.2f}x"
+                                                      for t in ("fp32", "bf16") for w in ("forward", "backward") for p_ in (0.1, 0.6))
+            + "  extra memory: none (the mask is recomputed from the seed)")
+        del plan
+
+
 def main():
     args = sys.argv[1:]
     out = os.path.join(ROOT, "profiles", "attention_probe.txt")
     if args[:1] == ["--out"]:
         out, args = args[1], args[2:]
-    fused_only, backward_only, heads_only, gat_only, bf16_only, bias_only = (args[:1] == [flag] for flag in
-                                                                             ("--fused", "--backward", "--heads", "--gat", "--bf16", "--bias"))
-    only = fused_only or backward_only or heads_only or gat_only or bf16_only or bias_only
+    fused_only, backward_only, heads_only, gat_only, bf16_only, bias_only, dropout_only = (
+        args[:1] == [flag] for flag in ("--fused", "--backward", "--heads", "--gat", "--bf16", "--bias", "--dropout"))
+    only = fused_only or backward_only or heads_only or gat_only or bf16_only or bias_only or dropout_only
     if only:
         args = args[1:]
     else:
@@ -467,6 +503,8 @@ def main():
             probe_bf16(name, a)
         if bias_only or not only:
             probe_bias(name, a)
+        if dropout_only or not only:
+            probe_dropout(name, a)
     with open(out, "a" if only else "w") as f:  # a part is appended, the whole run starts the file
         f.write("\n".join(LINES) + "\n")
 
