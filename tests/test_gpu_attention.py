@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import flex_amd
+from attention_walk_graphs import walk_graph
 from backward_ref import _directed
 from conftest import GOLDEN
 from f64ref import scenario
@@ -25,7 +26,11 @@ GRAPHS = {
     "rows_256_257": boundary_graph,
     "wide_512": lambda: scenario("wide", k=32, m=512)[0],
     "wide_3000": lambda: scenario("wide", k=32, m=3000)[0],
+    "walk_7_copies": lambda: walk_graph(7),
 }
+# flex_plan_softmax_info's group budget (group_entries): every graph above plans at the floor of 256 but the last, 7 copies of
+# tests/attention_walk_graphs.py's graph (490 000 rows, 1 495 606 entries), where a group holds two items on average
+GROUP_ENTRIES = {"walk_7_copies": 512}
 _cache = {}
 
 
@@ -57,6 +62,7 @@ def _grad(nnz, seed):
 @pytest.mark.parametrize("name", SCORE_SCENARIOS)
 def test_forward_and_backward_against_float64(graph, name):
     a, plan = graph_and_plan(graph)
+    assert plan.softmax_info()["group_entries"] == GROUP_ENTRIES.get(graph, 256)
     s = scores(name, a.rowPtr, seed=1)
     g = _grad(a.nnz, 2)
     sd, gd = _dev(s), _dev(g)
