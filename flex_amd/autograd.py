@@ -294,6 +294,47 @@ def dropout_functions():
     return _dropout_cache
 
 
+def _gat_dropout_function():
+    import torch
+
+    class _FusedGatAttentionDropout(torch.autograd.Function):
+        """_FusedGatAttention with the probabilities dropped after the softmax (probability drop_p, the kept ones scaled by
+        1 / (1 - drop_p)): flex_gat_attention_dropout in one launch, the UNDROPPED alpha [nnz, heads] kept only when a gradient is
+        needed; backward: the one call flex_gat_attention_dropout_backward (two launches) under the same drop_p and seed, which
+        recomputes the mask from the seed -- no mask is stored.  Only on an operator made with fused_attention=True and
+        fused_backward=True."""
+
+        @staticmethod
+        def forward(ctx, el, er, V, op, slope, drop_p, seed):
+            el, er, V = el.contiguous(), er.contiguous(), V.contiguous()
+            p = torch.zeros((op.nnz, el.shape[1]), dtype=torch.float32, device=V.device) if any(ctx.needs_input_grad[:3]) else None
+            out = op.plan.gat_attention_dropout(el, er, V, slope, drop_p, seed, probs=p)
+            ctx.op, ctx.slope, ctx.drop_p, ctx.seed = op, slope, drop_p, seed
+            ctx.save_for_backward(el, er, V, p)
+            return out
+
+        @staticmethod
+        def backward(ctx, grad_out):
+            el, er, V, p = ctx.saved_tensors
+            grads = ctx.op.plan.gat_attention_dropout_backward(el, er, V, p, grad_out.contiguous(), ctx.slope, ctx.drop_p, ctx.seed,
+                                                               want=tuple(ctx.needs_input_grad[:3]))
+            return (*grads, None, None, None, None)
+
+    return (_FusedGatAttentionDropout,)
+
+
+_gat_dropout_cache = None
+
+
+def gat_dropout_functions():
+    """(_FusedGatAttentionDropout,): the autograd Function of the GAT attention dropout, built at first use; functions() keeps its ten and
+    dropout_functions() its one."""
+    global _gat_dropout_cache
+    if _gat_dropout_cache is None:
+        _gat_dropout_cache = _gat_dropout_function()
+    return _gat_dropout_cache
+
+
 class SparseOperator:
     """C = A B for a fixed sparse pattern A, differentiable in B: grad_B = A^T grad_C.  Keeps the plan of A (k columns) and the plan of A^T.
     `a` is an m x n HostCsr; op(B) takes B [n, k] and returns C [m, k], float32 cuda tensors.
@@ -307,7 +348,8 @@ class SparseOperator:
     fused_backward=True (with fused_attention=True): the forward plan is also made with FLEX_PLAN_ATTENTION_BACKWARD and the backward of
     op.attention is one call of two launches (flex_attention_backward) that sets no plan's values.  Off by default.
     With both fused flags the operator also offers op.gat_attention(el, er, V, negative_slope): GAT's additive attention, H = el.shape[1]
-    heads in one forward launch and two backward launches (flex_gat_attention), differentiable in el [m, H], er [n, H] and V [n, k].
+    heads in one forward launch and two backward launches (flex_gat_attention), differentiable in el [m, H], er [n, H] and V [n, k];
+    dropout= drops its probabilities after the softmax in the same launches (flex_gat_attention_dropout).
     bf16=True: both plans are made with FLEX_PLAN_BF16 (k a multiple of 8): op(B) takes and returns torch.bfloat16 (float32 raises
     TypeError, as bfloat16 does on an fp32 operator), sums in float32, and backpropagates A^T grad_C in bfloat16 through flex_spmm_bf16 on
     the transposed plan.  The plain product only: NotImplementedError with learn_values, the fused flags or values=."""
@@ -431,12 +473,24 @@ class SparseOperator:
             return functions()[5].apply(Q, K, V, self, float(scale))
         return self(V, values=self.edge_softmax(self.sddmm(Q, K), scale))
 
-    def gat_attention(self, el, er, V, negative_slope: float = 0.2):
+    def gat_attention(self, el, er, V, negative_slope: float = 0.2, dropout: float = 0.0, seed: int | None = None, training: bool = True):
         """Out [m, k] = A(alpha) V per head with alpha = softmax over each row of A of leaky_relu(el[row, h] + er[col, h], negative_slope):
         the attention of a GAT layer, el = <h W, a_l> and er = <h W, a_r> being one scalar per node and head.  H = el.shape[1] heads; head h
         is columns [h k / H, (h + 1) k / H) of V and Out.  Differentiable in el [m, H], er [n, H] and V [n, k]; all heads in one forward
-        launch and two backward launches (flex_gat_attention); needs fused_attention=True and fused_backward=True."""
+        launch and two backward launches (flex_gat_attention); needs fused_attention=True and fused_backward=True.
+        dropout (0 <= dropout < 1) with training=True: the probabilities are dropped after the softmax with that probability and the
+        kept ones scaled by 1 / (1 - dropout), in the same three launches (flex_gat_attention_dropout): the mask is a hash of (seed,
+        entry, head) that the backward recomputes, so nothing nnz-sized is added.  seed=None draws 63 bits from torch's default
+        generator (torch.manual_seed reproduces a run); the seed is kept for the backward.  dropout=0.0 or training=False takes the path
+        above exactly as without the arguments."""
+        if not 0.0 <= dropout < 1.0:  # a NaN fails this too
+            raise ValueError(f"dropout must be a probability in [0, 1), not {dropout}")
         if not (self.fused_attention and self.fused_backward):
             raise NotImplementedError("gat_attention needs SparseOperator(..., learn_values=True, fused_attention=True, fused_backward=True): "
                                       "only the fused forward and backward compute the additive score")
+        if dropout > 0 and training:
+            import torch
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+            return gat_dropout_functions()[0].apply(el, er, V, self, float(negative_slope), float(dropout), int(seed) & 0xFFFFFFFFFFFFFFFF)
         return functions()[7].apply(el, er, V, self, float(negative_slope))

@@ -168,7 +168,7 @@ SYMBOLS = [
     "flex_attention_bf16", "flex_attention_bf16_backward", "flex_spmm_bf16", "flex_plan_is_bf16",
     "flex_attention_bias", "flex_attention_bias_backward", "flex_attention_bf16_bias", "flex_attention_bf16_bias_backward",
     "flex_attention_dropout", "flex_attention_dropout_backward", "flex_attention_bf16_dropout", "flex_attention_bf16_dropout_backward",
-    "flex_dropout_mask",
+    "flex_dropout_mask", "flex_gat_attention_dropout", "flex_gat_attention_dropout_backward",
 ]
 
 _lib = None
@@ -283,7 +283,9 @@ def _values_fn(name: str):
                       "flex_attention_bf16_dropout_backward": [vp, i32, vp, vp, vp, vp, vp, fl, fl, u64, vp, vp, vp, vp, vp, vp],
                       "flex_spmm_bf16": [vp, vp, vp, vp],
                       "flex_gat_attention": [vp, i32, vp, vp, vp, fl, vp, vp, vp],
-                      "flex_gat_attention_backward": [vp, i32, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp]}[name]
+                      "flex_gat_attention_backward": [vp, i32, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp],
+                      "flex_gat_attention_dropout": [vp, i32, vp, vp, vp, fl, fl, u64, vp, vp, vp],
+                      "flex_gat_attention_dropout_backward": [vp, i32, vp, vp, vp, vp, vp, fl, fl, u64, vp, vp, vp, vp, vp]}[name]
     return f
 
 
@@ -1062,6 +1064,64 @@ class Plan:
         self.gat_attention_backward_ptr(heads, el.data_ptr(), er.data_ptr(), V.data_ptr(), p.data_ptr(), grad_out.data_ptr(), slope,
                                         *(None if t is None else t.data_ptr() for t in outs), work.data_ptr(),
                                         torch.cuda.current_stream(V.device).cuda_stream)
+        return tuple(outs)
+
+    def gat_attention_dropout_ptr(self, heads: int, dEl_ptr: int, dEr_ptr: int, dV_ptr: int, slope: float, p: float, seed: int, dOut_ptr: int,
+                                  dP_ptr: int | None = None, stream: int = 0):
+        """flex_gat_attention_dropout; dEl is rows x H floats, dEr n x H, dP (optional) nnz x H, entry-major: it receives the UNDROPPED
+        alpha."""
+        _check(_values_fn("flex_gat_attention_dropout")(self._h, heads, dEl_ptr, dEr_ptr, dV_ptr, slope, p, seed, dOut_ptr, dP_ptr, stream),
+               "flex_gat_attention_dropout")
+
+    def gat_attention_dropout(self, el, er, V, slope: float, p: float, seed: int, out=None, probs=None):
+        """flex_gat_attention_dropout: gat_attention() whose probabilities are dropped after the softmax with probability p in [0, 1), the
+        kept ones scaled by 1 / (1 - p); the mask is binding.dropout_mask(seed, p, e * H + h), a function of the 64-bit seed.  probs
+        (optional, float32 [a.nnz, H]) receives the UNDROPPED alpha, which gat_attention_dropout_backward() starts from."""
+        import torch
+        i = self.info()
+        heads = self._node_scalars(el, er)
+        assert V.is_cuda and V.dtype == torch.float32 and V.is_contiguous() and tuple(V.shape) == (i["n"], i["k"])
+        if out is None:  # every row is written, except by a plan without entries, which launches nothing
+            out = (torch.empty if i["nnz"] else torch.zeros)((i["m"], i["k"]), dtype=torch.float32, device=V.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (i["m"], i["k"])
+        if probs is not None:
+            self._head_edge_arrays(heads, probs)
+        self.gat_attention_dropout_ptr(heads, el.data_ptr(), er.data_ptr(), V.data_ptr(), slope, p, int(seed) & 0xFFFFFFFFFFFFFFFF, out.data_ptr(),
+                                       None if probs is None else probs.data_ptr(), torch.cuda.current_stream(V.device).cuda_stream)
+        return out
+
+    def gat_attention_dropout_backward_ptr(self, heads: int, dEl_ptr: int, dEr_ptr: int, dV_ptr: int, dP_ptr: int, dGradOut_ptr: int, slope: float,
+                                           p: float, seed: int, dGradEl_ptr: int | None, dGradEr_ptr: int | None, dGradV_ptr: int | None,
+                                           dWork_ptr: int, stream: int = 0):
+        """flex_gat_attention_dropout_backward; dP and dWork are nnz x H floats, entry-major."""
+        _check(_values_fn("flex_gat_attention_dropout_backward")(self._h, heads, dEl_ptr, dEr_ptr, dV_ptr, dP_ptr, dGradOut_ptr, slope, p, seed,
+                                                                 dGradEl_ptr, dGradEr_ptr, dGradV_ptr, dWork_ptr, stream),
+               "flex_gat_attention_dropout_backward")
+
+    def gat_attention_dropout_backward(self, el, er, V, probs, grad_out, slope: float, p: float, seed: int, grad_el=None, grad_er=None,
+                                       grad_v=None, work=None, want=(True, True, True)):
+        """flex_gat_attention_dropout_backward: (gEl [m, H], gEr [n, H], gV [n, k]) of gat_attention_dropout()'s out from its probs
+        [a.nnz, H] (the undropped alpha), grad_out [m, k] and the same p and seed, in two launches; an output that `want` does not ask
+        for is None and is not computed.  work (optional): a float32 cuda tensor [a.nnz, H], not probs, that receives the gradient in
+        el + er per entry whenever gEl or gEr is wanted."""
+        import torch
+        i = self.info()
+        heads = self._node_scalars(el, er)
+        for t, rows in ((V, i["n"]), (grad_out, i["m"])):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (rows, i["k"])
+        if work is None:
+            work = torch.empty((self.src_nnz, heads), dtype=torch.float32, device=V.device)
+        self._head_edge_arrays(heads, probs, work)
+        outs = []
+        for wanted, t, shape in zip(want, (grad_el, grad_er, grad_v), ((i["m"], heads), (i["n"], heads), (i["n"], i["k"]))):
+            if wanted and t is None:  # every row is written, except by a plan without entries, which launches nothing
+                t = (torch.empty if i["nnz"] else torch.zeros)(shape, dtype=torch.float32, device=V.device)
+            if wanted:
+                assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape
+            outs.append(t if wanted else None)
+        self.gat_attention_dropout_backward_ptr(heads, el.data_ptr(), er.data_ptr(), V.data_ptr(), probs.data_ptr(), grad_out.data_ptr(), slope, p,
+                                                int(seed) & 0xFFFFFFFFFFFFFFFF, *(None if t is None else t.data_ptr() for t in outs),
+                                                work.data_ptr(), torch.cuda.current_stream(V.device).cuda_stream)
         return tuple(outs)
 
     def destroy(self):

@@ -408,6 +408,15 @@ int launch_gat_rows_backward(const flex_plan *p, const AttentionPick &pick, int 
                              const float *P, const float *G, float slope, float *GEl, float *Work, hipStream_t s);
 int launch_gat_columns_backward(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const float *G, const float *P, const float *DX,
                                 float *GEr, float *GV, hipStream_t s);
+// GAT with dropout after the softmax (attention_gat_dropout_kernels.hip, which also holds the two entry points: the host simulator has
+// no stand-ins for these)
+int launch_gat_dropout_rows(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const float *El, const float *Er, const float *V,
+                            float slope, const DropMask &dm, float *Out, float *P, hipStream_t s);
+int launch_gat_dropout_rows_backward(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const float *El, const float *Er,
+                                     const float *V, const float *P, const float *G, float slope, const DropMask &dm, float *GEl, float *Work,
+                                     hipStream_t s);
+int launch_gat_dropout_columns_backward(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const float *G, const float *P,
+                                        const float *DX, const DropMask &dm, float *GEr, float *GV, hipStream_t s);
 }  // namespace attention
 
 // FLEX_PLAN_TIMING in the environment: phase times of the planner and the clustering on stderr.  The only environment

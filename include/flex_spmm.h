@@ -33,6 +33,7 @@ extern "C" {
                               the equally additive FLEX_PLAN_BF16, flex_spmm_bf16 and flex_plan_is_bf16 (a new flag and two new calls, no struct),
                               the equally additive flex_attention_bias, flex_attention_bf16_bias and their backward calls (four new calls, no flag, no struct),
                               the equally additive flex_attention_dropout, flex_attention_bf16_dropout, their backward calls and flex_dropout_mask (five new calls, no flag, no struct),
+                              the equally additive flex_gat_attention_dropout and flex_gat_attention_dropout_backward (two new calls, no flag, no struct),
                               and the retired flex_plan_tuning.block_ablate, which keeps its place as block_ablate_retired and must be zero.
                               3: plan-time knobs leave the environment for the struct flex_plan_tuning, flex_plan_desc.tuning, flex_plan_get_tuning,
                               flex_order_cluster_ex, flex_set_host_threads; split rows are summed by a second launch by default.
@@ -750,6 +751,39 @@ int flex_gat_attention(const flex_plan *plan, int heads, const float *dEl, const
 int flex_gat_attention_backward(const flex_plan *plan, int heads, const float *dEl, const float *dEr, const float *dV, const float *dP,
                                 const float *dGradOut, float slope, float *dGradEl, float *dGradEr, float *dGradV, float *dWork,
                                 flex_stream_t stream);
+
+/* Attention dropout in the fused GAT attention: flex_gat_attention and flex_gat_attention_backward with the probabilities dropped after
+ * the softmax, as GAT trains (the paper's p is 0.6), still in ONE forward launch and TWO backward launches on the same plans.  The mask,
+ * its threshold and its index are flex_attention_dropout's, bit for bit (flex_dropout_mask is its host reference): with
+ * c = 1.0f / (1.0f - drop_p), computed in fp32 on the host, the factor of entry e and head h is
+ *     w_eh = keep(seed, e H + h) ? c : 0
+ * Entry index. e is the entry's index in the CSR the plan was made from; a row-range shard uses that global index.
+ * Forward.   Out[r, head h] = sum_e alpha_eh w_eh V[src(e), head h].  The score x = el + er, the LeakyReLU, the maximum, the sum, the
+ *   mask (-inf) and poison (+inf / NaN) rules and the dP written are flex_gat_attention's, bit for bit: dP holds the UNDROPPED alpha.
+ * Dropped entries are SELECTED OUT, not multiplied by zero: the V row of a dropped entry is not gathered, so an inf or NaN V row behind
+ *   a dropped entry reaches nothing.  A head of a row whose live entries are all dropped is +0 in every column of that head; a poisoned
+ *   head stays NaN.
+ * Backward, from the kept undropped p = dP:
+ *     da_eh   = w_eh <g[r, head h], V[src(e), head h]>          (a dropped entry: exactly +0, its V row is not gathered)
+ *     delta, dz = p (da - delta), dx by the sign of the recomputed x, gEl, gEr and dWork = dx exactly as in flex_gat_attention_backward
+ *     gV[c, head h] += (p_eh w_eh) g[row(e), head h]            (a dropped entry: its g row is not gathered)
+ *   dx holds the mask through da, so gEl and gEr do not see it a second time; the columns' launch needs the mask for gV only.
+ * Checks: drop_p must be finite with 0 <= drop_p < 1, anything else is FLEX_ERR_INVALID, checked beside slope; every other refusal is
+ * flex_gat_attention's and flex_gat_attention_backward's, code for code and in their order.  drop_p == 0: once nothing is refused the
+ * call forwards to the undropped entry point, so every output has its bits.  The forward runs on row-range shards, the backward does
+ * not.  Nothing is enqueued by a refused call.  Safe to capture in a hipGraph, no atomics, fixed order: bit-identical run to run for
+ * one seed.
+ * Accuracy: flex_gat_attention's bounds with every rounding count that now includes the product by c grown by one:
+ *   Out     |Out - Out64| <= sum_{e kept} (gamma(n_r + 4) alpha_e + dalpha_e) c |V| + 2^-126
+ *   dda_e    = c (gamma(d + 1) sum_j |g V| + d 2^-149) + 2^-149 on a kept entry, 0 on a dropped one
+ *   ddz, ddx, gEl, gEr: flex_gat_attention_backward's lines on this da and dda
+ *   |gV  - gV64|  <= sum_{e in c, kept} gamma(n_c + 1) p_e c |g[row]| + 2^-126
+ * The two calls are written `extern`: the GPU library alone defines them (attention_gat_dropout_kernels.hip). */
+extern int flex_gat_attention_dropout(const flex_plan *plan, int heads, const float *dEl, const float *dEr, const float *dV, float slope, float drop_p,
+                               uint64_t seed, float *dOut, float *dP, flex_stream_t stream);
+extern int flex_gat_attention_dropout_backward(const flex_plan *plan, int heads, const float *dEl, const float *dEr, const float *dV, const float *dP,
+                                        const float *dGradOut, float slope, float drop_p, uint64_t seed, float *dGradEl, float *dGradEr,
+                                        float *dGradV, float *dWork, flex_stream_t stream);
 
 /* ≙ alpha_freeMatGPU (mat.cuh:184-193). */
 int flex_plan_destroy(flex_plan *plan);

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Sparse graph attention, measured: the error of the exponential the edge softmax may use, and the time of flex_edge_softmax,
 flex_edge_softmax_backward and a whole attention step.  Writes profiles/attention_probe.txt (or the file given with --out): the whole run
-starts the file, a run of one part (--fused, --backward, --heads, --gat, --bf16, --bias, --dropout) appends to it.
+starts the file, a run of one part (--fused, --backward, --heads, --gat, --bf16, --bias, --dropout, --gat-dropout) appends to it.
 
 1. tools/exp_error.hip (built here with hipcc into flex_amd/lib if it is not there): the largest error in ulp of expf, __expf and
    exp2f on the prescaled argument over every fp32 argument in [-104, 0] against float64 exp.
@@ -42,7 +42,10 @@ starts the file, a run of one part (--fused, --backward, --heads, --gat, --bf16,
    flex_attention_heads / flex_attention_bf16 and their backward calls on the same plan in the same process -- what the mask costs (four
    32-bit multiplies per entry and head in each of the three launches) and what the V and g rows that are not gathered behind dropped
    entries save.  --dropout: only this part (and the copy rate).
-Usage: probe_attention.py [--out FILE] [--fused | --backward | --heads | --gat | --bf16 | --bias | --dropout] [graph ...]   (default: pubmed.csv flickr reddit soc-sign-epinions)"""
+11. Attention dropout in GAT (flex_gat_attention_dropout and its backward call), (k, H) = (64, 8), (128, 4), (256, 8), p = 0.1 and 0.6,
+   same graphs and protocol: the forward (with dP) and the backward against the undropped flex_gat_attention and
+   flex_gat_attention_backward on the same plan in the same process.  --gat-dropout: only this part (and the copy rate).
+Usage: probe_attention.py [--out FILE] [--fused | --backward | --heads | --gat | --bf16 | --bias | --dropout | --gat-dropout] [graph ...]   (default: pubmed.csv flickr reddit soc-sign-epinions)"""
 import ctypes as C
 import os
 import subprocess
@@ -473,14 +476,40 @@ def probe_dropout(name, a):
         del plan
 
 
+def probe_gat_dropout(name, a):
+    gen = torch.Generator(device="cuda").manual_seed(9)
+    seed, slope = 0x0123456789ABCDEF, 0.2
+    for k, H in ((64, 8), (128, 4), (256, 8)):
+        d = k // H
+        plan = flex_amd.Plan(a, k, attention=True, attention_backward=True)  # one plan serves every contender
+        el, er = (torch.rand((r, H), device="cuda", generator=gen) * 4 - 2 for r in (a.m, a.n))
+        V, g = (torch.rand((r, k), device="cuda", generator=gen) * 2 - 1 for r in (a.n, a.m))
+        out, gv = torch.empty((a.m, k), device="cuda"), torch.empty((a.n, k), device="cuda")
+        gel, ger = torch.empty((a.m, H), device="cuda"), torch.empty((a.n, H), device="cuda")
+        P, W = (torch.empty((a.nnz, H), device="cuda") for _ in range(2))
+        fns = {"forward": lambda: plan.gat_attention(el, er, V, slope, out=out, p=P),
+               "backward": lambda: plan.gat_attention_backward(el, er, V, P, g, slope, grad_el=gel, grad_er=ger, grad_v=gv, work=W)}
+        for p_ in (0.1, 0.6):
+            fns[f"forward p={p_}"] = lambda p_=p_: plan.gat_attention_dropout(el, er, V, slope, p_, seed, out=out, probs=P)
+            fns[f"backward p={p_}"] = lambda p_=p_: plan.gat_attention_dropout_backward(el, er, V, P, g, slope, p_, seed, grad_el=gel, grad_er=ger,
+                                                                                       grad_v=gv, work=W)
+        plan.gat_attention(el, er, V, slope, out=out, p=P)  # P holds probabilities for every backward
+        n = max(3, min(100, int(1e8 / max(1, a.nnz * k))))
+        best, spread = _alternate(fns, n)
+        say(f"{name} k={k} H={H} d={d} gat dropout: " + "  ".join(f"{key} {best[key]:.1f} us (+{spread[key]:.0f} % over 3 rounds)" for key in fns)
+            + "  dropout / no dropout: " + "  ".join(f"{w} p={p_} {best[f'{w} p={p_}'] / best[w]:.2f}x" for w in ("forward", "backward") for p_ in (0.1, 0.6))
+            + "  extra memory: none (the mask is recomputed from the seed)")
+        del plan
+
+
 def main():
     args = sys.argv[1:]
     out = os.path.join(ROOT, "profiles", "attention_probe.txt")
     if args[:1] == ["--out"]:
         out, args = args[1], args[2:]
-    fused_only, backward_only, heads_only, gat_only, bf16_only, bias_only, dropout_only = (
-        args[:1] == [flag] for flag in ("--fused", "--backward", "--heads", "--gat", "--bf16", "--bias", "--dropout"))
-    only = fused_only or backward_only or heads_only or gat_only or bf16_only or bias_only or dropout_only
+    fused_only, backward_only, heads_only, gat_only, bf16_only, bias_only, dropout_only, gat_dropout_only = (
+        args[:1] == [flag] for flag in ("--fused", "--backward", "--heads", "--gat", "--bf16", "--bias", "--dropout", "--gat-dropout"))
+    only = fused_only or backward_only or heads_only or gat_only or bf16_only or bias_only or dropout_only or gat_dropout_only
     if only:
         args = args[1:]
     else:
@@ -505,6 +534,8 @@ def main():
             probe_bias(name, a)
         if dropout_only or not only:
             probe_dropout(name, a)
+        if gat_dropout_only or not only:
+            probe_gat_dropout(name, a)
     with open(out, "a" if only else "w") as f:  # a part is appended, the whole run starts the file
         f.write("\n".join(LINES) + "\n")
 
