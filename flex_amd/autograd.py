@@ -12,8 +12,10 @@ LeakyReLU(el[row] + er[col]) per head in the same three launches (flex_gat_atten
 attention(..., bias=b) adds a learned term per entry and head to the scaled score before the softmax, in float32 or bfloat16 rows, still
 in three launches (flex_attention_bias, flex_attention_bf16_bias and their backward calls).  attention(..., dropout=p) drops the
 probabilities after the softmax, with or without a bias, in the same three launches (flex_attention_dropout, flex_attention_bf16_dropout
-and their backward calls): the mask is a hash of (seed, entry, head), so autograd keeps the seed and no mask.  torch is imported lazily, as
-in binding.py."""
+and their backward calls): the mask is a hash of (seed, entry, head), so autograd keeps the seed and no mask.  gat_attention on a
+torch.bfloat16 V, with or without dropout, runs the same three launches on bf16 V rows (flex_gat_attention_bf16,
+flex_gat_attention_bf16_dropout and their backward calls: float32 scores and sums, Out and grad V in bfloat16).  torch is imported
+lazily, as in binding.py."""
 from __future__ import annotations
 
 from . import binding
@@ -335,6 +337,65 @@ def gat_dropout_functions():
     return _gat_dropout_cache
 
 
+def _gat_bf16_function():
+    import torch
+
+    class _FusedGatAttentionBf16(torch.autograd.Function):
+        """_FusedGatAttention on torch.bfloat16 V (el and er float32): flex_gat_attention_bf16 in one launch, scores, softmax and sums in
+        float32, alpha [nnz, heads] kept in float32 only when a gradient is needed; backward: the one call
+        flex_gat_attention_bf16_backward (two launches) for the gradients that are needed -- grad V in bfloat16, grad el and grad er in
+        float32.  Only on an operator made with fused_attention=True and fused_backward=True."""
+
+        @staticmethod
+        def forward(ctx, el, er, V, op, slope):
+            el, er, V = el.contiguous(), er.contiguous(), V.contiguous()
+            p = torch.zeros((op.nnz, el.shape[1]), dtype=torch.float32, device=V.device) if any(ctx.needs_input_grad[:3]) else None
+            out = op.plan.gat_attention_bf16(el, er, V, slope, p=p)
+            ctx.op, ctx.slope = op, slope
+            ctx.save_for_backward(el, er, V, p)
+            return out
+
+        @staticmethod
+        def backward(ctx, grad_out):
+            el, er, V, p = ctx.saved_tensors
+            grads = ctx.op.plan.gat_attention_bf16_backward(el, er, V, p, grad_out.contiguous(), ctx.slope, want=tuple(ctx.needs_input_grad[:3]))
+            return (*grads, None, None)
+
+    class _FusedGatAttentionBf16Dropout(torch.autograd.Function):
+        """_FusedGatAttentionBf16 with the probabilities dropped after the softmax: flex_gat_attention_bf16_dropout and its backward under
+        the same drop_p and seed, which recomputes the mask from the seed -- no mask is stored."""
+
+        @staticmethod
+        def forward(ctx, el, er, V, op, slope, drop_p, seed):
+            el, er, V = el.contiguous(), er.contiguous(), V.contiguous()
+            p = torch.zeros((op.nnz, el.shape[1]), dtype=torch.float32, device=V.device) if any(ctx.needs_input_grad[:3]) else None
+            out = op.plan.gat_attention_bf16_dropout(el, er, V, slope, drop_p, seed, probs=p)
+            ctx.op, ctx.slope, ctx.drop_p, ctx.seed = op, slope, drop_p, seed
+            ctx.save_for_backward(el, er, V, p)
+            return out
+
+        @staticmethod
+        def backward(ctx, grad_out):
+            el, er, V, p = ctx.saved_tensors
+            grads = ctx.op.plan.gat_attention_bf16_dropout_backward(el, er, V, p, grad_out.contiguous(), ctx.slope, ctx.drop_p, ctx.seed,
+                                                                    want=tuple(ctx.needs_input_grad[:3]))
+            return (*grads, None, None, None, None)
+
+    return (_FusedGatAttentionBf16, _FusedGatAttentionBf16Dropout)
+
+
+_gat_bf16_cache = None
+
+
+def gat_bf16_functions():
+    """(_FusedGatAttentionBf16, _FusedGatAttentionBf16Dropout): the autograd Functions of the GAT attention on bfloat16 V, built at first
+    use; functions() keeps its ten, dropout_functions() and gat_dropout_functions() their one each."""
+    global _gat_bf16_cache
+    if _gat_bf16_cache is None:
+        _gat_bf16_cache = _gat_bf16_function()
+    return _gat_bf16_cache
+
+
 class SparseOperator:
     """C = A B for a fixed sparse pattern A, differentiable in B: grad_B = A^T grad_C.  Keeps the plan of A (k columns) and the plan of A^T.
     `a` is an m x n HostCsr; op(B) takes B [n, k] and returns C [m, k], float32 cuda tensors.
@@ -349,7 +410,8 @@ class SparseOperator:
     op.attention is one call of two launches (flex_attention_backward) that sets no plan's values.  Off by default.
     With both fused flags the operator also offers op.gat_attention(el, er, V, negative_slope): GAT's additive attention, H = el.shape[1]
     heads in one forward launch and two backward launches (flex_gat_attention), differentiable in el [m, H], er [n, H] and V [n, k];
-    dropout= drops its probabilities after the softmax in the same launches (flex_gat_attention_dropout).
+    dropout= drops its probabilities after the softmax in the same launches (flex_gat_attention_dropout); a torch.bfloat16 V takes the
+    bf16 kernels (flex_gat_attention_bf16, flex_gat_attention_bf16_dropout), Out and grad V in bfloat16.
     bf16=True: both plans are made with FLEX_PLAN_BF16 (k a multiple of 8): op(B) takes and returns torch.bfloat16 (float32 raises
     TypeError, as bfloat16 does on an fp32 operator), sums in float32, and backpropagates A^T grad_C in bfloat16 through flex_spmm_bf16 on
     the transposed plan.  The plain product only: NotImplementedError with learn_values, the fused flags or values=."""
@@ -482,15 +544,27 @@ class SparseOperator:
         kept ones scaled by 1 / (1 - dropout), in the same three launches (flex_gat_attention_dropout): the mask is a hash of (seed,
         entry, head) that the backward recomputes, so nothing nnz-sized is added.  seed=None draws 63 bits from torch's default
         generator (torch.manual_seed reproduces a run); the seed is kept for the backward.  dropout=0.0 or training=False takes the path
-        above exactly as without the arguments."""
+        above exactly as without the arguments.
+        A torch.bfloat16 V takes the bf16 kernels (flex_gat_attention_bf16, flex_gat_attention_bf16_dropout): V rows are gathered as
+        bfloat16, every sum is float32, Out and grad V come back in bfloat16, rounded once.  el and er are then float32 or bfloat16;
+        bfloat16 ones are widened before the call (the scores stay float32) and their gradients come back in bfloat16.  Any other mix
+        of dtypes is a TypeError."""
         if not 0.0 <= dropout < 1.0:  # a NaN fails this too
             raise ValueError(f"dropout must be a probability in [0, 1), not {dropout}")
         if not (self.fused_attention and self.fused_backward):
             raise NotImplementedError("gat_attention needs SparseOperator(..., learn_values=True, fused_attention=True, fused_backward=True): "
                                       "only the fused forward and backward compute the additive score")
+        import torch
+        bf16 = V.dtype == torch.bfloat16
+        if bf16:
+            if any(t.dtype not in (torch.float32, torch.bfloat16) for t in (el, er)):
+                raise TypeError(f"gat_attention on bfloat16 V takes el and er in float32 or bfloat16, not {el.dtype} and {er.dtype}")
+            el, er = el.float(), er.float()  # outside the Function: torch carries a bfloat16 leaf's gradient back to bfloat16
+        elif not (el.dtype == er.dtype == V.dtype == torch.float32):
+            raise TypeError(f"gat_attention takes float32 el, er and V, or bfloat16 V with float32 or bfloat16 el and er, not {el.dtype}, {er.dtype} and {V.dtype}")
         if dropout > 0 and training:
-            import torch
             if seed is None:
                 seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
-            return gat_dropout_functions()[0].apply(el, er, V, self, float(negative_slope), float(dropout), int(seed) & 0xFFFFFFFFFFFFFFFF)
-        return functions()[7].apply(el, er, V, self, float(negative_slope))
+            fn = gat_bf16_functions()[1] if bf16 else gat_dropout_functions()[0]
+            return fn.apply(el, er, V, self, float(negative_slope), float(dropout), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        return (gat_bf16_functions()[0] if bf16 else functions()[7]).apply(el, er, V, self, float(negative_slope))

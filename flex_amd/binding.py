@@ -169,6 +169,7 @@ SYMBOLS = [
     "flex_attention_bias", "flex_attention_bias_backward", "flex_attention_bf16_bias", "flex_attention_bf16_bias_backward",
     "flex_attention_dropout", "flex_attention_dropout_backward", "flex_attention_bf16_dropout", "flex_attention_bf16_dropout_backward",
     "flex_dropout_mask", "flex_gat_attention_dropout", "flex_gat_attention_dropout_backward",
+    "flex_gat_attention_bf16", "flex_gat_attention_bf16_backward", "flex_gat_attention_bf16_dropout", "flex_gat_attention_bf16_dropout_backward",
 ]
 
 _lib = None
@@ -285,7 +286,11 @@ def _values_fn(name: str):
                       "flex_gat_attention": [vp, i32, vp, vp, vp, fl, vp, vp, vp],
                       "flex_gat_attention_backward": [vp, i32, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp],
                       "flex_gat_attention_dropout": [vp, i32, vp, vp, vp, fl, fl, u64, vp, vp, vp],
-                      "flex_gat_attention_dropout_backward": [vp, i32, vp, vp, vp, vp, vp, fl, fl, u64, vp, vp, vp, vp, vp]}[name]
+                      "flex_gat_attention_dropout_backward": [vp, i32, vp, vp, vp, vp, vp, fl, fl, u64, vp, vp, vp, vp, vp],
+                      "flex_gat_attention_bf16": [vp, i32, vp, vp, vp, fl, vp, vp, vp],
+                      "flex_gat_attention_bf16_backward": [vp, i32, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp],
+                      "flex_gat_attention_bf16_dropout": [vp, i32, vp, vp, vp, fl, fl, u64, vp, vp, vp],
+                      "flex_gat_attention_bf16_dropout_backward": [vp, i32, vp, vp, vp, vp, vp, fl, fl, u64, vp, vp, vp, vp, vp]}[name]
     return f
 
 
@@ -1123,6 +1128,92 @@ class Plan:
                                                 int(seed) & 0xFFFFFFFFFFFFFFFF, *(None if t is None else t.data_ptr() for t in outs),
                                                 work.data_ptr(), torch.cuda.current_stream(V.device).cuda_stream)
         return tuple(outs)
+
+    def gat_attention_bf16_ptr(self, heads: int, dEl_ptr: int, dEr_ptr: int, dV_ptr: int, slope: float, dOut_ptr: int, dP_ptr: int | None = None,
+                               stream: int = 0):
+        """flex_gat_attention_bf16: gat_attention_ptr with bf16 rows V and Out; dEl, dEr and dP (optional) stay floats."""
+        _check(_values_fn("flex_gat_attention_bf16")(self._h, heads, dEl_ptr, dEr_ptr, dV_ptr, slope, dOut_ptr, dP_ptr, stream),
+               "flex_gat_attention_bf16")
+
+    def gat_attention_bf16_backward_ptr(self, heads: int, dEl_ptr: int, dEr_ptr: int, dV_ptr: int, dP_ptr: int, dGradOut_ptr: int, slope: float,
+                                        dGradEl_ptr: int | None, dGradEr_ptr: int | None, dGradV_ptr: int | None, dWork_ptr: int, stream: int = 0):
+        """flex_gat_attention_bf16_backward: gat_attention_backward_ptr with bf16 rows V, g and gV; the rest stays floats."""
+        _check(_values_fn("flex_gat_attention_bf16_backward")(self._h, heads, dEl_ptr, dEr_ptr, dV_ptr, dP_ptr, dGradOut_ptr, slope, dGradEl_ptr,
+                                                              dGradEr_ptr, dGradV_ptr, dWork_ptr, stream), "flex_gat_attention_bf16_backward")
+
+    def gat_attention_bf16_dropout_ptr(self, heads: int, dEl_ptr: int, dEr_ptr: int, dV_ptr: int, slope: float, p: float, seed: int, dOut_ptr: int,
+                                       dP_ptr: int | None = None, stream: int = 0):
+        """flex_gat_attention_bf16_dropout: gat_attention_dropout_ptr with bf16 rows V and Out."""
+        _check(_values_fn("flex_gat_attention_bf16_dropout")(self._h, heads, dEl_ptr, dEr_ptr, dV_ptr, slope, p, seed, dOut_ptr, dP_ptr, stream),
+               "flex_gat_attention_bf16_dropout")
+
+    def gat_attention_bf16_dropout_backward_ptr(self, heads: int, dEl_ptr: int, dEr_ptr: int, dV_ptr: int, dP_ptr: int, dGradOut_ptr: int,
+                                                slope: float, p: float, seed: int, dGradEl_ptr: int | None, dGradEr_ptr: int | None,
+                                                dGradV_ptr: int | None, dWork_ptr: int, stream: int = 0):
+        """flex_gat_attention_bf16_dropout_backward: gat_attention_dropout_backward_ptr with bf16 rows V, g and gV."""
+        _check(_values_fn("flex_gat_attention_bf16_dropout_backward")(self._h, heads, dEl_ptr, dEr_ptr, dV_ptr, dP_ptr, dGradOut_ptr, slope, p, seed,
+                                                                      dGradEl_ptr, dGradEr_ptr, dGradV_ptr, dWork_ptr, stream),
+               "flex_gat_attention_bf16_dropout_backward")
+
+    def _gat_bf16(self, run, el, er, V, args, out, p):
+        """The forward of the two bf16 GAT calls: run(heads, el, er, V, *args, out, p, stream) on bfloat16 V and out, float32 el, er, p."""
+        import torch
+        i = self.info()
+        heads = self._node_scalars(el, er)
+        assert V.is_cuda and V.dtype == torch.bfloat16 and V.is_contiguous() and tuple(V.shape) == (i["n"], i["k"]), "V: bfloat16 cuda [n, k]"
+        if out is None:  # every row is written, except by a plan without entries, which launches nothing
+            out = (torch.empty if i["nnz"] else torch.zeros)((i["m"], i["k"]), dtype=torch.bfloat16, device=V.device)
+        assert out.is_cuda and out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (i["m"], i["k"])
+        if p is not None:
+            self._head_edge_arrays(heads, p)
+        run(heads, el.data_ptr(), er.data_ptr(), V.data_ptr(), *args, out.data_ptr(), None if p is None else p.data_ptr(),
+            torch.cuda.current_stream(V.device).cuda_stream)
+        return out
+
+    def _gat_bf16_backward(self, run, el, er, V, p, grad_out, args, grads, work, want):
+        """The backward of the two bf16 GAT calls: V, grad_out and gV bfloat16; el, er, gEl, gEr, p and work float32."""
+        import torch
+        i = self.info()
+        heads = self._node_scalars(el, er)
+        for t, rows in ((V, i["n"]), (grad_out, i["m"])):
+            assert t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous() and tuple(t.shape) == (rows, i["k"]), "bfloat16 cuda [rows, k]"
+        if work is None:
+            work = torch.empty((self.src_nnz, heads), dtype=torch.float32, device=V.device)
+        self._head_edge_arrays(heads, p, work)
+        outs = []
+        shapes = (((i["m"], heads), torch.float32), ((i["n"], heads), torch.float32), ((i["n"], i["k"]), torch.bfloat16))
+        for wanted, t, (shape, dtype) in zip(want, grads, shapes):
+            if wanted and t is None:  # every row is written, except by a plan without entries, which launches nothing
+                t = (torch.empty if i["nnz"] else torch.zeros)(shape, dtype=dtype, device=V.device)
+            if wanted:
+                assert t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape
+            outs.append(t if wanted else None)
+        run(heads, el.data_ptr(), er.data_ptr(), V.data_ptr(), p.data_ptr(), grad_out.data_ptr(), *args,
+            *(None if t is None else t.data_ptr() for t in outs), work.data_ptr(), torch.cuda.current_stream(V.device).cuda_stream)
+        return tuple(outs)
+
+    def gat_attention_bf16(self, el, er, V, slope: float = 0.2, out=None, p=None):
+        """flex_gat_attention_bf16: gat_attention() on torch.bfloat16 V [n, k]; out [m, k] is bfloat16, every sum float32 and each element
+        rounded once at its store.  el [m, H], er [n, H] and p (optional, [a.nnz, H]) are float32."""
+        return self._gat_bf16(self.gat_attention_bf16_ptr, el, er, V, (slope,), out, p)
+
+    def gat_attention_bf16_backward(self, el, er, V, p, grad_out, slope: float = 0.2, grad_el=None, grad_er=None, grad_v=None, work=None,
+                                    want=(True, True, True)):
+        """flex_gat_attention_bf16_backward: gat_attention_backward() on torch.bfloat16 V and grad_out; gV is bfloat16, rounded once at its
+        store; gEl, gEr, p and work are float32."""
+        return self._gat_bf16_backward(self.gat_attention_bf16_backward_ptr, el, er, V, p, grad_out, (slope,), (grad_el, grad_er, grad_v), work, want)
+
+    def gat_attention_bf16_dropout(self, el, er, V, slope: float, p: float, seed: int, out=None, probs=None):
+        """flex_gat_attention_bf16_dropout: gat_attention_dropout() on torch.bfloat16 V; out is bfloat16; probs (optional, float32
+        [a.nnz, H]) receives the UNDROPPED alpha."""
+        return self._gat_bf16(self.gat_attention_bf16_dropout_ptr, el, er, V, (slope, p, int(seed) & 0xFFFFFFFFFFFFFFFF), out, probs)
+
+    def gat_attention_bf16_dropout_backward(self, el, er, V, probs, grad_out, slope: float, p: float, seed: int, grad_el=None, grad_er=None,
+                                            grad_v=None, work=None, want=(True, True, True)):
+        """flex_gat_attention_bf16_dropout_backward: gat_attention_dropout_backward() on torch.bfloat16 V and grad_out under the same p and
+        seed; gV is bfloat16; gEl, gEr, probs and work are float32."""
+        return self._gat_bf16_backward(self.gat_attention_bf16_dropout_backward_ptr, el, er, V, probs, grad_out,
+                                       (slope, p, int(seed) & 0xFFFFFFFFFFFFFFFF), (grad_el, grad_er, grad_v), work, want)
 
     def destroy(self):
         if getattr(self, "_h", None) and self._h.value:

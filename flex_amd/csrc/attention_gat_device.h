@@ -1,6 +1,7 @@
 // attention_gat_device.h -- the sweeps of the fused GAT attention, shared by attention_gat_kernels.hip (flex_gat_attention,
-// flex_gat_attention_backward: DROP off, the sweeps are what they were) and attention_gat_dropout_kernels.hip
-// (flex_gat_attention_dropout, flex_gat_attention_dropout_backward: DROP on).
+// flex_gat_attention_backward: DROP off, the sweeps are what they were), attention_gat_dropout_kernels.hip
+// (flex_gat_attention_dropout, flex_gat_attention_dropout_backward: DROP on) and attention_gat_bf16_kernels.hip (the four
+// flex_gat_attention_bf16 calls: E = flex_bf16, DROP off and on).
 //
 // The walk is attention_heads_kernels.hip's (attention_device.h): the same view, items, groups, slot / wave / block ownership by
 // place_of, W = sddmm_lanes(k) lanes per slot, four entries per pass, four columns per lane and slab, the XCD remap, State<1> per lane
@@ -23,6 +24,11 @@
 // the factor c, a dropped one is selected out: its V row (forward, row backward sweep 1) or g row (column backward) is not gathered, so
 // a non-finite row behind a dropped entry reaches nothing.  The er, P and dx loads do not see the mask; dx holds it through da, so gEl
 // and gEr need no second look at it, and the column launch uses the mask for gV alone.
+//
+// E: the element type of the row operands V, Out, G and GV, deduced from the pointers: float, or flex_bf16 in
+// attention_gat_bf16_kernels.hip.  The sweeps reach a row through load_cols, store_cols and write_row alone (attention_device.h), which
+// hand over and take fp32: with flex_bf16 a lane's four columns are one 8-byte access, widened exactly and rounded once at the store.
+// El, Er, P, DX, GEl, GEr, Work and every sum stay float, so on the widened operands the edge arrays and gEl, gEr have the fp32 bits.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -38,10 +44,10 @@ __device__ __forceinline__ float leaky(float x, float slope) { return x > 0.f ? 
 
 // ---- forward
 
-template <int W, int NS, bool DROP>
+template <int W, int NS, bool DROP, class E>
 __device__ __forceinline__ void run_item(const View &v, const HeadSplit &hs, const uint4 &it, int kind, const float *__restrict__ El,
-                                         const float *__restrict__ Er, const float *__restrict__ V, float slope, const DropMask &dm,
-                                         float *__restrict__ Out, float *__restrict__ P, uint32_t lane, uint32_t w, HeadsShared<W, NS> &sh) {
+                                         const float *__restrict__ Er, const E *__restrict__ V, float slope, const DropMask &dm,
+                                         E *__restrict__ Out, float *__restrict__ P, uint32_t lane, uint32_t w, HeadsShared<W, NS> &sh) {
     const uint32_t slot = lane / W, li = lane % W;
     const int slot_lane0 = static_cast<int>(lane - li);
     const HeadLane hl(hs, li);
@@ -69,7 +75,8 @@ __device__ __forceinline__ void run_item(const View &v, const HeadSplit &hs, con
         for (int u = 0; u < U; ++u) {
             const uint32_t col = __shfl(idx, slot_lane0 + u);
             valid[u] = j0 + u < pl.len;
-            const float *vr = V + static_cast<size_t>(col) * v.ldb, *ec = Er + static_cast<size_t>(col) * static_cast<size_t>(hs.H);
+            const E *vr = V + static_cast<size_t>(col) * v.ldb;
+            const float *ec = Er + static_cast<size_t>(col) * static_cast<size_t>(hs.H);
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
                 keep[u][s] = true;
@@ -146,7 +153,7 @@ __device__ __forceinline__ void run_item(const View &v, const HeadSplit &hs, con
         }
     }
     if (writer) {
-        float *orow = Out + static_cast<size_t>(pl.line) * v.ldc;
+        E *orow = Out + static_cast<size_t>(pl.line) * v.ldc;
 #pragma unroll
         for (int s = 0; s < NS; ++s) write_row<1, true>(orow + 4 * W * s, st[s], li, W, v.k - 4 * W * s);
     }
@@ -177,10 +184,10 @@ struct RowShared {
 };
 
 // DROP: da of a kept entry is c <g, V>, da of a dropped one +0 and its V row is not gathered; delta, dz, dx and gEl follow from da
-template <int W, int NS, bool DROP>
+template <int W, int NS, bool DROP, class E>
 __device__ __forceinline__ void run_row(const View &v, const HeadSplit &hs, const uint4 &it, int kind, const float *__restrict__ El,
-                                        const float *__restrict__ Er, const float *__restrict__ V, const float *__restrict__ P,
-                                        const float *__restrict__ G, float slope, const DropMask &dm, float *__restrict__ GEl,
+                                        const float *__restrict__ Er, const E *__restrict__ V, const float *__restrict__ P,
+                                        const E *__restrict__ G, float slope, const DropMask &dm, float *__restrict__ GEl,
                                         float *__restrict__ Work, uint32_t lane, uint32_t w, RowShared<W, NS> &sh) {
     const uint32_t slot = lane / W, li = lane % W;
     const int slot_lane0 = static_cast<int>(lane - li);
@@ -189,7 +196,7 @@ __device__ __forceinline__ void run_row(const View &v, const HeadSplit &hs, cons
     const LaneHeads<W, NS> lh(hs, li, v.k);
     float4 g[NS];
     float elr[NS], delta[NS];
-    const float *grow = G + static_cast<size_t>(pl.line) * v.ldc;
+    const E *grow = G + static_cast<size_t>(pl.line) * v.ldc;
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
         g[s] = pl.has_line ? load_cols<true>(grow, 4 * static_cast<int>(li) + 4 * W * s, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -209,7 +216,7 @@ __device__ __forceinline__ void run_row(const View &v, const HeadSplit &hs, cons
         for (int u = 0; u < U; ++u) {
             const uint32_t col = __shfl(idx, slot_lane0 + u);
             valid[u] = j0 + u < pl.len;
-            const float *vr = V + static_cast<size_t>(col) * v.ldb;
+            const E *vr = V + static_cast<size_t>(col) * v.ldb;
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
                 keep[u][s] = true;
@@ -309,10 +316,10 @@ struct ColumnShared {
 
 // DROP: gV alone sees the mask (dx holds it already): a kept entry adds (p c) g; a dropped one adds 0 x 0, neither its p nor its g row
 // being read for gV
-template <int W, int NS, bool DROP>
-__device__ __forceinline__ void run_column(const ColumnView &v, const HeadSplit &hs, const uint4 &it, int kind, const float *__restrict__ G,
+template <int W, int NS, bool DROP, class E>
+__device__ __forceinline__ void run_column(const ColumnView &v, const HeadSplit &hs, const uint4 &it, int kind, const E *__restrict__ G,
                                            const float *__restrict__ P, const float *__restrict__ DX, const DropMask &dm,
-                                           float *__restrict__ GEr, float *__restrict__ GV, uint32_t lane, uint32_t w, ColumnShared<W, NS> &sh) {
+                                           float *__restrict__ GEr, E *__restrict__ GV, uint32_t lane, uint32_t w, ColumnShared<W, NS> &sh) {
     const uint32_t slot = lane / W, li = lane % W;
     const int slot_lane0 = static_cast<int>(lane - li);
     const HeadLane hl(hs, li);
@@ -337,7 +344,7 @@ __device__ __forceinline__ void run_column(const ColumnView &v, const HeadSplit 
         for (int u = 0; u < U; ++u) {
             const uint32_t row = __shfl(re.x, slot_lane0 + u), e = __shfl(re.y, slot_lane0 + u);
             valid[u] = j0 + u < pl.len;
-            const float *gr = G + static_cast<size_t>(row) * v.ldc;
+            const E *gr = G + static_cast<size_t>(row) * v.ldc;
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
                 const bool live = valid[u] && lh.live[s];

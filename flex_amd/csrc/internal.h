@@ -417,6 +417,15 @@ int launch_gat_dropout_rows_backward(const flex_plan *p, const AttentionPick &pi
                                      hipStream_t s);
 int launch_gat_dropout_columns_backward(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const float *G, const float *P,
                                         const float *DX, const DropMask &dm, float *GEr, float *GV, hipStream_t s);
+// GAT on flex_bf16 V, Out, G and GV rows, dm NULL without dropout (attention_gat_bf16_kernels.hip, which also holds the four entry
+// points: the host simulator has no stand-ins for these)
+int launch_gat_bf16_rows(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const float *El, const float *Er, const flex_bf16 *V,
+                         float slope, const DropMask *dm, flex_bf16 *Out, float *P, hipStream_t s);
+int launch_gat_bf16_rows_backward(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const float *El, const float *Er,
+                                  const flex_bf16 *V, const float *P, const flex_bf16 *G, float slope, const DropMask *dm, float *GEl, float *Work,
+                                  hipStream_t s);
+int launch_gat_bf16_columns_backward(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const flex_bf16 *G, const float *P,
+                                     const float *DX, const DropMask *dm, float *GEr, flex_bf16 *GV, hipStream_t s);
 }  // namespace attention
 
 // FLEX_PLAN_TIMING in the environment: phase times of the planner and the clustering on stderr.  The only environment

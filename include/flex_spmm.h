@@ -34,6 +34,7 @@ extern "C" {
                               the equally additive flex_attention_bias, flex_attention_bf16_bias and their backward calls (four new calls, no flag, no struct),
                               the equally additive flex_attention_dropout, flex_attention_bf16_dropout, their backward calls and flex_dropout_mask (five new calls, no flag, no struct),
                               the equally additive flex_gat_attention_dropout and flex_gat_attention_dropout_backward (two new calls, no flag, no struct),
+                              the equally additive flex_gat_attention_bf16, flex_gat_attention_bf16_dropout and their backward calls (four new calls, no flag, no struct),
                               and the retired flex_plan_tuning.block_ablate, which keeps its place as block_ablate_retired and must be zero.
                               3: plan-time knobs leave the environment for the struct flex_plan_tuning, flex_plan_desc.tuning, flex_plan_get_tuning,
                               flex_order_cluster_ex, flex_set_host_threads; split rows are summed by a second launch by default.
@@ -784,6 +785,47 @@ extern int flex_gat_attention_dropout(const flex_plan *plan, int heads, const fl
 extern int flex_gat_attention_dropout_backward(const flex_plan *plan, int heads, const float *dEl, const float *dEr, const float *dV, const float *dP,
                                         const float *dGradOut, float slope, float drop_p, uint64_t seed, float *dGradEl, float *dGradEr,
                                         float *dGradV, float *dWork, flex_stream_t stream);
+
+/* The fused GAT attention on bf16 V rows, with and without dropout: flex_gat_attention, flex_gat_attention_backward,
+ * flex_gat_attention_dropout and flex_gat_attention_dropout_backward, argument for argument, with V, Out, g and gV held as flex_bf16 --
+ * half the bytes of the one row a nonzero gathers (the V row in the forward and in the rows' backward launch, the g row in the columns')
+ * -- in the same ONE forward launch and TWO backward launches, on the same plans: no new plan flag and no new image.  No reference
+ * counterpart.
+ *   dV, dOut, dGradOut, dGradV          flex_bf16 rows (the upper 16 bits of an IEEE float, torch.bfloat16); ldb and ldc are element strides
+ *   dEl, dEr, dGradEl, dGradEr          fp32 [rows, H] / [n, H] as before: one scalar per node and head has nothing to save, and a score
+ *                                       rounded to 8 bits would not be GAT's softmax
+ *   dP, dWork                           fp32 [nnz, H], entry-major, unrounded
+ * Definition: read every bf16 operand as the fp32 number it is (the conversion is exact); then everything is what the four fp32 GAT
+ * calls define -- x, the LeakyReLU, the mask (-inf) and poison (+inf / NaN) rules per head, +0 rows, "every entry (with dropout: every
+ * kept entry) multiplies its V row", da, delta, dx, gEl, gEr, gV, the mask bit of (seed, e H + h), dP keeping the UNDROPPED alpha --
+ * with every product and sum in fp32 in the fp32 kernels' order.  Only at the single store of each element of Out and gV the fp32 value
+ * is rounded to bf16, to nearest even: a NaN stays a NaN, +-inf stays +-inf, a finite value beyond the largest finite bf16 becomes
+ * +-inf, and a poisoned head still writes NaN into its own d columns only.  dP, dWork, gEl and gEr are what the fp32 calls write for
+ * the widened operands, bit for bit, and Out and gV are the bf16 roundings of theirs.
+ * Checks: the fp32 GAT calls' table, refusal for refusal and in the same order (heads < 1, a bad slope, in the dropout pair a drop_p
+ * outside [0, 1), a NULL operand, dWork == dP: FLEX_ERR_INVALID; k % heads, d outside {4, ..., 256}, k > 1024: FLEX_ERR_UNSUPPORTED), with
+ * one alignment rule over V, Out / g, gV: k % 4 == 0, ldb % 4 == 0, ldc % 4 == 0 in elements and every bf16 row operand 8-byte aligned
+ * (a NULL output counts as aligned); anything else is FLEX_ERR_UNSUPPORTED.  drop_p == 0: once nothing is refused the call runs the
+ * undropped bf16 launch, so every output has flex_gat_attention_bf16's bits.  A plan without entries: FLEX_OK, nothing written.  The
+ * forward runs on row-range shards (the mask at the whole matrix's entry indices), the backward does not.  Nothing is enqueued by a
+ * refused call.  Asynchronous on `stream`, no allocation, no host synchronisation (safe to capture in a hipGraph), no atomics, fixed
+ * order: bit-identical run to run.
+ * Accuracy, against float64 on the bf16 V and g (and the fp32 el, er and p): dP, dWork, gEl and gEr carry the bounds of the fp32 GAT
+ * calls (with dropout: of flex_gat_attention_dropout) unchanged.  An element y = rn_bf16(x32) of Out or gV, whose fp32 value x32 lies
+ * within those calls' bound32 of the float64 x64, satisfies
+ *     |y - x64| <= bound32 + 2^-8 (|x64| + bound32) + 2^-134
+ * 2^-8 being the unit roundoff of bf16 and 2^-134 half its smallest subnormal (flex_attention_bf16's bound).
+ * The four calls are written `extern`: the GPU library alone defines them (attention_gat_bf16_kernels.hip). */
+extern int flex_gat_attention_bf16(const flex_plan *plan, int heads, const float *dEl, const float *dEr, const flex_bf16 *dV, float slope,
+                            flex_bf16 *dOut, float *dP, flex_stream_t stream);
+extern int flex_gat_attention_bf16_backward(const flex_plan *plan, int heads, const float *dEl, const float *dEr, const flex_bf16 *dV,
+                                     const float *dP, const flex_bf16 *dGradOut, float slope, float *dGradEl, float *dGradEr,
+                                     flex_bf16 *dGradV, float *dWork, flex_stream_t stream);
+extern int flex_gat_attention_bf16_dropout(const flex_plan *plan, int heads, const float *dEl, const float *dEr, const flex_bf16 *dV, float slope,
+                                    float drop_p, uint64_t seed, flex_bf16 *dOut, float *dP, flex_stream_t stream);
+extern int flex_gat_attention_bf16_dropout_backward(const flex_plan *plan, int heads, const float *dEl, const float *dEr, const flex_bf16 *dV,
+                                             const float *dP, const flex_bf16 *dGradOut, float slope, float drop_p, uint64_t seed,
+                                             float *dGradEl, float *dGradEr, flex_bf16 *dGradV, float *dWork, flex_stream_t stream);
 
 /* ≙ alpha_freeMatGPU (mat.cuh:184-193). */
 int flex_plan_destroy(flex_plan *plan);

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Sparse graph attention, measured: the error of the exponential the edge softmax may use, and the time of flex_edge_softmax,
 flex_edge_softmax_backward and a whole attention step.  Writes profiles/attention_probe.txt (or the file given with --out): the whole run
-starts the file, a run of one part (--fused, --backward, --heads, --gat, --bf16, --bias, --dropout, --gat-dropout) appends to it.
+starts the file, a run of one part (--fused, --backward, --heads, --gat, --bf16, --bias, --dropout, --gat-dropout, --gat-bf16) appends to it.
 
 1. tools/exp_error.hip (built here with hipcc into flex_amd/lib if it is not there): the largest error in ulp of expf, __expf and
    exp2f on the prescaled argument over every fp32 argument in [-104, 0] against float64 exp.
@@ -45,7 +45,11 @@ starts the file, a run of one part (--fused, --backward, --heads, --gat, --bf16,
 11. Attention dropout in GAT (flex_gat_attention_dropout and its backward call), (k, H) = (64, 8), (128, 4), (256, 8), p = 0.1 and 0.6,
    same graphs and protocol: the forward (with dP) and the backward against the undropped flex_gat_attention and
    flex_gat_attention_backward on the same plan in the same process.  --gat-dropout: only this part (and the copy rate).
-Usage: probe_attention.py [--out FILE] [--fused | --backward | --heads | --gat | --bf16 | --bias | --dropout | --gat-dropout] [graph ...]   (default: pubmed.csv flickr reddit soc-sign-epinions)"""
+12. GAT on bf16 V rows (flex_gat_attention_bf16, flex_gat_attention_bf16_dropout and their backward calls), (k, H) = (64, 8), (128, 4),
+   (256, 8), without dropout and with p = 0.6, same graphs and protocol: the forward (with dP), the two-launch backward and the autograd
+   step of gat_attention on bfloat16 V against the same three on float32 V (flex_gat_attention, flex_gat_attention_dropout) on the same
+   operator, in the same process.  --gat-bf16: only this part (and the copy rate).
+Usage: probe_attention.py [--out FILE] [--fused | --backward | --heads | --gat | --bf16 | --bias | --dropout | --gat-dropout | --gat-bf16] [graph ...]   (default: pubmed.csv flickr reddit soc-sign-epinions)"""
 import ctypes as C
 import os
 import subprocess
@@ -502,14 +506,56 @@ def probe_gat_dropout(name, a):
         del plan
 
 
+def probe_gat_bf16(name, a):
+    gen = torch.Generator(device="cuda").manual_seed(10)
+    seed, slope, p_ = 0x0123456789ABCDEF, 0.2, 0.6
+    for k, H in ((64, 8), (128, 4), (256, 8)):
+        d = k // H
+        op = flex_amd.SparseOperator(a, k, learn_values=True, fused_attention=True, fused_backward=True)  # one plan serves every contender
+        plan = op.plan
+        el, er = (torch.rand((r, H), device="cuda", generator=gen) * 4 - 2 for r in (a.m, a.n))
+        V, g = (torch.rand((r, k), device="cuda", generator=gen) * 2 - 1 for r in (a.n, a.m))
+        rows = {torch.float32: (V, g), torch.bfloat16: (V.bfloat16(), g.bfloat16())}
+        outs = {dt: (torch.empty((a.m, k), device="cuda", dtype=dt), torch.empty((a.n, k), device="cuda", dtype=dt)) for dt in rows}
+        gel, ger = torch.empty((a.m, H), device="cuda"), torch.empty((a.n, H), device="cuda")
+        P, W = (torch.empty((a.nnz, H), device="cuda") for _ in range(2))
+        leaves = {dt: (el.clone().requires_grad_(), er.clone().requires_grad_(), r[0].clone().requires_grad_()) for dt, r in rows.items()}
+
+        def step(dt, dropped):
+            for x in leaves[dt]:
+                x.grad = None
+            op.gat_attention(*leaves[dt], slope, **(dict(dropout=p_, seed=seed) if dropped else {})).backward(rows[dt][1])
+
+        fns = {}
+        for dt, tag, plain, plain_b, drop, drop_b in (
+                (torch.float32, "fp32", plan.gat_attention, plan.gat_attention_backward, plan.gat_attention_dropout, plan.gat_attention_dropout_backward),
+                (torch.bfloat16, "bf16", plan.gat_attention_bf16, plan.gat_attention_bf16_backward, plan.gat_attention_bf16_dropout,
+                 plan.gat_attention_bf16_dropout_backward)):
+            (v, gg), (o, gv) = rows[dt], outs[dt]
+            fns[f"forward, {tag}"] = lambda v=v, o=o, f=plain: f(el, er, v, slope, out=o, p=P)
+            fns[f"backward, {tag}"] = lambda v=v, gg=gg, gv=gv, f=plain_b: f(el, er, v, P, gg, slope, grad_el=gel, grad_er=ger, grad_v=gv, work=W)
+            fns[f"step, {tag}"] = lambda dt=dt: step(dt, False)
+            fns[f"forward, {tag} p={p_}"] = lambda v=v, o=o, f=drop: f(el, er, v, slope, p_, seed, out=o, probs=P)
+            fns[f"backward, {tag} p={p_}"] = lambda v=v, gg=gg, gv=gv, f=drop_b: f(el, er, v, P, gg, slope, p_, seed, grad_el=gel, grad_er=ger, grad_v=gv, work=W)
+            fns[f"step, {tag} p={p_}"] = lambda dt=dt: step(dt, True)
+        plan.gat_attention(el, er, V, slope, out=outs[torch.float32][0], p=P)  # P holds probabilities for every backward
+        n = max(3, min(100, int(1e8 / max(1, a.nnz * k))))
+        best, spread = _alternate(fns, n)
+        say(f"{name} k={k} H={H} d={d} gat bf16: " + "  ".join(f"{key} {best[key]:.1f} us (+{spread[key]:.0f} % over 3 rounds)" for key in fns)
+            + "  fp32 / bf16: " + "  ".join(f"{w}{t} {best[f'{w}, fp32{t}'] / best[f'{w}, bf16{t}']:.2f}x" for t in ("", f" p={p_}") for w in ("forward", "backward", "step"))
+            + f"  row operands of a step: {2 * (a.m + a.n) * k * 2 / 2 ** 20:.1f} MiB in bf16, twice that in fp32 (V, Out and their gradients);"
+            + f" el, er, their gradients and the edge arrays ({8 * a.nnz * H / 2 ** 20:.1f} MiB) are fp32 either way")
+        del op, plan
+
+
 def main():
     args = sys.argv[1:]
     out = os.path.join(ROOT, "profiles", "attention_probe.txt")
     if args[:1] == ["--out"]:
         out, args = args[1], args[2:]
-    fused_only, backward_only, heads_only, gat_only, bf16_only, bias_only, dropout_only, gat_dropout_only = (
-        args[:1] == [flag] for flag in ("--fused", "--backward", "--heads", "--gat", "--bf16", "--bias", "--dropout", "--gat-dropout"))
-    only = fused_only or backward_only or heads_only or gat_only or bf16_only or bias_only or dropout_only or gat_dropout_only
+    fused_only, backward_only, heads_only, gat_only, bf16_only, bias_only, dropout_only, gat_dropout_only, gat_bf16_only = (
+        args[:1] == [flag] for flag in ("--fused", "--backward", "--heads", "--gat", "--bf16", "--bias", "--dropout", "--gat-dropout", "--gat-bf16"))
+    only = fused_only or backward_only or heads_only or gat_only or bf16_only or bias_only or dropout_only or gat_dropout_only or gat_bf16_only
     if only:
         args = args[1:]
     else:
@@ -536,6 +582,8 @@ def main():
             probe_dropout(name, a)
         if gat_dropout_only or not only:
             probe_gat_dropout(name, a)
+        if gat_bf16_only or not only:
+            probe_gat_bf16(name, a)
     with open(out, "a" if only else "w") as f:  # a part is appended, the whole run starts the file
         f.write("\n".join(LINES) + "\n")
 
