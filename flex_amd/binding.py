@@ -259,10 +259,11 @@ def lib():
 
 
 def _values_fn(name: str):
-    """flex_plan_set_values / flex_sddmm / flex_edge_softmax / flex_edge_softmax_backward / flex_attention / flex_attention_backward and the
-    two multi-head, the two bf16 and the two GAT calls and flex_spmm_bf16, looked up at first use and not when the library loads: a host-only build without the kernel files does not have to define them.  tests/hostsim
-    defines them all: the attention calls are the library's own entry points (csrc/attention_entry.h) on stand-in launchers that only log which
-    kernel the real ones would launch, the others are stand-ins that log the same way."""
+    """flex_plan_set_values / flex_sddmm / flex_edge_softmax / flex_edge_softmax_backward, the 22 fused-attention calls (flex_attention*,
+    flex_gat_attention*) and flex_spmm_bf16, looked up at first use and not when the library loads: a host-only build without the kernel
+    files does not have to define them.  tests/hostsim defines them all: the attention calls are the library's own entry points
+    (csrc/attention_entry.h) on stand-in launchers that only log which kernel the real ones would launch, the others are stand-ins that
+    log the same way."""
     L = lib()
     f = getattr(L, name)
     if f.argtypes is None:

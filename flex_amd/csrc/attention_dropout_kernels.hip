@@ -16,9 +16,9 @@
 // mask for gV alone: ds in dWork already holds it through da.
 //
 // This file holds the three kernels (namespace flex::dropout: 7 forms x (rows and rows backward x {float, bf16} x {no bias, bias} +
-// columns backward x {float, bf16}) = 70 instantiations), their launchers (internal.h, launch_dropout_*) and the four entry points: the
-// per-head template pair of attention_entry.h with the drop_p check beside the scale check.  They are here and not in attention_entry.h
-// because the host simulator includes that header and has no stand-ins for these launchers.
+// columns backward x {float, bf16}) = 70 instantiations) and their launchers for both element types (internal.h, launch_dropout_*: a
+// NULL Bias / GB launches the kernels without the bias); the entry points -- the per-head template pair with its drop flag set -- are
+// attention_entry.h's.
 #include <cmath>
 #include <cstdint>
 
@@ -103,99 +103,19 @@ int launch_dropout_columns_backward(const flex_plan *p, const AttentionPick &pic
     return FLEX_OK;
 }
 
-// ---- the entry points: heads_forward / heads_backward of attention_entry.h, refusal for refusal, with the drop_p check beside the
-// scale check.  drop_p == 0: once nothing is refused, `plain` -- the undropped entry point on the same operands -- runs instead, so the
-// bits are its own (its checks repeat these and pass).  A NULL dBias / dGradBias selects the kernels without the bias.
-
-template <class E, class F>
-static int dropout_forward(const flex_plan *p, int heads, const E *dQ, const E *dK, const E *dV, const float *dBias, float scale, float drop_p,
-                           uint64_t seed, E *dOut, float *dP, flex_stream_t stream, F &&plain) {
-    if (!p || !p->at_ok || heads < 1) return FLEX_ERR_INVALID;
-    if (!(std::isfinite(scale) && scale > 0.f) || !drop_p_ok(drop_p)) return FLEX_ERR_INVALID;
-    int lg;
-    if (const int rc = head_split_lg(p->k, heads, &lg)) return rc;
-    if (p->at_entries == 0) return FLEX_OK;
-    if (!dQ || !dK || !dV || !dOut) return FLEX_ERR_INVALID;
-    const AttentionPick pick = pick_rows<E>(p->k, p->ldb, p->ldc, {dQ, dK, dV, dOut});
-    if (!pick.vec4) return FLEX_ERR_UNSUPPORTED;
-    if (drop_p == 0.f) return plain();
-    const DeviceScope on(p->device);
-    FLEX_HIP_TRY(on.error());
-    if (const int rc = launch_dropout_rows(p, pick, heads, lg, dQ, dK, dV, dBias, scale, drop_mask(drop_p, seed), dOut, dP,
-                                           reinterpret_cast<hipStream_t>(stream)))
-        return rc;
-    FLEX_HIP_TRY(hipGetLastError());
-    return FLEX_OK;
-}
-
-template <class E, class F>
-static int dropout_backward(const flex_plan *p, int heads, const E *dQ, const E *dK, const E *dV, const float *dP, const E *dGradOut, float scale,
-                            float drop_p, uint64_t seed, E *dGradQ, E *dGradK, E *dGradV, float *dGradBias, float *dWork, flex_stream_t stream,
-                            F &&plain) {
-    if (!p || !p->ab_ok || heads < 1) return FLEX_ERR_INVALID;
-    if (!(std::isfinite(scale) && scale > 0.f) || !drop_p_ok(drop_p)) return FLEX_ERR_INVALID;
-    int lg;
-    if (const int rc = head_split_lg(p->k, heads, &lg)) return rc;
-    if (p->at_entries == 0) return FLEX_OK;
-    if (!dQ || !dK || !dV || !dP || !dGradOut || !dWork || dWork == dP) return FLEX_ERR_INVALID;
-    if (dGradBias && (dGradBias == dP || dGradBias == dWork)) return FLEX_ERR_INVALID;
-    const AttentionPick pick = pick_rows<E>(p->k, p->ldb, p->ldc, {dQ, dK, dV, dGradOut, dGradQ, dGradK, dGradV});
-    if (!pick.vec4) return FLEX_ERR_UNSUPPORTED;
-    if (!dGradQ && !dGradK && !dGradV && !dGradBias) return FLEX_OK;
-    if (drop_p == 0.f) return plain();
-    const DeviceScope on(p->device);
-    FLEX_HIP_TRY(on.error());
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const DropMask dm = drop_mask(drop_p, seed);
-    if (dGradQ || dGradK || dGradBias) {
-        if (const int rc = launch_dropout_rows_backward(p, pick, heads, lg, dK, dV, dP, dGradOut, scale, dm, dGradQ, dGradBias, dWork, s)) return rc;
-    }
-    if (dGradK || dGradV) {
-        if (const int rc = launch_dropout_columns_backward(p, pick, heads, lg, dQ, dGradOut, dP, dWork, dm, dGradK, dGradV, s)) return rc;
-    }
-    FLEX_HIP_TRY(hipGetLastError());
-    return FLEX_OK;
-}
+template int launch_dropout_rows<float>(const flex_plan *, const AttentionPick &, int, int, const float *, const float *, const float *, const float *,
+                                        float, const DropMask &, float *, float *, hipStream_t);
+template int launch_dropout_rows_backward<float>(const flex_plan *, const AttentionPick &, int, int, const float *, const float *, const float *,
+                                                 const float *, float, const DropMask &, float *, float *, float *, hipStream_t);
+template int launch_dropout_columns_backward<float>(const flex_plan *, const AttentionPick &, int, int, const float *, const float *, const float *,
+                                                    const float *, const DropMask &, float *, float *, hipStream_t);
+template int launch_dropout_rows<flex_bf16>(const flex_plan *, const AttentionPick &, int, int, const flex_bf16 *, const flex_bf16 *, const flex_bf16 *,
+                                            const float *, float, const DropMask &, flex_bf16 *, float *, hipStream_t);
+template int launch_dropout_rows_backward<flex_bf16>(const flex_plan *, const AttentionPick &, int, int, const flex_bf16 *, const flex_bf16 *,
+                                                     const float *, const flex_bf16 *, float, const DropMask &, flex_bf16 *, float *, float *,
+                                                     hipStream_t);
+template int launch_dropout_columns_backward<flex_bf16>(const flex_plan *, const AttentionPick &, int, int, const flex_bf16 *, const flex_bf16 *,
+                                                        const float *, const float *, const DropMask &, flex_bf16 *, flex_bf16 *, hipStream_t);
 
 }  // namespace attention
 }  // namespace flex
-
-extern "C" {
-
-int flex_attention_dropout(const flex_plan *p, int heads, const float *dQ, const float *dK, const float *dV, const float *dBias, float scale, float drop_p,
-                           uint64_t seed, float *dOut, float *dP, flex_stream_t stream) {
-    return flex::attention::dropout_forward<float>(p, heads, dQ, dK, dV, dBias, scale, drop_p, seed, dOut, dP, stream, [&] {
-        return dBias ? flex_attention_bias(p, heads, dQ, dK, dV, dBias, scale, dOut, dP, stream)
-                     : flex_attention_heads(p, heads, dQ, dK, dV, scale, dOut, dP, stream);
-    });
-}
-
-int flex_attention_dropout_backward(const flex_plan *p, int heads, const float *dQ, const float *dK, const float *dV, const float *dP,
-                                    const float *dGradOut, float scale, float drop_p, uint64_t seed, float *dGradQ, float *dGradK, float *dGradV,
-                                    float *dGradBias, float *dWork, flex_stream_t stream) {
-    return flex::attention::dropout_backward<float>(p, heads, dQ, dK, dV, dP, dGradOut, scale, drop_p, seed, dGradQ, dGradK, dGradV, dGradBias, dWork,
-                                                    stream, [&] {
-        return dGradBias ? flex_attention_bias_backward(p, heads, dQ, dK, dV, dP, dGradOut, scale, dGradQ, dGradK, dGradV, dGradBias, dWork, stream)
-                         : flex_attention_heads_backward(p, heads, dQ, dK, dV, dP, dGradOut, scale, dGradQ, dGradK, dGradV, dWork, stream);
-    });
-}
-
-int flex_attention_bf16_dropout(const flex_plan *p, int heads, const flex_bf16 *dQ, const flex_bf16 *dK, const flex_bf16 *dV, const float *dBias,
-                                float scale, float drop_p, uint64_t seed, flex_bf16 *dOut, float *dP, flex_stream_t stream) {
-    return flex::attention::dropout_forward<flex_bf16>(p, heads, dQ, dK, dV, dBias, scale, drop_p, seed, dOut, dP, stream, [&] {
-        return dBias ? flex_attention_bf16_bias(p, heads, dQ, dK, dV, dBias, scale, dOut, dP, stream)
-                     : flex_attention_bf16(p, heads, dQ, dK, dV, scale, dOut, dP, stream);
-    });
-}
-
-int flex_attention_bf16_dropout_backward(const flex_plan *p, int heads, const flex_bf16 *dQ, const flex_bf16 *dK, const flex_bf16 *dV, const float *dP,
-                                         const flex_bf16 *dGradOut, float scale, float drop_p, uint64_t seed, flex_bf16 *dGradQ, flex_bf16 *dGradK,
-                                         flex_bf16 *dGradV, float *dGradBias, float *dWork, flex_stream_t stream) {
-    return flex::attention::dropout_backward<flex_bf16>(p, heads, dQ, dK, dV, dP, dGradOut, scale, drop_p, seed, dGradQ, dGradK, dGradV, dGradBias,
-                                                        dWork, stream, [&] {
-        return dGradBias ? flex_attention_bf16_bias_backward(p, heads, dQ, dK, dV, dP, dGradOut, scale, dGradQ, dGradK, dGradV, dGradBias, dWork, stream)
-                         : flex_attention_bf16_backward(p, heads, dQ, dK, dV, dP, dGradOut, scale, dGradQ, dGradK, dGradV, dWork, stream);
-    });
-}
-
-}  // extern "C"

@@ -11,11 +11,9 @@
 // widened by shifts (exact), every sum in fp32, and one rounding to nearest even at the single 8-byte store of an element of Out or gV.
 // No 2-byte access, no atomics, fixed order everywhere.
 //
-// This file holds the three kernels (namespace flex::gat_bf16: 7 forms x 3 x DROP off / on = 42 instantiations), their launchers
-// (internal.h, launch_gat_bf16_*: a NULL mask launches DROP off) and the four entry points: flex_gat_attention's and
-// flex_gat_attention_backward's checks with pick_rows<flex_bf16> as the alignment rule and, in the dropout pair, the drop_p check
-// beside the slope check.  They are here and not in attention_entry.h because the host simulator includes that header and has no
-// stand-ins for these launchers.
+// This file holds the three kernels (namespace flex::gat_bf16: 7 forms x 3 x DROP off / on = 42 instantiations) and their launchers
+// (internal.h, launch_gat_bf16_*: a NULL mask launches DROP off); the entry points -- the GAT template pair on flex_bf16 rows, with
+// pick_rows<flex_bf16> as the alignment rule -- are attention_entry.h's.
 #include <cmath>
 #include <cstdint>
 
@@ -156,87 +154,5 @@ int launch_gat_bf16_columns_backward(const flex_plan *p, const AttentionPick &pi
     return FLEX_OK;
 }
 
-// ---- the entry points: flex_gat_attention / flex_gat_attention_backward of attention_entry.h, refusal for refusal, with
-// pick_rows<flex_bf16> over V, Out / g, gV as the alignment rule; `drop` adds the drop_p check beside the slope check.  drop_p == 0:
-// once nothing is refused the undropped launch runs, which is all the undropped entry point does from there on, so the bits are its own.
-
-// attention_entry.h's slope_ok: that header is for its one translation unit
-static bool gat_bf16_slope_ok(float slope) { return std::isfinite(slope) && slope > 0.f && slope <= 1.f; }
-
-static int gat_bf16_forward(bool drop, const flex_plan *p, int heads, const float *dEl, const float *dEr, const flex_bf16 *dV, float slope,
-                            float drop_p, uint64_t seed, flex_bf16 *dOut, float *dP, flex_stream_t stream) {
-    if (!p || !p->at_ok || heads < 1 || !gat_bf16_slope_ok(slope) || (drop && !drop_p_ok(drop_p))) return FLEX_ERR_INVALID;
-    int lg;
-    if (const int rc = head_split_lg(p->k, heads, &lg)) return rc;
-    if (p->at_entries == 0) return FLEX_OK;
-    if (!dEl || !dEr || !dV || !dOut) return FLEX_ERR_INVALID;
-    const AttentionPick pick = pick_rows<flex_bf16>(p->k, p->ldb, p->ldc, {dV, dOut});
-    if (!pick.vec4) return FLEX_ERR_UNSUPPORTED;
-    const bool masked = drop && drop_p != 0.f;
-    const DropMask dm = masked ? drop_mask(drop_p, seed) : DropMask{};
-    const DeviceScope on(p->device);
-    FLEX_HIP_TRY(on.error());
-    if (const int rc = launch_gat_bf16_rows(p, pick, heads, lg, dEl, dEr, dV, slope, masked ? &dm : nullptr, dOut, dP,
-                                            reinterpret_cast<hipStream_t>(stream)))
-        return rc;
-    FLEX_HIP_TRY(hipGetLastError());
-    return FLEX_OK;
-}
-
-static int gat_bf16_backward(bool drop, const flex_plan *p, int heads, const float *dEl, const float *dEr, const flex_bf16 *dV, const float *dP,
-                             const flex_bf16 *dGradOut, float slope, float drop_p, uint64_t seed, float *dGradEl, float *dGradEr,
-                             flex_bf16 *dGradV, float *dWork, flex_stream_t stream) {
-    if (!p || !p->ab_ok || heads < 1 || !gat_bf16_slope_ok(slope) || (drop && !drop_p_ok(drop_p))) return FLEX_ERR_INVALID;
-    int lg;
-    if (const int rc = head_split_lg(p->k, heads, &lg)) return rc;
-    if (p->at_entries == 0) return FLEX_OK;
-    if (!dEl || !dEr || !dV || !dP || !dGradOut || !dWork || dWork == dP) return FLEX_ERR_INVALID;
-    // the forward's rule over every row operand of the two launches (a NULL output is aligned)
-    const AttentionPick pick = pick_rows<flex_bf16>(p->k, p->ldb, p->ldc, {dV, dGradOut, dGradV});
-    if (!pick.vec4) return FLEX_ERR_UNSUPPORTED;
-    if (!dGradEl && !dGradEr && !dGradV) return FLEX_OK;
-    const bool masked = drop && drop_p != 0.f;
-    const DropMask dm = masked ? drop_mask(drop_p, seed) : DropMask{};
-    const DropMask *dmp = masked ? &dm : nullptr;
-    const DeviceScope on(p->device);
-    FLEX_HIP_TRY(on.error());
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (dGradEl || dGradEr) {
-        if (const int rc = launch_gat_bf16_rows_backward(p, pick, heads, lg, dEl, dEr, dV, dP, dGradOut, slope, dmp, dGradEl, dWork, s)) return rc;
-    }
-    if (dGradEr || dGradV) {
-        if (const int rc = launch_gat_bf16_columns_backward(p, pick, heads, lg, dGradOut, dP, dWork, dmp, dGradEr, dGradV, s)) return rc;
-    }
-    FLEX_HIP_TRY(hipGetLastError());
-    return FLEX_OK;
-}
-
 }  // namespace attention
 }  // namespace flex
-
-extern "C" {
-
-int flex_gat_attention_bf16(const flex_plan *p, int heads, const float *dEl, const float *dEr, const flex_bf16 *dV, float slope, flex_bf16 *dOut,
-                            float *dP, flex_stream_t stream) {
-    return flex::attention::gat_bf16_forward(false, p, heads, dEl, dEr, dV, slope, 0.f, 0, dOut, dP, stream);
-}
-
-int flex_gat_attention_bf16_backward(const flex_plan *p, int heads, const float *dEl, const float *dEr, const flex_bf16 *dV, const float *dP,
-                                     const flex_bf16 *dGradOut, float slope, float *dGradEl, float *dGradEr, flex_bf16 *dGradV, float *dWork,
-                                     flex_stream_t stream) {
-    return flex::attention::gat_bf16_backward(false, p, heads, dEl, dEr, dV, dP, dGradOut, slope, 0.f, 0, dGradEl, dGradEr, dGradV, dWork, stream);
-}
-
-int flex_gat_attention_bf16_dropout(const flex_plan *p, int heads, const float *dEl, const float *dEr, const flex_bf16 *dV, float slope, float drop_p,
-                                    uint64_t seed, flex_bf16 *dOut, float *dP, flex_stream_t stream) {
-    return flex::attention::gat_bf16_forward(true, p, heads, dEl, dEr, dV, slope, drop_p, seed, dOut, dP, stream);
-}
-
-int flex_gat_attention_bf16_dropout_backward(const flex_plan *p, int heads, const float *dEl, const float *dEr, const flex_bf16 *dV, const float *dP,
-                                             const flex_bf16 *dGradOut, float slope, float drop_p, uint64_t seed, float *dGradEl, float *dGradEr,
-                                             flex_bf16 *dGradV, float *dWork, flex_stream_t stream) {
-    return flex::attention::gat_bf16_backward(true, p, heads, dEl, dEr, dV, dP, dGradOut, slope, drop_p, seed, dGradEl, dGradEr, dGradV, dWork,
-                                              stream);
-}
-
-}  // extern "C"

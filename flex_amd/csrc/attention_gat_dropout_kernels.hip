@@ -12,10 +12,8 @@
 // out and its V row (forward, row backward) or g row (gV) is not gathered.  The column launch needs the mask for gV alone: dx in dWork
 // already holds it through da, and so do gEl and gEr.
 //
-// This file holds the three kernels (namespace flex::gat_dropout: 7 forms x 3 = 21 instantiations), their launchers (internal.h,
-// launch_gat_dropout_*) and the two entry points: flex_gat_attention's and flex_gat_attention_backward's checks with the drop_p check
-// beside the slope check.  They are here and not in attention_entry.h because the host simulator includes that header and has no
-// stand-ins for these launchers.
+// This file holds the three kernels (namespace flex::gat_dropout: 7 forms x 3 = 21 instantiations) and their launchers (internal.h,
+// launch_gat_dropout_*); the entry points -- the GAT template pair on float rows with its drop flag set -- are attention_entry.h's.
 #include <cmath>
 #include <cstdint>
 
@@ -142,78 +140,5 @@ int launch_gat_dropout_columns_backward(const flex_plan *p, const AttentionPick 
     return FLEX_OK;
 }
 
-// ---- the entry points: flex_gat_attention / flex_gat_attention_backward of attention_entry.h, refusal for refusal, with the drop_p
-// check beside the slope check.  drop_p == 0: once nothing is refused, `plain` -- the undropped entry point on the same operands -- runs
-// instead, so the bits are its own (its checks repeat these and pass).
-
-// attention_entry.h's slope_ok: that header is for its one translation unit
-static bool gat_slope_ok(float slope) { return std::isfinite(slope) && slope > 0.f && slope <= 1.f; }
-
-template <class F>
-static int gat_dropout_forward(const flex_plan *p, int heads, const float *dEl, const float *dEr, const float *dV, float slope, float drop_p,
-                               uint64_t seed, float *dOut, float *dP, flex_stream_t stream, F &&plain) {
-    if (!p || !p->at_ok || heads < 1 || !gat_slope_ok(slope) || !drop_p_ok(drop_p)) return FLEX_ERR_INVALID;
-    int lg;
-    if (const int rc = head_split_lg(p->k, heads, &lg)) return rc;
-    if (p->at_entries == 0) return FLEX_OK;
-    if (!dEl || !dEr || !dV || !dOut) return FLEX_ERR_INVALID;
-    const AttentionPick pick = attention_pick(p->k, p->ldb, p->ldc, dV, dOut, nullptr, nullptr);
-    if (!pick.vec4) return FLEX_ERR_UNSUPPORTED;
-    if (drop_p == 0.f) return plain();
-    const DeviceScope on(p->device);
-    FLEX_HIP_TRY(on.error());
-    if (const int rc = launch_gat_dropout_rows(p, pick, heads, lg, dEl, dEr, dV, slope, drop_mask(drop_p, seed), dOut, dP,
-                                               reinterpret_cast<hipStream_t>(stream)))
-        return rc;
-    FLEX_HIP_TRY(hipGetLastError());
-    return FLEX_OK;
-}
-
-template <class F>
-static int gat_dropout_backward(const flex_plan *p, int heads, const float *dEl, const float *dEr, const float *dV, const float *dP,
-                                const float *dGradOut, float slope, float drop_p, uint64_t seed, float *dGradEl, float *dGradEr, float *dGradV,
-                                float *dWork, flex_stream_t stream, F &&plain) {
-    if (!p || !p->ab_ok || heads < 1 || !gat_slope_ok(slope) || !drop_p_ok(drop_p)) return FLEX_ERR_INVALID;
-    int lg;
-    if (const int rc = head_split_lg(p->k, heads, &lg)) return rc;
-    if (p->at_entries == 0) return FLEX_OK;
-    if (!dEl || !dEr || !dV || !dP || !dGradOut || !dWork || dWork == dP) return FLEX_ERR_INVALID;
-    // the forward's rule over every row operand of the two launches (a NULL output is aligned)
-    const AttentionPick pick = attention_pick(p->k, p->ldb, p->ldc, dV, dGradOut, dGradV, nullptr);
-    if (!pick.vec4) return FLEX_ERR_UNSUPPORTED;
-    if (!dGradEl && !dGradEr && !dGradV) return FLEX_OK;
-    if (drop_p == 0.f) return plain();
-    const DeviceScope on(p->device);
-    FLEX_HIP_TRY(on.error());
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const DropMask dm = drop_mask(drop_p, seed);
-    if (dGradEl || dGradEr) {
-        if (const int rc = launch_gat_dropout_rows_backward(p, pick, heads, lg, dEl, dEr, dV, dP, dGradOut, slope, dm, dGradEl, dWork, s)) return rc;
-    }
-    if (dGradEr || dGradV) {
-        if (const int rc = launch_gat_dropout_columns_backward(p, pick, heads, lg, dGradOut, dP, dWork, dm, dGradEr, dGradV, s)) return rc;
-    }
-    FLEX_HIP_TRY(hipGetLastError());
-    return FLEX_OK;
-}
-
 }  // namespace attention
 }  // namespace flex
-
-extern "C" {
-
-int flex_gat_attention_dropout(const flex_plan *p, int heads, const float *dEl, const float *dEr, const float *dV, float slope, float drop_p,
-                               uint64_t seed, float *dOut, float *dP, flex_stream_t stream) {
-    return flex::attention::gat_dropout_forward(p, heads, dEl, dEr, dV, slope, drop_p, seed, dOut, dP, stream,
-                                                [&] { return flex_gat_attention(p, heads, dEl, dEr, dV, slope, dOut, dP, stream); });
-}
-
-int flex_gat_attention_dropout_backward(const flex_plan *p, int heads, const float *dEl, const float *dEr, const float *dV, const float *dP,
-                                        const float *dGradOut, float slope, float drop_p, uint64_t seed, float *dGradEl, float *dGradEr,
-                                        float *dGradV, float *dWork, flex_stream_t stream) {
-    return flex::attention::gat_dropout_backward(p, heads, dEl, dEr, dV, dP, dGradOut, slope, drop_p, seed, dGradEl, dGradEr, dGradV, dWork, stream, [&] {
-        return flex_gat_attention_backward(p, heads, dEl, dEr, dV, dP, dGradOut, slope, dGradEl, dGradEr, dGradV, dWork, stream);
-    });
-}
-
-}  // extern "C"

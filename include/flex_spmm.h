@@ -664,22 +664,20 @@ int flex_attention_bf16_bias_backward(const flex_plan *plan, int heads, const fl
  * reference for users and tests.
  * Checks: those of flex_attention_bf16 / flex_attention_bias and their backward calls, in their order, for both element types (heads
  * == 1 is served by the per-head kernels: k / heads a power of two in 4 .. 256 for every heads); drop_p must be finite with 0 <=
- * drop_p < 1, anything else is FLEX_ERR_INVALID, checked beside scale.  drop_p == 0: once nothing is refused the call forwards to the
- * undropped entry point (flex_attention_heads, flex_attention_bf16 or the bias form), so every output has its bits.  Nothing is
+ * drop_p < 1, anything else is FLEX_ERR_INVALID, checked beside scale.  drop_p == 0: once nothing is refused the call launches what
+ * the undropped entry point launches (flex_attention_heads, flex_attention_bf16 or the bias form), so every output has its bits.  Nothing is
  * enqueued by a refused call.  Safe to capture in a hipGraph, no atomics, fixed order: bit-identical run to run for one seed.
  * Accuracy: the undropped calls' bounds with every rounding count that now includes the product by c grown by one: Out gamma(n_r + 4) in
- * place of gamma(n_r + 3), on |V| of the kept entries times c; da gamma(d + 1); gV one more rounding per term; dP unchanged.
- * The four calls are written `extern`: the GPU library alone defines them (attention_dropout_kernels.hip), where the entry points
- * declared plainly above are attention_entry.h's, which a host-only build of the library's sources defines as well. */
-extern int flex_attention_dropout(const flex_plan *plan, int heads, const float *dQ, const float *dK, const float *dV, const float *dBias /* NULL: no bias */,
+ * place of gamma(n_r + 3), on |V| of the kept entries times c; da gamma(d + 1); gV one more rounding per term; dP unchanged. */
+int flex_attention_dropout(const flex_plan *plan, int heads, const float *dQ, const float *dK, const float *dV, const float *dBias /* NULL: no bias */,
                            float scale, float drop_p, uint64_t seed, float *dOut, float *dP, flex_stream_t stream);
-extern int flex_attention_dropout_backward(const flex_plan *plan, int heads, const float *dQ, const float *dK, const float *dV, const float *dP,
+int flex_attention_dropout_backward(const flex_plan *plan, int heads, const float *dQ, const float *dK, const float *dV, const float *dP,
                                     const float *dGradOut, float scale, float drop_p, uint64_t seed, float *dGradQ, float *dGradK, float *dGradV,
                                     float *dGradBias /* NULL */, float *dWork, flex_stream_t stream);
-extern int flex_attention_bf16_dropout(const flex_plan *plan, int heads, const flex_bf16 *dQ, const flex_bf16 *dK, const flex_bf16 *dV,
+int flex_attention_bf16_dropout(const flex_plan *plan, int heads, const flex_bf16 *dQ, const flex_bf16 *dK, const flex_bf16 *dV,
                                 const float *dBias /* NULL: no bias */, float scale, float drop_p, uint64_t seed, flex_bf16 *dOut, float *dP,
                                 flex_stream_t stream);
-extern int flex_attention_bf16_dropout_backward(const flex_plan *plan, int heads, const flex_bf16 *dQ, const flex_bf16 *dK, const flex_bf16 *dV,
+int flex_attention_bf16_dropout_backward(const flex_plan *plan, int heads, const flex_bf16 *dQ, const flex_bf16 *dK, const flex_bf16 *dV,
                                          const float *dP, const flex_bf16 *dGradOut, float scale, float drop_p, uint64_t seed, flex_bf16 *dGradQ,
                                          flex_bf16 *dGradK, flex_bf16 *dGradV, float *dGradBias /* NULL */, float *dWork, flex_stream_t stream);
 int flex_dropout_mask(uint64_t seed, float drop_p, uint64_t first, uint64_t count, uint8_t *keep_host);
@@ -771,18 +769,17 @@ int flex_gat_attention_backward(const flex_plan *plan, int heads, const float *d
  *   dx holds the mask through da, so gEl and gEr do not see it a second time; the columns' launch needs the mask for gV only.
  * Checks: drop_p must be finite with 0 <= drop_p < 1, anything else is FLEX_ERR_INVALID, checked beside slope; every other refusal is
  * flex_gat_attention's and flex_gat_attention_backward's, code for code and in their order.  drop_p == 0: once nothing is refused the
- * call forwards to the undropped entry point, so every output has its bits.  The forward runs on row-range shards, the backward does
+ * call launches the undropped kernels, so every output has flex_gat_attention's bits.  The forward runs on row-range shards, the backward does
  * not.  Nothing is enqueued by a refused call.  Safe to capture in a hipGraph, no atomics, fixed order: bit-identical run to run for
  * one seed.
  * Accuracy: flex_gat_attention's bounds with every rounding count that now includes the product by c grown by one:
  *   Out     |Out - Out64| <= sum_{e kept} (gamma(n_r + 4) alpha_e + dalpha_e) c |V| + 2^-126
  *   dda_e    = c (gamma(d + 1) sum_j |g V| + d 2^-149) + 2^-149 on a kept entry, 0 on a dropped one
  *   ddz, ddx, gEl, gEr: flex_gat_attention_backward's lines on this da and dda
- *   |gV  - gV64|  <= sum_{e in c, kept} gamma(n_c + 1) p_e c |g[row]| + 2^-126
- * The two calls are written `extern`: the GPU library alone defines them (attention_gat_dropout_kernels.hip). */
-extern int flex_gat_attention_dropout(const flex_plan *plan, int heads, const float *dEl, const float *dEr, const float *dV, float slope, float drop_p,
+ *   |gV  - gV64|  <= sum_{e in c, kept} gamma(n_c + 1) p_e c |g[row]| + 2^-126 */
+int flex_gat_attention_dropout(const flex_plan *plan, int heads, const float *dEl, const float *dEr, const float *dV, float slope, float drop_p,
                                uint64_t seed, float *dOut, float *dP, flex_stream_t stream);
-extern int flex_gat_attention_dropout_backward(const flex_plan *plan, int heads, const float *dEl, const float *dEr, const float *dV, const float *dP,
+int flex_gat_attention_dropout_backward(const flex_plan *plan, int heads, const float *dEl, const float *dEr, const float *dV, const float *dP,
                                         const float *dGradOut, float slope, float drop_p, uint64_t seed, float *dGradEl, float *dGradEr,
                                         float *dGradV, float *dWork, flex_stream_t stream);
 
@@ -814,16 +811,15 @@ extern int flex_gat_attention_dropout_backward(const flex_plan *plan, int heads,
  * calls (with dropout: of flex_gat_attention_dropout) unchanged.  An element y = rn_bf16(x32) of Out or gV, whose fp32 value x32 lies
  * within those calls' bound32 of the float64 x64, satisfies
  *     |y - x64| <= bound32 + 2^-8 (|x64| + bound32) + 2^-134
- * 2^-8 being the unit roundoff of bf16 and 2^-134 half its smallest subnormal (flex_attention_bf16's bound).
- * The four calls are written `extern`: the GPU library alone defines them (attention_gat_bf16_kernels.hip). */
-extern int flex_gat_attention_bf16(const flex_plan *plan, int heads, const float *dEl, const float *dEr, const flex_bf16 *dV, float slope,
+ * 2^-8 being the unit roundoff of bf16 and 2^-134 half its smallest subnormal (flex_attention_bf16's bound). */
+int flex_gat_attention_bf16(const flex_plan *plan, int heads, const float *dEl, const float *dEr, const flex_bf16 *dV, float slope,
                             flex_bf16 *dOut, float *dP, flex_stream_t stream);
-extern int flex_gat_attention_bf16_backward(const flex_plan *plan, int heads, const float *dEl, const float *dEr, const flex_bf16 *dV,
+int flex_gat_attention_bf16_backward(const flex_plan *plan, int heads, const float *dEl, const float *dEr, const flex_bf16 *dV,
                                      const float *dP, const flex_bf16 *dGradOut, float slope, float *dGradEl, float *dGradEr,
                                      flex_bf16 *dGradV, float *dWork, flex_stream_t stream);
-extern int flex_gat_attention_bf16_dropout(const flex_plan *plan, int heads, const float *dEl, const float *dEr, const flex_bf16 *dV, float slope,
+int flex_gat_attention_bf16_dropout(const flex_plan *plan, int heads, const float *dEl, const float *dEr, const flex_bf16 *dV, float slope,
                                     float drop_p, uint64_t seed, flex_bf16 *dOut, float *dP, flex_stream_t stream);
-extern int flex_gat_attention_bf16_dropout_backward(const flex_plan *plan, int heads, const float *dEl, const float *dEr, const flex_bf16 *dV,
+int flex_gat_attention_bf16_dropout_backward(const flex_plan *plan, int heads, const float *dEl, const float *dEr, const flex_bf16 *dV,
                                              const float *dP, const flex_bf16 *dGradOut, float slope, float drop_p, uint64_t seed,
                                              float *dGradEl, float *dGradEr, flex_bf16 *dGradV, float *dWork, flex_stream_t stream);
 

@@ -182,7 +182,7 @@ def wide64_case(c):
 SCALE, SLOPE = 0.25, 0.2
 
 
-def _fake(i, off=0):
+def fake_address(i, off=0):
     """A 16-byte aligned address of operand i's own, `off` floats further."""
     return 0x7F0000000000 + (i << 36) + 4 * off
 
@@ -196,12 +196,12 @@ def fake_launch(c, p):
     """The forward and then the backward of an attention case on plan p (the bf16 SpMM: its one call), every row operand `off` floats
     off 16 bytes, the gradients the case does not want NULL."""
     if c["family"] == "spmm_bf16":
-        p.spmm_bf16(_fake(0), _fake(1))
+        p.spmm_bf16(fake_address(0), fake_address(1))
         return
     off, H, want = c["off"], c["H"], c["want"]
-    q, k, v, out, g = (_fake(i, off) for i in range(5))
-    pr, work, bias, gb = (_fake(i, off) for i in range(5, 9))
-    grads = [_fake(9 + i, off) if w else None for i, w in enumerate(want[:3])]
+    q, k, v, out, g = (fake_address(i, off) for i in range(5))
+    pr, work, bias, gb = (fake_address(i, off) for i in range(5, 9))
+    grads = [fake_address(9 + i, off) if w else None for i, w in enumerate(want[:3])]
     if c["family"] in ("single", "heads"):
         heads = None if c["family"] == "single" else H
         p.attention_ptr(q, k, v, SCALE, out, pr, heads=heads)

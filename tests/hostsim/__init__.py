@@ -23,6 +23,17 @@ def build(extra_flags=(), out=_OUT):
     return out
 
 
+def binding_on_simulator():
+    """The body of a pytest fixture: flex_amd.binding loads the host-simulated library (FLEX_HOSTSIM_LIB, or the one build() makes) until
+    the fixture ends, and the fixture's value is that library."""
+    from flex_amd import binding
+    so = os.environ.get("FLEX_HOSTSIM_LIB") or build()
+    old_so, old_lib = binding._SO, binding._lib
+    binding._SO, binding._lib = so, None
+    yield binding.lib()
+    binding._SO, binding._lib = old_so, old_lib
+
+
 def launch_log(L, fn):
     """The kernel instantiations that fn() launched through L (a host-simulated library), in order, as `nm -C` names them: fn runs with
     the shim's launch log on (tests/hostsim/shim.cpp), where every launcher records what the real one would launch and computes nothing."""

@@ -9,7 +9,7 @@
 // (spmm_kernels.hip), launch_tiles (tile_kernels.hip) and launch_blocks (block_kernels.hip): a change there must be made here too.
 // flex_plan_set_values, flex_sddmm and flex_edge_softmax / _backward (values_kernels.hip, softmax_kernels.hip) are logged by the rules
 // the real ones use -- refresh_passes, sddmm_pick and softmax_vec of internal.h -- so nothing is mirrored for them but their refusals.
-// flex_spmm_bf16 is logged the same way.  The fused attention is logged the way the SpMM is: its twelve entry points are the library's own
+// flex_spmm_bf16 is logged the same way.  The fused attention is logged the way the SpMM is: its 22 entry points are the library's own
 // (attention_entry.h, included at the end of this file), and nothing of it is mirrored here but the names of the kernels its launchers launch.
 // The "device memory" is counted (hostsim_live_allocations) and an allocation can be made to fail (hostsim_fail_malloc_at), so that
 // a test can check that a plan gives back everything it allocated, also when its creation fails half way.
@@ -165,6 +165,48 @@ int launch_gat_rows_backward(Plan, Pick pick, int, int, F, F, F, F, F, float, fl
 int launch_gat_columns_backward(Plan, Pick pick, int, int, F, F, F, float *, float *, hipStream_t) {
     if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
     return log_form("gat::gat_columns_backward", pick, "");
+}
+// with dropout: Bias / GB NULL launches the kernels without the bias, as the real launchers decide it
+template <class E>
+int launch_dropout_rows(Plan, Pick pick, int, int, const E *, const E *, const E *, F Bias, float, const DropMask &, E *, float *, hipStream_t) {
+    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
+    return log_form("dropout::attention_dropout_rows", pick, (std::string(Bias ? ", true" : ", false") + kElemTail<E>).c_str());
+}
+template <class E>
+int launch_dropout_rows_backward(Plan, Pick pick, int, int, const E *, const E *, F, const E *, float, const DropMask &, E *, float *GB, float *,
+                                 hipStream_t) {
+    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
+    return log_form("dropout::attention_dropout_rows_backward", pick, (std::string(GB ? ", true" : ", false") + kElemTail<E>).c_str());
+}
+template <class E>
+int launch_dropout_columns_backward(Plan, Pick pick, int, int, const E *, const E *, F, F, const DropMask &, E *, E *, hipStream_t) {
+    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
+    return log_form("dropout::attention_dropout_columns_backward", pick, kElemTail<E>);
+}
+int launch_gat_dropout_rows(Plan, Pick pick, int, int, F, F, F, float, const DropMask &, float *, float *, hipStream_t) {
+    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
+    return log_form("gat_dropout::gat_dropout_rows", pick, "");
+}
+int launch_gat_dropout_rows_backward(Plan, Pick pick, int, int, F, F, F, F, F, float, const DropMask &, float *, float *, hipStream_t) {
+    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
+    return log_form("gat_dropout::gat_dropout_rows_backward", pick, "");
+}
+int launch_gat_dropout_columns_backward(Plan, Pick pick, int, int, F, F, F, const DropMask &, float *, float *, hipStream_t) {
+    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
+    return log_form("gat_dropout::gat_dropout_columns_backward", pick, "");
+}
+// bf16 V rows: a NULL mask launches DROP off
+int launch_gat_bf16_rows(Plan, Pick pick, int, int, F, F, B, float, const DropMask *dm, flex_bf16 *, float *, hipStream_t) {
+    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
+    return log_form("gat_bf16::gat_bf16_rows", pick, dm ? ", true" : ", false");
+}
+int launch_gat_bf16_rows_backward(Plan, Pick pick, int, int, F, F, B, F, B, float, const DropMask *dm, float *, float *, hipStream_t) {
+    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
+    return log_form("gat_bf16::gat_bf16_rows_backward", pick, dm ? ", true" : ", false");
+}
+int launch_gat_bf16_columns_backward(Plan, Pick pick, int, int, B, F, F, const DropMask *dm, float *, flex_bf16 *, hipStream_t) {
+    if (!g_log_on) return FLEX_ERR_UNSUPPORTED;
+    return log_form("gat_bf16::gat_bf16_columns_backward", pick, dm ? ", true" : ", false");
 }
 }  // namespace flex::attention
 

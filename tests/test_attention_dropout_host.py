@@ -1,7 +1,8 @@
 """Host checks of the attention dropout (include/flex_spmm.h: flex_attention_dropout and its backward, bf16 and bias forms, and
 flex_dropout_mask): the mask's test vectors and flex_dropout_mask against the numpy restatement, the statistics of the mask, the float64
 reference (tests/attention_dropout_ref.py) against an independent float64 torch autograd evaluation, every planted fault against the
-checker it targets, the public surface, and the census of the kernels in flex::dropout with the GPU case that runs each.  No GPU."""
+checker it targets, the public surface, and the census of the kernels in flex::dropout with the GPU case that runs each and the launches
+of every pair on the host simulator.  No GPU."""
 import ctypes
 import os
 import re
@@ -16,7 +17,7 @@ import attention_bias_ref as ab
 import attention_dropout_ref as ad
 import flex_amd
 import multihead_attention_ref as mh
-from attention_forms import FORM_OF_K, FORMS
+from attention_forms import ALL_WANTED, COLUMN_KERNEL_ALONE, FORM_OF_K, FORMS, ROW_KERNEL_ALONE, fake_address
 from backward_ref import _directed
 from conftest import ROOT
 from flex_amd import binding
@@ -360,3 +361,38 @@ def test_the_library_ships_exactly_the_seventy_kernels_and_a_gpu_case_runs_each(
     ids = {case_id(c) for c in CASES}
     assert all(v in ids for v in RUN_BY.values())
     assert {FORM_OF_K[k] for k, _ in PAIRS} == set(FORMS)
+
+
+# ---- the census against the launches
+
+@pytest.fixture
+def sim():
+    """(tests/hostsim, flex_amd.binding's library on the host simulator) for one test: the others here run on the library itself."""
+    hostsim = pytest.importorskip("hostsim")
+    for lib in hostsim.binding_on_simulator():
+        yield hostsim, lib
+
+
+def test_every_pair_launches_on_the_simulator_the_kernels_its_cases_declare(sim):
+    """The forward and then the backward of every (k, H), element type and bias setting, on fake operands (nothing is read or written):
+    the library's own entry points on the simulator's stand-in launchers must log kernels_of() of the case, and with one gradient
+    wanted the forward and one backward kernel: gQ (with a bias: and gBias) the row kernel, gV the column kernel."""
+    hostsim, lib = sim
+    a = graph("thresholds_lifted")
+    q, kk, v, out, g, pr, work, bias, gb, gq, gk, gv = (fake_address(i) for i in range(12))
+    for k, H in PAIRS:
+        plan = flex_amd.Plan(a, k, attention=True, attention_backward=True)
+        for kind in KINDS:
+            fwd, bwd = ((plan.attention_dropout_ptr, plan.attention_dropout_backward_ptr) if kind == "fp32" else
+                        (plan.attention_bf16_dropout_ptr, plan.attention_bf16_dropout_backward_ptr))
+            for with_bias in (False, True):
+                def launch(want, want_bias):
+                    fwd(q, kk, v, bias if with_bias else None, SCALE, 0.5, SEED, out, pr, heads=H)
+                    bwd(q, kk, v, pr, g, SCALE, 0.5, SEED, *(x if w else None for x, w in zip((gq, gk, gv), want)), gb if want_bias else None, work,
+                        heads=H)
+                names = ["dropout::" + n for n in kernels_of(("thresholds_lifted", k, H, kind, with_bias, 0.5))]
+                assert hostsim.launch_log(lib, lambda: launch(ALL_WANTED, with_bias)) == names, (k, H, kind, with_bias)
+                assert hostsim.launch_log(lib, lambda: launch(ROW_KERNEL_ALONE, with_bias)) == names[:2], (k, H, kind, with_bias)
+                # gBias is the row kernel's: the column kernel runs alone where it is not wanted either
+                assert hostsim.launch_log(lib, lambda: launch(COLUMN_KERNEL_ALONE, False)) == [names[0], names[2]], (k, H, kind, with_bias)
+        plan.destroy()

@@ -4,14 +4,17 @@ the host simulator (every test here but the last) and on the real library (the l
 The entry points are one source for both builds (flex_amd/csrc/attention_entry.h: the library compiles it into attention_kernels.hip's
 object, the simulator into tests/hostsim/shim.cpp's), so the two runs agree by construction; if they ever disagree, a build is wrong.
 What the table pins is the order of precedence of the refusals, which differs between the single-head pair, the per-head family (heads,
-bf16 and the two bias forms) and GAT.  The expected codes were written down from the entry points as they stood in the six
-attention_*_kernels.hip files at commit 03f89bd, before they moved: ENTRIES names, per entry point, that file and the line of each check
+bf16, the two bias forms and the four dropout calls) and GAT (fp32 and bf16 V rows, with and without dropout).  The expected codes were
+written down from the entry points as they stood in the attention_*_kernels.hip files before they moved -- the first twelve at commit
+03f89bd, the ten dropout and bf16-GAT calls at commit 4b269a3: ENTRIES names, per entry point, that file and the line of each check
 there, every row of ROWS names the check that answers it, and a failing row prints both.
 
-Graph and shapes: both_sides(threshold_graph()), k = 32 (the (W, NS) = (8, 1) form), H = 4 for the per-head families; fake operands on
-the simulator, as attention_forms.fake_launch has them."""
+Graph and shapes: both_sides(threshold_graph()), k = 32 (the (W, NS) = (8, 1) form), H = 4 for the per-head families, drop_p = 0.5 in a
+valid call; fake operands on the simulator, as attention_forms.fake_launch has them."""
 import os
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -24,21 +27,66 @@ from fused_attention_ref import threshold_graph
 
 OK, INVALID, UNSUPPORTED = 0, -1, -4  # include/flex_spmm.h: FLEX_OK, FLEX_ERR_INVALID, FLEX_ERR_UNSUPPORTED
 K, H = 32, 4
+DROP_P, SEED = 0.5, 0x0123456789ABCDEF
 
-# ---- the twelve entry points: arguments after the plan and before the stream (GAT's el, er, gEl, gEr stand under Q, K, GQ, GK and its
+# ---- the 22 entry points: arguments after the plan and before the stream (GAT's el, er, gEl, gEr stand under Q, K, GQ, GK and its
 # slope under scale), the operands that must not be NULL, and what a valid call launches at k = 32
 
 FWD, BWD = "Q K V scale Out P", "Q K V P G scale GQ GK GV Work"
 FWD_BIAS, BWD_BIAS = "Q K V Bias scale Out P", "Q K V P G scale GQ GK GV GB Work"
+FWD_DROP, BWD_DROP = "Q K V Bias scale drop_p seed Out P", "Q K V P G scale drop_p seed GQ GK GV GB Work"
+FWD_GAT_DROP, BWD_GAT_DROP = "Q K V scale drop_p seed Out P", "Q K V P G scale drop_p seed GQ GK GV Work"
 SINGLE_GENERIC = {False: ["attention_rows<8, 1, false>"], True: ["attention_rows_backward<8, 1, false>", "attention_columns_backward<8, 1, false>"]}
 
 
-def _entry(kind, backward, elem, args, file, lines, kernels):
-    need = [a for a in args.split() if a in ("Q", "K", "V", "Bias", "G", "Work") or a == ("P" if backward else "Out")]
-    return {"kind": kind, "backward": backward, "elem": elem, "args": args.split(), "need": need, "file": file, "lines": lines, "kernels": kernels}
+def _entry(kind, backward, elem, args, file, lines, kernels, at="03f89bd", **launches):
+    """launches: what the entry point launches in a call other than the valid one, by the name a row of ROWS gives that call."""
+    must = ("Q", "K", "V", "G", "Work") + (() if kind == "dropout" else ("Bias",))  # the dropout calls take a NULL bias
+    need = [a for a in args.split() if a in must or a == ("P" if backward else "Out")]
+    return {"kind": kind, "backward": backward, "elem": elem, "args": args.split(), "need": need, "file": file, "lines": lines, "at": at,
+            "kernels": kernels, "launches": {"valid": kernels, "generic": SINGLE_GENERIC[backward], **launches}}
 
 
-# "lines": where each check of an entry point stood in "file" at commit 03f89bd.  "plan": NULL plan, missing flag, heads < 1 (GAT: and the slope);
+def _three(rows, rows_bwd, cols_bwd, backward):
+    return [rows_bwd, cols_bwd] if backward else [rows]
+
+
+def _dropout_entry(backward, elem):
+    """One of the four dot-product dropout calls: the dropped kernels with and without the bias, and at drop_p = 0 the kernels of the
+    undropped call on the same operands (with a bias: the bias call; without: the per-head call, whose one head on fp32 rows is the
+    single-head pair)."""
+    e, plain = ("float", "attention_heads") if elem == "fp32" else ("unsigned short", "attention_bf16")
+    drop = lambda b: _three(f"dropout::attention_dropout_rows<8, 1, {b}, {e}>", f"dropout::attention_dropout_rows_backward<8, 1, {b}, {e}>",
+                            f"dropout::attention_dropout_columns_backward<8, 1, {e}>", backward)
+    heads = lambda stem, tail: _three(f"{stem}_rows<8, 1{tail}>", f"{stem}_rows_backward<8, 1{tail}>", f"{stem}_columns_backward<8, 1{tail}>", backward)
+    lines = ({"plan": 135, "scale": 136, "drop_p": 136, "split": 138, "empty": 139, "null": 140, "bias_alias": 141, "align": 143, "no_out": 144,
+              "p0": 145, "launch": 151} if backward else
+             {"plan": 113, "scale": 114, "drop_p": 114, "split": 116, "empty": 117, "null": 118, "align": 120, "p0": 121, "launch": 124})
+    return _entry("dropout", backward, elem, "heads " + (BWD_DROP if backward else FWD_DROP), "attention_dropout_kernels.hip", lines, drop("true"),
+                  at="4b269a3", no_bias=drop("false"),
+                  p0=_three(f"attention_bias_rows<8, 1, {e}>", f"attention_bias_rows_backward<8, 1, {e}>", f"{plain}_columns_backward<8, 1>", backward),
+                  p0_no_bias=heads(plain, ""), p0_no_bias_one_head=heads("attention", ", true") if elem == "fp32" else heads(plain, ""))
+
+
+def _gat_entry(backward, elem, drop):
+    """One of the six GAT calls after the first two: fp32 with dropout, bf16 without and with."""
+    if elem == "fp32":
+        file, stem, tail, plain_tail = "attention_gat_dropout_kernels.hip", "gat_dropout::gat_dropout", "", None
+        lines = ({"plan": 176, "split": 178, "empty": 179, "null": 180, "align": 183, "no_out": 184, "p0": 185, "launch": 191} if backward else
+                 {"plan": 155, "split": 157, "empty": 158, "null": 159, "align": 161, "p0": 162, "launch": 165})
+    else:
+        file, stem, tail, plain_tail = "attention_gat_bf16_kernels.hip", "gat_bf16::gat_bf16", ", true" if drop else ", false", ", false"
+        lines = ({"plan": 189, "split": 191, "empty": 192, "null": 193, "align": 196, "no_out": 197, "p0": 198, "launch": 205} if backward else
+                 {"plan": 168, "split": 170, "empty": 171, "null": 172, "align": 174, "p0": 175, "launch": 179})
+    lines |= {"scale": lines["plan"], "drop_p": lines["plan"]}  # the slope and drop_p stand in the check of the plan and the heads
+    names = lambda s, t: _three(f"{s}_rows<8, 1{t}>", f"{s}_rows_backward<8, 1{t}>", f"{s}_columns_backward<8, 1{t}>", backward)
+    args = (BWD_GAT_DROP if backward else FWD_GAT_DROP) if drop else (BWD if backward else FWD)
+    p0 = {"p0": names("gat::gat", "") if elem == "fp32" else names(stem, plain_tail)} if drop else {}
+    return _entry("gat_dropout" if drop else "gat", backward, elem, "heads " + args, file, lines, names(stem, tail), at="4b269a3", **p0)
+
+
+# "lines": where each check of an entry point stood in "file" at commit "at".  "plan": NULL plan, missing flag, heads < 1 (GAT: and the slope
+# and drop_p); "drop_p": the dropout probability, beside the scale or the slope; "p0": drop_p == 0 hands over to the undropped kernels;
 # "one_head": heads == 1 forwards to the single-head call; "split": head_split_lg; "empty": no entries; "null": a NULL operand or
 # dWork == dP; "bias_alias": dGradBias == dP or dWork; "align": the refusal of the non-vector form; "no_out": no output wanted;
 # "launch": the launches (the single-head pair: of the 16-byte or of the generic form)
@@ -80,16 +128,30 @@ ENTRIES = {
     "flex_gat_attention_backward": _entry("gat", True, "fp32", "heads " + BWD, "attention_gat_kernels.hip",
                                           {"plan": 489, "scale": 489, "split": 491, "empty": 492, "null": 493, "align": 496, "no_out": 497, "launch": 506},
                                           ["gat::gat_rows_backward<8, 1>", "gat::gat_columns_backward<8, 1>"]),
+    "flex_attention_dropout": _dropout_entry(False, "fp32"),
+    "flex_attention_dropout_backward": _dropout_entry(True, "fp32"),
+    "flex_attention_bf16_dropout": _dropout_entry(False, "bf16"),
+    "flex_attention_bf16_dropout_backward": _dropout_entry(True, "bf16"),
+    "flex_gat_attention_dropout": _gat_entry(False, "fp32", True),
+    "flex_gat_attention_dropout_backward": _gat_entry(True, "fp32", True),
+    "flex_gat_attention_bf16": _gat_entry(False, "bf16", False),
+    "flex_gat_attention_bf16_backward": _gat_entry(True, "bf16", False),
+    "flex_gat_attention_bf16_dropout": _gat_entry(False, "bf16", True),
+    "flex_gat_attention_bf16_dropout_backward": _gat_entry(True, "bf16", True),
 }
 
 # ---- the table.  A row: its name, what it changes in a valid call (a dict: "plan" -> which plan, "off" -> the operand moved 4 bytes,
 # "same" -> (operand, the operand whose address it takes), any other key -> the argument's new value), and per kind of entry point
 # (check that answers, code, what is launched: None = nothing, "valid" = the entry point's kernels, "generic" = the single-head
-# pair's generic form).  The kinds: "single", "heads" (flex_attention_heads and its backward, which forward heads == 1), "perhead" (bf16
-# and the bias forms) and "gat".  A row reaches the entry points of the kinds it names that have the arguments it names; a row that
-# takes outputs away reaches the backward calls.
-ALL = ("single", "heads", "perhead", "gat")
-PER_HEAD = ("heads", "perhead", "gat")
+# pair's generic form, any other name = that entry of the entry point's "launches").  The kinds: "single", "heads" (flex_attention_heads
+# and its backward, which forward heads == 1), "perhead" (bf16 and the bias forms), "dropout" (the four dot-product dropout calls), "gat"
+# (fp32 and bf16 V rows) and "gat_dropout" (the same with dropout).  A row reaches the entry points of the kinds it names that have the
+# arguments it names; a row that takes outputs away reaches the backward calls.
+DOT = ("single", "heads", "perhead", "dropout")
+GAT = ("gat", "gat_dropout")
+DROP = ("dropout", "gat_dropout")
+ALL = DOT + GAT
+PER_HEAD = ("heads", "perhead", "dropout") + GAT
 NO_OUTPUT = {"GQ": None, "GK": None, "GV": None, "GB": None}
 
 
@@ -103,11 +165,11 @@ ROWS = [
     ("plan_without_the_flag", {"plan": "unflagged"}, _same("plan", INVALID)),
     ("heads_0", {"heads": 0}, _same("plan", INVALID, kinds=PER_HEAD)),
     # scale (GAT: slope) comes before the head split and before the empty plan's early exit
-    ("scale_0", {"scale": 0.0}, _same("scale", INVALID, kinds=("single", "heads", "perhead"))),
-    ("scale_nan", {"scale": float("nan")}, _same("scale", INVALID, kinds=("single", "heads", "perhead"))),
-    ("scale_inf", {"scale": float("inf")}, _same("scale", INVALID, kinds=("single", "heads", "perhead"))),
-    ("slope_0", {"scale": 0.0}, _same("scale", INVALID, kinds=("gat",))),
-    ("slope_1.5", {"scale": 1.5}, _same("scale", INVALID, kinds=("gat",))),
+    ("scale_0", {"scale": 0.0}, _same("scale", INVALID, kinds=DOT)),
+    ("scale_nan", {"scale": float("nan")}, _same("scale", INVALID, kinds=DOT)),
+    ("scale_inf", {"scale": float("inf")}, _same("scale", INVALID, kinds=DOT)),
+    ("slope_0", {"scale": 0.0}, _same("scale", INVALID, kinds=GAT)),
+    ("slope_1.5", {"scale": 1.5}, _same("scale", INVALID, kinds=GAT)),
     ("heads_5", {"heads": 5}, _same("split", UNSUPPORTED, kinds=PER_HEAD)),  # 32 columns in 5 heads
     ("scale_0_and_heads_5", {"scale": 0.0, "heads": 5}, _same("scale", INVALID, kinds=PER_HEAD)),
     # FLEX_OK before the NULL-operand check; a bad head split is still refused on it
@@ -126,8 +188,30 @@ ROWS = [
      {"single": ("no_out", OK, None), **_same("align", UNSUPPORTED, kinds=PER_HEAD)}),
     ("null_work_and_v_4_bytes_off", {"Work": None, "off": "V"}, _same("null", INVALID)),
     # heads == 1 of flex_attention_heads and its backward is the single-head call, generic form included; the others run it themselves
-    ("one_head_v_4_bytes_off", {"heads": 1, "off": "V"}, {"heads": ("one_head", OK, "generic"), **_same("align", UNSUPPORTED, kinds=("perhead", "gat"))}),
-    ("one_head_scale_0", {"heads": 1, "scale": 0.0}, {"heads": ("one_head", INVALID, None), **_same("scale", INVALID, kinds=("perhead", "gat"))}),
+    ("one_head_v_4_bytes_off", {"heads": 1, "off": "V"}, {"heads": ("one_head", OK, "generic"), **_same("align", UNSUPPORTED, kinds=("perhead", "dropout") + GAT)}),
+    ("one_head_scale_0", {"heads": 1, "scale": 0.0}, {"heads": ("one_head", INVALID, None), **_same("scale", INVALID, kinds=("perhead", "dropout") + GAT)}),
+    # drop_p is answered beside the scale (GAT: beside the slope, in the check of the plan): before the head split and the empty plan's exit
+    ("drop_p_1", {"drop_p": 1.0}, _same("drop_p", INVALID, kinds=DROP)),
+    ("drop_p_negative", {"drop_p": -0.1}, _same("drop_p", INVALID, kinds=DROP)),
+    ("drop_p_nan", {"drop_p": float("nan")}, _same("drop_p", INVALID, kinds=DROP)),
+    ("drop_p_1_and_heads_5", {"drop_p": 1.0, "heads": 5}, _same("drop_p", INVALID, kinds=DROP)),
+    ("empty_plan_all_null_drop_p_1", {"plan": "empty", "all_null": True, "drop_p": 1.0}, _same("drop_p", INVALID, kinds=DROP)),
+    # the bias of the dot-product dropout calls is optional: NULL runs the kernels without it
+    ("no_bias", {"Bias": None}, _same("launch", OK, "no_bias", kinds=("dropout",))),
+    ("no_gbias", {"GB": None}, _same("launch", OK, "no_bias", kinds=("dropout",))),
+    # drop_p == 0 runs the undropped kernels, and only after every refusal: a misaligned operand is refused for one head too (the
+    # single-head call would run its generic form on it), and nothing runs where no output is wanted
+    ("drop_p_0", {"drop_p": 0.0}, _same("p0", OK, "p0", kinds=DROP)),
+    ("drop_p_0_no_bias", {"drop_p": 0.0, "Bias": None}, _same("p0", OK, "p0_no_bias", kinds=("dropout",))),
+    ("drop_p_0_no_gbias", {"drop_p": 0.0, "GB": None}, _same("p0", OK, "p0_no_bias", kinds=("dropout",))),
+    ("drop_p_0_one_head_no_bias", {"drop_p": 0.0, "heads": 1, "Bias": None}, _same("p0", OK, "p0_no_bias_one_head", kinds=("dropout",))),
+    ("drop_p_0_one_head_no_gbias", {"drop_p": 0.0, "heads": 1, "GB": None}, _same("p0", OK, "p0_no_bias_one_head", kinds=("dropout",))),
+    ("drop_p_0_v_4_bytes_off", {"drop_p": 0.0, "off": "V"}, _same("align", UNSUPPORTED, kinds=DROP)),
+    ("drop_p_0_gv_4_bytes_off", {"drop_p": 0.0, "off": "GV"}, _same("align", UNSUPPORTED, kinds=DROP)),
+    ("drop_p_0_one_head_v_4_bytes_off", {"drop_p": 0.0, "heads": 1, "off": "V"}, _same("align", UNSUPPORTED, kinds=DROP)),
+    ("drop_p_0_one_head_no_bias_v_4_bytes_off", {"drop_p": 0.0, "heads": 1, "Bias": None, "off": "V"}, _same("align", UNSUPPORTED, kinds=("dropout",))),
+    ("drop_p_0_one_head_no_gbias_v_4_bytes_off", {"drop_p": 0.0, "heads": 1, "GB": None, "off": "V"}, _same("align", UNSUPPORTED, kinds=("dropout",))),
+    ("drop_p_0_no_output", {"drop_p": 0.0, **NO_OUTPUT}, _same("no_out", OK, kinds=DROP)),
 ]
 
 
@@ -136,22 +220,22 @@ def _rows_of(name):
     e = ENTRIES[name]
     for row, change, expect in [(f"null_{a}", {a: None}, _same("null", INVALID)) for a in e["need"]] + ROWS:
         named = [a for a in change if a not in ("plan", "all_null", "off", "same")] + [change[m] for m in ("off",) if m in change] + list(change.get("same", ()))
-        if "GB" in change and change["GB"] is None:  # taking away an output that the entry point does not have changes nothing
+        if NO_OUTPUT.items() <= change.items():  # taking every output away: one that the entry point does not have changes nothing
             named.remove("GB")
         if e["kind"] not in expect or any(a not in e["args"] for a in named):
             continue
         if any(a in NO_OUTPUT for a in named) and not e["backward"]:
             continue
         check, code, launch = expect[e["kind"]]
-        kernels = [] if launch is None else e["kernels"] if launch == "valid" else SINGLE_GENERIC[e["backward"]]
+        kernels = [] if launch is None else e["launches"][launch]
         yield row, change, check, code, kernels
 
 
 def _arguments(e, change, plans, ops):
     """(plan handle, the arguments after it) of a row: the valid call's `ops` (name -> address) with the row's change."""
-    ops = dict(ops, heads=H, scale=forms.SLOPE if e["kind"] == "gat" else forms.SCALE)
+    ops = dict(ops, heads=H, scale=forms.SLOPE if e["kind"] in GAT else forms.SCALE, drop_p=DROP_P, seed=SEED)
     if change.get("all_null"):
-        ops.update({a: None for a in e["args"] if a not in ("heads", "scale")})
+        ops.update({a: None for a in e["args"] if a not in ("heads", "scale", "drop_p", "seed")})
     for a, value in change.items():
         if a == "off":
             ops[value] += 4
@@ -172,7 +256,7 @@ def _plans(a):
 
 def _where(name, row, check):
     e = ENTRIES[name]
-    return f"{name}, row {row}: answered by '{check}', {e['file']}:{e['lines'][check]} at 03f89bd"
+    return f"{name}, row {row}: answered by '{check}', {e['file']}:{e['lines'][check]} at {e['at']}"
 
 
 OPERANDS = ("Q", "K", "V", "Out", "G", "P", "Work", "Bias", "GB", "GQ", "GK", "GV")
@@ -211,7 +295,7 @@ def test_the_table_has_every_entry_point_and_every_row_reaches_some():
 def test_every_refusal_of_an_entry_point_keeps_its_code_its_precedence_and_its_launches(sim, sim_plans, name):
     e = ENTRIES[name]
     fn = binding._values_fn(name)
-    ops = {a: forms._fake(i) for i, a in enumerate(OPERANDS)}
+    ops = {a: forms.fake_address(i) for i, a in enumerate(OPERANDS)}
     for row, change, check, code, kernels in _rows_of(name):
         handle, args = _arguments(e, change, sim_plans, ops)
         got = []
@@ -221,6 +305,14 @@ def test_every_refusal_of_an_entry_point_keeps_its_code_its_precedence_and_its_l
     handle, args = _arguments(e, {}, sim_plans, ops)
     assert fn(handle, *args, 0) == UNSUPPORTED
     assert fn(None, *args, 0) == INVALID
+
+
+def test_the_simulator_defines_every_attention_launcher(sim):
+    """In a simulator build the launchers of the dropout and bf16-GAT families are weak references (internal.h, FLEX_SIM_OPTIONAL), so a
+    stand-in that the shim forgot is not an error when the library loads: it is one here, by name, before any call jumps through it."""
+    nm = shutil.which("nm") or "/usr/bin/nm"
+    out = subprocess.run([nm, "-C", "--undefined-only", binding._SO], capture_output=True, text=True, check=True).stdout
+    assert [line.split(None, 1)[1] for line in out.splitlines() if "flex::attention::launch_" in line] == []
 
 
 def test_the_shim_defines_no_attention_entry_point():
@@ -251,13 +343,14 @@ def test_the_real_library_answers_the_table_as_the_simulator_does():
         rows_dtype = torch.bfloat16 if e["elem"] == "bf16" else torch.float32
         edge = (a.nnz,) if e["kind"] == "single" else (a.nnz, H)
         shapes = {x: (a.m, K) for x in ("Q", "K", "V", "Out", "G", "GQ", "GK", "GV")} | {x: edge for x in ("P", "Work", "Bias", "GB")}
-        if e["kind"] == "gat":
-            shapes |= {x: (a.m, H) for x in ("Q", "K", "GQ", "GK")}  # el, er and their gradients (the lifted graph is square: m == n)
+        rows = ("V", "Out", "G", "GV") if e["kind"] in GAT else ("Q", "K", "V", "Out", "G", "GQ", "GK", "GV")  # the operands of the element type
+        if e["kind"] in GAT:
+            shapes |= {x: (a.m, H) for x in ("Q", "K", "GQ", "GK")}  # el, er and their gradients, floats (the lifted graph is square: m == n)
         shapes = {x: shape for x, shape in shapes.items() if x in e["args"]}
         written = [x for x in ("Out", "GQ", "GK", "GV", "GB", "Work") if x in e["args"]] + ([] if e["backward"] else ["P"])
         # every writable operand lies in one buffer filled with a sentinel, so "nothing was written" is one comparison per row; each
         # operand is 256-byte aligned and has four elements of slack, so an address 4 bytes on stays inside
-        dtypes = {x: rows_dtype if x in ("Q", "K", "V", "Out", "G", "GQ", "GK", "GV") else torch.float32 for x in shapes}  # GAT's rows are fp32
+        dtypes = {x: rows_dtype if x in rows else torch.float32 for x in shapes}
         nbytes = {x: -(-(int(np.prod(shapes[x])) + 4) * dtypes[x].itemsize // 256) * 256 for x in shapes}
         outputs = torch.empty(sum(nbytes[x] for x in written), dtype=torch.uint8, device="cuda")
         t, at = {}, 0

@@ -17,7 +17,7 @@ import flex_amd
 import gat_attention_ref as gat
 import gat_bf16_ref as gb
 import gat_dropout_ref as gd
-from attention_forms import FORM_OF_K, FORMS
+from attention_forms import ALL_WANTED, COLUMN_KERNEL_ALONE, FORM_OF_K, FORMS, ROW_KERNEL_ALONE, fake_address
 from conftest import ROOT
 from flex_amd import binding
 from test_gat_dropout_host import CASES as DROP_CASES
@@ -180,7 +180,7 @@ def test_the_library_exports_the_four_calls_and_the_header_declares_them():
     assert re.search(r"#define\s+FLEX_ABI_VERSION\s+3\b", hdr)
     L = ctypes.CDLL(flex_amd.lib_path())
     for name in NAMES_C:
-        assert re.search(r"\bextern\s+int\s+%s\s*\(" % name, code), f"{name} is not declared `extern int` in include/flex_spmm.h"
+        assert re.search(r"^int\s+%s\s*\(" % name, code, re.M), f"{name} is not declared `int {name}(` in include/flex_spmm.h"
         assert hasattr(L, name), f"{name} is not exported"
         assert name in binding.SYMBOLS
     assert [len(binding._values_fn(n).argtypes) for n in NAMES_C] == [9, 13, 11, 15]
@@ -254,3 +254,38 @@ def test_the_library_ships_exactly_the_forty_two_kernels_and_a_gpu_case_runs_eac
     ids = {case_id(c) for c in CASES}
     assert all(v in ids for v in RUN_BY.values())
     assert {FORM_OF_K[k] for k, _ in PAIRS} == set(FORMS)
+
+
+# ---- the census against the launches
+
+@pytest.fixture
+def sim():
+    """(tests/hostsim, flex_amd.binding's library on the host simulator) for one test: the others here run on the library itself."""
+    hostsim = pytest.importorskip("hostsim")
+    for lib in hostsim.binding_on_simulator():
+        yield hostsim, lib
+
+
+def test_every_pair_launches_on_the_simulator_the_kernels_its_cases_declare(sim):
+    """The forward and then the backward of every (k, H), undropped and dropped, on fake operands (nothing is read or written): the
+    library's own entry points on the simulator's stand-in launchers must log kernels_of() of the case, and with one gradient wanted
+    the forward and one backward kernel: gEl the row kernel, gV the column kernel."""
+    hostsim, lib = sim
+    a = graph("thresholds_lifted")
+    el, er, v, out, g, pr, work, gel, ger, gv = (fake_address(i) for i in range(10))
+    for k, H in PAIRS:
+        plan = flex_amd.Plan(a, k, attention=True, attention_backward=True)
+        for p in (None, 0.5):
+            def launch(want):
+                grads = [x if w else None for x, w in zip((gel, ger, gv), want)]
+                if p is None:
+                    plan.gat_attention_bf16_ptr(H, el, er, v, SLOPE, out, pr)
+                    plan.gat_attention_bf16_backward_ptr(H, el, er, v, pr, g, SLOPE, *grads, work)
+                else:
+                    plan.gat_attention_bf16_dropout_ptr(H, el, er, v, SLOPE, p, SEED, out, pr)
+                    plan.gat_attention_bf16_dropout_backward_ptr(H, el, er, v, pr, g, SLOPE, p, SEED, *grads, work)
+            names = ["gat_bf16::" + n for n in kernels_of(("thresholds_lifted", k, H, p))]
+            assert hostsim.launch_log(lib, lambda: launch(ALL_WANTED)) == names, (k, H, p)
+            assert hostsim.launch_log(lib, lambda: launch(ROW_KERNEL_ALONE)) == names[:2], (k, H, p)
+            assert hostsim.launch_log(lib, lambda: launch(COLUMN_KERNEL_ALONE)) == [names[0], names[2]], (k, H, p)
+        plan.destroy()
