@@ -144,6 +144,21 @@ SPMM_BF16_WIDE64_CASES = (
 
 CASES = SINGLE_CASES + HEADS_CASES + GAT_CASES + BF16_CASES + BIAS_FP32_CASES + BIAS_BF16_CASES + SPMM_BF16_CASES + SPMM_BF16_WIDE64_CASES
 
+# ---- the per-head families on padded rows (tests/test_gpu_attention_layouts.py): one (k, H) per (W, NS) form, ldb = k + 4, ldc = k + 8.
+# A padded plan takes the vector form and launches what its dense twin launches: each case is the twin's, with the leading dimensions.
+# Not part of CASES: the census counts every instantiation once through the dense cases, and drops a case from them to see it orphaned
+LAYOUT_DOT_PAIRS = [(8, 2), (32, 4), (48, 3), (128, 8), (256, 4), (512, 4), (1024, 64)]
+LAYOUT_GAT_PAIRS = [(4, 1), (32, 4), (48, 3), (128, 8), (256, 1), (512, 2), (1024, 4)]
+
+
+def _padded(cases, pairs):
+    twin = {(c["k"], c["H"]): c for c in cases}
+    return [dict(twin[k, H], ldb=k + 4, ldc=k + 8) for k, H in pairs]
+
+
+LAYOUT_CASES = (_padded(HEADS_CASES, LAYOUT_DOT_PAIRS) + _padded(GAT_CASES, LAYOUT_GAT_PAIRS) + _padded(BF16_CASES, LAYOUT_DOT_PAIRS)
+                + _padded(BIAS_FP32_CASES, LAYOUT_DOT_PAIRS) + _padded(BIAS_BF16_CASES, LAYOUT_DOT_PAIRS))
+
 
 def case_id(c):
     if c["family"] == "spmm_bf16":

@@ -76,6 +76,28 @@ def test_every_attention_case_launches_the_kernels_it_declares(sim, lifted, c):
     assert hostsim.launch_log(sim, lambda: forms.fake_launch(c, p)) == c["kernels"]
 
 
+@pytest.mark.parametrize("c", forms.LAYOUT_CASES, ids=forms.case_id)
+def test_every_layout_case_launches_the_kernels_it_declares(sim, lifted, c):
+    """A padded per-head plan (ldb = k + 4, ldc = k + 8: multiples of four elements) takes the vector form -- the only one these families
+    have -- and is neither refused nor rerouted: it launches what its dense twin launches."""
+    assert (c["ldb"], c["ldc"]) == (c["k"] + 4, c["k"] + 8) and c not in forms.CASES
+    twin = [d for d in forms.CASES if d["family"] == c["family"] and (d["k"], d["H"], d["ldb"], d["ldc"]) == (c["k"], c["H"], c["k"], c["k"])]
+    assert len(twin) == 1 and twin[0]["kernels"] == c["kernels"] and twin[0]["want"] == c["want"]
+    p = _plan(c, lifted)
+    assert hostsim.launch_log(sim, lambda: forms.fake_launch(c, p)) == c["kernels"]
+    odd = flex_amd.Plan(lifted, c["k"], attention=True, attention_backward=True, ldb=c["k"] + 6, ldc=c["ldc"])  # ldb % 4 == 2: refused, nothing logged
+    with pytest.raises(binding.FlexError, match="not supported"):
+        hostsim.launch_log(sim, lambda: forms.fake_launch(c, odd))
+    odd.destroy()
+
+
+def test_the_layout_cases_run_every_form_of_every_per_head_family_the_table_knows():
+    families = {}
+    for c in forms.LAYOUT_CASES:
+        families.setdefault(c["family"], []).append(forms.FORM_OF_K[c["k"]])
+    assert set(families) == {"heads", "gat", "bf16", "bias_fp32", "bias_bf16"} and all(f == forms.FORMS for f in families.values())
+
+
 @pytest.mark.parametrize("c", forms.SPMM_BF16_CASES, ids=forms.case_id)
 def test_every_bf16_spmm_case_launches_the_kernels_it_declares(sim, c):
     import spmm_bf16_ref as ref

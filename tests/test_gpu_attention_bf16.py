@@ -279,6 +279,33 @@ def test_refused_calls():
         p.attention(Q, K, V, SCALE, heads=4)
 
 
+def test_rows_8_bytes_off_a_16_byte_mark_are_served_and_give_the_bits_of_the_aligned_run():
+    """What the refusals above stop short of: a row operand four elements (8 bytes) into its buffer is aligned as the 8-byte form needs.
+    Q and gK alone, then every row operand (Q, K, V, g, Out, gQ, gK, gV): nothing is refused, every output has the aligned run's bits,
+    and the elements before and after the moved rows keep their fill."""
+    name, k, H = "directed_empty", 32, 4
+    a, names, Q, K, V, g = case_operands(name, k, H)
+    p = plan(name, k)
+    aligned = dict(zip(("out", "p", "gq", "gk", "gv", "ds"), _run(name, k, H)))
+    s = torch.cuda.current_stream().cuda_stream
+    rows = {"Q": a.m, "K": a.n, "V": a.n, "g": a.m, "out": a.m, "gq": a.m, "gk": a.n, "gv": a.n}
+    for moved in (("Q", "gk"), tuple(rows)):
+        t = {key: _filled((r * k + 8,)) for key, r in rows.items()}
+        at = {key: 4 if key in moved else 0 for key in t}
+        for key, x in (("Q", Q), ("K", K), ("V", V), ("g", g)):
+            t[key][at[key]:at[key] + rows[key] * k] = _dev_bf16(x).view(-1)
+        ptr = {key: t[key].data_ptr() + 2 * at[key] for key in t}
+        assert all((ptr[key] % 16 == 8) == (key in moved) for key in t)
+        pd, work = (torch.full((a.nnz, H), SENTINEL, device="cuda") for _ in range(2))
+        p.attention_bf16_ptr(ptr["Q"], ptr["K"], ptr["V"], SCALE, ptr["out"], pd.data_ptr(), s, heads=H)
+        p.attention_bf16_backward_ptr(ptr["Q"], ptr["K"], ptr["V"], pd.data_ptr(), ptr["g"], SCALE, ptr["gq"], ptr["gk"], ptr["gv"], work.data_ptr(), s, heads=H)
+        for key in ("out", "gq", "gk", "gv"):
+            x, lo, hi = _bits(t[key]), at[key], at[key] + rows[key] * k
+            assert bool((x[:lo] == FILL).all()) and bool((x[hi:] == FILL).all()), (moved, key)
+            assert _same_bits(x[lo:hi].reshape(rows[key], k), aligned[key]), (moved, key)
+        assert _same_bits(_host(pd), aligned["p"]) and _same_bits(_host(work), aligned["ds"]), moved
+
+
 # ---- 7. a row-range shard, forward
 
 def test_a_shard_writes_its_own_rows_and_entries_only_and_has_no_backward():

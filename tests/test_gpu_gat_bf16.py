@@ -421,13 +421,49 @@ def test_refused_calls_leave_the_outputs_untouched():
         assert untouched()
         shard.destroy()
     fwd, bwd, untouched = calls(p, 4, k, shift=8, grad_shift=8)                   # 8-byte aligned rows are served: nothing is refused
-    fwd(), bwd()
+    fwd(), bwd()                                                                  # (and compute the aligned run's bits: the test below)
     empty = binding.HostCsr(np.zeros(41, np.uint32), np.zeros(0, np.uint32), np.zeros(0, np.float32), n=17)
     pe = flex_amd.Plan(empty, k, attention=True, attention_backward=True)
     pe.gat_attention_bf16_ptr(4, None, None, None, SLOPE, None)  # no entries: no launch, nothing read
     pe.gat_attention_bf16_backward_ptr(4, None, None, None, None, None, SLOPE, None, None, None, None)
     pe.gat_attention_bf16_dropout_ptr(4, None, None, None, SLOPE, 0.5, SEED, None)
     pe.gat_attention_bf16_dropout_backward_ptr(4, None, None, None, None, None, SLOPE, 0.5, SEED, None, None, None, None)
+
+
+@pytest.mark.parametrize("drop", [None, 0.5], ids=["plain", "p0.5"])
+def test_rows_8_bytes_off_a_16_byte_mark_give_the_bits_of_the_aligned_run(drop):
+    """The shift=8, grad_shift=8 call of the refusals on real operands: V and gV four elements into their buffers, then every row operand
+    (V, g, Out, gV).  Every output has the aligned run's bits, and the elements before and after the moved rows keep their fill."""
+    c = ("directed_empty", 32, 4, drop)
+    name, k, H, _ = c
+    a, el, er, V, g = case_operands(name, k, H)
+    p = plan(name, k)
+    aligned = dict(zip(KEYS, _run(c)))
+    s = torch.cuda.current_stream().cuda_stream
+    eld, erd = _dev(el), _dev(er)
+    rows = {"V": a.n, "g": a.m, "out": a.m, "gv": a.n}
+    for moved in (("V", "gv"), ("V", "g", "out", "gv")):
+        t = {key: _filled16((r * k + 8,)) for key, r in rows.items()}
+        at = {key: 4 if key in moved else 0 for key in t}
+        for key, x in (("V", V), ("g", g)):
+            t[key][at[key]:at[key] + rows[key] * k] = _dev16(x).view(-1)
+        ptr = {key: t[key].data_ptr() + 2 * at[key] for key in t}
+        assert all((ptr[key] % 16 == 8) == (key in moved) for key in t)
+        pd, work, gel, ger = _filled((a.nnz, H)), _filled((a.nnz, H)), _filled((a.m, H)), _filled((a.n, H))
+        if drop is None:
+            p.gat_attention_bf16_ptr(H, eld.data_ptr(), erd.data_ptr(), ptr["V"], SLOPE, ptr["out"], pd.data_ptr(), s)
+            p.gat_attention_bf16_backward_ptr(H, eld.data_ptr(), erd.data_ptr(), ptr["V"], pd.data_ptr(), ptr["g"], SLOPE, gel.data_ptr(), ger.data_ptr(),
+                                              ptr["gv"], work.data_ptr(), s)
+        else:
+            p.gat_attention_bf16_dropout_ptr(H, eld.data_ptr(), erd.data_ptr(), ptr["V"], SLOPE, drop, SEED, ptr["out"], pd.data_ptr(), s)
+            p.gat_attention_bf16_dropout_backward_ptr(H, eld.data_ptr(), erd.data_ptr(), ptr["V"], pd.data_ptr(), ptr["g"], SLOPE, drop, SEED,
+                                                      gel.data_ptr(), ger.data_ptr(), ptr["gv"], work.data_ptr(), s)
+        for key in ("out", "gv"):
+            x, lo, hi = _host(t[key]), at[key], at[key] + rows[key] * k
+            assert _is_fill(x[:lo]) and _is_fill(x[hi:]), (moved, key)
+            assert _same_bits(x[lo:hi].reshape(rows[key], k), aligned[key]), (moved, key)
+        for key, x in (("p", pd), ("gel", gel), ("ger", ger), ("dx", work)):
+            assert _same_bits(_host(x), aligned[key]), (moved, key)
 
 
 # ---- 8. a row-range shard, forward
