@@ -254,6 +254,8 @@ static int create_common(flex_plan **out, const flex_csr *hostA, bool all_rows, 
     const bool attn_bwd = (flags & FLEX_PLAN_ATTENTION_BACKWARD) != 0;
     if (attn_bwd && !attn) return FLEX_ERR_INVALID;
     if (attn_bwd && !all_rows) return FLEX_ERR_UNSUPPORTED;
+    // hub rows are cut by schedule window (plan_build.cpp, cut_hub_rows) on plans of the caller's own square matrix, all rows, only
+    if (attn || transposed || !all_rows) tuning.hub_row = 1;
     flags &= ~(FLEX_PLAN_ATTENTION | FLEX_PLAN_ATTENTION_BACKWARD);  // the planner proper never sees them: the record stream is what it is without the flags
     TransposedCsr at;
     if (transposed) {
@@ -421,6 +423,8 @@ int flex_plan_get_info(const flex_plan *p, flex_plan_info *o) {
     o->block_records = static_cast<int64_t>(p->d_bk_rec.size());
     o->n_bundles = p->n_bundles;
     o->bundle_rows = p->bundle_rows;
+    o->n_moved_pieces = p->n_moved_pieces;
+    o->moved_records = p->moved_records;
     return FLEX_OK;
 }
 

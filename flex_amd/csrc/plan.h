@@ -114,6 +114,7 @@ struct flex_plan {
     uint64_t rec_fp = 0;          // packed plans: fingerprint of the 8-byte stream the image encodes (self-check)
     uint32_t n_bundles = 0;
     int64_t bundle_rows = 0;                // rows that sit in bundles
+    int64_t n_moved_pieces = 0, moved_records = 0;  // hub rows cut by schedule window (plan_build.cpp, cut_hub_rows)
     flex::DeviceArray<float> d_partial;
     flex::DeviceArray<flex::SplitRow> d_split;
     flex::DeviceArray<uint32_t> d_split_cnt;

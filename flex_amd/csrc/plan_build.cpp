@@ -7,9 +7,10 @@
 //   order_rows             sched[i] = row processed i-th (natural / RCM / community / Gorder), colpos = its inverse
 //   route_dense_tiles      detector report; 32x32 tiles dense enough for the MFMA kernel leave the record stream
 //   read_knobs             chunk budget, piece length, 2-D panel size ... (rules measured on MI355X, env overrides)
-//   cut_rows_into_pieces   a row is one piece, or several: by length (hubs) and, in 2-D, by column panel
+//   cut_rows_into_pieces   a row is one piece, or several: by length (hubs) and, in 2-D, by column panel; 1-D plans that qualify also
+//                          cut the records of a hub row by the schedule window of their column (moved pieces, cut_hub_rows)
 //   slice_rows_for_xcds    2-D: the eight row slices (1-D cuts the chunk table by cost instead, below)
-//   order_pieces           emission order: schedule order, or per slice phase by phase
+//   order_pieces           emission order: schedule order (a moved piece at its window's positions), or per slice phase by phase
 //   number_split_rows      rows summed from several pieces: consecutive partial slots + the arrival bookkeeping
 //   pack_tasks_into_chunks one task per piece, tasks packed into per-wave chunks of about one budget
 //   fill_records           {B-row offset, value} per nonzero, padded to whole steps (parallel over tasks)
@@ -40,10 +41,12 @@ namespace {
 struct Piece {
     uint32_t spos;       // position of the piece's row in the schedule
     uint32_t beg, end;   // its records [beg,end) in rcol/rval
-    uint32_t phase;      // 0 in 1-D; column panel + 1, or kFarPhase, in 2-D
+    uint32_t phase;      // 2-D: column panel + 1, or kFarPhase.  1-D: 0, or -- a row cut by cut_hub_rows, records in pcol/pval -- kHomePhase
+                         // for its home part and kMovedPhase + window for a moved piece
     uint32_t own_chunk;  // a slice of a run longer than one budget: a chunk of its own
 };
 constexpr uint32_t kFarPhase = 0xFFFFFFFEu;
+constexpr uint32_t kHomePhase = 1u, kMovedPhase = 2u;
 // What a task is made of: one piece, or a BUNDLE -- up to S short whole rows side by side, slot s of every step working on row s,
 // so that nothing is reduced across slots and a finished bundle is one 16-byte store per lane (spmm_kernels.hip, flush).
 struct TaskSpec {
@@ -162,6 +165,13 @@ class PlanBuilder {
     const float *rval = nullptr;
     uint32_t slice_row[kXcds + 1] = {0};  // 2-D: schedule positions of the XCD slices
     std::vector<uint32_t> emit;           // pieces in emission order
+    // hub rows cut by schedule window (cut_hub_rows): 0 = off
+    uint32_t hub_row = 0, hub_window = 0, hub_min_run = 0;
+    struct MovedPiece {
+        uint32_t epos, piece;  // emission position (a schedule position of the piece's window), index in `pieces`
+    };
+    std::vector<MovedPiece> moved;  // in piece order
+    int64_t moved_records = 0;
     // tasks
     bool bundles_on = false;
     uint32_t bundle_len = 0;              // rows of at most this many records are candidates for a bundle
@@ -499,8 +509,51 @@ class PlanBuilder {
         pack_mode = !pack_shape || tn.rec_pack == 2 ? 0 : tn.rec_pack == 1 ? 2 : (ktiles >= 2 && stream_bytes >= (32ull << 20)) ? 1 : 0;
         far_window = two_d ? 0u : static_cast<uint32_t>(std::max(0, tn.far_first));  // (2-D pieces are cut by column panel already)
         p->tuning.far_first = static_cast<int32_t>(far_window);
+        // Hub rows cut by schedule window (cut_hub_rows).  A row longer than one budget is summed from pieces anyway, so
+        // a piece may run anywhere in the schedule: the records of a row of at least `hub_row` records whose columns' vertices sit in
+        // one window of `hub_window` schedule positions -- at least `hub_min_run` of them, and not the row's own window -- become a
+        // piece that is emitted among the rows of THAT window, where the XCD that walks them keeps those B rows in its L2.  That needs
+        // schedule positions that are vertices (the whole square matrix, rows and columns named alike), contiguous XCD slices, and every
+        // nonzero on the 1-D record stream; plans whose records are also read by entry (FLEX_PLAN_MUTABLE_VALUES) keep the CSR order of
+        // a row, and plan.cpp turns the cut off for transposed and attention plans.  A knob of 1 forces the
+        // cut off; hub_row > 1 forces it on wherever the plan's kind allows it.
+        // The rule (MI355X, k = 128, plain bench.py runs alternated with the cut forced off; profiles/hub_pieces_ab_series.json,
+        // DESIGN.md 3.4): on when the plan fills the chip and the rows of at least hub_row records hold a tenth of the nonzeros.
+        // At 1024 / 8192 / 32: Amazon preset 8.056-8.069 -> 7.880-7.911 ms (-2.1 %, five runs each) on 52.06 -> 43.85 GB counted,
+        // Reddit preset 638-641 -> 623-628 us; the Flickr preset does not fill the chip and keeps its image.  min_run: 8 loses
+        // (8.10 -> 8.17-8.30: 3-5 M more padding records and twice the partial rows cost more than the misses saved), 16 gains 1.4 %,
+        // 32 is the optimum of 32 ... 128; hub_row 512-4096 and windows of 8192-16384 are level within 0.2 %, windows of 4096 lose
+        // with their shorter runs.
+        // Not looked at here: the moved pieces add exceptions to the packed stream (Amazon 2.0 -> 2.65 % of the records), and
+        // pack_records applies its limit of one per 16 records to the stream as cut -- a graph near that limit loses its packing to
+        // the cut (hub_row = 1 keeps it).  And col_map == dst_map compares the POINTERS: one map for rows and columns (a mapped
+        // loader), or none; two equal arrays passed separately leave the plan uncut.
+        const bool hub_off = tn.hub_row == 1 || tn.hub_window == 1 || tn.hub_min_run == 1;
+        const bool whole_graph = A->m == A->n && r0 == 0 && r1 == A->m && col_map == dst_map;
+        const bool hub_kind = !two_d && !mut && m > 0 && whole_graph && tiles.nnz == 0 && p->bk_blocks == 0 && p->xcd_remap && !xcd_dealt;
+        hub_row = hub_window = hub_min_run = 0;
+        if (hub_kind && !hub_off) {
+            const uint32_t row = static_cast<uint32_t>(std::max<long>(2, pick(tn.hub_row, 1024)));
+            bool on = tn.hub_row > 1;
+            if (!on && fills_the_chip()) {  // the rows of at least `row` records hold a tenth of the nonzeros or more
+                int64_t in_hubs = 0;
+                for (int32_t r = r0; r < r1; ++r) {
+                    const uint32_t len = A->rowPtr[r + 1] - A->rowPtr[r];
+                    if (len >= row) in_hubs += len;
+                }
+                on = in_hubs * 10 >= slice_nnz();
+            }
+            if (on) {
+                hub_row = row;
+                hub_window = static_cast<uint32_t>(std::max<long>(2, pick(tn.hub_window, 8192)));
+                hub_min_run = static_cast<uint32_t>(std::max<long>(2, pick(tn.hub_min_run, 32)));
+            }
+        }
         // what this plan was built with (flex_plan_get_tuning)
         flex_plan_tuning &u = p->tuning;
+        u.hub_row = hub_row ? static_cast<int32_t>(hub_row) : 1;
+        u.hub_window = hub_row ? static_cast<int32_t>(hub_window) : 1;
+        u.hub_min_run = hub_row ? static_cast<int32_t>(hub_min_run) : 1;
         u.lanes_per_nz = G;
         u.chunk_records = static_cast<int32_t>(wave_nnz);
         u.long_row = static_cast<int32_t>(long_row);
@@ -543,7 +596,8 @@ class PlanBuilder {
     // A run of `len` records as pieces: one, or (longer than a budget) several of about one budget.  The last piece to
     // arrive sums all of them with ONE wave, so a hub of 10^6 nonzeros cut into 10^4 budget-sized pieces spent 0.9 ms
     // in that sum alone (tools/probe_hub.py: 1263 us against 358 us without the hub): at most 256 pieces per run,
-    // longer ones instead: 564 us (774 pieces: 601 us).
+    // longer ones instead: 564 us (774 pieces: 601 us).  The cap is per RUN: a row cut by cut_hub_rows has one run per window
+    // it moves records to and may hold several hundred pieces in all (the Amazon preset's longest lists).
     void cut_run(std::vector<Piece> &out, uint32_t spos, uint32_t b, uint32_t e, uint32_t phase) const {
         const uint32_t len = e - b;
         if (len <= long_row) {
@@ -561,6 +615,7 @@ class PlanBuilder {
         rcol = A->col;
         rval = A->vals;
         if (two_d) return cut_by_column_panel();
+        if (hub_row) return cut_hub_rows();
         pieces.reserve(static_cast<size_t>(m) + 1024);
         for (int32_t i = 0; i < m; ++i) {
             const uint32_t r = sched[i];
@@ -568,6 +623,107 @@ class PlanBuilder {
             cut_run(pieces, static_cast<uint32_t>(i), A->rowPtr[r], A->rowPtr[r + 1], 0u);
         }
         row_first_piece[m] = static_cast<uint32_t>(pieces.size());
+        return FLEX_OK;
+    }
+
+    // 1-D with hub rows cut by schedule window (read_knobs).  The records of a row of at least hub_row records are grouped by the
+    // window of hub_window schedule positions their column's vertex sits in.  A group of at least hub_min_run records of another
+    // window than the row's own is a MOVED piece; all other records are the row's HOME part, and both keep the CSR order of their
+    // records.  Such a row's records are re-grouped into pcol/pval -- home part first, then the moved runs by window -- and its pieces
+    // point there (Piece::phase says so); a hub row without a moved run, like every other row, stays in A's arrays.  A run longer
+    // than one budget is cut by cut_run like any other.  The pieces of a row stay consecutive in `pieces`, home first: that order
+    // numbers the row's partial slots (number_split_rows) and is the order its sum is taken in.  What moves is a piece's place in
+    // the EMISSION order: the j-th of the n moved pieces of a window of L positions (counted in piece order) is emitted at position
+    // first + floor(j L / n) of that window -- a rule of the input alone.  Parallel over hub rows, results placed in row order.
+    int cut_hub_rows() {
+        std::vector<uint32_t> hub_pos;  // schedule positions of the hub rows
+        std::vector<uint64_t> hub_off(1, 0);
+        for (int32_t i = 0; i < m; ++i) {
+            const uint32_t r = sched[i], len = A->rowPtr[r + 1] - A->rowPtr[r];
+            if (len < hub_row) continue;
+            hub_pos.push_back(static_cast<uint32_t>(i));
+            hub_off.push_back(hub_off.back() + len);
+        }
+        if (hub_off.back() >= (uint64_t(1) << 32)) return FLEX_ERR_UNSUPPORTED;
+        pcol.resize(static_cast<size_t>(hub_off.back()));
+        pval.resize(static_cast<size_t>(hub_off.back()));
+        const int64_t n_hub = static_cast<int64_t>(hub_pos.size());
+        std::vector<std::vector<Piece>> cut(static_cast<size_t>(n_hub));
+        std::atomic<int> failed{0};
+        parallel_chunks(n_hub, [&](int64_t h) {
+            try {
+                const uint32_t i = hub_pos[static_cast<size_t>(h)], r = sched[i];
+                const uint32_t e0 = A->rowPtr[r], len = A->rowPtr[r + 1] - e0, own = i / hub_window;
+                std::vector<uint64_t> key(len);  // (window << 32) | index within the row
+                for (uint32_t z = 0; z < len; ++z) {
+                    const uint32_t c = A->col[e0 + z];
+                    key[z] = (static_cast<uint64_t>((colpos.empty() ? c : colpos[c]) / hub_window) << 32) | z;
+                }
+                std::sort(key.begin(), key.end());  // by window, CSR order within a window
+                std::vector<uint8_t> moves(len, 0);
+                uint32_t n_home = len;
+                for (uint32_t z0 = 0, z1; z0 < len; z0 = z1) {
+                    for (z1 = z0 + 1; z1 < len && (key[z1] >> 32) == (key[z0] >> 32); ++z1) {}
+                    if (z1 - z0 < hub_min_run || static_cast<uint32_t>(key[z0] >> 32) == own) continue;
+                    for (uint32_t z = z0; z < z1; ++z) moves[key[z] & 0xFFFFFFFFu] = 1;
+                    n_home -= z1 - z0;
+                }
+                if (n_home == len) return;  // nothing moves: an ordinary row
+                std::vector<Piece> &out = cut[static_cast<size_t>(h)];
+                const uint32_t o0 = static_cast<uint32_t>(hub_off[static_cast<size_t>(h)]);
+                uint32_t o = o0;
+                for (uint32_t z = 0; z < len; ++z)
+                    if (!moves[z]) {
+                        pcol[o] = A->col[e0 + z];
+                        pval[o] = A->vals[e0 + z];
+                        ++o;
+                    }
+                if (n_home) cut_run(out, i, o0, o, kHomePhase);
+                for (uint32_t z0 = 0, z1; z0 < len; z0 = z1) {
+                    for (z1 = z0 + 1; z1 < len && (key[z1] >> 32) == (key[z0] >> 32); ++z1) {}
+                    if (!moves[key[z0] & 0xFFFFFFFFu]) continue;
+                    const uint32_t b = o;
+                    for (uint32_t z = z0; z < z1; ++z, ++o) {
+                        pcol[o] = A->col[e0 + (key[z] & 0xFFFFFFFFu)];
+                        pval[o] = A->vals[e0 + (key[z] & 0xFFFFFFFFu)];
+                    }
+                    cut_run(out, i, b, o, kMovedPhase + static_cast<uint32_t>(key[z0] >> 32));
+                }
+            } catch (...) {
+                failed.store(1);
+            }
+        });
+        if (failed.load()) return FLEX_ERR_NOMEM;
+        pieces.reserve(static_cast<size_t>(m) + 1024);
+        const uint32_t n_win = (static_cast<uint32_t>(m) + hub_window - 1) / hub_window;
+        std::vector<uint32_t> in_window(n_win, 0u), seen(n_win, 0u);
+        size_t h = 0;
+        for (int32_t i = 0; i < m; ++i) {
+            const uint32_t r = sched[i];
+            row_first_piece[i] = static_cast<uint32_t>(pieces.size());
+            const bool hub = h < hub_pos.size() && hub_pos[h] == static_cast<uint32_t>(i);
+            if (hub && !cut[h].empty()) {
+                for (const Piece &pc : cut[h]) {
+                    if (pc.phase >= kMovedPhase) {
+                        moved.push_back({pc.phase - kMovedPhase, static_cast<uint32_t>(pieces.size())});  // the window, for now
+                        ++in_window[pc.phase - kMovedPhase];
+                        moved_records += pc.end - pc.beg;
+                    }
+                    pieces.push_back(pc);
+                }
+            } else {
+                cut_run(pieces, static_cast<uint32_t>(i), A->rowPtr[r], A->rowPtr[r + 1], 0u);
+            }
+            h += hub ? 1 : 0;
+        }
+        row_first_piece[m] = static_cast<uint32_t>(pieces.size());
+        if (pieces.size() >= (size_t(1) << 31)) return FLEX_ERR_UNSUPPORTED;
+        for (MovedPiece &mp : moved) {
+            const uint32_t w = mp.epos, first = w * hub_window, positions = std::min<uint32_t>(hub_window, static_cast<uint32_t>(m) - first);
+            mp.epos = first + static_cast<uint32_t>(static_cast<uint64_t>(seen[w]++) * positions / in_window[w]);
+        }
+        p->n_moved_pieces = static_cast<int64_t>(moved.size());
+        p->moved_records = moved_records;
         return FLEX_OK;
     }
 
@@ -685,6 +841,21 @@ class PlanBuilder {
     // emission order: 1-D = schedule order; 2-D = per slice, phase by phase (rows in schedule order inside a phase)
     void order_pieces() {
         emit.resize(pieces.size());
+        if (!two_d && !moved.empty()) {
+            // a stable sort of the pieces by emission position -- a moved piece's own (cut_hub_rows), any other piece's row's -- as a
+            // merge: both kinds are in that order already once the moved ones are sorted among themselves
+            std::vector<MovedPiece> by_pos(moved);
+            std::stable_sort(by_pos.begin(), by_pos.end(), [](const MovedPiece &a, const MovedPiece &b) { return a.epos < b.epos; });
+            size_t at = 0, q = 0;
+            for (uint32_t i = 0; i < pieces.size(); ++i) {
+                if (pieces[i].phase >= kMovedPhase) continue;
+                for (; q < by_pos.size() && (by_pos[q].epos < pieces[i].spos || (by_pos[q].epos == pieces[i].spos && by_pos[q].piece < i)); ++q)
+                    emit[at++] = by_pos[q].piece;
+                emit[at++] = i;
+            }
+            for (; q < by_pos.size(); ++q) emit[at++] = by_pos[q].piece;
+            return;
+        }
         std::iota(emit.begin(), emit.end(), 0u);
         if (!two_d) return;
         parallel_chunks(kXcds, [&](int64_t x) {
@@ -748,7 +919,8 @@ class PlanBuilder {
         };
         for (uint32_t e = 0; e < n_pieces; ++e) {
             const Piece &pc = pieces[emit[e]];
-            if (pc.own_chunk == 0 && pc.end - pc.beg <= bundle_len) {  // 1-D: a piece that is not a slice of a long row is a whole row
+            // 1-D: a piece that is neither a slice of a long row nor a part of a row cut by cut_hub_rows is a whole row
+            if (pc.own_chunk == 0 && pc.phase == 0 && pc.end - pc.beg <= bundle_len) {
                 buf.push_back(e);
                 if (buf.size() == 8u * S) flush_buf();
             } else {
@@ -822,11 +994,14 @@ class PlanBuilder {
         const uint32_t n_tasks = static_cast<uint32_t>(tasks.size());
         const uint32_t row_bytes32 = static_cast<uint32_t>(p->ldb) * 4u;
         constexpr int64_t kTaskBlk = 4096;
-        auto record_of = [&](uint32_t e) {
-            uint32_t c = rcol[e];
+        // where a piece's records are: rcol/rval, or -- a row cut by cut_hub_rows -- pcol/pval
+        auto cols_of = [&](const Piece &pc) { return hub_row && pc.phase ? pcol.data() : rcol; };
+        auto vals_of = [&](const Piece &pc) { return hub_row && pc.phase ? pval.data() : rval; };
+        auto record_of = [&](const Piece &pc, uint32_t e) {
+            uint32_t c = cols_of(pc)[e];
             if (col_map) c = static_cast<uint32_t>(col_map[c]);
             uint32_t bits;
-            std::memcpy(&bits, &rval[e], 4);
+            std::memcpy(&bits, &vals_of(pc)[e], 4);
             return make_uint2(p->off32 ? c * row_bytes32 : c, bits);
         };
         // mutable plans: which entry of the caller's CSR record `at` holds, and its value as given (the padding rule may change the
@@ -856,7 +1031,7 @@ class PlanBuilder {
                             const Piece &pc = pieces[emit[bundle_piece[ts.ref + s]]];
                             len = pc.end - pc.beg;
                             for (uint32_t j = 0; j < len; ++j) {
-                                base[static_cast<size_t>(j) * S + s] = record_of(pc.beg + j);
+                                base[static_cast<size_t>(j) * S + s] = record_of(pc, pc.beg + j);
                                 note_entry(t_beg[t] + static_cast<size_t>(j) * S + s, pc.beg + j);
                             }
                         }
@@ -881,7 +1056,7 @@ class PlanBuilder {
                 if (far_window == 0) {
                     for (uint32_t e = pc.beg; e < pc.end; ++e) {
                         note_entry(static_cast<size_t>(o - rec.data()), e);
-                        *o++ = record_of(e);
+                        *o++ = record_of(pc, e);
                     }
                 } else {
                     // FAR records first (tuning.far_first): a column whose vertex sits far from the row in the schedule is a likely L2
@@ -890,7 +1065,7 @@ class PlanBuilder {
                     // only their groups do.  The order inside each class is kept; the sum order of a row changes, its value within
                     // rounding, reproducibly.
                     const auto is_far = [&](uint32_t e) {
-                        const uint32_t c = rcol[e];
+                        const uint32_t c = cols_of(pc)[e];
                         const int64_t cp = colpos.empty() ? static_cast<int64_t>(c) : static_cast<int64_t>(colpos[c]);
                         const int64_t d = cp - static_cast<int64_t>(colpos.empty() ? r : i);
                         return (d < 0 ? -d : d) > static_cast<int64_t>(far_window);
@@ -899,7 +1074,7 @@ class PlanBuilder {
                         for (uint32_t e = pc.beg; e < pc.end; ++e)
                             if (is_far(e) != (near == 1)) {
                                 note_entry(static_cast<size_t>(o - rec.data()), e);
-                                *o++ = record_of(e);
+                                *o++ = record_of(pc, e);
                             }
                 }
                 // pad to a whole number of steps

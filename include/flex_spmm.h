@@ -238,7 +238,18 @@ typedef struct flex_plan_tuning {
                                 a column difference beyond 16 bits, 8 bytes each -- per 16 records).  Never on 2-D plans, on plans with
                                 FLEX_PLAN_MUTABLE_VALUES or FLEX_PLAN_ATTENTION, or where k, ldb or ldc is no multiple of 4: flex_plan_get_tuning
                                 then reports 2.  C is bit for bit the same either way */
-    int32_t reserved[4];     /* zero */
+    int32_t hub_row;         /* hub rows cut by schedule window (plan_build.cpp, cut_hub_rows): of a row of at least this many
+                                nonzeros (1024), those whose columns' vertices sit in one window of the schedule become a piece that runs
+                                among the rows of THAT window, beside the rows that read the same B rows.  > 1 also forces the cut on where
+                                the kind of plan allows it: the whole square matrix on the 1-D record stream, contiguous XCD slices, no dense
+                                tiles or hot blocks taken, rows and columns named alike -- no map, or ONE array passed as both col_map and row_map
+                                (flex_plan_create_mapped); two separate arrays, even equal ones, leave the plan uncut; never with
+                                FLEX_PLAN_MUTABLE_VALUES, FLEX_PLAN_ATTENTION, FLEX_PLAN_TRANSPOSE or a
+                                row range.  1 in any of the three knobs forces it off, and is what flex_plan_get_tuning reports when it is
+                                off.  C stays within rounding (a hub row's sum is taken in another order), reproducibly */
+    int32_t hub_window;      /* ... schedule positions per window (8192) */
+    int32_t hub_min_run;     /* ... a window's nonzeros move only if they are at least this many (32) */
+    int32_t reserved[1];     /* zero */
 } flex_plan_tuning;
 
 typedef struct flex_plan_desc {
@@ -854,6 +865,9 @@ typedef struct flex_plan_info {
     /* row bundles (0 when the plan has none) */
     int64_t n_bundles;        /* tasks that hold several short rows side by side */
     int64_t bundle_rows;      /* rows inside them */
+    /* hub rows cut by schedule window (flex_plan_tuning.hub_row; 0 when the cut is off) */
+    int64_t n_moved_pieces;   /* pieces of hub rows that run at their columns' place in the schedule instead of their row's */
+    int64_t moved_records;    /* nonzeros they hold */
 } flex_plan_info;
 int flex_plan_get_info(const flex_plan *plan, flex_plan_info *out);
 
