@@ -14,7 +14,9 @@ in three launches (flex_attention_bias, flex_attention_bf16_bias and their backw
 probabilities after the softmax, with or without a bias, in the same three launches (flex_attention_dropout, flex_attention_bf16_dropout
 and their backward calls): the mask is a hash of (seed, entry, head), so autograd keeps the seed and no mask.  gat_attention on a
 torch.bfloat16 V, with or without dropout, runs the same three launches on bf16 V rows (flex_gat_attention_bf16,
-flex_gat_attention_bf16_dropout and their backward calls: float32 scores and sums, Out and grad V in bfloat16).  torch is imported
+flex_gat_attention_bf16_dropout and their backward calls: float32 scores and sums, Out and grad V in bfloat16).
+gatv2_attention(xt, xs, att) runs GATv2's score att[h] . LeakyReLU(xt[row] + xs[col]), which needs the full rows, in one forward launch
+and up to three backward launches (flex_gatv2_attention, flex_gatv2_attention_backward), float32 only.  torch is imported
 lazily, as in binding.py."""
 from __future__ import annotations
 
@@ -337,6 +339,44 @@ def gat_dropout_functions():
     return _gat_dropout_cache
 
 
+def _gatv2_function():
+    import torch
+
+    class _FusedGatv2Attention(torch.autograd.Function):
+        """Out = A(alpha) xs per head, alpha = softmax over each row of A of <att[h], leaky_relu(xt[row] + xs[col], slope)> over the head's
+        columns: flex_gatv2_attention in one launch, alpha [nnz, heads] kept only when a gradient is needed; backward: the one call
+        flex_gatv2_attention_backward (up to three launches) for the gradients that are needed, in xt, xs and att.  xt may be xs: torch
+        sums the two gradients.  It sets no plan's values.  Only on an operator made with fused_attention=True and fused_backward=True."""
+
+        @staticmethod
+        def forward(ctx, xt, xs, att, op, slope):
+            xt, xs, att = xt.contiguous(), xs.contiguous(), att.contiguous()
+            p = torch.zeros((op.nnz, att.shape[0]), dtype=torch.float32, device=xs.device) if any(ctx.needs_input_grad[:3]) else None
+            out = op.plan.gatv2_attention(xt, xs, att, slope, p=p)
+            ctx.op, ctx.slope = op, slope
+            ctx.save_for_backward(xt, xs, att, p)
+            return out
+
+        @staticmethod
+        def backward(ctx, grad_out):
+            xt, xs, att, p = ctx.saved_tensors
+            grads = ctx.op.plan.gatv2_attention_backward(xt, xs, att, p, grad_out.contiguous(), ctx.slope, want=tuple(ctx.needs_input_grad[:3]))
+            return (*grads, None, None)
+
+    return (_FusedGatv2Attention,)
+
+
+_gatv2_cache = None
+
+
+def gatv2_functions():
+    """(_FusedGatv2Attention,): the autograd Function of the GATv2 attention, built at first use, as gat_dropout_functions()."""
+    global _gatv2_cache
+    if _gatv2_cache is None:
+        _gatv2_cache = _gatv2_function()
+    return _gatv2_cache
+
+
 def _gat_bf16_function():
     import torch
 
@@ -568,3 +608,18 @@ class SparseOperator:
             fn = gat_bf16_functions()[1] if bf16 else gat_dropout_functions()[0]
             return fn.apply(el, er, V, self, float(negative_slope), float(dropout), int(seed) & 0xFFFFFFFFFFFFFFFF)
         return (gat_bf16_functions()[0] if bf16 else functions()[7]).apply(el, er, V, self, float(negative_slope))
+
+    def gatv2_attention(self, xt, xs, att, negative_slope: float = 0.2):
+        """Out [m, k] = A(alpha) xs per head with alpha = softmax over each row of A of <att[h], leaky_relu(xt[row] + xs[col],
+        negative_slope)> over the head's columns: the attention of a GATv2 layer (PyG's and DGL's GATv2Conv), xt = h W_t and xs = h W_s
+        being the transformed features and the source row score operand and value alike.  H = att.shape[0] heads; head h is columns
+        [h k / H, (h + 1) k / H) of xt, xs and Out.  Differentiable in xt [m, k], xs [n, k] and att [H, k / H]; all heads in one forward
+        launch and up to three backward launches (flex_gatv2_attention); needs fused_attention=True and fused_backward=True.  xt may be
+        xs (share_weights): autograd sums the two gradients.  float32 only: any other dtype is a TypeError."""
+        if not (self.fused_attention and self.fused_backward):
+            raise NotImplementedError("gatv2_attention needs SparseOperator(..., learn_values=True, fused_attention=True, fused_backward=True): "
+                                      "only the fused forward and backward compute the score from the full rows")
+        import torch
+        if not (xt.dtype == xs.dtype == att.dtype == torch.float32):
+            raise TypeError(f"gatv2_attention takes float32 xt, xs and att, not {xt.dtype}, {xs.dtype} and {att.dtype}")
+        return gatv2_functions()[0].apply(xt, xs, att, self, float(negative_slope))

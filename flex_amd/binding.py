@@ -172,6 +172,7 @@ SYMBOLS = [
     "flex_attention_dropout", "flex_attention_dropout_backward", "flex_attention_bf16_dropout", "flex_attention_bf16_dropout_backward",
     "flex_dropout_mask", "flex_gat_attention_dropout", "flex_gat_attention_dropout_backward",
     "flex_gat_attention_bf16", "flex_gat_attention_bf16_backward", "flex_gat_attention_bf16_dropout", "flex_gat_attention_bf16_dropout_backward",
+    "flex_gatv2_attention", "flex_gatv2_attention_backward", "flex_gatv2_attention_work_size",
 ]
 
 _lib = None
@@ -262,7 +263,7 @@ def lib():
 
 def _values_fn(name: str):
     """flex_plan_set_values / flex_sddmm / flex_edge_softmax / flex_edge_softmax_backward, the 22 fused-attention calls (flex_attention*,
-    flex_gat_attention*) and flex_spmm_bf16, looked up at first use and not when the library loads: a host-only build without the kernel
+    flex_gat_attention*), the three GATv2 calls (flex_gatv2_attention*) and flex_spmm_bf16, looked up at first use and not when the library loads: a host-only build without the kernel
     files does not have to define them.  tests/hostsim defines them all: the attention calls are the library's own entry points
     (csrc/attention_entry.h) on stand-in launchers that only log which kernel the real ones would launch, the others are stand-ins that
     log the same way."""
@@ -293,7 +294,10 @@ def _values_fn(name: str):
                       "flex_gat_attention_bf16": [vp, i32, vp, vp, vp, fl, vp, vp, vp],
                       "flex_gat_attention_bf16_backward": [vp, i32, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp],
                       "flex_gat_attention_bf16_dropout": [vp, i32, vp, vp, vp, fl, fl, u64, vp, vp, vp],
-                      "flex_gat_attention_bf16_dropout_backward": [vp, i32, vp, vp, vp, vp, vp, fl, fl, u64, vp, vp, vp, vp, vp]}[name]
+                      "flex_gat_attention_bf16_dropout_backward": [vp, i32, vp, vp, vp, vp, vp, fl, fl, u64, vp, vp, vp, vp, vp],
+                      "flex_gatv2_attention": [vp, i32, vp, vp, vp, fl, vp, vp, vp],
+                      "flex_gatv2_attention_backward": [vp, i32, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp, vp],
+                      "flex_gatv2_attention_work_size": [vp, C.POINTER(u64)]}[name]
     return f
 
 
@@ -1072,6 +1076,81 @@ class Plan:
         self.gat_attention_backward_ptr(heads, el.data_ptr(), er.data_ptr(), V.data_ptr(), p.data_ptr(), grad_out.data_ptr(), slope,
                                         *(None if t is None else t.data_ptr() for t in outs), work.data_ptr(),
                                         torch.cuda.current_stream(V.device).cuda_stream)
+        return tuple(outs)
+
+    def gatv2_attention_ptr(self, heads: int, dXt_ptr: int, dXs_ptr: int, dAtt_ptr: int, slope: float, dOut_ptr: int, dP_ptr: int | None = None,
+                            stream: int = 0):
+        """flex_gatv2_attention; dXt is rows x k floats (stride ldc), dXs n x k (stride ldb), dAtt k, dP (optional) nnz x H, entry-major."""
+        _check(_values_fn("flex_gatv2_attention")(self._h, heads, dXt_ptr, dXs_ptr, dAtt_ptr, slope, dOut_ptr, dP_ptr, stream), "flex_gatv2_attention")
+
+    def gatv2_attention_backward_ptr(self, heads: int, dXt_ptr: int, dXs_ptr: int, dAtt_ptr: int, dP_ptr: int, dGradOut_ptr: int, slope: float,
+                                     dGradXt_ptr: int | None, dGradXs_ptr: int | None, dGradAtt_ptr: int | None, dWork_ptr: int,
+                                     dAttWork_ptr: int | None = None, stream: int = 0):
+        """flex_gatv2_attention_backward; dP and dWork are nnz x H floats, entry-major; dAttWork holds gatv2_attention_work_size() floats
+        and is needed where dGradAtt is wanted."""
+        _check(_values_fn("flex_gatv2_attention_backward")(self._h, heads, dXt_ptr, dXs_ptr, dAtt_ptr, dP_ptr, dGradOut_ptr, slope, dGradXt_ptr,
+                                                           dGradXs_ptr, dGradAtt_ptr, dWork_ptr, dAttWork_ptr, stream), "flex_gatv2_attention_backward")
+
+    def gatv2_attention_work_size(self) -> int:
+        """flex_gatv2_attention_work_size: the floats of the dAttWork of gatv2_attention_backward_ptr (k per workgroup of its row launch)."""
+        n = C.c_uint64(0)
+        _check(_values_fn("flex_gatv2_attention_work_size")(self._h, C.byref(n)), "flex_gatv2_attention_work_size")
+        return int(n.value)
+
+    def _gatv2_operands(self, xt, xs, att):
+        """heads, from att [H, d]; xt [m, k] like C, xs [n, k] like B: float32 cuda tensors, k = H d."""
+        import torch
+        i = self.info()
+        assert att.dim() == 2 and att.shape[0] >= 1 and att.shape[0] * att.shape[1] == i["k"], "att is [heads, k / heads]"
+        for t, shape in ((xt, (i["m"], i["k"])), (xs, (i["n"], i["k"])), (att, tuple(att.shape))):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape, "float32 cuda, xt [m, k], xs [n, k]"
+        return int(att.shape[0])
+
+    def gatv2_attention(self, xt, xs, att, slope: float = 0.2, out=None, p=None):
+        """flex_gatv2_attention: out [m, k] = sum over each row's entries of alpha xs[col] per head, alpha = the softmax over the row of
+        <att[h], leaky_relu(xt[row, head h] + xs[col, head h], slope)>, in one launch.  xt: [m, k], xs: [n, k], att: [H, k / H]; float32
+        cuda tensors; xt may be xs.  p (optional): a float32 cuda tensor [a.nnz, H] that receives alpha in a's CSR order for the plan's
+        rows (entries of other shards keep what it held)."""
+        import torch
+        i = self.info()
+        heads = self._gatv2_operands(xt, xs, att)
+        if out is None:  # every row is written, except by a plan without entries, which launches nothing
+            out = (torch.empty if i["nnz"] else torch.zeros)((i["m"], i["k"]), dtype=torch.float32, device=xs.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (i["m"], i["k"])
+        if p is not None:
+            self._head_edge_arrays(heads, p)
+        self.gatv2_attention_ptr(heads, xt.data_ptr(), xs.data_ptr(), att.data_ptr(), slope, out.data_ptr(), None if p is None else p.data_ptr(),
+                                 torch.cuda.current_stream(xs.device).cuda_stream)
+        return out
+
+    def gatv2_attention_backward(self, xt, xs, att, p, grad_out, slope: float = 0.2, grad_xt=None, grad_xs=None, grad_att=None, work=None,
+                                 want=(True, True, True), att_work=None):
+        """flex_gatv2_attention_backward: (gXt [m, k], gXs [n, k], gAtt [H, k / H]) of gatv2_attention()'s out from its p [a.nnz, H] and
+        grad_out [m, k], in up to three launches; an output that `want` does not ask for is None and is not computed.  work (optional): a
+        float32 cuda tensor [a.nnz, H], not p, that receives dz = p (da - delta) per entry whenever a gradient is wanted.  att_work
+        (optional): float32 cuda, at least gatv2_attention_work_size() floats; it is allocated here when gAtt is wanted and it is not passed."""
+        import torch
+        i = self.info()
+        heads = self._gatv2_operands(xt, xs, att)
+        assert grad_out.is_cuda and grad_out.dtype == torch.float32 and grad_out.is_contiguous() and tuple(grad_out.shape) == (i["m"], i["k"])
+        if work is None:
+            work = torch.empty((self.src_nnz, heads), dtype=torch.float32, device=xs.device)
+        self._head_edge_arrays(heads, p, work)
+        outs = []
+        for wanted, t, shape in zip(want, (grad_xt, grad_xs, grad_att), ((i["m"], i["k"]), (i["n"], i["k"]), tuple(att.shape))):
+            if wanted and t is None:  # every element is written, except by a plan without entries, which launches nothing
+                t = (torch.empty if i["nnz"] else torch.zeros)(shape, dtype=torch.float32, device=xs.device)
+            if wanted:
+                assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape
+            outs.append(t if wanted else None)
+        if outs[2] is not None:
+            need = self.gatv2_attention_work_size()
+            if att_work is None:
+                att_work = torch.empty(max(need, 1), dtype=torch.float32, device=xs.device)
+            assert att_work.is_cuda and att_work.dtype == torch.float32 and att_work.is_contiguous() and att_work.numel() >= need
+        self.gatv2_attention_backward_ptr(heads, xt.data_ptr(), xs.data_ptr(), att.data_ptr(), p.data_ptr(), grad_out.data_ptr(), slope,
+                                          *(None if t is None else t.data_ptr() for t in outs), work.data_ptr(),
+                                          None if outs[2] is None else att_work.data_ptr(), torch.cuda.current_stream(xs.device).cuda_stream)
         return tuple(outs)
 
     def gat_attention_dropout_ptr(self, heads: int, dEl_ptr: int, dEr_ptr: int, dV_ptr: int, slope: float, p: float, seed: int, dOut_ptr: int,

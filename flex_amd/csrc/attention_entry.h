@@ -13,6 +13,8 @@
 // and dWork == dP; the gBias aliases; alignment; no output wanted (OK).  GAT (six calls, one template pair over the element type of the V
 // rows, with a drop flag): the slope and drop_p stand in the first check, beside the plan and the heads; the rest is the per-head order.
 // drop_p == 0 is no refusal: it launches the undropped kernels of the same operands, after every check.
+// The GATv2 calls (flex_gatv2_attention, flex_gatv2_attention_backward, flex_gatv2_attention_work_size) are not among the 22: their entry
+// points live in attention_gatv2_entry.h, which attention_gatv2_kernels.hip alone includes, on launchers of namespace flex::gatv2.
 #pragma once
 #include <cmath>
 #include <cstdint>

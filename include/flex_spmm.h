@@ -35,6 +35,7 @@ extern "C" {
                               the equally additive flex_attention_dropout, flex_attention_bf16_dropout, their backward calls and flex_dropout_mask (five new calls, no flag, no struct),
                               the equally additive flex_gat_attention_dropout and flex_gat_attention_dropout_backward (two new calls, no flag, no struct),
                               the equally additive flex_gat_attention_bf16, flex_gat_attention_bf16_dropout and their backward calls (four new calls, no flag, no struct),
+                              the equally additive flex_gatv2_attention, flex_gatv2_attention_backward and flex_gatv2_attention_work_size (three new calls, no flag, no struct),
                               and the retired flex_plan_tuning.block_ablate, which keeps its place as block_ablate_retired and must be zero.
                               3: plan-time knobs leave the environment for the struct flex_plan_tuning, flex_plan_desc.tuning, flex_plan_get_tuning,
                               flex_order_cluster_ex, flex_set_host_threads; split rows are summed by a second launch by default.
@@ -833,6 +834,71 @@ int flex_gat_attention_bf16_dropout(const flex_plan *plan, int heads, const floa
 int flex_gat_attention_bf16_dropout_backward(const flex_plan *plan, int heads, const float *dEl, const float *dEr, const flex_bf16 *dV,
                                              const float *dP, const flex_bf16 *dGradOut, float slope, float drop_p, uint64_t seed,
                                              float *dGradEl, float *dGradEr, flex_bf16 *dGradV, float *dWork, flex_stream_t stream);
+
+/* The fused GATv2 attention (Brody, Alon, Yahav: "How attentive are graph attention networks?"; PyG's and DGL's GATv2Conv): the score
+ * a_h . LeakyReLU(W_t h_r + W_s h_c) cannot be written as el[r] + er[c], so it is formed from the full rows, in one forward launch and
+ * up to three backward launches on the plans of flex_attention_heads (FLEX_PLAN_ATTENTION, for the backward FLEX_PLAN_ATTENTION_BACKWARD
+ * as well; no flag of its own).  dXt is [rows of the plan, k] with Q's row convention and stride ldc, dXs is [hostA->n, k] with stride
+ * ldb.  Definition:
+ * - k = H d.
+ * - Head h owns columns [h d, (h + 1) d) of Xt, Xs, Out, g, gXt, gXs.
+ * - att is [H, d], which is k floats.  The coefficient of column c is att[c].
+ * - dP and dWork are [nnz, H], entry-major.
+ * For entry e of row r with source c = src(e), head h, column j of the head:
+ *     x_ej    = Xt[r, hd + j] + Xs[c, hd + j]
+ *     s_eh    = sum_j att[hd + j] * (x_ej > 0 ? x_ej : slope * x_ej)        (0 and NaN take the slope branch, as torch's leaky_relu)
+ *     alpha_.h = flex_edge_softmax's softmax over the row, scale 1
+ *     Out[r, head h] = sum_e alpha_eh Xs[c, head h]                           (the source row is score operand AND value, as in the paper, PyG and DGL)
+ *
+ *     da_eh   = <g[r, head h], Xs[c, head h]>     delta_rh = sum_e p_eh da_eh     dz_eh = p_eh (da_eh - delta_rh)
+ *     f_ej    = x_ej > 0 ? 1 : slope
+ *     gXt[r, hd + j] = sum_{e in r}       dz_eh att[hd + j] f_ej
+ *     gXs[c, hd + j] = sum_{src(e) = c}  (dz_eh att[hd + j] f_ej  +  p_eh g[row(e), hd + j])
+ *     gAtt[hd + j]   = sum_{all e}        dz_eh leaky(x_ej)
+ * Scope: fp32 only; d in {4, ..., 256}, a power of two, for every H, H = 1 included; k <= 1024; only the 16-byte form (k, ldb and ldc
+ * multiples of 4, every row operand -- Xt, Xs, att, Out, g, gXt, gXs, dAttWork -- 16-byte aligned); 0 < slope <= 1 and finite.  dXt may
+ * be the same buffer as dXs (share_weights; the plan is then square with ldb == ldc): every output has the bits of the call on two copies.
+ * Non-finite values: the forward keeps the softmax rules (s = -inf gives p = +0; a NaN or +inf score poisons that head of that row
+ * only: NaN in its d columns of Out and its entries of dP); there is no masking operand; the backward on non-finite operands is what
+ * the formulas give under IEEE.  Rows of gXt without entries and rows of gXs whose column has no entry are written as +0.
+ * Launches.  Forward: one.  Backward: the row launch runs whenever a gradient is wanted (each needs dz): it writes dz over da in
+ * dWork, gXt where wanted and, where gAtt is wanted, one k-row of partial sums per workgroup into dAttWork; the column launch runs for
+ * gXs alone; a small reduction launch, which sums the rows of dAttWork in an order that depends on the plan alone, runs for gAtt alone.
+ * Each of dGradXt, dGradXs, dGradAtt may be NULL; with none wanted the call returns FLEX_OK and launches nothing; an output has the
+ * same bits whichever others are asked for.  dAttWork must hold the floats that flex_gatv2_attention_work_size reports (k floats per
+ * workgroup of the row launch: a figure of the plan's walk, not of nnz x k); it is required only where dGradAtt is wanted.
+ * Checks, in this order: plan, flag, heads < 1, slope: FLEX_ERR_INVALID.  k % heads, d, k > 1024: FLEX_ERR_UNSUPPORTED.  A plan without
+ * entries: FLEX_OK, nothing written.  A NULL operand (Xt, Xs, att, Out; in the backward Xt, Xs, att, P, GradOut, Work, and AttWork where
+ * GradAtt is wanted) and dWork == dP: FLEX_ERR_INVALID.  Alignment: FLEX_ERR_UNSUPPORTED.  No output wanted: FLEX_OK.  The forward
+ * runs on row-range shards and writes the dP entries of its rows only; the backward is FLEX_ERR_INVALID there.  Asynchronous on
+ * `stream`, no allocation, no host synchronisation (safe to capture in a hipGraph), no atomics, fixed order: bit-identical run to run.
+ *
+ * Accuracy, with the u, gamma, E, D_r, R_r of flex_attention, n_r / n_c the entries of the row / column, L_ej = leaky(x_ej),
+ * w_ej = att_j f_ej; forward against float64 on the fp32 inputs, backward against float64 on the SAME fp32 Xt, Xs, att, p and g.  The
+ * float64 reference takes the branch of the leaky ReLU from the sign of the fp32 sum fl(Xt + Xs) and uses the fp32 value of slope.
+ *   score   ds_e     = gamma(d + 2) sum_j |att_j| |L_ej| + (d + sum_j |att_j|) 2^-149
+ *   alpha   dalpha_e = alpha_e [gamma(n_r + 4 D_r + (E + 3) R_r + 2 E + 4) + expm1(2 max_row(ds + |s| u))] + 2^-126
+ *   Out     |Out - Out64| <= sum_e (gamma(n_r + 3) alpha_e + dalpha_e) |Xs| + 2^-126
+ *   dda_e    = gamma(d) sum_j |g Xs| + d 2^-149
+ *   ddz_e    = gamma(n_r + 3) p_e (|da_e| + sum_j |p_j da_j|) + p_e (dda_e + sum_j p_j dda_j) + n_r 2^-149        (dWork is held to it)
+ *   |gXt - gXt64|   <= sum_{e in r} [(gamma(n_r + 1) |dz_e| + ddz_e) |w_ej| + |dz_e| 2^-149] + 2^-126
+ *   |gXs - gXs64|   <= sum_{e in c} [(gamma(2 n_c + 1) |dz_e| + ddz_e) |w_ej| + gamma(2 n_c) p_e |g[row]| + |dz_e| 2^-149] + 2^-126
+ *   |gAtt - gAtt64| <= sum_{all e}  [(gamma(T + 3) |dz_e| + ddz_e) |L_ej| + |dz_e| 2^-149] + 2^-126
+ *   T = min(nnz, 2048 + ceil(max_r n_r / 4) + ceil(m / 4) + 24)
+ * Derivation.  x = fl(xt + xs) is one rounding, L = x or fl(slope x) at most one more, which may be subnormal (2^-149, times |att_j|
+ * in the score); the score is a chain of four fmas per lane and a tree over the d / 4 lanes of the head, d roundings at most, each
+ * possibly subnormal: ds, which takes the place of flex_gat_attention's gamma(2) |s|.  From the scores on, alpha, Out, da, delta and dz are
+ * flex_gat_attention's code and bounds.  w = att or fl(att slope): one rounding.  gXt adds dz w by one fma per entry and the merges of
+ * the slots and waves, a tree of depth <= n_r; gXs adds two fmas per entry into one row, depth <= 2 n_c.  gAtt adds dz L by one fma per
+ * entry on a lane across the rows of its wave's group (at most the group budget, 2048 entries, or a quarter of a block row), then the
+ * slots (<= 4 steps), the waves (3), the chain of every fourth partial row (one row per workgroup, at most ceil(m / 4) + 2 of them to
+ * a chain) and the four chains (3): T, and never more than nnz, additions of zeros being exact.  First order, as the bounds above. */
+int flex_gatv2_attention(const flex_plan *plan, int heads, const float *dXt, const float *dXs, const float *dAtt, float slope, float *dOut,
+                         float *dP /* optional */, flex_stream_t stream);
+int flex_gatv2_attention_backward(const flex_plan *plan, int heads, const float *dXt, const float *dXs, const float *dAtt, const float *dP,
+                                  const float *dGradOut, float slope, float *dGradXt, float *dGradXs, float *dGradAtt, float *dWork,
+                                  float *dAttWork, flex_stream_t stream);
+int flex_gatv2_attention_work_size(const flex_plan *plan, uint64_t *floats); /* the size of dAttWork */
 
 /* ≙ alpha_freeMatGPU (mat.cuh:184-193). */
 int flex_plan_destroy(flex_plan *plan);

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Sparse graph attention, measured: the error of the exponential the edge softmax may use, and the time of flex_edge_softmax,
 flex_edge_softmax_backward and a whole attention step.  Writes profiles/attention_probe.txt (or the file given with --out): the whole run
-starts the file, a run of one part (--fused, --backward, --heads, --gat, --bf16, --bias, --dropout, --gat-dropout, --gat-bf16) appends to it.
+starts the file, a run of one part (--fused, --backward, --heads, --gat, --bf16, --bias, --dropout, --gat-dropout, --gat-bf16, --gatv2)
+appends to it.
 
 1. tools/exp_error.hip (built here with hipcc into flex_amd/lib if it is not there): the largest error in ulp of expf, __expf and
    exp2f on the prescaled argument over every fp32 argument in [-104, 0] against float64 exp.
@@ -49,7 +50,12 @@ starts the file, a run of one part (--fused, --backward, --heads, --gat, --bf16,
    (256, 8), without dropout and with p = 0.6, same graphs and protocol: the forward (with dP), the two-launch backward and the autograd
    step of gat_attention on bfloat16 V against the same three on float32 V (flex_gat_attention, flex_gat_attention_dropout) on the same
    operator, in the same process.  --gat-bf16: only this part (and the copy rate).
-Usage: probe_attention.py [--out FILE] [--fused | --backward | --heads | --gat | --bf16 | --bias | --dropout | --gat-dropout | --gat-bf16] [graph ...]   (default: pubmed.csv flickr reddit soc-sign-epinions)"""
+13. GATv2 (flex_gatv2_attention, flex_gatv2_attention_backward), (k, H) = (64, 8), (128, 4), (256, 8), same graphs and protocol: the
+   one-launch forward (with dP), the backward (all three gradients: three launches) and the autograd step of gatv2_attention against
+   what a user had before -- the [nnz, k] tensor Xt[row] + Xs[col] and the scores in torch, then per head edge_softmax and the SpMM
+   with values=alpha of an operator of width d on a column slice, torch autograd carrying the gradients.  --gatv2: only this part
+   (and the copy rate).
+Usage: probe_attention.py [--out FILE] [--fused | --backward | --heads | --gat | --bf16 | --bias | --dropout | --gat-dropout | --gat-bf16 | --gatv2] [graph ...]   (default: pubmed.csv flickr reddit soc-sign-epinions)"""
 import ctypes as C
 import os
 import subprocess
@@ -548,14 +554,79 @@ def probe_gat_bf16(name, a):
         del op, plan
 
 
+def probe_gatv2(name, a):
+    import numpy as np
+    gen = torch.Generator(device="cuda").manual_seed(13)
+    rp = a.rowPtr.astype(np.int64)
+    rows = torch.from_numpy(np.repeat(np.arange(a.m), np.diff(rp))).cuda()
+    cols = torch.from_numpy(a.col.astype(np.int64)).cuda()
+    slope = 0.2
+    for k, H in ((64, 8), (128, 4), (256, 8)):
+        d = k // H
+        fused = flex_amd.SparseOperator(a, k, learn_values=True, fused_attention=True, fused_backward=True)
+        one = flex_amd.SparseOperator(a, d, learn_values=True)  # what a user had: one head at a time on a column slice
+        xt, xs = (torch.rand((r, k), device="cuda", generator=gen) * 4 - 2 for r in (a.m, a.n))
+        att = torch.rand((H, d), device="cuda", generator=gen) * 2 - 1
+        g = torch.rand((a.m, k), device="cuda", generator=gen) * 2 - 1
+        out, gxt, gxs, gatt = torch.empty((a.m, k), device="cuda"), torch.empty((a.m, k), device="cuda"), torch.empty((a.n, k), device="cuda"), torch.empty((H, d), device="cuda")
+        P, W = torch.empty((a.nnz, H), device="cuda"), torch.empty((a.nnz, H), device="cuda")
+        att_floats = fused.plan.gatv2_attention_work_size()
+        AW = torch.empty(max(1, att_floats), device="cuda")
+        xtg, xsg, attg = (x.clone().requires_grad_() for x in (xt, xs, att))
+
+        def loop(xt, xs, att):
+            s = (torch.nn.functional.leaky_relu((xt[rows] + xs[cols]).view(-1, H, d), slope) * att).sum(-1)  # the [nnz, k] tensor
+            return torch.cat([one(xs[:, h * d:(h + 1) * d].contiguous(), values=one.edge_softmax(s[:, h].contiguous())) for h in range(H)], 1)
+
+        def loop_forward():
+            with torch.no_grad():
+                loop(xt, xs, att)
+
+        def clear():
+            for x in (xtg, xsg, attg):
+                x.grad = None
+
+        kept = loop(xtg, xsg, attg)
+
+        def loop_backward():
+            clear()
+            kept.backward(g, retain_graph=True)
+
+        def loop_step():
+            clear()
+            loop(xtg, xsg, attg).backward(g)
+
+        def fused_step():
+            clear()
+            fused.gatv2_attention(xtg, xsg, attg, slope).backward(g)
+
+        fused.plan.gatv2_attention(xt, xs, att, slope, out=out, p=P)
+        fns = {"forward, loop": loop_forward, "forward, fused": lambda: fused.plan.gatv2_attention(xt, xs, att, slope, out=out, p=P),
+               "backward, loop": loop_backward,
+               "backward, fused": lambda: fused.plan.gatv2_attention_backward(xt, xs, att, P, g, slope, grad_xt=gxt, grad_xs=gxs, grad_att=gatt, work=W, att_work=AW),
+               "step, loop": loop_step, "step, fused": fused_step}
+        n = max(3, min(100, int(1e8 / max(1, a.nnz * k))))
+        rounds = {key: [] for key in fns}
+        for _ in range(3):  # alternating: every round times each contender once
+            for key, fn in fns.items():
+                rounds[key].append(best_us(fn, n, rounds=1))
+        best = {key: min(v) for key, v in rounds.items()}
+        spread = {key: 100 * (max(v) - min(v)) / min(v) for key, v in rounds.items()}
+        say(f"{name} k={k} H={H} d={d} gatv2: " + "  ".join(f"{key} {best[key]:.1f} us (+{spread[key]:.0f} % over 3 rounds)" for key in fns)
+            + "  loop / fused: " + "  ".join(f"{w} {best[w + ', loop'] / best[w + ', fused']:.2f}x" for w in ("forward", "backward", "step"))
+            + f"  edge arrays of a step: fused {8 * a.nnz * H / 2 ** 20:.1f} MiB (P and work) + {4 * att_floats / 2 ** 20:.2f} MiB (gAtt partials), "
+              f"loop {4 * a.nnz * k / 2 ** 20:.1f} MiB for Xt[row] + Xs[col] alone")
+        del fused, one, kept
+
+
 def main():
     args = sys.argv[1:]
     out = os.path.join(ROOT, "profiles", "attention_probe.txt")
     if args[:1] == ["--out"]:
         out, args = args[1], args[2:]
-    fused_only, backward_only, heads_only, gat_only, bf16_only, bias_only, dropout_only, gat_dropout_only, gat_bf16_only = (
-        args[:1] == [flag] for flag in ("--fused", "--backward", "--heads", "--gat", "--bf16", "--bias", "--dropout", "--gat-dropout", "--gat-bf16"))
-    only = fused_only or backward_only or heads_only or gat_only or bf16_only or bias_only or dropout_only or gat_dropout_only or gat_bf16_only
+    fused_only, backward_only, heads_only, gat_only, bf16_only, bias_only, dropout_only, gat_dropout_only, gat_bf16_only, gatv2_only = (
+        args[:1] == [flag] for flag in ("--fused", "--backward", "--heads", "--gat", "--bf16", "--bias", "--dropout", "--gat-dropout", "--gat-bf16", "--gatv2"))
+    only = fused_only or backward_only or heads_only or gat_only or bf16_only or bias_only or dropout_only or gat_dropout_only or gat_bf16_only or gatv2_only
     if only:
         args = args[1:]
     else:
@@ -584,6 +655,11 @@ def main():
             probe_gat_dropout(name, a)
         if gat_bf16_only or not only:
             probe_gat_bf16(name, a)
+        if gatv2_only or not only:
+            try:
+                probe_gatv2(name, a)
+            except torch.cuda.OutOfMemoryError:  # the loop's [nnz, k] tensors and their autograd copies
+                say(f"{name} gatv2: the torch composition ran out of device memory")
     with open(out, "a" if only else "w") as f:  # a part is appended, the whole run starts the file
         f.write("\n".join(LINES) + "\n")
 
