@@ -16,8 +16,9 @@ and their backward calls): the mask is a hash of (seed, entry, head), so autogra
 torch.bfloat16 V, with or without dropout, runs the same three launches on bf16 V rows (flex_gat_attention_bf16,
 flex_gat_attention_bf16_dropout and their backward calls: float32 scores and sums, Out and grad V in bfloat16).
 gatv2_attention(xt, xs, att) runs GATv2's score att[h] . LeakyReLU(xt[row] + xs[col]), which needs the full rows, in one forward launch
-and up to three backward launches (flex_gatv2_attention, flex_gatv2_attention_backward), float32 only.  torch is imported
-lazily, as in binding.py."""
+and up to three backward launches (flex_gatv2_attention, flex_gatv2_attention_backward), float32 only; with dropout= it drops the
+probabilities after the softmax in the same launches (flex_dropout_gatv2_attention and its backward call), keeping the seed and no
+mask.  torch is imported lazily, as in binding.py."""
 from __future__ import annotations
 
 from . import binding
@@ -377,6 +378,47 @@ def gatv2_functions():
     return _gatv2_cache
 
 
+def _gatv2_dropout_function():
+    import torch
+
+    class _FusedGatv2AttentionDropout(torch.autograd.Function):
+        """_FusedGatv2Attention with the probabilities dropped after the softmax (probability drop_p, the kept ones scaled by
+        1 / (1 - drop_p)): flex_dropout_gatv2_attention in one launch, the UNDROPPED alpha [nnz, heads] kept only when a gradient is
+        needed; backward: the one call flex_dropout_gatv2_attention_backward (up to three launches) under the same drop_p and seed, which
+        recomputes the mask from the seed -- no mask is stored.  Only on an operator made with fused_attention=True and
+        fused_backward=True."""
+
+        @staticmethod
+        def forward(ctx, xt, xs, att, op, slope, drop_p, seed):
+            xt, xs, att = xt.contiguous(), xs.contiguous(), att.contiguous()
+            p = torch.zeros((op.nnz, att.shape[0]), dtype=torch.float32, device=xs.device) if any(ctx.needs_input_grad[:3]) else None
+            out = op.plan.gatv2_attention_dropout(xt, xs, att, slope, drop_p, seed, probs=p)
+            ctx.op, ctx.slope, ctx.drop_p, ctx.seed = op, slope, drop_p, seed
+            ctx.save_for_backward(xt, xs, att, p)
+            return out
+
+        @staticmethod
+        def backward(ctx, grad_out):
+            xt, xs, att, p = ctx.saved_tensors
+            grads = ctx.op.plan.gatv2_attention_dropout_backward(xt, xs, att, p, grad_out.contiguous(), ctx.slope, ctx.drop_p, ctx.seed,
+                                                                 want=tuple(ctx.needs_input_grad[:3]))
+            return (*grads, None, None, None, None)
+
+    return (_FusedGatv2AttentionDropout,)
+
+
+_gatv2_dropout_cache = None
+
+
+def gatv2_dropout_functions():
+    """(_FusedGatv2AttentionDropout,): the autograd Function of the GATv2 attention dropout, built at first use; gatv2_functions() keeps
+    its one."""
+    global _gatv2_dropout_cache
+    if _gatv2_dropout_cache is None:
+        _gatv2_dropout_cache = _gatv2_dropout_function()
+    return _gatv2_dropout_cache
+
+
 def _gat_bf16_function():
     import torch
 
@@ -609,17 +651,28 @@ class SparseOperator:
             return fn.apply(el, er, V, self, float(negative_slope), float(dropout), int(seed) & 0xFFFFFFFFFFFFFFFF)
         return (gat_bf16_functions()[0] if bf16 else functions()[7]).apply(el, er, V, self, float(negative_slope))
 
-    def gatv2_attention(self, xt, xs, att, negative_slope: float = 0.2):
+    def gatv2_attention(self, xt, xs, att, negative_slope: float = 0.2, dropout: float = 0.0, seed: int | None = None, training: bool = True):
         """Out [m, k] = A(alpha) xs per head with alpha = softmax over each row of A of <att[h], leaky_relu(xt[row] + xs[col],
         negative_slope)> over the head's columns: the attention of a GATv2 layer (PyG's and DGL's GATv2Conv), xt = h W_t and xs = h W_s
         being the transformed features and the source row score operand and value alike.  H = att.shape[0] heads; head h is columns
         [h k / H, (h + 1) k / H) of xt, xs and Out.  Differentiable in xt [m, k], xs [n, k] and att [H, k / H]; all heads in one forward
         launch and up to three backward launches (flex_gatv2_attention); needs fused_attention=True and fused_backward=True.  xt may be
-        xs (share_weights): autograd sums the two gradients.  float32 only: any other dtype is a TypeError."""
+        xs (share_weights): autograd sums the two gradients.  float32 only: any other dtype is a TypeError.
+        dropout (0 <= dropout < 1) with training=True: the probabilities are dropped after the softmax with that probability and the
+        kept ones scaled by 1 / (1 - dropout), in the same launches (flex_dropout_gatv2_attention); a dropped entry stays in the
+        softmax.  The mask is a hash of (seed, entry, head) that the backward recomputes, so nothing nnz-sized is added.  seed=None
+        draws 63 bits from torch's default generator (torch.manual_seed reproduces a run); the seed is kept for the backward.
+        dropout=0.0 or training=False takes the path above exactly as without the arguments."""
+        if not 0.0 <= dropout < 1.0:  # a NaN fails this too
+            raise ValueError(f"dropout must be a probability in [0, 1), not {dropout}")
         if not (self.fused_attention and self.fused_backward):
             raise NotImplementedError("gatv2_attention needs SparseOperator(..., learn_values=True, fused_attention=True, fused_backward=True): "
                                       "only the fused forward and backward compute the score from the full rows")
         import torch
         if not (xt.dtype == xs.dtype == att.dtype == torch.float32):
             raise TypeError(f"gatv2_attention takes float32 xt, xs and att, not {xt.dtype}, {xs.dtype} and {att.dtype}")
+        if dropout > 0 and training:
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+            return gatv2_dropout_functions()[0].apply(xt, xs, att, self, float(negative_slope), float(dropout), int(seed) & 0xFFFFFFFFFFFFFFFF)
         return gatv2_functions()[0].apply(xt, xs, att, self, float(negative_slope))

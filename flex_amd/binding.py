@@ -173,6 +173,7 @@ SYMBOLS = [
     "flex_dropout_mask", "flex_gat_attention_dropout", "flex_gat_attention_dropout_backward",
     "flex_gat_attention_bf16", "flex_gat_attention_bf16_backward", "flex_gat_attention_bf16_dropout", "flex_gat_attention_bf16_dropout_backward",
     "flex_gatv2_attention", "flex_gatv2_attention_backward", "flex_gatv2_attention_work_size",
+    "flex_dropout_gatv2_attention", "flex_dropout_gatv2_attention_backward",
 ]
 
 _lib = None
@@ -263,7 +264,7 @@ def lib():
 
 def _values_fn(name: str):
     """flex_plan_set_values / flex_sddmm / flex_edge_softmax / flex_edge_softmax_backward, the 22 fused-attention calls (flex_attention*,
-    flex_gat_attention*), the three GATv2 calls (flex_gatv2_attention*) and flex_spmm_bf16, looked up at first use and not when the library loads: a host-only build without the kernel
+    flex_gat_attention*), the three GATv2 calls (flex_gatv2_attention*), their two dropout forms (flex_dropout_gatv2_attention*) and flex_spmm_bf16, looked up at first use and not when the library loads: a host-only build without the kernel
     files does not have to define them.  tests/hostsim defines them all: the attention calls are the library's own entry points
     (csrc/attention_entry.h) on stand-in launchers that only log which kernel the real ones would launch, the others are stand-ins that
     log the same way."""
@@ -297,7 +298,9 @@ def _values_fn(name: str):
                       "flex_gat_attention_bf16_dropout_backward": [vp, i32, vp, vp, vp, vp, vp, fl, fl, u64, vp, vp, vp, vp, vp],
                       "flex_gatv2_attention": [vp, i32, vp, vp, vp, fl, vp, vp, vp],
                       "flex_gatv2_attention_backward": [vp, i32, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp, vp],
-                      "flex_gatv2_attention_work_size": [vp, C.POINTER(u64)]}[name]
+                      "flex_gatv2_attention_work_size": [vp, C.POINTER(u64)],
+                      "flex_dropout_gatv2_attention": [vp, i32, vp, vp, vp, fl, fl, u64, vp, vp, vp],
+                      "flex_dropout_gatv2_attention_backward": [vp, i32, vp, vp, vp, vp, vp, fl, fl, u64, vp, vp, vp, vp, vp, vp]}[name]
     return f
 
 
@@ -1151,6 +1154,67 @@ class Plan:
         self.gatv2_attention_backward_ptr(heads, xt.data_ptr(), xs.data_ptr(), att.data_ptr(), p.data_ptr(), grad_out.data_ptr(), slope,
                                           *(None if t is None else t.data_ptr() for t in outs), work.data_ptr(),
                                           None if outs[2] is None else att_work.data_ptr(), torch.cuda.current_stream(xs.device).cuda_stream)
+        return tuple(outs)
+
+    def gatv2_attention_dropout_ptr(self, heads: int, dXt_ptr: int, dXs_ptr: int, dAtt_ptr: int, slope: float, p: float, seed: int, dOut_ptr: int,
+                                    dP_ptr: int | None = None, stream: int = 0):
+        """flex_dropout_gatv2_attention; the operands are gatv2_attention_ptr's; dP (optional) receives the UNDROPPED alpha."""
+        _check(_values_fn("flex_dropout_gatv2_attention")(self._h, heads, dXt_ptr, dXs_ptr, dAtt_ptr, slope, p, seed, dOut_ptr, dP_ptr, stream),
+               "flex_dropout_gatv2_attention")
+
+    def gatv2_attention_dropout(self, xt, xs, att, slope: float, p: float, seed: int, out=None, probs=None):
+        """flex_dropout_gatv2_attention: gatv2_attention() whose probabilities are dropped after the softmax with probability p in [0, 1),
+        the kept ones scaled by 1 / (1 - p); the mask is binding.dropout_mask(seed, p, e * H + h), a function of the 64-bit seed.  A
+        dropped entry stays in the softmax.  probs (optional, float32 [a.nnz, H]) receives the UNDROPPED alpha, which
+        gatv2_attention_dropout_backward() starts from."""
+        import torch
+        i = self.info()
+        heads = self._gatv2_operands(xt, xs, att)
+        if out is None:  # every row is written, except by a plan without entries, which launches nothing
+            out = (torch.empty if i["nnz"] else torch.zeros)((i["m"], i["k"]), dtype=torch.float32, device=xs.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (i["m"], i["k"])
+        if probs is not None:
+            self._head_edge_arrays(heads, probs)
+        self.gatv2_attention_dropout_ptr(heads, xt.data_ptr(), xs.data_ptr(), att.data_ptr(), slope, p, int(seed) & 0xFFFFFFFFFFFFFFFF, out.data_ptr(),
+                                         None if probs is None else probs.data_ptr(), torch.cuda.current_stream(xs.device).cuda_stream)
+        return out
+
+    def gatv2_attention_dropout_backward_ptr(self, heads: int, dXt_ptr: int, dXs_ptr: int, dAtt_ptr: int, dP_ptr: int, dGradOut_ptr: int,
+                                             slope: float, p: float, seed: int, dGradXt_ptr: int | None, dGradXs_ptr: int | None,
+                                             dGradAtt_ptr: int | None, dWork_ptr: int, dAttWork_ptr: int | None = None, stream: int = 0):
+        """flex_dropout_gatv2_attention_backward; the operands are gatv2_attention_backward_ptr's, under the forward's p and seed."""
+        _check(_values_fn("flex_dropout_gatv2_attention_backward")(self._h, heads, dXt_ptr, dXs_ptr, dAtt_ptr, dP_ptr, dGradOut_ptr, slope, p, seed,
+                                                                   dGradXt_ptr, dGradXs_ptr, dGradAtt_ptr, dWork_ptr, dAttWork_ptr, stream),
+               "flex_dropout_gatv2_attention_backward")
+
+    def gatv2_attention_dropout_backward(self, xt, xs, att, probs, grad_out, slope: float, p: float, seed: int, grad_xt=None, grad_xs=None,
+                                         grad_att=None, work=None, want=(True, True, True), att_work=None):
+        """flex_dropout_gatv2_attention_backward: (gXt [m, k], gXs [n, k], gAtt [H, k / H]) of gatv2_attention_dropout()'s out from its
+        probs [a.nnz, H] (the undropped alpha), grad_out [m, k] and the same p and seed, in up to three launches; an output that `want`
+        does not ask for is None and is not computed.  work and att_work are gatv2_attention_backward()'s."""
+        import torch
+        i = self.info()
+        heads = self._gatv2_operands(xt, xs, att)
+        assert grad_out.is_cuda and grad_out.dtype == torch.float32 and grad_out.is_contiguous() and tuple(grad_out.shape) == (i["m"], i["k"])
+        if work is None:
+            work = torch.empty((self.src_nnz, heads), dtype=torch.float32, device=xs.device)
+        self._head_edge_arrays(heads, probs, work)
+        outs = []
+        for wanted, t, shape in zip(want, (grad_xt, grad_xs, grad_att), ((i["m"], i["k"]), (i["n"], i["k"]), tuple(att.shape))):
+            if wanted and t is None:  # every element is written, except by a plan without entries, which launches nothing
+                t = (torch.empty if i["nnz"] else torch.zeros)(shape, dtype=torch.float32, device=xs.device)
+            if wanted:
+                assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape
+            outs.append(t if wanted else None)
+        if outs[2] is not None:
+            need = self.gatv2_attention_work_size()
+            if att_work is None:
+                att_work = torch.empty(max(need, 1), dtype=torch.float32, device=xs.device)
+            assert att_work.is_cuda and att_work.dtype == torch.float32 and att_work.is_contiguous() and att_work.numel() >= need
+        self.gatv2_attention_dropout_backward_ptr(heads, xt.data_ptr(), xs.data_ptr(), att.data_ptr(), probs.data_ptr(), grad_out.data_ptr(), slope, p,
+                                                  int(seed) & 0xFFFFFFFFFFFFFFFF, *(None if t is None else t.data_ptr() for t in outs),
+                                                  work.data_ptr(), None if outs[2] is None else att_work.data_ptr(),
+                                                  torch.cuda.current_stream(xs.device).cuda_stream)
         return tuple(outs)
 
     def gat_attention_dropout_ptr(self, heads: int, dEl_ptr: int, dEr_ptr: int, dV_ptr: int, slope: float, p: float, seed: int, dOut_ptr: int,

@@ -12,6 +12,10 @@
 //                  keeps across all the rows of its workgroup
 //   column backward a slot holds Xs[c] and att; per entry it reads p and dz and gathers g[row] and Xt[row]; both terms of gXs go into
 //                  one accumulator row, the score term first
+// DROP (attention_gatv2_dropout_kernels.hip turns it on; off, the sweeps are what they were): the dropout of the probabilities after
+// the softmax, w = kept(dm, e H + h) ? dm.c : 0 (internal.h: DropMask; `kept` is attention_heads_device.h's).  A dropped entry is
+// gathered all the same and stays in the softmax; it is selected out of the value term of Out, of da in sweep 1 of the row backward
+// and of the p g term of gXs, and nowhere else: the score term of gXs, gXt and gAtt hold the mask through dz.
 // att f is a select between att and fl(att slope), so a term costs one fma.  Edge arrays are entry-major, (entry e, head h) at e H + h.
 // Lanes past k hold zeros and touch no edge array.  Fixed order everywhere, no atomics.  Only the 16-byte form is built.
 #pragma once
@@ -39,16 +43,18 @@ __device__ __forceinline__ float4 att_f(const float4 &a, const float4 &t, const 
 // ---- forward
 
 // attention_heads_device.h, sweep_heads, with the score of GATv2 and one gather per entry
-template <int W, int NS>
+template <int W, int NS, bool DROP = false>
 __device__ __forceinline__ void sweep(const attention::View &v, const attention::HeadSplit &hs, const attention::HeadLane &hl, const float4 (&xt)[NS],
                                       const float4 (&att)[NS], const float *__restrict__ Xs, float slope, float *__restrict__ P,
-                                      const attention::Place &pl, uint32_t lane, uint32_t li, attention::State<1> (&st)[NS]) {
+                                      const attention::Place &pl, uint32_t lane, uint32_t li, attention::State<1> (&st)[NS],
+                                      const DropMask &dm = DropMask{}) {
     using namespace attention;
     const int slot_lane0 = static_cast<int>(lane - li);
     for (uint32_t pass = 0; pass < pl.n_pass; ++pass) {
         const uint64_t j0 = (static_cast<uint64_t>(pass) * pl.T + pl.t) * U;
         const bool mine = li < static_cast<uint32_t>(U) && j0 + li < pl.len;
         const uint32_t idx = mine ? v.src[pl.first - v.e0 + j0 + li] : 0u;
+        const uint64_t i0 = DROP ? (pl.first + j0) * static_cast<uint64_t>(hs.H) : 0;  // the pass's first element of the edge arrays
         bool valid[U];
         float4 xs[U][NS];
 #pragma unroll
@@ -59,6 +65,16 @@ __device__ __forceinline__ void sweep(const attention::View &v, const attention:
 #pragma unroll
             for (int s = 0; s < NS; ++s)
                 xs[u][s] = valid[u] ? load_cols<true>(xr, 4 * static_cast<int>(li) + 4 * W * s, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        // DROP: bit s U + u is the keep bit of (entry u, the head of slab s): one register for the pass.  The loop is kept rolled, after
+        // the gathers are issued: unrolled, the scheduler interleaves the hashes with the scores and the kernel grows by 22 registers
+        uint32_t keep = 0;
+        if constexpr (DROP) {
+#pragma nounroll
+            for (int t = 0; t < NS * U; ++t) {
+                const uint32_t head = (li + static_cast<uint32_t>(W * (t / U))) >> hs.lg;
+                keep |= (kept(dm, i0 + static_cast<uint32_t>((t % U) * hs.H) + head) ? 1u : 0u) << t;
+            }
         }
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
@@ -92,7 +108,11 @@ __device__ __forceinline__ void sweep(const attention::View &v, const attention:
                     if (valid[u]) {
                         const float tm = term(sc[u], x.m, 1.f);
                         x.l += tm;
-                        axpy(x.acc[0], tm, xs[u][s]);
+                        if constexpr (DROP) {  // a dropped entry stays in the sum and leaves the value term: selected out, not 0 x xs
+                            if ((keep >> (s * U + u)) & 1u) axpy(x.acc[0], tm * dm.c, xs[u][s]);
+                        } else {
+                            axpy(x.acc[0], tm, xs[u][s]);
+                        }
                     }
                 }
             }
@@ -101,10 +121,11 @@ __device__ __forceinline__ void sweep(const attention::View &v, const attention:
 }
 
 // attention_heads_device.h, run_item_heads: the merges, the Out row and the second sweep of dP are the same code
-template <int W, int NS>
+template <int W, int NS, bool DROP = false>
 __device__ __forceinline__ void run_item(const attention::View &v, const attention::HeadSplit &hs, const uint4 &it, int kind, const float *__restrict__ Xt,
                                          const float *__restrict__ Xs, const float *__restrict__ Att, float slope, float *__restrict__ Out,
-                                         float *__restrict__ P, uint32_t lane, uint32_t w, attention::HeadsShared<W, NS> &sh) {
+                                         float *__restrict__ P, uint32_t lane, uint32_t w, attention::HeadsShared<W, NS> &sh,
+                                         const DropMask &dm = DropMask{}) {
     using namespace attention;
     const uint32_t slot = lane / W, li = lane % W;
     const HeadLane hl(hs, li);
@@ -121,7 +142,7 @@ __device__ __forceinline__ void run_item(const attention::View &v, const attenti
         st[s].l = 0.f;
         st[s].acc[0] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    sweep<W, NS>(v, hs, hl, xt, att, Xs, slope, P, pl, lane, li, st);
+    sweep<W, NS, DROP>(v, hs, hl, xt, att, Xs, slope, P, pl, lane, li, st, dm);
     if (kind != kSlotLine) merge_slots_heads<W, NS>(st, lane, 1.f);
     bool writer = kind == kSlotLine ? pl.has_line : slot == 0;
     if (kind == kBlockLine) {
@@ -178,11 +199,12 @@ __device__ __forceinline__ void run_item(const attention::View &v, const attenti
 // ---- row backward
 
 // attention_heads_device.h, run_row_heads.  ga: the lane's gAtt partial, which outlives the row (it is not read where GAtt is false)
-template <int W, int NS>
+template <int W, int NS, bool DROP = false>
 __device__ __forceinline__ void run_row(const attention::View &v, const attention::HeadSplit &hs, const uint4 &it, int kind, const float *__restrict__ Xt,
                                         const float *__restrict__ Xs, const float *__restrict__ Att, const float *__restrict__ P,
                                         const float *__restrict__ G, float slope, float *__restrict__ GXt, bool GAtt, float *__restrict__ Work,
-                                        float4 (&ga)[NS], uint32_t lane, uint32_t w, attention::HeadsRowShared<W, NS> &sh) {
+                                        float4 (&ga)[NS], uint32_t lane, uint32_t w, attention::HeadsRowShared<W, NS> &sh,
+                                        const DropMask &dm = DropMask{}) {
     using namespace attention;
     const uint32_t slot = lane / W, li = lane % W;
     const int slot_lane0 = static_cast<int>(lane - li);
@@ -213,15 +235,25 @@ __device__ __forceinline__ void run_row(const attention::View &v, const attentio
                 for (int s = 0; s < NS; ++s)
                     xs[u][s] = valid[u] ? load_cols<true>(xr, 4 * static_cast<int>(li) + 4 * W * s, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
+            uint32_t keep = 0;  // DROP: bit s U + u, in a rolled loop after the gathers are issued, as in the forward's sweep
+            if constexpr (DROP) {
+                const uint64_t i0 = (pl.first + j0) * static_cast<uint64_t>(hs.H);
+#pragma nounroll
+                for (int t = 0; t < NS * U; ++t) {
+                    const uint32_t head = (li + static_cast<uint32_t>(W * (t / U))) >> hs.lg;
+                    keep |= (kept(dm, i0 + static_cast<uint32_t>((t % U) * hs.H) + head) ? 1u : 0u) << t;
+                }
+            }
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
                 const int c = 4 * static_cast<int>(li) + 4 * W * s;
                 const uint32_t head = (li + static_cast<uint32_t>(W * s)) >> hs.lg;
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
-                    const float da = head_total<W>(dot_cols<true>(0.f, g[s], xs[u][s], c, v.k), hl.hw);
+                    float da = head_total<W>(dot_cols<true>(0.f, g[s], xs[u][s], c, v.k), hl.hw);
                     if (valid[u] && c < v.k) {
                         const uint64_t e = (pl.first + j0 + u) * static_cast<uint64_t>(hs.H) + head;
+                        if constexpr (DROP) da = ((keep >> (s * U + u)) & 1u) ? dm.c * da : 0.f;  // dropped: +0 whatever the dot product is
                         if (hl.writes(u)) Work[e] = da;
                         delta[s] = __builtin_fmaf(P[e], da, delta[s]);
                     }
@@ -353,11 +385,12 @@ struct ColumnShared {
 };
 
 // attention_heads_device.h, run_column_heads, with one accumulator row: gXs[c] = sum over the column's entries of dz (att f) + p g[row]
-template <int W, int NS>
+template <int W, int NS, bool DROP = false>
 __device__ __forceinline__ void run_column(const attention::ColumnView &v, const attention::HeadSplit &hs, const uint4 &it, int kind,
                                            const float *__restrict__ Xt, const float *__restrict__ Xs, const float *__restrict__ Att,
                                            const float *__restrict__ G, const float *__restrict__ P, const float *__restrict__ DZ, float slope,
-                                           float *__restrict__ GXs, uint32_t lane, uint32_t w, ColumnShared<W, NS> &sh) {
+                                           float *__restrict__ GXs, uint32_t lane, uint32_t w, ColumnShared<W, NS> &sh,
+                                           const DropMask &dm = DropMask{}) {
     using namespace attention;
     const uint32_t slot = lane / W, li = lane % W;
     const int slot_lane0 = static_cast<int>(lane - li);
@@ -392,9 +425,16 @@ __device__ __forceinline__ void run_column(const attention::ColumnView &v, const
                 const int c = 4 * static_cast<int>(li) + 4 * W * s;
                 const bool live = valid[u] && c < v.k;
                 const uint64_t eh = static_cast<uint64_t>(e) * static_cast<uint64_t>(hs.H) + ((li + static_cast<uint32_t>(W * s)) >> hs.lg);
-                pe[u][s] = live ? P[eh] : 0.f;
-                de[u][s] = live ? DZ[eh] : 0.f;
-                gg[u][s] = valid[u] ? load_cols<true>(gr, c, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
+                if constexpr (DROP) {  // the mask folds into p; a dropped entry's g row is not gathered and its p g term adds 0 x 0
+                    const bool keep = live && kept(dm, eh);
+                    pe[u][s] = keep ? P[eh] * dm.c : 0.f;
+                    de[u][s] = live ? DZ[eh] : 0.f;
+                    gg[u][s] = keep ? load_cols<true>(gr, c, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
+                } else {
+                    pe[u][s] = live ? P[eh] : 0.f;
+                    de[u][s] = live ? DZ[eh] : 0.f;
+                    gg[u][s] = valid[u] ? load_cols<true>(gr, c, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
+                }
                 if constexpr (!kLateXt) tt[u][s] = valid[u] ? load_cols<true>(tr, c, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
             trow[u] = tr;

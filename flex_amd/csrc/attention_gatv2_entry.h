@@ -3,43 +3,14 @@
 // happens for which outputs.  Host code only, and ordinary (non-inline) definitions, as attention_entry.h: this file is included by
 // exactly ONE translation unit per build -- attention_gatv2_kernels.hip in the GPU library, tests/hostsim_gatv2/launchers.cpp in the
 // host-simulator build of tests/test_gatv2_entry_host.py -- so both builds run the same entry points on launchers of their own
-// (flex::gatv2::launch_*, declared here: the view, the grid and the kernel in the library, a stand-in that logs the instantiation's
+// (flex::gatv2::launch_*, declared in attention_gatv2_common.h: the view, the grid and the kernel in the library, a stand-in that logs the instantiation's
 // name in the simulator).
 //
 // The order of refusals is the GAT calls' (attention_entry.h): plan, flag, heads and slope; head split; empty plan (OK); NULL operands
 // and dWork == dP; alignment; no output wanted (OK).  The backward launches the rows whenever a gradient is wanted (each needs dz), the
 // columns for gXs alone and the reduction for gAtt alone.
 #pragma once
-#include <cmath>
-#include <cstdint>
-
-#include "internal.h"
-#include "plan.h"
-
-namespace flex {
-namespace gatv2 {
-
-int launch_rows(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const float *Xt, const float *Xs, const float *Att, float slope,
-                float *Out, float *P, hipStream_t s);
-// AttWork NULL: no gAtt partials; GXt NULL: no gXt; dz is written over da in Work either way
-int launch_rows_backward(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const float *Xt, const float *Xs, const float *Att,
-                         const float *P, const float *G, float slope, float *GXt, float *Work, float *AttWork, hipStream_t s);
-int launch_columns_backward(const flex_plan *p, const AttentionPick &pick, int heads, int lg, const float *Xt, const float *Xs, const float *Att,
-                            const float *G, const float *P, const float *DZ, float slope, float *GXs, hipStream_t s);
-int launch_att_reduce(const flex_plan *p, const float *AttWork, float *GAtt, hipStream_t s);
-
-static bool slope_ok(float slope) { return std::isfinite(slope) && slope > 0.f && slope <= 1.f; }
-
-// The k-rows of dAttWork: one per workgroup of the row launch, which is attention_host.h's launch_grid of the row walk -- one
-// workgroup per block row, then one per kWavesPerBlock groups, under the remap a multiple of kXcds of the latter.
-static uint32_t att_work_rows(const flex_plan *p) {
-    uint32_t wgs = (p->n_at_groups + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (p->xcd_remap) wgs = (wgs + kXcds - 1) / kXcds * kXcds;
-    return p->n_at_block_rows + wgs;
-}
-
-}  // namespace gatv2
-}  // namespace flex
+#include "attention_gatv2_common.h"
 
 extern "C" {
 

@@ -36,6 +36,7 @@ extern "C" {
                               the equally additive flex_gat_attention_dropout and flex_gat_attention_dropout_backward (two new calls, no flag, no struct),
                               the equally additive flex_gat_attention_bf16, flex_gat_attention_bf16_dropout and their backward calls (four new calls, no flag, no struct),
                               the equally additive flex_gatv2_attention, flex_gatv2_attention_backward and flex_gatv2_attention_work_size (three new calls, no flag, no struct),
+                              the equally additive flex_dropout_gatv2_attention and flex_dropout_gatv2_attention_backward (two new calls, no flag, no struct),
                               and the retired flex_plan_tuning.block_ablate, which keeps its place as block_ablate_retired and must be zero.
                               3: plan-time knobs leave the environment for the struct flex_plan_tuning, flex_plan_desc.tuning, flex_plan_get_tuning,
                               flex_order_cluster_ex, flex_set_host_threads; split rows are summed by a second launch by default.
@@ -899,6 +900,44 @@ int flex_gatv2_attention_backward(const flex_plan *plan, int heads, const float 
                                   const float *dGradOut, float slope, float *dGradXt, float *dGradXs, float *dGradAtt, float *dWork,
                                   float *dAttWork, flex_stream_t stream);
 int flex_gatv2_attention_work_size(const flex_plan *plan, uint64_t *floats); /* the size of dAttWork */
+
+/* The fused GATv2 attention with dropout of the probabilities after the softmax (the `dropout` of PyG's and DGL's GATv2Conv), in the
+ * launches of flex_gatv2_attention and flex_gatv2_attention_backward, on the same plans, walk and grid.  The mask, its threshold and its
+ * index are flex_attention_dropout's, bit for bit (flex_dropout_mask is its host reference): with c = 1.0f / (1.0f - drop_p) computed in
+ * fp32 on the host, w_eh = keep(seed, e H + h) ? c : 0, where e is the entry's index in the CSR the plan was made from (a row-range
+ * shard uses the global index).  x, s, alpha, f and L are flex_gatv2_attention's, unchanged:
+ *     Out[r, head h] = sum_e alpha_eh w_eh Xs[c, head h]
+ *     da_eh    = w_eh <g[r, head h], Xs[c, head h]>     delta_rh = sum_e p_eh da_eh     dz_eh = p_eh (da_eh - delta_rh)
+ *     gXt[r, hd + j] = sum_{e in r}       dz_eh att[hd + j] f_ej
+ *     gAtt[hd + j]   = sum_{all e}        dz_eh L_ej
+ *     gXs[c, hd + j] = sum_{src(e) = c}  (dz_eh att[hd + j] f_ej  +  p_eh w_eh g[row(e), hd + j])
+ * In GATv2 the gathered row Xs[c] is score operand and value, so a dropped entry is still gathered and still takes part in the softmax.
+ * The mask enters in three places only: the value term of Out, da, and the p g term of gXs; not the score term of gXs, nor gXt, nor
+ * gAtt, which carry it through dz.
+ * - P.  The score, maximum, sum, poison rules and dP are flex_gatv2_attention's bit for bit: dP holds the UNDROPPED alpha.
+ * - Selection.  A dropped entry is selected out, not multiplied by zero: its value term in Out, its da (exactly +0, the dot product is
+ *   not used) and its p g term in gXs.  So a head of a row whose entries are all dropped is +0 bits in Out, and g[r, head h] of such a
+ *   head reaches no output, inf and NaN included.  A dropped entry with s = -inf and a -inf in its Xs row adds nothing to Out; a kept
+ *   one adds 0 x -inf = NaN, as the undropped call does.  A poisoned head stays NaN.  A head of a row of gXs without a kept entry is
+ *   NOT +0: the score term remains (unlike flex_gat_attention_dropout's gV).
+ * - drop_p must be finite and in [0, 1), else FLEX_ERR_INVALID, checked beside the slope.  drop_p == 0 launches the kernels of the
+ *   undropped calls after the refusals: every output has their bits.
+ * - Every other refusal, the operands, dWork, dAttWork (sized by flex_gatv2_attention_work_size), the launches per wanted gradient, the
+ *   scope and the stream rules are flex_gatv2_attention's and flex_gatv2_attention_backward's.  The forward runs on row-range shards;
+ *   the backward is FLEX_ERR_INVALID there.  The same (drop_p, seed) must be passed to the forward and to the backward.
+ *
+ * Accuracy, in the terms of flex_gatv2_attention, against float64 on the same fp32 operands under the same mask.  A kept probability is
+ * multiplied by c before it enters a sum, one more rounding wherever that product stands:
+ *   Out     |Out - Out64| <= sum_{kept e} (gamma(n_r + 4) alpha_e + dalpha_e) c |Xs| + 2^-126
+ *   dda_e    = c (gamma(d + 1) sum_j |g Xs| + d 2^-149) + 2^-149 on a kept entry, 0 on a dropped one
+ *   ddz, gXt, gAtt: flex_gatv2_attention's lines on this da and dda
+ *   |gXs - gXs64|   <= sum_{e in c} [(gamma(2 n_c + 1) |dz_e| + ddz_e) |w_ej| + |dz_e| 2^-149]
+ *                      + sum_{kept e in c} gamma(2 n_c + 1) p_e c |g[row]| + 2^-126 */
+int flex_dropout_gatv2_attention(const flex_plan *plan, int heads, const float *dXt, const float *dXs, const float *dAtt, float slope,
+                                 float drop_p, uint64_t seed, float *dOut, float *dP /* optional */, flex_stream_t stream);
+int flex_dropout_gatv2_attention_backward(const flex_plan *plan, int heads, const float *dXt, const float *dXs, const float *dAtt,
+                                          const float *dP, const float *dGradOut, float slope, float drop_p, uint64_t seed, float *dGradXt,
+                                          float *dGradXs, float *dGradAtt, float *dWork, float *dAttWork, flex_stream_t stream);
 
 /* ≙ alpha_freeMatGPU (mat.cuh:184-193). */
 int flex_plan_destroy(flex_plan *plan);

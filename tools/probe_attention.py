@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Sparse graph attention, measured: the error of the exponential the edge softmax may use, and the time of flex_edge_softmax,
 flex_edge_softmax_backward and a whole attention step.  Writes profiles/attention_probe.txt (or the file given with --out): the whole run
-starts the file, a run of one part (--fused, --backward, --heads, --gat, --bf16, --bias, --dropout, --gat-dropout, --gat-bf16, --gatv2)
+starts the file, a run of one part (--fused, --backward, --heads, --gat, --bf16, --bias, --dropout, --gat-dropout, --gat-bf16, --gatv2,
+--gatv2-dropout)
 appends to it.
 
 1. tools/exp_error.hip (built here with hipcc into flex_amd/lib if it is not there): the largest error in ulp of expf, __expf and
@@ -55,7 +56,11 @@ appends to it.
    what a user had before -- the [nnz, k] tensor Xt[row] + Xs[col] and the scores in torch, then per head edge_softmax and the SpMM
    with values=alpha of an operator of width d on a column slice, torch autograd carrying the gradients.  --gatv2: only this part
    (and the copy rate).
-Usage: probe_attention.py [--out FILE] [--fused | --backward | --heads | --gat | --bf16 | --bias | --dropout | --gat-dropout | --gat-bf16 | --gatv2] [graph ...]   (default: pubmed.csv flickr reddit soc-sign-epinions)"""
+14. Attention dropout in GATv2 (flex_dropout_gatv2_attention and its backward call), (k, H) = (64, 8), (128, 4), (256, 8), p = 0.1 and
+   0.6, same graphs and protocol: the forward (with dP) and the backward (all three gradients) against the undropped
+   flex_gatv2_attention and flex_gatv2_attention_backward on the same plan in the same process -- what the mask costs where every Xs
+   row is gathered all the same.  --gatv2-dropout: only this part (and the copy rate).
+Usage: probe_attention.py [--out FILE] [--fused | --backward | --heads | --gat | --bf16 | --bias | --dropout | --gat-dropout | --gat-bf16 | --gatv2 | --gatv2-dropout] [graph ...]   (default: pubmed.csv flickr reddit soc-sign-epinions)"""
 import ctypes as C
 import os
 import subprocess
@@ -619,14 +624,43 @@ def probe_gatv2(name, a):
         del fused, one, kept
 
 
+def probe_gatv2_dropout(name, a):
+    gen = torch.Generator(device="cuda").manual_seed(14)
+    seed, slope = 0x0123456789ABCDEF, 0.2
+    for k, H in ((64, 8), (128, 4), (256, 8)):
+        d = k // H
+        plan = flex_amd.Plan(a, k, attention=True, attention_backward=True)  # one plan serves every contender
+        xt, xs = (torch.rand((r, k), device="cuda", generator=gen) * 4 - 2 for r in (a.m, a.n))
+        att = torch.rand((H, d), device="cuda", generator=gen) * 2 - 1
+        g = torch.rand((a.m, k), device="cuda", generator=gen) * 2 - 1
+        out, gxt, gxs, gatt = torch.empty((a.m, k), device="cuda"), torch.empty((a.m, k), device="cuda"), torch.empty((a.n, k), device="cuda"), torch.empty((H, d), device="cuda")
+        P, W = (torch.empty((a.nnz, H), device="cuda") for _ in range(2))
+        AW = torch.empty(max(1, plan.gatv2_attention_work_size()), device="cuda")
+        fns = {"forward": lambda: plan.gatv2_attention(xt, xs, att, slope, out=out, p=P),
+               "backward": lambda: plan.gatv2_attention_backward(xt, xs, att, P, g, slope, grad_xt=gxt, grad_xs=gxs, grad_att=gatt, work=W, att_work=AW)}
+        for p_ in (0.1, 0.6):
+            fns[f"forward p={p_}"] = lambda p_=p_: plan.gatv2_attention_dropout(xt, xs, att, slope, p_, seed, out=out, probs=P)
+            fns[f"backward p={p_}"] = lambda p_=p_: plan.gatv2_attention_dropout_backward(xt, xs, att, P, g, slope, p_, seed, grad_xt=gxt, grad_xs=gxs,
+                                                                                         grad_att=gatt, work=W, att_work=AW)
+        plan.gatv2_attention(xt, xs, att, slope, out=out, p=P)  # P holds probabilities for every backward
+        n = max(3, min(100, int(1e8 / max(1, a.nnz * k))))
+        best, spread = _alternate(fns, n)
+        say(f"{name} k={k} H={H} d={d} gatv2 dropout: " + "  ".join(f"{key} {best[key]:.1f} us (+{spread[key]:.0f} % over 3 rounds)" for key in fns)
+            + "  dropout / no dropout: " + "  ".join(f"{w} p={p_} {best[f'{w} p={p_}'] / best[w]:.2f}x" for w in ("forward", "backward") for p_ in (0.1, 0.6))
+            + "  extra memory: none (the mask is recomputed from the seed)")
+        del plan
+
+
 def main():
     args = sys.argv[1:]
     out = os.path.join(ROOT, "profiles", "attention_probe.txt")
     if args[:1] == ["--out"]:
         out, args = args[1], args[2:]
-    fused_only, backward_only, heads_only, gat_only, bf16_only, bias_only, dropout_only, gat_dropout_only, gat_bf16_only, gatv2_only = (
-        args[:1] == [flag] for flag in ("--fused", "--backward", "--heads", "--gat", "--bf16", "--bias", "--dropout", "--gat-dropout", "--gat-bf16", "--gatv2"))
-    only = fused_only or backward_only or heads_only or gat_only or bf16_only or bias_only or dropout_only or gat_dropout_only or gat_bf16_only or gatv2_only
+    fused_only, backward_only, heads_only, gat_only, bf16_only, bias_only, dropout_only, gat_dropout_only, gat_bf16_only, gatv2_only, gatv2_dropout_only = (
+        args[:1] == [flag] for flag in ("--fused", "--backward", "--heads", "--gat", "--bf16", "--bias", "--dropout", "--gat-dropout", "--gat-bf16", "--gatv2",
+                                        "--gatv2-dropout"))
+    only = (fused_only or backward_only or heads_only or gat_only or bf16_only or bias_only or dropout_only or gat_dropout_only or gat_bf16_only or gatv2_only
+            or gatv2_dropout_only)
     if only:
         args = args[1:]
     else:
@@ -660,6 +694,8 @@ def main():
                 probe_gatv2(name, a)
             except torch.cuda.OutOfMemoryError:  # the loop's [nnz, k] tensors and their autograd copies
                 say(f"{name} gatv2: the torch composition ran out of device memory")
+        if gatv2_dropout_only or not only:
+            probe_gatv2_dropout(name, a)
     with open(out, "a" if only else "w") as f:  # a part is appended, the whole run starts the file
         f.write("\n".join(LINES) + "\n")
 
