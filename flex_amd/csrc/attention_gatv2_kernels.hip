@@ -1,7 +1,8 @@
 // attention_gatv2_kernels.hip -- the fused GATv2 attention (include/flex_spmm.h: flex_gatv2_attention, flex_gatv2_attention_backward,
 // flex_gatv2_attention_work_size): the score s = a_h . LeakyReLU(Xt[r] + Xs[src]) per head, in ONE forward launch and up to THREE
 // backward launches (rows: dz, gXt and the gAtt partials; columns: gXs; a small reduction: gAtt) on the plans of the multi-head fused
-// attention.  tests/test_gpu_gatv2_attention.py covers it, and holds every kernel handle of namespace gatv2 to a case that launches it.
+// attention.  tests/test_gpu_gatv2_attention.py covers it, and holds every kernel handle of namespace gatv2 to a case that launches it;
+// tests/test_gpu_gatv2_walks.py runs it above the floor group budget, without the XCD remap, and holds gAtt by the rows of dAttWork.
 //
 // The walk is attention_heads_kernels.hip's (attention_device.h): the same view, items, groups, slot / wave / block ownership by
 // place_of, W = sddmm_lanes(k) lanes per slot, four entries per pass, four columns per lane and slab, the XCD remap.  A head is

@@ -30,7 +30,19 @@ att a chain of four fmas per lane and a tree over the d / 4 lanes, d roundings a
 w = att f (one rounding) into gXt (one fma per entry, depth <= n_r) and gXs (two fmas per entry, depth <= 2 n_c), and through L into
 gAtt, whose T is the depth of the tree the kernels use: a lane's chain over its wave's group (at most the group budget of 2048
 entries, or a quarter of a block row), the slots (4), the waves (3), the chain of every fourth partial row (one row per workgroup, at
-most ceil(m / 4) + 2 to a chain) and the four chains (3); never more than nnz, additions of zeros being exact."""
+most ceil(m / 4) + 2 to a chain) and the four chains (3); never more than nnz, additions of zeros being exact.
+
+The whole-graph line of gAtt is an A PRIORI bound, not the check of gAtt: gamma(T + 3) sum |dz| |L| over every entry of the graph exceeds
+|gAtt| itself on large graphs (up to 7 |gAtt| on 7 copies of walk_graph(1) and 31 |gAtt| on 30, DESIGN.md section 3.23: gAtt = 0 would
+pass), and a kernel that loses whole items of its groups stays within it in most columns.  check_backward keeps it, for small graphs and for the comparison with the composition of engine calls.  The
+check of gAtt is check_att, in the two stages of the kernels:
+    partial rows   row w of dAttWork is the sum of dz_e leaky(x_ej) over the entries of ONE workgroup of the row launch
+                   (att_work_layout restates which), held to float64 under
+                       sum_{e in w} [(gamma(n_w + 3) |dz_e| + ddz_e) |L_ej| + |dz_e| 2^-149] + 2^-126,    n_w = the entries of w
+                   (any order of n fma terms is within gamma(n), so no model of the tree's depth enters; + 3 as in the line above); a row
+                   without entries is +0 bit for bit
+    the reduction  gAtt has the BITS of att_reduce32 of the rows the kernel wrote: four chains of every fourth row from 0.f, then
+                   ((c0 + c1) + c2) + c3, plain fp32 additions in a fixed order"""
 import numpy as np
 
 from fused_attention_backward_ref import both_sides  # noqa: F401  (the tests take the lifted graph from here)
@@ -266,6 +278,141 @@ def check_backward(a, xt, xs, att, p, g, slope, gXt=None, gXs=None, gAtt=None, d
     return worst
 
 
+# ---- gAtt in the two stages of the kernels: the partial row of every workgroup of the row launch, then gatt_reduce
+
+KXCDS, WAVES = 8, 4  # internal.h: kXcds, kWavesPerBlock
+
+
+def att_work_layout(rowptr, k, budget, remap):
+    """(row [nnz]: the row of dAttWork that receives the term of every entry, the row count): rows_backward restated.  The block rows
+    come first, a workgroup and a row each, in the order of walk_model's blocks; group g of the walk is run by wave g % 4 of workgroup
+    g // 4, and a workgroup stores at its blockIdx.x.  Under the remap the grid of the grouped items is padded to a multiple of 8
+    workgroups and the kernel runs workgroup wg = (x % 8) * per + x // 8 at id x (per = padded / 8): wg is stored at
+    x = (wg % per) * 8 + wg // per, and the ids that no workgroup with a group maps to hold rows without entries."""
+    from attention_walk_graphs import walk_model
+    items, grp, blocks = walk_model(rowptr, k, budget)
+    nnz = int(np.asarray(rowptr, np.int64)[-1] - np.asarray(rowptr, np.int64)[0])
+    wgs = -(-(len(grp) - 1) // WAVES) if len(items) else 0
+    if remap:
+        wgs = -(-wgs // KXCDS) * KXCDS
+    row = np.full(nnz, -1, np.int64)
+    first = int(np.asarray(rowptr, np.int64)[0])
+    for b, (e0, cnt, _, _) in enumerate(blocks.tolist()):
+        row[e0 - first:e0 - first + cnt] = b
+    wg = (np.searchsorted(grp, np.arange(len(items)), side="right") - 1) // WAVES
+    if remap and wgs:
+        per = wgs // KXCDS
+        wg = (wg % per) * KXCDS + wg // per
+    at = np.repeat(items[:, 0] - first, items[:, 1]) + (np.arange(int(items[:, 1].sum())) - np.repeat(np.cumsum(items[:, 1]) - items[:, 1], items[:, 1]))
+    row[at] = np.repeat(len(blocks) + wg, items[:, 1])
+    assert (row >= 0).all() and (row < len(blocks) + wgs).all()
+    return row, len(blocks) + wgs
+
+
+def att_line_terms(a, xt, xs, att, p, g, slope, drop=None):
+    """(w, s1, s2), each [m, k] in float64: per line (row) of a the sums over its entries of dz_e L_ej, of |dz_e| |L_ej| and of
+    ddz_e |L_ej| + |dz_e| 2^-149, dz and its bound ddz backward_reference's on the probabilities given -- gatv2_dropout_ref's under
+    drop = (p, seed).  A line's entries all belong to one workgroup of the row launch, so the rows of dAttWork are sums of lines."""
+    if drop is None:
+        ref = backward_reference(a, xt, xs, att, p, g, slope)
+    else:
+        import gatv2_dropout_ref
+        ref = gatv2_dropout_ref.backward_reference(a, xt, xs, att, p, g, slope, *drop)
+    row, _, _ = coo(a)
+    k, heads = xs.shape[1], att.shape[0]
+    d = k // heads
+    w, s1, s2 = (np.zeros((a.m, k)) for _ in range(3))
+    with np.errstate(invalid="ignore", over="ignore"):
+        for h in range(heads):
+            _, _, L, _ = head_terms(a, xt, xs, att, slope, h)
+            dz, adz, ddz = ref["dz"][:, h], np.abs(ref["dz"][:, h]), ref["dz_bound"][:, h]
+            for j in range(d):
+                aL = np.abs(L[:, j])
+                w[:, h * d + j] = np.bincount(row, weights=dz * L[:, j], minlength=a.m)
+                s1[:, h * d + j] = np.bincount(row, weights=adz * aL, minlength=a.m)
+                s2[:, h * d + j] = np.bincount(row, weights=ddz * aL + adz * SUB, minlength=a.m)
+    return w, s1, s2
+
+
+def att_partials_reference(a, xt, xs, att, p, g, slope, layout, drop=None, copies=1, lines=None):
+    """(want [rows, k], bound [rows, k]) in float64 of the rows of dAttWork under layout = att_work_layout(...), from the probabilities
+    given (the kernel's own fp32 P): want = sum over the row's entries of dz_e leaky(x_ej), bound = gamma(n_w + 3) sum |dz_e| |L_ej|
+    + sum (ddz_e |L_ej| + |dz_e| 2^-149) + 2^-126, n_w the entries of the row; a row without entries is 0 (the checker asks it +0 bit
+    for bit).  copies = T: the layout is that of the block-diagonal graph of T copies of a with the operands repeated (no dropout:
+    its mask differs from copy to copy), and a row of dAttWork is a sum of whole lines of known copies, each taken from the one-copy
+    terms.  lines: att_line_terms(...) computed before."""
+    row_of, n_rows = layout
+    assert drop is None or copies == 1
+    w, s1, s2 = att_line_terms(a, xt, xs, att, p, g, slope, drop) if lines is None else lines
+    rp = np.asarray(a.rowPtr, np.int64)
+    assert row_of.shape == (copies * a.nnz,)
+    first = (rp[:-1][None, :] + a.nnz * np.arange(copies)[:, None]).reshape(-1)  # the first entry of every line of every copy
+    full = np.tile(np.diff(rp) > 0, copies)
+    line_row = row_of[first[full]]
+    n_w = np.bincount(row_of, minlength=n_rows)
+    assert np.array_equal(np.bincount(line_row, weights=np.tile(np.diff(rp), copies)[full], minlength=n_rows), n_w)  # whole lines
+    k = xs.shape[1]
+    want, bound = np.zeros((n_rows, k)), np.zeros((n_rows, k))
+    with np.errstate(invalid="ignore", over="ignore"):
+        for c in range(k):
+            t = [np.bincount(line_row, weights=np.tile(x[:, c], copies)[full], minlength=n_rows) for x in (w, s1, s2)]
+            want[:, c], bound[:, c] = t[0], gamma(n_w + 3) * t[1] + t[2]
+    return want, bound + TINY
+
+
+def att_reduce32(att_work):
+    """gatt_reduce on the rows [rows, k] in fp32 numpy: chain w takes rows w, w + 4, ... from 0.f, then ((c0 + c1) + c2) + c3.  [k]."""
+    x = np.asarray(att_work, np.float32)
+    chains = np.zeros((WAVES, x.shape[1]), np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for r in range(x.shape[0]):
+            chains[r % WAVES] += x[r]
+        tot = chains[0]
+        for w in range(1, WAVES):
+            tot = tot + chains[w]
+    return tot.astype(np.float32)
+
+
+def check_att_reduce(att_work, gatt, what=""):
+    """gatt [H, d] has the bits of att_reduce32 of att_work [rows, k], the rows the kernel itself wrote (NaN for NaN, whatever the
+    payload)."""
+    gatt = np.asarray(gatt, np.float32).reshape(-1)
+    red = att_reduce32(att_work)
+    assert gatt.shape == red.shape, f"{what}: gAtt has {gatt.size} elements, want {red.size}"
+    assert np.array_equal(np.isnan(gatt), np.isnan(red)), f"{what}: gAtt is NaN exactly where the sum of the rows of dAttWork is"
+    ok = ~np.isnan(red)
+    differ = gatt[ok].view(np.uint32) != red[ok].view(np.uint32)
+    assert not differ.any(), f"{what}: gAtt has not the bits of gatt_reduce on the rows of dAttWork in {int(differ.sum())} of {red.size} columns"
+
+
+def check_att(a, xt, xs, att, p, g, slope, att_work, gatt, layout, drop=None, what="", ratios=None, copies=1, lines=None):
+    """gAtt in two stages.  att_work: what the kernel left in dAttWork, [rows of the layout, k] (or flat); gatt [H, d].  Asserts that
+    every element of every partial row is within its bound, a row without entries +0 bit for bit, NaN and infinities exactly where
+    float64 has them; and that gatt has the bits of att_reduce32(att_work).  copies, lines: att_partials_reference's.  Returns the
+    worst err / bound of the partial rows (ratios["att_work"] keeps it)."""
+    row_of, n_rows = layout
+    k = xs.shape[1]
+    got = np.asarray(att_work, np.float32)
+    assert got.size == n_rows * k, f"{what}: dAttWork holds {got.size} floats, the layout has {n_rows} rows of {k}"
+    got = got.reshape(n_rows, k)
+    want, bound = att_partials_reference(a, xt, xs, att, np.asarray(p, np.float32), g, slope, layout, drop, copies, lines)
+    idle = np.bincount(row_of, minlength=n_rows) == 0
+    assert np.all(got[idle].view(np.uint32) == 0), f"{what}: {int((got[idle].view(np.uint32) != 0).any(1).sum())} rows of dAttWork without entries are not +0 in every column"
+    assert np.array_equal(np.isnan(got), np.isnan(want)), f"{what}: dAttWork is NaN where float64 is, and nowhere else ({int((np.isnan(got) != np.isnan(want)).sum())} differ)"
+    inf = np.isinf(want)
+    assert np.array_equal(got[inf].astype(np.float64), want[inf]) and not np.isinf(got[~inf]).any(), f"{what}: dAttWork: infinities as float64 gives them"
+    fin = np.isfinite(want)
+    ratio = np.zeros(want.shape)
+    ratio[fin] = np.abs(got[fin].astype(np.float64) - want[fin]) / bound[fin]
+    worst = float(ratio.max()) if ratio.size else 0.0
+    assert worst <= 1.0, (f"{what}: {int((ratio > 1).sum())} elements in {int((ratio > 1).any(1).sum())} rows of dAttWork beyond the bound, worst err / bound {worst:.3g}, "
+                          f"median of the rows beyond it {float(np.median(ratio.max(1)[(ratio > 1).any(1)])):.3g}")
+    check_att_reduce(got, gatt, what)
+    if ratios is not None:
+        ratios["att_work"] = max(worst, ratios.get("att_work", 0.0))
+    return worst
+
+
 # ---- an evaluation in fp32 arithmetic
 
 FAULTS = ("no_att", "leaky_after_dot", "slope_on_positive", "next_heads_att", "head_major", "joint_softmax", "gxs_no_value", "gxt_no_f",
@@ -302,14 +449,16 @@ def _seg_fma(terms, seg, n, d):
     return acc
 
 
-def fp32_result(a, xt, xs, att, slope, g=None, p=None, fault=None):
+def fp32_result(a, xt, xs, att, slope, g=None, p=None, fault=None, partials=None):
     """dict(out, p) -- and, with g, dict(gxt, gxs, gatt, dz) from the p given (default: this forward's) -- evaluated in fp32 arithmetic
     with numpy (fmas where the kernels use them, chains where they use trees): what a right kernel returns up to the order of its
     additions.  The faults the checkers must catch: no_att: att left out (all ones); leaky_after_dot: the leaky ReLU applied after the
     dot with att (GAT's order); slope_on_positive: the slope applied where x > 0; next_heads_att: att of head h + 1 used for head h;
     head_major: P and dz delivered as [H, nnz] in the same memory; joint_softmax: one softmax over all heads' scores of a row;
     gxs_no_value: gXs without its term p g; gxt_no_f: gXt without f; gatt_from_x: gAtt from dz x in place of dz leaky(x);
-    poison_spreads: a row that one head poisons is NaN in every head's columns of Out."""
+    poison_spreads: a row that one head poisons is NaN in every head's columns of Out.
+    partials = att_work_layout(...): with g, also att_work [rows, k], every row of dAttWork as a chain of fmas over its entries in entry
+    order, and gatt is then att_reduce32 of these rows: the two stages of the kernels."""
     assert fault is None or fault in FAULTS, fault
     row, col, rp = coo(a)
     k, heads = xs.shape[1], att.shape[0]
@@ -364,6 +513,7 @@ def fp32_result(a, xt, xs, att, slope, g=None, p=None, fault=None):
         g = np.asarray(g, F32)
         gxt, gxs, gatt, dzs = np.zeros((a.m, k), F32), np.zeros((a.n, k), F32), np.zeros((heads, d), F32), []
         chunk = 512
+        rows32 = None if partials is None else np.zeros((partials[1], k), F32)
         with np.errstate(invalid="ignore", over="ignore"):
             for h in range(heads):
                 c = head_columns(k, heads, h)
@@ -382,7 +532,11 @@ def fp32_result(a, xt, xs, att, slope, g=None, p=None, fault=None):
                 for r in range(part.shape[0]):
                     tot = (tot + part[r]).astype(F32)
                 gatt[h] = tot
+                if partials is not None:
+                    rows32[:, c] = _seg_fma([(dz, src)], partials[0], partials[1], d)
         res.update(gxt=gxt, gxs=gxs, gatt=gatt, dz=np.stack(dzs, 1))
+        if partials is not None:
+            res.update(att_work=rows32, gatt=att_reduce32(rows32).reshape(heads, d))
     if fault == "head_major":
         for key in ("p", "dz"):
             if key in res:

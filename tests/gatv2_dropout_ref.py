@@ -177,7 +177,7 @@ FAULTS = FORWARD_FAULTS + BACKWARD_FAULTS
 _MASK_FAULTS = ("shard_local", "head_major", "next_head", "inverted", "seed_high_ignored")
 
 
-def fp32_result(a, xt, xs, att, slope, p, seed, g=None, probs=None, rows=None, fault=None):
+def fp32_result(a, xt, xs, att, slope, p, seed, g=None, probs=None, rows=None, fault=None, partials=None):
     """dict(out [rows, k], p [entries, H]; with g also gxt [m, k], gxs [n, k], gatt [H, d], dz [nnz, H]) evaluated in fp32 arithmetic
     with numpy, as gatv2_attention_ref.fp32_result (fmas where the kernels use them, chains where they use trees): what a right kernel
     returns up to the order of its additions.  The backward starts from `probs` (default: this forward's).  Faults:
@@ -195,7 +195,9 @@ def fp32_result(a, xt, xs, att, slope, p, seed, g=None, probs=None, rows=None, f
       gxt_masked_twice   gXt likewise
       gatt_masked_twice  gAtt likewise
       gxs_value_unmasked the value term of gXs is sum p g
-      da_unmasked        da = <g, Xs>"""
+      da_unmasked        da = <g, Xs>
+    partials = gatv2_attention_ref.att_work_layout(...): with g, also att_work [rows, k], every row of dAttWork as a chain of fmas over
+    its entries in entry order, and gatt is then att_reduce32 of these rows."""
     assert fault in (None,) + FAULTS, fault
     row, col, rp = coo(a, rows)
     m, k, heads = len(rp) - 1, xs.shape[1], att.shape[0]
@@ -249,6 +251,7 @@ def fp32_result(a, xt, xs, att, slope, p, seed, g=None, probs=None, rows=None, f
     g = np.asarray(g, F32)
     gxt, gxs, gatt, dzs = np.zeros((a.m, k), F32), np.zeros((a.n, k), F32), np.zeros((heads, d), F32), []
     chunk = 512
+    rows32 = None if partials is None else np.zeros((partials[1], k), F32)
     with np.errstate(invalid="ignore", over="ignore"):
         for h in range(heads):
             cs, sel = head_columns(k, heads, h), kp[:, h]
@@ -270,7 +273,11 @@ def fp32_result(a, xt, xs, att, slope, p, seed, g=None, probs=None, rows=None, f
             for r in range(part.shape[0]):
                 tot = (tot + part[r]).astype(F32)
             gatt[h] = tot
+            if partials is not None:
+                rows32[:, cs] = _seg_fma([(twice if fault == "gatt_masked_twice" else dz, Ls[h])], partials[0], partials[1], d)
     res.update(gxt=gxt, gxs=gxs, gatt=gatt, dz=np.stack(dzs, 1))
+    if partials is not None:
+        res.update(att_work=rows32, gatt=v2.att_reduce32(rows32).reshape(heads, d))
     return res
 
 
