@@ -340,6 +340,47 @@ def gat_dropout_functions():
     return _gat_dropout_cache
 
 
+def _gat_edge_function():
+    import torch
+
+    class _FusedGatEdgeAttention(torch.autograd.Function):
+        """_FusedGatAttention / _FusedGatAttentionDropout with a per-edge term ee [nnz, heads] inside the LeakyReLU:
+        flex_edge_gat_attention in one launch (drop_p = 0: no mask), the UNDROPPED alpha kept only when a gradient is needed;
+        backward: the one call flex_edge_gat_attention_backward (two launches) under the same drop_p and seed.  Keeps (el, er, ee, V, P)
+        and the seed, never a mask; the gradient in ee is the call's work array, so nothing nnz-sized is allocated beside it.  Only on
+        an operator made with fused_attention=True and fused_backward=True."""
+
+        @staticmethod
+        def forward(ctx, el, er, ee, V, op, slope, drop_p, seed):
+            el, er, ee, V = el.contiguous(), er.contiguous(), ee.contiguous(), V.contiguous()
+            p = torch.zeros((op.nnz, el.shape[1]), dtype=torch.float32, device=V.device) if any(ctx.needs_input_grad[:4]) else None
+            out = op.plan.gat_edge_attention(el, er, ee, V, slope, drop_p, seed, probs=p)
+            ctx.op, ctx.slope, ctx.drop_p, ctx.seed = op, slope, drop_p, seed
+            ctx.save_for_backward(el, er, ee, V, p)
+            return out
+
+        @staticmethod
+        def backward(ctx, grad_out):
+            el, er, ee, V, p = ctx.saved_tensors
+            grads = ctx.op.plan.gat_edge_attention_backward(el, er, ee, V, p, grad_out.contiguous(), ctx.slope, ctx.drop_p, ctx.seed,
+                                                            want=tuple(ctx.needs_input_grad[:4]))
+            return (*grads, None, None, None, None)
+
+    return (_FusedGatEdgeAttention,)
+
+
+_gat_edge_cache = None
+
+
+def gat_edge_functions():
+    """(_FusedGatEdgeAttention,): the autograd Function of the GAT attention with a per-edge score term, built at first use, as
+    gat_dropout_functions(); functions(), gat_dropout_functions() and gat_bf16_functions() keep their counts."""
+    global _gat_edge_cache
+    if _gat_edge_cache is None:
+        _gat_edge_cache = _gat_edge_function()
+    return _gat_edge_cache
+
+
 def _gatv2_function():
     import torch
 
@@ -617,7 +658,8 @@ class SparseOperator:
             return functions()[5].apply(Q, K, V, self, float(scale))
         return self(V, values=self.edge_softmax(self.sddmm(Q, K), scale))
 
-    def gat_attention(self, el, er, V, negative_slope: float = 0.2, dropout: float = 0.0, seed: int | None = None, training: bool = True):
+    def gat_attention(self, el, er, V, negative_slope: float = 0.2, dropout: float = 0.0, seed: int | None = None, training: bool = True,
+                      edge=None):
         """Out [m, k] = A(alpha) V per head with alpha = softmax over each row of A of leaky_relu(el[row, h] + er[col, h], negative_slope):
         the attention of a GAT layer, el = <h W, a_l> and er = <h W, a_r> being one scalar per node and head.  H = el.shape[1] heads; head h
         is columns [h k / H, (h + 1) k / H) of V and Out.  Differentiable in el [m, H], er [n, H] and V [n, k]; all heads in one forward
@@ -630,13 +672,27 @@ class SparseOperator:
         A torch.bfloat16 V takes the bf16 kernels (flex_gat_attention_bf16, flex_gat_attention_bf16_dropout): V rows are gathered as
         bfloat16, every sum is float32, Out and grad V come back in bfloat16, rounded once.  el and er are then float32 or bfloat16;
         bfloat16 ones are widened before the call (the scores stay float32) and their gradients come back in bfloat16.  Any other mix
-        of dtypes is a TypeError."""
+        of dtypes is a TypeError.
+        edge (a float32 [nnz, H] tensor in a's CSR order, differentiable): a per-edge, per-head term inside the LeakyReLU, the score
+        leaky_relu((el[row, h] + er[col, h]) + edge[e, h]) of a GAT layer with edge features (edge = <lin_edge(edge_attr), att_edge>),
+        in the same launches (flex_edge_gat_attention); -inf masks one entry for one head.  dropout, seed and training work as without
+        it.  float32 V only: anything else, and any other dtype or shape of edge, is a TypeError.  edge=None takes the paths above."""
         if not 0.0 <= dropout < 1.0:  # a NaN fails this too
             raise ValueError(f"dropout must be a probability in [0, 1), not {dropout}")
         if not (self.fused_attention and self.fused_backward):
             raise NotImplementedError("gat_attention needs SparseOperator(..., learn_values=True, fused_attention=True, fused_backward=True): "
                                       "only the fused forward and backward compute the additive score")
         import torch
+        if edge is not None:
+            if not (el.dtype == er.dtype == V.dtype == torch.float32):
+                raise TypeError(f"gat_attention with edge takes float32 el, er and V, not {el.dtype}, {er.dtype} and {V.dtype}")
+            if not isinstance(edge, torch.Tensor) or edge.dtype != torch.float32 or tuple(edge.shape) != (self.nnz, el.shape[1]):
+                raise TypeError(f"gat_attention takes a float32 edge of shape [nnz, heads] = [{self.nnz}, {el.shape[1]}], not "
+                                f"{getattr(edge, 'dtype', type(edge))} {tuple(getattr(edge, 'shape', ()))}")
+            drop = float(dropout) if training else 0.0
+            if drop > 0 and seed is None:
+                seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+            return gat_edge_functions()[0].apply(el, er, edge, V, self, float(negative_slope), drop, int(seed or 0) & 0xFFFFFFFFFFFFFFFF)
         bf16 = V.dtype == torch.bfloat16
         if bf16:
             if any(t.dtype not in (torch.float32, torch.bfloat16) for t in (el, er)):

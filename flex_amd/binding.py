@@ -174,6 +174,7 @@ SYMBOLS = [
     "flex_gat_attention_bf16", "flex_gat_attention_bf16_backward", "flex_gat_attention_bf16_dropout", "flex_gat_attention_bf16_dropout_backward",
     "flex_gatv2_attention", "flex_gatv2_attention_backward", "flex_gatv2_attention_work_size",
     "flex_dropout_gatv2_attention", "flex_dropout_gatv2_attention_backward",
+    "flex_edge_gat_attention", "flex_edge_gat_attention_backward",
 ]
 
 _lib = None
@@ -300,7 +301,9 @@ def _values_fn(name: str):
                       "flex_gatv2_attention_backward": [vp, i32, vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, vp, vp],
                       "flex_gatv2_attention_work_size": [vp, C.POINTER(u64)],
                       "flex_dropout_gatv2_attention": [vp, i32, vp, vp, vp, fl, fl, u64, vp, vp, vp],
-                      "flex_dropout_gatv2_attention_backward": [vp, i32, vp, vp, vp, vp, vp, fl, fl, u64, vp, vp, vp, vp, vp, vp]}[name]
+                      "flex_dropout_gatv2_attention_backward": [vp, i32, vp, vp, vp, vp, vp, fl, fl, u64, vp, vp, vp, vp, vp, vp],
+                      "flex_edge_gat_attention": [vp, i32, vp, vp, vp, vp, fl, fl, u64, vp, vp, vp],
+                      "flex_edge_gat_attention_backward": [vp, i32, vp, vp, vp, vp, vp, vp, fl, fl, u64, vp, vp, vp, vp, vp, vp]}[name]
     return f
 
 
@@ -1360,6 +1363,69 @@ class Plan:
         seed; gV is bfloat16; gEl, gEr, probs and work are float32."""
         return self._gat_bf16_backward(self.gat_attention_bf16_dropout_backward_ptr, el, er, V, probs, grad_out,
                                        (slope, p, int(seed) & 0xFFFFFFFFFFFFFFFF), (grad_el, grad_er, grad_v), work, want)
+
+    def gat_edge_attention_ptr(self, heads: int, dEl_ptr: int, dEr_ptr: int, dEe_ptr: int, dV_ptr: int, slope: float, p: float, seed: int,
+                               dOut_ptr: int, dP_ptr: int | None = None, stream: int = 0):
+        """flex_edge_gat_attention; dEl is rows x H floats, dEr n x H, dEe and dP (optional) nnz x H, entry-major; dP receives the
+        UNDROPPED alpha."""
+        _check(_values_fn("flex_edge_gat_attention")(self._h, heads, dEl_ptr, dEr_ptr, dEe_ptr, dV_ptr, slope, p, seed, dOut_ptr, dP_ptr, stream),
+               "flex_edge_gat_attention")
+
+    def gat_edge_attention(self, el, er, ee, V, slope: float, drop_p: float = 0.0, seed: int = 0, out=None, probs=None):
+        """flex_edge_gat_attention: gat_attention() (drop_p = 0) or gat_attention_dropout() with a per-edge term inside the LeakyReLU, the
+        score leaky_relu((el[row, h] + er[col, h]) + ee[e, h], slope).  ee: float32 cuda [a.nnz, H] in a's CSR order; -inf masks one
+        entry for one head.  probs (optional, float32 [a.nnz, H]) receives the UNDROPPED alpha."""
+        import torch
+        i = self.info()
+        heads = self._node_scalars(el, er)
+        self._head_edge_arrays(heads, ee)
+        assert V.is_cuda and V.dtype == torch.float32 and V.is_contiguous() and tuple(V.shape) == (i["n"], i["k"])
+        if out is None:  # every row is written, except by a plan without entries, which launches nothing
+            out = (torch.empty if i["nnz"] else torch.zeros)((i["m"], i["k"]), dtype=torch.float32, device=V.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (i["m"], i["k"])
+        if probs is not None:
+            self._head_edge_arrays(heads, probs)
+        self.gat_edge_attention_ptr(heads, el.data_ptr(), er.data_ptr(), ee.data_ptr(), V.data_ptr(), slope, drop_p, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                    out.data_ptr(), None if probs is None else probs.data_ptr(), torch.cuda.current_stream(V.device).cuda_stream)
+        return out
+
+    def gat_edge_attention_backward_ptr(self, heads: int, dEl_ptr: int, dEr_ptr: int, dEe_ptr: int, dV_ptr: int, dP_ptr: int, dGradOut_ptr: int,
+                                        slope: float, p: float, seed: int, dGradEl_ptr: int | None, dGradEr_ptr: int | None,
+                                        dGradEe_ptr: int | None, dGradV_ptr: int | None, dWork_ptr: int | None, stream: int = 0):
+        """flex_edge_gat_attention_backward; dEe, dP, dGradEe and dWork are nnz x H floats, entry-major; the work array is dGradEe where
+        it is given, else dWork."""
+        _check(_values_fn("flex_edge_gat_attention_backward")(self._h, heads, dEl_ptr, dEr_ptr, dEe_ptr, dV_ptr, dP_ptr, dGradOut_ptr, slope, p, seed,
+                                                              dGradEl_ptr, dGradEr_ptr, dGradEe_ptr, dGradV_ptr, dWork_ptr, stream),
+               "flex_edge_gat_attention_backward")
+
+    def gat_edge_attention_backward(self, el, er, ee, V, probs, grad_out, slope: float, drop_p: float = 0.0, seed: int = 0,
+                                    want=(True, True, True, True), grad_el=None, grad_er=None, grad_ee=None, grad_v=None, work=None):
+        """flex_edge_gat_attention_backward: (gEl [m, H], gEr [n, H], gEe [a.nnz, H], gV [n, k]) of gat_edge_attention()'s out from its
+        probs (the undropped alpha), grad_out [m, k] and the same drop_p and seed, in two launches; an output that `want` does not ask
+        for is None and is not computed.  The gEe tensor is the call's work array: the kernel writes dx into it and nothing is copied.
+        work (optional, float32 cuda [a.nnz, H], not probs) is the work array when gEe is not wanted; it is allocated here when needed."""
+        import torch
+        i = self.info()
+        heads = self._node_scalars(el, er)
+        for t, rows in ((V, i["n"]), (grad_out, i["m"])):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (rows, i["k"])
+        self._head_edge_arrays(heads, ee, probs)
+        shapes = ((i["m"], heads), (i["n"], heads), (self.src_nnz, heads), (i["n"], i["k"]))
+        outs = []
+        for wanted, t, shape in zip(want, (grad_el, grad_er, grad_ee, grad_v), shapes):
+            if wanted and t is None:  # every row is written, except by a plan without entries, which launches nothing
+                t = (torch.empty if i["nnz"] else torch.zeros)(shape, dtype=torch.float32, device=V.device)
+            if wanted:
+                assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape
+            outs.append(t if wanted else None)
+        if outs[2] is None and work is None:
+            work = torch.empty((self.src_nnz, heads), dtype=torch.float32, device=V.device)
+        if work is not None:
+            self._head_edge_arrays(heads, work)
+        self.gat_edge_attention_backward_ptr(heads, el.data_ptr(), er.data_ptr(), ee.data_ptr(), V.data_ptr(), probs.data_ptr(), grad_out.data_ptr(),
+                                             slope, drop_p, int(seed) & 0xFFFFFFFFFFFFFFFF, *(None if t is None else t.data_ptr() for t in outs),
+                                             None if work is None else work.data_ptr(), torch.cuda.current_stream(V.device).cuda_stream)
+        return tuple(outs)
 
     def destroy(self):
         if getattr(self, "_h", None) and self._h.value:

@@ -29,6 +29,12 @@
 // attention_gat_bf16_kernels.hip.  The sweeps reach a row through load_cols, store_cols and write_row alone (attention_device.h), which
 // hand over and take fp32: with flex_bf16 a lane's four columns are one 8-byte access, widened exactly and rounded once at the store.
 // El, Er, P, DX, GEl, GEr, Work and every sum stay float, so on the widened operands the edge arrays and gEl, gEr have the fp32 bits.
+//
+// EDGE (attention_gat_edge_kernels.hip turns it on; off, which is the default, the sweeps are what they were): a per-entry, per-head
+// term inside the LeakyReLU, x = (el + er) + ee in fp32 and in this order.  Ee is an edge array as dP: (entry e, head h) at e H + h, e
+// the whole matrix's entry index.  Forward: every live lane of a head loads its element with the pass's er loads and V gathers -- the
+// lanes of a head share the address, the H heads of an entry are one contiguous run; with DROP a dropped entry's term is read all the
+// same.  Row backward, sweep 2: the owning lane forms the same x.  d x / d ee = 1, so gEe is dx, which sweep 2 writes to Work already.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -44,10 +50,11 @@ __device__ __forceinline__ float leaky(float x, float slope) { return x > 0.f ? 
 
 // ---- forward
 
-template <int W, int NS, bool DROP, class E>
+template <int W, int NS, bool DROP, bool EDGE = false, class E>
 __device__ __forceinline__ void run_item(const View &v, const HeadSplit &hs, const uint4 &it, int kind, const float *__restrict__ El,
                                          const float *__restrict__ Er, const E *__restrict__ V, float slope, const DropMask &dm,
-                                         E *__restrict__ Out, float *__restrict__ P, uint32_t lane, uint32_t w, HeadsShared<W, NS> &sh) {
+                                         E *__restrict__ Out, float *__restrict__ P, uint32_t lane, uint32_t w, HeadsShared<W, NS> &sh,
+                                         const float *__restrict__ Ee = nullptr) {
     const uint32_t slot = lane / W, li = lane % W;
     const int slot_lane0 = static_cast<int>(lane - li);
     const HeadLane hl(hs, li);
@@ -68,9 +75,10 @@ __device__ __forceinline__ void run_item(const View &v, const HeadSplit &hs, con
         const uint32_t idx = mine ? v.src[pl.first - v.e0 + j0 + li] : 0u;
         bool valid[U];
         float er[U][NS];
+        float ee[U][NS];  // EDGE: the entry's own term of the score, a dropped entry's as well (it stays in the softmax)
         float4 vv[U][NS];
         bool keep[U][NS];  // DROP: whether (entry u, the head of slab s) is kept; a dropped entry's V row is not gathered and stays 0
-        const uint64_t i0 = DROP ? (pl.first + j0) * static_cast<uint64_t>(hs.H) : 0;  // the pass's first element of the edge arrays
+        const uint64_t i0 = (DROP || EDGE) ? (pl.first + j0) * static_cast<uint64_t>(hs.H) : 0;  // the pass's first element of the edge arrays
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const uint32_t col = __shfl(idx, slot_lane0 + u);
@@ -82,6 +90,8 @@ __device__ __forceinline__ void run_item(const View &v, const HeadSplit &hs, con
                 keep[u][s] = true;
                 if constexpr (DROP) keep[u][s] = valid[u] && kept(dm, i0 + static_cast<uint32_t>(u * hs.H) + lh.head[s]);
                 er[u][s] = (valid[u] && lh.live[s]) ? ec[lh.head[s]] : 0.f;
+                ee[u][s] = 0.f;
+                if constexpr (EDGE) ee[u][s] = (valid[u] && lh.live[s]) ? Ee[i0 + static_cast<uint32_t>(u * hs.H) + lh.head[s]] : 0.f;
                 vv[u][s] = (valid[u] && keep[u][s]) ? load_cols<true>(vr, 4 * static_cast<int>(li) + 4 * W * s, v.k) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
         }
@@ -91,7 +101,11 @@ __device__ __forceinline__ void run_item(const View &v, const HeadSplit &hs, con
             float pm = -INFINITY;
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                sc[u] = valid[u] ? leaky(elr[s] + er[u][s], slope) : -INFINITY;
+                if constexpr (EDGE) {
+                    sc[u] = valid[u] ? leaky((elr[s] + er[u][s]) + ee[u][s], slope) : -INFINITY;
+                } else {
+                    sc[u] = valid[u] ? leaky(elr[s] + er[u][s], slope) : -INFINITY;
+                }
                 pm = fmaxf(pm, max_key(sc[u]));
             }
             if (P && lh.live[s]) {
@@ -184,11 +198,12 @@ struct RowShared {
 };
 
 // DROP: da of a kept entry is c <g, V>, da of a dropped one +0 and its V row is not gathered; delta, dz, dx and gEl follow from da
-template <int W, int NS, bool DROP, class E>
+template <int W, int NS, bool DROP, bool EDGE = false, class E>
 __device__ __forceinline__ void run_row(const View &v, const HeadSplit &hs, const uint4 &it, int kind, const float *__restrict__ El,
                                         const float *__restrict__ Er, const E *__restrict__ V, const float *__restrict__ P,
                                         const E *__restrict__ G, float slope, const DropMask &dm, float *__restrict__ GEl,
-                                        float *__restrict__ Work, uint32_t lane, uint32_t w, RowShared<W, NS> &sh) {
+                                        float *__restrict__ Work, uint32_t lane, uint32_t w, RowShared<W, NS> &sh,
+                                        const float *__restrict__ Ee = nullptr) {
     const uint32_t slot = lane / W, li = lane % W;
     const int slot_lane0 = static_cast<int>(lane - li);
     const HeadLane hl(hs, li);
@@ -270,7 +285,8 @@ __device__ __forceinline__ void run_row(const View &v, const HeadSplit &hs, cons
                     if (!lh.live[s]) continue;
                     const uint64_t e = (pl.first + j0 + u) * static_cast<uint64_t>(hs.H) + lh.head[s];
                     const float dz = P[e] * (Work[e] - delta[s]);
-                    const float x = elr[s] + Er[static_cast<size_t>(col) * static_cast<size_t>(hs.H) + lh.head[s]];
+                    float x = elr[s] + Er[static_cast<size_t>(col) * static_cast<size_t>(hs.H) + lh.head[s]];
+                    if constexpr (EDGE) x = x + Ee[e];  // the forward's two additions in its order: the same bits
                     const float dx = x > 0.f ? dz : slope * dz;
                     Work[e] = dx;
                     gel[s] += dx;

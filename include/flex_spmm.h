@@ -37,6 +37,7 @@ extern "C" {
                               the equally additive flex_gat_attention_bf16, flex_gat_attention_bf16_dropout and their backward calls (four new calls, no flag, no struct),
                               the equally additive flex_gatv2_attention, flex_gatv2_attention_backward and flex_gatv2_attention_work_size (three new calls, no flag, no struct),
                               the equally additive flex_dropout_gatv2_attention and flex_dropout_gatv2_attention_backward (two new calls, no flag, no struct),
+                              the equally additive flex_edge_gat_attention and flex_edge_gat_attention_backward (two new calls, no flag, no struct),
                               and the retired flex_plan_tuning.block_ablate, which keeps its place as block_ablate_retired and must be zero.
                               3: plan-time knobs leave the environment for the struct flex_plan_tuning, flex_plan_desc.tuning, flex_plan_get_tuning,
                               flex_order_cluster_ex, flex_set_host_threads; split rows are summed by a second launch by default.
@@ -795,6 +796,47 @@ int flex_gat_attention_dropout(const flex_plan *plan, int heads, const float *dE
 int flex_gat_attention_dropout_backward(const flex_plan *plan, int heads, const float *dEl, const float *dEr, const float *dV, const float *dP,
                                         const float *dGradOut, float slope, float drop_p, uint64_t seed, float *dGradEl, float *dGradEr,
                                         float *dGradV, float *dWork, flex_stream_t stream);
+
+/* A per-edge term in the score of the fused GAT attention (edge features): the score of the edge-feature GAT of the common libraries,
+ * alpha = alpha_dst[i] + alpha_src[j] + alpha_edge[e] inside the LeakyReLU, with alpha_edge = <lin_edge(edge_attr), att_edge> computed
+ * by the caller.  One pair of calls serves both modes: drop_p == 0 launches kernels without the mask, anything else the dropout of
+ * flex_gat_attention_dropout.  Still ONE forward launch and TWO backward launches on the same plans; no plan flag, no new image.
+ * Everything is flex_gat_attention's and flex_gat_attention_dropout's except one line:
+ *     x_eh = fl(fl(el[r, h] + er[src(e), h]) + ee[e, h])      (fp32, in this order)
+ * - ee is [nnz, H] fp32, entry-major, in the CSR order the plan was made from.
+ * - s, alpha, Out, da, delta, dz, dx_eh = x_eh > 0 ? dz_eh : slope dz_eh, gEl, gEr, gV and the dropout mask of (seed, e H + h) are
+ *   unchanged.
+ * - gEe[e, h] = dx_eh.
+ * - ee[e, h] = -inf masks that entry for that head: p is exactly +0, and the row is +0 if all its entries are masked.
+ * - A NaN or +inf score poisons that head of that row only.  -inf + +inf counts as such a score.
+ * - On a row-range shard ee is indexed by the whole matrix's entry index, as dBias and dP are.  Only the shard's entries are read.
+ * - fp32 V only; d in {4, ..., 256}, a power of two, H = 1 included; k <= 1024; only the 16-byte form; 0 < slope <= 1.
+ * Backward.  The work array is dGradEe when it is given, else dWork: exactly one is needed, and if both are given dGradEe is used and
+ * dWork is untouched.  On return the work array holds dx: that IS gEe, not a copy of it (d x / d ee = 1 inside the pre-activation, so
+ * the gradient needs no sum of its own).  The rows' launch runs iff dGradEl, dGradEr or dGradEe is given, the columns' launch iff
+ * dGradEr or dGradV is given; the columns' launch is flex_gat_attention_backward's (flex_gat_attention_dropout_backward's with a mask),
+ * which reads P, dx and g alone.  Every output has the same bits whichever others are asked for.  With ee = +0 everywhere and no
+ * operand -0, every output has the bits of flex_gat_attention / flex_gat_attention_dropout and their backward calls.
+ * Checks: the refusals of flex_gat_attention_dropout and flex_gat_attention_dropout_backward, code for code and in their order; dEe joins
+ * the required operands (NULL: FLEX_ERR_INVALID); drop_p is checked beside the slope; both work pointers NULL, or the work array equal
+ * to dP: FLEX_ERR_INVALID.  The forward runs on row-range shards, the backward returns FLEX_ERR_INVALID there.  Nothing is enqueued by
+ * a refused call.  Safe to capture in a hipGraph, no atomics, fixed order: bit-identical run to run for one seed.
+ * Accuracy: flex_gat_attention's lines (with dropout, flex_gat_attention_dropout's) on another ds; the float64 reference uses the exact
+ * x = el + er + ee on the fp32 inputs and takes the LeakyReLU branch from the sign of the fp32 x formed in the order above.  Two rounded
+ * additions, where the first sum may cancel against ee, give
+ *     |x^ - x| <= u (1 + u) |el + er| + u |x|
+ * so with f_e = 1 or slope:
+ *     ds_e = gamma(2) f_e |el + er| + gamma(3) |s_e| + 2^-149
+ * in place of gamma(2) |s_e| + 2^-149.  Derivation: a = fl(el + er) = (el + er)(1 + d1) and x^ = fl(a + ee) = (x + (el + er) d1)(1 + d2)
+ * with |d1|, |d2| <= u, which is the first line; s^ = x^ or fl(slope x^), one more rounding that may be subnormal, so
+ * |s^ - s| <= f u (1 + u)^2 |el + er| + (u (1 + u) + u) |s| + 2^-149, inside the second line.  Where x^ and x differ in sign, |x| is
+ * below u (1 + u) |el + er| and either branch of the reference is within the same line.  alpha, Out, dda, ddz, ddx, gEl, gEr and gV
+ * keep their formulas with this ds; gEe is held to ddx. */
+int flex_edge_gat_attention(const flex_plan *plan, int heads, const float *dEl, const float *dEr, const float *dEe, const float *dV, float slope,
+                            float drop_p, uint64_t seed, float *dOut, float *dP /* optional */, flex_stream_t stream);
+int flex_edge_gat_attention_backward(const flex_plan *plan, int heads, const float *dEl, const float *dEr, const float *dEe, const float *dV,
+                                     const float *dP, const float *dGradOut, float slope, float drop_p, uint64_t seed, float *dGradEl,
+                                     float *dGradEr, float *dGradEe, float *dGradV, float *dWork, flex_stream_t stream);
 
 /* The fused GAT attention on bf16 V rows, with and without dropout: flex_gat_attention, flex_gat_attention_backward,
  * flex_gat_attention_dropout and flex_gat_attention_dropout_backward, argument for argument, with V, Out, g and gV held as flex_bf16 --

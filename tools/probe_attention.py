@@ -2,7 +2,7 @@
 """Sparse graph attention, measured: the error of the exponential the edge softmax may use, and the time of flex_edge_softmax,
 flex_edge_softmax_backward and a whole attention step.  Writes profiles/attention_probe.txt (or the file given with --out): the whole run
 starts the file, a run of one part (--fused, --backward, --heads, --gat, --bf16, --bias, --dropout, --gat-dropout, --gat-bf16, --gatv2,
---gatv2-dropout)
+--gatv2-dropout, --gat-edge)
 appends to it.
 
 1. tools/exp_error.hip (built here with hipcc into flex_amd/lib if it is not there): the largest error in ulp of expf, __expf and
@@ -60,7 +60,14 @@ appends to it.
    0.6, same graphs and protocol: the forward (with dP) and the backward (all three gradients) against the undropped
    flex_gatv2_attention and flex_gatv2_attention_backward on the same plan in the same process -- what the mask costs where every Xs
    row is gathered all the same.  --gatv2-dropout: only this part (and the copy rate).
-Usage: probe_attention.py [--out FILE] [--fused | --backward | --heads | --gat | --bf16 | --bias | --dropout | --gat-dropout | --gat-bf16 | --gatv2 | --gatv2-dropout] [graph ...]   (default: pubmed.csv flickr reddit soc-sign-epinions)"""
+15. A per-edge term in GAT's score (flex_edge_gat_attention and its backward call: edge features), (k, H) = (64, 8), (128, 4), (256, 8),
+   same graphs and protocol: the forward (with dP), the backward (all four gradients, gEe being the work array) and the autograd step
+   of gat_attention(..., edge=e) against (a) what a user had before -- per head, torch index arithmetic for the scores with ee,
+   edge_softmax and the SpMM with values=alpha of an operator of width d on a column slice, torch autograd carrying the gradients of
+   el, er and ee -- and (b) the edge-less flex_gat_attention and flex_gat_attention_backward on the same operator: the difference from
+   (b) is what the ee stream costs (nnz x H floats read in the forward and again in the row backward).  --gat-edge: only this part (and
+   the copy rate).
+Usage: probe_attention.py [--out FILE] [--fused | --backward | --heads | --gat | --bf16 | --bias | --dropout | --gat-dropout | --gat-bf16 | --gatv2 | --gatv2-dropout | --gat-edge] [graph ...]   (default: pubmed.csv flickr reddit soc-sign-epinions)"""
 import ctypes as C
 import os
 import subprocess
@@ -651,16 +658,86 @@ def probe_gatv2_dropout(name, a):
         del plan
 
 
+def probe_gat_edge(name, a):
+    import numpy as np
+    gen = torch.Generator(device="cuda").manual_seed(15)
+    rp = a.rowPtr.astype(np.int64)
+    rows = torch.from_numpy(np.repeat(np.arange(a.m), np.diff(rp))).cuda()
+    cols = torch.from_numpy(a.col.astype(np.int64)).cuda()
+    slope = 0.2
+    for k, H in ((64, 8), (128, 4), (256, 8)):
+        d = k // H
+        fused = flex_amd.SparseOperator(a, k, learn_values=True, fused_attention=True, fused_backward=True)
+        one = flex_amd.SparseOperator(a, d, learn_values=True)  # what a user had: one head at a time on a column slice
+        el, er = (torch.rand((r, H), device="cuda", generator=gen) * 4 - 2 for r in (a.m, a.n))
+        ee = torch.rand((a.nnz, H), device="cuda", generator=gen) * 4 - 2
+        V = torch.rand((a.n, k), device="cuda", generator=gen) * 2 - 1
+        g = torch.rand((a.m, k), device="cuda", generator=gen) * 2 - 1
+        out, gv = torch.empty((a.m, k), device="cuda"), torch.empty((a.n, k), device="cuda")
+        gel, ger = torch.empty((a.m, H), device="cuda"), torch.empty((a.n, H), device="cuda")
+        P, W, gee = (torch.empty((a.nnz, H), device="cuda") for _ in range(3))
+        elg, erg, eeg, Vg = (x.clone().requires_grad_() for x in (el, er, ee, V))
+
+        def loop(el, er, ee, V):
+            outs = []
+            for h in range(H):
+                s = torch.nn.functional.leaky_relu(el[rows, h] + er[cols, h] + ee[:, h], slope)
+                outs.append(one(V[:, h * d:(h + 1) * d].contiguous(), values=one.edge_softmax(s)))
+            return torch.cat(outs, 1)
+
+        def loop_forward():
+            with torch.no_grad():
+                loop(el, er, ee, V)
+
+        def clear():
+            for x in (elg, erg, eeg, Vg):
+                x.grad = None
+
+        kept = loop(elg, erg, eeg, Vg)
+
+        def loop_backward():
+            clear()
+            kept.backward(g, retain_graph=True)
+
+        def loop_step():
+            clear()
+            loop(elg, erg, eeg, Vg).backward(g)
+
+        def edge_step():
+            clear()
+            fused.gat_attention(elg, erg, Vg, slope, edge=eeg).backward(g)
+
+        def plain_step():
+            clear()
+            fused.gat_attention(elg, erg, Vg, slope).backward(g)
+
+        plan = fused.plan
+        plan.gat_edge_attention(el, er, ee, V, slope, out=out, probs=P)
+        fns = {"forward, loop": loop_forward, "forward, edge": lambda: plan.gat_edge_attention(el, er, ee, V, slope, out=out, probs=P),
+               "forward, no edge": lambda: plan.gat_attention(el, er, V, slope, out=out, p=P),
+               "backward, loop": loop_backward,
+               "backward, edge": lambda: plan.gat_edge_attention_backward(el, er, ee, V, P, g, slope, grad_el=gel, grad_er=ger, grad_ee=gee, grad_v=gv),
+               "backward, no edge": lambda: plan.gat_attention_backward(el, er, V, P, g, slope, grad_el=gel, grad_er=ger, grad_v=gv, work=W),
+               "step, loop": loop_step, "step, edge": edge_step, "step, no edge": plain_step}
+        n = max(3, min(100, int(1e8 / max(1, a.nnz * k))))
+        best, spread = _alternate(fns, n)
+        say(f"{name} k={k} H={H} d={d} gat edge: " + "  ".join(f"{key} {best[key]:.1f} us (+{spread[key]:.0f} % over 3 rounds)" for key in fns)
+            + "  loop / edge: " + "  ".join(f"{w} {best[w + ', loop'] / best[w + ', edge']:.2f}x" for w in ("forward", "backward", "step"))
+            + "  edge / no edge: " + "  ".join(f"{w} {best[w + ', edge'] / best[w + ', no edge']:.2f}x" for w in ("forward", "backward", "step"))
+            + f"  edge arrays of a step: {12 * a.nnz * H / 2 ** 20:.1f} MiB (ee, P and gEe = the work array, nnz x H floats each)")
+        del fused, one, kept
+
+
 def main():
     args = sys.argv[1:]
     out = os.path.join(ROOT, "profiles", "attention_probe.txt")
     if args[:1] == ["--out"]:
         out, args = args[1], args[2:]
-    fused_only, backward_only, heads_only, gat_only, bf16_only, bias_only, dropout_only, gat_dropout_only, gat_bf16_only, gatv2_only, gatv2_dropout_only = (
-        args[:1] == [flag] for flag in ("--fused", "--backward", "--heads", "--gat", "--bf16", "--bias", "--dropout", "--gat-dropout", "--gat-bf16", "--gatv2",
-                                        "--gatv2-dropout"))
+    (fused_only, backward_only, heads_only, gat_only, bf16_only, bias_only, dropout_only, gat_dropout_only, gat_bf16_only, gatv2_only, gatv2_dropout_only,
+     gat_edge_only) = (args[:1] == [flag] for flag in ("--fused", "--backward", "--heads", "--gat", "--bf16", "--bias", "--dropout", "--gat-dropout",
+                                                       "--gat-bf16", "--gatv2", "--gatv2-dropout", "--gat-edge"))
     only = (fused_only or backward_only or heads_only or gat_only or bf16_only or bias_only or dropout_only or gat_dropout_only or gat_bf16_only or gatv2_only
-            or gatv2_dropout_only)
+            or gatv2_dropout_only or gat_edge_only)
     if only:
         args = args[1:]
     else:
@@ -696,6 +773,8 @@ def main():
                 say(f"{name} gatv2: the torch composition ran out of device memory")
         if gatv2_dropout_only or not only:
             probe_gatv2_dropout(name, a)
+        if gat_edge_only or not only:
+            probe_gat_edge(name, a)
     with open(out, "a" if only else "w") as f:  # a part is appended, the whole run starts the file
         f.write("\n".join(LINES) + "\n")
 
