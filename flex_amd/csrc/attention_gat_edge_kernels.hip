@@ -3,6 +3,7 @@
 // (alpha_dst + alpha_src + alpha_edge), with and without dropout of the probabilities, in the one forward launch and the row launch of
 // the backward of the GAT calls, on the same plans, walk and grid.  tests/test_gpu_gat_edge.py covers it, and tests/test_gat_edge_host.py
 // holds every instantiation to a case that launches it.
+// tests/test_gpu_gat_edge_walks.py runs both kernels' own loop over a group's items, class pick and remap above the floor group budget.
 //
 // The sweeps are attention_gat_device.h's under their compile-time EDGE switch, with DROP off and on: the forward loads ee[e, head]
 // with the pass's er loads and V gathers (the lanes of a head share the address; a dropped entry's term is read all the same, it stays
