@@ -107,6 +107,8 @@ static int load_records(const flex_plan *p, const std::vector<uint32_t> &t_beg, 
         if (static_cast<uint64_t>(c.x) + c.y > p->n_tasks || c.z != t_beg[c.x] || c.w != t_beg[c.x + c.y] || c.z > c.w || c.w > n_rec) return FLEX_ERR_FORMAT;
         if (ce.y & kChunkWide) {
             if (ce.y != kChunkWide || ce.x != wide_used || wide_used + (c.w - c.z) > wide.size()) return FLEX_ERR_FORMAT;
+            // a wide chunk's records start at a whole step of `rec` as well: the kernels stage them with 16-byte loads (stage_n)
+            if (ce.x % (64u / static_cast<uint32_t>(p->lanes_per_nz)) != 0) return FLEX_ERR_FORMAT;
             std::copy(wide.begin() + static_cast<ptrdiff_t>(wide_used), wide.begin() + static_cast<ptrdiff_t>(wide_used + (c.w - c.z)), rec.begin() + c.z);
             wide_used += c.w - c.z;
             continue;
@@ -529,6 +531,11 @@ int flex_plan_self_check(const flex_plan *p) try {
     if (t_beg[0] != 0 || t_beg[p->n_tasks] != n_rec) return FLEX_ERR_FORMAT;
     for (uint32_t t = 0; t < p->n_tasks; ++t)
         if (t_beg[t] > t_beg[t + 1]) return FLEX_ERR_FORMAT;
+    // ... in whole steps: every task, hence every chunk and every record window, starts at a multiple of S = 64 / G records.  The
+    // staging step relies on it (spmm_device.h): its 16-byte loads of two 8-byte records, and the pair loads of the packed stream,
+    // are aligned because a window starts at an even record on every tile of two or more slots.
+    for (uint32_t t = 0; t <= p->n_tasks; ++t)
+        if (t_beg[t] % (64u / static_cast<uint32_t>(p->lanes_per_nz)) != 0) return FLEX_ERR_FORMAT;
     // chunks tile the tasks (in table order, skipping the empty padding entries), each within the kernel's limits
     // ... and a chunk's bundles name consecutive groups of S entries of ITS part of bd_rows (what the wave holds in two registers per
     // lane), each bundle's records are its steps x S, and the parts of the chunks tile bd_rows

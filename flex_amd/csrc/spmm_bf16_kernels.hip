@@ -125,36 +125,25 @@ __device__ __forceinline__ void compute_chunk_bf16(const PlanView &p, const Chun
         const uint32_t nsteps = wn / S;  // rows are padded to multiples of S
         const uint2 *lds_slot = my_lds + slot;
         uint32_t j = 0;
-        for (; j + U <= nsteps; j += U) {  // full blocks: no bound checks in the instruction stream
-            uint2 r[U];
-            float4 b[U];
+        // N steps from step j on: N LDS reads, N gathers back to back, then the sums in record order with the row-end test per step
+        auto block = [&](auto n) {
+            constexpr int N = decltype(n)::value;
+            uint2 r[N];
+            float4 b[N];
 #pragma unroll
-            for (int u = 0; u < U; ++u) r[u] = lds_slot[(j + u) * S];
+            for (int u = 0; u < N; ++u) r[u] = lds_slot[(j + u) * S];
 #pragma unroll
-            for (int u = 0; u < U; ++u) b[u] = gather4<OFF32>(Bb, r[u].x, lane_off, row_bytes);
+            for (int u = 0; u < N; ++u) b[u] = gather4<OFF32>(Bb, r[u].x, lane_off, row_bytes);
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
+            for (int u = 0; u < N; ++u) {
                 fma8(acc, as_f32(r[u].y), b[u]);
                 pos += S;
                 if (pos == row_end) flush(pos);
             }
-        }
-        if (j < nsteps) {  // the window's last, partial block
-            uint2 r[U];
-            float4 b[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) r[u] = lds_slot[min(j + u, nsteps - 1) * S];
-#pragma unroll
-            for (int u = 0; u < U; ++u) b[u] = gather4<OFF32>(Bb, r[u].x, lane_off, row_bytes);
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                if (j + u < nsteps) {  // wave-uniform
-                    fma8(acc, as_f32(r[u].y), b[u]);
-                    pos += S;
-                    if (pos == row_end) flush(pos);
-                }
-            }
-        }
+        };
+        for (; j + U <= nsteps; j += U) block(std::integral_constant<int, U>{});  // full blocks: no bound checks in the instruction stream
+        // the window's last, partial block: a wave-uniform case per number of steps left, so no gather fetches a line twice
+        if (j < nsteps) tail_cases<1, U>(nsteps - j, block);
     }
 }
 

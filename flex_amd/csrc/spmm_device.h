@@ -3,6 +3,8 @@
 // table.  Used by spmm_kernels.hip (fp32: spmm_flat_kernel) and spmm_bf16_kernels.hip (bf16 B and C: spmm_flat_bf16_kernel), which
 // walk a chunk in the same way and differ in what a gathered word holds and in how a finished row is stored.
 #pragma once
+#include <type_traits>
+
 #include "internal.h"
 
 namespace flex {
@@ -126,11 +128,24 @@ constexpr bool kTileHasBundles = 64 / G >= static_cast<int>(kBundleMinSlots);
 
 // One chunk = tasks [w_task[c], w_task[c+1]) = one contiguous run of the record stream.
 
-// Stage records [wz, wz+wn) of the stream into the wave's LDS slice: coalesced 512-B loads, lane l takes
-// records l, l+64, l+128, l+192.  Indices are clamped, not predicated (slots >= wn get a copy of the last
-// record and are never read), and the short-window case is a wave-uniform branch: every load is consumed
-// inside its branch, so (a) a long window has its four loads in flight together instead of four round
-// trips and (b) no pending load survives into the gather loop, where the compiler would otherwise put an
+// The last, partial block of a window's steps: f(integral_constant<N>) for N = left, 1 <= left < U.  `left` is wave-uniform, so this
+// is a short chain of scalar compares in front of U - 1 straight-line bodies, each with exactly N LDS reads and N gathers.
+template <int N, int U, class F>
+__device__ __forceinline__ void tail_cases(uint32_t left, F &f) {
+    if constexpr (N + 1 < U) {
+        if (left == N) f(std::integral_constant<int, N>{});
+        else tail_cases<N + 1, U>(left, f);
+    } else {
+        f(std::integral_constant<int, N>{});
+    }
+}
+
+// Stage records [wz, wz+wn) of the stream into the wave's LDS slice: coalesced loads, lane l takes records
+// 2 l and 2 l + 1 of every 128 (16 bytes; the one-slot tile: record l of every 64, 8 bytes).  Indices are
+// clamped, not predicated (slots >= wn get a copy of the last load's worth and are never read), and the
+// short-window case is a wave-uniform branch: every load is consumed
+// inside its branch, so (a) a long window has all its loads (two or four) in flight together instead of
+// one round trip each and (b) no pending load survives into the gather loop, where the compiler would otherwise put an
 // s_waitcnt vmcnt(0) at the loop head.
 typedef uint32_t v2u __attribute__((ext_vector_type(2)));
 template <bool NT>
@@ -143,24 +158,46 @@ __device__ __forceinline__ uint2 load_rec(const uint2 *ptr) {
     }
 }
 
-template <bool NT, int LOADS>
+// TWO (tiles of two or more slots per step: rows are padded to whole steps, so every window starts at an even record and holds an even
+// number): a lane takes two consecutive records per load -- 16 bytes, one ds_write_b128 -- and a window costs half the loads; the LDS
+// image is the same.  Non-temporal loads below 16 bytes run at 0.54-0.70x the 16-byte rate (MI355X_MICROARCH.md, visibility table).
+template <bool NT>
+__device__ __forceinline__ uint4 load_rec2(const uint4 *ptr) {
+    if constexpr (NT) {
+        const v4u v = __builtin_nontemporal_load(reinterpret_cast<const v4u *>(ptr));
+        return make_uint4(v.x, v.y, v.z, v.w);
+    } else {
+        return *ptr;
+    }
+}
+
+template <bool NT, bool TWO, int LOADS>
 __device__ __forceinline__ void stage_n(uint2 *my_lds, const uint2 *__restrict__ rec, uint32_t wz, uint32_t wn, int lane) {
-    uint2 r[LOADS];
+    if constexpr (TWO) {
+        uint4 r[LOADS];
 #pragma unroll
-    for (int i = 0; i < LOADS; ++i) r[i] = load_rec<NT>(rec + wz + min(static_cast<uint32_t>(i * 64 + lane), wn - 1));
+        for (int i = 0; i < LOADS; ++i) r[i] = load_rec2<NT>(reinterpret_cast<const uint4 *>(rec + wz) + min(static_cast<uint32_t>(i * 64 + lane), wn / 2 - 1));
 #pragma unroll
-    for (int i = 0; i < LOADS; ++i) my_lds[i * 64 + lane] = r[i];
+        for (int i = 0; i < LOADS; ++i) *reinterpret_cast<uint4 *>(my_lds + 2 * (i * 64 + lane)) = r[i];
+    } else {
+        uint2 r[LOADS];
+#pragma unroll
+        for (int i = 0; i < LOADS; ++i) r[i] = load_rec<NT>(rec + wz + min(static_cast<uint32_t>(i * 64 + lane), wn - 1));
+#pragma unroll
+        for (int i = 0; i < LOADS; ++i) my_lds[i * 64 + lane] = r[i];
+    }
 }
 
 template <bool NT, int G>
 __device__ __forceinline__ void stage_window_t(uint2 *my_lds, const uint2 *__restrict__ rec, uint32_t wz, uint32_t wn, int lane) {
-    if (wn <= 64) {
-        stage_n<NT, 1>(my_lds, rec, wz, wn, lane);
-    } else if constexpr (kWindowRecs<G> > 256) {
-        if (wn <= 256) stage_n<NT, 4>(my_lds, rec, wz, wn, lane);
-        else stage_n<NT, kWindowRecs<G> / 64>(my_lds, rec, wz, wn, lane);
-    } else {
-        stage_n<NT, 4>(my_lds, rec, wz, wn, lane);
+    if constexpr (64 / G >= 2) {  // 128 records per load of the wave
+        constexpr int FULL = kWindowRecs<G> / 128;
+        if (wn <= 128) stage_n<NT, true, 1>(my_lds, rec, wz, wn, lane);
+        else if (FULL > 2 && wn <= 256) stage_n<NT, true, 2>(my_lds, rec, wz, wn, lane);
+        else stage_n<NT, true, FULL>(my_lds, rec, wz, wn, lane);
+    } else {  // the one-slot tile: a window may start at an odd record
+        if (wn <= 64) stage_n<NT, false, 1>(my_lds, rec, wz, wn, lane);
+        else stage_n<NT, false, kWindowRecs<G> / 64>(my_lds, rec, wz, wn, lane);
     }
 }
 
@@ -188,6 +225,10 @@ __device__ __forceinline__ void stage_window(uint2 *my_lds, const uint2 *__restr
 // PAIR (tiles of two or more slots per step: every task, hence every window, starts at an even record): a lane takes two
 // consecutive records per load -- 8 bytes of values, 4 of differences, one 16-byte LDS write -- so a window costs as many loads as
 // it did at 8 bytes per record.  The one-slot tile (G = 64) may start at an odd record and loads record by record.
+// (Four values and four or eight differences per lane and load -- 16-byte loads, 3 per 512-record window instead of 8 -- measured
+// SLOWER on the Amazon preset, 8.21 against 7.83 ms -- DESIGN.md 3.4 "what a window carries", profiles/record_staging_ab_series.json,
+// `parts`: a lane that loads four or eight consecutive records writes them to LDS at a 32- or 64-byte lane stride.  The pair form
+// stays on every tile.)
 template <bool NT, class T>
 __device__ __forceinline__ T load_stream(const T *ptr) {
     if constexpr (NT) return __builtin_nontemporal_load(ptr);
@@ -238,6 +279,14 @@ __device__ __forceinline__ void stage_packed_t(uint2 *my_lds, const float *__res
     else stage_packed_n<NT, PAIR, FULL>(my_lds, val, dcol, wn, lane, vv);
 }
 
+// x of lane `from` (mod 64).  __shfl and its kin form their index from the hardware lane id, a loop invariant the compiler keeps in
+// registers across the gather loop -- one per shuffle distance; this one takes the caller's `lane`, which stage_window_packed makes anew
+// per window.  A register-allocation measure, checked against the compiler in use with `make asm` (the register
+// table), like the empty asm statements around it: another compiler version may not need it, or may need more.
+__device__ __forceinline__ uint32_t lane_read(uint32_t x, int from) {
+    return static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute((from & 63) << 2, static_cast<int>(x)));
+}
+
 template <int G, bool OFF32>
 __device__ __forceinline__ uint32_t stage_window_packed(const PlanView &p, uint2 *my_lds, uint32_t zb, uint32_t wz, uint32_t wn, uint2 cx,
                                                         uint32_t t0, uint32_t nt, uint32_t my_beg, uint32_t carry, uint32_t row_bytes32, int lane) {
@@ -257,9 +306,13 @@ __device__ __forceinline__ uint32_t stage_window_packed(const PlanView &p, uint2
     }
     if (lane == 0) my_lds[0].x += carry;
     // task starts: lane i holds t_beg[t0 + i] (i <= nt); an empty task starts where its successor does and owns no record
-    const uint32_t next_beg = __shfl_down(my_beg, 1);
+    const uint32_t next_beg = lane_read(my_beg, lane == 63 ? lane : lane + 1);
     const uint32_t at = my_beg - wz;
-    if (static_cast<uint32_t>(lane) < nt && next_beg != my_beg && at < wn) my_lds[at] = make_uint2(p.t_col0[t0 + lane], 1u);
+    if (static_cast<uint32_t>(lane) < nt && next_beg != my_beg && at < wn) {
+        uint32_t flag = 1u;  // made here: as a loop invariant the constant takes a register, or a scratch slot, across the gather loop
+        asm volatile("" : "+v"(flag));
+        my_lds[at] = make_uint2(p.t_col0[t0 + lane], flag);
+    }
     __builtin_amdgcn_wave_barrier();
     // the lane's R words, serially from 0
     uint32_t w[R], fbits = 0;
@@ -286,13 +339,13 @@ __device__ __forceinline__ uint32_t stage_window_packed(const PlanView &p, uint2
     uint32_t inc = run;
 #pragma unroll
     for (int dlt = 1; dlt < 64; dlt <<= 1) {
-        const uint32_t up = __shfl_up(inc, dlt);
+        const uint32_t up = lane_read(inc, lane - dlt);  // lanes below dlt read a lane they do not use
         if (lane >= dlt) inc += up;
     }
     const uint32_t exc_sum = inc - run;  // E[lane]
     const uint64_t below = __builtin_amdgcn_ballot_w64(fbits != 0) & ((uint64_t(1) << lane) - 1u);
     const int q = below ? 63 - __builtin_clzll(below) : 0;
-    const uint32_t e_q = __shfl(exc_sum, q);
+    const uint32_t e_q = lane_read(exc_sum, q);
     const uint32_t enter = below ? exc_sum - e_q : exc_sum;
     uint32_t last = 0;
 #pragma unroll
@@ -335,12 +388,12 @@ __device__ __forceinline__ bool place_of_wave(const PlanView &p, uint32_t wib, u
 }
 
 // What a wave holds of its chunk before the first record: the header {first task, #tasks, first record, end record}, the packed plan's
-// exception table entry, and -- lane i -- the descriptors of task i.
+// exception table entry, and -- lane i -- the descriptors of task i (t_aux is not among them: only the fp32 kernel's in-launch piece
+// sum reads it, and fetches it there).
 struct ChunkRegs {
     uint4 hdr;
     uint2 cx;
     uint32_t my_beg, my_dst;
-    uint2 my_aux;
     uint32_t my_bd0, my_bd1;
 };
 
@@ -362,7 +415,6 @@ __device__ __forceinline__ bool load_chunk(const PlanView &p, uint32_t chunk, in
     if (hdr.y == 0) return false;
     d.my_beg = (static_cast<uint32_t>(lane) <= hdr.y) ? p.t_beg[hdr.x + lane] : 0u;
     d.my_dst = (static_cast<uint32_t>(lane) < hdr.y) ? p.t_dst[hdr.x + lane] : 0u;
-    d.my_aux = (static_cast<uint32_t>(lane) < hdr.y) ? p.t_aux[hdr.x + lane] : make_uint2(0u, 0u);  // read at chunk end only
     d.my_bd0 = d.my_bd1 = kBundleNoRow;
     if (kTileHasBundles<G> && cb.y != 0) {  // uniform
         if (static_cast<uint32_t>(lane) < cb.y) d.my_bd0 = p.bd_rows[cb.x + lane];

@@ -136,7 +136,7 @@ __device__ __forceinline__ void wait_loads(v4f (&v)[N]) {
 // All the work of one chunk once its header {first task, #tasks, first record, end record} and its
 // task descriptors (lane i: t_beg[t0+i], t_dst[t0+i]) are in registers.
 template <int G, bool OFF32, int U>
-__device__ __forceinline__ void compute_chunk(const PlanView &p, uint4 hdr, uint32_t my_beg, uint32_t my_dst, uint2 my_aux,
+__device__ __forceinline__ void compute_chunk(const PlanView &p, uint4 hdr, uint32_t my_beg, uint32_t my_dst,
                                               uint32_t my_bd0, uint32_t my_bd1, uint2 cx, uint2 *my_lds, const char *__restrict__ Bb,
                                               float *__restrict__ C, int lane, int c0, bool col_ok, uint32_t tile, uint32_t ktiles) {
     constexpr int S = 64 / G;
@@ -215,42 +215,32 @@ __device__ __forceinline__ void compute_chunk(const PlanView &p, uint4 hdr, uint
     uint32_t pos = zb;  // stream position after the steps consumed so far
     for (uint32_t wz = zb; wz < ze; wz += kWindowRecs<G>) {
         const uint32_t wn = min(static_cast<uint32_t>(kWindowRecs<G>), ze - wz);
-        // stage this window's records: coalesced 512-B loads, one ds_write_b64 per lane and load
+        // stage this window's records: coalesced loads of two records per lane (1 KiB per wave load, one ds_write_b128 each; the
+        // one-slot tile and the packed stream: spmm_device.h)
         if (packed_chunk) carry = stage_window_packed<G, OFF32>(p, my_lds, zb, wz, wn, cx, hdr.x, nt, my_beg, carry, static_cast<uint32_t>(row_bytes), lane);
         else stage_window<G>(my_lds, rec, wz, wn, lane, p.rec_nt != 0);
         const uint32_t nsteps = wn / S;  // rows are padded to multiples of S
         const uint2 *lds_slot = my_lds + slot;
         uint32_t j = 0;
-        for (; j + U <= nsteps; j += U) {  // full blocks: no bound checks in the instruction stream
-            uint2 r[U];
-            float4 b[U];
+        // N steps from step j on: N LDS reads, N gathers back to back, then the sums in record order with the row-end test per step
+        auto block = [&](auto n) {
+            constexpr int N = decltype(n)::value;
+            uint2 r[N];
+            float4 b[N];
 #pragma unroll
-            for (int u = 0; u < U; ++u) r[u] = lds_slot[(j + u) * S];
+            for (int u = 0; u < N; ++u) r[u] = lds_slot[(j + u) * S];
 #pragma unroll
-            for (int u = 0; u < U; ++u) b[u] = gather4<OFF32>(Bb, r[u].x, lane_off, row_bytes);
+            for (int u = 0; u < N; ++u) b[u] = gather4<OFF32>(Bb, r[u].x, lane_off, row_bytes);
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
+            for (int u = 0; u < N; ++u) {
                 fma4(acc, as_f32(r[u].y), b[u]);
                 pos += S;
                 if (pos == row_end) flush(pos);
             }
-        }
-        if (j < nsteps) {  // the window's last, partial block
-            uint2 r[U];
-            float4 b[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) r[u] = lds_slot[min(j + u, nsteps - 1) * S];
-#pragma unroll
-            for (int u = 0; u < U; ++u) b[u] = gather4<OFF32>(Bb, r[u].x, lane_off, row_bytes);
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                if (j + u < nsteps) {  // wave-uniform
-                    fma4(acc, as_f32(r[u].y), b[u]);
-                    pos += S;
-                    if (pos == row_end) flush(pos);
-                }
-            }
-        }
+        };
+        for (; j + U <= nsteps; j += U) block(std::integral_constant<int, U>{});  // full blocks: no bound checks in the instruction stream
+        // the window's last, partial block: a wave-uniform case per number of steps left, so no gather fetches a line twice
+        if (j < nsteps) tail_cases<1, U>(nsteps - j, block);
     }
     // Pieces are combined INSIDE this launch by whichever piece arrives last (cdna guide G16, counter form with
     // write-through payload): (1) every partial sum of this chunk was stored write-through (sc1), so it is at
@@ -270,6 +260,9 @@ __device__ __forceinline__ void compute_chunk(const PlanView &p, uint4 hdr, uint
     // launch of a plan at a time (include/flex_spmm.h, flex_spmm).
     const bool mine_partial = static_cast<uint32_t>(lane) < nt && (my_dst & (kPartialFlag | kBundleFlag)) == kPartialFlag;
     if (p.fused_fixup && __builtin_amdgcn_ballot_w64(mine_partial) != 0) {  // wave-uniform
+        // t_aux is read here and nowhere else: fetched now, under the drain of the stores, not with the chunk's other descriptors --
+        // the two-launch form never loads it, and no register holds it across the gather loops
+        const uint2 my_aux = mine_partial ? p.t_aux[hdr.x + lane] : make_uint2(0u, 0u);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         uint32_t arrived = 0;
         if (mine_partial)
@@ -377,7 +370,6 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(U == (
     if (hdr.y == 0) return;  // an empty entry that pads this XCD's slice of the table (plan_build.cpp, build_chunk_table)
     const uint32_t my_beg = (static_cast<uint32_t>(lane) <= hdr.y) ? p.t_beg[hdr.x + lane] : 0u;
     const uint32_t my_dst = (static_cast<uint32_t>(lane) < hdr.y) ? p.t_dst[hdr.x + lane] : 0u;
-    const uint2 my_aux = (static_cast<uint32_t>(lane) < hdr.y) ? p.t_aux[hdr.x + lane] : make_uint2(0u, 0u);  // read at chunk end only
     uint32_t my_bd0 = kBundleNoRow, my_bd1 = kBundleNoRow;
     if (kTileHasBundles<G> && cb.y != 0) {  // uniform
         if (static_cast<uint32_t>(lane) < cb.y) my_bd0 = p.bd_rows[cb.x + lane];
@@ -385,7 +377,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(U == (
     }
     uint64_t stamp_t0 = 0;
     if constexpr (STAMP) stamp_t0 = __builtin_amdgcn_s_memrealtime();
-    compute_chunk<G, OFF32, U>(p, hdr, my_beg, my_dst, my_aux, my_bd0, my_bd1, cx, lds_rec[wib], reinterpret_cast<const char *>(B), C, lane, c0, col_ok, tile, ktiles);
+    compute_chunk<G, OFF32, U>(p, hdr, my_beg, my_dst, my_bd0, my_bd1, cx, lds_rec[wib], reinterpret_cast<const char *>(B), C, lane, c0, col_ok, tile, ktiles);
     if constexpr (STAMP) {
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // the wave's last stores have left
         const uint64_t stamp_t1 = __builtin_amdgcn_s_memrealtime();
@@ -488,9 +480,8 @@ __global__ __launch_bounds__(256) void spmm_generic_kernel(PlanView p, const flo
 // C[row,:] = partial[first,:] + partial[first+1,:] + ... in that fixed order.  Eight pieces are
 // loaded before the first add so the (tiny) kernel costs a couple of memory round trips, not
 // one per piece; the adds stay strictly in piece order, so the result is reproducible.
-__global__ __launch_bounds__(256) void spmm_fixup_kernel(const float *__restrict__ partial,
-                                                         const SplitRow *__restrict__ rows, uint32_t n_rows,
-                                                         int k, int ldc, float *__restrict__ C) {
+__device__ __forceinline__ void fixup_scalar(const float *__restrict__ partial, const SplitRow *__restrict__ rows, uint32_t n_rows,
+                                             int k, int ldc, float *__restrict__ C) {
     const int lane = threadIdx.x & 63;
     const uint32_t wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t i = blockIdx.x * kWavesPerBlock + wib;
@@ -515,6 +506,58 @@ __global__ __launch_bounds__(256) void spmm_fixup_kernel(const float *__restrict
             if (j + u < sr.count) s += v[u];
         C[static_cast<uint64_t>(sr.row) * ldc + c] = s;
     }
+}
+
+// The same sums with 16-byte loads and stores (k % 4 == 0, partial and the rows of C 16-byte aligned): a lane owns 4 adjacent columns,
+// a row takes lanes_per_row = min(k / 4, 64) lanes, and rows_per_wave = 64 / lanes_per_row rows share a wave (k = 128: two, k = 32:
+// eight), each with its own piece count -- the loops diverge between rows of a wave, not inside a row.  Eight pieces in flight before
+// the first add; every column starts from 0.f and adds its pieces strictly in piece order, as the scalar form does: the same bits.
+__device__ __forceinline__ void fixup_vec4(const float *__restrict__ partial, const SplitRow *__restrict__ rows, uint32_t n_rows, int k,
+                                           int ldc, float *__restrict__ C, uint32_t lanes_per_row, uint32_t rows_per_wave) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const uint32_t sub = lane / lanes_per_row;
+    const uint32_t i = wave * rows_per_wave + sub;
+    if (sub >= rows_per_wave || i >= n_rows) return;
+    const SplitRow sr = rows[i];
+    for (uint32_t c = (lane - sub * lanes_per_row) * 4u; c < static_cast<uint32_t>(k); c += lanes_per_row * 4u) {
+        const float *p = partial + static_cast<uint64_t>(sr.first) * k + c;
+        float4 s = {0.f, 0.f, 0.f, 0.f};
+        uint32_t j = 0;
+        for (; j + 8 <= sr.count; j += 8) {
+            float4 v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const float4 *>(p + static_cast<uint64_t>(j + u) * k);
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                s.x += v[u].x;
+                s.y += v[u].y;
+                s.z += v[u].z;
+                s.w += v[u].w;
+            }
+        }
+        float4 v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            v[u] = (j + u < sr.count) ? *reinterpret_cast<const float4 *>(p + static_cast<uint64_t>(j + u) * k) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            if (j + u < sr.count) {
+                s.x += v[u].x;
+                s.y += v[u].y;
+                s.z += v[u].z;
+                s.w += v[u].w;
+            }
+        *reinterpret_cast<float4 *>(C + static_cast<uint64_t>(sr.row) * ldc + c) = s;
+    }
+}
+
+// lanes_per_row = 0: the scalar form (launch_fixup decides; uniform over the launch)
+__global__ __launch_bounds__(256) void spmm_fixup_kernel(const float *__restrict__ partial, const SplitRow *__restrict__ rows, uint32_t n_rows,
+                                                         int k, int ldc, float *__restrict__ C, uint32_t lanes_per_row,
+                                                         uint32_t rows_per_wave) {
+    if (lanes_per_row != 0) fixup_vec4(partial, rows, n_rows, k, ldc, C, lanes_per_row, rows_per_wave);
+    else fixup_scalar(partial, rows, n_rows, k, ldc, C);
 }
 
 // dst[r,:] = src[idx[r],:]  (≙ flexspmm_v9_permuteX, flex.cu:276-289)
@@ -638,8 +681,12 @@ int kernel_attributes(int lanes_per_nz, bool off32, bool vec4, hipFuncAttributes
 
 int launch_fixup(const float *partial, const SplitRow *rows, uint32_t n_rows, int k, int ldc, float *dC, hipStream_t s) {
     if (n_rows == 0) return FLEX_OK;
-    const uint32_t nblk = (n_rows + kWavesPerBlock - 1) / kWavesPerBlock;
-    hipLaunchKernelGGL(spmm_fixup_kernel, dim3(nblk), dim3(256), 0, s, partial, rows, n_rows, k, ldc, dC);
+    const bool vec4 = k >= 4 && k % 4 == 0 && ldc % 4 == 0 && (reinterpret_cast<uintptr_t>(partial) | reinterpret_cast<uintptr_t>(dC)) % 16 == 0;
+    // the float4 form: a row on min(k / 4, 64) lanes, the wave's other lanes on further rows
+    const uint32_t lanes_per_row = !vec4 ? 0u : k / 4 < 64 ? static_cast<uint32_t>(k / 4) : 64u, rows_per_wave = vec4 ? 64u / lanes_per_row : 1u;
+    const uint32_t nwaves = (n_rows + rows_per_wave - 1) / rows_per_wave;
+    hipLaunchKernelGGL(spmm_fixup_kernel, dim3((nwaves + kWavesPerBlock - 1) / kWavesPerBlock), dim3(256), 0, s, partial, rows, n_rows, k, ldc,
+                       dC, lanes_per_row, rows_per_wave);
     FLEX_HIP_TRY(hipGetLastError());
     return FLEX_OK;
 }
