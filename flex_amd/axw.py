@@ -10,6 +10,7 @@ from . import binding
 FLEX_AXW_AUTO, FLEX_AXW_A_XW, FLEX_AXW_AX_W = 0, 1, 2
 FLEX_AXW_USE_BLAS = 0x10000  # flex_axw_create flag: rocBLAS for the dense half
 FLEX_AXW_BACKWARD = 0x20000  # flex_axw_create flag: plan A^T too, for flex_axw_backward
+FLEX_AXW_BF16 = 0x200000  # flex_axw_create flag: the bf16 layer (flex_axw_run_bf16), forward only
 _lib = None
 
 
@@ -29,6 +30,10 @@ def lib():
         L.flex_axw_ld.argtypes = [C.c_int]
         L.flex_axw_gemm_launch.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
         L.flex_axw_gemm_launch.restype = C.c_int
+        L.flex_axw_run_bf16.argtypes = L.flex_axw_run.argtypes
+        L.flex_axw_ld_bf16.argtypes = [C.c_int]
+        L.flex_axw_gemm_bf16_launch.argtypes = L.flex_axw_gemm_launch.argtypes
+        L.flex_axw_gemm_bf16_launch.restype = C.c_int
         _lib = L
     return _lib
 
@@ -39,36 +44,49 @@ def _gemm_launch(L_ptr: int, Wp_ptr: int, Out_ptr: int, n: int, dim: int, c: int
     return lib().flex_axw_gemm_launch(L_ptr, Wp_ptr, Out_ptr, n, dim, c, cp, n_cus, stream)
 
 
+def _gemm_bf16_launch(L_ptr: int, Wp_ptr: int, Out_ptr: int, n: int, dim: int, c: int, cp: int, n_cus: int, stream: int = 0) -> int:
+    """The bf16 MFMA GEMM of the bf16 layer on its own (flex_axw_gemm_bf16_launch, exported like flex_axw_gemm_launch): bf16
+    Out[n x cp] = L[n x dim] @ Wp[dim x cp] with fp32 sums, columns >= c written as +0 bits.  Returns the hipError_t; for tests."""
+    return lib().flex_axw_gemm_bf16_launch(L_ptr, Wp_ptr, Out_ptr, n, dim, c, cp, n_cus, stream)
+
+
 class Axw:
     """flex_axw handle: plans A for both SpMM widths once; run() computes A @ X @ W in either order."""
 
     def __init__(self, a: binding.HostCsr, dim: int, c: int, device: int = 0, order: int = binding.FLEX_ORDER_CLUSTER,
-                 backward: bool = False):
-        """backward: also plan A^T (FLEX_AXW_BACKWARD), for backward() and layer()."""
+                 backward: bool = False, bf16: bool = False):
+        """backward: also plan A^T (FLEX_AXW_BACKWARD), for backward() and layer().  bf16: the bf16 layer (FLEX_AXW_BF16): run() takes and
+        returns torch.bfloat16; forward only (dim % 16 == 0, dim and c <= 256, n >= 32)."""
         self._h = C.c_void_p()
         v = a.view()
-        flags = order | (FLEX_AXW_BACKWARD if backward else 0)
+        flags = order | (FLEX_AXW_BACKWARD if backward else 0) | (FLEX_AXW_BF16 if bf16 else 0)
         binding._check(lib().flex_axw_create(C.byref(self._h), C.byref(v), dim, c, device, flags), "flex_axw_create")
-        self.n, self.dim, self.c, self.ld = a.n, dim, c, lib().flex_axw_ld(c)
+        self.n, self.dim, self.c, self.ld = a.n, dim, c, (lib().flex_axw_ld_bf16(c) if bf16 else lib().flex_axw_ld(c))
         self.has_backward = backward
+        self.bf16 = bf16
 
     def run(self, X, W, order: int = FLEX_AXW_AUTO, timed: bool = False):
-        """X [n, dim], W [dim, c]: contiguous float32 cuda tensors.  Returns Out [n, ld] (columns >= c are zero)
-        and, if timed, (gemm_ms, spmm_ms)."""
+        """X [n, dim], W [dim, c]: contiguous cuda tensors, float32 -- torch.bfloat16 on a bf16 handle (any other dtype: TypeError).
+        Returns Out [n, ld] of that dtype (columns >= c are zero) and, if timed, (gemm_ms, spmm_ms)."""
         import torch
-        assert X.is_cuda and W.is_cuda and X.dtype == W.dtype == torch.float32 and X.is_contiguous() and W.is_contiguous()
+        want = torch.bfloat16 if self.bf16 else torch.float32
+        if X.dtype != want or W.dtype != want:
+            raise TypeError(f"Axw.run: this handle takes {want} X and W; got {X.dtype} and {W.dtype}")
+        assert X.is_cuda and W.is_cuda and X.is_contiguous() and W.is_contiguous()
         assert tuple(X.shape) == (self.n, self.dim) and tuple(W.shape) == (self.dim, self.c)
-        out = torch.empty((self.n, self.ld), dtype=torch.float32, device=X.device)
+        out = torch.empty((self.n, self.ld), dtype=want, device=X.device)
         g, s = C.c_float(), C.c_float()
-        binding._check(lib().flex_axw_run(self._h, order, X.data_ptr(), W.data_ptr(), out.data_ptr(),
-                                          torch.cuda.current_stream(X.device).cuda_stream,
-                                          C.byref(g) if timed else None, C.byref(s) if timed else None), "flex_axw_run")
+        call, what = (lib().flex_axw_run_bf16, "flex_axw_run_bf16") if self.bf16 else (lib().flex_axw_run, "flex_axw_run")
+        binding._check(call(self._h, order, X.data_ptr(), W.data_ptr(), out.data_ptr(), torch.cuda.current_stream(X.device).cuda_stream,
+                            C.byref(g) if timed else None, C.byref(s) if timed else None), what)
         return (out, (g.value, s.value)) if timed else out
 
     def backward(self, dOut, X, W, need_x: bool = True, need_w: bool = True):
         """flex_axw_backward: dOut [n, ld] (its padding columns are never read) -> (dX [n, dim] or None, dW [dim, c] or None),
         dX = A^T dOut W^T and dW = X^T (A^T dOut).  X and W are the forward's inputs (only the ones a requested gradient needs)."""
         import torch
+        if self.bf16:
+            raise binding.FlexError("Axw.backward: the bf16 layer (bf16=True, FLEX_AXW_BF16) is forward only: it has no backward yet")
         if not self.has_backward:
             raise binding.FlexError("Axw.backward: the handle was made without backward=True (FLEX_AXW_BACKWARD)")
         assert dOut.is_cuda and dOut.dtype == torch.float32 and dOut.is_contiguous() and tuple(dOut.shape) == (self.n, self.ld)
@@ -85,6 +103,8 @@ class Axw:
 
     def layer(self, X, W, order: int = FLEX_AXW_AUTO):
         """Differentiable A X W: Out [n, c] (a view of the padded product); its gradient flows to X and W through backward()."""
+        if self.bf16:
+            raise binding.FlexError("Axw.layer: the bf16 layer (bf16=True, FLEX_AXW_BF16) is forward only: it has no backward yet")
         if not self.has_backward:
             raise binding.FlexError("Axw.layer: the handle was made without backward=True (FLEX_AXW_BACKWARD)")
         from .autograd import functions

@@ -17,12 +17,16 @@ extern "C" hipError_t flex_axw_dw_launch(const float *X, const float *G, float *
                                          hipStream_t s);
 extern "C" hipError_t flex_axw_transpose_launch(const float *W, float *Wt, int dim, int c, int ld, hipStream_t s);
 extern "C" int flex_axw_dw_slices(int n, int n_cus);
+extern "C" hipError_t flex_axw_gemm_bf16_launch(const flex_bf16 *L, const flex_bf16 *Wp, flex_bf16 *Out, int n, int dim, int c, int cp,
+                                                int n_cus, hipStream_t s);  // axw_bf16_kernels.hip
+extern "C" hipError_t flex_axw_bf16_clear_padding_launch(flex_bf16 *Out, int n, int c, int cp, hipStream_t s);
 
 struct flex_axw {
     int32_t n = 0;
     int n_cus = 0;
     bool use_blas = false;  // FLEX_AXW_USE_BLAS in `flags`, or a shape the MFMA kernel does not take (dim % 4 != 0, dim > 256, n < 32)
     bool a_nonfinite = false;  // A holds an inf or NaN: in order A_XW its SpMM turns the zero padding of X*W into NaN
+    bool bf16 = false;  // FLEX_AXW_BF16: FLEX_PLAN_BF16 plans, the three arrays below hold flex_bf16, flex_axw_run_bf16 is the handle's run
     int dim = 0, c = 0, cp = 0, device = 0;
     flex_plan *plan_c = nullptr, *plan_dim = nullptr;
     float *d_xw = nullptr;  // n x cp
@@ -73,6 +77,7 @@ extern "C" {
 // Whole 128-byte lines per row: a B row that starts mid-line costs every gather one extra line
 // (measured, reddit shape: k=100 999 us, k=104 973 us, k=96 646 us, k=128 669 us -- DESIGN.md 3.3).
 int flex_axw_ld(int c) { return c <= 0 ? 0 : (c + 31) / 32 * 32; }
+int flex_axw_ld_bf16(int c) { return c <= 0 ? 0 : (c + 63) / 64 * 64; }  // the same 128 bytes, in 2-byte elements
 int flex_axw_last_blas_status(void) { return g_blas_status; }
 
 int flex_axw_destroy(flex_axw *h) {
@@ -101,31 +106,37 @@ int flex_axw_create(flex_axw **out, const flex_csr *A, int dim, int c, int devic
     if (!out) return FLEX_ERR_INVALID;
     *out = nullptr;
     if (!A || dim <= 0 || c <= 0 || device < 0 || A->m != A->n) return FLEX_ERR_INVALID;
-    if (flags & FLEX_PLAN_BF16) return FLEX_ERR_INVALID;  // the layer is fp32: its plans run flex_spmm
+    if (flags & FLEX_PLAN_BF16) return FLEX_ERR_INVALID;  // the bf16 layer is asked for by FLEX_AXW_BF16, which sets the plans' bit itself
+    const bool bf16 = (flags & FLEX_AXW_BF16) != 0;
+    // the bf16 layer is forward only, has no rocBLAS path and runs the shapes of flex_axw_gemm_bf16_launch
+    if (bf16 && ((flags & (FLEX_AXW_BACKWARD | FLEX_AXW_USE_BLAS)) || dim % 16 != 0 || dim > 256 || c > 256 || A->n < 32)) return FLEX_ERR_UNSUPPORTED;
     flex_axw *h = new (std::nothrow) flex_axw();
     if (!h) return FLEX_ERR_NOMEM;
     h->n = A->n;
     h->dim = dim;
     h->c = c;
-    h->cp = flex_axw_ld(c);
+    h->bf16 = bf16;
+    h->cp = bf16 ? flex_axw_ld_bf16(c) : flex_axw_ld(c);
     h->device = device;
     int prev = -1;
     (void)hipGetDevice(&prev);
     int rc = hip_fail(hipSetDevice(device));
     const bool want_blas = (flags & FLEX_AXW_USE_BLAS) != 0;
     const bool backward = (flags & FLEX_AXW_BACKWARD) != 0;
-    flags &= ~(FLEX_AXW_USE_BLAS | FLEX_AXW_BACKWARD);
+    flags &= ~(FLEX_AXW_USE_BLAS | FLEX_AXW_BACKWARD | FLEX_AXW_BF16);
+    if (bf16) flags |= FLEX_PLAN_BF16;
+    const size_t es = bf16 ? sizeof(flex_bf16) : sizeof(float);  // element size of the intermediates and of Wp
     if (!rc) rc = flex_plan_create(&h->plan_c, A, h->cp, device, flags);
     if (!rc) rc = flex_plan_create(&h->plan_dim, A, dim, device, flags);
     const size_t n1 = static_cast<size_t>(h->n > 0 ? h->n : 1);
-    if (!rc) rc = hip_fail(hipMalloc(reinterpret_cast<void **>(&h->d_xw), n1 * h->cp * sizeof(float)));
-    if (!rc) rc = hip_fail(hipMalloc(reinterpret_cast<void **>(&h->d_ax), n1 * dim * sizeof(float)));
-    if (!rc) rc = hip_fail(hipMalloc(reinterpret_cast<void **>(&h->d_wp), static_cast<size_t>(dim) * h->cp * sizeof(float)));
-    if (!rc) rc = hip_fail(hipMemset(h->d_wp, 0, static_cast<size_t>(dim) * h->cp * sizeof(float)));
-    if (!rc) rc = hip_fail(hipMemset(h->d_xw, 0, n1 * h->cp * sizeof(float)));  // its padding columns stay +0 for good
+    if (!rc) rc = hip_fail(hipMalloc(reinterpret_cast<void **>(&h->d_xw), n1 * h->cp * es));
+    if (!rc) rc = hip_fail(hipMalloc(reinterpret_cast<void **>(&h->d_ax), n1 * dim * es));
+    if (!rc) rc = hip_fail(hipMalloc(reinterpret_cast<void **>(&h->d_wp), static_cast<size_t>(dim) * h->cp * es));
+    if (!rc) rc = hip_fail(hipMemset(h->d_wp, 0, static_cast<size_t>(dim) * h->cp * es));
+    if (!rc) rc = hip_fail(hipMemset(h->d_xw, 0, n1 * h->cp * es));  // its padding columns stay +0 for good
     for (int64_t e = 0; e < A->nnz && !h->a_nonfinite; ++e) h->a_nonfinite = !std::isfinite(A->vals[e]);
     for (int i = 0; i < 3 && !rc; ++i) rc = hip_fail(hipEventCreate(&h->ev[i]));
-    if (!rc && rocblas_create_handle(&h->blas) != rocblas_status_success) rc = FLEX_ERR_UNSUPPORTED;
+    if (!rc && !bf16 && rocblas_create_handle(&h->blas) != rocblas_status_success) rc = FLEX_ERR_UNSUPPORTED;
     if (!rc) {
         hipDeviceProp_t prop;
         rc = hip_fail(hipGetDeviceProperties(&prop, device));
@@ -153,7 +164,7 @@ int flex_axw_create(flex_axw **out, const flex_csr *A, int dim, int c, int devic
 
 int flex_axw_run(flex_axw *h, int order, const float *dX, const float *dW, float *dOut, flex_stream_t stream,
                  float *gemm_ms, float *spmm_ms) {
-    if (!h || !dX || !dW || !dOut || order < FLEX_AXW_AUTO || order > FLEX_AXW_AX_W) return FLEX_ERR_INVALID;
+    if (!h || h->bf16 || !dX || !dW || !dOut || order < FLEX_AXW_AUTO || order > FLEX_AXW_AX_W) return FLEX_ERR_INVALID;
     if (h->n == 0) return FLEX_OK;
     if (order == FLEX_AXW_AUTO) order = h->cp <= h->dim ? FLEX_AXW_A_XW : FLEX_AXW_AX_W;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -178,6 +189,53 @@ int flex_axw_run(flex_axw *h, int order, const float *dX, const float *dW, float
         if (!rc) rc = flex_spmm(h->plan_dim, dX, h->d_ax, stream);
         if (!rc) rc = mark(1);
         if (!rc) rc = gemm_rm(h, h->d_ax, dOut, s);
+        if (!rc) rc = mark(2);
+    }
+    if (!rc && timed) {
+        rc = hip_fail(hipEventSynchronize(h->ev[2]));
+        float a = 0.f, b = 0.f;
+        if (!rc) rc = hip_fail(hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
+        if (!rc) rc = hip_fail(hipEventElapsedTime(&b, h->ev[1], h->ev[2]));
+        const bool gemm_first = order == FLEX_AXW_A_XW;
+        if (gemm_ms) *gemm_ms = gemm_first ? a : b;
+        if (spmm_ms) *spmm_ms = gemm_first ? b : a;
+    }
+    if (cur >= 0 && cur != h->device) (void)hipSetDevice(cur);
+    return rc;
+}
+
+// flex_axw_run on a FLEX_AXW_BF16 handle: the same two stages on flex_bf16, the dense one always axw_bf16_kernels.hip (create refused
+// every shape it does not take), the intermediate rounded to bf16 by the stage that writes it.
+int flex_axw_run_bf16(flex_axw *h, int order, const flex_bf16 *dX, const flex_bf16 *dW, flex_bf16 *dOut, flex_stream_t stream,
+                      float *gemm_ms, float *spmm_ms) {
+    if (!h || !h->bf16 || !dX || !dW || !dOut || order < FLEX_AXW_AUTO || order > FLEX_AXW_AX_W) return FLEX_ERR_INVALID;
+    if ((reinterpret_cast<uintptr_t>(dX) | reinterpret_cast<uintptr_t>(dOut)) & 15) return FLEX_ERR_UNSUPPORTED;
+    if (order == FLEX_AXW_AUTO) order = h->cp <= h->dim ? FLEX_AXW_A_XW : FLEX_AXW_AX_W;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    flex_bf16 *xw = reinterpret_cast<flex_bf16 *>(h->d_xw), *ax = reinterpret_cast<flex_bf16 *>(h->d_ax), *wp = reinterpret_cast<flex_bf16 *>(h->d_wp);
+    int cur = -1;
+    (void)hipGetDevice(&cur);
+    int rc = hip_fail(hipSetDevice(h->device));
+    const bool timed = gemm_ms || spmm_ms;
+    auto mark = [&](int i) { return timed ? hip_fail(hipEventRecord(h->ev[i], s)) : FLEX_OK; };
+    auto gemm = [&](const flex_bf16 *L, flex_bf16 *Cout) {
+        return hip_fail(flex_axw_gemm_bf16_launch(L, wp, Cout, h->n, h->dim, h->c, h->cp, h->n_cus, s));
+    };
+    // W -> Wp: dim rows of c elements into rows of cp (the zero padding was written once at create)
+    if (!rc)
+        rc = hip_fail(hipMemcpy2DAsync(wp, static_cast<size_t>(h->cp) * sizeof(flex_bf16), dW, static_cast<size_t>(h->c) * sizeof(flex_bf16),
+                                       static_cast<size_t>(h->c) * sizeof(flex_bf16), static_cast<size_t>(h->dim), hipMemcpyDeviceToDevice, s));
+    if (!rc) rc = mark(0);
+    if (order == FLEX_AXW_A_XW) {
+        if (!rc) rc = gemm(dX, xw);  // writes its padding columns as +0
+        if (!rc) rc = mark(1);
+        if (!rc) rc = flex_spmm_bf16(h->plan_c, xw, dOut, stream);
+        if (!rc && h->a_nonfinite) rc = hip_fail(flex_axw_bf16_clear_padding_launch(dOut, h->n, h->c, h->cp, s));  // inf x 0 = NaN there
+        if (!rc) rc = mark(2);
+    } else {
+        if (!rc) rc = flex_spmm_bf16(h->plan_dim, dX, ax, stream);
+        if (!rc) rc = mark(1);
+        if (!rc) rc = gemm(ax, dOut);
         if (!rc) rc = mark(2);
     }
     if (!rc && timed) {

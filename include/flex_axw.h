@@ -25,11 +25,19 @@ typedef struct flex_axw flex_axw;
 #define FLEX_AXW_USE_BLAS 0x10000u /* flex_axw_create flag: rocBLAS SGEMM for the dense half instead of the hand-written MFMA kernel (tools/probe_axw.py) */
 #define FLEX_AXW_BACKWARD 0x20000u /* flex_axw_create flag: also plan A^T and allocate what flex_axw_backward needs */
 
+#define FLEX_AXW_BF16 0x200000u /* flex_axw_create flag: the bf16 layer -- X, W, Out and both intermediates are flex_bf16, the plans are
+                                   FLEX_PLAN_BF16 plans and the handle runs flex_axw_run_bf16 (below) and nothing else.  Forward only and
+                                   without a rocBLAS path: FLEX_ERR_UNSUPPORTED together with FLEX_AXW_BACKWARD or FLEX_AXW_USE_BLAS, and
+                                   for a shape its kernel does not take (dim % 16 != 0, dim > 256, c > 256, n < 32).  The raw
+                                   FLEX_PLAN_BF16 bit in `flags` stays FLEX_ERR_INVALID */
+
 /* Leading dimension of Out and of the X*W intermediate: c rounded up to a multiple of 32 floats, so
  * that every row is a whole number of 128-byte cache lines (a row that starts mid-line costs each
  * gather one extra line: k=100 runs 50 % slower than k=128 on the reddit shape); the extra columns
  * come out as +0.0f, whatever the inputs hold (inf and NaN included). */
 int flex_axw_ld(int c);
+/* The same for a FLEX_AXW_BF16 handle: c rounded up to a multiple of 64 elements of 2 bytes -- whole 128-byte lines again. */
+int flex_axw_ld_bf16(int c);
 
 /* Plans A once per SpMM width (k = flex_axw_ld(c) and k = dim) and allocates the intermediates
  * (n x flex_axw_ld(c) and n x dim floats) and the padded copy of W on `device`.  `flags` as for
@@ -55,6 +63,31 @@ int flex_axw_create(flex_axw **out, const flex_csr *hostA, int dim, int c, int d
  * at the shapes tests/test_gpu_axw.py runs).  No residual is known. */
 int flex_axw_run(flex_axw *h, int order, const float *dX, const float *dW, float *dOut, flex_stream_t stream,
                  float *gemm_ms, float *spmm_ms);
+
+/* flex_axw_run of a FLEX_AXW_BF16 handle: Out[n x flex_axw_ld_bf16(c)] = A * dX[n x dim] * dW[dim x c], all device, row-major flex_bf16
+ * (the upper 16 bits of an IEEE float), on `stream`; orders, the AUTO rule (on flex_axw_ld_bf16(c) against dim) and gemm_ms / spmm_ms as
+ * for flex_axw_run.  FLEX_ERR_INVALID on a handle made without FLEX_AXW_BF16, as flex_axw_run (and flex_axw_backward) are on one made with
+ * it; dX and dOut must be 16-byte aligned (FLEX_ERR_UNSUPPORTED otherwise).  Nothing is enqueued in either case.
+ * Definition, every bf16 operand read as the fp32 number it is, rn_bf16 = one rounding to nearest even (a NaN stays a quiet NaN, what
+ * rounds past the largest finite bf16 becomes +-inf):
+ *     FLEX_AXW_A_XW:  T = rn_bf16(X W in fp32),     Out = flex_spmm_bf16(A, T);
+ *     FLEX_AXW_AX_W:  T = flex_spmm_bf16(A, X),     Out = rn_bf16(T W in fp32);
+ * two bf16 roundings in each order.  The dense stage is the bf16 MFMA kernel of axw_bf16_kernels.hip (v_mfma_f32_32x32x16_bf16, fp32
+ * accumulators, k in steps of 16 in ascending order); there is no other path.
+ * Accuracy (tests/axw_bf16_ref.py), with u = 2^-24, gamma and n_r as for flex_axw_run and
+ * bound_bf16(x, b) = b + 2^-8 (|x| + b) + 2^-134 (flex_attention_bf16's):
+ *   dense stage alone:   |x32 - L W| <= g := gamma(dim) |L||W| + dim 2^-149,   |Out - L W| <= bound_bf16(L W, g);
+ *   the layer: T64 the float64 first stage of the bf16 inputs, e1 its stage bound (bound_bf16(T64, g), or flex_spmm_bf16's bound), R the
+ *   float64 second stage of T64, E1 = |A| e1 (A_XW) or e1 |W| (AX_W), b2 the second stage's fp32 bound at |T64| + e1
+ *   (gamma(n_r) |A| (|T64| + e1) + n_r 2^-149, or gamma(dim) (|T64| + e1) |W| + dim 2^-149):
+ *       |Out - R| <= bound_bf16(R, E1 + b2),
+ *   NaN / +inf / -inf exactly where R has them, except that a rounding may overflow as flex_spmm_bf16 states; padding columns +0 bits
+ *   in every case.  Stated for normal inputs and sums (magnitudes well above 2^-126): what the bf16 MFMA does with subnormals is
+ *   recorded in DESIGN.md 3.26, not promised.
+ *   gamma(dim) assumes the matrix unit's sum of the 16 products of a step rounds no more than once per addition; the cancellation case
+ *   of tests/test_gpu_axw_bf16.py measures it (DESIGN.md 3.26 holds the figure). */
+int flex_axw_run_bf16(flex_axw *h, int order, const flex_bf16 *dX, const flex_bf16 *dW, flex_bf16 *dOut, flex_stream_t stream,
+                      float *gemm_ms, float *spmm_ms);
 
 /* The layer's gradients, for a handle made with FLEX_AXW_BACKWARD (FLEX_ERR_INVALID otherwise):
  *     G = A^T dOut (one flex_spmm of the transposed plan, k = c),  dGradX[n x dim] = G W^T,  dGradW[dim x c] = X^T G,

@@ -128,7 +128,7 @@ typedef struct flex_plan flex_plan;
                                        flex_plan_attention_backward_info: hostA's entries sorted by column -- 4 bytes per column, 8 per entry
                                        ({row, entry index}), 16 per work item, 4 per wave group.  Without the flag a plan uploads exactly what
                                        it uploads with FLEX_PLAN_ATTENTION alone */
-#define FLEX_PLAN_BF16 0x100000u /* B and C are flex_bf16, the upper 16 bits of an IEEE float, and sums are fp32: the plan runs flex_spmm_bf16
+#define FLEX_PLAN_BF16 0x100000u /* (0x200000u is taken by flex_axw.h) B and C are flex_bf16, the upper 16 bits of an IEEE float, and sums are fp32: the plan runs flex_spmm_bf16
                                        below and nothing else.  k, ldb and ldc stay in ELEMENTS and must be multiples of 8
                                        (FLEX_ERR_UNSUPPORTED otherwise): a bf16 row of k elements is, byte for byte, an fp32 row of k / 2 words,
                                        and the plan is the fp32 plan of that word width (lanes_per_nz, 32-bit offsets while n x ldb x 2 bytes
@@ -295,8 +295,8 @@ int flex_set_host_threads(int n);
 int flex_spmm(flex_plan *plan, const float *dB, float *dC, flex_stream_t stream);
 
 typedef uint16_t flex_bf16; /* the upper 16 bits of an IEEE float */
-/* flex_spmm on bf16 operands (FLEX_PLAN_BF16 plans only; FLEX_ERR_INVALID on any other plan, as flex_spmm, flex_plan_measure_imbalance
- * and the flex_axw calls are on a bf16 plan; nothing is enqueued).  dB: n x k row-major device flex_bf16, row stride ldb elements;
+/* flex_spmm on bf16 operands (FLEX_PLAN_BF16 plans only; FLEX_ERR_INVALID on any other plan, as flex_spmm and flex_plan_measure_imbalance
+ * are on a bf16 plan; nothing is enqueued.  flex_axw.h runs it for the handles made with FLEX_AXW_BF16).  dB: n x k row-major device flex_bf16, row stride ldb elements;
  * dC: m x k row-major device flex_bf16, row stride ldc elements, columns [0, k) of every row fully overwritten.  Both must be 16-byte aligned
  * (FLEX_ERR_UNSUPPORTED otherwise, C untouched): only the vector form is built.  Asynchronous, no allocation, no host sync, not
  * re-entrant per plan and guarded exactly as flex_spmm is.  Two launches: the row kernel, then the sum of the split rows' pieces.

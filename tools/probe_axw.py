@@ -1,5 +1,10 @@
 #!/usr/bin/env python3
-"""GEMM half of the A*X*W layer in isolation: time per order for a shape, library chosen by FLEX_AXW_LIB (ablations)."""
+"""GEMM half of the A*X*W layer in isolation: time per order for a shape, library chosen by FLEX_AXW_LIB (ablations).
+    probe_axw.py NAME DIM C      the fp32 layer on one shape
+    probe_axw.py --bf16          the bf16 layer (FLEX_AXW_BF16) against the fp32 one, alternated in this process, on flickr and reddit at
+                                 dim = c = 128 and dim = 256, c = 64: per-stage times, the bf16 GEMM against its streaming floor
+                                 (n dim + n cp) 2 bytes / HBM_RATE, the cancellation case's worst err / bound at the probe's n, and what the
+                                 bf16 MFMA does with subnormal operands and results."""
 import os
 import sys
 
@@ -10,6 +15,84 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import flex_amd  # noqa: E402
 import tools._knobs  # noqa: E402,F401  (FLEX_* environment knobs -> plan descriptor)
 from flex_amd import axw  # noqa: E402
+
+HBM_RATE = 8e12  # bytes / s: the roofline peak of DESIGN.md 3.4 (flex_hbm_probe measures 5.9e12 reading and 4.7e12 copying on this card)
+REPS = 30
+
+
+def timed(h, X, W, order):
+    """(gemm_us, spmm_us) of one more run"""
+    _, (g, s) = h.run(X, W, order, timed=True)
+    return g * 1e3, s * 1e3
+
+
+def bf16_table():
+    print(f"| graph | dim | c | order | fp32 gemm | fp32 spmm | fp32 layer | bf16 gemm | bf16 spmm | bf16 layer | bf16 / fp32 | gemm floor | gemm / floor |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|---|")
+    for name in ("flickr", "reddit"):
+        a = flex_amd.synth_graph(name)
+        for dim, c in ((128, 128), (256, 64)):
+            h32, h16 = axw.Axw(a, dim, c), axw.Axw(a, dim, c, bf16=True)
+            X = torch.rand((a.n, dim), device="cuda") * 2 - 1
+            W = torch.rand((dim, c), device="cuda")
+            Xb, Wb = X.bfloat16(), W.bfloat16()
+            for order in (axw.FLEX_AXW_A_XW, axw.FLEX_AXW_AX_W):
+                t32, t16 = [], []
+                for i in range(REPS + 5):  # alternated; the first five of each are warm-up
+                    r32, r16 = timed(h32, X, W, order), timed(h16, Xb, Wb, order)
+                    if i >= 5:
+                        t32.append(r32)
+                        t16.append(r16)
+                (g32, s32), (g16, s16) = np.median(t32, axis=0), np.median(t16, axis=0)
+                l32, l16 = np.median(np.sum(t32, axis=1)), np.median(np.sum(t16, axis=1))
+                floor = (a.n * dim + a.n * h16.ld) * 2 / HBM_RATE * 1e6
+                print(f"| {name} | {dim} | {c} | {'A(XW)' if order == axw.FLEX_AXW_A_XW else '(AX)W'} | {g32:.1f} | {s32:.1f} | {l32:.1f} | "
+                      f"{g16:.1f} | {s16:.1f} | {l16:.1f} | {l16 / l32:.2f} | {floor:.1f} | {g16 / floor:.2f} |", flush=True)
+            h32.destroy()
+            h16.destroy()
+
+
+def _gemm(L, Wp, c):
+    n, dim = L.shape
+    out = torch.empty((n, Wp.shape[1]), dtype=torch.bfloat16, device="cuda")
+    rc = axw._gemm_bf16_launch(L.data_ptr(), Wp.data_ptr(), out.data_ptr(), n, dim, c, Wp.shape[1],
+                               torch.cuda.get_device_properties(0).multi_processor_count, torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert rc == 0, rc
+    return out
+
+
+def cancellation(n=100000, dim=256, c=64):
+    """err / (gamma(dim) |L||W| + dim 2^-149 + the bf16 rounding's share) of the GEMM on rows of pairs (x, -x (1 + 2^-7)), in float64"""
+    g = torch.Generator(device="cuda").manual_seed(3)
+    L = torch.exp2(torch.rand((n, dim), device="cuda", generator=g) * 8 - 4).bfloat16()
+    L[:, 1::2] = -(L[:, 0::2].float() * (1 + 2.0 ** -7)).bfloat16()
+    W = torch.exp2(torch.rand((1, c), device="cuda", generator=g) * 8 - 4).bfloat16().repeat(dim, 1).contiguous()
+    out = _gemm(L, W, c).double()
+    ref, s = L.double() @ W.double(), L.double().abs() @ W.double().abs()
+    u = 2.0 ** -24
+    b32 = dim * u / (1 - dim * u) * s + dim * 2.0 ** -149
+    ratio = ((out - ref).abs() / (b32 + 2.0 ** -8 * (ref.abs() + b32) + 2.0 ** -134)).max().item()
+    print(f"cancellation, n={n} dim={dim} c={c}: worst err / bound {ratio:.4f} under gamma(dim); median |ref| / bound32 {(ref.abs() / b32).median().item():.1f}")
+
+
+def subnormals():
+    """the bf16 MFMA on a subnormal bf16 operand (2^-130 x 2^20 = 2^-110, a normal result) and on a subnormal sum (2^-65 x 2^-65 = 2^-130,
+    subnormal in fp32 and exactly representable as a bf16 subnormal)"""
+    for what, xbits, x, w in (("subnormal operand", 0x0008, 2.0 ** -130, 2.0 ** 20), ("subnormal fp32 sum", 0x1F00, 2.0 ** -65, 2.0 ** -65)):
+        L = torch.zeros((32, 16), dtype=torch.bfloat16, device="cuda")
+        L.view(torch.int16)[:, 0] = xbits  # the bits, not a conversion that might flush
+        W = torch.zeros((16, 64), dtype=torch.bfloat16, device="cuda")
+        W[0, :] = w
+        out = _gemm(L, W, 64)
+        print(f"{what}: {x:g} x {w:g} -> bits {out.view(torch.int16)[0, 0].item() & 0xFFFF:#06x} = {out.float()[0, 0].item():g} (exact {x * w:g})")
+
+
+if "--bf16" in sys.argv[1:]:
+    bf16_table()
+    cancellation()
+    subnormals()
+    sys.exit(0)
 
 name, dim, c = sys.argv[1], int(sys.argv[2]), int(sys.argv[3])
 a = flex_amd.synth_graph(name)
