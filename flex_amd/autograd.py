@@ -49,7 +49,7 @@ def _function():
         def backward(ctx, grad_out):
             X, W = ctx.saved_tensors
             h = ctx.h
-            dOut = torch.zeros((h.n, h.ld), dtype=torch.float32, device=grad_out.device)
+            dOut = torch.zeros((h.n, h.ld), dtype=torch.bfloat16 if h.bf16 else torch.float32, device=grad_out.device)
             dOut[:, : h.c] = grad_out
             gx, gw = h.backward(dOut, X, W, need_x=ctx.needs_input_grad[0], need_w=ctx.needs_input_grad[1])
             return gx, gw, None, None

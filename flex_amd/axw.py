@@ -10,7 +10,7 @@ from . import binding
 FLEX_AXW_AUTO, FLEX_AXW_A_XW, FLEX_AXW_AX_W = 0, 1, 2
 FLEX_AXW_USE_BLAS = 0x10000  # flex_axw_create flag: rocBLAS for the dense half
 FLEX_AXW_BACKWARD = 0x20000  # flex_axw_create flag: plan A^T too, for flex_axw_backward
-FLEX_AXW_BF16 = 0x200000  # flex_axw_create flag: the bf16 layer (flex_axw_run_bf16), forward only
+FLEX_AXW_BF16 = 0x200000  # flex_axw_create flag: the bf16 layer (flex_axw_run_bf16; with FLEX_AXW_BACKWARD flex_axw_backward_bf16)
 _lib = None
 
 
@@ -34,6 +34,12 @@ def lib():
         L.flex_axw_ld_bf16.argtypes = [C.c_int]
         L.flex_axw_gemm_bf16_launch.argtypes = L.flex_axw_gemm_launch.argtypes
         L.flex_axw_gemm_bf16_launch.restype = C.c_int
+        L.flex_axw_backward_bf16.argtypes = L.flex_axw_backward.argtypes
+        L.flex_axw_dw_bf16_launch.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+        L.flex_axw_dw_bf16_launch.restype = C.c_int
+        L.flex_axw_dw_bf16_slices.argtypes = [C.c_int, C.c_int]
+        L.flex_axw_dx_bf16_launch.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+        L.flex_axw_dx_bf16_launch.restype = C.c_int
         _lib = L
     return _lib
 
@@ -50,13 +56,25 @@ def _gemm_bf16_launch(L_ptr: int, Wp_ptr: int, Out_ptr: int, n: int, dim: int, c
     return lib().flex_axw_gemm_bf16_launch(L_ptr, Wp_ptr, Out_ptr, n, dim, c, cp, n_cus, stream)
 
 
+def _dw_bf16_launch(X_ptr: int, G_ptr: int, dW_ptr: int, part_ptr: int, n: int, dim: int, c: int, cp: int, n_cus: int, stream: int = 0) -> int:
+    """The bf16 dW kernel of flex_axw_backward_bf16 on its own (flex_axw_dw_bf16_launch): bf16 dW[dim x c] = X[n x dim]^T @ G[n x cp] through
+    the fp32 partials `part` (flex_axw_dw_bf16_slices(n, n_cus) x dim x c floats).  Returns the hipError_t; for tests."""
+    return lib().flex_axw_dw_bf16_launch(X_ptr, G_ptr, dW_ptr, part_ptr, n, dim, c, cp, n_cus, stream)
+
+
+def _dx_bf16_launch(G_ptr: int, Wt_ptr: int, dX_ptr: int, n: int, cp: int, dim: int, n_cus: int, stream: int = 0) -> int:
+    """The dX product of flex_axw_backward_bf16 on its own (flex_axw_dx_bf16_launch): bf16 dX[n x dim] = G[n x cp] @ Wt[cp x dim], dim any
+    multiple of 32.  Returns the hipError_t; for tests."""
+    return lib().flex_axw_dx_bf16_launch(G_ptr, Wt_ptr, dX_ptr, n, cp, dim, n_cus, stream)
+
+
 class Axw:
     """flex_axw handle: plans A for both SpMM widths once; run() computes A @ X @ W in either order."""
 
     def __init__(self, a: binding.HostCsr, dim: int, c: int, device: int = 0, order: int = binding.FLEX_ORDER_CLUSTER,
                  backward: bool = False, bf16: bool = False):
-        """backward: also plan A^T (FLEX_AXW_BACKWARD), for backward() and layer().  bf16: the bf16 layer (FLEX_AXW_BF16): run() takes and
-        returns torch.bfloat16; forward only (dim % 16 == 0, dim and c <= 256, n >= 32)."""
+        """backward: also plan A^T (FLEX_AXW_BACKWARD), for backward() and layer().  bf16: the bf16 layer (FLEX_AXW_BF16): run() and backward() take
+        and return torch.bfloat16 (dim % 16 == 0, dim and c <= 256, n >= 32; with backward=True dim % 32 == 0)."""
         self._h = C.c_void_p()
         v = a.view()
         flags = order | (FLEX_AXW_BACKWARD if backward else 0) | (FLEX_AXW_BF16 if bf16 else 0)
@@ -82,29 +100,31 @@ class Axw:
         return (out, (g.value, s.value)) if timed else out
 
     def backward(self, dOut, X, W, need_x: bool = True, need_w: bool = True):
-        """flex_axw_backward: dOut [n, ld] (its padding columns are never read) -> (dX [n, dim] or None, dW [dim, c] or None),
-        dX = A^T dOut W^T and dW = X^T (A^T dOut).  X and W are the forward's inputs (only the ones a requested gradient needs)."""
+        """flex_axw_backward: dOut [n, ld] -> (dX [n, dim] or None, dW [dim, c] or None), dX = A^T dOut W^T and dW = X^T (A^T dOut).  X and
+        W are the forward's inputs (only the ones a requested gradient needs).  float32, dOut's padding columns never read; on a bf16
+        handle flex_axw_backward_bf16: torch.bfloat16 in and out (any other dtype: TypeError), dOut's padding columns read and finite."""
         import torch
-        if self.bf16:
-            raise binding.FlexError("Axw.backward: the bf16 layer (bf16=True, FLEX_AXW_BF16) is forward only: it has no backward yet")
         if not self.has_backward:
             raise binding.FlexError("Axw.backward: the handle was made without backward=True (FLEX_AXW_BACKWARD)")
-        assert dOut.is_cuda and dOut.dtype == torch.float32 and dOut.is_contiguous() and tuple(dOut.shape) == (self.n, self.ld)
+        want = torch.bfloat16 if self.bf16 else torch.float32
+        given = [t for t, need in ((dOut, True), (X, need_w), (W, need_x)) if need]
+        if any(t.dtype != want for t in given):
+            raise TypeError(f"Axw.backward: this handle takes {want} dOut, X and W; got {[str(t.dtype) for t in given]}")
+        assert dOut.is_cuda and dOut.is_contiguous() and tuple(dOut.shape) == (self.n, self.ld)
         for t, need, shape in ((X, need_w, (self.n, self.dim)), (W, need_x, (self.dim, self.c))):
             if need:
-                assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape
-        gx = torch.empty((self.n, self.dim), dtype=torch.float32, device=dOut.device) if need_x else None
-        gw = torch.empty((self.dim, self.c), dtype=torch.float32, device=dOut.device) if need_w else None
+                assert t.is_cuda and t.is_contiguous() and tuple(t.shape) == shape
+        gx = torch.empty((self.n, self.dim), dtype=want, device=dOut.device) if need_x else None
+        gw = torch.empty((self.dim, self.c), dtype=want, device=dOut.device) if need_w else None
         ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        binding._check(lib().flex_axw_backward(self._h, ptr(X) if need_w else None, ptr(W) if need_x else None, dOut.data_ptr(),
-                                               ptr(gx), ptr(gw), torch.cuda.current_stream(dOut.device).cuda_stream),
-                       "flex_axw_backward")
+        call, what = (lib().flex_axw_backward_bf16, "flex_axw_backward_bf16") if self.bf16 else (lib().flex_axw_backward, "flex_axw_backward")
+        binding._check(call(self._h, ptr(X) if need_w else None, ptr(W) if need_x else None, dOut.data_ptr(), ptr(gx), ptr(gw),
+                            torch.cuda.current_stream(dOut.device).cuda_stream), what)
         return gx, gw
 
     def layer(self, X, W, order: int = FLEX_AXW_AUTO):
-        """Differentiable A X W: Out [n, c] (a view of the padded product); its gradient flows to X and W through backward()."""
-        if self.bf16:
-            raise binding.FlexError("Axw.layer: the bf16 layer (bf16=True, FLEX_AXW_BF16) is forward only: it has no backward yet")
+        """Differentiable A X W: Out [n, c] (a view of the padded product); its gradient flows to X and W through backward().  On a bf16
+        handle X, W, Out and the gradients are torch.bfloat16."""
         if not self.has_backward:
             raise binding.FlexError("Axw.layer: the handle was made without backward=True (FLEX_AXW_BACKWARD)")
         from .autograd import functions

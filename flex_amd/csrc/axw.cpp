@@ -20,13 +20,19 @@ extern "C" int flex_axw_dw_slices(int n, int n_cus);
 extern "C" hipError_t flex_axw_gemm_bf16_launch(const flex_bf16 *L, const flex_bf16 *Wp, flex_bf16 *Out, int n, int dim, int c, int cp,
                                                 int n_cus, hipStream_t s);  // axw_bf16_kernels.hip
 extern "C" hipError_t flex_axw_bf16_clear_padding_launch(flex_bf16 *Out, int n, int c, int cp, hipStream_t s);
+extern "C" hipError_t flex_axw_dx_bf16_launch(const flex_bf16 *G, const flex_bf16 *Wt, flex_bf16 *dX, int n, int cp, int dim, int n_cus,
+                                              hipStream_t s);
+extern "C" hipError_t flex_axw_bf16_transpose_launch(const flex_bf16 *W, flex_bf16 *Wt, int dim, int c, hipStream_t s);
+extern "C" hipError_t flex_axw_dw_bf16_launch(const flex_bf16 *X, const flex_bf16 *G, flex_bf16 *dW, float *part, int n, int dim, int c, int cp,
+                                              int n_cus, hipStream_t s);  // axw_bf16_backward_kernels.hip
+extern "C" int flex_axw_dw_bf16_slices(int n, int n_cus);
 
 struct flex_axw {
     int32_t n = 0;
     int n_cus = 0;
     bool use_blas = false;  // FLEX_AXW_USE_BLAS in `flags`, or a shape the MFMA kernel does not take (dim % 4 != 0, dim > 256, n < 32)
     bool a_nonfinite = false;  // A holds an inf or NaN: in order A_XW its SpMM turns the zero padding of X*W into NaN
-    bool bf16 = false;  // FLEX_AXW_BF16: FLEX_PLAN_BF16 plans, the three arrays below hold flex_bf16, flex_axw_run_bf16 is the handle's run
+    bool bf16 = false;  // FLEX_AXW_BF16: FLEX_PLAN_BF16 plans, the arrays below but d_part hold flex_bf16, the handle runs the _bf16 calls
     int dim = 0, c = 0, cp = 0, device = 0;
     flex_plan *plan_c = nullptr, *plan_dim = nullptr;
     float *d_xw = nullptr;  // n x cp
@@ -35,10 +41,10 @@ struct flex_axw {
     rocblas_handle blas = nullptr;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     // FLEX_AXW_BACKWARD only
-    flex_plan *plan_t = nullptr;  // A^T at k = c, ldb = ldc = cp
-    float *d_g = nullptr;         // G = A^T dOut, n x cp; its padding columns are +0 for good
-    float *d_wt = nullptr;        // W^T, cp x ld(dim), rows c .. cp-1 and columns dim .. zero
-    float *d_part = nullptr;      // dW partial sums: flex_axw_dw_slices(n, n_cus) x dim x c
+    flex_plan *plan_t = nullptr;  // A^T at k = c (bf16: c rounded up to 8), ldb = ldc = cp
+    float *d_g = nullptr;         // G = A^T dOut, n x cp; its padding columns are +0 for good (bf16: those from c rounded up to 8)
+    float *d_wt = nullptr;        // W^T, cp x ld(dim), rows c .. cp-1 and columns dim .. zero (bf16: cp x dim)
+    float *d_part = nullptr;      // dW partial sums: flex_axw_dw_slices(n, n_cus) x dim x c floats (bf16: flex_axw_dw_bf16_slices)
 };
 
 static thread_local int g_blas_status = 0;
@@ -108,8 +114,9 @@ int flex_axw_create(flex_axw **out, const flex_csr *A, int dim, int c, int devic
     if (!A || dim <= 0 || c <= 0 || device < 0 || A->m != A->n) return FLEX_ERR_INVALID;
     if (flags & FLEX_PLAN_BF16) return FLEX_ERR_INVALID;  // the bf16 layer is asked for by FLEX_AXW_BF16, which sets the plans' bit itself
     const bool bf16 = (flags & FLEX_AXW_BF16) != 0;
-    // the bf16 layer is forward only, has no rocBLAS path and runs the shapes of flex_axw_gemm_bf16_launch
-    if (bf16 && ((flags & (FLEX_AXW_BACKWARD | FLEX_AXW_USE_BLAS)) || dim % 16 != 0 || dim > 256 || c > 256 || A->n < 32)) return FLEX_ERR_UNSUPPORTED;
+    // the bf16 layer has no rocBLAS path and runs the shapes of flex_axw_gemm_bf16_launch; its backward writes dX in whole 32-column tiles
+    if (bf16 && ((flags & FLEX_AXW_USE_BLAS) || dim % 16 != 0 || dim > 256 || c > 256 || A->n < 32)) return FLEX_ERR_UNSUPPORTED;
+    if (bf16 && (flags & FLEX_AXW_BACKWARD) && dim % 32 != 0) return FLEX_ERR_UNSUPPORTED;
     flex_axw *h = new (std::nothrow) flex_axw();
     if (!h) return FLEX_ERR_NOMEM;
     h->n = A->n;
@@ -143,7 +150,18 @@ int flex_axw_create(flex_axw **out, const flex_csr *A, int dim, int c, int devic
         h->n_cus = prop.multiProcessorCount;
         h->use_blas = want_blas || dim % 4 != 0 || dim > 256 || h->n < 32;
     }
-    if (!rc && backward) {
+    if (!rc && backward && bf16) {
+        // a bf16 plan takes k % 8 == 0: columns c .. k8-1 of dOut are read and of G written, the columns from k8 on stay +0 for good
+        const int k8 = (c + 7) / 8 * 8;
+        const size_t wt = static_cast<size_t>(h->cp) * dim;
+        const size_t part = static_cast<size_t>(std::max(1, flex_axw_dw_bf16_slices(h->n, h->n_cus))) * dim * c;
+        rc = flex_plan_create_ld(&h->plan_t, A, k8, h->cp, h->cp, device, flags | FLEX_PLAN_TRANSPOSE);
+        if (!rc) rc = hip_fail(hipMalloc(reinterpret_cast<void **>(&h->d_g), n1 * h->cp * es));
+        if (!rc) rc = hip_fail(hipMemset(h->d_g, 0, n1 * h->cp * es));
+        if (!rc) rc = hip_fail(hipMalloc(reinterpret_cast<void **>(&h->d_wt), wt * es));
+        if (!rc) rc = hip_fail(hipMemset(h->d_wt, 0, wt * es));  // rows c .. cp-1 stay zero
+        if (!rc) rc = hip_fail(hipMalloc(reinterpret_cast<void **>(&h->d_part), part * sizeof(float)));
+    } else if (!rc && backward) {
         const size_t wt = static_cast<size_t>(h->cp) * flex_axw_ld(dim);
         const size_t part = static_cast<size_t>(std::max(1, flex_axw_dw_slices(h->n, h->n_cus))) * dim * c;
         rc = flex_plan_create_ld(&h->plan_t, A, c, h->cp, h->cp, device, flags | FLEX_PLAN_TRANSPOSE);
@@ -254,7 +272,7 @@ int flex_axw_run_bf16(flex_axw *h, int order, const flex_bf16 *dX, const flex_bf
 // G = A^T dOut (the transposed plan), then dGradX = G W^T and dGradW = X^T G (axw_kernels.hip; rocBLAS where the kernels do not take
 // the shape or FLEX_AXW_USE_BLAS asked for it).  Everything is queued on `stream`: no allocation, no host sync.
 int flex_axw_backward(flex_axw *h, const float *dX, const float *dW, const float *dOut, float *dGradX, float *dGradW, flex_stream_t stream) {
-    if (!h || !h->plan_t || !dOut || (dGradX && !dW) || (dGradW && !dX)) return FLEX_ERR_INVALID;
+    if (!h || h->bf16 || !h->plan_t || !dOut || (dGradX && !dW) || (dGradW && !dX)) return FLEX_ERR_INVALID;
     if (h->n == 0 || (!dGradX && !dGradW)) return FLEX_OK;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     int cur = -1;
@@ -286,6 +304,33 @@ int flex_axw_backward(flex_axw *h, const float *dX, const float *dW, const float
                                     h->dim, &zero, dGradW, h->c));
         }
     }
+    if (cur >= 0 && cur != h->device) (void)hipSetDevice(cur);
+    return rc;
+}
+
+// flex_axw_backward on a FLEX_AXW_BF16 handle: G = A^T dOut rounded once to bf16 (flex_spmm_bf16 on the transposed plan), then
+// dGradX = G Wt on the forward's bf16 MFMA kernel and dGradW = X^T G on axw_bf16_backward_kernels.hip.  Create refused every shape the
+// kernels do not take, so there is no other path.  Everything is queued on `stream`: no allocation, no host sync.
+int flex_axw_backward_bf16(flex_axw *h, const flex_bf16 *dX, const flex_bf16 *dW, const flex_bf16 *dOut, flex_bf16 *dGradX, flex_bf16 *dGradW,
+                           flex_stream_t stream) {
+    if (!h || !h->bf16 || !h->plan_t || !dOut || (dGradX && !dW) || (dGradW && !dX)) return FLEX_ERR_INVALID;
+    for (const void *p : {static_cast<const void *>(dOut), static_cast<const void *>(dGradX), static_cast<const void *>(dGradW),
+                          static_cast<const void *>(dGradX ? dW : nullptr), static_cast<const void *>(dGradW ? dX : nullptr)})
+        if (reinterpret_cast<uintptr_t>(p) & 15) return FLEX_ERR_UNSUPPORTED;
+    if (!dGradX && !dGradW) return FLEX_OK;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    flex_bf16 *g = reinterpret_cast<flex_bf16 *>(h->d_g), *wt = reinterpret_cast<flex_bf16 *>(h->d_wt);
+    int cur = -1;
+    (void)hipGetDevice(&cur);
+    int rc = hip_fail(hipSetDevice(h->device));
+    if (!rc) rc = flex_spmm_bf16(h->plan_t, dOut, g, stream);
+    // inf x 0 = NaN in G's padding columns would meet the zero rows of W^T: a NaN row of dGradX where the reference has inf
+    if (!rc && h->a_nonfinite) rc = hip_fail(flex_axw_bf16_clear_padding_launch(g, h->n, h->c, h->cp, s));
+    if (!rc && dGradX) {
+        rc = hip_fail(flex_axw_bf16_transpose_launch(dW, wt, h->dim, h->c, s));
+        if (!rc) rc = hip_fail(flex_axw_dx_bf16_launch(g, wt, dGradX, h->n, h->cp, h->dim, h->n_cus, s));
+    }
+    if (!rc && dGradW) rc = hip_fail(flex_axw_dw_bf16_launch(dX, g, dGradW, h->d_part, h->n, h->dim, h->c, h->cp, h->n_cus, s));
     if (cur >= 0 && cur != h->device) (void)hipSetDevice(cur);
     return rc;
 }

@@ -167,6 +167,15 @@ __global__ __launch_bounds__(256) void axw_bf16_clear_padding_kernel(flex_bf16 *
     if (e < static_cast<int64_t>(n) * w) Out[(e / w) * cp + c + e % w] = 0;
 }
 
+// Wt[k][i] = W[i][k] for i < dim, k < c (W: dim x c, Wt: dim elements a row); Wt's other rows are left as they are: the twin of
+// axw_transpose_kernel, for the dX product of flex_axw_backward_bf16
+__global__ __launch_bounds__(256) void axw_bf16_transpose_kernel(const flex_bf16 *__restrict__ W, flex_bf16 *__restrict__ Wt, int dim, int c) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= dim * c) return;
+    const int k = e / dim, i = e % dim;
+    Wt[static_cast<size_t>(k) * dim + i] = W[static_cast<size_t>(i) * c + k];
+}
+
 }  // namespace flex_axw_bf16
 
 // Out[n x cp] = L[n x dim] * Wp[dim x cp] on flex_bf16, columns c .. cp-1 of Out written as +0.  Takes n >= 32, dim % 16 == 0,
@@ -196,6 +205,48 @@ extern "C" hipError_t flex_axw_gemm_bf16_launch(const flex_bf16 *L, const flex_b
         default: go(axw_gemm_bf16_kernel<8>); break;
     }
     return e;
+}
+
+// The dX product of flex_axw_backward_bf16: dX[n x dim] = G[n x cp] * Wt[cp x dim] on flex_bf16 -- the kernel above with the contraction
+// over cp and NT = dim / 32 output tiles, odd counts included; dim is dX's row stride, so there is no padding to mask (c == cp == dim in
+// the kernel's terms).  Takes n >= 32, cp % 64 == 0, 0 < cp <= 256, dim % 32 == 0, 0 < dim <= 256, n_cus > 0 and 16-byte aligned G, Wt and
+// dX; anything else returns hipErrorInvalidValue before a launch.
+extern "C" hipError_t flex_axw_dx_bf16_launch(const flex_bf16 *G, const flex_bf16 *Wt, flex_bf16 *dX, int n, int cp, int dim, int n_cus,
+                                              hipStream_t s) {
+    using namespace flex_axw_bf16;
+    const auto misaligned = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
+    if (!G || !Wt || !dX || n < kRows || cp <= 0 || cp % 64 != 0 || cp > 256 || dim <= 0 || dim % 32 != 0 || dim > 256 || n_cus <= 0 ||
+        misaligned(G) || misaligned(Wt) || misaligned(dX))
+        return hipErrorInvalidValue;
+    const int n_panels = (n + kRows - 1) / kRows;
+    const size_t lds = static_cast<size_t>(cp) * dim * sizeof(flex_bf16);
+    const dim3 grid(static_cast<unsigned>(std::min(n_cus, (n_panels + 3) / 4))), block(64 * kWaves);
+    hipError_t e = hipSuccess;
+    auto go = [&](auto kernel) {
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+        if (e != hipSuccess) return;
+        hipLaunchKernelGGL(kernel, grid, block, lds, s, G, Wt, dX, n, cp, dim);
+        e = hipGetLastError();
+    };
+    switch (dim / 32) {
+        case 1: go(axw_gemm_bf16_kernel<1>); break;
+        case 2: go(axw_gemm_bf16_kernel<2>); break;
+        case 3: go(axw_gemm_bf16_kernel<3>); break;
+        case 4: go(axw_gemm_bf16_kernel<4>); break;
+        case 5: go(axw_gemm_bf16_kernel<5>); break;
+        case 6: go(axw_gemm_bf16_kernel<6>); break;
+        case 7: go(axw_gemm_bf16_kernel<7>); break;
+        default: go(axw_gemm_bf16_kernel<8>); break;
+    }
+    return e;
+}
+
+// Wt[c x dim] := W[dim x c]^T (rows c .. of Wt are not written)
+extern "C" hipError_t flex_axw_bf16_transpose_launch(const flex_bf16 *W, flex_bf16 *Wt, int dim, int c, hipStream_t s) {
+    using namespace flex_axw_bf16;
+    if (!W || !Wt || dim <= 0 || c <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(axw_bf16_transpose_kernel, dim3(static_cast<unsigned>((dim * c + 255) / 256)), dim3(256), 0, s, W, Wt, dim, c);
+    return hipGetLastError();
 }
 
 // columns c .. cp-1 of Out[n x cp] := +0 bits; c == cp: nothing to do

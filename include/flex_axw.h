@@ -26,10 +26,11 @@ typedef struct flex_axw flex_axw;
 #define FLEX_AXW_BACKWARD 0x20000u /* flex_axw_create flag: also plan A^T and allocate what flex_axw_backward needs */
 
 #define FLEX_AXW_BF16 0x200000u /* flex_axw_create flag: the bf16 layer -- X, W, Out and both intermediates are flex_bf16, the plans are
-                                   FLEX_PLAN_BF16 plans and the handle runs flex_axw_run_bf16 (below) and nothing else.  Forward only and
-                                   without a rocBLAS path: FLEX_ERR_UNSUPPORTED together with FLEX_AXW_BACKWARD or FLEX_AXW_USE_BLAS, and
-                                   for a shape its kernel does not take (dim % 16 != 0, dim > 256, c > 256, n < 32).  The raw
-                                   FLEX_PLAN_BF16 bit in `flags` stays FLEX_ERR_INVALID */
+                                   FLEX_PLAN_BF16 plans and the handle runs flex_axw_run_bf16 and, made with FLEX_AXW_BACKWARD as well,
+                                   flex_axw_backward_bf16 (both below) and nothing else.  Without a rocBLAS path: FLEX_ERR_UNSUPPORTED
+                                   together with FLEX_AXW_USE_BLAS, for a shape its kernels do not take (dim % 16 != 0, dim > 256,
+                                   c > 256, n < 32) and, together with FLEX_AXW_BACKWARD, for dim % 32 != 0 (dGradX is written in whole
+                                   32-column tiles).  The raw FLEX_PLAN_BF16 bit in `flags` stays FLEX_ERR_INVALID */
 
 /* Leading dimension of Out and of the X*W intermediate: c rounded up to a multiple of 32 floats, so
  * that every row is a whole number of 128-byte cache lines (a row that starts mid-line costs each
@@ -108,6 +109,29 @@ int flex_axw_run_bf16(flex_axw *h, int order, const flex_bf16 *dX, const flex_bf
  * float64 reference, under flex_axw_run's conditions (no stage sum reaches 2^120; no finite G entry that fp32 may round to zero or to
  * the other sign meets an inf or NaN of X or W). */
 int flex_axw_backward(flex_axw *h, const float *dX, const float *dW, const float *dOut, float *dGradX, float *dGradW, flex_stream_t stream);
+
+/* flex_axw_backward of a handle made with FLEX_AXW_BF16 | FLEX_AXW_BACKWARD (FLEX_ERR_INVALID on any other, as flex_axw_backward is on a
+ * bf16 handle), in the same association order, all device, row-major flex_bf16, on `stream`:
+ *     G      = flex_spmm_bf16(A^T, dOut)      n x flex_axw_ld_bf16(c), one rounding to bf16
+ *     dGradX = rn_bf16(G W^T in fp32)         n x dim     (the forward's bf16 MFMA kernel on a W^T staged by the call)
+ *     dGradW = rn_bf16(X^T G in fp32)         dim x c     (axw_bf16_backward_kernels.hip: fp32 partial sums per n-slice, added in slice
+ *                                                          order, rounded once)
+ * A NULL dGradX or dGradW skips that product, and its input (dW, resp. dX) may then be NULL; no allocation, no host sync (safe to capture
+ * in a hipGraph); ONE call of a handle in flight at a time; the same inputs give the same bits on every call (no atomics).  Every pointer
+ * passed must be 16-byte aligned (FLEX_ERR_UNSUPPORTED otherwise); nothing is enqueued in any refusal.
+ * dOut is n x flex_axw_ld_bf16(c), and -- unlike flex_axw_backward -- its padding columns ARE read (the bf16 transposed plan gathers whole
+ * groups of 8 columns): they must be finite (+0 is what flex_axw_run_bf16 writes).  Finite values there change no output bit: they meet
+ * only the zero rows of the staged W^T, and dGradW drops those columns.
+ * Accuracy (tests/axw_bf16_backward_ref.py), u, gamma, n_r and bound_bf16 as for flex_axw_run_bf16, cp = flex_axw_ld_bf16(c): G64 the
+ * float64 A^T dOut of the bf16 inputs, eG flex_spmm_bf16's bound for it (n_r of the rows of A^T);
+ *   dGradX: R = G64 W^T,  E1 = eG |W|^T,  b2 = gamma(cp) (|G64| + eG) |W|^T + cp 2^-149:            |dGradX - R| <= bound_bf16(R, E1 + b2);
+ *   dGradW: R = X^T G64,  E1 = |X|^T eG,  b2 = gamma(L) |X|^T (|G64| + eG) + L 2^-149 (1 + sum_r |X_ri|),
+ *           L = rows per slice + slices (flex_axw_backward's L_dW for this kernel's slices: rows = ceil(n / min(CUs, ceil(n / 256)))
+ *           rounded up to a multiple of 64, slices = ceil(n / rows)):                               |dGradW - R| <= bound_bf16(R, E1 + b2);
+ *   NaN / +inf / -inf exactly where R has them, under flex_axw_run_bf16's conditions.  Both gammas assume the matrix unit's sum of the 16
+ *   products of a step rounds no more than once per addition; DESIGN.md 3.27 holds what the cancellation cases measured. */
+int flex_axw_backward_bf16(flex_axw *h, const flex_bf16 *dX, const flex_bf16 *dW, const flex_bf16 *dOut, flex_bf16 *dGradX, flex_bf16 *dGradW,
+                           flex_stream_t stream);
 int flex_axw_destroy(flex_axw *h);
 /* last rocBLAS status seen (rocblas_status), for FLEX_ERR_UNSUPPORTED returns caused by rocBLAS */
 int flex_axw_last_blas_status(void);

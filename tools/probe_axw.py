@@ -4,7 +4,11 @@
     probe_axw.py --bf16          the bf16 layer (FLEX_AXW_BF16) against the fp32 one, alternated in this process, on flickr and reddit at
                                  dim = c = 128 and dim = 256, c = 64: per-stage times, the bf16 GEMM against its streaming floor
                                  (n dim + n cp) 2 bytes / HBM_RATE, the cancellation case's worst err / bound at the probe's n, and what the
-                                 bf16 MFMA does with subnormal operands and results."""
+                                 bf16 MFMA does with subnormal operands and results.
+    probe_axw.py --bf16-backward the bf16 backward (flex_axw_backward_bf16) against the fp32 one on the same graphs and shapes, alternated
+                                 in this process: medians of event times of the whole call, of the call without dW and of the call without
+                                 dX; the stages are their differences (A^T dOut = no-dW + no-dX - both, dX = both - no-dX, dW = both - no-dW),
+                                 the dense ones against their streaming floor (n dim + n cp) 2 bytes / HBM_RATE."""
 import os
 import sys
 
@@ -87,6 +91,48 @@ def subnormals():
         out = _gemm(L, W, 64)
         print(f"{what}: {x:g} x {w:g} -> bits {out.view(torch.int16)[0, 0].item() & 0xFFFF:#06x} = {out.float()[0, 0].item():g} (exact {x * w:g})")
 
+
+def backward_table():
+    def once(h, g, X, W, need_x, need_w):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        h.backward(g, X, W, need_x=need_x, need_w=need_w)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e3
+
+    print("| graph | dim | c | fp32 A^T dOut | fp32 dX | fp32 dW | fp32 all | bf16 A^T dOut | bf16 dX | bf16 dW | bf16 all | bf16 / fp32 | floor | dX / floor | dW / floor |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|")
+    for name in ("flickr", "reddit"):
+        a = flex_amd.synth_graph(name)
+        for dim, c in ((128, 128), (256, 64)):
+            h32, h16 = axw.Axw(a, dim, c, backward=True), axw.Axw(a, dim, c, backward=True, bf16=True)
+            X, W = torch.rand((a.n, dim), device="cuda") * 2 - 1, torch.rand((dim, c), device="cuda")
+            g32, g16 = torch.zeros((a.n, h32.ld), device="cuda"), torch.zeros((a.n, h16.ld), dtype=torch.bfloat16, device="cuda")
+            g32[:, :c] = torch.rand((a.n, c), device="cuda") * 2 - 1
+            g16[:, :c] = g32[:, :c].bfloat16()
+            ops = {32: (h32, g32, X, W), 16: (h16, g16, X.bfloat16(), W.bfloat16())}
+            t = {(k, v): [] for k in ops for v in range(3)}
+            for i in range(REPS + 5):  # alternated; the first five of each are warm-up
+                for v, (nx, nw) in enumerate(((True, True), (True, False), (False, True))):
+                    for k in ops:
+                        us = once(*ops[k], nx, nw)
+                        if i >= 5:
+                            t[k, v].append(us)
+            cells = []
+            for k in (32, 16):
+                both, no_dw, no_dx = (float(np.median(t[k, v])) for v in range(3))
+                cells += [no_dw + no_dx - both, both - no_dx, both - no_dw, both]
+            floor = (a.n * dim + a.n * h16.ld) * 2 / HBM_RATE * 1e6
+            print(f"| {name} | {dim} | {c} | " + " | ".join(f"{x:.1f}" for x in cells) + f" | {cells[7] / cells[3]:.2f} | {floor:.1f} | "
+                  f"{cells[5] / floor:.2f} | {cells[6] / floor:.2f} |", flush=True)
+            h32.destroy()
+            h16.destroy()
+
+
+if "--bf16-backward" in sys.argv[1:]:
+    backward_table()
+    sys.exit(0)
 
 if "--bf16" in sys.argv[1:]:
     bf16_table()
