@@ -40,6 +40,13 @@ def lib():
         L.flex_axw_dw_bf16_slices.argtypes = [C.c_int, C.c_int]
         L.flex_axw_dx_bf16_launch.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
         L.flex_axw_dx_bf16_launch.restype = C.c_int
+        L.flex_axw_gemm_bf16_wide_launch.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+        L.flex_axw_gemm_bf16_wide_launch.restype = C.c_int
+        L.flex_axw_dx_bf16_wide_launch.argtypes = L.flex_axw_dx_bf16_launch.argtypes
+        L.flex_axw_dx_bf16_wide_launch.restype = C.c_int
+        L.flex_axw_dw_bf16_wide_launch.argtypes = L.flex_axw_dw_bf16_launch.argtypes
+        L.flex_axw_dw_bf16_wide_launch.restype = C.c_int
+        L.flex_axw_dw_bf16_wide_slices.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
         _lib = L
     return _lib
 
@@ -68,13 +75,38 @@ def _dx_bf16_launch(G_ptr: int, Wt_ptr: int, dX_ptr: int, n: int, cp: int, dim: 
     return lib().flex_axw_dx_bf16_launch(G_ptr, Wt_ptr, dX_ptr, n, cp, dim, n_cus, stream)
 
 
+def _gemm_bf16_wide_launch(L_ptr: int, W_ptr: int, Wf_ptr: int, Out_ptr: int, n: int, dim: int, c: int, cp: int, n_cus: int, stream: int = 0) -> int:
+    """The bf16 GEMM of the bf16 layer at 256 < dim <= 4096 on its own (flex_axw_gemm_bf16_wide_launch): bf16 Out[n x cp] = L[n x dim] @
+    W[dim x c] -- W unpadded -- through the scratch Wf (dim x cp elements: W as MFMA fragments), columns >= c written as +0 bits.  Returns
+    the hipError_t; for tests."""
+    return lib().flex_axw_gemm_bf16_wide_launch(L_ptr, W_ptr, Wf_ptr, Out_ptr, n, dim, c, cp, n_cus, stream)
+
+
+def _dx_bf16_wide_launch(G_ptr: int, Wt_ptr: int, dX_ptr: int, n: int, cp: int, dim: int, n_cus: int, stream: int = 0) -> int:
+    """_dx_bf16_launch at 256 < dim <= 4096 (flex_axw_dx_bf16_wide_launch): dX in passes of 256 columns.  Returns the hipError_t; for tests."""
+    return lib().flex_axw_dx_bf16_wide_launch(G_ptr, Wt_ptr, dX_ptr, n, cp, dim, n_cus, stream)
+
+
+def _dw_bf16_wide_launch(X_ptr: int, G_ptr: int, dW_ptr: int, part_ptr: int, n: int, dim: int, c: int, cp: int, n_cus: int, stream: int = 0) -> int:
+    """_dw_bf16_launch at 256 < dim <= 4096, dim % 32 == 0 (flex_axw_dw_bf16_wide_launch); `part` holds _dw_bf16_wide_slices(n, dim, c, n_cus)
+    x dim x c floats.  Returns the hipError_t; for tests."""
+    return lib().flex_axw_dw_bf16_wide_launch(X_ptr, G_ptr, dW_ptr, part_ptr, n, dim, c, cp, n_cus, stream)
+
+
+def _dw_bf16_wide_slices(n: int, dim: int, c: int, n_cus: int) -> int:
+    """n-slices of the wide dW kernel (flex_axw_dw_bf16_wide_slices): at most n / (2 c), so that the fp32 partials stay below the bytes of X."""
+    return lib().flex_axw_dw_bf16_wide_slices(n, dim, c, n_cus)
+
+
 class Axw:
     """flex_axw handle: plans A for both SpMM widths once; run() computes A @ X @ W in either order."""
 
     def __init__(self, a: binding.HostCsr, dim: int, c: int, device: int = 0, order: int = binding.FLEX_ORDER_CLUSTER,
                  backward: bool = False, bf16: bool = False):
         """backward: also plan A^T (FLEX_AXW_BACKWARD), for backward() and layer().  bf16: the bf16 layer (FLEX_AXW_BF16): run() and backward() take
-        and return torch.bfloat16 (dim % 16 == 0, dim and c <= 256, n >= 32; with backward=True dim % 32 == 0)."""
+        and return torch.bfloat16 (dim % 16 == 0, dim <= 4096, c <= 256, n >= 32; with backward=True dim % 32 == 0).  dim > 256 runs the
+        wide kernels (axw_bf16_wide_kernels.hip); a width that is no multiple of 16 (602, 1433) is served exactly by zero columns of X and
+        zero rows of W."""
         self._h = C.c_void_p()
         v = a.view()
         flags = order | (FLEX_AXW_BACKWARD if backward else 0) | (FLEX_AXW_BF16 if bf16 else 0)

@@ -26,6 +26,13 @@ extern "C" hipError_t flex_axw_bf16_transpose_launch(const flex_bf16 *W, flex_bf
 extern "C" hipError_t flex_axw_dw_bf16_launch(const flex_bf16 *X, const flex_bf16 *G, flex_bf16 *dW, float *part, int n, int dim, int c, int cp,
                                               int n_cus, hipStream_t s);  // axw_bf16_backward_kernels.hip
 extern "C" int flex_axw_dw_bf16_slices(int n, int n_cus);
+extern "C" hipError_t flex_axw_gemm_bf16_wide_launch(const flex_bf16 *L, const flex_bf16 *W, flex_bf16 *Wf, flex_bf16 *Out, int n, int dim, int c,
+                                                     int cp, int n_cus, hipStream_t s);  // axw_bf16_wide_kernels.hip: 256 < dim <= 4096
+extern "C" hipError_t flex_axw_dx_bf16_wide_launch(const flex_bf16 *G, const flex_bf16 *Wt, flex_bf16 *dX, int n, int cp, int dim, int n_cus,
+                                                   hipStream_t s);
+extern "C" hipError_t flex_axw_dw_bf16_wide_launch(const flex_bf16 *X, const flex_bf16 *G, flex_bf16 *dW, float *part, int n, int dim, int c,
+                                                   int cp, int n_cus, hipStream_t s);
+extern "C" int flex_axw_dw_bf16_wide_slices(int n, int dim, int c, int n_cus);
 
 struct flex_axw {
     int32_t n = 0;
@@ -33,18 +40,19 @@ struct flex_axw {
     bool use_blas = false;  // FLEX_AXW_USE_BLAS in `flags`, or a shape the MFMA kernel does not take (dim % 4 != 0, dim > 256, n < 32)
     bool a_nonfinite = false;  // A holds an inf or NaN: in order A_XW its SpMM turns the zero padding of X*W into NaN
     bool bf16 = false;  // FLEX_AXW_BF16: FLEX_PLAN_BF16 plans, the arrays below but d_part hold flex_bf16, the handle runs the _bf16 calls
+    bool wide = false;  // bf16 && dim > 256: the dense half is axw_bf16_wide_kernels.hip, d_wp holds W in fragment order
     int dim = 0, c = 0, cp = 0, device = 0;
     flex_plan *plan_c = nullptr, *plan_dim = nullptr;
     float *d_xw = nullptr;  // n x cp
     float *d_ax = nullptr;  // n x dim
-    float *d_wp = nullptr;  // dim x cp (W with zero columns appended)
+    float *d_wp = nullptr;  // dim x cp (W with zero columns appended; wide: the same elements as MFMA fragments)
     rocblas_handle blas = nullptr;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     // FLEX_AXW_BACKWARD only
     flex_plan *plan_t = nullptr;  // A^T at k = c (bf16: c rounded up to 8), ldb = ldc = cp
     float *d_g = nullptr;         // G = A^T dOut, n x cp; its padding columns are +0 for good (bf16: those from c rounded up to 8)
     float *d_wt = nullptr;        // W^T, cp x ld(dim), rows c .. cp-1 and columns dim .. zero (bf16: cp x dim)
-    float *d_part = nullptr;      // dW partial sums: flex_axw_dw_slices(n, n_cus) x dim x c floats (bf16: flex_axw_dw_bf16_slices)
+    float *d_part = nullptr;      // dW partial sums: flex_axw_dw_slices(n, n_cus) x dim x c floats (bf16: flex_axw_dw_bf16_slices, wide: flex_axw_dw_bf16_wide_slices)
 };
 
 static thread_local int g_blas_status = 0;
@@ -114,8 +122,9 @@ int flex_axw_create(flex_axw **out, const flex_csr *A, int dim, int c, int devic
     if (!A || dim <= 0 || c <= 0 || device < 0 || A->m != A->n) return FLEX_ERR_INVALID;
     if (flags & FLEX_PLAN_BF16) return FLEX_ERR_INVALID;  // the bf16 layer is asked for by FLEX_AXW_BF16, which sets the plans' bit itself
     const bool bf16 = (flags & FLEX_AXW_BF16) != 0;
-    // the bf16 layer has no rocBLAS path and runs the shapes of flex_axw_gemm_bf16_launch; its backward writes dX in whole 32-column tiles
-    if (bf16 && ((flags & FLEX_AXW_USE_BLAS) || dim % 16 != 0 || dim > 256 || c > 256 || A->n < 32)) return FLEX_ERR_UNSUPPORTED;
+    // the bf16 layer has no rocBLAS path and runs the shapes of flex_axw_gemm_bf16_launch (dim <= 256) and flex_axw_gemm_bf16_wide_launch;
+    // its backward writes dX in whole 32-column tiles
+    if (bf16 && ((flags & FLEX_AXW_USE_BLAS) || dim % 16 != 0 || dim > 4096 || c > 256 || A->n < 32)) return FLEX_ERR_UNSUPPORTED;
     if (bf16 && (flags & FLEX_AXW_BACKWARD) && dim % 32 != 0) return FLEX_ERR_UNSUPPORTED;
     flex_axw *h = new (std::nothrow) flex_axw();
     if (!h) return FLEX_ERR_NOMEM;
@@ -123,6 +132,7 @@ int flex_axw_create(flex_axw **out, const flex_csr *A, int dim, int c, int devic
     h->dim = dim;
     h->c = c;
     h->bf16 = bf16;
+    h->wide = bf16 && dim > 256;
     h->cp = bf16 ? flex_axw_ld_bf16(c) : flex_axw_ld(c);
     h->device = device;
     int prev = -1;
@@ -154,7 +164,8 @@ int flex_axw_create(flex_axw **out, const flex_csr *A, int dim, int c, int devic
         // a bf16 plan takes k % 8 == 0: columns c .. k8-1 of dOut are read and of G written, the columns from k8 on stay +0 for good
         const int k8 = (c + 7) / 8 * 8;
         const size_t wt = static_cast<size_t>(h->cp) * dim;
-        const size_t part = static_cast<size_t>(std::max(1, flex_axw_dw_bf16_slices(h->n, h->n_cus))) * dim * c;
+        const int slices = h->wide ? flex_axw_dw_bf16_wide_slices(h->n, dim, c, h->n_cus) : flex_axw_dw_bf16_slices(h->n, h->n_cus);
+        const size_t part = static_cast<size_t>(std::max(1, slices)) * dim * c;
         rc = flex_plan_create_ld(&h->plan_t, A, k8, h->cp, h->cp, device, flags | FLEX_PLAN_TRANSPOSE);
         if (!rc) rc = hip_fail(hipMalloc(reinterpret_cast<void **>(&h->d_g), n1 * h->cp * es));
         if (!rc) rc = hip_fail(hipMemset(h->d_g, 0, n1 * h->cp * es));
@@ -222,8 +233,8 @@ int flex_axw_run(flex_axw *h, int order, const float *dX, const float *dW, float
     return rc;
 }
 
-// flex_axw_run on a FLEX_AXW_BF16 handle: the same two stages on flex_bf16, the dense one always axw_bf16_kernels.hip (create refused
-// every shape it does not take), the intermediate rounded to bf16 by the stage that writes it.
+// flex_axw_run on a FLEX_AXW_BF16 handle: the same two stages on flex_bf16, the dense one always axw_bf16_kernels.hip or, at dim > 256,
+// axw_bf16_wide_kernels.hip (create refused every shape they do not take), the intermediate rounded to bf16 by the stage that writes it.
 int flex_axw_run_bf16(flex_axw *h, int order, const flex_bf16 *dX, const flex_bf16 *dW, flex_bf16 *dOut, flex_stream_t stream,
                       float *gemm_ms, float *spmm_ms) {
     if (!h || !h->bf16 || !dX || !dW || !dOut || order < FLEX_AXW_AUTO || order > FLEX_AXW_AX_W) return FLEX_ERR_INVALID;
@@ -236,11 +247,12 @@ int flex_axw_run_bf16(flex_axw *h, int order, const flex_bf16 *dX, const flex_bf
     int rc = hip_fail(hipSetDevice(h->device));
     const bool timed = gemm_ms || spmm_ms;
     auto mark = [&](int i) { return timed ? hip_fail(hipEventRecord(h->ev[i], s)) : FLEX_OK; };
-    auto gemm = [&](const flex_bf16 *L, flex_bf16 *Cout) {
-        return hip_fail(flex_axw_gemm_bf16_launch(L, wp, Cout, h->n, h->dim, h->c, h->cp, h->n_cus, s));
+    auto gemm = [&](const flex_bf16 *L, flex_bf16 *Cout) {  // wide: packs W into wp (fragment order, zero columns included) first
+        return hip_fail(h->wide ? flex_axw_gemm_bf16_wide_launch(L, dW, wp, Cout, h->n, h->dim, h->c, h->cp, h->n_cus, s)
+                                : flex_axw_gemm_bf16_launch(L, wp, Cout, h->n, h->dim, h->c, h->cp, h->n_cus, s));
     };
     // W -> Wp: dim rows of c elements into rows of cp (the zero padding was written once at create)
-    if (!rc)
+    if (!rc && !h->wide)
         rc = hip_fail(hipMemcpy2DAsync(wp, static_cast<size_t>(h->cp) * sizeof(flex_bf16), dW, static_cast<size_t>(h->c) * sizeof(flex_bf16),
                                        static_cast<size_t>(h->c) * sizeof(flex_bf16), static_cast<size_t>(h->dim), hipMemcpyDeviceToDevice, s));
     if (!rc) rc = mark(0);
@@ -309,8 +321,8 @@ int flex_axw_backward(flex_axw *h, const float *dX, const float *dW, const float
 }
 
 // flex_axw_backward on a FLEX_AXW_BF16 handle: G = A^T dOut rounded once to bf16 (flex_spmm_bf16 on the transposed plan), then
-// dGradX = G Wt on the forward's bf16 MFMA kernel and dGradW = X^T G on axw_bf16_backward_kernels.hip.  Create refused every shape the
-// kernels do not take, so there is no other path.  Everything is queued on `stream`: no allocation, no host sync.
+// dGradX = G Wt on the forward's bf16 MFMA kernel and dGradW = X^T G on axw_bf16_backward_kernels.hip (at dim > 256 the launchers of
+// axw_bf16_wide_kernels.hip: dX in 256-column passes, dW under its own slice rule).  Create refused every shape the kernels do not take, so there is no other path.  Everything is queued on `stream`: no allocation, no host sync.
 int flex_axw_backward_bf16(flex_axw *h, const flex_bf16 *dX, const flex_bf16 *dW, const flex_bf16 *dOut, flex_bf16 *dGradX, flex_bf16 *dGradW,
                            flex_stream_t stream) {
     if (!h || !h->bf16 || !h->plan_t || !dOut || (dGradX && !dW) || (dGradW && !dX)) return FLEX_ERR_INVALID;
@@ -328,9 +340,11 @@ int flex_axw_backward_bf16(flex_axw *h, const flex_bf16 *dX, const flex_bf16 *dW
     if (!rc && h->a_nonfinite) rc = hip_fail(flex_axw_bf16_clear_padding_launch(g, h->n, h->c, h->cp, s));
     if (!rc && dGradX) {
         rc = hip_fail(flex_axw_bf16_transpose_launch(dW, wt, h->dim, h->c, s));
-        if (!rc) rc = hip_fail(flex_axw_dx_bf16_launch(g, wt, dGradX, h->n, h->cp, h->dim, h->n_cus, s));
+        if (!rc) rc = hip_fail((h->wide ? flex_axw_dx_bf16_wide_launch : flex_axw_dx_bf16_launch)(g, wt, dGradX, h->n, h->cp, h->dim, h->n_cus, s));
     }
-    if (!rc && dGradW) rc = hip_fail(flex_axw_dw_bf16_launch(dX, g, dGradW, h->d_part, h->n, h->dim, h->c, h->cp, h->n_cus, s));
+    if (!rc && dGradW)
+        rc = hip_fail((h->wide ? flex_axw_dw_bf16_wide_launch : flex_axw_dw_bf16_launch)(dX, g, dGradW, h->d_part, h->n, h->dim, h->c, h->cp,
+                                                                                         h->n_cus, s));
     if (cur >= 0 && cur != h->device) (void)hipSetDevice(cur);
     return rc;
 }

@@ -153,6 +153,9 @@ inline int dw_rows(int n, int n_cus) {
 
 }  // namespace flex_axw_bf16_backward
 
+extern "C" hipError_t flex_axw_dw_bf16_rows_launch(const flex_bf16 *X, const flex_bf16 *G, flex_bf16 *dW, float *part, int n, int dim, int c,
+                                                   int cp, int rows, hipStream_t s);
+
 // n-slices of the bf16 dW kernel: ceil(n / rows), rows = ceil(n / min(n_cus, ceil(n / 256))) rounded up to a multiple of 64; no slice is empty
 extern "C" int flex_axw_dw_bf16_slices(int n, int n_cus) {
     if (n <= 0 || n_cus <= 0) return 0;
@@ -170,7 +173,16 @@ extern "C" hipError_t flex_axw_dw_bf16_launch(const flex_bf16 *X, const flex_bf1
     if (!X || !G || !dW || !part || n < 32 || dim <= 0 || dim > 256 || dim % 8 != 0 || c <= 0 || c > cp || cp > 256 || cp % 32 != 0 || n_cus <= 0 ||
         misaligned(X) || misaligned(G))
         return hipErrorInvalidValue;
-    const int rows = dw_rows(n, n_cus), slices = (n + rows - 1) / rows;
+    return flex_axw_dw_bf16_rows_launch(X, G, dW, part, n, dim, c, cp, dw_rows(n, n_cus), s);
+}
+
+// The two launches behind flex_axw_dw_bf16_launch and flex_axw_dw_bf16_wide_launch (axw_bf16_wide_kernels.hip), which check their
+// arguments and choose `rows`, a multiple of 64: n-slices of `rows` rows, `part` holds ceil(n / rows) * dim * c floats.  Not checked
+// here: any dim % 8 == 0 is served by the grid of 128 x 128 blocks.
+extern "C" hipError_t flex_axw_dw_bf16_rows_launch(const flex_bf16 *X, const flex_bf16 *G, flex_bf16 *dW, float *part, int n, int dim, int c,
+                                                   int cp, int rows, hipStream_t s) {
+    using namespace flex_axw_bf16_backward;
+    const int slices = (n + rows - 1) / rows;
     const dim3 grid(static_cast<unsigned>(slices), static_cast<unsigned>(((dim + 127) / 128) * ((cp + 127) / 128)));
     hipLaunchKernelGGL(axw_dw_bf16_kernel, grid, dim3(256), 0, s, X, G, part, n, dim, c, cp, rows);
     hipError_t e = hipGetLastError();

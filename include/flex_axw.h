@@ -28,9 +28,11 @@ typedef struct flex_axw flex_axw;
 #define FLEX_AXW_BF16 0x200000u /* flex_axw_create flag: the bf16 layer -- X, W, Out and both intermediates are flex_bf16, the plans are
                                    FLEX_PLAN_BF16 plans and the handle runs flex_axw_run_bf16 and, made with FLEX_AXW_BACKWARD as well,
                                    flex_axw_backward_bf16 (both below) and nothing else.  Without a rocBLAS path: FLEX_ERR_UNSUPPORTED
-                                   together with FLEX_AXW_USE_BLAS, for a shape its kernels do not take (dim % 16 != 0, dim > 256,
+                                   together with FLEX_AXW_USE_BLAS, for a shape its kernels do not take (dim % 16 != 0, dim > 4096,
                                    c > 256, n < 32) and, together with FLEX_AXW_BACKWARD, for dim % 32 != 0 (dGradX is written in whole
-                                   32-column tiles).  The raw FLEX_PLAN_BF16 bit in `flags` stays FLEX_ERR_INVALID */
+                                   32-column tiles).  dim <= 256 runs axw_bf16_kernels.hip and axw_bf16_backward_kernels.hip, 256 < dim <=
+                                   4096 (the input layer of a GCN) axw_bf16_wide_kernels.hip.  A width that is no multiple of 16 (602, 1433)
+                                   is served by zero columns appended to X and zero rows to W: exact, a zero product adds nothing.  The raw FLEX_PLAN_BF16 bit in `flags` stays FLEX_ERR_INVALID */
 
 /* Leading dimension of Out and of the X*W intermediate: c rounded up to a multiple of 32 floats, so
  * that every row is a whole number of 128-byte cache lines (a row that starts mid-line costs each
@@ -74,7 +76,10 @@ int flex_axw_run(flex_axw *h, int order, const float *dX, const float *dW, float
  *     FLEX_AXW_A_XW:  T = rn_bf16(X W in fp32),     Out = flex_spmm_bf16(A, T);
  *     FLEX_AXW_AX_W:  T = flex_spmm_bf16(A, X),     Out = rn_bf16(T W in fp32);
  * two bf16 roundings in each order.  The dense stage is the bf16 MFMA kernel of axw_bf16_kernels.hip (v_mfma_f32_32x32x16_bf16, fp32
- * accumulators, k in steps of 16 in ascending order); there is no other path.
+ * accumulators, k in steps of 16 in ascending order) and, at 256 < dim <= 4096, its wide twin of axw_bf16_wide_kernels.hip (W streamed
+ * through LDS in slabs of 128 k values, the same single ascending k chain per entry); there is no other path.  The accuracy statements
+ * below hold unchanged over the whole range of dim (tests/test_gpu_axw_bf16_wide.py; DESIGN.md 3.28 holds the measured figures: the wide
+ * GEMM alone at most 0.98 of its bound, 0.29 in the cancellation case).
  * Accuracy (tests/axw_bf16_ref.py), with u = 2^-24, gamma and n_r as for flex_axw_run and
  * bound_bf16(x, b) = b + 2^-8 (|x| + b) + 2^-134 (flex_attention_bf16's):
  *   dense stage alone:   |x32 - L W| <= g := gamma(dim) |L||W| + dim 2^-149,   |Out - L W| <= bound_bf16(L W, g);
@@ -119,6 +124,10 @@ int flex_axw_backward(flex_axw *h, const float *dX, const float *dW, const float
  * A NULL dGradX or dGradW skips that product, and its input (dW, resp. dX) may then be NULL; no allocation, no host sync (safe to capture
  * in a hipGraph); ONE call of a handle in flight at a time; the same inputs give the same bits on every call (no atomics).  Every pointer
  * passed must be 16-byte aligned (FLEX_ERR_UNSUPPORTED otherwise); nothing is enqueued in any refusal.
+ * At 256 < dim <= 4096 (axw_bf16_wide_kernels.hip) dGradX is computed in passes of 256 output columns and dGradW under the slice rule
+ * rows = ceil(n / S0) rounded up to a multiple of 64, S0 = max(1, min(ceil(n / 256), ceil(2 CUs / (ceil(dim / 128) ceil(c / 128))),
+ * floor(n / (2 c)))), slices = ceil(n / rows): the partial sums stay below the bytes of X.  The accuracy statements below carry over
+ * unchanged, with L taken from that rule (DESIGN.md 3.28 holds the measured figures).
  * dOut is n x flex_axw_ld_bf16(c), and -- unlike flex_axw_backward -- its padding columns ARE read (the bf16 transposed plan gathers whole
  * groups of 8 columns): they must be finite (+0 is what flex_axw_run_bf16 writes).  Finite values there change no output bit: they meet
  * only the zero rows of the staged W^T, and dGradW drops those columns.

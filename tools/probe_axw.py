@@ -8,7 +8,9 @@
     probe_axw.py --bf16-backward the bf16 backward (flex_axw_backward_bf16) against the fp32 one on the same graphs and shapes, alternated
                                  in this process: medians of event times of the whole call, of the call without dW and of the call without
                                  dX; the stages are their differences (A^T dOut = no-dW + no-dX - both, dX = both - no-dX, dW = both - no-dW),
-                                 the dense ones against their streaming floor (n dim + n cp) 2 bytes / HBM_RATE."""
+                                 the dense ones against their streaming floor (n dim + n cp) 2 bytes / HBM_RATE.
+    probe_axw.py --bf16-wide     both tables at input-layer widths (axw_bf16_wide_kernels.hip): flickr at dim 512 and reddit at dim 608 (602
+                                 padded), c = 128 and 64, in the order AUTO picks there, A (X W); the fp32 handle runs rocBLAS at dim > 256."""
 import os
 import sys
 
@@ -30,17 +32,21 @@ def timed(h, X, W, order):
     return g * 1e3, s * 1e3
 
 
-def bf16_table():
+NARROW = {name: ((128, 128), (256, 64)) for name in ("flickr", "reddit")}  # graph -> (dim, c)
+WIDE = {"flickr": ((512, 128), (512, 64)), "reddit": ((608, 128), (608, 64))}
+
+
+def bf16_table(shapes=NARROW, orders=(axw.FLEX_AXW_A_XW, axw.FLEX_AXW_AX_W)):
     print(f"| graph | dim | c | order | fp32 gemm | fp32 spmm | fp32 layer | bf16 gemm | bf16 spmm | bf16 layer | bf16 / fp32 | gemm floor | gemm / floor |")
     print("|---|---|---|---|---|---|---|---|---|---|---|---|---|")
-    for name in ("flickr", "reddit"):
+    for name in shapes:
         a = flex_amd.synth_graph(name)
-        for dim, c in ((128, 128), (256, 64)):
+        for dim, c in shapes[name]:
             h32, h16 = axw.Axw(a, dim, c), axw.Axw(a, dim, c, bf16=True)
             X = torch.rand((a.n, dim), device="cuda") * 2 - 1
             W = torch.rand((dim, c), device="cuda")
             Xb, Wb = X.bfloat16(), W.bfloat16()
-            for order in (axw.FLEX_AXW_A_XW, axw.FLEX_AXW_AX_W):
+            for order in orders:
                 t32, t16 = [], []
                 for i in range(REPS + 5):  # alternated; the first five of each are warm-up
                     r32, r16 = timed(h32, X, W, order), timed(h16, Xb, Wb, order)
@@ -92,7 +98,7 @@ def subnormals():
         print(f"{what}: {x:g} x {w:g} -> bits {out.view(torch.int16)[0, 0].item() & 0xFFFF:#06x} = {out.float()[0, 0].item():g} (exact {x * w:g})")
 
 
-def backward_table():
+def backward_table(shapes=NARROW):
     def once(h, g, X, W, need_x, need_w):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -103,9 +109,9 @@ def backward_table():
 
     print("| graph | dim | c | fp32 A^T dOut | fp32 dX | fp32 dW | fp32 all | bf16 A^T dOut | bf16 dX | bf16 dW | bf16 all | bf16 / fp32 | floor | dX / floor | dW / floor |")
     print("|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|")
-    for name in ("flickr", "reddit"):
+    for name in shapes:
         a = flex_amd.synth_graph(name)
-        for dim, c in ((128, 128), (256, 64)):
+        for dim, c in shapes[name]:
             h32, h16 = axw.Axw(a, dim, c, backward=True), axw.Axw(a, dim, c, backward=True, bf16=True)
             X, W = torch.rand((a.n, dim), device="cuda") * 2 - 1, torch.rand((dim, c), device="cuda")
             g32, g16 = torch.zeros((a.n, h32.ld), device="cuda"), torch.zeros((a.n, h16.ld), dtype=torch.bfloat16, device="cuda")
@@ -129,6 +135,11 @@ def backward_table():
             h32.destroy()
             h16.destroy()
 
+
+if "--bf16-wide" in sys.argv[1:]:
+    bf16_table(WIDE, (axw.FLEX_AXW_A_XW,))
+    backward_table(WIDE)
+    sys.exit(0)
 
 if "--bf16-backward" in sys.argv[1:]:
     backward_table()
