@@ -11,6 +11,7 @@ FLEX_AXW_AUTO, FLEX_AXW_A_XW, FLEX_AXW_AX_W = 0, 1, 2
 FLEX_AXW_USE_BLAS = 0x10000  # flex_axw_create flag: rocBLAS for the dense half
 FLEX_AXW_BACKWARD = 0x20000  # flex_axw_create flag: plan A^T too, for flex_axw_backward
 FLEX_AXW_BF16 = 0x200000  # flex_axw_create flag: the bf16 layer (flex_axw_run_bf16; with FLEX_AXW_BACKWARD flex_axw_backward_bf16)
+FLEX_AXW_ROOT = 0x400000  # flex_axw_create flag, with FLEX_AXW_BF16: the buffers of flex_axw_run_root_bf16 (A X W + X R + b)
 _lib = None
 
 
@@ -47,6 +48,9 @@ def lib():
         L.flex_axw_dw_bf16_wide_launch.argtypes = L.flex_axw_dw_bf16_launch.argtypes
         L.flex_axw_dw_bf16_wide_launch.restype = C.c_int
         L.flex_axw_dw_bf16_wide_slices.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+        L.flex_axw_run_root_bf16.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.flex_axw_gemm_bf16_root_launch.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+        L.flex_axw_gemm_bf16_root_launch.restype = C.c_int
         _lib = L
     return _lib
 
@@ -98,22 +102,31 @@ def _dw_bf16_wide_slices(n: int, dim: int, c: int, n_cus: int) -> int:
     return lib().flex_axw_dw_bf16_wide_slices(n, dim, c, n_cus)
 
 
+def _gemm_bf16_root_launch(L1_ptr: int, W1_ptr: int, d1: int, L2_ptr, W2_ptr, d2: int, Cin_ptr, bias_ptr, Wf_ptr: int, Out_ptr: int, n: int,
+                           c: int, cp: int, n_cus: int, stream: int = 0) -> int:
+    """The dense stage of flex_axw_run_root_bf16 on its own (flex_axw_gemm_bf16_root_launch): bf16 Out[n x cp] = L1[n x d1] @ W1[d1 x c] +
+    L2[n x d2] @ W2[d2 x c] + Cin[n x cp] + bias[c] (fp32) in one fp32 chain, through the scratch Wf ((d1 + d2) x cp elements); L2 / W2 with
+    d2 = 0, Cin and bias may each be None.  Columns >= c are written as +0 bits.  Returns the hipError_t; for tests."""
+    return lib().flex_axw_gemm_bf16_root_launch(L1_ptr, W1_ptr, d1, L2_ptr, W2_ptr, d2, Cin_ptr, bias_ptr, Wf_ptr, Out_ptr, n, c, cp, n_cus, stream)
+
+
 class Axw:
     """flex_axw handle: plans A for both SpMM widths once; run() computes A @ X @ W in either order."""
 
     def __init__(self, a: binding.HostCsr, dim: int, c: int, device: int = 0, order: int = binding.FLEX_ORDER_CLUSTER,
-                 backward: bool = False, bf16: bool = False):
+                 backward: bool = False, bf16: bool = False, root: bool = False):
         """backward: also plan A^T (FLEX_AXW_BACKWARD), for backward() and layer().  bf16: the bf16 layer (FLEX_AXW_BF16): run() and backward() take
         and return torch.bfloat16 (dim % 16 == 0, dim <= 4096, c <= 256, n >= 32; with backward=True dim % 32 == 0).  dim > 256 runs the
         wide kernels (axw_bf16_wide_kernels.hip); a width that is no multiple of 16 (602, 1433) is served exactly by zero columns of X and
-        zero rows of W."""
+        zero rows of W.  root (with bf16=True only): the buffers of run_root() (FLEX_AXW_ROOT)."""
         self._h = C.c_void_p()
         v = a.view()
-        flags = order | (FLEX_AXW_BACKWARD if backward else 0) | (FLEX_AXW_BF16 if bf16 else 0)
+        flags = order | (FLEX_AXW_BACKWARD if backward else 0) | (FLEX_AXW_BF16 if bf16 else 0) | (FLEX_AXW_ROOT if root else 0)
         binding._check(lib().flex_axw_create(C.byref(self._h), C.byref(v), dim, c, device, flags), "flex_axw_create")
         self.n, self.dim, self.c, self.ld = a.n, dim, c, (lib().flex_axw_ld_bf16(c) if bf16 else lib().flex_axw_ld(c))
         self.has_backward = backward
         self.bf16 = bf16
+        self.has_root = root
 
     def run(self, X, W, order: int = FLEX_AXW_AUTO, timed: bool = False):
         """X [n, dim], W [dim, c]: contiguous cuda tensors, float32 -- torch.bfloat16 on a bf16 handle (any other dtype: TypeError).
@@ -129,6 +142,26 @@ class Axw:
         call, what = (lib().flex_axw_run_bf16, "flex_axw_run_bf16") if self.bf16 else (lib().flex_axw_run, "flex_axw_run")
         binding._check(call(self._h, order, X.data_ptr(), W.data_ptr(), out.data_ptr(), torch.cuda.current_stream(X.device).cuda_stream,
                             C.byref(g) if timed else None, C.byref(s) if timed else None), what)
+        return (out, (g.value, s.value)) if timed else out
+
+    def run_root(self, X, W, R, bias=None, order: int = FLEX_AXW_AUTO, timed: bool = False):
+        """flex_axw_run_root_bf16: A @ X @ W + X @ R + bias with one rounding after the last sum.  X [n, dim], W and R [dim, c]: contiguous
+        cuda torch.bfloat16; bias: float32 [c] or None (anything else: TypeError).  Returns Out [n, ld] in bfloat16 (columns >= c are zero)
+        and, if timed, (gemm_ms, spmm_ms).  Forward only: no autograd."""
+        import torch
+        if not self.has_root:
+            raise binding.FlexError("Axw.run_root: the handle was made without root=True (FLEX_AXW_ROOT)")
+        if any(t.dtype != torch.bfloat16 for t in (X, W, R)):
+            raise TypeError(f"Axw.run_root takes torch.bfloat16 X, W and R; got {X.dtype}, {W.dtype} and {R.dtype}")
+        if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (self.c,)):
+            raise TypeError(f"Axw.run_root takes a float32 bias of shape [{self.c}]; got {bias.dtype} {tuple(bias.shape)}")
+        assert all(t.is_cuda and t.is_contiguous() for t in (X, W, R)) and (bias is None or (bias.is_cuda and bias.is_contiguous()))
+        assert tuple(X.shape) == (self.n, self.dim) and tuple(W.shape) == tuple(R.shape) == (self.dim, self.c)
+        out = torch.empty((self.n, self.ld), dtype=torch.bfloat16, device=X.device)
+        g, s = C.c_float(), C.c_float()
+        binding._check(lib().flex_axw_run_root_bf16(self._h, order, X.data_ptr(), W.data_ptr(), R.data_ptr(), None if bias is None else bias.data_ptr(),
+                                                    out.data_ptr(), torch.cuda.current_stream(X.device).cuda_stream,
+                                                    C.byref(g) if timed else None, C.byref(s) if timed else None), "flex_axw_run_root_bf16")
         return (out, (g.value, s.value)) if timed else out
 
     def backward(self, dOut, X, W, need_x: bool = True, need_w: bool = True):

@@ -33,6 +33,9 @@ extern "C" hipError_t flex_axw_dx_bf16_wide_launch(const flex_bf16 *G, const fle
 extern "C" hipError_t flex_axw_dw_bf16_wide_launch(const flex_bf16 *X, const flex_bf16 *G, flex_bf16 *dW, float *part, int n, int dim, int c,
                                                    int cp, int n_cus, hipStream_t s);
 extern "C" int flex_axw_dw_bf16_wide_slices(int n, int dim, int c, int n_cus);
+extern "C" hipError_t flex_axw_gemm_bf16_root_launch(const flex_bf16 *L1, const flex_bf16 *W1, int d1, const flex_bf16 *L2, const flex_bf16 *W2,
+                                                     int d2, const flex_bf16 *Cin, const float *bias, flex_bf16 *Wf, flex_bf16 *Out, int n, int c,
+                                                     int cp, int n_cus, hipStream_t s);  // axw_bf16_root_kernels.hip
 
 struct flex_axw {
     int32_t n = 0;
@@ -47,11 +50,14 @@ struct flex_axw {
     float *d_ax = nullptr;  // n x dim
     float *d_wp = nullptr;  // dim x cp (W with zero columns appended; wide: the same elements as MFMA fragments)
     rocblas_handle blas = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // the fourth: FLEX_AXW_ROOT only
     // FLEX_AXW_BACKWARD only
     flex_plan *plan_t = nullptr;  // A^T at k = c (bf16: c rounded up to 8), ldb = ldc = cp
     float *d_g = nullptr;         // G = A^T dOut, n x cp; its padding columns are +0 for good (bf16: those from c rounded up to 8)
     float *d_wt = nullptr;        // W^T, cp x ld(dim), rows c .. cp-1 and columns dim .. zero (bf16: cp x dim)
+    // FLEX_AXW_ROOT only (flex_bf16)
+    float *d_s = nullptr;   // n x cp: A (X W) in order A_XW, the addend of the root kernel
+    float *d_wf = nullptr;  // 2 dim x cp: [W; R] as MFMA fragments (axw_bf16_root_kernels.hip)
     float *d_part = nullptr;      // dW partial sums: flex_axw_dw_slices(n, n_cus) x dim x c floats (bf16: flex_axw_dw_bf16_slices, wide: flex_axw_dw_bf16_wide_slices)
 };
 
@@ -105,6 +111,8 @@ int flex_axw_destroy(flex_axw *h) {
     (void)hipFree(h->d_g);
     (void)hipFree(h->d_wt);
     (void)hipFree(h->d_part);
+    (void)hipFree(h->d_s);
+    (void)hipFree(h->d_wf);
     (void)hipFree(h->d_xw);
     (void)hipFree(h->d_ax);
     (void)hipFree(h->d_wp);
@@ -126,6 +134,8 @@ int flex_axw_create(flex_axw **out, const flex_csr *A, int dim, int c, int devic
     // its backward writes dX in whole 32-column tiles
     if (bf16 && ((flags & FLEX_AXW_USE_BLAS) || dim % 16 != 0 || dim > 4096 || c > 256 || A->n < 32)) return FLEX_ERR_UNSUPPORTED;
     if (bf16 && (flags & FLEX_AXW_BACKWARD) && dim % 32 != 0) return FLEX_ERR_UNSUPPORTED;
+    const bool root = (flags & FLEX_AXW_ROOT) != 0;
+    if (root && !bf16) return FLEX_ERR_UNSUPPORTED;  // the root term is the bf16 layer's
     flex_axw *h = new (std::nothrow) flex_axw();
     if (!h) return FLEX_ERR_NOMEM;
     h->n = A->n;
@@ -140,7 +150,7 @@ int flex_axw_create(flex_axw **out, const flex_csr *A, int dim, int c, int devic
     int rc = hip_fail(hipSetDevice(device));
     const bool want_blas = (flags & FLEX_AXW_USE_BLAS) != 0;
     const bool backward = (flags & FLEX_AXW_BACKWARD) != 0;
-    flags &= ~(FLEX_AXW_USE_BLAS | FLEX_AXW_BACKWARD | FLEX_AXW_BF16);
+    flags &= ~(FLEX_AXW_USE_BLAS | FLEX_AXW_BACKWARD | FLEX_AXW_BF16 | FLEX_AXW_ROOT);
     if (bf16) flags |= FLEX_PLAN_BF16;
     const size_t es = bf16 ? sizeof(flex_bf16) : sizeof(float);  // element size of the intermediates and of Wp
     if (!rc) rc = flex_plan_create(&h->plan_c, A, h->cp, device, flags);
@@ -153,6 +163,12 @@ int flex_axw_create(flex_axw **out, const flex_csr *A, int dim, int c, int devic
     if (!rc) rc = hip_fail(hipMemset(h->d_xw, 0, n1 * h->cp * es));  // its padding columns stay +0 for good
     for (int64_t e = 0; e < A->nnz && !h->a_nonfinite; ++e) h->a_nonfinite = !std::isfinite(A->vals[e]);
     for (int i = 0; i < 3 && !rc; ++i) rc = hip_fail(hipEventCreate(&h->ev[i]));
+    if (root) {
+        if (!rc) rc = hip_fail(hipMalloc(reinterpret_cast<void **>(&h->d_s), n1 * h->cp * es));
+        if (!rc) rc = hip_fail(hipMemset(h->d_s, 0, n1 * h->cp * es));
+        if (!rc) rc = hip_fail(hipMalloc(reinterpret_cast<void **>(&h->d_wf), static_cast<size_t>(2) * dim * h->cp * es));
+        if (!rc) rc = hip_fail(hipEventCreate(&h->ev[3]));
+    }
     if (!rc && !bf16 && rocblas_create_handle(&h->blas) != rocblas_status_success) rc = FLEX_ERR_UNSUPPORTED;
     if (!rc) {
         hipDeviceProp_t prop;
@@ -276,6 +292,55 @@ int flex_axw_run_bf16(flex_axw *h, int order, const flex_bf16 *dX, const flex_bf
         const bool gemm_first = order == FLEX_AXW_A_XW;
         if (gemm_ms) *gemm_ms = gemm_first ? a : b;
         if (spmm_ms) *spmm_ms = gemm_first ? b : a;
+    }
+    if (cur >= 0 && cur != h->device) (void)hipSetDevice(cur);
+    return rc;
+}
+
+// flex_axw_run_bf16 with a root-weight term, on a handle made with FLEX_AXW_ROOT: Out = rn_bf16(A X W + X R + b).  The last stage of either
+// order is one launch of axw_bf16_root_kernels.hip: in AX_W both products in one accumulator chain (L1 = A X, L2 = X), in A_XW the root
+// product with A (X W) as its addend; the stages before it are flex_axw_run_bf16's own.
+int flex_axw_run_root_bf16(flex_axw *h, int order, const flex_bf16 *dX, const flex_bf16 *dW, const flex_bf16 *dR, const float *dBias,
+                           flex_bf16 *dOut, flex_stream_t stream, float *gemm_ms, float *spmm_ms) {
+    if (!h || !h->d_wf || !dX || !dW || !dR || !dOut || order < FLEX_AXW_AUTO || order > FLEX_AXW_AX_W) return FLEX_ERR_INVALID;
+    if ((reinterpret_cast<uintptr_t>(dX) | reinterpret_cast<uintptr_t>(dOut)) & 15) return FLEX_ERR_UNSUPPORTED;
+    if (order == FLEX_AXW_AUTO) order = h->cp <= h->dim ? FLEX_AXW_A_XW : FLEX_AXW_AX_W;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    flex_bf16 *xw = reinterpret_cast<flex_bf16 *>(h->d_xw), *ax = reinterpret_cast<flex_bf16 *>(h->d_ax), *wp = reinterpret_cast<flex_bf16 *>(h->d_wp);
+    flex_bf16 *sum = reinterpret_cast<flex_bf16 *>(h->d_s), *wf = reinterpret_cast<flex_bf16 *>(h->d_wf);
+    int cur = -1;
+    (void)hipGetDevice(&cur);
+    int rc = hip_fail(hipSetDevice(h->device));
+    const bool timed = gemm_ms || spmm_ms;
+    auto mark = [&](int i) { return timed ? hip_fail(hipEventRecord(h->ev[i], s)) : FLEX_OK; };
+    if (!rc) rc = mark(0);
+    if (order == FLEX_AXW_A_XW) {
+        if (!rc && !h->wide)  // W -> Wp, as flex_axw_run_bf16
+            rc = hip_fail(hipMemcpy2DAsync(wp, static_cast<size_t>(h->cp) * sizeof(flex_bf16), dW, static_cast<size_t>(h->c) * sizeof(flex_bf16),
+                                           static_cast<size_t>(h->c) * sizeof(flex_bf16), static_cast<size_t>(h->dim), hipMemcpyDeviceToDevice, s));
+        if (!rc)
+            rc = hip_fail(h->wide ? flex_axw_gemm_bf16_wide_launch(dX, dW, wp, xw, h->n, h->dim, h->c, h->cp, h->n_cus, s)
+                                  : flex_axw_gemm_bf16_launch(dX, wp, xw, h->n, h->dim, h->c, h->cp, h->n_cus, s));
+        if (!rc) rc = mark(1);
+        if (!rc) rc = flex_spmm_bf16(h->plan_c, xw, sum, stream);
+        if (!rc && h->a_nonfinite) rc = hip_fail(flex_axw_bf16_clear_padding_launch(sum, h->n, h->c, h->cp, s));  // inf x 0 = NaN there
+        if (!rc) rc = mark(2);
+        if (!rc) rc = hip_fail(flex_axw_gemm_bf16_root_launch(dX, dR, h->dim, nullptr, nullptr, 0, sum, dBias, wf, dOut, h->n, h->c, h->cp, h->n_cus, s));
+    } else {
+        if (!rc) rc = mark(1);  // no dense stage before the SpMM
+        if (!rc) rc = flex_spmm_bf16(h->plan_dim, dX, ax, stream);
+        if (!rc) rc = mark(2);
+        if (!rc) rc = hip_fail(flex_axw_gemm_bf16_root_launch(ax, dW, h->dim, dX, dR, h->dim, nullptr, dBias, wf, dOut, h->n, h->c, h->cp, h->n_cus, s));
+    }
+    if (!rc) rc = mark(3);
+    if (!rc && timed) {  // the dense stages either side of the SpMM count as gemm
+        rc = hip_fail(hipEventSynchronize(h->ev[3]));
+        float a = 0.f, b = 0.f, d = 0.f;
+        if (!rc) rc = hip_fail(hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
+        if (!rc) rc = hip_fail(hipEventElapsedTime(&b, h->ev[1], h->ev[2]));
+        if (!rc) rc = hip_fail(hipEventElapsedTime(&d, h->ev[2], h->ev[3]));
+        if (gemm_ms) *gemm_ms = a + d;
+        if (spmm_ms) *spmm_ms = b;
     }
     if (cur >= 0 && cur != h->device) (void)hipSetDevice(cur);
     return rc;

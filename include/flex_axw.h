@@ -34,6 +34,11 @@ typedef struct flex_axw flex_axw;
                                    4096 (the input layer of a GCN) axw_bf16_wide_kernels.hip.  A width that is no multiple of 16 (602, 1433)
                                    is served by zero columns appended to X and zero rows to W: exact, a zero product adds nothing.  The raw FLEX_PLAN_BF16 bit in `flags` stays FLEX_ERR_INVALID */
 
+#define FLEX_AXW_ROOT 0x400000u /* flex_axw_create flag, with FLEX_AXW_BF16 only (FLEX_ERR_UNSUPPORTED without it): the handle also runs
+                                   flex_axw_run_root_bf16 (below).  It only adds buffers -- a second n x flex_axw_ld_bf16(c) intermediate and
+                                   2 dim x flex_axw_ld_bf16(c) elements for [W; R] as MFMA fragments; every other call behaves as on a handle
+                                   made without it */
+
 /* Leading dimension of Out and of the X*W intermediate: c rounded up to a multiple of 32 floats, so
  * that every row is a whole number of 128-byte cache lines (a row that starts mid-line costs each
  * gather one extra line: k=100 runs 50 % slower than k=128 on the reddit shape); the extra columns
@@ -94,6 +99,35 @@ int flex_axw_run(flex_axw *h, int order, const float *dX, const float *dW, float
  *   of tests/test_gpu_axw_bf16.py measures it (DESIGN.md 3.26 holds the figure). */
 int flex_axw_run_bf16(flex_axw *h, int order, const flex_bf16 *dX, const flex_bf16 *dW, flex_bf16 *dOut, flex_stream_t stream,
                       float *gemm_ms, float *spmm_ms);
+
+/* The bf16 layer with a root-weight (self) term and a bias, the layer of GraphSAGE, GraphConv, GIN and residual GCNs, on a handle made
+ * with FLEX_AXW_BF16 | FLEX_AXW_ROOT (FLEX_ERR_INVALID on any other):
+ *     Out[n x flex_axw_ld_bf16(c)] = A dX dW + dX dR + dBias
+ * dX [n x dim], dW and dR [dim x c] flex_bf16, dBias c floats (fp32, like the other per-column operands of this library) or NULL, all
+ * device, row-major, on `stream`; orders, the AUTO rule and the alignment of dX and dOut as for flex_axw_run_bf16; gemm_ms is the sum of
+ * the dense stages, spmm_ms the SpMM's.  No allocation, no host sync unless timed, no atomics: the same inputs give the same bits on
+ * every call, and on every replay of a hipGraph it was captured into; ONE call of a handle in flight at a time.  Forward only.
+ * Definition, every bf16 operand read as the fp32 number it is:
+ *     FLEX_AXW_AX_W:  T = flex_spmm_bf16(A, X),  Out = rn_bf16(T W + X R + b)   one launch of axw_bf16_root_kernels.hip, L1 = T, L2 = X
+ *     FLEX_AXW_A_XW:  U = rn_bf16(X W)           flex_axw_run_bf16's dense stage
+ *                     S = flex_spmm_bf16(A, U)   into the handle's second intermediate
+ *                     Out = rn_bf16(X R + S + b) the same kernel, L1 = X, W1 = R, no second source, addend S
+ * two bf16 roundings in AX_W, three in A_XW.  The dense stage Out = rn_bf16(L1 W1 + L2 W2 + Cin + b) is one fp32 chain per entry: the
+ * accumulator STARTS as fp32(Cin) + b (one addition; +0 where both are absent), then takes the k-steps of 16 in ascending order, all of
+ * L1 W1 before all of L2 W2 (v_mfma_f32_32x32x16_bf16), and is rounded once at the store.  Cin's padding columns are ignored.
+ * Accuracy (tests/axw_bf16_root_ref.py), u, gamma, n_r, bound_bf16 as for flex_axw_run_bf16, M = 1, TINY = 2^-149, eSpmm(T64) =
+ * bound_bf16(T64, gamma(n_r) |A||B| + n_r TINY), flex_spmm_bf16's bound of T64 = A B:
+ *   dense stage alone:  g = gamma(d1 + d2 + 2) (|L1||W1| + |L2||W2| + |Cin| + |b|) + (d1 + d2) TINY,   |Out - ref64| <= bound_bf16(ref64, g);
+ *   FLEX_AXW_AX_W:  T64 = A X, e1 = eSpmm(T64), ref = T64 W + X R + b:
+ *       |Out - ref| <= bound_bf16(ref, e1 |W| + gamma(2 dim + 2) ((|T64| + e1) |W| + |X||R| + |b|) + 2 dim TINY);
+ *   FLEX_AXW_A_XW:  U64 = X W, eU = bound_bf16(U64, gamma(dim) |X||W| + dim TINY), S64 = A U64,
+ *                   eS = bound_bf16(S64, |A| eU + gamma(n_r) |A| (|U64| + eU) + n_r TINY), ref = S64 + X R + b:
+ *       |Out - ref| <= bound_bf16(ref, eS + gamma(dim + 2) (|X||R| + |S64| + eS + |b|) + dim TINY);
+ *   NaN / +inf / -inf exactly where ref has them, except that a rounding may overflow as flex_spmm_bf16 states; padding columns +0 bits in
+ *   every case.  Normal inputs and sums, and the matrix unit's one rounding per addition, as for flex_axw_run_bf16.  The bounds are
+ *   derived; DESIGN.md 3.29 holds what tests/test_gpu_axw_bf16_root.py measured against them. */
+int flex_axw_run_root_bf16(flex_axw *h, int order, const flex_bf16 *dX, const flex_bf16 *dW, const flex_bf16 *dR,
+                           const float *dBias /* c floats or NULL */, flex_bf16 *dOut, flex_stream_t stream, float *gemm_ms, float *spmm_ms);
 
 /* The layer's gradients, for a handle made with FLEX_AXW_BACKWARD (FLEX_ERR_INVALID otherwise):
  *     G = A^T dOut (one flex_spmm of the transposed plan, k = c),  dGradX[n x dim] = G W^T,  dGradW[dim x c] = X^T G,

@@ -10,7 +10,12 @@
                                  dX; the stages are their differences (A^T dOut = no-dW + no-dX - both, dX = both - no-dX, dW = both - no-dW),
                                  the dense ones against their streaming floor (n dim + n cp) 2 bytes / HBM_RATE.
     probe_axw.py --bf16-wide     both tables at input-layer widths (axw_bf16_wide_kernels.hip): flickr at dim 512 and reddit at dim 608 (602
-                                 padded), c = 128 and 64, in the order AUTO picks there, A (X W); the fp32 handle runs rocBLAS at dim > 256."""
+                                 padded), c = 128 and 64, in the order AUTO picks there, A (X W); the fp32 handle runs rocBLAS at dim > 256.
+    probe_axw.py --bf16-root     the layer with a root term, A X W + X R + b (flex_axw_run_root_bf16), in both orders against what a handle
+                                 without FLEX_AXW_ROOT offers -- Axw.run(X, W) in its AUTO order, then torch's bf16 X @ R, the add and the
+                                 bias -- alternated in this process on flickr at (128, 128), (512, 128) and reddit at (128, 128), (608, 128):
+                                 medians of event times of the whole calls and of the new call's stages, the dual-source stage of (A X) W
+                                 against its streaming floor (2 n dim + n cp) 2 bytes / HBM_RATE."""
 import os
 import sys
 
@@ -135,6 +140,53 @@ def backward_table(shapes=NARROW):
             h32.destroy()
             h16.destroy()
 
+
+ROOT = {"flickr": ((128, 128), (512, 128)), "reddit": ((128, 128), (608, 128))}
+
+
+def root_table(shapes=ROOT):
+    def whole(f):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        f()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e3
+
+    orders = (axw.FLEX_AXW_A_XW, axw.FLEX_AXW_AX_W)
+    print("| graph | dim | c | run + X@R + add + bias | A(XW) gemm | A(XW) spmm | A(XW) call | (AX)W gemm | (AX)W spmm | (AX)W call | "
+          "A(XW) / parent | (AX)W / parent | dual floor | (AX)W gemm / floor |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|---|---|")
+    for name in shapes:
+        a = flex_amd.synth_graph(name)
+        for dim, c in shapes[name]:
+            h = axw.Axw(a, dim, c, bf16=True, root=True)
+            X = (torch.rand((a.n, dim), device="cuda") * 2 - 1).bfloat16()
+            W, R = (torch.rand((dim, c), device="cuda").bfloat16() for _ in range(2))
+            bias = torch.rand(c, device="cuda")
+            bias16 = bias.bfloat16()
+            parent = lambda: h.run(X, W)[:, :c] + X @ R + bias16  # noqa: E731  (the flag changes nothing in run())
+            t = {k: [] for k in ("parent", *orders, *((o, "stages") for o in orders))}
+            for i in range(REPS + 5):  # alternated; the first five of each are warm-up
+                got = {"parent": whole(parent)}
+                for o in orders:
+                    got[o] = whole(lambda: h.run_root(X, W, R, bias, o))
+                    g, s = h.run_root(X, W, R, bias, o, timed=True)[1]
+                    got[o, "stages"] = (g * 1e3, s * 1e3)
+                if i >= 5:
+                    for k, v in got.items():
+                        t[k].append(v)
+            par, c1, c2 = (float(np.median(t[k])) for k in ("parent", *orders))
+            (g1, s1), (g2, s2) = (np.median(t[o, "stages"], axis=0) for o in orders)
+            floor = (2 * a.n * dim + a.n * h.ld) * 2 / HBM_RATE * 1e6
+            print(f"| {name} | {dim} | {c} | {par:.1f} | {g1:.1f} | {s1:.1f} | {c1:.1f} | {g2:.1f} | {s2:.1f} | {c2:.1f} | {c1 / par:.2f} | "
+                  f"{c2 / par:.2f} | {floor:.1f} | {g2 / floor:.2f} |", flush=True)
+            h.destroy()
+
+
+if "--bf16-root" in sys.argv[1:]:
+    root_table()
+    sys.exit(0)
 
 if "--bf16-wide" in sys.argv[1:]:
     bf16_table(WIDE, (axw.FLEX_AXW_A_XW,))
