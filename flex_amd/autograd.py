@@ -1,6 +1,7 @@
 """torch autograd over the engine: the gradient of C = A B with respect to B is A^T grad_C (a plan made with FLEX_PLAN_TRANSPOSE; on
 bfloat16 operands with SparseOperator(..., bf16=True): FLEX_PLAN_BF16 plans and flex_spmm_bf16, both ways),
-and the GCN layer Out = A X W (flex_amd.axw.Axw.layer) differentiates through flex_axw_backward.  With learn_values=True, SparseOperator
+and the GCN layer Out = A X W (flex_amd.axw.Axw.layer) differentiates through flex_axw_backward, its bf16 form with a root weight and a bias
+(Axw.root_layer: A X W + X R + b) through flex_axw_backward_root_bf16.  With learn_values=True, SparseOperator
 is differentiable in A's values as well: grad_v = SDDMM(grad_C, B) over A's pattern (flex_sddmm), and the values of every forward are
 set into the plans (flex_plan_set_values) without planning again.  The same two plans run a graph-attention layer end to end:
 scores by flex_sddmm as a forward op, their softmax over each row of A (flex_edge_softmax), and the SpMM with the result as A's values
@@ -253,6 +254,44 @@ def functions():
     if _cache is None:
         _cache = _function()
     return _cache
+
+
+def _axw_root_function():
+    import torch
+
+    class _AxwRootLayer(torch.autograd.Function):
+        """Out = A X W + X R + bias on a bf16 handle (Axw.run_root); backward: the one call flex_axw_backward_root_bf16.  dW and dR come from
+        one kernel: whichever of the two autograd did not ask for is dropped."""
+
+        @staticmethod
+        def forward(ctx, X, W, R, bias, h, order):
+            X, W, R = X.contiguous(), W.contiguous(), R.contiguous()
+            ctx.h = h
+            ctx.save_for_backward(X, W, R)
+            return h.run_root(X, W, R, None if bias is None else bias.contiguous(), order)[:, : h.c]
+
+        @staticmethod
+        def backward(ctx, grad_out):
+            X, W, R = ctx.saved_tensors
+            h = ctx.h
+            need = ctx.needs_input_grad
+            dOut = torch.zeros((h.n, h.ld), dtype=torch.bfloat16, device=grad_out.device)
+            dOut[:, : h.c] = grad_out
+            gx, gw, gr, gb = h.backward_root(dOut, X, W, R, need_x=need[0], need_w=need[1] or need[2], need_b=need[3])
+            return gx, gw if need[1] else None, gr if need[2] else None, gb, None, None
+
+    return (_AxwRootLayer,)
+
+
+_axw_root_cache = None
+
+
+def axw_root_functions():
+    """(_AxwRootLayer,): built at first use, as functions()."""
+    global _axw_root_cache
+    if _axw_root_cache is None:
+        _axw_root_cache = _axw_root_function()
+    return _axw_root_cache
 
 
 def _dropout_function():

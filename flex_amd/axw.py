@@ -51,6 +51,12 @@ def lib():
         L.flex_axw_run_root_bf16.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.flex_axw_gemm_bf16_root_launch.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
         L.flex_axw_gemm_bf16_root_launch.restype = C.c_int
+        L.flex_axw_backward_root_bf16.argtypes = [vp] * 10
+        L.flex_axw_dx_bf16_root_launch.argtypes = [vp] * 6 + [C.c_int] * 5 + [vp]
+        L.flex_axw_dx_bf16_root_launch.restype = C.c_int
+        L.flex_axw_dw_bf16_root_launch.argtypes = [vp] * 7 + [C.c_int] * 5 + [vp]
+        L.flex_axw_dw_bf16_root_launch.restype = C.c_int
+        L.flex_axw_dw_bf16_root_slices.argtypes = [C.c_int] * 4
         _lib = L
     return _lib
 
@@ -110,6 +116,27 @@ def _gemm_bf16_root_launch(L1_ptr: int, W1_ptr: int, d1: int, L2_ptr, W2_ptr, d2
     return lib().flex_axw_gemm_bf16_root_launch(L1_ptr, W1_ptr, d1, L2_ptr, W2_ptr, d2, Cin_ptr, bias_ptr, Wf_ptr, Out_ptr, n, c, cp, n_cus, stream)
 
 
+def _dx_bf16_root_launch(G_ptr: int, W_ptr: int, dOut_ptr: int, R_ptr: int, Wf_ptr: int, dX_ptr: int, n: int, c: int, cp: int, dim: int,
+                         n_cus: int, stream: int = 0) -> int:
+    """The dX product of flex_axw_backward_root_bf16 on its own (flex_axw_dx_bf16_root_launch): bf16 dX[n x dim] = G[n x cp] @ W[dim x c].T +
+    dOut[n x cp] @ R[dim x c].T in one fp32 chain, dim any multiple of 32 up to 4096, through the scratch Wf (2 dim x cp elements).  Returns the
+    hipError_t; for tests."""
+    return lib().flex_axw_dx_bf16_root_launch(G_ptr, W_ptr, dOut_ptr, R_ptr, Wf_ptr, dX_ptr, n, c, cp, dim, n_cus, stream)
+
+
+def _dw_bf16_root_launch(X_ptr, G_ptr: int, dOut_ptr: int, dW_ptr, dR_ptr, db_ptr, part_ptr: int, n: int, dim: int, c: int, cp: int, n_cus: int,
+                         stream: int = 0) -> int:
+    """The one-pass kernel of flex_axw_backward_root_bf16 on its own (flex_axw_dw_bf16_root_launch): bf16 dW = X.T @ G and dR = X.T @ dOut
+    [dim x c] and fp32 db = dOut.sum(0) [c] through the fp32 partials `part` (_dw_bf16_root_slices(n, dim, c, n_cus) x (2 dim c + c) floats);
+    an output that is None is not written.  Returns the hipError_t; for tests."""
+    return lib().flex_axw_dw_bf16_root_launch(X_ptr, G_ptr, dOut_ptr, dW_ptr, dR_ptr, db_ptr, part_ptr, n, dim, c, cp, n_cus, stream)
+
+
+def _dw_bf16_root_slices(n: int, dim: int, c: int, n_cus: int) -> int:
+    """n-slices of the one-pass dW / dR / db kernel (flex_axw_dw_bf16_root_slices): at most n / (4 c)."""
+    return lib().flex_axw_dw_bf16_root_slices(n, dim, c, n_cus)
+
+
 class Axw:
     """flex_axw handle: plans A for both SpMM widths once; run() computes A @ X @ W in either order."""
 
@@ -147,7 +174,7 @@ class Axw:
     def run_root(self, X, W, R, bias=None, order: int = FLEX_AXW_AUTO, timed: bool = False):
         """flex_axw_run_root_bf16: A @ X @ W + X @ R + bias with one rounding after the last sum.  X [n, dim], W and R [dim, c]: contiguous
         cuda torch.bfloat16; bias: float32 [c] or None (anything else: TypeError).  Returns Out [n, ld] in bfloat16 (columns >= c are zero)
-        and, if timed, (gemm_ms, spmm_ms).  Forward only: no autograd."""
+        and, if timed, (gemm_ms, spmm_ms).  No autograd: root_layer() is the differentiable form."""
         import torch
         if not self.has_root:
             raise binding.FlexError("Axw.run_root: the handle was made without root=True (FLEX_AXW_ROOT)")
@@ -194,6 +221,38 @@ class Axw:
             raise binding.FlexError("Axw.layer: the handle was made without backward=True (FLEX_AXW_BACKWARD)")
         from .autograd import functions
         return functions()[1].apply(X, W, self, order)
+
+    def backward_root(self, dOut, X, W, R, need_x: bool = True, need_w: bool = True, need_b: bool = True):
+        """flex_axw_backward_root_bf16: dOut [n, ld] -> (dX [n, dim], dW [dim, c], dR [dim, c], db [c] float32), each None unless asked for:
+        dX = A^T dOut W^T + dOut R^T in one chain, dW = X^T (A^T dOut), dR = X^T dOut, db = dOut.sum(0).  dW and dR come together (need_w).
+        X, W and R are the forward's inputs (only the ones a requested gradient needs); torch.bfloat16 (any other dtype: TypeError);
+        dOut's padding columns are read and must be finite."""
+        import torch
+        if not (self.has_backward and self.has_root):
+            raise binding.FlexError("Axw.backward_root: the handle was made without backward=True and root=True")
+        given = [t for t, need in ((dOut, True), (X, need_w), (W, need_x), (R, need_x)) if need]
+        if any(t.dtype != torch.bfloat16 for t in given):
+            raise TypeError(f"Axw.backward_root takes torch.bfloat16 dOut, X, W and R; got {[str(t.dtype) for t in given]}")
+        assert dOut.is_cuda and dOut.is_contiguous() and tuple(dOut.shape) == (self.n, self.ld)
+        for t, need, shape in ((X, need_w, (self.n, self.dim)), (W, need_x, (self.dim, self.c)), (R, need_x, (self.dim, self.c))):
+            if need:
+                assert t.is_cuda and t.is_contiguous() and tuple(t.shape) == shape
+        new = lambda need, shape, dtype=torch.bfloat16: torch.empty(shape, dtype=dtype, device=dOut.device) if need else None  # noqa: E731
+        gx, gw, gr = new(need_x, (self.n, self.dim)), new(need_w, (self.dim, self.c)), new(need_w, (self.dim, self.c))
+        gb = new(need_b, (self.c,), torch.float32)
+        ptr = lambda t, need=True: t.data_ptr() if need and t is not None else None  # noqa: E731
+        binding._check(lib().flex_axw_backward_root_bf16(self._h, ptr(X, need_w), ptr(W, need_x), ptr(R, need_x), dOut.data_ptr(), ptr(gx), ptr(gw),
+                                                         ptr(gr), ptr(gb), torch.cuda.current_stream(dOut.device).cuda_stream),
+                       "flex_axw_backward_root_bf16")
+        return gx, gw, gr, gb
+
+    def root_layer(self, X, W, R, bias=None, order: int = FLEX_AXW_AUTO):
+        """Differentiable A X W + X R + bias: Out [n, c] (a view of run_root()'s padded product); its gradient flows to X, W, R and bias
+        through backward_root().  X, W, R, Out and their gradients are torch.bfloat16, bias and its gradient float32."""
+        if not (self.has_backward and self.has_root):
+            raise binding.FlexError("Axw.root_layer: the handle was made without backward=True and root=True")
+        from .autograd import axw_root_functions
+        return axw_root_functions()[0].apply(X, W, R, bias, self, order)
 
     def destroy(self):
         if getattr(self, "_h", None) and self._h.value:

@@ -36,6 +36,12 @@ extern "C" int flex_axw_dw_bf16_wide_slices(int n, int dim, int c, int n_cus);
 extern "C" hipError_t flex_axw_gemm_bf16_root_launch(const flex_bf16 *L1, const flex_bf16 *W1, int d1, const flex_bf16 *L2, const flex_bf16 *W2,
                                                      int d2, const flex_bf16 *Cin, const float *bias, flex_bf16 *Wf, flex_bf16 *Out, int n, int c,
                                                      int cp, int n_cus, hipStream_t s);  // axw_bf16_root_kernels.hip
+extern "C" hipError_t flex_axw_dx_bf16_root_launch(const flex_bf16 *G, const flex_bf16 *W, const flex_bf16 *dOut, const flex_bf16 *R,
+                                                   flex_bf16 *Wf, flex_bf16 *dX, int n, int c, int cp, int dim, int n_cus, hipStream_t s);
+extern "C" hipError_t flex_axw_dw_bf16_root_launch(const flex_bf16 *X, const flex_bf16 *G, const flex_bf16 *dOut, flex_bf16 *dW, flex_bf16 *dR,
+                                                   float *db, float *part, int n, int dim, int c, int cp, int n_cus,
+                                                   hipStream_t s);  // axw_bf16_root_backward_kernels.hip
+extern "C" int flex_axw_dw_bf16_root_slices(int n, int dim, int c, int n_cus);
 
 struct flex_axw {
     int32_t n = 0;
@@ -181,7 +187,9 @@ int flex_axw_create(flex_axw **out, const flex_csr *A, int dim, int c, int devic
         const int k8 = (c + 7) / 8 * 8;
         const size_t wt = static_cast<size_t>(h->cp) * dim;
         const int slices = h->wide ? flex_axw_dw_bf16_wide_slices(h->n, dim, c, h->n_cus) : flex_axw_dw_bf16_slices(h->n, h->n_cus);
-        const size_t part = static_cast<size_t>(std::max(1, slices)) * dim * c;
+        size_t part = static_cast<size_t>(std::max(1, slices)) * dim * c;
+        if (root)  // flex_axw_backward_root_bf16's partials: [dW | dR | db] a slice, under a slice rule of their own
+            part = std::max(part, static_cast<size_t>(std::max(1, flex_axw_dw_bf16_root_slices(h->n, dim, c, h->n_cus))) * (2 * static_cast<size_t>(dim) * c + c));
         rc = flex_plan_create_ld(&h->plan_t, A, k8, h->cp, h->cp, device, flags | FLEX_PLAN_TRANSPOSE);
         if (!rc) rc = hip_fail(hipMalloc(reinterpret_cast<void **>(&h->d_g), n1 * h->cp * es));
         if (!rc) rc = hip_fail(hipMemset(h->d_g, 0, n1 * h->cp * es));
@@ -410,6 +418,38 @@ int flex_axw_backward_bf16(flex_axw *h, const flex_bf16 *dX, const flex_bf16 *dW
     if (!rc && dGradW)
         rc = hip_fail((h->wide ? flex_axw_dw_bf16_wide_launch : flex_axw_dw_bf16_launch)(dX, g, dGradW, h->d_part, h->n, h->dim, h->c, h->cp,
                                                                                          h->n_cus, s));
+    if (cur >= 0 && cur != h->device) (void)hipSetDevice(cur);
+    return rc;
+}
+
+// The backward of flex_axw_run_root_bf16: G = A^T dOut as flex_axw_backward_bf16, then dGradX = rn_bf16(G W^T + dOut R^T) in one chain (the
+// window form of axw_bf16_root_kernels.hip, [W^T; R^T] packed into the handle's d_wf: no d_wt and no transpose launch), and dGradW, dGradR
+// and dGradBias from one pass over X (axw_bf16_root_backward_kernels.hip).  Everything is queued on `stream`: no allocation, no host sync.
+int flex_axw_backward_root_bf16(flex_axw *h, const flex_bf16 *dX, const flex_bf16 *dW, const flex_bf16 *dR, const flex_bf16 *dOut,
+                                flex_bf16 *dGradX, flex_bf16 *dGradW, flex_bf16 *dGradR, float *dGradBias, flex_stream_t stream) {
+    if (!h || !h->bf16 || !h->plan_t || !h->d_wf || !dOut || (dGradW != nullptr) != (dGradR != nullptr) || (dGradX && (!dW || !dR)) ||
+        (dGradW && !dX))
+        return FLEX_ERR_INVALID;
+    for (const void *p : {static_cast<const void *>(dOut), static_cast<const void *>(dGradX), static_cast<const void *>(dGradW),
+                          static_cast<const void *>(dGradR), static_cast<const void *>(dGradX ? dW : nullptr),
+                          static_cast<const void *>(dGradX ? dR : nullptr), static_cast<const void *>(dGradW ? dX : nullptr)})
+        if (reinterpret_cast<uintptr_t>(p) & 15) return FLEX_ERR_UNSUPPORTED;
+    if (reinterpret_cast<uintptr_t>(dGradBias) & 3) return FLEX_ERR_UNSUPPORTED;
+    if (!dGradX && !dGradW && !dGradBias) return FLEX_OK;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    flex_bf16 *g = reinterpret_cast<flex_bf16 *>(h->d_g), *wf = reinterpret_cast<flex_bf16 *>(h->d_wf);
+    int cur = -1;
+    (void)hipGetDevice(&cur);
+    int rc = hip_fail(hipSetDevice(h->device));
+    if (dGradX || dGradW) {  // dGradBias alone needs no G
+        if (!rc) rc = flex_spmm_bf16(h->plan_t, dOut, g, stream);
+        // inf x 0 = NaN in G's padding columns would meet the zero rows of W^T, as in flex_axw_backward_bf16
+        if (!rc && h->a_nonfinite) rc = hip_fail(flex_axw_bf16_clear_padding_launch(g, h->n, h->c, h->cp, s));
+    }
+    if (!rc && dGradX) rc = hip_fail(flex_axw_dx_bf16_root_launch(g, dW, dOut, dR, wf, dGradX, h->n, h->c, h->cp, h->dim, h->n_cus, s));
+    if (!rc && (dGradW || dGradBias))
+        rc = hip_fail(flex_axw_dw_bf16_root_launch(dGradW ? dX : nullptr, g, dOut, dGradW, dGradR, dGradBias, h->d_part, h->n, h->dim, h->c, h->cp,
+                                                   h->n_cus, s));
     if (cur >= 0 && cur != h->device) (void)hipSetDevice(cur);
     return rc;
 }

@@ -25,6 +25,8 @@
 //   * Cin must not overlap Out: the overlapping last panel is computed twice over the rows it shares with its predecessor, and an
 //     in-place Cin would be added twice there.  The launcher refuses the overlap.
 // Panels a wave: P = 2 at cp = 64 (NT = 2), else 1, as the wide kernel (the compiler's report is in DESIGN.md 3.29: no scratch anywhere).
+// The same kernel, instantiated with kWindow, is the dX of the layer's backward (flex_axw_backward_root_bf16; flex_axw_dx_bf16_root_launch at
+// the end of this file): dX = rn_bf16(G W^T + dOut R^T) in 256-column passes over a transposing pack of [W^T; R^T].
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -61,7 +63,11 @@ __global__ __launch_bounds__(256) void axw_bf16_root_pack_kernel(const flex_bf16
     Wf[f] = u32x4{v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16), v[6] | (v[7] << 16)};
 }
 
-template <int NT, int P>  // 32-column tiles of Out, panels a wave
+// kWindow (the dual-source dX of flex_axw_backward_root_bf16, below): Out is a window of 32 NT whole columns, from 256 blockIdx.y on, of an
+// array whose rows are `c` elements apart (the parameter carries the row stride: a window has no padding to mask), Wf holds one
+// fragment stream of (d1 + d2) / 16 k-steps per 256-column pass, and there is neither a Cin nor a bias: the chain starts from +0.  The
+// instantiations with kWindow = false compile to the instructions they had before the switch existed.
+template <int NT, int P, bool kWindow = false>  // 32-column tiles of Out, panels a wave
 __global__ __launch_bounds__(64 * kWaves) void axw_gemm_bf16_root_kernel(const flex_bf16 *__restrict__ L1, int d1, const flex_bf16 *__restrict__ L2,
                                                                          int d2, const u32x4 *__restrict__ Wf, const flex_bf16 *__restrict__ Cin,
                                                                          const float *__restrict__ bias, flex_bf16 *__restrict__ Out, int n,
@@ -72,6 +78,10 @@ __global__ __launch_bounds__(64 * kWaves) void axw_gemm_bf16_root_kernel(const f
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // in an SGPR, and so is every panel's row
     const int j = lane & 31, h = lane >> 5;
     const int s1 = d1 >> 4, steps = (d1 + d2) >> 4, slabs = (steps + kSlab - 1) / kSlab;
+    if constexpr (kWindow) {
+        Wf += static_cast<size_t>(blockIdx.y) * steps * (8 * 64);  // a full pass is 8 tiles wide
+        Out += 256 * blockIdx.y;
+    }
     const int n_panels = (n + kRows - 1) / kRows;
     const int n_rounds = (n_panels + kWaves * P - 1) / (kWaves * P);  // gridDim.x <= n_rounds: every workgroup has a round
     auto panel_of = [&](int round, int p) { return (round * P + p) * kWaves + wave; };
@@ -107,7 +117,8 @@ __global__ __launch_bounds__(64 * kWaves) void axw_gemm_bf16_root_kernel(const f
             }
         }
     }
-    if (tid < cp) sBias[tid] = bias && tid < c ? bias[tid] : 0.f;
+    if constexpr (!kWindow)
+        if (tid < cp) sBias[tid] = bias && tid < c ? bias[tid] : 0.f;
     __syncthreads();  // sBias is read before a round's first slab barrier
 
     int buf = 0;
@@ -123,7 +134,12 @@ __global__ __launch_bounds__(64 * kWaves) void axw_gemm_bf16_root_kernel(const f
                 acc[p][t][4 * g + 2] = __uint_as_float(v[1] << 16) + b[2];
                 acc[p][t][4 * g + 3] = __uint_as_float(v[1] & 0xFFFF0000u) + b[3];
             };
-            if (Cin) {  // workgroup-uniform
+            if constexpr (kWindow) {
+#pragma unroll
+                for (int t = 0; t < NT; ++t)
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) acc[p][t][i] = 0.f;
+            } else if (Cin) {  // workgroup-uniform
                 const flex_bf16 *crow = Cin + static_cast<size_t>(panel_row(panel_of(round, p))) * cp + (j * cp + 4 * h);
 #pragma unroll
                 for (int t = 0; t < NT; ++t)
@@ -177,15 +193,61 @@ __global__ __launch_bounds__(64 * kWaves) void axw_gemm_bf16_root_kernel(const f
         for (int p = 0; p < P; ++p) {
             const int panel = panel_of(round, p);
             if (panel >= n_panels) continue;  // wave-uniform: the round's panels past the end were multiplied as copies of the last
-            flex_bf16 *dst = Out + static_cast<size_t>(panel_row(panel) + j) * cp + 16 * h;
             const f32x16(&panel_acc)[NT] = acc[p];  // the macro has a loop variable p of its own
-            FLEX_AXW_BF16_STORE_PANEL(NT, panel_acc, dst, c, h)
+            if constexpr (kWindow) {
+                flex_bf16 *dst = Out + static_cast<size_t>(panel_row(panel) + j) * c + 16 * h;
+                FLEX_AXW_BF16_STORE_PANEL(NT, panel_acc, dst, cp, h)
+            } else {
+                flex_bf16 *dst = Out + static_cast<size_t>(panel_row(panel) + j) * cp + 16 * h;
+                FLEX_AXW_BF16_STORE_PANEL(NT, panel_acc, dst, c, h)
+            }
         }
     }
 }
 
+// The transposing pack of the dual-source dX: the stream [W^T; R^T] (2 cp / 16 k-steps, rows c .. cp-1 of either zero) of every 256-column
+// pass of dX, pass after pass, into Wf (2 dim x cp elements in all).  Fragment (pass p, k-step s, tile t, lane) holds
+// Wsrc[256 p + 32 t + (lane & 31)][k .. k + 7], k = 16 s + 8 (lane >> 5) in W for k < cp and in R, set back by cp, after that: eight
+// consecutive elements of one row -- one 16-byte load where c % 8 == 0 and both pointers are 16-byte aligned (`vec`: k + 8 <= c or k >= c,
+// a fragment is whole or zero), eight 2-byte loads otherwise.  A narrower last pass has dim / 32 % 8 tiles; its fragments are fewer than
+// a full pass's, so f / (fragments of a full pass) names the pass of every fragment.  One thread a fragment.
+__global__ __launch_bounds__(256) void axw_bf16_root_pack_t_kernel(const flex_bf16 *__restrict__ W, const flex_bf16 *__restrict__ R,
+                                                                   u32x4 *__restrict__ Wf, int c, int cp, int dim, bool vec) {
+    const int f = blockIdx.x * 256 + threadIdx.x, steps = cp >> 3, pass_frags = steps * 8 * 64;
+    if (f >= steps * (dim >> 5) * 64) return;
+    const int p = f / pass_frags, rem = f - p * pass_frags, nt = min(8, (dim >> 5) - 8 * p);
+    const int lane = rem & 63, t = (rem >> 6) % nt, s = (rem >> 6) / nt;
+    const int row = 256 * p + 32 * t + (lane & 31), kk = 16 * s + 8 * (lane >> 5), k = kk < cp ? kk : kk - cp;
+    const flex_bf16 *src = (kk < cp ? W : R) + static_cast<size_t>(row) * c + k;
+    u32x4 v = {0u, 0u, 0u, 0u};
+    if (vec) {
+        if (k < c) v = *reinterpret_cast<const u32x4 *>(src);
+    } else {
+        uint32_t e[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) e[i] = k + i < c ? src[i] : 0u;
+        v = u32x4{e[0] | (e[1] << 16), e[2] | (e[3] << 16), e[4] | (e[5] << 16), e[6] | (e[7] << 16)};
+    }
+    Wf[f] = v;
+}
+
 inline bool misaligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
 inline bool width(int d, int least) { return d >= least && d <= 4096 && d % 16 == 0; }
+
+// one launch of the window kernel: `passes` windows of 32 NT columns of dX from column col0 on, their streams from wf on
+template <int NT>
+hipError_t launch_window(const flex_bf16 *G, const flex_bf16 *dOut, const u32x4 *wf, flex_bf16 *dX, int n, int cp, int dim, int passes, int n_cus,
+                         hipStream_t s) {
+    constexpr int P = NT <= 2 ? 2 : 1;  // panels a wave, as the forward: two while the accumulators are 64 registers or fewer
+    const auto kernel = axw_gemm_bf16_root_kernel<NT, P, true>;
+    const size_t lds = static_cast<size_t>(2) * kSlab * NT * 64 * sizeof(u32x4);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+    if (e != hipSuccess) return e;
+    const int n_panels = (n + kRows - 1) / kRows, n_rounds = (n_panels + kWaves * P - 1) / (kWaves * P);
+    hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(std::min(n_cus, n_rounds)), static_cast<unsigned>(passes)), dim3(64 * kWaves), lds, s, G,
+                       cp, dOut, cp, wf, static_cast<const flex_bf16 *>(nullptr), static_cast<const float *>(nullptr), dX, n, dim);
+    return hipGetLastError();
+}
 
 }  // namespace flex_axw_bf16_root
 
@@ -227,4 +289,36 @@ extern "C" hipError_t flex_axw_gemm_bf16_root_launch(const flex_bf16 *L1, const 
         default: go(axw_gemm_bf16_root_kernel<8, 1>, kWaves); break;
     }
     return e;
+}
+
+// dX[n x dim] = rn_bf16(G[n x cp] W^T + dOut[n x cp] R^T), W and R [dim x c], on flex_bf16: the dX of flex_axw_backward_root_bf16.  One fp32
+// chain per entry: +0, all of G W^T in ascending k, then all of dOut R^T, one rounding; columns c .. cp-1 of G and of dOut are read (they
+// meet zero rows and must be finite).  dim / 256 passes of 256 columns are the grid's y dimension and a narrower last pass a launch of
+// its own (another instantiation: NT = 1 .. 7), through Wf (2 dim x cp elements of scratch: every pass's [W^T; R^T] stream).  Takes
+// n >= 32, cp % 64 == 0, 0 < c <= cp <= 256, 0 < dim <= 4096, dim % 32 == 0, n_cus > 0 and 16-byte aligned G, dOut, Wf and dX (W, R: any
+// flex_bf16 pointer); anything else returns hipErrorInvalidValue before a launch.
+extern "C" hipError_t flex_axw_dx_bf16_root_launch(const flex_bf16 *G, const flex_bf16 *W, const flex_bf16 *dOut, const flex_bf16 *R,
+                                                   flex_bf16 *Wf, flex_bf16 *dX, int n, int c, int cp, int dim, int n_cus, hipStream_t s) {
+    using namespace flex_axw_bf16_root;
+    if (!G || !W || !dOut || !R || !Wf || !dX || n < kRows || cp <= 0 || cp % 64 != 0 || cp > 256 || c <= 0 || c > cp || dim <= 0 || dim > 4096 ||
+        dim % 32 != 0 || n_cus <= 0 || misaligned(G) || misaligned(dOut) || misaligned(Wf) || misaligned(dX))
+        return hipErrorInvalidValue;
+    u32x4 *wf = reinterpret_cast<u32x4 *>(Wf);
+    const int frags = (cp / 8) * (dim / 32) * 64, full = dim / 256, tail = dim % 256;
+    const bool vec = c % 8 == 0 && !misaligned(W) && !misaligned(R);
+    hipLaunchKernelGGL(axw_bf16_root_pack_t_kernel, dim3(static_cast<unsigned>((frags + 255) / 256)), dim3(256), 0, s, W, R, wf, c, cp, dim, vec);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && full > 0) e = launch_window<8>(G, dOut, wf, dX, n, cp, dim, full, n_cus, s);
+    if (e != hipSuccess || tail == 0) return e;
+    const u32x4 *twf = wf + static_cast<size_t>(full) * (cp / 8) * 8 * 64;
+    flex_bf16 *tdx = dX + 256 * full;
+    switch (tail / 32) {
+        case 1: return launch_window<1>(G, dOut, twf, tdx, n, cp, dim, 1, n_cus, s);
+        case 2: return launch_window<2>(G, dOut, twf, tdx, n, cp, dim, 1, n_cus, s);
+        case 3: return launch_window<3>(G, dOut, twf, tdx, n, cp, dim, 1, n_cus, s);
+        case 4: return launch_window<4>(G, dOut, twf, tdx, n, cp, dim, 1, n_cus, s);
+        case 5: return launch_window<5>(G, dOut, twf, tdx, n, cp, dim, 1, n_cus, s);
+        case 6: return launch_window<6>(G, dOut, twf, tdx, n, cp, dim, 1, n_cus, s);
+        default: return launch_window<7>(G, dOut, twf, tdx, n, cp, dim, 1, n_cus, s);
+    }
 }

@@ -106,7 +106,8 @@ int flex_axw_run_bf16(flex_axw *h, int order, const flex_bf16 *dX, const flex_bf
  * dX [n x dim], dW and dR [dim x c] flex_bf16, dBias c floats (fp32, like the other per-column operands of this library) or NULL, all
  * device, row-major, on `stream`; orders, the AUTO rule and the alignment of dX and dOut as for flex_axw_run_bf16; gemm_ms is the sum of
  * the dense stages, spmm_ms the SpMM's.  No allocation, no host sync unless timed, no atomics: the same inputs give the same bits on
- * every call, and on every replay of a hipGraph it was captured into; ONE call of a handle in flight at a time.  Forward only.
+ * every call, and on every replay of a hipGraph it was captured into; ONE call of a handle in flight at a time.  Its backward is
+ * flex_axw_backward_root_bf16 (below).
  * Definition, every bf16 operand read as the fp32 number it is:
  *     FLEX_AXW_AX_W:  T = flex_spmm_bf16(A, X),  Out = rn_bf16(T W + X R + b)   one launch of axw_bf16_root_kernels.hip, L1 = T, L2 = X
  *     FLEX_AXW_A_XW:  U = rn_bf16(X W)           flex_axw_run_bf16's dense stage
@@ -175,6 +176,35 @@ int flex_axw_backward(flex_axw *h, const float *dX, const float *dW, const float
  *   products of a step rounds no more than once per addition; DESIGN.md 3.27 holds what the cancellation cases measured. */
 int flex_axw_backward_bf16(flex_axw *h, const flex_bf16 *dX, const flex_bf16 *dW, const flex_bf16 *dOut, flex_bf16 *dGradX, flex_bf16 *dGradW,
                            flex_stream_t stream);
+
+/* The backward of flex_axw_run_root_bf16, on a handle made with FLEX_AXW_BF16 | FLEX_AXW_ROOT | FLEX_AXW_BACKWARD (FLEX_ERR_INVALID on a
+ * handle that lacks any of the three), all device, row-major, on `stream`; dX [n x dim], dW and dR [dim x c] are the forward's inputs:
+ *     G         = flex_spmm_bf16(A^T, dOut)       n x flex_axw_ld_bf16(c), one rounding to bf16, as flex_axw_backward_bf16
+ *     dGradX    = rn_bf16(G W^T + dOut R^T)       n x dim     ONE fp32 chain per entry: +0, all of G W^T in ascending k, then all of
+ *                                                             dOut R^T, one rounding (axw_bf16_root_kernels.hip, 256-column passes)
+ *     dGradW    = rn_bf16(X^T G)                  dim x c     } one pass over X (axw_bf16_root_backward_kernels.hip): fp32 partial sums per
+ *     dGradR    = rn_bf16(X^T dOut)               dim x c     } n-slice, added in slice order, dGradW and dGradR rounded once,
+ *     dGradBias = 1^T dOut                        c floats    } dGradBias kept in fp32
+ * dGradW and dGradR come from one kernel and are asked for together: exactly one of them NULL is FLEX_ERR_INVALID.  dGradX and dGradBias
+ * are each optional, and an input is needed only for the outputs that use it: dW and dR for dGradX, dX for dGradW and dGradR, dOut always.
+ * Every flex_bf16 pointer passed must be 16-byte aligned (FLEX_ERR_UNSUPPORTED otherwise); nothing is enqueued in any refusal.  No
+ * allocation, no host sync (safe to capture in a hipGraph), no atomics: the same inputs give the same bits on every call; ONE call of a
+ * handle in flight at a time.  All of dOut's padding columns c .. flex_axw_ld_bf16(c)-1 are read and must be finite; they meet zero rows
+ * of R^T (and, through G, of W^T) and change no output bit.  With dR = 0, dGradX has the bits of flex_axw_backward_bf16's.
+ * Slices of the second kernel: rows = ceil(n / S0) rounded up to a multiple of 64, S0 = max(1, min(ceil(n / 256), floor(wgs CUs /
+ * (ceil(dim / 128) ceil(c / 128))), floor(n / (4 c)))), wgs = 2 while c <= 64, else 1; slices = ceil(n / rows): the partial sums of dGradW
+ * and dGradR stay below the bytes of X.
+ * Accuracy (tests/axw_bf16_root_backward_ref.py), cp, G64, eG, u, gamma, bound_bf16, M = 1 and TINY = 2^-149 as for flex_axw_backward_bf16:
+ *   the dX kernel alone:  g = gamma(2 cp + 2) (|G||W|^T + |dOut||R|^T) + 2 cp TINY,   |dX - ref64| <= bound_bf16(ref64, g);
+ *   dGradX:    ref = G64 W^T + dOut R^T,  |dGradX - ref| <= bound_bf16(ref, eG |W|^T + gamma(2 cp + 2) ((|G64| + eG) |W|^T + |dOut||R|^T)
+ *              + 2 cp TINY);
+ *   dGradW:    flex_axw_backward_bf16's statement with L = rows per slice + slices of the rule above;
+ *   dGradR:    the same with dOut in place of G64 and eG = 0;
+ *   dGradBias: |dGradBias - 1^T dOut| <= gamma(L) 1^T |dOut| + L TINY, the same L; no bf16 rounding.
+ *   NaN / +inf / -inf exactly where the reference has them, under flex_axw_run_bf16's conditions.  The bounds are derived; DESIGN.md 3.30
+ *   holds what tests/test_gpu_axw_bf16_root_backward.py measured against them. */
+int flex_axw_backward_root_bf16(flex_axw *h, const flex_bf16 *dX, const flex_bf16 *dW, const flex_bf16 *dR, const flex_bf16 *dOut,
+                                flex_bf16 *dGradX, flex_bf16 *dGradW, flex_bf16 *dGradR, float *dGradBias /* fp32 */, flex_stream_t stream);
 int flex_axw_destroy(flex_axw *h);
 /* last rocBLAS status seen (rocblas_status), for FLEX_ERR_UNSUPPORTED returns caused by rocBLAS */
 int flex_axw_last_blas_status(void);

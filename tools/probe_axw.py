@@ -15,7 +15,13 @@
                                  without FLEX_AXW_ROOT offers -- Axw.run(X, W) in its AUTO order, then torch's bf16 X @ R, the add and the
                                  bias -- alternated in this process on flickr at (128, 128), (512, 128) and reddit at (128, 128), (608, 128):
                                  medians of event times of the whole calls and of the new call's stages, the dual-source stage of (A X) W
-                                 against its streaming floor (2 n dim + n cp) 2 bytes / HBM_RATE."""
+                                 against its streaming floor (2 n dim + n cp) 2 bytes / HBM_RATE.
+    probe_axw.py --bf16-root-backward  the backward of that layer (flex_axw_backward_root_bf16) against what the handle offered before it --
+                                 Axw.backward, then torch's bf16 dOut @ R.T and the add into dX, X.T @ dOut and dOut.sum(0) -- alternated in
+                                 this process: medians of event times of the whole calls, of the new call without dW / dR and without dX
+                                 (the stages are their differences, as for --bf16-backward), the one-pass dW / dR / db launcher against two
+                                 launches of the one-product dW launcher, and the dense stages against their streaming floors
+                                 (2 n cp + n dim) 2 bytes / HBM_RATE."""
 import os
 import sys
 
@@ -183,6 +189,70 @@ def root_table(shapes=ROOT):
                   f"{c2 / par:.2f} | {floor:.1f} | {g2 / floor:.2f} |", flush=True)
             h.destroy()
 
+
+ROOT_BACKWARD = {"flickr": ((128, 128), (512, 128)), "reddit": ((128, 128), (608, 128), (256, 64))}
+
+
+def root_backward_table(shapes=ROOT_BACKWARD):
+    def whole(f):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        f()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e3
+
+    print("| graph | dim | c | parent composition | new call | new / parent | A^T dOut | dX | dW dR db | two dW launches | dual dW launch | "
+          "dual / two | dX / floor | dW / floor |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|---|---|")
+    for name in shapes:
+        a = flex_amd.synth_graph(name)
+        cus = torch.cuda.get_device_properties(0).multi_processor_count
+        for dim, c in shapes[name]:
+            h = axw.Axw(a, dim, c, bf16=True, backward=True, root=True)
+            n, cp = a.n, h.ld
+            X = (torch.rand((n, dim), device="cuda") * 2 - 1).bfloat16()
+            W, R = (torch.rand((dim, c), device="cuda").bfloat16() for _ in range(2))
+            d = torch.zeros((n, cp), dtype=torch.bfloat16, device="cuda")
+            d[:, :c] = (torch.rand((n, c), device="cuda") * 2 - 1).bfloat16()
+            G = d.clone()  # any finite right operand times the same for the launchers
+            dW, dR, db = torch.empty_like(W), torch.empty_like(R), torch.empty(c, device="cuda")
+            part = torch.empty(max(axw._dw_bf16_root_slices(n, dim, c, cus) * (2 * dim * c + c),
+                                   (axw._dw_bf16_wide_slices(n, dim, c, cus) if dim > 256 else axw.lib().flex_axw_dw_bf16_slices(n, cus)) * dim * c),
+                               device="cuda")
+            one = axw._dw_bf16_wide_launch if dim > 256 else axw._dw_bf16_launch
+            s = torch.cuda.current_stream().cuda_stream
+            p = lambda t: t.data_ptr()  # noqa: E731
+
+            def parent():
+                gx, gw = h.backward(d, X, W)
+                gx += d[:, :c] @ R.T
+                return gx, gw, X.T @ d[:, :c], d.sum(0)
+
+            def two():
+                for right, out in ((G, dW), (d, dR)):
+                    assert one(p(X), p(right), p(out), p(part), n, dim, c, cp, cus, s) == 0
+
+            runs = {"parent": parent, "new": lambda: h.backward_root(d, X, W, R), "no_w": lambda: h.backward_root(d, X, W, R, need_w=False, need_b=False),
+                    "no_x": lambda: h.backward_root(d, X, W, R, need_x=False), "two": two,
+                    "dual": lambda: axw._dw_bf16_root_launch(p(X), p(G), p(d), p(dW), p(dR), p(db), p(part), n, dim, c, cp, cus, s)}
+            t = {k: [] for k in runs}
+            for i in range(REPS + 5):  # alternated; the first five of each are warm-up
+                for k, f in runs.items():
+                    us = whole(f)
+                    if i >= 5:
+                        t[k].append(us)
+            m = {k: float(np.median(v)) for k, v in t.items()}
+            dx, dw = m["new"] - m["no_x"], m["new"] - m["no_w"]
+            fx, fw = (2 * n * cp + n * dim) * 2 / HBM_RATE * 1e6, (n * dim + 2 * n * cp) * 2 / HBM_RATE * 1e6
+            print(f"| {name} | {dim} | {c} | {m['parent']:.1f} | {m['new']:.1f} | {m['new'] / m['parent']:.2f} | {m['no_w'] + m['no_x'] - m['new']:.1f} | "
+                  f"{dx:.1f} | {dw:.1f} | {m['two']:.1f} | {m['dual']:.1f} | {m['dual'] / m['two']:.2f} | {dx / fx:.2f} | {dw / fw:.2f} |", flush=True)
+            h.destroy()
+
+
+if "--bf16-root-backward" in sys.argv[1:]:
+    root_backward_table()
+    sys.exit(0)
 
 if "--bf16-root" in sys.argv[1:]:
     root_table()
