@@ -7,9 +7,11 @@
 #include <cmath>
 #include <algorithm>
 #include <cstdint>
+#include <initializer_list>
 #include <new>
 
 #include "../../include/flex_axw.h"
+#include "device_scope.h"
 
 extern "C" hipError_t flex_axw_gemm_launch(const float *L, const float *Wp, float *Out, int n, int dim, int c, int cp, int n_cus,
                                            hipStream_t s);  // axw_kernels.hip
@@ -96,6 +98,48 @@ int gemm_rm(flex_axw *h, const float *L, float *Cout, hipStream_t s) {
     return Cout == h->d_xw ? FLEX_OK : zero_padding(h, Cout, s);
 }
 
+// W -> Wp: dim rows of c elements of `es` bytes into rows of cp elements (the zero padding was written once at create)
+int pad_w(flex_axw *h, const void *W, size_t es, hipStream_t s) {
+    return hip_fail(hipMemcpy2DAsync(h->d_wp, h->cp * es, W, h->c * es, h->c * es, static_cast<size_t>(h->dim), hipMemcpyDeviceToDevice, s));
+}
+
+// The stage marks of a call that may be timed: mark(i) records event i, read(last, ms) waits for event `last` and sets ms[i] to the time
+// from event i to event i + 1.  Neither does anything when the call is not timed.
+struct Marks {
+    flex_axw *h;
+    hipStream_t s;
+    bool timed;
+    int operator()(int i) const { return timed ? hip_fail(hipEventRecord(h->ev[i], s)) : FLEX_OK; }
+    int read(int last, float *ms) const {
+        int rc = timed ? hip_fail(hipEventSynchronize(h->ev[last])) : FLEX_OK;
+        for (int i = 0; timed && i < last && !rc; ++i) rc = hip_fail(hipEventElapsedTime(&ms[i], h->ev[i], h->ev[i + 1]));
+        return rc;
+    }
+};
+
+bool misaligned16(std::initializer_list<const void *> ptrs) {
+    for (const void *p : ptrs)
+        if (reinterpret_cast<uintptr_t>(p) & 15) return true;
+    return false;
+}
+
+// the dense stage of the bf16 layer, Out = L W: the resident-W kernel on Wp (pad_w comes first) or, wide, the streamed one, which packs W
+// into d_wp itself
+int dense_bf16(flex_axw *h, const flex_bf16 *L, const flex_bf16 *W, flex_bf16 *Out, hipStream_t s) {
+    flex_bf16 *wp = reinterpret_cast<flex_bf16 *>(h->d_wp);
+    return hip_fail(h->wide ? flex_axw_gemm_bf16_wide_launch(L, W, wp, Out, h->n, h->dim, h->c, h->cp, h->n_cus, s)
+                            : flex_axw_gemm_bf16_launch(L, wp, Out, h->n, h->dim, h->c, h->cp, h->n_cus, s));
+}
+
+// G = A^T dOut rounded once to bf16 (the transposed plan), for both bf16 backwards.  A non-finite A: inf x 0 = NaN in G's padding
+// columns would meet the zero rows of W^T -- a NaN row of dGradX where the reference has inf -- so they are cleared
+int grad_aggregate_bf16(flex_axw *h, const flex_bf16 *dOut, flex_stream_t stream) {
+    flex_bf16 *g = reinterpret_cast<flex_bf16 *>(h->d_g);
+    int rc = flex_spmm_bf16(h->plan_t, dOut, g, stream);
+    if (!rc && h->a_nonfinite) rc = hip_fail(flex_axw_bf16_clear_padding_launch(g, h->n, h->c, h->cp, reinterpret_cast<hipStream_t>(stream)));
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -108,9 +152,7 @@ int flex_axw_last_blas_status(void) { return g_blas_status; }
 
 int flex_axw_destroy(flex_axw *h) {
     if (!h) return FLEX_OK;
-    int cur = -1;
-    (void)hipGetDevice(&cur);
-    (void)hipSetDevice(h->device);
+    const flex::DeviceScope on(h->device);
     flex_plan_destroy(h->plan_c);
     flex_plan_destroy(h->plan_dim);
     flex_plan_destroy(h->plan_t);
@@ -125,7 +167,6 @@ int flex_axw_destroy(flex_axw *h) {
     if (h->blas) rocblas_destroy_handle(h->blas);
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
-    if (cur >= 0) (void)hipSetDevice(cur);
     delete h;
     return FLEX_OK;
 }
@@ -151,9 +192,8 @@ int flex_axw_create(flex_axw **out, const flex_csr *A, int dim, int c, int devic
     h->wide = bf16 && dim > 256;
     h->cp = bf16 ? flex_axw_ld_bf16(c) : flex_axw_ld(c);
     h->device = device;
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    int rc = hip_fail(hipSetDevice(device));
+    const flex::DeviceScope on(device);
+    int rc = hip_fail(on.error());
     const bool want_blas = (flags & FLEX_AXW_USE_BLAS) != 0;
     const bool backward = (flags & FLEX_AXW_BACKWARD) != 0;
     flags &= ~(FLEX_AXW_USE_BLAS | FLEX_AXW_BACKWARD | FLEX_AXW_BF16 | FLEX_AXW_ROOT);
@@ -206,7 +246,6 @@ int flex_axw_create(flex_axw **out, const flex_csr *A, int dim, int c, int devic
         if (!rc) rc = hip_fail(hipMemset(h->d_wt, 0, wt * sizeof(float)));
         if (!rc) rc = hip_fail(hipMalloc(reinterpret_cast<void **>(&h->d_part), part * sizeof(float)));
     }
-    if (prev >= 0) (void)hipSetDevice(prev);
     if (rc) {
         flex_axw_destroy(h);
         return rc;
@@ -221,16 +260,11 @@ int flex_axw_run(flex_axw *h, int order, const float *dX, const float *dW, float
     if (h->n == 0) return FLEX_OK;
     if (order == FLEX_AXW_AUTO) order = h->cp <= h->dim ? FLEX_AXW_A_XW : FLEX_AXW_AX_W;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    int cur = -1;
-    (void)hipGetDevice(&cur);
-    int rc = hip_fail(hipSetDevice(h->device));
-    const bool timed = gemm_ms || spmm_ms;
-    auto mark = [&](int i) { return timed ? hip_fail(hipEventRecord(h->ev[i], s)) : FLEX_OK; };
+    const flex::DeviceScope on(h->device);
+    int rc = hip_fail(on.error());
+    const Marks mark{h, s, gemm_ms || spmm_ms};
     if (!rc && rocblas_set_stream(h->blas, s) != rocblas_status_success) rc = FLEX_ERR_UNSUPPORTED;
-    // W -> Wp: dim rows of c floats into rows of cp floats (the zero padding was written once at create)
-    if (!rc)
-        rc = hip_fail(hipMemcpy2DAsync(h->d_wp, static_cast<size_t>(h->cp) * sizeof(float), dW, static_cast<size_t>(h->c) * sizeof(float),
-                                       static_cast<size_t>(h->c) * sizeof(float), static_cast<size_t>(h->dim), hipMemcpyDeviceToDevice, s));
+    if (!rc) rc = pad_w(h, dW, sizeof(float), s);
     if (!rc) rc = mark(0);
     if (order == FLEX_AXW_A_XW) {  // run1: cusp.cu:18-75
         if (!rc) rc = gemm_rm(h, dX, h->d_xw, s);
@@ -244,16 +278,13 @@ int flex_axw_run(flex_axw *h, int order, const float *dX, const float *dW, float
         if (!rc) rc = gemm_rm(h, h->d_ax, dOut, s);
         if (!rc) rc = mark(2);
     }
-    if (!rc && timed) {
-        rc = hip_fail(hipEventSynchronize(h->ev[2]));
-        float a = 0.f, b = 0.f;
-        if (!rc) rc = hip_fail(hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
-        if (!rc) rc = hip_fail(hipEventElapsedTime(&b, h->ev[1], h->ev[2]));
+    float ms[2] = {0.f, 0.f};
+    if (!rc) rc = mark.read(2, ms);
+    if (!rc && mark.timed) {
         const bool gemm_first = order == FLEX_AXW_A_XW;
-        if (gemm_ms) *gemm_ms = gemm_first ? a : b;
-        if (spmm_ms) *spmm_ms = gemm_first ? b : a;
+        if (gemm_ms) *gemm_ms = ms[gemm_first ? 0 : 1];
+        if (spmm_ms) *spmm_ms = ms[gemm_first ? 1 : 0];
     }
-    if (cur >= 0 && cur != h->device) (void)hipSetDevice(cur);
     return rc;
 }
 
@@ -262,26 +293,17 @@ int flex_axw_run(flex_axw *h, int order, const float *dX, const float *dW, float
 int flex_axw_run_bf16(flex_axw *h, int order, const flex_bf16 *dX, const flex_bf16 *dW, flex_bf16 *dOut, flex_stream_t stream,
                       float *gemm_ms, float *spmm_ms) {
     if (!h || !h->bf16 || !dX || !dW || !dOut || order < FLEX_AXW_AUTO || order > FLEX_AXW_AX_W) return FLEX_ERR_INVALID;
-    if ((reinterpret_cast<uintptr_t>(dX) | reinterpret_cast<uintptr_t>(dOut)) & 15) return FLEX_ERR_UNSUPPORTED;
+    if (misaligned16({dX, dOut})) return FLEX_ERR_UNSUPPORTED;
     if (order == FLEX_AXW_AUTO) order = h->cp <= h->dim ? FLEX_AXW_A_XW : FLEX_AXW_AX_W;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    flex_bf16 *xw = reinterpret_cast<flex_bf16 *>(h->d_xw), *ax = reinterpret_cast<flex_bf16 *>(h->d_ax), *wp = reinterpret_cast<flex_bf16 *>(h->d_wp);
-    int cur = -1;
-    (void)hipGetDevice(&cur);
-    int rc = hip_fail(hipSetDevice(h->device));
-    const bool timed = gemm_ms || spmm_ms;
-    auto mark = [&](int i) { return timed ? hip_fail(hipEventRecord(h->ev[i], s)) : FLEX_OK; };
-    auto gemm = [&](const flex_bf16 *L, flex_bf16 *Cout) {  // wide: packs W into wp (fragment order, zero columns included) first
-        return hip_fail(h->wide ? flex_axw_gemm_bf16_wide_launch(L, dW, wp, Cout, h->n, h->dim, h->c, h->cp, h->n_cus, s)
-                                : flex_axw_gemm_bf16_launch(L, wp, Cout, h->n, h->dim, h->c, h->cp, h->n_cus, s));
-    };
-    // W -> Wp: dim rows of c elements into rows of cp (the zero padding was written once at create)
-    if (!rc && !h->wide)
-        rc = hip_fail(hipMemcpy2DAsync(wp, static_cast<size_t>(h->cp) * sizeof(flex_bf16), dW, static_cast<size_t>(h->c) * sizeof(flex_bf16),
-                                       static_cast<size_t>(h->c) * sizeof(flex_bf16), static_cast<size_t>(h->dim), hipMemcpyDeviceToDevice, s));
+    flex_bf16 *xw = reinterpret_cast<flex_bf16 *>(h->d_xw), *ax = reinterpret_cast<flex_bf16 *>(h->d_ax);
+    const flex::DeviceScope on(h->device);
+    int rc = hip_fail(on.error());
+    const Marks mark{h, s, gemm_ms || spmm_ms};
+    if (!rc && !h->wide) rc = pad_w(h, dW, sizeof(flex_bf16), s);  // before the first mark and, in (A X) W, before the SpMM
     if (!rc) rc = mark(0);
     if (order == FLEX_AXW_A_XW) {
-        if (!rc) rc = gemm(dX, xw);  // writes its padding columns as +0
+        if (!rc) rc = dense_bf16(h, dX, dW, xw, s);  // writes its padding columns as +0
         if (!rc) rc = mark(1);
         if (!rc) rc = flex_spmm_bf16(h->plan_c, xw, dOut, stream);
         if (!rc && h->a_nonfinite) rc = hip_fail(flex_axw_bf16_clear_padding_launch(dOut, h->n, h->c, h->cp, s));  // inf x 0 = NaN there
@@ -289,19 +311,16 @@ int flex_axw_run_bf16(flex_axw *h, int order, const flex_bf16 *dX, const flex_bf
     } else {
         if (!rc) rc = flex_spmm_bf16(h->plan_dim, dX, ax, stream);
         if (!rc) rc = mark(1);
-        if (!rc) rc = gemm(ax, dOut);
+        if (!rc) rc = dense_bf16(h, ax, dW, dOut, s);
         if (!rc) rc = mark(2);
     }
-    if (!rc && timed) {
-        rc = hip_fail(hipEventSynchronize(h->ev[2]));
-        float a = 0.f, b = 0.f;
-        if (!rc) rc = hip_fail(hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
-        if (!rc) rc = hip_fail(hipEventElapsedTime(&b, h->ev[1], h->ev[2]));
+    float ms[2] = {0.f, 0.f};
+    if (!rc) rc = mark.read(2, ms);
+    if (!rc && mark.timed) {
         const bool gemm_first = order == FLEX_AXW_A_XW;
-        if (gemm_ms) *gemm_ms = gemm_first ? a : b;
-        if (spmm_ms) *spmm_ms = gemm_first ? b : a;
+        if (gemm_ms) *gemm_ms = ms[gemm_first ? 0 : 1];
+        if (spmm_ms) *spmm_ms = ms[gemm_first ? 1 : 0];
     }
-    if (cur >= 0 && cur != h->device) (void)hipSetDevice(cur);
     return rc;
 }
 
@@ -311,24 +330,18 @@ int flex_axw_run_bf16(flex_axw *h, int order, const flex_bf16 *dX, const flex_bf
 int flex_axw_run_root_bf16(flex_axw *h, int order, const flex_bf16 *dX, const flex_bf16 *dW, const flex_bf16 *dR, const float *dBias,
                            flex_bf16 *dOut, flex_stream_t stream, float *gemm_ms, float *spmm_ms) {
     if (!h || !h->d_wf || !dX || !dW || !dR || !dOut || order < FLEX_AXW_AUTO || order > FLEX_AXW_AX_W) return FLEX_ERR_INVALID;
-    if ((reinterpret_cast<uintptr_t>(dX) | reinterpret_cast<uintptr_t>(dOut)) & 15) return FLEX_ERR_UNSUPPORTED;
+    if (misaligned16({dX, dOut})) return FLEX_ERR_UNSUPPORTED;
     if (order == FLEX_AXW_AUTO) order = h->cp <= h->dim ? FLEX_AXW_A_XW : FLEX_AXW_AX_W;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    flex_bf16 *xw = reinterpret_cast<flex_bf16 *>(h->d_xw), *ax = reinterpret_cast<flex_bf16 *>(h->d_ax), *wp = reinterpret_cast<flex_bf16 *>(h->d_wp);
+    flex_bf16 *xw = reinterpret_cast<flex_bf16 *>(h->d_xw), *ax = reinterpret_cast<flex_bf16 *>(h->d_ax);
     flex_bf16 *sum = reinterpret_cast<flex_bf16 *>(h->d_s), *wf = reinterpret_cast<flex_bf16 *>(h->d_wf);
-    int cur = -1;
-    (void)hipGetDevice(&cur);
-    int rc = hip_fail(hipSetDevice(h->device));
-    const bool timed = gemm_ms || spmm_ms;
-    auto mark = [&](int i) { return timed ? hip_fail(hipEventRecord(h->ev[i], s)) : FLEX_OK; };
+    const flex::DeviceScope on(h->device);
+    int rc = hip_fail(on.error());
+    const Marks mark{h, s, gemm_ms || spmm_ms};
     if (!rc) rc = mark(0);
     if (order == FLEX_AXW_A_XW) {
-        if (!rc && !h->wide)  // W -> Wp, as flex_axw_run_bf16
-            rc = hip_fail(hipMemcpy2DAsync(wp, static_cast<size_t>(h->cp) * sizeof(flex_bf16), dW, static_cast<size_t>(h->c) * sizeof(flex_bf16),
-                                           static_cast<size_t>(h->c) * sizeof(flex_bf16), static_cast<size_t>(h->dim), hipMemcpyDeviceToDevice, s));
-        if (!rc)
-            rc = hip_fail(h->wide ? flex_axw_gemm_bf16_wide_launch(dX, dW, wp, xw, h->n, h->dim, h->c, h->cp, h->n_cus, s)
-                                  : flex_axw_gemm_bf16_launch(dX, wp, xw, h->n, h->dim, h->c, h->cp, h->n_cus, s));
+        if (!rc && !h->wide) rc = pad_w(h, dW, sizeof(flex_bf16), s);
+        if (!rc) rc = dense_bf16(h, dX, dW, xw, s);
         if (!rc) rc = mark(1);
         if (!rc) rc = flex_spmm_bf16(h->plan_c, xw, sum, stream);
         if (!rc && h->a_nonfinite) rc = hip_fail(flex_axw_bf16_clear_padding_launch(sum, h->n, h->c, h->cp, s));  // inf x 0 = NaN there
@@ -341,16 +354,12 @@ int flex_axw_run_root_bf16(flex_axw *h, int order, const flex_bf16 *dX, const fl
         if (!rc) rc = hip_fail(flex_axw_gemm_bf16_root_launch(ax, dW, h->dim, dX, dR, h->dim, nullptr, dBias, wf, dOut, h->n, h->c, h->cp, h->n_cus, s));
     }
     if (!rc) rc = mark(3);
-    if (!rc && timed) {  // the dense stages either side of the SpMM count as gemm
-        rc = hip_fail(hipEventSynchronize(h->ev[3]));
-        float a = 0.f, b = 0.f, d = 0.f;
-        if (!rc) rc = hip_fail(hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
-        if (!rc) rc = hip_fail(hipEventElapsedTime(&b, h->ev[1], h->ev[2]));
-        if (!rc) rc = hip_fail(hipEventElapsedTime(&d, h->ev[2], h->ev[3]));
-        if (gemm_ms) *gemm_ms = a + d;
-        if (spmm_ms) *spmm_ms = b;
+    float ms[3] = {0.f, 0.f, 0.f};
+    if (!rc) rc = mark.read(3, ms);
+    if (!rc && mark.timed) {  // the dense stages either side of the SpMM count as gemm
+        if (gemm_ms) *gemm_ms = ms[0] + ms[2];
+        if (spmm_ms) *spmm_ms = ms[1];
     }
-    if (cur >= 0 && cur != h->device) (void)hipSetDevice(cur);
     return rc;
 }
 
@@ -360,9 +369,8 @@ int flex_axw_backward(flex_axw *h, const float *dX, const float *dW, const float
     if (!h || h->bf16 || !h->plan_t || !dOut || (dGradX && !dW) || (dGradW && !dX)) return FLEX_ERR_INVALID;
     if (h->n == 0 || (!dGradX && !dGradW)) return FLEX_OK;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    int cur = -1;
-    (void)hipGetDevice(&cur);
-    int rc = hip_fail(hipSetDevice(h->device));
+    const flex::DeviceScope on(h->device);
+    int rc = hip_fail(on.error());
     if (!rc && rocblas_set_stream(h->blas, s) != rocblas_status_success) rc = FLEX_ERR_UNSUPPORTED;
     if (!rc) rc = flex_spmm(h->plan_t, dOut, h->d_g, stream);  // reads columns 0 .. c-1 of dOut, writes columns 0 .. c-1 of G
     const float one = 1.0f, zero = 0.0f;
@@ -389,7 +397,6 @@ int flex_axw_backward(flex_axw *h, const float *dX, const float *dW, const float
                                     h->dim, &zero, dGradW, h->c));
         }
     }
-    if (cur >= 0 && cur != h->device) (void)hipSetDevice(cur);
     return rc;
 }
 
@@ -399,18 +406,13 @@ int flex_axw_backward(flex_axw *h, const float *dX, const float *dW, const float
 int flex_axw_backward_bf16(flex_axw *h, const flex_bf16 *dX, const flex_bf16 *dW, const flex_bf16 *dOut, flex_bf16 *dGradX, flex_bf16 *dGradW,
                            flex_stream_t stream) {
     if (!h || !h->bf16 || !h->plan_t || !dOut || (dGradX && !dW) || (dGradW && !dX)) return FLEX_ERR_INVALID;
-    for (const void *p : {static_cast<const void *>(dOut), static_cast<const void *>(dGradX), static_cast<const void *>(dGradW),
-                          static_cast<const void *>(dGradX ? dW : nullptr), static_cast<const void *>(dGradW ? dX : nullptr)})
-        if (reinterpret_cast<uintptr_t>(p) & 15) return FLEX_ERR_UNSUPPORTED;
+    if (misaligned16({dOut, dGradX, dGradW, dGradX ? dW : nullptr, dGradW ? dX : nullptr})) return FLEX_ERR_UNSUPPORTED;
     if (!dGradX && !dGradW) return FLEX_OK;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     flex_bf16 *g = reinterpret_cast<flex_bf16 *>(h->d_g), *wt = reinterpret_cast<flex_bf16 *>(h->d_wt);
-    int cur = -1;
-    (void)hipGetDevice(&cur);
-    int rc = hip_fail(hipSetDevice(h->device));
-    if (!rc) rc = flex_spmm_bf16(h->plan_t, dOut, g, stream);
-    // inf x 0 = NaN in G's padding columns would meet the zero rows of W^T: a NaN row of dGradX where the reference has inf
-    if (!rc && h->a_nonfinite) rc = hip_fail(flex_axw_bf16_clear_padding_launch(g, h->n, h->c, h->cp, s));
+    const flex::DeviceScope on(h->device);
+    int rc = hip_fail(on.error());
+    if (!rc) rc = grad_aggregate_bf16(h, dOut, stream);
     if (!rc && dGradX) {
         rc = hip_fail(flex_axw_bf16_transpose_launch(dW, wt, h->dim, h->c, s));
         if (!rc) rc = hip_fail((h->wide ? flex_axw_dx_bf16_wide_launch : flex_axw_dx_bf16_launch)(g, wt, dGradX, h->n, h->cp, h->dim, h->n_cus, s));
@@ -418,7 +420,6 @@ int flex_axw_backward_bf16(flex_axw *h, const flex_bf16 *dX, const flex_bf16 *dW
     if (!rc && dGradW)
         rc = hip_fail((h->wide ? flex_axw_dw_bf16_wide_launch : flex_axw_dw_bf16_launch)(dX, g, dGradW, h->d_part, h->n, h->dim, h->c, h->cp,
                                                                                          h->n_cus, s));
-    if (cur >= 0 && cur != h->device) (void)hipSetDevice(cur);
     return rc;
 }
 
@@ -430,27 +431,19 @@ int flex_axw_backward_root_bf16(flex_axw *h, const flex_bf16 *dX, const flex_bf1
     if (!h || !h->bf16 || !h->plan_t || !h->d_wf || !dOut || (dGradW != nullptr) != (dGradR != nullptr) || (dGradX && (!dW || !dR)) ||
         (dGradW && !dX))
         return FLEX_ERR_INVALID;
-    for (const void *p : {static_cast<const void *>(dOut), static_cast<const void *>(dGradX), static_cast<const void *>(dGradW),
-                          static_cast<const void *>(dGradR), static_cast<const void *>(dGradX ? dW : nullptr),
-                          static_cast<const void *>(dGradX ? dR : nullptr), static_cast<const void *>(dGradW ? dX : nullptr)})
-        if (reinterpret_cast<uintptr_t>(p) & 15) return FLEX_ERR_UNSUPPORTED;
+    if (misaligned16({dOut, dGradX, dGradW, dGradR, dGradX ? dW : nullptr, dGradX ? dR : nullptr, dGradW ? dX : nullptr}))
+        return FLEX_ERR_UNSUPPORTED;
     if (reinterpret_cast<uintptr_t>(dGradBias) & 3) return FLEX_ERR_UNSUPPORTED;
     if (!dGradX && !dGradW && !dGradBias) return FLEX_OK;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     flex_bf16 *g = reinterpret_cast<flex_bf16 *>(h->d_g), *wf = reinterpret_cast<flex_bf16 *>(h->d_wf);
-    int cur = -1;
-    (void)hipGetDevice(&cur);
-    int rc = hip_fail(hipSetDevice(h->device));
-    if (dGradX || dGradW) {  // dGradBias alone needs no G
-        if (!rc) rc = flex_spmm_bf16(h->plan_t, dOut, g, stream);
-        // inf x 0 = NaN in G's padding columns would meet the zero rows of W^T, as in flex_axw_backward_bf16
-        if (!rc && h->a_nonfinite) rc = hip_fail(flex_axw_bf16_clear_padding_launch(g, h->n, h->c, h->cp, s));
-    }
+    const flex::DeviceScope on(h->device);
+    int rc = hip_fail(on.error());
+    if (!rc && (dGradX || dGradW)) rc = grad_aggregate_bf16(h, dOut, stream);  // dGradBias alone needs no G
     if (!rc && dGradX) rc = hip_fail(flex_axw_dx_bf16_root_launch(g, dW, dOut, dR, wf, dGradX, h->n, h->c, h->cp, h->dim, h->n_cus, s));
     if (!rc && (dGradW || dGradBias))
         rc = hip_fail(flex_axw_dw_bf16_root_launch(dGradW ? dX : nullptr, g, dOut, dGradW, dGradR, dGradBias, h->d_part, h->n, h->dim, h->c, h->cp,
                                                    h->n_cus, s));
-    if (cur >= 0 && cur != h->device) (void)hipSetDevice(cur);
     return rc;
 }
 

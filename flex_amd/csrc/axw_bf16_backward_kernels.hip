@@ -30,21 +30,11 @@
 #include <algorithm>
 #include <cstdint>
 
-#include "attention_device.h"  // flex_bf16, bf16_bits: the project's one fp32 -> bf16 rounding
+#include "axw_bf16_dw_device.h"  // frag_slot, the block load and store, slice_sum: shared with axw_bf16_root_backward_kernels.hip
 
-namespace flex_axw_bf16_backward {
+namespace flex_axw_bf16_dw {
 
-using flex::attention::bf16_bits;
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kStage = 64;            // rows of a stage: four k-steps of 16
 constexpr int kFrags = 4 * 4 * 64;    // fragments of one operand of a stage: [4 k-steps][4 tiles][64 lanes]
-
-// slot of the fragment (k-step s, tile t, row half h, column i of the tile) in an operand's stage
-__device__ __forceinline__ int frag_slot(int s, int t, int h, int i) { return ((s * 4 + t) * 2 + h) * 32 + (i ^ (((i >> 4) & 1) | (t << 1))); }
 
 __global__ __launch_bounds__(256) void axw_dw_bf16_kernel(const flex_bf16 *__restrict__ X, const flex_bf16 *__restrict__ G,
                                                           float *__restrict__ part, int n, int dim, int c, int cp, int rows_per_slice) {
@@ -63,26 +53,10 @@ __global__ __launch_bounds__(256) void axw_dw_bf16_kernel(const flex_bf16 *__res
     const bool col_ok = col < ld;  // dim % 8 == 0 and cp % 8 == 0: a block's eight columns stand or fall together
     const flex_bf16 *src = (op ? G : X) + col;
     u32x4 v[8];
-    auto load = [&](int r0) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int r = r0 + 8 * rg + e;
-            v[e] = col_ok && r < r_end ? *reinterpret_cast<const u32x4 *>(src + static_cast<size_t>(r) * ld) : u32x4{0u, 0u, 0u, 0u};
-        }
-    };
-    // v[e][d] holds columns 2 d (low half) and 2 d + 1 of row e; fragment cc is column cc of the eight rows, rows 2 p and 2 p + 1 in word p
+    auto load = [&](int r0) { FLEX_AXW_DW_LOAD_BLOCK(v, src, ld, r0 + 8 * rg, r_end, col_ok) };
     auto store = [&](int buf) {
         u32x4 *dst = sF + (buf * 2 + op) * kFrags;
-#pragma unroll
-        for (int cc = 0; cc < 8; ++cc) {
-            u32x4 f;
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                const uint32_t lo = v[2 * p][cc >> 1], hi = v[2 * p + 1][cc >> 1];
-                f[p] = (cc & 1) ? (lo >> 16) | (hi & 0xFFFF0000u) : (lo & 0xFFFFu) | (hi << 16);
-            }
-            dst[frag_slot(rg >> 1, q >> 2, rg & 1, 8 * (q & 3) + cc)] = f;
-        }
+        FLEX_AXW_DW_STORE_BLOCK(v, dst, rg, q, 4)
     };
 
     f32x16 acc[4];
@@ -102,11 +76,11 @@ __global__ __launch_bounds__(256) void axw_dw_bf16_kernel(const flex_bf16 *__res
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 if (r0 + 16 * s >= r_end) break;  // wave-uniform
-                const bf16x8 a = __builtin_bit_cast(bf16x8, fx[frag_slot(s, wave, lane >> 5, lane & 31)]);
+                const bf16x8 a = __builtin_bit_cast(bf16x8, fx[frag_slot(s, wave, lane >> 5, lane & 31, 4)]);
 #pragma unroll
                 for (int t = 0; t < 4; ++t)
                     if (t < nt)
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8, fg[frag_slot(s, t, lane >> 5, lane & 31)]),
+                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8, fg[frag_slot(s, t, lane >> 5, lane & 31, 4)]),
                                                                          acc[t], 0, 0, 0);
             }
         }
@@ -118,31 +92,16 @@ __global__ __launch_bounds__(256) void axw_dw_bf16_kernel(const flex_bf16 *__res
     for (int t = 0; t < 4; ++t) {
         const int j = j0 + 32 * t + (lane & 31);
         if (t >= nt || j >= c) continue;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const int ii = i0 + (k & 3) + 8 * (k >> 2) + 4 * (lane >> 5);
-            if (ii < dim) dst[static_cast<size_t>(ii) * c + j] = acc[t][k];
-        }
+        FLEX_AXW_DW_FOR_TILE_ROWS(k, ii, i0, lane >> 5, dim) dst[static_cast<size_t>(ii) * c + j] = acc[t][k];
     }
 }
 
 // dW[e] = rn_bf16(part[0][e] + part[1][e] + ... + part[S-1][e]), left to right in fp32, the loads 16 at a time (axw_dw_reduce_kernel)
 __global__ __launch_bounds__(256) void axw_dw_bf16_reduce_kernel(const float *__restrict__ part, flex_bf16 *__restrict__ dW, int count,
                                                                  int slices) {
-    constexpr int kBatch = 16;
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= count) return;
-    float s = part[e];
-    int k = 1;
-    for (; k + kBatch <= slices; k += kBatch) {
-        float v[kBatch];
-#pragma unroll
-        for (int j = 0; j < kBatch; ++j) v[j] = part[static_cast<size_t>(k + j) * count + e];
-#pragma unroll
-        for (int j = 0; j < kBatch; ++j) s += v[j];
-    }
-    for (; k < slices; ++k) s += part[static_cast<size_t>(k) * count + e];
-    dW[e] = static_cast<flex_bf16>(bf16_bits(s));
+    dW[e] = static_cast<flex_bf16>(bf16_bits(slice_sum(part, e, count, slices)));
 }
 
 // rows of an n-slice: about 256, at most n_cus slices, a whole number of stages
@@ -151,7 +110,7 @@ inline int dw_rows(int n, int n_cus) {
     return ((n + s0 - 1) / s0 + kStage - 1) / kStage * kStage;
 }
 
-}  // namespace flex_axw_bf16_backward
+}  // namespace flex_axw_bf16_dw
 
 extern "C" hipError_t flex_axw_dw_bf16_rows_launch(const flex_bf16 *X, const flex_bf16 *G, flex_bf16 *dW, float *part, int n, int dim, int c,
                                                    int cp, int rows, hipStream_t s);
@@ -159,7 +118,7 @@ extern "C" hipError_t flex_axw_dw_bf16_rows_launch(const flex_bf16 *X, const fle
 // n-slices of the bf16 dW kernel: ceil(n / rows), rows = ceil(n / min(n_cus, ceil(n / 256))) rounded up to a multiple of 64; no slice is empty
 extern "C" int flex_axw_dw_bf16_slices(int n, int n_cus) {
     if (n <= 0 || n_cus <= 0) return 0;
-    const int rows = flex_axw_bf16_backward::dw_rows(n, n_cus);
+    const int rows = flex_axw_bf16_dw::dw_rows(n, n_cus);
     return (n + rows - 1) / rows;
 }
 
@@ -168,8 +127,7 @@ extern "C" int flex_axw_dw_bf16_slices(int n, int n_cus) {
 // hipErrorInvalidValue before a launch.  Returns hipSuccess or the launch error.
 extern "C" hipError_t flex_axw_dw_bf16_launch(const flex_bf16 *X, const flex_bf16 *G, flex_bf16 *dW, float *part, int n, int dim, int c, int cp,
                                               int n_cus, hipStream_t s) {
-    using namespace flex_axw_bf16_backward;
-    const auto misaligned = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
+    using namespace flex_axw_bf16_dw;
     if (!X || !G || !dW || !part || n < 32 || dim <= 0 || dim > 256 || dim % 8 != 0 || c <= 0 || c > cp || cp > 256 || cp % 32 != 0 || n_cus <= 0 ||
         misaligned(X) || misaligned(G))
         return hipErrorInvalidValue;
@@ -181,13 +139,11 @@ extern "C" hipError_t flex_axw_dw_bf16_launch(const flex_bf16 *X, const flex_bf1
 // here: any dim % 8 == 0 is served by the grid of 128 x 128 blocks.
 extern "C" hipError_t flex_axw_dw_bf16_rows_launch(const flex_bf16 *X, const flex_bf16 *G, flex_bf16 *dW, float *part, int n, int dim, int c,
                                                    int cp, int rows, hipStream_t s) {
-    using namespace flex_axw_bf16_backward;
+    using namespace flex_axw_bf16_dw;
     const int slices = (n + rows - 1) / rows;
     const dim3 grid(static_cast<unsigned>(slices), static_cast<unsigned>(((dim + 127) / 128) * ((cp + 127) / 128)));
-    hipLaunchKernelGGL(axw_dw_bf16_kernel, grid, dim3(256), 0, s, X, G, part, n, dim, c, cp, rows);
-    hipError_t e = hipGetLastError();
+    const hipError_t e = launch(axw_dw_bf16_kernel, grid, 256, 0, s, X, G, part, n, dim, c, cp, rows);
     if (e != hipSuccess) return e;
     const int count = dim * c;
-    hipLaunchKernelGGL(axw_dw_bf16_reduce_kernel, dim3(static_cast<unsigned>((count + 255) / 256)), dim3(256), 0, s, part, dW, count, slices);
-    return hipGetLastError();
+    return launch(axw_dw_bf16_reduce_kernel, dim3(static_cast<unsigned>((count + 255) / 256)), 256, 0, s, part, dW, count, slices);
 }

@@ -33,7 +33,7 @@
 #include <algorithm>
 #include <cstdint>
 
-#include "axw_bf16_device.h"  // axw_gemm_bf16_kernel, stage_w, store_panel: shared with axw_bf16_wide_kernels.hip
+#include "axw_bf16_device.h"  // axw_gemm_bf16_kernel, stage_w, the panel store and the launch helpers: shared with the wide and root files
 
 namespace flex_axw_bf16 {
 
@@ -62,27 +62,13 @@ __global__ __launch_bounds__(256) void axw_bf16_transpose_kernel(const flex_bf16
 extern "C" hipError_t flex_axw_gemm_bf16_launch(const flex_bf16 *L, const flex_bf16 *Wp, flex_bf16 *Out, int n, int dim, int c, int cp,
                                                 int n_cus, hipStream_t s) {
     using namespace flex_axw_bf16;
-    const auto misaligned = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
     if (!L || !Wp || !Out || n < kRows || dim <= 0 || dim % 16 != 0 || dim > 256 || cp <= 0 || cp % 64 != 0 || cp > 256 || c <= 0 || c > cp ||
         n_cus <= 0 || misaligned(L) || misaligned(Wp) || misaligned(Out))
         return hipErrorInvalidValue;
-    const int n_panels = (n + kRows - 1) / kRows;
-    const size_t lds = static_cast<size_t>(dim) * cp * sizeof(flex_bf16);
-    const dim3 grid(static_cast<unsigned>(std::min(n_cus, (n_panels + 3) / 4))), block(64 * kWaves);  // no workgroup without a panel
-    hipError_t e = hipSuccess;
-    auto go = [&](auto kernel) {  // more than 64 KiB of dynamic LDS has to be asked for
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        if (e != hipSuccess) return;
-        hipLaunchKernelGGL(kernel, grid, block, lds, s, L, Wp, Out, n, dim, c, 0);
-        e = hipGetLastError();
-    };
-    switch (cp / 32) {
-        case 2: go(axw_gemm_bf16_kernel<2>); break;
-        case 4: go(axw_gemm_bf16_kernel<4>); break;
-        case 6: go(axw_gemm_bf16_kernel<6>); break;
-        default: go(axw_gemm_bf16_kernel<8>); break;
-    }
-    return e;
+    return dispatch_tiles<2, 4, 6, 8>(cp / 32, [&](auto tiles) {
+        return launch(axw_gemm_bf16_kernel<decltype(tiles)::value>, dim3(panel_groups(n, 4, n_cus)), 64 * kWaves,
+                      static_cast<size_t>(dim) * cp * sizeof(flex_bf16), s, L, Wp, Out, n, dim, c, 0);
+    });
 }
 
 // The dX product of flex_axw_backward_bf16: dX[n x dim] = G[n x cp] * Wt[cp x dim] on flex_bf16 -- the kernel above with the contraction
@@ -92,39 +78,20 @@ extern "C" hipError_t flex_axw_gemm_bf16_launch(const flex_bf16 *L, const flex_b
 extern "C" hipError_t flex_axw_dx_bf16_launch(const flex_bf16 *G, const flex_bf16 *Wt, flex_bf16 *dX, int n, int cp, int dim, int n_cus,
                                               hipStream_t s) {
     using namespace flex_axw_bf16;
-    const auto misaligned = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
     if (!G || !Wt || !dX || n < kRows || cp <= 0 || cp % 64 != 0 || cp > 256 || dim <= 0 || dim % 32 != 0 || dim > 256 || n_cus <= 0 ||
         misaligned(G) || misaligned(Wt) || misaligned(dX))
         return hipErrorInvalidValue;
-    const int n_panels = (n + kRows - 1) / kRows;
-    const size_t lds = static_cast<size_t>(cp) * dim * sizeof(flex_bf16);
-    const dim3 grid(static_cast<unsigned>(std::min(n_cus, (n_panels + 3) / 4))), block(64 * kWaves);
-    hipError_t e = hipSuccess;
-    auto go = [&](auto kernel) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        if (e != hipSuccess) return;
-        hipLaunchKernelGGL(kernel, grid, block, lds, s, G, Wt, dX, n, cp, dim, 0);
-        e = hipGetLastError();
-    };
-    switch (dim / 32) {
-        case 1: go(axw_gemm_bf16_kernel<1>); break;
-        case 2: go(axw_gemm_bf16_kernel<2>); break;
-        case 3: go(axw_gemm_bf16_kernel<3>); break;
-        case 4: go(axw_gemm_bf16_kernel<4>); break;
-        case 5: go(axw_gemm_bf16_kernel<5>); break;
-        case 6: go(axw_gemm_bf16_kernel<6>); break;
-        case 7: go(axw_gemm_bf16_kernel<7>); break;
-        default: go(axw_gemm_bf16_kernel<8>); break;
-    }
-    return e;
+    return dispatch_tiles<1, 2, 3, 4, 5, 6, 7, 8>(dim / 32, [&](auto tiles) {
+        return launch(axw_gemm_bf16_kernel<decltype(tiles)::value>, dim3(panel_groups(n, 4, n_cus)), 64 * kWaves,
+                      static_cast<size_t>(cp) * dim * sizeof(flex_bf16), s, G, Wt, dX, n, cp, dim, 0);
+    });
 }
 
 // Wt[c x dim] := W[dim x c]^T (rows c .. of Wt are not written)
 extern "C" hipError_t flex_axw_bf16_transpose_launch(const flex_bf16 *W, flex_bf16 *Wt, int dim, int c, hipStream_t s) {
     using namespace flex_axw_bf16;
     if (!W || !Wt || dim <= 0 || c <= 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(axw_bf16_transpose_kernel, dim3(static_cast<unsigned>((dim * c + 255) / 256)), dim3(256), 0, s, W, Wt, dim, c);
-    return hipGetLastError();
+    return launch(axw_bf16_transpose_kernel, dim3(static_cast<unsigned>((dim * c + 255) / 256)), 256, 0, s, W, Wt, dim, c);
 }
 
 // columns c .. cp-1 of Out[n x cp] := +0 bits; c == cp: nothing to do
@@ -133,6 +100,5 @@ extern "C" hipError_t flex_axw_bf16_clear_padding_launch(flex_bf16 *Out, int n, 
     if (!Out || n <= 0 || c <= 0 || c > cp) return hipErrorInvalidValue;
     if (c == cp) return hipSuccess;
     const int64_t count = static_cast<int64_t>(n) * (cp - c);
-    hipLaunchKernelGGL(axw_bf16_clear_padding_kernel, dim3(static_cast<unsigned>((count + 255) / 256)), dim3(256), 0, s, Out, n, c, cp);
-    return hipGetLastError();
+    return launch(axw_bf16_clear_padding_kernel, dim3(static_cast<unsigned>((count + 255) / 256)), 256, 0, s, Out, n, c, cp);
 }

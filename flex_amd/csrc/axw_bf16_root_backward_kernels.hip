@@ -31,24 +31,12 @@
 #include <algorithm>
 #include <cstdint>
 
-#include "attention_device.h"  // flex_bf16, bf16_bits: the project's one fp32 -> bf16 rounding
+#include "axw_bf16_dw_device.h"  // frag_slot, the block load and store, slice_sum: shared with axw_bf16_backward_kernels.hip
 
-namespace flex_axw_bf16_root_backward {
+namespace flex_axw_bf16_dw {
 
-using flex::attention::bf16_bits;
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kStage = 64;           // rows of a stage: four k-steps of 16
 constexpr int kThreads = 6 * 64;     // three loader pairs, of which the first two multiply
 constexpr int kXFrags = 4 * 4 * 64;  // X's fragments of a stage: [4 k-steps][4 waves' row tiles][64 lanes]
-
-// slot of the fragment (k-step s, tile t of `tiles`, row half h, column i of the tile) in an operand's stage (axw_dw_bf16_kernel's swizzle)
-__device__ __forceinline__ int frag_slot(int s, int t, int h, int i, int tiles) {
-    return ((s * tiles + t) * 2 + h) * 32 + (i ^ (((i >> 4) & 1) | (t << 1)));
-}
 
 template <int NT>  // tiles of a column window of G and of dOut: min(4, cp / 32)
 __global__ __launch_bounds__(kThreads) void axw_dw_bf16_root_kernel(const flex_bf16 *__restrict__ X, const flex_bf16 *__restrict__ G,
@@ -74,27 +62,11 @@ __global__ __launch_bounds__(kThreads) void axw_dw_bf16_root_kernel(const flex_b
     const bool stores = want_w && (op == 0 || (q >> 2) < NT);
     const bool sums = op == 2 && gi == 0;  // wave-uniform
     const flex_bf16 *src = (op == 0 ? X : op == 1 ? G : dOut) + col;
-    u32x4 v[8];
-    auto load = [&](int r0) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int r = r0 + 8 * rg + e;
-            v[e] = col_ok && r < r_end ? *reinterpret_cast<const u32x4 *>(src + static_cast<size_t>(r) * ld) : u32x4{0u, 0u, 0u, 0u};
-        }
-    };
-    // v[e][d] holds columns 2 d (low half) and 2 d + 1 of row e; fragment cc is column cc of the eight rows, rows 2 p and 2 p + 1 in word p
+    u32x4 v[8];  // v[e][d]: columns 2 d (low half) and 2 d + 1 of row e of the block
+    auto load = [&](int r0) { FLEX_AXW_DW_LOAD_BLOCK(v, src, ld, r0 + 8 * rg, r_end, col_ok) };
     auto store = [&](int buf) {
         u32x4 *dst = sF + buf * kBufFrags + (op == 0 ? 0 : op == 1 ? kXFrags : kXFrags + kOpFrags);
-#pragma unroll
-        for (int cc = 0; cc < 8; ++cc) {
-            u32x4 f;
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                const uint32_t lo = v[2 * p][cc >> 1], hi = v[2 * p + 1][cc >> 1];
-                f[p] = (cc & 1) ? (lo >> 16) | (hi & 0xFFFF0000u) : (lo & 0xFFFFu) | (hi << 16);
-            }
-            dst[frag_slot(rg >> 1, q >> 2, rg & 1, 8 * (q & 3) + cc, op ? NT : 4)] = f;
-        }
+        FLEX_AXW_DW_STORE_BLOCK(v, dst, rg, q, op ? NT : 4)
     };
     float colsum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // db: columns col .. col + 7 over this thread's rows, in ascending order
     auto sum_rows = [&]() {
@@ -158,13 +130,9 @@ __global__ __launch_bounds__(kThreads) void axw_dw_bf16_root_kernel(const flex_b
     for (int t = 0; t < NT; ++t) {
         const int j = j0 + 32 * t + (lane & 31);
         if (t >= nt || j >= c) continue;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const int ii = i0 + (k & 3) + 8 * (k >> 2) + 4 * (lane >> 5);
-            if (ii < dim) {
-                dst[static_cast<size_t>(ii) * c + j] = acc[t][k];
-                dst[static_cast<size_t>(dim + ii) * c + j] = acc[NT + t][k];
-            }
+        FLEX_AXW_DW_FOR_TILE_ROWS(k, ii, i0, lane >> 5, dim) {
+            dst[static_cast<size_t>(ii) * c + j] = acc[t][k];
+            dst[static_cast<size_t>(dim + ii) * c + j] = acc[NT + t][k];
         }
     }
 }
@@ -175,19 +143,9 @@ __global__ __launch_bounds__(kThreads) void axw_dw_bf16_root_kernel(const flex_b
 __global__ __launch_bounds__(256) void axw_dw_bf16_root_reduce_kernel(const float *__restrict__ part, flex_bf16 *__restrict__ dW,
                                                                       flex_bf16 *__restrict__ dR, float *__restrict__ db, int first, int dc, int c,
                                                                       int slices) {
-    constexpr int kBatch = 16;
     const int e = first + blockIdx.x * 256 + threadIdx.x, count = 2 * dc + c;
     if (e >= count || (e < dc ? !dW : e < 2 * dc ? !dR : !db)) return;
-    float s = part[e];
-    int k = 1;
-    for (; k + kBatch <= slices; k += kBatch) {
-        float v[kBatch];
-#pragma unroll
-        for (int j = 0; j < kBatch; ++j) v[j] = part[static_cast<size_t>(k + j) * count + e];
-#pragma unroll
-        for (int j = 0; j < kBatch; ++j) s += v[j];
-    }
-    for (; k < slices; ++k) s += part[static_cast<size_t>(k) * count + e];
+    const float s = slice_sum(part, e, count, slices);
     if (e < dc)
         dW[e] = static_cast<flex_bf16>(bf16_bits(s));
     else if (e < 2 * dc)
@@ -210,24 +168,12 @@ inline int dw_root_rows(int n, int dim, int c, int n_cus) {
     return ((n + s0 - 1) / s0 + kStage - 1) / kStage * kStage;
 }
 
-template <int NT>
-hipError_t launch(const flex_bf16 *X, const flex_bf16 *G, const flex_bf16 *dOut, float *part, int n, int dim, int c, int cp, int rows, hipStream_t s) {
-    const auto kernel = axw_dw_bf16_root_kernel<NT>;
-    const size_t lds = static_cast<size_t>(2) * (kXFrags + 2 * 4 * NT * 64) * sizeof(u32x4);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    if (e != hipSuccess) return e;
-    const int slices = (n + rows - 1) / rows, blocks_i = X ? (dim + 127) / 128 : 1;
-    hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(slices), static_cast<unsigned>(blocks_i * ((cp + 127) / 128))), dim3(kThreads), lds, s, X, G,
-                       dOut, part, n, dim, c, cp, rows);
-    return hipGetLastError();
-}
-
-}  // namespace flex_axw_bf16_root_backward
+}  // namespace flex_axw_bf16_dw
 
 // n-slices of the dual dW kernel: ceil(n / rows), rows = dw_root_rows above; 0 for arguments the launcher refuses
 extern "C" int flex_axw_dw_bf16_root_slices(int n, int dim, int c, int n_cus) {
     if (n <= 0 || dim <= 0 || c <= 0 || n_cus <= 0) return 0;
-    const int rows = flex_axw_bf16_root_backward::dw_root_rows(n, dim, c, n_cus);
+    const int rows = flex_axw_bf16_dw::dw_root_rows(n, dim, c, n_cus);
     return (n + rows - 1) / rows;
 }
 
@@ -237,8 +183,7 @@ extern "C" int flex_axw_dw_bf16_root_slices(int n, int dim, int c, int n_cus) {
 // and dOut; anything else returns hipErrorInvalidValue before a launch.  Returns hipSuccess or the launch error.
 extern "C" hipError_t flex_axw_dw_bf16_root_launch(const flex_bf16 *X, const flex_bf16 *G, const flex_bf16 *dOut, flex_bf16 *dW, flex_bf16 *dR,
                                                    float *db, float *part, int n, int dim, int c, int cp, int n_cus, hipStream_t s) {
-    using namespace flex_axw_bf16_root_backward;
-    const auto misaligned = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
+    using namespace flex_axw_bf16_dw;
     const bool want_w = dW || dR;
     if ((want_w && !X) || !G || !dOut || !part || n < 32 || dim <= 0 || dim > 4096 || dim % 8 != 0 || c <= 0 || c > cp || cp > 256 || cp % 32 != 0 ||
         n_cus <= 0 || misaligned(X) || misaligned(G) || misaligned(dOut))
@@ -246,16 +191,13 @@ extern "C" hipError_t flex_axw_dw_bf16_root_launch(const flex_bf16 *X, const fle
     if (!want_w && !db) return hipSuccess;
     const int rows = dw_root_rows(n, dim, c, n_cus), slices = (n + rows - 1) / rows;
     const flex_bf16 *x = want_w ? X : nullptr;
-    hipError_t e;
-    switch (std::min(4, cp / 32)) {
-        case 1: e = launch<1>(x, G, dOut, part, n, dim, c, cp, rows, s); break;
-        case 2: e = launch<2>(x, G, dOut, part, n, dim, c, cp, rows, s); break;
-        case 3: e = launch<3>(x, G, dOut, part, n, dim, c, cp, rows, s); break;
-        default: e = launch<4>(x, G, dOut, part, n, dim, c, cp, rows, s); break;
-    }
+    const dim3 grid(static_cast<unsigned>(slices), static_cast<unsigned>((x ? (dim + 127) / 128 : 1) * ((cp + 127) / 128)));
+    const hipError_t e = dispatch_tiles<1, 2, 3, 4>(cp / 32, [&](auto tiles) {
+        constexpr int NT = decltype(tiles)::value;
+        return launch(axw_dw_bf16_root_kernel<NT>, grid, kThreads, static_cast<size_t>(2) * (kXFrags + 2 * 4 * NT * 64) * sizeof(u32x4), s, x, G, dOut,
+                      part, n, dim, c, cp, rows);
+    });
     if (e != hipSuccess) return e;
     const int dc = dim * c, first = want_w ? 0 : 2 * dc, todo = 2 * dc + c - first;
-    hipLaunchKernelGGL(axw_dw_bf16_root_reduce_kernel, dim3(static_cast<unsigned>((todo + 255) / 256)), dim3(256), 0, s, part, dW, dR, db, first, dc, c,
-                       slices);
-    return hipGetLastError();
+    return launch(axw_dw_bf16_root_reduce_kernel, dim3(static_cast<unsigned>((todo + 255) / 256)), 256, 0, s, part, dW, dR, db, first, dc, c, slices);
 }

@@ -6,8 +6,9 @@
 // Forward.  The L side is that of axw_bf16_kernels.hip: operands swapped (Wp^T the MFMA's A operand, L its B operand, 16 bytes of one row
 // a lane straight from global memory), v_mfma_f32_32x32x16_bf16, the k-steps in ascending order into ONE fp32 accumulator per entry (no
 // split of the contraction across waves or workgroups), the permlane store, the overlapping last panel, padding columns masked to +0.
-// The W side is new:
-//   * pack once: axw_bf16_pack_w_kernel turns W[dim x c] into the fragment order [k-step s][32-column tile t][lane][8 k values] in global
+// The kernel is axw_gemm_bf16_stream_kernel<NT, P, Stream::kWide> (axw_bf16_device.h): the body that the root forward and the root dX of
+// axw_bf16_root_kernels.hip instantiate with two sources.  Its W side:
+//   * pack once: axw_bf16_pack_kernel (axw_bf16_root_kernels.hip, d2 = 0) turns W[dim x c] into the fragment order [k-step s][32-column tile t][lane][8 k values] in global
 //     memory, zero padding columns included (dim x cp x 2 bytes, once per call: the eight 2-byte loads per fragment of stage_w are
 //     paid once, not once per round of panels).  A slab of kSlab = 8 k-steps (128 values of k, 256 bytes of each L row -- the unit whose
 //     L fragments a wave holds) is then 8 NT KiB of CONTIGUOUS memory in exactly the order the LDS wants.
@@ -40,100 +41,6 @@ extern "C" hipError_t flex_axw_dw_bf16_rows_launch(const flex_bf16 *X, const fle
 
 namespace flex_axw_bf16 {
 
-constexpr int kSlab = kUnit;  // k-steps of a slab of W
-
-// Wf[(s NT + t) 64 + lane] = the eight values W[16 s + 8 (lane >> 5) .. + 7][32 t + (lane & 31)], zero from column c on; one thread a fragment
-__global__ __launch_bounds__(256) void axw_bf16_pack_w_kernel(const flex_bf16 *__restrict__ W, u32x4 *__restrict__ Wf, int dim, int c, int nt) {
-    const int f = blockIdx.x * 256 + threadIdx.x;
-    if (f >= (dim >> 4) * nt * 64) return;
-    const int lane = f & 63, t = (f >> 6) % nt, s = (f >> 6) / nt;
-    const int col = 32 * t + (lane & 31), k0 = 16 * s + 8 * (lane >> 5);
-    uint32_t v[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = col < c ? W[static_cast<size_t>(k0 + e) * c + col] : 0u;
-    Wf[f] = u32x4{v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16), v[6] | (v[7] << 16)};
-}
-
-template <int NT, int P>  // 32-column tiles of Out, panels a wave
-__global__ __launch_bounds__(64 * kWaves) void axw_gemm_bf16_wide_kernel(const flex_bf16 *__restrict__ L, const u32x4 *__restrict__ Wf,
-                                                                         flex_bf16 *__restrict__ Out, int n, int dim, int c) {
-    extern __shared__ u32x4 sW[];  // [2 buffers][kSlab][NT][64] fragments of 8 bf16
-    constexpr int cp = 32 * NT, kStepFrags = NT * 64, kSlabFrags = kSlab * kStepFrags;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int j = lane & 31, h = lane >> 5;
-    const int steps = dim >> 4, slabs = (steps + kSlab - 1) / kSlab;
-    const int n_panels = (n + kRows - 1) / kRows;
-    const int n_rounds = (n_panels + kWaves * P - 1) / (kWaves * P);  // gridDim.x <= n_rounds: every workgroup has a round
-    auto panel_of = [&](int round, int p) { return (round * P + p) * kWaves + wave; };
-    auto panel_row = [&](int pnl) { return min(min(pnl, n_panels - 1) * kRows, n - kRows); };  // past the end: the last panel again
-    auto lfrag = [&](int pnl, int s) {
-        return *reinterpret_cast<const bf16x8 *>(L + static_cast<size_t>(panel_row(pnl) + j) * dim + 16 * s + 8 * h);
-    };
-    const bool stager = tid < kStepFrags;  // a k-step of W is NT KiB: one 16-byte fragment a thread of the first NT waves
-
-    bf16x8 pre[P][kSlab] = {};  // the L fragments of the slab about to be multiplied
-#pragma unroll
-    for (int q = 0; q < kSlab; ++q) {  // dim > 256: the first slab is a full one
-#pragma unroll
-        for (int p = 0; p < P; ++p) pre[p][q] = lfrag(panel_of(blockIdx.x, p), q);
-        if (stager) sW[q * kStepFrags + tid] = Wf[q * kStepFrags + tid];
-    }
-
-    int buf = 0;
-    const bf16x8 *wf = reinterpret_cast<const bf16x8 *>(sW) + lane;
-    for (int round = blockIdx.x; round < n_rounds; round += gridDim.x) {
-        f32x16 acc[P][NT];
-#pragma unroll
-        for (int p = 0; p < P; ++p)
-#pragma unroll
-            for (int t = 0; t < NT; ++t)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[p][t][i] = 0.f;
-        for (int sl = 0; sl < slabs; ++sl, buf ^= 1) {
-            // slab sl is whole in buffer buf (every store into it came before this barrier), and buffer buf ^ 1 was last read before it
-            __syncthreads();
-            const bool last = sl + 1 == slabs;  // workgroup-uniform, like everything that guards a load, a store or an MFMA below
-            const int nr = last ? round + gridDim.x : round, ns0 = last ? 0 : (sl + 1) * kSlab;
-            const int n_cur = min(kSlab, steps - sl * kSlab), n_next = nr < n_rounds ? min(kSlab, steps - ns0) : 0;
-            const u32x4 *src = Wf + static_cast<size_t>(ns0) * kStepFrags + tid;
-            u32x4 *dst = sW + (buf ^ 1) * kSlabFrags + tid;
-            const bf16x8 *w = wf + buf * kSlabFrags;
-            u32x4 stage[kSlab];
-#pragma unroll
-            for (int q = 0; q < kSlab; ++q) {
-                if (q >= 2 && q - 2 < n_next && stager) dst[(q - 2) * kStepFrags] = stage[q - 2];
-                bf16x8 b[P];
-#pragma unroll
-                for (int p = 0; p < P; ++p) b[p] = pre[p][q];
-                if (q < n_next) {
-#pragma unroll
-                    for (int p = 0; p < P; ++p) pre[p][q] = lfrag(panel_of(nr, p), ns0 + q);
-                    if (stager) stage[q] = src[q * kStepFrags];
-                }
-                if (q < n_cur) {
-#pragma unroll
-                    for (int t = 0; t < NT; ++t) {
-                        const bf16x8 a = w[(q * NT + t) * 64];
-#pragma unroll
-                        for (int p = 0; p < P; ++p) acc[p][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b[p], acc[p][t], 0, 0, 0);
-                    }
-                }
-            }
-#pragma unroll
-            for (int q = kSlab - 2; q < kSlab; ++q)
-                if (q < n_next && stager) dst[q * kStepFrags] = stage[q];
-        }
-#pragma unroll
-        for (int p = 0; p < P; ++p) {
-            const int panel = panel_of(round, p);
-            if (panel >= n_panels) continue;  // wave-uniform: the round's panels past the end were multiplied as copies of the last
-            flex_bf16 *dst = Out + static_cast<size_t>(panel_row(panel) + j) * cp + 16 * h;
-            const f32x16(&panel_acc)[NT] = acc[p];  // the macro has a loop variable p of its own
-            FLEX_AXW_BF16_STORE_PANEL(NT, panel_acc, dst, c, h)
-        }
-    }
-}
-
 // rows of an n-slice of the wide dW: ceil(n / S0) rounded up to a whole number of stages, S0 the smallest of
 //   ceil(n / 256)                      about 256 rows a slice, as the narrow rule,
 //   ceil(2 n_cus / blocks)             two workgroups a CU (64 KiB of LDS each) over the blocks = ceil(dim / 128) ceil(c / 128) of dW,
@@ -145,7 +52,6 @@ inline int dw_wide_rows(int n, int dim, int c, int n_cus) {
     return ((n + s0 - 1) / s0 + 63) / 64 * 64;
 }
 
-inline bool misaligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
 inline bool wide_dim(int dim, int multiple) { return dim > 256 && dim <= 4096 && dim % multiple == 0; }
 
 }  // namespace flex_axw_bf16
@@ -159,27 +65,14 @@ extern "C" hipError_t flex_axw_gemm_bf16_wide_launch(const flex_bf16 *L, const f
     if (!L || !W || !Wf || !Out || n < kRows || !wide_dim(dim, 16) || cp <= 0 || cp % 64 != 0 || cp > 256 || c <= 0 || c > cp || n_cus <= 0 ||
         misaligned(L) || misaligned(Wf) || misaligned(Out))
         return hipErrorInvalidValue;
-    const int nt = cp / 32, frags = (dim / 16) * nt * 64;
     u32x4 *wf = reinterpret_cast<u32x4 *>(Wf);
-    hipLaunchKernelGGL(axw_bf16_pack_w_kernel, dim3(static_cast<unsigned>((frags + 255) / 256)), dim3(256), 0, s, W, wf, dim, c, nt);
-    hipError_t e = hipGetLastError();
+    const hipError_t e = pack_launch(W, nullptr, wf, dim, 0, c, cp / 32, s);
     if (e != hipSuccess) return e;
-    const int n_panels = (n + kRows - 1) / kRows;
-    const size_t lds = static_cast<size_t>(2) * kSlab * nt * 64 * sizeof(u32x4);
-    auto go = [&](auto kernel, int panels_a_round) {  // more than 64 KiB of dynamic LDS has to be asked for
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        if (e != hipSuccess) return;
-        const int n_rounds = (n_panels + panels_a_round - 1) / panels_a_round;
-        hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(std::min(n_cus, n_rounds))), dim3(64 * kWaves), lds, s, L, wf, Out, n, dim, c);
-        e = hipGetLastError();
-    };
-    switch (nt) {
-        case 2: go(axw_gemm_bf16_wide_kernel<2, 2>, 2 * kWaves); break;
-        case 4: go(axw_gemm_bf16_wide_kernel<4, 1>, kWaves); break;
-        case 6: go(axw_gemm_bf16_wide_kernel<6, 1>, kWaves); break;
-        default: go(axw_gemm_bf16_wide_kernel<8, 1>, kWaves); break;
-    }
-    return e;
+    return dispatch_tiles<2, 4, 6, 8>(cp / 32, [&](auto tiles) {
+        constexpr int NT = decltype(tiles)::value, P = stream_panels(NT);
+        return launch(axw_gemm_bf16_stream_kernel<NT, P, Stream::kWide>, dim3(panel_groups(n, kWaves * P, n_cus)), 64 * kWaves, stream_lds(NT), s, L,
+                      dim, nullptr, 0, wf, nullptr, nullptr, Out, n, c);
+    });
 }
 
 // dX[n x dim] = G[n x cp] * Wt[cp x dim] on flex_bf16.  Takes n >= 32, cp % 64 == 0, 0 < cp <= 256, 256 < dim <= 4096, dim % 32 == 0,
@@ -190,29 +83,15 @@ extern "C" hipError_t flex_axw_dx_bf16_wide_launch(const flex_bf16 *G, const fle
     if (!G || !Wt || !dX || n < kRows || cp <= 0 || cp % 64 != 0 || cp > 256 || !wide_dim(dim, 32) || n_cus <= 0 || misaligned(G) ||
         misaligned(Wt) || misaligned(dX))
         return hipErrorInvalidValue;
-    const int n_panels = (n + kRows - 1) / kRows, groups = std::min(n_cus, (n_panels + 3) / 4);
     const int full = dim / 256, tail = dim % 256;
-    hipError_t e = hipSuccess;
-    auto go = [&](auto kernel, int passes, int col0, int width) {
-        const size_t lds = static_cast<size_t>(cp) * width * sizeof(flex_bf16);
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        if (e != hipSuccess) return;
-        hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(groups), static_cast<unsigned>(passes)), dim3(64 * kWaves), lds, s, G, Wt + col0,
-                           dX + col0, n, cp, width, dim);
-        e = hipGetLastError();
+    auto windows = [&](auto tiles, int passes, int col0) {  // `passes` windows of 32 NT columns of dX from column col0 on
+        constexpr int NT = decltype(tiles)::value;
+        return launch(axw_gemm_bf16_kernel<NT, true>, dim3(panel_groups(n, 4, n_cus), static_cast<unsigned>(passes)), 64 * kWaves,
+                      static_cast<size_t>(cp) * 32 * NT * sizeof(flex_bf16), s, G, Wt + col0, dX + col0, n, cp, 32 * NT, dim);
     };
-    go(axw_gemm_bf16_kernel<8, true>, full, 0, 256);
+    const hipError_t e = windows(std::integral_constant<int, 8>(), full, 0);
     if (e != hipSuccess || tail == 0) return e;
-    switch (tail / 32) {
-        case 1: go(axw_gemm_bf16_kernel<1, true>, 1, 256 * full, tail); break;
-        case 2: go(axw_gemm_bf16_kernel<2, true>, 1, 256 * full, tail); break;
-        case 3: go(axw_gemm_bf16_kernel<3, true>, 1, 256 * full, tail); break;
-        case 4: go(axw_gemm_bf16_kernel<4, true>, 1, 256 * full, tail); break;
-        case 5: go(axw_gemm_bf16_kernel<5, true>, 1, 256 * full, tail); break;
-        case 6: go(axw_gemm_bf16_kernel<6, true>, 1, 256 * full, tail); break;
-        default: go(axw_gemm_bf16_kernel<7, true>, 1, 256 * full, tail); break;
-    }
-    return e;
+    return dispatch_tiles<1, 2, 3, 4, 5, 6, 7>(tail / 32, [&](auto tiles) { return windows(tiles, 1, 256 * full); });
 }
 
 // n-slices of the wide bf16 dW: ceil(n / rows), rows = dw_wide_rows above; 0 for arguments the launcher refuses
