@@ -294,6 +294,46 @@ def axw_root_functions():
     return _axw_root_cache
 
 
+def _axw_root_act_function():
+    import torch
+
+    class _AxwRootActLayer(torch.autograd.Function):
+        """Out = dropout(relu(A X W + X R + bias)) on a bf16 handle, activation and mask inside the last kernel (Axw.run_root_act);
+        backward: the one call flex_axw_backward_root_act_bf16 on the saved Out -- no mask is stored and none recomputed: Out > 0
+        exactly where the unit was active and kept."""
+
+        @staticmethod
+        def forward(ctx, X, W, R, bias, h, order, p, seed):
+            X, W, R = X.contiguous(), W.contiguous(), R.contiguous()
+            out = h.run_root_act(X, W, R, None if bias is None else bias.contiguous(), p, seed, order)
+            ctx.h, ctx.p = h, p
+            ctx.save_for_backward(X, W, R, out)
+            return out[:, : h.c]
+
+        @staticmethod
+        def backward(ctx, grad_out):
+            X, W, R, out = ctx.saved_tensors
+            h = ctx.h
+            need = ctx.needs_input_grad
+            dOut = torch.zeros((h.n, h.ld), dtype=torch.bfloat16, device=grad_out.device)
+            dOut[:, : h.c] = grad_out
+            gx, gw, gr, gb = h.backward_root_act(dOut, out, X, W, R, ctx.p, need_x=need[0], need_w=need[1] or need[2], need_b=need[3])
+            return gx, gw if need[1] else None, gr if need[2] else None, gb, None, None, None, None
+
+    return (_AxwRootActLayer,)
+
+
+_axw_root_act_cache = None
+
+
+def axw_root_act_functions():
+    """(_AxwRootActLayer,): built at first use, as functions()."""
+    global _axw_root_act_cache
+    if _axw_root_act_cache is None:
+        _axw_root_act_cache = _axw_root_act_function()
+    return _axw_root_act_cache
+
+
 def _dropout_function():
     import torch
 

@@ -57,6 +57,12 @@ def lib():
         L.flex_axw_dw_bf16_root_launch.argtypes = [vp] * 7 + [C.c_int] * 5 + [vp]
         L.flex_axw_dw_bf16_root_launch.restype = C.c_int
         L.flex_axw_dw_bf16_root_slices.argtypes = [C.c_int] * 4
+        L.flex_axw_run_root_act_bf16.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.c_float, C.c_uint64, vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.flex_axw_backward_root_act_bf16.argtypes = [vp] * 11 + [C.c_float, vp]
+        L.flex_axw_gemm_bf16_root_act_launch.argtypes = L.flex_axw_gemm_bf16_root_launch.argtypes[:-1] + [C.c_float, C.c_uint64, vp]
+        L.flex_axw_gemm_bf16_root_act_launch.restype = C.c_int
+        L.flex_axw_act_grad_bf16_launch.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, vp]
+        L.flex_axw_act_grad_bf16_launch.restype = C.c_int
         _lib = L
     return _lib
 
@@ -137,6 +143,21 @@ def _dw_bf16_root_slices(n: int, dim: int, c: int, n_cus: int) -> int:
     return lib().flex_axw_dw_bf16_root_slices(n, dim, c, n_cus)
 
 
+def _gemm_bf16_root_act_launch(L1_ptr: int, W1_ptr: int, d1: int, L2_ptr, W2_ptr, d2: int, Cin_ptr, bias_ptr, Wf_ptr: int, Out_ptr: int, n: int,
+                               c: int, cp: int, n_cus: int, drop_p: float, seed: int, stream: int = 0) -> int:
+    """The dense stage of flex_axw_run_root_act_bf16 on its own (flex_axw_gemm_bf16_root_act_launch): _gemm_bf16_root_launch with ReLU and
+    dropout (probability drop_p, mask binding.dropout_mask(seed, drop_p, 0, n * c) as [n, c]) before the one rounding.  Returns the
+    hipError_t; for tests."""
+    return lib().flex_axw_gemm_bf16_root_act_launch(L1_ptr, W1_ptr, d1, L2_ptr, W2_ptr, d2, Cin_ptr, bias_ptr, Wf_ptr, Out_ptr, n, c, cp, n_cus,
+                                                    drop_p, seed, stream)
+
+
+def _act_grad_bf16_launch(Out_ptr: int, dOut_ptr: int, dZ_ptr: int, n: int, c: int, cp: int, cs: float, stream: int = 0) -> int:
+    """The first pass of flex_axw_backward_root_act_bf16 on its own (flex_axw_act_grad_bf16_launch): bf16 dZ[n x cp] = dOut * cs where
+    Out > 0, +0 elsewhere and in columns >= c.  Returns the hipError_t; for tests."""
+    return lib().flex_axw_act_grad_bf16_launch(Out_ptr, dOut_ptr, dZ_ptr, n, c, cp, cs, stream)
+
+
 class Axw:
     """flex_axw handle: plans A for both SpMM widths once; run() computes A @ X @ W in either order."""
 
@@ -191,6 +212,27 @@ class Axw:
                                                     C.byref(g) if timed else None, C.byref(s) if timed else None), "flex_axw_run_root_bf16")
         return (out, (g.value, s.value)) if timed else out
 
+    def run_root_act(self, X, W, R, bias=None, p: float = 0.0, seed: int = 0, order: int = FLEX_AXW_AUTO, timed: bool = False):
+        """flex_axw_run_root_act_bf16: run_root() with ReLU and dropout (probability p, the kept entries scaled by 1 / (1 - p), the mask
+        binding.dropout_mask(seed, p, 0, n * c) as [n, c]) applied in the last kernel before its one rounding.  Operands, errors and the
+        return value as run_root().  No autograd: root_layer(relu=True) is the differentiable form."""
+        import torch
+        if not self.has_root:
+            raise binding.FlexError("Axw.run_root_act: the handle was made without root=True (FLEX_AXW_ROOT)")
+        if any(t.dtype != torch.bfloat16 for t in (X, W, R)):
+            raise TypeError(f"Axw.run_root_act takes torch.bfloat16 X, W and R; got {X.dtype}, {W.dtype} and {R.dtype}")
+        if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (self.c,)):
+            raise TypeError(f"Axw.run_root_act takes a float32 bias of shape [{self.c}]; got {bias.dtype} {tuple(bias.shape)}")
+        assert all(t.is_cuda and t.is_contiguous() for t in (X, W, R)) and (bias is None or (bias.is_cuda and bias.is_contiguous()))
+        assert tuple(X.shape) == (self.n, self.dim) and tuple(W.shape) == tuple(R.shape) == (self.dim, self.c)
+        out = torch.empty((self.n, self.ld), dtype=torch.bfloat16, device=X.device)
+        g, s = C.c_float(), C.c_float()
+        binding._check(lib().flex_axw_run_root_act_bf16(self._h, order, X.data_ptr(), W.data_ptr(), R.data_ptr(),
+                                                        None if bias is None else bias.data_ptr(), out.data_ptr(), p, seed,
+                                                        torch.cuda.current_stream(X.device).cuda_stream, C.byref(g) if timed else None,
+                                                        C.byref(s) if timed else None), "flex_axw_run_root_act_bf16")
+        return (out, (g.value, s.value)) if timed else out
+
     def backward(self, dOut, X, W, need_x: bool = True, need_w: bool = True):
         """flex_axw_backward: dOut [n, ld] -> (dX [n, dim] or None, dW [dim, c] or None), dX = A^T dOut W^T and dW = X^T (A^T dOut).  X and
         W are the forward's inputs (only the ones a requested gradient needs).  float32, dOut's padding columns never read; on a bf16
@@ -222,15 +264,15 @@ class Axw:
         from .autograd import functions
         return functions()[1].apply(X, W, self, order)
 
-    def backward_root(self, dOut, X, W, R, need_x: bool = True, need_w: bool = True, need_b: bool = True):
+    def backward_root(self, dOut, X, W, R, need_x: bool = True, need_w: bool = True, need_b: bool = True, _act=None):
         """flex_axw_backward_root_bf16: dOut [n, ld] -> (dX [n, dim], dW [dim, c], dR [dim, c], db [c] float32), each None unless asked for:
         dX = A^T dOut W^T + dOut R^T in one chain, dW = X^T (A^T dOut), dR = X^T dOut, db = dOut.sum(0).  dW and dR come together (need_w).
         X, W and R are the forward's inputs (only the ones a requested gradient needs); torch.bfloat16 (any other dtype: TypeError);
-        dOut's padding columns are read and must be finite."""
+        dOut's padding columns are read and must be finite.  _act = (Out, p): backward_root_act()."""
         import torch
         if not (self.has_backward and self.has_root):
             raise binding.FlexError("Axw.backward_root: the handle was made without backward=True and root=True")
-        given = [t for t, need in ((dOut, True), (X, need_w), (W, need_x), (R, need_x)) if need]
+        given = [t for t, need in ((dOut, True), (X, need_w), (W, need_x), (R, need_x)) if need] + ([] if _act is None else [_act[0]])
         if any(t.dtype != torch.bfloat16 for t in given):
             raise TypeError(f"Axw.backward_root takes torch.bfloat16 dOut, X, W and R; got {[str(t.dtype) for t in given]}")
         assert dOut.is_cuda and dOut.is_contiguous() and tuple(dOut.shape) == (self.n, self.ld)
@@ -241,18 +283,43 @@ class Axw:
         gx, gw, gr = new(need_x, (self.n, self.dim)), new(need_w, (self.dim, self.c)), new(need_w, (self.dim, self.c))
         gb = new(need_b, (self.c,), torch.float32)
         ptr = lambda t, need=True: t.data_ptr() if need and t is not None else None  # noqa: E731
-        binding._check(lib().flex_axw_backward_root_bf16(self._h, ptr(X, need_w), ptr(W, need_x), ptr(R, need_x), dOut.data_ptr(), ptr(gx), ptr(gw),
-                                                         ptr(gr), ptr(gb), torch.cuda.current_stream(dOut.device).cuda_stream),
-                       "flex_axw_backward_root_bf16")
+        stream = torch.cuda.current_stream(dOut.device).cuda_stream
+        if _act is None:
+            binding._check(lib().flex_axw_backward_root_bf16(self._h, ptr(X, need_w), ptr(W, need_x), ptr(R, need_x), dOut.data_ptr(), ptr(gx),
+                                                             ptr(gw), ptr(gr), ptr(gb), stream), "flex_axw_backward_root_bf16")
+        else:
+            out, p = _act
+            assert out.is_cuda and out.is_contiguous() and tuple(out.shape) == (self.n, self.ld)
+            work = torch.empty_like(dOut)
+            binding._check(lib().flex_axw_backward_root_act_bf16(self._h, ptr(X, need_w), ptr(W, need_x), ptr(R, need_x), out.data_ptr(),
+                                                                 dOut.data_ptr(), work.data_ptr(), ptr(gx), ptr(gw), ptr(gr), ptr(gb), p, stream),
+                           "flex_axw_backward_root_act_bf16")
         return gx, gw, gr, gb
 
-    def root_layer(self, X, W, R, bias=None, order: int = FLEX_AXW_AUTO):
+    def backward_root_act(self, dOut, Out, X, W, R, p: float = 0.0, need_x: bool = True, need_w: bool = True, need_b: bool = True):
+        """flex_axw_backward_root_act_bf16: backward_root() of dZ = dOut / (1 - p) where Out > 0, +0 elsewhere; Out [n, ld] is what
+        run_root_act() returned under the same p (no mask, no seed).  dOut's padding columns are ignored."""
+        return self.backward_root(dOut, X, W, R, need_x, need_w, need_b, _act=(Out, p))
+
+    def root_layer(self, X, W, R, bias=None, order: int = FLEX_AXW_AUTO, relu: bool = False, dropout: float = 0.0, seed=None,
+                   training: bool = True):
         """Differentiable A X W + X R + bias: Out [n, c] (a view of run_root()'s padded product); its gradient flows to X, W, R and bias
-        through backward_root().  X, W, R, Out and their gradients are torch.bfloat16, bias and its gradient float32."""
+        through backward_root().  X, W, R, Out and their gradients are torch.bfloat16, bias and its gradient float32.
+        relu=True: the hidden layer dropout(relu(.)) in the same kernels (run_root_act / backward_root_act): dropout is the drop probability
+        (0 when training is False), seed the mask's (None: one is drawn from torch's generator); the backward keeps Out, not a mask.
+        dropout > 0 without relu=True is a ValueError: the backward reads the mask off Out > 0, which needs the ReLU."""
         if not (self.has_backward and self.has_root):
             raise binding.FlexError("Axw.root_layer: the handle was made without backward=True and root=True")
-        from .autograd import axw_root_functions
-        return axw_root_functions()[0].apply(X, W, R, bias, self, order)
+        from .autograd import axw_root_act_functions, axw_root_functions
+        if not relu:
+            if dropout > 0:
+                raise ValueError("Axw.root_layer: dropout > 0 needs relu=True")
+            return axw_root_functions()[0].apply(X, W, R, bias, self, order)
+        p = float(dropout) if training else 0.0
+        if p > 0 and seed is None:
+            import torch
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+        return axw_root_act_functions()[0].apply(X, W, R, bias, self, order, p, int(seed or 0) & 0xFFFFFFFFFFFFFFFF)
 
     def destroy(self):
         if getattr(self, "_h", None) and self._h.value:

@@ -44,6 +44,11 @@ extern "C" hipError_t flex_axw_dw_bf16_root_launch(const flex_bf16 *X, const fle
                                                    float *db, float *part, int n, int dim, int c, int cp, int n_cus,
                                                    hipStream_t s);  // axw_bf16_root_backward_kernels.hip
 extern "C" int flex_axw_dw_bf16_root_slices(int n, int dim, int c, int n_cus);
+extern "C" hipError_t flex_axw_gemm_bf16_root_act_launch(const flex_bf16 *L1, const flex_bf16 *W1, int d1, const flex_bf16 *L2, const flex_bf16 *W2,
+                                                         int d2, const flex_bf16 *Cin, const float *bias, flex_bf16 *Wf, flex_bf16 *Out, int n, int c,
+                                                         int cp, int n_cus, float drop_p, uint64_t seed, hipStream_t s);  // axw_bf16_act_kernels.hip
+extern "C" hipError_t flex_axw_act_grad_bf16_launch(const flex_bf16 *Out, const flex_bf16 *dOut, flex_bf16 *dZ, int n, int c, int cp, float cs,
+                                                    hipStream_t s);
 
 struct flex_axw {
     int32_t n = 0;
@@ -137,6 +142,82 @@ int grad_aggregate_bf16(flex_axw *h, const flex_bf16 *dOut, flex_stream_t stream
     flex_bf16 *g = reinterpret_cast<flex_bf16 *>(h->d_g);
     int rc = flex_spmm_bf16(h->plan_t, dOut, g, stream);
     if (!rc && h->a_nonfinite) rc = hip_fail(flex_axw_bf16_clear_padding_launch(g, h->n, h->c, h->cp, reinterpret_cast<hipStream_t>(stream)));
+    return rc;
+}
+
+// the activation of flex_axw_run_root_act_bf16; drop_p_ok is the rule of the attention dropout (0 <= drop_p < 1, finite)
+struct RootAct {
+    float drop_p;
+    uint64_t seed;
+};
+bool drop_p_ok(float p) { return std::isfinite(p) && p >= 0.f && p < 1.f; }
+
+// The two root forwards: the stages of either order, the last of them the root kernel or, with `act`, its ReLU-and-dropout form.
+int run_root(flex_axw *h, int order, const flex_bf16 *dX, const flex_bf16 *dW, const flex_bf16 *dR, const float *dBias, flex_bf16 *dOut,
+             const RootAct *act, flex_stream_t stream, float *gemm_ms, float *spmm_ms) {
+    if (!h || !h->d_wf || !dX || !dW || !dR || !dOut || order < FLEX_AXW_AUTO || order > FLEX_AXW_AX_W) return FLEX_ERR_INVALID;
+    if (misaligned16({dX, dOut})) return FLEX_ERR_UNSUPPORTED;
+    if (order == FLEX_AXW_AUTO) order = h->cp <= h->dim ? FLEX_AXW_A_XW : FLEX_AXW_AX_W;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    flex_bf16 *xw = reinterpret_cast<flex_bf16 *>(h->d_xw), *ax = reinterpret_cast<flex_bf16 *>(h->d_ax);
+    flex_bf16 *sum = reinterpret_cast<flex_bf16 *>(h->d_s), *wf = reinterpret_cast<flex_bf16 *>(h->d_wf);
+    const flex::DeviceScope on(h->device);
+    int rc = hip_fail(on.error());
+    const Marks mark{h, s, gemm_ms || spmm_ms};
+    auto last = [&](const flex_bf16 *L1, const flex_bf16 *W1, const flex_bf16 *L2, const flex_bf16 *W2, int d2, const flex_bf16 *Cin) {
+        return hip_fail(act ? flex_axw_gemm_bf16_root_act_launch(L1, W1, h->dim, L2, W2, d2, Cin, dBias, wf, dOut, h->n, h->c, h->cp, h->n_cus,
+                                                                  act->drop_p, act->seed, s)
+                            : flex_axw_gemm_bf16_root_launch(L1, W1, h->dim, L2, W2, d2, Cin, dBias, wf, dOut, h->n, h->c, h->cp, h->n_cus, s));
+    };
+    if (!rc) rc = mark(0);
+    if (order == FLEX_AXW_A_XW) {
+        if (!rc && !h->wide) rc = pad_w(h, dW, sizeof(flex_bf16), s);
+        if (!rc) rc = dense_bf16(h, dX, dW, xw, s);
+        if (!rc) rc = mark(1);
+        if (!rc) rc = flex_spmm_bf16(h->plan_c, xw, sum, stream);
+        if (!rc && h->a_nonfinite) rc = hip_fail(flex_axw_bf16_clear_padding_launch(sum, h->n, h->c, h->cp, s));  // inf x 0 = NaN there
+        if (!rc) rc = mark(2);
+        if (!rc) rc = last(dX, dR, nullptr, nullptr, 0, sum);
+    } else {
+        if (!rc) rc = mark(1);  // no dense stage before the SpMM
+        if (!rc) rc = flex_spmm_bf16(h->plan_dim, dX, ax, stream);
+        if (!rc) rc = mark(2);
+        if (!rc) rc = last(ax, dW, dX, dR, h->dim, nullptr);
+    }
+    if (!rc) rc = mark(3);
+    float ms[3] = {0.f, 0.f, 0.f};
+    if (!rc) rc = mark.read(3, ms);
+    if (!rc && mark.timed) {  // the dense stages either side of the SpMM count as gemm
+        if (gemm_ms) *gemm_ms = ms[0] + ms[2];
+        if (spmm_ms) *spmm_ms = ms[1];
+    }
+    return rc;
+}
+
+// What the two root backwards refuse, before anything is enqueued; FLEX_OK: the call goes on.
+int backward_root_refused(flex_axw *h, const flex_bf16 *dX, const flex_bf16 *dW, const flex_bf16 *dR, const flex_bf16 *dOut, flex_bf16 *dGradX,
+                          flex_bf16 *dGradW, flex_bf16 *dGradR, float *dGradBias) {
+    if (!h || !h->bf16 || !h->plan_t || !h->d_wf || !dOut || (dGradW != nullptr) != (dGradR != nullptr) || (dGradX && (!dW || !dR)) ||
+        (dGradW && !dX))
+        return FLEX_ERR_INVALID;
+    if (misaligned16({dOut, dGradX, dGradW, dGradR, dGradX ? dW : nullptr, dGradX ? dR : nullptr, dGradW ? dX : nullptr}))
+        return FLEX_ERR_UNSUPPORTED;
+    return reinterpret_cast<uintptr_t>(dGradBias) & 3 ? FLEX_ERR_UNSUPPORTED : FLEX_OK;
+}
+
+// The launches of the two root backwards, on a dOut (the activation's: its dZ) that backward_root_refused passed.
+int backward_root(flex_axw *h, const flex_bf16 *dX, const flex_bf16 *dW, const flex_bf16 *dR, const flex_bf16 *dOut, flex_bf16 *dGradX,
+                  flex_bf16 *dGradW, flex_bf16 *dGradR, float *dGradBias, flex_stream_t stream) {
+    if (!dGradX && !dGradW && !dGradBias) return FLEX_OK;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    flex_bf16 *g = reinterpret_cast<flex_bf16 *>(h->d_g), *wf = reinterpret_cast<flex_bf16 *>(h->d_wf);
+    const flex::DeviceScope on(h->device);
+    int rc = hip_fail(on.error());
+    if (!rc && (dGradX || dGradW)) rc = grad_aggregate_bf16(h, dOut, stream);  // dGradBias alone needs no G
+    if (!rc && dGradX) rc = hip_fail(flex_axw_dx_bf16_root_launch(g, dW, dOut, dR, wf, dGradX, h->n, h->c, h->cp, h->dim, h->n_cus, s));
+    if (!rc && (dGradW || dGradBias))
+        rc = hip_fail(flex_axw_dw_bf16_root_launch(dGradW ? dX : nullptr, g, dOut, dGradW, dGradR, dGradBias, h->d_part, h->n, h->dim, h->c, h->cp,
+                                                   h->n_cus, s));
     return rc;
 }
 
@@ -329,38 +410,16 @@ int flex_axw_run_bf16(flex_axw *h, int order, const flex_bf16 *dX, const flex_bf
 // product with A (X W) as its addend; the stages before it are flex_axw_run_bf16's own.
 int flex_axw_run_root_bf16(flex_axw *h, int order, const flex_bf16 *dX, const flex_bf16 *dW, const flex_bf16 *dR, const float *dBias,
                            flex_bf16 *dOut, flex_stream_t stream, float *gemm_ms, float *spmm_ms) {
-    if (!h || !h->d_wf || !dX || !dW || !dR || !dOut || order < FLEX_AXW_AUTO || order > FLEX_AXW_AX_W) return FLEX_ERR_INVALID;
-    if (misaligned16({dX, dOut})) return FLEX_ERR_UNSUPPORTED;
-    if (order == FLEX_AXW_AUTO) order = h->cp <= h->dim ? FLEX_AXW_A_XW : FLEX_AXW_AX_W;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    flex_bf16 *xw = reinterpret_cast<flex_bf16 *>(h->d_xw), *ax = reinterpret_cast<flex_bf16 *>(h->d_ax);
-    flex_bf16 *sum = reinterpret_cast<flex_bf16 *>(h->d_s), *wf = reinterpret_cast<flex_bf16 *>(h->d_wf);
-    const flex::DeviceScope on(h->device);
-    int rc = hip_fail(on.error());
-    const Marks mark{h, s, gemm_ms || spmm_ms};
-    if (!rc) rc = mark(0);
-    if (order == FLEX_AXW_A_XW) {
-        if (!rc && !h->wide) rc = pad_w(h, dW, sizeof(flex_bf16), s);
-        if (!rc) rc = dense_bf16(h, dX, dW, xw, s);
-        if (!rc) rc = mark(1);
-        if (!rc) rc = flex_spmm_bf16(h->plan_c, xw, sum, stream);
-        if (!rc && h->a_nonfinite) rc = hip_fail(flex_axw_bf16_clear_padding_launch(sum, h->n, h->c, h->cp, s));  // inf x 0 = NaN there
-        if (!rc) rc = mark(2);
-        if (!rc) rc = hip_fail(flex_axw_gemm_bf16_root_launch(dX, dR, h->dim, nullptr, nullptr, 0, sum, dBias, wf, dOut, h->n, h->c, h->cp, h->n_cus, s));
-    } else {
-        if (!rc) rc = mark(1);  // no dense stage before the SpMM
-        if (!rc) rc = flex_spmm_bf16(h->plan_dim, dX, ax, stream);
-        if (!rc) rc = mark(2);
-        if (!rc) rc = hip_fail(flex_axw_gemm_bf16_root_launch(ax, dW, h->dim, dX, dR, h->dim, nullptr, dBias, wf, dOut, h->n, h->c, h->cp, h->n_cus, s));
-    }
-    if (!rc) rc = mark(3);
-    float ms[3] = {0.f, 0.f, 0.f};
-    if (!rc) rc = mark.read(3, ms);
-    if (!rc && mark.timed) {  // the dense stages either side of the SpMM count as gemm
-        if (gemm_ms) *gemm_ms = ms[0] + ms[2];
-        if (spmm_ms) *spmm_ms = ms[1];
-    }
-    return rc;
+    return run_root(h, order, dX, dW, dR, dBias, dOut, nullptr, stream, gemm_ms, spmm_ms);
+}
+
+// flex_axw_run_root_bf16 with ReLU and dropout applied to the last dense launch's accumulators before their one rounding
+// (axw_bf16_act_kernels.hip); every launch before it, and the order of the graph's nodes, are that call's.
+int flex_axw_run_root_act_bf16(flex_axw *h, int order, const flex_bf16 *dX, const flex_bf16 *dW, const flex_bf16 *dR, const float *dBias,
+                               flex_bf16 *dOut, float drop_p, uint64_t seed, flex_stream_t stream, float *gemm_ms, float *spmm_ms) {
+    if (!drop_p_ok(drop_p)) return FLEX_ERR_INVALID;
+    const RootAct act{drop_p, seed};
+    return run_root(h, order, dX, dW, dR, dBias, dOut, &act, stream, gemm_ms, spmm_ms);
 }
 
 // G = A^T dOut (the transposed plan), then dGradX = G W^T and dGradW = X^T G (axw_kernels.hip; rocBLAS where the kernels do not take
@@ -428,23 +487,26 @@ int flex_axw_backward_bf16(flex_axw *h, const flex_bf16 *dX, const flex_bf16 *dW
 // and dGradBias from one pass over X (axw_bf16_root_backward_kernels.hip).  Everything is queued on `stream`: no allocation, no host sync.
 int flex_axw_backward_root_bf16(flex_axw *h, const flex_bf16 *dX, const flex_bf16 *dW, const flex_bf16 *dR, const flex_bf16 *dOut,
                                 flex_bf16 *dGradX, flex_bf16 *dGradW, flex_bf16 *dGradR, float *dGradBias, flex_stream_t stream) {
-    if (!h || !h->bf16 || !h->plan_t || !h->d_wf || !dOut || (dGradW != nullptr) != (dGradR != nullptr) || (dGradX && (!dW || !dR)) ||
-        (dGradW && !dX))
-        return FLEX_ERR_INVALID;
-    if (misaligned16({dOut, dGradX, dGradW, dGradR, dGradX ? dW : nullptr, dGradX ? dR : nullptr, dGradW ? dX : nullptr}))
-        return FLEX_ERR_UNSUPPORTED;
-    if (reinterpret_cast<uintptr_t>(dGradBias) & 3) return FLEX_ERR_UNSUPPORTED;
+    const int rc = backward_root_refused(h, dX, dW, dR, dOut, dGradX, dGradW, dGradR, dGradBias);
+    return rc ? rc : backward_root(h, dX, dW, dR, dOut, dGradX, dGradW, dGradR, dGradBias, stream);
+}
+
+// The backward of flex_axw_run_root_act_bf16: one pass writes dZ = Out > 0 ? rn_bf16(dOut / (1 - drop_p)) : +0 into dWork
+// (axw_bf16_act_kernels.hip: the stored Out is the mask), then flex_axw_backward_root_bf16's launches read dWork where they read dOut.
+int flex_axw_backward_root_act_bf16(flex_axw *h, const flex_bf16 *dX, const flex_bf16 *dW, const flex_bf16 *dR, const flex_bf16 *dFwdOut,
+                                    const flex_bf16 *dOut, flex_bf16 *dWork, flex_bf16 *dGradX, flex_bf16 *dGradW, flex_bf16 *dGradR,
+                                    float *dGradBias, float drop_p, flex_stream_t stream) {
+    if (!dFwdOut || !dWork || dWork == dOut || dWork == dFwdOut || !drop_p_ok(drop_p)) return FLEX_ERR_INVALID;
+    int rc = backward_root_refused(h, dX, dW, dR, dOut, dGradX, dGradW, dGradR, dGradBias);
+    if (rc) return rc;
+    if (misaligned16({dFwdOut, dWork})) return FLEX_ERR_UNSUPPORTED;
     if (!dGradX && !dGradW && !dGradBias) return FLEX_OK;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    flex_bf16 *g = reinterpret_cast<flex_bf16 *>(h->d_g), *wf = reinterpret_cast<flex_bf16 *>(h->d_wf);
     const flex::DeviceScope on(h->device);
-    int rc = hip_fail(on.error());
-    if (!rc && (dGradX || dGradW)) rc = grad_aggregate_bf16(h, dOut, stream);  // dGradBias alone needs no G
-    if (!rc && dGradX) rc = hip_fail(flex_axw_dx_bf16_root_launch(g, dW, dOut, dR, wf, dGradX, h->n, h->c, h->cp, h->dim, h->n_cus, s));
-    if (!rc && (dGradW || dGradBias))
-        rc = hip_fail(flex_axw_dw_bf16_root_launch(dGradW ? dX : nullptr, g, dOut, dGradW, dGradR, dGradBias, h->d_part, h->n, h->dim, h->c, h->cp,
-                                                   h->n_cus, s));
-    return rc;
+    rc = hip_fail(on.error());
+    if (!rc)
+        rc = hip_fail(flex_axw_act_grad_bf16_launch(dFwdOut, dOut, dWork, h->n, h->c, h->cp, 1.0f / (1.0f - drop_p),
+                                                    reinterpret_cast<hipStream_t>(stream)));
+    return rc ? rc : backward_root(h, dX, dW, dR, dWork, dGradX, dGradW, dGradR, dGradBias, stream);
 }
 
 }  // extern "C"

@@ -1,9 +1,9 @@
 // axw_bf16_device.h -- what the bf16 GEMM files of libflex_axw.so share (axw_bf16_kernels.hip, axw_bf16_wide_kernels.hip,
-// axw_bf16_root_kernels.hip):
+// axw_bf16_root_kernels.hip, axw_bf16_act_kernels.hip):
 //   * stage_w, FLEX_AXW_BF16_STORE_PANEL and axw_gemm_bf16_kernel: the GEMM with the whole W resident in LDS (the narrow forward and dX,
 //     the wide dX's windows).  Its data path is described at the top of axw_bf16_kernels.hip.
 //   * axw_gemm_bf16_stream_kernel: the GEMM with W streamed through two LDS slab buffers -- ONE body for the wide forward, the root
-//     forward and the root dX's windows (Stream).  The pipeline is described at the top of axw_bf16_wide_kernels.hip, the two sources,
+//     forward, its ReLU-and-dropout form and the root dX's windows (Stream).  The pipeline is described at the top of axw_bf16_wide_kernels.hip, the two sources,
 //     the addend and the bias at the top of axw_bf16_root_kernels.hip.
 //   * the host side of every launcher: misaligned, the panel arithmetic, launch and dispatch_tiles.  axw_bf16_dw_device.h includes this
 //     file for them.
@@ -151,22 +151,27 @@ __global__ __launch_bounds__(64 * kWaves) void axw_gemm_bf16_kernel(const flex_b
     }
 }
 
-// The three uses of the streamed GEMM below; everything that tells them apart is decided at compile time.
+// The four uses of the streamed GEMM below; everything that tells them apart is decided at compile time.
 //   kWide    Out[n x cp] = L1[n x d1] Wf: one source, the chain from +0 (flex_axw_gemm_bf16_wide_launch; L2, d2, Cin and bias are not read)
 //   kRoot    Out[n x cp] = L1 W1 + L2 W2 + Cin + bias: two sources, acc = fp32(Cin) + bias (flex_axw_gemm_bf16_root_launch)
 //   kWindow  the dual-source dX of flex_axw_dx_bf16_root_launch: two sources, the chain from +0; Out is a window of 32 NT whole columns,
 //            from 256 blockIdx.y on, of an array whose rows are `c` elements apart (the parameter carries the row stride: a window has
 //            no padding to mask), and Wf holds one fragment stream of (d1 + d2) / 16 k-steps per 256-column pass
-enum class Stream { kWide, kRoot, kWindow };
+//   kRootAct kRoot with ReLU, and with a flex::DropMask as `drop` dropout too, on the accumulators between the chain and the store
+//            (flex_axw_gemm_bf16_root_act_launch, axw_bf16_act_kernels.hip)
+enum class Stream { kWide, kRoot, kWindow, kRootAct };
 
 // Out = L1 Wf[0 .. d1) + L2 Wf[d1 .. d1 + d2): Wf in fragment order (axw_bf16_pack_kernel), streamed through two LDS buffers of kSlab k-steps.
-template <int NT, int P, Stream kForm>  // 32-column tiles of Out, panels a wave
+// `drop` is a parameter pack so that the forms without dropout keep the kernel arguments, and with them the code, they had.
+template <int NT, int P, Stream kForm, class... Drop>  // 32-column tiles of Out, panels a wave; kRootAct: no Drop or one flex::DropMask
 __global__ __launch_bounds__(64 * kWaves) void axw_gemm_bf16_stream_kernel(const flex_bf16 *__restrict__ L1, int d1, const flex_bf16 *__restrict__ L2,
                                                                            int d2, const u32x4 *__restrict__ Wf, const flex_bf16 *__restrict__ Cin,
                                                                            const float *__restrict__ bias, flex_bf16 *__restrict__ Out, int n,
-                                                                           int c) {
-    extern __shared__ u32x4 sW[];  // [2 buffers][kSlab][NT][64] fragments of 8 bf16, then (kRoot) cp floats of bias
-    constexpr bool kOne = kForm == Stream::kWide, kWindow = kForm == Stream::kWindow, kInit = kForm == Stream::kRoot;
+                                                                           int c, Drop... drop) {
+    extern __shared__ u32x4 sW[];  // [2 buffers][kSlab][NT][64] fragments of 8 bf16, then (kRoot, kRootAct) cp floats of bias
+    constexpr bool kOne = kForm == Stream::kWide, kWindow = kForm == Stream::kWindow, kAct = kForm == Stream::kRootAct;
+    constexpr bool kInit = kForm == Stream::kRoot || kAct, kDrop = sizeof...(Drop) > 0;
+    static_assert(kAct || !kDrop, "only kRootAct takes a mask");
     constexpr int cp = 32 * NT, kStepFrags = NT * 64, kSlabFrags = kSlab * kStepFrags;
     float *sBias = reinterpret_cast<float *>(sW + 2 * kSlabFrags);
     const int tid = threadIdx.x, lane = tid & 63;
@@ -293,7 +298,33 @@ __global__ __launch_bounds__(64 * kWaves) void axw_gemm_bf16_stream_kernel(const
             const int panel = panel_of(round, p);
             if (panel >= n_panels) continue;  // wave-uniform: the round's panels past the end were multiplied as copies of the last
             const f32x16(&panel_acc)[NT] = acc[p];  // the macro has a loop variable p of its own
-            if constexpr (kWindow) {
+            if constexpr (kAct) {
+                // a = z > 0 ? z : (z is NaN ? z : +0), then keep(seed, row c + column) ? a cs : +0 -- a select, so a dropped inf or NaN is
+                // +0 -- on one tile's 16 accumulators at a time, just before the store rounds them: the hash of a whole panel ahead of the
+                // store would be 16 NT more live values.  The mask index is 64-bit: the row's, one value a lane, plus the element's
+                // compile-time column offset.  The rows that an overlapping last panel stores twice get the same bits twice.
+                const size_t row = static_cast<size_t>(panel_row(panel) + j);
+                flex_bf16 *dst = Out + row * cp + 16 * h;
+                [[maybe_unused]] const uint64_t idx = row * c + 4 * h;
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    f32x16 tile[1] = {acc[p][t]};
+#pragma unroll
+                    for (int reg = 0; reg < 16; ++reg) {
+                        const float z = tile[0][reg], a = z <= 0.f ? 0.f : z;
+                        if constexpr (kDrop) {
+                            const flex::DropMask dm = [](const flex::DropMask &m) { return m; }(drop...);
+                            const bool keep = flex::dropout_bits(dm.seed_lo, dm.seed_hi, idx + (32 * t + 8 * (reg >> 2) + (reg & 3))) < dm.thr;
+                            tile[0][reg] = keep ? a * dm.c : 0.f;
+                        } else {
+                            tile[0][reg] = a;
+                        }
+                    }
+                    flex_bf16 *tile_dst = dst + 32 * t;  // the macro has a t of its own
+                    const int tile_c = c - 32 * t;
+                    FLEX_AXW_BF16_STORE_PANEL(1, tile, tile_dst, tile_c, h)
+                }
+            } else if constexpr (kWindow) {
                 flex_bf16 *dst = Out + static_cast<size_t>(panel_row(panel) + j) * c + 16 * h;
                 FLEX_AXW_BF16_STORE_PANEL(NT, panel_acc, dst, cp, h)
             } else {

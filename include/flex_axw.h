@@ -205,6 +205,38 @@ int flex_axw_backward_bf16(flex_axw *h, const flex_bf16 *dX, const flex_bf16 *dW
  *   holds what tests/test_gpu_axw_bf16_root_backward.py measured against them. */
 int flex_axw_backward_root_bf16(flex_axw *h, const flex_bf16 *dX, const flex_bf16 *dW, const flex_bf16 *dR, const flex_bf16 *dOut,
                                 flex_bf16 *dGradX, flex_bf16 *dGradW, flex_bf16 *dGradR, float *dGradBias /* fp32 */, flex_stream_t stream);
+
+/* flex_axw_run_root_bf16 with ReLU and dropout fused into its last dense launch (axw_bf16_act_kernels.hip), on the same handles, with the
+ * same operands, orders, checks and order of launches; the hidden layer of a GNN in one call.  With z the fp32 value that
+ * flex_axw_run_root_bf16 rounds (same chain, same order, same Cin + bias start), cs = 1.0f / (1.0f - drop_p) computed in fp32 on the host
+ * and idx = row * c + col (64-bit; c the true width, not flex_axw_ld_bf16(c)):
+ *     a   = z > 0 ? z : (z != z ? z : +0)            NaN stays NaN; -0 and negatives give +0 bits
+ *     Out = keep(seed, idx) ? rn_bf16(a * cs) : +0   ONE bf16 rounding; drop_p == 0: Out = rn_bf16(a), no hash evaluated
+ * Padding columns c .. flex_axw_ld_bf16(c)-1 are +0 bits.  Dropped entries are selected out, not multiplied by zero (the attention
+ * kernels' rule): a dropped inf or NaN gives +0.  keep is the function behind flex_dropout_mask (flex_spmm.h), its threshold rule
+ * included, bit for bit: flex_dropout_mask(seed, drop_p, 0, n * c, keep) is this call's mask, row-major [n x c].  With drop_p == 0, Out
+ * has the bits of flex_axw_run_root_bf16's with every entry whose sign bit is set and that is no NaN replaced by +0 (rounding is monotone
+ * and keeps the sign).  drop_p must be finite with 0 <= drop_p < 1, else FLEX_ERR_INVALID; nothing is enqueued by a refused call.  seed
+ * and drop_p travel as kernel arguments: a captured hipGraph replays the same mask.  No allocation, no host sync unless timed, no
+ * atomics: the same bits on every call.
+ * Accuracy (tests/axw_bf16_act_ref.py): with ref, E of flex_axw_run_root_bf16's statement for the same order (|z - ref| <= E before the
+ * last rounding), kept entries satisfy |Out - cs relu(ref)| <= bound_bf16(cs relu(ref), cs (1 + 2^-23) E + 2^-24 cs relu(|ref| + E)):
+ * ReLU is 1-Lipschitz, the product a * cs is one fp32 rounding, and the final bf16 rounding is applied to cs relu(ref).  Dropped entries
+ * and padding columns are +0 bits exactly.  DESIGN.md 3.32 holds what tests/test_gpu_axw_bf16_act.py measured. */
+int flex_axw_run_root_act_bf16(flex_axw *h, int order, const flex_bf16 *dX, const flex_bf16 *dW, const flex_bf16 *dR,
+                               const float *dBias /* c floats or NULL */, flex_bf16 *dOut, float drop_p, uint64_t seed, flex_stream_t stream,
+                               float *gemm_ms, float *spmm_ms);
+
+/* The backward of flex_axw_run_root_act_bf16, on a handle that also has FLEX_AXW_BACKWARD.  It is defined on the STORED output dFwdOut of
+ * that call, which the caller passes back -- no mask and no seed: Out > 0 exactly where the unit was active and kept --
+ *     dZ = Out > 0 ? rn_bf16(fp32(dOut) * cs) : +0      a float compare: NaN, +0 and -0 in Out give +0; columns >= c: +0
+ * with cs as above, written by one streaming pass into dWork, a caller-owned n x flex_axw_ld_bf16(c) flex_bf16 buffer, 16-byte aligned
+ * and distinct from dOut and dFwdOut (equal pointers: FLEX_ERR_INVALID; NULL dFwdOut or dWork and a drop_p outside [0, 1) too).
+ * Everything else is flex_axw_backward_root_bf16 evaluated on dZ in place of dOut, bit for bit: its outputs, NULL-output rules, checks
+ * and accuracy statements.  dOut's padding columns are read by the pass and ignored: dZ's are +0 whatever they hold. */
+int flex_axw_backward_root_act_bf16(flex_axw *h, const flex_bf16 *dX, const flex_bf16 *dW, const flex_bf16 *dR, const flex_bf16 *dFwdOut,
+                                    const flex_bf16 *dOut, flex_bf16 *dWork, flex_bf16 *dGradX, flex_bf16 *dGradW, flex_bf16 *dGradR,
+                                    float *dGradBias /* fp32 */, float drop_p, flex_stream_t stream);
 int flex_axw_destroy(flex_axw *h);
 /* last rocBLAS status seen (rocblas_status), for FLEX_ERR_UNSUPPORTED returns caused by rocBLAS */
 int flex_axw_last_blas_status(void);

@@ -21,7 +21,11 @@
                                  this process: medians of event times of the whole calls, of the new call without dW / dR and without dX
                                  (the stages are their differences, as for --bf16-backward), the one-pass dW / dR / db launcher against two
                                  launches of the one-product dW launcher, and the dense stages against their streaming floors
-                                 (2 n cp + n dim) 2 bytes / HBM_RATE."""
+                                 (2 n cp + n dim) 2 bytes / HBM_RATE.
+    probe_axw.py --bf16-root-act the hidden layer dropout(relu(A X W + X R + b)): run_root, torch.relu and F.dropout(p = 0.5), and the backward
+                                 of root_layer through those torch ops, against flex_axw_run_root_act_bf16 and flex_axw_backward_root_act_bf16
+                                 at p = 0 and p = 0.5, alternated in this process on flickr (128, 128) and reddit (128, 128), (608, 128): medians of
+                                 event times of the whole calls."""
 import os
 import sys
 
@@ -249,6 +253,55 @@ def root_backward_table(shapes=ROOT_BACKWARD):
                   f"{dx:.1f} | {dw:.1f} | {m['two']:.1f} | {m['dual']:.1f} | {m['dual'] / m['two']:.2f} | {dx / fx:.2f} | {dw / fw:.2f} |", flush=True)
             h.destroy()
 
+
+ROOT_ACT = {"flickr": ((128, 128),), "reddit": ((128, 128), (608, 128))}
+
+
+def root_act_table(shapes=ROOT_ACT):
+    import torch.nn.functional as F
+
+    def whole(f):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        f()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e3
+
+    print("| graph | dim | c | forward: run_root + relu + dropout | act p = 0 | act p = 0.5 | p = 0 / parent | p = 0.5 / parent | "
+          "backward: through torch's ops | act p = 0 | act p = 0.5 | p = 0 / parent | p = 0.5 / parent |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|---|")
+    for name in shapes:
+        a = flex_amd.synth_graph(name)
+        for dim, c in shapes[name]:
+            h = axw.Axw(a, dim, c, bf16=True, backward=True, root=True)
+            X = (torch.rand((a.n, dim), device="cuda") * 2 - 1).bfloat16()
+            W, R = ((torch.rand((dim, c), device="cuda") - 0.5).bfloat16() for _ in range(2))
+            bias = torch.rand(c, device="cuda") - 0.5
+            d = torch.zeros((a.n, h.ld), dtype=torch.bfloat16, device="cuda")
+            d[:, :c] = (torch.rand((a.n, c), device="cuda") * 2 - 1).bfloat16()
+            leaves = [t.clone().requires_grad_() for t in (X, W, R, bias)]
+            loss = F.dropout(torch.relu(h.root_layer(*leaves)), 0.5)  # the parent's graph, kept for its backward
+            out = {p: h.run_root_act(X, W, R, bias, p, 7) for p in (0.0, 0.5)}
+            runs = {"f": lambda: F.dropout(torch.relu(h.run_root(X, W, R, bias)), 0.5),
+                    "f0": lambda: h.run_root_act(X, W, R, bias, 0.0, 7), "f5": lambda: h.run_root_act(X, W, R, bias, 0.5, 7),
+                    "b": lambda: torch.autograd.grad(loss, leaves, d[:, :c], retain_graph=True),
+                    "b0": lambda: h.backward_root_act(d, out[0.0], X, W, R, 0.0), "b5": lambda: h.backward_root_act(d, out[0.5], X, W, R, 0.5)}
+            t = {k: [] for k in runs}
+            for i in range(REPS + 5):  # alternated; the first five of each are warm-up
+                for k, f in runs.items():
+                    us = whole(f)
+                    if i >= 5:
+                        t[k].append(us)
+            m = {k: float(np.median(v)) for k, v in t.items()}
+            print(f"| {name} | {dim} | {c} | {m['f']:.1f} | {m['f0']:.1f} | {m['f5']:.1f} | {m['f0'] / m['f']:.2f} | {m['f5'] / m['f']:.2f} | "
+                  f"{m['b']:.1f} | {m['b0']:.1f} | {m['b5']:.1f} | {m['b0'] / m['b']:.2f} | {m['b5'] / m['b']:.2f} |", flush=True)
+            h.destroy()
+
+
+if "--bf16-root-act" in sys.argv[1:]:
+    root_act_table()
+    sys.exit(0)
 
 if "--bf16-root-backward" in sys.argv[1:]:
     root_backward_table()
