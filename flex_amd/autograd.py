@@ -22,10 +22,40 @@ probabilities after the softmax in the same launches (flex_dropout_gatv2_attenti
 mask.  torch is imported lazily, as in binding.py."""
 from __future__ import annotations
 
+import functools
+
 from . import binding
 
 
-def _function():
+def _gat_shaped(name, doc, forward, backward, tensors, heads_at, dropout):
+    """The autograd Function `name` of a GAT-shaped attention: forward(ctx, *tensors, op, slope) -- followed by drop_p and seed where
+    `dropout` -- runs the Plan method `forward` on the first `tensors` arguments and keeps them, alpha [nnz, heads] (only when a
+    gradient is needed) and the scalars; backward runs the Plan method `backward` for the gradients that are needed and returns None
+    for op and every scalar.  heads_at = (argument, dimension): where heads is read, el.shape[1] or att.shape[0].  The dropout calls
+    take alpha as probs=, the others as p=."""
+    import torch
+
+    def fwd(ctx, *args):
+        ts, (op, *scalars) = [t.contiguous() for t in args[:tensors]], args[tensors:]
+        heads = ts[heads_at[0]].shape[heads_at[1]]
+        p = torch.zeros((op.nnz, heads), dtype=torch.float32, device=ts[-1].device) if any(ctx.needs_input_grad[:tensors]) else None
+        out = getattr(op.plan, forward)(*ts, *scalars, **{"probs" if dropout else "p": p})
+        ctx.op, ctx.scalars = op, scalars
+        ctx.save_for_backward(*ts, p)
+        return out
+
+    def bwd(ctx, grad_out):
+        *ts, p = ctx.saved_tensors
+        grads = getattr(ctx.op.plan, backward)(*ts, p, grad_out.contiguous(), *ctx.scalars, want=tuple(ctx.needs_input_grad[:tensors]))
+        return (*grads, None, *(None for _ in ctx.scalars))
+
+    return type(torch.autograd.Function)(name, (torch.autograd.Function,), {
+        "__doc__": doc, "__module__": __name__, "forward": staticmethod(fwd), "backward": staticmethod(bwd)})
+
+
+@functools.cache
+def functions():
+    """(_SpMM, _AxwLayer, _SpMMValues, _Sddmm, _EdgeSoftmax, _FusedAttention, _FusedAttentionHeads, _FusedGatAttention, _FusedAttentionBf16, _FusedAttentionBias): the autograd Functions, built at first use (torch is imported then)."""
     import torch
 
     class _SpMM(torch.autograd.Function):
@@ -176,26 +206,13 @@ def _function():
             grads = ctx.op.plan.attention_backward(Q, K, V, p, grad_out.contiguous(), ctx.scale, want=tuple(ctx.needs_input_grad[:3]), heads=ctx.heads)
             return (*grads, None, None, None)
 
-    class _FusedGatAttention(torch.autograd.Function):
+    _FusedGatAttention = _gat_shaped(
+        "_FusedGatAttention",
         """Out = A(alpha) V per head, alpha = softmax over each row of A of leaky_relu(el[row, h] + er[col, h], slope): flex_gat_attention
         in one launch, alpha [nnz, heads] kept only when a gradient is needed; backward: the one call flex_gat_attention_backward (two
         launches) for the gradients that are needed, in el, er and V.  It sets no plan's values.  Only on an operator made with
-        fused_attention=True and fused_backward=True."""
-
-        @staticmethod
-        def forward(ctx, el, er, V, op, slope):
-            el, er, V = el.contiguous(), er.contiguous(), V.contiguous()
-            p = torch.zeros((op.nnz, el.shape[1]), dtype=torch.float32, device=V.device) if any(ctx.needs_input_grad[:3]) else None
-            out = op.plan.gat_attention(el, er, V, slope, p=p)
-            ctx.op, ctx.slope = op, slope
-            ctx.save_for_backward(el, er, V, p)
-            return out
-
-        @staticmethod
-        def backward(ctx, grad_out):
-            el, er, V, p = ctx.saved_tensors
-            grads = ctx.op.plan.gat_attention_backward(el, er, V, p, grad_out.contiguous(), ctx.slope, want=tuple(ctx.needs_input_grad[:3]))
-            return (*grads, None, None)
+        fused_attention=True and fused_backward=True.""",
+        "gat_attention", "gat_attention_backward", 3, (0, 1), False)
 
     class _FusedAttentionBf16(torch.autograd.Function):
         """_FusedAttentionHeads on torch.bfloat16 Q, K, V (heads = 1 included): flex_attention_bf16 in one launch, scores, softmax and sums
@@ -245,18 +262,9 @@ def _function():
             _FusedAttentionBias)
 
 
-_cache = None
-
-
-def functions():
-    """(_SpMM, _AxwLayer, _SpMMValues, _Sddmm, _EdgeSoftmax, _FusedAttention, _FusedAttentionHeads, _FusedGatAttention, _FusedAttentionBf16, _FusedAttentionBias): the autograd Functions, built at first use (torch is imported then)."""
-    global _cache
-    if _cache is None:
-        _cache = _function()
-    return _cache
-
-
-def _axw_root_function():
+@functools.cache
+def axw_root_functions():
+    """(_AxwRootLayer,): built at first use, as functions()."""
     import torch
 
     class _AxwRootLayer(torch.autograd.Function):
@@ -283,18 +291,9 @@ def _axw_root_function():
     return (_AxwRootLayer,)
 
 
-_axw_root_cache = None
-
-
-def axw_root_functions():
-    """(_AxwRootLayer,): built at first use, as functions()."""
-    global _axw_root_cache
-    if _axw_root_cache is None:
-        _axw_root_cache = _axw_root_function()
-    return _axw_root_cache
-
-
-def _axw_root_act_function():
+@functools.cache
+def axw_root_act_functions():
+    """(_AxwRootActLayer,): built at first use, as functions()."""
     import torch
 
     class _AxwRootActLayer(torch.autograd.Function):
@@ -323,18 +322,9 @@ def _axw_root_act_function():
     return (_AxwRootActLayer,)
 
 
-_axw_root_act_cache = None
-
-
-def axw_root_act_functions():
-    """(_AxwRootActLayer,): built at first use, as functions()."""
-    global _axw_root_act_cache
-    if _axw_root_act_cache is None:
-        _axw_root_act_cache = _axw_root_act_function()
-    return _axw_root_act_cache
-
-
-def _dropout_function():
+@functools.cache
+def dropout_functions():
+    """(_FusedAttentionDropout,): the autograd Functions of the attention dropout, built at first use; functions() keeps its ten."""
     import torch
 
     class _FusedAttentionDropout(torch.autograd.Function):
@@ -367,235 +357,75 @@ def _dropout_function():
     return (_FusedAttentionDropout,)
 
 
-_dropout_cache = None
-
-
-def dropout_functions():
-    """(_FusedAttentionDropout,): the autograd Functions of the attention dropout, built at first use; functions() keeps its ten."""
-    global _dropout_cache
-    if _dropout_cache is None:
-        _dropout_cache = _dropout_function()
-    return _dropout_cache
-
-
-def _gat_dropout_function():
-    import torch
-
-    class _FusedGatAttentionDropout(torch.autograd.Function):
+@functools.cache
+def gat_dropout_functions():
+    """(_FusedGatAttentionDropout,): the autograd Function of the GAT attention dropout, built at first use; functions() keeps its ten and
+    dropout_functions() its one."""
+    return (_gat_shaped(
+        "_FusedGatAttentionDropout",
         """_FusedGatAttention with the probabilities dropped after the softmax (probability drop_p, the kept ones scaled by
         1 / (1 - drop_p)): flex_gat_attention_dropout in one launch, the UNDROPPED alpha [nnz, heads] kept only when a gradient is
         needed; backward: the one call flex_gat_attention_dropout_backward (two launches) under the same drop_p and seed, which
         recomputes the mask from the seed -- no mask is stored.  Only on an operator made with fused_attention=True and
-        fused_backward=True."""
-
-        @staticmethod
-        def forward(ctx, el, er, V, op, slope, drop_p, seed):
-            el, er, V = el.contiguous(), er.contiguous(), V.contiguous()
-            p = torch.zeros((op.nnz, el.shape[1]), dtype=torch.float32, device=V.device) if any(ctx.needs_input_grad[:3]) else None
-            out = op.plan.gat_attention_dropout(el, er, V, slope, drop_p, seed, probs=p)
-            ctx.op, ctx.slope, ctx.drop_p, ctx.seed = op, slope, drop_p, seed
-            ctx.save_for_backward(el, er, V, p)
-            return out
-
-        @staticmethod
-        def backward(ctx, grad_out):
-            el, er, V, p = ctx.saved_tensors
-            grads = ctx.op.plan.gat_attention_dropout_backward(el, er, V, p, grad_out.contiguous(), ctx.slope, ctx.drop_p, ctx.seed,
-                                                               want=tuple(ctx.needs_input_grad[:3]))
-            return (*grads, None, None, None, None)
-
-    return (_FusedGatAttentionDropout,)
+        fused_backward=True.""",
+        "gat_attention_dropout", "gat_attention_dropout_backward", 3, (0, 1), True),)
 
 
-_gat_dropout_cache = None
-
-
-def gat_dropout_functions():
-    """(_FusedGatAttentionDropout,): the autograd Function of the GAT attention dropout, built at first use; functions() keeps its ten and
-    dropout_functions() its one."""
-    global _gat_dropout_cache
-    if _gat_dropout_cache is None:
-        _gat_dropout_cache = _gat_dropout_function()
-    return _gat_dropout_cache
-
-
-def _gat_edge_function():
-    import torch
-
-    class _FusedGatEdgeAttention(torch.autograd.Function):
+@functools.cache
+def gat_edge_functions():
+    """(_FusedGatEdgeAttention,): the autograd Function of the GAT attention with a per-edge score term, built at first use, as
+    gat_dropout_functions(); functions(), gat_dropout_functions() and gat_bf16_functions() keep their counts."""
+    return (_gat_shaped(
+        "_FusedGatEdgeAttention",
         """_FusedGatAttention / _FusedGatAttentionDropout with a per-edge term ee [nnz, heads] inside the LeakyReLU:
         flex_edge_gat_attention in one launch (drop_p = 0: no mask), the UNDROPPED alpha kept only when a gradient is needed;
         backward: the one call flex_edge_gat_attention_backward (two launches) under the same drop_p and seed.  Keeps (el, er, ee, V, P)
         and the seed, never a mask; the gradient in ee is the call's work array, so nothing nnz-sized is allocated beside it.  Only on
-        an operator made with fused_attention=True and fused_backward=True."""
-
-        @staticmethod
-        def forward(ctx, el, er, ee, V, op, slope, drop_p, seed):
-            el, er, ee, V = el.contiguous(), er.contiguous(), ee.contiguous(), V.contiguous()
-            p = torch.zeros((op.nnz, el.shape[1]), dtype=torch.float32, device=V.device) if any(ctx.needs_input_grad[:4]) else None
-            out = op.plan.gat_edge_attention(el, er, ee, V, slope, drop_p, seed, probs=p)
-            ctx.op, ctx.slope, ctx.drop_p, ctx.seed = op, slope, drop_p, seed
-            ctx.save_for_backward(el, er, ee, V, p)
-            return out
-
-        @staticmethod
-        def backward(ctx, grad_out):
-            el, er, ee, V, p = ctx.saved_tensors
-            grads = ctx.op.plan.gat_edge_attention_backward(el, er, ee, V, p, grad_out.contiguous(), ctx.slope, ctx.drop_p, ctx.seed,
-                                                            want=tuple(ctx.needs_input_grad[:4]))
-            return (*grads, None, None, None, None)
-
-    return (_FusedGatEdgeAttention,)
+        an operator made with fused_attention=True and fused_backward=True.""",
+        "gat_edge_attention", "gat_edge_attention_backward", 4, (0, 1), True),)
 
 
-_gat_edge_cache = None
-
-
-def gat_edge_functions():
-    """(_FusedGatEdgeAttention,): the autograd Function of the GAT attention with a per-edge score term, built at first use, as
-    gat_dropout_functions(); functions(), gat_dropout_functions() and gat_bf16_functions() keep their counts."""
-    global _gat_edge_cache
-    if _gat_edge_cache is None:
-        _gat_edge_cache = _gat_edge_function()
-    return _gat_edge_cache
-
-
-def _gatv2_function():
-    import torch
-
-    class _FusedGatv2Attention(torch.autograd.Function):
+@functools.cache
+def gatv2_functions():
+    """(_FusedGatv2Attention,): the autograd Function of the GATv2 attention, built at first use, as gat_dropout_functions()."""
+    return (_gat_shaped(
+        "_FusedGatv2Attention",
         """Out = A(alpha) xs per head, alpha = softmax over each row of A of <att[h], leaky_relu(xt[row] + xs[col], slope)> over the head's
         columns: flex_gatv2_attention in one launch, alpha [nnz, heads] kept only when a gradient is needed; backward: the one call
         flex_gatv2_attention_backward (up to three launches) for the gradients that are needed, in xt, xs and att.  xt may be xs: torch
-        sums the two gradients.  It sets no plan's values.  Only on an operator made with fused_attention=True and fused_backward=True."""
-
-        @staticmethod
-        def forward(ctx, xt, xs, att, op, slope):
-            xt, xs, att = xt.contiguous(), xs.contiguous(), att.contiguous()
-            p = torch.zeros((op.nnz, att.shape[0]), dtype=torch.float32, device=xs.device) if any(ctx.needs_input_grad[:3]) else None
-            out = op.plan.gatv2_attention(xt, xs, att, slope, p=p)
-            ctx.op, ctx.slope = op, slope
-            ctx.save_for_backward(xt, xs, att, p)
-            return out
-
-        @staticmethod
-        def backward(ctx, grad_out):
-            xt, xs, att, p = ctx.saved_tensors
-            grads = ctx.op.plan.gatv2_attention_backward(xt, xs, att, p, grad_out.contiguous(), ctx.slope, want=tuple(ctx.needs_input_grad[:3]))
-            return (*grads, None, None)
-
-    return (_FusedGatv2Attention,)
+        sums the two gradients.  It sets no plan's values.  Only on an operator made with fused_attention=True and fused_backward=True.""",
+        "gatv2_attention", "gatv2_attention_backward", 3, (2, 0), False),)
 
 
-_gatv2_cache = None
-
-
-def gatv2_functions():
-    """(_FusedGatv2Attention,): the autograd Function of the GATv2 attention, built at first use, as gat_dropout_functions()."""
-    global _gatv2_cache
-    if _gatv2_cache is None:
-        _gatv2_cache = _gatv2_function()
-    return _gatv2_cache
-
-
-def _gatv2_dropout_function():
-    import torch
-
-    class _FusedGatv2AttentionDropout(torch.autograd.Function):
+@functools.cache
+def gatv2_dropout_functions():
+    """(_FusedGatv2AttentionDropout,): the autograd Function of the GATv2 attention dropout, built at first use; gatv2_functions() keeps
+    its one."""
+    return (_gat_shaped(
+        "_FusedGatv2AttentionDropout",
         """_FusedGatv2Attention with the probabilities dropped after the softmax (probability drop_p, the kept ones scaled by
         1 / (1 - drop_p)): flex_dropout_gatv2_attention in one launch, the UNDROPPED alpha [nnz, heads] kept only when a gradient is
         needed; backward: the one call flex_dropout_gatv2_attention_backward (up to three launches) under the same drop_p and seed, which
         recomputes the mask from the seed -- no mask is stored.  Only on an operator made with fused_attention=True and
-        fused_backward=True."""
-
-        @staticmethod
-        def forward(ctx, xt, xs, att, op, slope, drop_p, seed):
-            xt, xs, att = xt.contiguous(), xs.contiguous(), att.contiguous()
-            p = torch.zeros((op.nnz, att.shape[0]), dtype=torch.float32, device=xs.device) if any(ctx.needs_input_grad[:3]) else None
-            out = op.plan.gatv2_attention_dropout(xt, xs, att, slope, drop_p, seed, probs=p)
-            ctx.op, ctx.slope, ctx.drop_p, ctx.seed = op, slope, drop_p, seed
-            ctx.save_for_backward(xt, xs, att, p)
-            return out
-
-        @staticmethod
-        def backward(ctx, grad_out):
-            xt, xs, att, p = ctx.saved_tensors
-            grads = ctx.op.plan.gatv2_attention_dropout_backward(xt, xs, att, p, grad_out.contiguous(), ctx.slope, ctx.drop_p, ctx.seed,
-                                                                 want=tuple(ctx.needs_input_grad[:3]))
-            return (*grads, None, None, None, None)
-
-    return (_FusedGatv2AttentionDropout,)
+        fused_backward=True.""",
+        "gatv2_attention_dropout", "gatv2_attention_dropout_backward", 3, (2, 0), True),)
 
 
-_gatv2_dropout_cache = None
-
-
-def gatv2_dropout_functions():
-    """(_FusedGatv2AttentionDropout,): the autograd Function of the GATv2 attention dropout, built at first use; gatv2_functions() keeps
-    its one."""
-    global _gatv2_dropout_cache
-    if _gatv2_dropout_cache is None:
-        _gatv2_dropout_cache = _gatv2_dropout_function()
-    return _gatv2_dropout_cache
-
-
-def _gat_bf16_function():
-    import torch
-
-    class _FusedGatAttentionBf16(torch.autograd.Function):
-        """_FusedGatAttention on torch.bfloat16 V (el and er float32): flex_gat_attention_bf16 in one launch, scores, softmax and sums in
-        float32, alpha [nnz, heads] kept in float32 only when a gradient is needed; backward: the one call
-        flex_gat_attention_bf16_backward (two launches) for the gradients that are needed -- grad V in bfloat16, grad el and grad er in
-        float32.  Only on an operator made with fused_attention=True and fused_backward=True."""
-
-        @staticmethod
-        def forward(ctx, el, er, V, op, slope):
-            el, er, V = el.contiguous(), er.contiguous(), V.contiguous()
-            p = torch.zeros((op.nnz, el.shape[1]), dtype=torch.float32, device=V.device) if any(ctx.needs_input_grad[:3]) else None
-            out = op.plan.gat_attention_bf16(el, er, V, slope, p=p)
-            ctx.op, ctx.slope = op, slope
-            ctx.save_for_backward(el, er, V, p)
-            return out
-
-        @staticmethod
-        def backward(ctx, grad_out):
-            el, er, V, p = ctx.saved_tensors
-            grads = ctx.op.plan.gat_attention_bf16_backward(el, er, V, p, grad_out.contiguous(), ctx.slope, want=tuple(ctx.needs_input_grad[:3]))
-            return (*grads, None, None)
-
-    class _FusedGatAttentionBf16Dropout(torch.autograd.Function):
-        """_FusedGatAttentionBf16 with the probabilities dropped after the softmax: flex_gat_attention_bf16_dropout and its backward under
-        the same drop_p and seed, which recomputes the mask from the seed -- no mask is stored."""
-
-        @staticmethod
-        def forward(ctx, el, er, V, op, slope, drop_p, seed):
-            el, er, V = el.contiguous(), er.contiguous(), V.contiguous()
-            p = torch.zeros((op.nnz, el.shape[1]), dtype=torch.float32, device=V.device) if any(ctx.needs_input_grad[:3]) else None
-            out = op.plan.gat_attention_bf16_dropout(el, er, V, slope, drop_p, seed, probs=p)
-            ctx.op, ctx.slope, ctx.drop_p, ctx.seed = op, slope, drop_p, seed
-            ctx.save_for_backward(el, er, V, p)
-            return out
-
-        @staticmethod
-        def backward(ctx, grad_out):
-            el, er, V, p = ctx.saved_tensors
-            grads = ctx.op.plan.gat_attention_bf16_dropout_backward(el, er, V, p, grad_out.contiguous(), ctx.slope, ctx.drop_p, ctx.seed,
-                                                                    want=tuple(ctx.needs_input_grad[:3]))
-            return (*grads, None, None, None, None)
-
-    return (_FusedGatAttentionBf16, _FusedGatAttentionBf16Dropout)
-
-
-_gat_bf16_cache = None
-
-
+@functools.cache
 def gat_bf16_functions():
     """(_FusedGatAttentionBf16, _FusedGatAttentionBf16Dropout): the autograd Functions of the GAT attention on bfloat16 V, built at first
     use; functions() keeps its ten, dropout_functions() and gat_dropout_functions() their one each."""
-    global _gat_bf16_cache
-    if _gat_bf16_cache is None:
-        _gat_bf16_cache = _gat_bf16_function()
-    return _gat_bf16_cache
+    return (_gat_shaped(
+        "_FusedGatAttentionBf16",
+        """_FusedGatAttention on torch.bfloat16 V (el and er float32): flex_gat_attention_bf16 in one launch, scores, softmax and sums in
+        float32, alpha [nnz, heads] kept in float32 only when a gradient is needed; backward: the one call
+        flex_gat_attention_bf16_backward (two launches) for the gradients that are needed -- grad V in bfloat16, grad el and grad er in
+        float32.  Only on an operator made with fused_attention=True and fused_backward=True.""",
+        "gat_attention_bf16", "gat_attention_bf16_backward", 3, (0, 1), False), _gat_shaped(
+        "_FusedGatAttentionBf16Dropout",
+        """_FusedGatAttentionBf16 with the probabilities dropped after the softmax: flex_gat_attention_bf16_dropout and its backward under
+        the same drop_p and seed, which recomputes the mask from the seed -- no mask is stored.""",
+        "gat_attention_bf16_dropout", "gat_attention_bf16_dropout_backward", 3, (0, 1), True))
 
 
 class SparseOperator:

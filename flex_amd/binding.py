@@ -504,6 +504,43 @@ def order_deg(a: HostCsr, descending: bool = True) -> np.ndarray:
     return rank[: a.m]
 
 
+def _ptr(t):
+    """data_ptr() of a tensor; None stays None (an operand or output the call does without)."""
+    return None if t is None else t.data_ptr()
+
+
+def _stream(t):
+    """torch's current stream on the device of tensor t, as the raw hipStream_t."""
+    import torch
+    return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def _rows(dtype, k, *operands):
+    """The row operands of an attention call: each (tensor, rows) is a contiguous cuda tensor [rows, k] of `dtype`."""
+    for t, rows in operands:
+        assert t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == (rows, k), f"{dtype} cuda [rows, k]"
+
+
+def _output(t, shape, dtype, device, nnz):
+    """An output of an attention call: the given tensor, checked, or a new one.  Every element is written, except by a plan without
+    entries (nnz == 0), which launches nothing: a new output of that plan starts at zero."""
+    import torch
+    if t is None:
+        t = (torch.empty if nnz else torch.zeros)(shape, dtype=dtype, device=device)
+    assert t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape), f"{dtype} cuda {list(shape)}"
+    return t
+
+
+def _wanted(want, given, specs, device, nnz):
+    """The gradients of a backward call, one per (shape, dtype) of specs: _output() of the given one where `want` asks for it, else None."""
+    return [_output(t, shape, dtype, device, nnz) if wanted else None for wanted, t, (shape, dtype) in zip(want, given, specs)]
+
+
+def _dropout(p, seed):
+    """(p, seed) as every dropout call takes them: the seed is 64 bits, a negative one its two's complement."""
+    return p, int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
 class Plan:
     """flex_plan handle (≙ Mat after csr2_DiagTiling + alpha_transfer)."""
 
@@ -706,13 +743,20 @@ class Plan:
         _check(lib().flex_plan_attention_info(self._h, C.byref(i)), "flex_plan_attention_info")
         return {f: getattr(i, f) for f, _ in _AttentionInfo._fields_}
 
-    def attention_ptr(self, dQ_ptr: int, dK_ptr: int, dV_ptr: int, scale: float, dOut_ptr: int, dP_ptr: int | None = None, stream: int = 0,
-                      heads: int | None = None):
-        """heads=None: flex_attention.  heads=H (1 included): flex_attention_heads with that H; dP is then nnz x H floats, entry-major."""
-        if heads is None:
-            _check(_values_fn("flex_attention")(self._h, dQ_ptr, dK_ptr, dV_ptr, scale, dOut_ptr, dP_ptr, stream), "flex_attention")
-        else:
-            _check(_values_fn("flex_attention_heads")(self._h, heads, dQ_ptr, dK_ptr, dV_ptr, scale, dOut_ptr, dP_ptr, stream), "flex_attention_heads")
+    def attention_backward_info(self) -> dict:
+        """flex_plan_attention_backward_info: the schedule of attention_backward()'s column launch (columns, entries, items, groups, columns by class)."""
+        i = _AttentionBackwardInfo()
+        _check(lib().flex_plan_attention_backward_info(self._h, C.byref(i)), "flex_plan_attention_backward_info")
+        return {f: getattr(i, f) for f, _ in _AttentionBackwardInfo._fields_}
+
+    # The steps every torch-level attention wrapper below is made of: _rows, _output, _wanted, _ptr, _stream and _dropout above, the
+    # edge-array checks and the per-family operand checks here.  One forward and one backward body per operand family (Q/K/V, el/er/V,
+    # xt/xs/att) takes a dtype, the _ptr method to call and the scalars in the call's order; a wrapper whose call has a part of its own
+    # (the [nnz] arrays of attention(), gEe as the work array) is written from the steps directly.
+
+    def _call(self, name, *args):
+        """The library call `name` on this plan (looked up at first use, _values_fn); FlexError unless it returns 0."""
+        _check(_values_fn(name)(self._h, *args), name)
 
     def _head_edge_arrays(self, heads, *ts):
         """The edge arrays of the per-head calls (heads, bf16, bias and GAT): float32 cuda [nnz, heads], heads = 1 included."""
@@ -726,6 +770,73 @@ class Plan:
         else:
             self._head_edge_arrays(heads, *ts)
 
+    def _work(self, work, heads, device):
+        """The work array of a backward call, float32 [nnz, heads]: the given one, else a new one."""
+        import torch
+        return torch.empty((self.src_nnz, heads), dtype=torch.float32, device=device) if work is None else work
+
+    def _bias(self, bias, heads):
+        """A per-edge bias as the calls take it, float32 cuda [nnz, heads]: [nnz] is taken as [nnz, 1] when heads == 1; None (no bias) stays."""
+        if bias is None:
+            return None
+        if heads == 1 and bias.dim() == 1:
+            bias = bias.unsqueeze(1)
+        self._head_edge_arrays(heads, bias)
+        return bias
+
+    def _node_scalars(self, i, el, er):
+        """heads, from el [m, H] and er [n, H]: one float32 per node and head.  i: the plan's info()."""
+        import torch
+        assert el.dim() == 2 and el.shape[1] >= 1, "el is [m, heads]"
+        heads = int(el.shape[1])
+        for t, rows in ((el, i["m"]), (er, i["n"])):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (rows, heads), "float32 cuda [rows, heads]"
+        return heads
+
+    def _gatv2_operands(self, i, xt, xs, att):
+        """heads, from att [H, d]; xt [m, k] like C, xs [n, k] like B: float32 cuda tensors, k = H d.  i: the plan's info()."""
+        import torch
+        assert att.dim() == 2 and att.shape[0] >= 1 and att.shape[0] * att.shape[1] == i["k"], "att is [heads, k / heads]"
+        for t, shape in ((xt, (i["m"], i["k"])), (xs, (i["n"], i["k"])), (att, tuple(att.shape))):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape, "float32 cuda, xt [m, k], xs [n, k]"
+        return int(att.shape[0])
+
+    # ---- Q, K, V: attention, heads, bf16, bias, dropout
+
+    def _qkv_forward(self, dtype, run, Q, K, V, edge, scalars, heads, out, p):
+        """The forward of the per-head Q/K/V calls: run(Q, K, V, *edge, *scalars, out, p, stream, heads=heads) on rows of `dtype`.  edge:
+        the per-edge operands that precede the scalars -- nothing, or one bias (None: the call runs without it)."""
+        i = self.info()
+        _rows(dtype, i["k"], (Q, i["m"]), (K, i["n"]), (V, i["n"]))
+        edge = [self._bias(b, heads) for b in edge]
+        out = _output(out, (i["m"], i["k"]), dtype, Q.device, i["nnz"])
+        if p is not None:
+            self._head_edge_arrays(heads, p)
+        run(_ptr(Q), _ptr(K), _ptr(V), *map(_ptr, edge), *scalars, _ptr(out), _ptr(p), _stream(Q), heads=heads)
+        return out
+
+    def _qkv_backward(self, dtype, run, Q, K, V, p, grad_out, scalars, heads, grads, work, want):
+        """The backward of the per-head Q/K/V calls: run(Q, K, V, p, grad_out, *scalars, *grads, work, stream, heads=heads).  grads: (gQ, gK,
+        gV) and, where the call has one, gBias [nnz, heads] (float32), which a shorter `want` does not ask for."""
+        import torch
+        i = self.info()
+        _rows(dtype, i["k"], (Q, i["m"]), (K, i["n"]), (V, i["n"]), (grad_out, i["m"]))
+        work = self._work(work, heads, Q.device)
+        self._head_edge_arrays(heads, p, work)
+        mk, nk = ((i["m"], i["k"]), dtype), ((i["n"], i["k"]), dtype)
+        want = tuple(want) + (False,) * (len(grads) - len(want))
+        outs = _wanted(want, grads, (mk, nk, nk, ((self.src_nnz, heads), torch.float32)), Q.device, i["nnz"])
+        run(*map(_ptr, (Q, K, V, p, grad_out)), *scalars, *map(_ptr, outs), _ptr(work), _stream(Q), heads=heads)
+        return tuple(outs)
+
+    def attention_ptr(self, dQ_ptr: int, dK_ptr: int, dV_ptr: int, scale: float, dOut_ptr: int, dP_ptr: int | None = None, stream: int = 0,
+                      heads: int | None = None):
+        """heads=None: flex_attention.  heads=H (1 included): flex_attention_heads with that H; dP is then nnz x H floats, entry-major."""
+        if heads is None:
+            self._call("flex_attention", dQ_ptr, dK_ptr, dV_ptr, scale, dOut_ptr, dP_ptr, stream)
+        else:
+            self._call("flex_attention_heads", heads, dQ_ptr, dK_ptr, dV_ptr, scale, dOut_ptr, dP_ptr, stream)
+
     def attention(self, Q, K, V, scale: float, out=None, p=None, heads: int = 1):
         """flex_attention: out [m, k] = sum over each row's entries of alpha V[col], alpha = the softmax over the row of
         scale * <Q[row], K[col]>, in one launch.  Q: [m, k] like C; K, V: [n, k] like B; float32 cuda tensors.  p (optional): a float32
@@ -734,33 +845,22 @@ class Plan:
         p is then [a.nnz, heads]."""
         import torch
         i = self.info()
-        for t, rows in ((Q, i["m"]), (K, i["n"]), (V, i["n"])):
-            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (rows, i["k"])
-        if out is None:  # every row is written, except by a plan without entries, which launches nothing
-            out = (torch.empty if i["nnz"] else torch.zeros)((i["m"], i["k"]), dtype=torch.float32, device=Q.device)
-        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (i["m"], i["k"])
+        _rows(torch.float32, i["k"], (Q, i["m"]), (K, i["n"]), (V, i["n"]))
+        out = _output(out, (i["m"], i["k"]), torch.float32, Q.device, i["nnz"])
         if p is not None:
             self._edge_arrays(heads, p)
-        self.attention_ptr(Q.data_ptr(), K.data_ptr(), V.data_ptr(), scale, out.data_ptr(), None if p is None else p.data_ptr(),
-                           torch.cuda.current_stream(Q.device).cuda_stream, heads=None if heads == 1 else heads)
+        self.attention_ptr(_ptr(Q), _ptr(K), _ptr(V), scale, _ptr(out), _ptr(p), _stream(Q), heads=None if heads == 1 else heads)
         return out
-
-    def attention_backward_info(self) -> dict:
-        """flex_plan_attention_backward_info: the schedule of attention_backward()'s column launch (columns, entries, items, groups, columns by class)."""
-        i = _AttentionBackwardInfo()
-        _check(lib().flex_plan_attention_backward_info(self._h, C.byref(i)), "flex_plan_attention_backward_info")
-        return {f: getattr(i, f) for f, _ in _AttentionBackwardInfo._fields_}
 
     def attention_backward_ptr(self, dQ_ptr: int, dK_ptr: int, dV_ptr: int, dP_ptr: int, dGradOut_ptr: int, scale: float, dGradQ_ptr: int | None,
                                dGradK_ptr: int | None, dGradV_ptr: int | None, dWork_ptr: int, stream: int = 0, heads: int | None = None):
         """heads=None: flex_attention_backward.  heads=H (1 included): flex_attention_heads_backward with that H; dP and dWork are then
         nnz x H floats, entry-major."""
         if heads is None:
-            _check(_values_fn("flex_attention_backward")(self._h, dQ_ptr, dK_ptr, dV_ptr, dP_ptr, dGradOut_ptr, scale, dGradQ_ptr, dGradK_ptr, dGradV_ptr,
-                                                         dWork_ptr, stream), "flex_attention_backward")
+            self._call("flex_attention_backward", dQ_ptr, dK_ptr, dV_ptr, dP_ptr, dGradOut_ptr, scale, dGradQ_ptr, dGradK_ptr, dGradV_ptr, dWork_ptr, stream)
         else:
-            _check(_values_fn("flex_attention_heads_backward")(self._h, heads, dQ_ptr, dK_ptr, dV_ptr, dP_ptr, dGradOut_ptr, scale, dGradQ_ptr, dGradK_ptr,
-                                                               dGradV_ptr, dWork_ptr, stream), "flex_attention_heads_backward")
+            self._call("flex_attention_heads_backward", heads, dQ_ptr, dK_ptr, dV_ptr, dP_ptr, dGradOut_ptr, scale, dGradQ_ptr, dGradK_ptr, dGradV_ptr,
+                       dWork_ptr, stream)
 
     def attention_backward(self, Q, K, V, p, grad_out, scale: float, grad_q=None, grad_k=None, grad_v=None, work=None, want=(True, True, True),
                            heads: int = 1):
@@ -770,50 +870,33 @@ class Plan:
         attention(..., heads=heads); p and work are [a.nnz, heads]."""
         import torch
         i = self.info()
-        for t, rows in ((Q, i["m"]), (K, i["n"]), (V, i["n"]), (grad_out, i["m"])):
-            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (rows, i["k"])
+        _rows(torch.float32, i["k"], (Q, i["m"]), (K, i["n"]), (V, i["n"]), (grad_out, i["m"]))
         if work is None:
             work = torch.empty(self.src_nnz if heads == 1 else (self.src_nnz, heads), dtype=torch.float32, device=Q.device)
         self._edge_arrays(heads, p, work)
-        outs = []
-        for wanted, t, rows in zip(want, (grad_q, grad_k, grad_v), (i["m"], i["n"], i["n"])):
-            if wanted and t is None:  # every row is written, except by a plan without entries, which launches nothing
-                t = (torch.empty if i["nnz"] else torch.zeros)((rows, i["k"]), dtype=torch.float32, device=Q.device)
-            if wanted:
-                assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (rows, i["k"])
-            outs.append(t if wanted else None)
-        self.attention_backward_ptr(Q.data_ptr(), K.data_ptr(), V.data_ptr(), p.data_ptr(), grad_out.data_ptr(), scale,
-                                    *(None if t is None else t.data_ptr() for t in outs), work.data_ptr(),
-                                    torch.cuda.current_stream(Q.device).cuda_stream, heads=None if heads == 1 else heads)
+        mk, nk = ((i["m"], i["k"]), torch.float32), ((i["n"], i["k"]), torch.float32)
+        outs = _wanted(want, (grad_q, grad_k, grad_v), (mk, nk, nk), Q.device, i["nnz"])
+        self.attention_backward_ptr(*map(_ptr, (Q, K, V, p, grad_out)), scale, *map(_ptr, outs), _ptr(work), _stream(Q),
+                                    heads=None if heads == 1 else heads)
         return tuple(outs)
 
     def attention_bf16_ptr(self, dQ_ptr: int, dK_ptr: int, dV_ptr: int, scale: float, dOut_ptr: int, dP_ptr: int | None = None, stream: int = 0,
                            heads: int = 1):
         """flex_attention_bf16: Q, K, V and Out are bf16 rows, dP (optional) is nnz x H floats, entry-major."""
-        _check(_values_fn("flex_attention_bf16")(self._h, heads, dQ_ptr, dK_ptr, dV_ptr, scale, dOut_ptr, dP_ptr, stream), "flex_attention_bf16")
+        self._call("flex_attention_bf16", heads, dQ_ptr, dK_ptr, dV_ptr, scale, dOut_ptr, dP_ptr, stream)
 
     def attention_bf16(self, Q, K, V, scale: float, heads: int = 1, out=None, p=None):
         """flex_attention_bf16: attention(..., heads=heads) on torch.bfloat16 cuda tensors Q [m, k], K, V [n, k]; scores, softmax and sums
         in float32, out [m, k] bfloat16 rounded once at its store.  p (optional): a float32 cuda tensor [a.nnz, heads] that receives alpha,
         not rounded.  heads = 1 runs here too: k / heads is a power of two in 4 .. 256 for every heads."""
         import torch
-        i = self.info()
-        for t, rows in ((Q, i["m"]), (K, i["n"]), (V, i["n"])):
-            assert t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous() and tuple(t.shape) == (rows, i["k"]), "bfloat16 cuda [rows, k]"
-        if out is None:  # every row is written, except by a plan without entries, which launches nothing
-            out = (torch.empty if i["nnz"] else torch.zeros)((i["m"], i["k"]), dtype=torch.bfloat16, device=Q.device)
-        assert out.is_cuda and out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (i["m"], i["k"])
-        if p is not None:
-            self._head_edge_arrays(heads, p)
-        self.attention_bf16_ptr(Q.data_ptr(), K.data_ptr(), V.data_ptr(), scale, out.data_ptr(), None if p is None else p.data_ptr(),
-                                torch.cuda.current_stream(Q.device).cuda_stream, heads=heads)
-        return out
+        return self._qkv_forward(torch.bfloat16, self.attention_bf16_ptr, Q, K, V, (), (scale,), heads, out, p)
 
     def attention_bf16_backward_ptr(self, dQ_ptr: int, dK_ptr: int, dV_ptr: int, dP_ptr: int, dGradOut_ptr: int, scale: float, dGradQ_ptr: int | None,
                                     dGradK_ptr: int | None, dGradV_ptr: int | None, dWork_ptr: int, stream: int = 0, heads: int = 1):
         """flex_attention_bf16_backward: the row operands and the gradients are bf16 rows, dP and dWork nnz x H floats, entry-major."""
-        _check(_values_fn("flex_attention_bf16_backward")(self._h, heads, dQ_ptr, dK_ptr, dV_ptr, dP_ptr, dGradOut_ptr, scale, dGradQ_ptr, dGradK_ptr,
-                                                          dGradV_ptr, dWork_ptr, stream), "flex_attention_bf16_backward")
+        self._call("flex_attention_bf16_backward", heads, dQ_ptr, dK_ptr, dV_ptr, dP_ptr, dGradOut_ptr, scale, dGradQ_ptr, dGradK_ptr, dGradV_ptr,
+                   dWork_ptr, stream)
 
     def attention_bf16_backward(self, Q, K, V, p, grad_out, scale: float, heads: int = 1, grad_q=None, grad_k=None, grad_v=None, work=None,
                                 want=(True, True, True)):
@@ -821,86 +904,32 @@ class Plan:
         (float32) and grad_out [m, k] (bfloat16), in two launches; an output that `want` does not ask for is None and is not computed.
         work (optional): a float32 cuda tensor [a.nnz, heads], not p, that receives the gradient in the scores whenever gQ or gK is wanted."""
         import torch
-        i = self.info()
-        for t, rows in ((Q, i["m"]), (K, i["n"]), (V, i["n"]), (grad_out, i["m"])):
-            assert t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous() and tuple(t.shape) == (rows, i["k"]), "bfloat16 cuda [rows, k]"
-        if work is None:
-            work = torch.empty((self.src_nnz, heads), dtype=torch.float32, device=Q.device)
-        self._head_edge_arrays(heads, p, work)
-        outs = []
-        for wanted, t, rows in zip(want, (grad_q, grad_k, grad_v), (i["m"], i["n"], i["n"])):
-            if wanted and t is None:  # every row is written, except by a plan without entries, which launches nothing
-                t = (torch.empty if i["nnz"] else torch.zeros)((rows, i["k"]), dtype=torch.bfloat16, device=Q.device)
-            if wanted:
-                assert t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous() and tuple(t.shape) == (rows, i["k"])
-            outs.append(t if wanted else None)
-        self.attention_bf16_backward_ptr(Q.data_ptr(), K.data_ptr(), V.data_ptr(), p.data_ptr(), grad_out.data_ptr(), scale,
-                                         *(None if t is None else t.data_ptr() for t in outs), work.data_ptr(),
-                                         torch.cuda.current_stream(Q.device).cuda_stream, heads=heads)
-        return tuple(outs)
+        return self._qkv_backward(torch.bfloat16, self.attention_bf16_backward_ptr, Q, K, V, p, grad_out, (scale,), heads,
+                                  (grad_q, grad_k, grad_v), work, want)
 
     def attention_bias_ptr(self, dQ_ptr: int, dK_ptr: int, dV_ptr: int, dBias_ptr: int, scale: float, dOut_ptr: int, dP_ptr: int | None = None,
                            stream: int = 0, heads: int = 1):
         """flex_attention_bias: fp32 rows; dBias and dP (optional) are nnz x H floats, entry-major."""
-        _check(_values_fn("flex_attention_bias")(self._h, heads, dQ_ptr, dK_ptr, dV_ptr, dBias_ptr, scale, dOut_ptr, dP_ptr, stream), "flex_attention_bias")
+        self._call("flex_attention_bias", heads, dQ_ptr, dK_ptr, dV_ptr, dBias_ptr, scale, dOut_ptr, dP_ptr, stream)
 
     def attention_bf16_bias_ptr(self, dQ_ptr: int, dK_ptr: int, dV_ptr: int, dBias_ptr: int, scale: float, dOut_ptr: int, dP_ptr: int | None = None,
                                 stream: int = 0, heads: int = 1):
         """flex_attention_bf16_bias: Q, K, V and Out are bf16 rows; dBias and dP (optional) are nnz x H floats, entry-major."""
-        _check(_values_fn("flex_attention_bf16_bias")(self._h, heads, dQ_ptr, dK_ptr, dV_ptr, dBias_ptr, scale, dOut_ptr, dP_ptr, stream),
-               "flex_attention_bf16_bias")
+        self._call("flex_attention_bf16_bias", heads, dQ_ptr, dK_ptr, dV_ptr, dBias_ptr, scale, dOut_ptr, dP_ptr, stream)
 
     def attention_bias_backward_ptr(self, dQ_ptr: int, dK_ptr: int, dV_ptr: int, dP_ptr: int, dGradOut_ptr: int, scale: float, dGradQ_ptr: int | None,
                                     dGradK_ptr: int | None, dGradV_ptr: int | None, dGradBias_ptr: int | None, dWork_ptr: int, stream: int = 0,
                                     heads: int = 1):
         """flex_attention_bias_backward: fp32 rows; dP, dGradBias and dWork are nnz x H floats, entry-major."""
-        _check(_values_fn("flex_attention_bias_backward")(self._h, heads, dQ_ptr, dK_ptr, dV_ptr, dP_ptr, dGradOut_ptr, scale, dGradQ_ptr, dGradK_ptr,
-                                                          dGradV_ptr, dGradBias_ptr, dWork_ptr, stream), "flex_attention_bias_backward")
+        self._call("flex_attention_bias_backward", heads, dQ_ptr, dK_ptr, dV_ptr, dP_ptr, dGradOut_ptr, scale, dGradQ_ptr, dGradK_ptr, dGradV_ptr,
+                   dGradBias_ptr, dWork_ptr, stream)
 
     def attention_bf16_bias_backward_ptr(self, dQ_ptr: int, dK_ptr: int, dV_ptr: int, dP_ptr: int, dGradOut_ptr: int, scale: float,
                                          dGradQ_ptr: int | None, dGradK_ptr: int | None, dGradV_ptr: int | None, dGradBias_ptr: int | None,
                                          dWork_ptr: int, stream: int = 0, heads: int = 1):
         """flex_attention_bf16_bias_backward: the row operands and gQ, gK, gV are bf16 rows; dP, dGradBias and dWork nnz x H floats."""
-        _check(_values_fn("flex_attention_bf16_bias_backward")(self._h, heads, dQ_ptr, dK_ptr, dV_ptr, dP_ptr, dGradOut_ptr, scale, dGradQ_ptr,
-                                                               dGradK_ptr, dGradV_ptr, dGradBias_ptr, dWork_ptr, stream),
-               "flex_attention_bf16_bias_backward")
-
-    def _attention_bias(self, dtype, run, Q, K, V, bias, scale, heads, out, p):
-        import torch
-        i = self.info()
-        for t, rows in ((Q, i["m"]), (K, i["n"]), (V, i["n"])):
-            assert t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == (rows, i["k"]), f"{dtype} cuda [rows, k]"
-        if heads == 1 and bias.dim() == 1:
-            bias = bias.unsqueeze(1)
-        self._head_edge_arrays(heads, bias)
-        if out is None:  # every row is written, except by a plan without entries, which launches nothing
-            out = (torch.empty if i["nnz"] else torch.zeros)((i["m"], i["k"]), dtype=dtype, device=Q.device)
-        assert out.is_cuda and out.dtype == dtype and out.is_contiguous() and tuple(out.shape) == (i["m"], i["k"])
-        if p is not None:
-            self._head_edge_arrays(heads, p)
-        run(Q.data_ptr(), K.data_ptr(), V.data_ptr(), bias.data_ptr(), scale, out.data_ptr(), None if p is None else p.data_ptr(),
-            torch.cuda.current_stream(Q.device).cuda_stream, heads=heads)
-        return out
-
-    def _attention_bias_backward(self, dtype, run, Q, K, V, p, grad_out, scale, heads, grads, work, want):
-        import torch
-        i = self.info()
-        for t, rows in ((Q, i["m"]), (K, i["n"]), (V, i["n"]), (grad_out, i["m"])):
-            assert t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == (rows, i["k"]), f"{dtype} cuda [rows, k]"
-        if work is None:
-            work = torch.empty((self.src_nnz, heads), dtype=torch.float32, device=Q.device)
-        self._head_edge_arrays(heads, p, work)
-        shapes = ((i["m"], i["k"]), (i["n"], i["k"]), (i["n"], i["k"]), (self.src_nnz, heads))
-        outs = []
-        for wanted, t, shape, dt in zip(want, grads, shapes, (dtype, dtype, dtype, torch.float32)):
-            if wanted and t is None:  # every element is written, except by a plan without entries, which launches nothing
-                t = (torch.empty if i["nnz"] else torch.zeros)(shape, dtype=dt, device=Q.device)
-            if wanted:
-                assert t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape
-            outs.append(t if wanted else None)
-        run(Q.data_ptr(), K.data_ptr(), V.data_ptr(), p.data_ptr(), grad_out.data_ptr(), scale, *(None if t is None else t.data_ptr() for t in outs),
-            work.data_ptr(), torch.cuda.current_stream(Q.device).cuda_stream, heads=heads)
-        return tuple(outs)
+        self._call("flex_attention_bf16_bias_backward", heads, dQ_ptr, dK_ptr, dV_ptr, dP_ptr, dGradOut_ptr, scale, dGradQ_ptr, dGradK_ptr,
+                   dGradV_ptr, dGradBias_ptr, dWork_ptr, stream)
 
     def attention_bias(self, Q, K, V, bias, scale: float, heads: int = 1, out=None, p=None):
         """flex_attention_bias: attention(..., heads=heads) with bias [a.nnz, heads] (float32 cuda, a's CSR order; [a.nnz] is taken as
@@ -908,13 +937,13 @@ class Plan:
         Q [m, k], K, V [n, k] float32; p (optional): a float32 cuda tensor [a.nnz, heads] that receives alpha.  heads = 1 runs here too:
         k / heads is a power of two in 4 .. 256 for every heads."""
         import torch
-        return self._attention_bias(torch.float32, self.attention_bias_ptr, Q, K, V, bias, scale, heads, out, p)
+        return self._qkv_forward(torch.float32, self.attention_bias_ptr, Q, K, V, (bias,), (scale,), heads, out, p)
 
     def attention_bf16_bias(self, Q, K, V, bias, scale: float, heads: int = 1, out=None, p=None):
         """flex_attention_bf16_bias: attention_bias() on torch.bfloat16 Q, K, V; out is bfloat16, rounded once at its store; bias and p
         stay float32 and are not rounded."""
         import torch
-        return self._attention_bias(torch.bfloat16, self.attention_bf16_bias_ptr, Q, K, V, bias, scale, heads, out, p)
+        return self._qkv_forward(torch.bfloat16, self.attention_bf16_bias_ptr, Q, K, V, (bias,), (scale,), heads, out, p)
 
     def attention_bias_backward(self, Q, K, V, p, grad_out, scale: float, heads: int = 1, grad_q=None, grad_k=None, grad_v=None, grad_bias=None,
                                 work=None, want=(True, True, True, True)):
@@ -923,62 +952,41 @@ class Plan:
         and is not computed.  work (optional): a float32 cuda tensor [a.nnz, heads], neither p nor grad_bias, that receives the gradient
         in the scores whenever gQ, gK or gBias is wanted."""
         import torch
-        return self._attention_bias_backward(torch.float32, self.attention_bias_backward_ptr, Q, K, V, p, grad_out, scale, heads,
-                                             (grad_q, grad_k, grad_v, grad_bias), work, want)
+        return self._qkv_backward(torch.float32, self.attention_bias_backward_ptr, Q, K, V, p, grad_out, (scale,), heads,
+                                  (grad_q, grad_k, grad_v, grad_bias), work, want)
 
     def attention_bf16_bias_backward(self, Q, K, V, p, grad_out, scale: float, heads: int = 1, grad_q=None, grad_k=None, grad_v=None,
                                      grad_bias=None, work=None, want=(True, True, True, True)):
         """flex_attention_bf16_bias_backward: attention_bias_backward() on torch.bfloat16 Q, K, V and grad_out; gQ, gK and gV are bfloat16,
         p, gBias and work float32."""
         import torch
-        return self._attention_bias_backward(torch.bfloat16, self.attention_bf16_bias_backward_ptr, Q, K, V, p, grad_out, scale, heads,
-                                             (grad_q, grad_k, grad_v, grad_bias), work, want)
+        return self._qkv_backward(torch.bfloat16, self.attention_bf16_bias_backward_ptr, Q, K, V, p, grad_out, (scale,), heads,
+                                  (grad_q, grad_k, grad_v, grad_bias), work, want)
 
     def attention_dropout_ptr(self, dQ_ptr: int, dK_ptr: int, dV_ptr: int, dBias_ptr: int | None, scale: float, p: float, seed: int, dOut_ptr: int,
                               dP_ptr: int | None = None, stream: int = 0, heads: int = 1):
         """flex_attention_dropout: fp32 rows; dBias (None: no bias) and dP (optional) are nnz x H floats, entry-major; dP receives the
         UNDROPPED probabilities.  p: the dropout probability, 0 <= p < 1; seed: 64 bits."""
-        _check(_values_fn("flex_attention_dropout")(self._h, heads, dQ_ptr, dK_ptr, dV_ptr, dBias_ptr, scale, p, seed, dOut_ptr, dP_ptr, stream),
-               "flex_attention_dropout")
+        self._call("flex_attention_dropout", heads, dQ_ptr, dK_ptr, dV_ptr, dBias_ptr, scale, p, seed, dOut_ptr, dP_ptr, stream)
 
     def attention_bf16_dropout_ptr(self, dQ_ptr: int, dK_ptr: int, dV_ptr: int, dBias_ptr: int | None, scale: float, p: float, seed: int,
                                    dOut_ptr: int, dP_ptr: int | None = None, stream: int = 0, heads: int = 1):
         """flex_attention_bf16_dropout: attention_dropout_ptr on bf16 rows (Q, K, V, Out)."""
-        _check(_values_fn("flex_attention_bf16_dropout")(self._h, heads, dQ_ptr, dK_ptr, dV_ptr, dBias_ptr, scale, p, seed, dOut_ptr, dP_ptr, stream),
-               "flex_attention_bf16_dropout")
+        self._call("flex_attention_bf16_dropout", heads, dQ_ptr, dK_ptr, dV_ptr, dBias_ptr, scale, p, seed, dOut_ptr, dP_ptr, stream)
 
     def attention_dropout_backward_ptr(self, dQ_ptr: int, dK_ptr: int, dV_ptr: int, dP_ptr: int, dGradOut_ptr: int, scale: float, p: float, seed: int,
                                        dGradQ_ptr: int | None, dGradK_ptr: int | None, dGradV_ptr: int | None, dGradBias_ptr: int | None,
                                        dWork_ptr: int, stream: int = 0, heads: int = 1):
         """flex_attention_dropout_backward: fp32 rows; dP, dGradBias (None: not wanted) and dWork are nnz x H floats, entry-major."""
-        _check(_values_fn("flex_attention_dropout_backward")(self._h, heads, dQ_ptr, dK_ptr, dV_ptr, dP_ptr, dGradOut_ptr, scale, p, seed, dGradQ_ptr,
-                                                             dGradK_ptr, dGradV_ptr, dGradBias_ptr, dWork_ptr, stream), "flex_attention_dropout_backward")
+        self._call("flex_attention_dropout_backward", heads, dQ_ptr, dK_ptr, dV_ptr, dP_ptr, dGradOut_ptr, scale, p, seed, dGradQ_ptr, dGradK_ptr,
+                   dGradV_ptr, dGradBias_ptr, dWork_ptr, stream)
 
     def attention_bf16_dropout_backward_ptr(self, dQ_ptr: int, dK_ptr: int, dV_ptr: int, dP_ptr: int, dGradOut_ptr: int, scale: float, p: float,
                                             seed: int, dGradQ_ptr: int | None, dGradK_ptr: int | None, dGradV_ptr: int | None,
                                             dGradBias_ptr: int | None, dWork_ptr: int, stream: int = 0, heads: int = 1):
         """flex_attention_bf16_dropout_backward: attention_dropout_backward_ptr on bf16 rows (Q, K, V, g, gQ, gK, gV)."""
-        _check(_values_fn("flex_attention_bf16_dropout_backward")(self._h, heads, dQ_ptr, dK_ptr, dV_ptr, dP_ptr, dGradOut_ptr, scale, p, seed,
-                                                                  dGradQ_ptr, dGradK_ptr, dGradV_ptr, dGradBias_ptr, dWork_ptr, stream),
-               "flex_attention_bf16_dropout_backward")
-
-    def _attention_dropout(self, dtype, run, Q, K, V, scale, p, seed, heads, bias, out, probs):
-        import torch
-        i = self.info()
-        for t, rows in ((Q, i["m"]), (K, i["n"]), (V, i["n"])):
-            assert t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == (rows, i["k"]), f"{dtype} cuda [rows, k]"
-        if bias is not None:
-            if heads == 1 and bias.dim() == 1:
-                bias = bias.unsqueeze(1)
-            self._head_edge_arrays(heads, bias)
-        if out is None:  # every row is written, except by a plan without entries, which launches nothing
-            out = (torch.empty if i["nnz"] else torch.zeros)((i["m"], i["k"]), dtype=dtype, device=Q.device)
-        assert out.is_cuda and out.dtype == dtype and out.is_contiguous() and tuple(out.shape) == (i["m"], i["k"])
-        if probs is not None:
-            self._head_edge_arrays(heads, probs)
-        run(Q.data_ptr(), K.data_ptr(), V.data_ptr(), None if bias is None else bias.data_ptr(), scale, p, seed, out.data_ptr(),
-            None if probs is None else probs.data_ptr(), torch.cuda.current_stream(Q.device).cuda_stream, heads=heads)
-        return out
+        self._call("flex_attention_bf16_dropout_backward", heads, dQ_ptr, dK_ptr, dV_ptr, dP_ptr, dGradOut_ptr, scale, p, seed, dGradQ_ptr,
+                   dGradK_ptr, dGradV_ptr, dGradBias_ptr, dWork_ptr, stream)
 
     def attention_dropout(self, Q, K, V, scale: float, p: float, seed: int, heads: int = 1, bias=None, out=None, probs=None):
         """flex_attention_dropout: attention(..., heads=heads) (attention_bias() with bias [a.nnz, heads]) whose probabilities are dropped
@@ -987,20 +995,13 @@ class Plan:
         receives the UNDROPPED alpha, which attention_dropout_backward() starts from.  heads = 1 runs here too: k / heads is a power of
         two in 4 .. 256 for every heads.  p = 0 is the undropped call, bit for bit."""
         import torch
-        return self._attention_dropout(torch.float32, self.attention_dropout_ptr, Q, K, V, scale, p, seed, heads, bias, out, probs)
+        return self._qkv_forward(torch.float32, self.attention_dropout_ptr, Q, K, V, (bias,), (scale, *_dropout(p, seed)), heads, out, probs)
 
     def attention_bf16_dropout(self, Q, K, V, scale: float, p: float, seed: int, heads: int = 1, bias=None, out=None, probs=None):
         """flex_attention_bf16_dropout: attention_dropout() on torch.bfloat16 Q, K, V; out is bfloat16, rounded once at its store; bias and
         probs stay float32."""
         import torch
-        return self._attention_dropout(torch.bfloat16, self.attention_bf16_dropout_ptr, Q, K, V, scale, p, seed, heads, bias, out, probs)
-
-    def _attention_dropout_backward(self, dtype, run, Q, K, V, probs, grad_out, scale, p, seed, heads, grads, work, want):
-        import torch
-        if len(want) == 3:
-            want = (*want, False)
-        return self._attention_bias_backward(dtype, lambda q, k, v, pr, g, sc, *rest, heads: run(q, k, v, pr, g, sc, p, seed, *rest, heads=heads),
-                                             Q, K, V, probs, grad_out, scale, heads, grads, work, want)
+        return self._qkv_forward(torch.bfloat16, self.attention_bf16_dropout_ptr, Q, K, V, (bias,), (scale, *_dropout(p, seed)), heads, out, probs)
 
     def attention_dropout_backward(self, Q, K, V, probs, grad_out, scale: float, p: float, seed: int, heads: int = 1, grad_q=None, grad_k=None,
                                    grad_v=None, grad_bias=None, work=None, want=(True, True, True, False)):
@@ -1009,31 +1010,50 @@ class Plan:
         None and is not computed (gBias: only where the forward had a bias).  work (optional): a float32 cuda tensor [a.nnz, heads],
         neither probs nor grad_bias, that receives the gradient in the scores whenever gQ, gK or gBias is wanted."""
         import torch
-        return self._attention_dropout_backward(torch.float32, self.attention_dropout_backward_ptr, Q, K, V, probs, grad_out, scale, p, seed, heads,
-                                                (grad_q, grad_k, grad_v, grad_bias), work, want)
+        return self._qkv_backward(torch.float32, self.attention_dropout_backward_ptr, Q, K, V, probs, grad_out, (scale, *_dropout(p, seed)), heads,
+                                  (grad_q, grad_k, grad_v, grad_bias), work, want)
 
     def attention_bf16_dropout_backward(self, Q, K, V, probs, grad_out, scale: float, p: float, seed: int, heads: int = 1, grad_q=None,
                                         grad_k=None, grad_v=None, grad_bias=None, work=None, want=(True, True, True, False)):
         """flex_attention_bf16_dropout_backward: attention_dropout_backward() on torch.bfloat16 Q, K, V and grad_out; gQ, gK and gV are
         bfloat16, probs, gBias and work float32."""
         import torch
-        return self._attention_dropout_backward(torch.bfloat16, self.attention_bf16_dropout_backward_ptr, Q, K, V, probs, grad_out, scale, p, seed,
-                                                heads, (grad_q, grad_k, grad_v, grad_bias), work, want)
+        return self._qkv_backward(torch.bfloat16, self.attention_bf16_dropout_backward_ptr, Q, K, V, probs, grad_out, (scale, *_dropout(p, seed)),
+                                  heads, (grad_q, grad_k, grad_v, grad_bias), work, want)
+
+    # ---- el, er, V: GAT, dropout, bf16, edge
+
+    def _gat_forward(self, dtype, run, el, er, edge, V, scalars, out, p):
+        """The forward of the GAT calls: run(heads, el, er, *edge, V, *scalars, out, p, stream) on V and out rows of `dtype`; el, er, p and
+        the per-edge operands `edge` (nothing, or ee [nnz, heads]) are float32."""
+        i = self.info()
+        heads = self._node_scalars(i, el, er)
+        self._head_edge_arrays(heads, *edge)
+        _rows(dtype, i["k"], (V, i["n"]))
+        out = _output(out, (i["m"], i["k"]), dtype, V.device, i["nnz"])
+        if p is not None:
+            self._head_edge_arrays(heads, p)
+        run(heads, _ptr(el), _ptr(er), *map(_ptr, edge), _ptr(V), *scalars, _ptr(out), _ptr(p), _stream(V))
+        return out
+
+    def _gat_backward(self, dtype, run, el, er, V, p, grad_out, scalars, grads, work, want):
+        """The backward of the GAT calls without an edge term: run(heads, el, er, V, p, grad_out, *scalars, gEl, gEr, gV, work, stream);
+        V, grad_out and gV are rows of `dtype`; el, er, gEl, gEr, p and work float32."""
+        import torch
+        i = self.info()
+        heads = self._node_scalars(i, el, er)
+        _rows(dtype, i["k"], (V, i["n"]), (grad_out, i["m"]))
+        work = self._work(work, heads, V.device)
+        self._head_edge_arrays(heads, p, work)
+        specs = (((i["m"], heads), torch.float32), ((i["n"], heads), torch.float32), ((i["n"], i["k"]), dtype))
+        outs = _wanted(want, grads, specs, V.device, i["nnz"])
+        run(heads, *map(_ptr, (el, er, V, p, grad_out)), *scalars, *map(_ptr, outs), _ptr(work), _stream(V))
+        return tuple(outs)
 
     def gat_attention_ptr(self, heads: int, dEl_ptr: int, dEr_ptr: int, dV_ptr: int, slope: float, dOut_ptr: int, dP_ptr: int | None = None,
                           stream: int = 0):
         """flex_gat_attention; dEl is rows x H floats, dEr n x H, dP (optional) nnz x H, entry-major."""
-        _check(_values_fn("flex_gat_attention")(self._h, heads, dEl_ptr, dEr_ptr, dV_ptr, slope, dOut_ptr, dP_ptr, stream), "flex_gat_attention")
-
-    def _node_scalars(self, el, er):
-        """heads, from el [m, H] and er [n, H]: one float32 per node and head."""
-        import torch
-        i = self.info()
-        assert el.dim() == 2 and el.shape[1] >= 1, "el is [m, heads]"
-        heads = int(el.shape[1])
-        for t, rows in ((el, i["m"]), (er, i["n"])):
-            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (rows, heads), "float32 cuda [rows, heads]"
-        return heads
+        self._call("flex_gat_attention", heads, dEl_ptr, dEr_ptr, dV_ptr, slope, dOut_ptr, dP_ptr, stream)
 
     def gat_attention(self, el, er, V, slope: float = 0.2, out=None, p=None):
         """flex_gat_attention: out [m, k] = sum over each row's entries of alpha V[col] per head, alpha = the softmax over the row of
@@ -1041,23 +1061,13 @@ class Plan:
         V: [n, k] like B; float32 cuda tensors.  p (optional): a float32 cuda tensor [a.nnz, H] that receives alpha in a's CSR order
         for the plan's rows (entries of other shards keep what it held)."""
         import torch
-        i = self.info()
-        heads = self._node_scalars(el, er)
-        assert V.is_cuda and V.dtype == torch.float32 and V.is_contiguous() and tuple(V.shape) == (i["n"], i["k"])
-        if out is None:  # every row is written, except by a plan without entries, which launches nothing
-            out = (torch.empty if i["nnz"] else torch.zeros)((i["m"], i["k"]), dtype=torch.float32, device=V.device)
-        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (i["m"], i["k"])
-        if p is not None:
-            self._head_edge_arrays(heads, p)
-        self.gat_attention_ptr(heads, el.data_ptr(), er.data_ptr(), V.data_ptr(), slope, out.data_ptr(), None if p is None else p.data_ptr(),
-                               torch.cuda.current_stream(V.device).cuda_stream)
-        return out
+        return self._gat_forward(torch.float32, self.gat_attention_ptr, el, er, (), V, (slope,), out, p)
 
     def gat_attention_backward_ptr(self, heads: int, dEl_ptr: int, dEr_ptr: int, dV_ptr: int, dP_ptr: int, dGradOut_ptr: int, slope: float,
                                    dGradEl_ptr: int | None, dGradEr_ptr: int | None, dGradV_ptr: int | None, dWork_ptr: int, stream: int = 0):
         """flex_gat_attention_backward; dP and dWork are nnz x H floats, entry-major."""
-        _check(_values_fn("flex_gat_attention_backward")(self._h, heads, dEl_ptr, dEr_ptr, dV_ptr, dP_ptr, dGradOut_ptr, slope, dGradEl_ptr, dGradEr_ptr,
-                                                         dGradV_ptr, dWork_ptr, stream), "flex_gat_attention_backward")
+        self._call("flex_gat_attention_backward", heads, dEl_ptr, dEr_ptr, dV_ptr, dP_ptr, dGradOut_ptr, slope, dGradEl_ptr, dGradEr_ptr, dGradV_ptr,
+                   dWork_ptr, stream)
 
     def gat_attention_backward(self, el, er, V, p, grad_out, slope: float = 0.2, grad_el=None, grad_er=None, grad_v=None, work=None,
                                want=(True, True, True)):
@@ -1065,192 +1075,27 @@ class Plan:
         [m, k], in two launches; an output that `want` does not ask for is None and is not computed.  work (optional): a float32 cuda
         tensor [a.nnz, H], not p, that receives the gradient in el + er per entry whenever gEl or gEr is wanted."""
         import torch
-        i = self.info()
-        heads = self._node_scalars(el, er)
-        for t, rows in ((V, i["n"]), (grad_out, i["m"])):
-            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (rows, i["k"])
-        if work is None:
-            work = torch.empty((self.src_nnz, heads), dtype=torch.float32, device=V.device)
-        self._head_edge_arrays(heads, p, work)
-        outs = []
-        for wanted, t, shape in zip(want, (grad_el, grad_er, grad_v), ((i["m"], heads), (i["n"], heads), (i["n"], i["k"]))):
-            if wanted and t is None:  # every row is written, except by a plan without entries, which launches nothing
-                t = (torch.empty if i["nnz"] else torch.zeros)(shape, dtype=torch.float32, device=V.device)
-            if wanted:
-                assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape
-            outs.append(t if wanted else None)
-        self.gat_attention_backward_ptr(heads, el.data_ptr(), er.data_ptr(), V.data_ptr(), p.data_ptr(), grad_out.data_ptr(), slope,
-                                        *(None if t is None else t.data_ptr() for t in outs), work.data_ptr(),
-                                        torch.cuda.current_stream(V.device).cuda_stream)
-        return tuple(outs)
-
-    def gatv2_attention_ptr(self, heads: int, dXt_ptr: int, dXs_ptr: int, dAtt_ptr: int, slope: float, dOut_ptr: int, dP_ptr: int | None = None,
-                            stream: int = 0):
-        """flex_gatv2_attention; dXt is rows x k floats (stride ldc), dXs n x k (stride ldb), dAtt k, dP (optional) nnz x H, entry-major."""
-        _check(_values_fn("flex_gatv2_attention")(self._h, heads, dXt_ptr, dXs_ptr, dAtt_ptr, slope, dOut_ptr, dP_ptr, stream), "flex_gatv2_attention")
-
-    def gatv2_attention_backward_ptr(self, heads: int, dXt_ptr: int, dXs_ptr: int, dAtt_ptr: int, dP_ptr: int, dGradOut_ptr: int, slope: float,
-                                     dGradXt_ptr: int | None, dGradXs_ptr: int | None, dGradAtt_ptr: int | None, dWork_ptr: int,
-                                     dAttWork_ptr: int | None = None, stream: int = 0):
-        """flex_gatv2_attention_backward; dP and dWork are nnz x H floats, entry-major; dAttWork holds gatv2_attention_work_size() floats
-        and is needed where dGradAtt is wanted."""
-        _check(_values_fn("flex_gatv2_attention_backward")(self._h, heads, dXt_ptr, dXs_ptr, dAtt_ptr, dP_ptr, dGradOut_ptr, slope, dGradXt_ptr,
-                                                           dGradXs_ptr, dGradAtt_ptr, dWork_ptr, dAttWork_ptr, stream), "flex_gatv2_attention_backward")
-
-    def gatv2_attention_work_size(self) -> int:
-        """flex_gatv2_attention_work_size: the floats of the dAttWork of gatv2_attention_backward_ptr (k per workgroup of its row launch)."""
-        n = C.c_uint64(0)
-        _check(_values_fn("flex_gatv2_attention_work_size")(self._h, C.byref(n)), "flex_gatv2_attention_work_size")
-        return int(n.value)
-
-    def _gatv2_operands(self, xt, xs, att):
-        """heads, from att [H, d]; xt [m, k] like C, xs [n, k] like B: float32 cuda tensors, k = H d."""
-        import torch
-        i = self.info()
-        assert att.dim() == 2 and att.shape[0] >= 1 and att.shape[0] * att.shape[1] == i["k"], "att is [heads, k / heads]"
-        for t, shape in ((xt, (i["m"], i["k"])), (xs, (i["n"], i["k"])), (att, tuple(att.shape))):
-            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape, "float32 cuda, xt [m, k], xs [n, k]"
-        return int(att.shape[0])
-
-    def gatv2_attention(self, xt, xs, att, slope: float = 0.2, out=None, p=None):
-        """flex_gatv2_attention: out [m, k] = sum over each row's entries of alpha xs[col] per head, alpha = the softmax over the row of
-        <att[h], leaky_relu(xt[row, head h] + xs[col, head h], slope)>, in one launch.  xt: [m, k], xs: [n, k], att: [H, k / H]; float32
-        cuda tensors; xt may be xs.  p (optional): a float32 cuda tensor [a.nnz, H] that receives alpha in a's CSR order for the plan's
-        rows (entries of other shards keep what it held)."""
-        import torch
-        i = self.info()
-        heads = self._gatv2_operands(xt, xs, att)
-        if out is None:  # every row is written, except by a plan without entries, which launches nothing
-            out = (torch.empty if i["nnz"] else torch.zeros)((i["m"], i["k"]), dtype=torch.float32, device=xs.device)
-        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (i["m"], i["k"])
-        if p is not None:
-            self._head_edge_arrays(heads, p)
-        self.gatv2_attention_ptr(heads, xt.data_ptr(), xs.data_ptr(), att.data_ptr(), slope, out.data_ptr(), None if p is None else p.data_ptr(),
-                                 torch.cuda.current_stream(xs.device).cuda_stream)
-        return out
-
-    def gatv2_attention_backward(self, xt, xs, att, p, grad_out, slope: float = 0.2, grad_xt=None, grad_xs=None, grad_att=None, work=None,
-                                 want=(True, True, True), att_work=None):
-        """flex_gatv2_attention_backward: (gXt [m, k], gXs [n, k], gAtt [H, k / H]) of gatv2_attention()'s out from its p [a.nnz, H] and
-        grad_out [m, k], in up to three launches; an output that `want` does not ask for is None and is not computed.  work (optional): a
-        float32 cuda tensor [a.nnz, H], not p, that receives dz = p (da - delta) per entry whenever a gradient is wanted.  att_work
-        (optional): float32 cuda, at least gatv2_attention_work_size() floats; it is allocated here when gAtt is wanted and it is not passed."""
-        import torch
-        i = self.info()
-        heads = self._gatv2_operands(xt, xs, att)
-        assert grad_out.is_cuda and grad_out.dtype == torch.float32 and grad_out.is_contiguous() and tuple(grad_out.shape) == (i["m"], i["k"])
-        if work is None:
-            work = torch.empty((self.src_nnz, heads), dtype=torch.float32, device=xs.device)
-        self._head_edge_arrays(heads, p, work)
-        outs = []
-        for wanted, t, shape in zip(want, (grad_xt, grad_xs, grad_att), ((i["m"], i["k"]), (i["n"], i["k"]), tuple(att.shape))):
-            if wanted and t is None:  # every element is written, except by a plan without entries, which launches nothing
-                t = (torch.empty if i["nnz"] else torch.zeros)(shape, dtype=torch.float32, device=xs.device)
-            if wanted:
-                assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape
-            outs.append(t if wanted else None)
-        if outs[2] is not None:
-            need = self.gatv2_attention_work_size()
-            if att_work is None:
-                att_work = torch.empty(max(need, 1), dtype=torch.float32, device=xs.device)
-            assert att_work.is_cuda and att_work.dtype == torch.float32 and att_work.is_contiguous() and att_work.numel() >= need
-        self.gatv2_attention_backward_ptr(heads, xt.data_ptr(), xs.data_ptr(), att.data_ptr(), p.data_ptr(), grad_out.data_ptr(), slope,
-                                          *(None if t is None else t.data_ptr() for t in outs), work.data_ptr(),
-                                          None if outs[2] is None else att_work.data_ptr(), torch.cuda.current_stream(xs.device).cuda_stream)
-        return tuple(outs)
-
-    def gatv2_attention_dropout_ptr(self, heads: int, dXt_ptr: int, dXs_ptr: int, dAtt_ptr: int, slope: float, p: float, seed: int, dOut_ptr: int,
-                                    dP_ptr: int | None = None, stream: int = 0):
-        """flex_dropout_gatv2_attention; the operands are gatv2_attention_ptr's; dP (optional) receives the UNDROPPED alpha."""
-        _check(_values_fn("flex_dropout_gatv2_attention")(self._h, heads, dXt_ptr, dXs_ptr, dAtt_ptr, slope, p, seed, dOut_ptr, dP_ptr, stream),
-               "flex_dropout_gatv2_attention")
-
-    def gatv2_attention_dropout(self, xt, xs, att, slope: float, p: float, seed: int, out=None, probs=None):
-        """flex_dropout_gatv2_attention: gatv2_attention() whose probabilities are dropped after the softmax with probability p in [0, 1),
-        the kept ones scaled by 1 / (1 - p); the mask is binding.dropout_mask(seed, p, e * H + h), a function of the 64-bit seed.  A
-        dropped entry stays in the softmax.  probs (optional, float32 [a.nnz, H]) receives the UNDROPPED alpha, which
-        gatv2_attention_dropout_backward() starts from."""
-        import torch
-        i = self.info()
-        heads = self._gatv2_operands(xt, xs, att)
-        if out is None:  # every row is written, except by a plan without entries, which launches nothing
-            out = (torch.empty if i["nnz"] else torch.zeros)((i["m"], i["k"]), dtype=torch.float32, device=xs.device)
-        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (i["m"], i["k"])
-        if probs is not None:
-            self._head_edge_arrays(heads, probs)
-        self.gatv2_attention_dropout_ptr(heads, xt.data_ptr(), xs.data_ptr(), att.data_ptr(), slope, p, int(seed) & 0xFFFFFFFFFFFFFFFF, out.data_ptr(),
-                                         None if probs is None else probs.data_ptr(), torch.cuda.current_stream(xs.device).cuda_stream)
-        return out
-
-    def gatv2_attention_dropout_backward_ptr(self, heads: int, dXt_ptr: int, dXs_ptr: int, dAtt_ptr: int, dP_ptr: int, dGradOut_ptr: int,
-                                             slope: float, p: float, seed: int, dGradXt_ptr: int | None, dGradXs_ptr: int | None,
-                                             dGradAtt_ptr: int | None, dWork_ptr: int, dAttWork_ptr: int | None = None, stream: int = 0):
-        """flex_dropout_gatv2_attention_backward; the operands are gatv2_attention_backward_ptr's, under the forward's p and seed."""
-        _check(_values_fn("flex_dropout_gatv2_attention_backward")(self._h, heads, dXt_ptr, dXs_ptr, dAtt_ptr, dP_ptr, dGradOut_ptr, slope, p, seed,
-                                                                   dGradXt_ptr, dGradXs_ptr, dGradAtt_ptr, dWork_ptr, dAttWork_ptr, stream),
-               "flex_dropout_gatv2_attention_backward")
-
-    def gatv2_attention_dropout_backward(self, xt, xs, att, probs, grad_out, slope: float, p: float, seed: int, grad_xt=None, grad_xs=None,
-                                         grad_att=None, work=None, want=(True, True, True), att_work=None):
-        """flex_dropout_gatv2_attention_backward: (gXt [m, k], gXs [n, k], gAtt [H, k / H]) of gatv2_attention_dropout()'s out from its
-        probs [a.nnz, H] (the undropped alpha), grad_out [m, k] and the same p and seed, in up to three launches; an output that `want`
-        does not ask for is None and is not computed.  work and att_work are gatv2_attention_backward()'s."""
-        import torch
-        i = self.info()
-        heads = self._gatv2_operands(xt, xs, att)
-        assert grad_out.is_cuda and grad_out.dtype == torch.float32 and grad_out.is_contiguous() and tuple(grad_out.shape) == (i["m"], i["k"])
-        if work is None:
-            work = torch.empty((self.src_nnz, heads), dtype=torch.float32, device=xs.device)
-        self._head_edge_arrays(heads, probs, work)
-        outs = []
-        for wanted, t, shape in zip(want, (grad_xt, grad_xs, grad_att), ((i["m"], i["k"]), (i["n"], i["k"]), tuple(att.shape))):
-            if wanted and t is None:  # every element is written, except by a plan without entries, which launches nothing
-                t = (torch.empty if i["nnz"] else torch.zeros)(shape, dtype=torch.float32, device=xs.device)
-            if wanted:
-                assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape
-            outs.append(t if wanted else None)
-        if outs[2] is not None:
-            need = self.gatv2_attention_work_size()
-            if att_work is None:
-                att_work = torch.empty(max(need, 1), dtype=torch.float32, device=xs.device)
-            assert att_work.is_cuda and att_work.dtype == torch.float32 and att_work.is_contiguous() and att_work.numel() >= need
-        self.gatv2_attention_dropout_backward_ptr(heads, xt.data_ptr(), xs.data_ptr(), att.data_ptr(), probs.data_ptr(), grad_out.data_ptr(), slope, p,
-                                                  int(seed) & 0xFFFFFFFFFFFFFFFF, *(None if t is None else t.data_ptr() for t in outs),
-                                                  work.data_ptr(), None if outs[2] is None else att_work.data_ptr(),
-                                                  torch.cuda.current_stream(xs.device).cuda_stream)
-        return tuple(outs)
+        return self._gat_backward(torch.float32, self.gat_attention_backward_ptr, el, er, V, p, grad_out, (slope,), (grad_el, grad_er, grad_v), work, want)
 
     def gat_attention_dropout_ptr(self, heads: int, dEl_ptr: int, dEr_ptr: int, dV_ptr: int, slope: float, p: float, seed: int, dOut_ptr: int,
                                   dP_ptr: int | None = None, stream: int = 0):
         """flex_gat_attention_dropout; dEl is rows x H floats, dEr n x H, dP (optional) nnz x H, entry-major: it receives the UNDROPPED
         alpha."""
-        _check(_values_fn("flex_gat_attention_dropout")(self._h, heads, dEl_ptr, dEr_ptr, dV_ptr, slope, p, seed, dOut_ptr, dP_ptr, stream),
-               "flex_gat_attention_dropout")
+        self._call("flex_gat_attention_dropout", heads, dEl_ptr, dEr_ptr, dV_ptr, slope, p, seed, dOut_ptr, dP_ptr, stream)
 
     def gat_attention_dropout(self, el, er, V, slope: float, p: float, seed: int, out=None, probs=None):
         """flex_gat_attention_dropout: gat_attention() whose probabilities are dropped after the softmax with probability p in [0, 1), the
         kept ones scaled by 1 / (1 - p); the mask is binding.dropout_mask(seed, p, e * H + h), a function of the 64-bit seed.  probs
         (optional, float32 [a.nnz, H]) receives the UNDROPPED alpha, which gat_attention_dropout_backward() starts from."""
         import torch
-        i = self.info()
-        heads = self._node_scalars(el, er)
-        assert V.is_cuda and V.dtype == torch.float32 and V.is_contiguous() and tuple(V.shape) == (i["n"], i["k"])
-        if out is None:  # every row is written, except by a plan without entries, which launches nothing
-            out = (torch.empty if i["nnz"] else torch.zeros)((i["m"], i["k"]), dtype=torch.float32, device=V.device)
-        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (i["m"], i["k"])
-        if probs is not None:
-            self._head_edge_arrays(heads, probs)
-        self.gat_attention_dropout_ptr(heads, el.data_ptr(), er.data_ptr(), V.data_ptr(), slope, p, int(seed) & 0xFFFFFFFFFFFFFFFF, out.data_ptr(),
-                                       None if probs is None else probs.data_ptr(), torch.cuda.current_stream(V.device).cuda_stream)
-        return out
+        return self._gat_forward(torch.float32, self.gat_attention_dropout_ptr, el, er, (), V, (slope, *_dropout(p, seed)), out, probs)
 
     def gat_attention_dropout_backward_ptr(self, heads: int, dEl_ptr: int, dEr_ptr: int, dV_ptr: int, dP_ptr: int, dGradOut_ptr: int, slope: float,
                                            p: float, seed: int, dGradEl_ptr: int | None, dGradEr_ptr: int | None, dGradV_ptr: int | None,
                                            dWork_ptr: int, stream: int = 0):
         """flex_gat_attention_dropout_backward; dP and dWork are nnz x H floats, entry-major."""
-        _check(_values_fn("flex_gat_attention_dropout_backward")(self._h, heads, dEl_ptr, dEr_ptr, dV_ptr, dP_ptr, dGradOut_ptr, slope, p, seed,
-                                                                 dGradEl_ptr, dGradEr_ptr, dGradV_ptr, dWork_ptr, stream),
-               "flex_gat_attention_dropout_backward")
+        self._call("flex_gat_attention_dropout_backward", heads, dEl_ptr, dEr_ptr, dV_ptr, dP_ptr, dGradOut_ptr, slope, p, seed, dGradEl_ptr,
+                   dGradEr_ptr, dGradV_ptr, dWork_ptr, stream)
 
     def gat_attention_dropout_backward(self, el, er, V, probs, grad_out, slope: float, p: float, seed: int, grad_el=None, grad_er=None,
                                        grad_v=None, work=None, want=(True, True, True)):
@@ -1259,144 +1104,80 @@ class Plan:
         for is None and is not computed.  work (optional): a float32 cuda tensor [a.nnz, H], not probs, that receives the gradient in
         el + er per entry whenever gEl or gEr is wanted."""
         import torch
-        i = self.info()
-        heads = self._node_scalars(el, er)
-        for t, rows in ((V, i["n"]), (grad_out, i["m"])):
-            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (rows, i["k"])
-        if work is None:
-            work = torch.empty((self.src_nnz, heads), dtype=torch.float32, device=V.device)
-        self._head_edge_arrays(heads, probs, work)
-        outs = []
-        for wanted, t, shape in zip(want, (grad_el, grad_er, grad_v), ((i["m"], heads), (i["n"], heads), (i["n"], i["k"]))):
-            if wanted and t is None:  # every row is written, except by a plan without entries, which launches nothing
-                t = (torch.empty if i["nnz"] else torch.zeros)(shape, dtype=torch.float32, device=V.device)
-            if wanted:
-                assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape
-            outs.append(t if wanted else None)
-        self.gat_attention_dropout_backward_ptr(heads, el.data_ptr(), er.data_ptr(), V.data_ptr(), probs.data_ptr(), grad_out.data_ptr(), slope, p,
-                                                int(seed) & 0xFFFFFFFFFFFFFFFF, *(None if t is None else t.data_ptr() for t in outs),
-                                                work.data_ptr(), torch.cuda.current_stream(V.device).cuda_stream)
-        return tuple(outs)
+        return self._gat_backward(torch.float32, self.gat_attention_dropout_backward_ptr, el, er, V, probs, grad_out, (slope, *_dropout(p, seed)),
+                                  (grad_el, grad_er, grad_v), work, want)
 
     def gat_attention_bf16_ptr(self, heads: int, dEl_ptr: int, dEr_ptr: int, dV_ptr: int, slope: float, dOut_ptr: int, dP_ptr: int | None = None,
                                stream: int = 0):
         """flex_gat_attention_bf16: gat_attention_ptr with bf16 rows V and Out; dEl, dEr and dP (optional) stay floats."""
-        _check(_values_fn("flex_gat_attention_bf16")(self._h, heads, dEl_ptr, dEr_ptr, dV_ptr, slope, dOut_ptr, dP_ptr, stream),
-               "flex_gat_attention_bf16")
+        self._call("flex_gat_attention_bf16", heads, dEl_ptr, dEr_ptr, dV_ptr, slope, dOut_ptr, dP_ptr, stream)
 
     def gat_attention_bf16_backward_ptr(self, heads: int, dEl_ptr: int, dEr_ptr: int, dV_ptr: int, dP_ptr: int, dGradOut_ptr: int, slope: float,
                                         dGradEl_ptr: int | None, dGradEr_ptr: int | None, dGradV_ptr: int | None, dWork_ptr: int, stream: int = 0):
         """flex_gat_attention_bf16_backward: gat_attention_backward_ptr with bf16 rows V, g and gV; the rest stays floats."""
-        _check(_values_fn("flex_gat_attention_bf16_backward")(self._h, heads, dEl_ptr, dEr_ptr, dV_ptr, dP_ptr, dGradOut_ptr, slope, dGradEl_ptr,
-                                                              dGradEr_ptr, dGradV_ptr, dWork_ptr, stream), "flex_gat_attention_bf16_backward")
+        self._call("flex_gat_attention_bf16_backward", heads, dEl_ptr, dEr_ptr, dV_ptr, dP_ptr, dGradOut_ptr, slope, dGradEl_ptr, dGradEr_ptr,
+                   dGradV_ptr, dWork_ptr, stream)
 
     def gat_attention_bf16_dropout_ptr(self, heads: int, dEl_ptr: int, dEr_ptr: int, dV_ptr: int, slope: float, p: float, seed: int, dOut_ptr: int,
                                        dP_ptr: int | None = None, stream: int = 0):
         """flex_gat_attention_bf16_dropout: gat_attention_dropout_ptr with bf16 rows V and Out."""
-        _check(_values_fn("flex_gat_attention_bf16_dropout")(self._h, heads, dEl_ptr, dEr_ptr, dV_ptr, slope, p, seed, dOut_ptr, dP_ptr, stream),
-               "flex_gat_attention_bf16_dropout")
+        self._call("flex_gat_attention_bf16_dropout", heads, dEl_ptr, dEr_ptr, dV_ptr, slope, p, seed, dOut_ptr, dP_ptr, stream)
 
     def gat_attention_bf16_dropout_backward_ptr(self, heads: int, dEl_ptr: int, dEr_ptr: int, dV_ptr: int, dP_ptr: int, dGradOut_ptr: int,
                                                 slope: float, p: float, seed: int, dGradEl_ptr: int | None, dGradEr_ptr: int | None,
                                                 dGradV_ptr: int | None, dWork_ptr: int, stream: int = 0):
         """flex_gat_attention_bf16_dropout_backward: gat_attention_dropout_backward_ptr with bf16 rows V, g and gV."""
-        _check(_values_fn("flex_gat_attention_bf16_dropout_backward")(self._h, heads, dEl_ptr, dEr_ptr, dV_ptr, dP_ptr, dGradOut_ptr, slope, p, seed,
-                                                                      dGradEl_ptr, dGradEr_ptr, dGradV_ptr, dWork_ptr, stream),
-               "flex_gat_attention_bf16_dropout_backward")
-
-    def _gat_bf16(self, run, el, er, V, args, out, p):
-        """The forward of the two bf16 GAT calls: run(heads, el, er, V, *args, out, p, stream) on bfloat16 V and out, float32 el, er, p."""
-        import torch
-        i = self.info()
-        heads = self._node_scalars(el, er)
-        assert V.is_cuda and V.dtype == torch.bfloat16 and V.is_contiguous() and tuple(V.shape) == (i["n"], i["k"]), "V: bfloat16 cuda [n, k]"
-        if out is None:  # every row is written, except by a plan without entries, which launches nothing
-            out = (torch.empty if i["nnz"] else torch.zeros)((i["m"], i["k"]), dtype=torch.bfloat16, device=V.device)
-        assert out.is_cuda and out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (i["m"], i["k"])
-        if p is not None:
-            self._head_edge_arrays(heads, p)
-        run(heads, el.data_ptr(), er.data_ptr(), V.data_ptr(), *args, out.data_ptr(), None if p is None else p.data_ptr(),
-            torch.cuda.current_stream(V.device).cuda_stream)
-        return out
-
-    def _gat_bf16_backward(self, run, el, er, V, p, grad_out, args, grads, work, want):
-        """The backward of the two bf16 GAT calls: V, grad_out and gV bfloat16; el, er, gEl, gEr, p and work float32."""
-        import torch
-        i = self.info()
-        heads = self._node_scalars(el, er)
-        for t, rows in ((V, i["n"]), (grad_out, i["m"])):
-            assert t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous() and tuple(t.shape) == (rows, i["k"]), "bfloat16 cuda [rows, k]"
-        if work is None:
-            work = torch.empty((self.src_nnz, heads), dtype=torch.float32, device=V.device)
-        self._head_edge_arrays(heads, p, work)
-        outs = []
-        shapes = (((i["m"], heads), torch.float32), ((i["n"], heads), torch.float32), ((i["n"], i["k"]), torch.bfloat16))
-        for wanted, t, (shape, dtype) in zip(want, grads, shapes):
-            if wanted and t is None:  # every row is written, except by a plan without entries, which launches nothing
-                t = (torch.empty if i["nnz"] else torch.zeros)(shape, dtype=dtype, device=V.device)
-            if wanted:
-                assert t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape
-            outs.append(t if wanted else None)
-        run(heads, el.data_ptr(), er.data_ptr(), V.data_ptr(), p.data_ptr(), grad_out.data_ptr(), *args,
-            *(None if t is None else t.data_ptr() for t in outs), work.data_ptr(), torch.cuda.current_stream(V.device).cuda_stream)
-        return tuple(outs)
+        self._call("flex_gat_attention_bf16_dropout_backward", heads, dEl_ptr, dEr_ptr, dV_ptr, dP_ptr, dGradOut_ptr, slope, p, seed, dGradEl_ptr,
+                   dGradEr_ptr, dGradV_ptr, dWork_ptr, stream)
 
     def gat_attention_bf16(self, el, er, V, slope: float = 0.2, out=None, p=None):
         """flex_gat_attention_bf16: gat_attention() on torch.bfloat16 V [n, k]; out [m, k] is bfloat16, every sum float32 and each element
         rounded once at its store.  el [m, H], er [n, H] and p (optional, [a.nnz, H]) are float32."""
-        return self._gat_bf16(self.gat_attention_bf16_ptr, el, er, V, (slope,), out, p)
+        import torch
+        return self._gat_forward(torch.bfloat16, self.gat_attention_bf16_ptr, el, er, (), V, (slope,), out, p)
 
     def gat_attention_bf16_backward(self, el, er, V, p, grad_out, slope: float = 0.2, grad_el=None, grad_er=None, grad_v=None, work=None,
                                     want=(True, True, True)):
         """flex_gat_attention_bf16_backward: gat_attention_backward() on torch.bfloat16 V and grad_out; gV is bfloat16, rounded once at its
         store; gEl, gEr, p and work are float32."""
-        return self._gat_bf16_backward(self.gat_attention_bf16_backward_ptr, el, er, V, p, grad_out, (slope,), (grad_el, grad_er, grad_v), work, want)
+        import torch
+        return self._gat_backward(torch.bfloat16, self.gat_attention_bf16_backward_ptr, el, er, V, p, grad_out, (slope,), (grad_el, grad_er, grad_v),
+                                  work, want)
 
     def gat_attention_bf16_dropout(self, el, er, V, slope: float, p: float, seed: int, out=None, probs=None):
         """flex_gat_attention_bf16_dropout: gat_attention_dropout() on torch.bfloat16 V; out is bfloat16; probs (optional, float32
         [a.nnz, H]) receives the UNDROPPED alpha."""
-        return self._gat_bf16(self.gat_attention_bf16_dropout_ptr, el, er, V, (slope, p, int(seed) & 0xFFFFFFFFFFFFFFFF), out, probs)
+        import torch
+        return self._gat_forward(torch.bfloat16, self.gat_attention_bf16_dropout_ptr, el, er, (), V, (slope, *_dropout(p, seed)), out, probs)
 
     def gat_attention_bf16_dropout_backward(self, el, er, V, probs, grad_out, slope: float, p: float, seed: int, grad_el=None, grad_er=None,
                                             grad_v=None, work=None, want=(True, True, True)):
         """flex_gat_attention_bf16_dropout_backward: gat_attention_dropout_backward() on torch.bfloat16 V and grad_out under the same p and
         seed; gV is bfloat16; gEl, gEr, probs and work are float32."""
-        return self._gat_bf16_backward(self.gat_attention_bf16_dropout_backward_ptr, el, er, V, probs, grad_out,
-                                       (slope, p, int(seed) & 0xFFFFFFFFFFFFFFFF), (grad_el, grad_er, grad_v), work, want)
+        import torch
+        return self._gat_backward(torch.bfloat16, self.gat_attention_bf16_dropout_backward_ptr, el, er, V, probs, grad_out,
+                                  (slope, *_dropout(p, seed)), (grad_el, grad_er, grad_v), work, want)
 
     def gat_edge_attention_ptr(self, heads: int, dEl_ptr: int, dEr_ptr: int, dEe_ptr: int, dV_ptr: int, slope: float, p: float, seed: int,
                                dOut_ptr: int, dP_ptr: int | None = None, stream: int = 0):
         """flex_edge_gat_attention; dEl is rows x H floats, dEr n x H, dEe and dP (optional) nnz x H, entry-major; dP receives the
         UNDROPPED alpha."""
-        _check(_values_fn("flex_edge_gat_attention")(self._h, heads, dEl_ptr, dEr_ptr, dEe_ptr, dV_ptr, slope, p, seed, dOut_ptr, dP_ptr, stream),
-               "flex_edge_gat_attention")
+        self._call("flex_edge_gat_attention", heads, dEl_ptr, dEr_ptr, dEe_ptr, dV_ptr, slope, p, seed, dOut_ptr, dP_ptr, stream)
 
     def gat_edge_attention(self, el, er, ee, V, slope: float, drop_p: float = 0.0, seed: int = 0, out=None, probs=None):
         """flex_edge_gat_attention: gat_attention() (drop_p = 0) or gat_attention_dropout() with a per-edge term inside the LeakyReLU, the
         score leaky_relu((el[row, h] + er[col, h]) + ee[e, h], slope).  ee: float32 cuda [a.nnz, H] in a's CSR order; -inf masks one
         entry for one head.  probs (optional, float32 [a.nnz, H]) receives the UNDROPPED alpha."""
         import torch
-        i = self.info()
-        heads = self._node_scalars(el, er)
-        self._head_edge_arrays(heads, ee)
-        assert V.is_cuda and V.dtype == torch.float32 and V.is_contiguous() and tuple(V.shape) == (i["n"], i["k"])
-        if out is None:  # every row is written, except by a plan without entries, which launches nothing
-            out = (torch.empty if i["nnz"] else torch.zeros)((i["m"], i["k"]), dtype=torch.float32, device=V.device)
-        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (i["m"], i["k"])
-        if probs is not None:
-            self._head_edge_arrays(heads, probs)
-        self.gat_edge_attention_ptr(heads, el.data_ptr(), er.data_ptr(), ee.data_ptr(), V.data_ptr(), slope, drop_p, int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                    out.data_ptr(), None if probs is None else probs.data_ptr(), torch.cuda.current_stream(V.device).cuda_stream)
-        return out
+        return self._gat_forward(torch.float32, self.gat_edge_attention_ptr, el, er, (ee,), V, (slope, *_dropout(drop_p, seed)), out, probs)
 
     def gat_edge_attention_backward_ptr(self, heads: int, dEl_ptr: int, dEr_ptr: int, dEe_ptr: int, dV_ptr: int, dP_ptr: int, dGradOut_ptr: int,
                                         slope: float, p: float, seed: int, dGradEl_ptr: int | None, dGradEr_ptr: int | None,
                                         dGradEe_ptr: int | None, dGradV_ptr: int | None, dWork_ptr: int | None, stream: int = 0):
         """flex_edge_gat_attention_backward; dEe, dP, dGradEe and dWork are nnz x H floats, entry-major; the work array is dGradEe where
         it is given, else dWork."""
-        _check(_values_fn("flex_edge_gat_attention_backward")(self._h, heads, dEl_ptr, dEr_ptr, dEe_ptr, dV_ptr, dP_ptr, dGradOut_ptr, slope, p, seed,
-                                                              dGradEl_ptr, dGradEr_ptr, dGradEe_ptr, dGradV_ptr, dWork_ptr, stream),
-               "flex_edge_gat_attention_backward")
+        self._call("flex_edge_gat_attention_backward", heads, dEl_ptr, dEr_ptr, dEe_ptr, dV_ptr, dP_ptr, dGradOut_ptr, slope, p, seed, dGradEl_ptr,
+                   dGradEr_ptr, dGradEe_ptr, dGradV_ptr, dWork_ptr, stream)
 
     def gat_edge_attention_backward(self, el, er, ee, V, probs, grad_out, slope: float, drop_p: float = 0.0, seed: int = 0,
                                     want=(True, True, True, True), grad_el=None, grad_er=None, grad_ee=None, grad_v=None, work=None):
@@ -1406,26 +1187,115 @@ class Plan:
         work (optional, float32 cuda [a.nnz, H], not probs) is the work array when gEe is not wanted; it is allocated here when needed."""
         import torch
         i = self.info()
-        heads = self._node_scalars(el, er)
-        for t, rows in ((V, i["n"]), (grad_out, i["m"])):
-            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (rows, i["k"])
+        heads = self._node_scalars(i, el, er)
+        _rows(torch.float32, i["k"], (V, i["n"]), (grad_out, i["m"]))
         self._head_edge_arrays(heads, ee, probs)
-        shapes = ((i["m"], heads), (i["n"], heads), (self.src_nnz, heads), (i["n"], i["k"]))
-        outs = []
-        for wanted, t, shape in zip(want, (grad_el, grad_er, grad_ee, grad_v), shapes):
-            if wanted and t is None:  # every row is written, except by a plan without entries, which launches nothing
-                t = (torch.empty if i["nnz"] else torch.zeros)(shape, dtype=torch.float32, device=V.device)
-            if wanted:
-                assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape
-            outs.append(t if wanted else None)
-        if outs[2] is None and work is None:
-            work = torch.empty((self.src_nnz, heads), dtype=torch.float32, device=V.device)
+        specs = [(shape, torch.float32) for shape in ((i["m"], heads), (i["n"], heads), (self.src_nnz, heads), (i["n"], i["k"]))]
+        outs = _wanted(want, (grad_el, grad_er, grad_ee, grad_v), specs, V.device, i["nnz"])
+        if outs[2] is None:
+            work = self._work(work, heads, V.device)
         if work is not None:
             self._head_edge_arrays(heads, work)
-        self.gat_edge_attention_backward_ptr(heads, el.data_ptr(), er.data_ptr(), ee.data_ptr(), V.data_ptr(), probs.data_ptr(), grad_out.data_ptr(),
-                                             slope, drop_p, int(seed) & 0xFFFFFFFFFFFFFFFF, *(None if t is None else t.data_ptr() for t in outs),
-                                             None if work is None else work.data_ptr(), torch.cuda.current_stream(V.device).cuda_stream)
+        self.gat_edge_attention_backward_ptr(heads, *map(_ptr, (el, er, ee, V, probs, grad_out)), slope, *_dropout(drop_p, seed), *map(_ptr, outs),
+                                             _ptr(work), _stream(V))
         return tuple(outs)
+
+    # ---- xt, xs, att: GATv2, dropout (float32 only)
+
+    def _gatv2_forward(self, run, xt, xs, att, scalars, out, p):
+        """The forward of the GATv2 calls: run(heads, xt, xs, att, *scalars, out, p, stream)."""
+        import torch
+        i = self.info()
+        heads = self._gatv2_operands(i, xt, xs, att)
+        out = _output(out, (i["m"], i["k"]), torch.float32, xs.device, i["nnz"])
+        if p is not None:
+            self._head_edge_arrays(heads, p)
+        run(heads, _ptr(xt), _ptr(xs), _ptr(att), *scalars, _ptr(out), _ptr(p), _stream(xs))
+        return out
+
+    def _gatv2_backward(self, run, xt, xs, att, p, grad_out, scalars, grads, work, want, att_work):
+        """The backward of the GATv2 calls: run(heads, xt, xs, att, p, grad_out, *scalars, gXt, gXs, gAtt, work, att_work, stream); att_work
+        is passed, and allocated where it is missing, only when gAtt is wanted."""
+        import torch
+        i = self.info()
+        heads = self._gatv2_operands(i, xt, xs, att)
+        _rows(torch.float32, i["k"], (grad_out, i["m"]))
+        work = self._work(work, heads, xs.device)
+        self._head_edge_arrays(heads, p, work)
+        specs = [(shape, torch.float32) for shape in ((i["m"], i["k"]), (i["n"], i["k"]), tuple(att.shape))]
+        outs = _wanted(want, grads, specs, xs.device, i["nnz"])
+        if outs[2] is None:
+            att_work = None
+        else:
+            need = self.gatv2_attention_work_size()
+            if att_work is None:
+                att_work = torch.empty(max(need, 1), dtype=torch.float32, device=xs.device)
+            assert att_work.is_cuda and att_work.dtype == torch.float32 and att_work.is_contiguous() and att_work.numel() >= need, \
+                "att_work: float32 cuda, gatv2_attention_work_size() floats"
+        run(heads, *map(_ptr, (xt, xs, att, p, grad_out)), *scalars, *map(_ptr, outs), _ptr(work), _ptr(att_work), _stream(xs))
+        return tuple(outs)
+
+    def gatv2_attention_ptr(self, heads: int, dXt_ptr: int, dXs_ptr: int, dAtt_ptr: int, slope: float, dOut_ptr: int, dP_ptr: int | None = None,
+                            stream: int = 0):
+        """flex_gatv2_attention; dXt is rows x k floats (stride ldc), dXs n x k (stride ldb), dAtt k, dP (optional) nnz x H, entry-major."""
+        self._call("flex_gatv2_attention", heads, dXt_ptr, dXs_ptr, dAtt_ptr, slope, dOut_ptr, dP_ptr, stream)
+
+    def gatv2_attention_backward_ptr(self, heads: int, dXt_ptr: int, dXs_ptr: int, dAtt_ptr: int, dP_ptr: int, dGradOut_ptr: int, slope: float,
+                                     dGradXt_ptr: int | None, dGradXs_ptr: int | None, dGradAtt_ptr: int | None, dWork_ptr: int,
+                                     dAttWork_ptr: int | None = None, stream: int = 0):
+        """flex_gatv2_attention_backward; dP and dWork are nnz x H floats, entry-major; dAttWork holds gatv2_attention_work_size() floats
+        and is needed where dGradAtt is wanted."""
+        self._call("flex_gatv2_attention_backward", heads, dXt_ptr, dXs_ptr, dAtt_ptr, dP_ptr, dGradOut_ptr, slope, dGradXt_ptr, dGradXs_ptr,
+                   dGradAtt_ptr, dWork_ptr, dAttWork_ptr, stream)
+
+    def gatv2_attention_work_size(self) -> int:
+        """flex_gatv2_attention_work_size: the floats of the dAttWork of gatv2_attention_backward_ptr (k per workgroup of its row launch)."""
+        n = C.c_uint64(0)
+        self._call("flex_gatv2_attention_work_size", C.byref(n))
+        return int(n.value)
+
+    def gatv2_attention(self, xt, xs, att, slope: float = 0.2, out=None, p=None):
+        """flex_gatv2_attention: out [m, k] = sum over each row's entries of alpha xs[col] per head, alpha = the softmax over the row of
+        <att[h], leaky_relu(xt[row, head h] + xs[col, head h], slope)>, in one launch.  xt: [m, k], xs: [n, k], att: [H, k / H]; float32
+        cuda tensors; xt may be xs.  p (optional): a float32 cuda tensor [a.nnz, H] that receives alpha in a's CSR order for the plan's
+        rows (entries of other shards keep what it held)."""
+        return self._gatv2_forward(self.gatv2_attention_ptr, xt, xs, att, (slope,), out, p)
+
+    def gatv2_attention_backward(self, xt, xs, att, p, grad_out, slope: float = 0.2, grad_xt=None, grad_xs=None, grad_att=None, work=None,
+                                 want=(True, True, True), att_work=None):
+        """flex_gatv2_attention_backward: (gXt [m, k], gXs [n, k], gAtt [H, k / H]) of gatv2_attention()'s out from its p [a.nnz, H] and
+        grad_out [m, k], in up to three launches; an output that `want` does not ask for is None and is not computed.  work (optional): a
+        float32 cuda tensor [a.nnz, H], not p, that receives dz = p (da - delta) per entry whenever a gradient is wanted.  att_work
+        (optional): float32 cuda, at least gatv2_attention_work_size() floats; it is allocated here when gAtt is wanted and it is not passed."""
+        return self._gatv2_backward(self.gatv2_attention_backward_ptr, xt, xs, att, p, grad_out, (slope,), (grad_xt, grad_xs, grad_att), work, want,
+                                    att_work)
+
+    def gatv2_attention_dropout_ptr(self, heads: int, dXt_ptr: int, dXs_ptr: int, dAtt_ptr: int, slope: float, p: float, seed: int, dOut_ptr: int,
+                                    dP_ptr: int | None = None, stream: int = 0):
+        """flex_dropout_gatv2_attention; the operands are gatv2_attention_ptr's; dP (optional) receives the UNDROPPED alpha."""
+        self._call("flex_dropout_gatv2_attention", heads, dXt_ptr, dXs_ptr, dAtt_ptr, slope, p, seed, dOut_ptr, dP_ptr, stream)
+
+    def gatv2_attention_dropout(self, xt, xs, att, slope: float, p: float, seed: int, out=None, probs=None):
+        """flex_dropout_gatv2_attention: gatv2_attention() whose probabilities are dropped after the softmax with probability p in [0, 1),
+        the kept ones scaled by 1 / (1 - p); the mask is binding.dropout_mask(seed, p, e * H + h), a function of the 64-bit seed.  A
+        dropped entry stays in the softmax.  probs (optional, float32 [a.nnz, H]) receives the UNDROPPED alpha, which
+        gatv2_attention_dropout_backward() starts from."""
+        return self._gatv2_forward(self.gatv2_attention_dropout_ptr, xt, xs, att, (slope, *_dropout(p, seed)), out, probs)
+
+    def gatv2_attention_dropout_backward_ptr(self, heads: int, dXt_ptr: int, dXs_ptr: int, dAtt_ptr: int, dP_ptr: int, dGradOut_ptr: int,
+                                             slope: float, p: float, seed: int, dGradXt_ptr: int | None, dGradXs_ptr: int | None,
+                                             dGradAtt_ptr: int | None, dWork_ptr: int, dAttWork_ptr: int | None = None, stream: int = 0):
+        """flex_dropout_gatv2_attention_backward; the operands are gatv2_attention_backward_ptr's, under the forward's p and seed."""
+        self._call("flex_dropout_gatv2_attention_backward", heads, dXt_ptr, dXs_ptr, dAtt_ptr, dP_ptr, dGradOut_ptr, slope, p, seed, dGradXt_ptr,
+                   dGradXs_ptr, dGradAtt_ptr, dWork_ptr, dAttWork_ptr, stream)
+
+    def gatv2_attention_dropout_backward(self, xt, xs, att, probs, grad_out, slope: float, p: float, seed: int, grad_xt=None, grad_xs=None,
+                                         grad_att=None, work=None, want=(True, True, True), att_work=None):
+        """flex_dropout_gatv2_attention_backward: (gXt [m, k], gXs [n, k], gAtt [H, k / H]) of gatv2_attention_dropout()'s out from its
+        probs [a.nnz, H] (the undropped alpha), grad_out [m, k] and the same p and seed, in up to three launches; an output that `want`
+        does not ask for is None and is not computed.  work and att_work are gatv2_attention_backward()'s."""
+        return self._gatv2_backward(self.gatv2_attention_dropout_backward_ptr, xt, xs, att, probs, grad_out, (slope, *_dropout(p, seed)),
+                                    (grad_xt, grad_xs, grad_att), work, want, att_work)
 
     def destroy(self):
         if getattr(self, "_h", None) and self._h.value:
