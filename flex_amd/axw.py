@@ -8,10 +8,12 @@ import os
 from . import binding
 
 FLEX_AXW_AUTO, FLEX_AXW_A_XW, FLEX_AXW_AX_W = 0, 1, 2
+FLEX_AXW_AX_W_FUSED = 3  # order of run / run_root / run_root_act on a handle made with fused=True: (A X) W in one launch, no intermediate
 FLEX_AXW_USE_BLAS = 0x10000  # flex_axw_create flag: rocBLAS for the dense half
 FLEX_AXW_BACKWARD = 0x20000  # flex_axw_create flag: plan A^T too, for flex_axw_backward
 FLEX_AXW_BF16 = 0x200000  # flex_axw_create flag: the bf16 layer (flex_axw_run_bf16; with FLEX_AXW_BACKWARD flex_axw_backward_bf16)
 FLEX_AXW_ROOT = 0x400000  # flex_axw_create flag, with FLEX_AXW_BF16: the buffers of flex_axw_run_root_bf16 (A X W + X R + b)
+FLEX_AXW_FUSED = 0x800000  # flex_axw_create flag, with FLEX_AXW_BF16: A's CSR and the row panels on the device, for order FLEX_AXW_AX_W_FUSED
 _lib = None
 
 
@@ -63,6 +65,8 @@ def lib():
         L.flex_axw_gemm_bf16_root_act_launch.restype = C.c_int
         L.flex_axw_act_grad_bf16_launch.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, vp]
         L.flex_axw_act_grad_bf16_launch.restype = C.c_int
+        L.flex_axw_fused_bf16_launch.argtypes = [vp] * 6 + [C.c_int, C.c_float, C.c_uint64, C.c_int, vp]
+        L.flex_axw_fused_bf16_launch.restype = C.c_int
         _lib = L
     return _lib
 
@@ -158,27 +162,41 @@ def _act_grad_bf16_launch(Out_ptr: int, dOut_ptr: int, dZ_ptr: int, n: int, c: i
     return lib().flex_axw_act_grad_bf16_launch(Out_ptr, dOut_ptr, dZ_ptr, n, c, cp, cs, stream)
 
 
+def _fused_bf16_launch(h: "Axw", X_ptr: int, W_ptr: int, R_ptr, bias_ptr, Out_ptr: int, relu: bool, drop_p: float, seed: int, n_workgroups: int,
+                       stream: int = 0) -> int:
+    """The one launch of order FLEX_AXW_AX_W_FUSED on its own (flex_axw_fused_bf16_launch), with the grid size as an argument: any
+    n_workgroups > 0 gives the same bits.  R_ptr None: the plain layer (bias None, relu False, drop_p 0); else the root forms.  Returns the
+    hipError_t; for tests."""
+    return lib().flex_axw_fused_bf16_launch(h._h, X_ptr, W_ptr, R_ptr, bias_ptr, Out_ptr, int(relu), drop_p, seed, n_workgroups, stream)
+
+
 class Axw:
     """flex_axw handle: plans A for both SpMM widths once; run() computes A @ X @ W in either order."""
 
     def __init__(self, a: binding.HostCsr, dim: int, c: int, device: int = 0, order: int = binding.FLEX_ORDER_CLUSTER,
-                 backward: bool = False, bf16: bool = False, root: bool = False):
+                 backward: bool = False, bf16: bool = False, root: bool = False, fused: bool = False):
         """backward: also plan A^T (FLEX_AXW_BACKWARD), for backward() and layer().  bf16: the bf16 layer (FLEX_AXW_BF16): run() and backward() take
         and return torch.bfloat16 (dim % 16 == 0, dim <= 4096, c <= 256, n >= 32; with backward=True dim % 32 == 0).  dim > 256 runs the
         wide kernels (axw_bf16_wide_kernels.hip); a width that is no multiple of 16 (602, 1433) is served exactly by zero columns of X and
-        zero rows of W.  root (with bf16=True only): the buffers of run_root() (FLEX_AXW_ROOT)."""
+        zero rows of W.  root (with bf16=True only): the buffers of run_root() (FLEX_AXW_ROOT).  fused (with bf16=True only, dim <= 256): the
+        handle also keeps A's CSR and its 32-row panels on the device (FLEX_AXW_FUSED), and run(), run_root(), run_root_act(), layer() and
+        root_layer() take order=FLEX_AXW_AX_W_FUSED: order (A X) W as ONE kernel launch with no n x dim intermediate
+        (axw_bf16_fused_kernels.hip), within the same bounds as FLEX_AXW_AX_W but not its bits; AUTO never picks it."""
         self._h = C.c_void_p()
         v = a.view()
-        flags = order | (FLEX_AXW_BACKWARD if backward else 0) | (FLEX_AXW_BF16 if bf16 else 0) | (FLEX_AXW_ROOT if root else 0)
+        flags = order | (FLEX_AXW_BACKWARD if backward else 0) | (FLEX_AXW_BF16 if bf16 else 0) | (FLEX_AXW_ROOT if root else 0) | (
+            FLEX_AXW_FUSED if fused else 0)
         binding._check(lib().flex_axw_create(C.byref(self._h), C.byref(v), dim, c, device, flags), "flex_axw_create")
         self.n, self.dim, self.c, self.ld = a.n, dim, c, (lib().flex_axw_ld_bf16(c) if bf16 else lib().flex_axw_ld(c))
         self.has_backward = backward
         self.bf16 = bf16
         self.has_root = root
+        self.has_fused = fused
 
     def run(self, X, W, order: int = FLEX_AXW_AUTO, timed: bool = False):
         """X [n, dim], W [dim, c]: contiguous cuda tensors, float32 -- torch.bfloat16 on a bf16 handle (any other dtype: TypeError).
-        Returns Out [n, ld] of that dtype (columns >= c are zero) and, if timed, (gemm_ms, spmm_ms)."""
+        Returns Out [n, ld] of that dtype (columns >= c are zero) and, if timed, (gemm_ms, spmm_ms).  order=FLEX_AXW_AX_W_FUSED (a fused=True
+        handle): one launch, reported as spmm_ms with gemm_ms 0."""
         import torch
         want = torch.bfloat16 if self.bf16 else torch.float32
         if X.dtype != want or W.dtype != want:
@@ -195,7 +213,8 @@ class Axw:
     def run_root(self, X, W, R, bias=None, order: int = FLEX_AXW_AUTO, timed: bool = False):
         """flex_axw_run_root_bf16: A @ X @ W + X @ R + bias with one rounding after the last sum.  X [n, dim], W and R [dim, c]: contiguous
         cuda torch.bfloat16; bias: float32 [c] or None (anything else: TypeError).  Returns Out [n, ld] in bfloat16 (columns >= c are zero)
-        and, if timed, (gemm_ms, spmm_ms).  No autograd: root_layer() is the differentiable form."""
+        and, if timed, (gemm_ms, spmm_ms).  order=FLEX_AXW_AX_W_FUSED (a fused=True handle): the whole layer in one launch; FlexError
+        (FLEX_ERR_UNSUPPORTED) where [W; R] does not fit in LDS (dim = 256, c > 128).  No autograd: root_layer() is the differentiable form."""
         import torch
         if not self.has_root:
             raise binding.FlexError("Axw.run_root: the handle was made without root=True (FLEX_AXW_ROOT)")

@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <initializer_list>
 #include <new>
+#include <vector>
 
 #include "../../include/flex_axw.h"
 #include "device_scope.h"
@@ -49,6 +50,12 @@ extern "C" hipError_t flex_axw_gemm_bf16_root_act_launch(const flex_bf16 *L1, co
                                                          int cp, int n_cus, float drop_p, uint64_t seed, hipStream_t s);  // axw_bf16_act_kernels.hip
 extern "C" hipError_t flex_axw_act_grad_bf16_launch(const flex_bf16 *Out, const flex_bf16 *dOut, flex_bf16 *dZ, int n, int c, int cp, float cs,
                                                     hipStream_t s);
+namespace flex_axw_bf16 {  // axw_bf16_fused_kernels.hip: order FLEX_AXW_AX_W_FUSED
+int fused_tiles(int dim, int cp, bool root);
+hipError_t fused_launch(const uint32_t *rowPtr, const uint32_t *col, const float *vals, const int32_t *panel_rows, const uint64_t *cost_prefix,
+                        int n_panels, const flex_bf16 *X, const flex_bf16 *W, const flex_bf16 *R, const float *bias, flex_bf16 *Out, int dim, int c,
+                        int cp, int relu, float drop_p, uint64_t seed, int n_workgroups, hipStream_t s);
+}  // namespace flex_axw_bf16
 
 struct flex_axw {
     int32_t n = 0;
@@ -71,6 +78,12 @@ struct flex_axw {
     // FLEX_AXW_ROOT only (flex_bf16)
     float *d_s = nullptr;   // n x cp: A (X W) in order A_XW, the addend of the root kernel
     float *d_wf = nullptr;  // 2 dim x cp: [W; R] as MFMA fragments (axw_bf16_root_kernels.hip)
+    // FLEX_AXW_FUSED only: A's CSR on the device and the panels of order FLEX_AXW_AX_W_FUSED (axw_bf16_fused_kernels.hip)
+    uint32_t *d_row_ptr = nullptr, *d_col = nullptr;
+    float *d_vals = nullptr;
+    int32_t *d_panel_rows = nullptr;    // [n_panels][32] row ids in the handle's row order, the last panel filled with its last row
+    uint64_t *d_cost_prefix = nullptr;  // [n_panels + 1]: nonzeros + kFusedRowCost a row, summed over the panels before
+    int n_panels = 0;
     float *d_part = nullptr;      // dW partial sums: flex_axw_dw_slices(n, n_cus) x dim x c floats (bf16: flex_axw_dw_bf16_slices, wide: flex_axw_dw_bf16_wide_slices)
 };
 
@@ -152,11 +165,80 @@ struct RootAct {
 };
 bool drop_p_ok(float p) { return std::isfinite(p) && p >= 0.f && p < 1.f; }
 
+// What a row costs the fused kernel beside its nonzeros, in nonzeros: its share of the panel's MFMA chain and store, and the X row of the
+// root forms.  It also makes the prefix strictly ascending, so that the kernel's cuts tile the panel list.
+constexpr uint64_t kFusedRowCost = 8;
+
+// FLEX_AXW_FUSED: A's CSR, panel_rows and panel_cost_prefix on the device.  The panels take the rows in the rank of the handle's row order.
+int build_fused(flex_axw *h, const flex_csr *A, unsigned order) {
+    const int64_t n = A->n;
+    for (int64_t e = 0; e < A->nnz; ++e)
+        if (A->col[e] >= static_cast<uint32_t>(n)) return FLEX_ERR_INVALID;
+    std::vector<uint32_t> rank(static_cast<size_t>(n));
+    int rc = FLEX_OK;
+    if (order == FLEX_ORDER_RCM) rc = flex_order_rcm(A, rank.data());
+    else if (order == FLEX_ORDER_CLUSTER) rc = flex_order_cluster(A, rank.data());
+    else if (order == FLEX_ORDER_GORDER) rc = flex_order_gorder(A, 3, rank.data());
+    else
+        for (int64_t i = 0; i < n; ++i) rank[i] = static_cast<uint32_t>(i);
+    if (rc) return rc;
+    h->n_panels = static_cast<int>((n + 31) / 32);
+    std::vector<int32_t> rows(static_cast<size_t>(h->n_panels) * 32, -1);
+    for (int64_t i = 0; i < n; ++i) {
+        if (rank[i] >= static_cast<uint32_t>(n) || rows[rank[i]] >= 0) return FLEX_ERR_INVALID;  // not a permutation
+        rows[rank[i]] = static_cast<int32_t>(i);
+    }
+    for (size_t i = static_cast<size_t>(n); i < rows.size(); ++i) rows[i] = rows[n - 1];
+    std::vector<uint64_t> prefix(static_cast<size_t>(h->n_panels) + 1, 0);
+    for (int p = 0; p < h->n_panels; ++p) {
+        uint64_t cost = 0;
+        for (int j = 0; j < 32; ++j) cost += A->rowPtr[rows[32 * p + j] + 1] - A->rowPtr[rows[32 * p + j]] + kFusedRowCost;
+        prefix[p + 1] = prefix[p] + cost;
+    }
+    auto upload = [&](auto **dst, const auto *src, size_t count) {
+        const size_t bytes = std::max<size_t>(count, 1) * sizeof(*src);
+        int e = hip_fail(hipMalloc(reinterpret_cast<void **>(dst), bytes));
+        if (!e && count) e = hip_fail(hipMemcpy(*dst, src, count * sizeof(*src), hipMemcpyHostToDevice));
+        return e;
+    };
+    rc = upload(&h->d_row_ptr, A->rowPtr, static_cast<size_t>(n) + 1);
+    if (!rc) rc = upload(&h->d_col, A->col, static_cast<size_t>(A->nnz));
+    if (!rc) rc = upload(&h->d_vals, A->vals, static_cast<size_t>(A->nnz));
+    if (!rc) rc = upload(&h->d_panel_rows, rows.data(), rows.size());
+    if (!rc) rc = upload(&h->d_cost_prefix, prefix.data(), prefix.size());
+    return rc;
+}
+
+// The launch of order FLEX_AXW_AX_W_FUSED, timed as one SpMM stage: the three run calls' whole body in that order
+int run_fused(flex_axw *h, const flex_bf16 *dX, const flex_bf16 *dW, const flex_bf16 *dR, const float *dBias, flex_bf16 *dOut, const RootAct *act,
+              flex_stream_t stream, float *gemm_ms, float *spmm_ms) {
+    if (!flex_axw_bf16::fused_tiles(h->dim, h->cp, dR != nullptr)) return FLEX_ERR_UNSUPPORTED;  // [W; R] and one tile do not fit in LDS
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const flex::DeviceScope on(h->device);
+    int rc = hip_fail(on.error());
+    const Marks mark{h, s, gemm_ms || spmm_ms};
+    if (!rc) rc = mark(0);
+    if (!rc)
+        rc = hip_fail(flex_axw_bf16::fused_launch(h->d_row_ptr, h->d_col, h->d_vals, h->d_panel_rows, h->d_cost_prefix, h->n_panels, dX, dW, dR, dBias,
+                                                  dOut, h->dim, h->c, h->cp, act != nullptr, act ? act->drop_p : 0.f, act ? act->seed : 0,
+                                                  std::min(h->n_cus, h->n_panels), s));
+    if (!rc) rc = mark(1);
+    float ms[1] = {0.f};
+    if (!rc) rc = mark.read(1, ms);
+    if (!rc && mark.timed) {
+        if (gemm_ms) *gemm_ms = 0.f;
+        if (spmm_ms) *spmm_ms = ms[0];
+    }
+    return rc;
+}
+
 // The two root forwards: the stages of either order, the last of them the root kernel or, with `act`, its ReLU-and-dropout form.
 int run_root(flex_axw *h, int order, const flex_bf16 *dX, const flex_bf16 *dW, const flex_bf16 *dR, const float *dBias, flex_bf16 *dOut,
              const RootAct *act, flex_stream_t stream, float *gemm_ms, float *spmm_ms) {
-    if (!h || !h->d_wf || !dX || !dW || !dR || !dOut || order < FLEX_AXW_AUTO || order > FLEX_AXW_AX_W) return FLEX_ERR_INVALID;
+    if (!h || !h->d_wf || !dX || !dW || !dR || !dOut || order < FLEX_AXW_AUTO || order > (h->d_panel_rows ? FLEX_AXW_AX_W_FUSED : FLEX_AXW_AX_W))
+        return FLEX_ERR_INVALID;
     if (misaligned16({dX, dOut})) return FLEX_ERR_UNSUPPORTED;
+    if (order == FLEX_AXW_AX_W_FUSED) return run_fused(h, dX, dW, dR, dBias, dOut, act, stream, gemm_ms, spmm_ms);
     if (order == FLEX_AXW_AUTO) order = h->cp <= h->dim ? FLEX_AXW_A_XW : FLEX_AXW_AX_W;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     flex_bf16 *xw = reinterpret_cast<flex_bf16 *>(h->d_xw), *ax = reinterpret_cast<flex_bf16 *>(h->d_ax);
@@ -240,6 +322,11 @@ int flex_axw_destroy(flex_axw *h) {
     (void)hipFree(h->d_g);
     (void)hipFree(h->d_wt);
     (void)hipFree(h->d_part);
+    (void)hipFree(h->d_row_ptr);
+    (void)hipFree(h->d_col);
+    (void)hipFree(h->d_vals);
+    (void)hipFree(h->d_panel_rows);
+    (void)hipFree(h->d_cost_prefix);
     (void)hipFree(h->d_s);
     (void)hipFree(h->d_wf);
     (void)hipFree(h->d_xw);
@@ -264,6 +351,8 @@ int flex_axw_create(flex_axw **out, const flex_csr *A, int dim, int c, int devic
     if (bf16 && (flags & FLEX_AXW_BACKWARD) && dim % 32 != 0) return FLEX_ERR_UNSUPPORTED;
     const bool root = (flags & FLEX_AXW_ROOT) != 0;
     if (root && !bf16) return FLEX_ERR_UNSUPPORTED;  // the root term is the bf16 layer's
+    const bool fused = (flags & FLEX_AXW_FUSED) != 0;
+    if (fused && (!bf16 || dim > 256)) return FLEX_ERR_UNSUPPORTED;  // the fused order keeps the whole W in LDS
     flex_axw *h = new (std::nothrow) flex_axw();
     if (!h) return FLEX_ERR_NOMEM;
     h->n = A->n;
@@ -277,7 +366,7 @@ int flex_axw_create(flex_axw **out, const flex_csr *A, int dim, int c, int devic
     int rc = hip_fail(on.error());
     const bool want_blas = (flags & FLEX_AXW_USE_BLAS) != 0;
     const bool backward = (flags & FLEX_AXW_BACKWARD) != 0;
-    flags &= ~(FLEX_AXW_USE_BLAS | FLEX_AXW_BACKWARD | FLEX_AXW_BF16 | FLEX_AXW_ROOT);
+    flags &= ~(FLEX_AXW_USE_BLAS | FLEX_AXW_BACKWARD | FLEX_AXW_BF16 | FLEX_AXW_ROOT | FLEX_AXW_FUSED);
     if (bf16) flags |= FLEX_PLAN_BF16;
     const size_t es = bf16 ? sizeof(flex_bf16) : sizeof(float);  // element size of the intermediates and of Wp
     if (!rc) rc = flex_plan_create(&h->plan_c, A, h->cp, device, flags);
@@ -327,6 +416,7 @@ int flex_axw_create(flex_axw **out, const flex_csr *A, int dim, int c, int devic
         if (!rc) rc = hip_fail(hipMemset(h->d_wt, 0, wt * sizeof(float)));
         if (!rc) rc = hip_fail(hipMalloc(reinterpret_cast<void **>(&h->d_part), part * sizeof(float)));
     }
+    if (!rc && fused) rc = build_fused(h, A, flags & FLEX_ORDER_MASK);
     if (rc) {
         flex_axw_destroy(h);
         return rc;
@@ -373,8 +463,10 @@ int flex_axw_run(flex_axw *h, int order, const float *dX, const float *dW, float
 // axw_bf16_wide_kernels.hip (create refused every shape they do not take), the intermediate rounded to bf16 by the stage that writes it.
 int flex_axw_run_bf16(flex_axw *h, int order, const flex_bf16 *dX, const flex_bf16 *dW, flex_bf16 *dOut, flex_stream_t stream,
                       float *gemm_ms, float *spmm_ms) {
-    if (!h || !h->bf16 || !dX || !dW || !dOut || order < FLEX_AXW_AUTO || order > FLEX_AXW_AX_W) return FLEX_ERR_INVALID;
+    if (!h || !h->bf16 || !dX || !dW || !dOut || order < FLEX_AXW_AUTO || order > (h->d_panel_rows ? FLEX_AXW_AX_W_FUSED : FLEX_AXW_AX_W))
+        return FLEX_ERR_INVALID;
     if (misaligned16({dX, dOut})) return FLEX_ERR_UNSUPPORTED;
+    if (order == FLEX_AXW_AX_W_FUSED) return run_fused(h, dX, dW, nullptr, nullptr, dOut, nullptr, stream, gemm_ms, spmm_ms);
     if (order == FLEX_AXW_AUTO) order = h->cp <= h->dim ? FLEX_AXW_A_XW : FLEX_AXW_AX_W;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     flex_bf16 *xw = reinterpret_cast<flex_bf16 *>(h->d_xw), *ax = reinterpret_cast<flex_bf16 *>(h->d_ax);
@@ -507,6 +599,18 @@ int flex_axw_backward_root_act_bf16(flex_axw *h, const flex_bf16 *dX, const flex
         rc = hip_fail(flex_axw_act_grad_bf16_launch(dFwdOut, dOut, dWork, h->n, h->c, h->cp, 1.0f / (1.0f - drop_p),
                                                     reinterpret_cast<hipStream_t>(stream)));
     return rc ? rc : backward_root(h, dX, dW, dR, dWork, dGradX, dGradW, dGradR, dGradBias, stream);
+}
+
+// The launcher of order FLEX_AXW_AX_W_FUSED with the grid size as an argument (the run calls pass min(CUs, panels)); for tests, not part of
+// flex_axw.h.  R == NULL: the plain layer (bias, relu and drop_p must then be NULL, 0 and 0); else the root forms.  hipErrorInvalidValue
+// for n_workgroups <= 0, a misaligned X or Out, a handle made without FLEX_AXW_FUSED and a shape whose fragments do not fit in LDS.
+hipError_t flex_axw_fused_bf16_launch(flex_axw *h, const flex_bf16 *X, const flex_bf16 *W, const flex_bf16 *R, const float *bias, flex_bf16 *Out,
+                                      int relu, float drop_p, uint64_t seed, int n_workgroups, hipStream_t stream) {
+    if (!h || !h->d_panel_rows) return hipErrorInvalidValue;
+    const flex::DeviceScope on(h->device);
+    if (on.error() != hipSuccess) return on.error();
+    return flex_axw_bf16::fused_launch(h->d_row_ptr, h->d_col, h->d_vals, h->d_panel_rows, h->d_cost_prefix, h->n_panels, X, W, R, bias, Out, h->dim,
+                                       h->c, h->cp, relu, drop_p, seed, n_workgroups, stream);
 }
 
 }  // extern "C"

@@ -39,6 +39,32 @@ typedef struct flex_axw flex_axw;
                                    2 dim x flex_axw_ld_bf16(c) elements for [W; R] as MFMA fragments; every other call behaves as on a handle
                                    made without it */
 
+#define FLEX_AXW_FUSED 0x800000u /* flex_axw_create flag, with FLEX_AXW_BF16 only (FLEX_ERR_UNSUPPORTED without it, and for dim > 256): the handle
+                                    also runs order FLEX_AXW_AX_W_FUSED of flex_axw_run_bf16, flex_axw_run_root_bf16 and
+                                    flex_axw_run_root_act_bf16.  It only adds arrays -- A's CSR (rowPtr, col, vals) on the device, the 32-row
+                                    panels of the handle's row order and the prefix sum of their cost; every other call and order behaves as
+                                    on a handle made without it */
+#define FLEX_AXW_AX_W_FUSED 3 /* an `order` of the three bf16 run calls, on a handle made with FLEX_AXW_FUSED (FLEX_ERR_INVALID on any other,
+                                 like every out-of-range order): order FLEX_AXW_AX_W in ONE launch with no intermediate in memory
+                                 (axw_bf16_fused_kernels.hip).  FLEX_AXW_AUTO never selects it.
+                                     Out = rn_bf16( rn_bf16(A X) W )                     flex_axw_run_bf16
+                                     Out = rn_bf16( act( b + rn_bf16(A X) W + X R ) )    the root calls; act: identity, or ReLU and dropout as
+                                                                                         flex_axw_run_root_act_bf16 defines them (same mask)
+                                 The roundings are FLEX_AXW_AX_W's: A X is summed in fp32 -- every entry ONE fmaf chain from +0 over its row's
+                                 nonzeros in CSR order; a row of more than 512 nonzeros is cut into 8 ascending slices, one chain each, added in
+                                 slice order -- and rounded once to bf16; the dense chain is fp32 from b (or +0), ascending k-steps of 16
+                                 (v_mfma_f32_32x32x16_bf16), all of T W before all of X R, rounded once.  No atomics: the same inputs give the
+                                 same bits on every call and replay.  Bit equality with FLEX_AXW_AX_W is NOT promised (flex_spmm_bf16 sums a
+                                 row in another order); the accuracy statements of FLEX_AXW_AX_W hold unchanged, since their n_r = nnz(row) +
+                                 32 covers any order of the row sum with one rounding per addition, the 8 slice additions included.  NaN /
+                                 +inf / -inf and the +0 padding as for FLEX_AXW_AX_W, for a non-finite A too (the store masks the padding).
+                                 Shapes: dim <= 256, c <= 256.  W (and R) live in LDS as dim (2 dim) x flex_axw_ld_bf16(c) elements beside
+                                 tiles x 32 x (2 dim + 16) bytes of A X, 32 dim bytes of long-row partial sums and, in the root calls,
+                                 4 flex_axw_ld_bf16(c) bytes of bias: two tiles (the gather of one panel overlaps the product of the one
+                                 before) where that is within 160 KiB, else one; a root call that does not fit with one tile (dim = 256,
+                                 c > 128) returns FLEX_ERR_UNSUPPORTED, nothing written or enqueued.  A timed call reports the launch as
+                                 *spmm_ms and *gemm_ms = 0.  The call is one kernel launch: no allocation, no upload, capturable. */
+
 /* Leading dimension of Out and of the X*W intermediate: c rounded up to a multiple of 32 floats, so
  * that every row is a whole number of 128-byte cache lines (a row that starts mid-line costs each
  * gather one extra line: k=100 runs 50 % slower than k=128 on the reddit shape); the extra columns

@@ -25,7 +25,11 @@
     probe_axw.py --bf16-root-act the hidden layer dropout(relu(A X W + X R + b)): run_root, torch.relu and F.dropout(p = 0.5), and the backward
                                  of root_layer through those torch ops, against flex_axw_run_root_act_bf16 and flex_axw_backward_root_act_bf16
                                  at p = 0 and p = 0.5, alternated in this process on flickr (128, 128) and reddit (128, 128), (608, 128): medians of
-                                 event times of the whole calls."""
+                                 event times of the whole calls.
+    probe_axw.py --bf16-fused    order FLEX_AXW_AX_W_FUSED (one launch, no n x dim intermediate) against orders FLEX_AXW_AX_W and FLEX_AXW_AUTO
+                                 of the same handle, for run and run_root_act (p = 0.5), alternated in this process on pubmed.csv (128, 64),
+                                 flickr (128, 128), reddit (128, 128) and flickr (256, 256): medians of event times of the whole calls, and
+                                 the bytes each path moves at the least, computed from the shapes."""
 import os
 import sys
 
@@ -298,6 +302,53 @@ def root_act_table(shapes=ROOT_ACT):
                   f"{m['b']:.1f} | {m['b0']:.1f} | {m['b5']:.1f} | {m['b0'] / m['b']:.2f} | {m['b5'] / m['b']:.2f} |", flush=True)
             h.destroy()
 
+
+FUSED = (("pubmed", 128, 64), ("flickr", 128, 128), ("reddit", 128, 128), ("flickr", 256, 256))
+
+
+def fused_table(shapes=FUSED):
+    def whole(f):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        f()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e3
+
+    print("| graph | dim | c | call | (AX)W us | AUTO us | fused us | fused / (AX)W | fused / AUTO | (AX)W MB | fused MB |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|")
+    for name, dim, c in shapes:
+        a = (flex_amd.csv_load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "pubmed.csv"))
+             if name == "pubmed" else flex_amd.synth_graph(name))
+        root = 2 * dim * flex_amd.axw.lib().flex_axw_ld_bf16(c) * 2 <= 128 * 1024  # [W; R] fits beside a tile
+        h = axw.Axw(a, dim, c, bf16=True, root=root, fused=True)
+        X = (torch.rand((a.n, dim), device="cuda") * 2 - 1).bfloat16()
+        W, R = ((torch.rand((dim, c), device="cuda") - 0.5).bfloat16() for _ in range(2))
+        bias = torch.rand(c, device="cuda") - 0.5
+        nnz = int(a.rowPtr[-1])
+        # at the least: every nonzero's X row, column and value once, Out once; the unfused order writes and reads T = A X as well;
+        # the root forms read X once more
+        least = nnz * (2 * dim + 8) + a.n * h.ld * 2
+        calls = {"run": (lambda o: h.run(X, W, o), 0)}
+        if root:
+            calls["run_root_act p=0.5"] = (lambda o: h.run_root_act(X, W, R, bias, 0.5, 7, o), a.n * dim * 2)
+        for what, (f, extra) in calls.items():
+            orders = (axw.FLEX_AXW_AX_W, axw.FLEX_AXW_AUTO, axw.FLEX_AXW_AX_W_FUSED)
+            t = {o: [] for o in orders}
+            for i in range(REPS + 5):  # alternated; the first five of each are warm-up
+                for o in orders:
+                    us = whole(lambda: f(o))
+                    if i >= 5:
+                        t[o].append(us)
+            m = [float(np.median(t[o])) for o in orders]
+            print(f"| {name} | {dim} | {c} | {what} | {m[0]:.1f} | {m[1]:.1f} | {m[2]:.1f} | {m[2] / m[0]:.2f} | {m[2] / m[1]:.2f} | "
+                  f"{(least + extra + 2 * a.n * dim * 2) / 1e6:.1f} | {(least + extra) / 1e6:.1f} |", flush=True)
+        h.destroy()
+
+
+if "--bf16-fused" in sys.argv[1:]:
+    fused_table()
+    sys.exit(0)
 
 if "--bf16-root-act" in sys.argv[1:]:
     root_act_table()
